@@ -22,6 +22,7 @@ and `pq_train_sharded` are BASELINE configs[4].  A single graph does not shard (
 One JSON line on rank 0; extra objects: `roofline` (dominant kernel of the timed region, HIP events from inside
 the library), `adc_scan` (configs[3]: 10M x 96 B codes, HBM roofline), `rabitq_scan` (configs[4] on one GPU),
 `sq8_scan`, `int4_scan`, `flat_small_batch`, `hnsw_layer0` (configs[2]), `flat_ivf_probe`, `cpu_baseline`.
+`--dump-outputs DIR` also writes the ids and scores of the last timed step (dump_outputs).
 """
 from __future__ import annotations
 
@@ -1597,6 +1598,21 @@ def emit(full: dict):
 
 
 _REAL_STDOUT_FD = None
+DUMP_LIMIT = 64 << 20   # bytes written by --dump-outputs, all arrays together
+
+
+def dump_outputs(dirname: str, ids: torch.Tensor, scores: torch.Tensor):
+    """--dump-outputs: what the timed path returned in its last timed step, the whole [Q_BATCH, K] batch, so that two
+    builds run with the same arguments (same seeded rows and queries) can be compared output for output.  ids are the
+    uint32 row ids (0xFFFFFFFF = no row), stored as float64, which holds every one of them exactly."""
+    arrays = {"ids": ids.cpu().numpy().view(np.uint32).astype(np.float64),
+              "scores": scores.cpu().numpy().astype(np.float32)}
+    assert sum(a.nbytes for a in arrays.values()) <= DUMP_LIMIT
+    d = Path(dirname)
+    d.mkdir(parents=True, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(d / f"{name}.npy", a)
+    print(f"bench.py: last timed step's outputs -> {d}/{{{','.join(arrays)}}}.npy", file=sys.stderr, flush=True)
 
 
 def guard_stdout():
@@ -1649,7 +1665,12 @@ def main():
                          "BASELINE's configs[1] names; the filtered path is reported as `flat_exact_bf16_filter` either way)")
     ap.add_argument("--backend", default="nccl",
                     help="torch.distributed backend; 'gloo' lets several ranks share one GPU to smoke-test the N>1 path")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the timed path returned in its last timed step to DIR/ids.npy (float64: the uint32 row ids, "
+                         "0xFFFFFFFF = no row) and DIR/scores.npy (float32), [queries_per_step, k] each")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args))
@@ -1707,8 +1728,8 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    def flat_step(i):
-        return index.search(queries[i % n_batches], K, stream=stream)[0]
+    def flat_step(i):   # a step returns what the caller of its path receives: (ids, scores)
+        return index.search(queries[i % n_batches], K, stream=stream)
 
     # ---- which pipeline reaches recall@10 >= 0.95 fastest?  (N = 1: measured; N > 1: the exact path, sharded)
     hp = hnsw128 = hidx = hpq = None
@@ -1733,11 +1754,11 @@ def main():
 
     if op["path"] == "hnsw_f32":
         def step(i):
-            return hidx.search_hnsw(queries[i % n_batches], K, op["ef"], stream=stream)[0]
+            return hidx.search_hnsw(queries[i % n_batches], K, op["ef"], stream=stream)
     elif op["path"] == "hnsw_pq_rerank":
         def step(i):
             cand, _ = hidx.search_hnsw_pq(queries[i % n_batches], op["ef"], op["ef"], stream=stream)
-            return hidx.rerank(queries[i % n_batches], cand, K, stream=stream)[0]
+            return hidx.rerank(queries[i % n_batches], cand, K, stream=stream)
     else:
         step = flat_step
     prof_key = "flat_gemm" if op["path"] == "flat_exact" else ("hnsw_search" if op["path"] == "hnsw_f32" else "hnsw_search_pq")
@@ -1759,11 +1780,13 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     qps = args.steps * Q_BATCH / dt
+    if args.dump_outputs and rank == 0:   # before anything else runs on the index (untimed)
+        dump_outputs(args.dump_outputs, *res)
 
     # ---- recall@10 of the timed pipeline against the fp64 ground truth (checker, untimed) --------
     nrec = Q_BATCH if gt1024 is not None else 64
     qrec = queries[0][:nrec]
-    got_ids = step(0)[:nrec] if nrec == Q_BATCH else index.search(qrec, K, stream=stream)[0]
+    got_ids = step(0)[0][:nrec] if nrec == Q_BATCH else index.search(qrec, K, stream=stream)[0]
     if gt1024 is not None:
         gt = gt1024
     else:

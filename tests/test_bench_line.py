@@ -151,3 +151,17 @@ def test_design_table_is_the_committed_record():
     a, b = text.index(dt.BEGIN) + len(dt.BEGIN), text.index(dt.END)
     assert text[a:b].strip() == dt.table("r06").strip()
     assert text[a:b].count("\n") >= 20            # every kernel family has its row
+
+
+def test_dump_outputs_writes_the_step_result_as_floats(tmp_path):
+    """--dump-outputs: ids (uint32 bit patterns in int32, 0xFFFFFFFF = no row) come back exactly as float64, scores as float32."""
+    import numpy as np
+    import torch
+    import bench
+    ids = torch.tensor([[0, 7, -1], [4294967294 - 2**32, 3, 1]], dtype=torch.int32)
+    sc = torch.tensor([[0.5, 1.25, float("inf")], [-2.0, 0.0, 3e38]], dtype=torch.float32)
+    bench.dump_outputs(str(tmp_path / "d"), ids, sc)
+    got_i, got_s = np.load(tmp_path / "d" / "ids.npy"), np.load(tmp_path / "d" / "scores.npy")
+    assert got_i.dtype == np.float64 and got_s.dtype == np.float32
+    assert np.array_equal(got_i, [[0, 7, 4294967295], [4294967294, 3, 1]])
+    assert np.array_equal(got_s.view(np.uint32), sc.numpy().view(np.uint32))

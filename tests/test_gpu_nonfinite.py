@@ -257,10 +257,10 @@ def test_vamana_beam_with_nan_distances(vg, ctx, kind, metric, where):
     """diskann.Segment.Search (segment.go:503-706): the traversal queue is a PriorityQueue (float comparisons in the kernel too), the
     results a CandidateHeap whose root the stop test reads (`c.dist > heap[0].score`).  With NaN distances the heap's layout decides
     its contents, its root — and so where the walk stops: ids, scores AND the walk's counters equal the oracle's.  fp32 / PQ / RaBitQ
-    node scorers, L2 and Dot, with and without a filter, k below and above 64."""
+    node scorers, L2 and Dot, with and without a filter, k below and above 64.  The code scorers have one distance (L2 from the
+    codes, segment.go:512-541) whatever the segment's metric, while the result heap's order still follows the metric
+    (segment.go:597): a Dot segment holding codes is walked too."""
     from tests import graphs
-    if metric == 2 and kind != 0:
-        pytest.skip("the code scorers have one distance")
     rng = np.random.default_rng(77 + kind + metric)
     n, dim, r = 1500, 32, 16
     base = rng.standard_normal((n, dim)).astype(np.float32)
@@ -285,7 +285,7 @@ def test_vamana_beam_with_nan_distances(vg, ctx, kind, metric, where):
             sc[1] = np.nan
         opq.set_codebooks(rng.integers(-128, 128, m * 256 * 8).astype(np.int8), sc, ((rng.random(m) * 2 - 1) * 0.1).astype(np.float32))
         codes = rng.integers(0, 256, (n, m)).astype(np.uint8)
-        ov = o.VamanaIndex(g, entry, dim, o.VAMANA_PQ, pq=opq, codes=codes)
+        ov = o.VamanaIndex(g, entry, dim, o.VAMANA_PQ, metric=metric, pq=opq, codes=codes)
         pq = vg.ProductQuantizer(ctx, dim, m, 256)
         pq.set_codebooks(opq.codebooks, opq.scales, opq.offsets)
         idx.set_pq_codes(pq, codes)
@@ -296,7 +296,7 @@ def test_vamana_beam_with_nan_distances(vg, ctx, kind, metric, where):
             hubs = np.bincount(g[g != 0xFFFFFFFF].astype(np.int64), minlength=n).argsort()[-3:]
             codes[hubs[0], cb - 4:] = np.frombuffer(np.float32(np.nan).tobytes(), np.uint8)
             codes[hubs[1], cb - 4:] = np.frombuffer(np.float32(np.inf).tobytes(), np.uint8)
-        ov = o.VamanaIndex(g, entry, dim, o.VAMANA_RABITQ, codes=codes)
+        ov = o.VamanaIndex(g, entry, dim, o.VAMANA_RABITQ, metric=metric, codes=codes)
         idx.set_rabitq_codes(codes)
     masks = rng.random((nq, n)) < 0.4
     for k in (1, 10, 100):
