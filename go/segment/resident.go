@@ -54,6 +54,7 @@ type Resident struct {
 func fp(p []float32) *C.float  { return (*C.float)(unsafe.Pointer(&p[0])) }
 func up(p []uint32) *C.uint32_t { return (*C.uint32_t)(unsafe.Pointer(&p[0])) }
 func bp(p []byte) *C.uint8_t    { return (*C.uint8_t)(unsafe.Pointer(&p[0])) }
+func ip(p []int32) *C.int32_t   { return (*C.int32_t)(unsafe.Pointer(&p[0])) }
 
 // NewResident creates an empty twin of a segment of `rows` x `dim`.
 func NewResident(rows, dim int, metric distance.Metric) (*Resident, error) {
@@ -175,6 +176,23 @@ func (r *Resident) SearchFlat(queries []float32, nq, k int) ([]uint32, []float32
 	ids, sc := r.out(nq, k)
 	st := C.vg_search_flat(r.h, fp(queries), C.int64_t(nq), C.int32_t(k), up(ids), fp(sc), nil)
 	return ids, sc, hipctx.Err(int32(st))
+}
+
+// SearchThreshold: the flat-segment leg of Engine.SearchThreshold (engine/engine.go:1485-1531): Search(q, maxResults)
+// (flat/segment.go:447-721), then the rows with Score <= thresholds[q] (L2) / >= thresholds[q] (Dot, Cosine), best first.
+// Query q's rows are ids/scores[q*maxResults : q*maxResults+counts[q]].  thresholds: one per query.  maxResults <= 16384;
+// a segment with more than one IVF partition is refused (the reference would probe only some of them).
+func (r *Resident) SearchThreshold(queries []float32, nq int, thresholds []float32, maxResults int) ([]uint32, []float32, []int32, error) {
+	if len(thresholds) < nq {
+		return nil, nil, nil, fmt.Errorf("SearchThreshold: %d thresholds for %d queries", len(thresholds), nq)
+	}
+	if nq == 0 || maxResults == 0 {
+		return nil, nil, make([]int32, nq), nil
+	}
+	ids, sc := r.out(nq, maxResults)
+	counts := make([]int32, nq)
+	st := C.vg_search_flat_threshold(r.h, fp(queries), C.int64_t(nq), fp(thresholds), C.int32_t(maxResults), nil, 0, up(ids), fp(sc), ip(counts), nil)
+	return ids, sc, counts, hipctx.Err(int32(st))
 }
 
 // SearchPQ: the PQ branch (flat/segment.go:476-483,678-689): BuildDistanceTable + PqAdcLookup per row.

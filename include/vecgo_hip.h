@@ -55,8 +55,9 @@ extern "C" {
  *   7: (r05) vg_index_set_hnsw_tombstones
  *   8: (r05) vg_segment_search_filtered
  *   9: (r05) vg_index_enable_sq8_nomination
- *  10: (r06) vg_index_enable_pq_nomination; NaN scores answered as the reference's heaps answer them (see "NaN scores") */
-#define VG_ABI_MINOR 10
+ *  10: (r06) vg_index_enable_pq_nomination; NaN scores answered as the reference's heaps answer them (see "NaN scores")
+ *  11: vg_search_flat_threshold */
+#define VG_ABI_MINOR 11
 #define VG_INVALID_ID 0xFFFFFFFFu
 #define VG_STREAM_LEGACY ((void *)1) /* == hipStreamLegacy */
 
@@ -387,9 +388,32 @@ int32_t vg_search_flat(vg_index *idx, const float *queries, int64_t nq, int32_t 
  * Ids and scores are therefore bit-identical with and without the filter.  on == 0 drops the copy. */
 int32_t vg_index_enable_bf16_filter(vg_index *idx, int32_t on, void *stream);
 
+/* Engine.SearchThreshold over one flat segment (engine/engine.go:1485-1531): per query
+ * flat.Segment.Search(q, k = max_results) (flat/segment.go:447-721, fp32 branch), then the rows with
+ * Score <= thresholds[q] (L2) / Score >= thresholds[q] (Dot, Cosine) (:1518-1529), best first.
+ * ids/scores[nq*max_results]; counts[nq] = rows kept; slots after counts[q] hold VG_INVALID_ID and
+ * +Inf (L2) / -Inf (Dot, Cosine), as the other searches pad.  mask / mask_stride: the row filter,
+ * with the same convention as vg_search_flat_filtered (NULL = none).  max_results <= 16384.
+ * Both comparisons keep the boundary; a NaN threshold keeps nothing.  Up to 8 queries: an exact scan (one pass
+ * over the rows) lists the rows within each threshold.  Larger batches: the fused GEMM of vg_search_flat (fp32, or
+ * the bf16 filter when enabled) appends every row under the user's threshold widened by the GEMM's error bound, or
+ * under a sampled threshold where that is lower; the appended rows are re-scored exactly and filtered, and a
+ * query whose proof fails (list overflow, or a sampled threshold too close to its max_results-th score) is
+ * answered by the scan.  Then the best max_results rows by (Score, RowID).  A query whose scores may hold a NaN
+ * replays the reference's heap with k = max_results and filters what it pops.  nq == 0 or max_results == 0:
+ * nothing is written.
+ * VG_ERR_UNSUPPORTED: max_results > 16384, Hamming, an index with more than one IVF partition (the reference
+ * would probe only nprobes of them).  Pointers may be host or device.  (VG_ABI_MINOR 11.) */
+int32_t vg_search_flat_threshold(vg_index *idx, const float *queries, int64_t nq, const float *thresholds,
+                                 int32_t max_results, const uint8_t *mask, int64_t mask_stride,
+                                 uint32_t *ids, float *scores, int32_t *counts, void *stream);
+
 /* diagnostics of vg_search_flat since vg_index_set_vectors: how many queries were searched and
  * how many of them were answered by the exhaustive kernel instead of GEMM candidates + proof
- * (either pointer may be NULL).  Synchronises the stream. */
+ * (either pointer may be NULL).  Synchronises the stream.  vg_search_flat_threshold counts alike: its
+ * queries in the first count; in the second, the queries of a nominated batch whose proof failed and were
+ * scanned (and every query under the test hook VG_FLAT_FORCE_EXACT).  Batches of up to 8 queries are scanned
+ * from the start, like vg_search_flat's small batches, and are not counted in the second. */
 int32_t vg_index_flat_stats(vg_index *idx, int64_t *queries, int64_t *exhaustive, void *stream);
 
 /* exhaustive scan of the RaBitQ codes: RaBitQuantizer.Distance (rabitq.go:119-176) for every

@@ -579,6 +579,12 @@ struct Result {
     std::vector<uint32_t> ids;   // [nq * k], best first, VG_INVALID_ID padded
     std::vector<float> scores;   // [nq * k]
 };
+// Engine.SearchThreshold's answer: per query counts[q] rows within the threshold, best first (at most max_results)
+struct ThresholdResult {
+    std::vector<uint32_t> ids;     // [nq * max_results], VG_INVALID_ID after counts[q]
+    std::vector<float> scores;     // [nq * max_results]
+    std::vector<int32_t> counts;   // [nq]
+};
 
 // One resident segment (flat / memtable-HNSW / DiskANN): the batch-level search entry points.
 class Segment {
@@ -607,6 +613,19 @@ public:
 
     // flat.Segment.Search fp32 branch (flat/segment.go:691-721)
     Result SearchFlat(const float *queries, int64_t nq, int k) { return run(nq, k, [&](Result &r) { return vg_search_flat(h_, queries, nq, k, r.ids.data(), r.scores.data(), nullptr); }); }
+    // Engine.SearchThreshold's flat-segment leg (engine/engine.go:1485-1531): Search(q, max_results), then the rows within
+    // thresholds[q] (<= for L2, >= for Dot / Cosine); mask: the row filter of vg_search_flat_filtered (nullptr = none)
+    ThresholdResult SearchThreshold(const float *queries, int64_t nq, const float *thresholds, int max_results,
+                                    const uint8_t *mask = nullptr, int64_t mask_stride = 0)
+    {
+        ThresholdResult r;
+        r.ids.resize(static_cast<size_t>(nq) * max_results);
+        r.scores.resize(static_cast<size_t>(nq) * max_results);
+        r.counts.resize(static_cast<size_t>(nq));
+        check(vg_search_flat_threshold(h_, queries, nq, thresholds, max_results, mask, mask_stride, r.ids.data(), r.scores.data(),
+                                       r.counts.data(), nullptr));
+        return r;
+    }
     // opt-in: nominate with a bfloat16 MFMA GEMM over a bf16 copy of the rows; results stay bit-identical (vecgo_hip.h)
     void EnableBF16Filter(bool on = true) { check(vg_index_enable_bf16_filter(h_, on ? 1 : 0, nullptr)); }
     // flat.Segment.Search PQ branch (flat/segment.go:476-483,678-689)

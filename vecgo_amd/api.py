@@ -1263,6 +1263,39 @@ class Index:
         """flat.Segment.Search fp32 branch / hnsw.BruteSearch: exact brute force."""
         return self._search(self._lib.vg_search_flat, queries, k, out=out, stream=stream)
 
+    def search_flat_threshold(self, queries, thresholds, max_results, mask=None, out=None, stream=None):
+        """Engine.SearchThreshold over this flat segment (engine/engine.go:1485-1531): search_flat(q, max_results), then the rows
+        with score <= threshold (L2) / >= threshold (Dot, Cosine), best first.  thresholds: a scalar for the batch or one per
+        query; mask: as search_flat_filtered's (None = no filter).  Returns (ids [nq, max_results], scores, counts [nq]): query
+        q's rows are ids[q, :counts[q]], the rest padded with 0xFFFFFFFF / +-Inf."""
+        nq = _rows(queries, self.dim)
+        q, pq_ = _ptr(queries, np.float32)
+        if _is_torch(thresholds):
+            t = thresholds.to(torch.float32).reshape(-1)
+            if t.numel() == 1 and nq != 1:
+                t = t.expand(nq)
+            t = t.contiguous()
+        else:
+            t = np.asarray(thresholds, np.float32).reshape(-1)
+            if t.size == 1:
+                t = np.full(nq, t[0], np.float32)
+        if (t.numel() if _is_torch(t) else t.size) != nq:
+            raise ValueError(f"search_flat_threshold: one threshold for the batch or one per query ({nq})")
+        t, pt = _ptr(t, np.float32, nq)
+        m, pm, stride = (None, None, 0) if mask is None else self._packed_mask(mask, nq, "search_flat_threshold")
+        if out is None:
+            ids = _empty_like(queries, (nq, max_results), np.uint32)
+            scores = _empty_like(queries, (nq, max_results), np.float32)
+            counts = _empty_like(queries, (nq,), np.int32)
+        else:
+            ids, scores, counts = out
+        i, pi = _ptr(ids, np.uint32, nq * max_results)
+        s, ps = _ptr(scores, np.float32, nq * max_results)
+        c, pc = _ptr(counts, np.int32, nq)
+        check(self._lib.vg_search_flat_threshold(self._h, pq_, C.c_int64(nq), pt, C.c_int32(max_results), pm, C.c_int64(stride),
+                                                  pi, ps, pc, _stream_ptr(stream)))
+        return ids, scores, counts
+
     def enable_bf16_filter(self, on: bool = True, stream=None):
         """vg_index_enable_bf16_filter: nominate with a bfloat16 MFMA GEMM over a bf16 copy of the rows; the exact fp32
         re-score and the (widened) proof keep ids and scores bit-identical."""

@@ -1177,6 +1177,96 @@ int32_t flat_nominate_bf16(vg_ctx *ctx, const uint16_t *rows_bf16, const float *
 }
 }  // namespace vg
 
+// The nomination of vg_search_flat_threshold (k_flat_threshold.hip) for batches: the caller's threshold folded into the fused GEMM.
+// Per query the append threshold (GEMM score form) is the user's — L2: t - |q|^2, Dot: -t — widened by the verify kernels' error
+// bound, or the sample threshold where that is lower; untight[q] = 1 where the user's stands (every row within it is appended
+// unless the list overflows), 0 where the sample tightened it, -1 where no bound holds (non-finite rows or query: the proof fails).
+// Outputs in the caller's buffers: gthr / qnorm / untight [cnt], counts [cnt], cand [cnt * cap] (GEMM keys).
+namespace vg {
+__global__ __launch_bounds__(64) void flat_thr_combine_kernel(const float *__restrict__ uthr, const float *__restrict__ sthr, int sel_k,
+                                                              const float *__restrict__ queries, int dim, const float *__restrict__ norm_max,
+                                                              float eps_extra, bool dot, float *__restrict__ gthr, float *__restrict__ qnorm,
+                                                              int *__restrict__ untight)
+{
+    const int64_t q = blockIdx.x;
+    const int lane = threadIdx.x;
+    float qn = 0.0f;  // (any order: only feeds the bounds)
+    for (int j = lane; j < dim; j += 64) qn = __builtin_fmaf(queries[q * dim + j], queries[q * dim + j], qn);
+    for (int off = 32; off > 0; off >>= 1) qn += __shfl_xor(qn, off);
+    if (lane != 0) return;
+    qnorm[q] = qn;
+    const float xmax = norm_max[0];
+    const float bound = 2.002f * (qn + xmax);  // above every row's GEMM score (flat_thr_cap_kernel)
+    if (!(bound < 1e30f)) {
+        gthr[q] = -3.0e38f;  // append nothing; the scan answers the query
+        untight[q] = -1;
+        return;
+    }
+    const float t = uthr[q];
+    const float eps = (4.0f * (static_cast<float>(dim) * 5.9604645e-8f) + eps_extra) * (qn + xmax) + 1e-30f;
+    float ut = (dot ? -t : t - qn) + eps;
+    if (!(ut > -bound)) ut = -bound;  // keeps nothing (NaN, or below every score): no row is appended, none is wanted
+    if (ut > bound) ut = bound;       // keeps everything: every row is appended (the bf16 tiles need a finite threshold)
+    const float st = sthr ? sthr[q * sel_k + sel_k - 1] : INFINITY;
+    const bool user = ut <= st;
+    gthr[q] = user ? ut : st;
+    untight[q] = user ? 1 : 0;
+}
+
+int32_t flat_thr_nominate(vg_index *idx, hipStream_t st, const float *qp, const float *uthr, int64_t cnt, const uint8_t *m0,
+                          int64_t mask_stride, int cap, int sel_k, int sample_stride, bool bf16, float eps_extra, float *sc, uint64_t *partial,
+                          uint32_t *sid, float *sthr, uint16_t *qbf, int *counts_wide, float *gthr, float *qnorm, int *untight, int *counts,
+                          uint64_t *cand)
+{
+    const bool dot = idx->metric != VG_METRIC_L2;
+    const int64_t n = idx->n;
+    const int dim = idx->dim;
+    const int64_t mt = (cnt + kGemmBM - 1) / kGemmBM, nt = (n + kGemmBN - 1) / kGemmBN;
+    const int64_t nst = (nt + sample_stride - 1) / sample_stride, ns = nst * kGemmBN;
+    const int sel_slices = static_cast<int>(std::min<int64_t>(64, std::max<int64_t>(1, ns / 4096)));
+    const unsigned ucnt = static_cast<unsigned>(cnt);
+    const bool dma = dim % 4 == 0 && (reinterpret_cast<uintptr_t>(qp) & 15) == 0 && (reinterpret_cast<uintptr_t>(idx->d_vectors) & 15) == 0;
+    const float *ga = qp, *gb = idx->d_vectors;
+    int gdim = dim;
+    if (bf16) {
+        const int bdim = idx->vectors_bf16_dim;
+        VG_LAUNCH(f32_to_bf16_pad_kernel, dim3(static_cast<unsigned>((cnt * bdim + 255) / 256)), dim3(256), 0, st, qp, cnt, dim, bdim, qbf);
+        ga = reinterpret_cast<const float *>(qbf);
+        gb = reinterpret_cast<const float *>(idx->d_vectors_bf16);
+        gdim = bdim / 2;
+    }
+    const bool use_sample = n > cap;  // n <= cap: the list holds every row, the user's threshold stands
+    if (use_sample) {
+        VG_TRY(launch_gemm<1>(dot, dma || bf16, static_cast<unsigned>(mt * ((nst + 7) / 8) * 8), st,
+                              {ga, cnt, gb, n, gdim, idx->d_norms, sc, sample_stride, ns, nullptr, 0, 0, nullptr, nullptr, 0, m0, mask_stride}, bf16));
+        VG_LAUNCH(flat_select_kernel, dim3(sel_slices, ucnt), dim3(kSelThreads), 0, st, sc, ns, sel_slices, sel_k, partial);
+        VG_TRY(launch_topk_merge(partial, cnt, sel_slices, sel_k, false, sid, sthr, st));
+    }
+    VG_LAUNCH(flat_thr_combine_kernel, dim3(ucnt), dim3(64), 0, st, uthr, use_sample ? sthr : nullptr, sel_k, qp, dim, idx->d_norm_max,
+              eps_extra, dot, gthr, qnorm, untight);
+    VG_HIP(hipMemsetAsync(counts, 0, sizeof(int) * static_cast<size_t>(cnt), st));
+    ProfScope prof(idx->ctx, "flat_thr_gemm", st);
+    VG_TRY(launch_gemm<2>(dot, dma || bf16, static_cast<unsigned>(mt * ((nt + 7) / 8) * 8), st,
+                          {ga, cnt, gb, n, gdim, idx->d_norms, nullptr, 1, 0, gthr, 1, 0, counts, cand, cap, m0, mask_stride,
+                           idx->ctx->compute_units, bf16 ? counts_wide : nullptr}, bf16));
+    return VG_OK;
+}
+
+int64_t flat_thr_sample_cols(int64_t n, int sample_stride)
+{
+    const int64_t nt = (n + kGemmBN - 1) / kGemmBN;
+    return (nt + sample_stride - 1) / sample_stride * kGemmBN;
+}
+static_assert(kCountLine == 32, "k_flat_threshold.hip sizes the counter lines as 32 ints");
+
+// the work list of the queries whose proof failed (todo[0] = how many, todo[1 ..] = which) and the statistics
+int32_t launch_flat_todo(const int *flags, const int *always, int cnt, int *todo, unsigned long long *stats, hipStream_t st)
+{
+    VG_LAUNCH(flat_todo_kernel, dim3(1), dim3(256), 0, st, flags, always, cnt, todo, stats);
+    return VG_OK;
+}
+}  // namespace vg
+
 VG_API int32_t vg_index_enable_bf16_filter(vg_index *idx, int32_t on, void *stream)
 {
     VG_CHECK(idx, VG_ERR_INVALID_ARG, "vg_index_enable_bf16_filter: NULL index");

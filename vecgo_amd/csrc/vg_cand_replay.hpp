@@ -219,6 +219,9 @@ inline int32_t launch_cand_replay(const Scorer &sc, const float *queries, int di
 {
     if (nq == 0 || k == 0 || hook(kHookNoCandReplay)) return VG_OK;
     const size_t lds = sizeof(uint64_t) * (static_cast<size_t>(k) + 4) + sizeof(float) * kReplayChunk;  // (+ 4: vg_heap.hpp reads a node's four children together)
+    if (lds > 65536)  // (a heap of more than ~7.6k items: vg_search_flat_threshold's max_results, up to 16384 = 132 KiB)
+        VG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(cand_replay_kernel<Scorer, Heap>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   static_cast<int>(lds)));
     for (int64_t q0 = 0; q0 < nq; q0 += 1 << 30) {
         const int64_t cnt = std::min<int64_t>(nq - q0, 1 << 30);
         VG_LAUNCH((cand_replay_kernel<Scorer, Heap>), dim3(static_cast<unsigned>(cnt)), dim3(kReplayThreads), lds, st, sc, queries + q0 * dim, dim, n, k,
