@@ -167,6 +167,28 @@ func (r *Resident) BuildHNSW(m, efConstruction int) error {
 	return hipctx.Err(int32(C.vg_hnsw_build(r.h, C.int32_t(m), C.int32_t(efConstruction), 8192, 32, nil)))
 }
 
+// BuildVamana: diskann.Writer.buildGraph over the rows (diskann/writer.go:362-460) with the seeded initial graph;
+// R, L, alpha of 0 take NewWriter's defaults.  The graph replaces the resident Vamana graph.
+func (r *Resident) BuildVamana(R, L int, alpha float32, seed uint64) error {
+	return hipctx.Err(int32(C.vg_vamana_build(r.h, C.int32_t(R), C.int32_t(L), C.float(alpha), nil, C.uint64_t(seed), 8192, 32, nil)))
+}
+
+// VamanaGraph: (R, n*R neighbour ids with 0xFFFFFFFF = none, entry point) — what Writer.Flush writes.
+func (r *Resident) VamanaGraph() (int, []uint32, uint32, error) {
+	var R C.int32_t
+	var entry C.uint32_t
+	if err := hipctx.Err(int32(C.vg_index_get_vamana_graph(r.h, &R, &entry, nil, nil))); err != nil {
+		return 0, nil, 0, err
+	}
+	graph := make([]uint32, r.rows*int(R))
+	if len(graph) > 0 {
+		if err := hipctx.Err(int32(C.vg_index_get_vamana_graph(r.h, nil, nil, up(graph), nil))); err != nil {
+			return 0, nil, 0, err
+		}
+	}
+	return int(R), graph, uint32(entry), nil
+}
+
 // ---- searches: nq row-major queries in, nq*k (RowID, Score) best-first out -----------------------------------------
 
 func (r *Resident) out(nq, k int) ([]uint32, []float32) { return make([]uint32, nq*k), make([]float32, nq*k) }

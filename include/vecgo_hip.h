@@ -56,8 +56,9 @@ extern "C" {
  *   8: (r05) vg_segment_search_filtered
  *   9: (r05) vg_index_enable_sq8_nomination
  *  10: (r06) vg_index_enable_pq_nomination; NaN scores answered as the reference's heaps answer them (see "NaN scores")
- *  11: vg_search_flat_threshold */
-#define VG_ABI_MINOR 11
+ *  11: vg_search_flat_threshold
+ *  12: vg_vamana_build, vg_index_get_vamana_graph */
+#define VG_ABI_MINOR 12
 #define VG_INVALID_ID 0xFFFFFFFFu
 #define VG_STREAM_LEGACY ((void *)1) /* == hipStreamLegacy */
 
@@ -277,6 +278,47 @@ int32_t vg_index_get_hnsw_graph(const vg_index *idx, int32_t *m0, int32_t *m, in
  * empty slot), entry point = header.Entrypoint.  Scoring uses whichever of the index's data the
  * search call names. */
 int32_t vg_index_set_vamana_graph(vg_index *idx, int32_t r, const uint32_t *graph, uint32_t entry_point,
+                                  void *stream);
+/* Vamana construction over the index's fp32 rows: diskann.Writer.buildGraph (diskann/writer.go:362-460) with
+ * greedySearch (:472-569), robustPrune (:571-625) and addBackEdge (:627-643).  The graph and entry point replace the
+ * index's Vamana graph as vg_index_set_vamana_graph would; vg_search_vamana (any kind) walks it.  (VG_ABI_MINOR 12.)
+ * r, l, alpha of 0 take NewWriter's defaults (writer.go:84-110): 64, 100, 1.2.  1 <= r <= 64, 1 <= l <= 1024,
+ * max_batch <= 16384 and n < 2^31, else VG_ERR_UNSUPPORTED; n == 0 is VG_ERR_INVALID_ARG ("no vectors to write");
+ * no fp32 rows (vg_index_set_vectors) is VG_ERR_NOT_READY.
+ * Distance: distance.Provider(metric) (distance/distance.go:97-106) in the pair kernel's summation order
+ *   (squaredL2Avx512 / dotAvx512): SquaredL2 for L2; raw Dot for Cosine and Dot, sorted ASCENDING as the writer
+ *   sorts it — the reference's quirk, reproduced: such a graph links the least similar rows.
+ * Order: every sort ascends by (distance, id), distances compared as floats (-0 equals +0, every NaN after +Inf).
+ *   The reference sorts by distance only over map iteration order; ties by id is the rule it leaves open.
+ * Centroid and entry point (:386-404): centroid[j] = float32 sum over the rows in row order, divided by float32(n);
+ *   the entry point is the first row with dist(row, centroid) < minDist, minDist starting at MaxFloat32 (row 0 when
+ *   no row qualifies), fixed for the whole build.
+ * Initial graph (:414-428): init_graph, if not NULL, is n*r ids (host or device), VG_INVALID_ID = empty slot (the
+ *   row's ids keep their order, empty slots drop out); an id >= n, a self edge or an id twice in a row is
+ *   VG_ERR_INVALID_ARG.  NULL: node i takes j = rng_u64(seed, i, P, t) % n for t = 0, 1, ... (the shared counter
+ *   RNG, oracle vgo_rng_u64; P = 0x56414D414E41, "VAMANA"), skipping j == i and ids already taken, until it holds
+ *   min(r, n-1) ids, in draw order.
+ * Passes (:430-457): two passes over the nodes 0..n-1, the first with alpha 1, the second with alpha.  Per node i:
+ *   1. results = greedySearch(row i, entry, l) as written: the pool is sorted every round; take the first
+ *      unexpanded entry, stop if there is none or its index is >= l while the pool is longer than l; mark it
+ *      expanded, cut the pool to l+50 if longer; append its unvisited neighbours (the entry starts visited);
+ *      return the first l ids of the finally sorted pool.
+ *   2. list(i) = robustPrune(i, results U list(i), r, alpha): the candidates without i sorted by d(c, i); c is kept
+ *      while fewer than r are kept unless alpha * d(c, s) < d(c, i) (fp32) for a kept s, so a NaN keeps it.
+ *   3. for each neighbour in list order, addBackEdge(neighbour, i): nothing if i is listed, else append i, and if
+ *      the list is then longer than r, list = robustPrune(neighbour, list, r, alpha).
+ * Batches: nodes go in id order in batches of clamp(processed / growth_div, 1, max_batch) (processed counts the nodes
+ *   of both passes; a batch ends with its pass).  In a batch every node searches the graph as it stood when the
+ *   batch began and prunes its own list as it stood then; all new lists are written; then the back edges are
+ *   applied, each target's records in (source id, slot) order.  max_batch = 1 is the writer's sequential loop.
+ * Output: lists in the order the reference leaves them (prune output sorted, back edges appended), padded with
+ *   VG_INVALID_ID to r.  The writer's reorderBFS (reorder.go) stays with the caller.  Deterministic: the same
+ *   inputs give the same graph bit for bit. */
+int32_t vg_vamana_build(vg_index *idx, int32_t r, int32_t l, float alpha, const uint32_t *init_graph, uint64_t seed,
+                        int32_t max_batch, int32_t growth_div, void *stream);
+/* The index's Vamana graph in vg_index_set_vamana_graph's layout: r, entry point, graph[n*r] (host or device);
+ * graph NULL = the sizes only.  (VG_ABI_MINOR 12.) */
+int32_t vg_index_get_vamana_graph(const vg_index *idx, int32_t *r, uint32_t *entry_point, uint32_t *graph,
                                   void *stream);
 
 /* fp32 rows of the segment, n*dim row-major — the layout of

@@ -647,6 +647,20 @@ public:
     {
         check(vg_hnsw_build(h_, m, efConstruction, maxBatch, growthDiv, nullptr));
     }
+    // diskann.Writer.buildGraph over the segment's rows (writer.go:362-460); replaces the segment's Vamana graph
+    void BuildVamana(int r = 64, int l = 100, float alpha = 1.2f, const uint32_t *initGraph = nullptr, uint64_t seed = 0,
+                     int maxBatch = 8192, int growthDiv = 32)
+    {
+        check(vg_vamana_build(h_, r, l, alpha, initGraph, seed, maxBatch, growthDiv, nullptr));
+    }
+    // the Vamana graph (n * r ids, VG_INVALID_ID = empty slot) and its entry point
+    std::vector<uint32_t> VamanaGraph(int *r, uint32_t *entry) const
+    {
+        check(vg_index_get_vamana_graph(h_, r, entry, nullptr, nullptr));
+        std::vector<uint32_t> g(static_cast<size_t>(n_) * *r);
+        check(vg_index_get_vamana_graph(h_, nullptr, nullptr, g.data(), nullptr));
+        return g;
+    }
     // the graph walk scored from PQ codes (candidates for Rerank, engine/search.go:914-965)
     Result SearchHNSWPQ(const float *queries, int64_t nq, int k, int ef) { return run(nq, k, [&](Result &r) { return vg_search_hnsw_pq(h_, queries, nq, k, ef, r.ids.data(), r.scores.data(), nullptr, nullptr); }); }
     // hnsw.KNNSearch (hnsw.go:1650-1755)

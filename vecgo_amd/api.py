@@ -1036,6 +1036,29 @@ class Index:
         check(self._lib.vg_index_set_vamana_graph(self._h, C.c_int32(g.shape[1]), C.c_void_p(g.ctypes.data),
                                                   C.c_uint32(entry_point), _stream_ptr(stream)))
 
+    def build_vamana(self, r=64, l=100, alpha=1.2, init_graph=None, seed=0, max_batch=8192, growth_div=32, stream=None):
+        """diskann.Writer.buildGraph over rows 0..n-1 on the GPU (diskann/writer.go:362-460; the rules are
+        vg_vamana_build's in the header); the graph becomes the index's Vamana graph.  init_graph: [n, r] ids
+        (0xFFFFFFFF = empty slot) or None for the seeded random start.  max_batch=1 is the writer's sequential loop."""
+        g = None
+        if init_graph is not None:
+            g = np.ascontiguousarray(init_graph, np.uint32)
+            if g.shape != (self.n, r):
+                raise ValueError(f"init_graph must be [{self.n}, {r}], got {g.shape}")
+        check(self._lib.vg_vamana_build(self._h, C.c_int32(r), C.c_int32(l), C.c_float(alpha),
+                                        None if g is None else C.c_void_p(g.ctypes.data), C.c_uint64(seed),
+                                        C.c_int32(max_batch), C.c_int32(growth_div), _stream_ptr(stream)))
+
+    def get_vamana_graph(self, stream=None):
+        """(graph[n, r], entry_point) — set_vamana_graph's arguments."""
+        r, ep = C.c_int32(), C.c_uint32()
+        sp = _stream_ptr(stream)
+        check(self._lib.vg_index_get_vamana_graph(self._h, C.byref(r), C.byref(ep), None, sp))
+        g = np.empty((self.n, r.value), np.uint32)
+        if g.size:
+            check(self._lib.vg_index_get_vamana_graph(self._h, None, None, C.c_void_p(g.ctypes.data), sp))
+        return g, int(ep.value)
+
     def _graph_search(self, fn, queries, k, mid_arg, want_stats, stream):
         nq = _rows(queries, self.dim)
         q, pq_ = _ptr(queries, np.float32)
