@@ -167,6 +167,23 @@ func (r *Resident) BuildHNSW(m, efConstruction int) error {
 	return hipctx.Err(int32(C.vg_hnsw_build(r.h, C.int32_t(m), C.int32_t(efConstruction), 8192, 32, nil)))
 }
 
+// InsertHNSW: hnsw.ApplyInsert for len(rows)/dim new rows (hnsw.go:629-637), appended as rows r.rows.. and linked
+// into the resident HNSW graph (vg_hnsw_insert).  On an empty Resident the first call creates the rows and the graph.
+func (r *Resident) InsertHNSW(rows []float32, m, efConstruction int) error {
+	if r.dim <= 0 || len(rows)%r.dim != 0 {
+		return fmt.Errorf("segment: InsertHNSW: %d floats are not whole rows of %d", len(rows), r.dim)
+	}
+	count := len(rows) / r.dim
+	if count == 0 {
+		return nil
+	}
+	if err := hipctx.Err(int32(C.vg_hnsw_insert(r.h, fp(rows), C.int64_t(count), C.int32_t(m), C.int32_t(efConstruction), 8192, 32, nil))); err != nil {
+		return err
+	}
+	r.rows += count
+	return nil
+}
+
 // BuildVamana: diskann.Writer.buildGraph over the rows (diskann/writer.go:362-460) with the seeded initial graph;
 // R, L, alpha of 0 take NewWriter's defaults.  The graph replaces the resident Vamana graph.
 func (r *Resident) BuildVamana(R, L int, alpha float32, seed uint64) error {

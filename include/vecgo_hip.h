@@ -57,8 +57,9 @@ extern "C" {
  *   9: (r05) vg_index_enable_sq8_nomination
  *  10: (r06) vg_index_enable_pq_nomination; NaN scores answered as the reference's heaps answer them (see "NaN scores")
  *  11: vg_search_flat_threshold
- *  12: vg_vamana_build, vg_index_get_vamana_graph */
-#define VG_ABI_MINOR 12
+ *  12: vg_vamana_build, vg_index_get_vamana_graph
+ *  13: vg_hnsw_insert */
+#define VG_ABI_MINOR 13
 #define VG_INVALID_ID 0xFFFFFFFFu
 #define VG_STREAM_LEGACY ((void *)1) /* == hipStreamLegacy */
 
@@ -266,6 +267,39 @@ int32_t vg_index_set_hnsw_graph(vg_index *idx, int32_t m0, const uint32_t *l0, i
  * 2 <= m <= 32, ef_construction <= 1024. */
 int32_t vg_hnsw_build(vg_index *idx, int32_t m, int32_t ef_construction, int32_t max_batch,
                       int32_t growth_div, void *stream);
+/* hnsw.ApplyInsert for `count` new rows (hnsw.go:629-637, insertNode :902-984), appended to the index as rows
+ * n .. n+count-1 and linked into its HNSW graph: the memtable's write path.  rows: count*dim fp32, host or device.
+ *   Ids and levels: new row t gets id t and level layerForApplyInsert(t), as in vg_hnsw_build (random levels of
+ *     Insert's RNG are out of scope).  Existing nodes keep the levels the graph's slot table gives them (the graph
+ *     may have been uploaded by vg_index_set_hnsw_graph from a CPU Insert).
+ *   Batches: rows go in id order in batches of clamp(inserted / growth_div, 1, max_batch), `inserted` counting
+ *     every node already in the graph; a call always ends a batch.  Hence vg_hnsw_build over b rows equals
+ *     vg_hnsw_build over the first a rows followed by vg_hnsw_insert of rows a..b-1 whenever every call boundary is
+ *     a batch boundary of the one-call schedule — for any a when max_batch = 1 (the sequential loop).
+ *   Entry point: updateEntryPoint (hnsw.go:885-900) applies across calls: a new node above the top level becomes
+ *     the entry point and its new levels are created.
+ *   Empty index (n = 0, no graph): the first call creates the rows and the graph; repeated calls grow them.
+ *   Everything sized by n follows: the fp32 rows, their norms, the bf16 filter image if enabled, the tombstone
+ *     bitmap (new rows are live; tombstoned nodes stay in the graph and take part in the insert search, as
+ *     insertNode searches unfiltered), and every search sees n + count rows afterwards.  The layer-0 edge
+ *     distances of vg_index_set_hnsw_edge_distances are read by the insert and then dropped (the predicate-aware
+ *     walk recomputes them, same values).
+ *   Layout: the row arrays and the layer-0 table grow by capacity (x1.5); the upper levels are re-laid on every
+ *     call (O(upper rows * m) ids), new nodes' rows appended to each level's table — the layout of a full build.
+ *   Refusals, in this order: rows but no graph VG_ERR_NOT_READY; Hamming, m outside 2..32, ef_construction > 1024,
+ *     >= 2^31 rows after the insert VG_ERR_UNSUPPORTED (max_batch / growth_div < 1 VG_ERR_INVALID_ARG); m not the
+ *     graph's M or the graph's M0 not 2M VG_ERR_INVALID_ARG; PQ / SQ8 / INT4 / RaBitQ codes, IVF partitions, a
+ *     Vamana graph or a nomination image (segment state) VG_ERR_UNSUPPORTED.  count = 0 changes nothing.
+ *   Build state: a back link into an existing row needs the row's cached distances and the pair bits of its members.
+ *     They are derived on the GPU, per call, for the rows the call's back links reach (cost scales with those rows,
+ *     not n).  The pair bits are recomputed by the reference's pair kernel.  The cached distances cannot be: the
+ *     insert search caches the bounded kernel's sum once its result heap is full, another summation order.  So the
+ *     index keeps them for a graph it built or grew (4 B per slot, freed with the graph), and the equivalence above
+ *     holds for such graphs.  For a graph from vg_index_set_hnsw_graph the layer-0 edge distances of
+ *     vg_index_set_hnsw_edge_distances are used where given, else the pair kernel's distances: the same graph as the
+ *     reference wherever those equal what the reference cached. */
+int32_t vg_hnsw_insert(vg_index *idx, const float *rows, int64_t count, int32_t m, int32_t ef_construction,
+                       int32_t max_batch, int32_t growth_div, void *stream);
 /* layerForApplyInsert (hnsw.go:2103-2116) with layerMultiplier = 1/ln(m) (hnsw.go:218) */
 int32_t vg_hnsw_level_for_id(uint64_t id, int32_t m);
 /* The index's HNSW graph in vg_index_set_hnsw_graph's layout.  Every output may be NULL; call once for

@@ -647,6 +647,11 @@ public:
     {
         check(vg_hnsw_build(h_, m, efConstruction, maxBatch, growthDiv, nullptr));
     }
+    // hnsw.ApplyInsert for `count` rows appended as rows n .. n+count-1 (vg_hnsw_insert); rows host or device
+    void InsertHNSW(const float *rows, int64_t count, int m = 32, int ef = 300, int maxBatch = 8192, int growthDiv = 32)
+    {
+        check(vg_hnsw_insert(h_, rows, count, m, ef, maxBatch, growthDiv, nullptr));
+    }
     // diskann.Writer.buildGraph over the segment's rows (writer.go:362-460); replaces the segment's Vamana graph
     void BuildVamana(int r = 64, int l = 100, float alpha = 1.2f, const uint32_t *initGraph = nullptr, uint64_t seed = 0,
                      int maxBatch = 8192, int growthDiv = 32)

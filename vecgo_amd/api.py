@@ -1011,6 +1011,23 @@ class Index:
         check(self._lib.vg_hnsw_build(self._h, C.c_int32(m), C.c_int32(ef_construction), C.c_int32(max_batch),
                                       C.c_int32(growth_div), _stream_ptr(stream)))
 
+    def insert_hnsw(self, rows, m=32, ef_construction=300, max_batch=8192, growth_div=32, stream=None):
+        """hnsw.ApplyInsert on the GPU (vg_hnsw_insert): rows [count, dim] fp32 are appended as rows n .. n+count-1 and
+        linked into the index's HNSW graph (ids = row numbers, levels of ApplyInsert; batches of clamp(inserted /
+        growth_div, 1, max_batch)).  An empty index (n = 0) gets its rows and graph from the first call."""
+        if not _is_torch(rows):
+            rows = np.asarray(rows)
+        shape = tuple(rows.shape)
+        if len(shape) != 2 or shape[1] != self.dim:
+            raise ValueError(f"insert_hnsw: rows must be [count, {self.dim}], got {shape}")
+        if (rows.dtype != torch.float32) if _is_torch(rows) else (np.asarray(rows).dtype != np.float32):
+            raise TypeError(f"insert_hnsw: rows must be float32, got {rows.dtype}")
+        count = shape[0]
+        r, pr = _ptr(rows, np.float32, count * self.dim)
+        check(self._lib.vg_hnsw_insert(self._h, pr, C.c_int64(count), C.c_int32(m), C.c_int32(ef_construction),
+                                       C.c_int32(max_batch), C.c_int32(growth_div), _stream_ptr(stream)))
+        self.n += count
+
     def get_hnsw_graph(self, stream=None):
         """(l0[n, m0], upper=[(slot[n], adj[rows, m])...], entry_point) — set_hnsw_graph's arguments."""
         m0, m_, L, ep = C.c_int32(), C.c_int32(), C.c_int32(), C.c_uint32()

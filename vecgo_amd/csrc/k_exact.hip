@@ -141,6 +141,22 @@ __global__ void row_norms_kernel(const float *__restrict__ base, int64_t n, int 
 
 static bool metric_is_dot(int32_t metric) { return metric != VG_METRIC_L2; }
 
+namespace vg {
+__global__ void fold_max_kernel(float *__restrict__ dst, const float *__restrict__ src) { dst[0] = fmaxf(dst[0], src[0]); }
+
+int32_t append_row_norms(vg_index *idx, int64_t from, int64_t to, hipStream_t st)
+{
+    if (to <= from) return VG_OK;
+    DevTmp<float> mx;
+    VG_TRY(mx.init(1, st));
+    VG_LAUNCH(row_norms_kernel, dim3(static_cast<unsigned>((to - from + 3) / 4)), dim3(256), 0, st,
+              idx->d_vectors + from * idx->dim, to - from, idx->dim, idx->d_norms + from, reinterpret_cast<int *>(idx->d_norm_max + 1));
+    VG_LAUNCH(norm_max_kernel, dim3(1), dim3(1024), 0, st, idx->d_norms + from, to - from, mx.ptr);
+    VG_LAUNCH(fold_max_kernel, dim3(1), dim3(1), 0, st, idx->d_norm_max, mx.ptr);
+    return VG_OK;
+}
+}  // namespace vg
+
 VG_API int32_t vg_index_set_vectors(vg_index *idx, const float *base, void *stream)
 {
     VG_CHECK(idx, VG_ERR_INVALID_ARG, "vg_index_set_vectors: NULL index");
@@ -160,6 +176,7 @@ VG_API int32_t vg_index_set_vectors(vg_index *idx, const float *base, void *stre
         idx->d_flat_stats = nullptr;
         idx->d_vectors_bf16 = nullptr;
     }
+    idx->rows_cap = idx->bf16_cap = 0;
     if (idx->n == 0) return VG_OK;
     // all four allocations or none: a search must never find rows without their norms / counters
     const int32_t status = [&]() -> int32_t {

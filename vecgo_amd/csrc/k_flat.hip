@@ -1267,6 +1267,18 @@ int32_t launch_flat_todo(const int *flags, const int *always, int cnt, int *todo
 }
 }  // namespace vg
 
+namespace vg {
+int32_t append_bf16_rows(vg_index *idx, int64_t from, int64_t to, hipStream_t st)
+{
+    const int64_t count = (to - from) * idx->vectors_bf16_dim;
+    if (count <= 0) return VG_OK;
+    VG_LAUNCH(f32_to_bf16_pad_kernel, dim3(static_cast<unsigned>((count + 255) / 256)), dim3(256), 0, st,
+              idx->d_vectors + from * idx->dim, to - from, idx->dim, idx->vectors_bf16_dim,
+              idx->d_vectors_bf16 + from * idx->vectors_bf16_dim);
+    return VG_OK;
+}
+}  // namespace vg
+
 VG_API int32_t vg_index_enable_bf16_filter(vg_index *idx, int32_t on, void *stream)
 {
     VG_CHECK(idx, VG_ERR_INVALID_ARG, "vg_index_enable_bf16_filter: NULL index");
@@ -1277,6 +1289,7 @@ VG_API int32_t vg_index_enable_bf16_filter(vg_index *idx, int32_t on, void *stre
         VG_HIP(hipFree(idx->d_vectors_bf16));
         idx->d_vectors_bf16 = nullptr;
     }
+    idx->bf16_cap = 0;
     if (!on) return VG_OK;
     VG_CHECK(idx->d_vectors, VG_ERR_NOT_READY, "vg_index_enable_bf16_filter: index has no fp32 vectors");
     // rows of whole K steps (2 * kGemmBK = 64 bfloat16): the dimensions from dim on are zeros, which add nothing to a dot product

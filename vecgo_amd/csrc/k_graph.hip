@@ -698,6 +698,13 @@ VG_API int32_t vg_index_set_hnsw_graph(vg_index *idx, int32_t m0, const uint32_t
     VG_CHECK(idx->n == 0 || entry_point < idx->n, VG_ERR_INVALID_ARG, "vg_index_set_hnsw_graph: entry point out of range");
     VG_HIP(hipSetDevice(idx->ctx->device));
     hipStream_t st = vg::pick_stream(idx->ctx, stream);
+    idx->l0_cap = 0;
+    for (float **c : {&idx->d_hnsw_l0_cdist, &idx->d_hnsw_adj_cdist})  // a GPU build's cached distances: not this graph's
+        if (*c) {
+            VG_HIP(hipStreamSynchronize(st));
+            (void)hipFree(*c);
+            *c = nullptr;
+        }
     VG_TRY(replace_device_array(&idx->d_hnsw_l0, l0, static_cast<size_t>(idx->n) * m0, st));
     if (idx->d_hnsw_l0_dist) {  // the old graph's edge distances (vg_index_set_hnsw_edge_distances)
         VG_HIP(hipStreamSynchronize(st));

@@ -26,6 +26,9 @@
 // every candidate order is the order the reference's 4-ary heap would pop (rank by distance; on equal
 // distances the heap is replayed in LDS), so the graph equals what a letter-by-letter CPU run of hnsw.go builds
 // (the test oracle) — bit for bit, ties included.
+//
+// vg_hnsw_insert runs the same batches on a graph the index already holds: rows appended, the per-row build state of
+// older rows derived on demand (build_derive_kernel), see the comments at the entry point and DESIGN.md "HNSW insert".
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -43,19 +46,29 @@ constexpr int kBuildMaxEf = 1024;   // candidates per (node, level); heaps of th
 constexpr int kSelThreads = 256;
 
 // The graph under construction.  Rows: layer 0 row of node i = i (m0 slots); the row of node i on level
-// l >= 1 = n + level_off[l-1] + slots[(l-1)*n + i] (m slots).  Slot arrays are laid out as one array with
-// the n*m0 layer-0 slots first: that prefix IS the l0 table of vg_index_set_hnsw_graph, the rest its adj.
+// l >= 1 = n + level_off[l-1] + slots[(l-1)*n + i] (m slots).  The ids live in two tables: `ids` = the n*m0
+// layer-0 slots (the l0 table of vg_index_set_hnsw_graph), `ids_up` = the upper levels' rows (its adj).  The
+// build allocates them as one array (ids_up = ids + n*m0); vg_hnsw_insert links straight into the index's tables.
+//
+// Build state (dist, bits, cnt, good) is kept per STATE row.  The build makes every row itself and keeps state for
+// all of them: state row = row (smap null).  vg_hnsw_insert keeps it only for the rows the call touches: smap[row] =
+// the row's state row, -1 until the select kernel makes the row (a new node's row: state row = its pair index) or
+// build_derive_kernel derives it from the graph (a row that existed before the call: state rows from npairs on).
 struct BuildGraph {
     const float *base;
     int64_t n;
     int dim, metric, m0, m;
-    uint32_t *ids;    // 0xFFFFFFFF beyond cnt
+    uint32_t *ids;    // layer-0 rows; 0xFFFFFFFF beyond cnt
+    uint32_t *ids_up; // upper rows
     float *dist;      // d(row's node, member) as the insert search computed it
     uint64_t *bits;   // bit j of bits[slot i]: d(member i, member j) < dist[i]
-    int32_t *cnt;     // per row
-    uint8_t *good;    // per row: full, and every member was CHOSEN by the heuristic (none filled up): see build_link_kernel
+    int32_t *cnt;     // per state row
+    uint8_t *good;    // per state row: full, and every member was CHOSEN by the heuristic (none filled up): see build_link_kernel
     const uint32_t *slots;
     const int64_t *level_off;
+    int32_t *smap;      // vg_hnsw_insert: row -> state row (-1: none yet); null: the state row is the row
+    uint32_t *srow_row; // vg_hnsw_insert: state row -> row
+    uint32_t *row_node; // vg_hnsw_insert: the node of every row a back-link record targets (written by the select kernel)
 };
 
 __device__ __forceinline__ int64_t bg_row(const BuildGraph &g, uint32_t node, int level)
@@ -68,6 +81,16 @@ __device__ __forceinline__ int64_t bg_off(const BuildGraph &g, int64_t row)
     return row < g.n ? row * g.m0 : g.n * g.m0 + (row - g.n) * g.m;
 }
 __device__ __forceinline__ int bg_deg(const BuildGraph &g, int64_t row) { return row < g.n ? g.m0 : g.m; }
+__device__ __forceinline__ uint32_t *bg_ids(const BuildGraph &g, int64_t row)
+{
+    return row < g.n ? g.ids + row * g.m0 : g.ids_up + (row - g.n) * g.m;
+}
+constexpr int kStateStride = 64;  // slots per state row of vg_hnsw_insert (M0 <= 64)
+// first slot of a state row in dist / bits
+__device__ __forceinline__ int64_t bg_soff(const BuildGraph &g, int64_t row, int64_t srow)
+{
+    return g.smap ? srow * kStateStride : bg_off(g, row);
+}
 
 // h.distanceFunc (newDistanceFunc hnsw.go:2218-2238) of two rows, all lanes of the 16-lane group
 __device__ __forceinline__ float bg_pair(const BuildGraph &g, uint32_t a, uint32_t b, Sub16 sub)
@@ -79,8 +102,9 @@ __device__ __forceinline__ float bg_pair(const BuildGraph &g, uint32_t a, uint32
 // pair_base[t] = index of node t's first (node, level) pair counted from node 0 (levels min(level,top)..0
 // → pair index + level); the batch's lists are stored relative to pair_base[t0].
 // UK: the metric is not Dot, distances are >= +0 and the heaps compare bit patterns (heap_sift_down_uk, vg_heap.hpp)
+// levels / pair_base are indexed from node t_base on (the build: 0; vg_hnsw_insert: the first new row)
 template <bool UK>
-__global__ __launch_bounds__(64) void build_search_kernel(BuildGraph g, int64_t t0, uint32_t entry, int cur_top,
+__global__ __launch_bounds__(64) void build_search_kernel(BuildGraph g, int64_t t0, int64_t t_base, uint32_t entry, int cur_top,
                                                           const int32_t *__restrict__ levels,
                                                           const int64_t *__restrict__ pair_base, int ef,
                                                           uint32_t *__restrict__ visited_ws, int64_t vis_words,
@@ -101,13 +125,13 @@ __global__ __launch_bounds__(64) void build_search_kernel(BuildGraph g, int64_t 
     sc.metric = g.metric;
     sc.sub = Sub16::make(lane);
     uint32_t *vis = visited_ws + static_cast<int64_t>(blockIdx.x) * vis_words;
-    const int lt = levels[t];
-    const int64_t pair0 = pair_base[t] - pair_base[t0];
+    const int lt = levels[t - t_base];
+    const int64_t pair0 = pair_base[t - t_base] - pair_base[t0 - t_base];
 
     uint32_t cur = entry;
     float cur_d = sc.one(cur);
     for (int level = cur_top; level > lt; level--) {  // hnsw.go:918-934
-        auto row_of = [&](uint32_t node) -> const uint32_t * { return g.ids + bg_off(g, bg_row(g, node, level)); };
+        auto row_of = [&](uint32_t node) -> const uint32_t * { return bg_ids(g, bg_row(g, node, level)); };
         greedy_layer(sc, lane, row_of, g.m, nb_pair, nb_bnd, cur, cur_d);
     }
     const int first = lt < cur_top ? lt : cur_top;
@@ -119,7 +143,7 @@ __global__ __launch_bounds__(64) void build_search_kernel(BuildGraph g, int64_t 
             __syncthreads();
         }
         const int deg = level == 0 ? g.m0 : g.m;
-        auto row_of = [&](uint32_t node) -> const uint32_t * { return g.ids + bg_off(g, bg_row(g, node, level)); };
+        auto row_of = [&](uint32_t node) -> const uint32_t * { return bg_ids(g, bg_row(g, node, level)); };
         int res_len = 0;
         search_layer<UK>(sc, g.metric == kMetricL2, lane, row_of, deg, cur, cur_d, ef, cand, res, nb_pair, nb_bnd, vis,
                          res_len, st);
@@ -176,7 +200,9 @@ struct SelShared {
     int flag, nsel, nfinal;
 };
 
-__global__ __launch_bounds__(kSelThreads) void build_select_kernel(BuildGraph g, const uint32_t *__restrict__ pair_node,
+// pair_first: index of the batch's first pair among the call's pairs (vg_hnsw_insert's state rows of the new rows)
+__global__ __launch_bounds__(kSelThreads) void build_select_kernel(BuildGraph g, int64_t pair_first,
+                                                                   const uint32_t *__restrict__ pair_node,
                                                                    const int32_t *__restrict__ pair_level, int ef,
                                                                    const uint32_t *__restrict__ cand_ids,
                                                                    const float *__restrict__ cand_d,
@@ -191,7 +217,9 @@ __global__ __launch_bounds__(kSelThreads) void build_select_kernel(BuildGraph g,
     const uint32_t t = pair_node[p];
     const int level = pair_level[p];
     const int64_t row = bg_row(g, t, level);
-    const int64_t off = bg_off(g, row);
+    uint32_t *const rid = bg_ids(g, row);
+    const int64_t srow = g.smap ? pair_first + p : row;
+    const int64_t off = bg_soff(g, row, srow);
     const int m = bg_deg(g, row);
     const int nc = cand_n[p];
     const uint32_t *cid = cand_ids + p * ef;
@@ -285,19 +313,25 @@ __global__ __launch_bounds__(kSelThreads) void build_select_kernel(BuildGraph g,
             for (int j = 0; j < nf; j++)
                 if (j != i && sh.dm[i][j] < di) bits |= 1ull << j;
         }
-        g.ids[off + i] = i < nf ? sh.fid[i] : VG_INVALID_ID;
+        rid[i] = i < nf ? sh.fid[i] : VG_INVALID_ID;
         g.dist[off + i] = i < nf ? sh.fd[i] : 0.0f;
         g.bits[off + i] = bits;
         if (i < rec_stride) {
-            rec_row[p * rec_stride + i] = i < nf ? static_cast<uint32_t>(bg_row(g, sh.fid[i], level)) : VG_INVALID_ID;
+            const uint32_t trow = i < nf ? static_cast<uint32_t>(bg_row(g, sh.fid[i], level)) : VG_INVALID_ID;
+            if (g.row_node && i < nf) g.row_node[trow] = sh.fid[i];  // (every writer of a row writes the same node)
+            rec_row[p * rec_stride + i] = trow;
             rec_t[p * rec_stride + i] = t;
             rec_d[p * rec_stride + i] = i < nf ? sh.fd[i] : 0.0f;
         }
     }
     for (int i = m + tid; i < rec_stride; i += kSelThreads) rec_row[p * rec_stride + i] = VG_INVALID_ID;
     if (tid == 0) {
-        g.cnt[row] = nf;
-        g.good[row] = nf == m && nsel == m ? 1 : 0;
+        g.cnt[srow] = nf;
+        g.good[srow] = nf == m && nsel == m ? 1 : 0;
+        if (g.smap) {
+            g.smap[row] = static_cast<int32_t>(srow);
+            g.srow_row[srow] = static_cast<uint32_t>(row);
+        }
     }
 }
 
@@ -411,7 +445,9 @@ __global__ __launch_bounds__(kLinkThreads) void build_link_kernel(BuildGraph g, 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const Sub16 sub = Sub16::make(lane);
     const int64_t row = work[blockIdx.x];
-    const int64_t off = bg_off(g, row);
+    uint32_t *const rid = bg_ids(g, row);
+    const int64_t srow = g.smap ? g.smap[row] : row;
+    const int64_t off = bg_soff(g, row, srow);
     const int deg = bg_deg(g, row);
     const int nadd = rcnt[row];
     const uint32_t *at = srt_t + roff[row];
@@ -446,8 +482,8 @@ __global__ __launch_bounds__(kLinkThreads) void build_link_kernel(BuildGraph g, 
         return __ballot(lane + 1 < cnt && dist == nxt) != 0;
     };
     if (wave == 0) {
-        cnt = g.cnt[row];
-        id = lane < deg ? g.ids[off + lane] : VG_INVALID_ID;
+        cnt = g.cnt[srow];
+        id = lane < deg ? rid[lane] : VG_INVALID_ID;
         dist = lane < deg ? g.dist[off + lane] : 0.0f;
         bits = lane < deg ? g.bits[off + lane] : 0;
         // The cheap way out.  `good` = the row is full and applyHeuristic CHOSE every member (nothing was filled up),
@@ -460,7 +496,7 @@ __global__ __launch_bounds__(kLinkThreads) void build_link_kernel(BuildGraph g, 
         // changes (`stable`).  Hub rows — thousands of back links per batch, and two bit-equal cached distances among
         // their 64 almost always — would otherwise replay the heap for every record.  75 % of the back links of the
         // 1M x 768 build end here.
-        good = g.good[row] != 0;
+        good = g.good[srow] != 0;
         ties = row_has_ties();
         sh.mid[lane] = id;
     }
@@ -678,7 +714,7 @@ __global__ __launch_bounds__(kLinkThreads) void build_link_kernel(BuildGraph g, 
     }
     if (wave == 0) {
         if (lane < deg) {
-            g.ids[off + lane] = lane < cnt ? id : VG_INVALID_ID;
+            rid[lane] = lane < cnt ? id : VG_INVALID_ID;
             g.dist[off + lane] = lane < cnt ? dist : 0.0f;
             g.bits[off + lane] = lane < cnt ? bits : 0;
         }
@@ -688,7 +724,7 @@ __global__ __launch_bounds__(kLinkThreads) void build_link_kernel(BuildGraph g, 
                 atomicAdd(&totals->skipped, static_cast<unsigned long long>(n_skip));
                 atomicAdd(&totals->appended, static_cast<unsigned long long>(n_app));
                 atomicAdd(&totals->pruned, static_cast<unsigned long long>(n_prune));
-                atomicAdd(&totals->good_rows_seen, static_cast<unsigned long long>(g.good[row] ? 1 : 0));
+                atomicAdd(&totals->good_rows_seen, static_cast<unsigned long long>(g.good[srow] ? 1 : 0));
                 atomicMax(&totals->longest_chain, static_cast<unsigned long long>(nadd));
                 if (timed) {
                     atomicAdd(&totals->hub_rows, 1ull);
@@ -707,8 +743,8 @@ __global__ __launch_bounds__(kLinkThreads) void build_link_kernel(BuildGraph g, 
                                                    (static_cast<unsigned long long>(n_prune & 0xFFFF) << 8) | (n_tie > 255 ? 255 : n_tie));
                 }
             }
-            g.cnt[row] = cnt;
-            g.good[row] = good ? 1 : 0;
+            g.cnt[srow] = cnt;
+            g.good[srow] = good ? 1 : 0;
             rcnt[row] = 0;
             rfill[row] = 0;
         }
@@ -719,6 +755,147 @@ __global__ void fill_u32_kernel(uint32_t *p, int64_t n, uint32_t v)
 {
     const int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
     if (i < n) p[i] = v;
+}
+
+// ---- vg_hnsw_insert: build state of a row that existed before the call -------------------------------
+// One workgroup per row of the batch's work list that has no state row yet (one the build would have kept from
+// the insert that made it): its member ids come from the graph; dist[i] = the distance the row cached for member i;
+// bits[i] bit j = d(member i, member j) < dist[i], the pair distances by the reference's kernel in its summation order
+// (what the build compared: symmetric bit for bit).  dist comes from the cached distances the index keeps for a graph
+// it built (d_hnsw_*_cdist) — they cannot be recomputed: the insert search caches the bounded kernel's sum once its
+// result heap is full, another summation order — else from the uploaded layer-0 edge distances, else it is
+// d(row's node, member i) by the pair kernel.  good = 0: the first record that reaches the full row takes
+// addConnectionPrune's long path, which gives what the shortcut gives.  Runs after the count kernel (the work
+// list) and before the link kernel; the rows are distinct within a batch.
+struct DeriveShared {
+    float dm[64][65];
+    float md[64];
+    uint32_t mid[64];
+    int64_t srow;
+    int cnt, fresh;
+};
+
+__global__ __launch_bounds__(kSelThreads) void build_derive_kernel(BuildGraph g, const uint32_t *__restrict__ work,
+                                                                   const LinkCounters *__restrict__ ctr,
+                                                                   unsigned int *__restrict__ s_next, int64_t s_first,
+                                                                   const float *__restrict__ l0_dist, int64_t dist_rows,
+                                                                   const float *__restrict__ cd0, const float *__restrict__ cdu,
+                                                                   unsigned int *__restrict__ derived)
+{
+    __shared__ DeriveShared sh;
+    if (blockIdx.x >= ctr->nwork) return;
+    const int tid = threadIdx.x, grp = tid >> 4;
+    const Sub16 sub = Sub16::make(tid);
+    const int64_t row = work[blockIdx.x];
+    const int deg = bg_deg(g, row);
+    const uint32_t *rid = bg_ids(g, row);
+    if (tid == 0) {
+        int64_t s = g.smap[row];
+        sh.fresh = s < 0 ? 1 : 0;
+        if (s < 0) {
+            s = s_first + atomicAdd(s_next, 1u);
+            g.smap[row] = static_cast<int32_t>(s);
+            g.srow_row[s] = static_cast<uint32_t>(row);
+            atomicAdd(derived, 1u);
+        }
+        sh.srow = s;
+        int c = 0;
+        while (c < deg && rid[c] != VG_INVALID_ID) c++;
+        sh.cnt = c;
+    }
+    __syncthreads();
+    if (!sh.fresh) return;
+    const int cnt = sh.cnt;
+    const uint32_t node = g.row_node[row];
+    if (tid < cnt) sh.mid[tid] = rid[tid];
+    __syncthreads();
+    for (int i0 = 0; i0 < cnt; i0 += kSelThreads / 16) {
+        const int i = i0 + grp;
+        if (i < cnt) {
+            float d;
+            if (cd0)
+                d = row < g.n ? cd0[row * g.m0 + i] : cdu[(row - g.n) * g.m + i];
+            else if (l0_dist && row < dist_rows)
+                d = l0_dist[row * g.m0 + i];
+            else
+                d = bg_pair(g, sh.mid[i], node, sub);
+            if ((tid & 15) == 0) sh.md[i] = d;
+        }
+    }
+    const int npair = cnt * (cnt - 1) / 2;
+    for (int e0 = 0; e0 < npair; e0 += kSelThreads / 16) {
+        const int e = e0 + grp;
+        if (e < npair) {  // e = a (a - 1) / 2 + b, b < a
+            int a = static_cast<int>((1.0f + sqrtf(1.0f + 8.0f * static_cast<float>(e))) * 0.5f);
+            while (a * (a - 1) / 2 > e) a--;
+            while ((a + 1) * a / 2 <= e) a++;
+            const int b = e - a * (a - 1) / 2;
+            const float d = bg_pair(g, sh.mid[a], sh.mid[b], sub);
+            if ((tid & 15) == 0) {
+                sh.dm[a][b] = d;
+                sh.dm[b][a] = d;
+            }
+        }
+    }
+    __syncthreads();
+    const int64_t srow = sh.srow;
+    const int64_t off = srow * kStateStride;
+    for (int i = tid; i < deg; i += kSelThreads) {
+        uint64_t bits = 0;
+        if (i < cnt) {
+            const float di = sh.md[i];
+            for (int j = 0; j < cnt; j++)
+                if (j != i && sh.dm[i][j] < di) bits |= 1ull << j;
+        }
+        g.dist[off + i] = i < cnt ? sh.md[i] : 0.0f;
+        g.bits[off + i] = bits;
+    }
+    if (tid == 0) {
+        g.cnt[srow] = cnt;
+        g.good[srow] = 0;
+    }
+}
+
+// after the batches: every state row's cached distances back into the index's (l0 / upper) arrays
+__global__ void state_writeback_kernel(BuildGraph g, const unsigned int *__restrict__ s_next, int64_t npairs,
+                                       float *__restrict__ cd0, float *__restrict__ cdu)
+{
+    const int64_t s = blockIdx.x;
+    if (s >= npairs + static_cast<int64_t>(*s_next)) return;
+    const int64_t row = g.srow_row[s];
+    const int deg = bg_deg(g, row);
+    float *dst = row < g.n ? cd0 + row * g.m0 : cdu + (row - g.n) * g.m;
+    for (int i = threadIdx.x; i < deg; i += blockDim.x) dst[i] = g.dist[s * kStateStride + i];
+}
+
+// the upper slot table of n_new nodes from the old one (n_old nodes, L_old levels) and the new nodes' slots
+// (fresh[l * count + (i - n_old)])
+__global__ void slot_relayout_kernel(const uint32_t *__restrict__ old, int64_t n_old, int l_old,
+                                     const uint32_t *__restrict__ fresh, int64_t n_new, int l_new,
+                                     uint32_t *__restrict__ out)
+{
+    const int64_t e = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (e >= static_cast<int64_t>(l_new) * n_new) return;
+    const int l = static_cast<int>(e / n_new);
+    const int64_t i = e - static_cast<int64_t>(l) * n_new;
+    uint32_t v;
+    if (i >= n_old)
+        v = fresh[static_cast<int64_t>(l) * (n_new - n_old) + (i - n_old)];
+    else
+        v = l < l_old ? old[static_cast<int64_t>(l) * n_old + i] : VG_INVALID_ID;
+    out[e] = v;
+}
+
+// tombstone bits from `from` to the end of the byte that holds bit to - 1 cleared (little-endian bit order, as
+// the searches read them): the new rows are live
+__global__ void clear_bits_kernel(uint8_t *__restrict__ bm, int64_t from, int64_t to)
+{
+    const int64_t byte = from / 8 + static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (byte * 8 >= to) return;
+    uint8_t keep = 0;
+    for (int b = 0; b < 8; b++)
+        if (byte * 8 + b < from) keep |= static_cast<uint8_t>(1u << b);
+    bm[byte] &= keep;
 }
 
 // layerForApplyInsert (hnsw.go:2103-2116), layerMultiplier = 1 / ln(M) (hnsw.go:218)
@@ -754,6 +931,132 @@ struct DevBuf {
         return r;
     }
 };
+
+// One batch of the schedule: nodes t0 .. t0+size-1, their (node, level) pairs, the entry point and top level
+// their searches start from
+struct BuildBatch {
+    int64_t t0, size, npairs;
+    uint32_t entry;
+    int cur_top;
+};
+
+// Everything the batches of one call read or write besides the graph (device pointers unless noted)
+struct BuildRun {
+    int ef = 0;
+    int64_t t_base = 0;                               // levels / pair_base are indexed from this node on
+    int64_t total_rows = 0;
+    const std::vector<int64_t> *pair_base = nullptr;  // host copy of pair_base_d
+    const int32_t *levels = nullptr;
+    const int64_t *pair_base_d = nullptr;
+    const uint32_t *pair_node = nullptr;
+    const int32_t *pair_level = nullptr;
+    uint32_t *vis = nullptr, *cand_ids = nullptr;
+    float *cand_d = nullptr;
+    int32_t *cand_n = nullptr;
+    uint32_t *rec_row = nullptr, *rec_t = nullptr, *srt_t = nullptr, *ord = nullptr, *work = nullptr, *roff = nullptr;
+    float *rec_d = nullptr, *srt_d = nullptr, *ordd = nullptr;
+    int32_t *rcnt = nullptr, *rfill = nullptr;  // zero on entry; the link kernel leaves them zero
+    LinkCounters *ctr = nullptr;
+    LinkTotals *totals = nullptr;  // VG_BUILD_DEBUG only
+    // vg_hnsw_insert (g.smap set): state rows of the rows existing before the call come from s_first + *s_next
+    unsigned int *s_next = nullptr, *derived = nullptr;
+    int64_t s_first = 0;
+    const float *l0_dist = nullptr;  // uploaded layer-0 edge distances of rows < dist_rows, or null
+    int64_t dist_rows = 0;
+    const float *cd0 = nullptr, *cdu = nullptr;  // the index's cached distances (layer 0, upper), or null
+};
+
+// The batches, in order: search -> select -> group the back links by target row -> (insert: derive the state of
+// target rows that have none) -> link.  vg_hnsw_build and vg_hnsw_insert both run their schedule through here.
+static int32_t run_batches(vg_ctx *ctx, hipStream_t st, const BuildGraph &g, const std::vector<BuildBatch> &batches,
+                           const BuildRun &r, const char *fn)
+{
+    const int ef = r.ef, m0 = g.m0;
+    const size_t lds = static_cast<size_t>(3 * ef + 4) * sizeof(HItem) + 128 * sizeof(float);
+    auto search_kern = g.metric != VG_METRIC_DOT ? build_search_kernel<true> : build_search_kernel<false>;
+    VG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(search_kern),
+                               hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
+    const bool debug = r.totals != nullptr;
+    auto dbg_t0 = std::chrono::steady_clock::now();
+    unsigned long long dbg_max_chain = 0;
+    const int64_t pb0 = (*r.pair_base)[0];
+    for (const BuildBatch &bt : batches) {
+        const int64_t vis_words = (bt.t0 + 31) / 32;  // only nodes below t0 are reachable
+        const int64_t nrec = bt.npairs * m0;
+        VG_HIP(hipMemsetAsync(r.vis, 0, static_cast<size_t>(bt.size * vis_words) * 4, st));
+        VG_HIP(hipMemsetAsync(r.ctr, 0, sizeof(LinkCounters), st));
+        {
+            ProfScope prof(ctx, "hnsw_build_search", st);
+            VG_LAUNCH(search_kern, dim3(static_cast<unsigned>(bt.size)), dim3(64), lds, st, g, bt.t0, r.t_base,
+                      bt.entry, bt.cur_top, r.levels, r.pair_base_d, ef, r.vis, vis_words, r.cand_ids,
+                      r.cand_d, r.cand_n);
+        }
+        const int64_t pb = (*r.pair_base)[bt.t0 - r.t_base] - pb0;
+        {
+            ProfScope prof(ctx, "hnsw_build_select", st);
+            VG_LAUNCH(build_select_kernel, dim3(static_cast<unsigned>(bt.npairs)), dim3(kSelThreads), 0, st, g, pb,
+                      r.pair_node + pb, r.pair_level + pb, ef, r.cand_ids, r.cand_d, r.cand_n, m0,
+                      r.rec_row, r.rec_t, r.rec_d);
+        }
+        const int64_t max_work = std::min(nrec, r.total_rows);
+        auto link = [&]() -> int32_t {
+            VG_LAUNCH(build_link_kernel, dim3(static_cast<unsigned>(max_work)), dim3(kLinkThreads), 0, st, g, r.work,
+                      r.ctr, r.rcnt, r.rfill, r.roff, r.srt_t, r.srt_d, r.ord, r.ordd, r.totals);
+            return VG_OK;
+        };
+        {
+            ProfScope prof(ctx, "hnsw_build_link", st);
+            const unsigned gb = static_cast<unsigned>((nrec + 255) / 256);
+            VG_LAUNCH(build_count_kernel, dim3(gb), dim3(256), 0, st, r.rec_row, nrec, r.rcnt, r.work, r.ctr);
+            VG_LAUNCH(build_offsets_kernel, dim3(static_cast<unsigned>((max_work + 255) / 256)), dim3(256), 0, st,
+                      r.work, r.rcnt, r.roff, r.ctr);
+            VG_LAUNCH(build_fill_kernel, dim3(gb), dim3(256), 0, st, r.rec_row, r.rec_t, r.rec_d, nrec,
+                      r.roff, r.rfill, r.srt_t, r.srt_d);
+            if (!g.smap) VG_TRY(link());
+        }
+        if (g.smap) {
+            {
+                ProfScope prof(ctx, "hnsw_insert_derive", st);
+                VG_LAUNCH(build_derive_kernel, dim3(static_cast<unsigned>(max_work)), dim3(kSelThreads), 0, st, g, r.work,
+                          r.ctr, r.s_next, r.s_first, r.l0_dist, r.dist_rows, r.cd0, r.cdu, r.derived);
+            }
+            ProfScope prof(ctx, "hnsw_build_link", st);
+            VG_TRY(link());
+        }
+        if (debug) {  // per-batch wall time and the batch's longest per-row chain (the chain is a running maximum: reset it)
+            VG_HIP(hipStreamSynchronize(st));
+            const auto now = std::chrono::steady_clock::now();
+            LinkTotals t{};
+            VG_HIP(hipMemcpy(&t, r.totals, sizeof(t), hipMemcpyDeviceToHost));
+            const size_t bi = static_cast<size_t>(&bt - batches.data());
+            if (bi % 16 == 0 || bi + 1 == batches.size())
+                fprintf(stderr, "%s: batch %zu: %lld nodes, %.2f ms, longest chain %llu; longest link workgroup %.2f ms "
+                                "(%llu records, %llu pruned, %llu heap replays)\n", fn, bi, static_cast<long long>(bt.size),
+                        std::chrono::duration<double, std::milli>(now - dbg_t0).count(), t.longest_chain, (t.max_wg >> 40) / 1e5,
+                        (t.max_wg >> 24) & 0xFFFF, (t.max_wg >> 8) & 0xFFFF, t.max_wg & 0xFF);
+            dbg_t0 = now;
+            dbg_max_chain = std::max(dbg_max_chain, t.longest_chain);
+            const unsigned long long zero = 0;
+            VG_HIP(hipMemcpy(&r.totals->longest_chain, &zero, sizeof(zero), hipMemcpyHostToDevice));
+            VG_HIP(hipMemcpy(&r.totals->max_wg, &zero, sizeof(zero), hipMemcpyHostToDevice));
+        }
+    }
+    VG_HIP(hipStreamSynchronize(st));
+    if (debug) {
+        LinkTotals t{};
+        VG_HIP(hipMemcpy(&t, r.totals, sizeof(t), hipMemcpyDeviceToHost));
+        fprintf(stderr, "%s: back links %llu = %llu skipped (farther than a fully chosen row's last member) + %llu appended + "
+                        "%llu pruned; target-row visits that found the row fully chosen %llu; longest per-row chain in one batch %llu\n",
+                fn, t.records, t.skipped, t.appended, t.pruned, t.good_rows_seen, std::max(dbg_max_chain, t.longest_chain));
+        fprintf(stderr, "%s: rows with >= 1000 back links in a batch: %llu visits, %llu records of which %llu applied; per visit "
+                        "%.1f us in all = sort %.1f + scan %.1f + gather %.1f + replay %.1f (us); heap replays (ties) %llu\n", fn,
+                t.hub_rows, t.hub_records, t.hub_applied,
+                t.hub_rows ? t.hub_total / 100.0 / t.hub_rows : 0.0, t.hub_rows ? t.hub_sort / 100.0 / t.hub_rows : 0.0,
+                t.hub_rows ? t.hub_scan / 100.0 / t.hub_rows : 0.0, t.hub_rows ? t.hub_gather / 100.0 / t.hub_rows : 0.0,
+                t.hub_rows ? t.hub_replay / 100.0 / t.hub_rows : 0.0, t.hub_ties);
+    }
+    return VG_OK;
+}
 
 }  // namespace vg
 
@@ -801,11 +1104,7 @@ VG_API int32_t vg_hnsw_build(vg_index *idx, int32_t m, int32_t ef_construction, 
     VG_CHECK(total_rows < (int64_t(1) << 32) - 1, VG_ERR_UNSUPPORTED, "vg_hnsw_build: too many rows");
     const int64_t total_slots = n * m0 + upper_rows * m;
 
-    struct Batch {
-        int64_t t0, size, npairs;
-        uint32_t entry;
-        int cur_top;
-    };
+    using Batch = vg::BuildBatch;
     std::vector<Batch> batches;
     std::vector<int64_t> pair_base(static_cast<size_t>(n) + 1, 0);
     std::vector<uint32_t> pair_node;
@@ -909,73 +1208,35 @@ VG_API int32_t vg_hnsw_build(vg_index *idx, int32_t m, int32_t ef_construction, 
     VG_HIP(hipMemcpyAsync(d_pair_level.p, pair_level.data(), pair_level.size() * 4, hipMemcpyHostToDevice, st));
     VG_HIP(hipStreamSynchronize(st));  // the host vectors above go out of use only at return, but be explicit
 
-    vg::BuildGraph g{idx->d_vectors, n, idx->dim, idx->metric, m0, m, d_ids.p, d_dist.p, d_bits.p, d_cnt.p, d_good.p,
-                     d_slots.p, d_level_off.p};
-    const size_t lds = static_cast<size_t>(3 * ef + 4) * sizeof(vg::HItem) + 128 * sizeof(float);
-    auto search_kern = idx->metric != VG_METRIC_DOT ? vg::build_search_kernel<true> : vg::build_search_kernel<false>;
-    VG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(search_kern),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
-    auto dbg_t0 = std::chrono::steady_clock::now();
-    unsigned long long dbg_max_chain = 0;
-    for (const Batch &bt : batches) {
-        const int64_t vis_words = (bt.t0 + 31) / 32;  // only nodes below t0 are reachable
-        const int64_t nrec = bt.npairs * m0;
-        VG_HIP(hipMemsetAsync(d_vis.p, 0, static_cast<size_t>(bt.size * vis_words) * 4, st));
-        VG_HIP(hipMemsetAsync(d_ctr.p, 0, sizeof(vg::LinkCounters), st));
-        {
-            vg::ProfScope prof(idx->ctx, "hnsw_build_search", st);
-            VG_LAUNCH(search_kern, dim3(static_cast<unsigned>(bt.size)), dim3(64), lds, st, g, bt.t0,
-                      bt.entry, bt.cur_top, d_levels.p, d_pair_base.p, ef, d_vis.p, vis_words, d_cand_ids.p,
-                      d_cand_d.p, d_cand_n.p);
-        }
-        const int64_t pb = pair_base[bt.t0];
-        {
-            vg::ProfScope prof(idx->ctx, "hnsw_build_select", st);
-            VG_LAUNCH(vg::build_select_kernel, dim3(static_cast<unsigned>(bt.npairs)), dim3(vg::kSelThreads), 0, st, g,
-                      d_pair_node.p + pb, d_pair_level.p + pb, ef, d_cand_ids.p, d_cand_d.p, d_cand_n.p, m0,
-                      d_rec_row.p, d_rec_t.p, d_rec_d.p);
-        }
-        vg::ProfScope prof(idx->ctx, "hnsw_build_link", st);
-        const unsigned gb = static_cast<unsigned>((nrec + 255) / 256);
-        VG_LAUNCH(vg::build_count_kernel, dim3(gb), dim3(256), 0, st, d_rec_row.p, nrec, d_rcnt.p, d_work.p, d_ctr.p);
-        const int64_t max_work = std::min(nrec, total_rows);
-        VG_LAUNCH(vg::build_offsets_kernel, dim3(static_cast<unsigned>((max_work + 255) / 256)), dim3(256), 0, st,
-                  d_work.p, d_rcnt.p, d_roff.p, d_ctr.p);
-        VG_LAUNCH(vg::build_fill_kernel, dim3(gb), dim3(256), 0, st, d_rec_row.p, d_rec_t.p, d_rec_d.p, nrec,
-                  d_roff.p, d_rfill.p, d_srt_t.p, d_srt_d.p);
-        VG_LAUNCH(vg::build_link_kernel, dim3(static_cast<unsigned>(max_work)), dim3(vg::kLinkThreads), 0, st, g, d_work.p,
-                  d_ctr.p, d_rcnt.p, d_rfill.p, d_roff.p, d_srt_t.p, d_srt_d.p, d_ord.p, d_ordd.p, debug ? d_totals.p : nullptr);
-        if (debug) {  // per-batch wall time and the batch's longest per-row chain (the chain is a running maximum: reset it)
-            VG_HIP(hipStreamSynchronize(st));
-            const auto now = std::chrono::steady_clock::now();
-            vg::LinkTotals t{};
-            VG_HIP(hipMemcpy(&t, d_totals.p, sizeof(t), hipMemcpyDeviceToHost));
-            const size_t bi = static_cast<size_t>(&bt - batches.data());
-            if (bi % 16 == 0 || bi + 1 == batches.size())
-                fprintf(stderr, "vg_hnsw_build: batch %zu: %lld nodes, %.2f ms, longest chain %llu; longest link workgroup %.2f ms "
-                                "(%llu records, %llu pruned, %llu heap replays)\n", bi, static_cast<long long>(bt.size),
-                        std::chrono::duration<double, std::milli>(now - dbg_t0).count(), t.longest_chain, (t.max_wg >> 40) / 1e5,
-                        (t.max_wg >> 24) & 0xFFFF, (t.max_wg >> 8) & 0xFFFF, t.max_wg & 0xFF);
-            dbg_t0 = now;
-            dbg_max_chain = std::max(dbg_max_chain, t.longest_chain);
-            const unsigned long long zero = 0;
-            VG_HIP(hipMemcpy(&d_totals.p->longest_chain, &zero, sizeof(zero), hipMemcpyHostToDevice));
-            VG_HIP(hipMemcpy(&d_totals.p->max_wg, &zero, sizeof(zero), hipMemcpyHostToDevice));
-        }
-    }
-    VG_HIP(hipStreamSynchronize(st));
-    if (debug) {
-        vg::LinkTotals t{};
-        VG_HIP(hipMemcpy(&t, d_totals.p, sizeof(t), hipMemcpyDeviceToHost));
-        fprintf(stderr, "vg_hnsw_build: back links %llu = %llu skipped (farther than a fully chosen row's last member) + %llu appended + "
-                        "%llu pruned; target-row visits that found the row fully chosen %llu; longest per-row chain in one batch %llu\n",
-                t.records, t.skipped, t.appended, t.pruned, t.good_rows_seen, std::max(dbg_max_chain, t.longest_chain));
-        fprintf(stderr, "vg_hnsw_build: rows with >= 1000 back links in a batch: %llu visits, %llu records of which %llu applied; per visit "
-                        "%.1f us in all = sort %.1f + scan %.1f + gather %.1f + replay %.1f (us); heap replays (ties) %llu\n", t.hub_rows, t.hub_records, t.hub_applied,
-                t.hub_rows ? t.hub_total / 100.0 / t.hub_rows : 0.0, t.hub_rows ? t.hub_sort / 100.0 / t.hub_rows : 0.0,
-                t.hub_rows ? t.hub_scan / 100.0 / t.hub_rows : 0.0, t.hub_rows ? t.hub_gather / 100.0 / t.hub_rows : 0.0,
-                t.hub_rows ? t.hub_replay / 100.0 / t.hub_rows : 0.0, t.hub_ties);
-    }
+    vg::BuildGraph g{idx->d_vectors, n, idx->dim, idx->metric, m0, m, d_ids.p, d_ids.p + n * m0, d_dist.p, d_bits.p,
+                     d_cnt.p, d_good.p, d_slots.p, d_level_off.p, nullptr, nullptr, nullptr};
+    vg::BuildRun run{};
+    run.ef = ef;
+    run.t_base = 0;
+    run.total_rows = total_rows;
+    run.pair_base = &pair_base;
+    run.levels = d_levels.p;
+    run.pair_base_d = d_pair_base.p;
+    run.pair_node = d_pair_node.p;
+    run.pair_level = d_pair_level.p;
+    run.vis = d_vis.p;
+    run.cand_ids = d_cand_ids.p;
+    run.cand_d = d_cand_d.p;
+    run.cand_n = d_cand_n.p;
+    run.rec_row = d_rec_row.p;
+    run.rec_t = d_rec_t.p;
+    run.rec_d = d_rec_d.p;
+    run.srt_t = d_srt_t.p;
+    run.srt_d = d_srt_d.p;
+    run.ord = d_ord.p;
+    run.ordd = d_ordd.p;
+    run.work = d_work.p;
+    run.roff = d_roff.p;
+    run.rcnt = d_rcnt.p;
+    run.rfill = d_rfill.p;
+    run.ctr = d_ctr.p;
+    run.totals = debug ? d_totals.p : nullptr;
+    VG_TRY(vg::run_batches(idx->ctx, st, g, batches, run, "vg_hnsw_build"));
 
     // hand the graph to the index in vg_index_set_hnsw_graph's layout
     uint32_t entry = 0;
@@ -988,12 +1249,19 @@ VG_API int32_t vg_hnsw_build(vg_index *idx, int32_t m, int32_t ef_construction, 
     // the new arrays are allocated and filled BEFORE the index lets go of its previous graph: an allocation that
     // fails here (the build's own scratch is still held) leaves the previous graph searchable, metadata and all
     vg::DevBuf<uint32_t> l0, adj;
+    vg::DevBuf<float> l0c, adjc;  // the cached distances, for vg_hnsw_insert
     VG_TRY(l0.alloc(static_cast<size_t>(n) * m0));
     VG_TRY(adj.alloc(static_cast<size_t>(upper_rows) * m));
+    VG_TRY(l0c.alloc(static_cast<size_t>(n) * m0));
+    VG_TRY(adjc.alloc(static_cast<size_t>(upper_rows) * m));
     VG_HIP(hipMemcpyAsync(l0.p, d_ids.p, static_cast<size_t>(n) * m0 * 4, hipMemcpyDeviceToDevice, st));
-    if (upper_rows)
+    VG_HIP(hipMemcpyAsync(l0c.p, d_dist.p, static_cast<size_t>(n) * m0 * 4, hipMemcpyDeviceToDevice, st));
+    if (upper_rows) {
         VG_HIP(hipMemcpyAsync(adj.p, d_ids.p + n * m0, static_cast<size_t>(upper_rows) * m * 4,
                               hipMemcpyDeviceToDevice, st));
+        VG_HIP(hipMemcpyAsync(adjc.p, d_dist.p + n * m0, static_cast<size_t>(upper_rows) * m * 4,
+                              hipMemcpyDeviceToDevice, st));
+    }
     VG_HIP(hipStreamSynchronize(st));
     for (uint32_t **slot : {&idx->d_hnsw_l0, &idx->d_hnsw_slot, &idx->d_hnsw_adj})
         if (*slot) {
@@ -1005,6 +1273,11 @@ VG_API int32_t vg_hnsw_build(vg_index *idx, int32_t m, int32_t ef_construction, 
         idx->d_hnsw_level_off = nullptr;
     }
     idx->d_hnsw_l0 = l0.release();
+    idx->l0_cap = 0;
+    for (float **c : {&idx->d_hnsw_l0_cdist, &idx->d_hnsw_adj_cdist})
+        if (*c) (void)hipFree(*c);
+    idx->d_hnsw_l0_cdist = l0c.release();
+    idx->d_hnsw_adj_cdist = adjc.release();
     if (idx->d_hnsw_l0_dist) {  // the old graph's edge distances
         (void)hipFree(idx->d_hnsw_l0_dist);
         idx->d_hnsw_l0_dist = nullptr;
@@ -1016,6 +1289,329 @@ VG_API int32_t vg_hnsw_build(vg_index *idx, int32_t m, int32_t ef_construction, 
     idx->hnsw_m = m;
     idx->hnsw_max_level = cur_top;
     idx->hnsw_entry = entry;
+    return VG_OK;
+}
+
+namespace vg {
+// room for n_new rows in a device array that holds n_old (its capacity: *cap rows, 0 = n_old), grown by half at
+// least so that a run of small inserts copies the array O(log n) times; bytes(r) = its size at r rows
+template <typename T, typename F>
+static int32_t grow_rows(T **p, int64_t *cap, int64_t n_old, int64_t n_new, F bytes, hipStream_t st)
+{
+    const int64_t have = std::max(*cap, n_old);
+    if (*p && n_new <= have) return VG_OK;
+    const int64_t want = std::max(n_new, have + have / 2);
+    T *q = nullptr;
+    VG_HIP(hipMalloc(reinterpret_cast<void **>(&q), std::max<size_t>(bytes(want), 1)));
+    if (*p && n_old) {
+        const hipError_t e = hipMemcpyAsync(q, *p, bytes(n_old), hipMemcpyDeviceToDevice, st);
+        if (e != hipSuccess) {
+            (void)hipFree(q);
+            VG_HIP(e);
+        }
+    }
+    VG_HIP(hipStreamSynchronize(st));
+    if (*p) (void)hipFree(*p);
+    *p = q;
+    *cap = want;
+    return VG_OK;
+}
+}  // namespace vg
+
+VG_API int32_t vg_hnsw_insert(vg_index *idx, const float *rows, int64_t count, int32_t m, int32_t ef_construction,
+                              int32_t max_batch, int32_t growth_div, void *stream)
+{
+    VG_CHECK(idx, VG_ERR_INVALID_ARG, "vg_hnsw_insert: NULL index");
+    VG_CHECK(count >= 0 && (count == 0 || rows), VG_ERR_INVALID_ARG, "vg_hnsw_insert: negative count or NULL rows");
+    const int64_t n_old = idx->n;
+    VG_CHECK(n_old == 0 || (idx->d_vectors && idx->d_hnsw_l0), VG_ERR_NOT_READY,
+             "vg_hnsw_insert: the index has rows but no HNSW graph (vg_hnsw_build first)");
+    VG_CHECK(idx->metric != VG_METRIC_HAMMING, VG_ERR_UNSUPPORTED, "unsupported metric for float32: Hamming");
+    VG_CHECK(m >= 2 && m <= 32, VG_ERR_UNSUPPORTED, "vg_hnsw_insert: M=%d must be in 2..32 (M0 = 2M <= 64)", m);
+    VG_CHECK(ef_construction >= 1 && ef_construction <= vg::kBuildMaxEf, VG_ERR_UNSUPPORTED,
+             "vg_hnsw_insert: ef_construction=%d must be in 1..%d", ef_construction, vg::kBuildMaxEf);
+    VG_CHECK(max_batch >= 1 && growth_div >= 1, VG_ERR_INVALID_ARG, "vg_hnsw_insert: max_batch and growth_div must be >= 1");
+    VG_CHECK(n_old + count < (int64_t(1) << 31), VG_ERR_UNSUPPORTED, "vg_hnsw_insert: at most 2^31 rows");
+    VG_CHECK(n_old == 0 || (m == idx->hnsw_m && idx->hnsw_m0 == 2 * m), VG_ERR_INVALID_ARG,
+             "vg_hnsw_insert: M=%d does not match the graph's (M=%d, M0=%d)", m, idx->hnsw_m, idx->hnsw_m0);
+    const char *held = (idx->d_pq_tiles || idx->d_pq_rows) ? "PQ codes"
+                       : idx->d_sq_tiles                   ? "SQ8 codes"
+                       : idx->d_int4_rows                  ? "INT4 codes"
+                       : (idx->d_rq_tiles || idx->d_rq_rows) ? "RaBitQ codes"
+                       : idx->d_centroids                  ? "IVF partitions"
+                       : idx->d_vamana                     ? "a Vamana graph"
+                       : idx->d_sq_bf16                    ? "an SQ8 nomination image"
+                       : idx->d_pq_bf16                    ? "a PQ nomination image"
+                                                           : nullptr;
+    VG_CHECK(!held, VG_ERR_UNSUPPORTED, "vg_hnsw_insert: the index holds %s, which the new rows would lack (segment state, "
+             "not a memtable's)", held);
+    if (count == 0) return VG_OK;
+    VG_HIP(hipSetDevice(idx->ctx->device));
+    hipStream_t st = vg::pick_stream(idx->ctx, stream);
+    const int64_t n_new = n_old + count;
+    const int dim = idx->dim;
+    const int m0 = 2 * m;
+    const int ef = ef_construction;
+
+    // ---- the plan: levels, slots of the new nodes, batches (host) ----
+    const double mult = 1.0 / std::log(static_cast<double>(m));
+    std::vector<int32_t> levels(static_cast<size_t>(count));
+    int new_top = 0;
+    for (int64_t i = 0; i < count; i++) {
+        levels[i] = vg::level_for_id(static_cast<uint64_t>(n_old + i), mult);
+        new_top = std::max(new_top, levels[i]);
+    }
+    const int l_old = n_old ? idx->hnsw_max_level : 0;
+    std::vector<int64_t> old_off(static_cast<size_t>(l_old) + 1, 0);
+    if (l_old > 0) {
+        VG_HIP(hipMemcpyAsync(old_off.data(), idx->d_hnsw_level_off, old_off.size() * 8, hipMemcpyDeviceToHost, st));
+        VG_HIP(hipStreamSynchronize(st));
+    }
+    const int l_new = std::max(l_old, new_top);
+    // new nodes' upper rows go at the end of each level's table (slots in id order: a full build's layout)
+    std::vector<int64_t> new_off(static_cast<size_t>(l_new) + 1, 0);
+    std::vector<uint32_t> fresh(static_cast<size_t>(l_new) * count);
+    for (int l = 0; l < l_new; l++) {
+        uint32_t next = static_cast<uint32_t>(l < l_old ? old_off[l + 1] - old_off[l] : 0);
+        for (int64_t i = 0; i < count; i++) fresh[static_cast<size_t>(l) * count + i] = levels[i] >= l + 1 ? next++ : VG_INVALID_ID;
+        new_off[l + 1] = new_off[l] + next;
+    }
+    const int64_t upper_rows = new_off[l_new];
+    const int64_t total_rows = n_new + upper_rows;
+    VG_CHECK(total_rows < (int64_t(1) << 32) - 1, VG_ERR_UNSUPPORTED, "vg_hnsw_insert: too many rows");
+
+    using Batch = vg::BuildBatch;
+    std::vector<Batch> batches;
+    std::vector<int64_t> pair_base(static_cast<size_t>(count) + 1, 0);  // node t: pair_base[t - n_old]
+    uint32_t entry = n_old ? idx->hnsw_entry : 0;
+    int cur_top = n_old ? l_old : levels[0];
+    {
+        int64_t done = n_old ? n_old : 1;  // an empty graph: row 0 becomes the entry point, with no links
+        while (done < n_new) {
+            int64_t b = done / growth_div;
+            b = std::max<int64_t>(1, std::min<int64_t>(b, max_batch));
+            b = std::min(b, n_new - done);
+            Batch bt{done, b, 0, entry, cur_top};
+            for (int64_t t = done; t < done + b; t++) {
+                const int np = std::min(levels[t - n_old], cur_top) + 1;
+                pair_base[t - n_old + 1] = pair_base[t - n_old] + np;
+                bt.npairs += np;
+            }
+            for (int64_t t = done; t < done + b; t++)  // updateEntryPoint hnsw.go:885-900
+                if (levels[t - n_old] > cur_top) {
+                    cur_top = levels[t - n_old];
+                    entry = static_cast<uint32_t>(t);
+                }
+            batches.push_back(bt);
+            done += b;
+        }
+    }
+    const int64_t npairs = pair_base[count];
+    std::vector<uint32_t> pair_node(static_cast<size_t>(std::max<int64_t>(npairs, 1)));
+    std::vector<int32_t> pair_level(pair_node.size());
+    for (const Batch &bt : batches)
+        for (int64_t t = bt.t0; t < bt.t0 + bt.size; t++)
+            for (int l = 0; l <= std::min(levels[t - n_old], bt.cur_top); l++) {
+                pair_node[static_cast<size_t>(pair_base[t - n_old] + l)] = static_cast<uint32_t>(t);
+                pair_level[static_cast<size_t>(pair_base[t - n_old] + l)] = l;
+            }
+    int64_t max_pairs = 1, max_b = 1;
+    for (const auto &bt : batches) {
+        max_pairs = std::max(max_pairs, bt.npairs);
+        max_b = std::max(max_b, bt.size);
+    }
+    const int64_t vis_words_max = (n_new + 31) / 32;
+    VG_CHECK(max_b * vis_words_max * 4 <= (int64_t(1) << 32), VG_ERR_UNSUPPORTED,
+             "vg_hnsw_insert: max_batch=%d needs more than 4 GiB of visited bitmaps at %lld rows", max_batch,
+             static_cast<long long>(n_new));
+    // state rows: one per new (node, level) pair, then one per derived row.  A row is derived at most once per call
+    // and only when a record targets it: at most one per record, at most one per row.  (Derived rows are the graph's
+    // older rows and the rows a new node gets above the top level of its batch, which no pair makes.)
+    const int64_t n_state = npairs + std::min(total_rows, npairs * m0);
+
+    // ---- the rows and everything sized by n ----
+    vg::DevIn<float> in;
+    VG_TRY(in.init(rows, static_cast<size_t>(count) * dim, st));
+    if (!idx->d_norm_max) {
+        VG_HIP(hipMalloc(reinterpret_cast<void **>(&idx->d_norm_max), 2 * sizeof(float)));
+        VG_HIP(hipMemsetAsync(idx->d_norm_max, 0, 2 * sizeof(float), st));
+    }
+    if (!idx->d_flat_stats) {
+        VG_HIP(hipMalloc(reinterpret_cast<void **>(&idx->d_flat_stats), 2 * sizeof(unsigned long long)));
+        VG_HIP(hipMemsetAsync(idx->d_flat_stats, 0, 2 * sizeof(unsigned long long), st));
+    }
+    {
+        int64_t cap = idx->rows_cap;
+        VG_TRY(vg::grow_rows(&idx->d_norms, &cap, n_old, n_new, [](int64_t r) { return static_cast<size_t>(r) * 4; }, st));
+        int64_t cap_v = idx->rows_cap;
+        VG_TRY(vg::grow_rows(&idx->d_vectors, &cap_v, n_old, n_new,
+                             [&](int64_t r) { return static_cast<size_t>(r) * dim * 4; }, st));
+        idx->rows_cap = std::min(cap, cap_v);
+    }
+    VG_HIP(hipMemcpyAsync(idx->d_vectors + n_old * dim, in.ptr, static_cast<size_t>(count) * dim * 4, hipMemcpyDeviceToDevice, st));
+    VG_TRY(vg::append_row_norms(idx, n_old, n_new, st));
+    if (idx->d_vectors_bf16) {
+        const int64_t bd = idx->vectors_bf16_dim;
+        VG_TRY(vg::grow_rows(&idx->d_vectors_bf16, &idx->bf16_cap, n_old, n_new,
+                             [&](int64_t r) { return static_cast<size_t>(r) * bd * 2; }, st));
+        VG_TRY(vg::append_bf16_rows(idx, n_old, n_new, st));
+    }
+    if (idx->d_hnsw_tomb) {  // the new rows are live
+        VG_TRY(vg::grow_rows(&idx->d_hnsw_tomb, &idx->tomb_cap, n_old, n_new,
+                             [](int64_t r) { return static_cast<size_t>((r + 7) / 8); }, st));
+        const int64_t bytes = (n_new + 7) / 8 - n_old / 8;
+        VG_LAUNCH(vg::clear_bits_kernel, dim3(static_cast<unsigned>((bytes + 255) / 256)), dim3(256), 0, st, idx->d_hnsw_tomb,
+                  n_old, n_new);
+    }
+    // the cached distances go on with the graph when the index has them (a graph it built), or the call starts the graph
+    const bool keep_cd = n_old == 0 || (idx->d_hnsw_l0_cdist && (l_old == 0 || idx->d_hnsw_adj_cdist));
+    {
+        int64_t cap = idx->l0_cap, cap_c = idx->l0_cap;
+        VG_TRY(vg::grow_rows(&idx->d_hnsw_l0, &cap, n_old, n_new, [&](int64_t r) { return static_cast<size_t>(r) * m0 * 4; }, st));
+        if (keep_cd)
+            VG_TRY(vg::grow_rows(&idx->d_hnsw_l0_cdist, &cap_c, n_old, n_new,
+                                 [&](int64_t r) { return static_cast<size_t>(r) * m0 * 4; }, st));
+        idx->l0_cap = keep_cd ? std::min(cap, cap_c) : cap;
+    }
+    VG_HIP(hipMemsetAsync(idx->d_hnsw_l0 + n_old * m0, 0xFF, static_cast<size_t>(count) * m0 * 4, st));
+
+    // ---- the upper levels re-laid for n_new nodes (the index's, swapped in at the end) ----
+    vg::DevBuf<uint32_t> slots, adj;
+    vg::DevBuf<float> adjc;
+    vg::DevBuf<int64_t> level_off;
+    VG_TRY(slots.alloc(static_cast<size_t>(l_new) * n_new));
+    VG_TRY(adj.alloc(static_cast<size_t>(upper_rows) * m));
+    if (keep_cd) VG_TRY(adjc.alloc(static_cast<size_t>(upper_rows) * m));
+    VG_TRY(level_off.alloc(new_off.size()));
+    VG_HIP(hipMemcpyAsync(level_off.p, new_off.data(), new_off.size() * 8, hipMemcpyHostToDevice, st));
+    VG_HIP(hipMemsetAsync(adj.p, 0xFF, static_cast<size_t>(upper_rows) * m * 4, st));
+    for (int l = 0; l < l_old; l++)
+        if (old_off[l + 1] > old_off[l]) {
+            VG_HIP(hipMemcpyAsync(adj.p + new_off[l] * m, idx->d_hnsw_adj + old_off[l] * m,
+                                  static_cast<size_t>(old_off[l + 1] - old_off[l]) * m * 4, hipMemcpyDeviceToDevice, st));
+            if (keep_cd)
+                VG_HIP(hipMemcpyAsync(adjc.p + new_off[l] * m, idx->d_hnsw_adj_cdist + old_off[l] * m,
+                                      static_cast<size_t>(old_off[l + 1] - old_off[l]) * m * 4, hipMemcpyDeviceToDevice, st));
+        }
+
+    // ---- per-call scratch: the batches' buffers, sized by the call's largest batch, and the state rows ----
+    const int64_t max_rec = max_pairs * m0;
+    vg::ArenaCall ar(idx->ctx, st);
+    const int a_fresh = ar.add(fresh.size() * 4 + 4), a_lev = ar.add(levels.size() * 4), a_pb = ar.add(pair_base.size() * 8),
+              a_pn = ar.add(pair_node.size() * 4), a_pl = ar.add(pair_level.size() * 4),
+              a_vis = ar.add(static_cast<size_t>(max_b * vis_words_max) * 4),
+              a_cid = ar.add(static_cast<size_t>(max_pairs) * ef * 4), a_cd = ar.add(static_cast<size_t>(max_pairs) * ef * 4),
+              a_cn = ar.add(static_cast<size_t>(max_pairs) * 4), a_rr = ar.add(static_cast<size_t>(max_rec) * 4),
+              a_rt = ar.add(static_cast<size_t>(max_rec) * 4), a_rd = ar.add(static_cast<size_t>(max_rec) * 4),
+              a_st = ar.add(static_cast<size_t>(max_rec) * 4), a_sd = ar.add(static_cast<size_t>(max_rec) * 4),
+              a_or = ar.add(static_cast<size_t>(max_rec) * 4), a_od = ar.add(static_cast<size_t>(max_rec) * 4),
+              a_work = ar.add(static_cast<size_t>(std::min(max_rec, total_rows)) * 4),
+              a_roff = ar.add(static_cast<size_t>(total_rows) * 4), a_rcnt = ar.add(static_cast<size_t>(total_rows) * 4),
+              a_rfill = ar.add(static_cast<size_t>(total_rows) * 4), a_smap = ar.add(static_cast<size_t>(total_rows) * 4),
+              a_rnode = ar.add(static_cast<size_t>(total_rows) * 4), a_srow = ar.add(static_cast<size_t>(n_state) * 4),
+              a_dist = ar.add(static_cast<size_t>(n_state) * vg::kStateStride * 4),
+              a_bits = ar.add(static_cast<size_t>(n_state) * vg::kStateStride * 8), a_cnt = ar.add(static_cast<size_t>(n_state) * 4),
+              a_good = ar.add(static_cast<size_t>(n_state)), a_ctr = ar.add(sizeof(vg::LinkCounters)),
+              a_tot = ar.add(sizeof(vg::LinkTotals)), a_next = ar.add(8);
+    VG_TRY(ar.commit());
+    uint32_t *d_fresh = ar.get<uint32_t>(a_fresh);
+    VG_HIP(hipMemcpyAsync(d_fresh, fresh.data(), fresh.size() * 4, hipMemcpyHostToDevice, st));
+    if (l_new > 0) {
+        const int64_t e = static_cast<int64_t>(l_new) * n_new;
+        VG_LAUNCH(vg::slot_relayout_kernel, dim3(static_cast<unsigned>((e + 255) / 256)), dim3(256), 0, st, idx->d_hnsw_slot,
+                  n_old, l_old, d_fresh, n_new, l_new, slots.p);
+    }
+    vg::BuildRun run{};
+    run.ef = ef;
+    run.t_base = n_old;
+    run.total_rows = total_rows;
+    run.pair_base = &pair_base;
+    run.levels = ar.get<int32_t>(a_lev);
+    run.pair_base_d = ar.get<int64_t>(a_pb);
+    run.pair_node = ar.get<uint32_t>(a_pn);
+    run.pair_level = ar.get<int32_t>(a_pl);
+    run.vis = ar.get<uint32_t>(a_vis);
+    run.cand_ids = ar.get<uint32_t>(a_cid);
+    run.cand_d = ar.get<float>(a_cd);
+    run.cand_n = ar.get<int32_t>(a_cn);
+    run.rec_row = ar.get<uint32_t>(a_rr);
+    run.rec_t = ar.get<uint32_t>(a_rt);
+    run.rec_d = ar.get<float>(a_rd);
+    run.srt_t = ar.get<uint32_t>(a_st);
+    run.srt_d = ar.get<float>(a_sd);
+    run.ord = ar.get<uint32_t>(a_or);
+    run.ordd = ar.get<float>(a_od);
+    run.work = ar.get<uint32_t>(a_work);
+    run.roff = ar.get<uint32_t>(a_roff);
+    run.rcnt = ar.get<int32_t>(a_rcnt);
+    run.rfill = ar.get<int32_t>(a_rfill);
+    run.ctr = ar.get<vg::LinkCounters>(a_ctr);
+    run.totals = vg::hook(vg::kHookBuildDebug) ? ar.get<vg::LinkTotals>(a_tot) : nullptr;
+    run.s_next = ar.get<unsigned int>(a_next);
+    run.derived = run.s_next + 1;
+    run.s_first = npairs;
+    run.l0_dist = idx->d_hnsw_l0_dist;
+    run.dist_rows = idx->d_hnsw_l0_dist ? n_old : 0;
+    run.cd0 = keep_cd ? idx->d_hnsw_l0_cdist : nullptr;
+    run.cdu = keep_cd ? adjc.p : nullptr;
+    VG_HIP(hipMemcpyAsync(const_cast<int32_t *>(run.levels), levels.data(), levels.size() * 4, hipMemcpyHostToDevice, st));
+    VG_HIP(hipMemcpyAsync(const_cast<int64_t *>(run.pair_base_d), pair_base.data(), pair_base.size() * 8, hipMemcpyHostToDevice, st));
+    VG_HIP(hipMemcpyAsync(const_cast<uint32_t *>(run.pair_node), pair_node.data(), pair_node.size() * 4, hipMemcpyHostToDevice, st));
+    VG_HIP(hipMemcpyAsync(const_cast<int32_t *>(run.pair_level), pair_level.data(), pair_level.size() * 4, hipMemcpyHostToDevice, st));
+    VG_HIP(hipMemsetAsync(run.rcnt, 0, static_cast<size_t>(total_rows) * 4, st));
+    VG_HIP(hipMemsetAsync(run.rfill, 0, static_cast<size_t>(total_rows) * 4, st));
+    int32_t *smap = ar.get<int32_t>(a_smap);
+    VG_HIP(hipMemsetAsync(smap, 0xFF, static_cast<size_t>(total_rows) * 4, st));
+    VG_HIP(hipMemsetAsync(run.s_next, 0, 8, st));
+    if (run.totals) VG_HIP(hipMemsetAsync(run.totals, 0, sizeof(vg::LinkTotals), st));
+    vg::BuildGraph g{idx->d_vectors, n_new, dim, idx->metric, m0, m, idx->d_hnsw_l0, adj.p,
+                     ar.get<float>(a_dist), ar.get<uint64_t>(a_bits), ar.get<int32_t>(a_cnt), ar.get<uint8_t>(a_good),
+                     slots.p, level_off.p, smap, ar.get<uint32_t>(a_srow), ar.get<uint32_t>(a_rnode)};
+    VG_TRY(vg::run_batches(idx->ctx, st, g, batches, run, "vg_hnsw_insert"));
+    if (keep_cd && n_state > 0) {
+        VG_LAUNCH(vg::state_writeback_kernel, dim3(static_cast<unsigned>(n_state)), dim3(64), 0, st, g, run.s_next, npairs,
+                  idx->d_hnsw_l0_cdist, adjc.p);
+        VG_HIP(hipStreamSynchronize(st));
+    }
+    if (run.totals) {
+        unsigned int h[2] = {0, 0};
+        VG_HIP(hipMemcpy(h, run.s_next, sizeof h, hipMemcpyDeviceToHost));
+        fprintf(stderr, "vg_hnsw_insert: %lld rows, %lld batches, %u rows' build state derived\n", static_cast<long long>(count),
+                static_cast<long long>(batches.size()), h[1]);
+    }
+
+    // ---- hand over: the layer-0 table was grown in place; the upper levels are swapped in ----
+    for (uint32_t **slot : {&idx->d_hnsw_slot, &idx->d_hnsw_adj})
+        if (*slot) {
+            (void)hipFree(*slot);
+            *slot = nullptr;
+        }
+    if (idx->d_hnsw_level_off) {
+        (void)hipFree(idx->d_hnsw_level_off);
+        idx->d_hnsw_level_off = nullptr;
+    }
+    if (idx->d_hnsw_l0_dist) {  // cached for the old lists: the predicate-aware walk recomputes them (same values)
+        (void)hipFree(idx->d_hnsw_l0_dist);
+        idx->d_hnsw_l0_dist = nullptr;
+    }
+    idx->d_hnsw_slot = slots.release();
+    idx->d_hnsw_adj = adj.release();
+    idx->d_hnsw_level_off = level_off.release();
+    if (idx->d_hnsw_adj_cdist) {
+        (void)hipFree(idx->d_hnsw_adj_cdist);
+        idx->d_hnsw_adj_cdist = nullptr;
+    }
+    if (keep_cd)
+        idx->d_hnsw_adj_cdist = adjc.release();
+    else if (idx->d_hnsw_l0_cdist) {
+        (void)hipFree(idx->d_hnsw_l0_cdist);
+        idx->d_hnsw_l0_cdist = nullptr;
+    }
+    idx->hnsw_m0 = m0;
+    idx->hnsw_m = m;
+    idx->hnsw_max_level = cur_top;
+    idx->hnsw_entry = entry;
+    idx->n = n_new;
     return VG_OK;
 }
 

@@ -267,6 +267,7 @@ VG_API int32_t vg_index_set_hnsw_tombstones(vg_index *idx, const uint8_t *delete
         VG_HIP(hipFree(idx->d_hnsw_tomb));
         idx->d_hnsw_tomb = nullptr;
     }
+    idx->tomb_cap = 0;
     const size_t bytes = static_cast<size_t>((idx->n + 7) / 8);
     if (deleted == nullptr || bytes == 0) return VG_OK;
     uint8_t *d = nullptr;

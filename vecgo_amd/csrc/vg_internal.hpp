@@ -14,6 +14,8 @@
 
 #include "../../include/vecgo_hip.h"
 
+struct vg_index;
+
 #define VG_API extern "C" __attribute__((visibility("default")))
 
 namespace vg {
@@ -100,6 +102,10 @@ bool hook(Hook h);
 // dropped: on ROCm 7.2 / gfx950 a block it recycled after a pool trim came back zero-filled
 // after the copy into it had completed — see DESIGN.md "Scratch memory".)
 int32_t scratch_alloc(void **out, size_t bytes, hipStream_t s);
+// Rows appended to a resident index (vg_hnsw_insert): ||x||^2 and max |x| of rows from .. to-1 of d_vectors
+// folded into d_norms / d_norm_max (k_exact.hip); their bfloat16 filter image (k_flat.hip)
+int32_t append_row_norms(vg_index *idx, int64_t from, int64_t to, hipStream_t st);
+int32_t append_bf16_rows(vg_index *idx, int64_t from, int64_t to, hipStream_t st);
 void scratch_free(void *p);
 void scratch_trim(int device);
 
@@ -368,12 +374,18 @@ struct vg_index {
     // HNSW adjacency
     uint32_t *d_hnsw_l0 = nullptr;     // n*m0
     float *d_hnsw_l0_dist = nullptr;   // n*m0 cached edge distances (Neighbor.Dist) for the predicate-aware walk, or null
+    // the distances a GPU-built graph cached per slot as its inserts computed them (layer 0: like d_hnsw_l0, upper levels:
+    // like d_hnsw_adj), kept by vg_hnsw_build / vg_hnsw_insert for the next vg_hnsw_insert; null for an uploaded graph
+    float *d_hnsw_l0_cdist = nullptr, *d_hnsw_adj_cdist = nullptr;
     uint8_t *d_hnsw_tomb = nullptr;    // g.tombstones as a bitmap (ceil(n/8) bytes), or null: no deleted node
     uint32_t *d_hnsw_slot = nullptr;   // max_level*n
     uint32_t *d_hnsw_adj = nullptr;    // concatenated level tables
     int64_t *d_hnsw_level_off = nullptr;  // max_level+1 row offsets into d_hnsw_adj (in rows)
     int32_t hnsw_m0 = 0, hnsw_m = 0, hnsw_max_level = 0;
     uint32_t hnsw_entry = 0;
+    // rows that d_vectors / d_norms, d_vectors_bf16, d_hnsw_l0 and d_hnsw_tomb have room for: vg_hnsw_insert grows
+    // them by capacity; 0 = exactly n (every other entry point allocates them at n and resets these)
+    int64_t rows_cap = 0, bf16_cap = 0, l0_cap = 0, tomb_cap = 0;
     // Vamana adjacency
     uint32_t *d_vamana = nullptr;      // n*r
     int32_t vamana_r = 0;
