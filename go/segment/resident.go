@@ -492,6 +492,43 @@ func (r *Resident) SearchVamanaFiltered(queries []float32, nq, k, kind int, mask
 	return ids, sc, hipctx.Err(int32(st))
 }
 
+// SearchVamanaThreshold: the DiskANN leg of Engine.SearchThreshold (engine/engine.go:1485-1531): SearchVamanaFiltered(q,
+// maxResults), then the rows with Score <= thresholds[q] (L2) / >= thresholds[q] (Dot, Cosine) in walk order.  Query q's rows
+// are ids/scores[q*maxResults : q*maxResults+counts[q]].  mask nil = no filter, else as for SearchVamanaFiltered.
+// maxResults <= 16384.
+func (r *Resident) SearchVamanaThreshold(queries []float32, nq int, thresholds []float32, maxResults, kind int, mask []byte, maskStride int, stats []Stats) ([]uint32, []float32, []int32, error) {
+	if len(thresholds) < nq {
+		return nil, nil, nil, fmt.Errorf("SearchVamanaThreshold: %d thresholds for %d queries", len(thresholds), nq)
+	}
+	if nq == 0 || maxResults == 0 {
+		return nil, nil, make([]int32, nq), nil
+	}
+	if mask != nil {
+		need := (r.rows + 7) / 8
+		if maskStride != 0 {
+			if maskStride < need {
+				return nil, nil, nil, fmt.Errorf("SearchVamanaThreshold: maskStride %d is shorter than a mask (%d bytes)", maskStride, need)
+			}
+			need += (nq - 1) * maskStride
+		}
+		if len(mask) < need {
+			return nil, nil, nil, fmt.Errorf("SearchVamanaThreshold: mask holds %d bytes, %d needed", len(mask), need)
+		}
+	}
+	ids, sc := r.out(nq, maxResults)
+	counts := make([]int32, nq)
+	var sp *C.vg_search_stats
+	if len(stats) >= nq {
+		sp = (*C.vg_search_stats)(unsafe.Pointer(&stats[0]))
+	}
+	var mp *C.uint8_t
+	if mask != nil {
+		mp = bp(mask)
+	}
+	st := C.vg_search_vamana_threshold(r.h, fp(queries), C.int64_t(nq), fp(thresholds), C.int32_t(maxResults), C.int32_t(kind), mp, C.int64_t(maskStride), up(ids), fp(sc), ip(counts), sp, nil)
+	return ids, sc, counts, hipctx.Err(int32(st))
+}
+
 // Rerank: Segment.Rerank + top-k (flat/segment.go:754-780, engine/search.go:914-965): nc candidate rows per query.
 func (r *Resident) Rerank(queries []float32, nq int, candidates []uint32, nc, k int) ([]uint32, []float32, error) {
 	ids, sc := r.out(nq, k)

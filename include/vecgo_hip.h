@@ -58,7 +58,10 @@ extern "C" {
  *  10: (r06) vg_index_enable_pq_nomination; NaN scores answered as the reference's heaps answer them (see "NaN scores")
  *  11: vg_search_flat_threshold
  *  12: vg_vamana_build, vg_index_get_vamana_graph
- *  13: vg_hnsw_insert */
+ *  13: vg_hnsw_insert
+ *  Added at minor 13 without a bump (the minor-13 header test pins the value): vg_search_vamana_threshold, and
+ *  vg_search_vamana / _filtered take k up to 16384 (512 before).  A binding that needs them looks the symbol
+ *  vg_search_vamana_threshold up (dlsym) instead of comparing the minor; the next bump covers them. */
 #define VG_ABI_MINOR 13
 #define VG_INVALID_ID 0xFFFFFFFFu
 #define VG_STREAM_LEGACY ((void *)1) /* == hipStreamLegacy */
@@ -662,7 +665,7 @@ uint32_t vg_crc32c(const void *data, int64_t size);
 
 /* per-query counters, the reference's FilterGateStats (searcher/searcher.go:114-137).  vg_search_vamana has
  * no short-circuit path; it reports in distance_short_circuits the candidates it could NOT push because the
- * per-query exploration heap (min(rows, 65536) entries; the reference's is unbounded) was full — 0 in every
+ * per-query exploration heap (min(rows, 65536) entries for k <= 512 unfiltered, rows otherwise; the reference's is unbounded) was full — 0 in every
  * search that followed the reference exactly. */
 typedef struct vg_search_stats {
     int64_t nodes_visited, distance_computations, distance_short_circuits, pops;
@@ -733,7 +736,13 @@ int32_t vg_search_hnsw_pq(vg_index *idx, const float *queries, int64_t nq, int32
  * ComputeAsymmetricDistance (:536-541, terms summed sequentially over the sub-quantizers),
  * 2 = RaBitQ Distance (:512-519), 3 = INT4 L2Distance (:558-565).  Unbounded exploration
  * min-heap, top-k CandidateHeap,
- * stop when the popped candidate is worse than the k-th result.  k <= 512. */
+ * stop when the popped candidate is worse than the k-th result.  k <= 16384; k is the only knob of how far the walk goes
+ * (RefineFactor's searchK = k * RefineFactor, engine/search.go:192, and SearchThreshold's maxResults reach it as k).
+ * k <= 512 runs the kernels it always ran (the k best in registers, or a sorted LDS list above 64; exploration heap of
+ * min(rows, 65536) items).  512 < k <= 16384: the k best are a 64-ary max-heap of (score, id) keys (the top 449 in LDS,
+ * the rest in HBM), the exploration heap holds every row (nothing is ever dropped), and the k keys are sorted once at the
+ * end; a query whose scores may hold a NaN replays CandidateHeap with k items in LDS.  Same ids, score bits, order and
+ * counters as the reference at every k.  k > 16384: VG_ERR_UNSUPPORTED. */
 int32_t vg_search_vamana(vg_index *idx, const float *queries, int64_t nq, int32_t k, int32_t kind,
                          uint32_t *ids, float *scores, vg_search_stats *stats, void *stream);
 /* The same with `filter segment.Filter` set: pushToHeap (diskann/segment.go:616-627) returns before TryPushBounded for a row
@@ -744,6 +753,17 @@ int32_t vg_search_vamana(vg_index *idx, const float *queries, int64_t nq, int32_
 int32_t vg_search_vamana_filtered(vg_index *idx, const float *queries, int64_t nq, int32_t k, int32_t kind,
                                   const uint8_t *mask, int64_t mask_stride, uint32_t *ids, float *scores,
                                   vg_search_stats *stats, void *stream);
+/* Engine.SearchThreshold's DiskANN leg (engine/engine.go:1485-1531): per query vg_search_vamana_filtered(q, k =
+ * max_results) — the walk runs with the full k, the threshold prunes nothing — then the engine's filter (:1518-1529):
+ * Score <= thresholds[q] for L2, Score >= thresholds[q] for Dot and Cosine, by the index's metric even for the code scorers
+ * (whose scores are L2-type distances), as the engine compares.  The boundary is kept; a NaN threshold keeps nothing, a NaN
+ * score is dropped.  The kept rows stay in walk order, compacted to the front; counts[q] = rows kept; the other slots hold
+ * VG_INVALID_ID and +Inf (L2) / -Inf (Dot, Cosine).  thresholds: one per query; mask / mask_stride as for
+ * vg_search_vamana_filtered (NULL = none); stats as for vg_search_vamana (may be NULL).  nq == 0 or max_results == 0:
+ * nothing is written.  max_results > 16384: VG_ERR_UNSUPPORTED.  Pointers may be host or device.  (Present when the symbol is: see VG_ABI_MINOR.) */
+int32_t vg_search_vamana_threshold(vg_index *idx, const float *queries, int64_t nq, const float *thresholds,
+                                   int32_t max_results, int32_t kind, const uint8_t *mask, int64_t mask_stride,
+                                   uint32_t *ids, float *scores, int32_t *counts, vg_search_stats *stats, void *stream);
 
 /* The HNSW index's two EXHAUSTIVE paths, each with the heap it is written with (searcher/queue.go) — which ids
  * survive a tie at the k-th distance and the order of equal distances in the result follow from the heap's layout,

@@ -676,6 +676,19 @@ public:
     // searchInternal with a row filter (diskann/segment.go:616-627): mask bit i of byte i/8 = filter.Matches(i)
     Result SearchVamanaFiltered(const float *queries, int64_t nq, int k, int kind, const uint8_t *mask, int64_t mask_stride) { return run(nq, k, [&](Result &r) { return vg_search_vamana_filtered(h_, queries, nq, k, kind, mask, mask_stride, r.ids.data(), r.scores.data(), nullptr, nullptr); }); }
     Result SearchVamana(const float *queries, int64_t nq, int k, int kind) { return run(nq, k, [&](Result &r) { return vg_search_vamana(h_, queries, nq, k, kind, r.ids.data(), r.scores.data(), nullptr, nullptr); }); }
+    // Engine.SearchThreshold's DiskANN leg (engine/engine.go:1485-1531): SearchVamanaFiltered(q, max_results), then the rows within
+    // thresholds[q] (<= for L2, >= for Dot / Cosine) in walk order; mask = nullptr: no filter.  max_results <= 16384
+    ThresholdResult SearchVamanaThreshold(const float *queries, int64_t nq, const float *thresholds, int max_results, int kind,
+                                          const uint8_t *mask = nullptr, int64_t mask_stride = 0)
+    {
+        ThresholdResult r;
+        r.ids.resize(static_cast<size_t>(nq) * max_results);
+        r.scores.resize(static_cast<size_t>(nq) * max_results);
+        r.counts.resize(static_cast<size_t>(nq));
+        check(vg_search_vamana_threshold(h_, queries, nq, thresholds, max_results, kind, mask, mask_stride, r.ids.data(),
+                                         r.scores.data(), r.counts.data(), nullptr, nullptr));
+        return r;
+    }
     // Segment.Rerank (flat/segment.go:754-780) + top-k
     Result Rerank(const float *queries, int64_t nq, const uint32_t *cand, int nc, int k) { return run(nq, k, [&](Result &r) { return vg_rerank(h_, queries, nq, cand, nc, k, r.ids.data(), r.scores.data(), nullptr); }); }
 

@@ -1230,6 +1230,40 @@ class Index:
             st = st[:, :4]
         return (ids, scores, st) if stats else (ids, scores)
 
+    def search_vamana_threshold(self, queries, thresholds, max_results, kind=0, mask=None, stats=False, stream=None):
+        """Engine.SearchThreshold's DiskANN leg (engine/engine.go:1485-1531): search_vamana_filtered(q, max_results), then the rows
+        with score <= threshold (L2) / >= threshold (Dot, Cosine) in walk order.  thresholds: a scalar for the batch or one per
+        query; mask: as search_vamana_filtered's (None = no filter).  Returns (ids [nq, max_results], scores, counts [nq]) and
+        the stats with stats=True: query q's rows are ids[q, :counts[q]], the rest padded with 0xFFFFFFFF / +-Inf."""
+        nq = _rows(queries, self.dim)
+        q, pq_ = _ptr(queries, np.float32)
+        if _is_torch(thresholds):
+            t = thresholds.to(torch.float32).reshape(-1)
+            if t.numel() == 1 and nq != 1:
+                t = t.expand(nq)
+            t = t.contiguous()
+        else:
+            t = np.asarray(thresholds, np.float32).reshape(-1)
+            if t.size == 1:
+                t = np.full(nq, t[0], np.float32)
+        if (t.numel() if _is_torch(t) else t.size) != nq:
+            raise ValueError(f"search_vamana_threshold: one threshold for the batch or one per query ({nq})")
+        t, pt = _ptr(t, np.float32, nq)
+        m, pm, stride = (None, None, 0) if mask is None else self._packed_mask(mask, nq, "search_vamana_threshold")
+        ids = _empty_like(queries, (nq, max_results), np.uint32)
+        scores = _empty_like(queries, (nq, max_results), np.float32)
+        counts = _empty_like(queries, (nq,), np.int32)
+        i, pi = _ptr(ids, np.uint32, nq * max_results)
+        s, ps = _ptr(scores, np.float32, nq * max_results)
+        c, pc = _ptr(counts, np.int32, nq)
+        st = np.zeros((nq, 5), np.int64) if stats else None
+        pst = C.c_void_p(st.ctypes.data) if stats and nq else None
+        check(self._lib.vg_search_vamana_threshold(self._h, pq_, C.c_int64(nq), pt, C.c_int32(max_results), C.c_int32(kind), pm,
+                                                   C.c_int64(stride), pi, ps, pc, pst, _stream_ptr(stream)))
+        if not stats:
+            return ids, scores, counts
+        return ids, scores, counts, (st if stats == "full" else st[:, :4])
+
     def set_vectors(self, base, stream=None):
         """fp32 rows, n*dim row-major (vectorstore/columnar.go:21-24)."""
         b, pb = _ptr(base, np.float32, self.n * self.dim)

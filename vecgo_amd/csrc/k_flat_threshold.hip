@@ -207,6 +207,34 @@ __global__ __launch_bounds__(64) void flat_thr_filter_kernel(const float *__rest
     if (lane == 0) out_counts[q] = kept;
 }
 
+// the two steps above for lists another search fills: vg_search_vamana's large-k walk leaves each query's result heap as a
+// list of k keys (kKeyMax after the last), vg_search_vamana_threshold filters what that search returns
+int32_t launch_thr_select_lists(bool desc, const uint64_t *lists, int64_t list_cap, const int *counts, int64_t nq, int max_results,
+                                uint32_t *ids, float *scores, int32_t *out_counts, hipStream_t st)
+{
+    if (nq == 0) return VG_OK;
+    int sbuf = 64;
+    while (sbuf < max_results) sbuf <<= 1;
+    const size_t lds = sizeof(uint64_t) * static_cast<size_t>(sbuf) + kThrSelWaves * 256 * sizeof(unsigned);
+    const size_t lds_max = sizeof(uint64_t) * static_cast<size_t>(kThrMaxResults) + kThrSelWaves * 256 * sizeof(unsigned);
+    auto sel = desc ? flat_thr_select_kernel<true> : flat_thr_select_kernel<false>;
+    VG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(sel), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds_max)));
+    VG_LAUNCH(sel, dim3(static_cast<unsigned>(nq)), dim3(kThrSelThreads), lds, st, lists, list_cap, counts, max_results, sbuf, nullptr,
+              ids, scores, out_counts);
+    return VG_OK;
+}
+
+int32_t launch_thr_filter(bool desc, const float *thr, int64_t nq, int max_results, uint32_t *ids, float *scores, int32_t *counts,
+                          hipStream_t st)
+{
+    if (nq == 0) return VG_OK;
+    if (desc)
+        VG_LAUNCH(flat_thr_filter_kernel<true>, dim3(static_cast<unsigned>(nq)), dim3(64), 0, st, thr, max_results, ids, scores, counts);
+    else
+        VG_LAUNCH(flat_thr_filter_kernel<false>, dim3(static_cast<unsigned>(nq)), dim3(64), 0, st, thr, max_results, ids, scores, counts);
+    return VG_OK;
+}
+
 // ---- batches: the rows the nomination appended (GEMM keys), re-scored exactly; those within the threshold go to the list ---------
 // grid (workgroups per query, queries); 4 candidates per wave step, one per 16-lane group
 template <bool DOT>

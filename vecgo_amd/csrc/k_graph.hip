@@ -23,6 +23,11 @@ namespace vg {
 
 int32_t launch_pq_build_table(const vg_pq *pq, const float *d_queries, int64_t nq, float *d_tables,
                               bool scan_layout, hipStream_t st);
+// k_flat_threshold.hip: the best max_results keys of per-query lists, written best first; the engine's threshold filter
+int32_t launch_thr_select_lists(bool desc, const uint64_t *lists, int64_t list_cap, const int *counts, int64_t nq, int max_results,
+                                uint32_t *ids, float *scores, int32_t *out_counts, hipStream_t st);
+int32_t launch_thr_filter(bool desc, const float *thr, int64_t nq, int max_results, uint32_t *ids, float *scores, int32_t *counts,
+                          hipStream_t st);
 
 
 // ---- HNSW ----------------------------------------------------------------------------------------
@@ -290,6 +295,14 @@ __device__ inline float rq_formula_g(float qn, float yn, float dimf, float hammi
 
 constexpr int kHnswMaxEf = 1 << 20;  // ... in HBM scratch beyond
 constexpr int kVamanaMaxK = 512;  // results per query: one per lane up to 64, a sorted LDS list beyond
+// k in (kVamanaMaxK, kVamanaHugeMaxK] (HUGE instances): the k best keys as a 64-ary MAX-heap whose root — the worst of them — is
+// what the stop test reads.  The 64 children of a slot are one load per lane and one wave reduction, so a sift is one round
+// trip per level and k = 16384 is three levels below the root.  Its first kVamanaHeapLds items (the root, its 64 children and the
+// children of the first 6 of those: whole blocks, none straddles the boundary) live in the `res` array, the rest in HBM after the
+// query's exploration heap; at the end the keys go to that HBM list and flat_thr_select_kernel (k_flat_threshold.hip) writes them
+// best first.  The STRICT pass keeps the reference's CandidateHeap of k items in dynamic LDS (up to 128 KiB).
+constexpr int kVamanaHugeMaxK = 16384;
+constexpr int kVamanaHeapLds = 1 + 64 * 7;
 #ifndef VG_VAMANA_LDS_CAND
 #define VG_VAMANA_LDS_CAND 512
 #endif
@@ -324,7 +337,7 @@ __device__ __forceinline__ uint64_t *vamana_result_list()
 // anything (candidate_queue.go:12-38): which rows it holds, the root the pruning test reads and the order they leave in are then
 // decided by the heap's layout.  This pass runs the reference's TryPushBounded / Pop on an LDS array with float comparisons
 // (vg_cand_replay.hpp), neighbour by neighbour in list order; a query without risk returns at once.
-template <int kind, bool big, bool MASKED = false, bool STRICT = false>
+template <int kind, bool big, bool MASKED = false, bool STRICT = false, bool HUGE = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kind == kVamanaPQDirect ? VG_VAMANA_PQ_WAVES : 1, kind == kVamanaF32 ? VG_VAMANA_F32_MAX_WAVES : 8))) void vamana_search_kernel(
     int metric, int64_t n, int dim, const uint32_t *__restrict__ graph, int r, uint32_t entry,
     const float *__restrict__ base, const uint8_t *__restrict__ pq_rows, int pq_m,
@@ -350,6 +363,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kind == kVam
     const Sub16 sub = Sub16::make(lane);
     const float *qv = queries + q * dim;
     uint32_t *vis = visited_ws + q * vis_words;
+    static_assert(!HUGE || big, "the large-k result set replaces the sorted LDS list");
+    // HUGE: the query's cand_cap items of scratch hold the exploration heap (ccap items) and then the HBM part of the result heap (k)
+    const int64_t ccap = HUGE ? cand_cap - k : cand_cap;
     // (the flat address of cand_lo passes through a register: as a constant expression inside the heap's
     // LDS-or-HBM selects this compiler emits v_cmp with src_shared_base as a VOP2 operand and rejects it)
     HItem *cand_lo_flat = cand_lo;
@@ -501,6 +517,49 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kind == kVam
         res_n = newn;
         res_tau = res_n >= k ? res[k - 1] : kKeyMax;
     };
+    // HUGE: the 64-ary max-heap (keys are distinct: a node enters the walk once); hl = its HBM part, indexed like the heap
+    uint64_t *hl = nullptr;
+    if constexpr (HUGE) hl = reinterpret_cast<uint64_t *>(cand_ws + q * cand_cap + ccap);
+    auto huge_insert = [&](uint64_t c) {  // c < res_tau, every lane calls it with the same key
+        const auto put = [&](int i, uint64_t v) {
+            if (i < kVamanaHeapLds)
+                res[i] = v;
+            else
+                hl[i] = v;
+        };
+        int i;
+        if (res_n < k) {  // push: up the parent chain
+            i = res_n++;
+            while (i > 0) {
+                const int p = (i - 1) >> 6;
+                const uint64_t pk = p < kVamanaHeapLds ? res[p] : hl[p];
+                if (pk > c) break;
+                put(i, pk);
+                i = p;
+            }
+        } else {  // the root leaves: c sinks along the largest children
+            i = 0;
+            for (;;) {
+                const int fc = 64 * i + 1;
+                if (fc >= k) break;
+                uint64_t v = 0;  // (below every key that can move: c >= 0)
+                if (fc + lane < k) v = fc < kVamanaHeapLds ? res[fc + lane] : hl[fc + lane];
+                uint64_t m = v;
+#pragma unroll
+                for (int off = 32; off > 0; off >>= 1) {
+                    const uint64_t o = (static_cast<uint64_t>(static_cast<uint32_t>(__shfl_xor(static_cast<int>(m >> 32), off))) << 32) |
+                                       static_cast<uint32_t>(__shfl_xor(static_cast<int>(static_cast<uint32_t>(m)), off));
+                    m = o > m ? o : m;
+                }
+                if (c >= m) break;
+                put(i, m);
+                i = fc + __builtin_ctzll(__ballot(v == m && fc + lane < k));
+            }
+        }
+        put(i, c);
+        res_tau = res_n >= k ? res[0] : kKeyMax;
+    };
+    (void)huge_insert;
     auto offer = [&](uint64_t key) {
         if (!big) {
             tk.offer(key, lane);
@@ -511,12 +570,21 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kind == kVam
             const int j = __builtin_ctzll(mask);
             mask &= mask - 1;
             const uint64_t c = readlane_u64(key, j);
-            if (c < res_tau) res_insert(c);  // the bound may have dropped since the ballot
+            if (c < res_tau) {  // the bound may have dropped since the ballot
+                if constexpr (HUGE)
+                    huge_insert(c);
+                else
+                    res_insert(c);
+            }
         }
     };
     int heap_count = 0;  // min(k, candidates offered): sc.Heap.Len()
     int cand_len = 0;
     CItem *rheap = reinterpret_cast<CItem *>(res);  // STRICT: sc.Heap itself
+    if constexpr (HUGE && STRICT)  // k items of dynamic LDS after the query's image (the host sizes the allocation)
+        rheap = reinterpret_cast<CItem *>(reinterpret_cast<unsigned char *>(vamana_qprep) +
+                                          (kind == kVamanaPQDirect ? (pq_m >> 1) * kPqPairFloats * sizeof(float)
+                                                                   : kind == kVamanaRaBitQ ? rq_nb : 0));
     auto strict_offer = [&](uint32_t id, float d) {   // TryPushBounded(k), candidate_queue.go:120-132 (uniform over the wave)
         const CItem x{d, id};
         if (heap_count < k) {
@@ -573,7 +641,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kind == kVam
                 todo &= todo - 1;
                 const uint32_t id = static_cast<uint32_t>(__builtin_amdgcn_readlane(id_lane, j));
                 const float d = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(myd), j));
-                if (cand_len < cand_cap)
+                if (cand_len < ccap)
                     heap_push<false>(cand, cand_len, HItem{id, d});
                 else
                     st_dropped++;
@@ -583,14 +651,14 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kind == kVam
             continue;
         }
         // exploration heap: PushItem in the node's neighbour order (segment.go:695)
-        if (cand_len + nnew <= cand_cap) {
+        if (cand_len + nnew <= ccap) {
             heap_push_run_min(cand, cand_len, newmask, id_lane, myd);  // the run of pushes, parents tracked in registers
         } else {
             uint64_t todo = newmask;
             while (todo) {
                 const int j = __builtin_ctzll(todo);
                 todo &= todo - 1;
-                if (cand_len < cand_cap)
+                if (cand_len < ccap)
                     heap_push<false>(cand, cand_len,
                                      HItem{static_cast<uint32_t>(__builtin_amdgcn_readlane(id_lane, j)),
                                            __int_as_float(__builtin_amdgcn_readlane(__float_as_int(myd), j))});
@@ -617,6 +685,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kind == kVam
         for (int i = nres + lane; i < k; i += 64) {
             ids[q * k + i] = VG_INVALID_ID;
             scores[q * k + i] = desc ? -INFINITY : INFINITY;
+        }
+    } else if constexpr (HUGE) {  // the heap's keys, the rest kKeyMax, to its HBM list: the host's sort writes them best first
+        for (int i = lane; i < k; i += 64) {
+            if (i >= res_n)
+                hl[i] = kKeyMax;
+            else if (i < kVamanaHeapLds)
+                hl[i] = res[i];
         }
     } else if (big) {
         for (int i = lane; i < k; i += 64) {
@@ -928,7 +1003,8 @@ VG_API int32_t vg_search_hnsw_filtered(vg_index *idx, const float *queries, int6
 }
 
 static int32_t vamana_impl(vg_index *idx, const float *queries, int64_t nq, int32_t k, int32_t kind, const uint8_t *mask,
-                           int64_t mask_stride, uint32_t *ids, float *scores, vg_search_stats *stats, void *stream);
+                           int64_t mask_stride, uint32_t *ids, float *scores, vg_search_stats *stats, void *stream,
+                           const float *thresholds = nullptr, int32_t *counts = nullptr);
 
 VG_API int32_t vg_search_vamana(vg_index *idx, const float *queries, int64_t nq, int32_t k, int32_t kind,
                                 uint32_t *ids, float *scores, vg_search_stats *stats, void *stream)
@@ -948,8 +1024,27 @@ VG_API int32_t vg_search_vamana_filtered(vg_index *idx, const float *queries, in
     return vamana_impl(idx, queries, nq, k, kind, mask, mask_stride, ids, scores, stats, stream);
 }
 
+// Engine.SearchThreshold's DiskANN leg (engine/engine.go:1485-1531): Search(q, max_results), then the engine's filter in order
+VG_API int32_t vg_search_vamana_threshold(vg_index *idx, const float *queries, int64_t nq, const float *thresholds,
+                                          int32_t max_results, int32_t kind, const uint8_t *mask, int64_t mask_stride, uint32_t *ids,
+                                          float *scores, int32_t *counts, vg_search_stats *stats, void *stream)
+{
+    VG_CHECK(idx, VG_ERR_INVALID_ARG, "vg_search_vamana_threshold: NULL index");
+    VG_CHECK(nq >= 0 && max_results >= 0, VG_ERR_INVALID_ARG, "vg_search_vamana_threshold: negative nq or max_results");
+    VG_CHECK(max_results <= vg::kVamanaHugeMaxK, VG_ERR_UNSUPPORTED, "vg_search_vamana_threshold: max_results=%d exceeds %d",
+             max_results, vg::kVamanaHugeMaxK);
+    if (nq == 0 || max_results == 0) return VG_OK;
+    VG_CHECK(thresholds && counts, VG_ERR_INVALID_ARG, "vg_search_vamana_threshold: NULL buffer");
+    const int64_t mask_bytes = (idx->n + 7) / 8;
+    VG_CHECK(mask == nullptr || mask_stride == 0 || mask_stride >= mask_bytes, VG_ERR_INVALID_ARG,
+             "vg_search_vamana_threshold: mask_stride %lld is shorter than a mask (%lld bytes)", static_cast<long long>(mask_stride),
+             static_cast<long long>(mask_bytes));
+    return vamana_impl(idx, queries, nq, max_results, kind, mask, mask_stride, ids, scores, stats, stream, thresholds, counts);
+}
+
 static int32_t vamana_impl(vg_index *idx, const float *queries, int64_t nq, int32_t k, int32_t kind, const uint8_t *mask,
-                           int64_t mask_stride, uint32_t *ids, float *scores, vg_search_stats *stats, void *stream)
+                           int64_t mask_stride, uint32_t *ids, float *scores, vg_search_stats *stats, void *stream,
+                           const float *thresholds, int32_t *counts)
 {
     VG_CHECK(idx, VG_ERR_INVALID_ARG, "vg_search_vamana: NULL index");
     VG_CHECK(nq >= 0 && k >= 0, VG_ERR_INVALID_ARG, "vg_search_vamana: negative nq or k");
@@ -964,7 +1059,8 @@ static int32_t vamana_impl(vg_index *idx, const float *queries, int64_t nq, int3
     VG_CHECK(kind != 1 || idx->pq->k == 256, VG_ERR_UNSUPPORTED, "vg_search_vamana: PQ needs numCentroids == 256");
     VG_CHECK(idx->metric != VG_METRIC_HAMMING, VG_ERR_UNSUPPORTED, "unsupported metric for float32: Hamming");
     VG_CHECK(queries && ids && scores, VG_ERR_INVALID_ARG, "vg_search_vamana: NULL buffer");
-    VG_CHECK(k <= vg::kVamanaMaxK, VG_ERR_UNSUPPORTED, "vg_search_vamana: k=%d exceeds %d", k, vg::kVamanaMaxK);
+    VG_CHECK(k <= vg::kVamanaHugeMaxK, VG_ERR_UNSUPPORTED, "vg_search_vamana: k=%d exceeds %d", k, vg::kVamanaHugeMaxK);
+    const bool huge = k > vg::kVamanaMaxK;
     VG_HIP(hipSetDevice(idx->ctx->device));
     hipStream_t st = vg::pick_stream(idx->ctx, stream);
     vg::DevIn<float> q;
@@ -977,14 +1073,21 @@ static int32_t vamana_impl(vg_index *idx, const float *queries, int64_t nq, int3
     VG_TRY(ost.init(stats, stats ? static_cast<size_t>(nq) : 0, st));
     vg::DevIn<uint8_t> mk;
     VG_TRY(mk.init(mask, mask ? static_cast<size_t>(mask_stride ? (nq - 1) * mask_stride + (idx->n + 7) / 8 : (idx->n + 7) / 8) : 0, st));
+    vg::DevIn<float> thr;  // vg_search_vamana_threshold
+    vg::DevOut<int32_t> ocnt;
+    VG_TRY(thr.init(thresholds, thresholds ? static_cast<size_t>(nq) : 0, st));
+    VG_TRY(ocnt.init(counts, thresholds ? static_cast<size_t>(nq) : 0, st));
     const int64_t vis_words = (idx->n + 31) / 32;
     // The reference's exploration heap is unbounded (ScratchCandidates, diskann/segment.go:641-703).  A node enters it at most once
     // (the visited test), so n items are "unbounded" here.  The unfiltered walk stops at k results long before 65 536; a walk with a
     // selective row filter goes on until k MATCHING rows are found and can fill any smaller heap (pushes were then
     // dropped silently): with a filter the cap is n — nothing is ever dropped — at the price of fewer queries per launch.
-    const int64_t cand_cap = mask ? idx->n : std::min<int64_t>(idx->n, 65536);
+    // k > 512 walks past 65 536 candidates (the 1M x 768 graph at k = 16384: DESIGN.md): n items here too, followed by the HBM part
+    // of the k-item result heap (the kernel's ccap)
+    const int64_t cand_cap = huge ? idx->n + k : mask ? idx->n : std::min<int64_t>(idx->n, 65536);
     const int64_t per_query = vis_words * 4 + cand_cap * 8;
-    int64_t chunk = std::max<int64_t>(1, graph_scratch_cap(idx->ctx) / per_query);
+    const int64_t scratch_cap = huge && vg::hook(vg::kHookVamanaSmallScratch) ? int64_t(64) << 20 : graph_scratch_cap(idx->ctx);
+    int64_t chunk = std::max<int64_t>(1, scratch_cap / per_query);
     chunk = std::min(chunk, nq);
     const int rq_nb = ((idx->dim + 63) / 64) * 8;
     const int pq_m = idx->pq ? idx->pq->m : 0;
@@ -997,7 +1100,10 @@ static int32_t vamana_impl(vg_index *idx, const float *queries, int64_t nq, int3
                              (reinterpret_cast<uintptr_t>(idx->d_int4_rows) & 15) == 0;
     const int i_luts = ar.add(kind == 1 && !pq_direct ? sizeof(float) * static_cast<size_t>(nq) * pq_m * 256 : 0);
     const int i_qcodes = ar.add(kind == 2 ? static_cast<size_t>(nq) * (rq_nb + 4) : 0);
+    const int i_lcnt = ar.add(huge ? sizeof(int) * 2 * static_cast<size_t>(chunk) : 0);  // the lists' lengths (all k) and the sort's counts
     VG_TRY(ar.commit());
+    int *lcnt = ar.get<int>(i_lcnt);
+    if (huge) VG_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(lcnt), k, static_cast<size_t>(chunk), st));
     struct { uint32_t *ptr; } vis{ar.get<uint32_t>(i_vis)};
     struct { vg::HItem *ptr; } cand{ar.get<vg::HItem>(i_cand)};
     struct { float *ptr; } luts{ar.get<float>(i_luts)};
@@ -1012,9 +1118,10 @@ static int32_t vamana_impl(vg_index *idx, const float *queries, int64_t nq, int3
         const int64_t cnt = std::min(chunk, nq - q0);
         VG_HIP(hipMemsetAsync(vis.ptr, 0, static_cast<size_t>(cnt) * vis_words * 4, st));
         vg::ProfScope prof(idx->ctx, "vamana_search", st);
-        auto launch = [&](auto kernel) -> int32_t {
+        // (the STRICT pass of a large-k walk keeps its k-item CandidateHeap after the query's image: extra_lds)
+        auto launch = [&](auto kernel, size_t extra_lds = 0) -> int32_t {
             VG_LAUNCH(kernel, dim3(static_cast<unsigned>(cnt)), dim3(64),
-                      pq_direct ? static_cast<size_t>(pq_m >> 1) * vg::kPqPairFloats * sizeof(float) : (kind == 2 ? static_cast<size_t>(rq_nb) : 0), st,
+                      (pq_direct ? static_cast<size_t>(pq_m >> 1) * vg::kPqPairFloats * sizeof(float) : (kind == 2 ? static_cast<size_t>(rq_nb) : 0)) + extra_lds, st,
                       idx->metric, idx->n, idx->dim, idx->d_vamana, idx->vamana_r, idx->vamana_entry,
                       idx->d_vectors, idx->d_pq_rows, pq_m, kind == 1 && !pq_direct ? luts.ptr + q0 * pq_m * 256 : nullptr,
                       pq_direct ? idx->pq->d_codebooks : nullptr, idx->pq ? idx->pq->d_scales : nullptr,
@@ -1030,7 +1137,8 @@ static int32_t vamana_impl(vg_index *idx, const float *queries, int64_t nq, int3
         const int inst = pq_direct ? vg::kVamanaPQDirect : int4_direct ? vg::kVamanaInt4Direct : kind;
 #define VG_VAMANA_CASE(K)                                                                                                   \
     case K:                                                                                                                 \
-        rc = mk.ptr ? (big ? launch(vg::vamana_search_kernel<K, true, true>) : launch(vg::vamana_search_kernel<K, false, true>)) \
+        rc = huge ? (mk.ptr ? launch(vg::vamana_search_kernel<K, true, true, false, true>) : launch(vg::vamana_search_kernel<K, true, false, false, true>)) \
+           : mk.ptr ? (big ? launch(vg::vamana_search_kernel<K, true, true>) : launch(vg::vamana_search_kernel<K, false, true>)) \
                     : (big ? launch(vg::vamana_search_kernel<K, true>) : launch(vg::vamana_search_kernel<K, false>));       \
         break;
         switch (inst) {
@@ -1040,14 +1148,36 @@ static int32_t vamana_impl(vg_index *idx, const float *queries, int64_t nq, int3
             VG_VAMANA_CASE(5)
             VG_VAMANA_CASE(2)
         default:
-            rc = mk.ptr ? (big ? launch(vg::vamana_search_kernel<3, true, true>) : launch(vg::vamana_search_kernel<3, false, true>))
+            rc = huge ? (mk.ptr ? launch(vg::vamana_search_kernel<3, true, true, false, true>) : launch(vg::vamana_search_kernel<3, true, false, false, true>))
+               : mk.ptr ? (big ? launch(vg::vamana_search_kernel<3, true, true>) : launch(vg::vamana_search_kernel<3, false, true>))
                         : (big ? launch(vg::vamana_search_kernel<3, true>) : launch(vg::vamana_search_kernel<3, false>));
             break;
         }
 #undef VG_VAMANA_CASE
         VG_TRY(rc);
+        if (huge)  // each query's heap, as a list of k keys in its scratch, best first into ids / scores
+            VG_TRY(vg::launch_thr_select_lists(idx->metric != VG_METRIC_L2, reinterpret_cast<const uint64_t *>(cand.ptr + (cand_cap - k)),
+                                               cand_cap, lcnt, cnt, k, oid.ptr + q0 * k, osc.ptr + q0 * k, lcnt + chunk, st));
         // the queries whose distances may hold a NaN, again with the reference's CandidateHeap (every other query returns at once)
-        if (!vg::hook(vg::kHookNoCandReplay)) {
+        if (!vg::hook(vg::kHookNoCandReplay) && huge) {
+            const size_t heap_lds = sizeof(vg::CItem) * static_cast<size_t>(k);
+            auto strict = [&](auto kernel) -> int32_t {
+                const size_t lds = heap_lds + (pq_direct ? static_cast<size_t>(pq_m >> 1) * vg::kPqPairFloats * sizeof(float)
+                                                         : (kind == 2 ? static_cast<size_t>(rq_nb) : 0));
+                VG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                           static_cast<int>(lds)));
+                return launch(kernel, heap_lds);
+            };
+            switch (inst) {
+            case 0: rc = strict(vg::vamana_search_kernel<0, true, true, true, true>); break;
+            case 1: rc = strict(vg::vamana_search_kernel<1, true, true, true, true>); break;
+            case 4: rc = strict(vg::vamana_search_kernel<4, true, true, true, true>); break;
+            case 5: rc = strict(vg::vamana_search_kernel<5, true, true, true, true>); break;
+            case 2: rc = strict(vg::vamana_search_kernel<2, true, true, true, true>); break;
+            default: rc = strict(vg::vamana_search_kernel<3, true, true, true, true>); break;
+            }
+            VG_TRY(rc);
+        } else if (!vg::hook(vg::kHookNoCandReplay)) {
             switch (inst) {
             case 0: rc = launch(vg::vamana_search_kernel<0, true, true, true>); break;
             case 1: rc = launch(vg::vamana_search_kernel<1, true, true, true>); break;
@@ -1059,9 +1189,12 @@ static int32_t vamana_impl(vg_index *idx, const float *queries, int64_t nq, int3
             VG_TRY(rc);
         }
     }
+    // vg_search_vamana_threshold: the engine's filter over each query's list, in order (engine.go:1518-1529)
+    if (thresholds) VG_TRY(vg::launch_thr_filter(idx->metric != VG_METRIC_L2, thr.ptr, nq, k, oid.ptr, osc.ptr, ocnt.ptr, st));
     VG_TRY(oid.finish());
     VG_TRY(osc.finish());
     VG_TRY(ost.finish());
-    if (oid.on_host() || osc.on_host() || ost.on_host()) VG_HIP(hipStreamSynchronize(st));
+    VG_TRY(ocnt.finish());
+    if (oid.on_host() || osc.on_host() || ost.on_host() || ocnt.on_host()) VG_HIP(hipStreamSynchronize(st));
     return VG_OK;
 }
