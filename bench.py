@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
 """bench.py — BASELINE.json's metric on MI355X: queries/s at recall@10 >= 0.95 on 1M x 768 fp32 (i.i.d. normal).
 
-Which pipeline answers at that recall is MEASURED here, not assumed (N = 1):
+A plain run sets up, warms up, times the steps and prints the line: the exact path (configs[1], below) is timed, its
+recall@10 checked against an fp64 ground truth.  `--full` adds everything else described here, after the headline.
+
+Which pipeline answers at that recall is MEASURED with --full, not assumed (N = 1):
   * a real HNSW graph is built on the corpus on the GPU (vg_hnsw_build: hnsw.Insert with the reference's
     defaults M = 32 / M0 = 64 / EF = 300, levels of ApplyInsert) and PQ (m = 96, 256 centroids) is trained and
     the corpus encoded on the GPU;
@@ -16,11 +19,11 @@ so that the claim is witnessed, next to the same searches on the host's cores (`
 per thread, the reference's compiled AVX-512 kernels, same graph — identical answers).
 
 N > 1: the corpus is sharded by rows over the ranks (strong scaling) on the exact path, ONE all-gather of
-per-shard top-k (RCCL over xGMI), merge with the reference tie-break (vecgo_amd/sharded.py); `rabitq_sharded`
-and `pq_train_sharded` are BASELINE configs[4].  A single graph does not shard (replicas only).
+per-shard top-k (RCCL over xGMI), merge with the reference tie-break (vecgo_amd/sharded.py); with --full,
+`rabitq_sharded` and `pq_train_sharded` are BASELINE configs[4].  A single graph does not shard (replicas only).
 
-One JSON line on rank 0; extra objects: `roofline` (dominant kernel of the timed region, HIP events from inside
-the library), `adc_scan` (configs[3]: 10M x 96 B codes, HBM roofline), `rabitq_scan` (configs[4] on one GPU),
+One JSON line on rank 0 with `roofline` (dominant kernel of the timed region, HIP events from inside the library);
+--full adds `adc_scan` (configs[3]: 10M x 96 B codes, HBM roofline), `rabitq_scan` (configs[4] on one GPU),
 `sq8_scan`, `int4_scan`, `flat_small_batch`, `hnsw_layer0` (configs[2]), `flat_ivf_probe`, `cpu_baseline`.
 `--dump-outputs DIR` also writes the ids and scores of the last timed step (dump_outputs).
 """
@@ -1653,6 +1656,11 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, measure everything else: the HNSW / PQ frontier that picks the operating point, "
+                         "the CPU baseline and twins, the other scans, precisions, sizes and legs, the per-kernel rooflines with "
+                         "their rocprofv3 passes and, with --gpus N > 1, the sharded legs of BASELINE configs[4] (the --no-* "
+                         "options below leave parts of it out)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-adc", action="store_true")
     ap.add_argument("--no-hnsw", action="store_true")
@@ -1662,7 +1670,7 @@ def main():
     ap.add_argument("--torch-collective", action="store_true", help="N > 1: exchange through torch.distributed instead of vg_comm")
     ap.add_argument("--bf16-filter", action="store_true",
                     help="time the exact path WITH vg_index_enable_bf16_filter as the headline (default: the fp32 MFMA GEMM "
-                         "BASELINE's configs[1] names; the filtered path is reported as `flat_exact_bf16_filter` either way)")
+                         "BASELINE's configs[1] names; --full reports the filtered path as `flat_exact_bf16_filter` either way)")
     ap.add_argument("--backend", default="nccl",
                     help="torch.distributed backend; 'gloo' lets several ranks share one GPU to smoke-test the N>1 path")
     ap.add_argument("--dump-outputs", metavar="DIR",
@@ -1731,14 +1739,18 @@ def main():
     def flat_step(i):   # a step returns what the caller of its path receives: (ids, scores)
         return index.search(queries[i % n_batches], K, stream=stream)
 
-    # ---- which pipeline reaches recall@10 >= 0.95 fastest?  (N = 1: measured; N > 1: the exact path, sharded)
+    # ---- which pipeline reaches recall@10 >= 0.95 fastest?  (N = 1 with --full: measured; otherwise the exact path,
+    # which is where every measured frontier of this corpus has put it — sharded when N > 1)
     hp = hnsw128 = hidx = hpq = None
     gt1024 = None
     op = {"path": "flat_exact"}
-    if world == 1 and not args.no_hnsw:
-        for i in range(3):
+    if world == 1:
+        for i in range(3):   # the exact path's first calls load its code objects and scratch: set-up, whatever --warmup is
             flat_step(i)
         torch.cuda.synchronize()
+        gi, _ = fp64_topk_local(rows, queries[0], lo, K)   # independent ground truth: fp64 brute force
+        gt1024 = gi.cpu().numpy()
+    if world == 1 and args.full and not args.no_hnsw:
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record(stream)
         for i in range(3):
@@ -1746,8 +1758,6 @@ def main():
         e1.record(stream)
         torch.cuda.synchronize()
         exact_ms = e0.elapsed_time(e1) / 3
-        gi, _ = fp64_topk_local(rows, queries[0], lo, K)   # independent ground truth: fp64 brute force
-        gt1024 = gi.cpu().numpy()
         hp, hnsw128, hidx, hpq = hnsw_pq_frontier(vg, ctx, rows, queries, gt1024, exact_ms, stream,
                                                   with_cpu=not args.no_cpu_baseline)
         op = hp["operating_point"]
@@ -1804,7 +1814,7 @@ def main():
     recall = recall_at_k(got, gt)
 
     extra = {}
-    if world > 1:   # BASELINE configs[4]: every rank takes part
+    if world > 1 and args.full:   # BASELINE configs[4]: every rank takes part
         try:
             extra = multi_gpu_legs(vg, ctx, sharded, world, rank, device, stream, comm)
         except Exception as e:   # an extra must not cost the run its headline line (the same error on every rank
@@ -1852,8 +1862,9 @@ def main():
                    # BASELINE's metric names HNSW+PQ; WHICH pipeline is timed is measured, not assumed
                    "operating_point_note": "fastest of {HNSW fp32, HNSW on PQ codes + exact rerank, exact fp32 MFMA GEMM (configs[1])} "
                                            "with recall@10 >= 0.95 vs fp64 ground truth on this corpus, from the frontier measured "
-                                           "in this run (bench_full.json: hnsw_pq)" if world == 1 and not args.no_hnsw else
-                                           "exact fp32 path (configs[1]); no frontier measured in this mode",
+                                           "in this run (bench_full.json: hnsw_pq)" if hp is not None else
+                                           "exact fp32 path (configs[1]); no frontier measured in this mode"
+                                           + ("" if args.full else " (bench.py --gpus 1 --full measures it)"),
                    "rows": N_ROWS,
                    "dim": DIM, "k": K, "queries_per_step": Q_BATCH,
                    "parallelism": (f"row-shard x{world}, one all-gather of per-shard top-k per step ("
@@ -1892,21 +1903,22 @@ def main():
         leg("vamana_pq", lambda: vamana_pq(vg, ctx, hidx, rows, queries.reshape(-1, DIM)[:NQ_FLIGHT].contiguous(), gt1024, stream))
         hidx.close()
         hpq.close()
-    if world == 1:
+    one_full = world == 1 and args.full   # the extras of a --full run on one GPU
+    if one_full:
         if args.bf16_filter:
             index.index.enable_bf16_filter(False)
         leg("flat_exact_bf16_filter", lambda: flat_bf16_filter(vg, ctx, index.index, queries, gt, args.steps, stream))
         if "qps" in out["flat_exact_bf16_filter"]:
             out["flat_exact_bf16_filter"]["over_fp32_headline"] = out["flat_exact_bf16_filter"]["qps"] / qps
         leg("flat_small_batch", lambda: flat_small_batch(vg, ctx, index.index, queries[2], stream))
-    if world == 1 and not args.no_hnsw:
+    if one_full and not args.no_hnsw:
         leg("flat_ivf_probe", lambda: flat_ivf_probe(vg, ctx, rows, queries, gt[:64], stream))
         leg("structured_corpus", lambda: structured_corpus(vg, ctx, stream, device, with_cpu=not args.no_cpu_baseline))
-    cpu_on = world == 1 and not args.no_cpu_baseline
+    cpu_on = one_full and not args.no_cpu_baseline
     rows_host = rows.cpu().numpy() if cpu_on else None
-    if world == 1 and not args.no_build_side:
+    if one_full and not args.no_build_side:
         leg("build_side", lambda: build_side_legs(vg, ctx, rows, queries, stream, cpu_on, rows_host))
-    if world == 1 and not args.no_adc:
+    if one_full and not args.no_adc:
         del index
         leg("adc_scan", lambda: adc_scan_roofline(vg, ctx, stream, device, with_cpu=cpu_on))
         leg("rabitq_scan", lambda: rabitq_scan_roofline(vg, ctx, stream, device, with_cpu=cpu_on))
@@ -1917,7 +1929,7 @@ def main():
         if "value" in out["cpu_baseline"]:
             out["gpu_over_cpu_at_recall_bar"] = qps / out["cpu_baseline"]["value"]
     # roofline.traffic measured in THIS run (after everything else: a profiler pass that went wrong cannot touch a timing)
-    if world == 1 and op["path"] == "flat_exact" and not args.bf16_filter and not args.no_live_traffic and not REDUCED:
+    if one_full and op["path"] == "flat_exact" and not args.bf16_filter and not args.no_live_traffic and not REDUCED:
         tb, detail = live_traffic("flat_gemm_dma_kernel<false, 2, 0, false>", "flat_time.py")
         if tb is not None:
             out["roofline"]["traffic_committed"] = out["roofline"]["traffic"]

@@ -1,7 +1,8 @@
-"""bench.py --gpus 2 without a launcher: it must start two ranks itself (never report a 1-GPU run as n_gpus = 2) and run
-BASELINE configs[4]'s code — `rabitq_sharded` (row shards + one all-gather of per-shard top-k, engine/search.go:835-908's
-fan-out/merge) and `pq_train_sharded` (sub-quantizer ranges, pq.go:83-138) — here with gloo, two ranks sharing GPU 0 and
-reduced sizes (the line says so).  No scaling curve comes out of this: it proves the N > 1 code runs."""
+"""bench.py --gpus 2 without a launcher: it must start two ranks itself (never report a 1-GPU run as n_gpus = 2) and, with
+--full, run BASELINE configs[4]'s code — `rabitq_sharded` (row shards + one all-gather of per-shard top-k,
+engine/search.go:835-908's fan-out/merge) and `pq_train_sharded` (sub-quantizer ranges, pq.go:83-138) — here with gloo, two
+ranks sharing GPU 0 and reduced sizes (the line says so).  No scaling curve comes out of this: it proves the N > 1 code runs.
+A plain run (no --full) times the headline and nothing else."""
 import json
 import os
 import subprocess
@@ -23,7 +24,7 @@ def test_bench_gpus2_self_launch_gloo(world, tmp_path):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", str(world), "--backend", "gloo", "--steps", "3", "--warmup", "1",
-           "--dump-outputs", str(tmp_path / "out")]
+           "--full", "--dump-outputs", str(tmp_path / "out")]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     lines = r.stdout.splitlines()
@@ -46,3 +47,25 @@ def test_bench_gpus2_self_launch_gloo(world, tmp_path):
     assert ids.shape == sc.shape == (1024, 10) and ids.dtype == np.float64 and sc.dtype == np.float32
     assert np.all((ids >= 0) & (ids < 200000)) and np.all(np.diff(sc, axis=1) >= 0)
 
+
+def test_bench_plain_run_times_the_headline_only(tmp_path):
+    """Without --full a run sets up, warms up, times its steps, dumps them and prints the line: the exact path with its recall
+    against the fp64 ground truth and the roofline of the timed kernel, none of the extras (reduced sizes)."""
+    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", VECGO_BENCH_ROWS="200000", VECGO_BENCH_SCAN_ROWS="200000")
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+           "--dump-outputs", str(tmp_path / "out")]
+    r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+    lines = r.stdout.splitlines()
+    assert len(lines) == 1 and lines[0].startswith("{"), r.stdout[-3000:]
+    d = json.loads(lines[0])
+    assert d["n_gpus"] == 1 and d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["value"] > 0
+    assert d["unit"] == "queries/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert d["config"]["operating_point"] == "flat_exact" and "--full" in d["config"]["operating_point_note"]
+    assert d["recall_at_10"] == 1.0 and d["recall_queries"] == 1024
+    assert d["roofline"]["bound"] == "mfma" and d["roofline"]["launches"] >= 3
+    assert "cpu_baseline" not in d and [c["config"] for c in d["configs"]] == ["configs[1] flat exact fp32 MFMA GEMM"]
+    ids, sc = np.load(tmp_path / "out" / "ids.npy"), np.load(tmp_path / "out" / "scores.npy")
+    assert ids.shape == sc.shape == (1024, 10) and np.all((ids >= 0) & (ids < 200000)) and np.all(np.diff(sc, axis=1) >= 0)
