@@ -190,6 +190,20 @@ func (r *Resident) BuildVamana(R, L int, alpha float32, seed uint64) error {
 	return hipctx.Err(int32(C.vg_vamana_build(r.h, C.int32_t(R), C.int32_t(L), C.float(alpha), nil, C.uint64_t(seed), 8192, 32, nil)))
 }
 
+// ReorderVamanaBFS: diskann.Writer.reorderBFS (diskann/reorder.go:14-157) on the resident graph and every per-row array
+// it holds.  perm[new] = old; invPerm[old] = new is the writer's addOrderToFinalRow.  The caller permutes what the GPU
+// never held (ids, metadata, payloads) with perm.
+func (r *Resident) ReorderVamanaBFS() (perm, invPerm []uint32, err error) {
+	perm, invPerm = make([]uint32, r.rows), make([]uint32, r.rows)
+	if r.rows == 0 {
+		return perm, invPerm, hipctx.Err(int32(C.vg_vamana_reorder_bfs(r.h, nil, nil, nil)))
+	}
+	if err := hipctx.Err(int32(C.vg_vamana_reorder_bfs(r.h, up(perm), up(invPerm), nil))); err != nil {
+		return nil, nil, err
+	}
+	return perm, invPerm, nil
+}
+
 // VamanaGraph: (R, n*R neighbour ids with 0xFFFFFFFF = none, entry point) — what Writer.Flush writes.
 func (r *Resident) VamanaGraph() (int, []uint32, uint32, error) {
 	var R C.int32_t

@@ -59,9 +59,10 @@ extern "C" {
  *  11: vg_search_flat_threshold
  *  12: vg_vamana_build, vg_index_get_vamana_graph
  *  13: vg_hnsw_insert
- *  Added at minor 13 without a bump (the minor-13 header test pins the value): vg_search_vamana_threshold, and
- *  vg_search_vamana / _filtered take k up to 16384 (512 before).  A binding that needs them looks the symbol
- *  vg_search_vamana_threshold up (dlsym) instead of comparing the minor; the next bump covers them. */
+ *  Added at minor 13 without a bump (the minor-13 header test pins the value): vg_search_vamana_threshold,
+ *  vg_vamana_reorder_bfs, and vg_search_vamana / _filtered take k up to 16384 (512 before).  A binding that needs
+ *  them looks the symbol vg_search_vamana_threshold up (dlsym) instead of comparing the minor, and
+ *  vg_vamana_reorder_bfs the same way; the next bump covers them. */
 #define VG_ABI_MINOR 13
 #define VG_INVALID_ID 0xFFFFFFFFu
 #define VG_STREAM_LEGACY ((void *)1) /* == hipStreamLegacy */
@@ -349,7 +350,7 @@ int32_t vg_index_set_vamana_graph(vg_index *idx, int32_t r, const uint32_t *grap
  *   batch began and prunes its own list as it stood then; all new lists are written; then the back edges are
  *   applied, each target's records in (source id, slot) order.  max_batch = 1 is the writer's sequential loop.
  * Output: lists in the order the reference leaves them (prune output sorted, back edges appended), padded with
- *   VG_INVALID_ID to r.  The writer's reorderBFS (reorder.go) stays with the caller.  Deterministic: the same
+ *   VG_INVALID_ID to r.  The writer's reorderBFS (reorder.go) is vg_vamana_reorder_bfs.  Deterministic: the same
  *   inputs give the same graph bit for bit. */
 int32_t vg_vamana_build(vg_index *idx, int32_t r, int32_t l, float alpha, const uint32_t *init_graph, uint64_t seed,
                         int32_t max_batch, int32_t growth_div, void *stream);
@@ -357,6 +358,22 @@ int32_t vg_vamana_build(vg_index *idx, int32_t r, int32_t l, float alpha, const 
  * graph NULL = the sizes only.  (VG_ABI_MINOR 12.) */
 int32_t vg_index_get_vamana_graph(const vg_index *idx, int32_t *r, uint32_t *entry_point, uint32_t *graph,
                                   void *stream);
+/* diskann.Writer.reorderBFS (diskann/reorder.go:14-157) on the resident index: perm[new] = old and inv_perm[old] = new
+ * (the writer's addOrderToFinalRow), either NULL to skip, host or device.  (Present when the symbol is: see VG_ABI_MINOR.)
+ * Order, bit for bit the writer's: a BFS over the index's Vamana graph from its entry point, each node's list in slot
+ *   order, VG_INVALID_ID slots skipped wherever they sit; then, for i = 0 .. n-1 in id order, a fresh BFS from every i
+ *   still unvisited.  Self edges and ids listed twice are harmless: a visited node is never queued again.
+ * Afterwards the index is the segment the writer flushes: graph row new = old row perm[new] with every id mapped
+ *   through inv_perm (slot order and VG_INVALID_ID slots keep their places), entry point inv_perm[entry] (= 0), and
+ *   every per-row array permuted the same way: fp32 rows and their norms, the bf16 filter image, the PQ codes (rows,
+ *   tiles, nomination image and norms), the RaBitQ codes (rows, tiles, norms; the largest |norm| stays), the SQ8 tiles
+ *   and nomination image with its norms, the INT4 rows.  Row-count-invariant state (largest norms, quantizers, flat
+ *   search counters) does not change.  The caller permutes what the index never held: ids, metadata, payloads.
+ * Refusals, in this order, with nothing changed and nothing written: NULL index VG_ERR_INVALID_ARG; no Vamana graph
+ *   VG_ERR_NOT_READY; an HNSW graph, HNSW tombstones, HNSW edge distances or IVF partitions (memtable / flat segment
+ *   state) VG_ERR_UNSUPPORTED.  n = 0 is VG_OK with nothing done.
+ * Memory: one scratch buffer of the largest permuted array and O(n) for the BFS, released before the call returns. */
+int32_t vg_vamana_reorder_bfs(vg_index *idx, uint32_t *perm, uint32_t *inv_perm, void *stream);
 
 /* fp32 rows of the segment, n*dim row-major — the layout of
  * vectorstore.ColumnarStore (internal/vectorstore/columnar.go:21-24) and of

@@ -658,6 +658,9 @@ public:
     {
         check(vg_vamana_build(h_, r, l, alpha, initGraph, seed, maxBatch, growthDiv, nullptr));
     }
+    // diskann.Writer.reorderBFS (reorder.go:14-157): the graph and every per-row array into BFS order; perm[new] = old,
+    // invPerm[old] = new (either may be null; host or device)
+    void ReorderVamanaBFS(uint32_t *perm, uint32_t *invPerm) { check(vg_vamana_reorder_bfs(h_, perm, invPerm, nullptr)); }
     // the Vamana graph (n * r ids, VG_INVALID_ID = empty slot) and its entry point
     std::vector<uint32_t> VamanaGraph(int *r, uint32_t *entry) const
     {

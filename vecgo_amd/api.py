@@ -1076,6 +1076,16 @@ class Index:
             check(self._lib.vg_index_get_vamana_graph(self._h, None, None, C.c_void_p(g.ctypes.data), sp))
         return g, int(ep.value)
 
+    def reorder_vamana_bfs(self, stream=None):
+        """diskann.Writer.reorderBFS on the GPU (diskann/reorder.go:14-157; the rules are vg_vamana_reorder_bfs's in the
+        header): the graph, its entry point and every per-row array of the index move into BFS order.  Returns
+        (perm, inv_perm), np.uint32 of length n: perm[new] = old, inv_perm[old] = new."""
+        perm = np.empty(self.n, np.uint32)
+        inv = np.empty(self.n, np.uint32)
+        check(self._lib.vg_vamana_reorder_bfs(self._h, C.c_void_p(perm.ctypes.data), C.c_void_p(inv.ctypes.data),
+                                              _stream_ptr(stream)))
+        return perm, inv
+
     def _graph_search(self, fn, queries, k, mid_arg, want_stats, stream):
         nq = _rows(queries, self.dim)
         q, pq_ = _ptr(queries, np.float32)

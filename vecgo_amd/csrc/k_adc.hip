@@ -78,6 +78,14 @@ __global__ void pq_retile_kernel(const uint8_t *__restrict__ codes, int64_t n, i
     }
     tiles[gid] = make_uint4(w[0], w[1], w[2], w[3]);
 }
+// (vg_vamana_reorder_bfs rebuilds the tiles from its permuted row-major codes: k_vamana_reorder.hip)
+int32_t launch_pq_retile(const uint8_t *codes, int64_t n, int m, int groups, int64_t n_tiles, uint8_t *tiles, hipStream_t st)
+{
+    const int64_t total = n_tiles * groups * 64;
+    VG_LAUNCH(pq_retile_kernel, dim3(static_cast<unsigned>((total + 255) / 256)), dim3(256), 0, st, codes, n, m, groups, n_tiles,
+              reinterpret_cast<uint4 *>(tiles));
+    return VG_OK;
+}
 
 __device__ __forceinline__ uint32_t code_byte(const uint4 &c, int l)
 {

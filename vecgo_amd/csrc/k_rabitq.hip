@@ -135,6 +135,15 @@ __global__ void rabitq_retile_kernel(const uint8_t *__restrict__ codes, int64_t 
     }
     tiles[gid] = make_uint4(w[0], w[1], w[2], w[3]);
 }
+// (vg_vamana_reorder_bfs rebuilds the tiles and norms[0, n) from its permuted row-major codes: k_vamana_reorder.hip)
+int32_t launch_rabitq_retile(const uint8_t *codes, int64_t n, int nb, int groups, int64_t n_tiles, uint8_t *tiles, float *norms,
+                             hipStream_t st)
+{
+    const int64_t total = n_tiles * groups * 64;
+    VG_LAUNCH(rabitq_retile_kernel, dim3(static_cast<unsigned>((total + 255) / 256)), dim3(256), 0, st, codes, n, nb, groups, n_tiles,
+              reinterpret_cast<uint4 *>(tiles), norms);
+    return VG_OK;
+}
 
 // Exhaustive RaBitQ scan with fused top-k.  HBM-bound: (16*groups + 4) bytes per row.
 constexpr int kRqTiles = 2;  // 64-row tiles per trip of the d = 768 scan (4 is no faster)
