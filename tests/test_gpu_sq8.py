@@ -226,7 +226,7 @@ def test_nomination_with_dot_metric_and_filters(vg, ctx, metric, n, nq):
 @pytest.mark.parametrize("metric", [0, 2])
 def test_probed_batches_through_the_grouped_nomination(vg, ctx, metric, dim):
     """a partitioned SQ8 segment, partitions probed by many queries each: the grouped bf16 nomination per (query, probe) pair +
-    sq8_verify_kernel — nomination on = off = the oracle, with and without a filter"""
+    nominated_verify_kernel<Sq8Row> — nomination on = off = the oracle, with and without a filter"""
     from tests.test_gpu_probe import partitioned
     rng = np.random.default_rng(70 + metric)
     n, parts, nq, k = 12000, 6, 120, 10               # (dim 100: the bf16 image padded to 128)
@@ -258,7 +258,7 @@ def test_probed_batches_through_the_grouped_nomination(vg, ctx, metric, dim):
 @pytest.mark.parametrize("metric", [0, 2])
 def test_nomination_with_k_beyond_the_64_candidate_budget(vg, ctx, metric):
     """48 < k <= 256 over the whole segment, up to 160 over probed partitions: every row below the (deeper) threshold is re-scored
-    from the codes and sorted (sq8_verify_sort_kernel) — nomination on = off = the oracle, ties across the k-th place and
+    from the codes and sorted (nominated_verify_sort_kernel<Sq8Row>) — nomination on = off = the oracle, ties across the k-th place and
     filters included"""
     from tests.test_gpu_probe import partitioned
     rng = np.random.default_rng(170 + metric)

@@ -30,6 +30,7 @@
 #include "vg_device.hpp"
 #include "vg_internal.hpp"
 #include "vg_cand_replay.hpp"
+#include "vg_nominate.hpp"
 
 namespace vg {
 
@@ -1088,14 +1089,7 @@ VG_API int32_t vg_index_set_pq_codes(vg_index *idx, vg_pq *pq, const uint8_t *co
         VG_HIP(hipFree(idx->d_pq_tiles));
         idx->d_pq_tiles = nullptr;
     }
-    if (idx->d_pq_bf16) {  // the old codes' nomination image (vg_index_enable_pq_nomination again after new codes)
-        VG_HIP(hipStreamSynchronize(st));
-        VG_HIP(hipFree(idx->d_pq_bf16));
-        VG_HIP(hipFree(idx->d_pq_norms));
-        VG_HIP(hipFree(idx->d_pq_norm_max));
-        idx->d_pq_bf16 = nullptr;
-        idx->d_pq_norms = idx->d_pq_norm_max = nullptr;
-    }
+    VG_TRY(vg::nom_free(idx->pq_nom, st));  // the old codes' nomination image (vg_index_enable_pq_nomination again after new codes)
     idx->pq = pq;
     idx->pq_groups = (pq->m + 15) / 16;
     idx->n_tiles = (idx->n + 63) / 64;
@@ -1122,25 +1116,16 @@ VG_API int32_t vg_index_set_pq_codes(vg_index *idx, vg_pq *pq, const uint8_t *co
 // ---- batched search through a bfloat16 nomination (vg_index_enable_pq_nomination) ----------------------------------------------
 // One table scan per query runs at the LDS gather rate: 12.5 ms for 1024 queries x 1M x m = 96.  A row's table sum IS a squared
 // distance — sum_j |q_j - C_j[code_j]|^2 = |q - x^|^2 for the DECODED row x^ (pq.go:185-229; the table entries are computed from
-// the same fp32 centroid values, pq.go:468-491) — so with the opt-in image (x^ rounded to bfloat16, 2 bytes per dimension) the fused
-// flat search's nomination runs on it (k_flat.hip flat_nominate_bf16: threshold from a row sample, bf16 MFMA GEMM, the 64 best per
-// query), and this file re-scores those with the reference's own arithmetic — BuildDistanceTable + pqAdcLookupAvx512 on the CODES
-// — and proves that no row outside them can enter the k best: outside rows have GEMM score >= tau, and
-// |GEMM score + |q|^2 - table sum| <= eps (bfloat16 rounding of both operands, fp32 accumulation on both sides).  A query whose
-// proof fails is scanned as before.  The structure is the SQ8 batch search's (k_sq8.hip).
+// the same fp32 centroid values, pq.go:468-491) — so with the opt-in image (x^ rounded to bfloat16, 2 bytes per dimension) the batch
+// runs the shared nomination (vg_nominate.hpp), re-scores with the reference's own arithmetic — BuildDistanceTable +
+// pqAdcLookupAvx512 on the CODES (PqTableRow) — and proves the result (bfloat16 rounding of both operands, fp32 accumulation on
+// both sides).  A query whose proof fails is scanned as before.
 namespace vg {
-size_t flat_nominate_bf16_scratch(int64_t cnt, int64_t n, int dim, int sel_k);
-int32_t flat_nominate_bf16(vg_ctx *ctx, const uint16_t *rows_bf16, const float *norms, int64_t n, int dim, int dim_pad, const float *queries,
-                           int64_t cnt, char *scratch, float *thr, int *counts, uint32_t *cand_id, float *cand_sc, hipStream_t st,
-                           bool dot, const uint8_t *mask, int64_t mask_stride, int sel_k, bool pick, const uint64_t **cand_keys, int *cap,
-                           const float *norm_max);
-constexpr int kPqPickMaxK = 48, kPqNomMaxK = 256;  // as kSq8PickMaxK / kSq8NomMaxK
 // the batches the nomination takes: 1M x 768, m = 96, k = 10: 16 queries 0.24 ms scanned / 0.39 nominated, 32: 0.46 / 0.41, 64: 0.86 /
 // 0.43, 1024: 12.4 / 1.7 (tools/pq_nominate_time.py) — the scan costs ~12 us per query and 1M rows, the nomination ~0.4 ms up to
 // 128 queries; 100k rows: 128 queries 0.27 / 0.31, 256: 0.50 / 0.28 — from 24M (query, row) pairs up.  Test hook VG_PQ_NOM_ALWAYS:
 // every batch.
 constexpr int64_t kPqNomMinPairs = 24000000;
-static int pq_nominate_sel_k(int k) { return k <= kPqPickMaxK ? 8 : k <= 128 ? 16 : 32; }
 
 // one wave per row: lane l decodes sub-quantizers l, l + 64, ... — v = float32(int8) * scale ; v = v + offset, the two rounded
 // operations of the reference's dequantisation (pq.go:204-214) — rounds to bfloat16 (nearest even), writes the image row
@@ -1206,136 +1191,23 @@ __device__ __forceinline__ float pq_nominate_eps(int dim, int m, int sd, float q
     return ((4.0f * static_cast<float>(dim) + 2.0f * static_cast<float>(m + sd + 6)) * 5.9604645e-8f + 0.0078125f * 1.02f) * (qn + norm_max) + 1e-30f;
 }
 
-// per query: the table sum of its 64 nominated rows from the codes, the k best by (score, row id), and the proof (sq8_verify_kernel's)
-__global__ __launch_bounds__(64) void pq_verify_kernel(const uint8_t *__restrict__ codes, int m, int sd, const float *__restrict__ tables,
-                                                       const float *__restrict__ queries, const float *__restrict__ norm_max,
-                                                       const uint32_t *__restrict__ cand_ids, const float *__restrict__ cand_scores, int k,
-                                                       uint32_t *__restrict__ ids, float *__restrict__ scores, int *__restrict__ fail,
-                                                       const float *__restrict__ thr, const int *__restrict__ counts, int cap, int thr_stride)
-{
-    constexpr int kc = 64;
-    const int64_t q = blockIdx.x;
-    const int lane = threadIdx.x;
-    const int dim = m * sd;
-    const float *qv = queries + q * dim;
-    const uint32_t id = cand_ids[q * kc + lane];
-    uint64_t key = kKeyMax;
-    if (id != VG_INVALID_ID) key = make_key(pq_adc_row_score(tables + q * m * 256, codes + static_cast<int64_t>(id) * m, m), id, false);
-    WaveTopK tk;
-    tk.init(k);
-    tk.offer(key, lane);
-    float qn = 0.0f;
-    for (int j = lane; j < dim; j += 64) qn = __builtin_fmaf(qv[j], qv[j], qn);
-    for (int off = 32; off > 0; off >>= 1) qn += __shfl_xor(qn, off);
-    const uint64_t kth = readlane_u64(tk.list, k - 1);
-    const float tq = thr[q * thr_stride + (thr_stride - 1)];
-    const int cnt = counts[q];
-    bool ok = cnt <= cap;  // overflow: rows below the threshold were dropped
-    const float tau = cnt > kc ? fminf(tq, cand_scores[q * kc + (kc - 1)]) : tq;
-    const bool have_all = tq == INFINITY && cnt <= kc;
-    if (ok && !have_all && tau != INFINITY) {
-        const float eps = pq_nominate_eps(dim, m, sd, qn, norm_max[0]);
-        ok = kth != kKeyMax && key_score(kth, false) < (tau + qn) - eps;
+// the verify pair's Row (vg_nominate.hpp): the table sum of a nominated row from the codes against query q's table
+struct PqTableRow {
+    const uint8_t *codes;  // n * m, row-major
+    const float *tables;   // per query: m rows of 256
+    int m, sd, dim;        // dim = m * sd
+    __device__ float score(int64_t q, const float *, uint32_t id) const
+    {
+        return pq_adc_row_score(tables + q * m * 256, codes + static_cast<int64_t>(id) * m, m);
     }
-    if (lane < k) {
-        const uint64_t e = tk.list;
-        ids[q * k + lane] = e == kKeyMax ? VG_INVALID_ID : key_row(e);
-        scores[q * k + lane] = e == kKeyMax ? INFINITY : key_score(e, false);
-    }
-    if (lane == 0) fail[q] = ok ? 0 : 1;
-}
-
-// the same for k beyond the 64-candidate budget: EVERY appended row is re-scored — one lane per row — and sorted; the proof
-// compares the k-th exact score with the threshold itself (sq8_verify_sort_kernel's).  Dynamic LDS: cap keys.
-__global__ __launch_bounds__(256) void pq_verify_sort_kernel(const uint8_t *__restrict__ codes, int m, int sd, const float *__restrict__ tables,
-                                                             const float *__restrict__ queries, const float *__restrict__ norm_max,
-                                                             const uint64_t *__restrict__ cand, const int *__restrict__ counts, int cap, int k,
-                                                             uint32_t *__restrict__ ids, float *__restrict__ scores, int *__restrict__ fail,
-                                                             const float *__restrict__ thr, int thr_stride)
-{
-    extern __shared__ uint64_t sortbuf[];
-    const int64_t q = blockIdx.x;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int dim = m * sd;
-    const float *qv = queries + q * dim;
-    const int total = counts[q];
-    const int cnt = total < cap ? total : cap;
-    int n2 = 64;
-    while (n2 < cnt) n2 <<= 1;
-    for (int c = tid; c < cnt; c += 256) {
-        const uint32_t id = key_row(cand[q * cap + c]);
-        sortbuf[c] = make_key(pq_adc_row_score(tables + q * m * 256, codes + static_cast<int64_t>(id) * m, m), id, false);
-    }
-    for (int i = cnt + tid; i < n2; i += 256) sortbuf[i] = kKeyMax;
-    __syncthreads();
-    bitonic_sort_lds(sortbuf, n2, tid, 256);
-    for (int i = tid; i < k; i += 256) {
-        const uint64_t e = i < n2 ? sortbuf[i] : kKeyMax;
-        ids[q * k + i] = e == kKeyMax ? VG_INVALID_ID : key_row(e);
-        scores[q * k + i] = e == kKeyMax ? INFINITY : key_score(e, false);
-    }
-    if (tid >= 64) return;
-    float qn = 0.0f;
-    for (int j = lane; j < dim; j += 64) qn = __builtin_fmaf(qv[j], qv[j], qn);
-    for (int off = 32; off > 0; off >>= 1) qn += __shfl_xor(qn, off);
-    const uint64_t kth = k - 1 < n2 ? sortbuf[k - 1] : kKeyMax;
-    const float tau = thr[q * thr_stride + (thr_stride - 1)];
-    bool ok = total <= cap;
-    if (ok && tau != INFINITY)  // (tau == +Inf: no threshold was set, every row was appended)
-        ok = kth != kKeyMax && key_score(kth, false) < (tau + qn) - pq_nominate_eps(dim, m, sd, qn, norm_max[0]);
-    if (lane == 0) fail[q] = ok ? 0 : 1;
-}
+    __device__ float eps(float qn, float norm_max) const { return pq_nominate_eps(dim, m, sd, qn, norm_max); }
+};
 
 // whether a batch takes the nomination (device queries; ascending table sums over the whole segment, no row filter)
 static bool pq_nomination_applies(const vg_index *idx, const float *d_queries, int64_t nq, int k, const uint8_t *mask, bool desc)
 {
-    return idx->d_pq_bf16 && !mask && !desc && (nq * idx->n >= kPqNomMinPairs || hook(kHookPqNomAlways)) && k <= kPqNomMaxK && idx->n > k && idx->pq->k == 256 &&
+    return idx->pq_nom.rows && !mask && !desc && (nq * idx->n >= kPqNomMinPairs || hook(kHookPqNomAlways)) && k <= kNomMaxK && idx->n > k && idx->pq->k == 256 &&
            (reinterpret_cast<uintptr_t>(d_queries) & 15) == 0;
-}
-
-// The nomination + table sums + proof for a batch (device buffers): writes every query's k results and lists the queries whose
-// proof failed — the caller scans those.  4096 queries a pass.
-static int32_t pq_nominated_pass(vg_index *idx, const float *q, int64_t nq, int k, uint32_t *oid, float *osc, hipStream_t st,
-                                 std::vector<int> &failed)
-{
-    const vg_pq *pq = idx->pq;
-    for (int64_t q0 = 0; q0 < nq; q0 += 4096) {
-        const int64_t cnt = std::min<int64_t>(4096, nq - q0);
-        std::vector<int> h(static_cast<size_t>(cnt));
-        {
-            ArenaCall ar(idx->ctx, st);
-            const int sel_k = pq_nominate_sel_k(k);
-            const int i_scr = ar.add(flat_nominate_bf16_scratch(cnt, idx->n, idx->pq_bf16_dim, sel_k));
-            const int i_thr = ar.add(sizeof(float) * static_cast<size_t>(cnt) * sel_k);
-            const int i_cnt = ar.add(sizeof(int) * static_cast<size_t>(cnt));
-            const int i_cid = ar.add(sizeof(uint32_t) * static_cast<size_t>(cnt) * 64);
-            const int i_csc = ar.add(sizeof(float) * static_cast<size_t>(cnt) * 64);
-            const int i_fail = ar.add(sizeof(int) * static_cast<size_t>(cnt));
-            const int i_tab = ar.add(sizeof(float) * static_cast<size_t>(cnt) * pq->m * 256);
-            VG_TRY(ar.commit());
-            float *thr = ar.get<float>(i_thr), *csc = ar.get<float>(i_csc), *tables = ar.get<float>(i_tab);
-            int *counts = ar.get<int>(i_cnt), *fail = ar.get<int>(i_fail);
-            uint32_t *cid = ar.get<uint32_t>(i_cid);
-            const float *qq = q + q0 * idx->dim;
-            const uint64_t *cand = nullptr;
-            int cap = 0;
-            VG_TRY(launch_pq_build_table(pq, qq, cnt, tables, false, st));
-            VG_TRY(flat_nominate_bf16(idx->ctx, idx->d_pq_bf16, idx->d_pq_norms, idx->n, idx->dim, idx->pq_bf16_dim, qq, cnt, ar.get<char>(i_scr),
-                                      thr, counts, cid, csc, st, false, nullptr, 0, sel_k, k <= kPqPickMaxK, &cand, &cap, idx->d_pq_norm_max));
-            if (k <= kPqPickMaxK)
-                VG_LAUNCH(pq_verify_kernel, dim3(static_cast<unsigned>(cnt)), dim3(64), 0, st, idx->d_pq_rows, pq->m, pq->subdim, tables, qq,
-                          idx->d_pq_norm_max, cid, csc, k, oid + q0 * k, osc + q0 * k, fail, thr, counts, cap, sel_k);
-            else
-                VG_LAUNCH(pq_verify_sort_kernel, dim3(static_cast<unsigned>(cnt)), dim3(256), sizeof(uint64_t) * static_cast<size_t>(cap), st,
-                          idx->d_pq_rows, pq->m, pq->subdim, tables, qq, idx->d_pq_norm_max, cand, counts, cap, k, oid + q0 * k, osc + q0 * k,
-                          fail, thr, sel_k);
-            VG_HIP(hipMemcpyAsync(h.data(), fail, sizeof(int) * static_cast<size_t>(cnt), hipMemcpyDeviceToHost, st));
-            VG_HIP(hipStreamSynchronize(st));
-        }
-        for (int64_t i = 0; i < cnt; i++)
-            if (h[static_cast<size_t>(i)]) failed.push_back(static_cast<int>(q0 + i));
-    }
-    return VG_OK;
 }
 }  // namespace vg
 
@@ -1344,44 +1216,16 @@ VG_API int32_t vg_index_enable_pq_nomination(vg_index *idx, int32_t on, void *st
     VG_CHECK(idx, VG_ERR_INVALID_ARG, "vg_index_enable_pq_nomination: NULL index");
     VG_HIP(hipSetDevice(idx->ctx->device));
     hipStream_t st = vg::pick_stream(idx->ctx, stream);
-    if (idx->d_pq_bf16) {
-        VG_HIP(hipStreamSynchronize(st));
-        VG_HIP(hipFree(idx->d_pq_bf16));
-        VG_HIP(hipFree(idx->d_pq_norms));
-        VG_HIP(hipFree(idx->d_pq_norm_max));
-        idx->d_pq_bf16 = nullptr;
-        idx->d_pq_norms = idx->d_pq_norm_max = nullptr;
-    }
+    VG_TRY(vg::nom_free(idx->pq_nom, st));
     if (!on) return VG_OK;
     VG_CHECK(idx->pq && idx->d_pq_rows, VG_ERR_NOT_READY, "vg_index_enable_pq_nomination: index has no PQ codes");
     const vg_pq *pq = idx->pq;
     VG_CHECK(pq->trained, VG_ERR_NOT_TRAINED, "ProductQuantizer not trained");
     VG_CHECK(pq->k == 256, VG_ERR_UNSUPPORTED, "vg_index_enable_pq_nomination: needs numCentroids == 256 (got %d), as the table scan does", pq->k);
-    const int bdim = (idx->dim + 63) & ~63;  // whole K steps of the bf16 GEMM; the padding is zeros
-    // the three arrays are published together, after the image is built: a failure half way leaves the index as it was
-    uint16_t *img = nullptr;
-    float *norms = nullptr, *norm_max = nullptr;
-    auto give_up = [&](hipError_t e) {
-        (void)hipFree(img);
-        (void)hipFree(norms);
-        (void)hipFree(norm_max);
-        return e;
-    };
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(&img), static_cast<size_t>(idx->n) * bdim * sizeof(uint16_t));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&norms), static_cast<size_t>(idx->n) * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&norm_max), sizeof(float));
-    if (e == hipSuccess) e = hipMemsetAsync(norm_max, 0, sizeof(float), st);
-    if (e != hipSuccess) VG_HIP(give_up(e));
-    hipLaunchKernelGGL(vg::pq_decode_bf16_kernel, dim3(static_cast<unsigned>((idx->n + 3) / 4)), dim3(256), 0, st, idx->d_pq_rows, idx->n, pq->m,
-                       pq->k, pq->subdim, pq->d_codebooks, pq->d_scales, pq->d_offsets, img, bdim, norms, reinterpret_cast<int *>(norm_max));
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) VG_HIP(give_up(e));
-    idx->pq_bf16_dim = bdim;
-    idx->d_pq_bf16 = img;
-    idx->d_pq_norms = norms;
-    idx->d_pq_norm_max = norm_max;
-    return VG_OK;
+    return vg::nom_build(idx->pq_nom, idx->n, idx->dim, st, [&](const vg::NomImage &b, int *norm_max_bits) {
+        hipLaunchKernelGGL(vg::pq_decode_bf16_kernel, dim3(static_cast<unsigned>((idx->n + 3) / 4)), dim3(256), 0, st, idx->d_pq_rows, idx->n,
+                           pq->m, pq->k, pq->subdim, pq->d_codebooks, pq->d_scales, pq->d_offsets, b.rows, b.dim_pad, b.norms, norm_max_bits);
+    });
 }
 
 namespace vg {
@@ -1527,25 +1371,20 @@ static int32_t pq_adc_search_impl(vg_index *idx, const float *queries, int64_t n
         VG_TRY(vg::launch_topk_merge(none.ptr, nq, 1, k, false, oid.ptr, osc.ptr, st));
     } else if (allow_nomination && vg::pq_nomination_applies(idx, q.ptr, nq, k, mask, desc)) {
         std::vector<int> failed;
-        VG_TRY(vg::pq_nominated_pass(idx, q.ptr, nq, k, oid.ptr, osc.ptr, st, failed));
-        if (!failed.empty()) {  // the table scan for the queries whose proof failed (ties at the k-th score, thresholds too tight)
-            const int64_t nf = static_cast<int64_t>(failed.size());
-            vg::DevTmp<float> fq;
-            vg::DevTmp<uint32_t> fid;
-            vg::DevTmp<float> fsc;
-            VG_TRY(fq.init(static_cast<size_t>(nf) * idx->dim, st));
-            VG_TRY(fid.init(static_cast<size_t>(nf) * k, st));
-            VG_TRY(fsc.init(static_cast<size_t>(nf) * k, st));
-            for (int64_t i = 0; i < nf; i++)
-                VG_HIP(hipMemcpyAsync(fq.ptr + i * idx->dim, q.ptr + static_cast<int64_t>(failed[static_cast<size_t>(i)]) * idx->dim,
-                                      sizeof(float) * idx->dim, hipMemcpyDeviceToDevice, st));
-            VG_TRY(pq_adc_search_impl(idx, fq.ptr, nf, k, nullptr, 0, false, fid.ptr, fsc.ptr, st, false));
-            for (int64_t i = 0; i < nf; i++) {
-                const int64_t at = static_cast<int64_t>(failed[static_cast<size_t>(i)]) * k;
-                VG_HIP(hipMemcpyAsync(oid.ptr + at, fid.ptr + i * k, sizeof(uint32_t) * k, hipMemcpyDeviceToDevice, st));
-                VG_HIP(hipMemcpyAsync(osc.ptr + at, fsc.ptr + i * k, sizeof(float) * k, hipMemcpyDeviceToDevice, st));
-            }
-        }
+        // per pass: the queries' tables (BuildDistanceTable, the reference's layout), then the table sums of the nominees
+        auto verify = [&](const float *qq, int64_t cnt, const vg::ProbeNominated &nom, float *tables, uint32_t *pid, float *psc,
+                          int *fail) -> int32_t {
+            VG_TRY(vg::launch_pq_build_table(pq, qq, cnt, tables, false, st));
+            return vg::launch_nominated_verify<false>(vg::PqTableRow{idx->d_pq_rows, tables, pq->m, pq->subdim, idx->dim}, qq,
+                                                      idx->pq_nom.norm_max, cnt, nom, k, pid, psc, fail, st);
+        };
+        VG_TRY(vg::nominated_pass(idx, idx->pq_nom, false, q.ptr, nq, k, nullptr, 0, static_cast<size_t>(pq->m) * 256, oid.ptr, osc.ptr,
+                                  st, failed, verify));
+        // the table scan for the queries whose proof failed (ties at the k-th score, thresholds too tight)
+        VG_TRY(vg::rescan_failed(failed, q.ptr, idx->dim, k, nullptr, 0, 0, oid.ptr, osc.ptr, st,
+                                 [&](const float *fq, int64_t nf, const uint8_t *, int64_t, uint32_t *fid, float *fsc) {
+                                     return pq_adc_search_impl(idx, fq, nf, k, nullptr, 0, false, fid, fsc, st, false);
+                                 }));
     } else {
         int slices = vg::adc_slices(nq, idx->n_tiles, idx->ctx->compute_units);
         const bool bigk = k > 64;

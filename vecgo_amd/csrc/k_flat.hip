@@ -13,6 +13,7 @@
 #include "vg_cand_replay.hpp"
 #include "vg_flat_gemm.hpp"
 #include "vg_internal.hpp"
+#include "vg_nominate.hpp"
 
 namespace vg {
 
@@ -989,9 +990,9 @@ int32_t flat_probe_gemm(vg_index *idx, const float *pair_queries, int64_t pairs,
                         int ngroups, const int64_t grid[4], int sample_stride, int64_t ns_max, int k, uint32_t *pair_ids,
                         float *pair_scores, int *fail, char *scratch, const uint8_t *mask /* the batch's row filters, or null */,
                         const int64_t *mask_off /* [pairs]: byte offset of each bucketed pair's filter in `mask` */, hipStream_t st,
-                        const uint16_t *rows_bf16, const float *rows_norms, ProbeNominated *nominated)
+                        const NomImage &img, ProbeNominated *nominated)
 {
-    // rows_bf16 != null: nominate on that bfloat16 row image (with its norms) instead of the fp32 rows, and leave the exact
+    // img.rows != null: nominate on that bfloat16 row image (with its norms) instead of the fp32 rows, and leave the exact
     // re-score + proof to the caller: *nominated = where the per-pair thresholds / counts / 64 candidates are (the partition-probed
     // SQ8 scan, k_sq8.hip)
     // first_block / grid: [0] sample, [1] main launch of the 128-query tiles (groups of more than 64 pairs); [2], [3] the same of
@@ -999,13 +1000,13 @@ int32_t flat_probe_gemm(vg_index *idx, const float *pair_queries, int64_t pairs,
     // row tile, HBM-bound — a 128-query tile would spend the matrix cores on padding)
     const bool dot = idx->metric != VG_METRIC_L2;
     const int dim = idx->dim;
-    // (rows_bf16 == idx->d_vectors_bf16: the fp32 rows' own bf16 filter, vg_index_enable_bf16_filter — the nomination runs on it,
+    // (img.rows == idx->d_vectors_bf16: the fp32 rows' own bf16 filter, vg_index_enable_bf16_filter — the nomination runs on it,
     // the re-score and the proof below stay, the proof's margin widened as in vg_search_flat)
-    const bool bf16 = rows_bf16 != nullptr;
+    const bool bf16 = img.rows != nullptr;
     const int kc = 64, cap = kProbeGemmCap, sel_k = probe_gemm_sel_k(k, bf16);
-    const bool own_filter = bf16 && rows_bf16 == idx->d_vectors_bf16;
+    const bool own_filter = bf16 && img.rows == idx->d_vectors_bf16;
     const float *const queries_f32 = pair_queries;
-    const int bdim = !bf16 ? 0 : own_filter ? idx->vectors_bf16_dim : idx->sq_bf16_dim;  // row length of the bfloat16 image
+    const int bdim = img.dim_pad;  // row length of the bfloat16 image
     const ProbeGemmLayout l = probe_gemm_layout(pairs, ns_max, k, bdim);
     const int sel_slices = l.sel_slices;
     const float *grows = idx->d_vectors, *gnorms = idx->d_norms;
@@ -1015,8 +1016,8 @@ int32_t flat_probe_gemm(vg_index *idx, const float *pair_queries, int64_t pairs,
         VG_LAUNCH(f32_to_bf16_pad_kernel, dim3(static_cast<unsigned>((pairs * bdim + 255) / 256)), dim3(256), 0, st, pair_queries,
                   pairs, idx->dim, bdim, qbf);
         pair_queries = reinterpret_cast<const float *>(qbf);
-        grows = reinterpret_cast<const float *>(rows_bf16);
-        gnorms = rows_norms;
+        grows = reinterpret_cast<const float *>(img.rows);
+        gnorms = img.norms;
         gdim = bdim / 2;
     }
     float *sc = reinterpret_cast<float *>(scratch + l.sc), *thr = reinterpret_cast<float *>(scratch + l.thr);
@@ -1099,8 +1100,8 @@ int32_t flat_probe_gemm(vg_index *idx, const float *pair_queries, int64_t pairs,
 
 // The nomination stage of the fused flat search over ANY bfloat16 row image with its norms: thresholds from a row sample, the
 // bf16 MFMA GEMM appending what falls below them, the kc best per query — for a caller that re-scores and proves with its own
-// exact distance (the SQ8 batch search, k_sq8.hip: rows = the dequantised codes rounded to bfloat16, norms = |x^|^2).  L2 scores.
-// queries: cnt x dim fp32 (device), cnt <= 4096; rows_bf16: n x dim_pad (dim rounded up to a multiple of 64, the tail zeros).  Outputs (device, caller's):
+// exact distance (nominated_pass, vg_nominate.hpp: rows = a quantizer's decoded rows rounded to bfloat16, norms = |x^|^2).
+// queries: cnt x dim fp32 (device), cnt <= 4096; img: n rows of img.dim_pad (dim rounded up to a multiple of 64, the tail zeros).  Outputs (device, caller's):
 // thr[cnt * sel_k] (the threshold is a query's last entry), counts[cnt], cand_id / cand_sc[cnt * 64] ascending (pick only).
 namespace vg {
 constexpr int kNomKc = 64, kNomCap = 4096, kNomStride = 64;
@@ -1130,18 +1131,19 @@ static NominateLayout nominate_layout(int64_t cnt, int64_t n, int dim, int sel_k
     l.total = at;
     return l;
 }
-size_t flat_nominate_bf16_scratch(int64_t cnt, int64_t n, int dim, int sel_k) { return nominate_layout(cnt, n, dim, sel_k).total; }
+size_t flat_nominate_bf16_scratch(int64_t cnt, int64_t n, int dim_pad, int sel_k) { return nominate_layout(cnt, n, dim_pad, sel_k).total; }
 
-int32_t flat_nominate_bf16(vg_ctx *ctx, const uint16_t *rows_bf16, const float *norms, int64_t n, int dim, int dim_pad, const float *queries,
-                           int64_t cnt, char *scratch, float *thr, int *counts, uint32_t *cand_id, float *cand_sc, hipStream_t st,
-                           bool dot, const uint8_t *mask, int64_t mask_stride, int sel_k, bool pick, const uint64_t **cand_keys, int *cap,
-                           const float *norm_max)
+int32_t flat_nominate_bf16(vg_ctx *ctx, const NomImage &img, int64_t n, int dim, const float *queries, int64_t cnt, char *scratch,
+                           float *thr, int *counts, uint32_t *cand_id, float *cand_sc, hipStream_t st, bool dot, const uint8_t *mask,
+                           int64_t mask_stride, int sel_k, bool pick, const uint64_t **cand_keys, int *cap)
 {
     // dot: scores are -q.x (the largest dot products first); mask: a row filter per query (mask + q * mask_stride) or for the
     // batch (stride 0) — rejected rows are left out of the sample and of the candidates, as in flat_search_masked
     // sel_k: thresholds kept per query (thr[cnt * sel_k], the last is the query's: ~64 * sel_k rows pass it); pick: the 64 best
     // appended rows into cand_id / cand_sc; *cand_keys / *cap: every appended key, cap per query (in `scratch`)
-    // dim_pad: the image's row length (dim rounded up to whole 64-element K steps, the tail zeros); the queries are padded alike
+    // the queries are padded alike to the image's row length
+    const int dim_pad = img.dim_pad;
+    const float *norms = img.norms;
     const NominateLayout l = nominate_layout(cnt, n, dim_pad, sel_k);
     uint16_t *qbf = reinterpret_cast<uint16_t *>(scratch + l.qbf);
     float *sc = reinterpret_cast<float *>(scratch + l.sc);
@@ -1149,7 +1151,7 @@ int32_t flat_nominate_bf16(vg_ctx *ctx, const uint16_t *rows_bf16, const float *
     uint32_t *sid = reinterpret_cast<uint32_t *>(scratch + l.sid);
     const int64_t mt = (cnt + kGemmBM - 1) / kGemmBM, nt = (n + kGemmBN - 1) / kGemmBN, nst = l.ns / kGemmBN;
     VG_LAUNCH(f32_to_bf16_pad_kernel, dim3(static_cast<unsigned>((cnt * dim_pad + 255) / 256)), dim3(256), 0, st, queries, cnt, dim, dim_pad, qbf);
-    const float *ga = reinterpret_cast<const float *>(qbf), *gb = reinterpret_cast<const float *>(rows_bf16);
+    const float *ga = reinterpret_cast<const float *>(qbf), *gb = reinterpret_cast<const float *>(img.rows);
     const int gdim = dim_pad / 2;
     if (n > kNomCap) {
         VG_TRY(launch_gemm<1>(dot, true, static_cast<unsigned>(mt * ((nst + 7) / 8) * 8), st,
@@ -1160,8 +1162,7 @@ int32_t flat_nominate_bf16(vg_ctx *ctx, const uint16_t *rows_bf16, const float *
     } else {
         VG_LAUNCH(fill_f32_kernel, dim3(static_cast<unsigned>((cnt * sel_k + 255) / 256)), dim3(256), 0, st, thr, cnt * sel_k, INFINITY);
     }
-    // (norm_max: the largest of `norms`, device)
-    VG_LAUNCH(flat_thr_cap_kernel, dim3(static_cast<unsigned>(cnt)), dim3(64), 0, st, thr, sel_k, queries, dim, norm_max);
+    VG_LAUNCH(flat_thr_cap_kernel, dim3(static_cast<unsigned>(cnt)), dim3(64), 0, st, thr, sel_k, queries, dim, img.norm_max);
     VG_HIP(hipMemsetAsync(counts, 0, sizeof(int) * static_cast<size_t>(cnt), st));
     {
         ProfScope prof(ctx, "sq8_nominate_gemm", st);

@@ -1340,8 +1340,8 @@ VG_API int32_t vg_hnsw_insert(vg_index *idx, const float *rows, int64_t count, i
                        : (idx->d_rq_tiles || idx->d_rq_rows) ? "RaBitQ codes"
                        : idx->d_centroids                  ? "IVF partitions"
                        : idx->d_vamana                     ? "a Vamana graph"
-                       : idx->d_sq_bf16                    ? "an SQ8 nomination image"
-                       : idx->d_pq_bf16                    ? "a PQ nomination image"
+                       : idx->sq_nom.rows                  ? "an SQ8 nomination image"
+                       : idx->pq_nom.rows                  ? "a PQ nomination image"
                                                            : nullptr;
     VG_CHECK(!held, VG_ERR_UNSUPPORTED, "vg_hnsw_insert: the index holds %s, which the new rows would lack (segment state, "
              "not a memtable's)", held);

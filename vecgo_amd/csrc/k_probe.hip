@@ -14,6 +14,7 @@
 #include "vg_flat_gemm.hpp"
 #include "vg_internal.hpp"
 #include "vg_cand_replay.hpp"
+#include "vg_nominate.hpp"
 
 namespace vg {
 
@@ -40,16 +41,6 @@ int32_t pq_nan_replay(vg_index *idx, const float *d_queries, int64_t nq, int k, 
                       const uint32_t *d_probes, int np, const uint32_t *d_part_off, uint32_t *d_ids, float *d_scores, hipStream_t st);
 int32_t pq_adc_search_masked(vg_index *idx, const float *queries, int64_t nq, int32_t k, const uint8_t *mask, int64_t mask_stride,
                              bool desc, uint32_t *ids, float *scores, void *stream);
-size_t flat_probe_gemm_scratch_bytes(int64_t pairs, int64_t ns_max, int k, int bf16_dim);
-int32_t launch_sq8_verify(vg_index *idx, const float *queries, int64_t nq, const ProbeNominated &nom, int k, uint32_t *ids, float *scores,
-                          int *fail, hipStream_t st);
-int32_t flat_probe_gemm(vg_index *idx, const float *pair_queries, int64_t pairs, const GemmGroup *groups, const int64_t *const first_block[4],
-                        int ngroups, const int64_t grid[4], int sample_stride, int64_t ns_max, int k, uint32_t *pair_ids,
-                        float *pair_scores, int *fail, char *scratch, const uint8_t *mask, const int64_t *mask_off, hipStream_t st,
-                        const uint16_t *rows_bf16, const float *rows_norms, ProbeNominated *nominated);
-bool sq8_nomination_applies(const vg_index *idx, const float *d_queries, int64_t nq, int k);
-int32_t sq8_nominated_pass(vg_index *idx, const float *q, int64_t nq, int k, const uint8_t *mask, int64_t mask_stride, uint32_t *oid,
-                           float *osc, hipStream_t st, std::vector<int> &failed);
 int32_t launch_page_patch(int64_t nq, int k, int off, int kk, bool descending, const int *always_one,
                           const uint32_t *fids, const float *fscores, uint32_t *ids, float *scores, uint64_t *min_keys,
                           hipStream_t st);
@@ -736,6 +727,10 @@ static int32_t flat_probed_impl(vg_index *idx, const float *queries, int64_t nq,
     vg::DevIn<uint8_t> mk;
     const int64_t mask_bytes = (idx->n + 7) / 8;
     VG_TRY(mk.init(mask, mask ? static_cast<size_t>(mask_stride ? (nq - 1) * mask_stride + mask_bytes : mask_bytes) : 0, st));
+    // the queries whose proof failed, searched again without the nomination (rescan_failed, vg_nominate.hpp)
+    auto rescan = [&](const float *fq, int64_t nf, const uint8_t *fmask, int64_t fmask_stride, uint32_t *fid, float *fsc) {
+        return flat_probed_impl(idx, fq, nf, k, nprobes, scan, fmask, fmask_stride, fid, fsc, st, false);
+    };
 
     // A batch of filtered fp32 queries over the whole segment: the matrix-core nomination of vg_search_flat with the filter
     // applied where candidates are sampled and appended (k_flat.hip) — its cost does not depend on the selectivity, the
@@ -755,31 +750,7 @@ static int32_t flat_probed_impl(vg_index *idx, const float *queries, int64_t nq,
         !vg::hook(vg::kHookProbeNoGroup)) {
         std::vector<int> failed;
         VG_TRY(vg::sq8_nominated_pass(idx, q.ptr, nq, k, mk.ptr, mask_stride, oid.ptr, osc.ptr, st, failed));
-        if (!failed.empty()) {
-            const int64_t nf = static_cast<int64_t>(failed.size());
-            vg::DevTmp<float> fq;
-            vg::DevTmp<uint32_t> fid;
-            vg::DevTmp<float> fsc;
-            vg::DevTmp<uint8_t> fm;
-            VG_TRY(fq.init(static_cast<size_t>(nf) * idx->dim, st));
-            VG_TRY(fid.init(static_cast<size_t>(nf) * k, st));
-            VG_TRY(fsc.init(static_cast<size_t>(nf) * k, st));
-            VG_TRY(fm.init(mask_stride ? static_cast<size_t>(nf) * mask_bytes : 0, st));
-            for (int64_t i = 0; i < nf; i++) {
-                const int64_t src = failed[static_cast<size_t>(i)];
-                VG_HIP(hipMemcpyAsync(fq.ptr + i * idx->dim, q.ptr + src * idx->dim, sizeof(float) * idx->dim, hipMemcpyDeviceToDevice, st));
-                if (mask_stride)
-                    VG_HIP(hipMemcpyAsync(fm.ptr + i * mask_bytes, mk.ptr + src * mask_stride, static_cast<size_t>(mask_bytes),
-                                          hipMemcpyDeviceToDevice, st));
-            }
-            VG_TRY(flat_probed_impl(idx, fq.ptr, nf, k, nprobes, scan, mask_stride ? fm.ptr : mk.ptr, mask_stride ? mask_bytes : 0, fid.ptr,
-                                    fsc.ptr, st, false));
-            for (int64_t i = 0; i < nf; i++) {
-                const int64_t at = static_cast<int64_t>(failed[static_cast<size_t>(i)]) * k;
-                VG_HIP(hipMemcpyAsync(oid.ptr + at, fid.ptr + i * k, sizeof(uint32_t) * k, hipMemcpyDeviceToDevice, st));
-                VG_HIP(hipMemcpyAsync(osc.ptr + at, fsc.ptr + i * k, sizeof(float) * k, hipMemcpyDeviceToDevice, st));
-            }
-        }
+        VG_TRY(vg::rescan_failed(failed, q.ptr, idx->dim, k, mk.ptr, mask_stride, mask_bytes, oid.ptr, osc.ptr, st, rescan));
         VG_TRY(oid.finish());
         VG_TRY(osc.finish());
         if (oid.on_host() || osc.on_host()) VG_HIP(hipStreamSynchronize(st));
@@ -871,8 +842,8 @@ static int32_t flat_probed_impl(vg_index *idx, const float *queries, int64_t nq,
                             !vg::hook(vg::kHookProbeNoGroup) && !vg::hook(vg::kHookProbeNoGemm);
     const bool gemm_f32 = scan == VG_SCAN_F32 && gemm_shape && (reinterpret_cast<uintptr_t>(idx->d_vectors) & 15) == 0;
     // SQ8 with vg_index_enable_sq8_nomination: the same grouped nomination on the bfloat16 image of the dequantised rows, the
-    // pairs' 64 candidates re-scored from the codes and proven by sq8_verify_kernel (k_sq8.hip)
-    const bool gemm_sq8 = scan == VG_SCAN_SQ8 && gemm_shape && allow_nomination && idx->d_sq_bf16 != nullptr;
+    // pairs' 64 candidates re-scored from the codes and proven by the verify pair (launch_sq8_verify, k_sq8.hip)
+    const bool gemm_sq8 = scan == VG_SCAN_SQ8 && gemm_shape && allow_nomination && idx->sq_nom.rows != nullptr;
     const bool gemm = gemm_f32 || gemm_sq8;
     int64_t grids[4] = {0, 0, 0, 0}, ns_max = 0;  // sample / main of the 128-query tiles, sample / main of the 64-query tiles
     if (gemm) {  // launch bounds from the partition sizes: one query tile per partition + the batch's further tiles on the largest
@@ -913,7 +884,11 @@ static int32_t flat_probed_impl(vg_index *idx, const float *queries, int64_t nq,
     const int i_moff = ar.add(gemm ? sizeof(int64_t) * static_cast<size_t>(pairs) : 0);
     // (fp32 rows with vg_index_enable_bf16_filter: the grouped nomination on that image too)
     const bool gemm_f32_bf16 = gemm_f32 && idx->d_vectors_bf16 != nullptr;
-    const int i_gscr = ar.add(gemm ? vg::flat_probe_gemm_scratch_bytes(pairs, ns_max, k, gemm_sq8 ? idx->sq_bf16_dim : gemm_f32_bf16 ? idx->vectors_bf16_dim : 0) : 0);
+    // the image the grouped nomination runs on: none (the fp32 rows), the SQ8 image, or a view of the fp32 rows' bf16 filter
+    const vg::NomImage gimg = gemm_sq8        ? idx->sq_nom
+                              : gemm_f32_bf16 ? vg::NomImage{idx->d_vectors_bf16, idx->vectors_bf16_dim, idx->d_norms, idx->d_norm_max}
+                                              : vg::NomImage{};
+    const int i_gscr = ar.add(gemm ? vg::flat_probe_gemm_scratch_bytes(pairs, ns_max, k, gimg.dim_pad) : 0);
     VG_TRY(ar.commit());
     uint32_t *probes = probes_out && !whole ? probes_out : ar.get<uint32_t>(i_probes);
     uint64_t *partial = ar.get<uint64_t>(i_partial);
@@ -962,9 +937,7 @@ static int32_t flat_probed_impl(vg_index *idx, const float *queries, int64_t nq,
             const int64_t *const fb[4] = {fbs, fbm, fbss, fbsm};
             vg::ProbeNominated nom{};
             VG_TRY(vg::flat_probe_gemm(idx, pairq, pairs, bgrp, fb, parts, grids, vg::kProbeSampleStride, ns_max, k, pair_ids, pair_sc,
-                                       pfail, ar.get<char>(i_gscr), mk.ptr, moff, st,
-                                       gemm_sq8 ? idx->d_sq_bf16 : gemm_f32_bf16 ? idx->d_vectors_bf16 : nullptr,
-                                       gemm_sq8 ? idx->d_sq_norms : gemm_f32_bf16 ? idx->d_norms : nullptr, &nom));
+                                       pfail, ar.get<char>(i_gscr), mk.ptr, moff, st, gimg, &nom));
             if (gemm_sq8) VG_TRY(vg::launch_sq8_verify(idx, pairq, pairs, nom, k, pair_ids, pair_sc, pfail, st));
         }
         // lists = np * sub in this configuration; the pairs' k results fill the first np lists' worth of `partial`
@@ -972,38 +945,10 @@ static int32_t flat_probed_impl(vg_index *idx, const float *queries, int64_t nq,
                   partial, qfail);
         VG_TRY(vg::launch_topk_merge(partial, nq, np, k, desc, oid.ptr, osc.ptr, st));
         if (gemm_sq8 || k > 64) {  // the flagged queries (normally none) go through the scan kernels: read the flags, search that subset
-            std::vector<int> hq(static_cast<size_t>(nq));
-            VG_HIP(hipMemcpyAsync(hq.data(), qfail, sizeof(int) * static_cast<size_t>(nq), hipMemcpyDeviceToHost, st));
-            VG_HIP(hipStreamSynchronize(st));
             std::vector<int> failed;
-            for (int64_t i = 0; i < nq; i++)
-                if (hq[static_cast<size_t>(i)]) failed.push_back(static_cast<int>(i));
+            VG_TRY(vg::failed_list(qfail, nq, 0, st, failed));
             ar.lock.unlock();  // the subset's own search takes the arena
-            if (!failed.empty()) {
-                const int64_t nf = static_cast<int64_t>(failed.size());
-                vg::DevTmp<float> fq;
-                vg::DevTmp<uint32_t> fid;
-                vg::DevTmp<float> fsc;
-                vg::DevTmp<uint8_t> fm;
-                VG_TRY(fq.init(static_cast<size_t>(nf) * idx->dim, st));
-                VG_TRY(fid.init(static_cast<size_t>(nf) * k, st));
-                VG_TRY(fsc.init(static_cast<size_t>(nf) * k, st));
-                VG_TRY(fm.init(mk.ptr && mask_stride ? static_cast<size_t>(nf) * mask_bytes : 0, st));
-                for (int64_t i = 0; i < nf; i++) {
-                    const int64_t src = failed[static_cast<size_t>(i)];
-                    VG_HIP(hipMemcpyAsync(fq.ptr + i * idx->dim, q.ptr + src * idx->dim, sizeof(float) * idx->dim, hipMemcpyDeviceToDevice, st));
-                    if (mk.ptr && mask_stride)
-                        VG_HIP(hipMemcpyAsync(fm.ptr + i * mask_bytes, mk.ptr + src * mask_stride, static_cast<size_t>(mask_bytes),
-                                              hipMemcpyDeviceToDevice, st));
-                }
-                VG_TRY(flat_probed_impl(idx, fq.ptr, nf, k, nprobes, scan, mk.ptr ? (mask_stride ? fm.ptr : mk.ptr) : nullptr,
-                                        mask_stride ? mask_bytes : 0, fid.ptr, fsc.ptr, st, false));
-                for (int64_t i = 0; i < nf; i++) {
-                    const int64_t at = static_cast<int64_t>(failed[static_cast<size_t>(i)]) * k;
-                    VG_HIP(hipMemcpyAsync(oid.ptr + at, fid.ptr + i * k, sizeof(uint32_t) * k, hipMemcpyDeviceToDevice, st));
-                    VG_HIP(hipMemcpyAsync(osc.ptr + at, fsc.ptr + i * k, sizeof(float) * k, hipMemcpyDeviceToDevice, st));
-                }
-            }
+            VG_TRY(vg::rescan_failed(failed, q.ptr, idx->dim, k, mk.ptr, mask_stride, mask_bytes, oid.ptr, osc.ptr, st, rescan));
             VG_TRY(oid.finish());
             VG_TRY(osc.finish());
             if (oid.on_host() || osc.on_host()) VG_HIP(hipStreamSynchronize(st));

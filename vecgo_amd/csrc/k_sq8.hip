@@ -16,6 +16,7 @@
 #include "vg_device.hpp"
 #include "vg_internal.hpp"
 #include "vg_cand_replay.hpp"
+#include "vg_nominate.hpp"
 
 struct vg_int4 {
     vg_ctx *ctx = nullptr;
@@ -1528,28 +1529,16 @@ VG_API int32_t vg_sq8_l2_distance_batch(vg_sq8 *sq, const float *query, const ui
     return VG_OK;
 }
 
-// ---- batched L2 search through a bfloat16 nomination (vg_index_enable_sq8_nomination) -------------------------------------------
+// ---- batched search through a bfloat16 nomination (vg_index_enable_sq8_nomination) ---------------------------------------------
 // The multi-query scan decodes every code once per 4 queries and is bound by the vector ALU (44 ms per 1024 queries x 1M x 768).
-// With the opt-in image — the dequantised rows x^ = fma(code, invScale, min) rounded to bfloat16, 2 bytes per code — the fused flat
-// search's nomination runs on them (k_flat.hip flat_nominate_bf16: threshold from a row sample, bf16 MFMA GEMM, the 64 best per
-// query), and this file re-scores those 64 with the reference's own arithmetic on the CODES (sq8_row_score) and proves that no row
-// outside them can enter the k best: outside rows have GEMM score >= tau, and |GEMM score + |q|^2 - L2Distance| <= eps (bfloat16
-// rounding of both operands, fp32 accumulation, the reference's own rounding).  A query whose proof fails is scanned as before.
+// With the opt-in image — the dequantised rows x^ = fma(code, invScale, min) rounded to bfloat16, 2 bytes per code — the batch runs
+// the shared nomination (vg_nominate.hpp), re-scores with the reference's own arithmetic on the CODES (sq8_row_score, Sq8Row) and
+// proves the result (bfloat16 rounding of both operands, fp32 accumulation, the reference's own rounding).  A query whose proof
+// fails is scanned as before.
 namespace vg {
-size_t flat_nominate_bf16_scratch(int64_t cnt, int64_t n, int dim, int sel_k);
-int32_t flat_nominate_bf16(vg_ctx *ctx, const uint16_t *rows_bf16, const float *norms, int64_t n, int dim, int dim_pad, const float *queries,
-                           int64_t cnt, char *scratch, float *thr, int *counts, uint32_t *cand_id, float *cand_sc, hipStream_t st,
-                           bool dot, const uint8_t *mask, int64_t mask_stride, int sel_k, bool pick, const uint64_t **cand_keys, int *cap,
-                           const float *norm_max);
-// k <= 48: the 64 best nominees are re-scored (sq8_verify_kernel); up to 256: everything below the threshold
-// (sq8_verify_sort_kernel) — the 8th best of the 1/64 row sample passes ~512 rows, the 16th ~1024, the 32nd ~2048.  (The proof
-// wants the threshold 2^-7 (|q|^2 + |x^|^2) above the k-th score: ~512 rows for k = 100 left enough queries to the scan — random-
-// normal rows, 1M x 768 — that the batch took 8.3 ms, ~1024 rows 3 ms.)
-constexpr int kSq8PickMaxK = 48, kSq8NomMaxK = 256;
 #ifndef VG_SQ8_NOM_MIN_Q
 #define VG_SQ8_NOM_MIN_Q 5  // smallest batch the nomination takes: 1M x 768, scan / nominated ms: 4 queries 0.34 / 0.37, 6: 0.51 / 0.38, 16: 0.94 / 0.37
 #endif
-static int sq8_nominate_sel_k(int k) { return k <= kSq8PickMaxK ? 8 : k <= 128 ? 16 : 32; }
 
 __device__ __forceinline__ uint16_t sq8_bf16_rne(float x)
 {
@@ -1602,110 +1591,24 @@ __global__ __launch_bounds__(64) void sq8_dequant_bf16_kernel(const uint4 *__res
     if (lane == 0) atomicMax(norm_max_bits, __float_as_int(mx));  // non-negative floats order like their bits
 }
 
-// per query: exact L2Distance / DotProduct of its 64 nominated rows from the codes, the k best by (score, row id), and the proof
+// the verify pair's Row (vg_nominate.hpp): exact L2Distance / DotProduct of a nominated row from the codes
 template <bool DOT>
-__global__ __launch_bounds__(64) void sq8_verify_kernel(const uint4 *__restrict__ tiles, int groups, int dim, const float *__restrict__ mins,
-                                                        const float *__restrict__ inv, const float *__restrict__ queries,
-                                                        const float *__restrict__ norm_max, const uint32_t *__restrict__ cand_ids,
-                                                        const float *__restrict__ cand_scores, int k, uint32_t *__restrict__ ids,
-                                                        float *__restrict__ scores, int *__restrict__ fail, const float *__restrict__ thr,
-                                                        const int *__restrict__ counts, int cap, int thr_stride)
-{
-    constexpr int kc = 64;
-    const int64_t q = blockIdx.x;
-    const int lane = threadIdx.x;
-    const float *qv = queries + q * dim;
-    const uint32_t id = cand_ids[q * kc + lane];
-    uint64_t key = kKeyMax;
-    if (id != VG_INVALID_ID) {
-        const float d = sq8_row_score<DOT>(tiles + (static_cast<int64_t>(id >> 6) * groups) * 64 + (id & 63), groups, dim >> 4, dim & 15,
-                                           qv, mins, inv);
-        key = make_key(d, id, DOT);
+struct Sq8Row {
+    const uint4 *tiles;
+    int groups, dim;
+    const float *mins, *inv;
+    __device__ float score(int64_t, const float *qv, uint32_t id) const
+    {
+        return sq8_row_score<DOT>(tiles + (static_cast<int64_t>(id >> 6) * groups) * 64 + (id & 63), groups, dim >> 4, dim & 15, qv, mins, inv);
     }
-    WaveTopK tk;
-    tk.init(k);
-    tk.offer(key, lane);
-    float qn = 0.0f;
-    for (int j = lane; j < dim; j += 64) qn = __builtin_fmaf(qv[j], qv[j], qn);
-    for (int off = 32; off > 0; off >>= 1) qn += __shfl_xor(qn, off);
-    const uint64_t kth = readlane_u64(tk.list, k - 1);
-    const float tq = thr[q * thr_stride + (thr_stride - 1)];
-    const int cnt = counts[q];
-    bool ok = cnt <= cap;  // overflow: rows below the threshold were dropped
-    const float tau = cnt > kc ? fminf(tq, cand_scores[q * kc + (kc - 1)]) : tq;
-    const bool have_all = tq == INFINITY && cnt <= kc;
-    if (ok && !have_all && tau != INFINITY) {
-        // |s~ + |q|^2 - L2Distance|: bfloat16 rounding of q and x^ ((2^-7 + 2^-16)(|q|^2 + |x^|^2), as for the fp32 rows' bf16
-        // filter), the GEMM's fp32 accumulation and the reference's own 16-lane sums ((2 dim + dim/8 + 32) u of the same)
-        // (Dot: the score is -q.x^, half the L2 form's cross term: 2^-8 in place of 2^-7)
-        const float eps = (4.0f * (static_cast<float>(dim) * 5.9604645e-8f) + (DOT ? 0.00390625f : 0.0078125f) * 1.02f) * (qn + norm_max[0]) + 1e-30f;
-        if (kth == kKeyMax)
-            ok = false;
-        else if (DOT)
-            ok = key_score(kth, true) > (-tau) + eps;  // outside rows: -q.x >= tau
-        else
-            ok = key_score(kth, false) < (tau + qn) - eps;
+    // |s~ + |q|^2 - L2Distance|: bfloat16 rounding of q and x^ ((2^-7 + 2^-16)(|q|^2 + |x^|^2), as for the fp32 rows' bf16
+    // filter), the GEMM's fp32 accumulation and the reference's own 16-lane sums ((2 dim + dim/8 + 32) u of the same)
+    // (Dot: the score is -q.x^, half the L2 form's cross term: 2^-8 in place of 2^-7)
+    __device__ float eps(float qn, float norm_max) const
+    {
+        return (4.0f * (static_cast<float>(dim) * 5.9604645e-8f) + (DOT ? 0.00390625f : 0.0078125f) * 1.02f) * (qn + norm_max) + 1e-30f;
     }
-    if (lane < k) {
-        const uint64_t e = tk.list;
-        ids[q * k + lane] = e == kKeyMax ? VG_INVALID_ID : key_row(e);
-        scores[q * k + lane] = e == kKeyMax ? (DOT ? -INFINITY : INFINITY) : key_score(e, DOT);
-    }
-    if (lane == 0) fail[q] = ok ? 0 : 1;
-}
-
-// The same for k beyond the 64-candidate budget (flat_verify_sort_kernel's counterpart): EVERY appended row is re-scored from
-// the codes — one lane per row — and sorted; what is left to argue about is what the threshold excluded, so the proof compares
-// the k-th exact score with the threshold itself.  Dynamic LDS: cap keys.
-template <bool DOT>
-__global__ __launch_bounds__(256) void sq8_verify_sort_kernel(const uint4 *__restrict__ tiles, int groups, int dim, const float *__restrict__ mins,
-                                                              const float *__restrict__ inv, const float *__restrict__ queries,
-                                                              const float *__restrict__ norm_max, const uint64_t *__restrict__ cand,
-                                                              const int *__restrict__ counts, int cap, int k, uint32_t *__restrict__ ids,
-                                                              float *__restrict__ scores, int *__restrict__ fail, const float *__restrict__ thr,
-                                                              int thr_stride)
-{
-    extern __shared__ uint64_t sortbuf[];
-    const int64_t q = blockIdx.x;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const float *qv = queries + q * dim;
-    const int total = counts[q];
-    const int cnt = total < cap ? total : cap;
-    int n2 = 64;
-    while (n2 < cnt) n2 <<= 1;
-    for (int c = tid; c < cnt; c += 256) {
-        const uint32_t id = key_row(cand[q * cap + c]);
-        const float d = sq8_row_score<DOT>(tiles + (static_cast<int64_t>(id >> 6) * groups) * 64 + (id & 63), groups, dim >> 4, dim & 15,
-                                           qv, mins, inv);
-        sortbuf[c] = make_key(d, id, DOT);
-    }
-    for (int i = cnt + tid; i < n2; i += 256) sortbuf[i] = kKeyMax;
-    __syncthreads();
-    bitonic_sort_lds(sortbuf, n2, tid, 256);
-    for (int i = tid; i < k; i += 256) {
-        const uint64_t e = i < n2 ? sortbuf[i] : kKeyMax;
-        ids[q * k + i] = e == kKeyMax ? VG_INVALID_ID : key_row(e);
-        scores[q * k + i] = e == kKeyMax ? (DOT ? -INFINITY : INFINITY) : key_score(e, DOT);
-    }
-    if (tid >= 64) return;
-    float qn = 0.0f;
-    for (int j = lane; j < dim; j += 64) qn = __builtin_fmaf(qv[j], qv[j], qn);
-    for (int off = 32; off > 0; off >>= 1) qn += __shfl_xor(qn, off);
-    const uint64_t kth = k - 1 < n2 ? sortbuf[k - 1] : kKeyMax;
-    const float tau = thr[q * thr_stride + (thr_stride - 1)];
-    bool ok = total <= cap;
-    if (ok && tau != INFINITY) {  // (tau == +Inf: no threshold was set, every accepted row was appended)
-        // (the margin: sq8_verify_kernel's)
-        const float eps = (4.0f * (static_cast<float>(dim) * 5.9604645e-8f) + (DOT ? 0.00390625f : 0.0078125f) * 1.02f) * (qn + norm_max[0]) + 1e-30f;
-        if (kth == kKeyMax)
-            ok = false;
-        else if (DOT)
-            ok = key_score(kth, true) > (-tau) + eps;
-        else
-            ok = key_score(kth, false) < (tau + qn) - eps;
-    }
-    if (lane == 0) fail[q] = ok ? 0 : 1;
-}
+};
 }  // namespace vg
 
 VG_API int32_t vg_index_enable_sq8_nomination(vg_index *idx, int32_t on, void *stream)
@@ -1713,43 +1616,14 @@ VG_API int32_t vg_index_enable_sq8_nomination(vg_index *idx, int32_t on, void *s
     VG_CHECK(idx, VG_ERR_INVALID_ARG, "vg_index_enable_sq8_nomination: NULL index");
     VG_HIP(hipSetDevice(idx->ctx->device));
     hipStream_t st = vg::pick_stream(idx->ctx, stream);
-    if (idx->d_sq_bf16) {
-        VG_HIP(hipStreamSynchronize(st));
-        VG_HIP(hipFree(idx->d_sq_bf16));
-        VG_HIP(hipFree(idx->d_sq_norms));
-        VG_HIP(hipFree(idx->d_sq_norm_max));
-        idx->d_sq_bf16 = nullptr;
-        idx->d_sq_norms = idx->d_sq_norm_max = nullptr;
-    }
+    VG_TRY(vg::nom_free(idx->sq_nom, st));
     if (!on) return VG_OK;
     VG_CHECK(idx->sq && idx->d_sq_tiles, VG_ERR_NOT_READY, "vg_index_enable_sq8_nomination: index has no SQ8 codes");
-    const int bdim = (idx->dim + 63) & ~63;  // whole K steps of the bf16 GEMM; the padding is zeros
-    // the three arrays are published together, after the image is built: a failure half way leaves the index as it was (the
-    // batch search tests d_sq_bf16 alone — ADVICE r05: a failed second allocation left it set next to null norms)
-    uint16_t *img = nullptr;
-    float *norms = nullptr, *norm_max = nullptr;
-    auto give_up = [&](hipError_t e) {
-        (void)hipFree(img);
-        (void)hipFree(norms);
-        (void)hipFree(norm_max);
-        return e;
-    };
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(&img), static_cast<size_t>(idx->n) * bdim * sizeof(uint16_t));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&norms), static_cast<size_t>(idx->n) * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&norm_max), sizeof(float));
-    if (e == hipSuccess) e = hipMemsetAsync(norm_max, 0, sizeof(float), st);
-    if (e != hipSuccess) VG_HIP(give_up(e));
-    hipLaunchKernelGGL(vg::sq8_dequant_bf16_kernel, dim3(static_cast<unsigned>(idx->n_tiles)), dim3(64), 0, st,
-                       reinterpret_cast<const uint4 *>(idx->d_sq_tiles), idx->n, idx->dim, idx->sq_groups, idx->sq->d_mins, idx->sq->d_inv,
-                       img, bdim, norms, reinterpret_cast<int *>(norm_max));
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) VG_HIP(give_up(e));
-    idx->sq_bf16_dim = bdim;
-    idx->d_sq_bf16 = img;
-    idx->d_sq_norms = norms;
-    idx->d_sq_norm_max = norm_max;
-    return VG_OK;
+    return vg::nom_build(idx->sq_nom, idx->n, idx->dim, st, [&](const vg::NomImage &b, int *norm_max_bits) {
+        hipLaunchKernelGGL(vg::sq8_dequant_bf16_kernel, dim3(static_cast<unsigned>(idx->n_tiles)), dim3(64), 0, st,
+                           reinterpret_cast<const uint4 *>(idx->d_sq_tiles), idx->n, idx->dim, idx->sq_groups, idx->sq->d_mins, idx->sq->d_inv,
+                           b.rows, b.dim_pad, b.norms, norm_max_bits);
+    });
 }
 
 VG_API int32_t vg_index_set_sq8_codes(vg_index *idx, vg_sq8 *sq, const uint8_t *codes, void *stream)
@@ -1765,13 +1639,7 @@ VG_API int32_t vg_index_set_sq8_codes(vg_index *idx, vg_sq8 *sq, const uint8_t *
         VG_HIP(hipFree(idx->d_sq_tiles));
         idx->d_sq_tiles = nullptr;
     }
-    if (idx->d_sq_bf16) {  // the old codes' nomination image (vg_index_enable_sq8_nomination again after new codes)
-        VG_HIP(hipFree(idx->d_sq_bf16));
-        VG_HIP(hipFree(idx->d_sq_norms));
-        VG_HIP(hipFree(idx->d_sq_norm_max));
-        idx->d_sq_bf16 = nullptr;
-        idx->d_sq_norms = idx->d_sq_norm_max = nullptr;
-    }
+    VG_TRY(vg::nom_free(idx->sq_nom, st));  // the old codes' nomination image (vg_index_enable_sq8_nomination again after new codes)
     idx->sq = sq;
     idx->sq_groups = (idx->dim + 15) / 16;
     idx->n_tiles = (idx->n + 63) / 64;
@@ -1787,64 +1655,31 @@ VG_API int32_t vg_index_set_sq8_codes(vg_index *idx, vg_sq8 *sq, const uint8_t *
 }
 
 namespace vg {
-// sq8_verify_kernel over nq query rows whose nomination (8 thresholds, count, 64 candidates each) another file produced: the
-// partition-probed scan's (query, probe) pairs (k_probe.hip)
+// the verify pair over nq query rows whose nomination (thresholds, count, candidates each) the batch search or another file
+// produced: the partition-probed scan's (query, probe) pairs (k_probe.hip)
 int32_t launch_sq8_verify(vg_index *idx, const float *queries, int64_t nq, const ProbeNominated &nom, int k, uint32_t *ids, float *scores,
                           int *fail, hipStream_t st)
 {
-    const bool dot = idx->metric != VG_METRIC_L2;
-    if (k > kSq8PickMaxK) {
-        auto kern = dot ? sq8_verify_sort_kernel<true> : sq8_verify_sort_kernel<false>;
-        VG_LAUNCH(kern, dim3(static_cast<unsigned>(nq)), dim3(256), sizeof(uint64_t) * static_cast<size_t>(nom.cap), st,
-                  reinterpret_cast<const uint4 *>(idx->d_sq_tiles), idx->sq_groups, idx->dim, idx->sq->d_mins, idx->sq->d_inv, queries,
-                  idx->d_sq_norm_max, nom.cand, nom.counts, nom.cap, k, ids, scores, fail, nom.thr, nom.sel_k);
-        return VG_OK;
-    }
-    auto kern = dot ? sq8_verify_kernel<true> : sq8_verify_kernel<false>;
-    VG_LAUNCH(kern, dim3(static_cast<unsigned>(nq)), dim3(64), 0, st, reinterpret_cast<const uint4 *>(idx->d_sq_tiles), idx->sq_groups, idx->dim,
-              idx->sq->d_mins, idx->sq->d_inv, queries, idx->d_sq_norm_max, nom.cand_id, nom.cand_sc, k, ids, scores, fail, nom.thr, nom.counts,
-              nom.cap, nom.sel_k);
-    return VG_OK;
+    const uint4 *tiles = reinterpret_cast<const uint4 *>(idx->d_sq_tiles);
+    if (idx->metric != VG_METRIC_L2)
+        return launch_nominated_verify<true>(Sq8Row<true>{tiles, idx->sq_groups, idx->dim, idx->sq->d_mins, idx->sq->d_inv}, queries,
+                                             idx->sq_nom.norm_max, nq, nom, k, ids, scores, fail, st);
+    return launch_nominated_verify<false>(Sq8Row<false>{tiles, idx->sq_groups, idx->dim, idx->sq->d_mins, idx->sq->d_inv}, queries,
+                                          idx->sq_nom.norm_max, nq, nom, k, ids, scores, fail, st);
 }
 // whether a batch takes the nomination (vg_index_enable_sq8_nomination; device queries)
 bool sq8_nomination_applies(const vg_index *idx, const float *d_queries, int64_t nq, int k)
 {
-    return idx->d_sq_bf16 && nq >= VG_SQ8_NOM_MIN_Q && k <= kSq8NomMaxK && idx->n > k && (reinterpret_cast<uintptr_t>(d_queries) & 15) == 0;
+    return idx->sq_nom.rows && nq >= VG_SQ8_NOM_MIN_Q && k <= kNomMaxK && idx->n > k && (reinterpret_cast<uintptr_t>(d_queries) & 15) == 0;
 }
-// The nomination + exact re-score + proof for a batch (device buffers; mask: a device row filter per query / for the batch, or
-// null): writes every query's k results and lists the queries whose proof failed — the caller scans those.  4096 queries a pass.
+// nominated_pass with the SQ8 re-score (mask: a device row filter per query / for the batch, or null)
 int32_t sq8_nominated_pass(vg_index *idx, const float *q, int64_t nq, int k, const uint8_t *mask, int64_t mask_stride, uint32_t *oid,
                            float *osc, hipStream_t st, std::vector<int> &failed)
 {
-    const bool dot = idx->metric != VG_METRIC_L2;
-    for (int64_t q0 = 0; q0 < nq; q0 += 4096) {
-        const int64_t cnt = std::min<int64_t>(4096, nq - q0);
-        std::vector<int> h(static_cast<size_t>(cnt));
-        {
-            ArenaCall ar(idx->ctx, st);
-            const int sel_k = sq8_nominate_sel_k(k);
-            const int i_scr = ar.add(flat_nominate_bf16_scratch(cnt, idx->n, idx->sq_bf16_dim, sel_k));
-            const int i_thr = ar.add(sizeof(float) * static_cast<size_t>(cnt) * sel_k);
-            const int i_cnt = ar.add(sizeof(int) * static_cast<size_t>(cnt));
-            const int i_cid = ar.add(sizeof(uint32_t) * static_cast<size_t>(cnt) * 64);
-            const int i_csc = ar.add(sizeof(float) * static_cast<size_t>(cnt) * 64);
-            const int i_fail = ar.add(sizeof(int) * static_cast<size_t>(cnt));
-            VG_TRY(ar.commit());
-            float *thr = ar.get<float>(i_thr), *csc = ar.get<float>(i_csc);
-            int *counts = ar.get<int>(i_cnt), *fail = ar.get<int>(i_fail);
-            uint32_t *cid = ar.get<uint32_t>(i_cid);
-            ProbeNominated nom{thr, counts, cid, csc, 0, sel_k, nullptr};
-            VG_TRY(flat_nominate_bf16(idx->ctx, idx->d_sq_bf16, idx->d_sq_norms, idx->n, idx->dim, idx->sq_bf16_dim, q + q0 * idx->dim, cnt, ar.get<char>(i_scr),
-                                      thr, counts, cid, csc, st, dot, mask ? mask + q0 * mask_stride : nullptr, mask_stride, sel_k,
-                                      k <= kSq8PickMaxK, &nom.cand, &nom.cap, idx->d_sq_norm_max));
-            VG_TRY(launch_sq8_verify(idx, q + q0 * idx->dim, cnt, nom, k, oid + q0 * k, osc + q0 * k, fail, st));
-            VG_HIP(hipMemcpyAsync(h.data(), fail, sizeof(int) * static_cast<size_t>(cnt), hipMemcpyDeviceToHost, st));
-            VG_HIP(hipStreamSynchronize(st));
-        }
-        for (int64_t i = 0; i < cnt; i++)
-            if (h[static_cast<size_t>(i)]) failed.push_back(static_cast<int>(q0 + i));
-    }
-    return VG_OK;
+    return nominated_pass(idx, idx->sq_nom, idx->metric != VG_METRIC_L2, q, nq, k, mask, mask_stride, 0, oid, osc, st, failed,
+                          [&](const float *qq, int64_t cnt, const ProbeNominated &nom, float *, uint32_t *ids, float *scores, int *fail) {
+                              return launch_sq8_verify(idx, qq, cnt, nom, k, ids, scores, fail, st);
+                          });
 }
 }  // namespace vg
 
@@ -1939,24 +1774,11 @@ static int32_t sq8_search_impl(vg_index *idx, const float *queries, int64_t nq, 
     } else if (allow_nomination && vg::sq8_nomination_applies(idx, q.ptr, nq, k)) {
         std::vector<int> failed;
         VG_TRY(vg::sq8_nominated_pass(idx, q.ptr, nq, k, nullptr, 0, oid.ptr, osc.ptr, st, failed));
-        if (!failed.empty()) {  // the scan kernels for the queries whose proof failed (ties at the k-th score, thresholds too tight)
-            const int64_t nf = static_cast<int64_t>(failed.size());
-            vg::DevTmp<float> fq;
-            vg::DevTmp<uint32_t> fid;
-            vg::DevTmp<float> fsc;
-            VG_TRY(fq.init(static_cast<size_t>(nf) * idx->dim, st));
-            VG_TRY(fid.init(static_cast<size_t>(nf) * k, st));
-            VG_TRY(fsc.init(static_cast<size_t>(nf) * k, st));
-            for (int64_t i = 0; i < nf; i++)
-                VG_HIP(hipMemcpyAsync(fq.ptr + i * idx->dim, q.ptr + static_cast<int64_t>(failed[static_cast<size_t>(i)]) * idx->dim,
-                                      sizeof(float) * idx->dim, hipMemcpyDeviceToDevice, st));
-            VG_TRY(sq8_search_impl(idx, fq.ptr, nf, k, fid.ptr, fsc.ptr, st, false));
-            for (int64_t i = 0; i < nf; i++) {
-                const int64_t at = static_cast<int64_t>(failed[static_cast<size_t>(i)]) * k;
-                VG_HIP(hipMemcpyAsync(oid.ptr + at, fid.ptr + i * k, sizeof(uint32_t) * k, hipMemcpyDeviceToDevice, st));
-                VG_HIP(hipMemcpyAsync(osc.ptr + at, fsc.ptr + i * k, sizeof(float) * k, hipMemcpyDeviceToDevice, st));
-            }
-        }
+        // the scan kernels for the queries whose proof failed (ties at the k-th score, thresholds too tight)
+        VG_TRY(vg::rescan_failed(failed, q.ptr, idx->dim, k, nullptr, 0, 0, oid.ptr, osc.ptr, st,
+                                 [&](const float *fq, int64_t nf, const uint8_t *, int64_t, uint32_t *fid, float *fsc) {
+                                     return sq8_search_impl(idx, fq, nf, k, fid, fsc, st, false);
+                                 }));
     } else {
         // two or more queries: groups of kSqProbeQ share every decode (sq8_scan_mq_kernel)
         const size_t mq_lds = sizeof(float) * vg::kSqProbeQ * static_cast<size_t>(idx->sq_groups) * 16 +

@@ -398,10 +398,10 @@ VG_API int32_t vg_vamana_reorder_bfs(vg_index *idx, uint32_t *perm, uint32_t *in
     need(idx->d_vectors, n * idx->dim * 4);
     need(idx->d_vectors_bf16, n * bf16_bytes);
     need(idx->d_pq_rows, n * pq_m);
-    need(idx->d_pq_bf16, n * idx->pq_bf16_dim * 2);
+    need(idx->pq_nom.rows, n * idx->pq_nom.dim_pad * 2);
     need(idx->d_rq_rows, n * (rq_nb + 4));
     need(idx->d_sq_tiles, idx->n_tiles * idx->sq_groups * 64 * 16);
-    need(idx->d_sq_bf16, n * idx->sq_bf16_dim * 2);
+    need(idx->sq_nom.rows, n * idx->sq_nom.dim_pad * 2);
     need(idx->d_int4_rows, n * int4_row);
 
     // BFS state: order (perm), inv (inv_perm), the large levels' keys, masks and counts, and the scratch
@@ -466,8 +466,8 @@ VG_API int32_t vg_vamana_reorder_bfs(vg_index *idx, uint32_t *perm, uint32_t *in
             if (idx->d_pq_tiles)
                 VG_TRY(vg::launch_pq_retile(idx->d_pq_rows, n, idx->pq->m, idx->pq_groups, (n + 63) / 64, idx->d_pq_tiles, st));
         }
-        VG_TRY(vg::rb_permute_rows(idx->d_pq_bf16, n, static_cast<int64_t>(idx->pq_bf16_dim) * 2, p, scratch, st));
-        VG_TRY(vg::rb_permute_rows(idx->d_pq_norms, n, 4, p, scratch, st));
+        VG_TRY(vg::rb_permute_rows(idx->pq_nom.rows, n, static_cast<int64_t>(idx->pq_nom.dim_pad) * 2, p, scratch, st));
+        VG_TRY(vg::rb_permute_rows(idx->pq_nom.norms, n, 4, p, scratch, st));
         // RaBitQ: rows, then tiles and norms[0, n) rebuilt from them (norms[n], the largest |norm|, does not move)
         if (idx->d_rq_rows) {
             VG_TRY(vg::rb_permute_rows(idx->d_rq_rows, n, rq_nb + 4, p, scratch, st));
@@ -483,8 +483,8 @@ VG_API int32_t vg_vamana_reorder_bfs(vg_index *idx, uint32_t *perm, uint32_t *in
             VG_HIP(hipMemcpyAsync(idx->d_sq_tiles, scratch, static_cast<size_t>(tiles * idx->sq_groups * 64 * 16), hipMemcpyDeviceToDevice,
                                   st));
         }
-        VG_TRY(vg::rb_permute_rows(idx->d_sq_bf16, n, static_cast<int64_t>(idx->sq_bf16_dim) * 2, p, scratch, st));
-        VG_TRY(vg::rb_permute_rows(idx->d_sq_norms, n, 4, p, scratch, st));
+        VG_TRY(vg::rb_permute_rows(idx->sq_nom.rows, n, static_cast<int64_t>(idx->sq_nom.dim_pad) * 2, p, scratch, st));
+        VG_TRY(vg::rb_permute_rows(idx->sq_nom.norms, n, 4, p, scratch, st));
         // INT4 rows
         VG_TRY(vg::rb_permute_rows(idx->d_int4_rows, n, int4_row, p, scratch, st));
     }

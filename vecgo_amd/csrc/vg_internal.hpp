@@ -349,6 +349,25 @@ struct ProbeNominated {
     const uint64_t *cand;  // [pairs, cap]: every appended key (k > 48: all of them are re-scored)
 };
 constexpr int kProbeGemmMaxK = 160;  // deepest threshold: the 60th best of the 1/8 row sample, ~480 rows pass it
+// A bfloat16 row image the matrix-core nomination runs on (vg_nominate.hpp): a quantizer's DECODED rows rounded to bfloat16
+// (vg_index_enable_sq8_nomination, vg_index_enable_pq_nomination; all null when off), or a view of the fp32 rows' bf16 filter.
+struct NomImage {
+    uint16_t *rows = nullptr;  // n * dim_pad
+    int32_t dim_pad = 0;       // the row length: dim padded with zeros to whole 64-element K steps of the bf16 GEMM
+    float *norms = nullptr;    // n: |x^|^2 (fp32 of the unrounded values)
+    float *norm_max = nullptr; // [1]: the largest of them
+};
+// Frees an image (after the stream's work that may read it) and leaves it empty.
+inline int32_t nom_free(NomImage &img, hipStream_t st)
+{
+    if (!img.rows) return VG_OK;
+    VG_HIP(hipStreamSynchronize(st));
+    VG_HIP(hipFree(img.rows));
+    VG_HIP(hipFree(img.norms));
+    VG_HIP(hipFree(img.norm_max));
+    img = NomImage{};
+    return VG_OK;
+}
 }  // namespace vg
 
 struct vg_index {
@@ -393,17 +412,11 @@ struct vg_index {
     uint32_t vamana_entry = 0;
     // PQ codes in the reference's row-major layout (random access by node id in graph search)
     uint8_t *d_pq_rows = nullptr;
-    uint16_t *d_pq_bf16 = nullptr;     // vg_index_enable_pq_nomination: the DECODED rows (pq.go:185-229) rounded to bfloat16, n*pq_bf16_dim, or null
-    int32_t pq_bf16_dim = 0;           // its row length: dim padded with zeros to whole 64-element K steps of the bf16 GEMM
-    float *d_pq_norms = nullptr;       // ... their |x^|^2 (fp32 of the unrounded values), n, and the largest of them
-    float *d_pq_norm_max = nullptr;
+    vg::NomImage pq_nom;               // vg_index_enable_pq_nomination: the DECODED rows (pq.go:185-229)
     uint8_t *d_rq_rows = nullptr;
     // SQ8 codes, re-tiled like the PQ codes: [tile][group of 16 dims][lane][16 B]; see k_sq8.hip
     vg_sq8 *sq = nullptr;
-    uint16_t *d_sq_bf16 = nullptr;     // vg_index_enable_sq8_nomination: the dequantised codes rounded to bfloat16, n*sq_bf16_dim, or null
-    int32_t sq_bf16_dim = 0;           // its row length: dim padded with zeros to whole 64-element K steps of the bf16 GEMM
-    float *d_sq_norms = nullptr;       // ... their |x^|^2 (fp32 of the unrounded values), n, and the largest of them
-    float *d_sq_norm_max = nullptr;
+    vg::NomImage sq_nom;               // vg_index_enable_sq8_nomination: the dequantised codes
     uint8_t *d_sq_tiles = nullptr;
     int32_t sq_groups = 0;  // ceil(dim/16)
     // INT4 codes of a DiskANN segment, row-major n * ceil(dim/2), and the quantizer's lookup table
