@@ -31,6 +31,7 @@
 #include "vg_internal.hpp"
 #include "vg_cand_replay.hpp"
 #include "vg_nominate.hpp"
+#include "vg_search.hpp"
 
 namespace vg {
 
@@ -644,17 +645,13 @@ __global__ void patch_results_kernel(const int *__restrict__ flags, int k, const
 }
 
 int32_t launch_topk_merge(const uint64_t *partial, int64_t nq, int lists, int k, bool descending,
-                          uint32_t *ids, float *scores, hipStream_t st, const int *only_if = nullptr,
-                          const int *always = nullptr)
+                          uint32_t *ids, float *scores, hipStream_t st, const int *only_if, const int *always)
 {
     if (nq == 0 || k == 0) return VG_OK;
     VG_LAUNCH(topk_merge_kernel, dim3(static_cast<unsigned>(nq)), dim3(kMergeThreads), 0,
                        st, partial, lists, k, descending, ids, scores, only_if, always);
     return VG_OK;
 }
-
-int32_t launch_pq_build_table(const vg_pq *pq, const float *d_queries, int64_t nq,
-                              float *d_tables, bool scan_layout, hipStream_t st);
 
 // ---- partition-probed ADC scan (flat/segment.go:727-744 over the :678-689 branch) -----------------
 // One workgroup per (query, share of its probe list): the query's table is staged once, then the
@@ -1059,20 +1056,19 @@ static int32_t merge_topk_impl(vg_ctx *ctx, const uint32_t *ids_in, const float 
     vg::ArenaCall ar(ctx, st);
     const int i_keys = ar.add(sizeof(uint64_t) * static_cast<size_t>(nl) * nq * k);
     VG_TRY(ar.commit());
-    struct { uint64_t *ptr; } keys{ar.get<uint64_t>(i_keys)};
+    uint64_t *keys = ar.get<uint64_t>(i_keys);
     if (lists == 0) {
-        VG_HIP(hipMemsetAsync(keys.ptr, 0xFF, static_cast<size_t>(nq) * k * 8, st));
+        VG_HIP(hipMemsetAsync(keys, 0xFF, static_cast<size_t>(nq) * k * 8, st));
     } else {
         VG_LAUNCH(vg::pack_keys_kernel, dim3(static_cast<unsigned>((total + 255) / 256)), dim3(256),
-                           0, st, i_in.ptr, s_in.ptr, lists, nq, k, list_stride, desc, offs.ptr, keys.ptr);
+                           0, st, i_in.ptr, s_in.ptr, lists, nq, k, list_stride, desc, offs.ptr, keys);
     }
-    VG_TRY(vg::launch_topk_merge(keys.ptr, nq, nl, k, desc, oid.ptr, osc.ptr, st));
+    VG_TRY(vg::launch_topk_merge(keys, nq, nl, k, desc, oid.ptr, osc.ptr, st));
     if (lists > 0 && !vg::hook(vg::kHookNoCandReplay))  // queries with a NaN score in a list: the engine's heap, operation by operation
         VG_LAUNCH(vg::merge_nan_replay_kernel, dim3(static_cast<unsigned>(nq)), dim3(64), sizeof(uint64_t) * (static_cast<size_t>(k) + 4), st,
                   i_in.ptr, s_in.ptr, lists, nq, k, list_stride, desc, offs.ptr, oid.ptr, osc.ptr);
     VG_TRY(oid.finish());
     VG_TRY(osc.finish());
-    if (oid.on_host() || osc.on_host()) VG_HIP(hipStreamSynchronize(st));
     return VG_OK;
 }
 
@@ -1228,11 +1224,6 @@ VG_API int32_t vg_index_enable_pq_nomination(vg_index *idx, int32_t on, void *st
     });
 }
 
-namespace vg {
-int32_t pq_adc_search_masked(vg_index *idx, const float *queries, int64_t nq, int32_t k, const uint8_t *mask, int64_t mask_stride,
-                             bool desc, uint32_t *ids, float *scores, void *stream);
-}
-
 VG_API int32_t vg_search_pq_adc(vg_index *idx, const float *queries, int64_t nq, int32_t k,
                                 uint32_t *ids, float *scores, void *stream)
 {
@@ -1348,28 +1339,16 @@ static int32_t pq_adc_search_impl(vg_index *idx, const float *queries, int64_t n
     VG_CHECK(mask == nullptr || (!wide && k <= 64), VG_ERR_UNSUPPORTED, "pq_adc_search_masked: k=%d / m=%d take the probe kernels", k, pq->m);
     VG_CHECK(!wide || k <= 64, VG_ERR_UNSUPPORTED,
              "vg_search_pq_adc: m=%d lookup table does not fit the 160 KiB LDS; the chunked scan takes k <= 64", pq->m);
-    VG_HIP(hipSetDevice(idx->ctx->device));
-    hipStream_t st = vg::pick_stream(idx->ctx, stream);
+    vg::SearchIO io;
+    VG_TRY(io.init(idx->ctx, stream, queries, static_cast<size_t>(nq) * idx->dim, ids, scores, static_cast<size_t>(nq) * k));
+    const hipStream_t st = io.st;
+    const float *q = io.q.ptr;
+    uint32_t *oid = io.oid.ptr;
+    float *osc = io.osc.ptr;
 
-    vg::DevIn<float> q;
-    vg::DevOut<uint32_t> oid;
-    vg::DevOut<float> osc;
-    VG_TRY(q.init(queries, static_cast<size_t>(nq) * idx->dim, st));
-    VG_TRY(oid.init(ids, static_cast<size_t>(nq) * k, st));
-    VG_TRY(osc.init(scores, static_cast<size_t>(nq) * k, st));
-
-    // queries whose table sums may hold a NaN: the reference's heap, operation by operation (vg_cand_replay.hpp; not for the queries
-    // this function sends to itself after a failed proof: the caller's pass covers them)
-    auto nan_replay = [&]() -> int32_t {
-        if (!allow_nomination) return VG_OK;
-        return vg::pq_nan_replay(idx, q.ptr, nq, k, desc, mask, mask_stride, nullptr, 0, nullptr, oid.ptr, osc.ptr, st);
-    };
     if (idx->n == 0) {
-        vg::DevTmp<uint64_t> none;
-        VG_TRY(none.init(static_cast<size_t>(nq) * k, st));
-        VG_HIP(hipMemsetAsync(none.ptr, 0xFF, static_cast<size_t>(nq) * k * 8, st));
-        VG_TRY(vg::launch_topk_merge(none.ptr, nq, 1, k, false, oid.ptr, osc.ptr, st));
-    } else if (allow_nomination && vg::pq_nomination_applies(idx, q.ptr, nq, k, mask, desc)) {
+        VG_TRY(vg::empty_results(nq, k, false, oid, osc, st));
+    } else if (allow_nomination && vg::pq_nomination_applies(idx, q, nq, k, mask, desc)) {
         std::vector<int> failed;
         // per pass: the queries' tables (BuildDistanceTable, the reference's layout), then the table sums of the nominees
         auto verify = [&](const float *qq, int64_t cnt, const vg::ProbeNominated &nom, float *tables, uint32_t *pid, float *psc,
@@ -1378,10 +1357,10 @@ static int32_t pq_adc_search_impl(vg_index *idx, const float *queries, int64_t n
             return vg::launch_nominated_verify<false>(vg::PqTableRow{idx->d_pq_rows, tables, pq->m, pq->subdim, idx->dim}, qq,
                                                       idx->pq_nom.norm_max, cnt, nom, k, pid, psc, fail, st);
         };
-        VG_TRY(vg::nominated_pass(idx, idx->pq_nom, false, q.ptr, nq, k, nullptr, 0, static_cast<size_t>(pq->m) * 256, oid.ptr, osc.ptr,
+        VG_TRY(vg::nominated_pass(idx, idx->pq_nom, false, q, nq, k, nullptr, 0, static_cast<size_t>(pq->m) * 256, oid, osc,
                                   st, failed, verify));
         // the table scan for the queries whose proof failed (ties at the k-th score, thresholds too tight)
-        VG_TRY(vg::rescan_failed(failed, q.ptr, idx->dim, k, nullptr, 0, 0, oid.ptr, osc.ptr, st,
+        VG_TRY(vg::rescan_failed(failed, q, idx->dim, k, nullptr, 0, 0, oid, osc, st,
                                  [&](const float *fq, int64_t nf, const uint8_t *, int64_t, uint32_t *fid, float *fsc) {
                                      return pq_adc_search_impl(idx, fq, nf, k, nullptr, 0, false, fid, fsc, st, false);
                                  }));
@@ -1405,9 +1384,9 @@ static int32_t pq_adc_search_impl(vg_index *idx, const float *queries, int64_t n
         const int i_fid = ar.add(bigk_fast ? sizeof(uint32_t) * static_cast<size_t>(nq) * k : 0);
         const int i_fsc = ar.add(bigk_fast ? sizeof(float) * static_cast<size_t>(nq) * k : 0);
         VG_TRY(ar.commit());
-        struct { float *ptr; } tables{ar.get<float>(i_tables)};
-        struct { uint64_t *ptr; } partial{ar.get<uint64_t>(i_partial)};
-        VG_TRY(vg::launch_pq_build_table(pq, q.ptr, nq, tables.ptr, true, st));
+        float *tables = ar.get<float>(i_tables);
+        uint64_t *partial = ar.get<uint64_t>(i_partial);
+        VG_TRY(vg::launch_pq_build_table(pq, q, nq, tables, true, st));
         if (bigk_fast) {
             int *flags = ar.get<int>(i_flags);
             uint32_t *fid = ar.get<uint32_t>(i_fid);
@@ -1415,39 +1394,34 @@ static int32_t pq_adc_search_impl(vg_index *idx, const float *queries, int64_t n
             // (1) every wave keeps its 64 best; (2) select k of the union and prove it; (3) the
             // exhaustive LDS-buffer scan re-runs only for queries whose proof failed
             if (pq->m == 96)
-                VG_TRY((vg::launch_scan<6, true>(idx, tables.ptr, nq, k, slices, partial.ptr, st, 1)));
+                VG_TRY((vg::launch_scan<6, true>(idx, tables, nq, k, slices, partial, st, 1)));
             else
-                VG_TRY((vg::launch_scan<-1, true>(idx, tables.ptr, nq, k, slices, partial.ptr, st, 1)));
+                VG_TRY((vg::launch_scan<-1, true>(idx, tables, nq, k, slices, partial, st, 1)));
             VG_LAUNCH(vg::topk_select_verify_kernel, dim3(static_cast<unsigned>(nq)), dim3(vg::kMergeThreads), 0, st,
-                      partial.ptr, slices * vg::kAdcWaves, k, false, oid.ptr, osc.ptr, flags);
+                      partial, slices * vg::kAdcWaves, k, false, oid, osc, flags);
             if (pq->m == 96)
-                VG_TRY((vg::launch_scan<6, false>(idx, tables.ptr, nq, k, slices, partial.ptr, st, 0, flags)));
+                VG_TRY((vg::launch_scan<6, false>(idx, tables, nq, k, slices, partial, st, 0, flags)));
             else
-                VG_TRY((vg::launch_scan<-1, false>(idx, tables.ptr, nq, k, slices, partial.ptr, st, 0, flags)));
-            VG_TRY(vg::launch_topk_merge(partial.ptr, nq, slices, k, false, fid, fsc, st, flags));
+                VG_TRY((vg::launch_scan<-1, false>(idx, tables, nq, k, slices, partial, st, 0, flags)));
+            VG_TRY(vg::launch_topk_merge(partial, nq, slices, k, false, fid, fsc, st, flags));
             VG_LAUNCH(vg::patch_results_kernel, dim3(static_cast<unsigned>(nq)), dim3(64), 0, st, flags, k, fid, fsc,
-                      oid.ptr, osc.ptr);
-            VG_TRY(nan_replay());
-            VG_TRY(oid.finish());
-            VG_TRY(osc.finish());
-            if (oid.on_host() || osc.on_host()) VG_HIP(hipStreamSynchronize(st));
-            return VG_OK;
+                      oid, osc);
+        } else {
+            if (wide)
+                VG_TRY(vg::launch_scan_wide(idx, tables, nq, k, slices, partial, st));
+            else if (pq->m == 96 && k <= 64)
+                VG_TRY((vg::launch_scan<6, true>(idx, tables, nq, k, slices, partial, st, 0, nullptr, mask, mask_stride, desc)));
+            else if (pq->m == 96)
+                VG_TRY((vg::launch_scan<6, false>(idx, tables, nq, k, slices, partial, st)));
+            else if (k <= 64)
+                VG_TRY((vg::launch_scan<-1, true>(idx, tables, nq, k, slices, partial, st, 0, nullptr, mask, mask_stride, desc)));
+            else
+                VG_TRY((vg::launch_scan<-1, false>(idx, tables, nq, k, slices, partial, st)));
+            VG_TRY(vg::launch_topk_merge(partial, nq, slices, k, desc, oid, osc, st));
         }
-        if (wide)
-            VG_TRY(vg::launch_scan_wide(idx, tables.ptr, nq, k, slices, partial.ptr, st));
-        else if (pq->m == 96 && k <= 64)
-            VG_TRY((vg::launch_scan<6, true>(idx, tables.ptr, nq, k, slices, partial.ptr, st, 0, nullptr, mask, mask_stride, desc)));
-        else if (pq->m == 96)
-            VG_TRY((vg::launch_scan<6, false>(idx, tables.ptr, nq, k, slices, partial.ptr, st)));
-        else if (k <= 64)
-            VG_TRY((vg::launch_scan<-1, true>(idx, tables.ptr, nq, k, slices, partial.ptr, st, 0, nullptr, mask, mask_stride, desc)));
-        else
-            VG_TRY((vg::launch_scan<-1, false>(idx, tables.ptr, nq, k, slices, partial.ptr, st)));
-        VG_TRY(vg::launch_topk_merge(partial.ptr, nq, slices, k, desc, oid.ptr, osc.ptr, st));
     }
-    VG_TRY(nan_replay());
-    VG_TRY(oid.finish());
-    VG_TRY(osc.finish());
-    if (oid.on_host() || osc.on_host()) VG_HIP(hipStreamSynchronize(st));
-    return VG_OK;
+    // queries whose table sums may hold a NaN: the reference's heap, operation by operation (vg_cand_replay.hpp; not for the queries
+    // this function sends to itself after a failed proof: the caller's pass covers them)
+    if (allow_nomination) VG_TRY(vg::pq_nan_replay(idx, q, nq, k, desc, mask, mask_stride, nullptr, 0, nullptr, oid, osc, st));
+    return io.finish();
 }

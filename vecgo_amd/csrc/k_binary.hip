@@ -140,7 +140,6 @@ VG_API int32_t vg_binary_train(vg_ctx *ctx, int32_t dim, const float *vectors, i
               partial.ptr);
     VG_LAUNCH(vg::binary_finish_kernel, dim3(1), dim3(1), 0, st, partial.ptr, blocks, count, th.ptr);
     VG_TRY(th.finish());
-    if (th.on_host()) VG_HIP(hipStreamSynchronize(st));
     return VG_OK;
 }
 
@@ -160,7 +159,6 @@ VG_API int32_t vg_binary_encode(vg_ctx *ctx, int32_t dim, float threshold, const
     VG_LAUNCH(vg::binary_encode_kernel, dim3(static_cast<unsigned>((n + 15) / 16)), dim3(256), 0, st, v.ptr, n, dim,
               static_cast<const float *>(nullptr), threshold, c.ptr);
     VG_TRY(c.finish());
-    if (c.on_host()) VG_HIP(hipStreamSynchronize(st));
     return VG_OK;
 }
 
@@ -181,7 +179,6 @@ VG_API int32_t vg_binary_decode(vg_ctx *ctx, int32_t dim, float threshold, const
     VG_LAUNCH(vg::binary_decode_kernel, dim3(static_cast<unsigned>((total + 255) / 256)), dim3(256), 0, st, c.ptr, n, dim,
               code_bytes, threshold, o.ptr);
     VG_TRY(o.finish());
-    if (o.on_host()) VG_HIP(hipStreamSynchronize(st));
     return VG_OK;
 }
 
@@ -208,7 +205,6 @@ VG_API int32_t vg_binary_hamming_batch(vg_ctx *ctx, int32_t dim, float threshold
     VG_LAUNCH(vg::binary_hamming_kernel, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, st, qc.ptr, c.ptr, n,
               static_cast<int>(cb / 8), o.ptr);
     VG_TRY(o.finish());
-    if (o.on_host()) VG_HIP(hipStreamSynchronize(st));
     return VG_OK;
 }
 
@@ -243,6 +239,6 @@ VG_API int32_t vg_normalize_l2(vg_ctx *ctx, float *vectors, int64_t n, int32_t d
     VG_LAUNCH(vg::normalize_l2_kernel, dim3(static_cast<unsigned>((n + 15) / 16)), dim3(256), 0, st, dv, n, dim, o.ptr);
     if (host) VG_HIP(hipMemcpyAsync(vectors, dv, count * 4, hipMemcpyDeviceToHost, st));
     VG_TRY(o.finish());
-    if (host || o.on_host()) VG_HIP(hipStreamSynchronize(st));
+    if (host) VG_HIP(hipStreamSynchronize(st));
     return VG_OK;
 }

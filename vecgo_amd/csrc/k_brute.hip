@@ -23,6 +23,7 @@
 #include "vg_heap.hpp"
 #include "vg_internal.hpp"
 #include "vg_cand_replay.hpp"
+#include "vg_search.hpp"
 
 #include <algorithm>
 
@@ -531,10 +532,6 @@ static int32_t brute_nan_replay(vg_index *idx, const float *d_queries, int64_t n
 
 static int32_t brute_impl(vg_index *idx, const float *queries, int64_t nq, int32_t k, int32_t mode, const uint8_t *mask,
                           int64_t mask_stride, uint32_t *ids, float *scores, void *stream);
-namespace vg {
-int32_t flat_search_masked(vg_index *idx, const float *queries, int64_t nq, int32_t k, const uint8_t *mask, int64_t mask_stride,
-                           uint32_t *ids, float *scores, void *stream, bool l2_scores = false, bool cand_replay = true);
-}
 
 VG_API int32_t vg_search_hnsw_brute(vg_index *idx, const float *queries, int64_t nq, int32_t k, int32_t mode,
                                     const uint8_t *mask, int64_t mask_stride, uint32_t *ids, float *scores, void *stream)
@@ -555,60 +552,56 @@ VG_API int32_t vg_search_hnsw_brute(vg_index *idx, const float *queries, int64_t
                       k + 1 <= 512 /* vg_search_flat's kFlatMaxK */ && k <= vg::kBruteMaxK && (mode == VG_BRUTE_SCAN || mode == VG_BRUTE_BITMAP) &&
                       !vg::hook(vg::kHookBruteNoFlat);
     if (!fast) return brute_impl(idx, queries, nq, k, mode, mask, mask_stride, ids, scores, stream);
-    VG_HIP(hipSetDevice(idx->ctx->device));
-    hipStream_t st = vg::pick_stream(idx->ctx, stream);
-    vg::DevIn<float> q;
-    vg::DevOut<uint32_t> oid;
-    vg::DevOut<float> osc;
-    VG_TRY(q.init(queries, static_cast<size_t>(nq) * idx->dim, st));
-    VG_TRY(oid.init(ids, static_cast<size_t>(nq) * k, st));
-    VG_TRY(osc.init(scores, static_cast<size_t>(nq) * k, st));
+    vg::SearchIO io;
+    VG_TRY(io.init(idx->ctx, stream, queries, static_cast<size_t>(nq) * idx->dim, ids, scores, static_cast<size_t>(nq) * k, mask,
+                   vg::mask_span(mask, mask_stride, nq, idx->n)));
+    const hipStream_t st = io.st;
+    const float *q = io.q.ptr;
+    const uint8_t *mk = io.mk.ptr;
+    uint32_t *oid = io.oid.ptr;
+    float *osc = io.osc.ptr;
     vg::DevTmp<uint32_t> fid;
     vg::DevTmp<float> fsc;
     vg::DevTmp<int32_t> redo;
     VG_TRY(fid.init(static_cast<size_t>(nq) * (k + 1), st));
     VG_TRY(fsc.init(static_cast<size_t>(nq) * (k + 1), st));
     VG_TRY(redo.init(static_cast<size_t>(nq), st));
-    vg::DevIn<uint8_t> mk;
-    const int64_t mask_total = mask ? (mask_stride ? (nq - 1) * mask_stride + mask_bytes_fast : mask_bytes_fast) : 0;
-    VG_TRY(mk.init(mask, static_cast<size_t>(mask_total), st));
-    if (mk.ptr) {
+    if (mk) {
+        const int64_t mask_total = static_cast<int64_t>(vg::mask_span(mask, mask_stride, nq, idx->n));
         // The replay's distance pass reads only the rows that take part: below ~2 % of the rows it is the faster form
         // (1M x 768, per 1024 queries: replay 12 ms at 1 %, 23 at 3 %, 68 at 50 %; this form 12 - 18 whatever the fraction)
         vg::DevTmp<unsigned long long> cnt;
         VG_TRY(cnt.init(1, st));
         VG_HIP(hipMemsetAsync(cnt.ptr, 0, sizeof(unsigned long long), st));
         VG_LAUNCH(vg::mask_popcount_kernel, dim3(static_cast<unsigned>(std::min<int64_t>(1024, (mask_total + 255) / 256))), dim3(256), 0, st,
-                  mk.ptr, mask_total, cnt.ptr);
+                  mk, mask_total, cnt.ptr);
         unsigned long long set_bits = 0;
         VG_HIP(hipMemcpyAsync(&set_bits, cnt.ptr, sizeof(set_bits), hipMemcpyDeviceToHost, st));
         VG_HIP(hipStreamSynchronize(st));
         const double masks = mask_stride ? static_cast<double>(nq) : 1.0;
         if (static_cast<double>(set_bits) < 0.02 * masks * static_cast<double>(idx->n))
-            return brute_impl(idx, q.ptr, nq, k, mode, mk.ptr, mask_stride, ids, scores, stream);
+            return brute_impl(idx, q, nq, k, mode, mk, mask_stride, ids, scores, stream);
     }
     {
         vg::ProfScope prof(idx->ctx, "hnsw_brute_dist", st);  // (the distance work of this form)
         // (Cosine: the index's distance is 0.5 * squared L2 of the normalised rows — the flat search is asked for L2 scores)
-        VG_TRY(vg::flat_search_masked(idx, q.ptr, nq, k + 1, mk.ptr, mask_stride, fid.ptr, fsc.ptr, st, idx->metric == VG_METRIC_COSINE, false));
+        VG_TRY(vg::flat_search_masked(idx, q, nq, k + 1, mk, mask_stride, fid.ptr, fsc.ptr, st, idx->metric == VG_METRIC_COSINE, false));
     }
     VG_LAUNCH(vg::brute_from_flat_kernel, dim3(static_cast<unsigned>(nq)), dim3(64), 0, st, fid.ptr, fsc.ptr, nq, k,
-              idx->metric == VG_METRIC_DOT ? 1 : idx->metric == VG_METRIC_COSINE ? 2 : 0, oid.ptr, osc.ptr, redo.ptr);
+              idx->metric == VG_METRIC_DOT ? 1 : idx->metric == VG_METRIC_COSINE ? 2 : 0, oid, osc, redo.ptr);
     std::vector<int32_t> h(static_cast<size_t>(nq));
     VG_HIP(hipMemcpyAsync(h.data(), redo.ptr, sizeof(int32_t) * static_cast<size_t>(nq), hipMemcpyDeviceToHost, st));
     VG_HIP(hipStreamSynchronize(st));
     int64_t nredo = 0;
     for (int64_t i = 0; i < nq; i++) nredo += h[static_cast<size_t>(i)] != 0;
     if (nredo * 4 > nq)  // (masks that leave fewer than k + 1 rows to most queries: one batched pass instead of nq small ones)
-        return brute_impl(idx, q.ptr, nq, k, mode, mk.ptr, mask_stride, ids, scores, stream);
+        return brute_impl(idx, q, nq, k, mode, mk, mask_stride, ids, scores, stream);
     for (int64_t i = 0; i < nq; i++)  // ties / NaN: the heap's history decides — replayed one query at a time (rare)
         if (h[static_cast<size_t>(i)])
-            VG_TRY(brute_impl(idx, q.ptr + i * idx->dim, 1, k, mode, mk.ptr ? mk.ptr + i * mask_stride : nullptr, 0, oid.ptr + i * k,
-                              osc.ptr + i * k, st));
-    VG_TRY(vg::brute_nan_replay(idx, q.ptr, nq, k, mode, mk.ptr, mask_stride, oid.ptr, osc.ptr, st));  // queries whose distances may hold a NaN
-    VG_TRY(oid.finish());
-    VG_TRY(osc.finish());
-    return VG_OK;
+            VG_TRY(brute_impl(idx, q + i * idx->dim, 1, k, mode, mk ? mk + i * mask_stride : nullptr, 0, oid + i * k,
+                              osc + i * k, st));
+    VG_TRY(vg::brute_nan_replay(idx, q, nq, k, mode, mk, mask_stride, oid, osc, st));  // queries whose distances may hold a NaN
+    return io.finish();
 }
 
 static int32_t brute_impl(vg_index *idx, const float *queries, int64_t nq, int32_t k, int32_t mode,
@@ -626,16 +619,14 @@ static int32_t brute_impl(vg_index *idx, const float *queries, int64_t nq, int32
     VG_CHECK(mask == nullptr || mask_stride == 0 || mask_stride >= mask_bytes, VG_ERR_INVALID_ARG,
              "vg_search_hnsw_brute: mask_stride %lld is shorter than a mask (%lld bytes)", static_cast<long long>(mask_stride),
              static_cast<long long>(mask_bytes));
-    VG_HIP(hipSetDevice(idx->ctx->device));
-    hipStream_t st = vg::pick_stream(idx->ctx, stream);
-    vg::DevIn<float> q;
-    vg::DevIn<uint8_t> mk;
-    vg::DevOut<uint32_t> oid;
-    vg::DevOut<float> osc;
-    VG_TRY(q.init(queries, static_cast<size_t>(nq) * idx->dim, st));
-    VG_TRY(mk.init(mask, mask ? static_cast<size_t>(mask_stride ? (nq - 1) * mask_stride + mask_bytes : mask_bytes) : 0, st));
-    VG_TRY(oid.init(ids, static_cast<size_t>(nq) * k, st));
-    VG_TRY(osc.init(scores, static_cast<size_t>(nq) * k, st));
+    vg::SearchIO io;
+    VG_TRY(io.init(idx->ctx, stream, queries, static_cast<size_t>(nq) * idx->dim, ids, scores, static_cast<size_t>(nq) * k, mask,
+                   vg::mask_span(mask, mask_stride, nq, idx->n)));
+    const hipStream_t st = io.st;
+    const float *q = io.q.ptr;
+    const uint8_t *mk = io.mk.ptr;
+    uint32_t *oid = io.oid.ptr;
+    float *osc = io.osc.ptr;
     const int64_t n = idx->n;
     // dist[q][row] of one chunk of queries.  The query-blocked kernel gets its row reuse from kBruteQB = 16 queries per
     // workgroup, so a chunk of thousands of queries buys nothing: 2 GiB of distances (512 queries at 1M rows), but at
@@ -665,7 +656,7 @@ static int32_t brute_impl(vg_index *idx, const float *queries, int64_t nq, int32
                                                                                           vg::kBruteRowsPerBlock, 1), 65535));
     for (int64_t q0 = 0; q0 < nq; q0 += chunk) {
         const int64_t cnt = std::min(chunk, nq - q0);
-        const uint8_t *m0 = mk.ptr ? mk.ptr + q0 * mask_stride : nullptr;
+        const uint8_t *m0 = mk ? mk + q0 * mask_stride : nullptr;
         if (n > 0) {
             vg::ProfScope prof(idx->ctx, "hnsw_brute_dist", st);
             const bool mq = cnt >= 2 && idx->dim % 4 == 0 && idx->dim <= 1024 && (m0 == nullptr || mask_stride == 0);
@@ -679,7 +670,7 @@ static int32_t brute_impl(vg_index *idx, const float *queries, int64_t nq, int32
                 auto launch = [&](auto kern) -> int32_t {
                     VG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
                                                static_cast<int>(qlds)));
-                    VG_LAUNCH(kern, grid, block, qlds, st, idx->d_vectors, n, idx->dim, q.ptr + q0 * idx->dim,
+                    VG_LAUNCH(kern, grid, block, qlds, st, idx->d_vectors, n, idx->dim, q + q0 * idx->dim,
                               static_cast<int>(cnt), m0, dist, qblocks, static_cast<int>(slices));
                     return VG_OK;
                 };
@@ -692,7 +683,7 @@ static int32_t brute_impl(vg_index *idx, const float *queries, int64_t nq, int32
             } else {
                 const dim3 grid(static_cast<unsigned>(cnt), row_blocks), block(vg::kBruteDistThreads);
                 auto launch1 = [&](auto kern) -> int32_t {
-                    VG_LAUNCH(kern, grid, block, 0, st, idx->d_vectors, n, idx->dim, q.ptr + q0 * idx->dim, m0, mask_stride, dist);
+                    VG_LAUNCH(kern, grid, block, 0, st, idx->d_vectors, n, idx->dim, q + q0 * idx->dim, m0, mask_stride, dist);
                     return VG_OK;
                 };
                 const bool one = cnt == 1;
@@ -706,12 +697,10 @@ static int32_t brute_impl(vg_index *idx, const float *queries, int64_t nq, int32
         }
         vg::ProfScope prof(idx->ctx, "hnsw_brute_replay", st);
         VG_LAUNCH(replay, dim3(static_cast<unsigned>(cnt)), dim3(vg::kBruteThreads), lds, st, dist, n, m0, mask_stride, k,
-                  oid.ptr + q0 * k, osc.ptr + q0 * k);
+                  oid + q0 * k, osc + q0 * k);
     }
-    VG_TRY(vg::brute_nan_replay(idx, q.ptr, nq, k, mode, mk.ptr, mask_stride, oid.ptr, osc.ptr, st));  // queries whose distances may hold a NaN
-    VG_TRY(oid.finish());
-    VG_TRY(osc.finish());
-    return VG_OK;
+    VG_TRY(vg::brute_nan_replay(idx, q, nq, k, mode, mk, mask_stride, oid, osc, st));  // queries whose distances may hold a NaN
+    return io.finish();
 }
 
 VG_API int32_t vg_debug_heap_replay(vg_ctx *ctx, int32_t is_max, int32_t unsigned_keys, const int32_t *ops, int32_t n_ops,

@@ -223,14 +223,12 @@ static int32_t batch_impl(vg_ctx *ctx, bool dot, const float *query, const float
     VG_TRY(o.init(out, static_cast<size_t>(n), st));
     int64_t blocks = (n + 15) / 16;
     if (blocks > 4096) blocks = 4096;
-    if (dot)
-        VG_LAUNCH(vg::batch_kernel<true>, dim3(static_cast<unsigned>(blocks)),
+    {
+        auto kern = dot ? vg::batch_kernel<true> : vg::batch_kernel<false>;
+        VG_LAUNCH(kern, dim3(static_cast<unsigned>(blocks)),
                            dim3(vg::kExactThreads), 0, st, q.ptr, t.ptr, static_cast<int>(dim), n, o.ptr);
-    else
-        VG_LAUNCH(vg::batch_kernel<false>, dim3(static_cast<unsigned>(blocks)),
-                           dim3(vg::kExactThreads), 0, st, q.ptr, t.ptr, static_cast<int>(dim), n, o.ptr);
+    }
     VG_TRY(o.finish());
-    if (o.on_host()) VG_HIP(hipStreamSynchronize(st));
     return VG_OK;
 }
 
@@ -270,17 +268,14 @@ VG_API int32_t vg_score_candidates(vg_index *idx, const float *queries, int64_t 
     for (int64_t q0 = 0; q0 < nq; q0 += maxy) {
         int64_t cnt = nq - q0 < maxy ? nq - q0 : maxy;
         dim3 grid(gx, static_cast<unsigned>(cnt));
-        if (dot)
-            VG_LAUNCH(vg::score_candidates_kernel<true>, grid, dim3(vg::kExactThreads), 0, st,
+        {
+            auto kern = dot ? vg::score_candidates_kernel<true> : vg::score_candidates_kernel<false>;
+            VG_LAUNCH(kern, grid, dim3(vg::kExactThreads), 0, st,
                                idx->d_vectors, idx->n, idx->dim, q.ptr + q0 * idx->dim,
                                c.ptr + q0 * nc, nc, o.ptr + q0 * nc);
-        else
-            VG_LAUNCH(vg::score_candidates_kernel<false>, grid, dim3(vg::kExactThreads), 0, st,
-                               idx->d_vectors, idx->n, idx->dim, q.ptr + q0 * idx->dim,
-                               c.ptr + q0 * nc, nc, o.ptr + q0 * nc);
+        }
     }
     VG_TRY(o.finish());
-    if (o.on_host()) VG_HIP(hipStreamSynchronize(st));
     return VG_OK;
 }
 
@@ -323,6 +318,5 @@ VG_API int32_t vg_rerank(vg_index *idx, const float *queries, int64_t nq, const 
     }
     VG_TRY(oid.finish());
     VG_TRY(osc.finish());
-    if (oid.on_host() || osc.on_host()) VG_HIP(hipStreamSynchronize(st));
     return VG_OK;
 }

@@ -14,12 +14,9 @@
 #include "vg_flat_gemm.hpp"
 #include "vg_internal.hpp"
 #include "vg_nominate.hpp"
+#include "vg_search.hpp"
 
 namespace vg {
-
-int32_t launch_topk_merge(const uint64_t *partial, int64_t nq, int lists, int k, bool descending,
-                          uint32_t *ids, float *scores, hipStream_t st, const int *only_if = nullptr,
-                          const int *always = nullptr);
 
 // One GEMM launch.  `dma` picks the LDS-DMA kernel (16-byte aligned operands, dim % 4 == 0);
 // both kernels need more dynamic LDS than the 64 KiB a kernel gets by default.
@@ -646,11 +643,6 @@ int32_t launch_page_patch(int64_t nq, int k, int off, int kk, bool descending, c
 
 }  // namespace vg
 
-namespace vg {
-int32_t flat_search_masked(vg_index *idx, const float *queries, int64_t nq, int32_t k, const uint8_t *mask, int64_t mask_stride,
-                           uint32_t *ids, float *scores, void *stream, bool l2_scores = false, bool cand_replay = true);
-}
-
 VG_API int32_t vg_search_flat(vg_index *idx, const float *queries, int64_t nq, int32_t k, uint32_t *ids,
                               float *scores, void *stream)
 {
@@ -673,8 +665,6 @@ int32_t vg::flat_search_masked(vg_index *idx, const float *queries, int64_t nq, 
     VG_CHECK(idx->n == 0 || idx->d_vectors, VG_ERR_NOT_READY, "vg_search_flat: index has no fp32 vectors");
     VG_CHECK(queries && ids && scores, VG_ERR_INVALID_ARG, "vg_search_flat: NULL buffer");
     VG_CHECK(k <= vg::kFlatMaxK, VG_ERR_UNSUPPORTED, "vg_search_flat: k=%d exceeds %d", k, vg::kFlatMaxK);
-    VG_HIP(hipSetDevice(idx->ctx->device));
-    hipStream_t st = vg::pick_stream(idx->ctx, stream);
     const bool dot = idx->metric != VG_METRIC_L2 && !l2_scores;
     const int64_t n = idx->n;
     const int dim = idx->dim;
@@ -685,18 +675,15 @@ int32_t vg::flat_search_masked(vg_index *idx, const float *queries, int64_t nq, 
     const bool big_k_scan = k > vg::kGemmMaxK && unfused;  // unfused: 64 nominated candidates cannot prove k near 64
     VG_CHECK(k <= 64 || !unfused, VG_ERR_UNSUPPORTED, "vg_search_flat: k=%d needs the fused GEMM path", k);
 
-    vg::DevIn<float> q;
-    vg::DevOut<uint32_t> oid;
-    vg::DevOut<float> osc;
-    VG_TRY(q.init(queries, static_cast<size_t>(nq) * dim, st));
-    VG_TRY(oid.init(ids, static_cast<size_t>(nq) * k, st));
-    VG_TRY(osc.init(scores, static_cast<size_t>(nq) * k, st));
+    vg::SearchIO io;
+    VG_TRY(io.init(idx->ctx, stream, queries, static_cast<size_t>(nq) * dim, ids, scores, static_cast<size_t>(nq) * k));
+    const hipStream_t st = io.st;
+    const float *q = io.q.ptr;
+    uint32_t *oid = io.oid.ptr;
+    float *osc = io.osc.ptr;
 
     if (n == 0) {
-        vg::DevTmp<uint64_t> none;
-        VG_TRY(none.init(static_cast<size_t>(nq) * k, st));
-        VG_HIP(hipMemsetAsync(none.ptr, 0xFF, static_cast<size_t>(nq) * k * 8, st));
-        VG_TRY(vg::launch_topk_merge(none.ptr, nq, 1, k, dot, oid.ptr, osc.ptr, st));
+        VG_TRY(vg::empty_results(nq, k, dot, oid, osc, st));
     } else if (mask == nullptr && nq <= vg::kScanMaxBatch && k <= 64 && dim % 4 == 0 && dim <= 1024 && dim >= 64 && !vg::hook(vg::kHookFlatNoScan) &&
                !vg::hook(vg::kHookFlatForceExact) && !unfused && (reinterpret_cast<uintptr_t>(idx->d_vectors) & 15) == 0) {
         // small batch: HBM-bound exact scan, kScanQB queries per pass over the rows
@@ -709,14 +696,13 @@ int32_t vg::flat_search_masked(vg_index *idx, const float *queries, int64_t nq, 
         for (int64_t q0 = 0; q0 < nq; q0 += vg::kScanQB) {
             const int cnt = static_cast<int>(std::min<int64_t>(vg::kScanQB, nq - q0));
             vg::ProfScope prof(idx->ctx, "flat_scan", st);
-            if (dot)
-                VG_LAUNCH(vg::flat_scan_mq_kernel<true>, dim3(slices), dim3(256), lds, st, idx->d_vectors, n, dim,
-                          q.ptr + q0 * dim, cnt, slices, k, partial + q0 * slices * k);
-            else
-                VG_LAUNCH(vg::flat_scan_mq_kernel<false>, dim3(slices), dim3(256), lds, st, idx->d_vectors, n, dim,
-                          q.ptr + q0 * dim, cnt, slices, k, partial + q0 * slices * k);
+            {
+                auto kern = dot ? vg::flat_scan_mq_kernel<true> : vg::flat_scan_mq_kernel<false>;
+                VG_LAUNCH(kern, dim3(slices), dim3(256), lds, st, idx->d_vectors, n, dim,
+                          q + q0 * dim, cnt, slices, k, partial + q0 * slices * k);
+            }
         }
-        VG_TRY(vg::launch_topk_merge(partial, nq, slices, k, dot, oid.ptr, osc.ptr, st));
+        VG_TRY(vg::launch_topk_merge(partial, nq, slices, k, dot, oid, osc, st));
         VG_LAUNCH(vg::flat_todo_kernel, dim3(1), dim3(256), 0, st, nullptr, nullptr, static_cast<int>(nq), nullptr,
                   idx->d_flat_stats);
     } else if (big_k_scan) {
@@ -738,13 +724,12 @@ int32_t vg::flat_search_masked(vg_index *idx, const float *queries, int64_t nq, 
             VG_LAUNCH(vg::flat_todo_kernel, dim3(1), dim3(256), 0, st, flags, flags + qc, static_cast<int>(cnt), todo,
                       idx->d_flat_stats);
             const unsigned slots = static_cast<unsigned>(std::min<int64_t>(cnt, vg::kExactSlots));
-            if (dot)
-                VG_LAUNCH(vg::flat_exact_kernel<true>, dim3(ex_slices, slots), dim3(256), 0, st, idx->d_vectors, n, dim,
-                          q.ptr + q0 * dim, todo, ex_slices, k, fpartial);
-            else
-                VG_LAUNCH(vg::flat_exact_kernel<false>, dim3(ex_slices, slots), dim3(256), 0, st, idx->d_vectors, n, dim,
-                          q.ptr + q0 * dim, todo, ex_slices, k, fpartial);
-            VG_TRY(vg::launch_topk_merge(fpartial, cnt, ex_slices, k, dot, oid.ptr + q0 * k, osc.ptr + q0 * k, st));
+            {
+                auto kern = dot ? vg::flat_exact_kernel<true> : vg::flat_exact_kernel<false>;
+                VG_LAUNCH(kern, dim3(ex_slices, slots), dim3(256), 0, st, idx->d_vectors, n, dim,
+                          q + q0 * dim, todo, ex_slices, k, fpartial, nullptr, nullptr, 0);
+            }
+            VG_TRY(vg::launch_topk_merge(fpartial, cnt, ex_slices, k, dot, oid + q0 * k, osc + q0 * k, st));
         }
     } else {
         const bool fused = !unfused;  // test hook: materialise the score matrix
@@ -813,7 +798,7 @@ int32_t vg::flat_search_masked(vg_index *idx, const float *queries, int64_t nq, 
         VG_HIP(hipMemsetAsync(always, vg::hook(vg::kHookFlatForceExact) ? 1 : 0, sizeof(int), st));
         for (int64_t q0 = 0; q0 < nq; q0 += qc) {
             const int64_t cnt = std::min(qc, nq - q0);
-            const float *qp = q.ptr + q0 * dim;
+            const float *qp = q + q0 * dim;
             const uint8_t *m0 = mask ? mask + q0 * mask_stride : nullptr;
             const int64_t mt = (cnt + vg::kGemmBM - 1) / vg::kGemmBM;
             const unsigned ucnt = static_cast<unsigned>(cnt);
@@ -874,24 +859,20 @@ int32_t vg::flat_search_masked(vg_index *idx, const float *queries, int64_t nq, 
                 const size_t sort_lds = sizeof(uint64_t) * static_cast<size_t>(cap);
                 auto vk = dot ? vg::flat_verify_sort_kernel<true> : vg::flat_verify_sort_kernel<false>;
                 VG_LAUNCH(vk, dim3(ucnt), dim3(256), sort_lds, st, idx->d_vectors, dim, qp, idx->d_norm_max, cand, counts, cap,
-                          k, oid.ptr + q0 * k, osc.ptr + q0 * k, flags, thr, sel_k, sel_k - 1, eps_extra);
+                          k, oid + q0 * k, osc + q0 * k, flags, thr, sel_k, sel_k - 1, eps_extra);
             } else if (fused && k > vg::kGemmMaxK) {
-                if (dot)
-                    VG_LAUNCH(vg::flat_verify_all_kernel<true>, dim3(ucnt), dim3(256), 0, st, idx->d_vectors, dim, qp,
-                              idx->d_norm_max, cand, counts, cap, k, oid.ptr + q0 * k, osc.ptr + q0 * k, flags, thr, sel_k,
+                {
+                    auto kern = dot ? vg::flat_verify_all_kernel<true> : vg::flat_verify_all_kernel<false>;
+                    VG_LAUNCH(kern, dim3(ucnt), dim3(256), 0, st, idx->d_vectors, dim, qp,
+                              idx->d_norm_max, cand, counts, cap, k, oid + q0 * k, osc + q0 * k, flags, thr, sel_k,
                               sel_k - 1, eps_extra);
-                else
-                    VG_LAUNCH(vg::flat_verify_all_kernel<false>, dim3(ucnt), dim3(256), 0, st, idx->d_vectors, dim, qp,
-                              idx->d_norm_max, cand, counts, cap, k, oid.ptr + q0 * k, osc.ptr + q0 * k, flags, thr, sel_k,
-                              sel_k - 1, eps_extra);
-            } else if (dot)
-                VG_LAUNCH(vg::flat_verify_kernel<true>, dim3(ucnt), dim3(256), 0, st, idx->d_vectors, n, dim, qp,
-                          idx->d_norm_max, cand_id, cand_sc, kc, k, oid.ptr + q0 * k, osc.ptr + q0 * k, flags, vthr,
+                }
+            } else {
+                auto kern = dot ? vg::flat_verify_kernel<true> : vg::flat_verify_kernel<false>;
+                VG_LAUNCH(kern, dim3(ucnt), dim3(256), 0, st, idx->d_vectors, n, dim, qp,
+                          idx->d_norm_max, cand_id, cand_sc, kc, k, oid + q0 * k, osc + q0 * k, flags, vthr,
                           sel_k, sel_k - 1, counts, cap, eps_extra);
-            else
-                VG_LAUNCH(vg::flat_verify_kernel<false>, dim3(ucnt), dim3(256), 0, st, idx->d_vectors, n, dim, qp,
-                          idx->d_norm_max, cand_id, cand_sc, kc, k, oid.ptr + q0 * k, osc.ptr + q0 * k, flags, vthr,
-                          sel_k, sel_k - 1, counts, cap, eps_extra);
+            }
             // step 4 always launches, on the work list the proofs left behind (normally empty)
             VG_LAUNCH(vg::flat_todo_kernel, dim3(1), dim3(256), 0, st, flags, always, static_cast<int>(cnt), todo,
                       idx->d_flat_stats);
@@ -913,31 +894,27 @@ int32_t vg::flat_search_masked(vg_index *idx, const float *queries, int64_t nq, 
             for (int off = 0; off < k; off += 64) {
                 const int kk = std::min(64, k - off);
                 const uint64_t *floor_keys = off ? min_keys : nullptr;
-                if (dot)
-                    VG_LAUNCH(vg::flat_exact_kernel<true>, dim3(ex_slices, slots), dim3(256), 0, st, idx->d_vectors, n,
+                {
+                    auto kern = dot ? vg::flat_exact_kernel<true> : vg::flat_exact_kernel<false>;
+                    VG_LAUNCH(kern, dim3(ex_slices, slots), dim3(256), 0, st, idx->d_vectors, n,
                               dim, qp, todo, ex_slices, kk, fpartial, floor_keys, m0, mask_stride);
-                else
-                    VG_LAUNCH(vg::flat_exact_kernel<false>, dim3(ex_slices, slots), dim3(256), 0, st, idx->d_vectors, n,
-                              dim, qp, todo, ex_slices, kk, fpartial, floor_keys, m0, mask_stride);
+                }
                 VG_TRY(vg::launch_topk_merge(fpartial, cnt, ex_slices, kk, dot, fid, fsc, st, flags, always));
                 if (k <= 64)
                     VG_LAUNCH(vg::flat_patch_kernel, dim3(ucnt), dim3(64), 0, st, flags, always, k, fid, fsc,
-                              oid.ptr + q0 * k, osc.ptr + q0 * k);
+                              oid + q0 * k, osc + q0 * k);
                 else
                     VG_LAUNCH(vg::flat_page_patch_kernel, dim3(ucnt), dim3(64), 0, st, flags, always, k, off, kk, dot, fid,
-                              fsc, oid.ptr + q0 * k, osc.ptr + q0 * k, min_keys);
+                              fsc, oid + q0 * k, osc + q0 * k, min_keys);
             }
         }
     }
     // queries whose scores may hold a NaN (a non-finite query value / row, an overflowing dot product): the reference's heap,
     // operation by operation (vg_cand_replay.hpp); every other query returns from this launch at once
     if (n > 0 && cand_replay)
-        VG_TRY(vg::launch_cand_replay(vg::FlatF32Scorer{idx->d_vectors, idx->d_norm_max + 1, dim, dot, 0}, q.ptr, dim, n, nq, k, dot, mask, mask_stride,
-                                      oid.ptr, osc.ptr, st));
-    VG_TRY(oid.finish());
-    VG_TRY(osc.finish());
-    if (oid.on_host() || osc.on_host()) VG_HIP(hipStreamSynchronize(st));
-    return VG_OK;
+        VG_TRY(vg::launch_cand_replay(vg::FlatF32Scorer{idx->d_vectors, idx->d_norm_max + 1, dim, dot, 0}, q, dim, n, nq, k, dot, mask, mask_stride,
+                                      oid, osc, st));
+    return io.finish();
 }
 
 // The nomination + proof of vg_search_flat over MANY (queries, rows) problems in one set of launches: the partition-probed search
@@ -1088,12 +1065,11 @@ int32_t flat_probe_gemm(vg_index *idx, const float *pair_queries, int64_t pairs,
         auto vk = dot ? flat_verify_all_kernel<true> : flat_verify_all_kernel<false>;
         VG_LAUNCH(vk, dim3(upairs), dim3(256), 0, st, idx->d_vectors, dim, queries_f32, idx->d_norm_max, cand, counts, cap, k, pair_ids,
                   pair_scores, fail, thr, sel_k, sel_k - 1, eps_extra);
-    } else if (dot)
-        VG_LAUNCH(flat_verify_kernel<true>, dim3(upairs), dim3(256), 0, st, idx->d_vectors, idx->n, dim, queries_f32, idx->d_norm_max,
+    } else {
+        auto kern = dot ? flat_verify_kernel<true> : flat_verify_kernel<false>;
+        VG_LAUNCH(kern, dim3(upairs), dim3(256), 0, st, idx->d_vectors, idx->n, dim, queries_f32, idx->d_norm_max,
                   cand_id, cand_sc, kc, k, pair_ids, pair_scores, fail, thr, sel_k, sel_k - 1, counts, cap, eps_extra);
-    else
-        VG_LAUNCH(flat_verify_kernel<false>, dim3(upairs), dim3(256), 0, st, idx->d_vectors, idx->n, dim, queries_f32, idx->d_norm_max,
-                  cand_id, cand_sc, kc, k, pair_ids, pair_scores, fail, thr, sel_k, sel_k - 1, counts, cap, eps_extra);
+    }
     return VG_OK;
 }
 }  // namespace vg

@@ -14,6 +14,7 @@
 #include "vg_exact.hpp"
 #include "vg_cand_replay.hpp"
 #include "vg_internal.hpp"
+#include "vg_search.hpp"
 
 namespace vg {
 
@@ -282,13 +283,6 @@ __global__ void flat_thr_proof_kernel(int64_t cnt, const int *__restrict__ untig
     fail[q] = ok ? 0 : 1;
 }
 
-// (k_flat.hip)
-int64_t flat_thr_sample_cols(int64_t n, int sample_stride);
-int32_t flat_thr_nominate(vg_index *idx, hipStream_t st, const float *qp, const float *uthr, int64_t cnt, const uint8_t *m0,
-                          int64_t mask_stride, int cap, int sel_k, int sample_stride, bool bf16, float eps_extra, float *sc, uint64_t *partial,
-                          uint32_t *sid, float *sthr, uint16_t *qbf, int *counts_wide, float *gthr, float *qnorm, int *untight, int *counts,
-                          uint64_t *cand);
-int32_t launch_flat_todo(const int *flags, const int *always, int cnt, int *todo, unsigned long long *stats, hipStream_t st);
 constexpr int kThrCountLine = 32;  // (kCountLine of k_flat.hip: the persistent bf16 tile's counter lines)
 
 __global__ void flat_thr_stats_kernel(unsigned long long *__restrict__ stats, long long searched, long long exact)
@@ -504,6 +498,5 @@ VG_API int32_t vg_search_flat_threshold(vg_index *idx, const float *queries, int
     VG_TRY(oid.finish());
     VG_TRY(osc.finish());
     VG_TRY(ocnt.finish());
-    if (oid.on_host() || osc.on_host() || ocnt.on_host()) VG_HIP(hipStreamSynchronize(st));
     return VG_OK;
 }

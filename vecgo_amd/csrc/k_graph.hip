@@ -18,17 +18,9 @@
 #include "vg_hnsw_layer.hpp"
 #include "vg_internal.hpp"
 #include "vg_cand_replay.hpp"
+#include "vg_search.hpp"
 
 namespace vg {
-
-int32_t launch_pq_build_table(const vg_pq *pq, const float *d_queries, int64_t nq, float *d_tables,
-                              bool scan_layout, hipStream_t st);
-// k_flat_threshold.hip: the best max_results keys of per-query lists, written best first; the engine's threshold filter
-int32_t launch_thr_select_lists(bool desc, const uint64_t *lists, int64_t list_cap, const int *counts, int64_t nq, int max_results,
-                                uint32_t *ids, float *scores, int32_t *out_counts, hipStream_t st);
-int32_t launch_thr_filter(bool desc, const float *thr, int64_t nq, int max_results, uint32_t *ids, float *scores, int32_t *counts,
-                          hipStream_t st);
-
 
 // ---- HNSW ----------------------------------------------------------------------------------------
 // SPLIT = false: both heaps of the query live in LDS (3 * ef items, ef <= kHnswLdsEf).  SPLIT = true (larger ef:
@@ -713,9 +705,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kind == kVam
     }
 }
 
-// sign bits + norm of each query (RaBitQ Encode, k_rabitq.hip)
-int32_t launch_rabitq_encode(const float *d_vectors, int64_t n, int dim, uint8_t *d_codes, hipStream_t st);
-
 }  // namespace vg
 
 namespace vg {
@@ -969,7 +958,6 @@ static int32_t search_hnsw_impl(vg_index *idx, bool pq, const float *queries, in
     VG_TRY(oid.finish());
     VG_TRY(osc.finish());
     VG_TRY(ost.finish());
-    if (oid.on_host() || osc.on_host() || ost.on_host()) VG_HIP(hipStreamSynchronize(st));
     return VG_OK;
 }
 
@@ -1195,6 +1183,5 @@ static int32_t vamana_impl(vg_index *idx, const float *queries, int64_t nq, int3
     VG_TRY(osc.finish());
     VG_TRY(ost.finish());
     VG_TRY(ocnt.finish());
-    if (oid.on_host() || osc.on_host() || ost.on_host() || ocnt.on_host()) VG_HIP(hipStreamSynchronize(st));
     return VG_OK;
 }

@@ -361,6 +361,5 @@ VG_API int32_t vg_search_hnsw_predicate(vg_index *idx, const float *queries, int
     VG_TRY(oid.finish());
     VG_TRY(osc.finish());
     VG_TRY(ost.finish());
-    if (oid.on_host() || osc.on_host() || ost.on_host()) VG_HIP(hipStreamSynchronize(st));
     return VG_OK;
 }

@@ -1176,7 +1176,6 @@ VG_API int32_t vg_kmeans_assign(vg_ctx *ctx, const float *vectors, int64_t n, in
             VG_TRY(km_launch_exact(metric != VG_METRIC_L2, v.ptr, n, dim, c.ptr, k, o.ptr, nullptr, st));
     }
     VG_TRY(o.finish());
-    if (o.on_host()) VG_HIP(hipStreamSynchronize(st));
     return VG_OK;
 }
 
@@ -1342,7 +1341,6 @@ VG_API int32_t vg_squared_l2_bounded_batch(vg_ctx *ctx, const float *query, cons
                        static_cast<int>(dim), n, b.ptr, n_bounds, od.ptr, oe.ptr);
     VG_TRY(od.finish());
     VG_TRY(oe.finish());
-    if (od.on_host() || oe.on_host()) VG_HIP(hipStreamSynchronize(st));
     return VG_OK;
 }
 
@@ -1379,6 +1377,5 @@ VG_API int32_t vg_pq_adc_lookup_batch(vg_ctx *ctx, const float *table, const uin
                            t.ptr, c.ptr, static_cast<int>(m), n, o.ptr);
     }
     VG_TRY(o.finish());
-    if (o.on_host()) VG_HIP(hipStreamSynchronize(st));
     return VG_OK;
 }

@@ -378,7 +378,6 @@ VG_API int32_t vg_opq_rotate(vg_opq *o, const float *vectors, int64_t n, float *
     VG_TRY(d.init(out, static_cast<size_t>(n) * o->dim, st));
     VG_TRY(opq_rotate_dev(o, v.ptr, n, d.ptr, false, st));
     VG_TRY(d.finish());
-    if (d.on_host()) VG_HIP(hipStreamSynchronize(st));
     return VG_OK;
 }
 
@@ -415,7 +414,6 @@ VG_API int32_t vg_opq_decode(vg_opq *o, const uint8_t *codes, int64_t n, float *
     VG_TRY(vg_pq_decode(o->pq, codes, n, rotated.ptr, stream));
     VG_TRY(opq_rotate_dev(o, rotated.ptr, n, d.ptr, true, st));
     VG_TRY(d.finish());
-    if (d.on_host()) VG_HIP(hipStreamSynchronize(st));
     return VG_OK;
 }
 

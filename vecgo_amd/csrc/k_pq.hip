@@ -2,6 +2,7 @@
 #include "vg_device.hpp"
 #include "vg_hnsw_layer.hpp"
 #include "vg_internal.hpp"
+#include "vg_search.hpp"
 
 namespace vg {
 
@@ -221,6 +222,5 @@ VG_API int32_t vg_pq_build_distance_table(vg_pq *pq, const float *queries, int64
         VG_TRY(vg::launch_pq_build_table(pq, q.ptr, nq, t.ptr, false, st));
     }
     VG_TRY(t.finish());
-    if (t.on_host()) VG_HIP(hipStreamSynchronize(st));
     return VG_OK;
 }

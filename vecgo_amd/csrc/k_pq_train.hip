@@ -1573,7 +1573,6 @@ VG_API int32_t vg_pq_encode(vg_pq *pq, const float *vectors, int64_t n, uint8_t 
                   pq->d_offsets, c.ptr);
     }
     VG_TRY(c.finish());
-    if (c.on_host()) VG_HIP(hipStreamSynchronize(st));
     return VG_OK;
 }
 
@@ -1603,7 +1602,6 @@ VG_API int32_t vg_pq_decode(vg_pq *pq, const uint8_t *codes, int64_t n, float *o
                            pq->d_offsets, o.ptr);
     }
     VG_TRY(o.finish());
-    if (o.on_host()) VG_HIP(hipStreamSynchronize(st));
     return VG_OK;
 }
 
@@ -1633,6 +1631,5 @@ VG_API int32_t vg_pq_asymmetric_distance_batch(vg_pq *pq, const float *query, co
                            q.ptr, c.ptr, n, pq->dim, pq->m, pq->subdim, pq->k, pq->d_codebooks, pq->d_scales,
                            pq->d_offsets, o.ptr);
     VG_TRY(o.finish());
-    if (o.on_host()) VG_HIP(hipStreamSynchronize(st));
     return VG_OK;
 }

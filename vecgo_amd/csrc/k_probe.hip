@@ -15,35 +15,9 @@
 #include "vg_internal.hpp"
 #include "vg_cand_replay.hpp"
 #include "vg_nominate.hpp"
+#include "vg_search.hpp"
 
 namespace vg {
-
-int32_t launch_topk_merge(const uint64_t *partial, int64_t nq, int lists, int k, bool descending,
-                          uint32_t *ids, float *scores, hipStream_t st, const int *only_if = nullptr,
-                          const int *always = nullptr);
-int32_t launch_pq_build_table(const vg_pq *pq, const float *d_queries, int64_t nq, float *d_tables,
-                              bool scan_layout, hipStream_t st);
-int32_t launch_probe_scan_adc(const vg_index *idx, const float *tables, const uint32_t *probes, const uint32_t *part_off,
-                              int64_t nq, int np, int split, int k, uint64_t *partial, const uint64_t *min_keys, bool desc,
-                              const uint8_t *mask, int64_t mask_stride, hipStream_t st);
-int32_t launch_probe_scan_sq8(const vg_index *idx, const float *queries, const uint32_t *probes, const uint32_t *part_off,
-                              int64_t nq, int np, int sub, int k, uint64_t *partial, const uint64_t *min_keys,
-                              const uint8_t *mask, int64_t mask_stride, hipStream_t st);
-int32_t launch_probe_scan_sq8_grouped(const vg_index *idx, const float *queries, const uint32_t *part_off,
-                                      const uint32_t *pair_of, const ProbeGroup *groups, const uint32_t *ngroups, unsigned gmax,
-                                      int np, int sub, int k, uint64_t *partial, const uint64_t *min_keys, const uint8_t *mask,
-                                      int64_t mask_stride, hipStream_t st);
-int32_t flat_search_masked(vg_index *idx, const float *queries, int64_t nq, int32_t k, const uint8_t *mask, int64_t mask_stride,
-                           uint32_t *ids, float *scores, void *stream, bool l2_scores = false, bool cand_replay = true);
-int32_t sq8_nan_replay(vg_index *idx, const float *d_queries, int64_t nq, int k, const uint8_t *d_mask, int64_t mask_stride,
-                       const uint32_t *d_probes, int np, const uint32_t *d_part_off, uint32_t *d_ids, float *d_scores, hipStream_t st);
-int32_t pq_nan_replay(vg_index *idx, const float *d_queries, int64_t nq, int k, bool desc, const uint8_t *d_mask, int64_t mask_stride,
-                      const uint32_t *d_probes, int np, const uint32_t *d_part_off, uint32_t *d_ids, float *d_scores, hipStream_t st);
-int32_t pq_adc_search_masked(vg_index *idx, const float *queries, int64_t nq, int32_t k, const uint8_t *mask, int64_t mask_stride,
-                             bool desc, uint32_t *ids, float *scores, void *stream);
-int32_t launch_page_patch(int64_t nq, int k, int off, int kk, bool descending, const int *always_one,
-                          const uint32_t *fids, const float *fscores, uint32_t *ids, float *scores, uint64_t *min_keys,
-                          hipStream_t st);
 
 // ---- 1. the nprobes closest centroids (kmeans.go:217-280) -----------------------------------------
 // 16 lanes per centroid, batch-kernel order; for Dot / Cosine the reference sorts -dot ascending,
@@ -633,35 +607,29 @@ static int32_t flat_probed_entry(vg_index *idx, const float *queries, int64_t nq
     if (!idx || nq <= 0 || k <= 0 || !queries || !ids || !scores || (scan != VG_SCAN_F32 && scan != VG_SCAN_PQ && scan != VG_SCAN_SQ8) ||
         (idx->num_partitions <= 1 && mask == nullptr) || idx->n == 0 || vg::hook(vg::kHookNoCandReplay))
         return flat_probed_impl(idx, queries, nq, k, nprobes, scan, mask, mask_stride, ids, scores, stream);
-    VG_HIP(hipSetDevice(idx->ctx->device));
-    hipStream_t st = vg::pick_stream(idx->ctx, stream);
-    vg::DevIn<float> q;
-    vg::DevIn<uint8_t> mk;
-    vg::DevOut<uint32_t> oid;
-    vg::DevOut<float> osc;
-    const int64_t mask_bytes = (idx->n + 7) / 8;
-    VG_TRY(q.init(queries, static_cast<size_t>(nq) * idx->dim, st));
-    VG_TRY(mk.init(mask, mask ? static_cast<size_t>(mask_stride ? (nq - 1) * mask_stride + mask_bytes : mask_bytes) : 0, st));
-    VG_TRY(oid.init(ids, static_cast<size_t>(nq) * k, st));
-    VG_TRY(osc.init(scores, static_cast<size_t>(nq) * k, st));
+    vg::SearchIO io;
+    VG_TRY(io.init(idx->ctx, stream, queries, static_cast<size_t>(nq) * idx->dim, ids, scores, static_cast<size_t>(nq) * k, mask,
+                   vg::mask_span(mask, mask_stride, nq, idx->n)));
+    const hipStream_t st = io.st;
+    const float *q = io.q.ptr;
+    const uint8_t *mk = io.mk.ptr;
+    uint32_t *oid = io.oid.ptr;
+    float *osc = io.osc.ptr;
     const bool whole = idx->num_partitions <= 1, dot = idx->metric != VG_METRIC_L2;
     int np = nprobes <= 0 ? 1 : nprobes;
     if (np > idx->num_partitions) np = idx->num_partitions;
     vg::DevTmp<uint32_t> probes;  // the search leaves its probe lists here: the replay walks the same partitions in the same order
     if (!whole) VG_TRY(probes.init(static_cast<size_t>(nq) * np, st));
-    VG_TRY(flat_probed_impl(idx, q.ptr, nq, k, nprobes, scan, mk.ptr, mask_stride, oid.ptr, osc.ptr, st, true, whole ? nullptr : probes.ptr));
+    VG_TRY(flat_probed_impl(idx, q, nq, k, nprobes, scan, mk, mask_stride, oid, osc, st, true, whole ? nullptr : probes.ptr));
     const uint32_t *pr = whole ? nullptr : probes.ptr, *po = whole ? nullptr : idx->d_part_off;
     if (scan == VG_SCAN_SQ8)
-        VG_TRY(vg::sq8_nan_replay(idx, q.ptr, nq, k, mk.ptr, mask_stride, pr, np, po, oid.ptr, osc.ptr, st));
+        VG_TRY(vg::sq8_nan_replay(idx, q, nq, k, mk, mask_stride, pr, np, po, oid, osc, st));
     else if (scan == VG_SCAN_PQ)
-        VG_TRY(vg::pq_nan_replay(idx, q.ptr, nq, k, dot, mk.ptr, mask_stride, pr, np, po, oid.ptr, osc.ptr, st));
+        VG_TRY(vg::pq_nan_replay(idx, q, nq, k, dot, mk, mask_stride, pr, np, po, oid, osc, st));
     else
-        VG_TRY(vg::launch_cand_replay(vg::FlatF32Scorer{idx->d_vectors, idx->d_norm_max + 1, idx->dim, dot, 0}, q.ptr, idx->dim, idx->n, nq, k, dot,
-                                      mk.ptr, mask_stride, oid.ptr, osc.ptr, st, nullptr, pr, np, po));
-    VG_TRY(oid.finish());
-    VG_TRY(osc.finish());
-    if (oid.on_host() || osc.on_host()) VG_HIP(hipStreamSynchronize(st));
-    return VG_OK;
+        VG_TRY(vg::launch_cand_replay(vg::FlatF32Scorer{idx->d_vectors, idx->d_norm_max + 1, idx->dim, dot, 0}, q, idx->dim, idx->n, nq, k, dot,
+                                      mk, mask_stride, oid, osc, st, nullptr, pr, np, po));
+    return io.finish();
 }
 
 VG_API int32_t vg_search_flat_probed(vg_index *idx, const float *queries, int64_t nq, int32_t k, int32_t nprobes,
@@ -680,6 +648,354 @@ VG_API int32_t vg_search_flat_filtered(vg_index *idx, const float *queries, int6
              "vg_search_flat_filtered: mask_stride %lld is shorter than a mask (%lld bytes)", static_cast<long long>(mask_stride),
              static_cast<long long>(mask_bytes));
     return flat_probed_entry(idx, queries, nq, k, nprobes, scan, mask, mask_stride, ids, scores, stream);
+}
+
+// ---- flat_probed_impl on device buffers ----------------------------------------------------------------------------------
+// What the paths of one probed search share: the call's arguments as flat_probed_impl checked them (np probes per query over
+// `parts` ranges), and — once the arena is committed — the probe lists, the ranges and the shape of the per-query key lists.
+struct ProbedCall {
+    vg_index *idx;
+    const float *q;
+    int64_t nq;
+    int32_t k, nprobes;
+    int np, parts;
+    int32_t scan;
+    const uint8_t *mk;
+    int64_t mask_stride;
+    uint32_t *oid;
+    float *osc;
+    hipStream_t st;
+    bool allow_nomination;
+    bool whole, dot;  // segment.go:745-749: one range, the whole segment; the segment's metric
+    int64_t pairs;    // (query, probe) pairs
+    int sub = 1, split = 1, lists = 1;  // slices per probed range (fp32, SQ8) / shares of a probe list (PQ); k-lists per query
+    uint32_t *probes = nullptr;
+    const uint32_t *part_off = nullptr;
+    // the queries whose proof failed, searched again without the nomination (rescan_failed, vg_nominate.hpp)
+    int32_t rescan(const std::vector<int> &failed) const
+    {
+        return vg::rescan_failed(failed, q, idx->dim, k, mk, mask_stride, (idx->n + 7) / 8, oid, osc, st,
+                                 [&](const float *fq, int64_t nf, const uint8_t *fmask, int64_t fmask_stride, uint32_t *fid, float *fsc) {
+                                     return flat_probed_impl(idx, fq, nf, k, nprobes, scan, fmask, fmask_stride, fid, fsc, st, false);
+                                 });
+    }
+};
+
+// (a) A filtered search of the whole segment that another entry point answers faster; *done = false: none applies.
+static int32_t probed_whole_shortcut(const ProbedCall &c, bool *done)
+{
+    vg_index *idx = c.idx;
+    *done = c.whole && c.mk && !vg::hook(vg::kHookProbeNoGroup);  // (the test hook keeps the batch on the probe kernels)
+    if (!*done) return VG_OK;
+    // A batch of filtered fp32 queries over the whole segment: the matrix-core nomination of vg_search_flat with the filter
+    // applied where candidates are sampled and appended (k_flat.hip) — its cost does not depend on the selectivity, the
+    // probe kernels pay per wanted row: 8 queries up it wins or ties (tools/filtered_time.py).  Same results either way.
+    if (c.scan == VG_SCAN_F32 && c.nq >= 8) return vg::flat_search_masked(idx, c.q, c.nq, c.k, c.mk, c.mask_stride, c.oid, c.osc, c.st);
+    // A filtered SQ8 batch over the whole segment with vg_index_enable_sq8_nomination: the bf16 nomination with the filter in its
+    // epilogue, the exact re-score from the codes, the proof (k_sq8.hip); queries whose proof fails take the probe kernels
+    if (c.scan == VG_SCAN_SQ8 && c.allow_nomination && vg::sq8_nomination_applies(idx, c.q, c.nq, c.k)) {
+        std::vector<int> failed;
+        VG_TRY(vg::sq8_nominated_pass(idx, c.q, c.nq, c.k, c.mk, c.mask_stride, c.oid, c.osc, c.st, failed));
+        return c.rescan(failed);
+    }
+    // A filtered PQ scan of the whole segment, k <= 64 and a table that fits LDS: the pipelined scan of vg_search_pq_adc with
+    // the filter where keys are made (the probe kernel is the plain loop, twice its time)
+    if (c.scan == VG_SCAN_PQ && c.k <= 64 && idx->pq->m <= 96)
+        return vg::pq_adc_search_masked(idx, c.q, c.nq, c.k, c.mk, c.mask_stride, c.dot, c.oid, c.osc, c.st);
+    *done = false;
+    return VG_OK;
+}
+
+// (b) fp32 or SQ8, partitions probed by 12 or more queries each on average: nomination + proof on the matrix cores (2c)
+// (1M x 768 in 122 partitions, 1024 queries, ms per call, exact kernels -> this: nprobes 1 (8 per partition) 1.21 -> 1.18,
+// 2: 2.1 -> 1.4, 4: 3.75 -> 1.3, 8: 7.25 -> 2.3, 16: 11.6 -> 4.5, 32: 21.0 -> 7.0; tools/probe_gemm_time.py)
+// (a filtered batch too: a pair's filter is its query's — probe_gather_queries_kernel notes where each starts)
+// (k <= 48: the pairs' 64 best nominees re-scored; up to kProbeGemmMaxK: everything below a deeper threshold re-scored, and the
+// flagged queries — normally none — searched again as a subset, the scan kernels' k > 64 being paged)
+// plan() decides whether the path applies and adds its arena pieces; run() after the arena's commit().
+struct ProbedGemmPath {
+    bool f32 = false, sq8 = false;
+    int64_t grids[4] = {0, 0, 0, 0}, ns_max = 0;  // sample / main of the 128-query tiles, sample / main of the 64-query tiles
+    vg::NomImage gimg;  // the image the nomination runs on: none (the fp32 rows), the SQ8 image, or a view of the fp32 rows' bf16 filter
+    int i_bcnt = 0, i_bcur = 0, i_bgrp = 0, i_fbs = 0, i_fbm = 0, i_fbss = 0, i_fbsm = 0, i_bpair = 0, i_pairq = 0, i_pids = 0, i_pscore = 0,
+        i_pfail = 0, i_qfail = 0, i_moff = 0, i_gscr = 0;
+    bool applies() const { return f32 || sq8; }
+    // the keys the path leaves in the paged driver's `partial`: k per pair, also when k is paged for the scan kernels
+    static size_t partial_keys(const ProbedCall &c)
+    {
+        return c.whole || c.k > vg::kProbeGemmMaxK || c.scan == VG_SCAN_PQ || c.pairs > 65535 ? size_t(0) : static_cast<size_t>(c.pairs) * c.k;
+    }
+    void plan(const ProbedCall &c, vg::ArenaCall &ar)
+    {
+        const vg_index *idx = c.idx;
+        const int parts = c.parts, k = c.k;
+        const int64_t pairs = c.pairs;
+        const bool gemm_shape = !c.whole && k <= vg::kProbeGemmMaxK && (k <= 64 || c.allow_nomination) && idx->dim % 4 == 0 && pairs <= 65535 &&
+                                pairs >= 12 * static_cast<int64_t>(parts) &&
+                                (reinterpret_cast<uintptr_t>(c.q) & 15) == 0 && static_cast<int>(idx->h_part_off.size()) == parts + 1 &&
+                                !vg::hook(vg::kHookProbeNoGroup) && !vg::hook(vg::kHookProbeNoGemm);
+        f32 = c.scan == VG_SCAN_F32 && gemm_shape && (reinterpret_cast<uintptr_t>(idx->d_vectors) & 15) == 0;
+        // SQ8 with vg_index_enable_sq8_nomination: the same grouped nomination on the bfloat16 image of the dequantised rows, the
+        // pairs' 64 candidates re-scored from the codes and proven by the verify pair (launch_sq8_verify, k_sq8.hip)
+        sq8 = c.scan == VG_SCAN_SQ8 && gemm_shape && c.allow_nomination && idx->sq_nom.rows != nullptr;
+        const bool gemm = applies();
+        if (gemm) {  // launch bounds from the partition sizes: one query tile per partition + the batch's further tiles on the largest
+            int64_t sum_s = 0, sum_m = 0, max_s = 0, max_m = 0, max_nst = 0, max_nt = 0;
+            for (int p = 0; p < parts; p++) {
+                const int64_t rows = static_cast<int64_t>(idx->h_part_off[p + 1]) - idx->h_part_off[p];
+                const int64_t nt = (rows + vg::kGemmBN - 1) / vg::kGemmBN, nst = (nt + vg::kProbeSampleStride - 1) / vg::kProbeSampleStride;
+                const int64_t bs = ((nst + 7) / 8) * 8, bm = ((nt + 7) / 8) * 8;
+                sum_s += bs;
+                sum_m += bm;
+                max_s = std::max(max_s, bs);
+                max_m = std::max(max_m, bm);
+                grids[2] += nst;
+                grids[3] += nt;
+                max_nst = std::max(max_nst, nst);
+                max_nt = std::max(max_nt, nt);
+                ns_max = std::max(ns_max, nst * vg::kGemmBN);
+            }
+            grids[0] = sum_s + (pairs / vg::kGemmBM) * max_s;
+            grids[1] = sum_m + (pairs / vg::kGemmBM) * max_m;
+            grids[2] += (pairs / (vg::kProbeRB * vg::kG32BM)) * max_nst;  // (64-query tiles: a partition's first + the batch's further ones on the largest)
+            grids[3] += (pairs / (vg::kProbeRB * vg::kG32BM)) * max_nt;
+        }
+        const size_t gw = gemm ? static_cast<size_t>(parts) + 1 : 0;
+        i_bcnt = ar.add(sizeof(uint32_t) * gw);
+        i_bcur = ar.add(sizeof(uint32_t) * gw);
+        i_bgrp = ar.add(sizeof(vg::GemmGroup) * gw);
+        i_fbs = ar.add(sizeof(int64_t) * gw);
+        i_fbm = ar.add(sizeof(int64_t) * gw);
+        i_fbss = ar.add(sizeof(int64_t) * gw);
+        i_fbsm = ar.add(sizeof(int64_t) * gw);
+        i_bpair = ar.add(gemm ? sizeof(uint32_t) * static_cast<size_t>(pairs) : 0);
+        i_pairq = ar.add(gemm ? sizeof(float) * static_cast<size_t>(pairs) * idx->dim : 0);
+        i_pids = ar.add(gemm ? sizeof(uint32_t) * static_cast<size_t>(pairs) * k : 0);
+        i_pscore = ar.add(gemm ? sizeof(float) * static_cast<size_t>(pairs) * k : 0);
+        i_pfail = ar.add(gemm ? sizeof(int) * static_cast<size_t>(pairs) : 0);
+        i_qfail = ar.add(gemm ? sizeof(int) * static_cast<size_t>(c.nq) : 0);
+        i_moff = ar.add(gemm ? sizeof(int64_t) * static_cast<size_t>(pairs) : 0);
+        // (fp32 rows with vg_index_enable_bf16_filter: the grouped nomination on that image too)
+        const bool f32_bf16 = f32 && idx->d_vectors_bf16 != nullptr;
+        gimg = sq8        ? idx->sq_nom
+               : f32_bf16 ? vg::NomImage{idx->d_vectors_bf16, idx->vectors_bf16_dim, idx->d_norms, idx->d_norm_max}
+                          : vg::NomImage{};
+        i_gscr = ar.add(gemm ? vg::flat_probe_gemm_scratch_bytes(pairs, ns_max, k, gimg.dim_pad) : 0);
+    }
+    // bucket the pairs by partition, gather their queries, nominate + prove (flat_probe_gemm), pack, merge; then the queries
+    // whose proof failed.  partial: the paged driver's key lists.
+    int32_t run(const ProbedCall &c, vg::ArenaCall &ar, uint64_t *partial) const
+    {
+        vg_index *idx = c.idx;
+        const int64_t nq = c.nq, pairs = c.pairs;
+        const int k = c.k, np = c.np, parts = c.parts;
+        const hipStream_t st = c.st;
+        uint32_t *bcnt = ar.get<uint32_t>(i_bcnt), *bcur = ar.get<uint32_t>(i_bcur), *bpair = ar.get<uint32_t>(i_bpair);
+        vg::GemmGroup *bgrp = ar.get<vg::GemmGroup>(i_bgrp);
+        int64_t *fbs = ar.get<int64_t>(i_fbs), *fbm = ar.get<int64_t>(i_fbm), *fbss = ar.get<int64_t>(i_fbss), *fbsm = ar.get<int64_t>(i_fbsm);
+        float *pairq = ar.get<float>(i_pairq), *pair_sc = ar.get<float>(i_pscore);
+        uint32_t *pair_ids = ar.get<uint32_t>(i_pids);
+        int *pfail = ar.get<int>(i_pfail), *qfail = ar.get<int>(i_qfail);
+        const unsigned pb = static_cast<unsigned>((pairs + 255) / 256);
+        VG_HIP(hipMemsetAsync(bcnt, 0, sizeof(uint32_t) * (static_cast<size_t>(parts) + 1), st));
+        VG_HIP(hipMemsetAsync(qfail, 0, sizeof(int) * static_cast<size_t>(nq), st));
+        VG_LAUNCH(vg::probe_bucket_count_kernel, dim3(pb), dim3(256), 0, st, c.probes, pairs, bcnt);
+        VG_LAUNCH(vg::probe_bucket_scan_kernel, dim3(1), dim3(1024), 0, st, bcnt, c.part_off, parts, bcur, bgrp, fbs, fbm, fbss, fbsm);
+        VG_LAUNCH(vg::probe_bucket_fill_kernel, dim3(pb), dim3(256), 0, st, c.probes, pairs, bcur, bpair);
+        int64_t *moff = ar.get<int64_t>(i_moff);
+        VG_LAUNCH(vg::probe_gather_queries_kernel, dim3(static_cast<unsigned>(pairs)), dim3(256), 0, st, c.q, bpair, np, idx->dim, pairq,
+                  c.mask_stride, moff);
+        {
+            vg::ProfScope prof(idx->ctx, "flat_probe", st);
+            const int64_t *const fb[4] = {fbs, fbm, fbss, fbsm};
+            vg::ProbeNominated nom{};
+            VG_TRY(vg::flat_probe_gemm(idx, pairq, pairs, bgrp, fb, parts, grids, vg::kProbeSampleStride, ns_max, k, pair_ids, pair_sc,
+                                       pfail, ar.get<char>(i_gscr), c.mk, moff, st, gimg, &nom));
+            if (sq8) VG_TRY(vg::launch_sq8_verify(idx, pairq, pairs, nom, k, pair_ids, pair_sc, pfail, st));
+        }
+        // lists = np * sub in this configuration; the pairs' k results fill the first np lists' worth of `partial`
+        VG_LAUNCH(vg::probe_pack_kernel, dim3(static_cast<unsigned>(pairs)), dim3(64), 0, st, bpair, pair_ids, pair_sc, pfail, k, np, c.dot,
+                  partial, qfail);
+        VG_TRY(vg::launch_topk_merge(partial, nq, np, k, c.dot, c.oid, c.osc, st));
+        if (sq8 || k > 64) {  // the flagged queries (normally none) go through the scan kernels: read the flags, search that subset
+            std::vector<int> failed;
+            VG_TRY(vg::failed_list(qfail, nq, 0, st, failed));
+            ar.lock.unlock();  // the subset's own search takes the arena
+            return c.rescan(failed);
+        }
+        // the queries with a failed proof (ties at the k-th score, more than 4096 rows below a threshold): the exact kernel, one
+        // workgroup per (slice, probe, query) that leaves at once unless its query is flagged
+        for (int64_t q0 = 0; q0 < nq; q0 += 65535) {
+            const int64_t cnt = std::min<int64_t>(65535, nq - q0);
+            const dim3 grid(static_cast<unsigned>(c.sub), static_cast<unsigned>(np), static_cast<unsigned>(cnt));
+            auto kern = c.mk ? (c.dot ? vg::probe_scan_f32_kernel<true, true> : vg::probe_scan_f32_kernel<false, true>)
+                             : (c.dot ? vg::probe_scan_f32_kernel<true, false> : vg::probe_scan_f32_kernel<false, false>);
+            VG_LAUNCH(kern, grid, dim3(256), 0, st, idx->d_vectors, idx->dim, c.q + q0 * idx->dim, c.probes + q0 * np, c.part_off, np, c.sub, k,
+                      partial + q0 * c.lists * k, nullptr, c.mk ? c.mk + q0 * c.mask_stride : nullptr, c.mask_stride, qfail + q0);
+        }
+        return vg::launch_topk_merge(partial, nq, c.lists, k, c.dot, c.oid, c.osc, st, qfail);
+    }
+};
+
+// (c) The scan kernels over the probed ranges: fp32 pair order (grouped by partition when there are enough pairs), PQ table
+// lookups (k_adc.hip), SQ8 (k_sq8.hip).  plan() sizes the slices — c.sub, c.split, c.lists — and adds its arena pieces; scan():
+// one page of the paged driver, after the arena's commit().
+struct ProbedScanPath {
+    bool grouped_f32 = false, grouped_sq8 = false;
+    int64_t qchunk = 1;
+    int i_gcounts = 0, i_gcursor = 0, i_gstart = 0, i_pair_of = 0, i_groups = 0, i_ngroups = 0, i_tables = 0;
+    void plan(ProbedCall &c, vg::ArenaCall &ar)
+    {
+        const vg_index *idx = c.idx;
+        const int64_t nq = c.nq, pairs = c.pairs;
+        const int np = c.np, parts = c.parts;
+        // fp32: with enough pairs the queries are grouped by partition (rows read once per group); the
+        // row-in-registers scan needs 16-byte aligned rows of at most 1024 floats
+        // (a filtered whole segment is "probed" in every piece by every query: grouping pays from a handful of queries on)
+        const bool group_ok = (c.whole ? nq >= 4 : pairs >= 16) && !vg::hook(vg::kHookProbeNoGroup);  // test hook: one pass per pair
+        grouped_f32 = c.scan == VG_SCAN_F32 && group_ok && idx->dim % 4 == 0 && idx->dim <= 1024 &&
+                      (reinterpret_cast<uintptr_t>(idx->d_vectors) & 15) == 0;
+        // SQ8: the group's queries (padded to whole 16-dimension groups) have to fit LDS next to the merge scratch
+        grouped_sq8 = c.scan == VG_SCAN_SQ8 && group_ok &&
+                      sizeof(float) * vg::kProbeQB * static_cast<size_t>(idx->sq_groups) * 16 <= 128 * 1024;
+        const bool grouped = grouped_f32 || grouped_sq8;
+        // enough workgroups to fill the device when there are few (query, probe) pairs
+        const int want = 4 * idx->ctx->compute_units;
+        c.sub = static_cast<int>(std::min<int64_t>(32, std::max<int64_t>(1, (want + pairs - 1) / pairs)));
+        c.split = static_cast<int>(std::min<int64_t>(np, std::max<int64_t>(1, (idx->ctx->compute_units + nq - 1) / nq)));
+        if (grouped) {  // workgroups are (group of up to kProbeQB pairs) x slice: size the slices for the groups
+            const int64_t g_est = std::max<int64_t>(1, pairs / vg::kProbeQB) + std::min<int64_t>(parts, pairs) / 2;
+            c.sub = static_cast<int>(std::min<int64_t>(32, std::max<int64_t>(1, (want + g_est - 1) / g_est)));
+        }
+        c.lists = c.scan == VG_SCAN_PQ ? c.split : np * c.sub;
+        const int lut_words = c.scan == VG_SCAN_PQ ? (((idx->pq->m >> 4) + 1) >> 1) * 8192 + (idx->pq->m & 15) * 256 : 0;
+        qchunk = std::max<int64_t>(1, 65535 / np);
+        const int64_t chunk_pairs = std::min<int64_t>(nq, qchunk) * np;
+        const size_t gwords = grouped ? static_cast<size_t>(parts) + 1 : 0;
+        i_gcounts = ar.add(sizeof(uint32_t) * gwords);
+        i_gcursor = ar.add(sizeof(uint32_t) * gwords);
+        i_gstart = ar.add(sizeof(uint32_t) * gwords);
+        i_pair_of = ar.add(grouped ? sizeof(uint32_t) * static_cast<size_t>(chunk_pairs) : 0);
+        i_groups = ar.add(grouped ? sizeof(vg::ProbeGroup) * static_cast<size_t>(chunk_pairs) : 0);
+        i_ngroups = ar.add(grouped ? 256 : 0);
+        i_tables = ar.add(sizeof(float) * static_cast<size_t>(nq) * lut_words);
+    }
+    int32_t run(const ProbedCall &c, const vg::ArenaCall &ar, const vg::PagedTopK &pages) const
+    {
+        const vg_index *idx = c.idx;
+        const int64_t nq = c.nq;
+        const int np = c.np, parts = c.parts, sub = c.sub, lists = c.lists;
+        const hipStream_t st = c.st;
+        const uint8_t *mk = c.mk;
+        const bool dot = c.dot;
+        float *tables = ar.get<float>(i_tables);
+        uint32_t *gcounts = ar.get<uint32_t>(i_gcounts), *gcursor = ar.get<uint32_t>(i_gcursor);
+        uint32_t *gstart = ar.get<uint32_t>(i_gstart), *pair_of = ar.get<uint32_t>(i_pair_of);
+        uint32_t *ngroups = ar.get<uint32_t>(i_ngroups);
+        vg::ProbeGroup *groups = ar.get<vg::ProbeGroup>(i_groups);
+        const size_t mq_lds = sizeof(float) * vg::kProbeQB * static_cast<size_t>(idx->dim) + 4 * 64 * sizeof(uint64_t) + 64;
+        auto mq_kern = mk ? (dot ? vg::probe_scan_f32_mq_kernel<true, true> : vg::probe_scan_f32_mq_kernel<false, true>)
+                          : (dot ? vg::probe_scan_f32_mq_kernel<true, false> : vg::probe_scan_f32_mq_kernel<false, false>);
+        if (grouped_f32)
+            VG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(mq_kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       static_cast<int>(mq_lds)));
+        if (c.scan == VG_SCAN_PQ) VG_TRY(vg::launch_pq_build_table(idx->pq, c.q, nq, tables, true, st));
+        // a wave keeps 64 keys: k > 64 comes in pages of 64 results, each page a scan of the probed ranges for the
+        // keys after the previous page's last one
+        return pages.run(ar, lists, dot, c.oid, c.osc, st, [&](int kk, uint64_t *partial, const uint64_t *floor) -> int32_t {
+            if (grouped_f32 || grouped_sq8) {
+                for (int64_t q0 = 0; q0 < nq; q0 += qchunk) {
+                    const int64_t cnt = std::min<int64_t>(qchunk, nq - q0);
+                    const int64_t cpairs = cnt * np;
+                    const unsigned gmax = static_cast<unsigned>(std::min<int64_t>(cpairs, cpairs / vg::kProbeQB + parts));
+                    const uint8_t *m0 = mk ? mk + q0 * c.mask_stride : nullptr;
+                    VG_HIP(hipMemsetAsync(gcounts, 0, sizeof(uint32_t) * (static_cast<size_t>(parts) + 1), st));
+                    VG_LAUNCH(vg::probe_group_kernel, dim3(1), dim3(1024), 0, st, c.probes + q0 * np, cpairs, parts, gcounts, gcursor,
+                              gstart, pair_of, groups, ngroups);
+                    if (grouped_sq8) {
+                        VG_TRY(vg::launch_probe_scan_sq8_grouped(idx, c.q + q0 * idx->dim, c.part_off, pair_of, groups, ngroups, gmax, np,
+                                                                 sub, kk, partial + q0 * lists * kk, floor ? floor + q0 : nullptr, m0,
+                                                                 c.mask_stride, st));
+                        continue;
+                    }
+                    vg::ProfScope prof(idx->ctx, "flat_probe", st);
+                    VG_LAUNCH(mq_kern, dim3(static_cast<unsigned>(sub), gmax), dim3(256), mq_lds, st, idx->d_vectors, idx->dim,
+                              c.q + q0 * idx->dim, c.part_off, pair_of, groups, ngroups, np, sub, kk,
+                              partial + q0 * lists * kk, floor ? floor + q0 : nullptr, m0, c.mask_stride);
+                }
+            } else if (c.scan == VG_SCAN_F32) {
+                for (int64_t q0 = 0; q0 < nq; q0 += 65535) {
+                    const int64_t cnt = std::min<int64_t>(65535, nq - q0);
+                    const dim3 grid(static_cast<unsigned>(sub), static_cast<unsigned>(np), static_cast<unsigned>(cnt));
+                    vg::ProfScope prof(idx->ctx, "flat_probe", st);
+                    auto kern = mk ? (dot ? vg::probe_scan_f32_kernel<true, true> : vg::probe_scan_f32_kernel<false, true>)
+                                   : (dot ? vg::probe_scan_f32_kernel<true, false> : vg::probe_scan_f32_kernel<false, false>);
+                    VG_LAUNCH(kern, grid, dim3(256), 0, st, idx->d_vectors, idx->dim, c.q + q0 * idx->dim, c.probes + q0 * np,
+                              c.part_off, np, sub, kk, partial + q0 * lists * kk, floor ? floor + q0 : nullptr,
+                              mk ? mk + q0 * c.mask_stride : nullptr, c.mask_stride, nullptr);
+                }
+            } else if (c.scan == VG_SCAN_PQ) {
+                // the heap direction follows the segment metric for EVERY scan (flat/segment.go:449): with Dot / Cosine a PQ
+                // scan therefore keeps the k LARGEST table-lookup (squared-L2) distances — the reference as written
+                VG_TRY(vg::launch_probe_scan_adc(idx, tables, c.probes, c.part_off, nq, np, c.split, kk, partial, floor, dot, mk,
+                                                 c.mask_stride, st));
+            } else {
+                VG_TRY(vg::launch_probe_scan_sq8(idx, c.q, c.probes, c.part_off, nq, np, sub, kk, partial, floor, mk, c.mask_stride, st));
+            }
+            return VG_OK;
+        });
+    }
+};
+
+// The dispatch: a shortcut, the batch in chunks, or one arena for the probe lists and the two paths' pieces — then the grouped
+// nomination where it applies, else the scan kernels.  Whichever path answers returns from here; the caller copies the results back.
+static int32_t probed_search_device(vg_index *idx, const float *q, int64_t nq, int32_t k, int32_t nprobes, int np, int parts, int32_t scan,
+                                    const uint8_t *mk, int64_t mask_stride, uint32_t *oid, float *osc, hipStream_t st,
+                                    bool allow_nomination, uint32_t *probes_out)
+{
+    const bool whole = idx->num_partitions <= 1;
+    ProbedCall c{idx, q, nq, k, nprobes, np, parts, scan, mk, mask_stride, oid, osc, st, allow_nomination, whole, idx->metric != VG_METRIC_L2, nq * np};
+    bool done = false;
+    VG_TRY(probed_whole_shortcut(c, &done));
+    if (done) return VG_OK;
+    // More (query, probe) pairs than one grouped nomination takes (65535): the batch in chunks of queries that do fit, each
+    // chunk deciding for itself below — 8192 queries x 8 probes would otherwise run on the scan kernels, 3x the time per query.
+    const int64_t qc = 65535 / np;
+    if (!whole && nq * np > 65535 && scan != VG_SCAN_PQ && k <= vg::kProbeGemmMaxK && qc * np >= 12 * static_cast<int64_t>(parts) &&
+        !vg::hook(vg::kHookProbeNoGroup) && !vg::hook(vg::kHookProbeNoGemm)) {
+        for (int64_t q0 = 0; q0 < nq; q0 += qc) {
+            const int64_t cnt = std::min<int64_t>(qc, nq - q0);
+            VG_TRY(flat_probed_impl(idx, q + q0 * idx->dim, cnt, k, nprobes, scan, mk ? mk + q0 * mask_stride : nullptr,
+                                    mask_stride, oid + q0 * k, osc + q0 * k, st, allow_nomination,
+                                    probes_out ? probes_out + q0 * np : nullptr));
+        }
+        return VG_OK;
+    }
+    vg::ArenaCall ar(idx->ctx, st);
+    const int i_probes = ar.add(sizeof(uint32_t) * static_cast<size_t>(nq) * np);
+    const int i_whole = ar.add(whole ? sizeof(uint32_t) * (static_cast<size_t>(parts) + 1) : 0);
+    ProbedScanPath scan_path;
+    scan_path.plan(c, ar);
+    vg::PagedTopK pages;
+    pages.add(ar, nq, k, c.lists, ProbedGemmPath::partial_keys(c));
+    ProbedGemmPath gemm_path;
+    gemm_path.plan(c, ar);
+    VG_TRY(ar.commit());
+    c.probes = probes_out && !whole ? probes_out : ar.get<uint32_t>(i_probes);
+    c.part_off = whole ? ar.get<uint32_t>(i_whole) : idx->d_part_off;
+    if (whole) {
+        // filtered and unpartitioned: every query "probes" every piece of the one range
+        const int64_t threads = std::max<int64_t>(c.pairs, parts + 1);
+        VG_LAUNCH(vg::probe_whole_segment_kernel, dim3(static_cast<unsigned>((threads + 255) / 256)), dim3(256), 0, st, idx->n, parts,
+                  c.pairs, ar.get<uint32_t>(i_whole), c.probes);
+    } else {
+        // the reference's selection loop (kmeans.go:255: n <= k/4 && n < 16) is replayed where centroid distances tie; its LDS
+        // (8 bytes per partition, beside the kernel's 2.6 KB of static LDS) bounds that to 19 968 partitions — beyond, ties are
+        // broken by centroid id
+        VG_TRY(launch_probe_select(idx, q, nq, np, c.dot, c.probes, st));
+    }
+    if (gemm_path.applies()) return gemm_path.run(c, ar, ar.get<uint64_t>(pages.i_partial));
+    return scan_path.run(c, ar, pages);
 }
 
 static int32_t flat_probed_impl(vg_index *idx, const float *queries, int64_t nq, int32_t k, int32_t nprobes, int32_t scan,
@@ -706,7 +1022,6 @@ static int32_t flat_probed_impl(vg_index *idx, const float *queries, int64_t nq,
     const int parts = whole ? static_cast<int>(std::min<int64_t>(64, std::max<int64_t>(1, idx->n / 4096))) : idx->num_partitions;
     if (whole) np = parts;
     VG_CHECK(np <= 64, VG_ERR_UNSUPPORTED, "vg_search_flat_probed: nprobes=%d exceeds 64", np);
-    const bool dot = idx->metric != VG_METRIC_L2;
     if (scan == VG_SCAN_F32) {
         VG_CHECK(idx->d_vectors, VG_ERR_NOT_READY, "vg_search_flat_probed: index has no fp32 vectors");
     } else if (scan == VG_SCAN_PQ) {
@@ -716,319 +1031,10 @@ static int32_t flat_probed_impl(vg_index *idx, const float *queries, int64_t nq,
     } else {
         VG_CHECK(idx->sq && idx->d_sq_tiles, VG_ERR_NOT_READY, "vg_search_flat_probed: index has no SQ8 codes");
     }
-    VG_HIP(hipSetDevice(idx->ctx->device));
-    hipStream_t st = vg::pick_stream(idx->ctx, stream);
-    vg::DevIn<float> q;
-    vg::DevOut<uint32_t> oid;
-    vg::DevOut<float> osc;
-    VG_TRY(q.init(queries, static_cast<size_t>(nq) * idx->dim, st));
-    VG_TRY(oid.init(ids, static_cast<size_t>(nq) * k, st));
-    VG_TRY(osc.init(scores, static_cast<size_t>(nq) * k, st));
-    vg::DevIn<uint8_t> mk;
-    const int64_t mask_bytes = (idx->n + 7) / 8;
-    VG_TRY(mk.init(mask, mask ? static_cast<size_t>(mask_stride ? (nq - 1) * mask_stride + mask_bytes : mask_bytes) : 0, st));
-    // the queries whose proof failed, searched again without the nomination (rescan_failed, vg_nominate.hpp)
-    auto rescan = [&](const float *fq, int64_t nf, const uint8_t *fmask, int64_t fmask_stride, uint32_t *fid, float *fsc) {
-        return flat_probed_impl(idx, fq, nf, k, nprobes, scan, fmask, fmask_stride, fid, fsc, st, false);
-    };
-
-    // A batch of filtered fp32 queries over the whole segment: the matrix-core nomination of vg_search_flat with the filter
-    // applied where candidates are sampled and appended (k_flat.hip) — its cost does not depend on the selectivity, the
-    // kernels below pay per wanted row: 8 queries up it wins or ties (tools/filtered_time.py).  Same results either way
-    // (the test hook keeps the batch on the kernels below).
-    if (whole && scan == VG_SCAN_F32 && mk.ptr && nq >= 8 && !vg::hook(vg::kHookProbeNoGroup)) {
-        VG_TRY(vg::flat_search_masked(idx, q.ptr, nq, k, mk.ptr, mask_stride, oid.ptr, osc.ptr, stream));
-        VG_TRY(oid.finish());
-        VG_TRY(osc.finish());
-        if (oid.on_host() || osc.on_host()) VG_HIP(hipStreamSynchronize(st));
-        return VG_OK;
-    }
-
-    // A filtered SQ8 batch over the whole segment with vg_index_enable_sq8_nomination: the bf16 nomination with the filter in its
-    // epilogue, the exact re-score from the codes, the proof (k_sq8.hip); queries whose proof fails take the kernels below
-    if (whole && scan == VG_SCAN_SQ8 && mk.ptr && allow_nomination && vg::sq8_nomination_applies(idx, q.ptr, nq, k) &&
-        !vg::hook(vg::kHookProbeNoGroup)) {
-        std::vector<int> failed;
-        VG_TRY(vg::sq8_nominated_pass(idx, q.ptr, nq, k, mk.ptr, mask_stride, oid.ptr, osc.ptr, st, failed));
-        VG_TRY(vg::rescan_failed(failed, q.ptr, idx->dim, k, mk.ptr, mask_stride, mask_bytes, oid.ptr, osc.ptr, st, rescan));
-        VG_TRY(oid.finish());
-        VG_TRY(osc.finish());
-        if (oid.on_host() || osc.on_host()) VG_HIP(hipStreamSynchronize(st));
-        return VG_OK;
-    }
-
-    // A filtered PQ scan of the whole segment, k <= 64 and a table that fits LDS: the pipelined scan of vg_search_pq_adc with
-    // the filter where keys are made (the probe kernel below is the plain loop, twice its time)
-    if (whole && scan == VG_SCAN_PQ && mk.ptr && k <= 64 && idx->pq->m <= 96 && !vg::hook(vg::kHookProbeNoGroup)) {
-        VG_TRY(vg::pq_adc_search_masked(idx, q.ptr, nq, k, mk.ptr, mask_stride, dot, oid.ptr, osc.ptr, stream));
-        VG_TRY(oid.finish());
-        VG_TRY(osc.finish());
-        if (oid.on_host() || osc.on_host()) VG_HIP(hipStreamSynchronize(st));
-        return VG_OK;
-    }
-
-    // More (query, probe) pairs than one grouped nomination takes (65535): the batch in chunks of queries that do fit, each
-    // chunk deciding for itself below — 8192 queries x 8 probes would otherwise run on the scan kernels, 3x the time per query.
-    {
-        const int64_t qc = 65535 / np;
-        if (!whole && nq * np > 65535 && scan != VG_SCAN_PQ && k <= vg::kProbeGemmMaxK && qc * np >= 12 * static_cast<int64_t>(parts) &&
-            !vg::hook(vg::kHookProbeNoGroup) && !vg::hook(vg::kHookProbeNoGemm)) {
-            for (int64_t q0 = 0; q0 < nq; q0 += qc) {
-                const int64_t cnt = std::min<int64_t>(qc, nq - q0);
-                VG_TRY(flat_probed_impl(idx, q.ptr + q0 * idx->dim, cnt, k, nprobes, scan, mk.ptr ? mk.ptr + q0 * mask_stride : nullptr,
-                                        mask_stride, oid.ptr + q0 * k, osc.ptr + q0 * k, st, allow_nomination,
-                                        probes_out ? probes_out + q0 * np : nullptr));
-            }
-            VG_TRY(oid.finish());
-            VG_TRY(osc.finish());
-            if (oid.on_host() || osc.on_host()) VG_HIP(hipStreamSynchronize(st));
-            return VG_OK;
-        }
-    }
-    // enough workgroups to fill the device when there are few (query, probe) pairs
-    const int64_t pairs = nq * np;
-    // fp32: with enough pairs the queries are grouped by partition (rows read once per group); the
-    // row-in-registers scan needs 16-byte aligned rows of at most 1024 floats
-    // (a filtered whole segment is "probed" in every piece by every query: grouping pays from a handful of queries on)
-    const bool group_ok = (whole ? nq >= 4 : pairs >= 16) && !vg::hook(vg::kHookProbeNoGroup);  // test hook: one pass per pair
-    const bool grouped_f32 = scan == VG_SCAN_F32 && group_ok && idx->dim % 4 == 0 && idx->dim <= 1024 &&
-                             (reinterpret_cast<uintptr_t>(idx->d_vectors) & 15) == 0;
-    // SQ8: the group's queries (padded to whole 16-dimension groups) have to fit LDS next to the merge scratch
-    const bool grouped_sq8 = scan == VG_SCAN_SQ8 && group_ok &&
-                             sizeof(float) * vg::kProbeQB * static_cast<size_t>(idx->sq_groups) * 16 <= 128 * 1024;
-    const bool grouped = grouped_f32 || grouped_sq8;
-    const int want = 4 * idx->ctx->compute_units;
-    int sub = static_cast<int>(std::min<int64_t>(32, std::max<int64_t>(1, (want + pairs - 1) / pairs)));
-    int split = static_cast<int>(std::min<int64_t>(np, std::max<int64_t>(1, (idx->ctx->compute_units + nq - 1) / nq)));
-    if (grouped) {  // workgroups are (group of up to kProbeQB pairs) x slice: size the slices for the groups
-        const int64_t g_est = std::max<int64_t>(1, pairs / vg::kProbeQB) + std::min<int64_t>(parts, pairs) / 2;
-        sub = static_cast<int>(std::min<int64_t>(32, std::max<int64_t>(1, (want + g_est - 1) / g_est)));
-    }
-    const int lists = scan == VG_SCAN_PQ ? split : np * sub;
-    const int lut_words = scan == VG_SCAN_PQ ? (((idx->pq->m >> 4) + 1) >> 1) * 8192 + (idx->pq->m & 15) * 256 : 0;
-
-    const int64_t qchunk = std::max<int64_t>(1, 65535 / np);
-    const int64_t chunk_pairs = std::min<int64_t>(nq, qchunk) * np;
-    const size_t gwords = grouped ? static_cast<size_t>(parts) + 1 : 0;
-
-    vg::ArenaCall ar(idx->ctx, st);
-    const int i_gcounts = ar.add(sizeof(uint32_t) * gwords);
-    const int i_gcursor = ar.add(sizeof(uint32_t) * gwords);
-    const int i_gstart = ar.add(sizeof(uint32_t) * gwords);
-    const int i_pair_of = ar.add(grouped ? sizeof(uint32_t) * static_cast<size_t>(chunk_pairs) : 0);
-    const int i_groups = ar.add(grouped ? sizeof(vg::ProbeGroup) * static_cast<size_t>(chunk_pairs) : 0);
-    const int i_ngroups = ar.add(grouped ? 256 : 0);
-    const bool paged = k > 64;
-    const int pk = paged ? 64 : k;
-    const int i_probes = ar.add(sizeof(uint32_t) * static_cast<size_t>(nq) * np);
-    // (the grouped nomination leaves k keys per pair there, also when k is paged for the scan kernels)
-    const size_t partial_keys = std::max(static_cast<size_t>(nq) * lists * pk, whole || k > vg::kProbeGemmMaxK || scan == VG_SCAN_PQ || pairs > 65535 ? size_t(0) : static_cast<size_t>(pairs) * k);
-    const int i_partial = ar.add(sizeof(uint64_t) * partial_keys);
-    const int i_pid = ar.add(paged ? sizeof(uint32_t) * static_cast<size_t>(nq) * pk : 0);
-    const int i_psc = ar.add(paged ? sizeof(float) * static_cast<size_t>(nq) * pk : 0);
-    const int i_floor = ar.add(paged ? sizeof(uint64_t) * static_cast<size_t>(nq) : 0);
-    const int i_one = ar.add(paged ? 256 : 0);
-    const int i_tables = ar.add(sizeof(float) * static_cast<size_t>(nq) * lut_words);
-    const int i_whole = ar.add(whole ? sizeof(uint32_t) * (static_cast<size_t>(parts) + 1) : 0);
-    // fp32, unfiltered, partitions probed by 12 or more queries each on average: nomination + proof on the matrix cores (2c)
-    // (1M x 768 in 122 partitions, 1024 queries, ms per call, exact kernels -> this: nprobes 1 (8 per partition) 1.21 -> 1.18,
-    // 2: 2.1 -> 1.4, 4: 3.75 -> 1.3, 8: 7.25 -> 2.3, 16: 11.6 -> 4.5, 32: 21.0 -> 7.0; tools/probe_gemm_time.py)
-    // (a filtered batch too: a pair's filter is its query's — probe_gather_queries_kernel notes where each starts)
-    // (k <= 48: the pairs' 64 best nominees re-scored; up to kProbeGemmMaxK: everything below a deeper threshold re-scored, and the
-    // flagged queries — normally none — searched again as a subset, the scan kernels' k > 64 being paged)
-    const bool gemm_shape = !whole && k <= vg::kProbeGemmMaxK && (k <= 64 || allow_nomination) && idx->dim % 4 == 0 && pairs <= 65535 &&
-                            pairs >= 12 * static_cast<int64_t>(parts) &&
-                            (reinterpret_cast<uintptr_t>(q.ptr) & 15) == 0 && static_cast<int>(idx->h_part_off.size()) == parts + 1 &&
-                            !vg::hook(vg::kHookProbeNoGroup) && !vg::hook(vg::kHookProbeNoGemm);
-    const bool gemm_f32 = scan == VG_SCAN_F32 && gemm_shape && (reinterpret_cast<uintptr_t>(idx->d_vectors) & 15) == 0;
-    // SQ8 with vg_index_enable_sq8_nomination: the same grouped nomination on the bfloat16 image of the dequantised rows, the
-    // pairs' 64 candidates re-scored from the codes and proven by the verify pair (launch_sq8_verify, k_sq8.hip)
-    const bool gemm_sq8 = scan == VG_SCAN_SQ8 && gemm_shape && allow_nomination && idx->sq_nom.rows != nullptr;
-    const bool gemm = gemm_f32 || gemm_sq8;
-    int64_t grids[4] = {0, 0, 0, 0}, ns_max = 0;  // sample / main of the 128-query tiles, sample / main of the 64-query tiles
-    if (gemm) {  // launch bounds from the partition sizes: one query tile per partition + the batch's further tiles on the largest
-        int64_t sum_s = 0, sum_m = 0, max_s = 0, max_m = 0, max_nst = 0, max_nt = 0;
-        for (int p = 0; p < parts; p++) {
-            const int64_t rows = static_cast<int64_t>(idx->h_part_off[p + 1]) - idx->h_part_off[p];
-            const int64_t nt = (rows + vg::kGemmBN - 1) / vg::kGemmBN, nst = (nt + vg::kProbeSampleStride - 1) / vg::kProbeSampleStride;
-            const int64_t bs = ((nst + 7) / 8) * 8, bm = ((nt + 7) / 8) * 8;
-            sum_s += bs;
-            sum_m += bm;
-            max_s = std::max(max_s, bs);
-            max_m = std::max(max_m, bm);
-            grids[2] += nst;
-            grids[3] += nt;
-            max_nst = std::max(max_nst, nst);
-            max_nt = std::max(max_nt, nt);
-            ns_max = std::max(ns_max, nst * vg::kGemmBN);
-        }
-        grids[0] = sum_s + (pairs / vg::kGemmBM) * max_s;
-        grids[1] = sum_m + (pairs / vg::kGemmBM) * max_m;
-        grids[2] += (pairs / (vg::kProbeRB * vg::kG32BM)) * max_nst;  // (64-query tiles: a partition's first + the batch's further ones on the largest)
-        grids[3] += (pairs / (vg::kProbeRB * vg::kG32BM)) * max_nt;
-    }
-    const size_t gw = gemm ? static_cast<size_t>(parts) + 1 : 0;
-    const int i_bcnt = ar.add(sizeof(uint32_t) * gw);
-    const int i_bcur = ar.add(sizeof(uint32_t) * gw);
-    const int i_bgrp = ar.add(sizeof(vg::GemmGroup) * gw);
-    const int i_fbs = ar.add(sizeof(int64_t) * gw);
-    const int i_fbm = ar.add(sizeof(int64_t) * gw);
-    const int i_fbss = ar.add(sizeof(int64_t) * gw);
-    const int i_fbsm = ar.add(sizeof(int64_t) * gw);
-    const int i_bpair = ar.add(gemm ? sizeof(uint32_t) * static_cast<size_t>(pairs) : 0);
-    const int i_pairq = ar.add(gemm ? sizeof(float) * static_cast<size_t>(pairs) * idx->dim : 0);
-    const int i_pids = ar.add(gemm ? sizeof(uint32_t) * static_cast<size_t>(pairs) * k : 0);
-    const int i_pscore = ar.add(gemm ? sizeof(float) * static_cast<size_t>(pairs) * k : 0);
-    const int i_pfail = ar.add(gemm ? sizeof(int) * static_cast<size_t>(pairs) : 0);
-    const int i_qfail = ar.add(gemm ? sizeof(int) * static_cast<size_t>(nq) : 0);
-    const int i_moff = ar.add(gemm ? sizeof(int64_t) * static_cast<size_t>(pairs) : 0);
-    // (fp32 rows with vg_index_enable_bf16_filter: the grouped nomination on that image too)
-    const bool gemm_f32_bf16 = gemm_f32 && idx->d_vectors_bf16 != nullptr;
-    // the image the grouped nomination runs on: none (the fp32 rows), the SQ8 image, or a view of the fp32 rows' bf16 filter
-    const vg::NomImage gimg = gemm_sq8        ? idx->sq_nom
-                              : gemm_f32_bf16 ? vg::NomImage{idx->d_vectors_bf16, idx->vectors_bf16_dim, idx->d_norms, idx->d_norm_max}
-                                              : vg::NomImage{};
-    const int i_gscr = ar.add(gemm ? vg::flat_probe_gemm_scratch_bytes(pairs, ns_max, k, gimg.dim_pad) : 0);
-    VG_TRY(ar.commit());
-    uint32_t *probes = probes_out && !whole ? probes_out : ar.get<uint32_t>(i_probes);
-    uint64_t *partial = ar.get<uint64_t>(i_partial);
-    float *tables = ar.get<float>(i_tables);
-    uint32_t *pid = ar.get<uint32_t>(i_pid);
-    float *psc = ar.get<float>(i_psc);
-    uint64_t *floor_keys = ar.get<uint64_t>(i_floor);
-    int *one = ar.get<int>(i_one);
-    uint32_t *gcounts = ar.get<uint32_t>(i_gcounts), *gcursor = ar.get<uint32_t>(i_gcursor);
-    uint32_t *gstart = ar.get<uint32_t>(i_gstart), *pair_of = ar.get<uint32_t>(i_pair_of);
-    uint32_t *ngroups = ar.get<uint32_t>(i_ngroups);
-    vg::ProbeGroup *groups = ar.get<vg::ProbeGroup>(i_groups);
-
-    const uint32_t *part_off = whole ? ar.get<uint32_t>(i_whole) : idx->d_part_off;
-    if (whole) {
-        const int64_t threads = std::max<int64_t>(pairs, parts + 1);
-        VG_LAUNCH(vg::probe_whole_segment_kernel, dim3(static_cast<unsigned>((threads + 255) / 256)), dim3(256), 0, st, idx->n, parts,
-                  pairs, ar.get<uint32_t>(i_whole), probes);
-    } else {
-        // the reference's selection loop (kmeans.go:255: n <= k/4 && n < 16) is replayed where centroid distances tie; its LDS
-        // (8 bytes per partition, beside the kernel's 2.6 KB of static LDS) bounds that to 19 968 partitions — beyond, ties are
-        // broken by centroid id
-        VG_TRY(launch_probe_select(idx, q.ptr, nq, np, dot, probes, st));
-    }
-    // the heap direction follows the segment metric for EVERY scan (flat/segment.go:449): with Dot / Cosine a PQ
-    // scan therefore keeps the k LARGEST table-lookup (squared-L2) distances — the reference as written
-    const bool desc = dot;
-    if (gemm) {
-        uint32_t *bcnt = ar.get<uint32_t>(i_bcnt), *bcur = ar.get<uint32_t>(i_bcur), *bpair = ar.get<uint32_t>(i_bpair);
-        vg::GemmGroup *bgrp = ar.get<vg::GemmGroup>(i_bgrp);
-        int64_t *fbs = ar.get<int64_t>(i_fbs), *fbm = ar.get<int64_t>(i_fbm), *fbss = ar.get<int64_t>(i_fbss), *fbsm = ar.get<int64_t>(i_fbsm);
-        float *pairq = ar.get<float>(i_pairq), *pair_sc = ar.get<float>(i_pscore);
-        uint32_t *pair_ids = ar.get<uint32_t>(i_pids);
-        int *pfail = ar.get<int>(i_pfail), *qfail = ar.get<int>(i_qfail);
-        const unsigned pb = static_cast<unsigned>((pairs + 255) / 256);
-        VG_HIP(hipMemsetAsync(bcnt, 0, sizeof(uint32_t) * (static_cast<size_t>(parts) + 1), st));
-        VG_HIP(hipMemsetAsync(qfail, 0, sizeof(int) * static_cast<size_t>(nq), st));
-        VG_LAUNCH(vg::probe_bucket_count_kernel, dim3(pb), dim3(256), 0, st, probes, pairs, bcnt);
-        VG_LAUNCH(vg::probe_bucket_scan_kernel, dim3(1), dim3(1024), 0, st, bcnt, part_off, parts, bcur, bgrp, fbs, fbm, fbss, fbsm);
-        VG_LAUNCH(vg::probe_bucket_fill_kernel, dim3(pb), dim3(256), 0, st, probes, pairs, bcur, bpair);
-        int64_t *moff = ar.get<int64_t>(i_moff);
-        VG_LAUNCH(vg::probe_gather_queries_kernel, dim3(static_cast<unsigned>(pairs)), dim3(256), 0, st, q.ptr, bpair, np, idx->dim, pairq,
-                  mask_stride, moff);
-        {
-            vg::ProfScope prof(idx->ctx, "flat_probe", st);
-            const int64_t *const fb[4] = {fbs, fbm, fbss, fbsm};
-            vg::ProbeNominated nom{};
-            VG_TRY(vg::flat_probe_gemm(idx, pairq, pairs, bgrp, fb, parts, grids, vg::kProbeSampleStride, ns_max, k, pair_ids, pair_sc,
-                                       pfail, ar.get<char>(i_gscr), mk.ptr, moff, st, gimg, &nom));
-            if (gemm_sq8) VG_TRY(vg::launch_sq8_verify(idx, pairq, pairs, nom, k, pair_ids, pair_sc, pfail, st));
-        }
-        // lists = np * sub in this configuration; the pairs' k results fill the first np lists' worth of `partial`
-        VG_LAUNCH(vg::probe_pack_kernel, dim3(static_cast<unsigned>(pairs)), dim3(64), 0, st, bpair, pair_ids, pair_sc, pfail, k, np, desc,
-                  partial, qfail);
-        VG_TRY(vg::launch_topk_merge(partial, nq, np, k, desc, oid.ptr, osc.ptr, st));
-        if (gemm_sq8 || k > 64) {  // the flagged queries (normally none) go through the scan kernels: read the flags, search that subset
-            std::vector<int> failed;
-            VG_TRY(vg::failed_list(qfail, nq, 0, st, failed));
-            ar.lock.unlock();  // the subset's own search takes the arena
-            VG_TRY(vg::rescan_failed(failed, q.ptr, idx->dim, k, mk.ptr, mask_stride, mask_bytes, oid.ptr, osc.ptr, st, rescan));
-            VG_TRY(oid.finish());
-            VG_TRY(osc.finish());
-            if (oid.on_host() || osc.on_host()) VG_HIP(hipStreamSynchronize(st));
-            return VG_OK;
-        }
-        // the queries with a failed proof (ties at the k-th score, more than 4096 rows below a threshold): the exact kernel, one
-        // workgroup per (slice, probe, query) that leaves at once unless its query is flagged
-        for (int64_t q0 = 0; q0 < nq; q0 += 65535) {
-            const int64_t cnt = std::min<int64_t>(65535, nq - q0);
-            const dim3 grid(static_cast<unsigned>(sub), static_cast<unsigned>(np), static_cast<unsigned>(cnt));
-            auto kern = mk.ptr ? (dot ? vg::probe_scan_f32_kernel<true, true> : vg::probe_scan_f32_kernel<false, true>)
-                               : (dot ? vg::probe_scan_f32_kernel<true, false> : vg::probe_scan_f32_kernel<false, false>);
-            VG_LAUNCH(kern, grid, dim3(256), 0, st, idx->d_vectors, idx->dim, q.ptr + q0 * idx->dim, probes + q0 * np, part_off, np, sub, k,
-                      partial + q0 * lists * k, nullptr, mk.ptr ? mk.ptr + q0 * mask_stride : nullptr, mask_stride, qfail + q0);
-        }
-        VG_TRY(vg::launch_topk_merge(partial, nq, lists, k, desc, oid.ptr, osc.ptr, st, qfail));
-        VG_TRY(oid.finish());
-        VG_TRY(osc.finish());
-        if (oid.on_host() || osc.on_host()) VG_HIP(hipStreamSynchronize(st));
-        return VG_OK;
-    }
-    const size_t mq_lds = sizeof(float) * vg::kProbeQB * static_cast<size_t>(idx->dim) + 4 * 64 * sizeof(uint64_t) + 64;
-    auto mq_kern = mk.ptr ? (dot ? vg::probe_scan_f32_mq_kernel<true, true> : vg::probe_scan_f32_mq_kernel<false, true>)
-                          : (dot ? vg::probe_scan_f32_mq_kernel<true, false> : vg::probe_scan_f32_mq_kernel<false, false>);
-    if (grouped_f32)
-        VG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(mq_kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   static_cast<int>(mq_lds)));
-    if (scan == VG_SCAN_PQ) VG_TRY(vg::launch_pq_build_table(idx->pq, q.ptr, nq, tables, true, st));
-    if (paged) VG_HIP(hipMemsetAsync(one, 1, sizeof(int), st));
-    // a wave keeps 64 keys: k > 64 comes in pages of 64 results, each page a scan of the probed ranges for the
-    // keys after the previous page's last one
-    for (int off = 0; off < k; off += 64) {
-        const int kk = paged ? std::min(64, k - off) : k;
-        const uint64_t *floor = off ? floor_keys : nullptr;
-        if (grouped) {
-            for (int64_t q0 = 0; q0 < nq; q0 += qchunk) {
-                const int64_t cnt = std::min<int64_t>(qchunk, nq - q0);
-                const int64_t cpairs = cnt * np;
-                const unsigned gmax = static_cast<unsigned>(std::min<int64_t>(cpairs, cpairs / vg::kProbeQB + parts));
-                const uint8_t *m0 = mk.ptr ? mk.ptr + q0 * mask_stride : nullptr;
-                VG_HIP(hipMemsetAsync(gcounts, 0, sizeof(uint32_t) * (static_cast<size_t>(parts) + 1), st));
-                VG_LAUNCH(vg::probe_group_kernel, dim3(1), dim3(1024), 0, st, probes + q0 * np, cpairs, parts, gcounts, gcursor,
-                          gstart, pair_of, groups, ngroups);
-                if (grouped_sq8) {
-                    VG_TRY(vg::launch_probe_scan_sq8_grouped(idx, q.ptr + q0 * idx->dim, part_off, pair_of, groups, ngroups, gmax, np,
-                                                             sub, kk, partial + q0 * lists * kk, floor ? floor + q0 : nullptr, m0,
-                                                             mask_stride, st));
-                    continue;
-                }
-                vg::ProfScope prof(idx->ctx, "flat_probe", st);
-                VG_LAUNCH(mq_kern, dim3(static_cast<unsigned>(sub), gmax), dim3(256), mq_lds, st, idx->d_vectors, idx->dim,
-                          q.ptr + q0 * idx->dim, part_off, pair_of, groups, ngroups, np, sub, kk,
-                          partial + q0 * lists * kk, floor ? floor + q0 : nullptr, m0, mask_stride);
-            }
-        } else if (scan == VG_SCAN_F32) {
-            for (int64_t q0 = 0; q0 < nq; q0 += 65535) {
-                const int64_t cnt = std::min<int64_t>(65535, nq - q0);
-                const dim3 grid(static_cast<unsigned>(sub), static_cast<unsigned>(np), static_cast<unsigned>(cnt));
-                vg::ProfScope prof(idx->ctx, "flat_probe", st);
-                auto kern = mk.ptr ? (dot ? vg::probe_scan_f32_kernel<true, true> : vg::probe_scan_f32_kernel<false, true>)
-                                   : (dot ? vg::probe_scan_f32_kernel<true, false> : vg::probe_scan_f32_kernel<false, false>);
-                VG_LAUNCH(kern, grid, dim3(256), 0, st, idx->d_vectors, idx->dim, q.ptr + q0 * idx->dim, probes + q0 * np,
-                          part_off, np, sub, kk, partial + q0 * lists * kk, floor ? floor + q0 : nullptr,
-                          mk.ptr ? mk.ptr + q0 * mask_stride : nullptr, mask_stride, nullptr);
-            }
-        } else if (scan == VG_SCAN_PQ) {
-            VG_TRY(vg::launch_probe_scan_adc(idx, tables, probes, part_off, nq, np, split, kk, partial, floor, desc, mk.ptr,
-                                             mask_stride, st));
-        } else {
-            VG_TRY(vg::launch_probe_scan_sq8(idx, q.ptr, probes, part_off, nq, np, sub, kk, partial, floor, mk.ptr, mask_stride, st));
-        }
-        if (!paged) {
-            VG_TRY(vg::launch_topk_merge(partial, nq, lists, k, desc, oid.ptr, osc.ptr, st));
-        } else {
-            VG_TRY(vg::launch_topk_merge(partial, nq, lists, kk, desc, pid, psc, st));
-            VG_TRY(vg::launch_page_patch(nq, k, off, kk, desc, one, pid, psc, oid.ptr, osc.ptr, floor_keys, st));
-        }
-    }
-    VG_TRY(oid.finish());
-    VG_TRY(osc.finish());
-    if (oid.on_host() || osc.on_host()) VG_HIP(hipStreamSynchronize(st));
-    return VG_OK;
+    vg::SearchIO io;
+    VG_TRY(io.init(idx->ctx, stream, queries, static_cast<size_t>(nq) * idx->dim, ids, scores, static_cast<size_t>(nq) * k, mask,
+                   vg::mask_span(mask, mask_stride, nq, idx->n)));
+    VG_TRY(probed_search_device(idx, io.q.ptr, nq, k, nprobes, np, parts, scan, io.mk.ptr, mask_stride, io.oid.ptr, io.osc.ptr, io.st,
+                                allow_nomination, probes_out));
+    return io.finish();
 }

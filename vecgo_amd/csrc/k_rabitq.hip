@@ -5,15 +5,9 @@
 #include "vg_exact.hpp"
 #include "vg_internal.hpp"
 #include "vg_cand_replay.hpp"
+#include "vg_search.hpp"
 
 namespace vg {
-
-int32_t launch_page_patch(int64_t nq, int k, int off, int kk, bool descending, const int *always_one,
-                          const uint32_t *fids, const float *fscores, uint32_t *ids, float *scores, uint64_t *min_keys,
-                          hipStream_t st);
-int32_t launch_topk_merge(const uint64_t *partial, int64_t nq, int lists, int k, bool descending,
-                          uint32_t *ids, float *scores, hipStream_t st, const int *only_if = nullptr,
-                          const int *always = nullptr);
 
 __host__ __device__ inline int rq_words(int dim) { return (dim + 63) / 64; }
 
@@ -470,7 +464,6 @@ VG_API int32_t vg_rabitq_encode(vg_ctx *ctx, int32_t dim, const float *vectors, 
     VG_LAUNCH(vg::rabitq_encode_kernel, dim3(static_cast<unsigned>((n + 15) / 16)), dim3(256), 0, st,
                        v.ptr, n, dim, c.ptr);
     VG_TRY(c.finish());
-    if (c.on_host()) VG_HIP(hipStreamSynchronize(st));
     return VG_OK;
 }
 
@@ -496,7 +489,6 @@ VG_API int32_t vg_rabitq_distance_batch(vg_ctx *ctx, int32_t dim, const float *q
     VG_LAUNCH(vg::rabitq_distance_kernel, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, st,
                        qcode.ptr, c.ptr, n, dim, o.ptr);
     VG_TRY(o.finish());
-    if (o.on_host()) VG_HIP(hipStreamSynchronize(st));
     return VG_OK;
 }
 
@@ -517,7 +509,6 @@ VG_API int32_t vg_hamming_batch(vg_ctx *ctx, const uint8_t *a, const uint8_t *co
     VG_LAUNCH(vg::hamming_batch_kernel, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, st,
                        da.ptr, dc.ptr, nbytes, n, o.ptr);
     VG_TRY(o.finish());
-    if (o.on_host()) VG_HIP(hipStreamSynchronize(st));
     return VG_OK;
 }
 
@@ -570,19 +561,12 @@ VG_API int32_t vg_search_rabitq(vg_index *idx, const float *queries, int64_t nq,
     VG_CHECK(idx->n == 0 || idx->d_rq_tiles, VG_ERR_NOT_READY, "vg_search_rabitq: index has no RaBitQ codes");
     VG_CHECK(queries && ids && scores, VG_ERR_INVALID_ARG, "vg_search_rabitq: NULL buffer");
     VG_CHECK(k <= 512, VG_ERR_UNSUPPORTED, "vg_search_rabitq: k=%d exceeds 512", k);
-    VG_HIP(hipSetDevice(idx->ctx->device));
-    hipStream_t st = vg::pick_stream(idx->ctx, stream);
-    vg::DevIn<float> q;
-    vg::DevOut<uint32_t> oid;
-    vg::DevOut<float> osc;
-    VG_TRY(q.init(queries, static_cast<size_t>(nq) * idx->dim, st));
-    VG_TRY(oid.init(ids, static_cast<size_t>(nq) * k, st));
-    VG_TRY(osc.init(scores, static_cast<size_t>(nq) * k, st));
+    vg::SearchIO io;
+    VG_TRY(io.init(idx->ctx, stream, queries, static_cast<size_t>(nq) * idx->dim, ids, scores, static_cast<size_t>(nq) * k));
+    const hipStream_t st = io.st;
+    const float *q = io.q.ptr;
     if (idx->n == 0) {
-        vg::DevTmp<uint64_t> none;
-        VG_TRY(none.init(static_cast<size_t>(nq) * k, st));
-        VG_HIP(hipMemsetAsync(none.ptr, 0xFF, static_cast<size_t>(nq) * k * 8, st));
-        VG_TRY(vg::launch_topk_merge(none.ptr, nq, 1, k, false, oid.ptr, osc.ptr, st));
+        VG_TRY(vg::empty_results(nq, k, false, io.oid.ptr, io.osc.ptr, st));
     } else {
         const int nb = vg::rq_words(idx->dim) * 8;
         // two or more queries: blocks of kRqMq queries share every code load (rabitq_scan_mq_kernel)
@@ -593,27 +577,14 @@ VG_API int32_t vg_search_rabitq(vg_index *idx, const float *queries, int64_t nq,
                               vg::kRqWaves * sizeof(int) + vg::kRqMq * sizeof(float);
         vg::ArenaCall ar(idx->ctx, st);
         const int i_qcodes = ar.add(static_cast<size_t>(nq) * (nb + 4));
-        // a wave keeps 64 keys: k > 64 comes in pages of 64, one scan per page
-        const bool paged = k > 64;
-        const int pk = paged ? 64 : k;
-        const int i_partial = ar.add(sizeof(uint64_t) * static_cast<size_t>(nq) * slices * pk);
-        const int i_pid = ar.add(paged ? sizeof(uint32_t) * static_cast<size_t>(nq) * pk : 0);
-        const int i_psc = ar.add(paged ? sizeof(float) * static_cast<size_t>(nq) * pk : 0);
-        const int i_floor = ar.add(paged ? sizeof(uint64_t) * static_cast<size_t>(nq) : 0);
-        const int i_one = ar.add(paged ? 256 : 0);
+        vg::PagedTopK pages;  // a wave keeps 64 keys: k > 64 comes in pages of 64, one scan per page
+        pages.add(ar, nq, k, slices);
         VG_TRY(ar.commit());
-        struct { uint8_t *ptr; } qcodes{ar.get<uint8_t>(i_qcodes)};
-        struct { uint64_t *ptr; } partial{ar.get<uint64_t>(i_partial)};
-        uint64_t *floor_keys = ar.get<uint64_t>(i_floor);
-        uint32_t *pid = ar.get<uint32_t>(i_pid);
-        float *psc = ar.get<float>(i_psc);
-        int *one = ar.get<int>(i_one);
-        if (paged) VG_HIP(hipMemsetAsync(one, 1, sizeof(int), st));
+        uint8_t *qcodes = ar.get<uint8_t>(i_qcodes);
         VG_LAUNCH(vg::rabitq_encode_kernel, dim3(static_cast<unsigned>((nq + 15) / 16)), dim3(256), 0, st,
-                           q.ptr, nq, idx->dim, qcodes.ptr);
+                           q, nq, idx->dim, qcodes);
         const int64_t max_q = (1ll << 30) / slices;
-        for (int off = 0; off < k; off += 64) {
-            const int kk = paged ? std::min(64, k - off) : k;
+        VG_TRY(pages.run(ar, slices, false, io.oid.ptr, io.osc.ptr, st, [&](int kk, uint64_t *partial, const uint64_t *floor) -> int32_t {
             for (int64_t q0 = 0; mq && q0 < nq; q0 += max_q * vg::kRqMq) {  // whole query blocks per launch
                 const int64_t cnt = std::min<int64_t>(nq - q0, max_q * vg::kRqMq);
                 const int64_t ng = (cnt + vg::kRqMq - 1) / vg::kRqMq;
@@ -621,8 +592,8 @@ VG_API int32_t vg_search_rabitq(vg_index *idx, const float *queries, int64_t nq,
                 vg::ProfScope prof(idx->ctx, "rabitq_scan_mq", st);
                 VG_LAUNCH(kern, dim3(static_cast<unsigned>(ng * slices)), dim3(vg::kRqThreads), mq_lds, st,
                           reinterpret_cast<const uint4 *>(idx->d_rq_tiles), idx->d_rq_norms, idx->n, idx->n_tiles,
-                          idx->rq_groups, idx->dim, qcodes.ptr + q0 * (nb + 4), nb, slices, static_cast<int>(cnt), kk,
-                          partial.ptr + q0 * slices * kk, off ? floor_keys + q0 : nullptr);
+                          idx->rq_groups, idx->dim, qcodes + q0 * (nb + 4), nb, slices, static_cast<int>(cnt), kk,
+                          partial + q0 * slices * kk, floor ? floor + q0 : nullptr);
             }
             for (int64_t q0 = 0; !mq && q0 < nq; q0 += max_q) {
                 const int64_t cnt = nq - q0 < max_q ? nq - q0 : max_q;
@@ -630,22 +601,14 @@ VG_API int32_t vg_search_rabitq(vg_index *idx, const float *queries, int64_t nq,
                 VG_LAUNCH(vg::rabitq_scan_kernel, dim3(static_cast<unsigned>(cnt * slices)),
                                    dim3(vg::kRqThreads), 0, st, reinterpret_cast<const uint4 *>(idx->d_rq_tiles),
                                    idx->d_rq_norms, idx->n, idx->n_tiles, idx->rq_groups, idx->dim,
-                                   qcodes.ptr + q0 * (nb + 4), nb, slices, static_cast<int>(cnt), kk,
-                                   partial.ptr + q0 * slices * kk, off ? floor_keys + q0 : nullptr);
+                                   qcodes + q0 * (nb + 4), nb, slices, static_cast<int>(cnt), kk,
+                                   partial + q0 * slices * kk, floor ? floor + q0 : nullptr);
             }
-            if (!paged) {
-                VG_TRY(vg::launch_topk_merge(partial.ptr, nq, slices, k, false, oid.ptr, osc.ptr, st));
-            } else {
-                VG_TRY(vg::launch_topk_merge(partial.ptr, nq, slices, kk, false, pid, psc, st));
-                VG_TRY(vg::launch_page_patch(nq, k, off, kk, false, one, pid, psc, oid.ptr, osc.ptr, floor_keys, st));
-            }
-        }
+            return VG_OK;
+        }));
         // queries whose distances may hold a NaN: the reference's heap, operation by operation (vg_cand_replay.hpp)
-        VG_TRY(vg::launch_cand_replay(vg::RabitqScorer{idx->d_rq_rows, qcodes.ptr, idx->d_rq_norms + idx->n, idx->dim, nb}, q.ptr, idx->dim, idx->n, nq, k,
-                                      false, nullptr, 0, oid.ptr, osc.ptr, st));
+        VG_TRY(vg::launch_cand_replay(vg::RabitqScorer{idx->d_rq_rows, qcodes, idx->d_rq_norms + idx->n, idx->dim, nb}, q, idx->dim, idx->n, nq, k,
+                                      false, nullptr, 0, io.oid.ptr, io.osc.ptr, st));
     }
-    VG_TRY(oid.finish());
-    VG_TRY(osc.finish());
-    if (oid.on_host() || osc.on_host()) VG_HIP(hipStreamSynchronize(st));
-    return VG_OK;
+    return io.finish();
 }

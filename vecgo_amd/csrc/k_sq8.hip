@@ -17,6 +17,7 @@
 #include "vg_internal.hpp"
 #include "vg_cand_replay.hpp"
 #include "vg_nominate.hpp"
+#include "vg_search.hpp"
 
 struct vg_int4 {
     vg_ctx *ctx = nullptr;
@@ -34,13 +35,6 @@ struct vg_sq8 {
 };
 
 namespace vg {
-
-int32_t launch_page_patch(int64_t nq, int k, int off, int kk, bool descending, const int *always_one,
-                          const uint32_t *fids, const float *fscores, uint32_t *ids, float *scores, uint64_t *min_keys,
-                          hipStream_t st);
-int32_t launch_topk_merge(const uint64_t *partial, int64_t nq, int lists, int k, bool descending,
-                          uint32_t *ids, float *scores, hipStream_t st, const int *only_if = nullptr,
-                          const int *always = nullptr);
 
 constexpr float kF32Max = 3.40282346638528859811704183484516925440e+38f;
 
@@ -1715,7 +1709,7 @@ struct Sq8Scorer {
     __device__ void prepare(int64_t, const float *, int) const {}
     __device__ void score_chunk(int64_t, const float *q, int64_t row0, int64_t n, int tid, float *out) const
     {
-        const int64_t row = row0 + tid;  // (row0 is a multiple of 256: whole tiles of 64)
+        const int64_t row = row0 + tid;  // (any row: a probed range starts where its partition does, inside a tile of 64)
         if (row >= n) return;
         out[tid] = sq8_row_score<DOT>(tiles + ((row >> 6) * groups) * 64 + (row & 63), groups, dim >> 4, dim & 15, q, mins, inv);
     }
@@ -1758,24 +1752,19 @@ static int32_t sq8_search_impl(vg_index *idx, const float *queries, int64_t nq, 
     VG_CHECK(idx->n == 0 || idx->d_sq_tiles, VG_ERR_NOT_READY, "vg_search_sq8: index has no SQ8 codes");
     VG_CHECK(queries && ids && scores, VG_ERR_INVALID_ARG, "vg_search_sq8: NULL buffer");
     VG_CHECK(k <= 512, VG_ERR_UNSUPPORTED, "vg_search_sq8: k=%d exceeds 512", k);
-    VG_HIP(hipSetDevice(idx->ctx->device));
-    hipStream_t st = vg::pick_stream(idx->ctx, stream);
-    vg::DevIn<float> q;
-    vg::DevOut<uint32_t> oid;
-    vg::DevOut<float> osc;
-    VG_TRY(q.init(queries, static_cast<size_t>(nq) * idx->dim, st));
-    VG_TRY(oid.init(ids, static_cast<size_t>(nq) * k, st));
-    VG_TRY(osc.init(scores, static_cast<size_t>(nq) * k, st));
+    vg::SearchIO io;
+    VG_TRY(io.init(idx->ctx, stream, queries, static_cast<size_t>(nq) * idx->dim, ids, scores, static_cast<size_t>(nq) * k));
+    const hipStream_t st = io.st;
+    const float *q = io.q.ptr;
+    uint32_t *oid = io.oid.ptr;
+    float *osc = io.osc.ptr;
     if (idx->n == 0) {
-        vg::DevTmp<uint64_t> none;
-        VG_TRY(none.init(static_cast<size_t>(nq) * k, st));
-        VG_HIP(hipMemsetAsync(none.ptr, 0xFF, static_cast<size_t>(nq) * k * 8, st));
-        VG_TRY(vg::launch_topk_merge(none.ptr, nq, 1, k, false, oid.ptr, osc.ptr, st));
-    } else if (allow_nomination && vg::sq8_nomination_applies(idx, q.ptr, nq, k)) {
+        VG_TRY(vg::empty_results(nq, k, false, oid, osc, st));
+    } else if (allow_nomination && vg::sq8_nomination_applies(idx, q, nq, k)) {
         std::vector<int> failed;
-        VG_TRY(vg::sq8_nominated_pass(idx, q.ptr, nq, k, nullptr, 0, oid.ptr, osc.ptr, st, failed));
+        VG_TRY(vg::sq8_nominated_pass(idx, q, nq, k, nullptr, 0, oid, osc, st, failed));
         // the scan kernels for the queries whose proof failed (ties at the k-th score, thresholds too tight)
-        VG_TRY(vg::rescan_failed(failed, q.ptr, idx->dim, k, nullptr, 0, 0, oid.ptr, osc.ptr, st,
+        VG_TRY(vg::rescan_failed(failed, q, idx->dim, k, nullptr, 0, 0, oid, osc, st,
                                  [&](const float *fq, int64_t nf, const uint8_t *, int64_t, uint32_t *fid, float *fsc) {
                                      return sq8_search_impl(idx, fq, nf, k, fid, fsc, st, false);
                                  }));
@@ -1786,40 +1775,24 @@ static int32_t sq8_search_impl(vg_index *idx, const float *queries, int64_t nq, 
         const bool mq = nq >= 2 && mq_lds <= 128 * 1024;
         const int64_t units = mq ? (nq + vg::kSqProbeQ - 1) / vg::kSqProbeQ : nq;  // workgroups per slice
         const int slices = vg::sq_slices(units, idx->n_tiles, idx->ctx->compute_units);
-        // a wave keeps 64 keys: k > 64 comes in pages of 64, every page a scan for the keys after the previous
-        // page's last one (ceil(k / 64) scans)
-        const bool paged = k > 64;
-        const int pk = paged ? 64 : k;
         vg::ArenaCall ar(idx->ctx, st);
-        const int i_partial = ar.add(sizeof(uint64_t) * static_cast<size_t>(nq) * slices * pk);
-        const int i_pid = ar.add(paged ? sizeof(uint32_t) * static_cast<size_t>(nq) * pk : 0);
-        const int i_psc = ar.add(paged ? sizeof(float) * static_cast<size_t>(nq) * pk : 0);
-        const int i_floor = ar.add(paged ? sizeof(uint64_t) * static_cast<size_t>(nq) : 0);
-        const int i_one = ar.add(paged ? 256 : 0);
+        vg::PagedTopK pages;
+        pages.add(ar, nq, k, slices);
         VG_TRY(ar.commit());
-        uint64_t *partial = ar.get<uint64_t>(i_partial), *floor_keys = ar.get<uint64_t>(i_floor);
-        uint32_t *pid = ar.get<uint32_t>(i_pid);
-        float *psc = ar.get<float>(i_psc);
-        int *one = ar.get<int>(i_one);
-        if (paged) VG_HIP(hipMemsetAsync(one, 1, sizeof(int), st));
-        if (mq) {
-            auto kern = dot ? vg::sq8_scan_mq_kernel<true> : vg::sq8_scan_mq_kernel<false>;
-            VG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+        auto mq_kern = dot ? vg::sq8_scan_mq_kernel<true> : vg::sq8_scan_mq_kernel<false>;
+        if (mq)
+            VG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(mq_kern), hipFuncAttributeMaxDynamicSharedMemorySize,
                                        static_cast<int>(mq_lds)));
-        }
-        for (int off = 0; off < k; off += 64) {
-            const int kk = paged ? std::min(64, k - off) : k;
-            const uint64_t *floor = off ? floor_keys : nullptr;
+        VG_TRY(pages.run(ar, slices, dot, oid, osc, st, [&](int kk, uint64_t *partial, const uint64_t *floor) -> int32_t {
             if (mq) {
-                auto kern = dot ? vg::sq8_scan_mq_kernel<true> : vg::sq8_scan_mq_kernel<false>;
                 const int64_t max_q = ((1ll << 30) / slices) * vg::kSqProbeQ;  // whole groups per launch
                 for (int64_t q0 = 0; q0 < nq; q0 += max_q) {
                     const int64_t cnt = nq - q0 < max_q ? nq - q0 : max_q;
                     const int64_t ng = (cnt + vg::kSqProbeQ - 1) / vg::kSqProbeQ;
                     vg::ProfScope prof(idx->ctx, "sq8_scan", st);
-                    VG_LAUNCH(kern, dim3(static_cast<unsigned>(ng * slices)), dim3(vg::kSqThreads), mq_lds, st,
+                    VG_LAUNCH(mq_kern, dim3(static_cast<unsigned>(ng * slices)), dim3(vg::kSqThreads), mq_lds, st,
                               reinterpret_cast<const uint4 *>(idx->d_sq_tiles), idx->n, idx->n_tiles, idx->sq_groups, idx->dim,
-                              q.ptr + q0 * idx->dim, idx->sq->d_mins, idx->sq->d_inv, slices, static_cast<int>(cnt), kk,
+                              q + q0 * idx->dim, idx->sq->d_mins, idx->sq->d_inv, slices, static_cast<int>(cnt), kk,
                               partial + q0 * slices * kk, floor ? floor + q0 : nullptr);
                 }
             } else {
@@ -1836,24 +1809,17 @@ static int32_t sq8_search_impl(vg_index *idx, const float *queries, int64_t nq, 
                                      : (dot ? vg::sq8_scan_kernel<true, vg::kSqWaves> : vg::sq8_scan_kernel<false, vg::kSqWaves>);
                     VG_LAUNCH(kern, dim3(static_cast<unsigned>(cnt * slices)), dim3(wide ? 512 : vg::kSqThreads), 0, st,
                               reinterpret_cast<const uint4 *>(idx->d_sq_tiles), idx->n, idx->n_tiles, idx->sq_groups, idx->dim,
-                              q.ptr + q0 * idx->dim, idx->sq->d_mins, idx->sq->d_inv, slices, static_cast<int>(cnt), kk,
+                              q + q0 * idx->dim, idx->sq->d_mins, idx->sq->d_inv, slices, static_cast<int>(cnt), kk,
                               partial + q0 * slices * kk, floor ? floor + q0 : nullptr);
                 }
             }
-            if (!paged) {
-                VG_TRY(vg::launch_topk_merge(partial, nq, slices, k, dot, oid.ptr, osc.ptr, st));
-            } else {
-                VG_TRY(vg::launch_topk_merge(partial, nq, slices, kk, dot, pid, psc, st));
-                VG_TRY(vg::launch_page_patch(nq, k, off, kk, dot, one, pid, psc, oid.ptr, osc.ptr, floor_keys, st));
-            }
-        }
+            return VG_OK;
+        }));
     }
     // queries whose scores may hold a NaN: the reference's heap, operation by operation (vg_cand_replay.hpp; not for the
     // queries this function sends to itself after a failed proof: the caller's pass covers them)
-    if (idx->n > 0 && allow_nomination) VG_TRY(vg::sq8_nan_replay(idx, q.ptr, nq, k, nullptr, 0, nullptr, 0, nullptr, oid.ptr, osc.ptr, st));
-    VG_TRY(oid.finish());
-    VG_TRY(osc.finish());
-    return VG_OK;
+    if (idx->n > 0 && allow_nomination) VG_TRY(vg::sq8_nan_replay(idx, q, nq, k, nullptr, 0, nullptr, 0, nullptr, oid, osc, st));
+    return io.finish();
 }
 
 // ---- INT4 C ABI ---------------------------------------------------------------------------------------

@@ -27,13 +27,9 @@
 
 #include "vg_device.hpp"
 #include "vg_internal.hpp"
+#include "vg_search.hpp"
 
 namespace vg {
-
-// the existing retile kernels, behind host wrappers in their own files (k_adc.hip, k_rabitq.hip)
-int32_t launch_pq_retile(const uint8_t *codes, int64_t n, int m, int groups, int64_t n_tiles, uint8_t *tiles, hipStream_t st);
-int32_t launch_rabitq_retile(const uint8_t *codes, int64_t n, int nb, int groups, int64_t n_tiles, uint8_t *tiles, float *norms,
-                             hipStream_t st);
 
 constexpr uint32_t kRbUnvisited = 0xFFFFFFFFu;
 constexpr int kRbThreads = 256;

@@ -232,7 +232,6 @@ struct DevOut {
         ptr = owned;
         return VG_OK;
     }
-    bool on_host() const { return host != nullptr; }
     int32_t finish()
     {
         if (host && count) {

@@ -1,0 +1,168 @@
+// vg_search.hpp — what the search translation units share on the host: every function one .hip defines and another calls,
+// declared once (the defining file includes this header too, so a definition that disagrees does not compile), and the
+// scaffolding every scan entry point stands on: SearchIO (staged operands), empty_results, PagedTopK (k > 64 in pages).
+// (The bf16 nomination's functions are declared in vg_nominate.hpp.)
+#pragma once
+
+#include <algorithm>
+
+#include "vg_internal.hpp"
+
+namespace vg {
+
+// ---- k_adc.hip ------------------------------------------------------------------------------------
+// per query the k best of `lists` k-lists of keys -> ids / scores; only_if[q] == 0 leaves query q alone unless always[0] != 0
+int32_t launch_topk_merge(const uint64_t *partial, int64_t nq, int lists, int k, bool descending,
+                          uint32_t *ids, float *scores, hipStream_t st, const int *only_if = nullptr,
+                          const int *always = nullptr);
+// row-major PQ codes -> the scan's tiles (vg_vamana_reorder_bfs rebuilds them from its permuted codes)
+int32_t launch_pq_retile(const uint8_t *codes, int64_t n, int m, int groups, int64_t n_tiles, uint8_t *tiles, hipStream_t st);
+// the probed partitions' rows by table lookups, `split` k-lists per query
+int32_t launch_probe_scan_adc(const vg_index *idx, const float *tables, const uint32_t *probes, const uint32_t *part_off,
+                              int64_t nq, int np, int split, int k, uint64_t *partial, const uint64_t *min_keys, bool desc,
+                              const uint8_t *mask, int64_t mask_stride, hipStream_t st);
+// the replay for device buffers: the whole segment, or (probes: nq * np partition ids, part_off) the probed partitions; mask: a
+// device row filter per query / for the batch, or null; desc: a Dot / Cosine segment keeps the LARGEST sums (flat/segment.go:449)
+int32_t pq_nan_replay(vg_index *idx, const float *d_queries, int64_t nq, int k, bool desc, const uint8_t *d_mask, int64_t mask_stride,
+                      const uint32_t *d_probes, int np, const uint32_t *d_part_off, uint32_t *d_ids, float *d_scores, hipStream_t st);
+// vg_search_pq_adc with a DEVICE row filter (null: none) and the heap direction given
+int32_t pq_adc_search_masked(vg_index *idx, const float *queries, int64_t nq, int32_t k, const uint8_t *mask, int64_t mask_stride,
+                             bool desc, uint32_t *ids, float *scores, void *stream);
+
+// ---- k_pq.hip -------------------------------------------------------------------------------------
+// the queries' distance tables, in the ADC scan's LDS layout (scan_layout) or [m][k]
+int32_t launch_pq_build_table(const vg_pq *pq, const float *d_queries, int64_t nq, float *d_tables,
+                              bool scan_layout, hipStream_t st);
+
+// ---- k_flat.hip -----------------------------------------------------------------------------------
+// all queries of a paged scan (k > 64 through a kernel that keeps 64 keys per wave): copy page `off / 64` and
+// make its last key the floor of the next page
+int32_t launch_page_patch(int64_t nq, int k, int off, int kk, bool descending, const int *always_one,
+                          const uint32_t *fids, const float *fscores, uint32_t *ids, float *scores, uint64_t *min_keys,
+                          hipStream_t st);
+// vg_search_flat with a DEVICE row filter (null: none); l2_scores: squared-L2 scores whatever the index's metric;
+// cand_replay: the NaN replay of vg_cand_replay.hpp at the end (a caller that replays for itself passes false)
+int32_t flat_search_masked(vg_index *idx, const float *queries, int64_t nq, int32_t k, const uint8_t *mask, int64_t mask_stride,
+                           uint32_t *ids, float *scores, void *stream, bool l2_scores = false, bool cand_replay = true);
+// the threshold search's nomination (k_flat_threshold.hip): sample columns, the GEMM passes, the proof's work list
+int64_t flat_thr_sample_cols(int64_t n, int sample_stride);
+int32_t flat_thr_nominate(vg_index *idx, hipStream_t st, const float *qp, const float *uthr, int64_t cnt, const uint8_t *m0,
+                          int64_t mask_stride, int cap, int sel_k, int sample_stride, bool bf16, float eps_extra, float *sc, uint64_t *partial,
+                          uint32_t *sid, float *sthr, uint16_t *qbf, int *counts_wide, float *gthr, float *qnorm, int *untight, int *counts,
+                          uint64_t *cand);
+int32_t launch_flat_todo(const int *flags, const int *always, int cnt, int *todo, unsigned long long *stats, hipStream_t st);
+
+// ---- k_flat_threshold.hip -------------------------------------------------------------------------
+// the best max_results keys of per-query lists, written best first; the engine's threshold filter (vg_search_vamana's
+// large-k walk and vg_search_vamana_threshold, k_graph.hip)
+int32_t launch_thr_select_lists(bool desc, const uint64_t *lists, int64_t list_cap, const int *counts, int64_t nq, int max_results,
+                                uint32_t *ids, float *scores, int32_t *out_counts, hipStream_t st);
+int32_t launch_thr_filter(bool desc, const float *thr, int64_t nq, int max_results, uint32_t *ids, float *scores, int32_t *counts,
+                          hipStream_t st);
+
+// ---- k_sq8.hip ------------------------------------------------------------------------------------
+// the probed partitions' rows from the SQ8 codes: one pass per (query, probe), or per group of pairs of one partition
+int32_t launch_probe_scan_sq8(const vg_index *idx, const float *queries, const uint32_t *probes, const uint32_t *part_off,
+                              int64_t nq, int np, int sub, int k, uint64_t *partial, const uint64_t *min_keys,
+                              const uint8_t *mask, int64_t mask_stride, hipStream_t st);
+int32_t launch_probe_scan_sq8_grouped(const vg_index *idx, const float *queries, const uint32_t *part_off,
+                                      const uint32_t *pair_of, const ProbeGroup *groups, const uint32_t *ngroups, unsigned gmax,
+                                      int np, int sub, int k, uint64_t *partial, const uint64_t *min_keys, const uint8_t *mask,
+                                      int64_t mask_stride, hipStream_t st);
+// pq_nan_replay's twin (the heap direction follows the index's metric)
+int32_t sq8_nan_replay(vg_index *idx, const float *d_queries, int64_t nq, int k, const uint8_t *d_mask, int64_t mask_stride,
+                       const uint32_t *d_probes, int np, const uint32_t *d_part_off, uint32_t *d_ids, float *d_scores, hipStream_t st);
+
+// ---- k_rabitq.hip ---------------------------------------------------------------------------------
+// sign bits + norm of each vector (RaBitQ Encode)
+int32_t launch_rabitq_encode(const float *d_vectors, int64_t n, int dim, uint8_t *d_codes, hipStream_t st);
+// row-major codes -> the scan's tiles and norms[0, n) (vg_vamana_reorder_bfs rebuilds them from its permuted codes)
+int32_t launch_rabitq_retile(const uint8_t *codes, int64_t n, int nb, int groups, int64_t n_tiles, uint8_t *tiles, float *norms,
+                             hipStream_t st);
+
+// ---- the scaffolding of a search entry point ------------------------------------------------------
+// The operands of one search call: the device, the stream, the queries (and a row filter) staged into HBM when they live on the
+// host, ids / scores produced in HBM.  finish() copies the results back and waits for them where they went to the host.
+struct SearchIO {
+    hipStream_t st = nullptr;
+    DevIn<float> q;
+    DevIn<uint8_t> mk;
+    DevOut<uint32_t> oid;
+    DevOut<float> osc;
+    int32_t init(vg_ctx *ctx, void *stream, const float *queries, size_t query_floats, uint32_t *ids, float *scores, size_t results,
+                 const uint8_t *mask = nullptr, size_t mask_bytes = 0)
+    {
+        VG_HIP(hipSetDevice(ctx->device));
+        st = pick_stream(ctx, stream);
+        VG_TRY(q.init(queries, query_floats, st));
+        VG_TRY(oid.init(ids, results, st));
+        VG_TRY(osc.init(scores, results, st));
+        return mk.init(mask, mask_bytes, st);
+    }
+    int32_t finish()
+    {
+        VG_TRY(oid.finish());
+        return osc.finish();
+    }
+};
+
+// the bytes of nq row filters of an n-row index, mask_stride apart (0: one filter for the batch); no filter: 0
+inline size_t mask_span(const uint8_t *mask, int64_t mask_stride, int64_t nq, int64_t n)
+{
+    const int64_t mask_bytes = (n + 7) / 8;
+    return mask ? static_cast<size_t>(mask_stride ? (nq - 1) * mask_stride + mask_bytes : mask_bytes) : 0;
+}
+
+// The answer of an index without rows: k invalid ids per query, through the merge every scan ends in.
+inline int32_t empty_results(int64_t nq, int k, bool descending, uint32_t *ids, float *scores, hipStream_t st)
+{
+    DevTmp<uint64_t> none;
+    VG_TRY(none.init(static_cast<size_t>(nq) * k, st));
+    VG_HIP(hipMemsetAsync(none.ptr, 0xFF, static_cast<size_t>(nq) * k * 8, st));
+    return launch_topk_merge(none.ptr, nq, 1, k, descending, ids, scores, st);
+}
+
+// A scan whose waves keep 64 keys answers k > 64 in pages of 64 results, each page a scan for the keys after the previous
+// page's last one (ceil(k / 64) scans); k <= 64 is the one scan, merged straight into the results.  add() before the arena's
+// commit(), run() after it.  scan(kk, partial, floor): fills `lists` kk-lists per query in `partial`; floor[q] (null on the
+// first page) is the key the page's keys have to follow.
+struct PagedTopK {
+    int64_t nq = 0;
+    int k = 0;
+    int i_partial = 0, i_pid = 0, i_psc = 0, i_floor = 0, i_one = 0;
+    bool paged() const { return k > 64; }
+    // min_partial_keys: what else the caller keeps in `partial`
+    void add(ArenaCall &ar, int64_t nq_, int k_, int lists, size_t min_partial_keys = 0)
+    {
+        nq = nq_;
+        k = k_;
+        const int pk = paged() ? 64 : k;
+        i_partial = ar.add(sizeof(uint64_t) * std::max(static_cast<size_t>(nq) * lists * pk, min_partial_keys));
+        i_pid = ar.add(paged() ? sizeof(uint32_t) * static_cast<size_t>(nq) * pk : 0);
+        i_psc = ar.add(paged() ? sizeof(float) * static_cast<size_t>(nq) * pk : 0);
+        i_floor = ar.add(paged() ? sizeof(uint64_t) * static_cast<size_t>(nq) : 0);
+        i_one = ar.add(paged() ? 256 : 0);
+    }
+    template <class Scan>
+    int32_t run(const ArenaCall &ar, int lists, bool descending, uint32_t *ids, float *scores, hipStream_t st, Scan scan) const
+    {
+        uint64_t *partial = ar.get<uint64_t>(i_partial), *floor_keys = ar.get<uint64_t>(i_floor);
+        uint32_t *pid = ar.get<uint32_t>(i_pid);
+        float *psc = ar.get<float>(i_psc);
+        int *one = ar.get<int>(i_one);
+        if (paged()) VG_HIP(hipMemsetAsync(one, 1, sizeof(int), st));
+        for (int off = 0; off < k; off += 64) {
+            const int kk = paged() ? std::min(64, k - off) : k;
+            VG_TRY(scan(kk, partial, off ? floor_keys : nullptr));
+            if (!paged()) {
+                VG_TRY(launch_topk_merge(partial, nq, lists, k, descending, ids, scores, st));
+            } else {
+                VG_TRY(launch_topk_merge(partial, nq, lists, kk, descending, pid, psc, st));
+                VG_TRY(launch_page_patch(nq, k, off, kk, descending, one, pid, psc, ids, scores, floor_keys, st));
+            }
+        }
+        return VG_OK;
+    }
+};
+
+}  // namespace vg
