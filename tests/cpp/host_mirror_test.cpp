@@ -10,6 +10,7 @@
 #include <cstring>
 #include <random>
 
+#include "../../vecgo_amd/csrc/vg_walk_chunk.hpp"
 #include "vecgo_hip.hpp"
 #include "vg_oracle.h"
 
@@ -55,6 +56,15 @@ static std::vector<std::vector<float>> unit_vectors(std::mt19937 &rng, int n, in
 
 // what a host allocates per query for the graph searches' counters (the struct grew from 4 to 5 fields)
 static_assert(sizeof(vg_search_stats) == 5 * sizeof(int64_t), "vg_search_stats is five int64: bump VG_ABI_VERSION with it");
+
+// the queries of one launch of a graph walk (WalkChunks, vg_search.hpp): a cap below one query's scratch still walks one
+// query, a cap above the whole batch's takes the batch, in between the exact quotient
+static_assert(vg::walk_chunk(int64_t(1) << 30, (int64_t(1) << 30) + 1, 8192) == 1, "a query that does not fit walks alone");
+static_assert(vg::walk_chunk(int64_t(1) << 30, 650000, 8192) == 1651, "1 GiB of 650 000-byte queries: floor(2^30 / 650 000)");
+static_assert(vg::walk_chunk(int64_t(16) << 30, 650000, 8192) == 8192, "room for more than the batch: the batch");
+static_assert(vg::walk_chunk(int64_t(1) << 30, 131072, 8192) == 8192 && vg::walk_chunk(int64_t(1) << 30, 131073, 8192) == 8191,
+              "the quotient is exact at the boundary");
+static_assert(vg::walk_chunk(int64_t(1) << 30, 0, 5) == 5 && vg::walk_chunk(0, 100, 5) == 1, "no scratch per query; no room at all");
 
 int main()
 {

@@ -530,8 +530,102 @@ static int32_t brute_nan_replay(vg_index *idx, const float *d_queries, int64_t n
 }
 }  // namespace vg
 
+// the distance matrix of a chunk of queries + the reference's heap, replayed per query: what vg_search_hnsw_brute answers with
+// when its fast path does not apply
 static int32_t brute_impl(vg_index *idx, const float *queries, int64_t nq, int32_t k, int32_t mode, const uint8_t *mask,
-                          int64_t mask_stride, uint32_t *ids, float *scores, void *stream);
+                          int64_t mask_stride, uint32_t *ids, float *scores, void *stream)
+{
+    VG_CHECK(idx, VG_ERR_INVALID_ARG, "vg_search_hnsw_brute: NULL index");
+    VG_CHECK(nq >= 0 && k >= 0, VG_ERR_INVALID_ARG, "vg_search_hnsw_brute: negative nq or k");
+    VG_CHECK(mode == VG_BRUTE_SCAN || mode == VG_BRUTE_BITMAP, VG_ERR_INVALID_ARG, "vg_search_hnsw_brute: unknown mode %d", mode);
+    if (nq == 0 || k == 0) return VG_OK;
+    VG_CHECK(idx->metric != VG_METRIC_HAMMING, VG_ERR_UNSUPPORTED, "unsupported metric for float32: Hamming");
+    VG_CHECK(k <= vg::kBruteMaxK, VG_ERR_UNSUPPORTED, "vg_search_hnsw_brute: k=%d exceeds %d", k, vg::kBruteMaxK);
+    VG_CHECK(queries && ids && scores, VG_ERR_INVALID_ARG, "vg_search_hnsw_brute: NULL buffer");
+    VG_CHECK(idx->n == 0 || idx->d_vectors, VG_ERR_NOT_READY, "vg_search_hnsw_brute: index has no fp32 vectors");
+    VG_CHECK_MASK_STRIDE("vg_search_hnsw_brute", mask, mask_stride, idx->n);
+    vg::SearchIO io;
+    VG_TRY(io.init(idx->ctx, stream, queries, static_cast<size_t>(nq) * idx->dim, ids, scores, static_cast<size_t>(nq) * k, mask,
+                   vg::mask_span(mask, mask_stride, nq, idx->n)));
+    const hipStream_t st = io.st;
+    const float *q = io.q.ptr;
+    const uint8_t *mk = io.mk.ptr;
+    uint32_t *oid = io.oid.ptr;
+    float *osc = io.osc.ptr;
+    const int64_t n = idx->n;
+    // dist[q][row] of one chunk of queries.  The query-blocked kernel gets its row reuse from kBruteQB = 16 queries per
+    // workgroup, so a chunk of thousands of queries buys nothing: 2 GiB of distances (512 queries at 1M rows), but at
+    // least one block of 16 queries while that stays within 1/16 of the device's memory.  The buffer comes from the
+    // scratch cache (idle blocks go back to the driver when an allocation fails, and with the context), not from the
+    // grow-only arena — r04 took up to 16 GiB from the arena and kept it until the context was destroyed.  When the
+    // index leaves no room, the chunk is halved until the allocation succeeds.
+    const int64_t row_bytes = std::max<int64_t>(n, 1) * 4;
+    int64_t chunk = std::max<int64_t>(1, (int64_t(2) << 30) / row_bytes);
+    if (chunk < vg::kBruteQB) chunk = std::max<int64_t>(1, std::min<int64_t>(vg::kBruteQB, vg::scratch_cap(idx->ctx) / row_bytes));
+    chunk = std::min<int64_t>(std::min(chunk, nq), 65535);
+    vg::DevTmp<float> dist_buf;
+    for (;;) {
+        const int32_t rc = dist_buf.init(static_cast<size_t>(chunk) * static_cast<size_t>(std::max<int64_t>(n, 1)), st);
+        if (rc == VG_OK) break;
+        VG_CHECK(chunk > 1, rc, "vg_search_hnsw_brute: no room for one query's %lld distances: %s", static_cast<long long>(n),
+                 vg_last_error());
+        chunk = (chunk + 1) / 2;
+    }
+    float *dist = dist_buf.ptr;
+    const size_t lds = (static_cast<size_t>((k + 4 + 3) & ~3) + vg::kBruteStep) * sizeof(vg::HItem);
+    auto replay = mode == VG_BRUTE_SCAN ? vg::brute_replay_kernel<VG_BRUTE_SCAN> : vg::brute_replay_kernel<VG_BRUTE_BITMAP>;
+    VG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(replay), hipFuncAttributeMaxDynamicSharedMemorySize,
+                               static_cast<int>(lds)));
+    const unsigned row_blocks = static_cast<unsigned>(std::min<int64_t>(std::max<int64_t>((n + vg::kBruteRowsPerBlock - 1) /
+                                                                                          vg::kBruteRowsPerBlock, 1), 65535));
+    for (int64_t q0 = 0; q0 < nq; q0 += chunk) {
+        const int64_t cnt = std::min(chunk, nq - q0);
+        const uint8_t *m0 = mk ? mk + q0 * mask_stride : nullptr;
+        if (n > 0) {
+            vg::ProfScope prof(idx->ctx, "hnsw_brute_dist", st);
+            const bool mq = cnt >= 2 && idx->dim % 4 == 0 && idx->dim <= 1024 && (m0 == nullptr || mask_stride == 0);
+            if (mq) {  // query-blocked: rows read once per 16 queries
+                const int qblocks = static_cast<int>((cnt + vg::kBruteQB - 1) / vg::kBruteQB);
+                // ~8 workgroups per CU in all; slices in whole groups of 8 (one per XCD), at least 32 rows each
+                int64_t slices = (int64_t(8) * std::max(idx->ctx->compute_units, 1) + qblocks - 1) / qblocks;
+                slices = std::min<int64_t>(((slices + 7) / 8) * 8, std::max<int64_t>(8, ((n + 31) / 32 / 8) * 8));
+                const size_t qlds = static_cast<size_t>(vg::kBruteQB) * idx->dim * sizeof(float);
+                const dim3 grid(static_cast<unsigned>(qblocks * slices)), block(vg::kBruteDistThreads);
+                auto launch = [&](auto kern) -> int32_t {
+                    VG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                               static_cast<int>(qlds)));
+                    VG_LAUNCH(kern, grid, block, qlds, st, idx->d_vectors, n, idx->dim, q + q0 * idx->dim,
+                              static_cast<int>(cnt), m0, dist, qblocks, static_cast<int>(slices));
+                    return VG_OK;
+                };
+                if (idx->metric == VG_METRIC_L2)
+                    VG_TRY(launch(vg::brute_dist_mq_kernel<vg::kMetricL2>));
+                else if (idx->metric == VG_METRIC_COSINE)
+                    VG_TRY(launch(vg::brute_dist_mq_kernel<vg::kMetricCos>));
+                else
+                    VG_TRY(launch(vg::brute_dist_mq_kernel<vg::kMetricDot>));
+            } else {
+                const dim3 grid(static_cast<unsigned>(cnt), row_blocks), block(vg::kBruteDistThreads);
+                auto launch1 = [&](auto kern) -> int32_t {
+                    VG_LAUNCH(kern, grid, block, 0, st, idx->d_vectors, n, idx->dim, q + q0 * idx->dim, m0, mask_stride, dist);
+                    return VG_OK;
+                };
+                const bool one = cnt == 1;
+                if (idx->metric == VG_METRIC_L2)
+                    VG_TRY(one ? launch1(vg::brute_dist_kernel<vg::kMetricL2, true>) : launch1(vg::brute_dist_kernel<vg::kMetricL2, false>));
+                else if (idx->metric == VG_METRIC_COSINE)
+                    VG_TRY(one ? launch1(vg::brute_dist_kernel<vg::kMetricCos, true>) : launch1(vg::brute_dist_kernel<vg::kMetricCos, false>));
+                else
+                    VG_TRY(one ? launch1(vg::brute_dist_kernel<vg::kMetricDot, true>) : launch1(vg::brute_dist_kernel<vg::kMetricDot, false>));
+            }
+        }
+        vg::ProfScope prof(idx->ctx, "hnsw_brute_replay", st);
+        VG_LAUNCH(replay, dim3(static_cast<unsigned>(cnt)), dim3(vg::kBruteThreads), lds, st, dist, n, m0, mask_stride, k,
+                  oid + q0 * k, osc + q0 * k);
+    }
+    VG_TRY(vg::brute_nan_replay(idx, q, nq, k, mode, mk, mask_stride, oid, osc, st));  // queries whose distances may hold a NaN
+    return io.finish();
+}
 
 VG_API int32_t vg_search_hnsw_brute(vg_index *idx, const float *queries, int64_t nq, int32_t k, int32_t mode,
                                     const uint8_t *mask, int64_t mask_stride, uint32_t *ids, float *scores, void *stream)
@@ -600,105 +694,6 @@ VG_API int32_t vg_search_hnsw_brute(vg_index *idx, const float *queries, int64_t
         if (h[static_cast<size_t>(i)])
             VG_TRY(brute_impl(idx, q + i * idx->dim, 1, k, mode, mk ? mk + i * mask_stride : nullptr, 0, oid + i * k,
                               osc + i * k, st));
-    VG_TRY(vg::brute_nan_replay(idx, q, nq, k, mode, mk, mask_stride, oid, osc, st));  // queries whose distances may hold a NaN
-    return io.finish();
-}
-
-static int32_t brute_impl(vg_index *idx, const float *queries, int64_t nq, int32_t k, int32_t mode,
-                                    const uint8_t *mask, int64_t mask_stride, uint32_t *ids, float *scores, void *stream)
-{
-    VG_CHECK(idx, VG_ERR_INVALID_ARG, "vg_search_hnsw_brute: NULL index");
-    VG_CHECK(nq >= 0 && k >= 0, VG_ERR_INVALID_ARG, "vg_search_hnsw_brute: negative nq or k");
-    VG_CHECK(mode == VG_BRUTE_SCAN || mode == VG_BRUTE_BITMAP, VG_ERR_INVALID_ARG, "vg_search_hnsw_brute: unknown mode %d", mode);
-    if (nq == 0 || k == 0) return VG_OK;
-    VG_CHECK(idx->metric != VG_METRIC_HAMMING, VG_ERR_UNSUPPORTED, "unsupported metric for float32: Hamming");
-    VG_CHECK(k <= vg::kBruteMaxK, VG_ERR_UNSUPPORTED, "vg_search_hnsw_brute: k=%d exceeds %d", k, vg::kBruteMaxK);
-    VG_CHECK(queries && ids && scores, VG_ERR_INVALID_ARG, "vg_search_hnsw_brute: NULL buffer");
-    VG_CHECK(idx->n == 0 || idx->d_vectors, VG_ERR_NOT_READY, "vg_search_hnsw_brute: index has no fp32 vectors");
-    const int64_t mask_bytes = (idx->n + 7) / 8;
-    VG_CHECK(mask == nullptr || mask_stride == 0 || mask_stride >= mask_bytes, VG_ERR_INVALID_ARG,
-             "vg_search_hnsw_brute: mask_stride %lld is shorter than a mask (%lld bytes)", static_cast<long long>(mask_stride),
-             static_cast<long long>(mask_bytes));
-    vg::SearchIO io;
-    VG_TRY(io.init(idx->ctx, stream, queries, static_cast<size_t>(nq) * idx->dim, ids, scores, static_cast<size_t>(nq) * k, mask,
-                   vg::mask_span(mask, mask_stride, nq, idx->n)));
-    const hipStream_t st = io.st;
-    const float *q = io.q.ptr;
-    const uint8_t *mk = io.mk.ptr;
-    uint32_t *oid = io.oid.ptr;
-    float *osc = io.osc.ptr;
-    const int64_t n = idx->n;
-    // dist[q][row] of one chunk of queries.  The query-blocked kernel gets its row reuse from kBruteQB = 16 queries per
-    // workgroup, so a chunk of thousands of queries buys nothing: 2 GiB of distances (512 queries at 1M rows), but at
-    // least one block of 16 queries while that stays within 1/16 of the device's memory.  The buffer comes from the
-    // scratch cache (idle blocks go back to the driver when an allocation fails, and with the context), not from the
-    // grow-only arena — r04 took up to 16 GiB from the arena and kept it until the context was destroyed.  When the
-    // index leaves no room, the chunk is halved until the allocation succeeds.
-    const int64_t row_bytes = std::max<int64_t>(n, 1) * 4;
-    const int64_t cap16 = std::min<int64_t>(int64_t(16) << 30, std::max<int64_t>(int64_t(1) << 30, idx->ctx->hbm_bytes / 16));
-    int64_t chunk = std::max<int64_t>(1, (int64_t(2) << 30) / row_bytes);
-    if (chunk < vg::kBruteQB) chunk = std::max<int64_t>(1, std::min<int64_t>(vg::kBruteQB, cap16 / row_bytes));
-    chunk = std::min<int64_t>(std::min(chunk, nq), 65535);
-    vg::DevTmp<float> dist_buf;
-    for (;;) {
-        const int32_t rc = dist_buf.init(static_cast<size_t>(chunk) * static_cast<size_t>(std::max<int64_t>(n, 1)), st);
-        if (rc == VG_OK) break;
-        VG_CHECK(chunk > 1, rc, "vg_search_hnsw_brute: no room for one query's %lld distances: %s", static_cast<long long>(n),
-                 vg_last_error());
-        chunk = (chunk + 1) / 2;
-    }
-    float *dist = dist_buf.ptr;
-    const size_t lds = (static_cast<size_t>((k + 4 + 3) & ~3) + vg::kBruteStep) * sizeof(vg::HItem);
-    auto replay = mode == VG_BRUTE_SCAN ? vg::brute_replay_kernel<VG_BRUTE_SCAN> : vg::brute_replay_kernel<VG_BRUTE_BITMAP>;
-    VG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(replay), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               static_cast<int>(lds)));
-    const unsigned row_blocks = static_cast<unsigned>(std::min<int64_t>(std::max<int64_t>((n + vg::kBruteRowsPerBlock - 1) /
-                                                                                          vg::kBruteRowsPerBlock, 1), 65535));
-    for (int64_t q0 = 0; q0 < nq; q0 += chunk) {
-        const int64_t cnt = std::min(chunk, nq - q0);
-        const uint8_t *m0 = mk ? mk + q0 * mask_stride : nullptr;
-        if (n > 0) {
-            vg::ProfScope prof(idx->ctx, "hnsw_brute_dist", st);
-            const bool mq = cnt >= 2 && idx->dim % 4 == 0 && idx->dim <= 1024 && (m0 == nullptr || mask_stride == 0);
-            if (mq) {  // query-blocked: rows read once per 16 queries
-                const int qblocks = static_cast<int>((cnt + vg::kBruteQB - 1) / vg::kBruteQB);
-                // ~8 workgroups per CU in all; slices in whole groups of 8 (one per XCD), at least 32 rows each
-                int64_t slices = (int64_t(8) * std::max(idx->ctx->compute_units, 1) + qblocks - 1) / qblocks;
-                slices = std::min<int64_t>(((slices + 7) / 8) * 8, std::max<int64_t>(8, ((n + 31) / 32 / 8) * 8));
-                const size_t qlds = static_cast<size_t>(vg::kBruteQB) * idx->dim * sizeof(float);
-                const dim3 grid(static_cast<unsigned>(qblocks * slices)), block(vg::kBruteDistThreads);
-                auto launch = [&](auto kern) -> int32_t {
-                    VG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                               static_cast<int>(qlds)));
-                    VG_LAUNCH(kern, grid, block, qlds, st, idx->d_vectors, n, idx->dim, q + q0 * idx->dim,
-                              static_cast<int>(cnt), m0, dist, qblocks, static_cast<int>(slices));
-                    return VG_OK;
-                };
-                if (idx->metric == VG_METRIC_L2)
-                    VG_TRY(launch(vg::brute_dist_mq_kernel<vg::kMetricL2>));
-                else if (idx->metric == VG_METRIC_COSINE)
-                    VG_TRY(launch(vg::brute_dist_mq_kernel<vg::kMetricCos>));
-                else
-                    VG_TRY(launch(vg::brute_dist_mq_kernel<vg::kMetricDot>));
-            } else {
-                const dim3 grid(static_cast<unsigned>(cnt), row_blocks), block(vg::kBruteDistThreads);
-                auto launch1 = [&](auto kern) -> int32_t {
-                    VG_LAUNCH(kern, grid, block, 0, st, idx->d_vectors, n, idx->dim, q + q0 * idx->dim, m0, mask_stride, dist);
-                    return VG_OK;
-                };
-                const bool one = cnt == 1;
-                if (idx->metric == VG_METRIC_L2)
-                    VG_TRY(one ? launch1(vg::brute_dist_kernel<vg::kMetricL2, true>) : launch1(vg::brute_dist_kernel<vg::kMetricL2, false>));
-                else if (idx->metric == VG_METRIC_COSINE)
-                    VG_TRY(one ? launch1(vg::brute_dist_kernel<vg::kMetricCos, true>) : launch1(vg::brute_dist_kernel<vg::kMetricCos, false>));
-                else
-                    VG_TRY(one ? launch1(vg::brute_dist_kernel<vg::kMetricDot, true>) : launch1(vg::brute_dist_kernel<vg::kMetricDot, false>));
-            }
-        }
-        vg::ProfScope prof(idx->ctx, "hnsw_brute_replay", st);
-        VG_LAUNCH(replay, dim3(static_cast<unsigned>(cnt)), dim3(vg::kBruteThreads), lds, st, dist, n, m0, mask_stride, k,
-                  oid + q0 * k, osc + q0 * k);
-    }
     VG_TRY(vg::brute_nan_replay(idx, q, nq, k, mode, mk, mask_stride, oid, osc, st));  // queries whose distances may hold a NaN
     return io.finish();
 }

@@ -325,10 +325,7 @@ VG_API int32_t vg_search_flat_threshold(vg_index *idx, const float *queries, int
     if (nq == 0 || max_results == 0) return VG_OK;
     VG_CHECK(queries && thresholds && ids && scores && counts, VG_ERR_INVALID_ARG, "vg_search_flat_threshold: NULL buffer");
     VG_CHECK(idx->n == 0 || idx->d_vectors, VG_ERR_NOT_READY, "vg_search_flat_threshold: index has no fp32 vectors");
-    const int64_t mask_bytes = (idx->n + 7) / 8;
-    VG_CHECK(mask == nullptr || mask_stride == 0 || mask_stride >= mask_bytes, VG_ERR_INVALID_ARG,
-             "vg_search_flat_threshold: mask_stride %lld is shorter than a mask (%lld bytes)", static_cast<long long>(mask_stride),
-             static_cast<long long>(mask_bytes));
+    VG_CHECK_MASK_STRIDE("vg_search_flat_threshold", mask, mask_stride, idx->n);
     VG_HIP(hipSetDevice(idx->ctx->device));
     hipStream_t st = vg::pick_stream(idx->ctx, stream);
     const bool dot = idx->metric != VG_METRIC_L2;
@@ -343,7 +340,7 @@ VG_API int32_t vg_search_flat_threshold(vg_index *idx, const float *queries, int
     vg::DevOut<int32_t> ocnt;
     VG_TRY(q.init(queries, static_cast<size_t>(nq) * dim, st));
     VG_TRY(t.init(thresholds, static_cast<size_t>(nq), st));
-    VG_TRY(mk.init(mask, mask ? static_cast<size_t>(mask_stride ? (nq - 1) * mask_stride + mask_bytes : mask_bytes) : 0, st));
+    VG_TRY(mk.init(mask, vg::mask_span(mask, mask_stride, nq, idx->n), st));
     VG_TRY(oid.init(ids, out_n, st));
     VG_TRY(osc.init(scores, out_n, st));
     VG_TRY(ocnt.init(counts, static_cast<size_t>(nq), st));

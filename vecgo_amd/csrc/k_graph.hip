@@ -58,6 +58,28 @@ constexpr int kHnswLdsEf = 512;  // LDS items of the results heap (twice that fo
 #ifndef VG_LDS_PQ_WAVES
 #define VG_LDS_PQ_WAVES 4
 #endif
+// fp32 rows with split heaps keep the query itself in LDS (F32ScorerT<true>; the kernel's kQLds, the launch's LDS size)
+#ifndef VG_SPLIT_F32_QLDS
+#define VG_SPLIT_F32_QLDS 1
+#endif
+// The launch's heap layout.  Heaps in LDS up to kHnswLdsEf (12 KiB per query: the waves of a CU are then bounded by registers,
+// not LDS), beyond it split between LDS (the top levels) and HBM scratch.
+// split heaps: waves in flight beat heap levels in LDS.  The PQ walk (3.75 KiB of query constants in LDS): 128 items
+// = 7.4 KiB per query, 16 waves per CU: ef 1024 / 2048 40.7 / 81.9 -> 35.6 / 68.5 ms per 8192 queries against 256 items
+// (15 waves); the fp32 walk (the query itself in LDS): 128 items as well
+#ifndef VG_PQ_LDS_HEAPS_MAX
+#define VG_PQ_LDS_HEAPS_MAX 448  // PQ walk: all-LDS heaps at ef 512 are 16.7 KiB per query = 9 waves per CU (12.95 ms per 8192
+#endif                            // queries); split with 128 items in LDS: 16 waves, 12.47 ms; at ef 384 the other way round (7.95 vs 9.19)
+// items of the results heap a split walk keeps in LDS, twice that of the candidates heap
+// (swept on one box, ef 1024 / 2048: candidates : results = 768 : 384 46 / 94 ms, 128 : 768 47 / 95, 256 : 1024
+// 50 / 107, 256 : 2048 51 / 124, 1024 : 2048 58 / 152 — waves in flight beat heap levels in LDS)
+// (after heap_push_run_min the split hardly matters: 128 : 1024, 64 : 1088, 256 : 896, 384 : 768 all within 2 % of this)
+#ifndef VG_SPLIT_F32_LDS_EF
+#define VG_SPLIT_F32_LDS_EF 128
+#endif
+#ifndef VG_SPLIT_PQ_LDS_EF
+#define VG_SPLIT_PQ_LDS_EF 128
+#endif
 #define VG_HNSW_ATTR __attribute__((amdgpu_waves_per_eu(SPLIT ? (PQM ? VG_SPLIT_PQ_WAVES : VG_SPLIT_F32_WAVES) : (PQM == 2 ? VG_LDS_PQ_WAVES : 1), SPLIT ? (PQM ? VG_SPLIT_PQ_WAVES : VG_SPLIT_F32_WAVES) : 8)))
 // UK: the metric is not Dot, so every distance is >= +0 and the heaps compare bit patterns (heap_sift_down_uk).
 // PQM: 0 = fp32 rows, 1 = PQ codes scored from the query's table, 2 = PQ codes scored from the codebook (direct form)
@@ -96,9 +118,6 @@ __global__ __launch_bounds__(64) VG_HNSW_ATTR void hnsw_search_kernel(
     float *nb_bnd = nb_pair + 64;
     float *qprep = nb_bnd + 64;  // PQ direct form: (pq_m / 2) * 20 floats (a multiple of 8 bytes)
     // fp32 rows with split heaps: the query itself (dim floats, padded to 16 bytes) — F32ScorerT<true>
-#ifndef VG_SPLIT_F32_QLDS
-#define VG_SPLIT_F32_QLDS 1
-#endif
     constexpr bool kQLds = !PQ && SPLIT && VG_SPLIT_F32_QLDS;
     const int qwords = PQ ? (PQM == 2 ? (pq_m >> 1) * kPqPairFloats : 0) : (kQLds ? ((dim + 3) & ~3) : 0);
     HItem *heaps = reinterpret_cast<HItem *>(qprep + qwords);
@@ -820,16 +839,6 @@ VG_API int32_t vg_index_set_vamana_graph(vg_index *idx, int32_t r, const uint32_
     return VG_OK;
 }
 
-// Per-query scratch of the graph searches (visited bitmap, HBM part of the heaps, exploration heap) is carved from
-// the arena for as many queries as fit under this cap; the rest of the batch goes into further launches.  1 GiB (r02)
-// cut 8192 Vamana queries over 1M nodes (650 KB each) into 5 launches of 1650 wavefronts — fewer than the 3072 the
-// chip holds.  1/16 of the device's memory, at most 16 GiB.
-static int64_t graph_scratch_cap(const vg_ctx *ctx)
-{
-    const int64_t gib = int64_t(1) << 30;
-    return std::min<int64_t>(16 * gib, std::max<int64_t>(gib, ctx->hbm_bytes / 16));
-}
-
 static int32_t search_hnsw_impl(vg_index *idx, bool pq, const float *queries, int64_t nq, int32_t k, int32_t ef,
                                 uint32_t *ids, float *scores, vg_search_stats *stats, void *stream,
                                 const uint8_t *mask = nullptr, int64_t mask_stride = 0, double selectivity = 0.0)
@@ -856,57 +865,28 @@ static int32_t search_hnsw_impl(vg_index *idx, bool pq, const float *queries, in
         if (expanded < 1) expanded = 1;
         ef = static_cast<int32_t>(expanded);
     }
-    VG_HIP(hipSetDevice(idx->ctx->device));
-    hipStream_t st = vg::pick_stream(idx->ctx, stream);
-    vg::DevIn<float> q;
-    vg::DevOut<uint32_t> oid;
-    vg::DevOut<float> osc;
-    vg::DevOut<vg_search_stats> ost;
-    VG_TRY(q.init(queries, static_cast<size_t>(nq) * idx->dim, st));
-    VG_TRY(oid.init(ids, static_cast<size_t>(nq) * k, st));
-    VG_TRY(osc.init(scores, static_cast<size_t>(nq) * k, st));
-    VG_TRY(ost.init(stats, stats ? static_cast<size_t>(nq) : 0, st));
-    vg::DevIn<uint8_t> mk;
-    const int64_t mask_bytes = (idx->n + 7) / 8;
-    VG_TRY(mk.init(mask, mask ? static_cast<size_t>(mask_stride ? (nq - 1) * mask_stride + mask_bytes : mask_bytes) : 0, st));
-    const int64_t vis_words = (idx->n + 31) / 32;
+    vg::WalkIO io;
+    VG_TRY(io.init(idx->ctx, stream, queries, static_cast<size_t>(nq) * idx->dim, ids, scores, static_cast<size_t>(nq) * k, stats, nq, mask,
+                   vg::mask_span(mask, mask_stride, nq, idx->n)));
+    hipStream_t st = io.st;
     const int pq_m = pq ? idx->pq->m : 0;
-    // heaps in LDS up to kHnswLdsEf (12 KiB per query: the waves of a CU are then bounded by registers, not
-    // LDS), beyond it split between those 12 KiB (the top levels) and HBM scratch
-    // split heaps: waves in flight beat heap levels in LDS.  The PQ walk (3.75 KiB of query constants in LDS): 128 items
-    // = 7.4 KiB per query, 16 waves per CU: ef 1024 / 2048 40.7 / 81.9 -> 35.6 / 68.5 ms per 8192 queries against 256 items
-    // (15 waves); the fp32 walk (the query itself in LDS): 128 items as well
-#ifndef VG_PQ_LDS_HEAPS_MAX
-#define VG_PQ_LDS_HEAPS_MAX 448  // PQ walk: all-LDS heaps at ef 512 are 16.7 KiB per query = 9 waves per CU (12.95 ms per 8192
-#endif                            // queries); split with 128 items in LDS: 16 waves, 12.47 ms; at ef 384 the other way round (7.95 vs 9.19)
     // (a post-filter walk capped at 500 may keep more results than it walked with: the heaps are sized for the larger)
     const int ef_walk = ef;
     if (ef_keep > ef) ef = ef_keep;
     const bool lds_heaps = ef <= (pq ? VG_PQ_LDS_HEAPS_MAX : vg::kHnswLdsEf);
-    // (swept on one box, ef 1024 / 2048: candidates : results = 768 : 384 46 / 94 ms, 128 : 768 47 / 95, 256 : 1024
-    // 50 / 107, 256 : 2048 51 / 124, 1024 : 2048 58 / 152 — waves in flight beat heap levels in LDS)
-#ifndef VG_SPLIT_F32_LDS_EF
-#define VG_SPLIT_F32_LDS_EF 128
-#endif
-#ifndef VG_SPLIT_PQ_LDS_EF
-#define VG_SPLIT_PQ_LDS_EF 128
-#endif
     const int lds_ef = pq ? VG_SPLIT_PQ_LDS_EF : VG_SPLIT_F32_LDS_EF;
-    // (after heap_push_run_min the split hardly matters: 128 : 1024, 64 : 1088, 256 : 896, 384 : 768 all within 2 % of this)
     const int lds_cand = 2 * lds_ef, lds_res = lds_ef;
     const int64_t heap_bytes = lds_heaps ? 0 : static_cast<int64_t>(3) * ef * sizeof(vg::HItem);
     // sub-dimension 8: node terms straight from the codebook (vg_hnsw_layer.hpp PqScorer), no per-query table
     const bool pq_direct = pq && idx->pq->subdim == 8 && (reinterpret_cast<uintptr_t>(idx->pq->d_codebooks) & 7) == 0;
     const int64_t lut_bytes = pq_direct ? 0 : static_cast<int64_t>(pq_m) * 256 * sizeof(float);
-    int64_t chunk = std::max<int64_t>(1, graph_scratch_cap(idx->ctx) / std::max<int64_t>(vis_words * 4 + heap_bytes + lut_bytes, 1));
-    chunk = std::min(chunk, nq);
+    vg::WalkChunks wc(vg::scratch_cap(idx->ctx), heap_bytes + lut_bytes, idx->n, nq);
     vg::ArenaCall ar(idx->ctx, st);
-    const int i_vis = ar.add(sizeof(uint32_t) * static_cast<size_t>(chunk) * vis_words);
-    const int i_heap = ar.add(static_cast<size_t>(chunk) * heap_bytes);
-    const int i_luts = ar.add(static_cast<size_t>(chunk) * lut_bytes);
-    const int i_redo = ar.add(static_cast<size_t>(chunk));
+    wc.add(ar);
+    const int i_heap = ar.add(static_cast<size_t>(wc.chunk) * heap_bytes);
+    const int i_luts = ar.add(static_cast<size_t>(wc.chunk) * lut_bytes);
+    const int i_redo = ar.add(static_cast<size_t>(wc.chunk));
     VG_TRY(ar.commit());
-    struct { uint32_t *ptr; } vis{ar.get<uint32_t>(i_vis)};
     vg::HItem *heap_ws = lds_heaps ? nullptr : ar.get<vg::HItem>(i_heap);
     float *luts = pq && !pq_direct ? ar.get<float>(i_luts) : nullptr;
     // + 4 items: heap_sift_down_uk reads slots fc .. fc+3 whatever the heap's length
@@ -928,37 +908,30 @@ static int32_t search_hnsw_impl(vg_index *idx, bool pq, const float *queries, in
                                static_cast<int>(lds)));
     VG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern_f32), hipFuncAttributeMaxDynamicSharedMemorySize,
                                static_cast<int>(lds)));
-    for (int64_t q0 = 0; q0 < nq; q0 += chunk) {
-        const int64_t cnt = std::min(chunk, nq - q0);
-        VG_HIP(hipMemsetAsync(vis.ptr, 0, static_cast<size_t>(cnt) * vis_words * 4, st));
-        if (luts) VG_TRY(vg::launch_pq_build_table(idx->pq, q.ptr + q0 * idx->dim, cnt, luts, false, st));
+    VG_TRY(wc.for_each(st, [&](int64_t q0, int64_t cnt) -> int32_t {
+        if (luts) VG_TRY(vg::launch_pq_build_table(idx->pq, io.q.ptr + q0 * idx->dim, cnt, luts, false, st));
         // a graph with tombstones: every query takes the pass that walks as the reference writes it (float comparisons, each lane
         // at its turn) and reads the bitmap — the fast pass is tuned to its register budget without it
         VG_HIP(hipMemsetAsync(redo, idx->d_hnsw_tomb ? 1 : 0, static_cast<size_t>(cnt), st));
+        auto launch = [&](auto kernel) -> int32_t {
+            VG_LAUNCH(kernel, dim3(static_cast<unsigned>(cnt)), dim3(64), lds, st, idx->d_vectors, idx->n, idx->dim,
+                      idx->metric, idx->d_hnsw_l0, idx->hnsw_m0, idx->hnsw_max_level, idx->hnsw_m, idx->d_hnsw_slot,
+                      idx->d_hnsw_adj, idx->d_hnsw_level_off, idx->hnsw_entry, io.q.ptr + q0 * idx->dim,
+                      pq ? idx->d_pq_rows : nullptr, pq_m, luts, pq_direct ? idx->pq->d_codebooks : nullptr,
+                      pq ? idx->pq->d_scales : nullptr, pq ? idx->pq->d_offsets : nullptr, k, ef_walk, lds_cand, lds_res, wc.vis(),
+                      wc.vis_words, heap_ws, io.oid.ptr + q0 * k, io.osc.ptr + q0 * k, io.stats_at(q0), redo,
+                      io.mk.ptr ? io.mk.ptr + q0 * mask_stride : nullptr, mask_stride, ef_keep, idx->d_hnsw_tomb);
+            return VG_OK;
+        };
         if (!idx->d_hnsw_tomb) {
             vg::ProfScope prof(idx->ctx, pq ? "hnsw_search_pq" : "hnsw_search", st);
-            VG_LAUNCH(kern, dim3(static_cast<unsigned>(cnt)), dim3(64), lds, st, idx->d_vectors, idx->n, idx->dim,
-                      idx->metric, idx->d_hnsw_l0, idx->hnsw_m0, idx->hnsw_max_level, idx->hnsw_m, idx->d_hnsw_slot,
-                      idx->d_hnsw_adj, idx->d_hnsw_level_off, idx->hnsw_entry, q.ptr + q0 * idx->dim,
-                      pq ? idx->d_pq_rows : nullptr, pq_m, luts, pq_direct ? idx->pq->d_codebooks : nullptr,
-                      pq ? idx->pq->d_scales : nullptr, pq ? idx->pq->d_offsets : nullptr, k, ef_walk, lds_cand, lds_res, vis.ptr,
-                      vis_words, heap_ws, oid.ptr + q0 * k, osc.ptr + q0 * k, ost.ptr ? ost.ptr + q0 : nullptr, redo,
-                      mk.ptr ? mk.ptr + q0 * mask_stride : nullptr, mask_stride, ef_keep, idx->d_hnsw_tomb);
+            VG_TRY(launch(kern));
         }
         // (every workgroup of an ordinary batch leaves at its first instruction)
         vg::ProfScope prof_strict(idx->ctx, idx->d_hnsw_tomb ? (pq ? "hnsw_search_pq" : "hnsw_search") : "hnsw_search_redo", st);
-        VG_LAUNCH(kern_f32, dim3(static_cast<unsigned>(cnt)), dim3(64), lds, st, idx->d_vectors, idx->n, idx->dim,
-                      idx->metric, idx->d_hnsw_l0, idx->hnsw_m0, idx->hnsw_max_level, idx->hnsw_m, idx->d_hnsw_slot,
-                      idx->d_hnsw_adj, idx->d_hnsw_level_off, idx->hnsw_entry, q.ptr + q0 * idx->dim,
-                      pq ? idx->d_pq_rows : nullptr, pq_m, luts, pq_direct ? idx->pq->d_codebooks : nullptr,
-                      pq ? idx->pq->d_scales : nullptr, pq ? idx->pq->d_offsets : nullptr, k, ef_walk, lds_cand, lds_res, vis.ptr,
-                      vis_words, heap_ws, oid.ptr + q0 * k, osc.ptr + q0 * k, ost.ptr ? ost.ptr + q0 : nullptr, redo,
-                      mk.ptr ? mk.ptr + q0 * mask_stride : nullptr, mask_stride, ef_keep, idx->d_hnsw_tomb);
-    }
-    VG_TRY(oid.finish());
-    VG_TRY(osc.finish());
-    VG_TRY(ost.finish());
-    return VG_OK;
+        return launch(kern_f32);
+    }));
+    return io.finish();
 }
 
 VG_API int32_t vg_search_hnsw(vg_index *idx, const float *queries, int64_t nq, int32_t k, int32_t ef,
@@ -983,56 +956,27 @@ VG_API int32_t vg_search_hnsw_filtered(vg_index *idx, const float *queries, int6
     // at or below it (0 = unknown) the predicate-aware walk (searchLayerPredicateAware, :1406; k_hnsw_predicate.hip), no tombstones
     if (!(selectivity > 0.3))
         return vg_search_hnsw_predicate(idx, queries, nq, k, ef, mask, mask_stride, nullptr, ids, scores, stats, stream);
-    const int64_t mask_bytes = (idx->n + 7) / 8;
-    VG_CHECK(mask_stride == 0 || mask_stride >= mask_bytes, VG_ERR_INVALID_ARG,
-             "vg_search_hnsw_filtered: mask_stride %lld is shorter than a mask (%lld bytes)", static_cast<long long>(mask_stride),
-             static_cast<long long>(mask_bytes));
+    VG_CHECK_MASK_STRIDE("vg_search_hnsw_filtered", mask, mask_stride, idx->n);
     return search_hnsw_impl(idx, false, queries, nq, k, ef, ids, scores, stats, stream, mask, mask_stride, selectivity);
 }
 
-static int32_t vamana_impl(vg_index *idx, const float *queries, int64_t nq, int32_t k, int32_t kind, const uint8_t *mask,
-                           int64_t mask_stride, uint32_t *ids, float *scores, vg_search_stats *stats, void *stream,
-                           const float *thresholds = nullptr, int32_t *counts = nullptr);
-
-VG_API int32_t vg_search_vamana(vg_index *idx, const float *queries, int64_t nq, int32_t k, int32_t kind,
-                                uint32_t *ids, float *scores, vg_search_stats *stats, void *stream)
+// the scorer instance of a Vamana walk (vamana_search_kernel's `kind`) as a compile-time constant: f(integral_constant<int, K>)
+template <class F>
+static int32_t with_vamana_kind(int inst, F f)
 {
-    return vamana_impl(idx, queries, nq, k, kind, nullptr, 0, ids, scores, stats, stream);
-}
-
-VG_API int32_t vg_search_vamana_filtered(vg_index *idx, const float *queries, int64_t nq, int32_t k, int32_t kind,
-                                         const uint8_t *mask, int64_t mask_stride, uint32_t *ids, float *scores,
-                                         vg_search_stats *stats, void *stream)
-{
-    VG_CHECK(idx, VG_ERR_INVALID_ARG, "vg_search_vamana_filtered: NULL index");
-    const int64_t mask_bytes = (idx->n + 7) / 8;
-    VG_CHECK(mask == nullptr || mask_stride == 0 || mask_stride >= mask_bytes, VG_ERR_INVALID_ARG,
-             "vg_search_vamana_filtered: mask_stride %lld is shorter than a mask (%lld bytes)", static_cast<long long>(mask_stride),
-             static_cast<long long>(mask_bytes));
-    return vamana_impl(idx, queries, nq, k, kind, mask, mask_stride, ids, scores, stats, stream);
-}
-
-// Engine.SearchThreshold's DiskANN leg (engine/engine.go:1485-1531): Search(q, max_results), then the engine's filter in order
-VG_API int32_t vg_search_vamana_threshold(vg_index *idx, const float *queries, int64_t nq, const float *thresholds,
-                                          int32_t max_results, int32_t kind, const uint8_t *mask, int64_t mask_stride, uint32_t *ids,
-                                          float *scores, int32_t *counts, vg_search_stats *stats, void *stream)
-{
-    VG_CHECK(idx, VG_ERR_INVALID_ARG, "vg_search_vamana_threshold: NULL index");
-    VG_CHECK(nq >= 0 && max_results >= 0, VG_ERR_INVALID_ARG, "vg_search_vamana_threshold: negative nq or max_results");
-    VG_CHECK(max_results <= vg::kVamanaHugeMaxK, VG_ERR_UNSUPPORTED, "vg_search_vamana_threshold: max_results=%d exceeds %d",
-             max_results, vg::kVamanaHugeMaxK);
-    if (nq == 0 || max_results == 0) return VG_OK;
-    VG_CHECK(thresholds && counts, VG_ERR_INVALID_ARG, "vg_search_vamana_threshold: NULL buffer");
-    const int64_t mask_bytes = (idx->n + 7) / 8;
-    VG_CHECK(mask == nullptr || mask_stride == 0 || mask_stride >= mask_bytes, VG_ERR_INVALID_ARG,
-             "vg_search_vamana_threshold: mask_stride %lld is shorter than a mask (%lld bytes)", static_cast<long long>(mask_stride),
-             static_cast<long long>(mask_bytes));
-    return vamana_impl(idx, queries, nq, max_results, kind, mask, mask_stride, ids, scores, stats, stream, thresholds, counts);
+    switch (inst) {
+    case 0: return f(std::integral_constant<int, 0>{});
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 4: return f(std::integral_constant<int, 4>{});
+    case 5: return f(std::integral_constant<int, 5>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    default: return f(std::integral_constant<int, 3>{});
+    }
 }
 
 static int32_t vamana_impl(vg_index *idx, const float *queries, int64_t nq, int32_t k, int32_t kind, const uint8_t *mask,
                            int64_t mask_stride, uint32_t *ids, float *scores, vg_search_stats *stats, void *stream,
-                           const float *thresholds, int32_t *counts)
+                           const float *thresholds = nullptr, int32_t *counts = nullptr)
 {
     VG_CHECK(idx, VG_ERR_INVALID_ARG, "vg_search_vamana: NULL index");
     VG_CHECK(nq >= 0 && k >= 0, VG_ERR_INVALID_ARG, "vg_search_vamana: negative nq or k");
@@ -1049,23 +993,14 @@ static int32_t vamana_impl(vg_index *idx, const float *queries, int64_t nq, int3
     VG_CHECK(queries && ids && scores, VG_ERR_INVALID_ARG, "vg_search_vamana: NULL buffer");
     VG_CHECK(k <= vg::kVamanaHugeMaxK, VG_ERR_UNSUPPORTED, "vg_search_vamana: k=%d exceeds %d", k, vg::kVamanaHugeMaxK);
     const bool huge = k > vg::kVamanaMaxK;
-    VG_HIP(hipSetDevice(idx->ctx->device));
-    hipStream_t st = vg::pick_stream(idx->ctx, stream);
-    vg::DevIn<float> q;
-    vg::DevOut<uint32_t> oid;
-    vg::DevOut<float> osc;
-    vg::DevOut<vg_search_stats> ost;
-    VG_TRY(q.init(queries, static_cast<size_t>(nq) * idx->dim, st));
-    VG_TRY(oid.init(ids, static_cast<size_t>(nq) * k, st));
-    VG_TRY(osc.init(scores, static_cast<size_t>(nq) * k, st));
-    VG_TRY(ost.init(stats, stats ? static_cast<size_t>(nq) : 0, st));
-    vg::DevIn<uint8_t> mk;
-    VG_TRY(mk.init(mask, mask ? static_cast<size_t>(mask_stride ? (nq - 1) * mask_stride + (idx->n + 7) / 8 : (idx->n + 7) / 8) : 0, st));
+    vg::WalkIO io;
+    VG_TRY(io.init(idx->ctx, stream, queries, static_cast<size_t>(nq) * idx->dim, ids, scores, static_cast<size_t>(nq) * k, stats, nq, mask,
+                   vg::mask_span(mask, mask_stride, nq, idx->n)));
+    hipStream_t st = io.st;
     vg::DevIn<float> thr;  // vg_search_vamana_threshold
     vg::DevOut<int32_t> ocnt;
     VG_TRY(thr.init(thresholds, thresholds ? static_cast<size_t>(nq) : 0, st));
     VG_TRY(ocnt.init(counts, thresholds ? static_cast<size_t>(nq) : 0, st));
-    const int64_t vis_words = (idx->n + 31) / 32;
     // The reference's exploration heap is unbounded (ScratchCandidates, diskann/segment.go:641-703).  A node enters it at most once
     // (the visited test), so n items are "unbounded" here.  The unfiltered walk stops at k results long before 65 536; a walk with a
     // selective row filter goes on until k MATCHING rows are found and can fill any smaller heap (pushes were then
@@ -1073,14 +1008,12 @@ static int32_t vamana_impl(vg_index *idx, const float *queries, int64_t nq, int3
     // k > 512 walks past 65 536 candidates (the 1M x 768 graph at k = 16384: DESIGN.md): n items here too, followed by the HBM part
     // of the k-item result heap (the kernel's ccap)
     const int64_t cand_cap = huge ? idx->n + k : mask ? idx->n : std::min<int64_t>(idx->n, 65536);
-    const int64_t per_query = vis_words * 4 + cand_cap * 8;
-    const int64_t scratch_cap = huge && vg::hook(vg::kHookVamanaSmallScratch) ? int64_t(64) << 20 : graph_scratch_cap(idx->ctx);
-    int64_t chunk = std::max<int64_t>(1, scratch_cap / per_query);
-    chunk = std::min(chunk, nq);
+    vg::WalkChunks wc(huge && vg::hook(vg::kHookVamanaSmallScratch) ? int64_t(64) << 20 : vg::scratch_cap(idx->ctx), cand_cap * 8, idx->n, nq);
+    const int64_t chunk = wc.chunk;
     const int rq_nb = ((idx->dim + 63) / 64) * 8;
     const int pq_m = idx->pq ? idx->pq->m : 0;
     vg::ArenaCall ar(idx->ctx, st);
-    const int i_vis = ar.add(sizeof(uint32_t) * static_cast<size_t>(chunk) * vis_words);
+    wc.add(ar);
     const int i_cand = ar.add(sizeof(vg::HItem) * static_cast<size_t>(chunk) * cand_cap);
     const bool pq_direct = kind == 1 && idx->pq->subdim == 8 && (reinterpret_cast<uintptr_t>(idx->pq->d_codebooks) & 7) == 0;
     // INT4: terms evaluated in place when the rows are whole 32-element blocks (16-byte aligned codes)
@@ -1092,96 +1025,89 @@ static int32_t vamana_impl(vg_index *idx, const float *queries, int64_t nq, int3
     VG_TRY(ar.commit());
     int *lcnt = ar.get<int>(i_lcnt);
     if (huge) VG_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(lcnt), k, static_cast<size_t>(chunk), st));
-    struct { uint32_t *ptr; } vis{ar.get<uint32_t>(i_vis)};
-    struct { vg::HItem *ptr; } cand{ar.get<vg::HItem>(i_cand)};
-    struct { float *ptr; } luts{ar.get<float>(i_luts)};
-    struct { uint8_t *ptr; } qcodes{ar.get<uint8_t>(i_qcodes)};
+    vg::HItem *cand = ar.get<vg::HItem>(i_cand);
+    float *luts = ar.get<float>(i_luts);
+    uint8_t *qcodes = ar.get<uint8_t>(i_qcodes);
     if (kind == 1 && !pq_direct) {
-        VG_TRY(vg::launch_pq_build_table(idx->pq, q.ptr, nq, luts.ptr, false, st));
+        VG_TRY(vg::launch_pq_build_table(idx->pq, io.q.ptr, nq, luts, false, st));
     }
     if (kind == 2) {
-        VG_TRY(vg::launch_rabitq_encode(q.ptr, nq, idx->dim, qcodes.ptr, st));
+        VG_TRY(vg::launch_rabitq_encode(io.q.ptr, nq, idx->dim, qcodes, st));
     }
-    for (int64_t q0 = 0; q0 < nq; q0 += chunk) {
-        const int64_t cnt = std::min(chunk, nq - q0);
-        VG_HIP(hipMemsetAsync(vis.ptr, 0, static_cast<size_t>(cnt) * vis_words * 4, st));
+    const bool big = k > 64;
+    const int inst = pq_direct ? vg::kVamanaPQDirect : int4_direct ? vg::kVamanaInt4Direct : kind;
+    // what a launch keeps in LDS besides its heap: the direct PQ form's query constants, RaBitQ's query code
+    const size_t scorer_lds = pq_direct ? static_cast<size_t>(pq_m >> 1) * vg::kPqPairFloats * sizeof(float) : (kind == 2 ? static_cast<size_t>(rq_nb) : 0);
+    VG_TRY(wc.for_each(st, [&](int64_t q0, int64_t cnt) -> int32_t {
         vg::ProfScope prof(idx->ctx, "vamana_search", st);
         // (the STRICT pass of a large-k walk keeps its k-item CandidateHeap after the query's image: extra_lds)
         auto launch = [&](auto kernel, size_t extra_lds = 0) -> int32_t {
-            VG_LAUNCH(kernel, dim3(static_cast<unsigned>(cnt)), dim3(64),
-                      (pq_direct ? static_cast<size_t>(pq_m >> 1) * vg::kPqPairFloats * sizeof(float) : (kind == 2 ? static_cast<size_t>(rq_nb) : 0)) + extra_lds, st,
+            VG_LAUNCH(kernel, dim3(static_cast<unsigned>(cnt)), dim3(64), scorer_lds + extra_lds, st,
                       idx->metric, idx->n, idx->dim, idx->d_vamana, idx->vamana_r, idx->vamana_entry,
-                      idx->d_vectors, idx->d_pq_rows, pq_m, kind == 1 && !pq_direct ? luts.ptr + q0 * pq_m * 256 : nullptr,
+                      idx->d_vectors, idx->d_pq_rows, pq_m, kind == 1 && !pq_direct ? luts + q0 * pq_m * 256 : nullptr,
                       pq_direct ? idx->pq->d_codebooks : nullptr, idx->pq ? idx->pq->d_scales : nullptr,
                       idx->pq ? idx->pq->d_offsets : nullptr,
-                      idx->d_rq_rows, kind == 2 ? qcodes.ptr + q0 * (rq_nb + 4) : nullptr, rq_nb,
-                      idx->d_int4_rows, idx->int4_table, idx->int4_min, idx->int4_diff, q.ptr + q0 * idx->dim, k, cand.ptr, cand_cap, vis.ptr, vis_words, oid.ptr + q0 * k,
-                      osc.ptr + q0 * k, ost.ptr ? ost.ptr + q0 : nullptr, mk.ptr ? mk.ptr + q0 * mask_stride : nullptr, mask_stride,
+                      idx->d_rq_rows, kind == 2 ? qcodes + q0 * (rq_nb + 4) : nullptr, rq_nb,
+                      idx->d_int4_rows, idx->int4_table, idx->int4_min, idx->int4_diff, io.q.ptr + q0 * idx->dim, k, cand, cand_cap, wc.vis(), wc.vis_words, io.oid.ptr + q0 * k,
+                      io.osc.ptr + q0 * k, io.stats_at(q0), io.mk.ptr ? io.mk.ptr + q0 * mask_stride : nullptr, mask_stride,
                       kind == 0 ? idx->d_norm_max + 1 : kind == 2 ? idx->d_rq_norms + idx->n : nullptr);
             return VG_OK;
         };
-        const bool big = k > 64;
-        int32_t rc;
-        const int inst = pq_direct ? vg::kVamanaPQDirect : int4_direct ? vg::kVamanaInt4Direct : kind;
-#define VG_VAMANA_CASE(K)                                                                                                   \
-    case K:                                                                                                                 \
-        rc = huge ? (mk.ptr ? launch(vg::vamana_search_kernel<K, true, true, false, true>) : launch(vg::vamana_search_kernel<K, true, false, false, true>)) \
-           : mk.ptr ? (big ? launch(vg::vamana_search_kernel<K, true, true>) : launch(vg::vamana_search_kernel<K, false, true>)) \
-                    : (big ? launch(vg::vamana_search_kernel<K, true>) : launch(vg::vamana_search_kernel<K, false>));       \
-        break;
-        switch (inst) {
-            VG_VAMANA_CASE(0)
-            VG_VAMANA_CASE(1)
-            VG_VAMANA_CASE(4)
-            VG_VAMANA_CASE(5)
-            VG_VAMANA_CASE(2)
-        default:
-            rc = huge ? (mk.ptr ? launch(vg::vamana_search_kernel<3, true, true, false, true>) : launch(vg::vamana_search_kernel<3, true, false, false, true>))
-               : mk.ptr ? (big ? launch(vg::vamana_search_kernel<3, true, true>) : launch(vg::vamana_search_kernel<3, false, true>))
-                        : (big ? launch(vg::vamana_search_kernel<3, true>) : launch(vg::vamana_search_kernel<3, false>));
-            break;
-        }
-#undef VG_VAMANA_CASE
-        VG_TRY(rc);
-        if (huge)  // each query's heap, as a list of k keys in its scratch, best first into ids / scores
-            VG_TRY(vg::launch_thr_select_lists(idx->metric != VG_METRIC_L2, reinterpret_cast<const uint64_t *>(cand.ptr + (cand_cap - k)),
-                                               cand_cap, lcnt, cnt, k, oid.ptr + q0 * k, osc.ptr + q0 * k, lcnt + chunk, st));
-        // the queries whose distances may hold a NaN, again with the reference's CandidateHeap (every other query returns at once)
-        if (!vg::hook(vg::kHookNoCandReplay) && huge) {
-            const size_t heap_lds = sizeof(vg::CItem) * static_cast<size_t>(k);
-            auto strict = [&](auto kernel) -> int32_t {
-                const size_t lds = heap_lds + (pq_direct ? static_cast<size_t>(pq_m >> 1) * vg::kPqPairFloats * sizeof(float)
-                                                         : (kind == 2 ? static_cast<size_t>(rq_nb) : 0));
+        // the walk's kernel for scorer K; strict: the pass with the reference's CandidateHeap, which at large k keeps its k items in LDS
+        auto walk = [&](auto kind_c, bool strict) -> int32_t {
+            constexpr int K = decltype(kind_c)::value;
+            if (strict && huge) {
+                const size_t heap_lds = sizeof(vg::CItem) * static_cast<size_t>(k);
+                auto kernel = vg::vamana_search_kernel<K, true, true, true, true>;
                 VG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           static_cast<int>(lds)));
+                                           static_cast<int>(heap_lds + scorer_lds)));
                 return launch(kernel, heap_lds);
-            };
-            switch (inst) {
-            case 0: rc = strict(vg::vamana_search_kernel<0, true, true, true, true>); break;
-            case 1: rc = strict(vg::vamana_search_kernel<1, true, true, true, true>); break;
-            case 4: rc = strict(vg::vamana_search_kernel<4, true, true, true, true>); break;
-            case 5: rc = strict(vg::vamana_search_kernel<5, true, true, true, true>); break;
-            case 2: rc = strict(vg::vamana_search_kernel<2, true, true, true, true>); break;
-            default: rc = strict(vg::vamana_search_kernel<3, true, true, true, true>); break;
             }
-            VG_TRY(rc);
-        } else if (!vg::hook(vg::kHookNoCandReplay)) {
-            switch (inst) {
-            case 0: rc = launch(vg::vamana_search_kernel<0, true, true, true>); break;
-            case 1: rc = launch(vg::vamana_search_kernel<1, true, true, true>); break;
-            case 4: rc = launch(vg::vamana_search_kernel<4, true, true, true>); break;
-            case 5: rc = launch(vg::vamana_search_kernel<5, true, true, true>); break;
-            case 2: rc = launch(vg::vamana_search_kernel<2, true, true, true>); break;
-            default: rc = launch(vg::vamana_search_kernel<3, true, true, true>); break;
-            }
-            VG_TRY(rc);
-        }
-    }
+            if (strict) return launch(vg::vamana_search_kernel<K, true, true, true>);
+            if (huge) return io.mk.ptr ? launch(vg::vamana_search_kernel<K, true, true, false, true>) : launch(vg::vamana_search_kernel<K, true, false, false, true>);
+            if (io.mk.ptr) return big ? launch(vg::vamana_search_kernel<K, true, true>) : launch(vg::vamana_search_kernel<K, false, true>);
+            return big ? launch(vg::vamana_search_kernel<K, true>) : launch(vg::vamana_search_kernel<K, false>);
+        };
+        VG_TRY(with_vamana_kind(inst, [&](auto kind_c) { return walk(kind_c, false); }));
+        if (huge)  // each query's heap, as a list of k keys in its scratch, best first into ids / scores
+            VG_TRY(vg::launch_thr_select_lists(idx->metric != VG_METRIC_L2, reinterpret_cast<const uint64_t *>(cand + (cand_cap - k)),
+                                               cand_cap, lcnt, cnt, k, io.oid.ptr + q0 * k, io.osc.ptr + q0 * k, lcnt + chunk, st));
+        // the queries whose distances may hold a NaN, again with the reference's CandidateHeap (every other query returns at once)
+        if (!vg::hook(vg::kHookNoCandReplay)) VG_TRY(with_vamana_kind(inst, [&](auto kind_c) { return walk(kind_c, true); }));
+        return VG_OK;
+    }));
     // vg_search_vamana_threshold: the engine's filter over each query's list, in order (engine.go:1518-1529)
-    if (thresholds) VG_TRY(vg::launch_thr_filter(idx->metric != VG_METRIC_L2, thr.ptr, nq, k, oid.ptr, osc.ptr, ocnt.ptr, st));
-    VG_TRY(oid.finish());
-    VG_TRY(osc.finish());
-    VG_TRY(ost.finish());
-    VG_TRY(ocnt.finish());
-    return VG_OK;
+    if (thresholds) VG_TRY(vg::launch_thr_filter(idx->metric != VG_METRIC_L2, thr.ptr, nq, k, io.oid.ptr, io.osc.ptr, ocnt.ptr, st));
+    VG_TRY(io.finish());
+    return ocnt.finish();
+}
+
+VG_API int32_t vg_search_vamana(vg_index *idx, const float *queries, int64_t nq, int32_t k, int32_t kind,
+                                uint32_t *ids, float *scores, vg_search_stats *stats, void *stream)
+{
+    return vamana_impl(idx, queries, nq, k, kind, nullptr, 0, ids, scores, stats, stream);
+}
+
+VG_API int32_t vg_search_vamana_filtered(vg_index *idx, const float *queries, int64_t nq, int32_t k, int32_t kind,
+                                         const uint8_t *mask, int64_t mask_stride, uint32_t *ids, float *scores,
+                                         vg_search_stats *stats, void *stream)
+{
+    VG_CHECK(idx, VG_ERR_INVALID_ARG, "vg_search_vamana_filtered: NULL index");
+    VG_CHECK_MASK_STRIDE("vg_search_vamana_filtered", mask, mask_stride, idx->n);
+    return vamana_impl(idx, queries, nq, k, kind, mask, mask_stride, ids, scores, stats, stream);
+}
+
+// Engine.SearchThreshold's DiskANN leg (engine/engine.go:1485-1531): Search(q, max_results), then the engine's filter in order
+VG_API int32_t vg_search_vamana_threshold(vg_index *idx, const float *queries, int64_t nq, const float *thresholds,
+                                          int32_t max_results, int32_t kind, const uint8_t *mask, int64_t mask_stride, uint32_t *ids,
+                                          float *scores, int32_t *counts, vg_search_stats *stats, void *stream)
+{
+    VG_CHECK(idx, VG_ERR_INVALID_ARG, "vg_search_vamana_threshold: NULL index");
+    VG_CHECK(nq >= 0 && max_results >= 0, VG_ERR_INVALID_ARG, "vg_search_vamana_threshold: negative nq or max_results");
+    VG_CHECK(max_results <= vg::kVamanaHugeMaxK, VG_ERR_UNSUPPORTED, "vg_search_vamana_threshold: max_results=%d exceeds %d",
+             max_results, vg::kVamanaHugeMaxK);
+    if (nq == 0 || max_results == 0) return VG_OK;
+    VG_CHECK(thresholds && counts, VG_ERR_INVALID_ARG, "vg_search_vamana_threshold: NULL buffer");
+    VG_CHECK_MASK_STRIDE("vg_search_vamana_threshold", mask, mask_stride, idx->n);
+    return vamana_impl(idx, queries, nq, max_results, kind, mask, mask_stride, ids, scores, stats, stream, thresholds, counts);
 }

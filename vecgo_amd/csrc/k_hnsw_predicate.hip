@@ -15,6 +15,7 @@
 #include "vg_exact.hpp"
 #include "vg_hnsw_layer.hpp"
 #include "vg_internal.hpp"
+#include "vg_search.hpp"
 
 namespace vg {
 
@@ -295,71 +296,51 @@ VG_API int32_t vg_search_hnsw_predicate(vg_index *idx, const float *queries, int
     VG_CHECK(idx->d_vectors, VG_ERR_NOT_READY, "%s: index has no fp32 vectors", fn);
     VG_CHECK(idx->metric != VG_METRIC_HAMMING, VG_ERR_UNSUPPORTED, "unsupported metric for float32: Hamming");
     VG_CHECK(queries && ids && scores, VG_ERR_INVALID_ARG, "%s: NULL buffer", fn);
-    const int64_t mask_bytes = (idx->n + 7) / 8;
-    VG_CHECK(mask_stride == 0 || mask_stride >= mask_bytes, VG_ERR_INVALID_ARG, "%s: mask_stride %lld is shorter than a mask (%lld bytes)",
-             fn, static_cast<long long>(mask_stride), static_cast<long long>(mask_bytes));
+    VG_CHECK_MASK_STRIDE(fn, mask, mask_stride, idx->n);
     if (ef < k) ef = k;  // determineEF hnsw.go:1891-1894
     VG_CHECK(ef <= vg::kPredMaxEf, VG_ERR_UNSUPPORTED, "%s: ef=%d exceeds %d (the results heap lives in LDS)", fn, ef, vg::kPredMaxEf);
-    VG_HIP(hipSetDevice(idx->ctx->device));
-    hipStream_t st = vg::pick_stream(idx->ctx, stream);
+    vg::WalkIO io;
+    VG_TRY(io.init(idx->ctx, stream, queries, static_cast<size_t>(nq) * idx->dim, ids, scores, static_cast<size_t>(nq) * k, stats, nq, mask,
+                   vg::mask_span(mask, mask_stride, nq, idx->n)));
+    hipStream_t st = io.st;
     if (!idx->d_hnsw_l0_dist) VG_TRY(vg::hnsw_edge_distances(idx, nullptr, st));  // recomputed from the rows, once
-    vg::DevIn<float> q;
-    vg::DevIn<uint8_t> mk, dl;
-    vg::DevOut<uint32_t> oid;
-    vg::DevOut<float> osc;
-    vg::DevOut<vg_search_stats> ost;
-    VG_TRY(q.init(queries, static_cast<size_t>(nq) * idx->dim, st));
-    VG_TRY(mk.init(mask, static_cast<size_t>(mask_stride ? (nq - 1) * mask_stride + mask_bytes : mask_bytes), st));
-    VG_TRY(dl.init(deleted, deleted ? static_cast<size_t>(mask_bytes) : 0, st));
-    VG_TRY(oid.init(ids, static_cast<size_t>(nq) * k, st));
-    VG_TRY(osc.init(scores, static_cast<size_t>(nq) * k, st));
-    VG_TRY(ost.init(stats, stats ? static_cast<size_t>(nq) : 0, st));
-    const int64_t vis_words = (idx->n + 31) / 32;
+    vg::DevIn<uint8_t> dl;
+    VG_TRY(dl.init(deleted, deleted ? static_cast<size_t>((idx->n + 7) / 8) : 0, st));
     // The navigation queue is unbounded in the reference and can take every row (a filter nothing passes walks the whole
     // component on edge distances).  First pass: 128 k slots per query (an ordinary walk queues a few thousand nodes); a walk that
     // outgrows them stops and is run again with a slot per row, a few queries per launch (2 GiB of scratch, returned after the call)
     const int64_t cand_cap = std::min<int64_t>(idx->n, int64_t(1) << 17);
-    const int64_t per_query = vis_words * 4 + cand_cap * 8 + 1;
-    const int64_t gib = int64_t(1) << 30;
-    const int64_t scratch = std::min<int64_t>(16 * gib, std::max<int64_t>(gib, idx->ctx->hbm_bytes / 16));
-    int64_t chunk = std::max<int64_t>(1, scratch / per_query);
-    chunk = std::min(chunk, nq);
+    vg::WalkChunks wc(vg::scratch_cap(idx->ctx), cand_cap * 8 + 1, idx->n, nq);
     vg::ArenaCall ar(idx->ctx, st);
-    const int i_vis = ar.add(sizeof(uint32_t) * static_cast<size_t>(chunk) * vis_words);
-    const int i_cand = ar.add(sizeof(vg::HItem) * static_cast<size_t>(chunk) * cand_cap);
-    const int i_redo = ar.add(static_cast<size_t>(chunk));
+    wc.add(ar);
+    const int i_cand = ar.add(sizeof(vg::HItem) * static_cast<size_t>(wc.chunk) * cand_cap);
+    const int i_redo = ar.add(static_cast<size_t>(wc.chunk));
     VG_TRY(ar.commit());
     uint8_t *redo = ar.get<uint8_t>(i_redo);
     const bool second_pass = cand_cap < idx->n;
     const int64_t big_chunk = second_pass ? std::max<int64_t>(1, (int64_t(2) << 30) / (idx->n * 8)) : 0;
     vg::DevTmp<vg::HItem> big;
-    if (second_pass) VG_TRY(big.init(static_cast<size_t>(std::min(big_chunk, chunk)) * idx->n, st));
-    uint32_t *vis = ar.get<uint32_t>(i_vis);
+    if (second_pass) VG_TRY(big.init(static_cast<size_t>(std::min(big_chunk, wc.chunk)) * idx->n, st));
     vg::HItem *cand = ar.get<vg::HItem>(i_cand);
     const size_t lds = 128 * sizeof(float) + sizeof(vg::HItem) * (vg::kPredLdsCand + static_cast<size_t>(ef) + 1);
     VG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(vg::hnsw_predicate_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                static_cast<int>(lds)));
-    for (int64_t q0 = 0; q0 < nq; q0 += chunk) {
-        const int64_t cnt = std::min(chunk, nq - q0);
-        VG_HIP(hipMemsetAsync(vis, 0, static_cast<size_t>(cnt) * vis_words * 4, st));
+    VG_TRY(wc.for_each(st, [&](int64_t q0, int64_t cnt) -> int32_t {
         VG_HIP(hipMemsetAsync(redo, 0, static_cast<size_t>(cnt), st));
         vg::ProfScope prof(idx->ctx, "hnsw_predicate", st);
-        VG_LAUNCH(vg::hnsw_predicate_kernel, dim3(static_cast<unsigned>(cnt)), dim3(64), lds, st, idx->d_vectors, idx->n, idx->dim,
-                  idx->metric, idx->d_hnsw_l0, idx->d_hnsw_l0_dist, idx->hnsw_m0, idx->hnsw_max_level, idx->hnsw_m, idx->d_hnsw_slot,
-                  idx->d_hnsw_adj, idx->d_hnsw_level_off, idx->hnsw_entry, q.ptr + q0 * idx->dim, k, ef, mk.ptr + q0 * mask_stride,
-                  mask_stride, deleted ? dl.ptr : idx->d_hnsw_tomb, vis, vis_words, cand, cand_cap, oid.ptr + q0 * k, osc.ptr + q0 * k,
-                  ost.ptr ? ost.ptr + q0 : nullptr, redo, int64_t(-1));
-        for (int64_t r0 = 0; second_pass && r0 < cnt; r0 += big_chunk) {  // (every workgroup of an ordinary batch leaves at once)
-            const int64_t rc = std::min(big_chunk, cnt - r0);
-            VG_LAUNCH(vg::hnsw_predicate_kernel, dim3(static_cast<unsigned>(rc)), dim3(64), lds, st, idx->d_vectors, idx->n, idx->dim,
-                      idx->metric, idx->d_hnsw_l0, idx->d_hnsw_l0_dist, idx->hnsw_m0, idx->hnsw_max_level, idx->hnsw_m,
-                      idx->d_hnsw_slot, idx->d_hnsw_adj, idx->d_hnsw_level_off, idx->hnsw_entry, q.ptr + q0 * idx->dim, k, ef,
-                      mk.ptr + q0 * mask_stride, mask_stride, deleted ? dl.ptr : idx->d_hnsw_tomb, vis, vis_words, big.ptr, idx->n,
-                      oid.ptr + q0 * k, osc.ptr + q0 * k, ost.ptr ? ost.ptr + q0 : nullptr, redo, r0);
-        }
-    }
-    VG_TRY(oid.finish());
-    VG_TRY(osc.finish());
-    VG_TRY(ost.finish());
-    return VG_OK;
+        // `grid` walks of this chunk with queue[queue_cap] each; first_query: -1 = the chunk from its start, else the marked ones from there
+        auto launch = [&](int64_t grid, vg::HItem *queue, int64_t queue_cap, int64_t first_query) -> int32_t {
+            VG_LAUNCH(vg::hnsw_predicate_kernel, dim3(static_cast<unsigned>(grid)), dim3(64), lds, st, idx->d_vectors, idx->n, idx->dim,
+                      idx->metric, idx->d_hnsw_l0, idx->d_hnsw_l0_dist, idx->hnsw_m0, idx->hnsw_max_level, idx->hnsw_m, idx->d_hnsw_slot,
+                      idx->d_hnsw_adj, idx->d_hnsw_level_off, idx->hnsw_entry, io.q.ptr + q0 * idx->dim, k, ef, io.mk.ptr + q0 * mask_stride,
+                      mask_stride, deleted ? dl.ptr : idx->d_hnsw_tomb, wc.vis(), wc.vis_words, queue, queue_cap, io.oid.ptr + q0 * k,
+                      io.osc.ptr + q0 * k, io.stats_at(q0), redo, first_query);
+            return VG_OK;
+        };
+        VG_TRY(launch(cnt, cand, cand_cap, -1));
+        for (int64_t r0 = 0; second_pass && r0 < cnt; r0 += big_chunk)  // (every workgroup of an ordinary batch leaves at once)
+            VG_TRY(launch(std::min(big_chunk, cnt - r0), big.ptr, idx->n, r0));
+        return VG_OK;
+    }));
+    return io.finish();
 }

@@ -643,10 +643,7 @@ VG_API int32_t vg_search_flat_filtered(vg_index *idx, const float *queries, int6
                                        void *stream)
 {
     VG_CHECK(idx, VG_ERR_INVALID_ARG, "vg_search_flat_filtered: NULL index");
-    const int64_t mask_bytes = (idx->n + 7) / 8;
-    VG_CHECK(mask == nullptr || mask_stride == 0 || mask_stride >= mask_bytes, VG_ERR_INVALID_ARG,
-             "vg_search_flat_filtered: mask_stride %lld is shorter than a mask (%lld bytes)", static_cast<long long>(mask_stride),
-             static_cast<long long>(mask_bytes));
+    VG_CHECK_MASK_STRIDE("vg_search_flat_filtered", mask, mask_stride, idx->n);
     return flat_probed_entry(idx, queries, nq, k, nprobes, scan, mask, mask_stride, ids, scores, stream);
 }
 

@@ -23,6 +23,7 @@
 #include "vg_device.hpp"
 #include "vg_exact.hpp"
 #include "vg_internal.hpp"
+#include "vg_search.hpp"
 
 namespace vg {
 
@@ -513,8 +514,7 @@ VG_API int32_t vg_vamana_build(vg_index *idx, int32_t r, int32_t l, float alpha,
     // 1/16 of the device's memory (at most 16 GiB, at least 1 GiB), the rest of the batch in further launches
     const int64_t max_b = std::min<int64_t>(max_batch, n);
     const int64_t vis_words = (n + 31) / 32;
-    const int64_t gib = int64_t(1) << 30;
-    const int64_t vis_cap = std::min<int64_t>(16 * gib, std::max<int64_t>(gib, idx->ctx->hbm_bytes / 16));
+    const int64_t vis_cap = vg::scratch_cap(idx->ctx);
     const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(max_b, vis_cap / (vis_words * 4)));
     vg::VbBuf<uint32_t> vis, res, nl, work, roff, srt;
     vg::VbBuf<int32_t> rcnt, rfill;

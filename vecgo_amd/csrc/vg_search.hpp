@@ -1,12 +1,14 @@
 // vg_search.hpp — what the search translation units share on the host: every function one .hip defines and another calls,
 // declared once (the defining file includes this header too, so a definition that disagrees does not compile), and the
-// scaffolding every scan entry point stands on: SearchIO (staged operands), empty_results, PagedTopK (k > 64 in pages).
+// scaffolding every search entry point stands on: SearchIO (staged operands), empty_results, PagedTopK (k > 64 in pages),
+// and for the graph walks WalkIO (SearchIO + per-query counters) and WalkChunks (per-query scratch, a batch in launches).
 // (The bf16 nomination's functions are declared in vg_nominate.hpp.)
 #pragma once
 
 #include <algorithm>
 
 #include "vg_internal.hpp"
+#include "vg_walk_chunk.hpp"
 
 namespace vg {
 
@@ -106,12 +108,75 @@ struct SearchIO {
     }
 };
 
+// The walks' operands: SearchIO and the per-query counters (null: not asked for).
+struct WalkIO : SearchIO {
+    DevOut<vg_search_stats> ost;
+    int32_t init(vg_ctx *ctx, void *stream, const float *queries, size_t query_floats, uint32_t *ids, float *scores, size_t results,
+                 vg_search_stats *stats, int64_t nq, const uint8_t *mask = nullptr, size_t mask_bytes = 0)
+    {
+        VG_TRY(SearchIO::init(ctx, stream, queries, query_floats, ids, scores, results, mask, mask_bytes));
+        return ost.init(stats, stats ? static_cast<size_t>(nq) : 0, st);
+    }
+    vg_search_stats *stats_at(int64_t q0) const { return ost.ptr ? ost.ptr + q0 : nullptr; }
+    int32_t finish()
+    {
+        VG_TRY(SearchIO::finish());
+        return ost.finish();
+    }
+};
+
 // the bytes of nq row filters of an n-row index, mask_stride apart (0: one filter for the batch); no filter: 0
 inline size_t mask_span(const uint8_t *mask, int64_t mask_stride, int64_t nq, int64_t n)
 {
     const int64_t mask_bytes = (n + 7) / 8;
     return mask ? static_cast<size_t>(mask_stride ? (nq - 1) * mask_stride + mask_bytes : mask_bytes) : 0;
 }
+
+// a filter per query (mask_stride != 0) has to be at least a filter long; `fn`: the entry point the message names
+#define VG_CHECK_MASK_STRIDE(fn, mask, mask_stride, n)                                                                              \
+    VG_CHECK((mask) == nullptr || (mask_stride) == 0 || (mask_stride) >= ((n) + 7) / 8, VG_ERR_INVALID_ARG,                         \
+             "%s: mask_stride %lld is shorter than a mask (%lld bytes)", fn, static_cast<long long>(mask_stride),                   \
+             static_cast<long long>(((n) + 7) / 8))
+
+// Per-query scratch of the graph searches (visited bitmap, HBM part of the heaps, exploration heap) is carved from
+// the arena for as many queries as fit under this cap; the rest of the batch goes into further launches.  1 GiB (r02)
+// cut 8192 Vamana queries over 1M nodes (650 KB each) into 5 launches of 1650 wavefronts — fewer than the 3072 the
+// chip holds.  1/16 of the device's memory, at most 16 GiB.
+inline int64_t scratch_cap(const vg_ctx *ctx)
+{
+    const int64_t gib = int64_t(1) << 30;
+    return std::min<int64_t>(16 * gib, std::max<int64_t>(gib, ctx->hbm_bytes / 16));
+}
+
+// A batch of graph walks in launches of `chunk` queries (walk_chunk, vg_walk_chunk.hpp), each query with a visited bitmap of
+// vis_words words of its own.  other_bytes: a query's scratch besides the bitmap.  add() before the arena's commit() — the
+// caller's pieces are chunk times a query's —, for_each() after it.
+struct WalkChunks {
+    int64_t nq, vis_words, chunk;
+    const ArenaCall *ar = nullptr;
+    int i_vis = 0;
+    WalkChunks(int64_t cap, int64_t other_bytes, int64_t n, int64_t nq_)
+        : nq(nq_), vis_words((n + 31) / 32), chunk(walk_chunk(cap, vis_words * 4 + other_bytes, nq_))
+    {
+    }
+    void add(ArenaCall &a)
+    {
+        ar = &a;
+        i_vis = a.add(sizeof(uint32_t) * static_cast<size_t>(chunk) * vis_words);
+    }
+    uint32_t *vis() const { return ar->get<uint32_t>(i_vis); }
+    // body(q0, cnt): queries q0 .. q0 + cnt - 1 over cleared bitmaps; the first status that is not VG_OK ends the batch
+    template <class Body>
+    int32_t for_each(hipStream_t st, Body body) const
+    {
+        for (int64_t q0 = 0; q0 < nq; q0 += chunk) {
+            const int64_t cnt = std::min(chunk, nq - q0);
+            VG_HIP(hipMemsetAsync(vis(), 0, static_cast<size_t>(cnt) * vis_words * 4, st));
+            VG_TRY(body(q0, cnt));
+        }
+        return VG_OK;
+    }
+};
 
 // The answer of an index without rows: k invalid ids per query, through the merge every scan ends in.
 inline int32_t empty_results(int64_t nq, int k, bool descending, uint32_t *ids, float *scores, hipStream_t st)
