@@ -204,6 +204,81 @@ func (r *Resident) ReorderVamanaBFS() (perm, invPerm []uint32, err error) {
 	return perm, invPerm, nil
 }
 
+// Flat-segment quantization kinds of FlatBuild (flat/format.go:22-26 as the library's VG_QUANT_*).
+const (
+	FlatQuantNone, FlatQuantSQ8, FlatQuantPQ = int(C.VG_QUANT_NONE), int(C.VG_QUANT_SQ8), int(C.VG_QUANT_PQ)
+)
+
+// FlatBuild: flat.Writer.Flush's partitioning and quantization (flat/writer.go:99-223) on the resident rows: TrainKMeans,
+// AssignPartition, the counting sort by partition (perm[new] = old; invPerm[old] = new), then the quantizer trained on and
+// applied to the reordered rows.  sq / pq: the quantizer handle the kind needs (HIPScalarQuantizer.Handle() /
+// HIPProductQuantizer.Handle(), the latter created as (dim, pqM, 256); pqM 0 = dim/8), nil otherwise.  The caller permutes
+// what the GPU never held (ids, metadata, payloads) with perm.
+func (r *Resident) FlatBuild(numPartitions, quant, pqM int, seed uint64, sq, pq unsafe.Pointer) (perm, invPerm []uint32, err error) {
+	perm, invPerm = make([]uint32, r.rows), make([]uint32, r.rows)
+	var pp, pi *C.uint32_t
+	if r.rows > 0 {
+		pp, pi = up(perm), up(invPerm)
+	}
+	if err := hipctx.Err(int32(C.vg_flat_build(r.h, C.int32_t(numPartitions), C.int32_t(quant), C.int32_t(pqM), 0, 0, C.uint64_t(seed),
+		(*C.vg_sq8)(sq), (*C.vg_pq)(pq), pp, pi, nil))); err != nil {
+		return nil, nil, err
+	}
+	return perm, invPerm, nil
+}
+
+// WriteFlat: the file flat.Writer.Flush writes (flat/writer.go:312-470) for the resident segment, the body's CRC-32C computed
+// on the GPU.  ids in the segment's row order (nil = 0..rows-1); metadata / blockStats: the sections as Flush serialises them
+// (:230-307) from the documents permuted with FlatBuild's perm, nil = the bytes of rows without documents.
+func (r *Resident) WriteFlat(segmentID uint64, ids []uint64, metadata, blockStats []byte) ([]byte, error) {
+	var mb, sb C.int64_t = -1, -1
+	var mp, sp unsafe.Pointer
+	none := []byte{0} // an empty section still travels as a non-nil pointer
+	section := func(b []byte) (unsafe.Pointer, C.int64_t) {
+		if len(b) == 0 {
+			return unsafe.Pointer(&none[0]), 0
+		}
+		return unsafe.Pointer(&b[0]), C.int64_t(len(b))
+	}
+	if metadata != nil {
+		mp, mb = section(metadata)
+	}
+	if blockStats != nil {
+		sp, sb = section(blockStats)
+	}
+	size := int64(C.vg_segment_flat_image_size(r.h, mb, sb))
+	if size < 0 {
+		return nil, hipctx.Err(int32(C.VG_ERR_UNSUPPORTED))
+	}
+	if len(ids) != 0 && len(ids) != r.rows {
+		return nil, fmt.Errorf("segment: WriteFlat: %d ids for %d rows", len(ids), r.rows)
+	}
+	var ip64 *C.uint64_t
+	if len(ids) != 0 {
+		ip64 = (*C.uint64_t)(unsafe.Pointer(&ids[0]))
+	}
+	image := make([]byte, size)
+	var written C.int64_t
+	if err := hipctx.Err(int32(C.vg_segment_write_flat(r.h, C.uint64_t(segmentID), ip64, mp, mb, sp, sb, unsafe.Pointer(&image[0]),
+		C.int64_t(size), &written, nil))); err != nil {
+		return nil, err
+	}
+	return image[:int(written)], nil
+}
+
+// CRC32CDevice: hash.CRC32C (internal/hash/crc32c.go:15-17) of size bytes of device memory, computed on the GPU.
+func CRC32CDevice(devicePtr unsafe.Pointer, size int64) (uint32, error) {
+	p, err := hipctx.Ptr()
+	if err != nil {
+		return 0, err
+	}
+	var out C.uint32_t
+	if err := hipctx.Err(int32(C.vg_crc32c_device((*C.vg_ctx)(p), unsafe.Pointer(devicePtr), C.int64_t(size), &out, nil))); err != nil {
+		return 0, err
+	}
+	return uint32(out), nil
+}
+
 // VamanaGraph: (R, n*R neighbour ids with 0xFFFFFFFF = none, entry point) — what Writer.Flush writes.
 func (r *Resident) VamanaGraph() (int, []uint32, uint32, error) {
 	var R C.int32_t

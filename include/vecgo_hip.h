@@ -62,7 +62,8 @@ extern "C" {
  *  Added at minor 13 without a bump (the minor-13 header test pins the value): vg_search_vamana_threshold,
  *  vg_vamana_reorder_bfs, and vg_search_vamana / _filtered take k up to 16384 (512 before).  A binding that needs
  *  them looks the symbol vg_search_vamana_threshold up (dlsym) instead of comparing the minor, and
- *  vg_vamana_reorder_bfs the same way; the next bump covers them. */
+ *  vg_vamana_reorder_bfs the same way; the next bump covers them.  Likewise the flat writer: vg_flat_build,
+ *  vg_segment_flat_image_size, vg_segment_write_flat and vg_crc32c_device — bindings find them by symbol lookup. */
 #define VG_ABI_MINOR 13
 #define VG_INVALID_ID 0xFFFFFFFFu
 #define VG_STREAM_LEGACY ((void *)1) /* == hipStreamLegacy */
@@ -628,6 +629,30 @@ int32_t vg_search_flat_filtered(vg_index *idx, const float *queries, int64_t nq,
                                 int32_t scan, const uint8_t *mask, int64_t mask_stride, uint32_t *ids, float *scores,
                                 void *stream);
 
+/* flat.Writer.Flush's partitioning and quantization (flat/writer.go:99-223) on the resident index, over its fp32 rows where
+ * they lie.  (Present when the symbol is: see VG_ABI_MINOR.)
+ * Partitioning (:105-169), skipped when num_partitions <= 1 or rows < num_partitions (the index then has 0 partitions and
+ *   perm is the identity): kmeans.TrainKMeans over all rows with the index's metric = vg_kmeans_train(seed), kmeans_iters
+ *   iterations (0 = the writer's 10, :109), the centroids bit for bit; AssignPartition per row = vg_kmeans_assign; then the
+ *   writer's counting sort (:132-153): partition p's rows start at the exclusive prefix sum of the counts and keep their
+ *   ascending original order — exactly a stable sort by partition, part_offsets[P] = rows, an empty partition is two equal
+ *   offsets.  perm[new] = old and inv_perm[old] = new, either NULL to skip, host or device.  The rows, their norms and the
+ *   bf16 filter image move into that order; centroids and offsets are attached as vg_index_set_partitions attaches them.  The
+ *   caller permutes what the index never held: ids, metadata, payloads.
+ * Quantization (:171-223) of the reordered rows: VG_QUANT_NONE; VG_QUANT_SQ8: vg_sq8_train + vg_sq8_encode with `sq`, attached
+ *   as vg_index_set_sq8_codes does; VG_QUANT_PQ: `pq` = vg_pq_create(dim, pq_m, 256), pq_m 0 = dim / 8 (:66), vg_pq_train with
+ *   pq_iters iterations (0 = 20) and the same seed, vg_pq_encode, attached as vg_index_set_pq_codes does.  The quantizers are
+ *   the caller's objects, trained by this call, and outlive it like any quantizer an index refers to.
+ * Refusals, in this order, with nothing changed and nothing written: NULL index VG_ERR_INVALID_ARG; no fp32 rows
+ *   VG_ERR_NOT_READY; metric Hamming VG_ERR_UNSUPPORTED; an HNSW or Vamana graph, codes of any kind, partitions or a
+ *   nomination image already on the index VG_ERR_UNSUPPORTED; an unknown quantization, negative counts, or a kind without its
+ *   quantizer VG_ERR_INVALID_ARG; a quantizer of another dimension VG_ERR_DIM_MISMATCH; a vg_pq that is not (pq_m, 256)
+ *   VG_ERR_INVALID_ARG; a PQ shape vg_pq_train refuses: its status.  rows == 0 is VG_OK with nothing done.
+ * Memory: one scratch buffer of the rows' size while they move, O(rows) for the order, the codes once more before they are
+ *   attached; released before the call returns. */
+int32_t vg_flat_build(vg_index *idx, int32_t num_partitions, int32_t quantization, int32_t pq_m, int32_t kmeans_iters,
+                      int32_t pq_iters, uint64_t seed, vg_sq8 *sq, vg_pq *pq, uint32_t *perm, uint32_t *inv_perm, void *stream);
+
 /* ---- on-disk segment images --------------------------------------- */
 enum { VG_QUANT_NONE = 0, VG_QUANT_PQ = 1, VG_QUANT_SQ8 = 3, VG_QUANT_RABITQ = 5, VG_QUANT_INT4 = 6 }; /* quantization.Type, types.go:6-14 */
 typedef struct vg_segment_info {
@@ -679,6 +704,30 @@ vg_int4 *vg_segment_int4(vg_segment *seg);   /* NULL unless the segment is INT4-
 int32_t vg_segment_close(vg_segment *seg);
 /* hash.CRC32C (internal/hash/crc32c.go:15-17) */
 uint32_t vg_crc32c(const void *data, int64_t size);
+/* The same over `size` bytes of DEVICE memory, computed there: any start address, any length.  *out = the CRC (0 for
+ * size 0).  Status: NULL context / result / data, a negative size or host memory VG_ERR_INVALID_ARG.  (See VG_ABI_MINOR.) */
+int32_t vg_crc32c_device(vg_ctx *ctx, const void *device_ptr, int64_t size, uint32_t *out, void *stream);
+/* The file flat.Writer.Flush writes (flat/writer.go:312-470) for the resident index, into a host buffer: the 152-byte header
+ * (flat/format.go:28-56, :112-133), then with NO padding between them the centroids, the partition offsets, the quantization
+ * metadata (SQ8: mins then maxs; PQ: u32 m, u32 256, scales, offsets, int8 codebooks), the codes row-major, the fp32 rows,
+ * the ids as little-endian uint64, the metadata section and the block statistics.  Every header offset is the running
+ * position (:335-345), also of a section that is absent; NumPartitions is 0 for an unpartitioned index; Checksum is the
+ * CRC-32C of everything behind the header, the codes' and rows' share computed on the device (vg_crc32c_device) while the host
+ * checksums the small sections.  The payload side file is the host's.
+ *   ids: rows values in the index's (new) row order, NULL = 0 .. rows-1.
+ *   metadata_section / block_stats: the host's serialisation (:230-307) of its documents, permuted like the ids, copied
+ *     verbatim; NULL = what the writer emits when no row has a document: rows + 1 zero uint32 offsets and no blob; block
+ *     statistics uvarint(ceil(rows / 1024)) then per block uvarint(1), 0x00; for rows == 0 no metadata section and the one
+ *     byte 0x00.  vg_segment_flat_image_size takes the two sizes, a negative one standing for that NULL form.
+ *   *written (may be NULL) = vg_segment_flat_image_size = the bytes written.
+ * vg_segment_flat_image_size touches no device and changes nothing; -1 where vg_segment_write_flat would refuse the index.
+ * Refusals: a NULL index or image, image_size below vg_segment_flat_image_size VG_ERR_INVALID_ARG; rows > 0 without fp32
+ *   rows VG_ERR_NOT_READY; a graph on the index, RaBitQ or INT4 codes (the flat format has no type for them, format.go:22-26),
+ *   SQ8 and PQ codes at once, a PQ of other than 256 centroids VG_ERR_UNSUPPORTED.  (See VG_ABI_MINOR.) */
+int64_t vg_segment_flat_image_size(const vg_index *idx, int64_t metadata_bytes, int64_t block_stats_bytes);
+int32_t vg_segment_write_flat(vg_index *idx, uint64_t segment_id, const uint64_t *ids, const void *metadata_section,
+                              int64_t metadata_bytes, const void *block_stats, int64_t block_stats_bytes, void *image,
+                              int64_t image_size, int64_t *written, void *stream);
 
 /* per-query counters, the reference's FilterGateStats (searcher/searcher.go:114-137).  vg_search_vamana has
  * no short-circuit path; it reports in distance_short_circuits the candidates it could NOT push because the

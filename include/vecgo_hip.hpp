@@ -575,6 +575,14 @@ inline std::vector<int> FindClosestCentroids(const Context &c, const std::vector
 
 }  // namespace kmeans
 
+// hash.CRC32C (internal/hash/crc32c.go:15-17) of `size` bytes of device memory, computed on the device
+inline uint32_t CRC32CDevice(const Context &c, const void *devicePtr, int64_t size)
+{
+    uint32_t out = 0;
+    check(vg_crc32c_device(c.handle(), devicePtr, size, &out, nullptr));
+    return out;
+}
+
 struct Result {
     std::vector<uint32_t> ids;   // [nq * k], best first, VG_INVALID_ID padded
     std::vector<float> scores;   // [nq * k]
@@ -661,6 +669,35 @@ public:
     // diskann.Writer.reorderBFS (reorder.go:14-157): the graph and every per-row array into BFS order; perm[new] = old,
     // invPerm[old] = new (either may be null; host or device)
     void ReorderVamanaBFS(uint32_t *perm, uint32_t *invPerm) { check(vg_vamana_reorder_bfs(h_, perm, invPerm, nullptr)); }
+    // flat.Writer.Flush's partitioning and quantization (flat/writer.go:99-223) where the rows lie: k-means + the stable
+    // regrouping by partition (perm[new] = old, invPerm[old] = new; either may be null), then the quantizer (VG_QUANT_NONE /
+    // _SQ8 with sq / _PQ with pq = ProductQuantizer(dim, pqM ? pqM : dim / 8, 256)) trained on and applied to the new order
+    void FlatBuild(int numPartitions, int quantization, std::shared_ptr<quantization::ScalarQuantizer> sq,
+                   std::shared_ptr<quantization::ProductQuantizer> pq, uint32_t *perm, uint32_t *invPerm, uint64_t seed = 0,
+                   int pqM = 0, int kmeansIters = 0, int pqIters = 0)
+    {
+        check(vg_flat_build(h_, numPartitions, quantization, pqM, kmeansIters, pqIters, seed, sq ? sq->handle() : nullptr,
+                            pq ? pq->handle() : nullptr, perm, invPerm, nullptr));
+        if (quantization == VG_QUANT_SQ8) sq_ = std::move(sq);
+        if (quantization == VG_QUANT_PQ) pq_ = std::move(pq);
+    }
+    // the file Writer.Flush writes (flat/writer.go:312-470) for this segment; ids in the segment's row order (null: 0 .. rows-1),
+    // metadata / blockStats: the host's serialised sections (empty: the writer's bytes for rows without documents)
+    std::vector<uint8_t> WriteFlat(uint64_t segmentID, const uint64_t *ids = nullptr, const std::vector<uint8_t> *metadata = nullptr,
+                                   const std::vector<uint8_t> *blockStats = nullptr)
+    {
+        const int64_t size = vg_segment_flat_image_size(h_, metadata ? static_cast<int64_t>(metadata->size()) : -1,
+                                                        blockStats ? static_cast<int64_t>(blockStats->size()) : -1);
+        if (size < 0) check(VG_ERR_UNSUPPORTED);
+        std::vector<uint8_t> image(static_cast<size_t>(size));
+        static const uint8_t none = 0;  // (an empty section still travels as a non-null pointer)
+        int64_t written = 0;
+        check(vg_segment_write_flat(h_, segmentID, ids, metadata ? (metadata->empty() ? &none : metadata->data()) : nullptr,
+                                    metadata ? static_cast<int64_t>(metadata->size()) : 0,
+                                    blockStats ? (blockStats->empty() ? &none : blockStats->data()) : nullptr,
+                                    blockStats ? static_cast<int64_t>(blockStats->size()) : 0, image.data(), size, &written, nullptr));
+        return image;
+    }
     // the Vamana graph (n * r ids, VG_INVALID_ID = empty slot) and its entry point
     std::vector<uint32_t> VamanaGraph(int *r, uint32_t *entry) const
     {
@@ -707,6 +744,7 @@ private:
     }
     std::shared_ptr<Context> ctx_;
     std::shared_ptr<quantization::ProductQuantizer> pq_;
+    std::shared_ptr<quantization::ScalarQuantizer> sq_;
     vg_index *h_ = nullptr;
     int64_t n_;
     int dim_;

@@ -1086,6 +1086,51 @@ class Index:
                                               _stream_ptr(stream)))
         return perm, inv
 
+    QUANT_NONE, QUANT_PQ, QUANT_SQ8 = 0, 1, 3   # VG_QUANT_*
+
+    def flat_build(self, num_partitions, quantizer=None, seed=0, kmeans_iters=0, pq_iters=0, stream=None):
+        """flat.Writer.Flush's partitioning and quantization on the GPU (flat/writer.go:99-223; the rules are vg_flat_build's
+        in the header): k-means over the resident rows, the stable regrouping by partition, then `quantizer` — None, a
+        ScalarQuantizer, or a ProductQuantizer(dim, m, 256) — trained on and applied to the reordered rows and attached.
+        Returns (perm, inv_perm), np.uint32 of length n: perm[new] = old, inv_perm[old] = new."""
+        perm = np.empty(self.n, np.uint32)
+        inv = np.empty(self.n, np.uint32)
+        kind, sq, pq, m = self.QUANT_NONE, None, None, 0
+        if isinstance(quantizer, ScalarQuantizer):
+            kind, sq = self.QUANT_SQ8, quantizer._h
+        elif isinstance(quantizer, ProductQuantizer):
+            kind, pq, m = self.QUANT_PQ, quantizer._h, quantizer.num_subvectors
+        elif quantizer is not None:
+            raise TypeError("quantizer must be None, a ScalarQuantizer or a ProductQuantizer")
+        check(self._lib.vg_flat_build(self._h, C.c_int32(num_partitions), C.c_int32(kind), C.c_int32(m), C.c_int32(kmeans_iters),
+                                      C.c_int32(pq_iters), C.c_uint64(seed), sq, pq, C.c_void_p(perm.ctypes.data),
+                                      C.c_void_p(inv.ctypes.data), _stream_ptr(stream)))
+        if quantizer is not None and self.n:
+            self._keep.append(quantizer)
+        return perm, inv
+
+    def write_flat_segment(self, segment_id=0, ids=None, metadata=None, block_stats=None, stream=None) -> bytes:
+        """The file flat.Writer.Flush writes for this index (flat/writer.go:312-470; vg_segment_write_flat), the body's
+        CRC-32C computed on the GPU.  ids: uint64 per row in the index's order (None: 0 .. n-1); metadata / block_stats: the
+        sections as the host serialised them (None: the writer's bytes for rows without documents)."""
+        def section(b):
+            if b is None:
+                return None, None, C.c_int64(-1)
+            a = np.frombuffer(bytes(b) or b"\0", np.uint8)
+            return a, C.c_void_p(a.ctypes.data), C.c_int64(len(b))
+        md, pmd, nmd = section(metadata)
+        bs, pbs, nbs = section(block_stats)
+        self._lib.vg_segment_flat_image_size.restype = C.c_int64
+        size = self._lib.vg_segment_flat_image_size(self._h, nmd, nbs)
+        if size < 0:
+            check(-5)
+        i, pi = (None, None) if ids is None else _ptr(np.ascontiguousarray(ids, np.uint64), np.uint64, self.n)
+        image = np.empty(size, np.uint8)
+        written = C.c_int64(0)
+        check(self._lib.vg_segment_write_flat(self._h, C.c_uint64(segment_id), pi, pmd, nmd, pbs, nbs, C.c_void_p(image.ctypes.data),
+                                              C.c_int64(size), C.byref(written), _stream_ptr(stream)))
+        return image[:written.value].tobytes()
+
     def _graph_search(self, fn, queries, k, mid_arg, want_stats, stream):
         nq = _rows(queries, self.dim)
         q, pq_ = _ptr(queries, np.float32)
@@ -1466,3 +1511,15 @@ def crc32c(data) -> int:
     buf = np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else \
         np.ascontiguousarray(data, np.uint8)
     return int(lib.vg_crc32c(C.c_void_p(buf.ctypes.data), C.c_int64(buf.size)))
+
+
+def crc32c_device(ctx: Context, data, stream=None) -> int:
+    """hash.CRC32C of a device buffer (a torch tensor on the GPU, any dtype, contiguous), computed there: vg_crc32c_device."""
+    if not _is_torch(data) or not data.is_cuda:
+        raise TypeError("crc32c_device takes a torch tensor in device memory (crc32c is the host's)")
+    if not data.is_contiguous():
+        raise ValueError("crc32c_device: the tensor must be contiguous")
+    out = C.c_uint32(0)
+    check(ctx._lib.vg_crc32c_device(ctx._h, C.c_void_p(data.data_ptr()), C.c_int64(data.numel() * data.element_size()), C.byref(out),
+                                    _stream_ptr(stream)))
+    return int(out.value)

@@ -27,13 +27,6 @@ struct vg_int4 {
     float *d_table = nullptr;                   // [dim * 16] BuildInt4LookupTable
 };
 
-struct vg_sq8 {
-    vg_ctx *ctx = nullptr;
-    int32_t dim = 0;
-    bool trained = false;
-    float *d_mins = nullptr, *d_maxs = nullptr, *d_scales = nullptr, *d_inv = nullptr;  // [dim] each
-};
-
 namespace vg {
 
 constexpr float kF32Max = 3.40282346638528859811704183484516925440e+38f;

@@ -19,7 +19,7 @@
 //                       lane = slot): a 64-bit atomic min of p * r + j per node (reaches 2^37 at n < 2^31, r <= 64),
 //                       the winning slots as a ballot mask per parent, an exclusive scan of their counts, the scatter.
 //                       The host reads the state back once per such level only.
-// Permutation: rb_gather_kernel<W> moves rows of any size with W-byte accesses (16 where the row allows it),
+// Permutation: rb_gather_kernel<W> (vg_permute.hpp) moves rows of any size with W-byte accesses (16 where the row allows it),
 // rb_graph_kernel gathers graph rows and maps every id through inv_perm, rb_tiles_kernel moves the 16-byte pieces of
 // the tiled SQ8 layout between tiles.  The PQ and RaBitQ tiles are rebuilt from their permuted row-major copies.
 #include <algorithm>
@@ -27,12 +27,12 @@
 
 #include "vg_device.hpp"
 #include "vg_internal.hpp"
+#include "vg_permute.hpp"
 #include "vg_search.hpp"
 
 namespace vg {
 
 constexpr uint32_t kRbUnvisited = 0xFFFFFFFFu;
-constexpr int kRbThreads = 256;
 constexpr int kRbSlots = 2048;        // the largest level (S * r slots) the one-workgroup kernel walks
 constexpr int kRbPer = kRbSlots / kRbThreads;
 constexpr int kRbTableBits = 12;      // LDS hash table of node -> first slot: 2x the slots
@@ -47,27 +47,6 @@ struct RbState {
 // every read sees the L2 and never a line the CU's vector cache kept from before the write
 __device__ __forceinline__ uint32_t rb_load(const uint32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void rb_store(uint32_t *p, uint32_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// exclusive prefix of `cnt` over the workgroup in thread order; *total = the sum.  Ends with a barrier.
-__device__ uint32_t rb_block_scan(uint32_t cnt, uint32_t *wsum, uint32_t *total)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t incl = cnt;
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t o = __shfl_up(incl, d, 64);
-        if (lane >= d) incl += o;
-    }
-    if (lane == 63) wsum[wave] = incl;
-    __syncthreads();
-    uint32_t before = 0, all = 0;
-    for (int w = 0; w < kRbThreads / 64; w++) {
-        if (w < wave) before += wsum[w];
-        all += wsum[w];
-    }
-    __syncthreads();
-    *total = all;
-    return before + incl - cnt;
-}
 
 __device__ __forceinline__ uint32_t rb_hash(uint32_t v) { return (v * 2654435761u) >> (32 - kRbTableBits); }
 
@@ -278,19 +257,6 @@ __global__ __launch_bounds__(256) void rb_place_kernel(const uint32_t *__restric
 }
 
 // ---- the permutation ------------------------------------------------------------------------------------------------
-// dst row q = src row perm[q], rows of `words` W-byte words
-template <typename W>
-__global__ __launch_bounds__(256) void rb_gather_kernel(const W *__restrict__ src, W *__restrict__ dst, int64_t n, int64_t words,
-                                                        const uint32_t *__restrict__ perm)
-{
-    const int64_t total = n * words;
-    for (int64_t e = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; e < total;
-         e += static_cast<int64_t>(gridDim.x) * blockDim.x) {
-        const int64_t q = e / words, k = e - q * words;
-        dst[e] = src[static_cast<int64_t>(perm[q]) * words + k];
-    }
-}
-
 __device__ __forceinline__ uint32_t rb_map(uint32_t w, uint32_t n, const uint32_t *inv) { return w < n ? inv[w] : w; }
 
 // graph row q = old row perm[q], every id through inv_perm (VG_INVALID_ID stays where it is); 4 slots per thread
@@ -336,32 +302,6 @@ __global__ __launch_bounds__(256) void rb_tiles_kernel(const uint4 *__restrict__
         }
         dst[e] = x;
     }
-}
-
-static unsigned rb_grid(int64_t total)
-{
-    return static_cast<unsigned>(std::max<int64_t>(1, std::min<int64_t>((total + 255) / 256, 8192)));
-}
-
-// array <- array gathered by perm, through scratch; row_bytes of any size, the widest access that divides it
-static int32_t rb_permute_rows(void *array, int64_t n, int64_t row_bytes, const uint32_t *perm, void *scratch, hipStream_t st)
-{
-    if (!array || n == 0 || row_bytes == 0) return VG_OK;
-    const int64_t w = row_bytes % 16 == 0 ? 16 : row_bytes % 8 == 0 ? 8 : row_bytes % 4 == 0 ? 4 : row_bytes % 2 == 0 ? 2 : 1;
-    const int64_t words = row_bytes / w;
-    const unsigned grid = rb_grid(n * words);
-#define VG_RB_GATHER(T) \
-    VG_LAUNCH(rb_gather_kernel<T>, dim3(grid), dim3(256), 0, st, static_cast<const T *>(array), static_cast<T *>(scratch), n, words, perm)
-    switch (w) {
-        case 16: VG_RB_GATHER(uint4); break;
-        case 8: VG_RB_GATHER(uint2); break;
-        case 4: VG_RB_GATHER(uint32_t); break;
-        case 2: VG_RB_GATHER(uint16_t); break;
-        default: VG_RB_GATHER(uint8_t); break;
-    }
-#undef VG_RB_GATHER
-    VG_HIP(hipMemcpyAsync(array, scratch, static_cast<size_t>(n * row_bytes), hipMemcpyDeviceToDevice, st));
-    return VG_OK;
 }
 
 }  // namespace vg

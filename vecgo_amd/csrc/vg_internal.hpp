@@ -323,7 +323,13 @@ struct vg_pq {
     float *d_offsets = nullptr;     // m
 };
 
-struct vg_sq8;
+struct vg_sq8 {
+    vg_ctx *ctx = nullptr;
+    int32_t dim = 0;
+    bool trained = false;
+    float *d_mins = nullptr, *d_maxs = nullptr, *d_scales = nullptr, *d_inv = nullptr;  // [dim] each, one block: mins, maxs, scales, inverse scales
+};
+
 struct vg_int4;
 
 namespace vg {
