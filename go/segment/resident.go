@@ -184,6 +184,13 @@ func (r *Resident) InsertHNSW(rows []float32, m, efConstruction int) error {
 	return nil
 }
 
+// CompactHNSW: hnsw.Compact (internal/hnsw/compact.go:16-34) on the resident graph under its tombstones
+// (vg_hnsw_compact): live nodes with mostly dead lists are repaired, dead ids leave the live nodes' lists, dead nodes'
+// lists are emptied.  The tombstones stay set; a tombstoned entry point is the caller's to re-elect (recoverEntryPoint).
+func (r *Resident) CompactHNSW(efConstruction int) error {
+	return hipctx.Err(int32(C.vg_hnsw_compact(r.h, C.int32_t(efConstruction), 8192, nil, nil)))
+}
+
 // BuildVamana: diskann.Writer.buildGraph over the rows (diskann/writer.go:362-460) with the seeded initial graph;
 // R, L, alpha of 0 take NewWriter's defaults.  The graph replaces the resident Vamana graph.
 func (r *Resident) BuildVamana(R, L int, alpha float32, seed uint64) error {

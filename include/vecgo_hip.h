@@ -63,7 +63,8 @@ extern "C" {
  *  vg_vamana_reorder_bfs, and vg_search_vamana / _filtered take k up to 16384 (512 before).  A binding that needs
  *  them looks the symbol vg_search_vamana_threshold up (dlsym) instead of comparing the minor, and
  *  vg_vamana_reorder_bfs the same way; the next bump covers them.  Likewise the flat writer: vg_flat_build,
- *  vg_segment_flat_image_size, vg_segment_write_flat and vg_crc32c_device — bindings find them by symbol lookup. */
+ *  vg_segment_flat_image_size, vg_segment_write_flat and vg_crc32c_device — bindings find them by symbol lookup.
+ *  Likewise vg_hnsw_compact (with its caller-allocated vg_hnsw_compact_stats). */
 #define VG_ABI_MINOR 13
 #define VG_INVALID_ID 0xFFFFFFFFu
 #define VG_STREAM_LEGACY ((void *)1) /* == hipStreamLegacy */
@@ -307,6 +308,55 @@ int32_t vg_hnsw_insert(vg_index *idx, const float *rows, int64_t count, int32_t 
                        int32_t max_batch, int32_t growth_div, void *stream);
 /* layerForApplyInsert (hnsw.go:2103-2116) with layerMultiplier = 1/ln(m) (hnsw.go:218) */
 int32_t vg_hnsw_level_for_id(uint64_t id, int32_t m);
+/* HNSW.Compact (internal/hnsw/compact.go:16-34) on the index's graph under the tombstones of
+ * vg_index_set_hnsw_tombstones: the memtable's answer to deletes.  Three phases, as written:
+ *   1. repairActiveNodes / reconcileNode (:36-81, :174-233), every live node in id order.  checkRepairNeeded (:332-367):
+ *      level l needs repair when its list has fewer than M/2 (integer division; l = 0: fewer than M) non-tombstoned
+ *      members; a node with no such level is untouched.  greedyDescent (:235-258) from the entry point to the levels
+ *      above the node's level gives (currID, currDist), the entry of EVERY level below (the reference never updates it,
+ *      :226-231).  Per level: searchLayerPredicateAware (hnsw.go:1406-1557) on that level's lists with EF =
+ *      ef_construction, the filter "id != node" and the tombstones as isDeleted; mergeCandidatesWithActiveNeighbors
+ *      (:260-287): the results united with the node's non-tombstoned neighbours, an id present twice keeps the smaller
+ *      distance (`<`), everything pushed back with PushItemBounded(EF); updateConnectionsForRepair (:289-328): the
+ *      node's tombstoned neighbours are kept in slot order with their cached distances, selectNeighbors (heuristic,
+ *      hnsw.go:1011-1106) takes max(limit - kept, 0) of the merged heap (limit M0 on layer 0, M above), the list becomes
+ *      kept + selected, and only if something was selected (:315).
+ *   2. pruneNodeConnections (:370-401): every live node's list on every level loses its tombstoned ids; the survivors
+ *      keep their order and cached distances, freed slots are VG_INVALID_ID at the end.
+ *   3. clearNodeConnections (:404-421): every tombstoned node's lists become empty — the entry point's too.  (The
+ *      reference's test speaks of an exception for the entry point; its code makes none, and the code is what this
+ *      reproduces.  A tombstoned entry point walks to nothing afterwards; the host re-elects one as recoverEntryPoint
+ *      would, which is not part of this call.)
+ *   Rules the reference leaves open: the merged set is pushed back in ascending id order (the reference ranges over a
+ *     map).  A node's level is what the slot table gives it.  Levels that need no repair are walked by the reference
+ *     without effect and skipped here (k_hnsw_compact.hip says why that changes nothing).
+ *   Neighbor.Dist of a slot: vg_hnsw_insert's rule — the cached distance the index keeps for a graph it built or grew;
+ *     for a graph from vg_index_set_hnsw_graph the layer-0 edge distances of vg_index_set_hnsw_edge_distances where
+ *     given, otherwise the pair kernel's distance.  Distances the compaction computes are ComputeDistance
+ *     (vectorstore/columnar.go:29-49): the pair kernel in the index's HNSW metric, `ok` always true.
+ *   Batches: the nodes to repair are fixed up front (a repair writes only the node's own lists) and go in id order in
+ *     batches of max_batch; every node of a batch walks the graph as it stood when the batch began, then the batch's
+ *     lists are written.  max_batch = 1 is the reference with one worker; larger batches are what its GOMAXPROCS
+ *     workers see of one another (the max_batch contract of vg_hnsw_build).
+ *   Left as they are: the tombstones (still set), ids, rows, levels, the entry point and n.  The cached distances follow
+ *     the lists: a built graph's are rewritten in place and its recomputed layer-0 edge distances, if any, dropped (as
+ *     vg_hnsw_insert drops them); an uploaded graph's layer-0 edge distances are rewritten in place (computed first if
+ *     the index had none), so that the predicate-aware walk and a later vg_hnsw_insert read what setConnections stored.
+ *   The navigation queue, unbounded in the reference, has one slot per row: it cannot overflow, nothing is truncated.
+ *   ef_construction = 0 means 300 (Options.EF).  stats may be NULL.  With no tombstones set, or none of them true, the
+ *     call returns VG_OK, changes nothing and reports zeroed stats.
+ *   Refusals, in this order, nothing changed: NULL index VG_ERR_INVALID_ARG; no HNSW graph or no fp32 rows
+ *     VG_ERR_NOT_READY; max_batch < 1 VG_ERR_INVALID_ARG; Hamming, ef_construction > 1024, M outside 2..32 or
+ *     M0 != 2M VG_ERR_UNSUPPORTED; PQ / SQ8 / INT4 / RaBitQ codes, IVF partitions, a Vamana graph or a nomination image
+ *     (segment state, vg_hnsw_insert's list) VG_ERR_UNSUPPORTED.  (Present when the symbol is: see VG_ABI_MINOR.) */
+typedef struct vg_hnsw_compact_stats { /* caller-allocated, may be NULL */
+    int64_t repaired_nodes; /* live nodes with at least one list below its threshold */
+    int64_t repaired_lists; /* (node, level) lists rewritten by the repair phase */
+    int64_t pruned_links;   /* tombstoned ids removed from live nodes' lists (phase 2) */
+    int64_t cleared_nodes;  /* tombstoned nodes whose lists were emptied (phase 3): those that still held a link */
+} vg_hnsw_compact_stats;
+int32_t vg_hnsw_compact(vg_index *idx, int32_t ef_construction, int32_t max_batch, vg_hnsw_compact_stats *stats,
+                        void *stream);
 /* The index's HNSW graph in vg_index_set_hnsw_graph's layout.  Every output may be NULL; call once for
  * the sizes (m0, m, max_level, level_rows[max_level]), then with buffers: l0[n*m0],
  * upper_slot[max_level*n], upper_adj[sum(level_rows)*m] (host or device). */

@@ -660,6 +660,13 @@ public:
     {
         check(vg_hnsw_insert(h_, rows, count, m, ef, maxBatch, growthDiv, nullptr));
     }
+    // hnsw.Compact (compact.go:16-34) under the segment's tombstones (vg_hnsw_compact): repair, prune, clear
+    vg_hnsw_compact_stats CompactHNSW(int ef = 300, int maxBatch = 8192)
+    {
+        vg_hnsw_compact_stats stats{};
+        check(vg_hnsw_compact(h_, ef, maxBatch, &stats, nullptr));
+        return stats;
+    }
     // diskann.Writer.buildGraph over the segment's rows (writer.go:362-460); replaces the segment's Vamana graph
     void BuildVamana(int r = 64, int l = 100, float alpha = 1.2f, const uint32_t *initGraph = nullptr, uint64_t seed = 0,
                      int maxBatch = 8192, int growthDiv = 32)

@@ -1028,6 +1028,23 @@ class Index:
                                        C.c_int32(max_batch), C.c_int32(growth_div), _stream_ptr(stream)))
         self.n += count
 
+    def compact_hnsw(self, ef_construction=300, max_batch=8192, stream=None):
+        """hnsw.Compact on the GPU (vg_hnsw_compact) under the tombstones of set_hnsw_tombstones: live nodes whose lists
+        are mostly dead are repaired (batches of max_batch nodes in id order; max_batch=1 is the reference with one worker),
+        live nodes' lists lose their tombstoned ids, tombstoned nodes' lists are emptied.  Returns the counters
+        {repaired_nodes, repaired_lists, pruned_links, cleared_nodes}."""
+        if isinstance(ef_construction, bool) or not isinstance(ef_construction, (int, np.integer)):
+            raise TypeError(f"compact_hnsw: ef_construction must be an int, got {type(ef_construction).__name__}")
+        if isinstance(max_batch, bool) or not isinstance(max_batch, (int, np.integer)):
+            raise TypeError(f"compact_hnsw: max_batch must be an int, got {type(max_batch).__name__}")
+        if ef_construction < 0 or ef_construction > 1024:
+            raise ValueError(f"compact_hnsw: ef_construction must be in 0..1024 (0 = 300), got {ef_construction}")
+        if max_batch < 1:
+            raise ValueError(f"compact_hnsw: max_batch must be >= 1, got {max_batch}")
+        stats = (C.c_int64 * 4)()
+        check(self._lib.vg_hnsw_compact(self._h, C.c_int32(ef_construction), C.c_int32(max_batch), stats, _stream_ptr(stream)))
+        return dict(zip(("repaired_nodes", "repaired_lists", "pruned_links", "cleared_nodes"), (int(v) for v in stats)))
+
     def get_hnsw_graph(self, stream=None):
         """(l0[n, m0], upper=[(slot[n], adj[rows, m])...], entry_point) — set_hnsw_graph's arguments."""
         m0, m_, L, ep = C.c_int32(), C.c_int32(), C.c_int32(), C.c_uint32()

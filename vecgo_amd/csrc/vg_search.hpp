@@ -31,6 +31,10 @@ int32_t pq_nan_replay(vg_index *idx, const float *d_queries, int64_t nq, int k, 
 int32_t pq_adc_search_masked(vg_index *idx, const float *queries, int64_t nq, int32_t k, const uint8_t *mask, int64_t mask_stride,
                              bool desc, uint32_t *ids, float *scores, void *stream);
 
+// ---- k_hnsw_predicate.hip -------------------------------------------------------------------------
+// the index's layer-0 edge distances (Neighbor.Dist): uploaded from l0_dist, or (null) recomputed from the rows by the pair kernel
+int32_t hnsw_edge_distances(vg_index *idx, const float *l0_dist, hipStream_t st);
+
 // ---- k_pq.hip -------------------------------------------------------------------------------------
 // the queries' distance tables, in the ADC scan's LDS layout (scan_layout) or [m][k]
 int32_t launch_pq_build_table(const vg_pq *pq, const float *d_queries, int64_t nq, float *d_tables,
