@@ -3,13 +3,16 @@
 //   internal/quantization/pq_test.go:10-140, rabitq_test.go:10-97, internal/kmeans/kmeans_test.go:12-93,
 //   distance/distance_test.go, internal/segment/flat/pq_test.go:17-93.
 // The flat search is checked bit-for-bit against the CPU oracle (test infrastructure).
+// The host-only plan of the HNSW builders (vg_build_plan.hpp) is checked first, against the oracle's schedule and
+// layout: that part needs no device.
 // Exit code 0 = all checks passed; 77 = no gfx950 device (the mirror refused to run: there is no
-// CPU fallback).
+// CPU fallback) and the host-only checks passed.
 #include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <random>
 
+#include "../../vecgo_amd/csrc/vg_build_plan.hpp"
 #include "../../vecgo_amd/csrc/vg_walk_chunk.hpp"
 #include "vecgo_hip.hpp"
 #include "vg_oracle.h"
@@ -66,8 +69,89 @@ static_assert(vg::walk_chunk(int64_t(1) << 30, 131072, 8192) == 8192 && vg::walk
               "the quotient is exact at the boundary");
 static_assert(vg::walk_chunk(int64_t(1) << 30, 0, 5) == 5 && vg::walk_chunk(0, 100, 5) == 1, "no scratch per query; no room at all");
 
+// The (node, level) pairs and the batches of a plan, restated: pair_base is contiguous, every node's pairs are levels
+// 0..min(level, top when its batch began) in order, every batch starts from the entry point and top level that
+// updateEntryPoint (hnsw.go:885-900) leaves after the batches before it.
+static void check_plan_pairs(const vg::HnswBuildPlan &p, uint32_t entry, int top)
+{
+    const int64_t n_old = p.n_old;
+    int64_t done = n_old ? n_old : 1, max_pairs = 1, max_b = 1;
+    EXPECT(p.pair_base.size() == size_t(p.count) + 1 && p.pair_base[0] == 0);
+    if (!n_old && p.count) EXPECT(p.pair_base[1] == 0);  // row 0 of an empty graph: the entry point, no links
+    for (const vg::BuildBatch &bt : p.batches) {
+        EXPECT(bt.t0 == done && bt.size >= 1 && bt.entry == entry && bt.cur_top == top);
+        int64_t npairs = 0;
+        for (int64_t t = bt.t0; t < bt.t0 + bt.size; t++) {
+            const int64_t i = t - n_old, base = p.pair_base[i];
+            const int np = std::min(p.levels[i], bt.cur_top) + 1;
+            EXPECT(p.pair_base[i + 1] == base + np);
+            for (int l = 0; l < np; l++) EXPECT(p.pair_node[base + l] == uint32_t(t) && p.pair_level[base + l] == l);
+            npairs += np;
+        }
+        for (int64_t t = bt.t0; t < bt.t0 + bt.size; t++)
+            if (p.levels[t - n_old] > top) top = p.levels[t - n_old], entry = uint32_t(t);
+        EXPECT(bt.npairs == npairs);
+        max_pairs = std::max(max_pairs, npairs);
+        max_b = std::max(max_b, bt.size);
+        done += bt.size;
+    }
+    EXPECT(done == std::max<int64_t>(n_old + p.count, 1) || p.count == 0);
+    EXPECT(int64_t(p.pair_node.size()) == p.pair_base[p.count] && p.pair_level.size() == p.pair_node.size());
+    EXPECT(p.max_pairs == max_pairs && p.max_b == max_b);
+    EXPECT(p.entry == entry && p.top == top);
+}
+
+// vg_build_plan.hpp against the oracle: the batch rule, the levels and level rows, and that an insert plan over [c, n)
+// ends where the full plan over [0, n) ends.  M = 2 at n = 1200 is the smallest shape where a new top level appears
+// mid-schedule; n = 1 is an empty schedule.
+static void check_build_plan()
+{
+    const int ns[] = {1, 2, 40, 1200}, ms[] = {2, 8, 32}, sched[][2] = {{1, 32}, {64, 16}, {8192, 32}};
+    for (int n : ns)
+        for (int m : ms)
+            for (auto &sc : sched) {
+                const int mb = sc[0], gd = sc[1];
+                const vg::HnswBuildPlan full = vg::plan_hnsw_build(0, n, m, mb, gd, 0, 0, {});
+                std::vector<int32_t> lv(n);
+                int64_t rows[63];
+                const int top = vgo_hnsw_build_layout(n, m, lv.data(), rows);
+                EXPECT(full.top == top && full.levels == lv && full.level_off.size() == size_t(top) + 1);
+                for (int l = 0; l < top; l++) EXPECT(full.level_off[l + 1] - full.level_off[l] == rows[l]);
+                EXPECT(full.upper_rows == full.level_off[top] && full.total_rows == n + full.upper_rows);
+                EXPECT(full.slots.size() == size_t(top) * n);
+                for (int l = 0; l < top; l++) {
+                    uint32_t next = 0;
+                    for (int i = 0; i < n; i++) EXPECT(full.slots[size_t(l) * n + i] == (lv[i] >= l + 1 ? next++ : 0xFFFFFFFFu));
+                }
+                size_t bi = 0;
+                for (int64_t done = 1; done < n; bi++) {
+                    const int64_t b = vgo_hnsw_build_batch(done, n, mb, gd);
+                    EXPECT(vg::next_batch(done, n, mb, gd) == b);
+                    EXPECT(bi < full.batches.size() && full.batches[bi].t0 == done && full.batches[bi].size == b);
+                    done += b;
+                }
+                EXPECT(bi == full.batches.size());
+                check_plan_pairs(full, 0, lv[0]);
+                for (int c : {1, n / 2, n - 1}) {
+                    if (c < 1 || c > n - 1) continue;
+                    const vg::HnswBuildPlan head = vg::plan_hnsw_build(0, c, m, mb, gd, 0, 0, {});
+                    const vg::HnswBuildPlan tail = vg::plan_hnsw_build(c, n - c, m, mb, gd, head.entry, head.top, head.level_off);
+                    check_plan_pairs(tail, head.entry, head.top);
+                    EXPECT(tail.entry == full.entry && tail.top == full.top && tail.level_off == full.level_off);
+                    EXPECT(tail.total_rows == full.total_rows);
+                    for (int l = 0; l < top; l++)  // the new nodes' rows go where a full build puts them
+                        for (int i = c; i < n; i++) EXPECT(tail.slots[size_t(l) * (n - c) + (i - c)] == full.slots[size_t(l) * n + i]);
+                }
+            }
+}
+
 int main()
 {
+    check_build_plan();
+    if (g_fail) {
+        std::fprintf(stderr, "%d host-only check(s) failed\n", g_fail);
+        return 1;
+    }
     if (vg_abi_version() != VG_ABI_VERSION) {
         std::printf("libvecgo_hip.so has ABI version %d, the header %d\n", vg_abi_version(), VG_ABI_VERSION);
         return 1;

@@ -96,3 +96,37 @@ def test_built_graph_recall(vg, ctx):
     gt, _ = idx.search_flat(q, 10)
     hit = sum(len(set(a.tolist()) & set(b.tolist())) for a, b in zip(ids, gt))
     assert hit / 1000 >= 0.99
+
+
+def test_build_replaces_an_uploaded_graph(vg, ctx):
+    """The hand-over of a built graph to an index that already holds one: an uploaded graph (other lists: ef 16) with
+    its edge distances set.  vg_hnsw_build must leave what a fresh index gets, and nothing of the older graph behind:
+    an insert afterwards derives its build state from the cached distances of the NEW lists, so 600 rows built + 50
+    inserted at a batch boundary is the build of 650."""
+    n, extra, dim, m, ef, max_batch, growth_div = 600, 50, 16, 8, 64, 22, 8
+    done, cuts = 1, []
+    while done < n + extra:
+        done += min(max(done // growth_div, 1), max_batch, n + extra - done)
+        cuts.append(done)
+    assert n in cuts  # the two calls' batches are the one call's
+    rng = np.random.default_rng(650)
+    base = rng.standard_normal((n + extra, dim)).astype(np.float32)
+    args = dict(m=m, ef_construction=ef, max_batch=max_batch, growth_div=growth_div)
+
+    def built(rows):
+        fresh = vg.Index(ctx, rows.shape[0], dim)
+        fresh.set_vectors(rows)
+        fresh.build_hnsw(**args)
+        graph = fresh.get_hnsw_graph()
+        fresh.close()
+        return graph
+
+    idx = vg.Index(ctx, n, dim)
+    idx.set_vectors(base[:n])
+    l0, upper, ep = o.hnsw_build(base[:n], dim, m=m, ef=16, max_batch=1, growth_div=32)
+    idx.set_hnsw_graph(l0, upper, ep, m=m)
+    idx.set_hnsw_edge_distances()
+    idx.build_hnsw(**args)
+    _same_graph(idx.get_hnsw_graph(), built(base[:n]))
+    idx.insert_hnsw(base[n:], **args)
+    _same_graph(idx.get_hnsw_graph(), built(base))

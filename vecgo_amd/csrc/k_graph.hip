@@ -756,11 +756,8 @@ static int32_t check_adjacency(const uint32_t *d_ids, int64_t count, int64_t n, 
 template <typename T>
 static int32_t replace_device_array(T **slot, const T *src, size_t count, hipStream_t st)
 {
-    if (*slot) {
-        VG_HIP(hipStreamSynchronize(st));
-        VG_HIP(hipFree(*slot));
-        *slot = nullptr;
-    }
+    if (*slot) VG_HIP(hipStreamSynchronize(st));
+    vg::drop_device(slot);
     if (count == 0) return VG_OK;
     VG_HIP(hipMalloc(reinterpret_cast<void **>(slot), count * sizeof(T)));
     VG_HIP(hipMemcpyAsync(*slot, src, count * sizeof(T), hipMemcpyDefault, st));
@@ -782,18 +779,12 @@ VG_API int32_t vg_index_set_hnsw_graph(vg_index *idx, int32_t m0, const uint32_t
     VG_HIP(hipSetDevice(idx->ctx->device));
     hipStream_t st = vg::pick_stream(idx->ctx, stream);
     idx->l0_cap = 0;
-    for (float **c : {&idx->d_hnsw_l0_cdist, &idx->d_hnsw_adj_cdist})  // a GPU build's cached distances: not this graph's
-        if (*c) {
-            VG_HIP(hipStreamSynchronize(st));
-            (void)hipFree(*c);
-            *c = nullptr;
-        }
+    if (idx->d_hnsw_l0_cdist || idx->d_hnsw_adj_cdist) VG_HIP(hipStreamSynchronize(st));
+    vg::drop_device(&idx->d_hnsw_l0_cdist);  // a GPU build's cached distances: not this graph's
+    vg::drop_device(&idx->d_hnsw_adj_cdist);
     VG_TRY(replace_device_array(&idx->d_hnsw_l0, l0, static_cast<size_t>(idx->n) * m0, st));
-    if (idx->d_hnsw_l0_dist) {  // the old graph's edge distances (vg_index_set_hnsw_edge_distances)
-        VG_HIP(hipStreamSynchronize(st));
-        (void)hipFree(idx->d_hnsw_l0_dist);
-        idx->d_hnsw_l0_dist = nullptr;
-    }
+    if (idx->d_hnsw_l0_dist) VG_HIP(hipStreamSynchronize(st));
+    vg::drop_device(&idx->d_hnsw_l0_dist);  // the old graph's edge distances (vg_index_set_hnsw_edge_distances)
     std::vector<int64_t> off(max_level + 1, 0);
     for (int l = 0; l < max_level; l++) {
         VG_CHECK(level_rows[l] >= 0, VG_ERR_INVALID_ARG, "vg_index_set_hnsw_graph: negative level_rows");
@@ -806,8 +797,7 @@ VG_API int32_t vg_index_set_hnsw_graph(vg_index *idx, int32_t m0, const uint32_t
     int32_t bad = check_adjacency(idx->d_hnsw_l0, idx->n * m0, idx->n, st, "vg_index_set_hnsw_graph (layer 0)");
     if (bad == VG_OK) bad = check_adjacency(idx->d_hnsw_adj, off[max_level] * m, idx->n, st, "vg_index_set_hnsw_graph (upper layers)");
     if (bad != VG_OK) {  // a graph that failed the check is not searchable
-        (void)hipFree(idx->d_hnsw_l0);
-        idx->d_hnsw_l0 = nullptr;
+        vg::drop_device(&idx->d_hnsw_l0);
         return bad;
     }
     idx->hnsw_m0 = m0;

@@ -12,7 +12,7 @@
 //                            results heap is popped into a best-first candidate list per (node, level).
 //   2. build_select_kernel   one workgroup per (node, level): selectNeighborsHeuristic over the list; the
 //                            node's own row is written, and one back-link record per chosen neighbour.
-//   3. build_count / offsets / fill kernels group the back-link records by target row;
+//   3. the back-link records are grouped by target row (vg_group_records.hpp, build_fill_kernel);
 //      build_link_kernel     one workgroup (4 waves) per target row applies its records in id order: append while
 //                            the row has room (addConnectionSimple), else addConnectionPrune; the four waves share
 //                            the 64 pair distances of a link, wave 0 keeps the row.
@@ -34,8 +34,10 @@
 #include <cmath>
 #include <vector>
 
+#include "vg_build_plan.hpp"
 #include "vg_device.hpp"
 #include "vg_exact.hpp"
+#include "vg_group_records.hpp"
 #include "vg_heap.hpp"
 #include "vg_hnsw_layer.hpp"
 #include "vg_internal.hpp"
@@ -336,55 +338,11 @@ __global__ __launch_bounds__(kSelThreads) void build_select_kernel(BuildGraph g,
 }
 
 // ---- 3. back links ---------------------------------------------------------------------------------
-struct LinkCounters {
-    unsigned int nwork, total;
-};
 struct LinkTotals {  // over the whole build (VG_BUILD_DEBUG prints them)
     unsigned long long records, skipped, appended, pruned, good_rows_seen, longest_chain;
     // rows with >= 1000 records in a batch (hubs), 100 MHz ticks: where one workgroup's time goes
     unsigned long long hub_rows, hub_records, hub_applied, hub_sort, hub_scan, hub_gather, hub_replay, hub_total, hub_ties, max_wg;
 };
-
-// Both kernels append to ONE counter: a per-thread atomicAdd on it would serialise ~400 k atomics per batch on one
-// L2 line (measured: most of the back-link stage).  The lanes of a wave are counted with a ballot / summed with a
-// shuffle scan and the wave does one atomicAdd.
-__global__ void build_count_kernel(const uint32_t *__restrict__ rec_row, int64_t nrec, int32_t *__restrict__ rcnt,
-                                   uint32_t *__restrict__ work, LinkCounters *__restrict__ ctr)
-{
-    const int64_t r = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-    const int lane = threadIdx.x & 63;
-    uint32_t row = VG_INVALID_ID;
-    if (r < nrec) row = rec_row[r];
-    const bool first = row != VG_INVALID_ID && atomicAdd(&rcnt[row], 1) == 0;  // the row's first record this batch
-    const uint64_t m = __ballot(first);
-    if (m == 0) return;
-    unsigned int base = 0;
-    if (lane == __builtin_ctzll(m)) base = atomicAdd(&ctr->nwork, static_cast<unsigned int>(__popcll(m)));
-    base = __shfl(base, __builtin_ctzll(m));
-    if (first) work[base + __popcll(m & ((1ull << lane) - 1))] = row;
-}
-
-__global__ void build_offsets_kernel(const uint32_t *__restrict__ work, const int32_t *__restrict__ rcnt,
-                                     uint32_t *__restrict__ roff, LinkCounters *__restrict__ ctr)
-{
-    const unsigned int w = blockIdx.x * blockDim.x + threadIdx.x;
-    const int lane = threadIdx.x & 63;
-    const bool live = w < ctr->nwork;
-    const uint32_t row = live ? work[w] : 0;
-    const unsigned int mine = live ? static_cast<unsigned int>(rcnt[row]) : 0u;
-    unsigned int incl = mine;  // inclusive scan over the wave
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const unsigned int up = __shfl_up(incl, d);
-        if (lane >= d) incl += up;
-    }
-    const unsigned int total = __shfl(incl, 63);
-    if (total == 0) return;
-    unsigned int base = 0;
-    if (lane == 63) base = atomicAdd(&ctr->total, total);
-    base = __shfl(base, 63);
-    if (live) roff[row] = base + incl - mine;
-}
 
 __global__ void build_fill_kernel(const uint32_t *__restrict__ rec_row, const uint32_t *__restrict__ rec_t,
                                   const float *__restrict__ rec_d, int64_t nrec, const uint32_t *__restrict__ roff,
@@ -432,7 +390,7 @@ __device__ __forceinline__ void wave_sync()
 // rows in flight per wave).  A row's records are a serial chain — a hub row (near to very many nodes, as
 // high-dimensional data has them) can receive thousands per batch — so what counts is the latency of one link.
 __global__ __launch_bounds__(kLinkThreads) void build_link_kernel(BuildGraph g, const uint32_t *__restrict__ work,
-                                                                  const LinkCounters *__restrict__ ctr,
+                                                                  const GroupCounters *__restrict__ ctr,
                                                                   int32_t *__restrict__ rcnt, int32_t *__restrict__ rfill,
                                                                   const uint32_t *__restrict__ roff,
                                                                   const uint32_t *__restrict__ srt_t,
@@ -776,7 +734,7 @@ struct DeriveShared {
 };
 
 __global__ __launch_bounds__(kSelThreads) void build_derive_kernel(BuildGraph g, const uint32_t *__restrict__ work,
-                                                                   const LinkCounters *__restrict__ ctr,
+                                                                   const GroupCounters *__restrict__ ctr,
                                                                    unsigned int *__restrict__ s_next, int64_t s_first,
                                                                    const float *__restrict__ l0_dist, int64_t dist_rows,
                                                                    const float *__restrict__ cd0, const float *__restrict__ cdu,
@@ -898,107 +856,150 @@ __global__ void clear_bits_kernel(uint8_t *__restrict__ bm, int64_t from, int64_
     bm[byte] &= keep;
 }
 
-// layerForApplyInsert (hnsw.go:2103-2116), layerMultiplier = 1 / ln(M) (hnsw.go:218)
-static int32_t level_for_id(uint64_t id, double mult)
-{
-    uint64_t x = id + 0x9e3779b97f4a7c15ull;
-    x = (x ^ (x >> 30)) * 0xbf58476d1ce4e5b9ull;
-    x = (x ^ (x >> 27)) * 0x94d049bb133111ebull;
-    x ^= x >> 31;
-    const double inv = 1.0 / 9007199254740992.0;
-    double r = static_cast<double>(x >> 11) * inv;
-    if (r == 0) r = inv;
-    const int32_t lv = static_cast<int32_t>(std::floor(-std::log(r) * mult));
-    return lv > 62 ? 62 : lv;
-}
-
-template <typename T>
-struct DevBuf {
-    T *p = nullptr;
-    ~DevBuf()
-    {
-        if (p) (void)hipFree(p);
-    }
-    int32_t alloc(size_t count)
-    {
-        VG_HIP(hipMalloc(reinterpret_cast<void **>(&p), std::max<size_t>(count, 1) * sizeof(T)));
-        return VG_OK;
-    }
-    T *release()
-    {
-        T *r = p;
-        p = nullptr;
-        return r;
-    }
-};
-
-// One batch of the schedule: nodes t0 .. t0+size-1, their (node, level) pairs, the entry point and top level
-// their searches start from
-struct BuildBatch {
-    int64_t t0, size, npairs;
-    uint32_t entry;
-    int cur_top;
-};
-
-// Everything the batches of one call read or write besides the graph (device pointers unless noted)
+// Everything the batches of one call read or write besides the graph and the plan (device pointers): carve_run
 struct BuildRun {
     int ef = 0;
-    int64_t t_base = 0;                               // levels / pair_base are indexed from this node on
-    int64_t total_rows = 0;
-    const std::vector<int64_t> *pair_base = nullptr;  // host copy of pair_base_d
-    const int32_t *levels = nullptr;
-    const int64_t *pair_base_d = nullptr;
-    const uint32_t *pair_node = nullptr;
-    const int32_t *pair_level = nullptr;
+    int32_t *levels = nullptr;  // the plan's levels / pair_base / pair_node / pair_level
+    int64_t *pair_base = nullptr;
+    uint32_t *pair_node = nullptr;
+    int32_t *pair_level = nullptr;
     uint32_t *vis = nullptr, *cand_ids = nullptr;
     float *cand_d = nullptr;
     int32_t *cand_n = nullptr;
     uint32_t *rec_row = nullptr, *rec_t = nullptr, *srt_t = nullptr, *ord = nullptr, *work = nullptr, *roff = nullptr;
     float *rec_d = nullptr, *srt_d = nullptr, *ordd = nullptr;
     int32_t *rcnt = nullptr, *rfill = nullptr;  // zero on entry; the link kernel leaves them zero
-    LinkCounters *ctr = nullptr;
+    GroupCounters *ctr = nullptr;
     LinkTotals *totals = nullptr;  // VG_BUILD_DEBUG only
     // vg_hnsw_insert (g.smap set): state rows of the rows existing before the call come from s_first + *s_next
     unsigned int *s_next = nullptr, *derived = nullptr;
-    int64_t s_first = 0;
+    int64_t s_first = 0, n_state = 0;
     const float *l0_dist = nullptr;  // uploaded layer-0 edge distances of rows < dist_rows, or null
     int64_t dist_rows = 0;
     const float *cd0 = nullptr, *cdu = nullptr;  // the index's cached distances (layer 0, upper), or null
 };
 
-// The batches, in order: search -> select -> group the back links by target row -> (insert: derive the state of
-// target rows that have none) -> link.  vg_hnsw_build and vg_hnsw_insert both run their schedule through here.
-static int32_t run_batches(vg_ctx *ctx, hipStream_t st, const BuildGraph &g, const std::vector<BuildBatch> &batches,
-                           const BuildRun &r, const char *fn)
+// One piece of a call's scratch after the other, each 256-byte aligned; base null: only the sizes are added up
+struct Carve {
+    char *base;
+    size_t off = 0;
+    template <typename T>
+    void take(T *&p, int64_t count)
+    {
+        p = base ? reinterpret_cast<T *>(base + off) : nullptr;
+        off += (static_cast<size_t>(count) * sizeof(T) + 255) & ~size_t(255);
+    }
+};
+
+// Every per-call scratch piece of run_batches with its size: the plan's device copy, the batches' buffers (sized by
+// the call's largest batch) and, for vg_hnsw_insert, the state rows.  base null: returns the bytes the call needs;
+// else points r (and, insert, g's state) into them.
+static size_t carve_run(char *base, const HnswBuildPlan &p, int m0, bool insert, BuildRun &r, BuildGraph &g)
 {
+    Carve c{base};
+    const int64_t npairs = p.pair_base[p.count], max_rec = p.max_pairs * m0;
+    c.take(r.levels, p.count);
+    c.take(r.pair_base, p.count + 1);
+    c.take(r.pair_node, npairs);
+    c.take(r.pair_level, npairs);
+    c.take(r.vis, p.max_b * ((p.n_old + p.count + 31) / 32));  // one visited bitmap per node of a batch
+    c.take(r.cand_ids, p.max_pairs * r.ef);
+    c.take(r.cand_d, p.max_pairs * r.ef);
+    c.take(r.cand_n, p.max_pairs);
+    for (uint32_t **q : {&r.rec_row, &r.rec_t, &r.srt_t, &r.ord}) c.take(*q, max_rec);
+    for (float **q : {&r.rec_d, &r.srt_d, &r.ordd}) c.take(*q, max_rec);
+    c.take(r.work, std::min(max_rec, p.total_rows));
+    c.take(r.roff, p.total_rows);
+    c.take(r.rcnt, p.total_rows);
+    c.take(r.rfill, p.total_rows);
+    c.take(r.ctr, 1);
+    c.take(r.totals, 1);
+    if (!hook(kHookBuildDebug)) r.totals = nullptr;
+    if (insert) {
+        // state rows: one per new (node, level) pair, then one per derived row.  A row is derived at most once per call
+        // and only when a record targets it: at most one per record, at most one per row.  (Derived rows are the graph's
+        // older rows and the rows a new node gets above the top level of its batch, which no pair makes.)
+        r.s_first = npairs;
+        r.n_state = npairs + std::min(p.total_rows, npairs * m0);
+        c.take(g.smap, p.total_rows);
+        c.take(g.row_node, p.total_rows);
+        c.take(g.srow_row, r.n_state);
+        c.take(g.dist, r.n_state * kStateStride);
+        c.take(g.bits, r.n_state * kStateStride);
+        c.take(g.cnt, r.n_state);
+        c.take(g.good, r.n_state);
+        c.take(r.s_next, 2);
+        r.derived = r.s_next + 1;
+    }
+    return c.off;
+}
+
+// VG_BUILD_DEBUG, after a batch: its wall time and its longest per-row chain (a running maximum on the device: reset
+// here), every 16th batch printed.  tools/hnsw_build_debug.py reads the lines.
+struct BatchDebug {
+    std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+    unsigned long long max_chain = 0;
+};
+static int32_t debug_batch(const char *fn, hipStream_t st, LinkTotals *totals, size_t bi, size_t nbatches, int64_t size,
+                           BatchDebug &dbg)
+{
+    VG_HIP(hipStreamSynchronize(st));
+    const auto now = std::chrono::steady_clock::now();
+    LinkTotals t{};
+    VG_HIP(hipMemcpy(&t, totals, sizeof(t), hipMemcpyDeviceToHost));
+    if (bi % 16 == 0 || bi + 1 == nbatches)
+        fprintf(stderr, "%s: batch %zu: %lld nodes, %.2f ms, longest chain %llu; longest link workgroup %.2f ms "
+                        "(%llu records, %llu pruned, %llu heap replays)\n", fn, bi, static_cast<long long>(size),
+                std::chrono::duration<double, std::milli>(now - dbg.t0).count(), t.longest_chain, (t.max_wg >> 40) / 1e5,
+                (t.max_wg >> 24) & 0xFFFF, (t.max_wg >> 8) & 0xFFFF, t.max_wg & 0xFF);
+    dbg.t0 = now;
+    dbg.max_chain = std::max(dbg.max_chain, t.longest_chain);
+    const unsigned long long zero = 0;
+    VG_HIP(hipMemcpy(&totals->longest_chain, &zero, sizeof(zero), hipMemcpyHostToDevice));
+    VG_HIP(hipMemcpy(&totals->max_wg, &zero, sizeof(zero), hipMemcpyHostToDevice));
+    return VG_OK;
+}
+
+// The batches, in order: search -> select -> group the back links by target row -> (insert: derive the state of
+// target rows that have none) -> link.  vg_hnsw_build and vg_hnsw_insert both run their plan through here; it starts
+// with the plan's copy to the device and the zeros the kernels count on, and returns with the stream idle.
+static int32_t run_batches(vg_ctx *ctx, hipStream_t st, const BuildGraph &g, const HnswBuildPlan &p, const BuildRun &r,
+                           const char *fn)
+{
+    VG_HIP(hipMemcpyAsync(r.levels, p.levels.data(), p.levels.size() * 4, hipMemcpyHostToDevice, st));
+    VG_HIP(hipMemcpyAsync(r.pair_base, p.pair_base.data(), p.pair_base.size() * 8, hipMemcpyHostToDevice, st));
+    VG_HIP(hipMemcpyAsync(r.pair_node, p.pair_node.data(), p.pair_node.size() * 4, hipMemcpyHostToDevice, st));
+    VG_HIP(hipMemcpyAsync(r.pair_level, p.pair_level.data(), p.pair_level.size() * 4, hipMemcpyHostToDevice, st));
+    VG_HIP(hipMemsetAsync(r.rcnt, 0, static_cast<size_t>(p.total_rows) * 4, st));
+    VG_HIP(hipMemsetAsync(r.rfill, 0, static_cast<size_t>(p.total_rows) * 4, st));
+    if (r.totals) VG_HIP(hipMemsetAsync(r.totals, 0, sizeof(LinkTotals), st));
+    if (g.smap) {
+        VG_HIP(hipMemsetAsync(g.smap, 0xFF, static_cast<size_t>(p.total_rows) * 4, st));
+        VG_HIP(hipMemsetAsync(r.s_next, 0, 8, st));
+    }
     const int ef = r.ef, m0 = g.m0;
     const size_t lds = static_cast<size_t>(3 * ef + 4) * sizeof(HItem) + 128 * sizeof(float);
     auto search_kern = g.metric != VG_METRIC_DOT ? build_search_kernel<true> : build_search_kernel<false>;
     VG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(search_kern),
                                hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
-    const bool debug = r.totals != nullptr;
-    auto dbg_t0 = std::chrono::steady_clock::now();
-    unsigned long long dbg_max_chain = 0;
-    const int64_t pb0 = (*r.pair_base)[0];
-    for (const BuildBatch &bt : batches) {
+    BatchDebug dbg;
+    for (const BuildBatch &bt : p.batches) {
         const int64_t vis_words = (bt.t0 + 31) / 32;  // only nodes below t0 are reachable
         const int64_t nrec = bt.npairs * m0;
         VG_HIP(hipMemsetAsync(r.vis, 0, static_cast<size_t>(bt.size * vis_words) * 4, st));
-        VG_HIP(hipMemsetAsync(r.ctr, 0, sizeof(LinkCounters), st));
         {
             ProfScope prof(ctx, "hnsw_build_search", st);
-            VG_LAUNCH(search_kern, dim3(static_cast<unsigned>(bt.size)), dim3(64), lds, st, g, bt.t0, r.t_base,
-                      bt.entry, bt.cur_top, r.levels, r.pair_base_d, ef, r.vis, vis_words, r.cand_ids,
-                      r.cand_d, r.cand_n);
+            VG_LAUNCH(search_kern, dim3(static_cast<unsigned>(bt.size)), dim3(64), lds, st, g, bt.t0, p.n_old, bt.entry,
+                      bt.cur_top, r.levels, r.pair_base, ef, r.vis, vis_words, r.cand_ids, r.cand_d, r.cand_n);
         }
-        const int64_t pb = (*r.pair_base)[bt.t0 - r.t_base] - pb0;
+        const int64_t pb = p.pair_base[bt.t0 - p.n_old];
         {
             ProfScope prof(ctx, "hnsw_build_select", st);
             VG_LAUNCH(build_select_kernel, dim3(static_cast<unsigned>(bt.npairs)), dim3(kSelThreads), 0, st, g, pb,
                       r.pair_node + pb, r.pair_level + pb, ef, r.cand_ids, r.cand_d, r.cand_n, m0,
                       r.rec_row, r.rec_t, r.rec_d);
         }
-        const int64_t max_work = std::min(nrec, r.total_rows);
+        const int64_t max_work = std::min(nrec, p.total_rows);
         auto link = [&]() -> int32_t {
             VG_LAUNCH(build_link_kernel, dim3(static_cast<unsigned>(max_work)), dim3(kLinkThreads), 0, st, g, r.work,
                       r.ctr, r.rcnt, r.rfill, r.roff, r.srt_t, r.srt_d, r.ord, r.ordd, r.totals);
@@ -1006,12 +1007,9 @@ static int32_t run_batches(vg_ctx *ctx, hipStream_t st, const BuildGraph &g, con
         };
         {
             ProfScope prof(ctx, "hnsw_build_link", st);
-            const unsigned gb = static_cast<unsigned>((nrec + 255) / 256);
-            VG_LAUNCH(build_count_kernel, dim3(gb), dim3(256), 0, st, r.rec_row, nrec, r.rcnt, r.work, r.ctr);
-            VG_LAUNCH(build_offsets_kernel, dim3(static_cast<unsigned>((max_work + 255) / 256)), dim3(256), 0, st,
-                      r.work, r.rcnt, r.roff, r.ctr);
-            VG_LAUNCH(build_fill_kernel, dim3(gb), dim3(256), 0, st, r.rec_row, r.rec_t, r.rec_d, nrec,
-                      r.roff, r.rfill, r.srt_t, r.srt_d);
+            VG_TRY(group_count_offsets(r.rec_row, nrec, max_work, r.rcnt, r.work, r.roff, r.ctr, st));
+            VG_LAUNCH(build_fill_kernel, dim3(static_cast<unsigned>((nrec + 255) / 256)), dim3(256), 0, st, r.rec_row,
+                      r.rec_t, r.rec_d, nrec, r.roff, r.rfill, r.srt_t, r.srt_d);
             if (!g.smap) VG_TRY(link());
         }
         if (g.smap) {
@@ -1023,31 +1021,16 @@ static int32_t run_batches(vg_ctx *ctx, hipStream_t st, const BuildGraph &g, con
             ProfScope prof(ctx, "hnsw_build_link", st);
             VG_TRY(link());
         }
-        if (debug) {  // per-batch wall time and the batch's longest per-row chain (the chain is a running maximum: reset it)
-            VG_HIP(hipStreamSynchronize(st));
-            const auto now = std::chrono::steady_clock::now();
-            LinkTotals t{};
-            VG_HIP(hipMemcpy(&t, r.totals, sizeof(t), hipMemcpyDeviceToHost));
-            const size_t bi = static_cast<size_t>(&bt - batches.data());
-            if (bi % 16 == 0 || bi + 1 == batches.size())
-                fprintf(stderr, "%s: batch %zu: %lld nodes, %.2f ms, longest chain %llu; longest link workgroup %.2f ms "
-                                "(%llu records, %llu pruned, %llu heap replays)\n", fn, bi, static_cast<long long>(bt.size),
-                        std::chrono::duration<double, std::milli>(now - dbg_t0).count(), t.longest_chain, (t.max_wg >> 40) / 1e5,
-                        (t.max_wg >> 24) & 0xFFFF, (t.max_wg >> 8) & 0xFFFF, t.max_wg & 0xFF);
-            dbg_t0 = now;
-            dbg_max_chain = std::max(dbg_max_chain, t.longest_chain);
-            const unsigned long long zero = 0;
-            VG_HIP(hipMemcpy(&r.totals->longest_chain, &zero, sizeof(zero), hipMemcpyHostToDevice));
-            VG_HIP(hipMemcpy(&r.totals->max_wg, &zero, sizeof(zero), hipMemcpyHostToDevice));
-        }
+        if (r.totals)
+            VG_TRY(debug_batch(fn, st, r.totals, static_cast<size_t>(&bt - p.batches.data()), p.batches.size(), bt.size, dbg));
     }
     VG_HIP(hipStreamSynchronize(st));
-    if (debug) {
+    if (r.totals) {
         LinkTotals t{};
         VG_HIP(hipMemcpy(&t, r.totals, sizeof(t), hipMemcpyDeviceToHost));
         fprintf(stderr, "%s: back links %llu = %llu skipped (farther than a fully chosen row's last member) + %llu appended + "
                         "%llu pruned; target-row visits that found the row fully chosen %llu; longest per-row chain in one batch %llu\n",
-                fn, t.records, t.skipped, t.appended, t.pruned, t.good_rows_seen, std::max(dbg_max_chain, t.longest_chain));
+                fn, t.records, t.skipped, t.appended, t.pruned, t.good_rows_seen, std::max(dbg.max_chain, t.longest_chain));
         fprintf(stderr, "%s: rows with >= 1000 back links in a batch: %llu visits, %llu records of which %llu applied; per visit "
                         "%.1f us in all = sort %.1f + scan %.1f + gather %.1f + replay %.1f (us); heap replays (ties) %llu\n", fn,
                 t.hub_rows, t.hub_records, t.hub_applied,
@@ -1055,6 +1038,69 @@ static int32_t run_batches(vg_ctx *ctx, hipStream_t st, const BuildGraph &g, con
                 t.hub_rows ? t.hub_scan / 100.0 / t.hub_rows : 0.0, t.hub_rows ? t.hub_gather / 100.0 / t.hub_rows : 0.0,
                 t.hub_rows ? t.hub_replay / 100.0 / t.hub_rows : 0.0, t.hub_ties);
     }
+    return VG_OK;
+}
+
+static int32_t check_hnsw_build_args(const char *fn, int m, int ef, int max_batch, int growth_div)
+{
+    VG_CHECK(m >= 2 && m <= 32, VG_ERR_UNSUPPORTED, "%s: M=%d must be in 2..32 (M0 = 2M <= 64)", fn, m);
+    VG_CHECK(ef >= 1 && ef <= kBuildMaxEf, VG_ERR_UNSUPPORTED, "%s: ef_construction=%d must be in 1..%d", fn, ef, kBuildMaxEf);
+    VG_CHECK(max_batch >= 1 && growth_div >= 1, VG_ERR_INVALID_ARG, "%s: max_batch and growth_div must be >= 1", fn);
+    return VG_OK;
+}
+
+static int32_t check_plan(const char *fn, const HnswBuildPlan &p, int max_batch)
+{
+    const int64_t n = p.n_old + p.count;
+    VG_CHECK(p.total_rows < (int64_t(1) << 32) - 1, VG_ERR_UNSUPPORTED, "%s: too many rows", fn);
+    // visited bitmaps: one per node of a batch, at most 4 GiB — larger batches are not worth more
+    VG_CHECK(p.max_b * ((n + 31) / 32) * 4 <= (int64_t(1) << 32), VG_ERR_UNSUPPORTED,
+             "%s: max_batch=%d needs more than 4 GiB of visited bitmaps at %lld rows", fn, max_batch, static_cast<long long>(n));
+    return VG_OK;
+}
+
+// The one hand-over of a built or grown graph to the index, in vg_index_set_hnsw_graph's layout, once the stream is
+// idle.  Each array replaces what the index held; one passed as the index's own (grown in place) stays.  l0c / adjc:
+// the cached distances for the next vg_hnsw_insert, or null (the index then keeps none).  Edge distances uploaded for
+// the older lists go: the predicate-aware walk recomputes them (same values).  Tombstones are no part of it, on
+// purpose: vg_hnsw_build leaves d_hnsw_tomb as it was, vg_hnsw_insert has grown it already.
+// vg_index_set_hnsw_graph does not come through here: it frees every older array BEFORE it allocates the next, and a
+// failure half way leaves what it had replaced by then.
+static void adopt_hnsw_graph(vg_index *idx, uint32_t *l0, float *l0c, uint32_t *slot, uint32_t *adj, float *adjc,
+                             int64_t *level_off, int m, const HnswBuildPlan &p)
+{
+    auto put = [](auto **held, auto *fresh) {
+        if (*held != fresh) drop_device(held);
+        *held = fresh;
+    };
+    put(&idx->d_hnsw_l0, l0);
+    put(&idx->d_hnsw_l0_cdist, l0c);
+    put(&idx->d_hnsw_slot, slot);
+    put(&idx->d_hnsw_adj, adj);
+    put(&idx->d_hnsw_adj_cdist, adjc);
+    put(&idx->d_hnsw_level_off, level_off);
+    drop_device(&idx->d_hnsw_l0_dist);
+    idx->hnsw_m0 = 2 * m;
+    idx->hnsw_m = m;
+    idx->hnsw_max_level = p.top;
+    idx->hnsw_entry = p.entry;
+}
+
+// room for n_new rows in a device array that holds n_old (its capacity: *cap rows, 0 = n_old), grown by half at
+// least so that a run of small inserts copies the array O(log n) times; bytes(r) = its size at r rows
+template <typename T, typename F>
+static int32_t grow_rows(T **p, int64_t *cap, int64_t n_old, int64_t n_new, F bytes, hipStream_t st)
+{
+    const int64_t have = std::max(*cap, n_old);
+    if (*p && n_new <= have) return VG_OK;
+    const int64_t want = std::max(n_new, have + have / 2);
+    DevBuf<char> q;
+    VG_TRY(q.alloc(bytes(want)));
+    if (*p && n_old) VG_HIP(hipMemcpyAsync(q.p, *p, bytes(n_old), hipMemcpyDeviceToDevice, st));
+    VG_HIP(hipStreamSynchronize(st));
+    drop_device(p);
+    *p = reinterpret_cast<T *>(q.release());
+    *cap = want;
     return VG_OK;
 }
 
@@ -1068,185 +1114,56 @@ VG_API int32_t vg_hnsw_level_for_id(uint64_t id, int32_t m)
 VG_API int32_t vg_hnsw_build(vg_index *idx, int32_t m, int32_t ef_construction, int32_t max_batch,
                              int32_t growth_div, void *stream)
 {
-    VG_CHECK(idx, VG_ERR_INVALID_ARG, "vg_hnsw_build: NULL index");
-    VG_CHECK(idx->d_vectors && idx->n > 0, VG_ERR_NOT_READY, "vg_hnsw_build: index has no fp32 vectors");
+    const char *fn = "vg_hnsw_build";
+    VG_CHECK(idx, VG_ERR_INVALID_ARG, "%s: NULL index", fn);
+    VG_CHECK(idx->d_vectors && idx->n > 0, VG_ERR_NOT_READY, "%s: index has no fp32 vectors", fn);
     VG_CHECK(idx->metric != VG_METRIC_HAMMING, VG_ERR_UNSUPPORTED, "unsupported metric for float32: Hamming");
-    VG_CHECK(m >= 2 && m <= 32, VG_ERR_UNSUPPORTED, "vg_hnsw_build: M=%d must be in 2..32 (M0 = 2M <= 64)", m);
-    VG_CHECK(ef_construction >= 1 && ef_construction <= vg::kBuildMaxEf, VG_ERR_UNSUPPORTED,
-             "vg_hnsw_build: ef_construction=%d must be in 1..%d", ef_construction, vg::kBuildMaxEf);
-    VG_CHECK(max_batch >= 1 && growth_div >= 1, VG_ERR_INVALID_ARG, "vg_hnsw_build: max_batch and growth_div must be >= 1");
-    VG_CHECK(idx->n < (int64_t(1) << 31), VG_ERR_UNSUPPORTED, "vg_hnsw_build: at most 2^31 rows");
+    VG_TRY(vg::check_hnsw_build_args(fn, m, ef_construction, max_batch, growth_div));
+    VG_CHECK(idx->n < (int64_t(1) << 31), VG_ERR_UNSUPPORTED, "%s: at most 2^31 rows", fn);
     VG_HIP(hipSetDevice(idx->ctx->device));
     hipStream_t st = vg::pick_stream(idx->ctx, stream);
     const int64_t n = idx->n;
     const int m0 = 2 * m;  // mmax0Multiplier hnsw.go:28
-    const int ef = ef_construction;
 
-    // levels, slots, and what every node's insert will see as the top level (all known up front: ids and
-    // levels are deterministic and so is the batch schedule)
-    const double mult = 1.0 / std::log(static_cast<double>(m));
-    std::vector<int32_t> levels(static_cast<size_t>(n));
-    int top = 0;
-    for (int64_t i = 0; i < n; i++) {
-        levels[i] = vg::level_for_id(static_cast<uint64_t>(i), mult);
-        top = std::max(top, levels[i]);
-    }
-    std::vector<int64_t> level_rows(static_cast<size_t>(top), 0), level_off(static_cast<size_t>(top) + 1, 0);
-    std::vector<uint32_t> slots(static_cast<size_t>(top) * n);
-    for (int l = 0; l < top; l++) {
-        uint32_t next = 0;
-        for (int64_t i = 0; i < n; i++) slots[static_cast<size_t>(l) * n + i] = levels[i] >= l + 1 ? next++ : VG_INVALID_ID;
-        level_rows[l] = next;
-        level_off[l + 1] = level_off[l] + next;
-    }
-    const int64_t upper_rows = level_off[top];
-    const int64_t total_rows = n + upper_rows;
-    VG_CHECK(total_rows < (int64_t(1) << 32) - 1, VG_ERR_UNSUPPORTED, "vg_hnsw_build: too many rows");
+    // levels, slots, and what every node's insert will see as the top level: all known up front (vg_build_plan.hpp).
+    // The plan's slot table is [top][n], the index's own layout: it is uploaded as it stands.
+    const vg::HnswBuildPlan plan = vg::plan_hnsw_build(0, n, m, max_batch, growth_div, 0, 0, {});
+    VG_TRY(vg::check_plan(fn, plan, max_batch));
+    const int64_t upper_rows = plan.upper_rows, total_rows = plan.total_rows;
     const int64_t total_slots = n * m0 + upper_rows * m;
 
-    using Batch = vg::BuildBatch;
-    std::vector<Batch> batches;
-    std::vector<int64_t> pair_base(static_cast<size_t>(n) + 1, 0);
-    std::vector<uint32_t> pair_node;
-    std::vector<int32_t> pair_level;
-    {
-        uint32_t entry = 0;
-        int cur_top = levels[0];
-        int64_t done = 1;
-        pair_base[1] = 0;
-        int64_t max_pairs = 0;
-        while (done < n) {
-            int64_t b = done / growth_div;
-            b = std::max<int64_t>(1, std::min<int64_t>(b, max_batch));
-            b = std::min(b, n - done);
-            Batch bt{done, b, 0, entry, cur_top};
-            for (int64_t t = done; t < done + b; t++) {
-                const int np = std::min(levels[t], cur_top) + 1;
-                pair_base[t + 1] = pair_base[t] + np;
-                bt.npairs += np;
-            }
-            for (int64_t t = done; t < done + b; t++)  // updateEntryPoint hnsw.go:885-900
-                if (levels[t] > cur_top) {
-                    cur_top = levels[t];
-                    entry = static_cast<uint32_t>(t);
-                }
-            batches.push_back(bt);
-            max_pairs = std::max(max_pairs, bt.npairs);
-            done += b;
-        }
-        pair_node.resize(static_cast<size_t>(pair_base[n]));
-        pair_level.resize(static_cast<size_t>(pair_base[n]));
-        for (const Batch &bt : batches)
-            for (int64_t t = bt.t0; t < bt.t0 + bt.size; t++)
-                for (int l = 0; l <= std::min(levels[t], bt.cur_top); l++) {
-                    pair_node[static_cast<size_t>(pair_base[t] + l)] = static_cast<uint32_t>(t);
-                    pair_level[static_cast<size_t>(pair_base[t] + l)] = l;
-                }
-    }
-    int64_t max_pairs = 1, max_b = 1;
-    for (const auto &bt : batches) {
-        max_pairs = std::max(max_pairs, bt.npairs);
-        max_b = std::max(max_b, bt.size);
-    }
-    const int64_t vis_words_max = (n + 31) / 32;
-    // visited bitmaps: one per node of a batch, at most 4 GiB — larger batches are not worth more
-    VG_CHECK(max_b * vis_words_max * 4 <= (int64_t(1) << 32), VG_ERR_UNSUPPORTED,
-             "vg_hnsw_build: max_batch=%d needs more than 4 GiB of visited bitmaps at %lld rows", max_batch,
-             static_cast<long long>(n));
-
-    vg::DevBuf<uint32_t> d_ids, d_slots, d_vis, d_cand_ids, d_rec_row, d_rec_t, d_work, d_roff, d_srt_t, d_pair_node, d_ord;
-    vg::DevBuf<float> d_dist, d_cand_d, d_rec_d, d_srt_d, d_ordd;
+    // the graph with its build state for every row, and the batches' scratch: the call's own, not the context arena's,
+    // which would keep gigabytes of it for the life of the context
+    vg::DevBuf<uint32_t> d_ids, d_slots;
+    vg::DevBuf<float> d_dist;
     vg::DevBuf<uint64_t> d_bits;
-    vg::DevBuf<int32_t> d_cnt, d_levels, d_cand_n, d_rcnt, d_rfill, d_pair_level;
+    vg::DevBuf<int32_t> d_cnt;
     vg::DevBuf<uint8_t> d_good;
-    vg::DevBuf<int64_t> d_level_off, d_pair_base;
-    vg::DevBuf<vg::LinkCounters> d_ctr;
-    vg::DevBuf<vg::LinkTotals> d_totals;
-    const bool debug = vg::hook(vg::kHookBuildDebug);
+    vg::DevBuf<int64_t> d_level_off;
+    vg::DevBuf<char> scratch;
     VG_TRY(d_ids.alloc(static_cast<size_t>(total_slots)));
     VG_TRY(d_dist.alloc(static_cast<size_t>(total_slots)));
     VG_TRY(d_bits.alloc(static_cast<size_t>(total_slots)));
     VG_TRY(d_cnt.alloc(static_cast<size_t>(total_rows)));
     VG_TRY(d_good.alloc(static_cast<size_t>(total_rows)));
-    VG_TRY(d_slots.alloc(slots.size()));
-    VG_TRY(d_level_off.alloc(level_off.size()));
-    VG_TRY(d_levels.alloc(static_cast<size_t>(n)));
-    VG_TRY(d_pair_base.alloc(pair_base.size()));
-    VG_TRY(d_pair_node.alloc(pair_node.size()));
-    VG_TRY(d_pair_level.alloc(pair_level.size()));
-    VG_TRY(d_vis.alloc(static_cast<size_t>(max_b * vis_words_max)));
-    VG_TRY(d_cand_ids.alloc(static_cast<size_t>(max_pairs) * ef));
-    VG_TRY(d_cand_d.alloc(static_cast<size_t>(max_pairs) * ef));
-    VG_TRY(d_cand_n.alloc(static_cast<size_t>(max_pairs)));
-    const int64_t max_rec = max_pairs * m0;
-    VG_TRY(d_rec_row.alloc(static_cast<size_t>(max_rec)));
-    VG_TRY(d_rec_t.alloc(static_cast<size_t>(max_rec)));
-    VG_TRY(d_rec_d.alloc(static_cast<size_t>(max_rec)));
-    VG_TRY(d_srt_t.alloc(static_cast<size_t>(max_rec)));
-    VG_TRY(d_srt_d.alloc(static_cast<size_t>(max_rec)));
-    VG_TRY(d_ord.alloc(static_cast<size_t>(max_rec)));
-    VG_TRY(d_ordd.alloc(static_cast<size_t>(max_rec)));
-    VG_TRY(d_work.alloc(static_cast<size_t>(std::min(max_rec, total_rows))));
-    VG_TRY(d_roff.alloc(static_cast<size_t>(total_rows)));
-    VG_TRY(d_rcnt.alloc(static_cast<size_t>(total_rows)));
-    VG_TRY(d_rfill.alloc(static_cast<size_t>(total_rows)));
-    VG_TRY(d_ctr.alloc(1));
-    VG_TRY(d_totals.alloc(1));
-    VG_HIP(hipMemsetAsync(d_totals.p, 0, sizeof(vg::LinkTotals), st));
+    VG_TRY(d_slots.alloc(plan.slots.size()));
+    VG_TRY(d_level_off.alloc(plan.level_off.size()));
+    vg::BuildGraph g{idx->d_vectors, n, idx->dim, idx->metric, m0, m, d_ids.p, d_ids.p + n * m0, d_dist.p, d_bits.p,
+                     d_cnt.p, d_good.p, d_slots.p, d_level_off.p, nullptr, nullptr, nullptr};
+    vg::BuildRun run{};
+    run.ef = ef_construction;
+    VG_TRY(scratch.alloc(vg::carve_run(nullptr, plan, m0, false, run, g)));
+    vg::carve_run(scratch.p, plan, m0, false, run, g);
     VG_HIP(hipMemsetAsync(d_ids.p, 0xFF, static_cast<size_t>(total_slots) * 4, st));
     VG_HIP(hipMemsetAsync(d_dist.p, 0, static_cast<size_t>(total_slots) * 4, st));
     VG_HIP(hipMemsetAsync(d_bits.p, 0, static_cast<size_t>(total_slots) * 8, st));
     VG_HIP(hipMemsetAsync(d_cnt.p, 0, static_cast<size_t>(total_rows) * 4, st));
     VG_HIP(hipMemsetAsync(d_good.p, 0, static_cast<size_t>(total_rows), st));
-    VG_HIP(hipMemsetAsync(d_rcnt.p, 0, static_cast<size_t>(total_rows) * 4, st));
-    VG_HIP(hipMemsetAsync(d_rfill.p, 0, static_cast<size_t>(total_rows) * 4, st));
-    VG_HIP(hipMemcpyAsync(d_slots.p, slots.data(), slots.size() * 4, hipMemcpyHostToDevice, st));
-    VG_HIP(hipMemcpyAsync(d_level_off.p, level_off.data(), level_off.size() * 8, hipMemcpyHostToDevice, st));
-    VG_HIP(hipMemcpyAsync(d_levels.p, levels.data(), levels.size() * 4, hipMemcpyHostToDevice, st));
-    VG_HIP(hipMemcpyAsync(d_pair_base.p, pair_base.data(), pair_base.size() * 8, hipMemcpyHostToDevice, st));
-    VG_HIP(hipMemcpyAsync(d_pair_node.p, pair_node.data(), pair_node.size() * 4, hipMemcpyHostToDevice, st));
-    VG_HIP(hipMemcpyAsync(d_pair_level.p, pair_level.data(), pair_level.size() * 4, hipMemcpyHostToDevice, st));
-    VG_HIP(hipStreamSynchronize(st));  // the host vectors above go out of use only at return, but be explicit
+    VG_HIP(hipMemcpyAsync(d_slots.p, plan.slots.data(), plan.slots.size() * 4, hipMemcpyHostToDevice, st));
+    VG_HIP(hipMemcpyAsync(d_level_off.p, plan.level_off.data(), plan.level_off.size() * 8, hipMemcpyHostToDevice, st));
+    VG_TRY(vg::run_batches(idx->ctx, st, g, plan, run, fn));
 
-    vg::BuildGraph g{idx->d_vectors, n, idx->dim, idx->metric, m0, m, d_ids.p, d_ids.p + n * m0, d_dist.p, d_bits.p,
-                     d_cnt.p, d_good.p, d_slots.p, d_level_off.p, nullptr, nullptr, nullptr};
-    vg::BuildRun run{};
-    run.ef = ef;
-    run.t_base = 0;
-    run.total_rows = total_rows;
-    run.pair_base = &pair_base;
-    run.levels = d_levels.p;
-    run.pair_base_d = d_pair_base.p;
-    run.pair_node = d_pair_node.p;
-    run.pair_level = d_pair_level.p;
-    run.vis = d_vis.p;
-    run.cand_ids = d_cand_ids.p;
-    run.cand_d = d_cand_d.p;
-    run.cand_n = d_cand_n.p;
-    run.rec_row = d_rec_row.p;
-    run.rec_t = d_rec_t.p;
-    run.rec_d = d_rec_d.p;
-    run.srt_t = d_srt_t.p;
-    run.srt_d = d_srt_d.p;
-    run.ord = d_ord.p;
-    run.ordd = d_ordd.p;
-    run.work = d_work.p;
-    run.roff = d_roff.p;
-    run.rcnt = d_rcnt.p;
-    run.rfill = d_rfill.p;
-    run.ctr = d_ctr.p;
-    run.totals = debug ? d_totals.p : nullptr;
-    VG_TRY(vg::run_batches(idx->ctx, st, g, batches, run, "vg_hnsw_build"));
-
-    // hand the graph to the index in vg_index_set_hnsw_graph's layout
-    uint32_t entry = 0;
-    int cur_top = levels[0];
-    for (int64_t t = 1; t < n; t++)
-        if (levels[t] > cur_top) {
-            cur_top = levels[t];
-            entry = static_cast<uint32_t>(t);
-        }
-    // the new arrays are allocated and filled BEFORE the index lets go of its previous graph: an allocation that
+    // the index's arrays are allocated and filled BEFORE the index lets go of its previous graph: an allocation that
     // fails here (the build's own scratch is still held) leaves the previous graph searchable, metadata and all
     vg::DevBuf<uint32_t> l0, adj;
     vg::DevBuf<float> l0c, adjc;  // the cached distances, for vg_hnsw_insert
@@ -1257,177 +1174,52 @@ VG_API int32_t vg_hnsw_build(vg_index *idx, int32_t m, int32_t ef_construction, 
     VG_HIP(hipMemcpyAsync(l0.p, d_ids.p, static_cast<size_t>(n) * m0 * 4, hipMemcpyDeviceToDevice, st));
     VG_HIP(hipMemcpyAsync(l0c.p, d_dist.p, static_cast<size_t>(n) * m0 * 4, hipMemcpyDeviceToDevice, st));
     if (upper_rows) {
-        VG_HIP(hipMemcpyAsync(adj.p, d_ids.p + n * m0, static_cast<size_t>(upper_rows) * m * 4,
-                              hipMemcpyDeviceToDevice, st));
-        VG_HIP(hipMemcpyAsync(adjc.p, d_dist.p + n * m0, static_cast<size_t>(upper_rows) * m * 4,
-                              hipMemcpyDeviceToDevice, st));
+        VG_HIP(hipMemcpyAsync(adj.p, g.ids_up, static_cast<size_t>(upper_rows) * m * 4, hipMemcpyDeviceToDevice, st));
+        VG_HIP(hipMemcpyAsync(adjc.p, d_dist.p + n * m0, static_cast<size_t>(upper_rows) * m * 4, hipMemcpyDeviceToDevice, st));
     }
     VG_HIP(hipStreamSynchronize(st));
-    for (uint32_t **slot : {&idx->d_hnsw_l0, &idx->d_hnsw_slot, &idx->d_hnsw_adj})
-        if (*slot) {
-            (void)hipFree(*slot);
-            *slot = nullptr;
-        }
-    if (idx->d_hnsw_level_off) {
-        (void)hipFree(idx->d_hnsw_level_off);
-        idx->d_hnsw_level_off = nullptr;
-    }
-    idx->d_hnsw_l0 = l0.release();
+    vg::adopt_hnsw_graph(idx, l0.release(), l0c.release(), d_slots.release(), adj.release(), adjc.release(),
+                         d_level_off.release(), m, plan);
     idx->l0_cap = 0;
-    for (float **c : {&idx->d_hnsw_l0_cdist, &idx->d_hnsw_adj_cdist})
-        if (*c) (void)hipFree(*c);
-    idx->d_hnsw_l0_cdist = l0c.release();
-    idx->d_hnsw_adj_cdist = adjc.release();
-    if (idx->d_hnsw_l0_dist) {  // the old graph's edge distances
-        (void)hipFree(idx->d_hnsw_l0_dist);
-        idx->d_hnsw_l0_dist = nullptr;
-    }
-    idx->d_hnsw_adj = adj.release();
-    idx->d_hnsw_slot = d_slots.release();
-    idx->d_hnsw_level_off = d_level_off.release();
-    idx->hnsw_m0 = m0;
-    idx->hnsw_m = m;
-    idx->hnsw_max_level = cur_top;
-    idx->hnsw_entry = entry;
     return VG_OK;
 }
-
-namespace vg {
-// room for n_new rows in a device array that holds n_old (its capacity: *cap rows, 0 = n_old), grown by half at
-// least so that a run of small inserts copies the array O(log n) times; bytes(r) = its size at r rows
-template <typename T, typename F>
-static int32_t grow_rows(T **p, int64_t *cap, int64_t n_old, int64_t n_new, F bytes, hipStream_t st)
-{
-    const int64_t have = std::max(*cap, n_old);
-    if (*p && n_new <= have) return VG_OK;
-    const int64_t want = std::max(n_new, have + have / 2);
-    T *q = nullptr;
-    VG_HIP(hipMalloc(reinterpret_cast<void **>(&q), std::max<size_t>(bytes(want), 1)));
-    if (*p && n_old) {
-        const hipError_t e = hipMemcpyAsync(q, *p, bytes(n_old), hipMemcpyDeviceToDevice, st);
-        if (e != hipSuccess) {
-            (void)hipFree(q);
-            VG_HIP(e);
-        }
-    }
-    VG_HIP(hipStreamSynchronize(st));
-    if (*p) (void)hipFree(*p);
-    *p = q;
-    *cap = want;
-    return VG_OK;
-}
-}  // namespace vg
 
 VG_API int32_t vg_hnsw_insert(vg_index *idx, const float *rows, int64_t count, int32_t m, int32_t ef_construction,
                               int32_t max_batch, int32_t growth_div, void *stream)
 {
-    VG_CHECK(idx, VG_ERR_INVALID_ARG, "vg_hnsw_insert: NULL index");
-    VG_CHECK(count >= 0 && (count == 0 || rows), VG_ERR_INVALID_ARG, "vg_hnsw_insert: negative count or NULL rows");
+    const char *fn = "vg_hnsw_insert";
+    VG_CHECK(idx, VG_ERR_INVALID_ARG, "%s: NULL index", fn);
+    VG_CHECK(count >= 0 && (count == 0 || rows), VG_ERR_INVALID_ARG, "%s: negative count or NULL rows", fn);
     const int64_t n_old = idx->n;
     VG_CHECK(n_old == 0 || (idx->d_vectors && idx->d_hnsw_l0), VG_ERR_NOT_READY,
-             "vg_hnsw_insert: the index has rows but no HNSW graph (vg_hnsw_build first)");
+             "%s: the index has rows but no HNSW graph (vg_hnsw_build first)", fn);
     VG_CHECK(idx->metric != VG_METRIC_HAMMING, VG_ERR_UNSUPPORTED, "unsupported metric for float32: Hamming");
-    VG_CHECK(m >= 2 && m <= 32, VG_ERR_UNSUPPORTED, "vg_hnsw_insert: M=%d must be in 2..32 (M0 = 2M <= 64)", m);
-    VG_CHECK(ef_construction >= 1 && ef_construction <= vg::kBuildMaxEf, VG_ERR_UNSUPPORTED,
-             "vg_hnsw_insert: ef_construction=%d must be in 1..%d", ef_construction, vg::kBuildMaxEf);
-    VG_CHECK(max_batch >= 1 && growth_div >= 1, VG_ERR_INVALID_ARG, "vg_hnsw_insert: max_batch and growth_div must be >= 1");
-    VG_CHECK(n_old + count < (int64_t(1) << 31), VG_ERR_UNSUPPORTED, "vg_hnsw_insert: at most 2^31 rows");
+    VG_TRY(vg::check_hnsw_build_args(fn, m, ef_construction, max_batch, growth_div));
+    VG_CHECK(n_old + count < (int64_t(1) << 31), VG_ERR_UNSUPPORTED, "%s: at most 2^31 rows", fn);
     VG_CHECK(n_old == 0 || (m == idx->hnsw_m && idx->hnsw_m0 == 2 * m), VG_ERR_INVALID_ARG,
-             "vg_hnsw_insert: M=%d does not match the graph's (M=%d, M0=%d)", m, idx->hnsw_m, idx->hnsw_m0);
-    const char *held = (idx->d_pq_tiles || idx->d_pq_rows) ? "PQ codes"
-                       : idx->d_sq_tiles                   ? "SQ8 codes"
-                       : idx->d_int4_rows                  ? "INT4 codes"
-                       : (idx->d_rq_tiles || idx->d_rq_rows) ? "RaBitQ codes"
-                       : idx->d_centroids                  ? "IVF partitions"
-                       : idx->d_vamana                     ? "a Vamana graph"
-                       : idx->sq_nom.rows                  ? "an SQ8 nomination image"
-                       : idx->pq_nom.rows                  ? "a PQ nomination image"
-                                                           : nullptr;
-    VG_CHECK(!held, VG_ERR_UNSUPPORTED, "vg_hnsw_insert: the index holds %s, which the new rows would lack (segment state, "
-             "not a memtable's)", held);
+             "%s: M=%d does not match the graph's (M=%d, M0=%d)", fn, m, idx->hnsw_m, idx->hnsw_m0);
+    const char *held = vg::held_segment_state(idx);
+    VG_CHECK(!held, VG_ERR_UNSUPPORTED, "%s: the index holds %s, which the new rows would lack (segment state, "
+             "not a memtable's)", fn, held);
     if (count == 0) return VG_OK;
     VG_HIP(hipSetDevice(idx->ctx->device));
     hipStream_t st = vg::pick_stream(idx->ctx, stream);
     const int64_t n_new = n_old + count;
     const int dim = idx->dim;
     const int m0 = 2 * m;
-    const int ef = ef_construction;
 
     // ---- the plan: levels, slots of the new nodes, batches (host) ----
-    const double mult = 1.0 / std::log(static_cast<double>(m));
-    std::vector<int32_t> levels(static_cast<size_t>(count));
-    int new_top = 0;
-    for (int64_t i = 0; i < count; i++) {
-        levels[i] = vg::level_for_id(static_cast<uint64_t>(n_old + i), mult);
-        new_top = std::max(new_top, levels[i]);
-    }
     const int l_old = n_old ? idx->hnsw_max_level : 0;
     std::vector<int64_t> old_off(static_cast<size_t>(l_old) + 1, 0);
     if (l_old > 0) {
         VG_HIP(hipMemcpyAsync(old_off.data(), idx->d_hnsw_level_off, old_off.size() * 8, hipMemcpyDeviceToHost, st));
         VG_HIP(hipStreamSynchronize(st));
     }
-    const int l_new = std::max(l_old, new_top);
-    // new nodes' upper rows go at the end of each level's table (slots in id order: a full build's layout)
-    std::vector<int64_t> new_off(static_cast<size_t>(l_new) + 1, 0);
-    std::vector<uint32_t> fresh(static_cast<size_t>(l_new) * count);
-    for (int l = 0; l < l_new; l++) {
-        uint32_t next = static_cast<uint32_t>(l < l_old ? old_off[l + 1] - old_off[l] : 0);
-        for (int64_t i = 0; i < count; i++) fresh[static_cast<size_t>(l) * count + i] = levels[i] >= l + 1 ? next++ : VG_INVALID_ID;
-        new_off[l + 1] = new_off[l] + next;
-    }
-    const int64_t upper_rows = new_off[l_new];
-    const int64_t total_rows = n_new + upper_rows;
-    VG_CHECK(total_rows < (int64_t(1) << 32) - 1, VG_ERR_UNSUPPORTED, "vg_hnsw_insert: too many rows");
-
-    using Batch = vg::BuildBatch;
-    std::vector<Batch> batches;
-    std::vector<int64_t> pair_base(static_cast<size_t>(count) + 1, 0);  // node t: pair_base[t - n_old]
-    uint32_t entry = n_old ? idx->hnsw_entry : 0;
-    int cur_top = n_old ? l_old : levels[0];
-    {
-        int64_t done = n_old ? n_old : 1;  // an empty graph: row 0 becomes the entry point, with no links
-        while (done < n_new) {
-            int64_t b = done / growth_div;
-            b = std::max<int64_t>(1, std::min<int64_t>(b, max_batch));
-            b = std::min(b, n_new - done);
-            Batch bt{done, b, 0, entry, cur_top};
-            for (int64_t t = done; t < done + b; t++) {
-                const int np = std::min(levels[t - n_old], cur_top) + 1;
-                pair_base[t - n_old + 1] = pair_base[t - n_old] + np;
-                bt.npairs += np;
-            }
-            for (int64_t t = done; t < done + b; t++)  // updateEntryPoint hnsw.go:885-900
-                if (levels[t - n_old] > cur_top) {
-                    cur_top = levels[t - n_old];
-                    entry = static_cast<uint32_t>(t);
-                }
-            batches.push_back(bt);
-            done += b;
-        }
-    }
-    const int64_t npairs = pair_base[count];
-    std::vector<uint32_t> pair_node(static_cast<size_t>(std::max<int64_t>(npairs, 1)));
-    std::vector<int32_t> pair_level(pair_node.size());
-    for (const Batch &bt : batches)
-        for (int64_t t = bt.t0; t < bt.t0 + bt.size; t++)
-            for (int l = 0; l <= std::min(levels[t - n_old], bt.cur_top); l++) {
-                pair_node[static_cast<size_t>(pair_base[t - n_old] + l)] = static_cast<uint32_t>(t);
-                pair_level[static_cast<size_t>(pair_base[t - n_old] + l)] = l;
-            }
-    int64_t max_pairs = 1, max_b = 1;
-    for (const auto &bt : batches) {
-        max_pairs = std::max(max_pairs, bt.npairs);
-        max_b = std::max(max_b, bt.size);
-    }
-    const int64_t vis_words_max = (n_new + 31) / 32;
-    VG_CHECK(max_b * vis_words_max * 4 <= (int64_t(1) << 32), VG_ERR_UNSUPPORTED,
-             "vg_hnsw_insert: max_batch=%d needs more than 4 GiB of visited bitmaps at %lld rows", max_batch,
-             static_cast<long long>(n_new));
-    // state rows: one per new (node, level) pair, then one per derived row.  A row is derived at most once per call
-    // and only when a record targets it: at most one per record, at most one per row.  (Derived rows are the graph's
-    // older rows and the rows a new node gets above the top level of its batch, which no pair makes.)
-    const int64_t n_state = npairs + std::min(total_rows, npairs * m0);
+    const vg::HnswBuildPlan plan = vg::plan_hnsw_build(n_old, count, m, max_batch, growth_div, idx->hnsw_entry, l_old, old_off);
+    VG_TRY(vg::check_plan(fn, plan, max_batch));
+    const std::vector<int64_t> &new_off = plan.level_off;
+    const int l_new = plan.top;
+    const int64_t upper_rows = plan.upper_rows;
 
     // ---- the rows and everything sized by n ----
     vg::DevIn<float> in;
@@ -1494,123 +1286,44 @@ VG_API int32_t vg_hnsw_insert(vg_index *idx, const float *rows, int64_t count, i
                                       static_cast<size_t>(old_off[l + 1] - old_off[l]) * m * 4, hipMemcpyDeviceToDevice, st));
         }
 
-    // ---- per-call scratch: the batches' buffers, sized by the call's largest batch, and the state rows ----
-    const int64_t max_rec = max_pairs * m0;
-    vg::ArenaCall ar(idx->ctx, st);
-    const int a_fresh = ar.add(fresh.size() * 4 + 4), a_lev = ar.add(levels.size() * 4), a_pb = ar.add(pair_base.size() * 8),
-              a_pn = ar.add(pair_node.size() * 4), a_pl = ar.add(pair_level.size() * 4),
-              a_vis = ar.add(static_cast<size_t>(max_b * vis_words_max) * 4),
-              a_cid = ar.add(static_cast<size_t>(max_pairs) * ef * 4), a_cd = ar.add(static_cast<size_t>(max_pairs) * ef * 4),
-              a_cn = ar.add(static_cast<size_t>(max_pairs) * 4), a_rr = ar.add(static_cast<size_t>(max_rec) * 4),
-              a_rt = ar.add(static_cast<size_t>(max_rec) * 4), a_rd = ar.add(static_cast<size_t>(max_rec) * 4),
-              a_st = ar.add(static_cast<size_t>(max_rec) * 4), a_sd = ar.add(static_cast<size_t>(max_rec) * 4),
-              a_or = ar.add(static_cast<size_t>(max_rec) * 4), a_od = ar.add(static_cast<size_t>(max_rec) * 4),
-              a_work = ar.add(static_cast<size_t>(std::min(max_rec, total_rows)) * 4),
-              a_roff = ar.add(static_cast<size_t>(total_rows) * 4), a_rcnt = ar.add(static_cast<size_t>(total_rows) * 4),
-              a_rfill = ar.add(static_cast<size_t>(total_rows) * 4), a_smap = ar.add(static_cast<size_t>(total_rows) * 4),
-              a_rnode = ar.add(static_cast<size_t>(total_rows) * 4), a_srow = ar.add(static_cast<size_t>(n_state) * 4),
-              a_dist = ar.add(static_cast<size_t>(n_state) * vg::kStateStride * 4),
-              a_bits = ar.add(static_cast<size_t>(n_state) * vg::kStateStride * 8), a_cnt = ar.add(static_cast<size_t>(n_state) * 4),
-              a_good = ar.add(static_cast<size_t>(n_state)), a_ctr = ar.add(sizeof(vg::LinkCounters)),
-              a_tot = ar.add(sizeof(vg::LinkTotals)), a_next = ar.add(8);
-    VG_TRY(ar.commit());
-    uint32_t *d_fresh = ar.get<uint32_t>(a_fresh);
-    VG_HIP(hipMemcpyAsync(d_fresh, fresh.data(), fresh.size() * 4, hipMemcpyHostToDevice, st));
-    if (l_new > 0) {
-        const int64_t e = static_cast<int64_t>(l_new) * n_new;
-        VG_LAUNCH(vg::slot_relayout_kernel, dim3(static_cast<unsigned>((e + 255) / 256)), dim3(256), 0, st, idx->d_hnsw_slot,
-                  n_old, l_old, d_fresh, n_new, l_new, slots.p);
-    }
+    // ---- per-call scratch, on the context arena: the batches' and the state rows', then the plan's slot table ----
+    vg::BuildGraph g{idx->d_vectors, n_new, dim, idx->metric, m0, m, idx->d_hnsw_l0, adj.p, nullptr, nullptr, nullptr, nullptr,
+                     slots.p, level_off.p, nullptr, nullptr, nullptr};
     vg::BuildRun run{};
-    run.ef = ef;
-    run.t_base = n_old;
-    run.total_rows = total_rows;
-    run.pair_base = &pair_base;
-    run.levels = ar.get<int32_t>(a_lev);
-    run.pair_base_d = ar.get<int64_t>(a_pb);
-    run.pair_node = ar.get<uint32_t>(a_pn);
-    run.pair_level = ar.get<int32_t>(a_pl);
-    run.vis = ar.get<uint32_t>(a_vis);
-    run.cand_ids = ar.get<uint32_t>(a_cid);
-    run.cand_d = ar.get<float>(a_cd);
-    run.cand_n = ar.get<int32_t>(a_cn);
-    run.rec_row = ar.get<uint32_t>(a_rr);
-    run.rec_t = ar.get<uint32_t>(a_rt);
-    run.rec_d = ar.get<float>(a_rd);
-    run.srt_t = ar.get<uint32_t>(a_st);
-    run.srt_d = ar.get<float>(a_sd);
-    run.ord = ar.get<uint32_t>(a_or);
-    run.ordd = ar.get<float>(a_od);
-    run.work = ar.get<uint32_t>(a_work);
-    run.roff = ar.get<uint32_t>(a_roff);
-    run.rcnt = ar.get<int32_t>(a_rcnt);
-    run.rfill = ar.get<int32_t>(a_rfill);
-    run.ctr = ar.get<vg::LinkCounters>(a_ctr);
-    run.totals = vg::hook(vg::kHookBuildDebug) ? ar.get<vg::LinkTotals>(a_tot) : nullptr;
-    run.s_next = ar.get<unsigned int>(a_next);
-    run.derived = run.s_next + 1;
-    run.s_first = npairs;
+    run.ef = ef_construction;
     run.l0_dist = idx->d_hnsw_l0_dist;
     run.dist_rows = idx->d_hnsw_l0_dist ? n_old : 0;
     run.cd0 = keep_cd ? idx->d_hnsw_l0_cdist : nullptr;
     run.cdu = keep_cd ? adjc.p : nullptr;
-    VG_HIP(hipMemcpyAsync(const_cast<int32_t *>(run.levels), levels.data(), levels.size() * 4, hipMemcpyHostToDevice, st));
-    VG_HIP(hipMemcpyAsync(const_cast<int64_t *>(run.pair_base_d), pair_base.data(), pair_base.size() * 8, hipMemcpyHostToDevice, st));
-    VG_HIP(hipMemcpyAsync(const_cast<uint32_t *>(run.pair_node), pair_node.data(), pair_node.size() * 4, hipMemcpyHostToDevice, st));
-    VG_HIP(hipMemcpyAsync(const_cast<int32_t *>(run.pair_level), pair_level.data(), pair_level.size() * 4, hipMemcpyHostToDevice, st));
-    VG_HIP(hipMemsetAsync(run.rcnt, 0, static_cast<size_t>(total_rows) * 4, st));
-    VG_HIP(hipMemsetAsync(run.rfill, 0, static_cast<size_t>(total_rows) * 4, st));
-    int32_t *smap = ar.get<int32_t>(a_smap);
-    VG_HIP(hipMemsetAsync(smap, 0xFF, static_cast<size_t>(total_rows) * 4, st));
-    VG_HIP(hipMemsetAsync(run.s_next, 0, 8, st));
-    if (run.totals) VG_HIP(hipMemsetAsync(run.totals, 0, sizeof(vg::LinkTotals), st));
-    vg::BuildGraph g{idx->d_vectors, n_new, dim, idx->metric, m0, m, idx->d_hnsw_l0, adj.p,
-                     ar.get<float>(a_dist), ar.get<uint64_t>(a_bits), ar.get<int32_t>(a_cnt), ar.get<uint8_t>(a_good),
-                     slots.p, level_off.p, smap, ar.get<uint32_t>(a_srow), ar.get<uint32_t>(a_rnode)};
-    VG_TRY(vg::run_batches(idx->ctx, st, g, batches, run, "vg_hnsw_insert"));
-    if (keep_cd && n_state > 0) {
-        VG_LAUNCH(vg::state_writeback_kernel, dim3(static_cast<unsigned>(n_state)), dim3(64), 0, st, g, run.s_next, npairs,
-                  idx->d_hnsw_l0_cdist, adjc.p);
+    vg::ArenaCall ar(idx->ctx, st);
+    const int a_run = ar.add(vg::carve_run(nullptr, plan, m0, true, run, g)), a_fresh = ar.add(plan.slots.size() * 4);
+    VG_TRY(ar.commit());
+    vg::carve_run(ar.get<char>(a_run), plan, m0, true, run, g);
+    // The plan's table holds the new nodes only ([l_new][count]); the index's holds every node: the older nodes' slots
+    // are merged in on the device.  (vg_hnsw_build needs no such step: with no older nodes the two tables are one.)
+    if (l_new > 0) {
+        uint32_t *d_fresh = ar.get<uint32_t>(a_fresh);
+        VG_HIP(hipMemcpyAsync(d_fresh, plan.slots.data(), plan.slots.size() * 4, hipMemcpyHostToDevice, st));
+        const int64_t e = static_cast<int64_t>(l_new) * n_new;
+        VG_LAUNCH(vg::slot_relayout_kernel, dim3(static_cast<unsigned>((e + 255) / 256)), dim3(256), 0, st, idx->d_hnsw_slot,
+                  n_old, l_old, d_fresh, n_new, l_new, slots.p);
+    }
+    VG_TRY(vg::run_batches(idx->ctx, st, g, plan, run, fn));
+    if (keep_cd && run.n_state > 0) {
+        VG_LAUNCH(vg::state_writeback_kernel, dim3(static_cast<unsigned>(run.n_state)), dim3(64), 0, st, g, run.s_next,
+                  run.s_first, idx->d_hnsw_l0_cdist, adjc.p);
         VG_HIP(hipStreamSynchronize(st));
     }
     if (run.totals) {
         unsigned int h[2] = {0, 0};
         VG_HIP(hipMemcpy(h, run.s_next, sizeof h, hipMemcpyDeviceToHost));
-        fprintf(stderr, "vg_hnsw_insert: %lld rows, %lld batches, %u rows' build state derived\n", static_cast<long long>(count),
-                static_cast<long long>(batches.size()), h[1]);
+        fprintf(stderr, "%s: %lld rows, %lld batches, %u rows' build state derived\n", fn, static_cast<long long>(count),
+                static_cast<long long>(plan.batches.size()), h[1]);
     }
 
-    // ---- hand over: the layer-0 table was grown in place; the upper levels are swapped in ----
-    for (uint32_t **slot : {&idx->d_hnsw_slot, &idx->d_hnsw_adj})
-        if (*slot) {
-            (void)hipFree(*slot);
-            *slot = nullptr;
-        }
-    if (idx->d_hnsw_level_off) {
-        (void)hipFree(idx->d_hnsw_level_off);
-        idx->d_hnsw_level_off = nullptr;
-    }
-    if (idx->d_hnsw_l0_dist) {  // cached for the old lists: the predicate-aware walk recomputes them (same values)
-        (void)hipFree(idx->d_hnsw_l0_dist);
-        idx->d_hnsw_l0_dist = nullptr;
-    }
-    idx->d_hnsw_slot = slots.release();
-    idx->d_hnsw_adj = adj.release();
-    idx->d_hnsw_level_off = level_off.release();
-    if (idx->d_hnsw_adj_cdist) {
-        (void)hipFree(idx->d_hnsw_adj_cdist);
-        idx->d_hnsw_adj_cdist = nullptr;
-    }
-    if (keep_cd)
-        idx->d_hnsw_adj_cdist = adjc.release();
-    else if (idx->d_hnsw_l0_cdist) {
-        (void)hipFree(idx->d_hnsw_l0_cdist);
-        idx->d_hnsw_l0_cdist = nullptr;
-    }
-    idx->hnsw_m0 = m0;
-    idx->hnsw_m = m;
-    idx->hnsw_max_level = cur_top;
-    idx->hnsw_entry = entry;
+    // ---- hand over: the layer-0 tables were grown in place; the upper levels are swapped in ----
+    vg::adopt_hnsw_graph(idx, idx->d_hnsw_l0, keep_cd ? idx->d_hnsw_l0_cdist : nullptr, slots.release(), adj.release(),
+                         keep_cd ? adjc.release() : nullptr, level_off.release(), m, plan);
     idx->n = n_new;
     return VG_OK;
 }

@@ -442,15 +442,7 @@ VG_API int32_t vg_hnsw_compact(vg_index *idx, int32_t ef_construction, int32_t m
              "%s: ef_construction=%d must be in 1..%d (0 = 300)", fn, ef_construction, vg::kCompactMaxEf);
     const int m = idx->hnsw_m, m0 = idx->hnsw_m0;
     VG_CHECK(m >= 2 && m <= 32 && m0 == 2 * m, VG_ERR_UNSUPPORTED, "%s: the graph's M=%d, M0=%d: M must be in 2..32 and M0 = 2M", fn, m, m0);
-    const char *held = (idx->d_pq_tiles || idx->d_pq_rows) ? "PQ codes"
-                       : idx->d_sq_tiles                   ? "SQ8 codes"
-                       : idx->d_int4_rows                  ? "INT4 codes"
-                       : (idx->d_rq_tiles || idx->d_rq_rows) ? "RaBitQ codes"
-                       : idx->d_centroids                  ? "IVF partitions"
-                       : idx->d_vamana                     ? "a Vamana graph"
-                       : idx->sq_nom.rows                  ? "an SQ8 nomination image"
-                       : idx->pq_nom.rows                  ? "a PQ nomination image"
-                                                           : nullptr;
+    const char *held = vg::held_segment_state(idx);
     VG_CHECK(!held, VG_ERR_UNSUPPORTED, "%s: the index holds %s (segment state, not a memtable's)", fn, held);
     VG_CHECK(idx->hnsw_max_level < 63, VG_ERR_UNSUPPORTED, "%s: %d levels (at most 63)", fn, idx->hnsw_max_level + 1);
     if (stats) *stats = vg_hnsw_compact_stats{0, 0, 0, 0};
@@ -570,16 +562,10 @@ VG_API int32_t vg_hnsw_compact(vg_index *idx, int32_t ef_construction, int32_t m
     VG_HIP(hipMemcpyAsync(h_counters, counters.ptr, sizeof h_counters, hipMemcpyDeviceToHost, st));
     VG_HIP(hipStreamSynchronize(st));
     if (built) {
-        if (idx->d_hnsw_l0_dist) {  // recomputed from the rows for the old lists: dropped, as vg_hnsw_insert drops it
-            (void)hipFree(idx->d_hnsw_l0_dist);
-            idx->d_hnsw_l0_dist = nullptr;
-        }
-    } else {
-        for (float **stale : {&idx->d_hnsw_l0_cdist, &idx->d_hnsw_adj_cdist})  // (a partial set: never read as the graph's)
-            if (*stale) {
-                (void)hipFree(*stale);
-                *stale = nullptr;
-            }
+        vg::drop_device(&idx->d_hnsw_l0_dist);  // recomputed from the rows for the old lists: dropped, as vg_hnsw_insert drops it
+    } else {  // (a partial set: never read as the graph's)
+        vg::drop_device(&idx->d_hnsw_l0_cdist);
+        vg::drop_device(&idx->d_hnsw_adj_cdist);
     }
     if (stats) {
         stats->repaired_nodes = nrep;

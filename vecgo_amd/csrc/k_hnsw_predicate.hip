@@ -217,11 +217,8 @@ __global__ __launch_bounds__(64) void hnsw_predicate_kernel(
 int32_t hnsw_edge_distances(vg_index *idx, const float *l0_dist, hipStream_t st)
 {
     const size_t count = static_cast<size_t>(idx->n) * idx->hnsw_m0;
-    if (idx->d_hnsw_l0_dist) {
-        VG_HIP(hipStreamSynchronize(st));  // earlier searches may still read the old array
-        VG_HIP(hipFree(idx->d_hnsw_l0_dist));
-        idx->d_hnsw_l0_dist = nullptr;
-    }
+    if (idx->d_hnsw_l0_dist) VG_HIP(hipStreamSynchronize(st));  // earlier searches may still read the old array
+    vg::drop_device(&idx->d_hnsw_l0_dist);
     if (count == 0) return VG_OK;
     float *d = nullptr;
     VG_HIP(hipMalloc(reinterpret_cast<void **>(&d), count * sizeof(float)));
@@ -264,10 +261,7 @@ VG_API int32_t vg_index_set_hnsw_tombstones(vg_index *idx, const uint8_t *delete
     VG_HIP(hipSetDevice(idx->ctx->device));
     hipStream_t st = vg::pick_stream(idx->ctx, stream);
     VG_HIP(hipStreamSynchronize(st));  // earlier searches may still read the old bitmap
-    if (idx->d_hnsw_tomb) {
-        VG_HIP(hipFree(idx->d_hnsw_tomb));
-        idx->d_hnsw_tomb = nullptr;
-    }
+    vg::drop_device(&idx->d_hnsw_tomb);
     idx->tomb_cap = 0;
     const size_t bytes = static_cast<size_t>((idx->n + 7) / 8);
     if (deleted == nullptr || bytes == 0) return VG_OK;

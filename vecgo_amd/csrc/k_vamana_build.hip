@@ -13,15 +13,17 @@
 //                           a visited bitmap of n bits per node in HBM.
 //   2. vb_prune_kernel      one workgroup per node: robustPrune over the search's l results and the old list.
 //   3. vb_write_kernel      the new lists into the graph; one back-edge record per (node, slot).
-//   4. vb_count / offsets / fill group the records by target; vb_link_kernel: one workgroup per target sorts its
+//   4. the records are grouped by target (vg_group_records.hpp, vb_fill_kernel); vb_link_kernel: one workgroup per target sorts its
 //      records by record index (= (source, slot) order) and applies addBackEdge to its list in LDS.
 // Every distance is the reference's pair kernel in its summation order (vg_exact.hpp, distance.Provider).
 #include <algorithm>
 #include <cfloat>
 #include <vector>
 
+#include "vg_build_plan.hpp"
 #include "vg_device.hpp"
 #include "vg_exact.hpp"
+#include "vg_group_records.hpp"
 #include "vg_internal.hpp"
 #include "vg_search.hpp"
 
@@ -292,48 +294,8 @@ __global__ void vb_write_kernel(const uint32_t *__restrict__ lists, int64_t coun
 }
 
 // ---- 4. back edges -----------------------------------------------------------------------------------
-struct VbCounters {
-    unsigned int nwork, total;
-};
-
-// records: rec[i] = target of record i (VG_INVALID_ID = none); record i = (source node0 + i / r, slot i % r)
-__global__ void vb_count_kernel(const uint32_t *__restrict__ rec, int64_t nrec, int32_t *__restrict__ rcnt,
-                                uint32_t *__restrict__ work, VbCounters *__restrict__ ctr)
-{
-    const int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-    const int lane = threadIdx.x & 63;
-    const uint32_t t = i < nrec ? rec[i] : VG_INVALID_ID;
-    const bool first = t != VG_INVALID_ID && atomicAdd(&rcnt[t], 1) == 0;
-    const uint64_t m = __ballot(first);
-    if (m == 0) return;
-    unsigned int b = 0;
-    if (lane == __builtin_ctzll(m)) b = atomicAdd(&ctr->nwork, static_cast<unsigned int>(__popcll(m)));
-    b = __shfl(b, __builtin_ctzll(m));
-    if (first) work[b + __popcll(m & ((1ull << lane) - 1))] = t;
-}
-
-__global__ void vb_offsets_kernel(const uint32_t *__restrict__ work, const int32_t *__restrict__ rcnt,
-                                  uint32_t *__restrict__ roff, VbCounters *__restrict__ ctr)
-{
-    const unsigned int w = blockIdx.x * blockDim.x + threadIdx.x;
-    const int lane = threadIdx.x & 63;
-    const bool live = w < ctr->nwork;
-    const uint32_t t = live ? work[w] : 0;
-    const unsigned int mine = live ? static_cast<unsigned int>(rcnt[t]) : 0u;
-    unsigned int incl = mine;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const unsigned int up = __shfl_up(incl, d);
-        if (lane >= d) incl += up;
-    }
-    const unsigned int total = __shfl(incl, 63);
-    if (total == 0) return;
-    unsigned int b = 0;
-    if (lane == 63) b = atomicAdd(&ctr->total, total);
-    b = __shfl(b, 63);
-    if (live) roff[t] = b + incl - mine;
-}
-
+// records: rec[i] = target of record i (VG_INVALID_ID = none); record i = (source node0 + i / r, slot i % r); grouped by
+// target: vg_group_records.hpp
 __global__ void vb_fill_kernel(const uint32_t *__restrict__ rec, int64_t nrec, const uint32_t *__restrict__ roff,
                                int32_t *__restrict__ rfill, uint32_t *__restrict__ srt)
 {
@@ -350,7 +312,7 @@ __global__ void vb_fill_kernel(const uint32_t *__restrict__ rec, int64_t nrec, c
 __global__ __launch_bounds__(kVbThreads) void vb_link_kernel(const float *__restrict__ base, int dim, bool dot, int r,
                                                              float alpha, int64_t node0, uint32_t *__restrict__ graph,
                                                              const uint32_t *__restrict__ work,
-                                                             const VbCounters *__restrict__ ctr, int32_t *__restrict__ rcnt,
+                                                             const GroupCounters *__restrict__ ctr, int32_t *__restrict__ rcnt,
                                                              int32_t *__restrict__ rfill, const uint32_t *__restrict__ roff,
                                                              const uint32_t *__restrict__ srt)
 {
@@ -414,26 +376,6 @@ __global__ __launch_bounds__(kVbThreads) void vb_link_kernel(const float *__rest
     }
 }
 
-template <typename T>
-struct VbBuf {
-    T *p = nullptr;
-    ~VbBuf()
-    {
-        if (p) (void)hipFree(p);
-    }
-    int32_t alloc(size_t count)
-    {
-        VG_HIP(hipMalloc(reinterpret_cast<void **>(&p), std::max<size_t>(count, 1) * sizeof(T)));
-        return VG_OK;
-    }
-    T *release()
-    {
-        T *q = p;
-        p = nullptr;
-        return q;
-    }
-};
-
 static int next_pow2(int x)
 {
     int p = 1;
@@ -467,7 +409,7 @@ VG_API int32_t vg_vamana_build(vg_index *idx, int32_t r, int32_t l, float alpha,
     const bool dot = idx->metric != VG_METRIC_L2;  // Cosine and Dot: raw Dot, ascending (distance.go:97-106)
     const float *base = idx->d_vectors;
 
-    vg::VbBuf<uint32_t> g;
+    vg::DevBuf<uint32_t> g;
     VG_TRY(g.alloc(static_cast<size_t>(n) * r));
     if (init_graph) {  // validated and compacted (empty slots dropped, order kept) on the host
         std::vector<uint32_t> h(static_cast<size_t>(n) * r);
@@ -497,8 +439,8 @@ VG_API int32_t vg_vamana_build(vg_index *idx, int32_t r, int32_t l, float alpha,
     }
 
     // centroid and entry point (writer.go:386-404)
-    vg::VbBuf<float> cen;
-    vg::VbBuf<unsigned long long> best;
+    vg::DevBuf<float> cen;
+    vg::DevBuf<unsigned long long> best;
     VG_TRY(cen.alloc(static_cast<size_t>(dim)));
     VG_TRY(best.alloc(1));
     VG_HIP(hipMemsetAsync(best.p, 0xFF, 8, st));
@@ -516,9 +458,9 @@ VG_API int32_t vg_vamana_build(vg_index *idx, int32_t r, int32_t l, float alpha,
     const int64_t vis_words = (n + 31) / 32;
     const int64_t vis_cap = vg::scratch_cap(idx->ctx);
     const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(max_b, vis_cap / (vis_words * 4)));
-    vg::VbBuf<uint32_t> vis, res, nl, work, roff, srt;
-    vg::VbBuf<int32_t> rcnt, rfill;
-    vg::VbBuf<vg::VbCounters> ctr;
+    vg::DevBuf<uint32_t> vis, res, nl, work, roff, srt;
+    vg::DevBuf<int32_t> rcnt, rfill;
+    vg::DevBuf<vg::GroupCounters> ctr;
     VG_TRY(vis.alloc(static_cast<size_t>(chunk * vis_words)));
     VG_TRY(res.alloc(static_cast<size_t>(max_b) * l));
     VG_TRY(nl.alloc(static_cast<size_t>(max_b) * r));
@@ -546,7 +488,7 @@ VG_API int32_t vg_vamana_build(vg_index *idx, int32_t r, int32_t l, float alpha,
     for (int pass = 0; pass < 2; pass++) {  // writer.go:430-457
         const float a = pass == 0 ? 1.0f : alpha;
         for (int64_t t0 = 0; t0 < n;) {
-            const int64_t b = std::min(std::max<int64_t>(1, std::min<int64_t>(processed / growth_div, max_batch)), n - t0);
+            const int64_t b = vg::next_batch(processed, (pass + 1) * n, max_batch, growth_div);  // (= n - t0 at the most)
             {
                 vg::ProfScope prof(idx->ctx, "vamana_build_search", st);
                 for (int64_t c0 = 0; c0 < b; c0 += chunk) {
@@ -566,13 +508,10 @@ VG_API int32_t vg_vamana_build(vg_index *idx, int32_t r, int32_t l, float alpha,
             {
                 vg::ProfScope prof(idx->ctx, "vamana_build_backedge", st);
                 const int64_t nrec = b * r;
-                const unsigned gb = static_cast<unsigned>((nrec + 255) / 256);
                 const int64_t max_work = std::min(nrec, n);
-                VG_HIP(hipMemsetAsync(ctr.p, 0, sizeof(vg::VbCounters), st));
-                VG_LAUNCH(vg::vb_count_kernel, dim3(gb), dim3(256), 0, st, nl.p, nrec, rcnt.p, work.p, ctr.p);
-                VG_LAUNCH(vg::vb_offsets_kernel, dim3(static_cast<unsigned>((max_work + 255) / 256)), dim3(256), 0, st,
-                          work.p, rcnt.p, roff.p, ctr.p);
-                VG_LAUNCH(vg::vb_fill_kernel, dim3(gb), dim3(256), 0, st, nl.p, nrec, roff.p, rfill.p, srt.p);
+                VG_TRY(vg::group_count_offsets(nl.p, nrec, max_work, rcnt.p, work.p, roff.p, ctr.p, st));
+                VG_LAUNCH(vg::vb_fill_kernel, dim3(static_cast<unsigned>((nrec + 255) / 256)), dim3(256), 0, st, nl.p, nrec,
+                          roff.p, rfill.p, srt.p);
                 VG_LAUNCH(vg::vb_link_kernel, dim3(static_cast<unsigned>(max_work)), dim3(vg::kVbThreads), link_lds, st,
                           base, dim, dot, r, a, t0, g.p, work.p, ctr.p, rcnt.p, rfill.p, roff.p, srt.p);
             }

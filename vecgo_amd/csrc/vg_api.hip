@@ -281,14 +281,10 @@ VG_API int32_t vg_index_destroy(vg_index *idx)
     if (idx->d_vectors_bf16) (void)hipFree(idx->d_vectors_bf16);
     if (idx->d_rq_tiles) (void)hipFree(idx->d_rq_tiles);
     if (idx->d_rq_norms) (void)hipFree(idx->d_rq_norms);
-    if (idx->d_hnsw_l0) (void)hipFree(idx->d_hnsw_l0);
-    if (idx->d_hnsw_l0_dist) (void)hipFree(idx->d_hnsw_l0_dist);
-    if (idx->d_hnsw_l0_cdist) (void)hipFree(idx->d_hnsw_l0_cdist);
-    if (idx->d_hnsw_adj_cdist) (void)hipFree(idx->d_hnsw_adj_cdist);
-    if (idx->d_hnsw_tomb) (void)hipFree(idx->d_hnsw_tomb);
-    if (idx->d_hnsw_slot) (void)hipFree(idx->d_hnsw_slot);
-    if (idx->d_hnsw_adj) (void)hipFree(idx->d_hnsw_adj);
-    if (idx->d_hnsw_level_off) (void)hipFree(idx->d_hnsw_level_off);
+    for (uint32_t **a : {&idx->d_hnsw_l0, &idx->d_hnsw_slot, &idx->d_hnsw_adj}) vg::drop_device(a);
+    for (float **a : {&idx->d_hnsw_l0_dist, &idx->d_hnsw_l0_cdist, &idx->d_hnsw_adj_cdist}) vg::drop_device(a);
+    vg::drop_device(&idx->d_hnsw_tomb);
+    vg::drop_device(&idx->d_hnsw_level_off);
     if (idx->d_vamana) (void)hipFree(idx->d_vamana);
     if (idx->d_pq_rows) (void)hipFree(idx->d_pq_rows);
     if (idx->d_rq_rows) (void)hipFree(idx->d_rq_rows);

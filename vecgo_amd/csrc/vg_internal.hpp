@@ -3,6 +3,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
@@ -312,6 +313,36 @@ struct DevTmp {
     }
 };
 
+// A device array of the call's own (hipMalloc, at least one element): freed at return unless release() hands it on
+template <typename T>
+struct DevBuf {
+    T *p = nullptr;
+    ~DevBuf()
+    {
+        if (p) (void)hipFree(p);
+    }
+    int32_t alloc(size_t count)
+    {
+        VG_HIP(hipMalloc(reinterpret_cast<void **>(&p), std::max<size_t>(count, 1) * sizeof(T)));
+        return VG_OK;
+    }
+    T *release()
+    {
+        T *r = p;
+        p = nullptr;
+        return r;
+    }
+};
+
+// Frees the device array a slot holds, if any, and leaves the slot null.  Work that may still read the array is the
+// caller's to wait for.
+template <typename T>
+inline void drop_device(T **slot)
+{
+    if (*slot) (void)hipFree(*slot);
+    *slot = nullptr;
+}
+
 }  // namespace vg
 
 struct vg_pq {
@@ -434,3 +465,20 @@ struct vg_index {
     std::vector<uint32_t> h_part_off;  // the same on the host (launch bounds of the grouped GEMM, k_probe.hip)
     int32_t num_partitions = 0;
 };
+
+namespace vg {
+// What a segment's index holds besides fp32 rows and an HNSW graph, or null: rows appended or lists rewritten by a
+// memtable's entry point (vg_hnsw_insert, vg_hnsw_compact) would leave it behind
+inline const char *held_segment_state(const vg_index *idx)
+{
+    return (idx->d_pq_tiles || idx->d_pq_rows)   ? "PQ codes"
+           : idx->d_sq_tiles                     ? "SQ8 codes"
+           : idx->d_int4_rows                    ? "INT4 codes"
+           : (idx->d_rq_tiles || idx->d_rq_rows) ? "RaBitQ codes"
+           : idx->d_centroids                    ? "IVF partitions"
+           : idx->d_vamana                       ? "a Vamana graph"
+           : idx->sq_nom.rows                    ? "an SQ8 nomination image"
+           : idx->pq_nom.rows                    ? "a PQ nomination image"
+                                                 : nullptr;
+}
+}  // namespace vg
