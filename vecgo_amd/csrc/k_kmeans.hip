@@ -141,12 +141,17 @@ __global__ __launch_bounds__(256) void km_assign_regs_kernel(const float *__rest
 #pragma unroll
         for (int e = 0; e < NBLK; e++) rr[p][e] = r4[e * 16];
     }
+    // The walk from centroid 0 takes score 0 whatever it is (the reference stays on 0 for good when d[0] is NaN).  A later
+    // range must not do that with ITS first score: a NaN at c_lo would hide the whole range from the combine, where the
+    // reference skips that one centroid.  It starts from the worst value instead, which only a non-NaN score replaces; a
+    // range left at (worst, c_lo) — all NaN, or nothing better than +-Inf — loses every strict comparison of the combine,
+    // as each of its scores does in the reference's scan.
     float bd[kKmRows];
     int best[kKmRows];
 #pragma unroll
     for (int p = 0; p < kKmRows; p++) {
-        bd[p] = 0.0f;
-        best[p] = 0;
+        bd[p] = c_lo > 0 ? (DOT ? -INFINITY : INFINITY) : 0.0f;
+        best[p] = c_lo;
     }
     constexpr int tile4 = kKmTile * dim / 4;         // float4 per full tile
     constexpr int kStage = (tile4 + 255) / 256;      // ... and per thread
@@ -207,7 +212,7 @@ __global__ __launch_bounds__(256) void km_assign_regs_kernel(const float *__rest
                     b[t] = dpp_partner_add<kDppQuadXor1>(x2);
                 }
                 const float total = (b[0] + b[2]) + (b[1] + b[3]);
-                if (c == c_lo || (DOT ? (total > bd[p]) : (total < bd[p]))) {
+                if (c == 0 || (DOT ? (total > bd[p]) : (total < bd[p]))) {
                     bd[p] = total;
                     best[p] = c;
                 }
