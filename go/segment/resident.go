@@ -273,6 +273,72 @@ func (r *Resident) WriteFlat(segmentID uint64, ids []uint64, metadata, blockStat
 	return image[:int(written)], nil
 }
 
+// DiskANN quantization kinds of DiskANNBuild (quantization.Type, types.go:6-14, as the library's VG_QUANT_*).
+const (
+	DiskANNQuantNone, DiskANNQuantPQ, DiskANNQuantRaBitQ, DiskANNQuantInt4 = int(C.VG_QUANT_NONE), int(C.VG_QUANT_PQ), int(C.VG_QUANT_RABITQ), int(C.VG_QUANT_INT4)
+)
+
+// DiskANNBuild: diskann.Writer.Write up to Flush (diskann/writer.go:217-253) on the resident rows: the quantizer trained on and
+// applied to the rows in add order (pq: HIPProductQuantizer.Handle() created as (dim, pqM, 256); iq: HIPInt4Quantizer.Handle();
+// nil otherwise), buildGraph, reorderBFS (perm[new] = old; invPerm[old] = new, the writer's addOrderToFinalRow).  used is the
+// kind of the codes now on the segment: DiskANNQuantNone for PQ over fewer than 256 rows (trainPQ, :276-279).  The caller
+// permutes what the GPU never held (ids, metadata, payloads) with perm and rebuilds its inverted index (reorder.go:138-150).
+func (r *Resident) DiskANNBuild(R, L int, alpha float32, quant, pqM int, seed uint64, pq, iq unsafe.Pointer) (perm, invPerm []uint32, used int, err error) {
+	perm, invPerm = make([]uint32, r.rows), make([]uint32, r.rows)
+	var pp, pi *C.uint32_t
+	if r.rows > 0 {
+		pp, pi = up(perm), up(invPerm)
+	}
+	var u C.int32_t
+	if err := hipctx.Err(int32(C.vg_diskann_build(r.h, C.int32_t(R), C.int32_t(L), C.float(alpha), C.int32_t(quant), C.int32_t(pqM), 0,
+		C.uint64_t(seed), 8192, 32, (*C.vg_pq)(pq), (*C.vg_int4)(iq), pp, pi, &u, nil))); err != nil {
+		return nil, nil, 0, err
+	}
+	return perm, invPerm, int(u), nil
+}
+
+// WriteDiskANN: the file diskann.Writer.Flush writes (diskann/writer.go:645-856) for the resident segment, most of the body's
+// CRC-32C computed on the GPU.  searchListSize: the header's L (0 = 100); compressionType: Options.CompressionType, recorded
+// only (the sections are raw, as the reference's); ids in the segment's row order (nil = 0..rows-1); metadata / metadataIndex:
+// the sections as Flush serialises them (:797-833) from the documents permuted with DiskANNBuild's perm, nil = the bytes of
+// rows without documents.
+func (r *Resident) WriteDiskANN(segmentID uint64, searchListSize, compressionType int, ids []uint64, metadata, metadataIndex []byte) ([]byte, error) {
+	var mb, xb C.int64_t = -1, -1
+	var mp, xp unsafe.Pointer
+	none := []byte{0} // an empty section still travels as a non-nil pointer
+	section := func(b []byte) (unsafe.Pointer, C.int64_t) {
+		if len(b) == 0 {
+			return unsafe.Pointer(&none[0]), 0
+		}
+		return unsafe.Pointer(&b[0]), C.int64_t(len(b))
+	}
+	if metadata != nil {
+		mp, mb = section(metadata)
+	}
+	if metadataIndex != nil {
+		xp, xb = section(metadataIndex)
+	}
+	if len(ids) != 0 && len(ids) != r.rows {
+		return nil, fmt.Errorf("segment: WriteDiskANN: %d ids for %d rows", len(ids), r.rows)
+	}
+	var ip64 *C.uint64_t
+	if len(ids) != 0 {
+		ip64 = (*C.uint64_t)(unsafe.Pointer(&ids[0]))
+	}
+	size := int64(C.vg_segment_diskann_image_size(r.h, mb, xb))
+	if size < 0 { // the call names the refusal
+		return nil, hipctx.Err(int32(C.vg_segment_write_diskann(r.h, C.uint64_t(segmentID), C.int32_t(searchListSize), C.int32_t(compressionType),
+			ip64, mp, mb, xp, xb, unsafe.Pointer(&none[0]), 0, nil, nil)))
+	}
+	image := make([]byte, size)
+	var written C.int64_t
+	if err := hipctx.Err(int32(C.vg_segment_write_diskann(r.h, C.uint64_t(segmentID), C.int32_t(searchListSize), C.int32_t(compressionType),
+		ip64, mp, mb, xp, xb, unsafe.Pointer(&image[0]), C.int64_t(size), &written, nil))); err != nil {
+		return nil, err
+	}
+	return image[:int(written)], nil
+}
+
 // CRC32CDevice: hash.CRC32C (internal/hash/crc32c.go:15-17) of size bytes of device memory, computed on the GPU.
 func CRC32CDevice(devicePtr unsafe.Pointer, size int64) (uint32, error) {
 	p, err := hipctx.Ptr()

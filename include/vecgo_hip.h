@@ -64,7 +64,8 @@ extern "C" {
  *  them looks the symbol vg_search_vamana_threshold up (dlsym) instead of comparing the minor, and
  *  vg_vamana_reorder_bfs the same way; the next bump covers them.  Likewise the flat writer: vg_flat_build,
  *  vg_segment_flat_image_size, vg_segment_write_flat and vg_crc32c_device — bindings find them by symbol lookup.
- *  Likewise vg_hnsw_compact (with its caller-allocated vg_hnsw_compact_stats). */
+ *  Likewise vg_hnsw_compact (with its caller-allocated vg_hnsw_compact_stats).  Likewise the DiskANN writer:
+ *  vg_diskann_build, vg_segment_diskann_image_size and vg_segment_write_diskann, found by symbol lookup. */
 #define VG_ABI_MINOR 13
 #define VG_INVALID_ID 0xFFFFFFFFu
 #define VG_STREAM_LEGACY ((void *)1) /* == hipStreamLegacy */
@@ -778,6 +779,67 @@ int64_t vg_segment_flat_image_size(const vg_index *idx, int64_t metadata_bytes, 
 int32_t vg_segment_write_flat(vg_index *idx, uint64_t segment_id, const uint64_t *ids, const void *metadata_section,
                               int64_t metadata_bytes, const void *block_stats, int64_t block_stats_bytes, void *image,
                               int64_t image_size, int64_t *written, void *stream);
+
+/* diskann.Writer.Write up to Flush (diskann/writer.go:217-253) on the resident index, over its fp32 rows where they lie, in the
+ * writer's order.  (Present when the symbol is: see VG_ABI_MINOR.)
+ * 1. Quantize (:229-242, :274-360) the rows in add order: VG_QUANT_NONE; VG_QUANT_PQ with `pq` = vg_pq_create(dim, pq_m, 256):
+ *    trainPQ's rule first — fewer than 256 rows switch quantization off (:276-279: *quantization_used = VG_QUANT_NONE, `pq`
+ *    untouched, no codes; 256 rows train) — else vg_pq_train with pq_iters iterations (0 = 20) and `seed`, vg_pq_encode,
+ *    attached as vg_index_set_pq_codes does; VG_QUANT_RABITQ: vg_rabitq_encode, attached as vg_index_set_rabitq_codes does;
+ *    VG_QUANT_INT4 with `iq`: vg_int4_train + vg_int4_encode, attached as vg_index_set_int4_codes does.  The quantizers are the
+ *    caller's objects, trained by this call, and outlive it like any quantizer an index refers to.
+ * 2. buildGraph (:244-247) = vg_vamana_build(idx, r, l, alpha, NULL, seed, max_batch, growth_div): its defaults and limits.
+ * 2.5 reorderBFS (:249-253) = vg_vamana_reorder_bfs(idx, perm, inv_perm): either may be NULL, host or device; the codes of
+ *    step 1 move with the rows.  The caller permutes what the index never held: ids, metadata, payloads.
+ * The result is bit for bit what those calls give when made one after another.  *quantization_used (may be NULL) = the
+ *   VG_QUANT_* kind of the codes that ended up on the index.
+ * Refusals, in this order, with nothing changed and nothing written: NULL index VG_ERR_INVALID_ARG; rows without fp32 rows
+ *   VG_ERR_NOT_READY; rows == 0 VG_ERR_INVALID_ARG ("no vectors to write", :218-220); codes of any kind, IVF partitions, a
+ *   Vamana graph, a nomination image, an HNSW graph or its tombstones or edge distances VG_ERR_UNSUPPORTED; an unknown
+ *   quantization, VG_QUANT_SQ8 (the DiskANN format has none) or a kind without its quantizer VG_ERR_INVALID_ARG; VG_QUANT_PQ with
+ *   pq_m <= 0 VG_ERR_INVALID_ARG (a deviation: the reference then trains nothing, :230, and writes a header that claims PQ with
+ *   no codes behind it, :678-681); a vg_pq that is not (pq_m, 256) VG_ERR_INVALID_ARG; a quantizer of another dimension
+ *   VG_ERR_DIM_MISMATCH; then what vg_pq_train (when it will train), vg_index_set_rabitq_codes and vg_vamana_build refuse about
+ *   the shape, with their own status and message.
+ * A failure after these checks (out of memory, a HIP error) returns its status with *quantization_used, perm and inv_perm
+ *   unwritten, and leaves the index at the step it reached: a failure in step 1 leaves no codes attached (the quantizer may be
+ *   trained); in step 2 the codes of step 1 in add order and no graph; in step 2.5 codes and graph in add order when the
+ *   failure is an allocation (vg_vamana_reorder_bfs allocates before it moves anything), while after a HIP error in its
+ *   permutation the per-row arrays may disagree and the index is only good for vg_index_destroy. */
+int32_t vg_diskann_build(vg_index *idx, int32_t r, int32_t l, float alpha, int32_t quantization, int32_t pq_m, int32_t pq_iters,
+                         uint64_t seed, int32_t max_batch, int32_t growth_div, vg_pq *pq, vg_int4 *iq, uint32_t *perm,
+                         uint32_t *inv_perm, int32_t *quantization_used, void *stream);
+/* The file diskann.Writer.Flush writes (diskann/writer.go:645-856) for the resident index, into a host buffer: the 160-byte
+ * header (diskann/format.go:51-78), then with NO padding between them (bytesWritten is a running sum, :695-833) the fp32 rows,
+ * the graph (rows x MaxDegree little-endian uint32, VG_INVALID_ID = empty slot: the resident table verbatim), the codes
+ * row-major with their parameters behind them, the ids as little-endian uint64, the metadata section and the metadata
+ * inverted index.  Codes: PQ at PQCodesOffset, then at PQCodebookOffset m fp32 scales, m fp32 offsets and the int8 codebooks
+ * (no `m, K` in front, unlike the flat format, :742-763); INT4 at PQCodesOffset, then at PQCodebookOffset
+ * Int4Quantizer.MarshalBinary (quantization/int4.go:171-188: u32 dim, min[dim], diff[dim]), which ends where the ids start;
+ * RaBitQ at BQCodesOffset, no parameters.
+ *   Header: Magic 0x4449534B, Version 2, SegmentID, RowCount, Dim, Metric; MaxDegree = the graph's r; SearchListSize =
+ *     search_list_size (the index does not keep l; 0 = NewWriter's 100); Entrypoint = the index's; QuantizationType = the
+ *     VG_QUANT_* kind of the codes on the index; PQSubvectors / PQCentroids for PQ, else 0; CompressionType = compression_type
+ *     verbatim (0, 1 or 2: the reference records 1 = LZ4 by default, :92, and writes every section raw, :697-740, as this call
+ *     does); padding and reserved bytes 0.  Offsets of absent sections stay 0 (they are assigned inside their branches only,
+ *     :727-775) and BlockStatsOffset is 0, the writer never sets it.  Checksum = CRC-32C of everything behind the header: the
+ *     rows', graph's and codes' share computed on the device and chained on the host, which checksums the small sections.
+ *   ids: rows values in the index's (new) row order, NULL = 0 .. rows-1.
+ *   metadata_section: the host's serialisation (:797-823) of its documents permuted like the ids, copied verbatim; NULL = rows + 1
+ *     zero uint64 offsets and no blob.  metadata_index: WriteInvertedIndex's bytes (:825-833), verbatim; NULL = the one byte
+ *     0x00 of an empty index (internal/metadata/unified.go:1724-1733).  vg_segment_diskann_image_size takes the two sizes, a
+ *     negative one standing for that NULL form.  The payload side file stays the host's.
+ *   *written (may be NULL) = vg_segment_diskann_image_size = the bytes written.
+ * vg_segment_diskann_image_size touches no device and changes nothing; -1 where vg_segment_write_diskann would refuse the index.
+ * Refusals, in this order, with nothing written: a NULL index or image, a compression_type outside 0..2, a negative
+ *   search_list_size or a negative size of a given section VG_ERR_INVALID_ARG; rows == 0 VG_ERR_INVALID_ARG; no fp32 rows or no
+ *   Vamana graph VG_ERR_NOT_READY; an HNSW graph, IVF partitions, SQ8 codes or more than one kind of codes VG_ERR_UNSUPPORTED;
+ *   image_size below vg_segment_diskann_image_size VG_ERR_INVALID_ARG.  (See VG_ABI_MINOR.) */
+int64_t vg_segment_diskann_image_size(const vg_index *idx, int64_t metadata_bytes, int64_t metadata_index_bytes);
+int32_t vg_segment_write_diskann(vg_index *idx, uint64_t segment_id, int32_t search_list_size, int32_t compression_type,
+                                 const uint64_t *ids, const void *metadata_section, int64_t metadata_bytes,
+                                 const void *metadata_index, int64_t metadata_index_bytes, void *image, int64_t image_size,
+                                 int64_t *written, void *stream);
 
 /* per-query counters, the reference's FilterGateStats (searcher/searcher.go:114-137).  vg_search_vamana has
  * no short-circuit path; it reports in distance_short_circuits the candidates it could NOT push because the

@@ -705,6 +705,40 @@ public:
                                     blockStats ? static_cast<int64_t>(blockStats->size()) : 0, image.data(), size, &written, nullptr));
         return image;
     }
+    // diskann.Writer.Write up to Flush (diskann/writer.go:217-253) where the rows lie: the quantizer (VG_QUANT_NONE / _PQ with
+    // pq = ProductQuantizer(dim, pqM, 256) / _RABITQ / _INT4 with iq) trained on and applied to the rows in add order, then
+    // BuildVamana, then ReorderVamanaBFS (perm[new] = old, invPerm[old] = new; either may be null).  Returns the VG_QUANT_* kind
+    // of the codes now on the segment: VG_QUANT_NONE for PQ over fewer than 256 rows (trainPQ, :276-279)
+    int DiskANNBuild(int r, int l, float alpha, int quantization, std::shared_ptr<quantization::ProductQuantizer> pq,
+                     std::shared_ptr<quantization::Int4Quantizer> iq, uint32_t *perm, uint32_t *invPerm, uint64_t seed = 0,
+                     int pqM = 0, int pqIters = 0, int maxBatch = 8192, int growthDiv = 32)
+    {
+        int32_t used = VG_QUANT_NONE;
+        check(vg_diskann_build(h_, r, l, alpha, quantization, pqM, pqIters, seed, maxBatch, growthDiv, pq ? pq->handle() : nullptr,
+                               iq ? iq->handle() : nullptr, perm, invPerm, &used, nullptr));
+        if (used == VG_QUANT_PQ) pq_ = std::move(pq);
+        if (used == VG_QUANT_INT4) iq_ = std::move(iq);
+        return used;
+    }
+    // the file Writer.Flush writes (diskann/writer.go:645-856) for this segment; searchListSize: the header's L (0 = 100);
+    // compressionType: recorded, the sections are raw; ids in the segment's row order (null: 0 .. rows-1); metadata /
+    // metadataIndex: the host's serialised sections (null: the writer's bytes for rows without documents)
+    std::vector<uint8_t> WriteDiskANN(uint64_t segmentID, int searchListSize = 0, int compressionType = 1, const uint64_t *ids = nullptr,
+                                      const std::vector<uint8_t> *metadata = nullptr, const std::vector<uint8_t> *metadataIndex = nullptr)
+    {
+        const int64_t size = vg_segment_diskann_image_size(h_, metadata ? static_cast<int64_t>(metadata->size()) : -1,
+                                                           metadataIndex ? static_cast<int64_t>(metadataIndex->size()) : -1);
+        std::vector<uint8_t> image(static_cast<size_t>(size < 0 ? 1 : size));  // (size < 0: the call below names the refusal)
+        static const uint8_t none = 0;  // (an empty section still travels as a non-null pointer)
+        int64_t written = 0;
+        check(vg_segment_write_diskann(h_, segmentID, searchListSize, compressionType, ids,
+                                       metadata ? (metadata->empty() ? &none : metadata->data()) : nullptr,
+                                       metadata ? static_cast<int64_t>(metadata->size()) : 0,
+                                       metadataIndex ? (metadataIndex->empty() ? &none : metadataIndex->data()) : nullptr,
+                                       metadataIndex ? static_cast<int64_t>(metadataIndex->size()) : 0, image.data(), size < 0 ? 0 : size,
+                                       &written, nullptr));
+        return image;
+    }
     // the Vamana graph (n * r ids, VG_INVALID_ID = empty slot) and its entry point
     std::vector<uint32_t> VamanaGraph(int *r, uint32_t *entry) const
     {
@@ -752,6 +786,7 @@ private:
     std::shared_ptr<Context> ctx_;
     std::shared_ptr<quantization::ProductQuantizer> pq_;
     std::shared_ptr<quantization::ScalarQuantizer> sq_;
+    std::shared_ptr<quantization::Int4Quantizer> iq_;
     vg_index *h_ = nullptr;
     int64_t n_;
     int dim_;

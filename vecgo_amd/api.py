@@ -1148,6 +1148,57 @@ class Index:
                                               C.c_int64(size), C.byref(written), _stream_ptr(stream)))
         return image[:written.value].tobytes()
 
+    QUANT_RABITQ, QUANT_INT4 = 5, 6   # VG_QUANT_*
+
+    def diskann_build(self, r=64, l=100, alpha=1.2, quantizer=None, seed=0, pq_iters=0, max_batch=8192, growth_div=32, stream=None):
+        """diskann.Writer.Write up to Flush on the GPU (diskann/writer.go:217-253; the rules are vg_diskann_build's in the
+        header): `quantizer` — None, a ProductQuantizer(dim, m, 256), a RaBitQuantizer or an Int4Quantizer — trained on and
+        applied to the rows in add order and attached, then build_vamana(r, l, alpha, seed=seed, ...), then
+        reorder_vamana_bfs.  Returns (perm, inv_perm, quantization_used): np.uint32 of length n, perm[new] = old,
+        inv_perm[old] = new, and the VG_QUANT_* kind of the codes now on the index (QUANT_NONE for a ProductQuantizer over
+        fewer than 256 rows: trainPQ's rule)."""
+        kind, pq, iq, m = self.QUANT_NONE, None, None, 0
+        if isinstance(quantizer, ProductQuantizer):
+            kind, pq, m = self.QUANT_PQ, quantizer._h, quantizer.num_subvectors
+        elif isinstance(quantizer, RaBitQuantizer):
+            kind = self.QUANT_RABITQ
+        elif isinstance(quantizer, Int4Quantizer):
+            kind, iq = self.QUANT_INT4, quantizer._h
+        elif quantizer is not None:
+            raise TypeError("quantizer must be None, a ProductQuantizer, a RaBitQuantizer or an Int4Quantizer")
+        perm = np.empty(self.n, np.uint32)
+        inv = np.empty(self.n, np.uint32)
+        used = C.c_int32(0)
+        check(self._lib.vg_diskann_build(self._h, C.c_int32(r), C.c_int32(l), C.c_float(alpha), C.c_int32(kind), C.c_int32(m),
+                                         C.c_int32(pq_iters), C.c_uint64(seed), C.c_int32(max_batch), C.c_int32(growth_div), pq, iq,
+                                         C.c_void_p(perm.ctypes.data), C.c_void_p(inv.ctypes.data), C.byref(used), _stream_ptr(stream)))
+        if used.value in (self.QUANT_PQ, self.QUANT_INT4):
+            self._keep.append(quantizer)
+        return perm, inv, int(used.value)
+
+    def write_diskann_segment(self, segment_id=0, search_list_size=0, compression_type=1, ids=None, metadata=None,
+                              metadata_index=None, stream=None) -> bytes:
+        """The file diskann.Writer.Flush writes for this index (diskann/writer.go:645-856; vg_segment_write_diskann), most of
+        the body's CRC-32C computed on the GPU.  search_list_size: the header's L (0 = 100); compression_type: recorded, the
+        sections are raw; ids: uint64 per row in the index's order (None: 0 .. n-1); metadata / metadata_index: the sections as
+        the host serialised them (None: the writer's bytes for rows without documents)."""
+        def section(b):
+            if b is None:
+                return None, None, C.c_int64(-1)
+            a = np.frombuffer(bytes(b) or b"\0", np.uint8)
+            return a, C.c_void_p(a.ctypes.data), C.c_int64(len(b))
+        md, pmd, nmd = section(metadata)
+        mi, pmi, nmi = section(metadata_index)
+        self._lib.vg_segment_diskann_image_size.restype = C.c_int64
+        size = self._lib.vg_segment_diskann_image_size(self._h, nmd, nmi)
+        i, pi = (None, None) if ids is None else _ptr(np.ascontiguousarray(ids, np.uint64), np.uint64, self.n)
+        image = np.empty(max(size, 1), np.uint8)   # (size < 0: the call below names the refusal)
+        written = C.c_int64(0)
+        check(self._lib.vg_segment_write_diskann(self._h, C.c_uint64(segment_id), C.c_int32(search_list_size), C.c_int32(compression_type),
+                                                 pi, pmd, nmd, pmi, nmi, C.c_void_p(image.ctypes.data), C.c_int64(max(size, 0)),
+                                                 C.byref(written), _stream_ptr(stream)))
+        return image[:written.value].tobytes()
+
     def _graph_search(self, fn, queries, k, mid_arg, want_stats, stream):
         nq = _rows(queries, self.dim)
         q, pq_ = _ptr(queries, np.float32)

@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "vg_crc32c.hpp"
+#include "vg_crc_device.hpp"
 #include "vg_internal.hpp"
 #include "vg_permute.hpp"
 #include "vg_segment_layout.hpp"
@@ -275,7 +276,7 @@ __global__ __launch_bounds__(64) void crc_edges_kernel(const uint8_t *__restrict
     out[threadIdx.x] = c;
 }
 
-static int32_t crc_tables(int device, const CrcTables **out)
+int32_t crc_tables(int device, const CrcTables **out)
 {
     static std::mutex mu;
     static const CrcTables *per_device[64] = {nullptr};
@@ -298,41 +299,37 @@ static int32_t crc_tables(int device, const CrcTables **out)
     return VG_OK;
 }
 
-// One byte range's CRC in two steps: launch() enqueues the kernels, which leave head, tail and the blocks' registers in
-// d_out[0 .. words()); finish() chains a host copy of them.
-struct CrcJob {
-    int64_t size = 0, head = 0, pieces = 0, tail = 0, blocks = 0;
-    void plan(const void *ptr, int64_t bytes)
-    {
-        size = bytes;
-        head = std::min<int64_t>(bytes, static_cast<int64_t>((16 - (reinterpret_cast<uintptr_t>(ptr) & 15)) & 15));
-        pieces = (bytes - head) / 16;
-        tail = bytes - head - pieces * 16;
-        blocks = (pieces + kCrcBlockPieces - 1) / kCrcBlockPieces;
+// CrcJob (vg_crc_device.hpp): one byte range's CRC in two steps
+void CrcJob::plan(const void *ptr, int64_t bytes)
+{
+    size = bytes;
+    head = std::min<int64_t>(bytes, static_cast<int64_t>((16 - (reinterpret_cast<uintptr_t>(ptr) & 15)) & 15));
+    pieces = (bytes - head) / 16;
+    tail = bytes - head - pieces * 16;
+    blocks = (pieces + kCrcBlockPieces - 1) / kCrcBlockPieces;
+}
+
+int32_t CrcJob::launch(const void *ptr, const CrcTables *tables, uint32_t *d_out, hipStream_t st) const
+{
+    const uint8_t *p = static_cast<const uint8_t *>(ptr);
+    VG_LAUNCH(crc_edges_kernel, dim3(1), dim3(64), 0, st, p, static_cast<int>(head), p + head + pieces * 16, static_cast<int>(tail), tables,
+              d_out);
+    if (blocks)
+        VG_LAUNCH(crc_blocks_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kCrcThreads), 0, st, reinterpret_cast<const uint4 *>(p + head),
+                  pieces, tables, d_out + 2);
+    return VG_OK;
+}
+
+uint32_t CrcJob::finish(const uint32_t *h_out) const
+{
+    const uint32_t full = crc::xpow8(static_cast<uint64_t>(kCrcBlockBytes));
+    uint32_t acc = h_out[0];
+    for (int64_t b = 0; b < blocks; b++) {
+        const int64_t bytes = std::min(kCrcBlockPieces, pieces - b * kCrcBlockPieces) * 16;
+        acc = crc::mulmod(bytes == kCrcBlockBytes ? full : crc::xpow8(static_cast<uint64_t>(bytes)), acc) ^ h_out[2 + b];
     }
-    size_t words() const { return static_cast<size_t>(blocks) + 2; }
-    int32_t launch(const void *ptr, const CrcTables *tables, uint32_t *d_out, hipStream_t st) const
-    {
-        const uint8_t *p = static_cast<const uint8_t *>(ptr);
-        VG_LAUNCH(crc_edges_kernel, dim3(1), dim3(64), 0, st, p, static_cast<int>(head), p + head + pieces * 16, static_cast<int>(tail), tables,
-                  d_out);
-        if (blocks)
-            VG_LAUNCH(crc_blocks_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kCrcThreads), 0, st, reinterpret_cast<const uint4 *>(p + head),
-                      pieces, tables, d_out + 2);
-        return VG_OK;
-    }
-    // the raw register of the whole range
-    uint32_t finish(const uint32_t *h_out) const
-    {
-        const uint32_t full = crc::xpow8(static_cast<uint64_t>(kCrcBlockBytes));
-        uint32_t acc = h_out[0];
-        for (int64_t b = 0; b < blocks; b++) {
-            const int64_t bytes = std::min(kCrcBlockPieces, pieces - b * kCrcBlockPieces) * 16;
-            acc = crc::mulmod(bytes == kCrcBlockBytes ? full : crc::xpow8(static_cast<uint64_t>(bytes)), acc) ^ h_out[2 + b];
-        }
-        return crc::combine(acc, h_out[1], static_cast<uint64_t>(tail));
-    }
-};
+    return crc::combine(acc, h_out[1], static_cast<uint64_t>(tail));
+}
 
 // ---- the image's layout (writer.go:312-345) -----------------------------------------------------------------------------
 struct FlatImage {
@@ -374,9 +371,6 @@ static int32_t flat_image_plan(const vg_index *idx, int64_t metadata_bytes, int6
     L.stats = stats_bytes >= 0 ? static_cast<uint64_t>(stats_bytes) : uvarint_len(stat_blocks) + 2 * stat_blocks;
     return VG_OK;
 }
-
-static void wr32(uint8_t *p, uint32_t v) { memcpy(p, &v, 4); }  // (little-endian host, as the rest of the library assumes)
-static void wr64(uint8_t *p, uint64_t v) { memcpy(p, &v, 8); }
 
 }  // namespace vg
 
@@ -430,11 +424,7 @@ VG_API int32_t vg_flat_build(vg_index *idx, int32_t num_partitions, int32_t quan
         VG_CHECK(pq->m == want_m && pq->k == 256, VG_ERR_INVALID_ARG,
                  "vg_flat_build: the vg_pq has m = %d, k = %d; the writer's is NewProductQuantizer(dim, %d, 256) (writer.go:204)", pq->m, pq->k,
                  want_m);
-        // what vg_pq_train would refuse, before anything moves
-        VG_CHECK(idx->n <= INT32_MAX, VG_ERR_UNSUPPORTED, "vg_pq_train: more than 2^31-1 training vectors");
-        VG_CHECK(pq->subdim <= 256, VG_ERR_UNSUPPORTED, "vg_pq_train: sub-vector dim %d > 256", pq->subdim);
-        VG_CHECK(static_cast<size_t>(pq->k) * pq->subdim * sizeof(float) <= 152 * 1024, VG_ERR_UNSUPPORTED,
-                 "vg_pq_train: codebook of one sub-quantizer exceeds 152 KiB");
+        VG_TRY(vg::pq_train_refusal(pq, idx->n));  // before anything moves
     }
     const int64_t n = idx->n;
     if (n == 0) return VG_OK;
@@ -517,8 +507,6 @@ VG_API int32_t vg_segment_write_flat(vg_index *idx, uint64_t segment_id, const u
                                      int64_t image_size, int64_t *written, void *stream)
 {
     using namespace vg::seglayout;
-    using vg::wr32;
-    using vg::wr64;
     if (written) *written = 0;
     vg::FlatImage L;
     VG_TRY(vg::flat_image_plan(idx, metadata_section ? metadata_bytes : -1, block_stats ? block_stats_bytes : -1, L, "vg_segment_write_flat"));

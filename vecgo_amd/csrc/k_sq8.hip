@@ -19,14 +19,6 @@
 #include "vg_nominate.hpp"
 #include "vg_search.hpp"
 
-struct vg_int4 {
-    vg_ctx *ctx = nullptr;
-    int32_t dim = 0;
-    bool trained = false;
-    float *d_min = nullptr, *d_diff = nullptr;  // [dim] each
-    float *d_table = nullptr;                   // [dim * 16] BuildInt4LookupTable
-};
-
 namespace vg {
 
 constexpr float kF32Max = 3.40282346638528859811704183484516925440e+38f;

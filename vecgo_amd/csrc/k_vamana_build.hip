@@ -383,25 +383,32 @@ static int next_pow2(int x)
     return p;
 }
 
+// r, l, alpha of 0 become NewWriter's defaults (writer.go:84-95); then every refusal vg_vamana_build makes before it allocates
+// (vg_search.hpp: vg_diskann_build makes them before it quantizes)
+int32_t vamana_build_check(const vg_index *idx, int32_t &r, int32_t &l, float &alpha, int32_t max_batch, int32_t growth_div)
+{
+    if (r == 0) r = 64;
+    if (l == 0) l = 100;
+    if (alpha == 0.0f) alpha = 1.2f;
+    VG_CHECK(r >= 1 && r <= kVbMaxR, VG_ERR_UNSUPPORTED, "vg_vamana_build: r=%d must be in 1..%d", r, kVbMaxR);
+    VG_CHECK(l >= 1 && l <= kVbMaxL, VG_ERR_UNSUPPORTED, "vg_vamana_build: l=%d must be in 1..%d", l, kVbMaxL);
+    VG_CHECK(max_batch >= 1 && growth_div >= 1, VG_ERR_INVALID_ARG, "vg_vamana_build: max_batch and growth_div must be >= 1");
+    VG_CHECK(max_batch <= kVbMaxBatch, VG_ERR_UNSUPPORTED, "vg_vamana_build: max_batch=%d must be <= %d", max_batch, kVbMaxBatch);
+    VG_CHECK(idx->n > 0, VG_ERR_INVALID_ARG, "vg_vamana_build: no vectors to write (n = 0)");
+    VG_CHECK(idx->n < (int64_t(1) << 31), VG_ERR_UNSUPPORTED, "vg_vamana_build: n=%lld must be below 2^31",
+             static_cast<long long>(idx->n));
+    VG_CHECK(idx->d_vectors, VG_ERR_NOT_READY, "vg_vamana_build: index has no fp32 vectors");
+    VG_CHECK(idx->metric != VG_METRIC_HAMMING, VG_ERR_UNSUPPORTED, "unsupported metric for float32: Hamming");
+    return VG_OK;
+}
+
 }  // namespace vg
 
 VG_API int32_t vg_vamana_build(vg_index *idx, int32_t r, int32_t l, float alpha, const uint32_t *init_graph,
                                uint64_t seed, int32_t max_batch, int32_t growth_div, void *stream)
 {
     VG_CHECK(idx, VG_ERR_INVALID_ARG, "vg_vamana_build: NULL index");
-    if (r == 0) r = 64;  // NewWriter's defaults (writer.go:84-95)
-    if (l == 0) l = 100;
-    if (alpha == 0.0f) alpha = 1.2f;
-    VG_CHECK(r >= 1 && r <= vg::kVbMaxR, VG_ERR_UNSUPPORTED, "vg_vamana_build: r=%d must be in 1..%d", r, vg::kVbMaxR);
-    VG_CHECK(l >= 1 && l <= vg::kVbMaxL, VG_ERR_UNSUPPORTED, "vg_vamana_build: l=%d must be in 1..%d", l, vg::kVbMaxL);
-    VG_CHECK(max_batch >= 1 && growth_div >= 1, VG_ERR_INVALID_ARG, "vg_vamana_build: max_batch and growth_div must be >= 1");
-    VG_CHECK(max_batch <= vg::kVbMaxBatch, VG_ERR_UNSUPPORTED, "vg_vamana_build: max_batch=%d must be <= %d", max_batch,
-             vg::kVbMaxBatch);
-    VG_CHECK(idx->n > 0, VG_ERR_INVALID_ARG, "vg_vamana_build: no vectors to write (n = 0)");
-    VG_CHECK(idx->n < (int64_t(1) << 31), VG_ERR_UNSUPPORTED, "vg_vamana_build: n=%lld must be below 2^31",
-             static_cast<long long>(idx->n));
-    VG_CHECK(idx->d_vectors, VG_ERR_NOT_READY, "vg_vamana_build: index has no fp32 vectors");
-    VG_CHECK(idx->metric != VG_METRIC_HAMMING, VG_ERR_UNSUPPORTED, "unsupported metric for float32: Hamming");
+    VG_TRY(vg::vamana_build_check(idx, r, l, alpha, max_batch, growth_div));
     VG_HIP(hipSetDevice(idx->ctx->device));
     hipStream_t st = vg::pick_stream(idx->ctx, stream);
     const int64_t n = idx->n;

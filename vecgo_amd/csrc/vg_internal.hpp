@@ -354,6 +354,19 @@ struct vg_pq {
     float *d_offsets = nullptr;     // m
 };
 
+namespace vg {
+// What vg_pq_train refuses about a quantizer's shape and n training rows, with its status and message: for the builders
+// (vg_flat_build, vg_diskann_build), which refuse before they change anything.
+inline int32_t pq_train_refusal(const vg_pq *pq, int64_t n)
+{
+    VG_CHECK(n <= INT32_MAX, VG_ERR_UNSUPPORTED, "vg_pq_train: more than 2^31-1 training vectors");
+    VG_CHECK(pq->subdim <= 256, VG_ERR_UNSUPPORTED, "vg_pq_train: sub-vector dim %d > 256", pq->subdim);
+    VG_CHECK(static_cast<size_t>(pq->k) * pq->subdim * sizeof(float) <= 152 * 1024, VG_ERR_UNSUPPORTED,
+             "vg_pq_train: codebook of one sub-quantizer exceeds 152 KiB");
+    return VG_OK;
+}
+}  // namespace vg
+
 struct vg_sq8 {
     vg_ctx *ctx = nullptr;
     int32_t dim = 0;
@@ -361,7 +374,13 @@ struct vg_sq8 {
     float *d_mins = nullptr, *d_maxs = nullptr, *d_scales = nullptr, *d_inv = nullptr;  // [dim] each, one block: mins, maxs, scales, inverse scales
 };
 
-struct vg_int4;
+struct vg_int4 {
+    vg_ctx *ctx = nullptr;
+    int32_t dim = 0;
+    bool trained = false;
+    float *d_min = nullptr, *d_diff = nullptr;  // [dim] each
+    float *d_table = nullptr;                   // [dim * 16] BuildInt4LookupTable
+};
 
 namespace vg {
 // Partition-probed scans (k_probe.hip): (query, probe) pairs bucketed by partition and cut into groups

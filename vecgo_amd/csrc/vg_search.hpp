@@ -79,6 +79,10 @@ int32_t launch_probe_scan_sq8_grouped(const vg_index *idx, const float *queries,
 int32_t sq8_nan_replay(vg_index *idx, const float *d_queries, int64_t nq, int k, const uint8_t *d_mask, int64_t mask_stride,
                        const uint32_t *d_probes, int np, const uint32_t *d_part_off, uint32_t *d_ids, float *d_scores, hipStream_t st);
 
+// ---- k_vamana_build.hip ---------------------------------------------------------------------------
+// vg_vamana_build's defaults (r, l, alpha of 0) and every refusal it makes before it allocates, with its status and message
+int32_t vamana_build_check(const vg_index *idx, int32_t &r, int32_t &l, float &alpha, int32_t max_batch, int32_t growth_div);
+
 // ---- k_rabitq.hip ---------------------------------------------------------------------------------
 // sign bits + norm of each vector (RaBitQ Encode)
 int32_t launch_rabitq_encode(const float *d_vectors, int64_t n, int dim, uint8_t *d_codes, hipStream_t st);

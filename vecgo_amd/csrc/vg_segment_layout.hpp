@@ -24,6 +24,13 @@ inline uint32_t rd32(const uint8_t *p)
 }
 inline uint16_t rd16(const uint8_t *p) { return static_cast<uint16_t>(p[0] | (p[1] << 8)); }
 inline uint64_t rd64(const uint8_t *p) { return static_cast<uint64_t>(rd32(p)) | (static_cast<uint64_t>(rd32(p + 4)) << 32); }
+// (the writers' twins)
+inline void wr32(uint8_t *p, uint32_t v)
+{
+    for (int i = 0; i < 4; i++) p[i] = static_cast<uint8_t>(v >> (8 * i));
+}
+inline void wr16(uint8_t *p, uint16_t v) { p[0] = static_cast<uint8_t>(v), p[1] = static_cast<uint8_t>(v >> 8); }
+inline void wr64(uint8_t *p, uint64_t v) { wr32(p, static_cast<uint32_t>(v)), wr32(p + 4, static_cast<uint32_t>(v >> 32)); }
 
 // CRC-32C (Castagnoli, reflected polynomial 0x82F63B78) — internal/hash/crc32c.go:15-17
 struct Crc32cTables {
