@@ -224,7 +224,8 @@ int32_t vg_hamming_batch(vg_ctx *ctx, const uint8_t *a, const uint8_t *codes, in
 
 /* Test hooks (process-wide): force an alternative path so that tests can compare the paths bit for bit.
  * Names: VG_FLAT_NO_SMALL_TILE, VG_FLAT_UNFUSED, VG_FLAT_NO_SCAN, VG_FLAT_FORCE_EXACT, VG_FLAT_NO_DMA,
- * VG_FLAT_DEBUG, VG_PROBE_NO_GROUP, VG_ADC_BIGK_EXHAUSTIVE, VG_BUILD_DEBUG.  The environment variable of the same
+ * VG_FLAT_DEBUG, VG_PROBE_NO_GROUP, VG_ADC_BIGK_EXHAUSTIVE, VG_BUILD_DEBUG, VG_FLAT_RESCORE_SAMPLE (the full list: Hook in
+ * csrc/vg_internal.hpp).  The environment variable of the same
  * name ("1") gives the initial value, read once; the search entry points never call getenv. */
 int32_t vg_debug_set_hook(const char *name, int32_t on);
 /* Test entry point: a script of searcher.PriorityQueue operations (queue.go) replayed by ONE wave on the device

@@ -97,7 +97,7 @@ static void run_old(const char *name, const Bufs &b)
     const float ms = time_ms(b, [&] {
         hipLaunchKernelGGL(kern, dim3(unsigned(mt * ((nt + 7) / 8) * 8)), dim3(vg::kGemmThreads), vg::kDmaLdsBytes, 0, b.q, b.nq, b.base, b.n,
                            b.dw, b.norms, (float *)nullptr, 1, int64_t(0), b.thr, 1, 0, b.counts, b.cand, b.cap, (const uint8_t *)nullptr,
-                           int64_t(0));
+                           int64_t(0), 0);
     });
     report(name, b, ms);
 }

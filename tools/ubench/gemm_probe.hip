@@ -1,7 +1,10 @@
 // Prices the stages of flat_gemm_kernel (vecgo_amd/csrc/vg_flat_gemm.hpp) by timing PROBE variants
 // of the same code on 1024 queries x N rows x 768 dims.
 //   hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -std=c++17 -I../../vecgo_amd/csrc \
-//         gemm_probe.hip -o gemm_probe && ./gemm_probe [N]
+//         gemm_probe.hip -o gemm_probe && ./gemm_probe [N [THRESHOLD]]
+// THRESHOLD (default -1e30: nothing passes, the epilogue only compares): every query's threshold.  The scores here are about
+// normal with sigma 18.5 (uniform(-1, 1) operands of 768 dims), so -60.6 lets ~520 of 1M rows pass per query, as many as the
+// flat search's sampled threshold does: "full kernel" minus "- epilogue" is then the price of the compare AND of the appends.
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -46,7 +49,7 @@ static void run(const char *name, const float *q, int64_t nq, const float *base,
         CK(hipMemset(counts, 0, sizeof(int) * nq));
         CK(hipEventRecord(e0));
         hipLaunchKernelGGL(kern, grid, dim3(vg::kGemmThreads), lds, 0, q, nq, base, n, dim, norms,
-                           scores, 1, n, thr, 1, 0, counts, cand, cap);
+                           scores, 1, n, thr, 1, 0, counts, cand, cap, (const uint8_t *)nullptr, int64_t(0), 0);
         CK(hipEventRecord(e1));
         CK(hipEventSynchronize(e1));
         float ms;
@@ -74,7 +77,7 @@ int main(int argc, char **argv)
     fill<<<unsigned((nq * dim + 255) / 256), 256>>>(q, nq * dim, 1);
     fill<<<unsigned((n * dim + 255) / 256), 256>>>(base, n * dim, 2);
     fill<<<unsigned((n + 255) / 256), 256>>>(norms, n, 3);
-    std::vector<float> h(nq, -1e30f);  // nothing passes the threshold
+    std::vector<float> h(nq, argc > 2 ? float(atof(argv[2])) : -1e30f);  // default: nothing passes the threshold
     CK(hipMemcpy(thr, h.data(), nq * 4, hipMemcpyHostToDevice));
     CK(hipDeviceSynchronize());
     run<2, 0>("full kernel (MODE 2)", q, nq, base, n, dim, norms, scores, thr, counts, cand, cap);

@@ -43,8 +43,20 @@ struct GemmArgs {
     // after the other (1024 queries x 1M x 768: 0.16 of the kernel's 1.35 ms went there — "keys stored without atomics" in
     // profiles/r06_gemm_bf16_probe.txt).  Null: the tile counts in `counts` itself.
     int *counts_wide = nullptr;
+    // MODE 2, > 1: every skip_stride-th row tile is left out — the tiles MODE 1 sampled, whose passing rows the caller appends from
+    // the sample itself (flat_sample_append_kernel).  Only where gemm_skips_sample() says so; 0: every tile.
+    int skip_stride = 0;
 };
 constexpr int kCountLine = 32;
+// Whether launch_gemm_t runs a kernel that honours GemmArgs::skip_stride for these arguments: the fp32 128 x 128 tiles (LDS-DMA and
+// register-staged), whose MODE 1 and MODE 2 are one body with one accumulation order.  Not the 32-row tiles (up to 96 queries), not
+// a bf16 kernel.  The ONE place that decides: the caller appends the sampled rows itself exactly where this is true (a row
+// appended by both, or by neither, is a wrong answer).
+static bool gemm_skips_sample(bool dma, int64_t nq, bool bf16)
+{
+    if (bf16 || hook(kHookFlatRescoreSample)) return false;
+    return !(dma && nq <= 3 * kG32BM && !hook(kHookFlatNoSmallTile));
+}
 __global__ void counts_narrow_kernel(const int *__restrict__ wide, int64_t nq, int *__restrict__ counts)
 {
     const int64_t q = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
@@ -54,6 +66,14 @@ __global__ void counts_narrow_kernel(const int *__restrict__ wide, int64_t nq, i
 template <bool DOT, int MODE>
 static int32_t launch_gemm_t(bool dma, unsigned blocks, hipStream_t st, const GemmArgs &a, bool bf16)
 {
+    const int skip = MODE == 2 ? a.skip_stride : 0;
+    VG_CHECK(skip == 0 || (skip > 1 && gemm_skips_sample(dma, a.nq, bf16)), VG_ERR_INVALID_ARG, "launch_gemm: skip_stride on a kernel without it");
+    if (skip) {  // the grid of the tiles that are left, in the same XCD-aware order
+        const int64_t mt = (a.nq + kGemmBM - 1) / kGemmBM, nt = (a.n + kGemmBN - 1) / kGemmBN;
+        const int64_t left = nt - gemm_skip_sampled_tiles(nt, skip);
+        if (left == 0) return VG_OK;
+        blocks = static_cast<unsigned>(mt * ((left + 7) / 8) * 8);
+    }
     if (bf16) {  // rows of bfloat16 (a.dim = 4-byte words per row): the LDS-DMA tiles only
         constexpr int M = MODE == 0 ? 1 : MODE;
         // up to 128 queries: the tile of 1 .. 4 blocks of 32 query rows (HBM-bound at the bf16 rate: 65 .. 128 queries 0.44 .. 0.49 ms on
@@ -95,7 +115,7 @@ static int32_t launch_gemm_t(bool dma, unsigned blocks, hipStream_t st, const Ge
                                    static_cast<int>(kDmaLdsBytes)));
         VG_LAUNCH(kern, dim3(blocks), dim3(kGemmThreads), kDmaLdsBytes, st, a.queries, a.nq, a.base, a.n, a.dim,
                   a.norms, a.scores, a.tile_stride, a.out_cols, a.thr, a.thr_stride, a.thr_off, a.counts, a.cand,
-                  a.cap, a.mask, a.mask_stride);
+                  a.cap, a.mask, a.mask_stride, 0);
         return VG_OK;
     }
     // (test hook kHookFlatNoSmallTile: always the 128-query tile)
@@ -120,14 +140,14 @@ static int32_t launch_gemm_t(bool dma, unsigned blocks, hipStream_t st, const Ge
                                    static_cast<int>(kDmaLdsBytes)));
         VG_LAUNCH(kern, dim3(blocks), dim3(kGemmThreads), kDmaLdsBytes, st, a.queries, a.nq, a.base, a.n, a.dim,
                   a.norms, a.scores, a.tile_stride, a.out_cols, a.thr, a.thr_stride, a.thr_off, a.counts, a.cand,
-                  a.cap, a.mask, a.mask_stride);
+                  a.cap, a.mask, a.mask_stride, skip);
     } else {
         auto kern = flat_gemm_kernel<DOT, MODE>;
         VG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
                                    static_cast<int>(kGemmLdsBytes)));
         VG_LAUNCH(kern, dim3(blocks), dim3(kGemmThreads), kGemmLdsBytes, st, a.queries, a.nq, a.base, a.n, a.dim,
                   a.norms, a.scores, a.tile_stride, a.out_cols, a.thr, a.thr_stride, a.thr_off, a.counts, a.cand,
-                  a.cap, a.mask, a.mask_stride);
+                  a.cap, a.mask, a.mask_stride, skip);
     }
     return VG_OK;
 }
@@ -190,6 +210,70 @@ __global__ __launch_bounds__(256) void flat_todo_kernel(const int *__restrict__ 
     int at = part[tid];
     for (int i = lo; i < hi; i++)
         if (all || flags[i] != 0) todo[1 + at++] = i;
+}
+
+// The sampled row tiles are scored once.  MODE 1 has left their scores in sc[q][ns] (+Inf for a column past n and for a row the
+// query's filter rejects); MODE 2 of the same 128 x 128 tile would compute the same bits again and compare them with the query's
+// threshold.  So, once the thresholds exist: one workgroup per query walks its sample, appends key(sc, row) for every column with
+// sc < threshold — column c = row (c / 128) * sample_stride * 128 + c % 128 — and SETS counts[q] to how many passed (those past
+// `cap` too: the overflow test wants the full count), which also stands in for the memset in front of the main GEMM; that GEMM
+// then leaves the sampled tiles out (GemmArgs::skip_stride).  Slots: a ballot prefix per wave, the waves' totals through LDS (no
+// atomics; the order of a list's keys means nothing).  A round is 4096 columns — four 16-byte loads per thread, all issued before
+// the first compare (one load per thread and round: 62 rounds of a load's latency and a barrier at 1M rows).
+constexpr int kSampleAppendThreads = 256, kSampleAppendVec = 4;
+__global__ __launch_bounds__(kSampleAppendThreads) void flat_sample_append_kernel(
+    const float *__restrict__ sc /* 16-byte aligned, ns % 4 == 0 */, int64_t ns, int sample_stride, const float *__restrict__ thr,
+    int thr_stride, int thr_off, int *__restrict__ counts, uint64_t *__restrict__ cand, int cap)
+{
+    constexpr int kWaves = kSampleAppendThreads / 64, kPiece = kSampleAppendThreads * 4, kRound = kPiece * kSampleAppendVec;
+    __shared__ int wave_n[2][kWaves];
+    const int64_t q = blockIdx.x;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const float t = thr[q * thr_stride + thr_off];
+    const float *row = sc + q * ns;
+    uint64_t *dst = cand + q * cap;
+    const uint64_t below = (uint64_t(1) << lane) - 1;
+    int run = 0;  // passed so far (uniform over the workgroup)
+    for (int64_t c0 = 0, round = 0; c0 < ns; c0 += kRound, round++) {
+        float v[kSampleAppendVec][4];
+#pragma unroll
+        for (int u = 0; u < kSampleAppendVec; u++) {
+            const int64_t c = c0 + u * kPiece + tid * 4;
+            const float4 x = c < ns ? *reinterpret_cast<const float4 *>(row + c) : make_float4(INFINITY, INFINITY, INFINITY, INFINITY);
+            v[u][0] = x.x; v[u][1] = x.y; v[u][2] = x.z; v[u][3] = x.w;
+        }
+        int mine = 0;  // this wave's
+#pragma unroll
+        for (int u = 0; u < kSampleAppendVec; u++)
+#pragma unroll
+            for (int e = 0; e < 4; e++) mine += __popcll(__ballot(v[u][e] < t));
+        const int b = static_cast<int>(round & 1);  // two sets of totals: one barrier per round
+        if (lane == 0) wave_n[b][wave] = mine;
+        __syncthreads();
+        int at = run, all = 0;
+#pragma unroll
+        for (int w = 0; w < kWaves; w++) {
+            const int cnt = wave_n[b][w];
+            at += w < wave ? cnt : 0;
+            all += cnt;
+        }
+        if (mine != 0) {  // (uniform over the wave)
+#pragma unroll
+            for (int u = 0; u < kSampleAppendVec; u++)
+#pragma unroll
+                for (int e = 0; e < 4; e++) {
+                    const bool pass = v[u][e] < t;
+                    const uint64_t bal = __ballot(pass);
+                    const int pos = at + __popcll(bal & below);
+                    const int64_t c = c0 + u * kPiece + tid * 4 + e;
+                    if (pass && pos < cap)
+                        dst[pos] = make_key(v[u][e], static_cast<uint32_t>((c / kGemmBN) * sample_stride * kGemmBN + c % kGemmBN), false);
+                    at += __popcll(bal);
+                }
+        }
+        run += all;
+    }
+    if (tid == 0) counts[q] = run;
 }
 
 // per query: the kc best keys among the candidates the fused GEMM appended (count <= cap)
@@ -829,13 +913,20 @@ int32_t vg::flat_search_masked(vg_index *idx, const float *queries, int64_t nq, 
                               0, st, thr, cnt * sel_k, INFINITY);
                 }
                 if (bf16) VG_LAUNCH(vg::flat_thr_cap_kernel, dim3(ucnt), dim3(64), 0, st, thr, sel_k, qp, dim, idx->d_norm_max);
-                // (b) the GEMM, appending every element below its query's threshold
-                VG_HIP(hipMemsetAsync(counts, 0, sizeof(int) * static_cast<size_t>(cnt), st));
+                // (b) the GEMM, appending every element below its query's threshold.  The sampled tiles' scores are in `sc` already,
+                // bit for bit, where (a) ran the same tile: what passes there is appended from `sc` (which also sets the counters)
+                // and the GEMM leaves those tiles out — 63/64 of the elements (test hook kHookFlatRescoreSample: all of them again)
+                const bool once = use_sample && vg::gemm_skips_sample(dma, cnt, bf16);
+                if (!once) VG_HIP(hipMemsetAsync(counts, 0, sizeof(int) * static_cast<size_t>(cnt), st));
                 {
                     vg::ProfScope prof(idx->ctx, "flat_gemm", st);
+                    if (once)
+                        VG_LAUNCH(vg::flat_sample_append_kernel, dim3(ucnt), dim3(vg::kSampleAppendThreads), 0, st, sc, ns, sample_stride,
+                                  thr, sel_k, sel_k - 1, counts, cand, cap);
                     VG_TRY(vg::launch_gemm<2>(dot, dma, static_cast<unsigned>(mt * ((nt + 7) / 8) * 8), st,
                                               {ga, cnt, gb, n, gdim, idx->d_norms, nullptr, 1, 0, thr,
-                                               sel_k, sel_k - 1, counts, cand, cap, m0, mask_stride, idx->ctx->compute_units, counts_wide}, bf16));
+                                               sel_k, sel_k - 1, counts, cand, cap, m0, mask_stride, idx->ctx->compute_units, counts_wide,
+                                               once ? sample_stride : 0}, bf16));
                 }
                 // (c) the kc best appended keys (k > kGemmMaxK: all of them go to the exact re-score below)
                 if (k <= vg::kGemmMaxK)

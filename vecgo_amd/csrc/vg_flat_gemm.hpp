@@ -51,6 +51,56 @@ __device__ __forceinline__ void gemm_epilogue(const f32x16 (&acc)[2][2], float *
             for (int g = 0; g < 4; g++)
                 t4[i][g] = *reinterpret_cast<const float4 *>(lds_thr + wr * 64 + i * 32 + 8 * g + 4 * (lane >> 5));
     }
+    if constexpr (MODE == 2) {
+        // Per 32 x 32 block: (1) its 16 scores and their compares with no branch between them — what passes is 16 lane masks;
+        // (2) only a block in which something passed looks at its elements again.  An append is a returning atomic on the
+        // query's counter, a device-scope round trip: it is NOT waited for where it is issued.  The lane parks (slot, query,
+        // key) and stores the key at the end of the tile, after ONE wait for all the appends of the wave's 64 x 64 elements
+        // (about two per wave and tile at the flat search's thresholds, each of which used to be waited out before the next
+        // element was compared).  A lane with a second hit in the tile (rare) first stores its parked key; the wait that takes
+        // sits behind `parked`, a branch no other lane's hit enters.
+        bool parked = false;
+        int park_pos = 0, park_ql = 0;
+        uint64_t park_key = 0;
+        auto store_parked = [&]() {
+            if (park_pos < cap) cand[(q0 + park_ql) * cap + park_pos] = park_key;
+        };
+#pragma unroll
+        for (int j = 0; j < 2; j++) {
+            const int64_t nn = n0 + wc * 64 + j * 32 + (lane & 31);
+            const bool row_ok = nn < n;
+#pragma unroll
+            for (int i = 0; i < 2; i++) {
+                float sc[16];
+                bool pass[16], any = false;
+#pragma unroll
+                for (int r = 0; r < 16; r++) {
+                    const float4 tv = t4[i][r >> 2];
+                    const float t = (r & 3) == 0 ? tv.x : (r & 3) == 1 ? tv.y : (r & 3) == 2 ? tv.z : tv.w;
+                    sc[r] = DOT ? -acc[i][j][r] : __builtin_fmaf(-2.0f, acc[i][j][r], xn[j]);
+                    pass[r] = row_ok && sc[r] < t;
+                    any |= pass[r];
+                }
+                if (any) {
+#pragma unroll
+                    for (int r = 0; r < 16; r++) {
+                        if (!pass[r]) continue;
+                        const int ql = wr * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+                        const int64_t qq = q0 + ql;
+                        // the filter bit is looked at only for the few elements below the threshold
+                        if (mask != nullptr && !mask_bit(filter_of(qq), nn + row_base)) continue;
+                        if (parked) store_parked();
+                        park_pos = atomicAdd(&counts[qq], 1);
+                        park_ql = ql;
+                        park_key = make_key(sc[r], static_cast<uint32_t>(nn) + row_base, false);
+                        parked = true;
+                    }
+                }
+            }
+        }
+        if (parked) store_parked();
+        return;
+    }
 #pragma unroll
     for (int j = 0; j < 2; j++) {
         const int col = wc * 64 + j * 32 + (lane & 31);
@@ -65,19 +115,11 @@ __device__ __forceinline__ void gemm_epilogue(const f32x16 (&acc)[2][2], float *
                 const float sc = DOT ? -dotv : __builtin_fmaf(-2.0f, dotv, xn[j]);
                 if (MODE == 0) {
                     if (qq < nq && nn < n) scores[qq * n + nn] = sc;
-                } else if (MODE == 1) {
+                } else {
                     // (a row the query's filter rejects is not in the sample: the threshold is a quantile of the rows it wants)
                     if (qq < nq)
                         scores[qq * out_cols + tn * kGemmBN + col] =
                             nn < n && (mask == nullptr || mask_bit(filter_of(qq), nn + row_base)) ? sc : INFINITY;
-                } else {
-                    const float4 tv = t4[i][r >> 2];
-                    const float t = (r & 3) == 0 ? tv.x : (r & 3) == 1 ? tv.y : (r & 3) == 2 ? tv.z : tv.w;
-                    // the filter bit is looked at only for the few elements below the threshold
-                    if (nn < n && sc < t && (mask == nullptr || mask_bit(filter_of(qq), nn + row_base))) {
-                        const int pos = atomicAdd(&counts[qq], 1);
-                        if (pos < cap) cand[qq * cap + pos] = make_key(sc, static_cast<uint32_t>(nn) + row_base, false);
-                    }
                 }
             }
         }
@@ -100,6 +142,25 @@ __device__ __forceinline__ void gemm_epilogue_inputs(float &thr_reg, float (&xn)
     }
 }
 
+// The row tile of a workgroup.  skip_stride = s > 1 (MODE 2 only): the caller has already appended what passes in every s-th row
+// tile (the tiles MODE 1 sampled: flat_sample_append_kernel, k_flat.hip), so the grid covers only the tiles with tn % s != 0 —
+// `tn` comes in as the compact index t of such a tile (in the XCD-aware order, as a plain tile index would) and leaves as
+// tn = t + t / (s - 1) + 1.  False: no such tile, the workgroup has nothing to do.
+__host__ __device__ inline int64_t gemm_skip_sampled_tiles(int64_t ntiles, int skip_stride)
+{
+    return skip_stride > 1 ? (ntiles + skip_stride - 1) / skip_stride : 0;
+}
+template <int MODE>
+__device__ __forceinline__ bool gemm_row_tile(int64_t &tn, int64_t ntiles, int skip_stride)
+{
+    if (MODE == 2 && skip_stride > 1) {
+        if (tn >= ntiles - gemm_skip_sampled_tiles(ntiles, skip_stride)) return false;
+        tn += static_cast<int>(tn) / (skip_stride - 1) + 1;  // (a grid index: 32 bits)
+        return true;
+    }
+    return tn < ntiles;
+}
+
 // MODE 0: scores[q][n] for every row.  MODE 1: only every tile_stride-th row tile, written
 // compactly (row length out_cols; columns past n hold +Inf) — the sample that sets the per-query
 // threshold.  MODE 2: no score matrix at all: an element below its query's threshold is appended
@@ -114,7 +175,7 @@ __global__ __launch_bounds__(kGemmThreads) void flat_gemm_kernel(
     int dim, const float *__restrict__ norms, float *__restrict__ scores, int tile_stride,
     int64_t out_cols, const float *__restrict__ thr, int thr_stride, int thr_off,
     int *__restrict__ counts, uint64_t *__restrict__ cand, int cap, const uint8_t *__restrict__ mask = nullptr,
-    int64_t mask_stride = 0)
+    int64_t mask_stride = 0, int skip_stride = 0)
 {
     extern __shared__ float gemm_lds[];  // A0 | B0 | A1 | B1, kGemmLdsBytes
     float *const As0 = gemm_lds, *const Bs0 = gemm_lds + kGemmTile;
@@ -127,9 +188,9 @@ __global__ __launch_bounds__(kGemmThreads) void flat_gemm_kernel(
                                      : (n + kGemmBN - 1) / kGemmBN;
     const int64_t bt = blockIdx.x;
     const int64_t xcd = bt & 7, jx = bt >> 3;
-    const int64_t tn = (jx / mtiles) * 8 + xcd;
+    int64_t tn = (jx / mtiles) * 8 + xcd;
     const int tm = static_cast<int>(jx % mtiles);
-    if (tn >= ntiles) return;
+    if (!gemm_row_tile<MODE>(tn, ntiles, skip_stride)) return;
     const int64_t q0 = static_cast<int64_t>(tm) * kGemmBM;
     const int64_t n0 = (MODE == 1 ? tn * tile_stride : tn) * kGemmBN;
 
@@ -325,16 +386,16 @@ __device__ __forceinline__ void flat_gemm_dma_body(
     int dim, const float *__restrict__ norms, float *__restrict__ scores, int tile_stride,
     int64_t out_cols, const float *__restrict__ thr, int thr_stride, int thr_off,
     int *__restrict__ counts, uint64_t *__restrict__ cand, int cap, const uint8_t *__restrict__ mask,
-    int64_t mask_stride, int64_t bt, uint32_t row_base, const int64_t *__restrict__ mask_off = nullptr)
+    int64_t mask_stride, int64_t bt, uint32_t row_base, const int64_t *__restrict__ mask_off = nullptr, int skip_stride = 0)
 {
     extern __shared__ float gemm_lds[];
     const int mtiles = static_cast<int>((nq + kGemmBM - 1) / kGemmBM);
     const int64_t ntiles = MODE == 1 ? (((n + kGemmBN - 1) / kGemmBN) + tile_stride - 1) / tile_stride
                                      : (n + kGemmBN - 1) / kGemmBN;
     const int64_t xcd = bt & 7, jx = bt >> 3;
-    const int64_t tn = (jx / mtiles) * 8 + xcd;
+    int64_t tn = (jx / mtiles) * 8 + xcd;
     const int tm = static_cast<int>(jx % mtiles);
-    if (tn >= ntiles) return;
+    if (!gemm_row_tile<MODE>(tn, ntiles, skip_stride)) return;
     const int64_t q0 = static_cast<int64_t>(tm) * kGemmBM;
     const int64_t n0 = (MODE == 1 ? tn * tile_stride : tn) * kGemmBN;
 
@@ -481,10 +542,10 @@ __global__ __launch_bounds__(kGemmThreads) void flat_gemm_dma_kernel(
     int dim, const float *__restrict__ norms, float *__restrict__ scores, int tile_stride,
     int64_t out_cols, const float *__restrict__ thr, int thr_stride, int thr_off,
     int *__restrict__ counts, uint64_t *__restrict__ cand, int cap, const uint8_t *__restrict__ mask = nullptr,
-    int64_t mask_stride = 0)
+    int64_t mask_stride = 0, int skip_stride = 0)
 {
     flat_gemm_dma_body<DOT, MODE, PROBE, BF16, false>(queries, nq, base, n, dim, norms, scores, tile_stride, out_cols, thr, thr_stride,
-                                                       thr_off, counts, cand, cap, mask, mask_stride, blockIdx.x, 0u);
+                                                       thr_off, counts, cand, cap, mask, mask_stride, blockIdx.x, 0u, nullptr, skip_stride);
 }
 
 // One launch over MANY problems that share the row matrix (the partition-probed flat search, k_probe.hip: problem p = the queries

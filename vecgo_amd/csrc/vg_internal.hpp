@@ -94,6 +94,7 @@ enum Hook {
     kHookKmNoRanges,          // VG_KM_NO_RANGES         k-means: the listed points' exact pass in one walk over the centroids (no ranges)
     kHookNoCandReplay,        // VG_NO_CAND_REPLAY       no heap replay for queries whose scores may hold a NaN (vg_cand_replay.hpp): what the fast paths alone answer
     kHookVamanaSmallScratch,  // VG_VAMANA_SMALL_SCRATCH vg_search_vamana with k > 512: 64 MiB of per-launch scratch, so that a small batch takes several launches
+    kHookFlatRescoreSample,   // VG_FLAT_RESCORE_SAMPLE  flat search: the main GEMM multiplies the sampled row tiles again (no append from the sample)
     kHookCount
 };
 bool hook(Hook h);
