@@ -13,6 +13,7 @@
 #include <random>
 
 #include "../../vecgo_amd/csrc/vg_build_plan.hpp"
+#include "../../vecgo_amd/csrc/vg_scan_slices.hpp"
 #include "../../vecgo_amd/csrc/vg_walk_chunk.hpp"
 #include "vecgo_hip.hpp"
 #include "vg_oracle.h"
@@ -68,6 +69,16 @@ static_assert(vg::walk_chunk(int64_t(16) << 30, 650000, 8192) == 8192, "room for
 static_assert(vg::walk_chunk(int64_t(1) << 30, 131072, 8192) == 8192 && vg::walk_chunk(int64_t(1) << 30, 131073, 8192) == 8191,
               "the quotient is exact at the boundary");
 static_assert(vg::walk_chunk(int64_t(1) << 30, 0, 5) == 5 && vg::walk_chunk(0, 100, 5) == 1, "no scratch per query; no room at all");
+
+// the slices of a whole-segment code scan (vg_scan_slices.hpp): SQ8 and RaBitQ ask for 4 workgroups per CU over the
+// segment's tiles, the PQ ADC scan for 1 over its 8-wave groups of tiles; a multiple of 8, never more than the tiles allow
+static_assert(vg::scan_slices(1, 15625, 256, 4) == 1024, "one query, 1M rows: 4 workgroups on each of 256 CUs");
+static_assert(vg::scan_slices(3, 15625, 256, 4) == 344, "ceil(1024 / 3) = 342, up to a multiple of 8");
+static_assert(vg::scan_slices(256, 15625, 256, 4) == 8, "enough units per slice: one slice per XCD");
+static_assert(vg::scan_slices(1, 100, 256, 4) == 96, "100 tiles: the multiple of 8 below");
+static_assert(vg::scan_slices(1, 5, 256, 4) == 8, "fewer tiles than XCDs: still 8");
+static_assert(vg::scan_slices(1, 1954, 256, 1) == 256, "ADC, 1M rows in groups of 8 waves: one workgroup per CU");
+static_assert(vg::scan_slices(1024, 1954, 256, 1) == 8, "ADC, more queries than CUs");
 
 // The (node, level) pairs and the batches of a plan, restated: pair_base is contiguous, every node's pairs are levels
 // 0..min(level, top when its batch began) in order, every batch starts from the entry point and top level that

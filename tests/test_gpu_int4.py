@@ -26,7 +26,9 @@ def ctx(vg):
     return vg.Context(0)
 
 
-@pytest.mark.parametrize("n,dim", [(400, 128), (200, 768), (257, 100), (64, 17), (1, 3), (300, 33), (500, 64)])
+# n > 8192: the shared min / max pass (dim_minmax_kernel) walks 1024 uneven row chunks, 8 rows at a time and a remainder;
+# dim 260: a second block of dimensions with 4 live threads
+@pytest.mark.parametrize("n,dim", [(400, 128), (200, 768), (257, 100), (64, 17), (1, 3), (300, 33), (500, 64), (9001, 5), (20011, 260)])
 def test_train_encode_decode_distances_match_oracle(vg, ctx, n, dim):
     rng = np.random.default_rng(n + dim)
     x = rng.standard_normal((n, dim)).astype(np.float32)

@@ -23,7 +23,9 @@ def ctx(vg):
     return vg.Context(0)
 
 
-@pytest.mark.parametrize("n,dim", [(500, 128), (300, 768), (257, 100), (64, 17), (5, 3), (1000, 16)])
+# n > 8192: the shared min / max pass (dim_minmax_kernel) walks 1024 uneven row chunks, 8 rows at a time and a remainder;
+# dim 260: a second block of dimensions with 4 live threads
+@pytest.mark.parametrize("n,dim", [(500, 128), (300, 768), (257, 100), (64, 17), (5, 3), (1000, 16), (9001, 5), (20011, 260)])
 def test_train_encode_decode_match_oracle(vg, ctx, n, dim):
     rng = np.random.default_rng(n + dim)
     x = rng.standard_normal((n, dim)).astype(np.float32)

@@ -17,11 +17,11 @@ HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 
 
 @pytest.fixture(scope="module")
-def sq8_asm(tmp_path_factory):
+def int4_asm(tmp_path_factory):
     if not Path(HIPCC).exists():
         pytest.skip("no hipcc")
-    out = tmp_path_factory.mktemp("isa") / "k_sq8.s"
-    src = ROOT / "vecgo_amd" / "csrc" / "k_sq8.hip"
+    out = tmp_path_factory.mktemp("isa") / "k_int4.s"
+    src = ROOT / "vecgo_amd" / "csrc" / "k_int4.hip"
     flags = re.search(r"^FLAGS\s*:=\s*(.*?)(?:\n\S|\Z)", (src.parent / "Makefile").read_text(), flags=re.S | re.M).group(1)
     flags = [f for f in flags.replace("\\\n", " ").split() if f not in ("-fPIC",) and not f.startswith("$(")]
     cmd = [HIPCC, "--offload-arch=gfx950", *[f for f in flags if not f.startswith("--offload-arch")],
@@ -38,8 +38,8 @@ def _kernel(asm, mangled_prefix):
 
 
 @pytest.mark.parametrize("inst", ["ILb1E", "ILb0E"])   # PRE = true / false
-def test_int4_lookup_loop_has_nothing_else_on_lgkmcnt(sq8_asm, inst):
-    body, meta = _kernel(sq8_asm, f"_ZN2vg20int4_scan_tab_kernel{inst}")
+def test_int4_lookup_loop_has_nothing_else_on_lgkmcnt(int4_asm, inst):
+    body, meta = _kernel(int4_asm, f"_ZN2vg20int4_scan_tab_kernel{inst}")
     assert re.search(r"; ScratchSize: 0\b", meta), "int4_scan_tab_kernel spills: scratch traffic inside the counted waits"
     lines = body.splitlines()
     start = next(i for i, ln in enumerate(lines) if "Inner Loop Header: Depth=2" in ln)

@@ -1,4 +1,4 @@
-"""Stage probe of int4_scan_tab_kernel (a -DVG_I4_TIMING build: tools/build_variant.sh i4t k_sq8.hip -DVG_I4_TIMING, run
+"""Stage probe of int4_scan_tab_kernel (a -DVG_I4_TIMING build: tools/build_variant.sh i4t k_int4.hip -DVG_I4_TIMING, run
 with VECGO_HIP_LIB=variants/libvecgo_i4t.so): s_memtime cycles (100 MHz constant clock on gfx9: 10 ns per tick) per
 wave by phase — waiting for the piece's global loads + issuing the staging writes, the staging round trip until the
 first 16 code bytes are back, the 8 x 32 lookups of the piece.  argv: [N]."""

@@ -31,6 +31,7 @@
 #include "vg_internal.hpp"
 #include "vg_cand_replay.hpp"
 #include "vg_nominate.hpp"
+#include "vg_scan_slices.hpp"
 #include "vg_search.hpp"
 
 namespace vg {
@@ -767,20 +768,6 @@ int32_t launch_probe_scan_adc(const vg_index *idx, const float *tables, const ui
     return VG_OK;
 }
 
-static int adc_slices(int64_t nq, int64_t n_tiles, int cus)
-{
-    // smallest multiple of 8 (one group per XCD) with slices*nq >= #CUs, at least one
-    // workgroup-iteration of tiles per slice
-    int64_t s = (cus + nq - 1) / nq;
-    s = ((s + 7) / 8) * 8;
-    int64_t max_s = (n_tiles + kAdcWaves - 1) / kAdcWaves;
-    max_s = (max_s / 8) * 8;
-    if (max_s < 8) max_s = 8;
-    if (s > max_s) s = max_s;
-    if (s < 8) s = 8;
-    return static_cast<int>(s);
-}
-
 template <int GF, bool SMALLK>
 static int32_t launch_scan(const vg_index *idx, const float *tables, int64_t nq, int k,
                            int slices, uint64_t *partial, hipStream_t st, int raw_lists = 0,
@@ -1203,7 +1190,7 @@ struct PqTableRow {
 static bool pq_nomination_applies(const vg_index *idx, const float *d_queries, int64_t nq, int k, const uint8_t *mask, bool desc)
 {
     return idx->pq_nom.rows && !mask && !desc && (nq * idx->n >= kPqNomMinPairs || hook(kHookPqNomAlways)) && k <= kNomMaxK && idx->n > k && idx->pq->k == 256 &&
-           (reinterpret_cast<uintptr_t>(d_queries) & 15) == 0;
+           aligned16(d_queries);
 }
 }  // namespace vg
 
@@ -1365,17 +1352,14 @@ static int32_t pq_adc_search_impl(vg_index *idx, const float *queries, int64_t n
                                      return pq_adc_search_impl(idx, fq, nf, k, nullptr, 0, false, fid, fsc, st, false);
                                  }));
     } else {
-        int slices = vg::adc_slices(nq, idx->n_tiles, idx->ctx->compute_units);
+        // one workgroup per CU: the smallest multiple of 8 (one group per XCD) with slices * nq >= #CUs, at least one
+        // workgroup-iteration of tiles (kAdcWaves of them) per slice
+        const int64_t tile_groups = (idx->n_tiles + vg::kAdcWaves - 1) / vg::kAdcWaves;
+        int slices = vg::scan_slices(nq, tile_groups, idx->ctx->compute_units, 1);
         const bool bigk = k > 64;
         const bool bigk_fast = bigk && !vg::hook(vg::kHookAdcBigkExhaustive);  // test hook: LDS-buffer path only
-        if (bigk_fast) {
-            // enough waves that a wave expects <= ~8 of the k best rows (capacity 64 each)
-            int64_t want = ((static_cast<int64_t>(k) / 64 + 7) / 8) * 8;
-            int64_t max_s = (((idx->n_tiles + vg::kAdcWaves - 1) / vg::kAdcWaves) / 8) * 8;
-            if (max_s < 8) max_s = 8;
-            if (want > max_s) want = max_s;
-            if (want > slices) slices = static_cast<int>(want);
-        }
+        // enough waves that a wave expects <= ~8 of the k best rows (capacity 64 each): k / 64 workgroups by the same rule
+        if (bigk_fast) slices = std::max(slices, vg::scan_slices(1, tile_groups, k / 64, 1));
         vg::ArenaCall ar(idx->ctx, st);
         const int i_tables = ar.add(sizeof(float) * static_cast<size_t>(nq) * vg::lut_image_words(pq->m));
         const int i_partial = ar.add(sizeof(uint64_t) * static_cast<size_t>(nq) * slices *

@@ -24,6 +24,27 @@ __global__ __launch_bounds__(kExactThreads) void batch_kernel(const float *__res
     }
 }
 
+// simd.SquaredL2Bounded over n targets, each against its own bound (or one bound for all)
+__global__ __launch_bounds__(256) void bounded_batch_kernel(const float *__restrict__ query,
+                                                            const float *__restrict__ targets, int dim, int64_t n,
+                                                            const float *__restrict__ bounds, int64_t n_bounds,
+                                                            float *__restrict__ dist, int32_t *__restrict__ exceeded)
+{
+    const Sub16 sub = Sub16::make(threadIdx.x);
+    const int64_t groups = static_cast<int64_t>(gridDim.x) * 16;
+    for (int64_t i = static_cast<int64_t>(blockIdx.x) * 16 + (threadIdx.x >> 4); i < n; i += groups) {
+        float v = exact_pair16<false, kBounded, true>(targets + i * dim, query, dim, sub);  // (read once: nontemporal)
+        const float b = bounds[n_bounds == 1 ? 0 : i];
+        const bool over = v > b;  // partial sums never decrease: some block's partial > bound <=> the full sum is
+        // the reference returns the PARTIAL total of the block where it stopped: replayed for the pairs that exceed
+        if (over) v = exact_l2_bounded_partial16(targets + i * dim, query, dim, sub, b, v);
+        if ((threadIdx.x & 15) == 0) {
+            dist[i] = v;
+            exceeded[i] = over ? 1 : 0;
+        }
+    }
+}
+
 // scores[q][c] = exact distance(query q, row cand[q][c]); one workgroup per (query, chunk)
 template <bool DOT>
 __global__ __launch_bounds__(kExactThreads) void score_candidates_kernel(
@@ -242,6 +263,34 @@ VG_API int32_t vg_dot_batch(vg_ctx *ctx, const float *query, const float *target
                             int64_t n, float *out, void *stream)
 {
     return batch_impl(ctx, true, query, targets, dim, n, out, stream);
+}
+
+VG_API int32_t vg_squared_l2_bounded_batch(vg_ctx *ctx, const float *query, const float *targets, int64_t dim,
+                                           int64_t n, const float *bounds, int64_t n_bounds, float *dist,
+                                           int32_t *exceeded, void *stream)
+{
+    VG_CHECK(ctx, VG_ERR_INVALID_ARG, "vg_squared_l2_bounded_batch: ctx is NULL");
+    if (n <= 0) return VG_OK;
+    VG_CHECK(dim >= 0 && dim < (1 << 30), VG_ERR_INVALID_ARG, "vg_squared_l2_bounded_batch: bad dim");
+    VG_CHECK(bounds && dist && exceeded && (n_bounds == 1 || n_bounds == n), VG_ERR_INVALID_ARG,
+             "vg_squared_l2_bounded_batch: bounds must have 1 or n entries");
+    VG_CHECK(dim == 0 || (query && targets), VG_ERR_INVALID_ARG, "vg_squared_l2_bounded_batch: NULL buffer");
+    VG_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = vg::pick_stream(ctx, stream);
+    vg::DevIn<float> q, t, b;
+    vg::DevOut<float> od;
+    vg::DevOut<int32_t> oe;
+    VG_TRY(q.init(query, static_cast<size_t>(dim), st));
+    VG_TRY(t.init(targets, static_cast<size_t>(n) * dim, st));
+    VG_TRY(b.init(bounds, static_cast<size_t>(n_bounds), st));
+    VG_TRY(od.init(dist, static_cast<size_t>(n), st));
+    VG_TRY(oe.init(exceeded, static_cast<size_t>(n), st));
+    int64_t blocks = std::min<int64_t>((n + 15) / 16, 4096);
+    VG_LAUNCH(vg::bounded_batch_kernel, dim3(static_cast<unsigned>(blocks)), dim3(256), 0, st, q.ptr, t.ptr,
+                       static_cast<int>(dim), n, b.ptr, n_bounds, od.ptr, oe.ptr);
+    VG_TRY(od.finish());
+    VG_TRY(oe.finish());
+    return VG_OK;
 }
 
 VG_API int32_t vg_score_candidates(vg_index *idx, const float *queries, int64_t nq,

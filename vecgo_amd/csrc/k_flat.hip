@@ -1062,7 +1062,7 @@ int32_t flat_probe_gemm(vg_index *idx, const float *pair_queries, int64_t pairs,
 {
     // img.rows != null: nominate on that bfloat16 row image (with its norms) instead of the fp32 rows, and leave the exact
     // re-score + proof to the caller: *nominated = where the per-pair thresholds / counts / 64 candidates are (the partition-probed
-    // SQ8 scan, k_sq8.hip)
+    // SQ8 scan, k_sq8_scan.hip)
     // first_block / grid: [0] sample, [1] main launch of the 128-query tiles (groups of more than 64 pairs); [2], [3] the same of
     // the 64-query tiles (flat_gemm_dma32_grouped_kernel<.., 2>: a group of at most 64 pairs is one query tile, one workgroup per
     // row tile, HBM-bound — a 128-query tile would spend the matrix cores on padding)

@@ -180,7 +180,7 @@ static int32_t fg_group(const int32_t *assign, int64_t n, int P, uint32_t *perm,
 }
 
 // ---- SQ8 codes back to the reference's row-major layout -----------------------------------------------------------------
-// the inverse of sq8_retile_kernel (k_sq8.hip): piece (tile, group, lane) -> codes[row * dim + group * 16 ...]
+// the inverse of sq8_retile_kernel (k_sq8_scan.hip): piece (tile, group, lane) -> codes[row * dim + group * 16 ...]
 __global__ __launch_bounds__(256) void fg_sq8_untile_kernel(const uint4 *__restrict__ tiles, int64_t n, int dim, int groups, int64_t n_tiles,
                                                             uint8_t *__restrict__ codes)
 {

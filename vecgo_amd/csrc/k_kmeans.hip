@@ -1,5 +1,4 @@
-// k_kmeans.hip — internal/kmeans (TrainKMeans, AssignPartition, FindClosestCentroids) plus the
-// remaining batched L0 seams (SquaredL2Bounded, PqAdcLookup).
+// k_kmeans.hip — internal/kmeans (TrainKMeans, AssignPartition, FindClosestCentroids).
 #include <algorithm>
 #include <numeric>
 
@@ -426,136 +425,6 @@ __global__ void km_gather_rows_kernel(const float *__restrict__ vectors, int dim
     if (gid >= static_cast<int64_t>(k) * dim) return;
     out[gid] = vectors[rows[gid / dim] * dim + gid % dim];
 }
-
-__global__ __launch_bounds__(256) void bounded_batch_kernel(const float *__restrict__ query,
-                                                            const float *__restrict__ targets, int dim, int64_t n,
-                                                            const float *__restrict__ bounds, int64_t n_bounds,
-                                                            float *__restrict__ dist, int32_t *__restrict__ exceeded)
-{
-    const Sub16 sub = Sub16::make(threadIdx.x);
-    const int64_t groups = static_cast<int64_t>(gridDim.x) * 16;
-    for (int64_t i = static_cast<int64_t>(blockIdx.x) * 16 + (threadIdx.x >> 4); i < n; i += groups) {
-        float v = exact_pair16<false, kBounded, true>(targets + i * dim, query, dim, sub);  // (read once: nontemporal)
-        const float b = bounds[n_bounds == 1 ? 0 : i];
-        const bool over = v > b;  // partial sums never decrease: some block's partial > bound <=> the full sum is
-        // the reference returns the PARTIAL total of the block where it stopped: replayed for the pairs that exceed
-        if (over) v = exact_l2_bounded_partial16(targets + i * dim, query, dim, sub, b, v);
-        if ((threadIdx.x & 15) == 0) {
-            dist[i] = v;
-            exceeded[i] = over ? 1 : 0;
-        }
-    }
-}
-
-// pqAdcLookupAvx512 (floats_avx512.c:135-167): thread per code row
-__global__ void adc_lookup_batch_kernel(const float *__restrict__ table, const uint8_t *__restrict__ codes, int m,
-                                        int64_t n, float *__restrict__ out)
-{
-    const int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const uint8_t *c = codes + i * m;
-    float acc[16];
-#pragma unroll
-    for (int l = 0; l < 16; l++) acc[l] = 0.0f;
-    int j = 0;
-    for (; j + 16 <= m; j += 16) {
-#pragma unroll
-        for (int l = 0; l < 16; l++) acc[l] = acc[l] + table[(j + l) * 256 + c[j + l]];
-    }
-    float total = reduce16_regs(acc);
-    for (; j < m; j++) total = total + table[j * 256 + c[j]];
-    out[i] = total;
-}
-
-// The same sums as a streaming scan (m % 16 == 0, table <= 128 KiB): the kernel above reads a code byte by byte at an
-// m-byte stride and every table entry from global memory (0.86 TB/s of codes at m = 96).  Here the table sits in LDS
-// (m KiB, one persistent workgroup per CU), a wave takes 64 rows — one contiguous 64 m-byte block, read as whole lines —
-// and turns them through its LDS (row stride 16 x odd: conflict-free ds_read_b128); each lane then walks ITS code:
-// acc[l] += table[(j + l) * 256 + code[j + l]] for j ascending, the reduce tree — the arithmetic of pqAdcLookupAvx512.
-// (The re-tiled index scan, pq_adc_scan_kernel, pre-rotates the codes per lane so that its lookups avoid most bank
-// conflicts; a row-major batch cannot, and runs at the LDS rate of random 4-byte reads.)
-template <int M16>  // m / 16 when known at compile time, 0 = any
-__global__ __launch_bounds__(512) void adc_lookup_batch_lds_kernel(const float *__restrict__ table, const uint8_t *__restrict__ codes,
-                                                                   int m_rt, int stride, int64_t n, float *__restrict__ out)
-{
-    extern __shared__ __attribute__((aligned(16))) unsigned char adc_smem[];
-    const int m = M16 ? M16 * 16 : m_rt;
-    const int m16 = M16 ? M16 : m_rt >> 4;
-    float *lut = reinterpret_cast<float *>(adc_smem);
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, waves = blockDim.x >> 6;
-    {
-        const float4 *src = reinterpret_cast<const float4 *>(table);
-        float4 *dst = reinterpret_cast<float4 *>(lut);
-        for (int i = tid; i < m * 64; i += blockDim.x) dst[i] = src[i];
-    }
-    __syncthreads();
-    unsigned char *stage = adc_smem + static_cast<size_t>(m) * 1024 + static_cast<size_t>(wave) * 64 * stride;
-    const int64_t n_tiles = (n + 63) / 64;
-    const int units = 64 * m16;  // 16-byte units of a tile
-    const int64_t tile_step = static_cast<int64_t>(gridDim.x) * waves;
-    // unit e of tile t (past n: the tile's last valid unit again — valid memory, values unused)
-    auto get = [&](int64_t t, int e) {
-        const int64_t row0 = t * 64;
-        const int64_t last_unit = (n - row0 < 64 ? n - row0 : 64) * m16 - 1;
-        return load_stream(reinterpret_cast<const uint4 *>(codes + row0 * m + (e <= last_unit ? e : last_unit) * 16));  // read once
-    };
-    auto put = [&](int e, const uint4 u) {
-        const int r = e / m16, part = e - r * m16;
-        *reinterpret_cast<uint4 *>(stage + r * stride + part * 16) = u;
-    };
-    int64_t tile = static_cast<int64_t>(blockIdx.x) * waves + wave;
-    if (tile >= n_tiles) return;
-    // m = 96: a lane's six units of the NEXT tile are requested before this tile's lookups (8 waves per CU do not hide an
-    // HBM round trip per tile by themselves: the waves waited 72 % of their cycles)
-    uint4 p0, p1, p2, p3, p4, p5;
-    if (M16 == 6) {
-        p0 = get(tile, lane);
-        p1 = get(tile, lane + 64);
-        p2 = get(tile, lane + 128);
-        p3 = get(tile, lane + 192);
-        p4 = get(tile, lane + 256);
-        p5 = get(tile, lane + 320);
-    }
-    for (; tile < n_tiles; tile += tile_step) {
-        const int64_t row0 = tile * 64;
-        if (M16 == 6) {
-            put(lane, p0);
-            put(lane + 64, p1);
-            put(lane + 128, p2);
-            put(lane + 192, p3);
-            put(lane + 256, p4);
-            put(lane + 320, p5);
-            const int64_t tn = tile + tile_step < n_tiles ? tile + tile_step : tile;
-            p0 = get(tn, lane);
-            p1 = get(tn, lane + 64);
-            p2 = get(tn, lane + 128);
-            p3 = get(tn, lane + 192);
-            p4 = get(tn, lane + 256);
-            p5 = get(tn, lane + 320);
-        } else {
-            for (int e0 = 0; e0 < units; e0 += 64) {
-                const uint4 u = get(tile, e0 + lane);
-                if (e0 + lane < units) put(e0 + lane, u);
-            }
-        }
-        float acc[16];
-#pragma unroll
-        for (int l = 0; l < 16; l++) acc[l] = 0.0f;
-        for (int g = 0; g < m16; g++) {
-            const uint4 c = *reinterpret_cast<const uint4 *>(stage + lane * stride + g * 16);
-            const uint32_t w[4] = {c.x, c.y, c.z, c.w};
-            const float *row = lut + g * 16 * 256;
-            float t[16];
-#pragma unroll
-            for (int l = 0; l < 16; l++) t[l] = row[l * 256 + ((w[l >> 2] >> (8 * (l & 3))) & 0xFFu)];
-#pragma unroll
-            for (int l = 0; l < 16; l++) acc[l] = acc[l] + t[l];
-        }
-        const float total = reduce16_regs(acc);
-        if (row0 + lane < n) out[row0 + lane] = total;
-    }
-}
-
 
 // ---- assignment by MFMA nomination + exact decision ------------------------------------------------------------------
 // The assignment pass is a [points x centroids x dim] product: n * k * dim fused multiply-adds on the matrix cores
@@ -1026,7 +895,7 @@ static int32_t km_launch_exact(bool dot, const float *v, int64_t n, int dim, con
                                int *changed, hipStream_t st, const int32_t *list = nullptr, const int *list_count = nullptr,
                                float *range_d = nullptr, int32_t *range_i = nullptr)
 {
-    const bool aligned = (reinterpret_cast<uintptr_t>(v) & 15) == 0 && (reinterpret_cast<uintptr_t>(cent) & 15) == 0;
+    const bool aligned = vg::aligned16(v, cent);
     if (aligned) {
         switch (dim) {
         case 64: return km_launch_regs<1>(dot, v, n, cent, k, assign, changed, st, list, list_count, range_d, range_i);
@@ -1073,7 +942,7 @@ struct KmMfma {
 
     static bool eligible(const float *v, int64_t n, int dim, const float *cent, int k)
     {
-        const bool aligned = ((reinterpret_cast<uintptr_t>(v) | reinterpret_cast<uintptr_t>(cent)) & 15) == 0;
+        const bool aligned = vg::aligned16(v, cent);
         // below a few thousand points the passes around the GEMM cost more than the reference-order kernel
         return aligned && dim % 4 == 0 && dim >= 32 && n >= 4096 && n <= INT32_MAX && k >= 2 && !vg::hook(vg::kHookKmNoMfma);
     }
@@ -1318,69 +1187,5 @@ VG_API int32_t vg_find_closest_centroids(vg_ctx *ctx, const float *query, const 
         for (int i = 0; i < n; i++) out[i] = order[static_cast<size_t>(i)];
     }
     if (n_out) *n_out = n;
-    return VG_OK;
-}
-
-VG_API int32_t vg_squared_l2_bounded_batch(vg_ctx *ctx, const float *query, const float *targets, int64_t dim,
-                                           int64_t n, const float *bounds, int64_t n_bounds, float *dist,
-                                           int32_t *exceeded, void *stream)
-{
-    VG_CHECK(ctx, VG_ERR_INVALID_ARG, "vg_squared_l2_bounded_batch: ctx is NULL");
-    if (n <= 0) return VG_OK;
-    VG_CHECK(dim >= 0 && dim < (1 << 30), VG_ERR_INVALID_ARG, "vg_squared_l2_bounded_batch: bad dim");
-    VG_CHECK(bounds && dist && exceeded && (n_bounds == 1 || n_bounds == n), VG_ERR_INVALID_ARG,
-             "vg_squared_l2_bounded_batch: bounds must have 1 or n entries");
-    VG_CHECK(dim == 0 || (query && targets), VG_ERR_INVALID_ARG, "vg_squared_l2_bounded_batch: NULL buffer");
-    VG_HIP(hipSetDevice(ctx->device));
-    hipStream_t st = vg::pick_stream(ctx, stream);
-    vg::DevIn<float> q, t, b;
-    vg::DevOut<float> od;
-    vg::DevOut<int32_t> oe;
-    VG_TRY(q.init(query, static_cast<size_t>(dim), st));
-    VG_TRY(t.init(targets, static_cast<size_t>(n) * dim, st));
-    VG_TRY(b.init(bounds, static_cast<size_t>(n_bounds), st));
-    VG_TRY(od.init(dist, static_cast<size_t>(n), st));
-    VG_TRY(oe.init(exceeded, static_cast<size_t>(n), st));
-    int64_t blocks = std::min<int64_t>((n + 15) / 16, 4096);
-    VG_LAUNCH(vg::bounded_batch_kernel, dim3(static_cast<unsigned>(blocks)), dim3(256), 0, st, q.ptr, t.ptr,
-                       static_cast<int>(dim), n, b.ptr, n_bounds, od.ptr, oe.ptr);
-    VG_TRY(od.finish());
-    VG_TRY(oe.finish());
-    return VG_OK;
-}
-
-VG_API int32_t vg_pq_adc_lookup_batch(vg_ctx *ctx, const float *table, const uint8_t *codes, int64_t m, int64_t n,
-                                      float *out, void *stream)
-{
-    VG_CHECK(ctx, VG_ERR_INVALID_ARG, "vg_pq_adc_lookup_batch: ctx is NULL");
-    VG_CHECK(m >= 0 && n >= 0 && m < (1 << 20), VG_ERR_INVALID_ARG, "vg_pq_adc_lookup_batch: bad sizes");
-    if (n == 0) return VG_OK;
-    VG_CHECK(out && (m == 0 || (table && codes)), VG_ERR_INVALID_ARG, "vg_pq_adc_lookup_batch: NULL buffer");
-    VG_HIP(hipSetDevice(ctx->device));
-    hipStream_t st = vg::pick_stream(ctx, stream);
-    vg::DevIn<float> t;
-    vg::DevIn<uint8_t> c;
-    vg::DevOut<float> o;
-    VG_TRY(t.init(table, static_cast<size_t>(m) * 256, st));
-    VG_TRY(c.init(codes, static_cast<size_t>(n) * m, st));
-    VG_TRY(o.init(out, static_cast<size_t>(n), st));
-    // table in LDS + rows turned through LDS when both fit (m % 16 == 0)
-    const int stride = static_cast<int>(16 * ((m >> 4) | 1));
-    const int64_t lds_free = 160 * 1024 - m * 1024;
-    const int waves = m > 0 && m % 16 == 0 ? static_cast<int>(std::min<int64_t>(8, lds_free / (64 * stride))) : 0;
-    const bool aligned = ((reinterpret_cast<uintptr_t>(c.ptr) | reinterpret_cast<uintptr_t>(t.ptr)) & 15) == 0;
-    if (waves >= 2 && aligned) {
-        const size_t lds = static_cast<size_t>(m) * 1024 + static_cast<size_t>(waves) * 64 * stride;
-        const int64_t tiles = (n + 63) / 64;
-        const unsigned blocks = static_cast<unsigned>(std::min<int64_t>((tiles + waves - 1) / waves, std::max(ctx->compute_units, 1)));
-        auto kern = m == 96 ? vg::adc_lookup_batch_lds_kernel<6> : vg::adc_lookup_batch_lds_kernel<0>;
-        VG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   static_cast<int>(lds)));
-        VG_LAUNCH(kern, dim3(blocks), dim3(waves * 64), lds, st, t.ptr, c.ptr, static_cast<int>(m), stride, n, o.ptr);
-    } else {
-        VG_LAUNCH(vg::adc_lookup_batch_kernel, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, st,
-                           t.ptr, c.ptr, static_cast<int>(m), n, o.ptr);
-    }
-    VG_TRY(o.finish());
     return VG_OK;
 }

@@ -5,7 +5,7 @@
 // is total — (score, row id) — so the result is the k best keys of the union of the probed ranges:
 //   1. per query: distances to the P centroids in SquaredL2Batch / DotBatch order, the nprobes best
 //   2. per (query, probe[, slice]): scan of that partition's rows with the segment's scan type
-//      (fp32 pair order here; PQ table lookups k_adc.hip; SQ8 k_sq8.hip), a k-list each
+//      (fp32 pair order here; PQ table lookups k_adc.hip; SQ8 k_sq8_scan.hip), a k-list each
 //   3. one merge of the lists per query
 #include <algorithm>
 
@@ -689,7 +689,7 @@ static int32_t probed_whole_shortcut(const ProbedCall &c, bool *done)
     // probe kernels pay per wanted row: 8 queries up it wins or ties (tools/filtered_time.py).  Same results either way.
     if (c.scan == VG_SCAN_F32 && c.nq >= 8) return vg::flat_search_masked(idx, c.q, c.nq, c.k, c.mk, c.mask_stride, c.oid, c.osc, c.st);
     // A filtered SQ8 batch over the whole segment with vg_index_enable_sq8_nomination: the bf16 nomination with the filter in its
-    // epilogue, the exact re-score from the codes, the proof (k_sq8.hip); queries whose proof fails take the probe kernels
+    // epilogue, the exact re-score from the codes, the proof (k_sq8_scan.hip); queries whose proof fails take the probe kernels
     if (c.scan == VG_SCAN_SQ8 && c.allow_nomination && vg::sq8_nomination_applies(idx, c.q, c.nq, c.k)) {
         std::vector<int> failed;
         VG_TRY(vg::sq8_nominated_pass(idx, c.q, c.nq, c.k, c.mk, c.mask_stride, c.oid, c.osc, c.st, failed));
@@ -733,7 +733,7 @@ struct ProbedGemmPath {
                                 !vg::hook(vg::kHookProbeNoGroup) && !vg::hook(vg::kHookProbeNoGemm);
         f32 = c.scan == VG_SCAN_F32 && gemm_shape && (reinterpret_cast<uintptr_t>(idx->d_vectors) & 15) == 0;
         // SQ8 with vg_index_enable_sq8_nomination: the same grouped nomination on the bfloat16 image of the dequantised rows, the
-        // pairs' 64 candidates re-scored from the codes and proven by the verify pair (launch_sq8_verify, k_sq8.hip)
+        // pairs' 64 candidates re-scored from the codes and proven by the verify pair (launch_sq8_verify, k_sq8_scan.hip)
         sq8 = c.scan == VG_SCAN_SQ8 && gemm_shape && c.allow_nomination && idx->sq_nom.rows != nullptr;
         const bool gemm = applies();
         if (gemm) {  // launch bounds from the partition sizes: one query tile per partition + the batch's further tiles on the largest
@@ -835,7 +835,7 @@ struct ProbedGemmPath {
 };
 
 // (c) The scan kernels over the probed ranges: fp32 pair order (grouped by partition when there are enough pairs), PQ table
-// lookups (k_adc.hip), SQ8 (k_sq8.hip).  plan() sizes the slices — c.sub, c.split, c.lists — and adds its arena pieces; scan():
+// lookups (k_adc.hip), SQ8 (k_sq8_scan.hip).  plan() sizes the slices — c.sub, c.split, c.lists — and adds its arena pieces; scan():
 // one page of the paged driver, after the arena's commit().
 struct ProbedScanPath {
     bool grouped_f32 = false, grouped_sq8 = false;

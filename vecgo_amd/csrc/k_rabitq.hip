@@ -5,6 +5,7 @@
 #include "vg_exact.hpp"
 #include "vg_internal.hpp"
 #include "vg_cand_replay.hpp"
+#include "vg_scan_slices.hpp"
 #include "vg_search.hpp"
 
 namespace vg {
@@ -432,17 +433,6 @@ struct RabitqScorer {
     }
 };
 
-static int rq_slices(int64_t nq, int64_t n_tiles, int cus)
-{
-    int64_t s = (4 * static_cast<int64_t>(cus) + nq - 1) / nq;  // ~4 workgroups of 256 threads per CU (swept 2..8: 3-4 best)
-    s = ((s + 7) / 8) * 8;
-    int64_t max_s = (n_tiles / 8) * 8;
-    if (max_s < 8) max_s = 8;
-    if (s > max_s) s = max_s;
-    if (s < 8) s = 8;
-    return static_cast<int>(s);
-}
-
 }  // namespace vg
 
 VG_API int64_t vg_rabitq_code_bytes(int32_t dim) { return static_cast<int64_t>((dim + 63) / 64) * 8 + 4; }
@@ -572,7 +562,7 @@ VG_API int32_t vg_search_rabitq(vg_index *idx, const float *queries, int64_t nq,
         // two or more queries: blocks of kRqMq queries share every code load (rabitq_scan_mq_kernel)
         const bool mq = nq >= 2;
         const int64_t units = mq ? (nq + vg::kRqMq - 1) / vg::kRqMq : nq;  // workgroups per slice
-        const int slices = vg::rq_slices(units, idx->n_tiles, idx->ctx->compute_units);
+        const int slices = vg::scan_slices(units, idx->n_tiles, idx->ctx->compute_units, 4);  // ~4 workgroups of 256 threads per CU (swept 2..8: 3-4 best)
         const size_t mq_lds = static_cast<size_t>(vg::kRqMq) * idx->rq_groups * 16 + vg::kRqWaves * 64 * sizeof(uint64_t) +
                               vg::kRqWaves * sizeof(int) + vg::kRqMq * sizeof(float);
         vg::ArenaCall ar(idx->ctx, st);

@@ -283,7 +283,7 @@ __global__ __launch_bounds__(256) void rb_graph_kernel(const uint32_t *__restric
     }
 }
 
-// tiled [tile][group][lane] 16-byte pieces (k_sq8.hip's layout): piece (row q, group) = old piece (perm[q], group);
+// tiled [tile][group][lane] 16-byte pieces (k_sq8_scan.hip's layout): piece (row q, group) = old piece (perm[q], group);
 // the padding past n stays zero
 __global__ __launch_bounds__(256) void rb_tiles_kernel(const uint4 *__restrict__ src, uint4 *__restrict__ dst, int64_t n, int groups,
                                                        int64_t n_tiles, const uint32_t *__restrict__ perm)

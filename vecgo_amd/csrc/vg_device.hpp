@@ -14,6 +14,7 @@ namespace vg {
 
 constexpr int kWave = 64;
 constexpr uint64_t kKeyMax = 0xFFFFFFFFFFFFFFFFull;
+constexpr float kF32Max = 3.40282346638528859811704183484516925440e+38f;  // math.MaxFloat32: where the Trains' min / max start
 
 // fp32 → uint32 whose unsigned order equals the float order (ascending).
 __device__ __forceinline__ uint32_t f32_ordered(float f)

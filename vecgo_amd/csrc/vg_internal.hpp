@@ -344,6 +344,23 @@ inline void drop_device(T **slot)
     *slot = nullptr;
 }
 
+// whether every pointer is 16-byte aligned: the condition of the codecs' and scans' 16-byte loads and stores
+template <typename... T>
+inline bool aligned16(const T *...p)
+{
+    return ((reinterpret_cast<uintptr_t>(p) | ...) & 15) == 0;
+}
+
+// The grid of a row-walk codec kernel (sq8_encode4_kernel, k_sq8.hip): a thread owns a few consecutive dimensions and walks
+// rpt rows, blocks_y = gridDim.y covers the n rows.
+constexpr int kRowsPerThread = 16;  // at least; more when n / 16 exceeds the grid's y range
+inline int rows_per_thread(int64_t n) { return static_cast<int>(std::max<int64_t>(kRowsPerThread, (n + 65534) / 65535)); }
+struct RowWalk {
+    int rpt;
+    unsigned blocks_y;
+    explicit RowWalk(int64_t n) : rpt(rows_per_thread(n)), blocks_y(static_cast<unsigned>((n + rpt - 1) / rpt)) {}
+};
+
 }  // namespace vg
 
 struct vg_pq {
@@ -393,7 +410,7 @@ struct ProbeGroup {
     uint32_t count;  // 1..kProbeQB
 };
 // The grouped nomination of the probed scans (flat_probe_gemm, k_flat.hip), where the caller re-scores with its own exact
-// distance (SQ8: launch_sq8_verify, k_sq8.hip): per (query, probe) pair its thresholds, how many rows fell below the last one,
+// distance (SQ8: launch_sq8_verify, k_sq8_scan.hip): per (query, probe) pair its thresholds, how many rows fell below the last one,
 // and those rows.
 struct ProbeNominated {
     float *thr;            // [pairs, sel_k]: the pair's threshold is entry sel_k - 1
@@ -470,7 +487,7 @@ struct vg_index {
     uint8_t *d_pq_rows = nullptr;
     vg::NomImage pq_nom;               // vg_index_enable_pq_nomination: the DECODED rows (pq.go:185-229)
     uint8_t *d_rq_rows = nullptr;
-    // SQ8 codes, re-tiled like the PQ codes: [tile][group of 16 dims][lane][16 B]; see k_sq8.hip
+    // SQ8 codes, re-tiled like the PQ codes: [tile][group of 16 dims][lane][16 B]; see k_sq8_scan.hip
     vg_sq8 *sq = nullptr;
     vg::NomImage sq_nom;               // vg_index_enable_sq8_nomination: the dequantised codes
     uint8_t *d_sq_tiles = nullptr;

@@ -1,5 +1,5 @@
 // vg_nominate.hpp — the batched search through a bfloat16 nomination image, shared by the quantizers that have one
-// (vg_index_enable_sq8_nomination, k_sq8.hip; vg_index_enable_pq_nomination, k_adc.hip).
+// (vg_index_enable_sq8_nomination, k_sq8_scan.hip; vg_index_enable_pq_nomination, k_adc.hip).
 // The image holds a quantizer's DECODED rows x^ rounded to bfloat16 with their norms (NomImage, vg_internal.hpp); the fused flat
 // search's nomination runs on it (k_flat.hip flat_nominate_bf16: threshold from a row sample, bf16 MFMA GEMM, the 64 best per
 // query), the verify kernels below re-score the nominees with the reference's own arithmetic on the CODES (the quantizer's Row)
@@ -33,7 +33,7 @@ int32_t flat_probe_gemm(vg_index *idx, const float *pair_queries, int64_t pairs,
                         int ngroups, const int64_t grid[4], int sample_stride, int64_t ns_max, int k, uint32_t *pair_ids,
                         float *pair_scores, int *fail, char *scratch, const uint8_t *mask, const int64_t *mask_off, hipStream_t st,
                         const NomImage &img, ProbeNominated *nominated);
-// k_sq8.hip
+// k_sq8_scan.hip
 int32_t launch_sq8_verify(vg_index *idx, const float *queries, int64_t nq, const ProbeNominated &nom, int k, uint32_t *ids, float *scores,
                           int *fail, hipStream_t st);
 bool sq8_nomination_applies(const vg_index *idx, const float *d_queries, int64_t nq, int k);

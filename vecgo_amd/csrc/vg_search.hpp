@@ -67,6 +67,12 @@ int32_t launch_thr_filter(bool desc, const float *thr, int64_t nq, int max_resul
                           hipStream_t st);
 
 // ---- k_sq8.hip ------------------------------------------------------------------------------------
+// stage 1 of a quantizer's Train (SQ8, INT4) over device rows: per-dimension min / max of min(n, 1024) row chunks,
+// pmin / pmax [chunks][dim] allocated here for the caller's finish kernel
+int32_t launch_dim_minmax(const float *d_rows, int64_t n, int dim, DevTmp<float> &pmin, DevTmp<float> &pmax, int &chunks,
+                          hipStream_t st);
+
+// ---- k_sq8_scan.hip -------------------------------------------------------------------------------
 // the probed partitions' rows from the SQ8 codes: one pass per (query, probe), or per group of pairs of one partition
 int32_t launch_probe_scan_sq8(const vg_index *idx, const float *queries, const uint32_t *probes, const uint32_t *part_off,
                               int64_t nq, int np, int sub, int k, uint64_t *partial, const uint64_t *min_keys,
