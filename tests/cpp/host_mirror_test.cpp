@@ -79,6 +79,14 @@ static_assert(vg::scan_slices(1, 100, 256, 4) == 96, "100 tiles: the multiple of
 static_assert(vg::scan_slices(1, 5, 256, 4) == 8, "fewer tiles than XCDs: still 8");
 static_assert(vg::scan_slices(1, 1954, 256, 1) == 256, "ADC, 1M rows in groups of 8 waves: one workgroup per CU");
 static_assert(vg::scan_slices(1024, 1954, 256, 1) == 8, "ADC, more queries than CUs");
+// the sizes of tests/test_gpu_scan_trips.py on 256 CUs (tests/test_scan_shapes_cpu.py pins tests/scan_shapes.py to the same lines)
+static_assert(vg::scan_slices(1, 4688, 256, 4) == 1024, "300 001 rows: 4688 tiles over 4096 dealt waves, trips 2 / 1 (SQ8 4 waves, RaBitQ)");
+static_assert(vg::scan_slices(1, 586, 256, 1) == 256, "300 001 rows in groups of 8 tiles: 2048 dealt waves, trips 3 / 2 (ADC)");
+static_assert(vg::scan_slices(1, 9376, 256, 4) == 1024, "600 001 rows: 9376 tiles, trips 3 / 2 at 4 waves (RaBitQ ring)");
+static_assert(9376 >= 8 * vg::scan_slices(1, 9376, 256, 4) && 4688 < 8 * vg::scan_slices(1, 4688, 256, 4),
+              "600 001 rows reach the SQ8 8-wave workgroup (trips 2 / 1), 300 001 do not");
+static_assert(vg::scan_slices(65, 313, 256, 4) == 16, "20 000 rows, 1030 RaBitQ queries in blocks of 16");
+static_assert(vg::scan_slices(150, 313, 256, 4) == 8, "20 000 rows, 600 SQ8 queries in groups of 4");
 
 // The (node, level) pairs and the batches of a plan, restated: pair_base is contiguous, every node's pairs are levels
 // 0..min(level, top when its batch began) in order, every batch starts from the entry point and top level that

@@ -88,6 +88,10 @@ def test_rabitq_errors(vg, ctx):
         rq.encode(np.zeros(63, np.float32))
     with pytest.raises(vg.VecgoHipError):  # rabitq.go:123-125
         rq.distance(np.zeros(64, np.float32), np.zeros(11, np.uint8))
+    wide = vg.Index(ctx, 10, 8193)         # 8192 dimensions fill the scan's 64 groups of query bits: one more is refused
+    with pytest.raises(vg.VecgoHipError) as e:
+        wide.set_rabitq_codes(np.zeros((10, o.rabitq_code_bytes(8193)), np.uint8))
+    assert e.value.status == -5
 
 
 @pytest.mark.parametrize("n,dim,nq,k", [(3000, 128, 4, 100), (700, 768, 2, 300), (100, 64, 3, 128)])
