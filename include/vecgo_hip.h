@@ -14,8 +14,44 @@
  *     which (hipPointerGetAttributes).  Host buffers are staged through HBM and
  *     the call returns after the results are back in the caller's buffer (the Go
  *     `//go:noescape` contract: no pointer is retained).  When every buffer of a
- *     call is a device pointer the call only enqueues work on `stream` and
- *     returns; results are ready when the stream reaches that point.
+ *     call is a device pointer, all of the call's work is enqueued on `stream`, in
+ *     order with what the caller enqueued there before; results are ready when the
+ *     stream reaches that point.  Whether the call also returns before that work
+ *     has run depends on the entry point: see "Enqueue-only entry points" below.
+ *   - Alignment: a pointer must be aligned to its element type (4 bytes for float,
+ *     uint32_t and int32_t; 1 for codes and masks) and to nothing more.  ANY
+ *     ELEMENT-ALIGNED DEVICE POINTER IS ACCEPTED AND GIVES THE SAME BITS as a 16-byte
+ *     aligned one — a row range of a larger tensor, a slice of an arena.  Where a
+ *     kernel needs 16-byte aligned operands the library either runs its element-wise
+ *     twin or passes the buffer through a scratch block with device-to-device copies on
+ *     `stream` (nothing waits); a 16-byte aligned device pointer is always used where it
+ *     lies, which is the fast path.  Host pointers are staged whatever their alignment.
+ *   - Enqueue-only entry points.  With every buffer device-resident these return as
+ *     soon as their work is enqueued, without waiting for `stream`: vg_sq8_encode /
+ *     _decode / _l2_distance_batch, vg_int4_encode / _decode / _l2_distance_batch,
+ *     vg_pq_encode / _decode / _asymmetric_distance_batch / _build_distance_table,
+ *     vg_pq_adc_lookup_batch, vg_opq_rotate / _encode / _decode /
+ *     _asymmetric_distance_batch, vg_binary_encode / _decode / _hamming_batch,
+ *     vg_normalize_l2, vg_rabitq_encode / _distance_batch, vg_kmeans_assign,
+ *     vg_search_flat, vg_search_flat_threshold (batches below its nomination),
+ *     vg_search_flat_filtered, vg_search_flat_probed, vg_search_sq8 and vg_search_pq_adc
+ *     (batches that keep the scan), vg_search_rabitq, vg_search_hnsw, vg_search_hnsw_pq,
+ *     vg_search_hnsw_filtered, vg_search_hnsw_predicate, vg_search_vamana (k <= 512),
+ *     vg_search_vamana_filtered, vg_search_vamana_threshold, vg_rerank,
+ *     vg_score_candidates — with stats == NULL where there is one.  (The first call of
+ *     an entry on a stream may allocate its scratch; tests/test_gpu_device_buffers.py
+ *     asserts the list.)
+ *     These WAIT for `stream` inside the call, device buffers or not, because the host
+ *     needs a value the device computes: every *_train (the solves and convergence tests
+ *     are the host's); the builders and maintenance calls (vg_hnsw_build / _insert /
+ *     _compact, vg_vamana_build, vg_vamana_reorder_bfs, vg_flat_build, vg_diskann_build,
+ *     vg_segment_*); vg_index_set_* and vg_index_enable_* (storage is replaced; the
+ *     caller's buffer is free again at return); every getter; vg_search_hnsw_brute (reads
+ *     its filter's population count and redo flags back); vg_search_sq8 and
+ *     vg_search_pq_adc when the bfloat16 nomination takes the batch, and
+ *     vg_search_flat_threshold when its nomination does (the proofs' flags are read
+ *     back); any call that is handed a host buffer, a stats array on the host included.
+ *     Entry points in neither list make no promise either way.
  *   - `stream` is a hipStream_t passed as void*.  NULL = the context's own (non-blocking)
  *     stream — right for host-buffer callers such as cgo.  A caller that produces device
  *     buffers on HIP's legacy default stream (handle 0, e.g. PyTorch's default stream) must
@@ -121,7 +157,9 @@ int32_t vg_ctx_device_info(vg_ctx *ctx, char *arch, int32_t arch_len, int32_t *c
  * every launch of the named hot kernels is bracketed by an event pair.  vg_profile_read
  * synchronises, then returns the number of launches and their summed duration since the last
  * read for `kernel` ("flat_gemm", "pq_adc_scan", "rabitq_scan", "flat_select", "topk_merge",
- * "hnsw_search", "vamana_search"), and clears those records. */
+ * "hnsw_search", "vamana_search"), and clears those records.  The name "staged_device_buffers" is a counter, not a
+ * kernel: how many misaligned DEVICE buffers the process passed through a scratch block since the last read ("Alignment"
+ * above), profiling enabled or not; total_ms is 0. */
 int32_t vg_profile_enable(vg_ctx *ctx, int32_t on);
 int32_t vg_profile_read(vg_ctx *ctx, const char *kernel, int64_t *launches, double *total_ms);
 

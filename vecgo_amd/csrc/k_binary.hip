@@ -226,18 +226,22 @@ VG_API int32_t vg_normalize_l2(vg_ctx *ctx, float *vectors, int64_t n, int32_t d
     }
     VG_CHECK(vectors, VG_ERR_INVALID_ARG, "vg_normalize_l2: NULL vectors");
     const size_t count = static_cast<size_t>(n) * dim;
+    // in place: a host buffer, or a device view that is not 16-byte aligned (the kernel reads its rows as float4), goes
+    // through a scratch block and back on the stream; only the host waits for it
     float *dv = vectors;
     vg::DevTmp<float> staged;
     const bool host = !vg::is_device_ptr(vectors);
-    if (host) {
+    const bool stage = host || !vg::aligned16(vectors);
+    if (stage) {
+        if (!host) vg::note_staged_device_buffer();
         VG_TRY(staged.init(count, st));
-        VG_HIP(hipMemcpyAsync(staged.ptr, vectors, count * 4, hipMemcpyHostToDevice, st));
+        VG_HIP(hipMemcpyAsync(staged.ptr, vectors, count * 4, host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, st));
         dv = staged.ptr;
     }
     vg::DevOut<uint8_t> o;
     VG_TRY(o.init(ok, ok ? static_cast<size_t>(n) : 0, st));
     VG_LAUNCH(vg::normalize_l2_kernel, dim3(static_cast<unsigned>((n + 15) / 16)), dim3(256), 0, st, dv, n, dim, o.ptr);
-    if (host) VG_HIP(hipMemcpyAsync(vectors, dv, count * 4, hipMemcpyDeviceToHost, st));
+    if (stage) VG_HIP(hipMemcpyAsync(vectors, dv, count * 4, host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, st));
     VG_TRY(o.finish());
     if (host) VG_HIP(hipStreamSynchronize(st));
     return VG_OK;

@@ -533,7 +533,7 @@ static int32_t brute_nan_replay(vg_index *idx, const float *d_queries, int64_t n
 // the distance matrix of a chunk of queries + the reference's heap, replayed per query: what vg_search_hnsw_brute answers with
 // when its fast path does not apply
 static int32_t brute_impl(vg_index *idx, const float *queries, int64_t nq, int32_t k, int32_t mode, const uint8_t *mask,
-                          int64_t mask_stride, uint32_t *ids, float *scores, void *stream)
+                          int64_t mask_stride, uint32_t *ids, float *scores, void *stream, vg::Align align = vg::kStage16)
 {
     VG_CHECK(idx, VG_ERR_INVALID_ARG, "vg_search_hnsw_brute: NULL index");
     VG_CHECK(nq >= 0 && k >= 0, VG_ERR_INVALID_ARG, "vg_search_hnsw_brute: negative nq or k");
@@ -546,7 +546,7 @@ static int32_t brute_impl(vg_index *idx, const float *queries, int64_t nq, int32
     VG_CHECK_MASK_STRIDE("vg_search_hnsw_brute", mask, mask_stride, idx->n);
     vg::SearchIO io;
     VG_TRY(io.init(idx->ctx, stream, queries, static_cast<size_t>(nq) * idx->dim, ids, scores, static_cast<size_t>(nq) * k, mask,
-                   vg::mask_span(mask, mask_stride, nq, idx->n)));
+                   vg::mask_span(mask, mask_stride, nq, idx->n), align));
     const hipStream_t st = io.st;
     const float *q = io.q.ptr;
     const uint8_t *mk = io.mk.ptr;
@@ -692,8 +692,9 @@ VG_API int32_t vg_search_hnsw_brute(vg_index *idx, const float *queries, int64_t
         return brute_impl(idx, q, nq, k, mode, mk, mask_stride, ids, scores, stream);
     for (int64_t i = 0; i < nq; i++)  // ties / NaN: the heap's history decides — replayed one query at a time (rare)
         if (h[static_cast<size_t>(i)])
+            // one query's slice of this call's own operands, where it lies (an aligned caller's replay copies nothing)
             VG_TRY(brute_impl(idx, q + i * idx->dim, 1, k, mode, mk ? mk + i * mask_stride : nullptr, 0, oid + i * k,
-                              osc + i * k, st));
+                              osc + i * k, st, vg::kAnyAlign));
     VG_TRY(vg::brute_nan_replay(idx, q, nq, k, mode, mk, mask_stride, oid, osc, st));  // queries whose distances may hold a NaN
     return io.finish();
 }

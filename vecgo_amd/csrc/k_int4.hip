@@ -685,8 +685,8 @@ VG_API int32_t vg_int4_encode(vg_int4 *iq, const float *vectors, int64_t n, uint
     const int64_t cs = vg_int4_code_bytes(iq->dim);
     vg::DevIn<float> v;
     vg::DevOut<uint8_t> c;
-    VG_TRY(v.init(vectors, static_cast<size_t>(n) * iq->dim, st));
-    VG_TRY(c.init(codes, static_cast<size_t>(n * cs), st));
+    VG_TRY(v.init(vectors, static_cast<size_t>(n) * iq->dim, st, vg::kAnyAlign));
+    VG_TRY(c.init(codes, static_cast<size_t>(n * cs), st, vg::kAnyAlign));
     const vg::RowWalk walk(n);
     if (iq->dim % 8 == 0 && vg::aligned16(v.ptr, c.ptr))
         VG_LAUNCH(vg::int4_encode8_kernel, dim3((iq->dim / 8 + 255) / 256, walk.blocks_y),
@@ -710,8 +710,8 @@ VG_API int32_t vg_int4_decode(vg_int4 *iq, const uint8_t *codes, int64_t n, floa
     const int64_t cs = vg_int4_code_bytes(iq->dim);
     vg::DevIn<uint8_t> c;
     vg::DevOut<float> o;
-    VG_TRY(c.init(codes, static_cast<size_t>(n * cs), st));
-    VG_TRY(o.init(out, static_cast<size_t>(n) * iq->dim, st));
+    VG_TRY(c.init(codes, static_cast<size_t>(n * cs), st, vg::kAnyAlign));
+    VG_TRY(o.init(out, static_cast<size_t>(n) * iq->dim, st, vg::kAnyAlign));
     const vg::RowWalk walk(n);
     if (iq->dim % 8 == 0 && vg::aligned16(c.ptr, o.ptr))
         VG_LAUNCH(vg::int4_decode8_kernel, dim3((iq->dim / 8 + 255) / 256, walk.blocks_y),
@@ -740,7 +740,7 @@ VG_API int32_t vg_int4_l2_distance_batch(vg_int4 *iq, const float *query, const 
     vg::DevIn<uint8_t> c;
     vg::DevOut<float> o;
     VG_TRY(q.init(query, static_cast<size_t>(iq->dim), st));
-    VG_TRY(c.init(codes, static_cast<size_t>(n * cs), st));
+    VG_TRY(c.init(codes, static_cast<size_t>(n * cs), st, vg::kAnyAlign));
     VG_TRY(o.init(out, static_cast<size_t>(n), st));
     const bool scan = iq->dim % 64 == 0 && vg::aligned16(c.ptr);
     const unsigned scan_blocks = static_cast<unsigned>(((n + 63) / 64 + vg::kI4Waves - 1) / vg::kI4Waves);

@@ -346,8 +346,8 @@ VG_API int32_t vg_pq_adc_lookup_batch(vg_ctx *ctx, const float *table, const uin
     vg::DevIn<float> t;
     vg::DevIn<uint8_t> c;
     vg::DevOut<float> o;
-    VG_TRY(t.init(table, static_cast<size_t>(m) * 256, st));
-    VG_TRY(c.init(codes, static_cast<size_t>(n) * m, st));
+    VG_TRY(t.init(table, static_cast<size_t>(m) * 256, st, vg::kAnyAlign));
+    VG_TRY(c.init(codes, static_cast<size_t>(n) * m, st, vg::kAnyAlign));
     VG_TRY(o.init(out, static_cast<size_t>(n), st));
     // table in LDS + rows turned through LDS when both fit (m % 16 == 0)
     const int stride = static_cast<int>(16 * ((m >> 4) | 1));

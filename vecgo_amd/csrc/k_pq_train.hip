@@ -1525,7 +1525,7 @@ VG_API int32_t vg_pq_encode(vg_pq *pq, const float *vectors, int64_t n, uint8_t 
     hipStream_t st = vg::pick_stream(pq->ctx, stream);
     vg::DevIn<float> v;
     vg::DevOut<uint8_t> c;
-    VG_TRY(v.init(vectors, static_cast<size_t>(n) * pq->dim, st));
+    VG_TRY(v.init(vectors, static_cast<size_t>(n) * pq->dim, st, vg::kAnyAlign));
     VG_TRY(c.init(codes, static_cast<size_t>(n) * pq->m, st));
     const size_t lds = static_cast<size_t>(pq->k) * pq->subdim * sizeof(float);
     VG_CHECK(lds <= 152 * 1024, VG_ERR_UNSUPPORTED, "vg_pq_encode: codebook of one sub-quantizer exceeds 152 KiB");
@@ -1587,8 +1587,8 @@ VG_API int32_t vg_pq_decode(vg_pq *pq, const uint8_t *codes, int64_t n, float *o
     hipStream_t st = vg::pick_stream(pq->ctx, stream);
     vg::DevIn<uint8_t> c;
     vg::DevOut<float> o;
-    VG_TRY(c.init(codes, static_cast<size_t>(n) * pq->m, st));
-    VG_TRY(o.init(out, static_cast<size_t>(n) * pq->dim, st));
+    VG_TRY(c.init(codes, static_cast<size_t>(n) * pq->m, st, vg::kAnyAlign));
+    VG_TRY(o.init(out, static_cast<size_t>(n) * pq->dim, st, vg::kAnyAlign));
     const int64_t total = n * pq->dim;
     if (pq->subdim == 8 && pq->k == 256 && (reinterpret_cast<uintptr_t>(pq->d_codebooks) & 7) == 0 &&
         (reinterpret_cast<uintptr_t>(o.ptr) & 15) == 0) {
@@ -1619,7 +1619,7 @@ VG_API int32_t vg_pq_asymmetric_distance_batch(vg_pq *pq, const float *query, co
     vg::DevIn<uint8_t> c;
     vg::DevOut<float> o;
     VG_TRY(q.init(query, static_cast<size_t>(pq->dim), st));
-    VG_TRY(c.init(codes, static_cast<size_t>(n) * pq->m, st));
+    VG_TRY(c.init(codes, static_cast<size_t>(n) * pq->m, st, vg::kAnyAlign));
     VG_TRY(o.init(out, static_cast<size_t>(n), st));
     if (pq->subdim == 8 && pq->k == 256 && (reinterpret_cast<uintptr_t>(pq->d_codebooks) & 7) == 0 &&
         (reinterpret_cast<uintptr_t>(c.ptr) & 15) == 0)

@@ -472,7 +472,7 @@ VG_API int32_t vg_rabitq_distance_batch(vg_ctx *ctx, int32_t dim, const float *q
     vg::DevOut<float> o;
     vg::DevTmp<uint8_t> qcode;
     VG_TRY(q.init(query, static_cast<size_t>(dim), st));
-    VG_TRY(c.init(codes, static_cast<size_t>(n) * cb, st));
+    VG_TRY(c.init(codes, static_cast<size_t>(n) * cb, st, vg::kAnyAlign));
     VG_TRY(o.init(out, static_cast<size_t>(n), st));
     VG_TRY(qcode.init(static_cast<size_t>(cb), st));
     VG_LAUNCH(vg::rabitq_encode_kernel, dim3(1), dim3(256), 0, st, q.ptr, int64_t(1), dim, qcode.ptr);
@@ -493,8 +493,8 @@ VG_API int32_t vg_hamming_batch(vg_ctx *ctx, const uint8_t *a, const uint8_t *co
     hipStream_t st = vg::pick_stream(ctx, stream);
     vg::DevIn<uint8_t> da, dc;
     vg::DevOut<int32_t> o;
-    VG_TRY(da.init(a, static_cast<size_t>(nbytes), st));
-    VG_TRY(dc.init(codes, static_cast<size_t>(n) * nbytes, st));
+    VG_TRY(da.init(a, static_cast<size_t>(nbytes), st, vg::kAnyAlign));
+    VG_TRY(dc.init(codes, static_cast<size_t>(n) * nbytes, st, vg::kAnyAlign));
     VG_TRY(o.init(out, static_cast<size_t>(n), st));
     VG_LAUNCH(vg::hamming_batch_kernel, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, st,
                        da.ptr, dc.ptr, nbytes, n, o.ptr);

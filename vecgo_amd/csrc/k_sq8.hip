@@ -369,8 +369,8 @@ VG_API int32_t vg_sq8_encode(vg_sq8 *sq, const float *vectors, int64_t n, uint8_
     const int64_t total = n * sq->dim;
     vg::DevIn<float> v;
     vg::DevOut<uint8_t> c;
-    VG_TRY(v.init(vectors, static_cast<size_t>(total), st));
-    VG_TRY(c.init(codes, static_cast<size_t>(total), st));
+    VG_TRY(v.init(vectors, static_cast<size_t>(total), st, vg::kAnyAlign));
+    VG_TRY(c.init(codes, static_cast<size_t>(total), st, vg::kAnyAlign));
     const vg::RowWalk walk(n);
     if (sq->dim % 4 == 0 && vg::aligned16(v.ptr, c.ptr))
         VG_LAUNCH(vg::sq8_encode4_kernel, dim3((sq->dim / 4 + 255) / 256, walk.blocks_y),
@@ -394,8 +394,8 @@ VG_API int32_t vg_sq8_decode(vg_sq8 *sq, const uint8_t *codes, int64_t n, float 
     const int64_t total = n * sq->dim;
     vg::DevIn<uint8_t> c;
     vg::DevOut<float> o;
-    VG_TRY(c.init(codes, static_cast<size_t>(total), st));
-    VG_TRY(o.init(out, static_cast<size_t>(total), st));
+    VG_TRY(c.init(codes, static_cast<size_t>(total), st, vg::kAnyAlign));
+    VG_TRY(o.init(out, static_cast<size_t>(total), st, vg::kAnyAlign));
     const vg::RowWalk walk(n);
     if (sq->dim % 4 == 0 && vg::aligned16(c.ptr, o.ptr))
         VG_LAUNCH(vg::sq8_decode4_kernel, dim3((sq->dim / 4 + 255) / 256, walk.blocks_y),
@@ -421,7 +421,7 @@ VG_API int32_t vg_sq8_l2_distance_batch(vg_sq8 *sq, const float *query, const ui
     vg::DevIn<uint8_t> c;
     vg::DevOut<float> o;
     VG_TRY(q.init(query, static_cast<size_t>(sq->dim), st));
-    VG_TRY(c.init(codes, static_cast<size_t>(n) * sq->dim, st));
+    VG_TRY(c.init(codes, static_cast<size_t>(n) * sq->dim, st, vg::kAnyAlign));
     VG_TRY(o.init(out, static_cast<size_t>(n), st));
     if (sq->dim % 128 == 0 && vg::aligned16(c.ptr))
         VG_LAUNCH(vg::sq8_l2_batch_turn_kernel,

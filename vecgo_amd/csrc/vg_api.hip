@@ -28,6 +28,7 @@ bool is_device_ptr(const void *p)
 }
 
 namespace {
+std::atomic<int64_t> g_staged_device_buffers{0};
 struct ScratchBlock {
     void *p;
     size_t cap;
@@ -49,6 +50,9 @@ size_t scratch_round(size_t bytes)
     return (bytes + bytes / 8 + mib - 1) / mib * mib;  // 12.5 % slack, whole MiB
 }
 }  // namespace
+
+void note_staged_device_buffer() { g_staged_device_buffers.fetch_add(1, std::memory_order_relaxed); }
+int64_t take_staged_device_buffers() { return g_staged_device_buffers.exchange(0, std::memory_order_relaxed); }
 
 int32_t scratch_alloc(void **out, size_t bytes, hipStream_t s)
 {
@@ -226,6 +230,11 @@ VG_API int32_t vg_profile_enable(vg_ctx *ctx, int32_t on)
 VG_API int32_t vg_profile_read(vg_ctx *ctx, const char *kernel, int64_t *launches, double *total_ms)
 {
     VG_CHECK(ctx && kernel && launches && total_ms, VG_ERR_INVALID_ARG, "vg_profile_read: NULL argument");
+    if (strcmp(kernel, "staged_device_buffers") == 0) {  // a counter, not a kernel (see the header)
+        *launches = vg::take_staged_device_buffers();
+        *total_ms = 0.0;
+        return VG_OK;
+    }
     VG_HIP(hipSetDevice(ctx->device));
     std::lock_guard<std::mutex> g(ctx->prof_mu);
     int64_t n = 0;

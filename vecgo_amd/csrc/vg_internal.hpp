@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
@@ -180,26 +181,45 @@ inline hipStream_t pick_stream(vg_ctx *ctx, void *stream)
     return stream ? reinterpret_cast<hipStream_t>(stream) : ctx->stream;
 }
 
+// whether every pointer is 16-byte aligned: the condition of the codecs' and scans' 16-byte loads and stores
+template <typename... T>
+inline bool aligned16(const T *...p)
+{
+    return ((reinterpret_cast<uintptr_t>(p) | ...) & 15) == 0;
+}
+
+// What a call site does with a DEVICE pointer of the caller's that is element-aligned but not 16-byte aligned (a view into
+// a larger buffer).  Kernels read and write their operands through wider types (float4, uint4, uint64_t, direct-to-LDS
+// loads), so the default hands them a 16-byte aligned copy: the buffer goes through a scratch block by a device-to-device
+// copy on the call's stream, outputs come back the same way, and nothing waits.  A call site that tests the pointer itself
+// (aligned16) and has a kernel of plain element accesses for the other case says kAnyAlign and keeps the pointer.  A
+// 16-byte aligned device pointer is always used where it lies.
+enum Align { kStage16, kAnyAlign };
+// counts the device buffers staged so: read and cleared by vg_profile_read("staged_device_buffers")
+void note_staged_device_buffer();
+
 // Read-only input that may live on the host: staged into HBM for the call.
 template <typename T>
 struct DevIn {
     const T *ptr = nullptr;
     T *owned = nullptr;
     hipStream_t st = nullptr;
-    int32_t init(const T *p, size_t count, hipStream_t s)
+    int32_t init(const T *p, size_t count, hipStream_t s, Align align = kStage16)
     {
         st = s;
         if (count == 0 || p == nullptr) {
             ptr = p;
             return VG_OK;
         }
-        if (is_device_ptr(p)) {
+        const bool dev = is_device_ptr(p);
+        if (dev && (align == kAnyAlign || aligned16(p))) {
             ptr = p;
             return VG_OK;
         }
-        // Host buffers are the slow path (cgo, tests): staged through a cached HBM block
+        // Host buffers are the slow path (cgo, tests): staged through a cached HBM block; so is a misaligned device view
+        if (dev) note_staged_device_buffer();
         VG_TRY(scratch_alloc(reinterpret_cast<void **>(&owned), count * sizeof(T), s));
-        VG_HIP(hipMemcpyAsync(owned, p, count * sizeof(T), hipMemcpyHostToDevice, s));
+        VG_HIP(hipMemcpyAsync(owned, p, count * sizeof(T), dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
         ptr = owned;
         return VG_OK;
     }
@@ -215,9 +235,10 @@ struct DevOut {
     T *ptr = nullptr;
     T *owned = nullptr;
     T *host = nullptr;
+    T *dev = nullptr;  // a misaligned device buffer of the caller's that `owned` stands in for
     size_t count = 0;
     hipStream_t st = nullptr;
-    int32_t init(T *p, size_t n, hipStream_t s)
+    int32_t init(T *p, size_t n, hipStream_t s, Align align = kStage16)
     {
         st = s;
         count = n;
@@ -225,11 +246,13 @@ struct DevOut {
             ptr = p;
             return VG_OK;
         }
-        if (is_device_ptr(p)) {
+        const bool on_device = is_device_ptr(p);
+        if (on_device && (align == kAnyAlign || aligned16(p))) {
             ptr = p;
             return VG_OK;
         }
-        host = p;
+        (on_device ? dev : host) = p;
+        if (on_device) note_staged_device_buffer();
         VG_TRY(scratch_alloc(reinterpret_cast<void **>(&owned), n * sizeof(T), s));
         ptr = owned;
         return VG_OK;
@@ -240,6 +263,7 @@ struct DevOut {
             VG_HIP(hipMemcpyAsync(host, owned, count * sizeof(T), hipMemcpyDeviceToHost, st));
             VG_HIP(hipStreamSynchronize(st));
         }
+        if (dev && count) VG_HIP(hipMemcpyAsync(dev, owned, count * sizeof(T), hipMemcpyDeviceToDevice, st));  // stream-ordered: no wait
         return VG_OK;
     }
     ~DevOut()
@@ -342,13 +366,6 @@ inline void drop_device(T **slot)
 {
     if (*slot) (void)hipFree(*slot);
     *slot = nullptr;
-}
-
-// whether every pointer is 16-byte aligned: the condition of the codecs' and scans' 16-byte loads and stores
-template <typename... T>
-inline bool aligned16(const T *...p)
-{
-    return ((reinterpret_cast<uintptr_t>(p) | ...) & 15) == 0;
 }
 
 // The grid of a row-walk codec kernel (sq8_encode4_kernel, k_sq8.hip): a thread owns a few consecutive dimensions and walks

@@ -106,14 +106,15 @@ struct SearchIO {
     DevOut<uint32_t> oid;
     DevOut<float> osc;
     int32_t init(vg_ctx *ctx, void *stream, const float *queries, size_t query_floats, uint32_t *ids, float *scores, size_t results,
-                 const uint8_t *mask = nullptr, size_t mask_bytes = 0)
+                 const uint8_t *mask = nullptr, size_t mask_bytes = 0, Align align = kStage16)
     {
+        // align: kAnyAlign only for the library's own sub-ranges of operands an outer SearchIO has already taken
         VG_HIP(hipSetDevice(ctx->device));
         st = pick_stream(ctx, stream);
-        VG_TRY(q.init(queries, query_floats, st));
-        VG_TRY(oid.init(ids, results, st));
-        VG_TRY(osc.init(scores, results, st));
-        return mk.init(mask, mask_bytes, st);
+        VG_TRY(q.init(queries, query_floats, st, align));
+        VG_TRY(oid.init(ids, results, st, align));
+        VG_TRY(osc.init(scores, results, st, align));
+        return mk.init(mask, mask_bytes, st, align);
     }
     int32_t finish()
     {
