@@ -382,7 +382,7 @@ func (r *Resident) SearchFlat(queries []float32, nq, k int) ([]uint32, []float32
 // SearchThreshold: the flat-segment leg of Engine.SearchThreshold (engine/engine.go:1485-1531): Search(q, maxResults)
 // (flat/segment.go:447-721), then the rows with Score <= thresholds[q] (L2) / >= thresholds[q] (Dot, Cosine), best first.
 // Query q's rows are ids/scores[q*maxResults : q*maxResults+counts[q]].  thresholds: one per query.  maxResults <= 16384;
-// a segment with more than one IVF partition is refused (the reference would probe only some of them).
+// a segment with more than one IVF partition is refused (the reference would probe only some of them): SearchProbedThreshold.
 func (r *Resident) SearchThreshold(queries []float32, nq int, thresholds []float32, maxResults int) ([]uint32, []float32, []int32, error) {
 	if len(thresholds) < nq {
 		return nil, nil, nil, fmt.Errorf("SearchThreshold: %d thresholds for %d queries", len(thresholds), nq)
@@ -393,6 +393,75 @@ func (r *Resident) SearchThreshold(queries []float32, nq int, thresholds []float
 	ids, sc := r.out(nq, maxResults)
 	counts := make([]int32, nq)
 	st := C.vg_search_flat_threshold(r.h, fp(queries), C.int64_t(nq), fp(thresholds), C.int32_t(maxResults), nil, 0, up(ids), fp(sc), ip(counts), nil)
+	return ids, sc, counts, hipctx.Err(int32(st))
+}
+
+// thresholdOperands: what the probed threshold searches check and allocate: one threshold per query, a mask long enough for
+// its stride (nil = no filter), the result arrays.  ok == false: nothing to do (nq or maxResults is 0).
+func (r *Resident) thresholdOperands(name string, nq int, thresholds []float32, maxResults int, mask []byte, maskStride int) (ids []uint32, sc []float32, counts []int32, ok bool, err error) {
+	if len(thresholds) < nq {
+		return nil, nil, nil, false, fmt.Errorf("%s: %d thresholds for %d queries", name, len(thresholds), nq)
+	}
+	counts = make([]int32, nq)
+	if nq == 0 || maxResults == 0 {
+		return nil, nil, counts, false, nil
+	}
+	if mask != nil {
+		need := (r.rows + 7) / 8
+		if maskStride != 0 {
+			if maskStride < need {
+				return nil, nil, nil, false, fmt.Errorf("%s: maskStride %d is shorter than a mask (%d bytes)", name, maskStride, need)
+			}
+			need += (nq - 1) * maskStride
+		}
+		if len(mask) < need {
+			return nil, nil, nil, false, fmt.Errorf("%s: mask holds %d bytes, %d needed", name, len(mask), need)
+		}
+	}
+	ids, sc = r.out(nq, maxResults)
+	return ids, sc, counts, true, nil
+}
+
+// SearchProbedThreshold: Engine.SearchThreshold (engine/engine.go:1485-1531) over a flat segment with codes and / or IVF
+// partitions (flat/segment.go:447-780): the best maxResults rows of the nprobes closest partitions (or of the whole segment)
+// by the score of `scan`, then — rerank — their exact scores, then the rows with Score <= thresholds[q] (L2) / >=
+// thresholds[q] (Dot, Cosine), best first.  rerank false: the threshold is compared with the scan score (the segment-level
+// answer).  Query q's rows are ids/scores[q*maxResults : q*maxResults+counts[q]].  mask nil = no filter, else as for
+// SearchFiltered.  maxResults <= 16384, nprobes <= 64.
+func (r *Resident) SearchProbedThreshold(queries []float32, nq int, thresholds []float32, maxResults, nprobes int, scan int32, rerank bool, mask []byte, maskStride int) ([]uint32, []float32, []int32, error) {
+	ids, sc, counts, ok, err := r.thresholdOperands("SearchProbedThreshold", nq, thresholds, maxResults, mask, maskStride)
+	if !ok {
+		return nil, nil, counts, err
+	}
+	var mp *C.uint8_t
+	if mask != nil {
+		mp = bp(mask)
+	}
+	rr := 0
+	if rerank {
+		rr = 1
+	}
+	st := C.vg_search_flat_probed_threshold(r.h, fp(queries), C.int64_t(nq), fp(thresholds), C.int32_t(maxResults), C.int32_t(nprobes), C.int32_t(scan), C.int32_t(rr), mp, C.int64_t(maskStride), up(ids), fp(sc), ip(counts), nil)
+	return ids, sc, counts, hipctx.Err(int32(st))
+}
+
+// SearchSegmentThreshold: Engine.SearchThreshold for a segment opened from its file, by what the file holds: a flat segment
+// is SearchProbedThreshold with the segment's scan, a DiskANN segment SearchVamanaThreshold with its kind (nprobes and rerank
+// are unused there).
+func (r *Resident) SearchSegmentThreshold(queries []float32, nq int, thresholds []float32, maxResults, nprobes int, rerank bool, mask []byte, maskStride int) ([]uint32, []float32, []int32, error) {
+	ids, sc, counts, ok, err := r.thresholdOperands("SearchSegmentThreshold", nq, thresholds, maxResults, mask, maskStride)
+	if !ok {
+		return nil, nil, counts, err
+	}
+	var mp *C.uint8_t
+	if mask != nil {
+		mp = bp(mask)
+	}
+	rr := 0
+	if rerank {
+		rr = 1
+	}
+	st := C.vg_segment_search_threshold(r.seg, fp(queries), C.int64_t(nq), fp(thresholds), C.int32_t(maxResults), C.int32_t(nprobes), C.int32_t(rr), mp, C.int64_t(maskStride), up(ids), fp(sc), ip(counts), nil)
 	return ids, sc, counts, hipctx.Err(int32(st))
 }
 

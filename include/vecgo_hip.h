@@ -34,7 +34,7 @@
  *     _asymmetric_distance_batch, vg_binary_encode / _decode / _hamming_batch,
  *     vg_normalize_l2, vg_rabitq_encode / _distance_batch, vg_kmeans_assign,
  *     vg_search_flat, vg_search_flat_threshold (batches below its nomination),
- *     vg_search_flat_filtered, vg_search_flat_probed, vg_search_sq8 and vg_search_pq_adc
+ *     vg_search_flat_probed_threshold, vg_search_flat_filtered, vg_search_flat_probed, vg_search_sq8 and vg_search_pq_adc
  *     (batches that keep the scan), vg_search_rabitq, vg_search_hnsw, vg_search_hnsw_pq,
  *     vg_search_hnsw_filtered, vg_search_hnsw_predicate, vg_search_vamana (k <= 512),
  *     vg_search_vamana_filtered, vg_search_vamana_threshold, vg_rerank,
@@ -101,7 +101,9 @@ extern "C" {
  *  vg_vamana_reorder_bfs the same way; the next bump covers them.  Likewise the flat writer: vg_flat_build,
  *  vg_segment_flat_image_size, vg_segment_write_flat and vg_crc32c_device — bindings find them by symbol lookup.
  *  Likewise vg_hnsw_compact (with its caller-allocated vg_hnsw_compact_stats).  Likewise the DiskANN writer:
- *  vg_diskann_build, vg_segment_diskann_image_size and vg_segment_write_diskann, found by symbol lookup. */
+ *  vg_diskann_build, vg_segment_diskann_image_size and vg_segment_write_diskann, found by symbol lookup.  Likewise the
+ *  threshold search over coded / partitioned flat segments: vg_search_flat_probed_threshold and
+ *  vg_segment_search_threshold, found by symbol lookup. */
 #define VG_ABI_MINOR 13
 #define VG_INVALID_ID 0xFFFFFFFFu
 #define VG_STREAM_LEGACY ((void *)1) /* == hipStreamLegacy */
@@ -262,7 +264,7 @@ int32_t vg_hamming_batch(vg_ctx *ctx, const uint8_t *a, const uint8_t *codes, in
 
 /* Test hooks (process-wide): force an alternative path so that tests can compare the paths bit for bit.
  * Names: VG_FLAT_NO_SMALL_TILE, VG_FLAT_UNFUSED, VG_FLAT_NO_SCAN, VG_FLAT_FORCE_EXACT, VG_FLAT_NO_DMA,
- * VG_FLAT_DEBUG, VG_PROBE_NO_GROUP, VG_ADC_BIGK_EXHAUSTIVE, VG_BUILD_DEBUG, VG_FLAT_RESCORE_SAMPLE (the full list: Hook in
+ * VG_FLAT_DEBUG, VG_PROBE_NO_GROUP, VG_ADC_BIGK_EXHAUSTIVE, VG_BUILD_DEBUG, VG_FLAT_RESCORE_SAMPLE, VG_PTHR_FORCE_HIST (the full list: Hook in
  * csrc/vg_internal.hpp).  The environment variable of the same
  * name ("1") gives the initial value, read once; the search entry points never call getenv. */
 int32_t vg_debug_set_hook(const char *name, int32_t on);
@@ -719,6 +721,41 @@ int32_t vg_search_flat_filtered(vg_index *idx, const float *queries, int64_t nq,
                                 int32_t scan, const uint8_t *mask, int64_t mask_stride, uint32_t *ids, float *scores,
                                 void *stream);
 
+/* Engine.SearchThreshold (engine/engine.go:1485-1531) over a flat segment that carries codes and / or IVF partitions — what
+ * vg_search_flat_threshold refuses.  Per query three steps:
+ *   1. flat.Segment.Search(q, k = max_results, nprobes, filter) (flat/segment.go:447-751) with the scan `scan` (VG_SCAN_F32 fp32
+ *      rows, VG_SCAN_SQ8 L2Distance / DotProduct of the codes by metric, VG_SCAN_PQ table lookups), over the whole segment or —
+ *      more than one partition — the nprobes closest ones: the best max_results rows by (scan score, row id).  scan, nprobes,
+ *      mask / mask_stride mean what they mean for vg_search_flat_filtered (nprobes <= 0 is 1, ignored with at most one
+ *      partition, <= 64; NULL mask = none); probe choice and its tie rules are vg_search_flat_probed's; scan scores are bit for
+ *      bit that entry's for the same row.
+ *   2. rerank != 0: Segment.Rerank (flat/segment.go:754-780, engine/search.go:914-980) — every candidate's exact
+ *      distance.SquaredL2 / distance.Dot from the index's fp32 rows, all of them ordered by (exact score, row id).  (With
+ *      VG_SCAN_F32 the step changes nothing and is skipped.)
+ *   3. the engine's filter (:1518-1529): Score <= thresholds[q] (L2) / Score >= thresholds[q] (Dot, Cosine), by the index's
+ *      metric whatever the scan (a Dot / Cosine PQ scan keeps and compares its LARGEST table sums, as the reference's heap
+ *      does).  The boundary is kept; NaN on either side keeps nothing.
+ * rerank == 0 is the segment-level answer: the rows of step 1 whose SCAN score is within the threshold, scores the scan's.
+ * rerank != 0 is the engine's: the threshold is compared with the exact score, scores are exact; needs fp32 rows on the index.
+ * Output as vg_search_flat_threshold: ids/scores[nq*max_results], counts[nq], best first, the slots after counts[q] hold
+ * VG_INVALID_ID and +Inf (L2) / -Inf (Dot, Cosine); host or device pointers; nq == 0 or max_results == 0 writes nothing.
+ * Without rerank (and with fp32 rows either way) one scan appends the rows within the threshold to a list per query and the best
+ * max_results of it are selected; with rerank over codes two scans find the best max_results rows by code score exactly (a
+ * 65536-bin histogram of the keys' top 16 bits per query, then every key at or below the bin where the count reaches
+ * max_results), which are re-scored, filtered and ordered.  The whole segment is read once per 8 queries (PQ: per query), a
+ * probed partition once per (query, probe) pair.
+ * NaN scores: a query whose scan scores may hold a NaN or an Inf has step 1 answered by the reference's heap replayed with
+ * k = max_results over the same ranges (see "NaN scores"); steps 2 and 3 follow the replay.  Not restated, as for vg_rerank:
+ * NaN EXACT scores inside step 2's heap are dropped by the filter and the rest are ordered by key.
+ * Refusals, each decided before any work: max_results > 16384 VG_ERR_UNSUPPORTED (the number in the message); Hamming
+ * VG_ERR_UNSUPPORTED; nprobes > 64 VG_ERR_UNSUPPORTED; a scan kind the index has no data for, or rerank != 0 without fp32
+ * rows, VG_ERR_NOT_READY; a PQ of other than 256 centroids VG_ERR_UNSUPPORTED, as vg_search_flat_probed(VG_SCAN_PQ); a PQ
+ * table that does not fit one LDS image (m > 96) VG_ERR_UNSUPPORTED.  (Present when the symbol is: see VG_ABI_MINOR.) */
+int32_t vg_search_flat_probed_threshold(vg_index *idx, const float *queries, int64_t nq, const float *thresholds,
+                                        int32_t max_results, int32_t nprobes, int32_t scan /* VG_SCAN_* */, int32_t rerank,
+                                        const uint8_t *mask, int64_t mask_stride,
+                                        uint32_t *ids, float *scores, int32_t *counts, void *stream);
+
 /* flat.Writer.Flush's partitioning and quantization (flat/writer.go:99-223) on the resident index, over its fp32 rows where
  * they lie.  (Present when the symbol is: see VG_ABI_MINOR.)
  * Partitioning (:105-169), skipped when num_partitions <= 1 or rows < num_partitions (the index then has 0 partitions and
@@ -779,6 +816,13 @@ int32_t vg_segment_search(vg_segment *seg, const float *queries, int64_t nq, int
  * mask + q * mask_stride (0 = one for the batch); NULL = vg_segment_search.  (VG_ABI_MINOR 8.) */
 int32_t vg_segment_search_filtered(vg_segment *seg, const float *queries, int64_t nq, int32_t k, int32_t nprobes,
                                    const uint8_t *mask, int64_t mask_stride, uint32_t *ids, float *scores, void *stream);
+/* Engine.SearchThreshold over one segment, by what the file holds: a flat segment is vg_search_flat_probed_threshold with the
+ * scan vg_segment_search picks (SQ8 codes, else PQ, else fp32 rows); a DiskANN segment is vg_search_vamana_threshold with the
+ * segment's kind — nprobes and rerank are ignored there (the walk's scores are what the engine compares).
+ * (Present when the symbol is: see VG_ABI_MINOR.) */
+int32_t vg_segment_search_threshold(vg_segment *seg, const float *queries, int64_t nq, const float *thresholds,
+                                    int32_t max_results, int32_t nprobes, int32_t rerank, const uint8_t *mask,
+                                    int64_t mask_stride, uint32_t *ids, float *scores, int32_t *counts, void *stream);
 /* diskann segment (diskann/format.go:8-119, segment.go:165-440,1393-1408): fp32 rows, the
  * N x R uint32 graph and entry point, PQ codebooks + codes or RaBitQ codes; search with
  * or INT4 parameters + codes; search with vg_search_vamana (kind 0 / 1 / 2 / 3).  The header's

@@ -634,6 +634,20 @@ public:
                                        r.counts.data(), nullptr));
         return r;
     }
+    // Engine.SearchThreshold over a flat segment with codes and / or IVF partitions (engine/engine.go:1485-1531 over
+    // flat/segment.go:447-780): the best max_results rows of the probed partitions by the score of `scan` (VG_SCAN_*), their
+    // exact scores when `rerank`, then the rows within thresholds[q]; rerank false compares the scan score
+    ThresholdResult SearchProbedThreshold(const float *queries, int64_t nq, const float *thresholds, int max_results, int nprobes,
+                                          int scan, bool rerank, const uint8_t *mask = nullptr, int64_t mask_stride = 0)
+    {
+        ThresholdResult r;
+        r.ids.resize(static_cast<size_t>(nq) * max_results);
+        r.scores.resize(static_cast<size_t>(nq) * max_results);
+        r.counts.resize(static_cast<size_t>(nq));
+        check(vg_search_flat_probed_threshold(h_, queries, nq, thresholds, max_results, nprobes, scan, rerank ? 1 : 0, mask, mask_stride,
+                                              r.ids.data(), r.scores.data(), r.counts.data(), nullptr));
+        return r;
+    }
     // opt-in: nominate with a bfloat16 MFMA GEMM over a bf16 copy of the rows; results stay bit-identical (vecgo_hip.h)
     void EnableBF16Filter(bool on = true) { check(vg_index_enable_bf16_filter(h_, on ? 1 : 0, nullptr)); }
     // flat.Segment.Search PQ branch (flat/segment.go:476-483,678-689)

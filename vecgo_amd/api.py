@@ -1460,11 +1460,9 @@ class Index:
         """flat.Segment.Search fp32 branch / hnsw.BruteSearch: exact brute force."""
         return self._search(self._lib.vg_search_flat, queries, k, out=out, stream=stream)
 
-    def search_flat_threshold(self, queries, thresholds, max_results, mask=None, out=None, stream=None):
-        """Engine.SearchThreshold over this flat segment (engine/engine.go:1485-1531): search_flat(q, max_results), then the rows
-        with score <= threshold (L2) / >= threshold (Dot, Cosine), best first.  thresholds: a scalar for the batch or one per
-        query; mask: as search_flat_filtered's (None = no filter).  Returns (ids [nq, max_results], scores, counts [nq]): query
-        q's rows are ids[q, :counts[q]], the rest padded with 0xFFFFFFFF / +-Inf."""
+    def _threshold_search(self, name, call, queries, thresholds, max_results, mask, out):
+        """The operands every threshold search shares, staged; call(queries, nq, thresholds, mask, mask_stride, ids, scores,
+        counts) is the entry point with them."""
         nq = _rows(queries, self.dim)
         q, pq_ = _ptr(queries, np.float32)
         if _is_torch(thresholds):
@@ -1477,9 +1475,9 @@ class Index:
             if t.size == 1:
                 t = np.full(nq, t[0], np.float32)
         if (t.numel() if _is_torch(t) else t.size) != nq:
-            raise ValueError(f"search_flat_threshold: one threshold for the batch or one per query ({nq})")
+            raise ValueError(f"{name}: one threshold for the batch or one per query ({nq})")
         t, pt = _ptr(t, np.float32, nq)
-        m, pm, stride = (None, None, 0) if mask is None else self._packed_mask(mask, nq, "search_flat_threshold")
+        m, pm, stride = (None, None, 0) if mask is None else self._packed_mask(mask, nq, name)
         if out is None:
             ids = _empty_like(queries, (nq, max_results), np.uint32)
             scores = _empty_like(queries, (nq, max_results), np.float32)
@@ -1489,9 +1487,31 @@ class Index:
         i, pi = _ptr(ids, np.uint32, nq * max_results)
         s, ps = _ptr(scores, np.float32, nq * max_results)
         c, pc = _ptr(counts, np.int32, nq)
-        check(self._lib.vg_search_flat_threshold(self._h, pq_, C.c_int64(nq), pt, C.c_int32(max_results), pm, C.c_int64(stride),
-                                                  pi, ps, pc, _stream_ptr(stream)))
+        check(call(pq_, C.c_int64(nq), pt, pm, C.c_int64(stride), pi, ps, pc))
         return ids, scores, counts
+
+    def search_flat_threshold(self, queries, thresholds, max_results, mask=None, out=None, stream=None):
+        """Engine.SearchThreshold over this flat segment (engine/engine.go:1485-1531): search_flat(q, max_results), then the rows
+        with score <= threshold (L2) / >= threshold (Dot, Cosine), best first.  thresholds: a scalar for the batch or one per
+        query; mask: as search_flat_filtered's (None = no filter).  Returns (ids [nq, max_results], scores, counts [nq]): query
+        q's rows are ids[q, :counts[q]], the rest padded with 0xFFFFFFFF / +-Inf."""
+        def call(pq_, nq, pt, pm, stride, pi, ps, pc):
+            return self._lib.vg_search_flat_threshold(self._h, pq_, nq, pt, C.c_int32(max_results), pm, stride, pi, ps, pc,
+                                                      _stream_ptr(stream))
+        return self._threshold_search("search_flat_threshold", call, queries, thresholds, max_results, mask, out)
+
+    def search_flat_probed_threshold(self, queries, thresholds, max_results, nprobes=0, scan=0, rerank=False, mask=None, out=None,
+                                     stream=None):
+        """Engine.SearchThreshold over a flat segment with codes and / or IVF partitions (engine/engine.go:1485-1531 over
+        flat/segment.go:447-780): the best max_results rows of the probed partitions (or the whole segment) by the score of
+        `scan` (SCAN_F32 / SCAN_PQ / SCAN_SQ8), then the rows within the threshold, best first.  rerank=False compares the
+        threshold with the scan score (the segment-level answer); rerank=True re-scores the candidates exactly from the fp32
+        rows first and compares that (the engine's).  Operands and result as search_flat_threshold's."""
+        def call(pq_, nq, pt, pm, stride, pi, ps, pc):
+            return self._lib.vg_search_flat_probed_threshold(self._h, pq_, nq, pt, C.c_int32(max_results), C.c_int32(nprobes),
+                                                             C.c_int32(scan), C.c_int32(1 if rerank else 0), pm, stride, pi, ps, pc,
+                                                             _stream_ptr(stream))
+        return self._threshold_search("search_flat_probed_threshold", call, queries, thresholds, max_results, mask, out)
 
     def enable_bf16_filter(self, on: bool = True, stream=None):
         """vg_index_enable_bf16_filter: nominate with a bfloat16 MFMA GEMM over a bf16 copy of the rows; the exact fp32
@@ -1557,6 +1577,16 @@ class Segment:
         def fn(_index_handle, *args):
             return self._lib.vg_segment_search_filtered(seg, *args)
         return self.index._search(fn, queries, k, extra=(C.c_int32(nprobes), pm, C.c_int64(stride)), out=out, stream=stream)
+
+    def search_threshold(self, queries, thresholds, max_results, nprobes=0, rerank=False, mask=None, out=None, stream=None):
+        """Engine.SearchThreshold over this segment, by what the file holds: search_flat_probed_threshold with the segment's
+        scan on a flat segment, search_vamana_threshold with its kind on a DiskANN one (nprobes and rerank unused there)."""
+        seg = self._h
+
+        def call(pq_, nq, pt, pm, stride, pi, ps, pc):
+            return self._lib.vg_segment_search_threshold(seg, pq_, nq, pt, C.c_int32(max_results), C.c_int32(nprobes),
+                                                         C.c_int32(1 if rerank else 0), pm, stride, pi, ps, pc, _stream_ptr(stream))
+        return self.index._threshold_search("Segment.search_threshold", call, queries, thresholds, max_results, mask, out)
 
     def close(self):
         if getattr(self, "_h", None):

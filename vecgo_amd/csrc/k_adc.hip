@@ -27,6 +27,7 @@
 // _mm512_reduce_add_ps tree, then the m%16 tail added sequentially.  fp32 adds only.
 #include <algorithm>
 
+#include "vg_adc_row.hpp"
 #include "vg_device.hpp"
 #include "vg_internal.hpp"
 #include "vg_cand_replay.hpp"
@@ -90,12 +91,6 @@ int32_t launch_pq_retile(const uint8_t *codes, int64_t n, int m, int groups, int
     return VG_OK;
 }
 
-__device__ __forceinline__ uint32_t code_byte(const uint4 &c, int l)
-{
-    uint32_t w = (l < 4) ? c.x : (l < 8) ? c.y : (l < 12) ? c.z : c.w;
-    return (w >> (8 * (l & 3))) & 0xFFu;
-}
-
 
 // ---- hand-pipelined LDS gathers -------------------------------------------------------------
 // hipcc waits after every few ds_read_b32 of an unrolled gather, which at 2 waves/SIMD leaves the
@@ -152,9 +147,6 @@ __device__ __forceinline__ void accumulate_half(float (&acc)[16], const Vals8 &x
 #pragma unroll
     for (int i = 0; i < 8; i++) acc[H * 8 + i] = acc[H * 8 + i] + x.v[i];
 }
-
-// words of the per-query LUT image (pair-interleaved full groups + natural tail rows)
-__host__ __device__ inline int lut_image_words(int m) { return (((m >> 4) + 1) >> 1) * 8192 + (m & 15) * 256; }
 
 __device__ __forceinline__ int64_t min64(int64_t a, int64_t b) { return a < b ? a : b; }
 __device__ __forceinline__ bool span_nonempty(int64_t t0, int64_t t1) { return t1 > t0; }
@@ -668,7 +660,6 @@ __global__ __launch_bounds__(kAdcThreads) void pq_adc_probe_kernel(
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     float *lut = reinterpret_cast<float *>(smem);
     const int lut_words = lut_image_words(m);
-    const int lut_tail_word = (((m >> 4) + 1) >> 1) * 8192;
     uint64_t *buf = reinterpret_cast<uint64_t *>(smem + static_cast<size_t>(lut_words) * sizeof(float));
     const int y = blockIdx.x;
     const int64_t q = blockIdx.y;
@@ -690,7 +681,6 @@ __global__ __launch_bounds__(kAdcThreads) void pq_adc_probe_kernel(
         for (int i = r * kAdcThreads + tid; i < n4; i += kAdcThreads) dst[i] = src[i];
     }
     __syncthreads();
-    const int gfull = m >> 4, tail = m & 15;
     const uint8_t *mq = mask ? mask + q * mask_stride : nullptr;  // filter.Matches (segment.go:631-635)
     WaveTopK wtk;
     wtk.init(k);
@@ -703,20 +693,7 @@ __global__ __launch_bounds__(kAdcThreads) void pq_adc_probe_kernel(
             const int64_t row = tile * 64 + lane;
             const bool live = row >= R0 && row < R1 && row < n_rows && mask_bit(mq, row);
             if (mq && !__any(live)) continue;  // a tile the filter leaves nothing of: its codes are not read
-            float acc[16];
-#pragma unroll
-            for (int l = 0; l < 16; l++) acc[l] = 0.0f;
-            for (int g = 0; g < gfull; g++) {
-                const uint4 c = tp[g * 64];
-#pragma unroll
-                for (int sl = 0; sl < 16; sl++)
-                    acc[sl] = acc[sl] + lut[((g >> 1) * 256 + code_byte(c, sl)) * 32 + (g & 1) * 16 + ((sl + rot) & 15)];
-            }
-            float total = reduce16_regs(acc);
-            if (tail) {
-                const uint4 c = tp[gfull * 64];
-                for (int l = 0; l < tail; l++) total = total + lut[lut_tail_word + l * 256 + code_byte(c, l)];
-            }
+            const float total = adc_row_score_lds(lut, tp, m, rot);
             uint64_t key = live ? make_key(total, static_cast<uint32_t>(row), desc) : kKeyMax;
             if (min_keys && key <= min_keys[q]) key = kKeyMax;  // paged results (k > 64)
             wtk.offer(key, lane);

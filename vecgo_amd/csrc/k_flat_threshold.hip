@@ -30,18 +30,6 @@ __device__ __forceinline__ bool thr_keep(float score, float t)
     return DOT ? score >= t : score <= t;
 }
 
-// the leader lanes (one per 16-lane group) whose `pass` is set append `key` to the list: one atomic per wave
-__device__ __forceinline__ void wave_append(bool pass, uint64_t key, int *count, uint64_t *list, int lane)
-{
-    const uint64_t m = __ballot(pass);
-    if (m == 0) return;
-    const int first = __builtin_ctzll(m);
-    int at = 0;
-    if (lane == first) at = atomicAdd(count, __popcll(m));
-    at = __shfl(at, first);
-    if (pass) list[at + __popcll(m & ((uint64_t(1) << lane) - 1))] = key;
-}
-
 // ---- 1. the scan: every row against up to kThrQB queries, the rows within a query's threshold appended ----------
 // Slot j of the pass is query qmap[j] (null: j) of the arrays passed.  REGS: the row is loaded once into registers (dim % 4 == 0, 64 <= dim <= 1024,
 // 16-byte aligned rows) and scored against the queries in LDS (exact_rowregs16, the flat scan's form); otherwise every
@@ -238,27 +226,50 @@ int32_t launch_thr_filter(bool desc, const float *thr, int64_t nq, int max_resul
 
 // ---- batches: the rows the nomination appended (GEMM keys), re-scored exactly; those within the threshold go to the list ---------
 // grid (workgroups per query, queries); 4 candidates per wave step, one per 16-lane group
+// cand_ids (null: the keys of `cand`, counts[q] each): a search's result rows instead, cap per query, VG_INVALID_ID where a
+// slot is unused — Segment.Rerank's input after a scan over codes (k_probed_threshold.hip)
 template <bool DOT>
 __global__ __launch_bounds__(256) void flat_thr_rescore_kernel(const float *__restrict__ base, int dim, const float *__restrict__ queries,
                                                                const float *__restrict__ thr, const uint64_t *__restrict__ cand,
-                                                               const int *__restrict__ counts, int cap, uint64_t *__restrict__ lists,
-                                                               int *__restrict__ list_counts)
+                                                               const uint32_t *__restrict__ cand_ids, const int *__restrict__ counts,
+                                                               int cap, uint64_t *__restrict__ lists, int *__restrict__ list_counts)
 {
     const int64_t q = blockIdx.y;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const Sub16 sub = Sub16::make(tid);
-    const int c = counts[q] < cap ? counts[q] : cap;
+    const int c = cand_ids ? cap : (counts[q] < cap ? counts[q] : cap);
     if (c == 0) return;
     const float *qv = queries + q * dim;
     const float t = thr[q];
     for (int c0 = blockIdx.x * 16 + wave * 4; c0 < c; c0 += gridDim.x * 16) {
         const int ci = c0 + (lane >> 4);
-        const bool live = ci < c;
-        const uint32_t id = key_row(cand[q * cap + (live ? ci : c - 1)]);
+        bool live = ci < c;
+        uint32_t id = cand_ids ? cand_ids[q * cap + (live ? ci : c - 1)] : key_row(cand[q * cap + (live ? ci : c - 1)]);
+        if (cand_ids && id == VG_INVALID_ID) {
+            live = false;
+            id = 0;
+        }
         const float v = exact_pair16<DOT, kPair>(base + static_cast<int64_t>(id) * dim, qv, dim, sub);
         const bool pass = live && (lane & 15) == 0 && thr_keep<DOT>(v, t);
         wave_append(pass, make_key(v, id, DOT), list_counts + q, lists + q * cap, lane);
     }
+}
+
+// Segment.Rerank over a search's result rows (ids[nq * cap], VG_INVALID_ID where unused): the exact scores within each query's
+// threshold, as keys in lists[nq * cap] / list_counts[nq] (zeroed here)
+int32_t launch_thr_rescore_ids(bool desc, const float *base, int dim, const float *queries, const float *thr, const uint32_t *ids,
+                               int64_t nq, int cap, uint64_t *lists, int *list_counts, hipStream_t st)
+{
+    if (nq == 0 || cap == 0) return VG_OK;
+    VG_HIP(hipMemsetAsync(list_counts, 0, sizeof(int) * static_cast<size_t>(nq), st));
+    const dim3 grid(static_cast<unsigned>(std::min(32, std::max(1, cap / 2048))), static_cast<unsigned>(nq));
+    if (desc)
+        VG_LAUNCH(flat_thr_rescore_kernel<true>, grid, dim3(256), 0, st, base, dim, queries, thr, nullptr, ids, nullptr, cap, lists,
+                  list_counts);
+    else
+        VG_LAUNCH(flat_thr_rescore_kernel<false>, grid, dim3(256), 0, st, base, dim, queries, thr, nullptr, ids, nullptr, cap, lists,
+                  list_counts);
+    return VG_OK;
 }
 
 // The proof of a nominated query (one thread per query).  The user's threshold stood (untight = 1) and the list did not
@@ -454,10 +465,10 @@ VG_API int32_t vg_search_flat_threshold(vg_index *idx, const float *queries, int
                 vg::ProfScope prof(idx->ctx, "flat_thr_rescore", st);
                 if (dot)
                     VG_LAUNCH(vg::flat_thr_rescore_kernel<true>, dim3(rescore_wgs, uc), dim3(256), 0, st, idx->d_vectors, dim, qp, tp, cand,
-                              gcounts, cap, elist, ecount);
+                              nullptr, gcounts, cap, elist, ecount);
                 else
                     VG_LAUNCH(vg::flat_thr_rescore_kernel<false>, dim3(rescore_wgs, uc), dim3(256), 0, st, idx->d_vectors, dim, qp, tp, cand,
-                              gcounts, cap, elist, ecount);
+                              nullptr, gcounts, cap, elist, ecount);
             }
             {
                 vg::ProfScope prof(idx->ctx, "flat_thr_select", st);

@@ -584,7 +584,7 @@ static int32_t flat_probed_impl(vg_index *idx, const float *queries, int64_t nq,
                                 bool allow_nomination = true, uint32_t *probes_out = nullptr);
 
 // kmeans.FindClosestCentroids for every query (device buffers): probes[q * np + j]
-static int32_t launch_probe_select(const vg_index *idx, const float *d_queries, int64_t nq, int np, bool dot, uint32_t *d_probes, hipStream_t st)
+int32_t vg::launch_probe_select(const vg_index *idx, const float *d_queries, int64_t nq, int np, bool dot, uint32_t *d_probes, hipStream_t st)
 {
     const size_t sel_lds = 8 * static_cast<size_t>(idx->num_partitions);
     const int emulate = np <= idx->num_partitions / 4 && np < 16 && sel_lds <= 156 * 1024;
@@ -989,7 +989,7 @@ static int32_t probed_search_device(vg_index *idx, const float *q, int64_t nq, i
         // the reference's selection loop (kmeans.go:255: n <= k/4 && n < 16) is replayed where centroid distances tie; its LDS
         // (8 bytes per partition, beside the kernel's 2.6 KB of static LDS) bounds that to 19 968 partitions — beyond, ties are
         // broken by centroid id
-        VG_TRY(launch_probe_select(idx, q, nq, np, c.dot, c.probes, st));
+        VG_TRY(vg::launch_probe_select(idx, q, nq, np, c.dot, c.probes, st));
     }
     if (gemm_path.applies()) return gemm_path.run(c, ar, ar.get<uint64_t>(pages.i_partial));
     return scan_path.run(c, ar, pages);

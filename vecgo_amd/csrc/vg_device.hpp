@@ -116,6 +116,18 @@ __device__ __forceinline__ bool mask_bit(const uint8_t *__restrict__ mask, int64
     return mask == nullptr || ((mask[i >> 3] >> (i & 7)) & 1);
 }
 
+// the lanes whose `pass` is set append `key` to the list (the caller sizes it for every key that can pass): one atomic per wave
+__device__ __forceinline__ void wave_append(bool pass, uint64_t key, int *count, uint64_t *list, int lane)
+{
+    const uint64_t m = __ballot(pass);
+    if (m == 0) return;
+    const int first = __builtin_ctzll(m);
+    int at = 0;
+    if (lane == first) at = atomicAdd(count, __popcll(m));
+    at = __shfl(at, first);
+    if (pass) list[at + __popcll(m & ((uint64_t(1) << lane) - 1))] = key;
+}
+
 struct WaveTopK {
     uint64_t list;  // lane i: i-th smallest key of this wave so far
     uint64_t tau;   // wave-uniform: key at lane k-1 (kKeyMax until k keys were seen)

@@ -96,6 +96,7 @@ enum Hook {
     kHookNoCandReplay,        // VG_NO_CAND_REPLAY       no heap replay for queries whose scores may hold a NaN (vg_cand_replay.hpp): what the fast paths alone answer
     kHookVamanaSmallScratch,  // VG_VAMANA_SMALL_SCRATCH vg_search_vamana with k > 512: 64 MiB of per-launch scratch, so that a small batch takes several launches
     kHookFlatRescoreSample,   // VG_FLAT_RESCORE_SAMPLE  flat search: the main GEMM multiplies the sampled row tiles again (no append from the sample)
+    kHookPthrForceHist,       // VG_PTHR_FORCE_HIST      vg_search_flat_probed_threshold without rerank: the top-max_results-by-histogram form, then the filter
     kHookCount
 };
 bool hook(Hook h);

@@ -65,6 +65,12 @@ int32_t launch_thr_select_lists(bool desc, const uint64_t *lists, int64_t list_c
                                 uint32_t *ids, float *scores, int32_t *out_counts, hipStream_t st);
 int32_t launch_thr_filter(bool desc, const float *thr, int64_t nq, int max_results, uint32_t *ids, float *scores, int32_t *counts,
                           hipStream_t st);
+int32_t launch_thr_rescore_ids(bool desc, const float *base, int dim, const float *queries, const float *thr, const uint32_t *ids,
+                               int64_t nq, int cap, uint64_t *lists, int *list_counts, hipStream_t st);
+
+// ---- k_probe.hip ----------------------------------------------------------------------------------
+// kmeans.FindClosestCentroids for every query (device buffers): probes[q * np + j]
+int32_t launch_probe_select(const vg_index *idx, const float *d_queries, int64_t nq, int np, bool dot, uint32_t *d_probes, hipStream_t st);
 
 // ---- k_sq8.hip ------------------------------------------------------------------------------------
 // stage 1 of a quantizer's Train (SQ8, INT4) over device rows: per-dimension min / max of min(n, 1024) row chunks,

@@ -166,6 +166,26 @@ VG_API int32_t vg_segment_search_filtered(vg_segment *seg, const float *queries,
     return vg_search_flat_filtered(seg->idx, queries, nq, k, nprobes, scan, mask, mask_stride, ids, scores, stream);
 }
 
+// Engine.SearchThreshold over one segment (engine/engine.go:1485-1531), by what the file holds
+VG_API int32_t vg_segment_search_threshold(vg_segment *seg, const float *queries, int64_t nq, const float *thresholds,
+                                           int32_t max_results, int32_t nprobes, int32_t rerank, const uint8_t *mask,
+                                           int64_t mask_stride, uint32_t *ids, float *scores, int32_t *counts, void *stream)
+{
+    VG_CHECK(seg && seg->idx, VG_ERR_INVALID_ARG, "vg_segment_search_threshold: NULL segment");
+    if (seg->info.kind == 1) {  // (the walk's scores are what the engine compares: rerank is not part of this leg)
+        const int32_t kind = seg->info.quantization == VG_QUANT_RABITQ ? 2
+                             : seg->info.quantization == VG_QUANT_PQ   ? 1
+                             : seg->info.quantization == VG_QUANT_INT4 ? 3
+                                                                       : 0;
+        return vg_search_vamana_threshold(seg->idx, queries, nq, thresholds, max_results, kind, mask, mask_stride, ids, scores, counts,
+                                          nullptr, stream);
+    }
+    // flat/segment.go:657-701: SQ8 codes if the segment has them, else PQ table lookups, else fp32 rows
+    const int32_t scan = seg->info.quantization == VG_QUANT_SQ8 ? VG_SCAN_SQ8 : seg->info.quantization == VG_QUANT_PQ ? VG_SCAN_PQ : VG_SCAN_F32;
+    return vg_search_flat_probed_threshold(seg->idx, queries, nq, thresholds, max_results, nprobes, scan, rerank, mask, mask_stride, ids,
+                                           scores, counts, stream);
+}
+
 VG_API int32_t vg_segment_open_diskann(vg_ctx *ctx, const void *image, int64_t size, int32_t verify_checksum,
                                        vg_segment **out, void *stream)
 {
