@@ -197,6 +197,34 @@ func (r *Resident) BuildVamana(R, L int, alpha float32, seed uint64) error {
 	return hipctx.Err(int32(C.vg_vamana_build(r.h, C.int32_t(R), C.int32_t(L), C.float(alpha), nil, C.uint64_t(seed), 8192, 32, nil)))
 }
 
+// InsertVamana: FreshVamana.Insert for len(rows)/dim new rows (diskann/fresh_vamana.go:178-222), appended as rows r.rows..
+// and linked into the resident Vamana graph (vg_vamana_insert).  R, L, alpha of 0 take FreshDefault*.  deleted: bit i of byte
+// i/8 = node i is deleted (FreshVamana.Delete; the rows before the call), nil = none.  On an empty Resident the first call
+// creates the rows and the graph.
+func (r *Resident) InsertVamana(rows []float32, R, L int, alpha float32, deleted []byte, seed uint64) error {
+	if r.dim <= 0 || len(rows)%r.dim != 0 {
+		return fmt.Errorf("segment: InsertVamana: %d floats are not whole rows of %d", len(rows), r.dim)
+	}
+	count := len(rows) / r.dim
+	if count == 0 {
+		return nil
+	}
+	var dp *C.uint8_t
+	if deleted != nil {
+		if len(deleted) < (r.rows+7)/8 {
+			return fmt.Errorf("segment: InsertVamana: deleted holds %d bytes, %d needed", len(deleted), (r.rows+7)/8)
+		}
+		if len(deleted) > 0 {
+			dp = bp(deleted)
+		}
+	}
+	if err := hipctx.Err(int32(C.vg_vamana_insert(r.h, fp(rows), C.int64_t(count), C.int32_t(R), C.int32_t(L), C.float(alpha), dp, C.uint64_t(seed), 8192, 32, nil))); err != nil {
+		return err
+	}
+	r.rows += count
+	return nil
+}
+
 // ReorderVamanaBFS: diskann.Writer.reorderBFS (diskann/reorder.go:14-157) on the resident graph and every per-row array
 // it holds.  perm[new] = old; invPerm[old] = new is the writer's addOrderToFinalRow.  The caller permutes what the GPU
 // never held (ids, metadata, payloads) with perm.
@@ -757,6 +785,39 @@ func (r *Resident) SearchVamanaThreshold(queries []float32, nq int, thresholds [
 		mp = bp(mask)
 	}
 	st := C.vg_search_vamana_threshold(r.h, fp(queries), C.int64_t(nq), fp(thresholds), C.int32_t(maxResults), C.int32_t(kind), mp, C.int64_t(maskStride), up(ids), fp(sc), ip(counts), sp, nil)
+	return ids, sc, counts, hipctx.Err(int32(st))
+}
+
+// SearchVamanaFresh: FreshVamana.Search, and with a mask SearchWithFilter (diskann/fresh_vamana.go:272-364), over the resident
+// Vamana graph (vg_search_vamana_fresh).  L = the index's search list size (0 = 100); deleted as for InsertVamana; mask /
+// maskStride as for SearchVamanaThreshold.  Query q's rows are ids[q*k : q*k+counts[q]].
+func (r *Resident) SearchVamanaFresh(queries []float32, nq, k, L int, deleted, mask []byte, maskStride int) ([]uint32, []float32, []int32, error) {
+	if nq == 0 || k == 0 {
+		return nil, nil, make([]int32, nq), nil
+	}
+	need := (r.rows + 7) / 8
+	var dp, mp *C.uint8_t
+	if deleted != nil && need > 0 {
+		if len(deleted) < need {
+			return nil, nil, nil, fmt.Errorf("SearchVamanaFresh: deleted holds %d bytes, %d needed", len(deleted), need)
+		}
+		dp = bp(deleted)
+	}
+	if mask != nil {
+		if maskStride != 0 {
+			if maskStride < need {
+				return nil, nil, nil, fmt.Errorf("SearchVamanaFresh: maskStride %d is shorter than a mask (%d bytes)", maskStride, need)
+			}
+			need += (nq - 1) * maskStride
+		}
+		if len(mask) < need || len(mask) == 0 {
+			return nil, nil, nil, fmt.Errorf("SearchVamanaFresh: mask holds %d bytes, %d needed", len(mask), need)
+		}
+		mp = bp(mask)
+	}
+	ids, sc := r.out(nq, k)
+	counts := make([]int32, nq)
+	st := C.vg_search_vamana_fresh(r.h, fp(queries), C.int64_t(nq), C.int32_t(k), C.int32_t(L), dp, mp, C.int64_t(maskStride), up(ids), fp(sc), ip(counts), nil)
 	return ids, sc, counts, hipctx.Err(int32(st))
 }
 

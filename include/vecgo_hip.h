@@ -44,7 +44,7 @@
  *     These WAIT for `stream` inside the call, device buffers or not, because the host
  *     needs a value the device computes: every *_train (the solves and convergence tests
  *     are the host's); the builders and maintenance calls (vg_hnsw_build / _insert /
- *     _compact, vg_vamana_build, vg_vamana_reorder_bfs, vg_flat_build, vg_diskann_build,
+ *     _compact, vg_vamana_build, vg_vamana_insert, vg_vamana_reorder_bfs, vg_flat_build, vg_diskann_build,
  *     vg_segment_*); vg_index_set_* and vg_index_enable_* (storage is replaced; the
  *     caller's buffer is free again at return); every getter; vg_search_hnsw_brute (reads
  *     its filter's population count and redo flags back); vg_search_sq8 and
@@ -103,7 +103,8 @@ extern "C" {
  *  Likewise vg_hnsw_compact (with its caller-allocated vg_hnsw_compact_stats).  Likewise the DiskANN writer:
  *  vg_diskann_build, vg_segment_diskann_image_size and vg_segment_write_diskann, found by symbol lookup.  Likewise the
  *  threshold search over coded / partitioned flat segments: vg_search_flat_probed_threshold and
- *  vg_segment_search_threshold, found by symbol lookup. */
+ *  vg_segment_search_threshold, found by symbol lookup.  Likewise the streaming Vamana index: vg_vamana_insert and
+ *  vg_search_vamana_fresh, found by symbol lookup. */
 #define VG_ABI_MINOR 13
 #define VG_INVALID_ID 0xFFFFFFFFu
 #define VG_STREAM_LEGACY ((void *)1) /* == hipStreamLegacy */
@@ -447,6 +448,56 @@ int32_t vg_index_set_vamana_graph(vg_index *idx, int32_t r, const uint32_t *grap
  *   inputs give the same graph bit for bit. */
 int32_t vg_vamana_build(vg_index *idx, int32_t r, int32_t l, float alpha, const uint32_t *init_graph, uint64_t seed,
                         int32_t max_batch, int32_t growth_div, void *stream);
+/* FreshVamana.Insert (internal/segment/diskann/fresh_vamana.go:178-222) for `count` new rows, appended to the index as rows
+ * n .. n+count-1 and linked into its Vamana graph: the streaming index's write path.  rows: count*dim fp32, host or device.
+ * A node id is the row number (allocateNodeLocked :444-469).  r, l, alpha of 0 take FreshDefault* (:20-24): 64, 100, 1.2.
+ *   Empty index (n = 0, no graph): the first call creates the rows and the graph; row 0 becomes the entry point and has no
+ *     links (:198-201).  Otherwise the index's graph may come from vg_vamana_build, vg_index_set_vamana_graph or earlier
+ *     calls; r must be the graph's.  VG_INVALID_ID slots are skipped wherever they sit; every list this call writes is a
+ *     dense prefix padded with VG_INVALID_ID.
+ *   deleted: bit i of byte i/8 = node i is deleted (FreshVamana.Delete is that one bit, the caller's to keep), ceil(n/8)
+ *     bytes for the n rows that exist before the call, host or device, NULL = none; new rows are live.
+ *   Distance: distance.Provider(metric) in the pair kernel's summation order, exactly as vg_vamana_build states it (raw Dot
+ *     for Cosine and Dot, sorted ascending: the reference's quirk, reproduced).  In a sorted list -0 equals +0.
+ *   Per node t:
+ *   1. results = searchCandidatesLocked(row t, entry, l) (:616-671).  Two lists ordered by distance: candidates (cap 2l,
+ *      popped from the front) and results (cap l, non-deleted nodes only; deleted nodes are still walked through).  The
+ *      walk stops when results holds l items and the popped distance is greater than its last one, or candidates is empty.
+ *      A popped node's unvisited neighbours are taken in list order.  insertCandidate (:898-923) places an item after
+ *      every entry whose distance is <= its own and drops it when that position is >= cap: the order is (distance,
+ *      arrival), which the reference pins.
+ *   2. list(t) = robustPruneLocked(t, results, r, alpha) (:748-792): candidates in (distance, position) order; t itself and
+ *      deleted ids are skipped; c is kept unless d(c, s) < alpha * c.dist for a kept s (the product is fp32, its own
+ *      rounding step; a false comparison keeps c); stops at r kept.  The reference's sort.Slice moves nothing on the
+ *      already ordered results and is a stable insertion sort on <= 12 items: the rule here is "stable by position"
+ *      everywhere, which beyond 12 unordered items (the reverse edge's r + 1 candidates) is the rule the reference leaves open.
+ *   3. for each neighbour in list order, addReverseEdgeLocked(neighbour, t) (:698-745): nothing if t is listed; appended
+ *      while the list is shorter than r; at r the list in slot order followed by t, with distances to the neighbour, sorted
+ *      stably by distance, goes through robustPruneLocked(neighbour, ..., r, alpha), which drops deleted ids and may keep
+ *      fewer than r.
+ *   4. maybeUpdateEntryPoint (:795-801) with count = t + 1: t becomes the entry point when count < 100, or when
+ *      count % 500 == 0 and u < 0.1.  The reference's rand.Float32() is replaced (a stated deviation, like vg_vamana_build's
+ *      initial graph) by u = float32(rng_u64(seed, count, P, 0) >> 40) * 2^-24, in [0, 1): the shared counter RNG (oracle
+ *      vgo_rng_u64), P = 0x4652455348 ("FRESH").
+ *   Batches: nodes go in id order in batches of clamp(nodes in the graph / growth_div, 1, max_batch); a call always ends a
+ *     batch.  Every node of a batch searches the graph, and starts from the entry point, as they stood when the batch
+ *     began; then the new lists are written; then the reverse edges are applied, each target's in (source id, slot) order.
+ *     max_batch = 1 is the reference's serialized Insert loop (growMu).  Hence one call of a+b rows equals a call of a rows
+ *     followed by a call of b rows whenever the call boundary is a batch boundary: for any a when max_batch = 1.
+ *   NaN distances: a NaN orders after +Inf, in arrival order among NaNs, and compares greater than any number in the stop
+ *     test (a stated deviation: sort.Search over a slice that NaNs left unordered is not restated).  Such inputs complete
+ *     and leave a structurally valid graph.
+ *   Everything sized by n follows: the fp32 rows, their norms, the bf16 filter image if enabled and the graph table grow by
+ *     capacity (x1.5), and every search (vg_search_vamana*, vg_search_vamana_fresh), vg_vamana_reorder_bfs,
+ *     vg_index_get_vamana_graph and vg_segment_write_diskann see n + count rows afterwards.  The visited bitmaps (n bits
+ *     per searching node) of a launch stay under 1/16 of device memory; larger batches take several launches.
+ *   Refusals, in this order, nothing changed: NULL index, count < 0 VG_ERR_INVALID_ARG; rows but no Vamana graph
+ *     VG_ERR_NOT_READY; Hamming, r outside 1..64, l outside 1..1024, max_batch > 16384, >= 2^31 rows after the insert
+ *     VG_ERR_UNSUPPORTED; max_batch < 1 or growth_div < 1 VG_ERR_INVALID_ARG; r not the graph's VG_ERR_INVALID_ARG; PQ / SQ8 /
+ *     INT4 / RaBitQ codes, IVF partitions, an HNSW graph or tombstones, or a nomination image VG_ERR_UNSUPPORTED.
+ *     count = 0 changes nothing.  (Present when the symbol is: see VG_ABI_MINOR.) */
+int32_t vg_vamana_insert(vg_index *idx, const float *rows, int64_t count, int32_t r, int32_t l, float alpha,
+                         const uint8_t *deleted, uint64_t seed, int32_t max_batch, int32_t growth_div, void *stream);
 /* The index's Vamana graph in vg_index_set_vamana_graph's layout: r, entry point, graph[n*r] (host or device);
  * graph NULL = the sizes only.  (VG_ABI_MINOR 12.) */
 int32_t vg_index_get_vamana_graph(const vg_index *idx, int32_t *r, uint32_t *entry_point, uint32_t *graph,
@@ -1014,6 +1065,21 @@ int32_t vg_search_vamana(vg_index *idx, const float *queries, int64_t nq, int32_
 int32_t vg_search_vamana_filtered(vg_index *idx, const float *queries, int64_t nq, int32_t k, int32_t kind,
                                   const uint8_t *mask, int64_t mask_stride, uint32_t *ids, float *scores,
                                   vg_search_stats *stats, void *stream);
+/* FreshVamana.Search (fresh_vamana.go:272-315) and, with a mask, SearchWithFilter (:318-364) over the index's Vamana graph
+ * and fp32 rows.  greedySearch (:535-613) is the walk of vg_vamana_insert's step 1 with caps 2 ef and ef, except that results
+ * takes every node, deleted ones too.  l = FreshVamana's search list size (0 = 100); only ef is limited.
+ *   mask NULL: ef = max(2k, l); the first k results that are not deleted are returned.
+ *   mask set:  ef = max(10k, 2l); the first k results that are not deleted and whose mask bit is set.  mask / mask_stride as
+ *     for vg_search_vamana_filtered (bit i of byte i/8 = filter(i), query q's at mask + q * mask_stride, 0 = one for the batch).
+ *   deleted: as for vg_vamana_insert, ceil(n/8) bytes, NULL = none.
+ * ids / scores: nq * k, scores the walk's distances (vg_vamana_insert's Distance and NaN rules); counts[q] <= k rows found
+ * (may be NULL), the remaining slots hold VG_INVALID_ID and +Inf (L2) / -Inf (Dot, Cosine) as the threshold searches pad
+ * them.  An index without rows answers counts 0.  ef > 2048 (two lists of 2 ef and ef 8-byte keys, ping-ponged in LDS)
+ * VG_ERR_UNSUPPORTED; no graph VG_ERR_NOT_READY.  Pointers may be host or device.  (Present when the symbol is: see
+ * VG_ABI_MINOR.) */
+int32_t vg_search_vamana_fresh(vg_index *idx, const float *queries, int64_t nq, int32_t k, int32_t l, const uint8_t *deleted,
+                               const uint8_t *mask, int64_t mask_stride, uint32_t *ids, float *scores, int32_t *counts,
+                               void *stream);
 /* Engine.SearchThreshold's DiskANN leg (engine/engine.go:1485-1531): per query vg_search_vamana_filtered(q, k =
  * max_results) — the walk runs with the full k, the threshold prunes nothing — then the engine's filter (:1518-1529):
  * Score <= thresholds[q] for L2, Score >= thresholds[q] for Dot and Cosine, by the index's metric even for the code scorers

@@ -687,6 +687,13 @@ public:
     {
         check(vg_vamana_build(h_, r, l, alpha, initGraph, seed, maxBatch, growthDiv, nullptr));
     }
+    // FreshVamana.Insert (fresh_vamana.go:178-222) for `count` rows appended as rows n .. n+count-1 (vg_vamana_insert); rows and
+    // deleted (bit i of byte i/8 = node i is deleted, the rows before the call; null = none) host or device
+    void InsertVamana(const float *rows, int64_t count, int r = 64, int l = 100, float alpha = 1.2f, const uint8_t *deleted = nullptr,
+                      uint64_t seed = 0, int maxBatch = 8192, int growthDiv = 32)
+    {
+        check(vg_vamana_insert(h_, rows, count, r, l, alpha, deleted, seed, maxBatch, growthDiv, nullptr));
+    }
     // diskann.Writer.reorderBFS (reorder.go:14-157): the graph and every per-row array into BFS order; perm[new] = old,
     // invPerm[old] = new (either may be null; host or device)
     void ReorderVamanaBFS(uint32_t *perm, uint32_t *invPerm) { check(vg_vamana_reorder_bfs(h_, perm, invPerm, nullptr)); }
@@ -771,6 +778,19 @@ public:
     // searchInternal with a row filter (diskann/segment.go:616-627): mask bit i of byte i/8 = filter.Matches(i)
     Result SearchVamanaFiltered(const float *queries, int64_t nq, int k, int kind, const uint8_t *mask, int64_t mask_stride) { return run(nq, k, [&](Result &r) { return vg_search_vamana_filtered(h_, queries, nq, k, kind, mask, mask_stride, r.ids.data(), r.scores.data(), nullptr, nullptr); }); }
     Result SearchVamana(const float *queries, int64_t nq, int k, int kind) { return run(nq, k, [&](Result &r) { return vg_search_vamana(h_, queries, nq, k, kind, r.ids.data(), r.scores.data(), nullptr, nullptr); }); }
+    // FreshVamana.Search / SearchWithFilter (fresh_vamana.go:272-364): l = the index's search list size, deleted as for
+    // InsertVamana, mask = nullptr: Search.  counts[q] rows found, the rest padded
+    ThresholdResult SearchVamanaFresh(const float *queries, int64_t nq, int k, int l = 100, const uint8_t *deleted = nullptr,
+                                      const uint8_t *mask = nullptr, int64_t mask_stride = 0)
+    {
+        ThresholdResult r;
+        r.ids.resize(static_cast<size_t>(nq) * k);
+        r.scores.resize(static_cast<size_t>(nq) * k);
+        r.counts.resize(static_cast<size_t>(nq));
+        check(vg_search_vamana_fresh(h_, queries, nq, k, l, deleted, mask, mask_stride, r.ids.data(), r.scores.data(), r.counts.data(),
+                                     nullptr));
+        return r;
+    }
     // Engine.SearchThreshold's DiskANN leg (engine/engine.go:1485-1531): SearchVamanaFiltered(q, max_results), then the rows within
     // thresholds[q] (<= for L2, >= for Dot / Cosine) in walk order; mask = nullptr: no filter.  max_results <= 16384
     ThresholdResult SearchVamanaThreshold(const float *queries, int64_t nq, const float *thresholds, int max_results, int kind,

@@ -1083,6 +1083,43 @@ class Index:
                                         None if g is None else C.c_void_p(g.ctypes.data), C.c_uint64(seed),
                                         C.c_int32(max_batch), C.c_int32(growth_div), _stream_ptr(stream)))
 
+    def insert_vamana(self, rows, r=64, l=100, alpha=1.2, deleted=None, seed=0, max_batch=8192, growth_div=32, stream=None):
+        """FreshVamana.Insert on the GPU (vg_vamana_insert; the rules are the header's): rows [count, dim] fp32 are appended as
+        rows n .. n+count-1 and linked into the index's Vamana graph (batches of clamp(nodes / growth_div, 1, max_batch);
+        max_batch=1 is the reference's serialized loop).  deleted: bool[n] / packed bits over the rows before the call, or
+        None.  An empty index (n = 0) gets its rows and graph from the first call."""
+        if not _is_torch(rows):
+            rows = np.asarray(rows)
+        shape = tuple(rows.shape)
+        if len(shape) != 2 or shape[1] != self.dim:
+            raise ValueError(f"insert_vamana: rows must be [count, {self.dim}], got {shape}")
+        if (rows.dtype != torch.float32) if _is_torch(rows) else (np.asarray(rows).dtype != np.float32):
+            raise TypeError(f"insert_vamana: rows must be float32, got {rows.dtype}")
+        count = shape[0]
+        rr, pr = _ptr(rows, np.float32, count * self.dim)
+        d, pd, _ = (None, None, 0) if deleted is None or self.n == 0 else self._packed_mask(deleted, 1, "insert_vamana")
+        check(self._lib.vg_vamana_insert(self._h, pr, C.c_int64(count), C.c_int32(r), C.c_int32(l), C.c_float(alpha), pd,
+                                         C.c_uint64(seed), C.c_int32(max_batch), C.c_int32(growth_div), _stream_ptr(stream)))
+        self.n += count
+
+    def search_vamana_fresh(self, queries, k, l=100, deleted=None, mask=None, stream=None):
+        """FreshVamana.Search, and with a mask SearchWithFilter, on the GPU (vg_search_vamana_fresh): l = the index's search
+        list size; deleted: bool[n] / packed bits or None; mask: as search_vamana_filtered's.  Returns (ids [nq, k], scores,
+        counts [nq]): query q's rows are ids[q, :counts[q]], the rest padded with 0xFFFFFFFF / +-Inf."""
+        nq = _rows(queries, self.dim)
+        q, pq_ = _ptr(queries, np.float32)
+        d, pd, _ = (None, None, 0) if deleted is None or self.n == 0 else self._packed_mask(deleted, 1, "search_vamana_fresh")
+        m, pm, stride = (None, None, 0) if mask is None else self._packed_mask(mask, nq, "search_vamana_fresh")
+        ids = _empty_like(queries, (nq, k), np.uint32)
+        scores = _empty_like(queries, (nq, k), np.float32)
+        counts = _empty_like(queries, (nq,), np.int32)
+        i, pi = _ptr(ids, np.uint32, nq * k)
+        s, ps = _ptr(scores, np.float32, nq * k)
+        c, pc = _ptr(counts, np.int32, nq)
+        check(self._lib.vg_search_vamana_fresh(self._h, pq_, C.c_int64(nq), C.c_int32(k), C.c_int32(l), pd, pm, C.c_int64(stride),
+                                               pi, ps, pc, _stream_ptr(stream)))
+        return ids, scores, counts
+
     def get_vamana_graph(self, stream=None):
         """(graph[n, r], entry_point) — set_vamana_graph's arguments."""
         r, ep = C.c_int32(), C.c_uint32()

@@ -824,6 +824,7 @@ VG_API int32_t vg_index_set_vamana_graph(vg_index *idx, int32_t r, const uint32_
         idx->d_vamana = nullptr;
         return bad;
     }
+    idx->vamana_cap = 0;
     idx->vamana_r = r;
     idx->vamana_entry = entry_point;
     return VG_OK;

@@ -38,6 +38,7 @@
 #include "vg_device.hpp"
 #include "vg_exact.hpp"
 #include "vg_group_records.hpp"
+#include "vg_grow_rows.hpp"
 #include "vg_heap.hpp"
 #include "vg_hnsw_layer.hpp"
 #include "vg_internal.hpp"
@@ -1086,24 +1087,6 @@ static void adopt_hnsw_graph(vg_index *idx, uint32_t *l0, float *l0c, uint32_t *
     idx->hnsw_entry = p.entry;
 }
 
-// room for n_new rows in a device array that holds n_old (its capacity: *cap rows, 0 = n_old), grown by half at
-// least so that a run of small inserts copies the array O(log n) times; bytes(r) = its size at r rows
-template <typename T, typename F>
-static int32_t grow_rows(T **p, int64_t *cap, int64_t n_old, int64_t n_new, F bytes, hipStream_t st)
-{
-    const int64_t have = std::max(*cap, n_old);
-    if (*p && n_new <= have) return VG_OK;
-    const int64_t want = std::max(n_new, have + have / 2);
-    DevBuf<char> q;
-    VG_TRY(q.alloc(bytes(want)));
-    if (*p && n_old) VG_HIP(hipMemcpyAsync(q.p, *p, bytes(n_old), hipMemcpyDeviceToDevice, st));
-    VG_HIP(hipStreamSynchronize(st));
-    drop_device(p);
-    *p = reinterpret_cast<T *>(q.release());
-    *cap = want;
-    return VG_OK;
-}
-
 }  // namespace vg
 
 VG_API int32_t vg_hnsw_level_for_id(uint64_t id, int32_t m)
@@ -1224,30 +1207,7 @@ VG_API int32_t vg_hnsw_insert(vg_index *idx, const float *rows, int64_t count, i
     // ---- the rows and everything sized by n ----
     vg::DevIn<float> in;
     VG_TRY(in.init(rows, static_cast<size_t>(count) * dim, st));
-    if (!idx->d_norm_max) {
-        VG_HIP(hipMalloc(reinterpret_cast<void **>(&idx->d_norm_max), 2 * sizeof(float)));
-        VG_HIP(hipMemsetAsync(idx->d_norm_max, 0, 2 * sizeof(float), st));
-    }
-    if (!idx->d_flat_stats) {
-        VG_HIP(hipMalloc(reinterpret_cast<void **>(&idx->d_flat_stats), 2 * sizeof(unsigned long long)));
-        VG_HIP(hipMemsetAsync(idx->d_flat_stats, 0, 2 * sizeof(unsigned long long), st));
-    }
-    {
-        int64_t cap = idx->rows_cap;
-        VG_TRY(vg::grow_rows(&idx->d_norms, &cap, n_old, n_new, [](int64_t r) { return static_cast<size_t>(r) * 4; }, st));
-        int64_t cap_v = idx->rows_cap;
-        VG_TRY(vg::grow_rows(&idx->d_vectors, &cap_v, n_old, n_new,
-                             [&](int64_t r) { return static_cast<size_t>(r) * dim * 4; }, st));
-        idx->rows_cap = std::min(cap, cap_v);
-    }
-    VG_HIP(hipMemcpyAsync(idx->d_vectors + n_old * dim, in.ptr, static_cast<size_t>(count) * dim * 4, hipMemcpyDeviceToDevice, st));
-    VG_TRY(vg::append_row_norms(idx, n_old, n_new, st));
-    if (idx->d_vectors_bf16) {
-        const int64_t bd = idx->vectors_bf16_dim;
-        VG_TRY(vg::grow_rows(&idx->d_vectors_bf16, &idx->bf16_cap, n_old, n_new,
-                             [&](int64_t r) { return static_cast<size_t>(r) * bd * 2; }, st));
-        VG_TRY(vg::append_bf16_rows(idx, n_old, n_new, st));
-    }
+    VG_TRY(vg::append_index_rows(idx, in.ptr, count, st));
     if (idx->d_hnsw_tomb) {  // the new rows are live
         VG_TRY(vg::grow_rows(&idx->d_hnsw_tomb, &idx->tomb_cap, n_old, n_new,
                              [](int64_t r) { return static_cast<size_t>((r + 7) / 8); }, st));

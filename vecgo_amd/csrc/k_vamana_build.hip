@@ -13,7 +13,7 @@
 //                           a visited bitmap of n bits per node in HBM.
 //   2. vb_prune_kernel      one workgroup per node: robustPrune over the search's l results and the old list.
 //   3. vb_write_kernel      the new lists into the graph; one back-edge record per (node, slot).
-//   4. the records are grouped by target (vg_group_records.hpp, vb_fill_kernel); vb_link_kernel: one workgroup per target sorts its
+//   4. the records are grouped by target (vg_group_records.hpp); vb_link_kernel: one workgroup per target sorts its
 //      records by record index (= (source, slot) order) and applies addBackEdge to its list in LDS.
 // Every distance is the reference's pair kernel in its summation order (vg_exact.hpp, distance.Provider).
 #include <algorithm>
@@ -26,6 +26,7 @@
 #include "vg_group_records.hpp"
 #include "vg_internal.hpp"
 #include "vg_search.hpp"
+#include "vg_vamana_common.hpp"
 
 namespace vg {
 
@@ -36,37 +37,6 @@ constexpr int kVbThreads = 256;
 constexpr uint32_t kVbExpanded = 0x80000000u;  // pool entries: bit 31 of the id (ids < 2^31) = expanded
 // purpose constant of the initial graph's draws: rng_u64(seed, node, kVamanaInitPurpose, t) (header)
 constexpr uint64_t kVamanaInitPurpose = 0x56414D414E41ull;  // "VAMANA"
-
-__host__ __device__ inline uint64_t vb_splitmix64(uint64_t x)
-{
-    x += 0x9e3779b97f4a7c15ULL;
-    x = (x ^ (x >> 30)) * 0xbf58476d1ce4e5b9ULL;
-    x = (x ^ (x >> 27)) * 0x94d049bb133111ebULL;
-    return x ^ (x >> 31);
-}
-// vgo_rng_u64 (the oracle's counter RNG)
-__host__ __device__ inline uint64_t vb_rng_u64(uint64_t seed, uint64_t a, uint64_t b, uint64_t c)
-{
-    uint64_t h = vb_splitmix64(seed);
-    h = vb_splitmix64(h ^ a);
-    h = vb_splitmix64(h ^ b);
-    return vb_splitmix64(h ^ c);
-}
-
-// canonical (distance, id) key: -0 -> +0, every NaN -> the positive quiet NaN (above +Inf)
-__device__ __forceinline__ uint64_t vb_key(float d, uint32_t id)
-{
-    uint32_t u = __float_as_uint(d);
-    if (d != d) u = 0x7FC00000u;
-    else if (d == 0.0f) u = 0u;
-    return make_key(__uint_as_float(u), id, false);
-}
-
-// distance.Provider(metric)(a, b): SquaredL2 or Dot in the pair kernel's order, all 16 lanes of a group
-__device__ __forceinline__ float vb_pair(const float *a, const float *b, int dim, bool dot, Sub16 sub)
-{
-    return dot ? exact_pair16<true, kPair>(a, b, dim, sub) : exact_pair16<false, kPair>(a, b, dim, sub);
-}
 
 // ---- centroid, entry point, initial graph ------------------------------------------------------------
 __global__ void vb_centroid_kernel(const float *__restrict__ base, int64_t n, int dim, float *__restrict__ c)
@@ -295,17 +265,7 @@ __global__ void vb_write_kernel(const uint32_t *__restrict__ lists, int64_t coun
 
 // ---- 4. back edges -----------------------------------------------------------------------------------
 // records: rec[i] = target of record i (VG_INVALID_ID = none); record i = (source node0 + i / r, slot i % r); grouped by
-// target: vg_group_records.hpp
-__global__ void vb_fill_kernel(const uint32_t *__restrict__ rec, int64_t nrec, const uint32_t *__restrict__ roff,
-                               int32_t *__restrict__ rfill, uint32_t *__restrict__ srt)
-{
-    const int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-    if (i >= nrec) return;
-    const uint32_t t = rec[i];
-    if (t == VG_INVALID_ID) return;
-    srt[roff[t] + static_cast<uint32_t>(atomicAdd(&rfill[t], 1))] = static_cast<uint32_t>(i);
-}
-
+// target (vg_group_records.hpp), the record's index as its payload (vg_vamana_common.hpp)
 // One workgroup per target: its records sorted by index (= (source, slot) order; the fill wrote them in any order),
 // then addBackEdge(target, source) for each: nothing if the source is listed, else append, and robustPrune(target,
 // list, r, alpha) once the list is longer than r.  LDS: the records (np2 of them, dynamic), the list.
@@ -374,13 +334,6 @@ __global__ __launch_bounds__(kVbThreads) void vb_link_kernel(const float *__rest
         rcnt[t] = 0;
         rfill[t] = 0;
     }
-}
-
-static int next_pow2(int x)
-{
-    int p = 1;
-    while (p < x) p <<= 1;
-    return p;
 }
 
 // r, l, alpha of 0 become NewWriter's defaults (writer.go:84-95); then every refusal vg_vamana_build makes before it allocates
@@ -517,7 +470,7 @@ VG_API int32_t vg_vamana_build(vg_index *idx, int32_t r, int32_t l, float alpha,
                 const int64_t nrec = b * r;
                 const int64_t max_work = std::min(nrec, n);
                 VG_TRY(vg::group_count_offsets(nl.p, nrec, max_work, rcnt.p, work.p, roff.p, ctr.p, st));
-                VG_LAUNCH(vg::vb_fill_kernel, dim3(static_cast<unsigned>((nrec + 255) / 256)), dim3(256), 0, st, nl.p, nrec,
+                VG_LAUNCH(vg::group_fill_index_kernel, dim3(static_cast<unsigned>((nrec + 255) / 256)), dim3(256), 0, st, nl.p, nrec,
                           roff.p, rfill.p, srt.p);
                 VG_LAUNCH(vg::vb_link_kernel, dim3(static_cast<unsigned>(max_work)), dim3(vg::kVbThreads), link_lds, st,
                           base, dim, dot, r, a, t0, g.p, work.p, ctr.p, rcnt.p, rfill.p, roff.p, srt.p);
@@ -529,6 +482,7 @@ VG_API int32_t vg_vamana_build(vg_index *idx, int32_t r, int32_t l, float alpha,
     VG_HIP(hipStreamSynchronize(st));
     if (idx->d_vamana) (void)hipFree(idx->d_vamana);
     idx->d_vamana = g.release();
+    idx->vamana_cap = 0;
     idx->vamana_r = r;
     idx->vamana_entry = entry;
     return VG_OK;

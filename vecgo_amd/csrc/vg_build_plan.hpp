@@ -1,7 +1,7 @@
 // vg_build_plan.hpp — what the graph builders work out on the host before the first kernel: the level of every new
 // node, where its upper rows go, the batch schedule and the (node, level) pairs of every batch.  All of it follows
 // from the ids alone (ApplyInsert's ids are the row numbers, the levels a hash of them), so it is known up front.
-// Plain C++: no HIP, the host test program includes it.
+// Plain C++: no HIP, the host test program includes it (the counter RNG alone is also a device function under hipcc).
 #pragma once
 
 #include <algorithm>
@@ -9,7 +9,29 @@
 #include <cstdint>
 #include <vector>
 
+#if defined(__HIPCC__)
+#define VG_HOST_DEVICE __host__ __device__
+#else
+#define VG_HOST_DEVICE
+#endif
+
 namespace vg {
+
+VG_HOST_DEVICE inline uint64_t vb_splitmix64(uint64_t x)
+{
+    x += 0x9e3779b97f4a7c15ULL;
+    x = (x ^ (x >> 30)) * 0xbf58476d1ce4e5b9ULL;
+    x = (x ^ (x >> 27)) * 0x94d049bb133111ebULL;
+    return x ^ (x >> 31);
+}
+// vgo_rng_u64 (the oracle's counter RNG): the Vamana build's initial graph, the FreshVamana insert's entry-point draws
+VG_HOST_DEVICE inline uint64_t vb_rng_u64(uint64_t seed, uint64_t a, uint64_t b, uint64_t c)
+{
+    uint64_t h = vb_splitmix64(seed);
+    h = vb_splitmix64(h ^ a);
+    h = vb_splitmix64(h ^ b);
+    return vb_splitmix64(h ^ c);
+}
 
 // layerForApplyInsert (hnsw.go:2103-2116), layerMultiplier = 1 / ln(M) (hnsw.go:218)
 inline int32_t level_for_id(uint64_t id, double mult)
@@ -30,6 +52,19 @@ inline int32_t level_for_id(uint64_t id, double mult)
 inline int64_t next_batch(int64_t done, int64_t end, int64_t max_batch, int64_t growth_div)
 {
     return std::min(std::max<int64_t>(1, std::min(done / growth_div, max_batch)), end - done);
+}
+
+// purpose constant of the FreshVamana entry-point draws: rng_u64(seed, count, kFreshEntryPurpose, 0) (header, vg_vamana_insert)
+constexpr uint64_t kFreshEntryPurpose = 0x4652455348ull;  // "FRESH"
+
+// maybeUpdateEntryPoint (fresh_vamana.go:795-801) after the insert that made the graph `count` nodes: below 100 always,
+// at every multiple of 500 with probability 0.1 (the draw: the top 24 bits of the counter RNG as a float32 in [0, 1))
+inline bool fresh_entry_moves(int64_t count, uint64_t seed)
+{
+    if (count < 100) return true;
+    if (count % 500 != 0) return false;
+    const float u = static_cast<float>(vb_rng_u64(seed, static_cast<uint64_t>(count), kFreshEntryPurpose, 0) >> 40) * (1.0f / 16777216.0f);
+    return u < 0.1f;
 }
 
 // One batch of the schedule: nodes t0 .. t0+size-1, their (node, level) pairs, the entry point and top level
@@ -107,6 +142,31 @@ inline HnswBuildPlan plan_hnsw_build(int64_t n_old, int64_t count, int m, int64_
         }
         bt.npairs = p.pair_base[done + bt.size - n_old] - p.pair_base[done - n_old];
         p.max_pairs = std::max(p.max_pairs, bt.npairs);
+        p.max_b = std::max(p.max_b, bt.size);
+        p.batches.push_back(bt);
+        done += bt.size;
+    }
+    return p;
+}
+
+// vg_vamana_insert's schedule for nodes n_old .. n_old+count-1: the batches (npairs, cur_top unused) with the entry point
+// every node of a batch starts from, and the entry point after the last.  An empty graph: row 0 becomes the entry point,
+// with no links, and is no batch's node.
+struct FreshInsertPlan {
+    std::vector<BuildBatch> batches;
+    int64_t max_b = 1;
+    uint32_t entry = 0;
+};
+inline FreshInsertPlan plan_fresh_insert(int64_t n_old, int64_t count, int64_t max_batch, int64_t growth_div, uint64_t seed,
+                                         uint32_t old_entry)
+{
+    FreshInsertPlan p;
+    p.entry = n_old ? old_entry : 0;
+    const int64_t end = n_old + count;
+    for (int64_t done = n_old ? n_old : 1; done < end;) {
+        const BuildBatch bt{done, next_batch(done, end, max_batch, growth_div), 0, p.entry, 0};
+        for (int64_t t = done; t < done + bt.size; t++)
+            if (fresh_entry_moves(t + 1, seed)) p.entry = static_cast<uint32_t>(t);
         p.max_b = std::max(p.max_b, bt.size);
         p.batches.push_back(bt);
         done += bt.size;

@@ -499,6 +499,7 @@ struct vg_index {
     int64_t rows_cap = 0, bf16_cap = 0, l0_cap = 0, tomb_cap = 0;
     // Vamana adjacency
     uint32_t *d_vamana = nullptr;      // n*r
+    int64_t vamana_cap = 0;            // rows d_vamana has room for: vg_vamana_insert grows it by capacity; 0 = exactly n
     int32_t vamana_r = 0;
     uint32_t vamana_entry = 0;
     // PQ codes in the reference's row-major layout (random access by node id in graph search)
@@ -532,6 +533,20 @@ inline const char *held_segment_state(const vg_index *idx)
            : (idx->d_rq_tiles || idx->d_rq_rows) ? "RaBitQ codes"
            : idx->d_centroids                    ? "IVF partitions"
            : idx->d_vamana                       ? "a Vamana graph"
+           : idx->sq_nom.rows                    ? "an SQ8 nomination image"
+           : idx->pq_nom.rows                    ? "a PQ nomination image"
+                                                 : nullptr;
+}
+// The same for the streaming Vamana insert (vg_vamana_insert): what its new rows would lack, or null
+inline const char *held_fresh_state(const vg_index *idx)
+{
+    return (idx->d_pq_tiles || idx->d_pq_rows)   ? "PQ codes"
+           : idx->d_sq_tiles                     ? "SQ8 codes"
+           : idx->d_int4_rows                    ? "INT4 codes"
+           : (idx->d_rq_tiles || idx->d_rq_rows) ? "RaBitQ codes"
+           : idx->d_centroids                    ? "IVF partitions"
+           : idx->d_hnsw_l0                      ? "an HNSW graph"
+           : idx->d_hnsw_tomb                    ? "HNSW tombstones"
            : idx->sq_nom.rows                    ? "an SQ8 nomination image"
            : idx->pq_nom.rows                    ? "a PQ nomination image"
                                                  : nullptr;
