@@ -1119,7 +1119,15 @@ int32_t vg_search_hnsw_brute(vg_index *idx, const float *queries, int64_t nq, in
  * shards, one per GPU: lists[l] holds nq*k (id, score) results of shard l, ids local to the
  * shard; id_offsets[l] (may be NULL = all 0) is added to make them global.  Output: the k best
  * of the union per query, best first.  metric picks the direction (L2 ascending, Dot/Cosine
- * descending).  ids_in/scores_in are [lists][nq][k] contiguous. */
+ * descending).  ids_in/scores_in are [lists][nq][k] contiguous; every list best first, unused slots
+ * VG_INVALID_ID at its end.  k <= 1024.
+ * A candidate that repeats across lists — the same score and the same GLOBAL id in two lists: replicated
+ * or overlapping shards with id_offsets NULL, or offsets that make two ids coincide — is kept as often as
+ * it is listed, the copies adjacent, as the engine's heap keeps candidates that differ only in SegmentID;
+ * the merge does not deduplicate.  Zero scores of opposite sign are equal (InternalCandidateBetter
+ * compares floats): among them the lower global id comes first, whatever the sign, and every score is
+ * returned with the sign it came with (see "NaN scores": such a query is answered by the fan-in replay).
+ * id_offsets are expected to ascend with the list, so that (SegmentID, RowID) orders like the global id. */
 int32_t vg_merge_topk(vg_ctx *ctx, const uint32_t *ids_in, const float *scores_in, int32_t lists,
                       int64_t nq, int32_t k, int32_t metric, const uint32_t *id_offsets,
                       uint32_t *ids, float *scores, void *stream);
@@ -1185,7 +1193,8 @@ int32_t vg_comm_all_gather_topk(vg_comm *comm, const uint32_t *local_ids, const 
  * to everything) are replayed; with more than 12 partitions AND NaN centroid distances the full sort is pdqsort proper, whose
  * order is not restated (NaN distances sort last).  vg_merge_topk / _packed (and vg_comm_all_gather_topk through them) replay
  * the engine's fan-in (engine/search.go:904-918: every list from its last valid entry to its first into one heap with
- * TryPushBounded, then popped) for a query whose lists hold a NaN.  Not covered: vg_rerank — the order in which the engine hands
+ * TryPushBounded, then popped) for a query whose lists hold a NaN.  The same fan-in replay also answers a query whose lists hold
+ * a -0.0 score: the key orders -0.0 strictly before +0.0, the reference's float comparison ties them.  Not covered: vg_rerank — the order in which the engine hands
  * it the candidates comes out of an unstable sort (search.go:921), so there is no defined outcome to reproduce; NaN scores
  * order as the largest keys there. */
 

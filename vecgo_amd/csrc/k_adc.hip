@@ -482,11 +482,15 @@ __global__ __launch_bounds__(kMergeThreads) void topk_merge_kernel(
     const int c = cnt;
     int have;
     if (c <= 1024) {
-        // brute-force rank among the survivors (keys are unique)
+        // brute-force rank among the survivors; a candidate listed twice (the same score and global id in two lists) is two
+        // equal keys: the buffer position breaks the tie, so they take consecutive ranks, as the sort below places them
         for (int i = tid; i < c; i += kMergeThreads) {
             const uint64_t e = buf[i];
             int rank = 0;
-            for (int j = 0; j < c; j++) rank += (buf[j] < e) ? 1 : 0;
+            for (int j = 0; j < c; j++) {
+                const uint64_t o = buf[j];
+                rank += (o < e || (o == e && j < i)) ? 1 : 0;
+            }
             if (rank < k) {
                 oid[rank] = key_row(e);
                 osc[rank] = key_score(e, descending);
@@ -921,12 +925,15 @@ __global__ __launch_bounds__(64) void merge_nan_replay_kernel(const uint32_t *__
     CItem *heap = reinterpret_cast<CItem *>(merge_lds);
     const int64_t q = blockIdx.x;
     const int lane = threadIdx.x;
+    // a NaN, or a -0.0 score: InternalCandidateBetter compares floats, for which -0.0 == +0.0 (the lower global id wins),
+    // while the key orders -0.0 strictly first; the replay below compares floats.  (The library's own searches emit one sign of
+    // zero per metric; a caller's lists may hold both.)
     bool nan = false;
     for (int t = lane; t < lists * k; t += 64) {
         const int64_t src = static_cast<int64_t>(t / k) * list_stride + q * k + t % k;
         if (ids_in[src] != VG_INVALID_ID) {
             const float v = scores_in[src];
-            nan = nan || v != v;
+            nan = nan || v != v || __float_as_uint(v) == 0x80000000u;
         }
     }
     if (!__any(nan)) return;
@@ -1028,7 +1035,7 @@ static int32_t merge_topk_impl(vg_ctx *ctx, const uint32_t *ids_in, const float 
                            0, st, i_in.ptr, s_in.ptr, lists, nq, k, list_stride, desc, offs.ptr, keys);
     }
     VG_TRY(vg::launch_topk_merge(keys, nq, nl, k, desc, oid.ptr, osc.ptr, st));
-    if (lists > 0 && !vg::hook(vg::kHookNoCandReplay))  // queries with a NaN score in a list: the engine's heap, operation by operation
+    if (lists > 0 && !vg::hook(vg::kHookNoCandReplay))  // queries with a NaN or a -0.0 score in a list: the engine's heap, operation by operation
         VG_LAUNCH(vg::merge_nan_replay_kernel, dim3(static_cast<unsigned>(nq)), dim3(64), sizeof(uint64_t) * (static_cast<size_t>(k) + 4), st,
                   i_in.ptr, s_in.ptr, lists, nq, k, list_stride, desc, offs.ptr, oid.ptr, osc.ptr);
     VG_TRY(oid.finish());
