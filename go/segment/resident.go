@@ -225,6 +225,23 @@ func (r *Resident) InsertVamana(rows []float32, R, L int, alpha float32, deleted
 	return nil
 }
 
+// ConsolidateVamana: FreshVamana.consolidate (diskann/fresh_vamana.go:803-867) on the resident Vamana graph
+// (vg_vamana_consolidate): every live node that lists a deleted one gets a new list from a fresh search and prune; no
+// reverse edges, the entry point stays.  L, alpha of 0 take FreshDefault*.  deleted as for InsertVamana, over all r.rows
+// rows; nil = nothing to do.  The host keeps the bitmap and the trigger (more than a tenth of the nodes deleted).
+func (r *Resident) ConsolidateVamana(L int, alpha float32, deleted []byte) error {
+	var dp *C.uint8_t
+	if deleted != nil {
+		if len(deleted) < (r.rows+7)/8 {
+			return fmt.Errorf("segment: ConsolidateVamana: deleted holds %d bytes, %d needed", len(deleted), (r.rows+7)/8)
+		}
+		if len(deleted) > 0 {
+			dp = bp(deleted)
+		}
+	}
+	return hipctx.Err(int32(C.vg_vamana_consolidate(r.h, C.int32_t(L), C.float(alpha), dp, 8192, nil, nil)))
+}
+
 // ReorderVamanaBFS: diskann.Writer.reorderBFS (diskann/reorder.go:14-157) on the resident graph and every per-row array
 // it holds.  perm[new] = old; invPerm[old] = new is the writer's addOrderToFinalRow.  The caller permutes what the GPU
 // never held (ids, metadata, payloads) with perm.

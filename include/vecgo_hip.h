@@ -44,7 +44,7 @@
  *     These WAIT for `stream` inside the call, device buffers or not, because the host
  *     needs a value the device computes: every *_train (the solves and convergence tests
  *     are the host's); the builders and maintenance calls (vg_hnsw_build / _insert /
- *     _compact, vg_vamana_build, vg_vamana_insert, vg_vamana_reorder_bfs, vg_flat_build, vg_diskann_build,
+ *     _compact, vg_vamana_build, vg_vamana_insert, vg_vamana_consolidate, vg_vamana_reorder_bfs, vg_flat_build, vg_diskann_build,
  *     vg_segment_*); vg_index_set_* and vg_index_enable_* (storage is replaced; the
  *     caller's buffer is free again at return); every getter; vg_search_hnsw_brute (reads
  *     its filter's population count and redo flags back); vg_search_sq8 and
@@ -104,7 +104,8 @@ extern "C" {
  *  vg_diskann_build, vg_segment_diskann_image_size and vg_segment_write_diskann, found by symbol lookup.  Likewise the
  *  threshold search over coded / partitioned flat segments: vg_search_flat_probed_threshold and
  *  vg_segment_search_threshold, found by symbol lookup.  Likewise the streaming Vamana index: vg_vamana_insert and
- *  vg_search_vamana_fresh, found by symbol lookup. */
+ *  vg_search_vamana_fresh, found by symbol lookup; and its delete path, vg_vamana_consolidate (with its caller-allocated
+ *  vg_vamana_consolidate_stats), the same way. */
 #define VG_ABI_MINOR 13
 #define VG_INVALID_ID 0xFFFFFFFFu
 #define VG_STREAM_LEGACY ((void *)1) /* == hipStreamLegacy */
@@ -498,6 +499,49 @@ int32_t vg_vamana_build(vg_index *idx, int32_t r, int32_t l, float alpha, const 
  *     count = 0 changes nothing.  (Present when the symbol is: see VG_ABI_MINOR.) */
 int32_t vg_vamana_insert(vg_index *idx, const float *rows, int64_t count, int32_t r, int32_t l, float alpha,
                          const uint8_t *deleted, uint64_t seed, int32_t max_batch, int32_t growth_div, void *stream);
+/* FreshVamana.consolidate (internal/segment/diskann/fresh_vamana.go:803-867) on the index's Vamana graph: every live node
+ * that lists a deleted node gets a new list from a fresh search and prune, so that afterwards no live node lists a deleted
+ * one.  The streaming index's delete path; the reference starts it once more than a tenth of the nodes are deleted
+ * (:25-26, :261-266): that trigger, like the bitmap, is the caller's.
+ *   Parameters: r is the graph's own.  l, alpha of 0 take FreshDefaultL / FreshDefaultAlpha: 100, 1.2.  deleted: bit i of
+ *     byte i/8 = node i is deleted, ceil(n/8) bytes, host or device, any byte alignment; NULL = nothing is deleted: VG_OK,
+ *     stats all zero, nothing written.  stats may be NULL and is written only on VG_OK.
+ *   Repair set: the live nodes with a deleted id in any non-empty slot of their list, wherever the slot sits (VG_INVALID_ID
+ *     slots are skipped as everywhere else), in ascending id order (:821-847).  A repair rewrites only the node's own list,
+ *     and the test for a node reads only that list: the set is fixed before the first repair, by one pass over the graph as
+ *     it stands at the call; only the walks depend on the order of the repairs.
+ *   Per node i of the set (:859-862), steps 1 and 2 of vg_vamana_insert, word for word the same rules:
+ *   1. results = searchCandidatesLocked(row i, entry, l): the same two lists with caps 2l and l, the same stop test, the
+ *      (distance, arrival) order with -0 equal to +0, a NaN after +Inf in arrival order and greater than any number in the
+ *      stop test; deleted nodes are walked through and stay out of results.  The node searches for its own row, so it
+ *      normally meets itself at distance 0.
+ *   2. list(i) = robustPruneLocked(i, results, r, alpha): i itself and deleted ids are skipped, the fp32 alpha * c.dist
+ *      product, stops at r kept.  The new list is a dense prefix padded with VG_INVALID_ID, and may be shorter than the old
+ *      one, or empty.
+ *   No reverse edges are added and the entry point is never moved, even when it is itself deleted (walks still start there
+ *     and pass through it).  Hence repaired lists usually come out shorter and recall can drop: the reference's behaviour,
+ *     restated, not improved on.
+ *   Batches: the repair set is cut into batches of max_batch nodes in id order; every node of a batch walks the graph as it
+ *     stood when the batch began, then the batch's lists are written.  max_batch = 1 is the reference's loop.  There is no
+ *     growth schedule: the graph does not grow.
+ *   Idempotent: a repaired list holds no deleted id, a list that was not repaired held none; a second call with the same
+ *     bitmap repairs nothing and changes no bit of the graph.
+ *   Unchanged: n, the rows, the entry point (deleted or not), every list of a deleted node, and every list of a live node
+ *     that named no deleted id, bit for bit, holes included.  No id is released.  Codes, partitions, nomination images and
+ *     HNSW state on the index are neither needed nor touched (nothing is appended: none of vg_vamana_insert's segment-state
+ *     refusals).  The visited bitmaps of a launch stay under 1/16 of device memory, as the insert's do.
+ *   Refusals, in this order, nothing changed: NULL index VG_ERR_INVALID_ARG; (n == 0: VG_OK, stats zero, :815-818); no fp32
+ *     rows or no Vamana graph VG_ERR_NOT_READY; Hamming, the graph's r outside 1..64, l outside 1..1024, max_batch > 16384
+ *     (l result keys of scratch per batch node: 128 MiB at l = 1024) VG_ERR_UNSUPPORTED; max_batch < 1 VG_ERR_INVALID_ARG.
+ *     (Present when the symbol is: see VG_ABI_MINOR.) */
+typedef struct vg_vamana_consolidate_stats { /* caller-allocated, may be NULL */
+    int64_t repaired_nodes; /* live nodes with at least one deleted id in their list */
+    int64_t dropped_links;  /* slots of those lists that named a deleted id (an id listed twice counts twice) */
+    int64_t links_before;   /* non-empty slots of the repaired nodes' lists before the call */
+    int64_t links_after;    /* ... and after */
+} vg_vamana_consolidate_stats;
+int32_t vg_vamana_consolidate(vg_index *idx, int32_t l, float alpha, const uint8_t *deleted, int32_t max_batch,
+                              vg_vamana_consolidate_stats *stats, void *stream);
 /* The index's Vamana graph in vg_index_set_vamana_graph's layout: r, entry point, graph[n*r] (host or device);
  * graph NULL = the sizes only.  (VG_ABI_MINOR 12.) */
 int32_t vg_index_get_vamana_graph(const vg_index *idx, int32_t *r, uint32_t *entry_point, uint32_t *graph,

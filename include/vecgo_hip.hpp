@@ -694,6 +694,14 @@ public:
     {
         check(vg_vamana_insert(h_, rows, count, r, l, alpha, deleted, seed, maxBatch, growthDiv, nullptr));
     }
+    // FreshVamana.consolidate (fresh_vamana.go:803-867) under the caller's deleted bits (vg_vamana_consolidate; bit i of byte
+    // i/8, host or device, null = none): every live node that lists a deleted one is searched for and pruned again
+    vg_vamana_consolidate_stats ConsolidateVamana(const uint8_t *deleted, int l = 100, float alpha = 1.2f, int maxBatch = 8192)
+    {
+        vg_vamana_consolidate_stats stats{};
+        check(vg_vamana_consolidate(h_, l, alpha, deleted, maxBatch, &stats, nullptr));
+        return stats;
+    }
     // diskann.Writer.reorderBFS (reorder.go:14-157): the graph and every per-row array into BFS order; perm[new] = old,
     // invPerm[old] = new (either may be null; host or device)
     void ReorderVamanaBFS(uint32_t *perm, uint32_t *invPerm) { check(vg_vamana_reorder_bfs(h_, perm, invPerm, nullptr)); }

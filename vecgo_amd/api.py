@@ -1102,6 +1102,27 @@ class Index:
                                          C.c_uint64(seed), C.c_int32(max_batch), C.c_int32(growth_div), _stream_ptr(stream)))
         self.n += count
 
+    def consolidate_vamana(self, deleted, l=100, alpha=1.2, max_batch=8192, stream=None):
+        """FreshVamana.consolidate on the GPU (vg_vamana_consolidate; the rules are the header's): every live node whose
+        list names a deleted node is searched for and pruned again (batches of max_batch such nodes in id order; max_batch=1
+        is the reference's loop); no reverse edges, the entry point stays.  deleted: bool[n] / packed bits, or None (nothing
+        to do).  Returns the counters {repaired_nodes, dropped_links, links_before, links_after}."""
+        if isinstance(l, bool) or not isinstance(l, (int, np.integer)):
+            raise TypeError(f"consolidate_vamana: l must be an int, got {type(l).__name__}")
+        if isinstance(max_batch, bool) or not isinstance(max_batch, (int, np.integer)):
+            raise TypeError(f"consolidate_vamana: max_batch must be an int, got {type(max_batch).__name__}")
+        if isinstance(alpha, bool) or not isinstance(alpha, (int, float, np.integer, np.floating)):
+            raise TypeError(f"consolidate_vamana: alpha must be a number, got {type(alpha).__name__}")
+        if l < 0 or l > 1024:
+            raise ValueError(f"consolidate_vamana: l must be in 0..1024 (0 = 100), got {l}")
+        if max_batch < 1 or max_batch > 16384:
+            raise ValueError(f"consolidate_vamana: max_batch must be in 1..16384, got {max_batch}")
+        d, pd, _ = (None, None, 0) if deleted is None or self.n == 0 else self._packed_mask(deleted, 1, "consolidate_vamana")
+        stats = (C.c_int64 * 4)()
+        check(self._lib.vg_vamana_consolidate(self._h, C.c_int32(l), C.c_float(alpha), pd, C.c_int32(max_batch), stats,
+                                              _stream_ptr(stream)))
+        return dict(zip(("repaired_nodes", "dropped_links", "links_before", "links_after"), (int(v) for v in stats)))
+
     def search_vamana_fresh(self, queries, k, l=100, deleted=None, mask=None, stream=None):
         """FreshVamana.Search, and with a mask SearchWithFilter, on the GPU (vg_search_vamana_fresh): l = the index's search
         list size; deleted: bool[n] / packed bits or None; mask: as search_vamana_filtered's.  Returns (ids [nq, k], scores,

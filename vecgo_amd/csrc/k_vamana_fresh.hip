@@ -18,9 +18,13 @@
 //                             reverse-edge record per slot.
 //   3. the records are grouped by target (vg_group_records.hpp); fv_link_kernel: one workgroup per target sorts its records
 //      by record index (= (source, slot) order) and applies addReverseEdge to its list in LDS.
+// FreshVamana.consolidate (:803-867, vg_vamana_consolidate) is steps 1 and 2 for nodes already in the graph, no reverse edges:
+//   fv_mark_kernel            one pass over the n x r table: a need-bit per live node that lists a deleted id, the counters.
+//   per batch of the marked nodes (the host's ascending id list): fv_walk_kernel<true> and fv_prune_kernel over that list.
 // Every distance is the reference's pair kernel in its summation order (vg_exact.hpp, distance.Provider).
 #include <algorithm>
 #include <cmath>
+#include <vector>
 
 #include "vg_build_plan.hpp"
 #include "vg_device.hpp"
@@ -79,15 +83,17 @@ __device__ __forceinline__ int fv_merge(const uint64_t *src, int len, const uint
 }
 
 // ---- 1. searchCandidatesLocked / greedySearch ----------------------------------------------------------
-// One wavefront per searching node or query blockIdx.x, whose vector is queries + blockIdx.x * dim.  INSERT: `results`
+// One wavefront per searching node or query blockIdx.x, whose vector is queries + blockIdx.x * dim, or with qids (the
+// consolidate's repair list) row qids[blockIdx.x] of base.  INSERT: `results`
 // leaves deleted nodes out and goes to res (ef keys, kKeyMax after the last).  Otherwise `results` takes every node and
 // its first k entries that are neither deleted nor masked out go to ids / scores / counts.
 // LDS (dynamic): candidates 2 x 2 ef keys, results 2 x ef keys, the fresh keys ranked for either list 2 x 64.
 template <bool INSERT>
 __global__ __launch_bounds__(64) void fv_walk_kernel(const float *__restrict__ base, int dim, bool dot,
                                                       const uint32_t *__restrict__ graph, int r, int ef, uint32_t entry,
-                                                      const float *__restrict__ queries, const uint8_t *__restrict__ deleted,
-                                                      int64_t n_del, uint32_t *__restrict__ vis, int64_t vis_words,
+                                                      const float *__restrict__ queries, const uint32_t *__restrict__ qids,
+                                                      const uint8_t *__restrict__ deleted, int64_t n_del,
+                                                      uint32_t *__restrict__ vis, int64_t vis_words,
                                                       uint64_t *__restrict__ res, int k, const uint8_t *__restrict__ mask,
                                                       int64_t mask_stride, float pad_score, uint32_t *__restrict__ ids,
                                                       float *__restrict__ scores, int32_t *__restrict__ counts)
@@ -101,7 +107,7 @@ __global__ __launch_bounds__(64) void fv_walk_kernel(const float *__restrict__ b
     const Sub16 sub = Sub16::make(lane);
     const int grp = lane >> 4;
     const int64_t b = blockIdx.x;
-    const float *q = queries + b * dim;
+    const float *q = qids ? base + static_cast<int64_t>(qids[b]) * dim : queries + b * dim;
     uint32_t *vw = vis + b * vis_words;
     int chead = 0, clen = 1, rlen = 0;
     {
@@ -243,27 +249,29 @@ __device__ int fv_select(const float *__restrict__ base, int dim, bool dot, cons
     return *nkept;
 }
 
-// list(node0 + blockIdx.x) = robustPrune(node, its search results, r, alpha), into the graph and (one reverse-edge record
-// per slot) into nl
+// list(node) = robustPrune(node, its search results, r, alpha) for node = node0 + blockIdx.x, or nodes[blockIdx.x] with a
+// list of nodes, into the graph; with nl, one reverse-edge record per slot; with links, the kept ids are counted
 __global__ __launch_bounds__(kFvThreads) void fv_prune_kernel(const float *__restrict__ base, int dim, bool dot, int r, int l,
-                                                              float alpha, int64_t node0, const uint64_t *__restrict__ res,
-                                                              const uint8_t *__restrict__ deleted, int64_t n_del,
-                                                              uint32_t *__restrict__ graph, uint32_t *__restrict__ nl)
+                                                              float alpha, int64_t node0, const uint32_t *__restrict__ nodes,
+                                                              const uint64_t *__restrict__ res, const uint8_t *__restrict__ deleted,
+                                                              int64_t n_del, uint32_t *__restrict__ graph, uint32_t *__restrict__ nl,
+                                                              unsigned long long *__restrict__ links)
 {
     __shared__ uint64_t ck[kFvMaxL];
     __shared__ uint32_t kept[kFvMaxR];
     __shared__ int flag, nkept;
     const int tid = threadIdx.x;
     const int64_t b = blockIdx.x;
-    const uint32_t node = static_cast<uint32_t>(node0 + b);
+    const uint32_t node = nodes ? nodes[b] : static_cast<uint32_t>(node0 + b);
     for (int i = tid; i < l; i += kFvThreads) ck[i] = res[b * l + i];
     __syncthreads();
     const int nk = fv_select(base, dim, dot, ck, l, node, r, alpha, deleted, n_del, kept, &flag, &nkept);
     for (int i = tid; i < r; i += kFvThreads) {
         const uint32_t v = i < nk ? kept[i] : VG_INVALID_ID;
         graph[static_cast<int64_t>(node) * r + i] = v;
-        nl[b * r + i] = v;
+        if (nl) nl[b * r + i] = v;
     }
+    if (links && tid == 0) atomicAdd(links, static_cast<unsigned long long>(nk));
 }
 
 // ---- 3. addReverseEdgeLocked ---------------------------------------------------------------------------
@@ -352,6 +360,53 @@ __global__ __launch_bounds__(kFvThreads) void fv_link_kernel(const float *__rest
         rcnt[t] = 0;
         rfill[t] = 0;
     }
+}
+
+// ---- 4. consolidate's repair set (fresh_vamana.go:836-847) ---------------------------------------------
+// One pass over the n x r table.  A wavefront owns one word of need = 32 consecutive nodes = one contiguous run of 32 r
+// slots, and reads it 64 lanes at a time: g lanes per node (g = r rounded up to a power of two, at least 2), each lane one
+// slot, 64 / g whole nodes per step.  A live node with a deleted id in any non-empty slot gets its bit; the word is stored
+// once, whole (no atomics, nothing to clear).  ctr[0..3) += such nodes, their slots that name a deleted id, their non-empty
+// slots: summed per wavefront in registers, per workgroup in LDS, then one atomicAdd each per workgroup that found any.
+__global__ __launch_bounds__(kFvThreads) void fv_mark_kernel(const uint32_t *__restrict__ graph, int64_t n, int r, int g,
+                                                             const uint8_t *__restrict__ deleted, uint32_t *__restrict__ need,
+                                                             unsigned long long *__restrict__ ctr)
+{
+    __shared__ unsigned int tot[3];
+    if (threadIdx.x < 3) tot[threadIdx.x] = 0;
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    const int64_t word = static_cast<int64_t>(blockIdx.x) * (kFvThreads / 64) + (threadIdx.x >> 6);
+    if (word * 32 < n) {  // uniform over the wavefront
+        const int per = 64 / g, slot = lane & (g - 1), sub = lane >> __builtin_ctz(g);
+        const uint64_t mine = (g == 64 ? ~0ull : (1ull << g) - 1) << (lane & ~(g - 1));
+        uint32_t bits = 0;
+        unsigned int nodes = 0, dropped = 0, before = 0;
+        for (int s = 0; s < 32; s += per) {
+            const int64_t node = word * 32 + s + sub;
+            uint32_t id = VG_INVALID_ID;
+            if (node < n && slot < r && !fv_deleted(deleted, n, static_cast<uint32_t>(node))) id = graph[node * r + slot];
+            const bool linked = id != VG_INVALID_ID;  // a non-empty slot of a live node
+            const uint64_t dead = __ballot(linked && fv_deleted(deleted, n, id));
+            const bool repair = (dead & mine) != 0;
+            const uint64_t heads = __ballot(repair && slot == 0);  // bit j g = node s + j is to be repaired: folded to bit j
+            const uint64_t fold = __ballot(lane < per && ((heads >> (lane < per ? lane * g : 0)) & 1));
+            bits |= static_cast<uint32_t>(fold) << s;
+            nodes += __popcll(heads);
+            dropped += __popcll(dead);
+            before += __popcll(__ballot(repair && linked));
+        }
+        if (lane == 0) {
+            need[word] = bits;
+            if (nodes) {
+                atomicAdd(&tot[0], nodes);
+                atomicAdd(&tot[1], dropped);
+                atomicAdd(&tot[2], before);
+            }
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x < 3 && tot[threadIdx.x]) atomicAdd(&ctr[threadIdx.x], static_cast<unsigned long long>(tot[threadIdx.x]));
 }
 
 template <bool INSERT>
@@ -448,14 +503,14 @@ VG_API int32_t vg_vamana_insert(vg_index *idx, const float *rows, int64_t count,
                 const int64_t cn = std::min(chunk, b - c0);
                 VG_HIP(hipMemsetAsync(vis, 0, static_cast<size_t>(cn * vis_words) * 4, st));
                 VG_LAUNCH(vg::fv_walk_kernel<true>, dim3(static_cast<unsigned>(cn)), dim3(64), walk_lds, st, base, dim, dot, g, r, l,
-                          bt.entry, base + (t0 + c0) * dim, del.ptr, n_old, vis, vis_words, res + c0 * l, 0, nullptr, int64_t(0),
-                          0.0f, nullptr, nullptr, nullptr);
+                          bt.entry, base + (t0 + c0) * dim, nullptr, del.ptr, n_old, vis, vis_words, res + c0 * l, 0, nullptr,
+                          int64_t(0), 0.0f, nullptr, nullptr, nullptr);
             }
         }
         {
             vg::ProfScope prof(idx->ctx, "vamana_insert_prune", st);
             VG_LAUNCH(vg::fv_prune_kernel, dim3(static_cast<unsigned>(b)), dim3(vg::kFvThreads), 0, st, base, dim, dot, r, l, alpha,
-                      t0, res, del.ptr, n_old, g, nl);
+                      t0, nullptr, res, del.ptr, n_old, g, nl, nullptr);
         }
         {
             vg::ProfScope prof(idx->ctx, "vamana_insert_reverse", st);
@@ -472,6 +527,102 @@ VG_API int32_t vg_vamana_insert(vg_index *idx, const float *rows, int64_t count,
     idx->vamana_r = r;
     idx->vamana_entry = plan.entry;
     idx->n = n_new;
+    return VG_OK;
+}
+
+VG_API int32_t vg_vamana_consolidate(vg_index *idx, int32_t l, float alpha, const uint8_t *deleted, int32_t max_batch,
+                                     vg_vamana_consolidate_stats *stats, void *stream)
+{
+    const char *fn = "vg_vamana_consolidate";
+    const vg_vamana_consolidate_stats none{0, 0, 0, 0};
+    VG_CHECK(idx, VG_ERR_INVALID_ARG, "%s: NULL index", fn);
+    const int64_t n = idx->n;
+    if (n == 0) {  // consolidate returns on an empty index (:815-818)
+        if (stats) *stats = none;
+        return VG_OK;
+    }
+    VG_CHECK(idx->d_vectors && idx->d_vamana, VG_ERR_NOT_READY, "%s: index has no fp32 vectors or no Vamana graph", fn);
+    if (l == 0) l = 100;  // FreshDefaultL / Alpha (fresh_vamana.go:20-24)
+    if (alpha == 0.0f) alpha = 1.2f;
+    const int r = idx->vamana_r;
+    VG_CHECK(idx->metric != VG_METRIC_HAMMING, VG_ERR_UNSUPPORTED, "unsupported metric for float32: Hamming");
+    VG_CHECK(r >= 1 && r <= vg::kFvMaxR, VG_ERR_UNSUPPORTED, "%s: the graph's r=%d must be in 1..%d", fn, r, vg::kFvMaxR);
+    VG_CHECK(l >= 1 && l <= vg::kFvMaxL, VG_ERR_UNSUPPORTED, "%s: l=%d must be in 1..%d", fn, l, vg::kFvMaxL);
+    VG_CHECK(max_batch <= vg::kFvMaxBatch, VG_ERR_UNSUPPORTED, "%s: max_batch=%d must be <= %d", fn, max_batch, vg::kFvMaxBatch);
+    VG_CHECK(max_batch >= 1, VG_ERR_INVALID_ARG, "%s: max_batch=%d must be >= 1", fn, max_batch);
+    if (!deleted) {  // nothing is deleted: nothing to repair
+        if (stats) *stats = none;
+        return VG_OK;
+    }
+    VG_HIP(hipSetDevice(idx->ctx->device));
+    hipStream_t st = vg::pick_stream(idx->ctx, stream);
+    const int dim = idx->dim;
+    const bool dot = idx->metric != VG_METRIC_L2;  // Cosine and Dot: raw Dot, ascending (distance.go:97-106)
+    const float *base = idx->d_vectors;
+    uint32_t *g = idx->d_vamana;
+    vg::DevIn<uint8_t> del;
+    VG_TRY(del.init(deleted, static_cast<size_t>((n + 7) / 8), st, vg::kAnyAlign));
+
+    // ---- per-call scratch on the context arena: the need bits, the repair list (at most n ids), per batch node l result
+    // keys; visited bitmaps for as many searching nodes as fit under the scratch cap, the rest of a batch in further launches
+    const int64_t max_b = std::min<int64_t>(max_batch, n);
+    const int64_t vis_words = (n + 31) / 32;
+    const int64_t chunk = vg::walk_chunk(vg::scratch_cap(idx->ctx), vis_words * 4, max_b);
+    vg::ArenaCall ar(idx->ctx, st);
+    const int a_need = ar.add(static_cast<size_t>(vis_words) * 4), a_rep = ar.add(static_cast<size_t>(n) * 4),
+              a_vis = ar.add(static_cast<size_t>(chunk * vis_words) * 4), a_res = ar.add(static_cast<size_t>(max_b) * l * 8),
+              a_ctr = ar.add(4 * sizeof(unsigned long long));
+    VG_TRY(ar.commit());
+    uint32_t *need = ar.get<uint32_t>(a_need), *d_rep = ar.get<uint32_t>(a_rep), *vis = ar.get<uint32_t>(a_vis);
+    uint64_t *res = ar.get<uint64_t>(a_res);
+    unsigned long long *ctr = ar.get<unsigned long long>(a_ctr);
+
+    // ---- which nodes: fixed before the first repair (a repair rewrites only the node's own list) ----
+    VG_HIP(hipMemsetAsync(ctr, 0, 4 * sizeof(unsigned long long), st));
+    {
+        vg::ProfScope prof(idx->ctx, "vamana_consolidate_mark", st);
+        const int waves = vg::kFvThreads / 64;  // one word of need each
+        VG_LAUNCH(vg::fv_mark_kernel, dim3(static_cast<unsigned>((vis_words + waves - 1) / waves)), dim3(vg::kFvThreads), 0, st, g,
+                  n, r, std::max(2, vg::next_pow2(r)), del.ptr, need, ctr);
+    }
+    std::vector<uint32_t> h_need(static_cast<size_t>(vis_words)), rep;
+    VG_HIP(hipMemcpyAsync(h_need.data(), need, h_need.size() * 4, hipMemcpyDeviceToHost, st));
+    VG_HIP(hipStreamSynchronize(st));  // the host plans the launches from the count
+    for (int64_t w = 0; w < vis_words; w++)
+        for (uint32_t m = h_need[static_cast<size_t>(w)]; m; m &= m - 1)
+            rep.push_back(static_cast<uint32_t>(w * 32 + __builtin_ctz(m)));
+    const int64_t nrep = static_cast<int64_t>(rep.size());
+    if (nrep == 0) {
+        if (stats) *stats = none;
+        return VG_OK;
+    }
+    VG_HIP(hipMemcpyAsync(d_rep, rep.data(), rep.size() * 4, hipMemcpyHostToDevice, st));
+
+    // ---- batches of max_batch marked nodes in id order, each over the graph as it stood when the batch began ----
+    size_t walk_lds = 0;
+    VG_TRY(vg::fv_walk_lds<true>(l, &walk_lds));
+    for (int64_t b0 = 0; b0 < nrep; b0 += max_batch) {
+        const int64_t b = std::min<int64_t>(max_batch, nrep - b0);
+        {
+            vg::ProfScope prof(idx->ctx, "vamana_consolidate_search", st);
+            for (int64_t c0 = 0; c0 < b; c0 += chunk) {
+                const int64_t cn = std::min(chunk, b - c0);
+                VG_HIP(hipMemsetAsync(vis, 0, static_cast<size_t>(cn * vis_words) * 4, st));
+                VG_LAUNCH(vg::fv_walk_kernel<true>, dim3(static_cast<unsigned>(cn)), dim3(64), walk_lds, st, base, dim, dot, g, r, l,
+                          idx->vamana_entry, nullptr, d_rep + b0 + c0, del.ptr, n, vis, vis_words, res + c0 * l, 0, nullptr,
+                          int64_t(0), 0.0f, nullptr, nullptr, nullptr);
+            }
+        }
+        vg::ProfScope prof(idx->ctx, "vamana_consolidate_prune", st);
+        VG_LAUNCH(vg::fv_prune_kernel, dim3(static_cast<unsigned>(b)), dim3(vg::kFvThreads), 0, st, base, dim, dot, r, l, alpha,
+                  int64_t(0), d_rep + b0, res, del.ptr, n, g, nullptr, ctr + 3);
+    }
+    unsigned long long h_ctr[4] = {0, 0, 0, 0};
+    VG_HIP(hipMemcpyAsync(h_ctr, ctr, sizeof h_ctr, hipMemcpyDeviceToHost, st));
+    VG_HIP(hipStreamSynchronize(st));
+    if (stats)
+        *stats = vg_vamana_consolidate_stats{static_cast<int64_t>(h_ctr[0]), static_cast<int64_t>(h_ctr[1]),
+                                             static_cast<int64_t>(h_ctr[2]), static_cast<int64_t>(h_ctr[3])};
     return VG_OK;
 }
 
@@ -522,7 +673,7 @@ VG_API int32_t vg_search_vamana_fresh(vg_index *idx, const float *queries, int64
     VG_TRY(wc.for_each(st, [&](int64_t q0, int64_t cnt) -> int32_t {
         vg::ProfScope prof(idx->ctx, "vamana_fresh_search", st);
         VG_LAUNCH(vg::fv_walk_kernel<false>, dim3(static_cast<unsigned>(cnt)), dim3(64), walk_lds, st, idx->d_vectors, idx->dim, dot,
-                  idx->d_vamana, idx->vamana_r, ef, idx->vamana_entry, io.q.ptr + q0 * idx->dim, del.ptr, idx->n, wc.vis(),
+                  idx->d_vamana, idx->vamana_r, ef, idx->vamana_entry, io.q.ptr + q0 * idx->dim, nullptr, del.ptr, idx->n, wc.vis(),
                   wc.vis_words, nullptr, k, io.mk.ptr ? io.mk.ptr + q0 * mask_stride : nullptr, mask_stride, pad,
                   io.oid.ptr + q0 * k, io.osc.ptr + q0 * k, ocnt.ptr ? ocnt.ptr + q0 : nullptr);
         return VG_OK;
