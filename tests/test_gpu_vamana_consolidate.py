@@ -4,9 +4,8 @@ the same entry point, the same four counters; then vg_search_vamana_fresh under 
 ids and score bits.  Then the no-ops, the composition with vg_vamana_insert, device buffers and a caller's stream, and the
 refusals.
 
-Not covered: no test can shrink the scratch cap, so the split of a batch's visited bitmaps over several launches runs only
-through the code this call shares with vg_vamana_insert.  Two refusals cannot be reached through the public calls and are
-not tested: a Hamming index takes no fp32 rows ("no fp32 vectors" comes first), and no call installs a graph with r outside
+The split of a batch's visited bitmaps over several launches is tests/test_gpu_vamana_chunks.py's.  Not covered: two
+refusals cannot be reached through the public calls and are not tested: a Hamming index takes no fp32 rows ("no fp32 vectors" comes first), and no call installs a graph with r outside
 1..64."""
 import ctypes as C
 

@@ -5,9 +5,10 @@ timed: the graph is put back before every run, one warm-up run, RUNS timed runs 
 stream synchronise): median, min and max seconds, us per repaired node, the counters; the stage split (mark / search /
 prune, profiler events) from a run of its own.  Beside it the yardsticks: vg_vamana_build over the live rows only, and
 the insert's us per node from this process; recall@10 of vg_search_vamana_fresh over the live rows before the consolidate,
-after it, and over the rebuilt graph.  One JSON line.
+after it, and over the rebuilt graph; graph_crc32: zlib.crc32 over the bytes and entry point of the graph before the consolidate,
+after it, and rebuilt (two libraries that compute the same thing print the same).  One JSON line.
 usage: vamana_consolidate_time.py [N0 INS DIM DEL RUNS]   (default 80000 20000 128 0.1 5)"""
-import sys, time, json, statistics
+import sys, time, json, statistics, zlib
 from pathlib import Path
 sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
 import numpy as np
@@ -37,6 +38,11 @@ def recall(idx, dele, ids_of=None):
     return round(float((ids[:, :, None] == truth[:, None, :]).any(2).mean()), 4)
 
 
+def crc(idx):
+    g, e = idx.get_vamana_graph()
+    return zlib.crc32(int(e).to_bytes(4, "little"), zlib.crc32(g.tobytes()))
+
+
 def wall(fn):
     torch.cuda.synchronize(); t0 = time.perf_counter()
     out = fn()
@@ -49,6 +55,7 @@ build0_s, _ = wall(lambda: idx.build_vamana())
 insert_s, _ = wall(lambda: idx.insert_vamana(rows[n0:]))
 g0, entry = idx.get_vamana_graph()
 recall_before = recall(idx, deleted)
+crcs = {"before": crc(idx)}
 
 times, stats = [], None
 for run in range(runs + 1):  # the first one warms up
@@ -57,6 +64,7 @@ for run in range(runs + 1):  # the first one warms up
     if run:
         times.append(s)
 recall_after = recall(idx, deleted)
+crcs["after"] = crc(idx)
 assert idx.consolidate_vamana(packed)["repaired_nodes"] == 0  # idempotent
 idx.set_vamana_graph(g0, entry)
 ctx.profile_enable(True)
@@ -68,6 +76,7 @@ idx.close()
 
 rebuilt = vg.Index(ctx, live.size, dim); rebuilt.set_vectors(live_rows)
 rebuild_s, _ = wall(lambda: rebuilt.build_vamana())
+crcs["rebuilt"] = crc(rebuilt)
 med = statistics.median(times)
 print(json.dumps({
     "n": n, "dim": dim, "deleted": int(deleted.sum()), "max_batch": 8192, "runs": runs, "stats": stats,
@@ -76,4 +85,5 @@ print(json.dumps({
     "consolidate_stages_ms": stage_ms,
     "insert_us_per_node": round(insert_s / ins * 1e6, 2), "build_n0_us_per_node": round(build0_s / n0 * 1e6, 2),
     "rebuild_live_s": round(rebuild_s, 3), "rebuild_live_us_per_node": round(rebuild_s / live.size * 1e6, 2),
+    "graph_crc32": crcs,
     "recall10": {"before": recall_before, "after": recall_after, "rebuilt": recall(rebuilt, None, ids_of=live)}}), flush=True)

@@ -880,18 +880,6 @@ struct BuildRun {
     const float *cd0 = nullptr, *cdu = nullptr;  // the index's cached distances (layer 0, upper), or null
 };
 
-// One piece of a call's scratch after the other, each 256-byte aligned; base null: only the sizes are added up
-struct Carve {
-    char *base;
-    size_t off = 0;
-    template <typename T>
-    void take(T *&p, int64_t count)
-    {
-        p = base ? reinterpret_cast<T *>(base + off) : nullptr;
-        off += (static_cast<size_t>(count) * sizeof(T) + 255) & ~size_t(255);
-    }
-};
-
 // Every per-call scratch piece of run_batches with its size: the plan's device copy, the batches' buffers (sized by
 // the call's largest batch) and, for vg_hnsw_insert, the state rows.  base null: returns the bytes the call needs;
 // else points r (and, insert, g's state) into them.

@@ -30,10 +30,6 @@
 
 namespace vg {
 
-constexpr int kVbMaxR = 64;
-constexpr int kVbMaxL = 1024;
-constexpr int kVbMaxBatch = 16384;  // records of one target per batch are sorted in LDS (4 B each)
-constexpr int kVbThreads = 256;
 constexpr uint32_t kVbExpanded = 0x80000000u;  // pool entries: bit 31 of the id (ids < 2^31) = expanded
 // purpose constant of the initial graph's draws: rng_u64(seed, node, kVamanaInitPurpose, t) (header)
 constexpr uint64_t kVamanaInitPurpose = 0x56414D414E41ull;  // "VAMANA"
@@ -50,11 +46,11 @@ __global__ void vb_centroid_kernel(const float *__restrict__ base, int64_t n, in
 
 // the first row with dist(row, centroid) < minDist (minDist from MaxFloat32) = the least (canonical key) among the
 // rows whose distance is below MaxFloat32; *best stays kKeyMax (entry 0) when there is none
-__global__ __launch_bounds__(kVbThreads) void vb_entry_kernel(const float *__restrict__ base, int64_t n, int dim, bool dot,
-                                                              const float *__restrict__ c, unsigned long long *__restrict__ best)
+__global__ __launch_bounds__(kVamanaThreads) void vb_entry_kernel(const float *__restrict__ base, int64_t n, int dim, bool dot,
+                                                                  const float *__restrict__ c, unsigned long long *__restrict__ best)
 {
     const int tid = threadIdx.x;
-    const int64_t row = static_cast<int64_t>(blockIdx.x) * (kVbThreads / 16) + (tid >> 4);
+    const int64_t row = static_cast<int64_t>(blockIdx.x) * (kVamanaThreads / 16) + (tid >> 4);
     if (row >= n) return;  // whole 16-lane groups leave together
     const float d = vb_pair(base + row * dim, c, dim, dot, Sub16::make(tid));
     if ((tid & 15) == 0 && d < FLT_MAX) atomicMin(best, static_cast<unsigned long long>(vb_key(d, static_cast<uint32_t>(row))));
@@ -176,42 +172,12 @@ __global__ __launch_bounds__(64) void vb_search_kernel(const float *__restrict__
 }
 
 // ---- 2. robustPrune ----------------------------------------------------------------------------------
-// keys[0..np2) sorted, kKeyMax last; equal keys (one id seen twice) count once.  The greedy selection of
-// writer.go:598-617: candidate c is kept unless alpha * d(c, s) < d(c, node) for a kept s (fp32; NaN keeps it).
-// Returns the number kept (kept[0..nk)); every thread of the workgroup.
-__device__ int vb_select(const float *__restrict__ base, int dim, bool dot, const uint64_t *keys, int np2, int r,
-                         float alpha, uint32_t *kept, int *flag, int *nkept)
-{
-    const int tid = threadIdx.x, grp = tid >> 4;
-    const Sub16 sub = Sub16::make(tid);
-    if (tid == 0) *nkept = 0;
-    __syncthreads();
-    for (int i = 0; i < np2; i++) {
-        const uint64_t key = keys[i];
-        const int nk = *nkept;
-        if (key == kKeyMax || nk >= r) break;          // uniform
-        if (i > 0 && keys[i - 1] == key) continue;     // the same id twice
-        const uint32_t id = key_row(key);
-        const float dist = key_score(key, false);
-        const float *cv = base + static_cast<int64_t>(id) * dim;
-        if (tid == 0) *flag = 0;
-        __syncthreads();
-        for (int s0 = 0; s0 < nk; s0 += kVbThreads / 16) {
-            const int s = s0 + grp;
-            if (s < nk) {
-                const float dcs = vb_pair(cv, base + static_cast<int64_t>(kept[s]) * dim, dim, dot, sub);
-                if ((tid & 15) == 0 && alpha * dcs < dist) *flag = 1;
-            }
-        }
-        __syncthreads();
-        if (tid == 0 && !*flag) {
-            kept[nk] = id;
-            *nkept = nk + 1;
-        }
-        __syncthreads();
-    }
-    return *nkept;
-}
+// vamana_select's rule for the writer's greedy selection (writer.go:598-617) over keys[0..np2) sorted, kKeyMax last: equal
+// keys (one id seen twice) count once; candidate c is kept unless alpha * d(c, s) < d(c, node) for a kept s (fp32; NaN keeps it)
+struct WriterRule {
+    __device__ bool skip(const uint64_t *keys, int i, uint32_t) const { return i > 0 && keys[i - 1] == keys[i]; }
+    __device__ bool occludes(float alpha, float dcs, float dist) const { return alpha * dcs < dist; }
+};
 
 // keys of candidates cands[0..nc) against node (invalid ids and the node itself drop out), padded to np2, sorted
 __device__ void vb_keys(const float *__restrict__ base, int dim, bool dot, uint32_t node, const uint32_t *cands, int nc,
@@ -220,7 +186,7 @@ __device__ void vb_keys(const float *__restrict__ base, int dim, bool dot, uint3
     const int tid = threadIdx.x, grp = tid >> 4;
     const Sub16 sub = Sub16::make(tid);
     const float *nv = base + static_cast<int64_t>(node) * dim;
-    for (int c0 = 0; c0 < np2; c0 += kVbThreads / 16) {
+    for (int c0 = 0; c0 < np2; c0 += kVamanaThreads / 16) {
         const int c = c0 + grp;
         uint64_t key = kKeyMax;
         if (c < nc) {
@@ -231,28 +197,28 @@ __device__ void vb_keys(const float *__restrict__ base, int dim, bool dot, uint3
         if ((tid & 15) == 0 && c < np2) keys[c] = key;
     }
     __syncthreads();
-    bitonic_sort_lds(keys, np2, tid, kVbThreads);
+    bitonic_sort_lds(keys, np2, tid, kVamanaThreads);
 }
 
 // graph[i] = robustPrune(i, results ∪ graph[i], r, alpha) for node0 + blockIdx.x; LDS keys: np2 >= l + r
-__global__ __launch_bounds__(kVbThreads) void vb_prune_kernel(const float *__restrict__ base, int dim, bool dot,
-                                                              const uint32_t *__restrict__ graph, int r, int l, float alpha,
-                                                              int64_t node0, const uint32_t *__restrict__ res, int np2,
-                                                              uint32_t *__restrict__ out)
+__global__ __launch_bounds__(kVamanaThreads) void vb_prune_kernel(const float *__restrict__ base, int dim, bool dot,
+                                                                  const uint32_t *__restrict__ graph, int r, int l, float alpha,
+                                                                  int64_t node0, const uint32_t *__restrict__ res, int np2,
+                                                                  uint32_t *__restrict__ out)
 {
     extern __shared__ uint64_t vb_lds[];
-    __shared__ uint32_t cands[kVbMaxL + kVbMaxR];
-    __shared__ uint32_t kept[kVbMaxR];
+    __shared__ uint32_t cands[kVamanaMaxL + kVamanaMaxR];
+    __shared__ uint32_t kept[kVamanaMaxR];
     __shared__ int flag, nkept;
     const int tid = threadIdx.x;
     const int64_t b = blockIdx.x;
     const uint32_t node = static_cast<uint32_t>(node0 + b);
-    for (int i = tid; i < l; i += kVbThreads) cands[i] = res[b * l + i];
-    for (int i = tid; i < r; i += kVbThreads) cands[l + i] = graph[static_cast<int64_t>(node) * r + i];
+    for (int i = tid; i < l; i += kVamanaThreads) cands[i] = res[b * l + i];
+    for (int i = tid; i < r; i += kVamanaThreads) cands[l + i] = graph[static_cast<int64_t>(node) * r + i];
     __syncthreads();
     vb_keys(base, dim, dot, node, cands, l + r, np2, vb_lds);
-    const int nk = vb_select(base, dim, dot, vb_lds, np2, r, alpha, kept, &flag, &nkept);
-    for (int i = tid; i < r; i += kVbThreads) out[b * r + i] = i < nk ? kept[i] : VG_INVALID_ID;
+    const int nk = vamana_select(WriterRule{}, base, dim, dot, vb_lds, np2, r, alpha, kept, &flag, &nkept);
+    for (int i = tid; i < r; i += kVamanaThreads) out[b * r + i] = i < nk ? kept[i] : VG_INVALID_ID;
 }
 
 // ---- 3. new lists, back-edge records -------------------------------------------------------------------
@@ -264,89 +230,38 @@ __global__ void vb_write_kernel(const uint32_t *__restrict__ lists, int64_t coun
 }
 
 // ---- 4. back edges -----------------------------------------------------------------------------------
-// records: rec[i] = target of record i (VG_INVALID_ID = none); record i = (source node0 + i / r, slot i % r); grouped by
-// target (vg_group_records.hpp), the record's index as its payload (vg_vamana_common.hpp)
-// One workgroup per target: its records sorted by index (= (source, slot) order; the fill wrote them in any order),
-// then addBackEdge(target, source) for each: nothing if the source is listed, else append, and robustPrune(target,
-// list, r, alpha) once the list is longer than r.  LDS: the records (np2 of them, dynamic), the list.
-__global__ __launch_bounds__(kVbThreads) void vb_link_kernel(const float *__restrict__ base, int dim, bool dot, int r,
-                                                             float alpha, int64_t node0, uint32_t *__restrict__ graph,
-                                                             const uint32_t *__restrict__ work,
-                                                             const GroupCounters *__restrict__ ctr, int32_t *__restrict__ rcnt,
-                                                             int32_t *__restrict__ rfill, const uint32_t *__restrict__ roff,
-                                                             const uint32_t *__restrict__ srt)
+// One workgroup per target (vamana_link_target): addBackEdge(target, source) for each of its records: nothing if the source
+// is listed, else append, and robustPrune(target, list, r, alpha) once the list is longer than r.
+// LDS: the records (np2 of them, dynamic), the list.
+__global__ __launch_bounds__(kVamanaThreads) void vb_link_kernel(const float *__restrict__ base, int dim, bool dot, int r,
+                                                                 float alpha, int64_t node0, uint32_t *__restrict__ graph,
+                                                                 const uint32_t *__restrict__ work,
+                                                                 const GroupCounters *__restrict__ ctr, int32_t *__restrict__ rcnt,
+                                                                 int32_t *__restrict__ rfill, const uint32_t *__restrict__ roff,
+                                                                 const uint32_t *__restrict__ srt)
 {
     extern __shared__ uint64_t vb_lds[];
-    __shared__ uint64_t keys[2 * kVbMaxR];
-    __shared__ uint32_t list[kVbMaxR + 1];
-    __shared__ uint32_t kept[kVbMaxR];
+    __shared__ uint64_t keys[2 * kVamanaMaxR];
+    __shared__ uint32_t list[kVamanaMaxR + 1];
+    __shared__ uint32_t kept[kVamanaMaxR];
     __shared__ int flag, nkept, cnt;
-    if (blockIdx.x >= ctr->nwork) return;
-    const int tid = threadIdx.x;
-    const uint32_t t = work[blockIdx.x];
-    const int nrec = rcnt[t];
-    const uint32_t *mine = srt + roff[t];
-    int np2 = 1;
-    while (np2 < nrec) np2 <<= 1;
-    uint32_t *order = reinterpret_cast<uint32_t *>(vb_lds);
-    for (int i = tid; i < np2; i += kVbThreads) order[i] = i < nrec ? mine[i] : 0xFFFFFFFFu;
-    for (int i = tid; i < r; i += kVbThreads) list[i] = graph[static_cast<int64_t>(t) * r + i];
-    if (tid == 0) {
-        int c = 0;
-        while (c < r && graph[static_cast<int64_t>(t) * r + c] != VG_INVALID_ID) c++;
-        cnt = c;
-    }
-    __syncthreads();
-    // bitonic sort of the 32-bit record indices
-    for (int size = 2; size <= np2; size <<= 1)
-        for (int stride = size >> 1; stride > 0; stride >>= 1) {
-            for (int x = tid; x < (np2 >> 1); x += kVbThreads) {
-                const int lo = ((x / stride) * (stride << 1)) + (x % stride), hi = lo + stride;
-                const bool up = (lo & size) == 0;
-                const uint32_t a = order[lo], b = order[hi];
-                if ((a > b) == up) {
-                    order[lo] = b;
-                    order[hi] = a;
-                }
-            }
-            __syncthreads();
-        }
-    for (int k = 0; k < nrec; k++) {
-        const uint32_t src = static_cast<uint32_t>(node0 + order[k] / static_cast<uint32_t>(r));
-        const int c = cnt;
-        if (__syncthreads_or(tid < c && list[tid] == src)) continue;  // already listed
-        if (tid == 0) list[c] = src;
-        __syncthreads();
-        if (c + 1 <= r) {
-            if (tid == 0) cnt = c + 1;
-            __syncthreads();
-            continue;
-        }
-        vb_keys(base, dim, dot, t, list, c + 1, 2 * kVbMaxR, keys);
-        const int nk = vb_select(base, dim, dot, keys, 2 * kVbMaxR, r, alpha, kept, &flag, &nkept);
-        for (int i = tid; i < nk; i += kVbThreads) list[i] = kept[i];
-        if (tid == 0) cnt = nk;
-        __syncthreads();
-    }
-    const int c = cnt;
-    for (int i = tid; i < r; i += kVbThreads) graph[static_cast<int64_t>(t) * r + i] = i < c ? list[i] : VG_INVALID_ID;
-    if (tid == 0) {
-        rcnt[t] = 0;
-        rfill[t] = 0;
-    }
+    // a list of r + 1: robustPrune(target, list, r, alpha)
+    auto full = [&](uint32_t t, int nc) {
+        vb_keys(base, dim, dot, t, list, nc, 2 * kVamanaMaxR, keys);
+        const int nk = vamana_select(WriterRule{}, base, dim, dot, keys, 2 * kVamanaMaxR, r, alpha, kept, &flag, &nkept);
+        for (int i = threadIdx.x; i < nk; i += kVamanaThreads) list[i] = kept[i];
+        return nk;
+    };
+    vamana_link_target(r, node0, graph, work, ctr, rcnt, rfill, roff, srt, reinterpret_cast<uint32_t *>(vb_lds), list, &cnt, full);
 }
 
-// r, l, alpha of 0 become NewWriter's defaults (writer.go:84-95); then every refusal vg_vamana_build makes before it allocates
+// r, l, alpha of 0 become the defaults (vamana_check_rl); then every refusal vg_vamana_build makes before it allocates
 // (vg_search.hpp: vg_diskann_build makes them before it quantizes)
 int32_t vamana_build_check(const vg_index *idx, int32_t &r, int32_t &l, float &alpha, int32_t max_batch, int32_t growth_div)
 {
-    if (r == 0) r = 64;
-    if (l == 0) l = 100;
-    if (alpha == 0.0f) alpha = 1.2f;
-    VG_CHECK(r >= 1 && r <= kVbMaxR, VG_ERR_UNSUPPORTED, "vg_vamana_build: r=%d must be in 1..%d", r, kVbMaxR);
-    VG_CHECK(l >= 1 && l <= kVbMaxL, VG_ERR_UNSUPPORTED, "vg_vamana_build: l=%d must be in 1..%d", l, kVbMaxL);
+    VG_TRY(vamana_check_rl("vg_vamana_build", "r", r, l, alpha));
     VG_CHECK(max_batch >= 1 && growth_div >= 1, VG_ERR_INVALID_ARG, "vg_vamana_build: max_batch and growth_div must be >= 1");
-    VG_CHECK(max_batch <= kVbMaxBatch, VG_ERR_UNSUPPORTED, "vg_vamana_build: max_batch=%d must be <= %d", max_batch, kVbMaxBatch);
+    VG_TRY(vamana_check_batch("vg_vamana_build", max_batch));
     VG_CHECK(idx->n > 0, VG_ERR_INVALID_ARG, "vg_vamana_build: no vectors to write (n = 0)");
     VG_CHECK(idx->n < (int64_t(1) << 31), VG_ERR_UNSUPPORTED, "vg_vamana_build: n=%lld must be below 2^31",
              static_cast<long long>(idx->n));
@@ -405,44 +320,28 @@ VG_API int32_t vg_vamana_build(vg_index *idx, int32_t r, int32_t l, float alpha,
     VG_TRY(best.alloc(1));
     VG_HIP(hipMemsetAsync(best.p, 0xFF, 8, st));
     VG_LAUNCH(vg::vb_centroid_kernel, dim3(static_cast<unsigned>((dim + 63) / 64)), dim3(64), 0, st, base, n, dim, cen.p);
-    VG_LAUNCH(vg::vb_entry_kernel, dim3(static_cast<unsigned>((n + 15) / 16)), dim3(vg::kVbThreads), 0, st, base, n, dim,
+    VG_LAUNCH(vg::vb_entry_kernel, dim3(static_cast<unsigned>((n + 15) / 16)), dim3(vg::kVamanaThreads), 0, st, base, n, dim,
               dot, cen.p, best.p);
     unsigned long long hbest = 0;
     VG_HIP(hipMemcpyAsync(&hbest, best.p, 8, hipMemcpyDeviceToHost, st));
     VG_HIP(hipStreamSynchronize(st));
     const uint32_t entry = hbest == vg::kKeyMax ? 0u : static_cast<uint32_t>(hbest);
 
-    // scratch: per batch node l results and r new slots; visited bitmaps for as many search nodes as fit under
-    // 1/16 of the device's memory (at most 16 GiB, at least 1 GiB), the rest of the batch in further launches
-    const int64_t max_b = std::min<int64_t>(max_batch, n);
-    const int64_t vis_words = (n + 31) / 32;
-    const int64_t vis_cap = vg::scratch_cap(idx->ctx);
-    const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(max_b, vis_cap / (vis_words * 4)));
-    vg::DevBuf<uint32_t> vis, res, nl, work, roff, srt;
-    vg::DevBuf<int32_t> rcnt, rfill;
-    vg::DevBuf<vg::GroupCounters> ctr;
-    VG_TRY(vis.alloc(static_cast<size_t>(chunk * vis_words)));
-    VG_TRY(res.alloc(static_cast<size_t>(max_b) * l));
-    VG_TRY(nl.alloc(static_cast<size_t>(max_b) * r));
-    VG_TRY(work.alloc(static_cast<size_t>(std::min<int64_t>(max_b * r, n))));
-    VG_TRY(srt.alloc(static_cast<size_t>(max_b) * r));
-    VG_TRY(roff.alloc(static_cast<size_t>(n)));
-    VG_TRY(rcnt.alloc(static_cast<size_t>(n)));
-    VG_TRY(rfill.alloc(static_cast<size_t>(n)));
-    VG_TRY(ctr.alloc(1));
-    VG_HIP(hipMemsetAsync(rcnt.p, 0, static_cast<size_t>(n) * 4, st));
-    VG_HIP(hipMemsetAsync(rfill.p, 0, static_cast<size_t>(n) * 4, st));
+    // scratch: per batch node l results and r new slots (records), visited bitmaps; the call's own, freed at return
+    vg::VamanaBatch bt(idx->ctx, n, std::min<int64_t>(max_batch, n), static_cast<size_t>(l) * 4, r);
+    vg::DevBuf<char> scratch;
+    VG_TRY(scratch.alloc(bt.carve(nullptr)));
+    bt.carve(scratch.p);
+    VG_TRY(bt.start_records(vg::vb_link_kernel, st));
+    uint32_t *res = reinterpret_cast<uint32_t *>(bt.res);
 
     const size_t search_lds = static_cast<size_t>(2 * (l + 50 + r) + 64) * 8;
     const int prune_np2 = vg::next_pow2(l + r);
     const size_t prune_lds = static_cast<size_t>(prune_np2) * 8;
-    const size_t link_lds = static_cast<size_t>(vg::next_pow2(static_cast<int>(max_b))) * 4;
     VG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(vg::vb_search_kernel),
                                hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(search_lds)));
     VG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(vg::vb_prune_kernel),
                                hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(prune_lds)));
-    VG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(vg::vb_link_kernel),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(link_lds)));
 
     int64_t processed = 0;
     for (int pass = 0; pass < 2; pass++) {  // writer.go:430-457
@@ -451,29 +350,22 @@ VG_API int32_t vg_vamana_build(vg_index *idx, int32_t r, int32_t l, float alpha,
             const int64_t b = vg::next_batch(processed, (pass + 1) * n, max_batch, growth_div);  // (= n - t0 at the most)
             {
                 vg::ProfScope prof(idx->ctx, "vamana_build_search", st);
-                for (int64_t c0 = 0; c0 < b; c0 += chunk) {
-                    const int64_t cn = std::min(chunk, b - c0);
-                    VG_HIP(hipMemsetAsync(vis.p, 0, static_cast<size_t>(cn * vis_words) * 4, st));
+                VG_TRY(vg::for_each_walk_chunk(bt.vis, bt.vis_words, bt.chunk, b, st, [&](int64_t c0, int64_t cn) -> int32_t {
                     VG_LAUNCH(vg::vb_search_kernel, dim3(static_cast<unsigned>(cn)), dim3(64), search_lds, st, base, n, dim,
-                              dot, g.p, r, l, entry, t0 + c0, vis.p, vis_words, res.p + c0 * l);
-                }
+                              dot, g.p, r, l, entry, t0 + c0, bt.vis, bt.vis_words, res + c0 * l);
+                    return VG_OK;
+                }));
             }
             {
                 vg::ProfScope prof(idx->ctx, "vamana_build_prune", st);
-                VG_LAUNCH(vg::vb_prune_kernel, dim3(static_cast<unsigned>(b)), dim3(vg::kVbThreads), prune_lds, st, base,
-                          dim, dot, g.p, r, l, a, t0, res.p, prune_np2, nl.p);
-                VG_LAUNCH(vg::vb_write_kernel, dim3(static_cast<unsigned>((b * r + 255) / 256)), dim3(256), 0, st, nl.p,
+                VG_LAUNCH(vg::vb_prune_kernel, dim3(static_cast<unsigned>(b)), dim3(vg::kVamanaThreads), prune_lds, st, base,
+                          dim, dot, g.p, r, l, a, t0, res, prune_np2, bt.nl);
+                VG_LAUNCH(vg::vb_write_kernel, dim3(static_cast<unsigned>((b * r + 255) / 256)), dim3(256), 0, st, bt.nl,
                           b, r, t0, g.p);
             }
             {
                 vg::ProfScope prof(idx->ctx, "vamana_build_backedge", st);
-                const int64_t nrec = b * r;
-                const int64_t max_work = std::min(nrec, n);
-                VG_TRY(vg::group_count_offsets(nl.p, nrec, max_work, rcnt.p, work.p, roff.p, ctr.p, st));
-                VG_LAUNCH(vg::group_fill_index_kernel, dim3(static_cast<unsigned>((nrec + 255) / 256)), dim3(256), 0, st, nl.p, nrec,
-                          roff.p, rfill.p, srt.p);
-                VG_LAUNCH(vg::vb_link_kernel, dim3(static_cast<unsigned>(max_work)), dim3(vg::kVbThreads), link_lds, st,
-                          base, dim, dot, r, a, t0, g.p, work.p, ctr.p, rcnt.p, rfill.p, roff.p, srt.p);
+                VG_TRY(bt.reverse_edges(b, st, vg::vb_link_kernel, base, dim, dot, r, a, t0, g.p));
             }
             t0 += b;
             processed += b;

@@ -37,11 +37,7 @@
 
 namespace vg {
 
-constexpr int kFvMaxR = 64;
-constexpr int kFvMaxL = 1024;
-constexpr int kFvMaxBatch = 16384;  // records of one target per batch are sorted in LDS (4 B each)
-constexpr int kFvMaxEf = 2048;      // 6 ef keys of 8 bytes (two lists of 2 ef and ef, ping-ponged): 96 KiB of LDS
-constexpr int kFvThreads = 256;
+constexpr int kFvMaxEf = 2048;  // 6 ef keys of 8 bytes (two lists of 2 ef and ef, ping-ponged): 96 KiB of LDS
 
 // bit i of byte i/8 = node i is deleted; the bitmap covers nodes below n_del, later nodes are live
 __device__ __forceinline__ bool fv_deleted(const uint8_t *__restrict__ del, int64_t n_del, uint32_t id)
@@ -211,62 +207,35 @@ __global__ __launch_bounds__(64) void fv_walk_kernel(const float *__restrict__ b
 }
 
 // ---- 2. robustPruneLocked ------------------------------------------------------------------------------
-// ck[0..nc): the candidates in (distance, position) order, kKeyMax after the last.  The greedy selection of
-// fresh_vamana.go:762-789: self and deleted ids are skipped; c is kept unless d(c, s) < alpha * c.dist for a kept s (the
-// product is fp32 and its own rounding step; a false comparison, a NaN's included, keeps c); stops at r kept.
-// Returns the number kept (kept[0..nk)); every thread of the workgroup.
-__device__ int fv_select(const float *__restrict__ base, int dim, bool dot, const uint64_t *ck, int nc, uint32_t self, int r,
-                         float alpha, const uint8_t *__restrict__ deleted, int64_t n_del, uint32_t *kept, int *flag, int *nkept)
-{
-    const int tid = threadIdx.x, grp = tid >> 4;
-    const Sub16 sub = Sub16::make(tid);
-    if (tid == 0) *nkept = 0;
-    __syncthreads();
-    for (int i = 0; i < nc; i++) {
-        const uint64_t key = ck[i];
-        const int nk = *nkept;
-        if (key == kKeyMax || nk >= r) break;  // uniform
-        const uint32_t id = key_row(key);
-        if (id == self || fv_deleted(deleted, n_del, id)) continue;
-        const float bound = alpha * key_score(key, false);
-        const float *cv = base + static_cast<int64_t>(id) * dim;
-        if (tid == 0) *flag = 0;
-        __syncthreads();
-        for (int s0 = 0; s0 < nk; s0 += kFvThreads / 16) {
-            const int s = s0 + grp;
-            if (s < nk) {
-                const float dcs = vb_pair(cv, base + static_cast<int64_t>(kept[s]) * dim, dim, dot, sub);
-                if ((tid & 15) == 0 && dcs < bound) *flag = 1;
-            }
-        }
-        __syncthreads();
-        if (tid == 0 && !*flag) {
-            kept[nk] = id;
-            *nkept = nk + 1;
-        }
-        __syncthreads();
-    }
-    return *nkept;
-}
+// vamana_select's rule for the greedy selection of fresh_vamana.go:762-789 over the candidates in (distance, position)
+// order, kKeyMax after the last: self and deleted ids are skipped; c is kept unless d(c, s) < alpha * c.dist for a kept s
+// (the product is fp32 and its own rounding step; a false comparison, a NaN's included, keeps c)
+struct FreshRule {
+    uint32_t self;
+    const uint8_t *__restrict__ deleted;  // restrict as the kernels' parameter is: without it the selection compiles to other code
+    int64_t n_del;
+    __device__ bool skip(const uint64_t *, int, uint32_t id) const { return id == self || fv_deleted(deleted, n_del, id); }
+    __device__ bool occludes(float alpha, float dcs, float dist) const { return dcs < alpha * dist; }
+};
 
 // list(node) = robustPrune(node, its search results, r, alpha) for node = node0 + blockIdx.x, or nodes[blockIdx.x] with a
 // list of nodes, into the graph; with nl, one reverse-edge record per slot; with links, the kept ids are counted
-__global__ __launch_bounds__(kFvThreads) void fv_prune_kernel(const float *__restrict__ base, int dim, bool dot, int r, int l,
-                                                              float alpha, int64_t node0, const uint32_t *__restrict__ nodes,
-                                                              const uint64_t *__restrict__ res, const uint8_t *__restrict__ deleted,
-                                                              int64_t n_del, uint32_t *__restrict__ graph, uint32_t *__restrict__ nl,
-                                                              unsigned long long *__restrict__ links)
+__global__ __launch_bounds__(kVamanaThreads) void fv_prune_kernel(const float *__restrict__ base, int dim, bool dot, int r, int l,
+                                                                  float alpha, int64_t node0, const uint32_t *__restrict__ nodes,
+                                                                  const uint64_t *__restrict__ res, const uint8_t *__restrict__ deleted,
+                                                                  int64_t n_del, uint32_t *__restrict__ graph, uint32_t *__restrict__ nl,
+                                                                  unsigned long long *__restrict__ links)
 {
-    __shared__ uint64_t ck[kFvMaxL];
-    __shared__ uint32_t kept[kFvMaxR];
+    __shared__ uint64_t ck[kVamanaMaxL];
+    __shared__ uint32_t kept[kVamanaMaxR];
     __shared__ int flag, nkept;
     const int tid = threadIdx.x;
     const int64_t b = blockIdx.x;
     const uint32_t node = nodes ? nodes[b] : static_cast<uint32_t>(node0 + b);
-    for (int i = tid; i < l; i += kFvThreads) ck[i] = res[b * l + i];
+    for (int i = tid; i < l; i += kVamanaThreads) ck[i] = res[b * l + i];
     __syncthreads();
-    const int nk = fv_select(base, dim, dot, ck, l, node, r, alpha, deleted, n_del, kept, &flag, &nkept);
-    for (int i = tid; i < r; i += kFvThreads) {
+    const int nk = vamana_select(FreshRule{node, deleted, n_del}, base, dim, dot, ck, l, r, alpha, kept, &flag, &nkept);
+    for (int i = tid; i < r; i += kVamanaThreads) {
         const uint32_t v = i < nk ? kept[i] : VG_INVALID_ID;
         graph[static_cast<int64_t>(node) * r + i] = v;
         if (nl) nl[b * r + i] = v;
@@ -275,91 +244,43 @@ __global__ __launch_bounds__(kFvThreads) void fv_prune_kernel(const float *__res
 }
 
 // ---- 3. addReverseEdgeLocked ---------------------------------------------------------------------------
-// records: nl[i] = target of record i (VG_INVALID_ID = none); record i = (source node0 + i / r, slot i % r).  One workgroup
-// per target: its list without empty slots, its records sorted by index (= (source, slot) order), then for each source:
-// nothing if it is listed; appended while the list is shorter than r; at r the list in slot order followed by the source,
-// sorted stably by distance to the target, goes through robustPrune(target, ..., r, alpha), which drops deleted ids and
-// may keep fewer than r.  LDS: the records (np2 of them, dynamic), the list.
-__global__ __launch_bounds__(kFvThreads) void fv_link_kernel(const float *__restrict__ base, int dim, bool dot, int r, float alpha,
-                                                             int64_t node0, const uint8_t *__restrict__ deleted, int64_t n_del,
-                                                             uint32_t *__restrict__ graph, const uint32_t *__restrict__ work,
-                                                             const GroupCounters *__restrict__ ctr, int32_t *__restrict__ rcnt,
-                                                             int32_t *__restrict__ rfill, const uint32_t *__restrict__ roff,
-                                                             const uint32_t *__restrict__ srt)
+// One workgroup per target (vamana_link_target) applies addReverseEdge for each of its records: nothing if the source is
+// listed; appended while the list is shorter than r; at r the list in slot order followed by the source, sorted stably by
+// distance to the target, goes through robustPrune(target, ..., r, alpha), which drops deleted ids and may keep fewer than r.
+// LDS: the records (np2 of them, dynamic), the list.
+__global__ __launch_bounds__(kVamanaThreads) void fv_link_kernel(const float *__restrict__ base, int dim, bool dot, int r, float alpha,
+                                                                 int64_t node0, const uint8_t *__restrict__ deleted, int64_t n_del,
+                                                                 uint32_t *__restrict__ graph, const uint32_t *__restrict__ work,
+                                                                 const GroupCounters *__restrict__ ctr, int32_t *__restrict__ rcnt,
+                                                                 int32_t *__restrict__ rfill, const uint32_t *__restrict__ roff,
+                                                                 const uint32_t *__restrict__ srt)
 {
     extern __shared__ uint64_t fv_lds[];
-    __shared__ uint64_t keys[2 * kFvMaxR];
-    __shared__ uint64_t ck[kFvMaxR + 1];
-    __shared__ uint32_t list[kFvMaxR + 1];
-    __shared__ uint32_t kept[kFvMaxR];
+    __shared__ uint64_t keys[2 * kVamanaMaxR];
+    __shared__ uint64_t ck[kVamanaMaxR + 1];
+    __shared__ uint32_t list[kVamanaMaxR + 1];
+    __shared__ uint32_t kept[kVamanaMaxR];
     __shared__ int flag, nkept, cnt;
-    if (blockIdx.x >= ctr->nwork) return;
-    const int tid = threadIdx.x, grp = tid >> 4;
-    const Sub16 sub = Sub16::make(tid);
-    const uint32_t t = work[blockIdx.x];
-    const float *tv = base + static_cast<int64_t>(t) * dim;
-    const int nrec = rcnt[t];
-    const uint32_t *mine = srt + roff[t];
-    int np2 = 1;
-    while (np2 < nrec) np2 <<= 1;
-    uint32_t *order = reinterpret_cast<uint32_t *>(fv_lds);
-    for (int i = tid; i < np2; i += kFvThreads) order[i] = i < nrec ? mine[i] : 0xFFFFFFFFu;
-    if (tid == 0) {
-        int c = 0;
-        for (int s = 0; s < r; s++) {
-            const uint32_t v = graph[static_cast<int64_t>(t) * r + s];
-            if (v != VG_INVALID_ID) list[c++] = v;
-        }
-        cnt = c;
-    }
-    __syncthreads();
-    // bitonic sort of the 32-bit record indices
-    for (int size = 2; size <= np2; size <<= 1)
-        for (int stride = size >> 1; stride > 0; stride >>= 1) {
-            for (int x = tid; x < (np2 >> 1); x += kFvThreads) {
-                const int lo = ((x / stride) * (stride << 1)) + (x % stride), hi = lo + stride;
-                const bool up = (lo & size) == 0;
-                const uint32_t a = order[lo], b = order[hi];
-                if ((a > b) == up) {
-                    order[lo] = b;
-                    order[hi] = a;
-                }
-            }
-            __syncthreads();
-        }
-    for (int k = 0; k < nrec; k++) {
-        const uint32_t src = static_cast<uint32_t>(node0 + order[k] / static_cast<uint32_t>(r));
-        const int c = cnt;
-        if (__syncthreads_or(tid < c && list[tid] == src)) continue;  // already listed
-        if (tid == 0) list[c] = src;
-        __syncthreads();
-        if (c < r) {
-            if (tid == 0) cnt = c + 1;
-            __syncthreads();
-            continue;
-        }
-        // c == r: the r + 1 candidates keyed (distance, position), sorted, then keyed (distance, id) for the prune
-        for (int c0 = 0; c0 < 2 * kFvMaxR; c0 += kFvThreads / 16) {
+    // a list of r + 1: the candidates keyed (distance, position), sorted, then keyed (distance, id) for the prune
+    auto full = [&](uint32_t t, int nc) {
+        const int tid = threadIdx.x, grp = tid >> 4;
+        const Sub16 sub = Sub16::make(tid);
+        const float *tv = base + static_cast<int64_t>(t) * dim;
+        for (int c0 = 0; c0 < 2 * kVamanaMaxR; c0 += kVamanaThreads / 16) {
             const int i = c0 + grp;
             uint64_t key = kKeyMax;
-            if (i <= c) key = vb_key(vb_pair(tv, base + static_cast<int64_t>(list[i]) * dim, dim, dot, sub), static_cast<uint32_t>(i));
+            if (i < nc) key = vb_key(vb_pair(tv, base + static_cast<int64_t>(list[i]) * dim, dim, dot, sub), static_cast<uint32_t>(i));
             if ((tid & 15) == 0) keys[i] = key;
         }
         __syncthreads();
-        bitonic_sort_lds(keys, 2 * kFvMaxR, tid, kFvThreads);
-        if (tid <= c) ck[tid] = (keys[tid] & 0xFFFFFFFF00000000ull) | list[key_row(keys[tid])];
+        bitonic_sort_lds(keys, 2 * kVamanaMaxR, tid, kVamanaThreads);
+        if (tid < nc) ck[tid] = (keys[tid] & 0xFFFFFFFF00000000ull) | list[key_row(keys[tid])];
         __syncthreads();
-        const int nk = fv_select(base, dim, dot, ck, c + 1, t, r, alpha, deleted, n_del, kept, &flag, &nkept);
-        for (int i = tid; i < nk; i += kFvThreads) list[i] = kept[i];
-        if (tid == 0) cnt = nk;
-        __syncthreads();
-    }
-    const int c = cnt;
-    for (int i = tid; i < r; i += kFvThreads) graph[static_cast<int64_t>(t) * r + i] = i < c ? list[i] : VG_INVALID_ID;
-    if (tid == 0) {
-        rcnt[t] = 0;
-        rfill[t] = 0;
-    }
+        const int nk = vamana_select(FreshRule{t, deleted, n_del}, base, dim, dot, ck, nc, r, alpha, kept, &flag, &nkept);
+        for (int i = tid; i < nk; i += kVamanaThreads) list[i] = kept[i];
+        return nk;
+    };
+    vamana_link_target(r, node0, graph, work, ctr, rcnt, rfill, roff, srt, reinterpret_cast<uint32_t *>(fv_lds), list, &cnt, full);
 }
 
 // ---- 4. consolidate's repair set (fresh_vamana.go:836-847) ---------------------------------------------
@@ -368,15 +289,15 @@ __global__ __launch_bounds__(kFvThreads) void fv_link_kernel(const float *__rest
 // slot, 64 / g whole nodes per step.  A live node with a deleted id in any non-empty slot gets its bit; the word is stored
 // once, whole (no atomics, nothing to clear).  ctr[0..3) += such nodes, their slots that name a deleted id, their non-empty
 // slots: summed per wavefront in registers, per workgroup in LDS, then one atomicAdd each per workgroup that found any.
-__global__ __launch_bounds__(kFvThreads) void fv_mark_kernel(const uint32_t *__restrict__ graph, int64_t n, int r, int g,
-                                                             const uint8_t *__restrict__ deleted, uint32_t *__restrict__ need,
-                                                             unsigned long long *__restrict__ ctr)
+__global__ __launch_bounds__(kVamanaThreads) void fv_mark_kernel(const uint32_t *__restrict__ graph, int64_t n, int r, int g,
+                                                                 const uint8_t *__restrict__ deleted, uint32_t *__restrict__ need,
+                                                                 unsigned long long *__restrict__ ctr)
 {
     __shared__ unsigned int tot[3];
     if (threadIdx.x < 3) tot[threadIdx.x] = 0;
     __syncthreads();
     const int lane = threadIdx.x & 63;
-    const int64_t word = static_cast<int64_t>(blockIdx.x) * (kFvThreads / 64) + (threadIdx.x >> 6);
+    const int64_t word = static_cast<int64_t>(blockIdx.x) * (kVamanaThreads / 64) + (threadIdx.x >> 6);
     if (word * 32 < n) {  // uniform over the wavefront
         const int per = 64 / g, slot = lane & (g - 1), sub = lane >> __builtin_ctz(g);
         const uint64_t mine = (g == 64 ? ~0ull : (1ull << g) - 1) << (lane & ~(g - 1));
@@ -418,6 +339,18 @@ static int32_t fv_walk_lds(int ef, size_t *lds)
     return VG_OK;
 }
 
+// The searches of nodes c0 .. c0 + cn - 1 of a batch (VamanaBatch::search), whose vectors are the rows from `queries` on or
+// the rows qids[0..) of base; l result keys each into bt.res.  (The query search's outputs are not the insert walk's.)
+static int32_t fv_insert_walk(const VamanaBatch &bt, int64_t c0, int64_t cn, size_t walk_lds, hipStream_t st, const float *base, int dim,
+                              bool dot, const uint32_t *g, int r, int l, uint32_t entry, const float *queries, const uint32_t *qids,
+                              const uint8_t *deleted, int64_t n_del)
+{
+    VG_LAUNCH(fv_walk_kernel<true>, dim3(static_cast<unsigned>(cn)), dim3(64), walk_lds, st, base, dim, dot, g, r, l, entry,
+              queries ? queries + c0 * dim : nullptr, qids ? qids + c0 : nullptr, deleted, n_del, bt.vis, bt.vis_words,
+              reinterpret_cast<uint64_t *>(bt.res) + c0 * l, 0, nullptr, int64_t(0), 0.0f, nullptr, nullptr, nullptr);
+    return VG_OK;
+}
+
 }  // namespace vg
 
 VG_API int32_t vg_vamana_insert(vg_index *idx, const float *rows, int64_t count, int32_t r, int32_t l, float alpha,
@@ -431,13 +364,9 @@ VG_API int32_t vg_vamana_insert(vg_index *idx, const float *rows, int64_t count,
     VG_CHECK(n_old == 0 || (idx->d_vectors && idx->d_vamana), VG_ERR_NOT_READY,
              "%s: the index has %lld rows but no Vamana graph (vg_vamana_build or vg_index_set_vamana_graph first)", fn,
              static_cast<long long>(n_old));
-    if (r == 0) r = 64;  // FreshDefaultR / L / Alpha (fresh_vamana.go:20-24)
-    if (l == 0) l = 100;
-    if (alpha == 0.0f) alpha = 1.2f;
     VG_CHECK(idx->metric != VG_METRIC_HAMMING, VG_ERR_UNSUPPORTED, "unsupported metric for float32: Hamming");
-    VG_CHECK(r >= 1 && r <= vg::kFvMaxR, VG_ERR_UNSUPPORTED, "%s: r=%d must be in 1..%d", fn, r, vg::kFvMaxR);
-    VG_CHECK(l >= 1 && l <= vg::kFvMaxL, VG_ERR_UNSUPPORTED, "%s: l=%d must be in 1..%d", fn, l, vg::kFvMaxL);
-    VG_CHECK(max_batch <= vg::kFvMaxBatch, VG_ERR_UNSUPPORTED, "%s: max_batch=%d must be <= %d", fn, max_batch, vg::kFvMaxBatch);
+    VG_TRY(vg::vamana_check_rl(fn, "r", r, l, alpha));
+    VG_TRY(vg::vamana_check_batch(fn, max_batch));
     VG_CHECK(n_old + count < (int64_t(1) << 31), VG_ERR_UNSUPPORTED, "%s: %lld rows after the insert, must be below 2^31", fn,
              static_cast<long long>(n_old + count));
     VG_CHECK(max_batch >= 1 && growth_div >= 1, VG_ERR_INVALID_ARG, "%s: max_batch=%d and growth_div=%d must be >= 1", fn,
@@ -468,59 +397,33 @@ VG_API int32_t vg_vamana_insert(vg_index *idx, const float *rows, int64_t count,
     const float *base = idx->d_vectors;
     uint32_t *g = idx->d_vamana;
 
-    // ---- per-call scratch on the context arena: per batch node l result keys and r records; visited bitmaps for as many
-    // searching nodes as fit under the scratch cap, the rest of a batch in further launches
-    const int64_t max_b = plan.max_b;
-    const int64_t vis_words = (n_new + 31) / 32;
-    const int64_t chunk = vg::walk_chunk(vg::scratch_cap(idx->ctx), vis_words * 4, max_b);
-    const int64_t max_work_all = std::min<int64_t>(max_b * r, n_new);
+    // ---- per-call scratch on the context arena: per batch node l result keys and r records, visited bitmaps
+    vg::VamanaBatch bs(idx->ctx, n_new, plan.max_b, static_cast<size_t>(l) * 8, r);
     vg::ArenaCall ar(idx->ctx, st);
-    const int a_vis = ar.add(static_cast<size_t>(chunk * vis_words) * 4), a_res = ar.add(static_cast<size_t>(max_b) * l * 8),
-              a_nl = ar.add(static_cast<size_t>(max_b) * r * 4), a_work = ar.add(static_cast<size_t>(max_work_all) * 4),
-              a_srt = ar.add(static_cast<size_t>(max_b) * r * 4), a_roff = ar.add(static_cast<size_t>(n_new) * 4),
-              a_rcnt = ar.add(static_cast<size_t>(n_new) * 4), a_rfill = ar.add(static_cast<size_t>(n_new) * 4),
-              a_ctr = ar.add(sizeof(vg::GroupCounters));
+    const int a_bs = ar.add(bs.carve(nullptr));
     VG_TRY(ar.commit());
-    uint32_t *vis = ar.get<uint32_t>(a_vis), *nl = ar.get<uint32_t>(a_nl), *work = ar.get<uint32_t>(a_work),
-             *srt = ar.get<uint32_t>(a_srt), *roff = ar.get<uint32_t>(a_roff);
-    uint64_t *res = ar.get<uint64_t>(a_res);
-    int32_t *rcnt = ar.get<int32_t>(a_rcnt), *rfill = ar.get<int32_t>(a_rfill);
-    vg::GroupCounters *ctr = ar.get<vg::GroupCounters>(a_ctr);
-    VG_HIP(hipMemsetAsync(rcnt, 0, static_cast<size_t>(n_new) * 4, st));
-    VG_HIP(hipMemsetAsync(rfill, 0, static_cast<size_t>(n_new) * 4, st));
-
+    bs.carve(ar.get<char>(a_bs));
+    VG_TRY(bs.start_records(vg::fv_link_kernel, st));
     size_t walk_lds = 0;
     VG_TRY(vg::fv_walk_lds<true>(l, &walk_lds));
-    const size_t link_lds = static_cast<size_t>(vg::next_pow2(static_cast<int>(max_b))) * 4;
-    VG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(vg::fv_link_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               static_cast<int>(link_lds)));
 
     for (const vg::BuildBatch &bt : plan.batches) {
         const int64_t t0 = bt.t0, b = bt.size;
         {
             vg::ProfScope prof(idx->ctx, "vamana_insert_search", st);
-            for (int64_t c0 = 0; c0 < b; c0 += chunk) {
-                const int64_t cn = std::min(chunk, b - c0);
-                VG_HIP(hipMemsetAsync(vis, 0, static_cast<size_t>(cn * vis_words) * 4, st));
-                VG_LAUNCH(vg::fv_walk_kernel<true>, dim3(static_cast<unsigned>(cn)), dim3(64), walk_lds, st, base, dim, dot, g, r, l,
-                          bt.entry, base + (t0 + c0) * dim, nullptr, del.ptr, n_old, vis, vis_words, res + c0 * l, 0, nullptr,
-                          int64_t(0), 0.0f, nullptr, nullptr, nullptr);
-            }
+            VG_TRY(vg::for_each_walk_chunk(bs.vis, bs.vis_words, bs.chunk, b, st, [&](int64_t c0, int64_t cn) {
+                return vg::fv_insert_walk(bs, c0, cn, walk_lds, st, base, dim, dot, g, r, l, bt.entry, base + t0 * dim, nullptr, del.ptr,
+                                          n_old);
+            }));
         }
         {
             vg::ProfScope prof(idx->ctx, "vamana_insert_prune", st);
-            VG_LAUNCH(vg::fv_prune_kernel, dim3(static_cast<unsigned>(b)), dim3(vg::kFvThreads), 0, st, base, dim, dot, r, l, alpha,
-                      t0, nullptr, res, del.ptr, n_old, g, nl, nullptr);
+            VG_LAUNCH(vg::fv_prune_kernel, dim3(static_cast<unsigned>(b)), dim3(vg::kVamanaThreads), 0, st, base, dim, dot, r, l, alpha,
+                      t0, nullptr, reinterpret_cast<const uint64_t *>(bs.res), del.ptr, n_old, g, bs.nl, nullptr);
         }
         {
             vg::ProfScope prof(idx->ctx, "vamana_insert_reverse", st);
-            const int64_t nrec = b * r;
-            const int64_t max_work = std::min(nrec, n_new);
-            VG_TRY(vg::group_count_offsets(nl, nrec, max_work, rcnt, work, roff, ctr, st));
-            VG_LAUNCH(vg::group_fill_index_kernel, dim3(static_cast<unsigned>((nrec + 255) / 256)), dim3(256), 0, st, nl, nrec, roff,
-                      rfill, srt);
-            VG_LAUNCH(vg::fv_link_kernel, dim3(static_cast<unsigned>(max_work)), dim3(vg::kFvThreads), link_lds, st, base, dim, dot,
-                      r, alpha, t0, del.ptr, n_old, g, work, ctr, rcnt, rfill, roff, srt);
+            VG_TRY(bs.reverse_edges(b, st, vg::fv_link_kernel, base, dim, dot, r, alpha, t0, del.ptr, n_old, g));
         }
     }
     VG_HIP(hipStreamSynchronize(st));
@@ -542,13 +445,10 @@ VG_API int32_t vg_vamana_consolidate(vg_index *idx, int32_t l, float alpha, cons
         return VG_OK;
     }
     VG_CHECK(idx->d_vectors && idx->d_vamana, VG_ERR_NOT_READY, "%s: index has no fp32 vectors or no Vamana graph", fn);
-    if (l == 0) l = 100;  // FreshDefaultL / Alpha (fresh_vamana.go:20-24)
-    if (alpha == 0.0f) alpha = 1.2f;
-    const int r = idx->vamana_r;
+    int32_t r = idx->vamana_r;
     VG_CHECK(idx->metric != VG_METRIC_HAMMING, VG_ERR_UNSUPPORTED, "unsupported metric for float32: Hamming");
-    VG_CHECK(r >= 1 && r <= vg::kFvMaxR, VG_ERR_UNSUPPORTED, "%s: the graph's r=%d must be in 1..%d", fn, r, vg::kFvMaxR);
-    VG_CHECK(l >= 1 && l <= vg::kFvMaxL, VG_ERR_UNSUPPORTED, "%s: l=%d must be in 1..%d", fn, l, vg::kFvMaxL);
-    VG_CHECK(max_batch <= vg::kFvMaxBatch, VG_ERR_UNSUPPORTED, "%s: max_batch=%d must be <= %d", fn, max_batch, vg::kFvMaxBatch);
+    VG_TRY(vg::vamana_check_rl(fn, "the graph's r", r, l, alpha));
+    VG_TRY(vg::vamana_check_batch(fn, max_batch));
     VG_CHECK(max_batch >= 1, VG_ERR_INVALID_ARG, "%s: max_batch=%d must be >= 1", fn, max_batch);
     if (!deleted) {  // nothing is deleted: nothing to repair
         if (stats) *stats = none;
@@ -564,25 +464,23 @@ VG_API int32_t vg_vamana_consolidate(vg_index *idx, int32_t l, float alpha, cons
     VG_TRY(del.init(deleted, static_cast<size_t>((n + 7) / 8), st, vg::kAnyAlign));
 
     // ---- per-call scratch on the context arena: the need bits, the repair list (at most n ids), per batch node l result
-    // keys; visited bitmaps for as many searching nodes as fit under the scratch cap, the rest of a batch in further launches
-    const int64_t max_b = std::min<int64_t>(max_batch, n);
-    const int64_t vis_words = (n + 31) / 32;
-    const int64_t chunk = vg::walk_chunk(vg::scratch_cap(idx->ctx), vis_words * 4, max_b);
+    // keys and the visited bitmaps (no records)
+    vg::VamanaBatch bs(idx->ctx, n, std::min<int64_t>(max_batch, n), static_cast<size_t>(l) * 8, 0);
+    const int64_t vis_words = bs.vis_words;
     vg::ArenaCall ar(idx->ctx, st);
     const int a_need = ar.add(static_cast<size_t>(vis_words) * 4), a_rep = ar.add(static_cast<size_t>(n) * 4),
-              a_vis = ar.add(static_cast<size_t>(chunk * vis_words) * 4), a_res = ar.add(static_cast<size_t>(max_b) * l * 8),
-              a_ctr = ar.add(4 * sizeof(unsigned long long));
+              a_bs = ar.add(bs.carve(nullptr)), a_ctr = ar.add(4 * sizeof(unsigned long long));
     VG_TRY(ar.commit());
-    uint32_t *need = ar.get<uint32_t>(a_need), *d_rep = ar.get<uint32_t>(a_rep), *vis = ar.get<uint32_t>(a_vis);
-    uint64_t *res = ar.get<uint64_t>(a_res);
+    bs.carve(ar.get<char>(a_bs));
+    uint32_t *need = ar.get<uint32_t>(a_need), *d_rep = ar.get<uint32_t>(a_rep);
     unsigned long long *ctr = ar.get<unsigned long long>(a_ctr);
 
     // ---- which nodes: fixed before the first repair (a repair rewrites only the node's own list) ----
     VG_HIP(hipMemsetAsync(ctr, 0, 4 * sizeof(unsigned long long), st));
     {
         vg::ProfScope prof(idx->ctx, "vamana_consolidate_mark", st);
-        const int waves = vg::kFvThreads / 64;  // one word of need each
-        VG_LAUNCH(vg::fv_mark_kernel, dim3(static_cast<unsigned>((vis_words + waves - 1) / waves)), dim3(vg::kFvThreads), 0, st, g,
+        const int waves = vg::kVamanaThreads / 64;  // one word of need each
+        VG_LAUNCH(vg::fv_mark_kernel, dim3(static_cast<unsigned>((vis_words + waves - 1) / waves)), dim3(vg::kVamanaThreads), 0, st, g,
                   n, r, std::max(2, vg::next_pow2(r)), del.ptr, need, ctr);
     }
     std::vector<uint32_t> h_need(static_cast<size_t>(vis_words)), rep;
@@ -605,17 +503,14 @@ VG_API int32_t vg_vamana_consolidate(vg_index *idx, int32_t l, float alpha, cons
         const int64_t b = std::min<int64_t>(max_batch, nrep - b0);
         {
             vg::ProfScope prof(idx->ctx, "vamana_consolidate_search", st);
-            for (int64_t c0 = 0; c0 < b; c0 += chunk) {
-                const int64_t cn = std::min(chunk, b - c0);
-                VG_HIP(hipMemsetAsync(vis, 0, static_cast<size_t>(cn * vis_words) * 4, st));
-                VG_LAUNCH(vg::fv_walk_kernel<true>, dim3(static_cast<unsigned>(cn)), dim3(64), walk_lds, st, base, dim, dot, g, r, l,
-                          idx->vamana_entry, nullptr, d_rep + b0 + c0, del.ptr, n, vis, vis_words, res + c0 * l, 0, nullptr,
-                          int64_t(0), 0.0f, nullptr, nullptr, nullptr);
-            }
+            VG_TRY(vg::for_each_walk_chunk(bs.vis, bs.vis_words, bs.chunk, b, st, [&](int64_t c0, int64_t cn) {
+                return vg::fv_insert_walk(bs, c0, cn, walk_lds, st, base, dim, dot, g, r, l, idx->vamana_entry, nullptr, d_rep + b0,
+                                          del.ptr, n);
+            }));
         }
         vg::ProfScope prof(idx->ctx, "vamana_consolidate_prune", st);
-        VG_LAUNCH(vg::fv_prune_kernel, dim3(static_cast<unsigned>(b)), dim3(vg::kFvThreads), 0, st, base, dim, dot, r, l, alpha,
-                  int64_t(0), d_rep + b0, res, del.ptr, n, g, nullptr, ctr + 3);
+        VG_LAUNCH(vg::fv_prune_kernel, dim3(static_cast<unsigned>(b)), dim3(vg::kVamanaThreads), 0, st, base, dim, dot, r, l, alpha,
+                  int64_t(0), d_rep + b0, reinterpret_cast<const uint64_t *>(bs.res), del.ptr, n, g, nullptr, ctr + 3);
     }
     unsigned long long h_ctr[4] = {0, 0, 0, 0};
     VG_HIP(hipMemcpyAsync(h_ctr, ctr, sizeof h_ctr, hipMemcpyDeviceToHost, st));

@@ -45,9 +45,11 @@ __device__ __forceinline__ float key_score(uint64_t key, bool descending)
 }
 __device__ __forceinline__ uint32_t key_row(uint64_t key) { return static_cast<uint32_t>(key); }
 
-// Bitonic sort (ascending) of n = power-of-two 64-bit keys in LDS by the whole
-// workgroup.  Caller guarantees a __syncthreads() before; ends with one.
-__device__ __forceinline__ void bitonic_sort_lds(uint64_t *buf, int n, int tid, int nthreads)
+// Bitonic sort (ascending) of n = power-of-two keys in LDS by the whole workgroup: 64-bit
+// selection keys, or 32-bit indices (the Vamana builders' record order).  Caller guarantees a
+// __syncthreads() before; ends with one (n > 1).
+template <typename K>
+__device__ __forceinline__ void bitonic_sort_lds(K *buf, int n, int tid, int nthreads)
 {
     for (int size = 2; size <= n; size <<= 1) {
         for (int stride = size >> 1; stride > 0; stride >>= 1) {
@@ -55,7 +57,7 @@ __device__ __forceinline__ void bitonic_sort_lds(uint64_t *buf, int n, int tid, 
                 int lo = ((t / stride) * (stride << 1)) + (t % stride);
                 int hi = lo + stride;
                 bool up = ((lo & size) == 0);
-                uint64_t a = buf[lo], b = buf[hi];
+                K a = buf[lo], b = buf[hi];
                 if ((a > b) == up) {
                     buf[lo] = b;
                     buf[hi] = a;

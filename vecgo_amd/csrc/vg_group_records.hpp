@@ -1,8 +1,10 @@
 // vg_group_records.hpp — the records of a batch grouped by the row they target: the back links of the HNSW build
-// (k_hnsw_build.hip) and the back edges of the Vamana build (k_vamana_build.hip).  Per batch: rcnt[row] = the row's
+// and insert (k_hnsw_build.hip) and the back edges of the two Vamana builders (k_vamana_build.hip, k_vamana_fresh.hip,
+// through VamanaBatch::reverse_edges, vg_vamana_common.hpp).  Per batch: rcnt[row] = the row's
 // records, work[0 .. nwork) = the rows that have any, roff[row] = where the row's records start in the grouped order.
-// The builders' own fill kernels then place every record's payload at roff[row] + (rfill[row]++), and their link
-// kernels take one target row per workgroup and leave rcnt / rfill zero for the next batch.
+// The builders' own fill kernels (the Vamana builders share group_fill_index_kernel) then place every record's payload at
+// roff[row] + (rfill[row]++), and their link kernels take one target row per workgroup and leave rcnt / rfill zero for
+// the next batch.
 #pragma once
 
 #include "vg_internal.hpp"

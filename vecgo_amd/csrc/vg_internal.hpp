@@ -94,7 +94,7 @@ enum Hook {
     kHookPqNomAlways,         // VG_PQ_NOM_ALWAYS        vg_index_enable_pq_nomination: batches of any size take the nomination
     kHookKmNoRanges,          // VG_KM_NO_RANGES         k-means: the listed points' exact pass in one walk over the centroids (no ranges)
     kHookNoCandReplay,        // VG_NO_CAND_REPLAY       no heap replay for queries whose scores may hold a NaN (vg_cand_replay.hpp): what the fast paths alone answer
-    kHookVamanaSmallScratch,  // VG_VAMANA_SMALL_SCRATCH vg_search_vamana with k > 512: 64 MiB of per-launch scratch, so that a small batch takes several launches
+    kHookVamanaSmallScratch,  // VG_VAMANA_SMALL_SCRATCH a small batch takes several launches: vg_search_vamana with k > 512 gets 64 MiB of per-launch scratch, the Vamana builders' visited bitmaps (VamanaBatch, vg_vamana_common.hpp) 64 KiB
     kHookFlatRescoreSample,   // VG_FLAT_RESCORE_SAMPLE  flat search: the main GEMM multiplies the sampled row tiles again (no append from the sample)
     kHookPthrForceHist,       // VG_PTHR_FORCE_HIST      vg_search_flat_probed_threshold without rerank: the top-max_results-by-histogram form, then the filter
     kHookCount
@@ -318,6 +318,18 @@ struct ArenaCall {
     T *get(int i) const
     {
         return reinterpret_cast<T *>(base + offs[static_cast<size_t>(i)]);
+    }
+};
+
+// One piece of a call's scratch after the other, each 256-byte aligned; base null: only the sizes are added up
+struct Carve {
+    char *base;
+    size_t off = 0;
+    template <typename T>
+    void take(T *&p, int64_t count)
+    {
+        p = base ? reinterpret_cast<T *>(base + off) : nullptr;
+        off += (static_cast<size_t>(count) * sizeof(T) + 255) & ~size_t(255);
     }
 };
 

@@ -169,7 +169,20 @@ inline int64_t scratch_cap(const vg_ctx *ctx)
     return std::min<int64_t>(16 * gib, std::max<int64_t>(gib, ctx->hbm_bytes / 16));
 }
 
-// A batch of graph walks in launches of `chunk` queries (walk_chunk, vg_walk_chunk.hpp), each query with a visited bitmap of
+// `count` graph walks in launches of at most `chunk` (walk_chunk, vg_walk_chunk.hpp), vis holding `chunk` visited bitmaps of
+// vis_words words: body(q0, cnt) walks q0 .. q0 + cnt - 1 over cleared bitmaps; the first status that is not VG_OK ends the batch
+template <class Body>
+inline int32_t for_each_walk_chunk(uint32_t *vis, int64_t vis_words, int64_t chunk, int64_t count, hipStream_t st, Body body)
+{
+    for (int64_t q0 = 0; q0 < count; q0 += chunk) {
+        const int64_t cnt = std::min(chunk, count - q0);
+        VG_HIP(hipMemsetAsync(vis, 0, static_cast<size_t>(cnt) * vis_words * 4, st));
+        VG_TRY(body(q0, cnt));
+    }
+    return VG_OK;
+}
+
+// A batch of graph walks in launches of `chunk` queries (for_each_walk_chunk), each query with a visited bitmap of
 // vis_words words of its own.  other_bytes: a query's scratch besides the bitmap.  add() before the arena's commit() — the
 // caller's pieces are chunk times a query's —, for_each() after it.
 struct WalkChunks {
@@ -186,16 +199,10 @@ struct WalkChunks {
         i_vis = a.add(sizeof(uint32_t) * static_cast<size_t>(chunk) * vis_words);
     }
     uint32_t *vis() const { return ar->get<uint32_t>(i_vis); }
-    // body(q0, cnt): queries q0 .. q0 + cnt - 1 over cleared bitmaps; the first status that is not VG_OK ends the batch
     template <class Body>
     int32_t for_each(hipStream_t st, Body body) const
     {
-        for (int64_t q0 = 0; q0 < nq; q0 += chunk) {
-            const int64_t cnt = std::min(chunk, nq - q0);
-            VG_HIP(hipMemsetAsync(vis(), 0, static_cast<size_t>(cnt) * vis_words * 4, st));
-            VG_TRY(body(q0, cnt));
-        }
-        return VG_OK;
+        return for_each_walk_chunk(vis(), vis_words, chunk, nq, st, body);
     }
 };
 
