@@ -270,6 +270,40 @@ def test_poor_sample_falls_back_to_the_scan(vg, ctx):
     verify(ids, sc, cnt, base, dim, q, thr, 100, L2, range(nq))
 
 
+@pytest.mark.parametrize("dim", [64, 100])   # the rows in registers; pairs scored from memory
+def test_scattered_fall_back_scans_each_slots_own_query(vg, ctx, dim):
+    """The input of test_poor_sample_falls_back_to_the_scan, 17 queries: those with i % 3 == 0 ask for nothing (threshold -1: the
+    user's threshold stands, the list is empty, the proof holds), the other 11 for everything (their lists overflow).  The scan
+    then answers 11 queries at slots that are not their query numbers, in passes of 8 and 3: slot s reads the query, threshold
+    and filter of query qmap[s].  The per-query filter has a different row for every query.
+    Rows sorted farthest first leave only the ~7000 rows after the last sampled tile under the sample threshold, and a filter
+    that keeps 30 % of them does not overflow a 4096-key list (measured: no fall-back).  So the farthest rows fill the tiles
+    the sample reads (every 64th tile of 128 rows) and the rest follow farthest first: every other row passes the sample
+    threshold, 30 % of them too."""
+    rng = np.random.default_rng(23 + dim)
+    n, nq = 40000, 17
+    base = rng.standard_normal((n, dim)).astype(np.float32)
+    centre = rng.standard_normal(dim).astype(np.float32)
+    far_first = np.argsort(-((base - centre) ** 2).sum(1))
+    sampled = (np.arange(n) // 128) % 64 == 0
+    order = np.empty(n, np.int64)
+    order[sampled] = far_first[:sampled.sum()]
+    order[~sampled] = far_first[sampled.sum():]
+    base = np.ascontiguousarray(base[order])
+    q = (centre + rng.standard_normal((nq, dim)).astype(np.float32) * 0.01).astype(np.float32)
+    idx = vg.Index(ctx, n, dim, vg.Metric.L2)
+    idx.set_vectors(base)
+    thr = np.full(nq, np.inf, np.float32)
+    thr[::3] = -1.0
+    per_query = rng.random((nq, n)) < 0.3
+    for mask in (None, per_query):
+        s0 = idx.flat_stats()
+        ids, sc, cnt = idx.search_flat_threshold(q, thr, 100, mask=mask)
+        s1 = idx.flat_stats()
+        assert s1[0] - s0[0] == nq and s1[1] - s0[1] == 11, (s1[0] - s0[0], s1[1] - s0[1])
+        verify(ids, sc, cnt, base, dim, q, thr, 100, L2, range(nq), mask=mask)
+
+
 def test_clustered_corpus(vg, ctx):
     """rows in tight clusters around a few centres (thousands of near-equal scores around every threshold); a batch is
     nominated, and what its proofs leave is scanned"""

@@ -3,7 +3,8 @@
 //   Score <= threshold (L2) / Score >= threshold (Dot, Cosine), best first.
 //   1. one pass over the rows scores every row against up to 8 queries in the reference's summation order and
 //      appends the key (score bits, row id) of every row whose EXACT score passes its query's threshold to that
-//      query's list in HBM (n keys per query: it cannot overflow, nothing is left to prove)
+//      query's list in HBM (n keys per query: it cannot overflow, nothing is left to prove): launch_thr_scan_f32, the
+//      probed threshold search's exact scan (k_probed_threshold.hip)
 //   2. per query the best min(count, max_results) keys of its list: a bitonic sort in LDS, or — a list longer
 //      than the LDS buffer — a radix select of the max_results-th key over the list first
 //   3. queries whose scores may hold a NaN: the reference's heap replayed with k = max_results (vg_cand_replay.hpp),
@@ -18,8 +19,6 @@
 
 namespace vg {
 
-constexpr int kThrMaxResults = 16384;  // the selection's LDS buffer (128 KiB of keys) and the replay's heap
-constexpr int kThrQB = 8;              // queries one pass over the rows carries
 constexpr int kThrSelThreads = 1024;
 constexpr int kThrSelWaves = kThrSelThreads / 64;
 
@@ -28,65 +27,6 @@ template <bool DOT>
 __device__ __forceinline__ bool thr_keep(float score, float t)
 {
     return DOT ? score >= t : score <= t;
-}
-
-// ---- 1. the scan: every row against up to kThrQB queries, the rows within a query's threshold appended ----------
-// Slot j of the pass is query qmap[j] (null: j) of the arrays passed.  REGS: the row is loaded once into registers (dim % 4 == 0, 64 <= dim <= 1024,
-// 16-byte aligned rows) and scored against the queries in LDS (exact_rowregs16, the flat scan's form); otherwise every
-// pair is scored from memory (exact_pair16, any dim).  Both are the reference's kPair order.
-// mask: bit i of byte i / 8 of query q's filter at mask + q * mask_stride (stride 0: one filter), or null.
-template <bool DOT, bool REGS>
-__global__ __launch_bounds__(256) void flat_thr_scan_kernel(const float *__restrict__ base, int64_t n, int dim,
-                                                            const float *__restrict__ queries, const float *__restrict__ thr,
-                                                            const int *__restrict__ qmap, int nq, int slices, const uint8_t *__restrict__ mask,
-                                                            int64_t mask_stride, int64_t list_cap, uint64_t *__restrict__ lists,
-                                                            int *__restrict__ counts)
-{
-    extern __shared__ float qlds[];  // REGS: nq * dim floats
-    const int s = blockIdx.x;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    if (REGS) {
-        for (int t = tid; t < nq * dim; t += 256) {
-            const int qi = t / dim;
-            qlds[t] = queries[static_cast<int64_t>(qmap ? qmap[qi] : qi) * dim + (t - qi * dim)];
-        }
-        __syncthreads();
-    }
-    float tq[kThrQB];
-    const uint8_t *mq[kThrQB];
-    const float *qv[kThrQB];
-#pragma unroll
-    for (int qi = 0; qi < kThrQB; qi++) {
-        const int64_t qq = qi < nq ? (qmap ? qmap[qi] : qi) : 0;
-        tq[qi] = thr[qq];
-        mq[qi] = mask ? mask + qq * mask_stride : nullptr;
-        qv[qi] = queries + qq * dim;
-    }
-    const Sub16 sub = Sub16::make(tid);
-    const int nblk = dim >> 6;
-    const int64_t r0 = n * s / slices, r1 = n * (s + 1) / slices;
-    for (int64_t i0 = r0 + wave * 4; i0 < r1; i0 += 16) {
-        const int64_t i = i0 + (lane >> 4);
-        const bool live = i < r1;
-        const float *row = base + (live ? i : r1 - 1) * dim;
-        float4 rr[16];
-        if (REGS) {
-            const float4 *r4 = reinterpret_cast<const float4 *>(row) + sub.f4;
-#pragma unroll
-            for (int e = 0; e < 16; e++)
-                if (e < nblk) rr[e] = load_stream(r4 + e * 16);
-        }
-#pragma unroll
-        for (int qi = 0; qi < kThrQB; qi++) {
-            if (qi < nq) {
-                const float v = REGS ? exact_rowregs16<DOT>(rr, nblk, row, qlds + static_cast<size_t>(qi) * dim, dim, sub)
-                                     : exact_pair16<DOT, kPair>(row, qv[qi], dim, sub);
-                const bool pass = live && (lane & 15) == 0 && thr_keep<DOT>(v, tq[qi]) && mask_bit(mq[qi], i);
-                wave_append(pass, make_key(v, static_cast<uint32_t>(i), DOT), counts + qi,
-                            lists + static_cast<int64_t>(qi) * list_cap, lane);
-            }
-        }
-    }
 }
 
 // ---- 2. selection: the best min(count, max_results) keys of a list, in order ----------------------------------------
@@ -196,32 +136,34 @@ __global__ __launch_bounds__(64) void flat_thr_filter_kernel(const float *__rest
     if (lane == 0) out_counts[q] = kept;
 }
 
-// the two steps above for lists another search fills: vg_search_vamana's large-k walk leaves each query's result heap as a
-// list of k keys (kKeyMax after the last), vg_search_vamana_threshold filters what that search returns
-int32_t launch_thr_select_lists(bool desc, const uint64_t *lists, int64_t list_cap, const int *counts, int64_t nq, int max_results,
-                                uint32_t *ids, float *scores, int32_t *out_counts, hipStream_t st)
+// the two steps above, for this file's lists and for those another search fills: the probed scans' (k_probed_threshold.hip) and
+// the result heap vg_search_vamana's large-k walk leaves as a list of k keys (kKeyMax after the last)
+int32_t launch_thr_select_lists(bool desc, const uint64_t *lists, int64_t list_cap, const int *counts, const int *qmap, int64_t nq,
+                                int64_t longest, int max_results, uint32_t *ids, float *scores, int32_t *out_counts, hipStream_t st)
 {
     if (nq == 0) return VG_OK;
-    int sbuf = 64;
-    while (sbuf < max_results) sbuf <<= 1;
-    const size_t lds = sizeof(uint64_t) * static_cast<size_t>(sbuf) + kThrSelWaves * 256 * sizeof(unsigned);
-    const size_t lds_max = sizeof(uint64_t) * static_cast<size_t>(kThrMaxResults) + kThrSelWaves * 256 * sizeof(unsigned);
-    auto sel = desc ? flat_thr_select_kernel<true> : flat_thr_select_kernel<false>;
-    VG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(sel), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds_max)));
-    VG_LAUNCH(sel, dim3(static_cast<unsigned>(nq)), dim3(kThrSelThreads), lds, st, lists, list_cap, counts, max_results, sbuf, nullptr,
-              ids, scores, out_counts);
-    return VG_OK;
+    int sbuf = 64;  // the LDS keys: the longest list that can occur, at least max_results, at most kThrMaxResults
+    while (sbuf < std::max<int64_t>(max_results, std::min<int64_t>(longest, kThrMaxResults))) sbuf <<= 1;
+    const size_t hist = kThrSelWaves * 256 * sizeof(unsigned);
+    return with_metric(desc, [&](auto dot) -> int32_t {
+        auto sel = flat_thr_select_kernel<decltype(dot)::value>;
+        VG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(sel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   static_cast<int>(sizeof(uint64_t) * kThrMaxResults + hist)));
+        VG_LAUNCH(sel, dim3(static_cast<unsigned>(nq)), dim3(kThrSelThreads), sizeof(uint64_t) * static_cast<size_t>(sbuf) + hist, st, lists,
+                  list_cap, counts, max_results, sbuf, qmap, ids, scores, out_counts);
+        return VG_OK;
+    });
 }
 
 int32_t launch_thr_filter(bool desc, const float *thr, int64_t nq, int max_results, uint32_t *ids, float *scores, int32_t *counts,
                           hipStream_t st)
 {
     if (nq == 0) return VG_OK;
-    if (desc)
-        VG_LAUNCH(flat_thr_filter_kernel<true>, dim3(static_cast<unsigned>(nq)), dim3(64), 0, st, thr, max_results, ids, scores, counts);
-    else
-        VG_LAUNCH(flat_thr_filter_kernel<false>, dim3(static_cast<unsigned>(nq)), dim3(64), 0, st, thr, max_results, ids, scores, counts);
-    return VG_OK;
+    return with_metric(desc, [&](auto dot) -> int32_t {
+        VG_LAUNCH(flat_thr_filter_kernel<decltype(dot)::value>, dim3(static_cast<unsigned>(nq)), dim3(64), 0, st, thr, max_results, ids,
+                  scores, counts);
+        return VG_OK;
+    });
 }
 
 // ---- batches: the rows the nomination appended (GEMM keys), re-scored exactly; those within the threshold go to the list ---------
@@ -255,21 +197,18 @@ __global__ __launch_bounds__(256) void flat_thr_rescore_kernel(const float *__re
     }
 }
 
-// Segment.Rerank over a search's result rows (ids[nq * cap], VG_INVALID_ID where unused): the exact scores within each query's
-// threshold, as keys in lists[nq * cap] / list_counts[nq] (zeroed here)
-int32_t launch_thr_rescore_ids(bool desc, const float *base, int dim, const float *queries, const float *thr, const uint32_t *ids,
-                               int64_t nq, int cap, uint64_t *lists, int *list_counts, hipStream_t st)
+int32_t launch_thr_rescore(bool desc, const float *base, int dim, const float *queries, const float *thr, const uint64_t *cand,
+                           const int *cand_counts, const uint32_t *cand_ids, int64_t nq, int cap, uint64_t *lists, int *list_counts,
+                           hipStream_t st)
 {
     if (nq == 0 || cap == 0) return VG_OK;
     VG_HIP(hipMemsetAsync(list_counts, 0, sizeof(int) * static_cast<size_t>(nq), st));
     const dim3 grid(static_cast<unsigned>(std::min(32, std::max(1, cap / 2048))), static_cast<unsigned>(nq));
-    if (desc)
-        VG_LAUNCH(flat_thr_rescore_kernel<true>, grid, dim3(256), 0, st, base, dim, queries, thr, nullptr, ids, nullptr, cap, lists,
-                  list_counts);
-    else
-        VG_LAUNCH(flat_thr_rescore_kernel<false>, grid, dim3(256), 0, st, base, dim, queries, thr, nullptr, ids, nullptr, cap, lists,
-                  list_counts);
-    return VG_OK;
+    return with_metric(desc, [&](auto dot) -> int32_t {
+        VG_LAUNCH(flat_thr_rescore_kernel<decltype(dot)::value>, grid, dim3(256), 0, st, base, dim, queries, thr, cand, cand_ids,
+                  cand_counts, cap, lists, list_counts);
+        return VG_OK;
+    });
 }
 
 // The proof of a nominated query (one thread per query).  The user's threshold stood (untight = 1) and the list did not
@@ -304,20 +243,6 @@ __global__ void flat_thr_stats_kernel(unsigned long long *__restrict__ stats, lo
     }
 }
 
-template <bool DOT>
-static int32_t launch_thr_pass(bool regs, unsigned slices, size_t lds, hipStream_t st, const float *base, int64_t n, int dim,
-                               const float *queries, const float *thr, const int *qmap, int cnt, const uint8_t *mask, int64_t mask_stride,
-                               int64_t list_cap, uint64_t *lists, int *counts)
-{
-    if (regs)
-        VG_LAUNCH((flat_thr_scan_kernel<DOT, true>), dim3(slices), dim3(256), lds, st, base, n, dim, queries, thr, qmap, cnt,
-                  static_cast<int>(slices), mask, mask_stride, list_cap, lists, counts);
-    else
-        VG_LAUNCH((flat_thr_scan_kernel<DOT, false>), dim3(slices), dim3(256), 0, st, base, n, dim, queries, thr, qmap, cnt,
-                  static_cast<int>(slices), mask, mask_stride, list_cap, lists, counts);
-    return VG_OK;
-}
-
 }  // namespace vg
 
 VG_API int32_t vg_search_flat_threshold(vg_index *idx, const float *queries, int64_t nq, const float *thresholds,
@@ -337,29 +262,12 @@ VG_API int32_t vg_search_flat_threshold(vg_index *idx, const float *queries, int
     VG_CHECK(queries && thresholds && ids && scores && counts, VG_ERR_INVALID_ARG, "vg_search_flat_threshold: NULL buffer");
     VG_CHECK(idx->n == 0 || idx->d_vectors, VG_ERR_NOT_READY, "vg_search_flat_threshold: index has no fp32 vectors");
     VG_CHECK_MASK_STRIDE("vg_search_flat_threshold", mask, mask_stride, idx->n);
-    VG_HIP(hipSetDevice(idx->ctx->device));
-    hipStream_t st = vg::pick_stream(idx->ctx, stream);
+    vg::ThrIO io;
+    VG_TRY(io.init(idx, stream, queries, nq, thresholds, max_results, mask, mask_stride, ids, scores, counts));
+    hipStream_t st = io.st;
     const bool dot = idx->metric != VG_METRIC_L2;
     const int64_t n = idx->n;
     const int dim = idx->dim;
-    const size_t out_n = static_cast<size_t>(nq) * max_results;
-
-    vg::DevIn<float> q, t;
-    vg::DevIn<uint8_t> mk;
-    vg::DevOut<uint32_t> oid;
-    vg::DevOut<float> osc;
-    vg::DevOut<int32_t> ocnt;
-    VG_TRY(q.init(queries, static_cast<size_t>(nq) * dim, st));
-    VG_TRY(t.init(thresholds, static_cast<size_t>(nq), st));
-    VG_TRY(mk.init(mask, vg::mask_span(mask, mask_stride, nq, idx->n), st));
-    VG_TRY(oid.init(ids, out_n, st));
-    VG_TRY(osc.init(scores, out_n, st));
-    VG_TRY(ocnt.init(counts, static_cast<size_t>(nq), st));
-
-    // the register form of the scan: rows of whole float4 (dim % 4 == 0, 16-byte aligned), up to 16 float4 per lane
-    const bool regs = dim % 4 == 0 && dim >= 64 && dim <= 1024 && (reinterpret_cast<uintptr_t>(idx->d_vectors) & 15) == 0;
-    const unsigned slices = static_cast<unsigned>(std::min<int64_t>(4 * idx->ctx->compute_units, std::max<int64_t>(1, n / 64)));
-    const size_t scan_lds = regs ? sizeof(float) * static_cast<size_t>(vg::kThrQB) * dim : 0;
     const int64_t list_cap = std::max<int64_t>(n, 1);
     // batches of more than kThrQB queries are nominated on the matrix cores (test hooks: VG_FLAT_NO_SCAN nominates every batch,
     // VG_FLAT_FORCE_EXACT scans every query); the rest, and the queries whose proof fails, take the scan
@@ -381,13 +289,6 @@ VG_API int32_t vg_search_flat_threshold(vg_index *idx, const float *queries, int
     int64_t qc = std::min<int64_t>(4096, std::max<int64_t>(128, (int64_t(1) << 25) / cap));  // whole 128-query tiles, <= 2^25 keys
     qc = std::min<int64_t>(qc, nq);
     if (!nominate) qc = 0;
-    const int64_t list_rows = std::max<int64_t>(list_cap, 1);
-    int sbuf = 64;  // the selection's LDS keys: the longest list that can occur, at least max_results, at most 16384
-    while (sbuf < std::min<int64_t>(vg::kThrMaxResults, std::max<int64_t>(std::max<int64_t>(list_rows, nominate ? cap : 0), max_results)))
-        sbuf <<= 1;
-    const size_t sel_lds = sizeof(uint64_t) * static_cast<size_t>(sbuf) + vg::kThrSelWaves * 256 * sizeof(unsigned);
-    auto sel = dot ? vg::flat_thr_select_kernel<true> : vg::flat_thr_select_kernel<false>;
-    VG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(sel), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(sel_lds)));
 
     vg::ArenaCall ar(idx->ctx, st);
     const int i_lists = ar.add(sizeof(uint64_t) * static_cast<size_t>(vg::kThrQB) * list_cap);
@@ -418,21 +319,16 @@ VG_API int32_t vg_search_flat_threshold(vg_index *idx, const float *queries, int
         VG_HIP(hipMemsetAsync(cnt, 0, sizeof(int) * vg::kThrQB, st));
         if (n > 0) {
             vg::ProfScope prof(idx->ctx, "flat_thr_scan", st);
-            VG_TRY(dot ? vg::launch_thr_pass<true>(regs, slices, scan_lds, st, idx->d_vectors, n, dim, qp, tp, qmap, c, m0, mask_stride,
-                                                   list_cap, lists, cnt)
-                       : vg::launch_thr_pass<false>(regs, slices, scan_lds, st, idx->d_vectors, n, dim, qp, tp, qmap, c, m0, mask_stride,
-                                                    list_cap, lists, cnt));
+            VG_TRY(vg::launch_thr_scan_f32(idx, qp, tp, qmap, c, m0, mask_stride, list_cap, lists, cnt, st));
         }
         vg::ProfScope prof(idx->ctx, "flat_thr_select", st);
-        VG_LAUNCH(sel, dim3(static_cast<unsigned>(c)), dim3(vg::kThrSelThreads), sel_lds, st, lists, list_cap, cnt, max_results, sbuf,
-                  qmap, oi, os, oc);
-        return VG_OK;
+        return vg::launch_thr_select_lists(dot, lists, list_cap, cnt, qmap, c, list_cap, max_results, oi, os, oc, st);
     };
     if (!nominate) {
         for (int64_t q0 = 0; q0 < nq; q0 += vg::kThrQB) {
             const int c = static_cast<int>(std::min<int64_t>(vg::kThrQB, nq - q0));
-            VG_TRY(scan(q.ptr + q0 * dim, t.ptr + q0, mk.ptr ? mk.ptr + q0 * mask_stride : nullptr, nullptr, c, oid.ptr + q0 * max_results,
-                        osc.ptr + q0 * max_results, ocnt.ptr + q0));
+            VG_TRY(scan(io.q.ptr + q0 * dim, io.t.ptr + q0, io.mk.ptr ? io.mk.ptr + q0 * mask_stride : nullptr, nullptr, c,
+                        io.oid.ptr + q0 * max_results, io.osc.ptr + q0 * max_results, io.ocnt.ptr + q0));
         }
         // (as vg_search_flat's small-batch scan: queries searched; VG_FLAT_FORCE_EXACT counts them as the exhaustive kernel's)
         if (idx->d_flat_stats)
@@ -447,41 +343,31 @@ VG_API int32_t vg_search_flat_threshold(vg_index *idx, const float *queries, int
         int *fail = ar.get<int>(i_fail), *todo = ar.get<int>(i_todo), *ecount = ar.get<int>(i_ecount);
         int *always = fail + qc;  // (flat_todo_kernel's "every query" switch: off)
         VG_HIP(hipMemsetAsync(always, 0, sizeof(int), st));
-        const unsigned rescore_wgs = static_cast<unsigned>(std::min(32, std::max(1, cap / 2048)));
         for (int64_t q0 = 0; q0 < nq; q0 += qc) {
             const int64_t c = std::min(qc, nq - q0);
-            const unsigned uc = static_cast<unsigned>(c);
-            const float *qp = q.ptr + q0 * dim, *tp = t.ptr + q0;
-            const uint8_t *m0 = mk.ptr ? mk.ptr + q0 * mask_stride : nullptr;
-            uint32_t *oi = oid.ptr + q0 * max_results;
-            float *os = osc.ptr + q0 * max_results;
-            int32_t *oc = ocnt.ptr + q0;
+            const float *qp = io.q.ptr + q0 * dim, *tp = io.t.ptr + q0;
+            const uint8_t *m0 = io.mk.ptr ? io.mk.ptr + q0 * mask_stride : nullptr;
+            uint32_t *oi = io.oid.ptr + q0 * max_results;
+            float *os = io.osc.ptr + q0 * max_results;
+            int32_t *oc = io.ocnt.ptr + q0;
             // (a) every row below the query's append threshold (the user's, widened, or the sample's) is appended
             VG_TRY(vg::flat_thr_nominate(idx, st, qp, tp, c, m0, mask_stride, cap, sel_k, sample_stride, bf16, eps_extra, sc, partial, sid,
                                          sthr, qbf, cwide, gthr, qnorm, untight, gcounts, cand));
             // (b) re-scored exactly; the rows within the user's threshold form the query's list; (c) its best max_results
-            VG_HIP(hipMemsetAsync(ecount, 0, sizeof(int) * static_cast<size_t>(c), st));
             {
                 vg::ProfScope prof(idx->ctx, "flat_thr_rescore", st);
-                if (dot)
-                    VG_LAUNCH(vg::flat_thr_rescore_kernel<true>, dim3(rescore_wgs, uc), dim3(256), 0, st, idx->d_vectors, dim, qp, tp, cand,
-                              nullptr, gcounts, cap, elist, ecount);
-                else
-                    VG_LAUNCH(vg::flat_thr_rescore_kernel<false>, dim3(rescore_wgs, uc), dim3(256), 0, st, idx->d_vectors, dim, qp, tp, cand,
-                              nullptr, gcounts, cap, elist, ecount);
+                VG_TRY(vg::launch_thr_rescore(dot, idx->d_vectors, dim, qp, tp, cand, gcounts, nullptr, c, cap, elist, ecount, st));
             }
             {
                 vg::ProfScope prof(idx->ctx, "flat_thr_select", st);
-                VG_LAUNCH(sel, dim3(uc), dim3(vg::kThrSelThreads), sel_lds, st, elist, static_cast<int64_t>(cap), ecount, max_results, sbuf,
-                          nullptr, oi, os, oc);
+                VG_TRY(vg::launch_thr_select_lists(dot, elist, cap, ecount, nullptr, c, cap, max_results, oi, os, oc, st));
             }
             // (d) the proof; the queries it leaves go to the scan, kThrQB per pass over the rows
-            if (dot)
-                VG_LAUNCH(vg::flat_thr_proof_kernel<true>, dim3(static_cast<unsigned>((c + 255) / 256)), dim3(256), 0, st, c, untight, gcounts,
-                          cap, gthr, qnorm, idx->d_norm_max, dim, eps_extra, max_results, oc, os, fail);
-            else
-                VG_LAUNCH(vg::flat_thr_proof_kernel<false>, dim3(static_cast<unsigned>((c + 255) / 256)), dim3(256), 0, st, c, untight, gcounts,
-                          cap, gthr, qnorm, idx->d_norm_max, dim, eps_extra, max_results, oc, os, fail);
+            VG_TRY(vg::with_metric(dot, [&](auto dot_c) -> int32_t {
+                VG_LAUNCH(vg::flat_thr_proof_kernel<decltype(dot_c)::value>, dim3(static_cast<unsigned>((c + 255) / 256)), dim3(256), 0, st, c,
+                          untight, gcounts, cap, gthr, qnorm, idx->d_norm_max, dim, eps_extra, max_results, oc, os, fail);
+                return VG_OK;
+            }));
             VG_TRY(vg::launch_flat_todo(fail, always, static_cast<int>(c), todo, idx->d_flat_stats, st));
             int ntodo = 0;
             VG_HIP(hipMemcpyAsync(&ntodo, todo, sizeof(int), hipMemcpyDeviceToHost, st));
@@ -492,19 +378,10 @@ VG_API int32_t vg_search_flat_threshold(vg_index *idx, const float *queries, int
     }
     // queries whose scores may hold a NaN: flat.Segment.Search(q, max_results) as its heap answers it, then the filter
     if (n > 0) {
-        VG_TRY(vg::launch_cand_replay(vg::FlatF32Scorer{idx->d_vectors, idx->d_norm_max + 1, dim, dot, 0}, q.ptr, dim, n, nq,
-                                      max_results, dot, mk.ptr, mask_stride, oid.ptr, osc.ptr, st));
-        if (!vg::hook(vg::kHookNoCandReplay)) {
-            if (dot)
-                VG_LAUNCH(vg::flat_thr_filter_kernel<true>, dim3(static_cast<unsigned>(nq)), dim3(64), 0, st, t.ptr, max_results,
-                          oid.ptr, osc.ptr, ocnt.ptr);
-            else
-                VG_LAUNCH(vg::flat_thr_filter_kernel<false>, dim3(static_cast<unsigned>(nq)), dim3(64), 0, st, t.ptr, max_results,
-                          oid.ptr, osc.ptr, ocnt.ptr);
-        }
+        VG_TRY(vg::launch_cand_replay(vg::FlatF32Scorer{idx->d_vectors, idx->d_norm_max + 1, dim, dot, 0}, io.q.ptr, dim, n, nq,
+                                      max_results, dot, io.mk.ptr, mask_stride, io.oid.ptr, io.osc.ptr, st));
+        if (!vg::hook(vg::kHookNoCandReplay))
+            VG_TRY(vg::launch_thr_filter(dot, io.t.ptr, nq, max_results, io.oid.ptr, io.osc.ptr, io.ocnt.ptr, st));
     }
-    VG_TRY(oid.finish());
-    VG_TRY(osc.finish());
-    VG_TRY(ocnt.finish());
-    return VG_OK;
+    return io.finish();
 }

@@ -1062,7 +1062,7 @@ static int32_t vamana_impl(vg_index *idx, const float *queries, int64_t nq, int3
         VG_TRY(with_vamana_kind(inst, [&](auto kind_c) { return walk(kind_c, false); }));
         if (huge)  // each query's heap, as a list of k keys in its scratch, best first into ids / scores
             VG_TRY(vg::launch_thr_select_lists(idx->metric != VG_METRIC_L2, reinterpret_cast<const uint64_t *>(cand + (cand_cap - k)),
-                                               cand_cap, lcnt, cnt, k, io.oid.ptr + q0 * k, io.osc.ptr + q0 * k, lcnt + chunk, st));
+                                               cand_cap, lcnt, nullptr, cnt, k, k, io.oid.ptr + q0 * k, io.osc.ptr + q0 * k, lcnt + chunk, st));
         // the queries whose distances may hold a NaN, again with the reference's CandidateHeap (every other query returns at once)
         if (!vg::hook(vg::kHookNoCandReplay)) VG_TRY(with_vamana_kind(inst, [&](auto kind_c) { return walk(kind_c, true); }));
         return VG_OK;

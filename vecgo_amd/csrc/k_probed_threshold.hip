@@ -28,25 +28,26 @@
 
 namespace vg {
 
-constexpr int kPthrMaxResults = 16384;  // flat_thr_select_kernel's LDS buffer and the replay's heap
-constexpr int kPthrQB = 8;              // queries one pass over the whole segment carries (fp32, SQ8)
 constexpr int kPthrBins = 65536;        // the top 16 bits of a key
 constexpr size_t kPthrLutMax = 96 * 1024;  // a PQ table image the scan holds in LDS (m <= 96 at 256 centroids)
 enum PthrMode { kPthrThr = 0, kPthrHist = 1, kPthrBin = 2 };
 
+// the query of slot s of a launch (qmap null: s)
+__device__ __forceinline__ int64_t pthr_query(const int *__restrict__ qmap, int64_t s) { return qmap ? qmap[s] : s; }
+
 // ---- the row scorers ----------------------------------------------------------------------------------------------------
 // kRows rows per wave step, row_of(lane) the lane's row within the step, owner(lane) the lane that reports it.  prepare() once per
-// workgroup (queries: the pass's first query; LDS staging), begin_row() per step, score() per (step, query of the pass) by ALL
-// lanes of the wave.  Scores are bit for bit vg_search_flat_probed's for the same row.
+// workgroup (queries: the launch's; the pass is slots q0 .. q0 + cnt - 1; LDS staging), begin_row() per step, score() per (step,
+// slot qi of the pass, q its query) by ALL lanes of the wave.  Scores are bit for bit vg_search_flat_probed's for the same row.
 
 // fp32 rows, 16 lanes per row (flat/segment.go:691-701).  REGS: the row once into registers, the queries in LDS
 // (exact_rowregs16: dim % 4 == 0, 64 <= dim <= 1024, 16-byte aligned rows); else every pair from memory (exact_pair16, any dim)
 template <bool DOT, bool REGS>
 struct PthrF32 {
     static constexpr int kRows = 4;
+    static constexpr bool desc = DOT;
     const float *base;
     int dim;
-    bool desc;
     struct Row {
         Sub16 sub;
         const float *row;
@@ -54,11 +55,14 @@ struct PthrF32 {
     };
     __device__ static int row_of(int lane) { return lane >> 4; }
     __device__ static bool owner(int lane) { return (lane & 15) == 0; }
-    __device__ void prepare(Row &r, float *lds, const float *queries, int64_t, int cnt, int tid) const
+    __device__ void prepare(Row &r, float *lds, const float *queries, const int *qmap, int64_t q0, int cnt, int tid) const
     {
         r.sub = Sub16::make(tid);
         if (REGS) {
-            for (int t = tid; t < cnt * dim; t += 256) lds[t] = queries[t];
+            for (int t = tid; t < cnt * dim; t += 256) {
+                const int qi = t / dim;
+                lds[t] = queries[pthr_query(qmap, q0 + qi) * dim + (t - qi * dim)];
+            }
             __syncthreads();
         }
     }
@@ -71,13 +75,13 @@ struct PthrF32 {
             const int nblk = dim >> 6;
 #pragma unroll
             for (int e = 0; e < 16; e++)
-                if (e < nblk) r.rr[e] = r4[e * 16];
+                if (e < nblk) r.rr[e] = load_stream(r4 + e * 16);  // (a pass reads a row once)
         }
     }
-    __device__ float score(const Row &r, const float *lds, const float *queries, int qi) const
+    __device__ float score(const Row &r, const float *lds, const float *q, int qi) const
     {
         return REGS ? exact_rowregs16<DOT>(r.rr, dim >> 6, r.row, lds + static_cast<size_t>(qi) * dim, dim, r.sub)
-                    : exact_pair16<DOT, kPair>(r.row, queries + static_cast<int64_t>(qi) * dim, dim, r.sub);
+                    : exact_pair16<DOT, kPair>(r.row, q, dim, r.sub);
     }
 };
 
@@ -85,20 +89,20 @@ struct PthrF32 {
 template <bool DOT>
 struct PthrSq8 {
     static constexpr int kRows = 64;
+    static constexpr bool desc = DOT;
     const uint4 *tiles;
     const float *mins, *inv;
     int groups, dim;
-    bool desc;
     struct Row {
         const uint4 *tp;
     };
     __device__ static int row_of(int lane) { return lane; }
     __device__ static bool owner(int) { return true; }
-    __device__ void prepare(Row &, float *, const float *, int64_t, int, int) const {}
+    __device__ void prepare(Row &, float *, const float *, const int *, int64_t, int, int) const {}
     __device__ void begin_row(Row &r, int64_t row, int lane) const { r.tp = tiles + ((row >> 6) * groups) * 64 + lane; }
-    __device__ float score(const Row &r, const float *, const float *queries, int qi) const
+    __device__ float score(const Row &r, const float *, const float *q, int) const
     {
-        return sq8_row_score<DOT>(r.tp, groups, dim >> 4, dim & 15, queries + static_cast<int64_t>(qi) * dim, mins, inv);
+        return sq8_row_score<DOT>(r.tp, groups, dim >> 4, dim & 15, q, mins, inv);
     }
 };
 
@@ -106,7 +110,7 @@ struct PthrSq8 {
 struct PthrPq {
     static constexpr int kRows = 64;
     const uint4 *tiles;
-    const float *tables;  // per query of the launch: lut_image_words(m)
+    const float *tables;  // per slot of the launch: lut_image_words(m)
     int m, groups;
     bool desc;
     struct Row {
@@ -115,7 +119,7 @@ struct PthrPq {
     };
     __device__ static int row_of(int lane) { return lane; }
     __device__ static bool owner(int) { return true; }
-    __device__ void prepare(Row &, float *lds, const float *, int64_t q0, int, int tid) const
+    __device__ void prepare(Row &, float *lds, const float *, const int *, int64_t q0, int, int tid) const
     {
         const int n4 = lut_image_words(m) / 4;
         const float4 *src = reinterpret_cast<const float4 *>(tables + q0 * lut_image_words(m));
@@ -160,17 +164,19 @@ __device__ __forceinline__ void wave_hist(bool on, uint32_t bin, uint32_t *tags,
 }
 
 // ---- the scan ----------------------------------------------------------------------------------------------------------
-// grid (slice, range j, pass): pass g carries queries g * QB .. of the launch.  probes (QB == 1): range j is partition
-// probes[q * np + j], rows part_off[p] .. part_off[p + 1] — it may start anywhere inside a wave step, an empty partition is two
+// grid (slice, range j, pass): pass g carries slots g * QB .. of the launch's nq.  Slot s answers query q = qmap[s] (null: s — the
+// queries a failed proof sends back to vg_search_flat_threshold are scattered): it reads q's row of queries, thr and mask, and
+// writes list, count, histogram and cut s.  probes (QB == 1, no qmap): range j is partition
+// probes[s * np + j], rows part_off[p] .. part_off[p + 1] — it may start anywhere inside a wave step, an empty partition is two
 // equal offsets; null: piece j of np equal pieces of the whole segment.  A range is walked in steps of S::kRows rows aligned to
 // kRows (the SQ8 / PQ tiles), the rows outside it masked.  mask: bit i of byte i / 8 of query q's filter at
 // mask + q * mask_stride (stride 0: one filter), or null.
-// MODE kPthrThr: a row whose score passes thr[q] is appended to lists[q]; kPthrHist: bin (key >> 48) of hist[q] counts it;
-// kPthrBin: appended when its bin is at or below cut[q].
+// MODE kPthrThr: a row whose score passes thr[q] is appended to lists[s]; kPthrHist: bin (key >> 48) of hist[s] counts it;
+// kPthrBin: appended when its bin is at or below cut[s].
 template <class S, int MODE, int QB>
-__global__ __launch_bounds__(256) void pthr_scan_kernel(const S sc, const float *__restrict__ queries, int dim, int64_t nq, int64_t n,
-                                                        const uint32_t *__restrict__ probes, const uint32_t *__restrict__ part_off,
-                                                        int np, int sub_n, const float *__restrict__ thr,
+__global__ __launch_bounds__(256) void pthr_scan_kernel(const S sc, const float *__restrict__ queries, const int *__restrict__ qmap, int dim,
+                                                        int64_t nq, int64_t n, const uint32_t *__restrict__ probes,
+                                                        const uint32_t *__restrict__ part_off, int np, int sub_n, const float *__restrict__ thr,
                                                         const uint32_t *__restrict__ cut, const uint8_t *__restrict__ mask,
                                                         int64_t mask_stride, int64_t list_cap, uint64_t *__restrict__ lists,
                                                         int *__restrict__ counts, unsigned *__restrict__ hist, int scorer_lds_words)
@@ -190,18 +196,19 @@ __global__ __launch_bounds__(256) void pthr_scan_kernel(const S sc, const float 
         R1 = n * (j + 1) / np;
     }
     if (R1 <= R0) return;  // (the whole workgroup)
-    const float *qv = queries + q0 * dim;
     typename S::Row rs;
-    sc.prepare(rs, pthr_lds, qv, q0, cnt, tid);
+    sc.prepare(rs, pthr_lds, queries, qmap, q0, cnt, tid);
     float tq[QB];
     uint32_t cq[QB];
     const uint8_t *mq[QB];
+    const float *qv[QB];
 #pragma unroll
     for (int qi = 0; qi < QB; qi++) {
-        const int64_t qq = qi < cnt ? q0 + qi : q0;
+        const int64_t slot = qi < cnt ? q0 + qi : q0, qq = pthr_query(qmap, slot);
         tq[qi] = MODE == kPthrThr ? thr[qq] : 0.0f;
-        cq[qi] = MODE == kPthrBin ? cut[qq] : 0u;
+        cq[qi] = MODE == kPthrBin ? cut[slot] : 0u;
         mq[qi] = mask ? mask + qq * mask_stride : nullptr;
+        qv[qi] = queries + qq * dim;
     }
     uint32_t *htags = reinterpret_cast<uint32_t *>(pthr_lds + scorer_lds_words);
     unsigned *hslots = htags + QB * kPthrSlots;
@@ -228,7 +235,7 @@ __global__ __launch_bounds__(256) void pthr_scan_kernel(const S sc, const float 
 #pragma unroll
         for (int qi = 0; qi < QB; qi++) {
             if (qi < cnt) {
-                const float v = sc.score(rs, pthr_lds, qv, qi);
+                const float v = sc.score(rs, pthr_lds, qv[qi], qi);
                 const uint64_t key = make_key(v, static_cast<uint32_t>(row), sc.desc);
                 const bool live = in && S::owner(lane) && mask_bit(mq[qi], in ? row : R0);
                 const uint32_t bin = static_cast<uint32_t>(key >> 48);
@@ -280,6 +287,7 @@ __global__ __launch_bounds__(1024) void pthr_cut_kernel(const unsigned *__restri
 
 struct PthrArgs {
     const float *queries;
+    const int *qmap;
     int dim;
     int64_t nq, n;
     const uint32_t *probes, *part_off;
@@ -301,8 +309,8 @@ static int32_t launch_pthr(const S &sc, int mode, size_t lds, const PthrArgs &a,
     auto go = [&](auto kern) -> int32_t {
         if (bytes > 48 * 1024)
             VG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(bytes)));
-        VG_LAUNCH(kern, grid, dim3(256), bytes, st, sc, a.queries, a.dim, a.nq, a.n, a.probes, a.part_off, a.np, a.sub, a.thr, a.cut, a.mask,
-                  a.mask_stride, a.list_cap, a.lists, a.counts, a.hist, static_cast<int>(lds / sizeof(float)));
+        VG_LAUNCH(kern, grid, dim3(256), bytes, st, sc, a.queries, a.qmap, a.dim, a.nq, a.n, a.probes, a.part_off, a.np, a.sub, a.thr, a.cut,
+                  a.mask, a.mask_stride, a.list_cap, a.lists, a.counts, a.hist, static_cast<int>(lds / sizeof(float)));
         return VG_OK;
     };
     if (mode == kPthrHist) return go(pthr_scan_kernel<S, kPthrHist, QB>);
@@ -310,29 +318,47 @@ static int32_t launch_pthr(const S &sc, int mode, size_t lds, const PthrArgs &a,
     return go(pthr_scan_kernel<S, kPthrThr, QB>);
 }
 
-// the scorer of the call: scan kind, metric, the fp32 register form; qb: kPthrQB (the whole segment, fp32 / SQ8) or 1
-static int32_t pthr_pass(const vg_index *idx, int32_t scan, bool dot, bool regs, int qb, const float *tables, int mode, const PthrArgs &a,
-                         hipStream_t st)
+// the scorer of the call: scan kind, metric, the fp32 register form; qb: kThrQB (the whole segment, fp32 / SQ8) or 1
+static int32_t pthr_pass(const vg_index *idx, int32_t scan, int qb, const float *tables, int mode, const PthrArgs &a, hipStream_t st)
 {
+    VG_CHECK(!(a.qmap && a.probes), VG_ERR_INVALID_ARG, "pthr_pass: a slot map over probed partitions");
+    const bool dot = idx->metric != VG_METRIC_L2;
     if (scan == VG_SCAN_PQ) {
         const PthrPq sc{reinterpret_cast<const uint4 *>(idx->d_pq_tiles), tables, idx->pq->m, idx->pq_groups, dot};
         return launch_pthr<PthrPq, 1>(sc, mode, sizeof(float) * static_cast<size_t>(lut_image_words(idx->pq->m)), a, st);
     }
     auto with_qb = [&](auto sc, size_t lds_per_query) -> int32_t {
         using S = decltype(sc);
-        return qb == 1 ? launch_pthr<S, 1>(sc, mode, lds_per_query, a, st) : launch_pthr<S, kPthrQB>(sc, mode, lds_per_query * kPthrQB, a, st);
+        return qb == 1 ? launch_pthr<S, 1>(sc, mode, lds_per_query, a, st) : launch_pthr<S, kThrQB>(sc, mode, lds_per_query * kThrQB, a, st);
     };
-    if (scan == VG_SCAN_SQ8) {
-        const uint4 *tiles = reinterpret_cast<const uint4 *>(idx->d_sq_tiles);
-        return dot ? with_qb(PthrSq8<true>{tiles, idx->sq->d_mins, idx->sq->d_inv, idx->sq_groups, idx->dim, true}, 0)
-                   : with_qb(PthrSq8<false>{tiles, idx->sq->d_mins, idx->sq->d_inv, idx->sq_groups, idx->dim, false}, 0);
-    }
-    const size_t qlds = sizeof(float) * static_cast<size_t>(idx->dim);
-    if (regs)
-        return dot ? with_qb(PthrF32<true, true>{idx->d_vectors, idx->dim, true}, qlds)
-                   : with_qb(PthrF32<false, true>{idx->d_vectors, idx->dim, false}, qlds);
-    return dot ? with_qb(PthrF32<true, false>{idx->d_vectors, idx->dim, true}, 0)
-               : with_qb(PthrF32<false, false>{idx->d_vectors, idx->dim, false}, 0);
+    return with_metric(dot, [&](auto dot_c) -> int32_t {
+        constexpr bool DOT = decltype(dot_c)::value;
+        if (scan == VG_SCAN_SQ8)
+            return with_qb(PthrSq8<DOT>{reinterpret_cast<const uint4 *>(idx->d_sq_tiles), idx->sq->d_mins, idx->sq->d_inv, idx->sq_groups,
+                                        idx->dim}, 0);
+        if (thr_scan_regs(idx)) return with_qb(PthrF32<DOT, true>{idx->d_vectors, idx->dim}, sizeof(float) * static_cast<size_t>(idx->dim));
+        return with_qb(PthrF32<DOT, false>{idx->d_vectors, idx->dim}, 0);
+    });
+}
+
+// the grid of a launch of `slots` slots, qb per pass: the ranges of a pass (np probed partitions; np 0: the whole segment in up to
+// 64 pieces of at least 4096 rows) and the slices of a range, for ~4 workgroups per CU (PQ: one, its table fills the LDS)
+static void pthr_grid(const vg_index *idx, int32_t scan, int np, int64_t slots, int qb, int &ranges, int &sub)
+{
+    ranges = np ? np : static_cast<int>(std::min<int64_t>(64, std::max<int64_t>(1, idx->n / 4096)));
+    const int64_t passes = (slots + qb - 1) / qb * ranges;
+    const int64_t want_wgs = (scan == VG_SCAN_PQ ? 1 : 4) * static_cast<int64_t>(idx->ctx->compute_units);
+    sub = static_cast<int>(std::min<int64_t>(32, std::max<int64_t>(1, (want_wgs + passes - 1) / passes)));
+}
+
+int32_t launch_thr_scan_f32(const vg_index *idx, const float *queries, const float *thr, const int *qmap, int64_t cnt,
+                            const uint8_t *mask, int64_t mask_stride, int64_t list_cap, uint64_t *lists, int *counts, hipStream_t st)
+{
+    int ranges, sub;
+    pthr_grid(idx, VG_SCAN_F32, 0, cnt, kThrQB, ranges, sub);
+    const PthrArgs a{queries, qmap, idx->dim, cnt, idx->n, nullptr, nullptr, ranges, sub, thr, nullptr, mask, mask_stride, list_cap, lists,
+                     counts, nullptr};
+    return pthr_pass(idx, VG_SCAN_F32, kThrQB, nullptr, kPthrThr, a, st);
 }
 
 }  // namespace vg
@@ -346,7 +372,7 @@ VG_API int32_t vg_search_flat_probed_threshold(vg_index *idx, const float *queri
     VG_CHECK(idx, VG_ERR_INVALID_ARG, "%s: NULL index", fn);
     VG_CHECK(nq >= 0 && max_results >= 0, VG_ERR_INVALID_ARG, "%s: negative nq or max_results", fn);
     VG_CHECK(scan == VG_SCAN_F32 || scan == VG_SCAN_PQ || scan == VG_SCAN_SQ8, VG_ERR_INVALID_ARG, "%s: unknown scan type %d", fn, scan);
-    VG_CHECK(max_results <= vg::kPthrMaxResults, VG_ERR_UNSUPPORTED, "%s: max_results=%d exceeds %d", fn, max_results, vg::kPthrMaxResults);
+    VG_CHECK(max_results <= vg::kThrMaxResults, VG_ERR_UNSUPPORTED, "%s: max_results=%d exceeds %d", fn, max_results, vg::kThrMaxResults);
     VG_CHECK(idx->metric != VG_METRIC_HAMMING, VG_ERR_UNSUPPORTED, "unsupported metric for float32: Hamming");
     const bool whole = idx->num_partitions <= 1;  // segment.go:745-749: one range, the whole segment
     int np = nprobes <= 0 ? 1 : nprobes;          // segment.go:728-731
@@ -367,31 +393,16 @@ VG_API int32_t vg_search_flat_probed_threshold(vg_index *idx, const float *queri
     if (nq == 0 || max_results == 0) return VG_OK;
     VG_CHECK(queries && thresholds && ids && scores && counts, VG_ERR_INVALID_ARG, "%s: NULL buffer", fn);
     VG_CHECK_MASK_STRIDE(fn, mask, mask_stride, n);
-    VG_HIP(hipSetDevice(idx->ctx->device));
-    hipStream_t st = vg::pick_stream(idx->ctx, stream);
+    vg::ThrIO io;
+    VG_TRY(io.init(idx, stream, queries, nq, thresholds, max_results, mask, mask_stride, ids, scores, counts));
+    hipStream_t st = io.st;
     const bool dot = idx->metric != VG_METRIC_L2;  // (the heap direction of EVERY scan follows the metric: flat/segment.go:449)
     const int dim = idx->dim;
-    const size_t out_n = static_cast<size_t>(nq) * max_results;
-
-    vg::DevIn<float> q, t;
-    vg::DevIn<uint8_t> mk;
-    vg::DevOut<uint32_t> oid;
-    vg::DevOut<float> osc;
-    vg::DevOut<int32_t> ocnt;
-    VG_TRY(q.init(queries, static_cast<size_t>(nq) * dim, st));
-    VG_TRY(t.init(thresholds, static_cast<size_t>(nq), st));
-    VG_TRY(mk.init(mask, vg::mask_span(mask, mask_stride, nq, n), st));
-    VG_TRY(oid.init(ids, out_n, st));
-    VG_TRY(osc.init(scores, out_n, st));
-    VG_TRY(ocnt.init(counts, static_cast<size_t>(nq), st));
 
     // bound form (b): the threshold says nothing about code scores (test hook: also without rerank, then the filter by scan score)
     const bool rerank_codes = rerank && scan != VG_SCAN_F32;
     const bool use_hist = rerank_codes || (!rerank && vg::hook(vg::kHookPthrForceHist));
-    const bool regs = scan == VG_SCAN_F32 && dim % 4 == 0 && dim >= 64 && dim <= 1024 && (reinterpret_cast<uintptr_t>(idx->d_vectors) & 15) == 0;
-    // the ranges of a pass: the probed partitions, or the whole segment in up to 64 pieces of at least 4096 rows
-    const int ranges = whole ? static_cast<int>(std::min<int64_t>(64, std::max<int64_t>(1, n / 4096))) : np;
-    const int qb = whole && scan != VG_SCAN_PQ ? vg::kPthrQB : 1;
+    const int qb = whole && scan != VG_SCAN_PQ ? vg::kThrQB : 1;
     // the rows a query can see: the whole segment, or its np largest partitions at most
     int64_t list_cap = std::max<int64_t>(n, 1);
     if (!whole && static_cast<int>(idx->h_part_off.size()) == idx->num_partitions + 1) {
@@ -402,16 +413,14 @@ VG_API int32_t vg_search_flat_probed_threshold(vg_index *idx, const float *queri
         for (int j = 0; j < np; j++) sum += sizes[j];
         list_cap = std::max<int64_t>(std::min(sum, n), 1);
     }
-    // queries per launch: their lists stay below 2^25 keys (256 MiB), whole passes of kPthrQB
+    // queries per launch: their lists stay below 2^25 keys (256 MiB), whole passes of kThrQB
     int64_t qc = std::min<int64_t>(64, std::max<int64_t>(1, (int64_t(1) << 25) / list_cap));
     if (qb > 1) qc = std::max<int64_t>(qb, qc / qb * qb);
     qc = std::min(qc, nq);
     const size_t uqc = static_cast<size_t>(qc);
     const int lut_words = scan == VG_SCAN_PQ ? vg::lut_image_words(idx->pq->m) : 0;
-    // ~4 workgroups per CU (PQ: one, its table fills the LDS)
-    const int64_t passes = (qc + qb - 1) / qb * ranges;
-    const int64_t want_wgs = (scan == VG_SCAN_PQ ? 1 : 4) * static_cast<int64_t>(idx->ctx->compute_units);
-    const int sub = static_cast<int>(std::min<int64_t>(32, std::max<int64_t>(1, (want_wgs + passes - 1) / passes)));
+    int ranges, sub;
+    vg::pthr_grid(idx, scan, whole ? 0 : np, qc, qb, ranges, sub);
 
     vg::ArenaCall ar(idx->ctx, st);
     const int i_lists = ar.add(sizeof(uint64_t) * uqc * list_cap);
@@ -431,55 +440,52 @@ VG_API int32_t vg_search_flat_probed_threshold(vg_index *idx, const float *queri
     float *tables = ar.get<float>(i_tables);
     const uint32_t *part_off = whole ? nullptr : idx->d_part_off;
 
-    if (!whole) VG_TRY(vg::launch_probe_select(idx, q.ptr, nq, np, dot, probes, st));
+    if (!whole) VG_TRY(vg::launch_probe_select(idx, io.q.ptr, nq, np, dot, probes, st));
     // step 1, the candidate stage: per query the best max_results rows it can see (form a: of those within its threshold)
     for (int64_t q0 = 0; q0 < nq; q0 += qc) {
         const int64_t c = std::min(qc, nq - q0);
         VG_HIP(hipMemsetAsync(cnt, 0, sizeof(int) * static_cast<size_t>(c), st));
         if (n > 0) {
-            if (scan == VG_SCAN_PQ) VG_TRY(vg::launch_pq_build_table(idx->pq, q.ptr + q0 * dim, c, tables, true, st));
-            const vg::PthrArgs a{q.ptr + q0 * dim, dim, c, n, probes ? probes + q0 * np : nullptr, part_off, ranges, sub, t.ptr + q0, cut,
-                                 mk.ptr ? mk.ptr + q0 * mask_stride : nullptr, mask_stride, list_cap, lists, cnt, hist};
+            if (scan == VG_SCAN_PQ) VG_TRY(vg::launch_pq_build_table(idx->pq, io.q.ptr + q0 * dim, c, tables, true, st));
+            const vg::PthrArgs a{io.q.ptr + q0 * dim, nullptr, dim, c, n, probes ? probes + q0 * np : nullptr, part_off, ranges, sub,
+                                 io.t.ptr + q0, cut, io.mk.ptr ? io.mk.ptr + q0 * mask_stride : nullptr, mask_stride, list_cap, lists, cnt, hist};
             vg::ProfScope prof(idx->ctx, "probed_thr_scan", st);
             if (use_hist) {
                 VG_HIP(hipMemsetAsync(hist, 0, sizeof(unsigned) * static_cast<size_t>(c) * vg::kPthrBins, st));
-                VG_TRY(vg::pthr_pass(idx, scan, dot, regs, qb, tables, vg::kPthrHist, a, st));
+                VG_TRY(vg::pthr_pass(idx, scan, qb, tables, vg::kPthrHist, a, st));
                 VG_LAUNCH(vg::pthr_cut_kernel, dim3(static_cast<unsigned>(c)), dim3(1024), 0, st, hist, max_results, cut);
-                VG_TRY(vg::pthr_pass(idx, scan, dot, regs, qb, tables, vg::kPthrBin, a, st));
+                VG_TRY(vg::pthr_pass(idx, scan, qb, tables, vg::kPthrBin, a, st));
             } else {
-                VG_TRY(vg::pthr_pass(idx, scan, dot, regs, qb, tables, vg::kPthrThr, a, st));
+                VG_TRY(vg::pthr_pass(idx, scan, qb, tables, vg::kPthrThr, a, st));
             }
         }
         vg::ProfScope prof(idx->ctx, "probed_thr_select", st);
-        VG_TRY(vg::launch_thr_select_lists(dot, lists, list_cap, cnt, c, max_results, oid.ptr + q0 * max_results, osc.ptr + q0 * max_results,
-                                           ocnt.ptr + q0, st));
+        VG_TRY(vg::launch_thr_select_lists(dot, lists, list_cap, cnt, nullptr, c, list_cap, max_results, io.oid.ptr + q0 * max_results,
+                                           io.osc.ptr + q0 * max_results, io.ocnt.ptr + q0, st));
     }
     if (n > 0) {
         // queries whose scan scores may hold a NaN: flat.Segment.Search(q, max_results) as its heap answers it, over the same ranges
         if (scan == VG_SCAN_SQ8)
-            VG_TRY(vg::sq8_nan_replay(idx, q.ptr, nq, max_results, mk.ptr, mask_stride, probes, np, part_off, oid.ptr, osc.ptr, st));
+            VG_TRY(vg::sq8_nan_replay(idx, io.q.ptr, nq, max_results, io.mk.ptr, mask_stride, probes, np, part_off, io.oid.ptr, io.osc.ptr, st));
         else if (scan == VG_SCAN_PQ)
-            VG_TRY(vg::pq_nan_replay(idx, q.ptr, nq, max_results, dot, mk.ptr, mask_stride, probes, np, part_off, oid.ptr, osc.ptr, st));
+            VG_TRY(vg::pq_nan_replay(idx, io.q.ptr, nq, max_results, dot, io.mk.ptr, mask_stride, probes, np, part_off, io.oid.ptr, io.osc.ptr, st));
         else
-            VG_TRY(vg::launch_cand_replay(vg::FlatF32Scorer{idx->d_vectors, idx->d_norm_max + 1, dim, dot, 0}, q.ptr, dim, n, nq, max_results,
-                                          dot, mk.ptr, mask_stride, oid.ptr, osc.ptr, st, nullptr, probes, np, part_off));
+            VG_TRY(vg::launch_cand_replay(vg::FlatF32Scorer{idx->d_vectors, idx->d_norm_max + 1, dim, dot, 0}, io.q.ptr, dim, n, nq, max_results,
+                                          dot, io.mk.ptr, mask_stride, io.oid.ptr, io.osc.ptr, st, nullptr, probes, np, part_off));
         if (rerank_codes) {
             // step 2, Segment.Rerank: every candidate's exact score; step 3 fused: those within the threshold, best first
             for (int64_t q0 = 0; q0 < nq; q0 += qc) {
                 const int64_t c = std::min(qc, nq - q0);
                 vg::ProfScope prof(idx->ctx, "probed_thr_rerank", st);
-                VG_TRY(vg::launch_thr_rescore_ids(dot, idx->d_vectors, dim, q.ptr + q0 * dim, t.ptr + q0, oid.ptr + q0 * max_results, c,
-                                                  max_results, elist, ecount, st));
-                VG_TRY(vg::launch_thr_select_lists(dot, elist, max_results, ecount, c, max_results, oid.ptr + q0 * max_results,
-                                                   osc.ptr + q0 * max_results, ocnt.ptr + q0, st));
+                VG_TRY(vg::launch_thr_rescore(dot, idx->d_vectors, dim, io.q.ptr + q0 * dim, io.t.ptr + q0, nullptr, nullptr,
+                                              io.oid.ptr + q0 * max_results, c, max_results, elist, ecount, st));
+                VG_TRY(vg::launch_thr_select_lists(dot, elist, max_results, ecount, nullptr, c, max_results, max_results,
+                                                   io.oid.ptr + q0 * max_results, io.osc.ptr + q0 * max_results, io.ocnt.ptr + q0, st));
             }
         } else {
             // step 3 over what the replay or form (b) left (idempotent on form (a)'s lists)
-            VG_TRY(vg::launch_thr_filter(dot, t.ptr, nq, max_results, oid.ptr, osc.ptr, ocnt.ptr, st));
+            VG_TRY(vg::launch_thr_filter(dot, io.t.ptr, nq, max_results, io.oid.ptr, io.osc.ptr, io.ocnt.ptr, st));
         }
     }
-    VG_TRY(oid.finish());
-    VG_TRY(osc.finish());
-    VG_TRY(ocnt.finish());
-    return VG_OK;
+    return io.finish();
 }

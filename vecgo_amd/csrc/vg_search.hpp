@@ -1,11 +1,13 @@
 // vg_search.hpp — what the search translation units share on the host: every function one .hip defines and another calls,
 // declared once (the defining file includes this header too, so a definition that disagrees does not compile), and the
 // scaffolding every search entry point stands on: SearchIO (staged operands), empty_results, PagedTopK (k > 64 in pages),
+// for the flat threshold searches ThrIO (SearchIO + thresholds and counts), their constants and metric dispatch,
 // and for the graph walks WalkIO (SearchIO + per-query counters) and WalkChunks (per-query scratch, a batch in launches).
 // (The bf16 nomination's functions are declared in vg_nominate.hpp.)
 #pragma once
 
 #include <algorithm>
+#include <type_traits>
 
 #include "vg_internal.hpp"
 #include "vg_walk_chunk.hpp"
@@ -58,15 +60,39 @@ int32_t flat_thr_nominate(vg_index *idx, hipStream_t st, const float *qp, const 
                           uint64_t *cand);
 int32_t launch_flat_todo(const int *flags, const int *always, int cnt, int *todo, unsigned long long *stats, hipStream_t st);
 
-// ---- k_flat_threshold.hip -------------------------------------------------------------------------
-// the best max_results keys of per-query lists, written best first; the engine's threshold filter (vg_search_vamana's
-// large-k walk and vg_search_vamana_threshold, k_graph.hip)
-int32_t launch_thr_select_lists(bool desc, const uint64_t *lists, int64_t list_cap, const int *counts, int64_t nq, int max_results,
-                                uint32_t *ids, float *scores, int32_t *out_counts, hipStream_t st);
+// ---- the threshold searches: k_flat_threshold.hip, k_probed_threshold.hip (and the large-k Vamana walk, k_graph.hip) ----
+constexpr int kThrMaxResults = 16384;  // the selection's LDS buffer (128 KiB of keys) and the replay's heap
+constexpr int kThrQB = 8;              // queries one pass over the whole segment carries (fp32, SQ8)
+// the register form of the exact scan: rows of whole float4 (dim % 4 == 0, 16-byte aligned), up to 16 float4 per lane
+inline bool thr_scan_regs(const vg_index *idx)
+{
+    return idx->dim % 4 == 0 && idx->dim >= 64 && idx->dim <= 1024 && aligned16(idx->d_vectors);
+}
+// the metric of a launch as a compile-time constant: f(std::true_type) for Dot / Cosine, f(std::false_type) for L2
+template <class F>
+inline int32_t with_metric(bool dot, F f)
+{
+    return dot ? f(std::true_type{}) : f(std::false_type{});
+}
+// k_flat_threshold.hip.  The best max_results keys of `nq` lists (list s: counts[s] keys at lists + s * list_cap), written best
+// first to query qmap[s] (null: s) of ids / scores / out_counts; `longest`: no list holds more keys.  A list of up to 16384
+// keys is sorted whole in LDS, a longer one radix-selects its max_results-th key first.
+int32_t launch_thr_select_lists(bool desc, const uint64_t *lists, int64_t list_cap, const int *counts, const int *qmap, int64_t nq,
+                                int64_t longest, int max_results, uint32_t *ids, float *scores, int32_t *out_counts, hipStream_t st);
+// the engine's filter over each query's results, in order
 int32_t launch_thr_filter(bool desc, const float *thr, int64_t nq, int max_results, uint32_t *ids, float *scores, int32_t *counts,
                           hipStream_t st);
-int32_t launch_thr_rescore_ids(bool desc, const float *base, int dim, const float *queries, const float *thr, const uint32_t *ids,
-                               int64_t nq, int cap, uint64_t *lists, int *list_counts, hipStream_t st);
+// Exact scores of candidate rows, those within each query's threshold as keys in lists[nq * cap] / list_counts[nq] (zeroed
+// here).  cand_ids null: the rows of the nomination's keys, cand_counts[q] (at most cap) of cand[q * cap ..]; else a search's
+// result rows cand_ids[nq * cap], VG_INVALID_ID where unused (Segment.Rerank's input)
+int32_t launch_thr_rescore(bool desc, const float *base, int dim, const float *queries, const float *thr, const uint64_t *cand,
+                           const int *cand_counts, const uint32_t *cand_ids, int64_t nq, int cap, uint64_t *lists, int *list_counts,
+                           hipStream_t st);
+// k_probed_threshold.hip.  One exact fp32 pass over the whole segment for `cnt` slots, kThrQB per workgroup: slot s scores
+// every row against query qmap[s] (null: s) of queries / thr / mask and appends the keys within its threshold and filter to
+// list s (lists + s * list_cap, counts[s]; the caller zeroes the counts)
+int32_t launch_thr_scan_f32(const vg_index *idx, const float *queries, const float *thr, const int *qmap, int64_t cnt,
+                            const uint8_t *mask, int64_t mask_stride, int64_t list_cap, uint64_t *lists, int *counts, hipStream_t st);
 
 // ---- k_probe.hip ----------------------------------------------------------------------------------
 // kmeans.FindClosestCentroids for every query (device buffers): probes[q * np + j]
@@ -152,6 +178,25 @@ inline size_t mask_span(const uint8_t *mask, int64_t mask_stride, int64_t nq, in
     const int64_t mask_bytes = (n + 7) / 8;
     return mask ? static_cast<size_t>(mask_stride ? (nq - 1) * mask_stride + mask_bytes : mask_bytes) : 0;
 }
+
+// The flat threshold searches' operands: SearchIO (max_results ids / scores per query), a threshold per query and the counts.
+struct ThrIO : SearchIO {
+    DevIn<float> t;
+    DevOut<int32_t> ocnt;
+    int32_t init(const vg_index *idx, void *stream, const float *queries, int64_t nq, const float *thresholds, int max_results,
+                 const uint8_t *mask, int64_t mask_stride, uint32_t *ids, float *scores, int32_t *counts)
+    {
+        VG_TRY(SearchIO::init(idx->ctx, stream, queries, static_cast<size_t>(nq) * idx->dim, ids, scores,
+                              static_cast<size_t>(nq) * max_results, mask, mask_span(mask, mask_stride, nq, idx->n)));
+        VG_TRY(t.init(thresholds, static_cast<size_t>(nq), st));
+        return ocnt.init(counts, static_cast<size_t>(nq), st);
+    }
+    int32_t finish()
+    {
+        VG_TRY(SearchIO::finish());
+        return ocnt.finish();
+    }
+};
 
 // a filter per query (mask_stride != 0) has to be at least a filter long; `fn`: the entry point the message names
 #define VG_CHECK_MASK_STRIDE(fn, mask, mask_stride, n)                                                                              \
