@@ -4,7 +4,7 @@
 //           the 64 lookups are ds_read_b64
 //   MODE 2  the same with LDS-DMA (global_load_lds_dwordx4: no staging registers, no ds_write)
 //   MODE 3  no lookups at all (the terms' arithmetic alone)
-// ARITH = 1 adds the real term arithmetic of vg_hnsw_layer.hpp (pq_term8_quad), 0 just consumes the centroid words.
+// ARITH = 1 adds the real term arithmetic of vg_node_score.hpp (pq_term8_quad), 0 just consumes the centroid words.
 // One wave per workgroup like hnsw_search_kernel, WPS waves per SIMD through amdgpu_waves_per_eu + LDS padding: the walk
 // kernel's heaps leave ~2.6 KiB of LDS per wave at 16 waves per CU (ef 128), i.e. a ring of ONE slice; RING > 1 models
 // fewer waves per CU.  Prints ns per 64-node batch and G node scores/s.
@@ -15,7 +15,7 @@
 #include <cstdlib>
 #include <vector>
 
-#include "vg_hnsw_layer.hpp"
+#include "vg_node_score.hpp"
 
 #define CK(x)                                                        \
     do {                                                             \

@@ -141,10 +141,7 @@ __global__ __launch_bounds__(64) VG_HNSW_ATTR void hnsw_search_kernel(
         sc.qv = queries + q * dim;
         sc.qprep = qprep;
         sc.m = pq_m;
-        if constexpr (PQM == 2) {
-            pq_direct_prepare(qprep, sc.qv, pq_scales, pq_offsets, pq_m, lane);
-            __syncthreads();
-        }
+        sc.prepare(lane);
     } else {
         sc.base = base;
         sc.qv = queries + q * dim;
@@ -291,19 +288,6 @@ __global__ __launch_bounds__(64) VG_HNSW_ATTR void hnsw_search_kernel(
 }
 
 // ---- Vamana --------------------------------------------------------------------------------------
-enum { kVamanaF32 = 0, kVamanaPQ = 1, kVamanaRaBitQ = 2, kVamanaInt4 = 3, kVamanaPQDirect = 4, kVamanaInt4Direct = 5 /* 4, 5: kernel instances only */ };
-
-__device__ inline float rq_formula_g(float qn, float yn, float dimf, float hamming)
-{
-    const float t1 = qn - yn;
-    const float t1sq = t1 * t1;
-    float t2 = 4.0f * qn;
-    t2 = t2 * yn;
-    t2 = t2 / dimf;
-    t2 = t2 * hamming;
-    return t1sq + t2;
-}
-
 constexpr int kHnswMaxEf = 1 << 20;  // ... in HBM scratch beyond
 constexpr int kVamanaMaxK = 512;  // results per query: one per lane up to 64, a sorted LDS list beyond
 // k in (kVamanaMaxK, kVamanaHugeMaxK] (HUGE instances): the k best keys as a 64-ary MAX-heap whose root — the worst of them — is
@@ -319,16 +303,179 @@ constexpr int kVamanaHeapLds = 1 + 64 * 7;
 #endif
 constexpr int kVamanaLdsCand = VG_VAMANA_LDS_CAND;  // items of the exploration heap kept in LDS (4 KiB: 16 waves per CU next to the PQ constants)
 
-template <bool big>
-__device__ __forceinline__ uint64_t *vamana_result_list()
-{
-    if constexpr (big) {
-        __shared__ uint64_t list[kVamanaMaxK];
-        return list;
-    } else {
-        return nullptr;
+// ---- sc.Heap, the k best rows a walk has met (TryPushBounded(k), candidate_queue.go:120-132), in four forms -------------------
+//   count            min(k, rows offered) = sc.Heap.Len()
+//   offer(key, n)    every lane's key (make_key, or kKeyMax for none), n of them real; STRICT: offer(id, d), one row, uniform
+//   worst()          the score the stop test reads once count == k
+//   write(ids, scores)  the query's k output slots, best first, the rest padded
+// A set kept by 64-bit keys is order-free: a total order.  `lds`: the kernel's `res` array (STRICT + HUGE: k items of dynamic LDS).
+struct VamanaResultBase {
+    uint64_t *res, *hl;  // `lds`, and the large-k heap's part in HBM
+    int k, lane, count = 0;
+    bool desc;
+    __device__ __forceinline__ VamanaResultBase(uint64_t *lds, uint64_t *hbm, int k_, int lane_, bool desc_) : res(lds), hl(hbm), k(k_), lane(lane_), desc(desc_) {}
+    __device__ __forceinline__ void counted(int n) { count = count + n < k ? count + n : k; }
+    __device__ __forceinline__ void put(uint32_t *ids, float *scores, int i, uint64_t e) const
+    {
+        ids[i] = e == kKeyMax ? VG_INVALID_ID : key_row(e);
+        scores[i] = e == kKeyMax ? (desc ? -INFINITY : INFINITY) : key_score(e, desc);
     }
-}
+};
+
+struct VamanaResultRegs : VamanaResultBase {  // k <= 64: one key per lane (WaveTopK)
+    WaveTopK tk;
+    __device__ __forceinline__ VamanaResultRegs(uint64_t *, uint64_t *, int k_, int lane_, bool desc_) : VamanaResultBase(nullptr, nullptr, k_, lane_, desc_) { tk.init(k_); }
+    __device__ __forceinline__ void offer(uint64_t key, int n)
+    {
+        tk.offer(key, lane);
+        counted(n);
+    }
+    __device__ __forceinline__ float worst() const { return key_score(tk.tau, desc); }
+    __device__ __forceinline__ void write(uint32_t *ids, float *scores) const
+    {
+        if (lane < k) put(ids, scores, lane, tk.list);
+    }
+};
+
+// k > 64: the keys in memory, bookkeeping wave-uniform; Set::insert(c) takes one key below the bound `tau`
+template <class Set>
+struct VamanaResultKeys : VamanaResultBase {
+    using VamanaResultBase::VamanaResultBase;
+    int n = 0;
+    uint64_t tau = kKeyMax;
+    __device__ __forceinline__ void offer(uint64_t key, int npass)
+    {
+        uint64_t mask = __ballot(key < tau);
+        while (mask) {
+            const int j = __builtin_ctzll(mask);
+            mask &= mask - 1;
+            const uint64_t c = readlane_u64(key, j);
+            if (c < tau) static_cast<Set *>(this)->insert(c);  // (the bound may have dropped since the ballot)
+        }
+        counted(npass);
+    }
+    __device__ __forceinline__ float worst() const { return key_score(tau, desc); }
+};
+
+struct VamanaResultList : VamanaResultKeys<VamanaResultList> {  // k <= kVamanaMaxK: a sorted list in LDS
+    using VamanaResultKeys::VamanaResultKeys;
+    __device__ __forceinline__ void insert(uint64_t c)  // c < tau, every lane calls it with the same key
+    {
+        int lo = 0, hi = n;  // first position whose key is >= c (keys are distinct)
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (res[mid] < c)
+                lo = mid + 1;
+            else
+                hi = mid;
+        }
+        const int newn = n < k ? n + 1 : k;
+        uint64_t moved[kVamanaMaxK / 64];
+#pragma unroll
+        for (int u = 0; u < kVamanaMaxK / 64; u++) {
+            const int i = lo + lane + u * 64;
+            moved[u] = i < newn - 1 ? res[i] : kKeyMax;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int u = 0; u < kVamanaMaxK / 64; u++) {
+            const int i = lo + lane + u * 64;
+            if (i < newn - 1) res[i + 1] = moved[u];
+        }
+        if (lane == 0) res[lo] = c;
+        __syncthreads();
+        n = newn;
+        tau = n >= k ? res[k - 1] : kKeyMax;
+    }
+    __device__ __forceinline__ void write(uint32_t *ids, float *scores) const
+    {
+        for (int i = lane; i < k; i += 64) put(ids, scores, i, i < n ? res[i] : kKeyMax);
+    }
+};
+
+// k <= kVamanaHugeMaxK: the 64-ary max-heap (keys are distinct: a node enters the walk once); hl = its HBM part, indexed like the heap
+struct VamanaResultHeap : VamanaResultKeys<VamanaResultHeap> {
+    using VamanaResultKeys::VamanaResultKeys;
+    __device__ __forceinline__ void set(int i, uint64_t v)
+    {
+        if (i < kVamanaHeapLds)
+            res[i] = v;
+        else
+            hl[i] = v;
+    }
+    __device__ __forceinline__ void insert(uint64_t c)  // c < tau, every lane calls it with the same key
+    {
+        int i;
+        if (n < k) {  // push: up the parent chain
+            i = n++;
+            while (i > 0) {
+                const int p = (i - 1) >> 6;
+                const uint64_t pk = p < kVamanaHeapLds ? res[p] : hl[p];
+                if (pk > c) break;
+                set(i, pk);
+                i = p;
+            }
+        } else {  // the root leaves: c sinks along the largest children
+            i = 0;
+            for (;;) {
+                const int fc = 64 * i + 1;
+                if (fc >= k) break;
+                uint64_t v = 0;  // (below every key that can move: c >= 0)
+                if (fc + lane < k) v = fc < kVamanaHeapLds ? res[fc + lane] : hl[fc + lane];
+                uint64_t m = v;
+#pragma unroll
+                for (int off = 32; off > 0; off >>= 1) {
+                    const uint64_t o = (static_cast<uint64_t>(static_cast<uint32_t>(__shfl_xor(static_cast<int>(m >> 32), off))) << 32) |
+                                       static_cast<uint32_t>(__shfl_xor(static_cast<int>(static_cast<uint32_t>(m)), off));
+                    m = o > m ? o : m;
+                }
+                if (c >= m) break;
+                set(i, m);
+                i = fc + __builtin_ctzll(__ballot(v == m && fc + lane < k));
+            }
+        }
+        set(i, c);
+        tau = n >= k ? res[0] : kKeyMax;
+    }
+    __device__ __forceinline__ void write(uint32_t *, float *) const  // the heap's keys, the rest kKeyMax, to its HBM list: the host's sort writes them best first
+    {
+        for (int i = lane; i < k; i += 64) {
+            if (i >= n)
+                hl[i] = kKeyMax;
+            else if (i < kVamanaHeapLds)
+                hl[i] = res[i];
+        }
+    }
+};
+
+// STRICT: the reference's CandidateHeap itself (vg_cand_replay.hpp), float comparisons, uniform over the wave
+struct VamanaResultStrict : VamanaResultBase {
+    using VamanaResultBase::VamanaResultBase;
+    CItem *const heap = reinterpret_cast<CItem *>(res);
+    __device__ __forceinline__ void offer(uint32_t id, float d)
+    {
+        const CItem x{d, id};
+        if (count < k) {
+            cand_up(heap, count, x, desc);
+            count++;
+        } else if (cand_better(x, cand_load(heap, 0), desc)) {
+            cand_down(heap, 0, count, x, desc);
+        }
+    }
+    __device__ __forceinline__ float worst() const { return cand_load(heap, 0).score; }
+    __device__ __forceinline__ void write(uint32_t *ids, float *scores)  // the engine empties the heap with Pop() (engine/search.go:859-862): reported best first
+    {
+        const int nres = count;
+        for (int i = nres - 1; i >= 0; i--) {
+            const CItem it = cand_pop(heap, count, desc);
+            if (lane == 0) {
+                ids[i] = it.row;
+                scores[i] = it.score;
+            }
+        }
+        for (int i = nres + lane; i < k; i += 64) put(ids, scores, i, kKeyMax);
+    }
+};
 
 // one instance per node scorer and per result-set form: the fp32 scorer's row blocks in flight do not set the
 // register budget of the code scorers, and the k <= 64 search carries no LDS result list
@@ -340,14 +487,16 @@ __device__ __forceinline__ uint64_t *vamana_result_list()
 #ifndef VG_VAMANA_PQ_WAVES
 #define VG_VAMANA_PQ_WAVES 4
 #endif
+// diskann.Segment.searchInternal (segment.go:603-706) with the node scorer VamanaScorer<kind> (vg_node_score.hpp) and the result set
+// of the instance: big = k > 64, HUGE = k > kVamanaMaxK.
 // MASKED: vg_search_vamana_filtered (pushToHeap's filter, segment.go:616-627) — a template flag: the unfiltered instances keep
 // their register budgets (a runtime mask cost 13 registers: the PQ-direct scorer spilled, the others lost a wave per SIMD)
-// STRICT (with big and MASKED): the second pass over the queries whose distances may hold a NaN (a non-finite query value or index
-// datum; dot products that can overflow both ways; RaBitQ: 4 |q| |y| overflowing next to a Hamming distance of 0).  The result
-// set above is kept by 64-bit keys — a total order — while for the reference's CandidateHeap a NaN is neither better nor worse than
-// anything (candidate_queue.go:12-38): which rows it holds, the root the pruning test reads and the order they leave in are then
-// decided by the heap's layout.  This pass runs the reference's TryPushBounded / Pop on an LDS array with float comparisons
-// (vg_cand_replay.hpp), neighbour by neighbour in list order; a query without risk returns at once.
+// STRICT (with big and MASKED): the second pass over the queries whose distances may hold a NaN (Scorer::risk: a non-finite query
+// value or index datum; dot products that can overflow both ways; RaBitQ: 4 |q| |y| overflowing next to a Hamming distance of 0).
+// The result set above is kept by 64-bit keys — a total order — while for the reference's CandidateHeap a NaN is neither better nor
+// worse than anything (candidate_queue.go:12-38): which rows it holds, the root the pruning test reads and the order they leave in are
+// then decided by the heap's layout.  This pass runs the reference's TryPushBounded / Pop on an LDS array with float comparisons
+// (VamanaResultStrict), neighbour by neighbour in list order; a query without risk returns at once.
 template <int kind, bool big, bool MASKED = false, bool STRICT = false, bool HUGE = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kind == kVamanaPQDirect ? VG_VAMANA_PQ_WAVES : 1, kind == kVamanaF32 ? VG_VAMANA_F32_MAX_WAVES : 8))) void vamana_search_kernel(
     int metric, int64_t n, int dim, const uint32_t *__restrict__ graph, int r, uint32_t entry,
@@ -368,13 +517,14 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kind == kVam
     // heap peaks a little above that — live in LDS: a
     // popped node pushes up to R = 64 neighbours one after the other, each a sift of dependent accesses
     __shared__ HItem cand_lo[kVamanaLdsCand];
-    extern __shared__ __attribute__((aligned(16))) float vamana_qprep[];  // PQ direct form: pq_direct_prepare's image
+    extern __shared__ __attribute__((aligned(16))) float vamana_qprep[];  // the scorer's staging, Scorer::lds_bytes of it
+    __shared__ vg_f2v int4_pairs[256];  // INT4 direct form: code byte -> (hi / 15, lo / 15)
+    static_assert(!HUGE || big, "the large-k result set replaces the sorted LDS list");
+    using Scorer = typename VamanaScorer<kind>::type;
+    using Results = std::conditional_t<STRICT, VamanaResultStrict, std::conditional_t<HUGE, VamanaResultHeap, std::conditional_t<big, VamanaResultList, VamanaResultRegs>>>;
     const int64_t q = blockIdx.x;
     const int lane = threadIdx.x;
-    const Sub16 sub = Sub16::make(lane);
-    const float *qv = queries + q * dim;
     uint32_t *vis = visited_ws + q * vis_words;
-    static_assert(!HUGE || big, "the large-k result set replaces the sorted LDS list");
     // HUGE: the query's cand_cap items of scratch hold the exploration heap (ccap items) and then the HBM part of the result heap (k)
     const int64_t ccap = HUGE ? cand_cap - k : cand_cap;
     // (the flat address of cand_lo passes through a register: as a constant expression inside the heap's
@@ -383,255 +533,55 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kind == kVam
     asm volatile("" : "+s"(cand_lo_flat));
     const SplitHeap cand{cand_lo_flat, cand_ws + q * cand_cap, kVamanaLdsCand};
     const bool desc = metric != kMetricL2;  // sc.Heap.Reset(s.Metric() != MetricL2), segment.go:597
-    const float *lut = luts ? luts + q * static_cast<int64_t>(pq_m) * 256 : nullptr;
-    const uint8_t *qc = qcodes ? qcodes + q * static_cast<int64_t>(rq_nb + 4) : nullptr;
-    float qn = 0.0f;
-    if (kind == kVamanaRaBitQ) {
-        const uint32_t b = qc[rq_nb] | (qc[rq_nb + 1] << 8) | (qc[rq_nb + 2] << 16) |
-                           (static_cast<uint32_t>(qc[rq_nb + 3]) << 24);
-        qn = __uint_as_float(b);
-        // the query's sign words in LDS (rq_nb bytes of the dynamic allocation; qcodes rows are 4-byte aligned)
-        for (int i = lane; i < (rq_nb >> 2); i += 64)
-            reinterpret_cast<uint32_t *>(vamana_qprep)[i] = reinterpret_cast<const uint32_t *>(qc)[i];
-        __syncthreads();
-    }
-    if constexpr (STRICT) {
-        bool bad = false;
-        for (int j = lane; j < dim; j += 64) bad = bad || !is_finite_f32(qv[j]);
-        // (the tests of vg_cand_replay.hpp's scorers: non-finite inputs, or magnitudes whose partial sums could overflow)
-        float vm = 0.0f;  // the largest |value| a row can hold
-        if (kind == kVamanaF32) {
-            vm = risk_absmax[0];
-        } else if (kind == kVamanaRaBitQ) {
-            const float ma = risk_absmax[0];
-            bad = bad || !is_finite_f32(qn) || !is_finite_f32(ma) || !(4.0f * fabsf(qn) * ma < 1e38f) || !(score_bound(fabsf(qn), ma, false) < 1e38f);
-        } else if (kind == kVamanaPQ || kind == kVamanaPQDirect) {
-            for (int j = lane; j < pq_m; j += 64) {
-                bad = bad || !is_finite_f32(pq_scales[j]) || !is_finite_f32(pq_offsets[j]);
-                vm = fmaxf(vm, 128.0f * fabsf(pq_scales[j]) + fabsf(pq_offsets[j]));
-            }
-        } else if (int4_min && int4_diff) {
-            for (int j = lane; j < dim; j += 64) {
-                bad = bad || !is_finite_f32(int4_min[j]) || !is_finite_f32(int4_diff[j]);
-                vm = fmaxf(vm, fabsf(int4_min[j]) + fabsf(int4_diff[j]));
-            }
+    const float *qv = queries + q * dim;
+    const Scorer sc = [&] {
+        if constexpr (kind == kVamanaF32) {
+            return Scorer{base, qv, risk_absmax, dim, desc, Sub16::make(lane)};
+        } else if constexpr (kind == kVamanaPQ || kind == kVamanaPQDirect) {
+            return Scorer{pq_rows, luts ? luts + q * static_cast<int64_t>(pq_m) * 256 : nullptr, pq_cb, pq_scales, pq_offsets, qv, vamana_qprep, pq_m, dim};
+        } else if constexpr (kind == kVamanaRaBitQ) {
+            const uint8_t *qc = qcodes + q * static_cast<int64_t>(rq_nb + 4);
+            return Scorer{rq_rows, qc, qv, risk_absmax, (typename Scorer::lds_u32 *)vamana_qprep, Scorer::norm_of(qc, rq_nb), rq_nb, dim};
         } else {
-            for (int j = lane; j < dim * 16; j += 64) {  // (the lookup table holds the decoded values)
-                bad = bad || !is_finite_f32(int4_table[j]);
-                vm = fmaxf(vm, fabsf(int4_table[j]));
-            }
+            return Scorer{qv, int4_table, int4_min, int4_diff, int4_rows, kind == kVamanaInt4Direct ? int4_pairs : nullptr, dim};
         }
-        if (kind != kVamanaRaBitQ) {
-            for (int off = 32; off > 0; off >>= 1) vm = fmaxf(vm, __shfl_xor(vm, off));
-            bad = bad || !is_finite_f32(vm);
-            const bool as_dot = kind == kVamanaF32 && desc;
-            for (int j = lane; j < dim; j += 64) bad = bad || !(score_bound(fabsf(qv[j]), vm, as_dot) * static_cast<float>(dim) < 1e38f);
-        }
-        if (!__any(bad)) return;
+    }();
+    sc.prepare(lane);
+    if constexpr (STRICT) {
+        if (!__any(sc.risk(lane))) return;
         for (int64_t w = lane; w < vis_words; w += 64) vis[w] = 0u;  // the first pass's marks
         __syncthreads();
     }
-    int64_t st_visited = 0, st_dc = 0, st_pops = 0, st_dropped = 0;
-    __shared__ vg_f2v int4_pairs[256];  // INT4 direct form: code byte -> (hi / 15, lo / 15)
-    if (kind == kVamanaInt4Direct) {
-        int4_fill_pairs(int4_pairs, lane, 64);
-        __syncthreads();
-    }
-    if (kind == kVamanaPQDirect) {
-        pq_direct_prepare(vamana_qprep, qv, pq_scales, pq_offsets, pq_m, lane);
-        __syncthreads();
-    }
-
-    // score the nodes held by the lanes in `mask` (one id per lane) into nb_d[lane]
-    auto score_mask = [&](uint64_t mask, uint32_t id_lane) {
-        if (kind == kVamanaF32) {
-            while (mask) {
-                const int mine = take4(mask, lane);
-                const uint32_t id = __shfl(id_lane, mine < 0 ? 0 : mine);
-                if (mine >= 0) {
-                    const float *row = base + static_cast<int64_t>(id) * dim;
-                    // distFunc(query, vec) = distance.Provider(metric): SquaredL2 or Dot
-                    const float d = desc ? exact_pair16<true, kPair>(row, qv, dim, sub)
-                                         : exact_pair16<false, kPair>(row, qv, dim, sub);
-                    if ((lane & 15) == 0) nb_d[mine] = d;
-                }
-            }
-        } else if ((mask >> lane) & 1) {
-            if (kind == kVamanaPQ || kind == kVamanaPQDirect) {
-                // ComputeAsymmetricDistance (pq.go:234-260): term(m) = BuildDistanceTable entry, summed
-                // sequentially over the sub-quantizers (vg_hnsw_layer.hpp: loads batched, sum order kept)
-                const uint8_t *code = pq_rows + static_cast<int64_t>(id_lane) * pq_m;
-                nb_d[lane] = kind == kVamanaPQ ? pq_asym_distance(code, lut, pq_m)
-                                               : pq_direct_distance(code, pq_cb, pq_scales, pq_offsets, qv, vamana_qprep, pq_m);
-            } else if (kind == kVamanaInt4Direct) {
-                // the same terms evaluated in place of the table read (vg_device.hpp)
-                nb_d[lane] = int4_l2_direct(qv, int4_rows + static_cast<int64_t>(id_lane) * (dim >> 1), dim, int4_min,
-                                            int4_diff, int4_pairs);
-            } else if (kind == kVamanaInt4) {
-                // iq.L2Distance (diskann/segment.go:558-565) = int4L2DistancePrecomputedAvx512 order
-                nb_d[lane] = int4_l2_precomputed(qv, int4_rows + static_cast<int64_t>(id_lane) * ((dim + 1) / 2), dim,
-                                                 int4_table);
-            } else {
-                // rows are rq_nb + 4 bytes with rq_nb a multiple of 8: every row is 4-byte aligned, so the
-                // bits and the norm are read as dwords, 8 loads in flight at a time; the query's words come from
-                // LDS (broadcast reads) — as scalar loads each one was a round trip the pass waited out
-                const uint32_t *cw = reinterpret_cast<const uint32_t *>(rq_rows + static_cast<int64_t>(id_lane) * (rq_nb + 4));
-                const uint32_t *qw = reinterpret_cast<const uint32_t *>(vamana_qprep);
-                const int nw = rq_nb >> 2;
-                int h = 0;
-                int b0 = 0;
-                for (; b0 + 8 <= nw; b0 += 8) {
-                    uint32_t x[8];
-#pragma unroll
-                    for (int u = 0; u < 8; u++) x[u] = cw[b0 + u];
-#pragma unroll
-                    for (int u = 0; u < 8; u++) h += __popc(x[u] ^ qw[b0 + u]);
-                }
-                for (; b0 < nw; b0++) h += __popc(cw[b0] ^ qw[b0]);
-                const uint32_t yb = cw[nw];
-                nb_d[lane] = rq_formula_g(qn, __uint_as_float(yb), static_cast<float>(dim), static_cast<float>(h));
-            }
-        }
-        __syncthreads();
-    };
-
-    WaveTopK tk;  // sc.Heap: top-k by (Score, RowID) — candidate_queue.go:12-23
-    tk.init(k < 64 ? k : 64);
-    // k > 64: the k best keys as a sorted list in LDS instead of one key per lane (wave-uniform bookkeeping)
-    int res_n = 0;
-    uint64_t res_tau = kKeyMax;
-    auto res_insert = [&](uint64_t c) {  // c < res_tau, every lane calls it with the same key
-        int lo = 0, hi = res_n;          // first position whose key is >= c (keys are distinct)
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (res[mid] < c)
-                lo = mid + 1;
-            else
-                hi = mid;
-        }
-        const int newn = res_n < k ? res_n + 1 : k;
-        if constexpr (!big) return;
-        uint64_t moved[kVamanaMaxK / 64];
-#pragma unroll
-        for (int u = 0; u < kVamanaMaxK / 64; u++) {
-            const int i = lo + lane + u * 64;
-            moved[u] = i < newn - 1 ? res[i] : kKeyMax;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int u = 0; u < kVamanaMaxK / 64; u++) {
-            const int i = lo + lane + u * 64;
-            if (i < newn - 1) res[i + 1] = moved[u];
-        }
-        if (lane == 0) res[lo] = c;
-        __syncthreads();
-        res_n = newn;
-        res_tau = res_n >= k ? res[k - 1] : kKeyMax;
-    };
-    // HUGE: the 64-ary max-heap (keys are distinct: a node enters the walk once); hl = its HBM part, indexed like the heap
-    uint64_t *hl = nullptr;
-    if constexpr (HUGE) hl = reinterpret_cast<uint64_t *>(cand_ws + q * cand_cap + ccap);
-    auto huge_insert = [&](uint64_t c) {  // c < res_tau, every lane calls it with the same key
-        const auto put = [&](int i, uint64_t v) {
-            if (i < kVamanaHeapLds)
-                res[i] = v;
-            else
-                hl[i] = v;
-        };
-        int i;
-        if (res_n < k) {  // push: up the parent chain
-            i = res_n++;
-            while (i > 0) {
-                const int p = (i - 1) >> 6;
-                const uint64_t pk = p < kVamanaHeapLds ? res[p] : hl[p];
-                if (pk > c) break;
-                put(i, pk);
-                i = p;
-            }
-        } else {  // the root leaves: c sinks along the largest children
-            i = 0;
-            for (;;) {
-                const int fc = 64 * i + 1;
-                if (fc >= k) break;
-                uint64_t v = 0;  // (below every key that can move: c >= 0)
-                if (fc + lane < k) v = fc < kVamanaHeapLds ? res[fc + lane] : hl[fc + lane];
-                uint64_t m = v;
-#pragma unroll
-                for (int off = 32; off > 0; off >>= 1) {
-                    const uint64_t o = (static_cast<uint64_t>(static_cast<uint32_t>(__shfl_xor(static_cast<int>(m >> 32), off))) << 32) |
-                                       static_cast<uint32_t>(__shfl_xor(static_cast<int>(static_cast<uint32_t>(m)), off));
-                    m = o > m ? o : m;
-                }
-                if (c >= m) break;
-                put(i, m);
-                i = fc + __builtin_ctzll(__ballot(v == m && fc + lane < k));
-            }
-        }
-        put(i, c);
-        res_tau = res_n >= k ? res[0] : kKeyMax;
-    };
-    (void)huge_insert;
-    auto offer = [&](uint64_t key) {
-        if (!big) {
-            tk.offer(key, lane);
-            return;
-        }
-        uint64_t mask = __ballot(key < res_tau);
-        while (mask) {
-            const int j = __builtin_ctzll(mask);
-            mask &= mask - 1;
-            const uint64_t c = readlane_u64(key, j);
-            if (c < res_tau) {  // the bound may have dropped since the ballot
-                if constexpr (HUGE)
-                    huge_insert(c);
-                else
-                    res_insert(c);
-            }
-        }
-    };
-    int heap_count = 0;  // min(k, candidates offered): sc.Heap.Len()
-    int cand_len = 0;
-    CItem *rheap = reinterpret_cast<CItem *>(res);  // STRICT: sc.Heap itself
-    if constexpr (HUGE && STRICT)  // k items of dynamic LDS after the query's image (the host sizes the allocation)
-        rheap = reinterpret_cast<CItem *>(reinterpret_cast<unsigned char *>(vamana_qprep) +
-                                          (kind == kVamanaPQDirect ? (pq_m >> 1) * kPqPairFloats * sizeof(float)
-                                                                   : kind == kVamanaRaBitQ ? rq_nb : 0));
-    auto strict_offer = [&](uint32_t id, float d) {   // TryPushBounded(k), candidate_queue.go:120-132 (uniform over the wave)
-        const CItem x{d, id};
-        if (heap_count < k) {
-            cand_up(rheap, heap_count, x, desc);
-            heap_count++;
-        } else if (cand_better(x, cand_load(rheap, 0), desc)) {
-            cand_down(rheap, 0, heap_count, x, desc);
-        }
-    };
-    (void)strict_offer;
+    uint64_t *set_lds = res, *set_hbm = nullptr;
+    if constexpr (HUGE && STRICT)  // k items of dynamic LDS after the scorer's staging (the host sizes the allocation)
+        set_lds = reinterpret_cast<uint64_t *>(reinterpret_cast<unsigned char *>(vamana_qprep) + Scorer::lds_bytes(pq_m, rq_nb));
+    else if constexpr (HUGE)
+        set_hbm = reinterpret_cast<uint64_t *>(cand_ws + q * cand_cap + ccap);
+    Results results(set_lds, set_hbm, k, lane, desc);
 
     // start node (segment.go:603-636)
+    int64_t st_visited = 0, st_dc = 1, st_pops = 0, st_dropped = 0;
+    int cand_len = 0;
     if (lane == 0) atomicOr(&vis[entry >> 5], 1u << (entry & 31));
-    score_mask(1ull, entry);
+    sc.many(1ull, entry, lane, nb_d);
+    __syncthreads();
     const float sd = nb_d[0];
-    st_dc++;
     heap_push<false>(cand, cand_len, HItem{entry, sd});
     // pushToHeap (segment.go:616-627): a row whose filter.Matches is false goes to the traversal queue only — sc.Heap, and with it
     // the pruning test below, holds matching rows
     const uint8_t *mq = MASKED && mask ? mask + blockIdx.x * mask_stride : nullptr;
     const bool entry_ok = !MASKED || mask_bit(mq, entry);
     if constexpr (STRICT) {
-        if (entry_ok) strict_offer(entry, sd);
+        if (entry_ok) results.offer(entry, sd);
     } else {
-        offer(lane == 0 && entry_ok ? make_key(sd, entry, desc) : kKeyMax);
-        heap_count = entry_ok && 1 < k ? 1 : (entry_ok ? k : 0);
+        results.offer(lane == 0 && entry_ok ? make_key(sd, entry, desc) : kKeyMax, entry_ok);
     }
     __syncthreads();
 
     while (cand_len > 0) {
         const HItem c = heap_pop<false>(cand, cand_len);
         st_pops++;
-        if (heap_count >= k) {
-            const float worst = STRICT ? cand_load(rheap, 0).score : key_score(big ? res_tau : tk.tau, desc);
-            if (c.dist > worst) break;
-        }
+        if (results.count >= k && c.dist > results.worst()) break;
         const uint32_t id_lane = lane < r ? graph[static_cast<int64_t>(c.node) * r + lane] : VG_INVALID_ID;
         bool fresh = false;
         if (id_lane != VG_INVALID_ID && id_lane < n) {
@@ -643,78 +593,34 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kind == kVam
         const int nnew = __popcll(newmask);
         st_visited += nnew;
         st_dc += nnew;
-        score_mask(newmask, id_lane);
+        sc.many(newmask, id_lane, lane, nb_d);
+        __syncthreads();
         const float myd = nb_d[lane];
-        if constexpr (STRICT) {  // neighbour by neighbour: PushItem, then pushToHeap (segment.go:690-700)
-            uint64_t todo = newmask;
-            while (todo) {
+        // exploration heap: PushItem in the node's neighbour order (segment.go:695) — as one run, parents tracked in registers, or
+        // neighbour by neighbour; STRICT: each followed by its pushToHeap (segment.go:690-700)
+        if (!STRICT && cand_len + nnew <= ccap) {
+            heap_push_run_min(cand, cand_len, newmask, id_lane, myd);
+        } else {
+            for (uint64_t todo = newmask; todo; todo &= todo - 1) {
                 const int j = __builtin_ctzll(todo);
-                todo &= todo - 1;
                 const uint32_t id = static_cast<uint32_t>(__builtin_amdgcn_readlane(id_lane, j));
                 const float d = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(myd), j));
                 if (cand_len < ccap)
                     heap_push<false>(cand, cand_len, HItem{id, d});
                 else
-                    st_dropped++;
-                if (mask_bit(mq, id)) strict_offer(id, d);
-            }
-            __syncthreads();
-            continue;
-        }
-        // exploration heap: PushItem in the node's neighbour order (segment.go:695)
-        if (cand_len + nnew <= ccap) {
-            heap_push_run_min(cand, cand_len, newmask, id_lane, myd);  // the run of pushes, parents tracked in registers
-        } else {
-            uint64_t todo = newmask;
-            while (todo) {
-                const int j = __builtin_ctzll(todo);
-                todo &= todo - 1;
-                if (cand_len < ccap)
-                    heap_push<false>(cand, cand_len,
-                                     HItem{static_cast<uint32_t>(__builtin_amdgcn_readlane(id_lane, j)),
-                                           __int_as_float(__builtin_amdgcn_readlane(__float_as_int(myd), j))});
-                else
                     st_dropped++;  // the reference's heap is unbounded: reported, see vg_search_stats
+                if constexpr (STRICT) {
+                    if (mask_bit(mq, id)) results.offer(id, d);
+                }
             }
         }
-        // result heap: TryPushBounded(k) — a set maintained by (score, id): order-free
-        const bool pass = fresh && (!MASKED || mask_bit(mq, id_lane));
-        const int npass = MASKED ? __popcll(__ballot(pass)) : nnew;
-        offer(pass ? make_key(myd, id_lane, desc) : kKeyMax);
-        heap_count = heap_count + npass < k ? heap_count + npass : k;
+        if constexpr (!STRICT) {  // result heap: TryPushBounded(k) — a set maintained by (score, id): order-free
+            const bool pass = fresh && (!MASKED || mask_bit(mq, id_lane));
+            results.offer(pass ? make_key(myd, id_lane, desc) : kKeyMax, MASKED ? __popcll(__ballot(pass)) : nnew);
+        }
         __syncthreads();
     }
-    if constexpr (STRICT) {  // the engine empties the heap with Pop() (engine/search.go:859-862): reported best first
-        const int nres = heap_count;
-        for (int i = nres - 1; i >= 0; i--) {
-            const CItem it = cand_pop(rheap, heap_count, desc);
-            if (lane == 0) {
-                ids[q * k + i] = it.row;
-                scores[q * k + i] = it.score;
-            }
-        }
-        for (int i = nres + lane; i < k; i += 64) {
-            ids[q * k + i] = VG_INVALID_ID;
-            scores[q * k + i] = desc ? -INFINITY : INFINITY;
-        }
-    } else if constexpr (HUGE) {  // the heap's keys, the rest kKeyMax, to its HBM list: the host's sort writes them best first
-        for (int i = lane; i < k; i += 64) {
-            if (i >= res_n)
-                hl[i] = kKeyMax;
-            else if (i < kVamanaHeapLds)
-                hl[i] = res[i];
-        }
-    } else if (big) {
-        for (int i = lane; i < k; i += 64) {
-            const uint64_t e = i < res_n ? res[i] : kKeyMax;
-            ids[q * k + i] = e == kKeyMax ? VG_INVALID_ID : key_row(e);
-            scores[q * k + i] = e == kKeyMax ? (desc ? -INFINITY : INFINITY) : key_score(e, desc);
-        }
-    } else if (lane < k) {
-        const uint64_t e = tk.list;
-        ids[q * k + lane] = e == kKeyMax ? VG_INVALID_ID : key_row(e);
-        scores[q * k + lane] = e == kKeyMax ? (desc ? -INFINITY : INFINITY) : key_score(e, desc);
-    }
+    results.write(ids + q * k, scores + q * k);
     if (stats && lane == 0) {
         stats[q].nodes_visited = st_visited;
         stats[q].distance_computations = st_dc;
@@ -868,7 +774,7 @@ static int32_t search_hnsw_impl(vg_index *idx, bool pq, const float *queries, in
     const int lds_ef = pq ? VG_SPLIT_PQ_LDS_EF : VG_SPLIT_F32_LDS_EF;
     const int lds_cand = 2 * lds_ef, lds_res = lds_ef;
     const int64_t heap_bytes = lds_heaps ? 0 : static_cast<int64_t>(3) * ef * sizeof(vg::HItem);
-    // sub-dimension 8: node terms straight from the codebook (vg_hnsw_layer.hpp PqScorer), no per-query table
+    // sub-dimension 8: node terms straight from the codebook (vg_node_score.hpp PqScorer), no per-query table
     const bool pq_direct = pq && idx->pq->subdim == 8 && (reinterpret_cast<uintptr_t>(idx->pq->d_codebooks) & 7) == 0;
     const int64_t lut_bytes = pq_direct ? 0 : static_cast<int64_t>(pq_m) * 256 * sizeof(float);
     vg::WalkChunks wc(vg::scratch_cap(idx->ctx), heap_bytes + lut_bytes, idx->n, nq);
@@ -1027,8 +933,12 @@ static int32_t vamana_impl(vg_index *idx, const float *queries, int64_t nq, int3
     }
     const bool big = k > 64;
     const int inst = pq_direct ? vg::kVamanaPQDirect : int4_direct ? vg::kVamanaInt4Direct : kind;
-    // what a launch keeps in LDS besides its heap: the direct PQ form's query constants, RaBitQ's query code
-    const size_t scorer_lds = pq_direct ? static_cast<size_t>(pq_m >> 1) * vg::kPqPairFloats * sizeof(float) : (kind == 2 ? static_cast<size_t>(rq_nb) : 0);
+    // what a launch keeps in LDS besides its heap: the scorer's staging (the direct PQ form's query constants, RaBitQ's query code)
+    size_t scorer_lds = 0;
+    (void)with_vamana_kind(inst, [&](auto kind_c) -> int32_t {
+        scorer_lds = vg::VamanaScorer<decltype(kind_c)::value>::type::lds_bytes(pq_m, rq_nb);
+        return VG_OK;
+    });
     VG_TRY(wc.for_each(st, [&](int64_t q0, int64_t cnt) -> int32_t {
         vg::ProfScope prof(idx->ctx, "vamana_search", st);
         // (the STRICT pass of a large-k walk keeps its k-item CandidateHeap after the query's image: extra_lds)

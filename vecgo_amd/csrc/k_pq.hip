@@ -1,6 +1,6 @@
 // k_pq.hip — quantization.ProductQuantizer on the device (internal/quantization/pq.go).
 #include "vg_device.hpp"
-#include "vg_hnsw_layer.hpp"
+#include "vg_node_score.hpp"
 #include "vg_internal.hpp"
 #include "vg_search.hpp"
 
@@ -62,7 +62,7 @@ __global__ __launch_bounds__(256) void pq_build_table_rows8_kernel(const float *
                                                                     const float *__restrict__ offsets, int m,
                                                                     float *__restrict__ tables)
 {
-    // Two sub-quantizers per packed-fp32 instruction (pq_term8_pair, vg_hnsw_layer.hpp: each half is the scalar
+    // Two sub-quantizers per packed-fp32 instruction (pq_term8_pair, vg_node_score.hpp: each half is the scalar
     // operation of its own sub-quantizer — the same five rounded operations per dimension, in order): 28 instead of 48
     // vector instructions per table entry.  The kernel is bound by exactly that count (4096 waves x 96 x 48 instructions
     // at one per 4 cycles and SIMD = the 40 us it took; 8 codebook entries in flight per thread changed nothing).

@@ -9,7 +9,7 @@
 #include <algorithm>
 
 #include "vg_device.hpp"
-#include "vg_hnsw_layer.hpp"
+#include "vg_node_score.hpp"
 #include "vg_internal.hpp"
 
 namespace vg {
@@ -861,7 +861,7 @@ __global__ void pq_asym_kernel(const float *__restrict__ query, const uint8_t *_
     out[i] = distance;
 }
 
-// The same distances with the graph walks' term code (vg_hnsw_layer.hpp: sub-dimension 8, two sub-quantizers per
+// The same distances with the graph walks' term code (vg_node_score.hpp: sub-dimension 8, two sub-quantizers per
 // packed-fp32 instruction, the query's constants laid out once per workgroup in LDS, 16 centroid loads in flight per
 // lane): 1.12 -> ~0.1 ms per million codes at m = 96.  Bit for bit the loop above (the same five rounded operations per
 // dimension, terms added in sub-quantizer order).

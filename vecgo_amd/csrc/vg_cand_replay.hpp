@@ -15,6 +15,7 @@
 // heap's history; the scans' pre-tests `score < bound` drop them while the bound is still +Inf.)  A query without risk returns at once (the
 // launch costs a few microseconds per search call); a query with risk overwrites what the fast path wrote for it.  Rare by
 // construction — such inputs are garbage — so the walk is written for exactness, not speed: ~n * dim / 100 GB/s per query.
+// (The DiskANN walk's STRICT pass asks its node scorers the same question: their risk() and walk_risk, vg_node_score.hpp.)
 #pragma once
 
 #include <hip/hip_runtime.h>
