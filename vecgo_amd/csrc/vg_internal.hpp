@@ -97,6 +97,7 @@ enum Hook {
     kHookVamanaSmallScratch,  // VG_VAMANA_SMALL_SCRATCH a small batch takes several launches: vg_search_vamana with k > 512 gets 64 MiB of per-launch scratch, the Vamana builders' visited bitmaps (VamanaBatch, vg_vamana_common.hpp) 64 KiB
     kHookFlatRescoreSample,   // VG_FLAT_RESCORE_SAMPLE  flat search: the main GEMM multiplies the sampled row tiles again (no append from the sample)
     kHookPthrForceHist,       // VG_PTHR_FORCE_HIST      vg_search_flat_probed_threshold without rerank: the top-max_results-by-histogram form, then the filter
+    kHookWalkSmallScratch,    // VG_WALK_SMALL_SCRATCH   a search walk's batch goes in launches of at most 5 queries (WalkChunks, vg_search.hpp): vg_search_hnsw / _pq / _filtered / _predicate, vg_search_vamana and its kin, vg_search_vamana_fresh
     kHookCount
 };
 bool hook(Hook h);

@@ -229,7 +229,9 @@ inline int32_t for_each_walk_chunk(uint32_t *vis, int64_t vis_words, int64_t chu
 
 // A batch of graph walks in launches of `chunk` queries (for_each_walk_chunk), each query with a visited bitmap of
 // vis_words words of its own.  other_bytes: a query's scratch besides the bitmap.  add() before the arena's commit() — the
-// caller's pieces are chunk times a query's —, for_each() after it.
+// caller's pieces are chunk times a query's —, for_each() after it.  The test hook VG_WALK_SMALL_SCRATCH caps a launch at
+// kWalkHookChunk queries, so that a test batch takes the several launches a batch over a large graph takes.
+constexpr int64_t kWalkHookChunk = 5;
 struct WalkChunks {
     int64_t nq, vis_words, chunk;
     const ArenaCall *ar = nullptr;
@@ -237,6 +239,7 @@ struct WalkChunks {
     WalkChunks(int64_t cap, int64_t other_bytes, int64_t n, int64_t nq_)
         : nq(nq_), vis_words((n + 31) / 32), chunk(walk_chunk(cap, vis_words * 4 + other_bytes, nq_))
     {
+        if (hook(kHookWalkSmallScratch)) chunk = std::min(chunk, kWalkHookChunk);
     }
     void add(ArenaCall &a)
     {
