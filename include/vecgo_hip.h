@@ -163,7 +163,8 @@ int32_t vg_ctx_device_info(vg_ctx *ctx, char *arch, int32_t arch_len, int32_t *c
  * read for `kernel` ("flat_gemm", "pq_adc_scan", "rabitq_scan", "flat_select", "topk_merge",
  * "hnsw_search", "vamana_search"), and clears those records.  The name "staged_device_buffers" is a counter, not a
  * kernel: how many misaligned DEVICE buffers the process passed through a scratch block since the last read ("Alignment"
- * above), profiling enabled or not; total_ms is 0. */
+ * above), profiling enabled or not; total_ms is 0.  Likewise "flat_split_launches": launches of vg_search_flat's split
+ * nomination tile (three bfloat16 products on the fp32 rows) since the last read. */
 int32_t vg_profile_enable(vg_ctx *ctx, int32_t on);
 int32_t vg_profile_read(vg_ctx *ctx, const char *kernel, int64_t *launches, double *total_ms);
 

@@ -1,5 +1,6 @@
 // k_flat.hip — exact brute-force search (flat/segment.go:691-721, hnsw.go:2021-2101):
-//   1. scores[q][n] = ||x_n||^2 - 2 q.x_n  (L2)  or  -q.x_n  (Dot)   fp32 MFMA GEMM
+//   1. scores[q][n] = ||x_n||^2 - 2 q.x_n  (L2)  or  -q.x_n  (Dot)   fp32 MFMA GEMM (above 128 queries: the split tile,
+//      three bf16 products on the fp32 rows — gemm_runs_split)
 //   2. per query: the kc smallest scores                              streaming select
 //   3. exact re-scoring of those kc rows in the reference's summation order, top-k by
 //      (Score, RowID), and a proof that no other row can belong to the top-k (k > 48: every row whose
@@ -46,15 +47,53 @@ struct GemmArgs {
     // MODE 2, > 1: every skip_stride-th row tile is left out — the tiles MODE 1 sampled, whose passing rows the caller appends from
     // the sample itself (flat_sample_append_kernel).  Only where gemm_skips_sample() says so; 0: every tile.
     int skip_stride = 0;
+    // MODE 2: the split tile (flat_gemm_split_big_kernel) — `queries` is flat_split_queries_kernel's image of the chunk, `base` the
+    // fp32 rows.  Set only where gemm_runs_split() says so (vg_search_flat's fused path).
+    bool split = false;
 };
 constexpr int kCountLine = 32;
+// Whether a MODE 2 launch of vg_search_flat's fused path runs the split tile: fp32 rows nominated by three bfloat16 products on the
+// persistent 256 x 256 tile instead of the fp32 matrix instruction (16x the rate per product).  The ONE place that decides: the
+// launcher, the query image and the proof's margin (split_gemm_eps) all follow it.  More than one 128-query tile, LDS-DMA operands
+// (16-byte aligned), whole K steps of 32 floats, and the big tile's own limits (32-bit candidate offsets, 16-bit threshold stride).
+// (test hook kHookFlatNoSplit: the fp32 GEMM as before)
+static bool gemm_runs_split(bool fused, bool bf16, bool dma, int64_t nq, int dim, int cap, int thr_stride)
+{
+    return fused && !bf16 && dma && nq > kGemmBM && dim % kGemmBK == 0 && nq * static_cast<int64_t>(cap) < (int64_t(1) << 31) &&
+           thr_stride < 65536 && !hook(kHookFlatNoSplit);
+}
+// The split tile's |score - true score| as a multiple of |q|^2 + max |x|^2 (the verify kernels' eps_extra).  With u = 2^-8
+// (bfloat16 keeps 8 significant bits, round to nearest even) an operand is x = hi + lo + rho: hi = rne(x), the remainder
+// r = x - hi exact in fp32 with |r| <= u |x|, lo = rne(r), so |lo| <= u |x| and |rho| <= u^2 |x|.  The tile sums
+// q_hi x_hi + q_lo x_hi + q_hi x_lo, every product exact in fp32 (16 significant bits), and leaves out
+//     q_lo x_lo + rho_q x + (q_hi + q_lo) rho_x:   at most (3 u^2 + u^4) |q_i x_i| per element,
+// over a row (3 * 2^-16 + 2^-32) |q||x| <= 1.5001 * 2^-16 (|q|^2 + |x|^2).                                              [dropped]
+// The accumulator starts at s = t (Dot) or (t - |x|^2) / 2 (L2), exact three-way splits summed by 8 matrix-unit additions, takes
+// the 3 dim products, and the appended key's score is one more fma: m = 3 dim + 16 roundings, each taken to lose 2^-24 of the
+// largest partial sum whatever the order: m 2^-24 (|s| + S), S = sum |products| <= (1 + u)^2 |q||x| <= 0.51 (|q|^2 + |x|^2).
+// flat_thr_cap_kernel keeps t <= 2.002 (|q|^2 + max |x|^2) (a sampled threshold is a score and far inside), so |s| <= 2.002 of
+// that for Dot and (2.002 + 1) / 2 <= 1.501 for L2.                                                                 [accumulation]
+//     Dot:  1.5001 * 2^-16 + 2.52 (3 dim + 16) 2^-24          L2 (the score is -2 acc + ...: twice):  3.0002 * 2^-16 + 4.03 (3 dim + 16) 2^-24
+// At dim 768: 1.7e-4 and 6.0e-4, beside the fp32 GEMM's own 4 dim 2^-24 = 1.8e-4 (kept: it also covers the exact re-score's
+// roundings) and the bfloat16 filter's 8e-3.  tests/test_flat_split_bound.py models the sum and checks this function's formula.
+// What the split cannot represent: |x| >= 2^128 (1 - 2^-9) rounds hi to Inf and lo to NaN, an Inf or NaN operand likewise —
+// the accumulator of every product with it is NaN, and a NaN is never appended (the sign test is a float compare).  Such a row has
+// |x|^2 = Inf or NaN, so d_norm_max is not finite and every query's margin eps is Inf or NaN: no proof holds and the exhaustive
+// kernel answers, as under the bfloat16 filter; such a query has |q|^2 not finite, the same.  Denormals: a product or a lo half
+// below 2^-126 that the matrix unit or the subtraction flushes moves the sum by at most 2^-126 dim max|q_i| < 1e-35 (1 + |q|^2),
+// inside eps's absolute 1e-30 or its relative part.
+static float split_gemm_eps(bool dot, int dim)
+{
+    const float m = static_cast<float>(3 * dim + 16) * 5.9604645e-8f;
+    return dot ? 1.5001f * 1.52587890625e-5f + 2.52f * m : 3.0002f * 1.52587890625e-5f + 4.03f * m;
+}
 // Whether launch_gemm_t runs a kernel that honours GemmArgs::skip_stride for these arguments: the fp32 128 x 128 tiles (LDS-DMA and
 // register-staged), whose MODE 1 and MODE 2 are one body with one accumulation order.  Not the 32-row tiles (up to 96 queries), not
-// a bf16 kernel.  The ONE place that decides: the caller appends the sampled rows itself exactly where this is true (a row
+// a bf16 kernel, not the split tile (`split`: gemm_runs_split's answer).  The ONE place that decides: the caller appends the sampled rows itself exactly where this is true (a row
 // appended by both, or by neither, is a wrong answer).
-static bool gemm_skips_sample(bool dma, int64_t nq, bool bf16)
+static bool gemm_skips_sample(bool dma, int64_t nq, bool bf16, bool split = false)
 {
-    if (bf16 || hook(kHookFlatRescoreSample)) return false;
+    if (bf16 || split || hook(kHookFlatRescoreSample)) return false;
     return !(dma && nq <= 3 * kG32BM && !hook(kHookFlatNoSmallTile));
 }
 __global__ void counts_narrow_kernel(const int *__restrict__ wide, int64_t nq, int *__restrict__ counts)
@@ -67,7 +106,26 @@ template <bool DOT, int MODE>
 static int32_t launch_gemm_t(bool dma, unsigned blocks, hipStream_t st, const GemmArgs &a, bool bf16)
 {
     const int skip = MODE == 2 ? a.skip_stride : 0;
-    VG_CHECK(skip == 0 || (skip > 1 && gemm_skips_sample(dma, a.nq, bf16)), VG_ERR_INVALID_ARG, "launch_gemm: skip_stride on a kernel without it");
+    VG_CHECK(skip == 0 || (skip > 1 && gemm_skips_sample(dma, a.nq, bf16, a.split)), VG_ERR_INVALID_ARG, "launch_gemm: skip_stride on a kernel without it");
+    // the persistent 256 x 256 tile (bf16 images, or the split tile on the fp32 rows): one workgroup per CU, wide counters
+    auto launch_big = [&](auto kern, size_t lds) -> int32_t {
+        VG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   static_cast<int>(lds)));
+        const int64_t mt = (a.nq + kBigBM - 1) / kBigBM, nt = (a.n + kBigBN - 1) / kBigBN;
+        const int64_t slots = mt * ((nt + 7) / 8) * 8, per_cu = std::max(a.cus / 8, 1) * 8;  // (one workgroup per CU: LDS)
+        if (a.counts_wide) VG_HIP(hipMemsetAsync(a.counts_wide, 0, sizeof(int) * static_cast<size_t>(a.nq) * kCountLine, st));
+        VG_LAUNCH(kern, dim3(static_cast<unsigned>(std::min(slots, per_cu))), dim3(kBigThreads), lds, st, a.queries, a.nq,
+                  a.base, a.n, a.dim, a.norms, a.thr, a.thr_stride, a.thr_off, a.counts_wide ? a.counts_wide : a.counts, a.cand, a.cap, a.mask,
+                  a.mask_stride, a.counts_wide ? kCountLine : 1);
+        if (a.counts_wide)
+            VG_LAUNCH(counts_narrow_kernel, dim3(static_cast<unsigned>((a.nq + 255) / 256)), dim3(256), 0, st, a.counts_wide, a.nq, a.counts);
+        return VG_OK;
+    };
+    if (MODE == 2 && a.split) {
+        VG_CHECK(!bf16 && gemm_runs_split(true, false, dma, a.nq, a.dim, a.cap, a.thr_stride), VG_ERR_INVALID_ARG, "launch_gemm: split tile on a call without it");
+        note_flat_split_launch();
+        return launch_big(flat_gemm_split_big_kernel<DOT, 3>, big_lds_bytes<3>());
+    }
     if (skip) {  // the grid of the tiles that are left, in the same XCD-aware order
         const int64_t mt = (a.nq + kGemmBM - 1) / kGemmBM, nt = (a.n + kGemmBN - 1) / kGemmBN;
         const int64_t left = nt - gemm_skip_sampled_tiles(nt, skip);
@@ -97,18 +155,7 @@ static int32_t launch_gemm_t(bool dma, unsigned blocks, hipStream_t st, const Ge
             !hook(kHookFlatNoBigTile)) {
             const bool two = hook(kHookFlatBigTile2);
             auto kern = two ? flat_gemm_bf16_big_kernel<DOT, 2> : hook(kHookFlatBigEarlyB) ? flat_gemm_bf16_big_kernel<DOT, 3, 512> : flat_gemm_bf16_big_kernel<DOT, 3>;
-            const size_t lds = two ? big_lds_bytes<2>() : big_lds_bytes<3>();
-            VG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       static_cast<int>(lds)));
-            const int64_t mt = (a.nq + kBigBM - 1) / kBigBM, nt = (a.n + kBigBN - 1) / kBigBN;
-            const int64_t slots = mt * ((nt + 7) / 8) * 8, per_cu = std::max(a.cus / 8, 1) * 8;  // (one workgroup per CU: LDS)
-            if (a.counts_wide) VG_HIP(hipMemsetAsync(a.counts_wide, 0, sizeof(int) * static_cast<size_t>(a.nq) * kCountLine, st));
-            VG_LAUNCH(kern, dim3(static_cast<unsigned>(std::min(slots, per_cu))), dim3(kBigThreads), lds, st, a.queries, a.nq,
-                      a.base, a.n, a.dim, a.norms, a.thr, a.thr_stride, a.thr_off, a.counts_wide ? a.counts_wide : a.counts, a.cand, a.cap, a.mask,
-                      a.mask_stride, a.counts_wide ? kCountLine : 1);
-            if (a.counts_wide)
-                VG_LAUNCH(counts_narrow_kernel, dim3(static_cast<unsigned>((a.nq + 255) / 256)), dim3(256), 0, st, a.counts_wide, a.nq, a.counts);
-            return VG_OK;
+            return launch_big(kern, two ? big_lds_bytes<2>() : big_lds_bytes<3>());
         }
         auto kern = flat_gemm_dma_kernel<DOT, M, 0, true>;
         VG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -173,6 +220,23 @@ __global__ void f32_to_bf16_pad_kernel(const float *__restrict__ src, int64_t ro
     else
         v = static_cast<uint16_t>((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
     dst[i] = v;
+}
+
+// The queries of the split tile (flat_gemm_split_big_kernel) as an image of `dim` 4-byte words per row, like the fp32 row it is
+// made from: every 128-byte K step holds [hi of its 32 elements | lo of the same 32], so that both operands advance by the same
+// k per step.  One thread per pair of elements; dim % 32 == 0.
+__global__ void flat_split_queries_kernel(const float *__restrict__ src, int64_t rows, int dim, uint32_t *__restrict__ dst)
+{
+    const int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;  // pair index
+    const int half = dim / 2;
+    if (i >= rows * half) return;
+    const int64_t r = i / half;
+    const int p = static_cast<int>(i - r * half), s = p >> 4, w = p & 15;
+    const float2 v = *reinterpret_cast<const float2 *>(src + r * dim + 32 * s + 2 * w);
+    uint32_t hi, lo;
+    split2_bf16(v.x, v.y, hi, lo);
+    dst[r * dim + 32 * s + w] = hi;
+    dst[r * dim + 32 * s + 16 + w] = lo;
 }
 
 // After the proofs: the work list of step 4 (todo[0] = how many queries need the exhaustive scan,
@@ -864,9 +928,12 @@ int32_t vg::flat_search_masked(vg_index *idx, const float *queries, int64_t nq, 
         // (any dim: the copies' rows are padded with zeros to whole K steps, vectors_bf16_dim)
         const bool bf16 = idx->d_vectors_bf16 != nullptr && fused && !vg::hook(vg::kHookFlatNoDma);
         const int bdim = idx->vectors_bf16_dim;
-        const float eps_extra = !bf16 ? 0.0f : (dot ? 0.00390625f : 0.0078125f) * 1.02f;
-        const int i_qbf = ar.add(bf16 ? sizeof(uint16_t) * static_cast<size_t>(qc) * bdim : 0);
-        const int i_cwide = ar.add(bf16 ? sizeof(int) * static_cast<size_t>(qc) * vg::kCountLine : 0);
+        const float bf16_eps = !bf16 ? 0.0f : (dot ? 0.00390625f : 0.0078125f) * 1.02f;
+        // without the filter, a chunk above 128 queries nominates on the split tile (gemm_runs_split, decided per chunk below: the
+        // margin grows by split_gemm_eps, the chunk's queries are written as a hi | lo image, the appends count in wide counters)
+        const bool may_split = vg::gemm_runs_split(fused, bf16, true, qc, dim, cap, sel_k);
+        const int i_qbf = ar.add(bf16 ? sizeof(uint16_t) * static_cast<size_t>(qc) * bdim : may_split ? sizeof(uint32_t) * static_cast<size_t>(qc) * dim : 0);
+        const int i_cwide = ar.add(bf16 || may_split ? sizeof(int) * static_cast<size_t>(qc) * vg::kCountLine : 0);
         VG_TRY(ar.commit());
         uint16_t *qbf = ar.get<uint16_t>(i_qbf);
         float *sc = ar.get<float>(i_sc), *thr = ar.get<float>(i_thr);
@@ -876,7 +943,7 @@ int32_t vg::flat_search_masked(vg_index *idx, const float *queries, int64_t nq, 
         uint64_t *min_keys = ar.get<uint64_t>(i_minkeys);
         uint32_t *sid = ar.get<uint32_t>(i_sid), *cand_id = ar.get<uint32_t>(i_cand_id), *fid = ar.get<uint32_t>(i_fid);
         int *counts = ar.get<int>(i_counts), *flags = ar.get<int>(i_flags), *todo = ar.get<int>(i_todo);
-        int *counts_wide = bf16 ? ar.get<int>(i_cwide) : nullptr;
+        int *counts_wide = bf16 || may_split ? ar.get<int>(i_cwide) : nullptr;
 
         int *always = flags + qc;  // test hook kHookFlatForceExact: run step 4 for every query
         VG_HIP(hipMemsetAsync(always, vg::hook(vg::kHookFlatForceExact) ? 1 : 0, sizeof(int), st));
@@ -889,6 +956,8 @@ int32_t vg::flat_search_masked(vg_index *idx, const float *queries, int64_t nq, 
             // (test hook kHookFlatNoDma: force the register-staged GEMM)
             const bool dma = dim % 4 == 0 && (reinterpret_cast<uintptr_t>(qp) & 15) == 0 &&
                              (reinterpret_cast<uintptr_t>(idx->d_vectors) & 15) == 0 && !vg::hook(vg::kHookFlatNoDma);
+            const bool split = vg::gemm_runs_split(fused, bf16, dma, cnt, dim, cap, sel_k);
+            const float eps_extra = split ? vg::split_gemm_eps(dot, dim) : bf16_eps;
             // operands of the nomination GEMMs
             const float *ga = qp, *gb = idx->d_vectors;
             int gdim = dim;
@@ -912,11 +981,14 @@ int32_t vg::flat_search_masked(vg_index *idx, const float *queries, int64_t nq, 
                     VG_LAUNCH(vg::fill_f32_kernel, dim3(static_cast<unsigned>((cnt * sel_k + 255) / 256)), dim3(256),
                               0, st, thr, cnt * sel_k, INFINITY);
                 }
-                if (bf16) VG_LAUNCH(vg::flat_thr_cap_kernel, dim3(ucnt), dim3(64), 0, st, thr, sel_k, qp, dim, idx->d_norm_max);
+                if (bf16 || split) VG_LAUNCH(vg::flat_thr_cap_kernel, dim3(ucnt), dim3(64), 0, st, thr, sel_k, qp, dim, idx->d_norm_max);
+                if (split)
+                    VG_LAUNCH(vg::flat_split_queries_kernel, dim3(static_cast<unsigned>((cnt * (dim / 2) + 255) / 256)), dim3(256), 0, st, qp,
+                              cnt, dim, reinterpret_cast<uint32_t *>(qbf));
                 // (b) the GEMM, appending every element below its query's threshold.  The sampled tiles' scores are in `sc` already,
                 // bit for bit, where (a) ran the same tile: what passes there is appended from `sc` (which also sets the counters)
                 // and the GEMM leaves those tiles out — 63/64 of the elements (test hook kHookFlatRescoreSample: all of them again)
-                const bool once = use_sample && vg::gemm_skips_sample(dma, cnt, bf16);
+                const bool once = use_sample && vg::gemm_skips_sample(dma, cnt, bf16, split);
                 if (!once) VG_HIP(hipMemsetAsync(counts, 0, sizeof(int) * static_cast<size_t>(cnt), st));
                 {
                     vg::ProfScope prof(idx->ctx, "flat_gemm", st);
@@ -924,9 +996,9 @@ int32_t vg::flat_search_masked(vg_index *idx, const float *queries, int64_t nq, 
                         VG_LAUNCH(vg::flat_sample_append_kernel, dim3(ucnt), dim3(vg::kSampleAppendThreads), 0, st, sc, ns, sample_stride,
                                   thr, sel_k, sel_k - 1, counts, cand, cap);
                     VG_TRY(vg::launch_gemm<2>(dot, dma, static_cast<unsigned>(mt * ((nt + 7) / 8) * 8), st,
-                                              {ga, cnt, gb, n, gdim, idx->d_norms, nullptr, 1, 0, thr,
-                                               sel_k, sel_k - 1, counts, cand, cap, m0, mask_stride, idx->ctx->compute_units, counts_wide,
-                                               once ? sample_stride : 0}, bf16));
+                                              {split ? reinterpret_cast<const float *>(qbf) : ga, cnt, gb, n, gdim, idx->d_norms, nullptr, 1, 0, thr,
+                                               sel_k, sel_k - 1, counts, cand, cap, m0, mask_stride, idx->ctx->compute_units,
+                                               bf16 || split ? counts_wide : nullptr, once ? sample_stride : 0, split}, bf16));
                 }
                 // (c) the kc best appended keys (k > kGemmMaxK: all of them go to the exact re-score below)
                 if (k <= vg::kGemmMaxK)

@@ -29,6 +29,7 @@ bool is_device_ptr(const void *p)
 
 namespace {
 std::atomic<int64_t> g_staged_device_buffers{0};
+std::atomic<int64_t> g_flat_split_launches{0};
 struct ScratchBlock {
     void *p;
     size_t cap;
@@ -53,6 +54,8 @@ size_t scratch_round(size_t bytes)
 
 void note_staged_device_buffer() { g_staged_device_buffers.fetch_add(1, std::memory_order_relaxed); }
 int64_t take_staged_device_buffers() { return g_staged_device_buffers.exchange(0, std::memory_order_relaxed); }
+void note_flat_split_launch() { g_flat_split_launches.fetch_add(1, std::memory_order_relaxed); }
+int64_t take_flat_split_launches() { return g_flat_split_launches.exchange(0, std::memory_order_relaxed); }
 
 int32_t scratch_alloc(void **out, size_t bytes, hipStream_t s)
 {
@@ -235,6 +238,11 @@ VG_API int32_t vg_profile_read(vg_ctx *ctx, const char *kernel, int64_t *launche
         *total_ms = 0.0;
         return VG_OK;
     }
+    if (strcmp(kernel, "flat_split_launches") == 0) {  // likewise
+        *launches = vg::take_flat_split_launches();
+        *total_ms = 0.0;
+        return VG_OK;
+    }
     VG_HIP(hipSetDevice(ctx->device));
     std::lock_guard<std::mutex> g(ctx->prof_mu);
     int64_t n = 0;
@@ -319,7 +327,7 @@ static const char *const kHookNames[kHookCount] = {"VG_FLAT_NO_SMALL_TILE", "VG_
                                                    "VG_PQ_LIST_ALL", "VG_PQ_FP32_MFMA", "VG_PROBE_NO_GEMM", "VG_FLAT_NO_BIG_TILE",
                                                    "VG_FLAT_BIG_TILE_2", "VG_FLAT_BIG_EARLY_B", "VG_PQ_NOM_ALWAYS", "VG_KM_NO_RANGES", "VG_NO_CAND_REPLAY",
                                                    "VG_VAMANA_SMALL_SCRATCH", "VG_FLAT_RESCORE_SAMPLE", "VG_PTHR_FORCE_HIST",
-                                                   "VG_WALK_SMALL_SCRATCH"};
+                                                   "VG_WALK_SMALL_SCRATCH", "VG_FLAT_NO_SPLIT"};
 static void hooks_from_env()
 {
     for (int h = 0; h < kHookCount; h++) {

@@ -1,4 +1,4 @@
-// vg_flat_gemm.hpp — the fp32 MFMA GEMM that nominates candidates for the flat search (k_flat.hip).
+// vg_flat_gemm.hpp — the MFMA GEMMs that nominate candidates for the flat search (k_flat.hip): fp32, bf16 images, and the split tile.
 // Kept in a header so that tools/ubench/gemm_probe.hip can time variants of the same code.
 #pragma once
 
@@ -6,6 +6,7 @@
 
 #include <cmath>
 #include <cstdint>
+#include <type_traits>
 
 #include "vg_device.hpp"
 
@@ -635,8 +636,29 @@ __device__ __forceinline__ int big_max3_i32(int a, int b, int c)
     return r;
 }
 
-template <bool DOT, int NB, int PROBE = 0>
-__global__ __launch_bounds__(kBigThreads) void flat_gemm_bf16_big_kernel(
+// (hi, lo) bfloat16 halves of two floats, a in the low half of each word: hi = round-to-nearest-even (v_cvt_pk_bf16_f32), lo = the
+// same of the remainder a - hi, which fp32 holds exactly.  The subtractions stay scalar: packed fp32 VALU is no gain beside MFMAs.
+typedef __bf16 vg_bf16x2 __attribute__((ext_vector_type(2)));
+typedef float vg_f32x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ void split2_bf16(float a, float b, uint32_t &hi, uint32_t &lo)
+{
+    hi = __builtin_bit_cast(uint32_t, __builtin_convertvector(vg_f32x2{a, b}, vg_bf16x2));
+    const float ra = a - __uint_as_float(hi << 16), rb = b - __uint_as_float(hi & 0xFFFF0000u);
+    lo = __builtin_bit_cast(uint32_t, __builtin_convertvector(vg_f32x2{ra, rb}, vg_bf16x2));
+}
+
+// The persistent tile's body.  SPLIT = false: both operands are bfloat16 images (flat_gemm_bf16_big_kernel).  SPLIT = true
+// (flat_gemm_split_big_kernel): fp32 nomination as three bfloat16 products, q.x ~ q_hi.x_hi + q_lo.x_hi + q_hi.x_lo with fp32
+// accumulation.  `base` is the fp32 rows themselves, `queries` the image of flat_split_queries_kernel, `dim` the fp32 row length:
+// a K step is still 128 bytes of a row in both tiles — fills, swizzle, buffers, waits, starting values, sign test and appends are
+// shared — but it is 32 elements = two operand groups of 16 k, each multiplied in two PHASES (query blocks 0-1, then 2-3) of
+// 2 x 2 x 3 matrix instructions, so that the step keeps its four-part rotated loop.  For group j lane (r, h) reads the query
+// granules 2j + h (hi) and 4 + 2j + h (lo) and the row granules 4j + 2h, 4j + 2h + 1 (its 8 floats), which it splits in registers
+// (split2_bf16) in front of the group's first phase, between that phase's matrix instructions.  All four granule indices are
+// constant over the 16 lanes of a ds_read_b128 pass, so slot = granule ^ ((R >> 1) & 7) visits 16 different 16-byte bank groups
+// as in the bf16 tile: no bank conflicts.  The error of the three-product sum: see split_gemm_eps (k_flat.hip).
+template <bool DOT, int NB, int PROBE, bool SPLIT>
+__device__ __forceinline__ void flat_gemm_big_body(
     const float *__restrict__ queries, int64_t nq, const float *__restrict__ base, int64_t n, int dim /* 4-byte words per row */,
     const float *__restrict__ norms, const float *__restrict__ thr, int thr_stride, int thr_off, int *__restrict__ counts,
     uint64_t *__restrict__ cand, int cap, const uint8_t *__restrict__ mask, int64_t mask_stride,
@@ -751,7 +773,11 @@ __global__ __launch_bounds__(kBigThreads) void flat_gemm_bf16_big_kernel(
     const int h = lane >> 5, f = (lane >> 1) & 7;
     int lpart[4];  // floats: this lane's row within a 32-row block + its swizzled granule of group j
 #pragma unroll
-    for (int j = 0; j < 4; j++) lpart[j] = (lane & 31) * kGemmBK + ((2 * j + h) ^ f) * 4;
+    for (int j = 0; j < 4; j++) {
+        // (SPLIT: 0, 1 = the query image's hi granule of group 0, 1; 2, 3 = the rows' first granule of group 0, 1)
+        const int gran = !SPLIT ? 2 * j + h : j < 2 ? 2 * j + h : 4 * (j - 2) + 2 * h;
+        lpart[j] = (lane & 31) * kGemmBK + (gran ^ f) * 4;
+    }
     const int a_wave = wr * 128 * kGemmBK, b_wave = wc * 64 * kGemmBK;  // wave-uniform
 
     // Per tile: lane l keeps the thresholds of the wave's query rows l and 64 + l and the norm of its row column l, loaded a
@@ -934,22 +960,92 @@ __global__ __launch_bounds__(kBigThreads) void flat_gemm_bf16_big_kernel(
         if (++tiles_done % kFlushEvery == 0) flush_parked();
     };
 
-    float4 fa[2][4], fb[2][2];  // [set][block]: operand granules of one group (16 k) — the group being multiplied / the next one
-    auto read_group = [&](const float *As, const float *Bs, int j, int set) {
-        const float *pa = As + a_wave + lpart[j], *pb = Bs + b_wave + lpart[j];
+    // The four parts of a K step, part p multiplied from register set p & 1 while part p + 1 is read into the other.
+    // bf16: part = operand group p (16 k); fa[set][block], fb[set][block] = the group's granules.
+    // SPLIT: part = phase p of group p >> 1 (query blocks 2 (p & 1), + 1); fa[set][2 b + (0: hi, 1: lo)] = the phase's query
+    // granules; fb[block][0 / 1] = the row granules (8 floats per block) of the group to split NEXT — read with the group's odd
+    // phase one part ahead, split into bc[block][0: hi, 1: lo] by the group's even phase.
+    float4 fa[2][4], fb[2][2];
+    uint4 bc[2][2];
+    auto read_part = [&](const float *As, const float *Bs, auto P) {
+        constexpr int p = decltype(P)::value, set = p & 1;
+        if constexpr (!SPLIT) {
+            const float *pa = As + a_wave + lpart[p], *pb = Bs + b_wave + lpart[p];
 #pragma unroll
-        for (int i = 0; i < 4; i++) fa[set][i] = *reinterpret_cast<const float4 *>(pa + i * 32 * kGemmBK);
+            for (int i = 0; i < 4; i++) fa[set][i] = *reinterpret_cast<const float4 *>(pa + i * 32 * kGemmBK);
 #pragma unroll
-        for (int i = 0; i < 2; i++) fb[set][i] = *reinterpret_cast<const float4 *>(pb + i * 32 * kGemmBK);
+            for (int i = 0; i < 2; i++) fb[set][i] = *reinterpret_cast<const float4 *>(pb + i * 32 * kGemmBK);
+        } else {
+            // (lo granule = hi granule + 4, the row's second granule = its first + 1: slots ^ 4 and ^ 1, floats ^ 16 and ^ 4)
+            const int oa = a_wave + lpart[p >> 1] + 2 * (p & 1) * 32 * kGemmBK;
+#pragma unroll
+            for (int b = 0; b < 2; b++) {
+                fa[set][2 * b] = *reinterpret_cast<const float4 *>(As + oa + b * 32 * kGemmBK);
+                fa[set][2 * b + 1] = *reinterpret_cast<const float4 *>(As + ((oa + b * 32 * kGemmBK) ^ 16));
+            }
+            if constexpr ((p & 1) == 0) {
+                const int ob = b_wave + lpart[2 + (p >> 1)];
+#pragma unroll
+                for (int b = 0; b < 2; b++) {
+                    fb[b][0] = *reinterpret_cast<const float4 *>(Bs + ob + b * 32 * kGemmBK);
+                    fb[b][1] = *reinterpret_cast<const float4 *>(Bs + ((ob + b * 32 * kGemmBK) ^ 4));
+                }
+            }
+        }
     };
-    auto mfma_group = [&](int set) {
+    auto mfma_part = [&](auto P) {
+        constexpr int p = decltype(P)::value, set = p & 1;
+        if constexpr (!SPLIT) {
 #pragma unroll
-        for (int i = 0; i < 4; i++)
+            for (int i = 0; i < 4; i++)
 #pragma unroll
-            for (int j = 0; j < 2; j++)
-                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(vg_bf16x8, fa[set][i]),
-                                                                   __builtin_bit_cast(vg_bf16x8, fb[set][j]), acc[i][j], 0, 0, 0);
+                for (int j = 0; j < 2; j++)
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(vg_bf16x8, fa[set][i]),
+                                                                       __builtin_bit_cast(vg_bf16x8, fb[set][j]), acc[i][j], 0, 0, 0);
+        } else {
+            constexpr int i0 = 2 * (p & 1), even = (p & 1) == 0;
+            // word w (two elements) of row block b: the raw floats, and where its halves go
+            auto raw = [&](int b, int w) { return w == 0 ? make_float2(fb[b][0].x, fb[b][0].y) : w == 1 ? make_float2(fb[b][0].z, fb[b][0].w) :
+                                                  w == 2 ? make_float2(fb[b][1].x, fb[b][1].y) : make_float2(fb[b][1].z, fb[b][1].w); };
+            auto put = [](uint4 &v, int w, uint32_t x) { (w == 0 ? v.x : w == 1 ? v.y : w == 2 ? v.z : v.w) = x; };
+            auto get = [](const uint4 &v, int w) { return w == 0 ? v.x : w == 1 ? v.y : w == 2 ? v.z : v.w; };
+            if constexpr (even) {  // the rows' hi halves: 8 v_cvt_pk_bf16_f32 in front of the first matrix instruction
+#pragma unroll
+                for (int b = 0; b < 2; b++)
+#pragma unroll
+                    for (int w = 0; w < 4; w++)
+                        put(bc[b][0], w, __builtin_bit_cast(uint32_t, __builtin_convertvector(vg_f32x2{raw(b, w).x, raw(b, w).y}, vg_bf16x2)));
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            // Product by product over the four accumulators (no matrix instruction waits for the one before it): q_hi.x_hi and
+            // q_lo.x_hi first, which need only the rows' hi halves — the lo halves (x - hi, rounded: 5 instructions per word) are
+            // computed BETWEEN those eight, one word behind each, the order pinned: bunched in front, the conversions of both
+            // waves of a SIMD (in step at the barrier) leave the matrix pipe empty; left to the scheduler they stay bunched.
+#pragma unroll
+            for (int pr = 0; pr < 3; pr++)
+#pragma unroll
+                for (int b = 0; b < 2; b++)
+#pragma unroll
+                    for (int j = 0; j < 2; j++) {
+                        acc[i0 + b][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
+                            __builtin_bit_cast(vg_bf16x8, fa[set][2 * b + (pr == 1 ? 1 : 0)]),
+                            __builtin_bit_cast(vg_bf16x8, bc[j][pr == 2 ? 1 : 0]), acc[i0 + b][j], 0, 0, 0);
+                        if constexpr (even) {
+                            if (pr < 2) {
+                                const int u = pr * 4 + b * 2 + j, rb = u >> 2, w = u & 3;
+                                const uint32_t hi = get(bc[rb][0], w);
+                                const float ra = raw(rb, w).x - __uint_as_float(hi << 16), rc = raw(rb, w).y - __uint_as_float(hi & 0xFFFF0000u);
+                                put(bc[rb][1], w, __builtin_bit_cast(uint32_t, __builtin_convertvector(vg_f32x2{ra, rc}, vg_bf16x2)));
+                                __builtin_amdgcn_sched_barrier(0);
+                            }
+                        }
+                    }
+        }
     };
+    using P0 = std::integral_constant<int, 0>;
+    using P1 = std::integral_constant<int, 1>;
+    using P2 = std::integral_constant<int, 2>;
+    using P3 = std::integral_constant<int, 3>;
 
     // prologue: the first step's tiles (NB = 3: and the second step's row tile) in flight, the first tile's starting values
     // computed under them, then published
@@ -966,7 +1062,7 @@ __global__ __launch_bounds__(kBigThreads) void flat_gemm_bf16_big_kernel(
     asm volatile("" ::: "memory");
     int ra = 0, rb = 0;  // buffers the current step is read from
     __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): no scalar load pending at the loop's entry (see the wait inside it)
-    read_group(gemm_lds, gemm_lds + 2 * kBigTile, 0, 0);
+    read_part(gemm_lds, gemm_lds + 2 * kBigTile, P0{});
     // Step g: the four operand groups of the step's tiles, group j+1 read from LDS while group j is multiplied; the fills of the
     // NEXT step's tiles — query tile g+1, row tile g+NB-1, into the buffers the barrier at the end of step g-1 freed — go out
     // behind the first two groups' matrix instructions (an LDS-DMA piece costs the issuing wave ~60 cycles: eight of them right
@@ -987,20 +1083,20 @@ __global__ __launch_bounds__(kBigThreads) void flat_gemm_bf16_big_kernel(
             if (n_pos.bt >= total) n_pos = c_pos;  // (after the last tile: its own values once more, 8 idle matrix instructions)
             tile_loads(n_pos);
         }
-        if (!(PROBE & 16)) read_group(As, Bs, 1, 1);
+        if (!(PROBE & 16)) read_part(As, Bs, P1{});
         __builtin_amdgcn_sched_barrier(0);
-        mfma_group(0);
+        mfma_part(P0{});
         __builtin_amdgcn_sched_barrier(0);
         if (g + 1 < S && !(PROBE & 2)) stage_a();
         if (g + NB - 1 < S && !(PROBE & 2) && (PROBE & 512)) stage_b();  // (stage probe: the row tile's fill one group earlier)
-        if (!(PROBE & 16)) read_group(As, Bs, 2, 0);
+        if (!(PROBE & 16)) read_part(As, Bs, P2{});
         __builtin_amdgcn_sched_barrier(0);
-        mfma_group(1);
+        mfma_part(P1{});
         __builtin_amdgcn_sched_barrier(0);
         if (g + NB - 1 < S && !(PROBE & 2) && !(PROBE & 512)) stage_b();
-        if (!(PROBE & 16)) read_group(As, Bs, 3, 1);
+        if (!(PROBE & 16)) read_part(As, Bs, P3{});
         __builtin_amdgcn_sched_barrier(0);
-        mfma_group(0);
+        mfma_part(P2{});
         __builtin_amdgcn_sched_barrier(0);
         ra ^= 1;
         rb = rb + 1 == NB ? 0 : rb + 1;
@@ -1015,9 +1111,9 @@ __global__ __launch_bounds__(kBigThreads) void flat_gemm_bf16_big_kernel(
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         if (!(PROBE & 8)) __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
-        if (!(PROBE & 16)) read_group(gemm_lds + ra * kBigTile, gemm_lds + (2 + rb) * kBigTile, 0, 0);
+        if (!(PROBE & 16)) read_part(gemm_lds + ra * kBigTile, gemm_lds + (2 + rb) * kBigTile, P0{});
         __builtin_amdgcn_sched_barrier(0);
-        mfma_group(1);  // group 3 of step g, from registers
+        mfma_part(P3{});  // part 3 of step g, from registers
         __builtin_amdgcn_sched_barrier(0);
         if (last) {
             if (!(PROBE & 1)) {
@@ -1047,6 +1143,26 @@ __global__ __launch_bounds__(kBigThreads) void flat_gemm_bf16_big_kernel(
     }
     flush_parked();
     if ((PROBE & 32768) && lane == 0) atomicAdd(&counts[nq * count_stride], flushes);  // (stage probe: how often a wave flushed, counts[nq])
+}
+
+template <bool DOT, int NB, int PROBE = 0>
+__global__ __launch_bounds__(kBigThreads) void flat_gemm_bf16_big_kernel(
+    const float *__restrict__ queries, int64_t nq, const float *__restrict__ base, int64_t n, int dim, const float *__restrict__ norms,
+    const float *__restrict__ thr, int thr_stride, int thr_off, int *__restrict__ counts, uint64_t *__restrict__ cand, int cap,
+    const uint8_t *__restrict__ mask, int64_t mask_stride, int count_stride)
+{
+    flat_gemm_big_body<DOT, NB, PROBE, false>(queries, nq, base, n, dim, norms, thr, thr_stride, thr_off, counts, cand, cap, mask,
+                                              mask_stride, count_stride);
+}
+// fp32 rows, split into bfloat16 hi + lo at operand-read time: `queries` = flat_split_queries_kernel's image, dim % 32 == 0
+template <bool DOT, int NB, int PROBE = 0>
+__global__ __launch_bounds__(kBigThreads) void flat_gemm_split_big_kernel(
+    const float *__restrict__ queries, int64_t nq, const float *__restrict__ base, int64_t n, int dim, const float *__restrict__ norms,
+    const float *__restrict__ thr, int thr_stride, int thr_off, int *__restrict__ counts, uint64_t *__restrict__ cand, int cap,
+    const uint8_t *__restrict__ mask, int64_t mask_stride, int count_stride)
+{
+    flat_gemm_big_body<DOT, NB, PROBE, true>(queries, nq, base, n, dim, norms, thr, thr_stride, thr_off, counts, cand, cap, mask,
+                                             mask_stride, count_stride);
 }
 
 // ---- 5..64 queries: the same pipeline with a 32 x 128 or 64 x 128 tile ------------------------------

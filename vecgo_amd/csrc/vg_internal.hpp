@@ -98,6 +98,7 @@ enum Hook {
     kHookFlatRescoreSample,   // VG_FLAT_RESCORE_SAMPLE  flat search: the main GEMM multiplies the sampled row tiles again (no append from the sample)
     kHookPthrForceHist,       // VG_PTHR_FORCE_HIST      vg_search_flat_probed_threshold without rerank: the top-max_results-by-histogram form, then the filter
     kHookWalkSmallScratch,    // VG_WALK_SMALL_SCRATCH   a search walk's batch goes in launches of at most 5 queries (WalkChunks, vg_search.hpp): vg_search_hnsw / _pq / _filtered / _predicate, vg_search_vamana and its kin, vg_search_vamana_fresh
+    kHookFlatNoSplit,         // VG_FLAT_NO_SPLIT        vg_search_flat above 128 queries: the fp32 MFMA GEMM, not the split tile (three bf16 products)
     kHookCount
 };
 bool hook(Hook h);
@@ -199,6 +200,8 @@ inline bool aligned16(const T *...p)
 enum Align { kStage16, kAnyAlign };
 // counts the device buffers staged so: read and cleared by vg_profile_read("staged_device_buffers")
 void note_staged_device_buffer();
+// launches of the flat search's split tile: read and cleared by vg_profile_read("flat_split_launches")
+void note_flat_split_launch();
 
 // Read-only input that may live on the host: staged into HBM for the call.
 template <typename T>
