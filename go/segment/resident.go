@@ -544,6 +544,14 @@ func (r *Resident) EnablePQNomination(on bool) error {
 	return hipctx.Err(int32(C.vg_index_enable_pq_nomination(r.h, v, nil)))
 }
 
+// FlatRetried: how many queries of the fp32 flat search, since the rows were attached, the one-product bfloat16 screen left
+// open and the three-product pass nominated again (a host whose neighbours lie closer than ~2^-7 relative sees it grow).
+func (r *Resident) FlatRetried() (int64, error) {
+	var n C.int64_t
+	st := C.vg_index_flat_retried(r.h, &n, nil)
+	return int64(n), hipctx.Err(int32(st))
+}
+
 // SearchRaBitQ: exhaustive scan of the RaBitQ codes (rq.Distance per row).
 func (r *Resident) SearchRaBitQ(queries []float32, nq, k int) ([]uint32, []float32, error) {
 	ids, sc := r.out(nq, k)

@@ -105,7 +105,7 @@ extern "C" {
  *  threshold search over coded / partitioned flat segments: vg_search_flat_probed_threshold and
  *  vg_segment_search_threshold, found by symbol lookup.  Likewise the streaming Vamana index: vg_vamana_insert and
  *  vg_search_vamana_fresh, found by symbol lookup; and its delete path, vg_vamana_consolidate (with its caller-allocated
- *  vg_vamana_consolidate_stats), the same way. */
+ *  vg_vamana_consolidate_stats), the same way.  Likewise vg_index_flat_retried, found by symbol lookup. */
 #define VG_ABI_MINOR 13
 #define VG_INVALID_ID 0xFFFFFFFFu
 #define VG_STREAM_LEGACY ((void *)1) /* == hipStreamLegacy */
@@ -160,7 +160,7 @@ int32_t vg_ctx_device_info(vg_ctx *ctx, char *arch, int32_t arch_len, int32_t *c
  * per-query FilterGateStats.SearchTimeNanos, searcher/searcher.go:114-137).  While enabled,
  * every launch of the named hot kernels is bracketed by an event pair.  vg_profile_read
  * synchronises, then returns the number of launches and their summed duration since the last
- * read for `kernel` ("flat_gemm", "pq_adc_scan", "rabitq_scan", "flat_select", "topk_merge",
+ * read for `kernel` ("flat_gemm", "flat_retry", "pq_adc_scan", "rabitq_scan", "flat_select", "topk_merge",
  * "hnsw_search", "vamana_search"), and clears those records.  The name "staged_device_buffers" is a counter, not a
  * kernel: how many misaligned DEVICE buffers the process passed through a scratch block since the last read ("Alignment"
  * above), profiling enabled or not; total_ms is 0.  Likewise "flat_split_launches": launches of vg_search_flat's split
@@ -660,7 +660,11 @@ int32_t vg_score_candidates(vg_index *idx, const float *queries, int64_t nq,
  * (distance.Provider, distance/distance.go:91-106).  k <= 512: up to k = 48 the 64 best GEMM
  * scores per query are re-scored and proved; above that every row under the query's threshold is
  * (the threshold is taken deeper in the sample for k > 64, ~3k rows pass it, sorted in LDS); batches
- * of up to 4 queries with k <= 64 take the exhaustive exact scan instead. */
+ * of up to 4 queries with k <= 64 take the exhaustive exact scan instead.
+ * Above 128 queries (dim % 32 == 0, no bf16 filter) the candidates come from bfloat16 matrix products on the fp32 rows: up
+ * to k = 16 first a SCREEN, one product of the operands' rounded halves with the bfloat16 rounding in the proof's margin, and
+ * for the queries whose proof fails under that margin three products (fp32-grade margin) over their 256-query tiles only;
+ * above k = 16 the three products for every query; then the exhaustive kernel as above.  vg_index_flat_retried counts the queries the screen left open. */
 int32_t vg_search_flat(vg_index *idx, const float *queries, int64_t nq, int32_t k, uint32_t *ids,
                        float *scores, void *stream);
 /* Optional bfloat16 FILTER for vg_search_flat (no reference counterpart; the results stay the reference's).  on != 0:
@@ -700,6 +704,11 @@ int32_t vg_search_flat_threshold(vg_index *idx, const float *queries, int64_t nq
  * scanned (and every query under the test hook VG_FLAT_FORCE_EXACT).  Batches of up to 8 queries are scanned
  * from the start, like vg_search_flat's small batches, and are not counted in the second. */
 int32_t vg_index_flat_stats(vg_index *idx, int64_t *queries, int64_t *exhaustive, void *stream);
+
+/* one more count of vg_search_flat since vg_index_set_vectors: the queries whose one-product screen (see vg_search_flat) could
+ * not prove their answer and which the three-product pass nominated again.  A retried query is not an exhaustive one: it counts
+ * in vg_index_flat_stats' second value only if its second proof fails too.  Synchronises the stream. */
+int32_t vg_index_flat_retried(vg_index *idx, int64_t *retried, void *stream);
 
 /* exhaustive scan of the RaBitQ codes: RaBitQuantizer.Distance (rabitq.go:119-176) for every
  * row, best k by (Score, RowID).  The reference only scores RaBitQ codes node by node inside the

@@ -1582,6 +1582,13 @@ class Index:
         check(self._lib.vg_index_flat_stats(self._h, C.byref(q), C.byref(e), _stream_ptr(stream)))
         return q.value, e.value
 
+    def flat_retried(self, stream=None):
+        """vg_index_flat_retried: queries of search_flat since set_vectors that the one-product screen could not prove and the
+        three-product pass nominated again."""
+        r = C.c_int64(0)
+        check(self._lib.vg_index_flat_retried(self._h, C.byref(r), _stream_ptr(stream)))
+        return r.value
+
     def search_pq_adc(self, queries, k, out=None, stream=None):
         """flat.Segment.Search PQ branch (flat/segment.go:476-483,678-689,714-721)."""
         return self._search(self._lib.vg_search_pq_adc, queries, k, out=out, stream=stream)

@@ -1,6 +1,7 @@
 // k_flat.hip — exact brute-force search (flat/segment.go:691-721, hnsw.go:2021-2101):
 //   1. scores[q][n] = ||x_n||^2 - 2 q.x_n  (L2)  or  -q.x_n  (Dot)   fp32 MFMA GEMM (above 128 queries: the split tile,
-//      three bf16 products on the fp32 rows — gemm_runs_split)
+//      three bf16 products on the fp32 rows — gemm_runs_split; up to k = 16 behind a one-product screen whose proof, where it
+//      holds, ends the query at step 3 — gemm_runs_screen)
 //   2. per query: the kc smallest scores                              streaming select
 //   3. exact re-scoring of those kc rows in the reference's summation order, top-k by
 //      (Score, RowID), and a proof that no other row can belong to the top-k (k > 48: every row whose
@@ -50,6 +51,11 @@ struct GemmArgs {
     // MODE 2: the split tile (flat_gemm_split_big_kernel) — `queries` is flat_split_queries_kernel's image of the chunk, `base` the
     // fp32 rows.  Set only where gemm_runs_split() says so (vg_search_flat's fused path).
     bool split = false;
+    // with `split`: the screen (flat_gemm_screen_big_kernel), the product of the hi halves alone — where gemm_runs_screen() says so
+    bool screen = false;
+    // with `split`, not `screen`: the retry behind a screen.  Bit tm of the word = query tile tm holds a query to retry; the others
+    // are not multiplied.  flat_retry_prepare_kernel has written it and zeroed the counters of the queries to retry.
+    const uint32_t *tile_active = nullptr;
 };
 constexpr int kCountLine = 32;
 // Whether a MODE 2 launch of vg_search_flat's fused path runs the split tile: fp32 rows nominated by three bfloat16 products on the
@@ -87,6 +93,22 @@ static float split_gemm_eps(bool dot, int dim)
     const float m = static_cast<float>(3 * dim + 16) * 5.9604645e-8f;
     return dot ? 1.5001f * 1.52587890625e-5f + 2.52f * m : 3.0002f * 1.52587890625e-5f + 4.03f * m;
 }
+// The screen's (flat_gemm_screen_big_kernel, where gemm_runs_screen() says so) |score - true score| as a multiple of
+// |q|^2 + max |x|^2.  With u = 2^-8 both operands are rounded to bfloat16, q_hi = q (1 + d), x_hi = x (1 + e), |d|, |e| <= u: a product is off by at most (2 u + u^2) |q_i x_i| = (2^-7 + 2^-16) |q_i x_i|,
+// the dot product by (2^-7 + 2^-16) |q||x| <= (2^-8 + 2^-17) (|q|^2 + |x|^2); an L2 score is |x|^2 - 2 q.x, twice that — the
+// bfloat16 filter's bound (vg_search_flat).                                                                          [operands]
+// The accumulation is the split tile's with a third of the products: the same starting value s (|s| <= 2.002 for Dot, 1.501 for
+// L2, by flat_thr_cap_kernel's cap), m = dim + 16 roundings (8 matrix-unit additions of the starting value, dim products, the
+// key's fma; the rest is room), each at most 2^-24 (|s| + S), S = sum |products| <= (1 + u)^2 |q||x| <= 0.51 (|q|^2 + |x|^2):
+//     Dot:  2^-8 + 2^-17 + 2.52 (dim + 16) 2^-24          L2:  2^-7 + 2^-16 + 4.03 (dim + 16) 2^-24                [accumulation]
+// At dim 768 the L2 margin is 7.828e-3 + 1.88e-4 = 8.02e-3: the filter's "x 1.02" (7.97e-3, which has the 128 x 128 tile's
+// zero-started sum to cover) is NOT enough for this tile from dim ~ 570 on, so the accumulation term is added as it is.
+// tests/test_flat_screen_bound.py models the sum.  Values bfloat16 cannot hold: as for the split tile (split_gemm_eps).
+static float screen_gemm_eps(bool dot, int dim)
+{
+    const float m = static_cast<float>(dim + 16) * 5.9604645e-8f;
+    return dot ? 0.00390625f + 7.62939453125e-6f + 2.52f * m : 0.0078125f + 1.52587890625e-5f + 4.03f * m;
+}
 // Whether launch_gemm_t runs a kernel that honours GemmArgs::skip_stride for these arguments: the fp32 128 x 128 tiles (LDS-DMA and
 // register-staged), whose MODE 1 and MODE 2 are one body with one accumulation order.  Not the 32-row tiles (up to 96 queries), not
 // a bf16 kernel, not the split tile (`split`: gemm_runs_split's answer).  The ONE place that decides: the caller appends the sampled rows itself exactly where this is true (a row
@@ -108,23 +130,27 @@ static int32_t launch_gemm_t(bool dma, unsigned blocks, hipStream_t st, const Ge
     const int skip = MODE == 2 ? a.skip_stride : 0;
     VG_CHECK(skip == 0 || (skip > 1 && gemm_skips_sample(dma, a.nq, bf16, a.split)), VG_ERR_INVALID_ARG, "launch_gemm: skip_stride on a kernel without it");
     // the persistent 256 x 256 tile (bf16 images, or the split tile on the fp32 rows): one workgroup per CU, wide counters
-    auto launch_big = [&](auto kern, size_t lds) -> int32_t {
+    // (extra: the split tile's tile_active.  A retry's counters are flat_retry_prepare_kernel's to zero: those of the queries it
+    // retries, the others keep what the screen counted)
+    auto launch_big = [&](auto kern, size_t lds, auto... extra) -> int32_t {
         VG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
                                    static_cast<int>(lds)));
         const int64_t mt = (a.nq + kBigBM - 1) / kBigBM, nt = (a.n + kBigBN - 1) / kBigBN;
         const int64_t slots = mt * ((nt + 7) / 8) * 8, per_cu = std::max(a.cus / 8, 1) * 8;  // (one workgroup per CU: LDS)
-        if (a.counts_wide) VG_HIP(hipMemsetAsync(a.counts_wide, 0, sizeof(int) * static_cast<size_t>(a.nq) * kCountLine, st));
+        if (a.counts_wide && !a.tile_active) VG_HIP(hipMemsetAsync(a.counts_wide, 0, sizeof(int) * static_cast<size_t>(a.nq) * kCountLine, st));
         VG_LAUNCH(kern, dim3(static_cast<unsigned>(std::min(slots, per_cu))), dim3(kBigThreads), lds, st, a.queries, a.nq,
                   a.base, a.n, a.dim, a.norms, a.thr, a.thr_stride, a.thr_off, a.counts_wide ? a.counts_wide : a.counts, a.cand, a.cap, a.mask,
-                  a.mask_stride, a.counts_wide ? kCountLine : 1);
+                  a.mask_stride, a.counts_wide ? kCountLine : 1, extra...);
         if (a.counts_wide)
             VG_LAUNCH(counts_narrow_kernel, dim3(static_cast<unsigned>((a.nq + 255) / 256)), dim3(256), 0, st, a.counts_wide, a.nq, a.counts);
         return VG_OK;
     };
     if (MODE == 2 && a.split) {
         VG_CHECK(!bf16 && gemm_runs_split(true, false, dma, a.nq, a.dim, a.cap, a.thr_stride), VG_ERR_INVALID_ARG, "launch_gemm: split tile on a call without it");
+        if (a.screen) return launch_big(flat_gemm_screen_big_kernel<DOT, 3>, big_lds_bytes<3>());
+        VG_CHECK(!a.tile_active || (a.nq <= 32 * kBigBM && a.counts_wide), VG_ERR_INVALID_ARG, "launch_gemm: tile_active is one word, with wide counters");
         note_flat_split_launch();
-        return launch_big(flat_gemm_split_big_kernel<DOT, 3>, big_lds_bytes<3>());
+        return launch_big(flat_gemm_split_big_kernel<DOT, 3>, big_lds_bytes<3>(), a.tile_active);
     }
     if (skip) {  // the grid of the tiles that are left, in the same XCD-aware order
         const int64_t mt = (a.nq + kGemmBM - 1) / kGemmBM, nt = (a.n + kGemmBN - 1) / kGemmBN;
@@ -276,6 +302,41 @@ __global__ __launch_bounds__(256) void flat_todo_kernel(const int *__restrict__ 
         if (all || flags[i] != 0) todo[1 + at++] = i;
 }
 
+// Between the screen's proofs and the split tile's retry (vg_search_flat): a query whose flag is set is retried — its counters
+// (narrow and wide) go back to zero, its threshold stays, its 256-query tile is marked in the word *tile_active — and every other
+// query of the chunk gets the threshold -Inf, for which the tile's clamp appends nothing.  all: every query counts as flagged
+// (test hook kHookFlatScreenFail).  stats[2] += the queries retried.  ONE workgroup, a round per query tile (at most 32: the
+// word is written whole, no memset and no atomics in front of it).
+__global__ __launch_bounds__(kBigBM) void flat_retry_prepare_kernel(int *__restrict__ flags, bool all, int cnt, float *__restrict__ thr,
+                                                                    int thr_stride, int thr_off, int *__restrict__ counts,
+                                                                    int *__restrict__ counts_wide, uint32_t *__restrict__ tile_active,
+                                                                    unsigned long long *__restrict__ stats)
+{
+    uint32_t word = 0;
+    int total = 0;
+    for (int t = 0; t * kBigBM < cnt; t++) {
+        const int q = t * kBigBM + static_cast<int>(threadIdx.x);
+        bool retry = false;
+        if (q < cnt) {
+            retry = all || flags[q] != 0;
+            if (retry) {
+                flags[q] = 1;
+                counts[q] = 0;
+                counts_wide[static_cast<int64_t>(q) * kCountLine] = 0;
+            } else {
+                thr[static_cast<int64_t>(q) * thr_stride + thr_off] = -INFINITY;
+            }
+        }
+        const int here = __syncthreads_count(retry);
+        word |= here ? 1u << t : 0u;
+        total += here;
+    }
+    if (threadIdx.x == 0) {
+        *tile_active = word;
+        if (total) atomicAdd(&stats[2], static_cast<unsigned long long>(total));
+    }
+}
+
 // The sampled row tiles are scored once.  MODE 1 has left their scores in sc[q][ns] (+Inf for a column past n and for a row the
 // query's filter rejects); MODE 2 of the same 128 x 128 tile would compute the same bits again and compare them with the query's
 // threshold.  So, once the thresholds exist: one workgroup per query walks its sample, appends key(sc, row) for every column with
@@ -341,15 +402,17 @@ __global__ __launch_bounds__(kSampleAppendThreads) void flat_sample_append_kerne
 }
 
 // per query: the kc best keys among the candidates the fused GEMM appended (count <= cap)
+// only (or null: every query): the workgroup of a query with only[q] == 0 returns at once and writes nothing
 __global__ __launch_bounds__(256) void flat_pick_kernel(const uint64_t *__restrict__ cand,
                                                         const int *__restrict__ counts, int cap, int kc,
                                                         uint32_t *__restrict__ cand_ids,
-                                                        float *__restrict__ cand_scores)
+                                                        float *__restrict__ cand_scores, const int *__restrict__ only)
 {
     __shared__ uint64_t lists[4 * 64];
     __shared__ int valid[4];
     __shared__ uint64_t best[64];
     const int64_t q = blockIdx.x;
+    if (only && only[q] == 0) return;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     int c = counts[q];
     if (c > cap) c = cap;
@@ -456,17 +519,20 @@ __global__ __launch_bounds__(kSelThreads) void flat_select_kernel(const float *_
 
 // ---- 3. exact re-score + proof -----------------------------------------------------------------
 // cand_ids/cand_scores: the kc best GEMM scores per query, ascending.  One workgroup per query.
+// only (or null: every query; may be `fallback` itself): the workgroup of a query with only[q] == 0 returns at once and writes
+// nothing — the second proof of the queries whose first one failed rewrites their flag and leaves the others' answers alone.
 template <bool DOT>
 __global__ __launch_bounds__(256) void flat_verify_kernel(
     const float *__restrict__ base, int64_t n, int dim, const float *__restrict__ queries,
     const float *__restrict__ norms_max /* [1] */, const uint32_t *__restrict__ cand_ids,
     const float *__restrict__ cand_scores, int kc, int k, uint32_t *__restrict__ ids,
-    float *__restrict__ scores, int *__restrict__ fallback, const float *__restrict__ thr, int thr_stride,
-    int thr_off, const int *__restrict__ counts, int cap, float eps_extra)
+    float *__restrict__ scores, int *fallback, const float *__restrict__ thr, int thr_stride,
+    int thr_off, const int *__restrict__ counts, int cap, float eps_extra, const int *only)
 {
     __shared__ uint64_t keys[64];
     const Sub16 sub = Sub16::make(threadIdx.x);
     const int64_t q = blockIdx.x;
+    if (only && only[q] == 0) return;
     const float *qv = queries + q * dim;
     for (int c = threadIdx.x >> 4; c < kc; c += 16) {
         const uint32_t id = cand_ids[q * kc + c];
@@ -698,6 +764,21 @@ __global__ __launch_bounds__(256) void flat_exact_kernel(const float *__restrict
 constexpr int kScanQB = 8;        // queries one pass can carry
 constexpr int kGemmMaxK = 48;     // largest k the 64-candidate nomination + proof serves (above: flat_verify_all_kernel)
 constexpr int kFlatMaxK = 512;    // candidates appended per query stay well under the 4096-key buffer (3k expected)
+// Whether a chunk that runs the split tile (gemm_runs_split's answer) is screened first: one product, q_hi.x_hi, over every pair,
+// its proof with the wide margin screen_gemm_eps, and the three-product tile only for the 256-query tiles that hold a query whose
+// proof failed.  The ONE place that decides.  The cascade serves the proof from 64 picked candidates (k <= kGemmMaxK: the other
+// verify kernels keep the split tile alone), but the screen's proof wants the k-th neighbour further below the 64th than its
+// margin, ~2^-7 (|q|^2 + max |x|^2), and on unclustered rows that holds only while k is a small part of the 64: standard-normal
+// rows (5000 x 32 .. 768, tests/test_gpu_flat_screen.py's data, on the GPU and in a numpy model of the proof) leave no query
+// open up to k = 24, 12 % of them at k = 32 (dim 768) and 13 % (dim 32) to all of them (dim 768) at k = 48 — where the screen
+// is a pass for nothing in front of the three-product pass.  So: up to kScreenMaxK = 16 results, a quarter of the candidates.
+// (test hooks: kHookFlatNoScreen — no screen, the split tile for every tile; kHookFlatNoSplit turns both off;
+// kHookFlatScreenFail, which fails every screen proof, also runs the screen up to kGemmMaxK so that the retry is tested there)
+constexpr int kScreenMaxK = 16;
+static bool gemm_runs_screen(bool split, int k)
+{
+    return split && !hook(kHookFlatNoScreen) && k <= (hook(kHookFlatScreenFail) ? kGemmMaxK : kScreenMaxK);
+}
 constexpr int kScanMaxBatch = 4;  // ... and the batch size up to which the scan beats the 32-query GEMM tile
 template <bool DOT>
 __global__ __launch_bounds__(256) void flat_scan_mq_kernel(const float *__restrict__ base, int64_t n, int dim,
@@ -934,6 +1015,7 @@ int32_t vg::flat_search_masked(vg_index *idx, const float *queries, int64_t nq, 
         const bool may_split = vg::gemm_runs_split(fused, bf16, true, qc, dim, cap, sel_k);
         const int i_qbf = ar.add(bf16 ? sizeof(uint16_t) * static_cast<size_t>(qc) * bdim : may_split ? sizeof(uint32_t) * static_cast<size_t>(qc) * dim : 0);
         const int i_cwide = ar.add(bf16 || may_split ? sizeof(int) * static_cast<size_t>(qc) * vg::kCountLine : 0);
+        const int i_active = ar.add(may_split ? sizeof(uint32_t) : 0);  // the retry's query tiles (flat_retry_prepare_kernel)
         VG_TRY(ar.commit());
         uint16_t *qbf = ar.get<uint16_t>(i_qbf);
         float *sc = ar.get<float>(i_sc), *thr = ar.get<float>(i_thr);
@@ -944,6 +1026,7 @@ int32_t vg::flat_search_masked(vg_index *idx, const float *queries, int64_t nq, 
         uint32_t *sid = ar.get<uint32_t>(i_sid), *cand_id = ar.get<uint32_t>(i_cand_id), *fid = ar.get<uint32_t>(i_fid);
         int *counts = ar.get<int>(i_counts), *flags = ar.get<int>(i_flags), *todo = ar.get<int>(i_todo);
         int *counts_wide = bf16 || may_split ? ar.get<int>(i_cwide) : nullptr;
+        uint32_t *tile_active = may_split ? ar.get<uint32_t>(i_active) : nullptr;
 
         int *always = flags + qc;  // test hook kHookFlatForceExact: run step 4 for every query
         VG_HIP(hipMemsetAsync(always, vg::hook(vg::kHookFlatForceExact) ? 1 : 0, sizeof(int), st));
@@ -957,7 +1040,9 @@ int32_t vg::flat_search_masked(vg_index *idx, const float *queries, int64_t nq, 
             const bool dma = dim % 4 == 0 && (reinterpret_cast<uintptr_t>(qp) & 15) == 0 &&
                              (reinterpret_cast<uintptr_t>(idx->d_vectors) & 15) == 0 && !vg::hook(vg::kHookFlatNoDma);
             const bool split = vg::gemm_runs_split(fused, bf16, dma, cnt, dim, cap, sel_k);
-            const float eps_extra = split ? vg::split_gemm_eps(dot, dim) : bf16_eps;
+            // ... behind a screen: the hi halves' product and the wide margin first, the split tile for the queries that leaves open
+            const bool screen = vg::gemm_runs_screen(split, k);
+            const float eps_extra = screen ? vg::screen_gemm_eps(dot, dim) : split ? vg::split_gemm_eps(dot, dim) : bf16_eps;
             // operands of the nomination GEMMs
             const float *ga = qp, *gb = idx->d_vectors;
             int gdim = dim;
@@ -998,11 +1083,11 @@ int32_t vg::flat_search_masked(vg_index *idx, const float *queries, int64_t nq, 
                     VG_TRY(vg::launch_gemm<2>(dot, dma, static_cast<unsigned>(mt * ((nt + 7) / 8) * 8), st,
                                               {split ? reinterpret_cast<const float *>(qbf) : ga, cnt, gb, n, gdim, idx->d_norms, nullptr, 1, 0, thr,
                                                sel_k, sel_k - 1, counts, cand, cap, m0, mask_stride, idx->ctx->compute_units,
-                                               bf16 || split ? counts_wide : nullptr, once ? sample_stride : 0, split}, bf16));
+                                               bf16 || split ? counts_wide : nullptr, once ? sample_stride : 0, split, screen}, bf16));
                 }
                 // (c) the kc best appended keys (k > kGemmMaxK: all of them go to the exact re-score below)
                 if (k <= vg::kGemmMaxK)
-                    VG_LAUNCH(vg::flat_pick_kernel, dim3(ucnt), dim3(256), 0, st, cand, counts, cap, kc, cand_id, cand_sc);
+                    VG_LAUNCH(vg::flat_pick_kernel, dim3(ucnt), dim3(256), 0, st, cand, counts, cap, kc, cand_id, cand_sc, nullptr);
             } else {
                 {
                     vg::ProfScope prof(idx->ctx, "flat_gemm", st);
@@ -1034,7 +1119,25 @@ int32_t vg::flat_search_masked(vg_index *idx, const float *queries, int64_t nq, 
                 auto kern = dot ? vg::flat_verify_kernel<true> : vg::flat_verify_kernel<false>;
                 VG_LAUNCH(kern, dim3(ucnt), dim3(256), 0, st, idx->d_vectors, n, dim, qp,
                           idx->d_norm_max, cand_id, cand_sc, kc, k, oid + q0 * k, osc + q0 * k, flags, vthr,
-                          sel_k, sel_k - 1, counts, cap, eps_extra);
+                          sel_k, sel_k - 1, counts, cap, eps_extra, nullptr);
+                // The retry behind a screen.  A query whose proof held is finished; for the others (normally none) the split tile
+                // runs on the 256-query tiles that hold one — launched ALWAYS, once per chunk: with no tile marked every workgroup
+                // returns at once — then the pick and the proof again, for the flagged queries only and with the split tile's margin.
+                // (test hook kHookFlatScreenFail: every screen proof counts as failed)
+                if (screen) {
+                    VG_LAUNCH(vg::flat_retry_prepare_kernel, dim3(1), dim3(vg::kBigBM), 0, st, flags, vg::hook(vg::kHookFlatScreenFail),
+                              static_cast<int>(cnt), thr, sel_k, sel_k - 1, counts, counts_wide, tile_active, idx->d_flat_stats);
+                    {
+                        vg::ProfScope prof(idx->ctx, "flat_retry", st);
+                        VG_TRY(vg::launch_gemm<2>(dot, dma, 0, st,
+                                                  {reinterpret_cast<const float *>(qbf), cnt, gb, n, gdim, idx->d_norms, nullptr, 1, 0, thr, sel_k,
+                                                   sel_k - 1, counts, cand, cap, m0, mask_stride, idx->ctx->compute_units, counts_wide, 0, true,
+                                                   false, tile_active}));
+                    }
+                    VG_LAUNCH(vg::flat_pick_kernel, dim3(ucnt), dim3(256), 0, st, cand, counts, cap, kc, cand_id, cand_sc, flags);
+                    VG_LAUNCH(kern, dim3(ucnt), dim3(256), 0, st, idx->d_vectors, n, dim, qp, idx->d_norm_max, cand_id, cand_sc, kc, k,
+                              oid + q0 * k, osc + q0 * k, flags, vthr, sel_k, sel_k - 1, counts, cap, vg::split_gemm_eps(dot, dim), flags);
+                }
             }
             // step 4 always launches, on the work list the proofs left behind (normally empty)
             VG_LAUNCH(vg::flat_todo_kernel, dim3(1), dim3(256), 0, st, flags, always, static_cast<int>(cnt), todo,
@@ -1208,7 +1311,7 @@ int32_t flat_probe_gemm(vg_index *idx, const float *pair_queries, int64_t pairs,
     }
     // (c) the kc best of them, (d) re-scored exactly, the k best, and the proof against everything not nominated
     // (k > kGemmMaxK: every appended row is re-scored — flat_verify_all / _sort, as in vg_search_flat)
-    if (k <= kGemmMaxK) VG_LAUNCH(flat_pick_kernel, dim3(upairs), dim3(256), 0, st, cand, counts, cap, kc, cand_id, cand_sc);
+    if (k <= kGemmMaxK) VG_LAUNCH(flat_pick_kernel, dim3(upairs), dim3(256), 0, st, cand, counts, cap, kc, cand_id, cand_sc, nullptr);
     if (bf16 && !own_filter) {
         nominated->thr = thr;
         nominated->counts = counts;
@@ -1231,7 +1334,7 @@ int32_t flat_probe_gemm(vg_index *idx, const float *pair_queries, int64_t pairs,
     } else {
         auto kern = dot ? flat_verify_kernel<true> : flat_verify_kernel<false>;
         VG_LAUNCH(kern, dim3(upairs), dim3(256), 0, st, idx->d_vectors, idx->n, dim, queries_f32, idx->d_norm_max,
-                  cand_id, cand_sc, kc, k, pair_ids, pair_scores, fail, thr, sel_k, sel_k - 1, counts, cap, eps_extra);
+                  cand_id, cand_sc, kc, k, pair_ids, pair_scores, fail, thr, sel_k, sel_k - 1, counts, cap, eps_extra, nullptr);
     }
     return VG_OK;
 }
@@ -1310,7 +1413,7 @@ int32_t flat_nominate_bf16(vg_ctx *ctx, const NomImage &img, int64_t n, int dim,
                                ctx->compute_units, reinterpret_cast<int *>(scratch + l.cwide)},
                               true));
     }
-    if (pick) VG_LAUNCH(flat_pick_kernel, dim3(static_cast<unsigned>(cnt)), dim3(256), 0, st, cand, counts, kNomCap, kNomKc, cand_id, cand_sc);
+    if (pick) VG_LAUNCH(flat_pick_kernel, dim3(static_cast<unsigned>(cnt)), dim3(256), 0, st, cand, counts, kNomCap, kNomKc, cand_id, cand_sc, nullptr);
     *cand_keys = cand;
     *cap = kNomCap;
     return VG_OK;
@@ -1453,5 +1556,18 @@ VG_API int32_t vg_index_flat_stats(vg_index *idx, int64_t *queries, int64_t *exh
     VG_HIP(hipStreamSynchronize(st));
     if (queries) *queries = static_cast<int64_t>(h[0]);
     if (exhaustive) *exhaustive = static_cast<int64_t>(h[1]);
+    return VG_OK;
+}
+
+VG_API int32_t vg_index_flat_retried(vg_index *idx, int64_t *retried, void *stream)
+{
+    VG_CHECK(idx && retried, VG_ERR_INVALID_ARG, "vg_index_flat_retried: NULL index or pointer");
+    VG_CHECK(idx->d_flat_stats, VG_ERR_INVALID_ARG, "vg_index_flat_retried: no fp32 vectors attached");
+    VG_HIP(hipSetDevice(idx->ctx->device));
+    hipStream_t st = vg::pick_stream(idx->ctx, stream);
+    unsigned long long h = 0;
+    VG_HIP(hipMemcpyAsync(&h, idx->d_flat_stats + 2, sizeof h, hipMemcpyDeviceToHost, st));
+    VG_HIP(hipStreamSynchronize(st));
+    *retried = static_cast<int64_t>(h);
     return VG_OK;
 }

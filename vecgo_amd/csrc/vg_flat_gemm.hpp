@@ -647,7 +647,7 @@ __device__ __forceinline__ void split2_bf16(float a, float b, uint32_t &hi, uint
     lo = __builtin_bit_cast(uint32_t, __builtin_convertvector(vg_f32x2{ra, rb}, vg_bf16x2));
 }
 
-// The persistent tile's body.  SPLIT = false: both operands are bfloat16 images (flat_gemm_bf16_big_kernel).  SPLIT = true
+// The persistent tile's body.  OPS = kBigImages: both operands are bfloat16 images (flat_gemm_bf16_big_kernel).  OPS = kBigSplit
 // (flat_gemm_split_big_kernel): fp32 nomination as three bfloat16 products, q.x ~ q_hi.x_hi + q_lo.x_hi + q_hi.x_lo with fp32
 // accumulation.  `base` is the fp32 rows themselves, `queries` the image of flat_split_queries_kernel, `dim` the fp32 row length:
 // a K step is still 128 bytes of a row in both tiles — fills, swizzle, buffers, waits, starting values, sign test and appends are
@@ -657,14 +657,24 @@ __device__ __forceinline__ void split2_bf16(float a, float b, uint32_t &hi, uint
 // (split2_bf16) in front of the group's first phase, between that phase's matrix instructions.  All four granule indices are
 // constant over the 16 lanes of a ds_read_b128 pass, so slot = granule ^ ((R >> 1) & 7) visits 16 different 16-byte bank groups
 // as in the bf16 tile: no bank conflicts.  The error of the three-product sum: see split_gemm_eps (k_flat.hip).
-template <bool DOT, int NB, int PROBE, bool SPLIT>
+// OPS = kBigScreen (flat_gemm_screen_big_kernel): the split tile's operands, fills and phases, but ONE product, q_hi.x_hi — a lane
+// converts its 8 floats of a group with the 4 v_cvt_pk_bf16_f32 of the split's hi half and reads only the hi granules of the query
+// image: 2 x 2 matrix instructions per phase.  Its error is the bfloat16 filter's: screen_gemm_eps (k_flat.hip).
+// `tile_active` (or null: every tile): bit tm says whether query tile tm is multiplied at all — step() passes over the slots of
+// the others as it passes over the row-tile holes, and a workgroup that is left with no slot returns before it touches LDS
+// (vg_search_flat's retry of the queries whose screen proof failed).  One word: at most 32 query tiles (the launcher checks).
+enum { kBigImages = 0, kBigSplit = 1, kBigScreen = 2 };
+template <bool DOT, int NB, int PROBE, int OPS>
 __device__ __forceinline__ void flat_gemm_big_body(
     const float *__restrict__ queries, int64_t nq, const float *__restrict__ base, int64_t n, int dim /* 4-byte words per row */,
     const float *__restrict__ norms, const float *__restrict__ thr, int thr_stride, int thr_off, int *__restrict__ counts,
     uint64_t *__restrict__ cand, int cap, const uint8_t *__restrict__ mask, int64_t mask_stride,
-    int count_stride /* ints between two queries' counters: 32 = a 128-byte line each (see launch_gemm_t) */)
+    int count_stride /* ints between two queries' counters: 32 = a 128-byte line each (see launch_gemm_t) */,
+    const uint32_t *__restrict__ tile_active = nullptr)
 {
     static_assert(NB == 2 || NB == 3, "two or three row-tile buffers");
+    constexpr bool SPLIT = OPS != kBigImages;  // fp32 rows converted in registers (three products, or the screen's one)
+    constexpr bool SCREEN = OPS == kBigScreen;
     extern __shared__ float gemm_lds[];
     const int mtiles = static_cast<int>((nq + kBigBM - 1) / kBigBM);
     const int ntiles = static_cast<int>((n + kBigBN - 1) / kBigBN);
@@ -680,6 +690,8 @@ __device__ __forceinline__ void flat_gemm_big_body(
     };
     auto tm_of = [&](const Pos &p) { return p.rem; };
     auto tn_of = [&](const Pos &p) { return p.quo * 8 + xcd; };
+    const uint32_t active = tile_active ? *tile_active : 0xFFFFFFFFu;  // (read once: no scalar load inside the K-step loop)
+    auto hole = [&](const Pos &p) { return tn_of(p) >= ntiles || ((active >> (p.rem & 31)) & 1u) == 0; };
     auto step = [&](Pos &p) {  // this workgroup's next slot that holds a tile (bt >= total: none)
         do {
             p.bt += G;
@@ -689,13 +701,13 @@ __device__ __forceinline__ void flat_gemm_big_body(
                 p.rem -= mtiles;
                 p.quo++;
             }
-        } while (p.bt < total && tn_of(p) >= ntiles);
+        } while (p.bt < total && hole(p));
     };
     Pos pos0;
     pos0.bt = static_cast<int>(blockIdx.x);
     pos0.quo = (pos0.bt >> 3) / mtiles;
     pos0.rem = (pos0.bt >> 3) % mtiles;
-    if (pos0.bt < total && tn_of(pos0) >= ntiles) step(pos0);
+    if (pos0.bt < total && hole(pos0)) step(pos0);
     if (pos0.bt >= total) return;
     int my_tiles = 0;
     for (Pos p = pos0; p.bt < total; step(p)) my_tiles++;
@@ -981,7 +993,7 @@ __device__ __forceinline__ void flat_gemm_big_body(
 #pragma unroll
             for (int b = 0; b < 2; b++) {
                 fa[set][2 * b] = *reinterpret_cast<const float4 *>(As + oa + b * 32 * kGemmBK);
-                fa[set][2 * b + 1] = *reinterpret_cast<const float4 *>(As + ((oa + b * 32 * kGemmBK) ^ 16));
+                if constexpr (!SCREEN) fa[set][2 * b + 1] = *reinterpret_cast<const float4 *>(As + ((oa + b * 32 * kGemmBK) ^ 16));
             }
             if constexpr ((p & 1) == 0) {
                 const int ob = b_wave + lpart[2 + (p >> 1)];
@@ -1021,8 +1033,9 @@ __device__ __forceinline__ void flat_gemm_big_body(
             // q_lo.x_hi first, which need only the rows' hi halves — the lo halves (x - hi, rounded: 5 instructions per word) are
             // computed BETWEEN those eight, one word behind each, the order pinned: bunched in front, the conversions of both
             // waves of a SIMD (in step at the barrier) leave the matrix pipe empty; left to the scheduler they stay bunched.
+            // (the screen: the first product only, and no lo halves)
 #pragma unroll
-            for (int pr = 0; pr < 3; pr++)
+            for (int pr = 0; pr < (SCREEN ? 1 : 3); pr++)
 #pragma unroll
                 for (int b = 0; b < 2; b++)
 #pragma unroll
@@ -1030,7 +1043,7 @@ __device__ __forceinline__ void flat_gemm_big_body(
                         acc[i0 + b][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
                             __builtin_bit_cast(vg_bf16x8, fa[set][2 * b + (pr == 1 ? 1 : 0)]),
                             __builtin_bit_cast(vg_bf16x8, bc[j][pr == 2 ? 1 : 0]), acc[i0 + b][j], 0, 0, 0);
-                        if constexpr (even) {
+                        if constexpr (even && !SCREEN) {
                             if (pr < 2) {
                                 const int u = pr * 4 + b * 2 + j, rb = u >> 2, w = u & 3;
                                 const uint32_t hi = get(bc[rb][0], w);
@@ -1151,18 +1164,29 @@ __global__ __launch_bounds__(kBigThreads) void flat_gemm_bf16_big_kernel(
     const float *__restrict__ thr, int thr_stride, int thr_off, int *__restrict__ counts, uint64_t *__restrict__ cand, int cap,
     const uint8_t *__restrict__ mask, int64_t mask_stride, int count_stride)
 {
-    flat_gemm_big_body<DOT, NB, PROBE, false>(queries, nq, base, n, dim, norms, thr, thr_stride, thr_off, counts, cand, cap, mask,
-                                              mask_stride, count_stride);
+    flat_gemm_big_body<DOT, NB, PROBE, kBigImages>(queries, nq, base, n, dim, norms, thr, thr_stride, thr_off, counts, cand, cap, mask,
+                                                   mask_stride, count_stride);
 }
-// fp32 rows, split into bfloat16 hi + lo at operand-read time: `queries` = flat_split_queries_kernel's image, dim % 32 == 0
+// fp32 rows, split into bfloat16 hi + lo at operand-read time: `queries` = flat_split_queries_kernel's image, dim % 32 == 0;
+// tile_active: see the body (null = every query tile)
 template <bool DOT, int NB, int PROBE = 0>
 __global__ __launch_bounds__(kBigThreads) void flat_gemm_split_big_kernel(
     const float *__restrict__ queries, int64_t nq, const float *__restrict__ base, int64_t n, int dim, const float *__restrict__ norms,
     const float *__restrict__ thr, int thr_stride, int thr_off, int *__restrict__ counts, uint64_t *__restrict__ cand, int cap,
+    const uint8_t *__restrict__ mask, int64_t mask_stride, int count_stride, const uint32_t *__restrict__ tile_active)
+{
+    flat_gemm_big_body<DOT, NB, PROBE, kBigSplit>(queries, nq, base, n, dim, norms, thr, thr_stride, thr_off, counts, cand, cap, mask,
+                                                  mask_stride, count_stride, tile_active);
+}
+// the same operands, the product of the hi halves alone (the screen in front of the split tile)
+template <bool DOT, int NB, int PROBE = 0>
+__global__ __launch_bounds__(kBigThreads) void flat_gemm_screen_big_kernel(
+    const float *__restrict__ queries, int64_t nq, const float *__restrict__ base, int64_t n, int dim, const float *__restrict__ norms,
+    const float *__restrict__ thr, int thr_stride, int thr_off, int *__restrict__ counts, uint64_t *__restrict__ cand, int cap,
     const uint8_t *__restrict__ mask, int64_t mask_stride, int count_stride)
 {
-    flat_gemm_big_body<DOT, NB, PROBE, true>(queries, nq, base, n, dim, norms, thr, thr_stride, thr_off, counts, cand, cap, mask,
-                                             mask_stride, count_stride);
+    flat_gemm_big_body<DOT, NB, PROBE, kBigScreen>(queries, nq, base, n, dim, norms, thr, thr_stride, thr_off, counts, cand, cap, mask,
+                                                   mask_stride, count_stride);
 }
 
 // ---- 5..64 queries: the same pipeline with a 32 x 128 or 64 x 128 tile ------------------------------

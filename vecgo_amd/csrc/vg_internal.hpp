@@ -99,6 +99,8 @@ enum Hook {
     kHookPthrForceHist,       // VG_PTHR_FORCE_HIST      vg_search_flat_probed_threshold without rerank: the top-max_results-by-histogram form, then the filter
     kHookWalkSmallScratch,    // VG_WALK_SMALL_SCRATCH   a search walk's batch goes in launches of at most 5 queries (WalkChunks, vg_search.hpp): vg_search_hnsw / _pq / _filtered / _predicate, vg_search_vamana and its kin, vg_search_vamana_fresh
     kHookFlatNoSplit,         // VG_FLAT_NO_SPLIT        vg_search_flat above 128 queries: the fp32 MFMA GEMM, not the split tile (three bf16 products)
+    kHookFlatNoScreen,        // VG_FLAT_NO_SCREEN       vg_search_flat on the split tile: no one-product screen in front, the three-product pass for every tile
+    kHookFlatScreenFail,      // VG_FLAT_SCREEN_FAIL     vg_search_flat behind a screen: every screen proof counts as failed, every query is retried on the split tile (and the screen runs up to k = 48, not 16)
     kHookCount
 };
 bool hook(Hook h);
@@ -493,7 +495,7 @@ struct vg_index {
     float *d_norm_max = nullptr;  // [1] max ||x||^2: error bound of the GEMM-form scores
     uint16_t *d_vectors_bf16 = nullptr;  // optional bfloat16 copy of the rows: vg_index_enable_bf16_filter
     int32_t vectors_bf16_dim = 0;        // its row length: dim padded with zeros to whole 64-element K steps of the bf16 GEMM
-    unsigned long long *d_flat_stats = nullptr;  // [2] queries searched, queries sent to the exhaustive kernel
+    unsigned long long *d_flat_stats = nullptr;  // [3] queries searched, queries sent to the exhaustive kernel, queries retried on the split tile behind a screen
     // RaBitQ: sign bits re-tiled [tile][group][lane][16 B] and the stored norms
     uint8_t *d_rq_tiles = nullptr;
     float *d_rq_norms = nullptr;
