@@ -8,6 +8,8 @@
 //      GEMM score is under the query's threshold is re-scored, the proof is against the threshold)
 //   4. queries whose proof fails are recomputed by the exhaustive exact kernel
 // Steps 1-2 only nominate candidates; every reported id/score comes from step 3/4.
+// The host side has each step once (GemmArgs, sample_thresholds, launch_flat_pick, launch_flat_verify) for its four drivers:
+// flat_search_masked, flat_probe_gemm, flat_nominate_bf16, flat_thr_nominate; a driver's scratch is a struct that carves itself.
 #include <algorithm>
 
 #include "vg_device.hpp"
@@ -20,25 +22,38 @@
 
 namespace vg {
 
-// One GEMM launch.  `dma` picks the LDS-DMA kernel (16-byte aligned operands, dim % 4 == 0);
-// both kernels need more dynamic LDS than the 64 KiB a kernel gets by default.
-struct GemmArgs {
-    const float *queries;
-    int64_t nq;
-    const float *base;
+// What the nomination GEMMs multiply: the fp32 queries and the n fp32 rows, or bfloat16 images of both (dim_words: 4-byte words per
+// row).  `dma` picks the LDS-DMA kernels (16-byte aligned operands, dim % 4 == 0).  Filled by fp32_operands / gemm_operands.
+struct GemmOperands {
+    const float *a, *b;
     int64_t n;
-    int dim;
+    int dim_words;
     const float *norms;
-    float *scores;
-    int tile_stride;
-    int64_t out_cols;
-    const float *thr;
-    int thr_stride, thr_off;
-    int *counts;
-    uint64_t *cand;
-    int cap;
-    const uint8_t *mask = nullptr;  // row filter of a filtered search (k_probe.hip): bit per (query, row), or one per row
-    int64_t mask_stride = 0;
+    bool bf16, dma;
+};
+// One nomination's problem, shared by its GEMM launches: cnt queries against the rows, a row filter per query (mask + q *
+// mask_stride: a bit per row), for the batch (stride 0) or none (k_probe.hip).
+struct NomCall {
+    hipStream_t st;
+    bool dot;
+    GemmOperands ops;
+    int64_t cnt;
+    const uint8_t *mask;
+    int64_t mask_stride;
+    unsigned ucnt() const { return static_cast<unsigned>(cnt); }
+};
+// One GEMM launch, built by name: sample() or append() of a problem, then the parts a launch has beyond them.
+struct GemmArgs {
+    const NomCall &c;
+    const float *queries;  // c.ops.a, or the split tile's image of it
+    float *scores = nullptr;
+    int tile_stride = 1;
+    int64_t out_cols = 0;
+    const float *thr = nullptr;
+    int thr_stride = 0, thr_off = 0;
+    int *counts = nullptr;
+    uint64_t *cand = nullptr;
+    int cap = 0;
     int cus = 256;  // compute units of the device (the persistent bf16 tile launches one workgroup per CU)
     // nq * kCountLine ints of scratch: the persistent bf16 tile's counters, one 128-byte line per query.  An append is a returning
     // atomic on its query's counter; 1024 counters in 32 lines are 16 k atomics per line and launch, and a line serves them one
@@ -56,6 +71,27 @@ struct GemmArgs {
     // with `split`, not `screen`: the retry behind a screen.  Bit tm of the word = query tile tm holds a query to retry; the others
     // are not multiplied.  flat_retry_prepare_kernel has written it and zeroed the counters of the queries to retry.
     const uint32_t *tile_active = nullptr;
+
+    explicit GemmArgs(const NomCall &call) : c(call), queries(call.ops.a) {}
+    // MODE 0 / 1: the scores of every stride-th row tile into sc[cnt][cols] (stride 1: the whole score matrix)
+    static GemmArgs sample(const NomCall &c, float *sc, int stride, int64_t cols)
+    {
+        GemmArgs a(c);
+        a.scores = sc, a.tile_stride = stride, a.out_cols = cols;
+        return a;
+    }
+    // MODE 2: every row scoring below its query's threshold thr[q * sel_k + sel_k - 1] appended to cand[q * cap ..], counted in counts[q]
+    static GemmArgs append(const NomCall &c, const float *thr, int sel_k, int *counts, uint64_t *cand, int cap)
+    {
+        GemmArgs a(c);
+        a.thr = thr, a.thr_stride = sel_k, a.thr_off = sel_k - 1, a.counts = counts, a.cand = cand, a.cap = cap;
+        return a;
+    }
+    GemmArgs &wide(int *lines, int compute_units) { return counts_wide = lines, cus = compute_units, *this; }
+    GemmArgs &skipping(int stride) { return skip_stride = stride, *this; }
+    GemmArgs &split_tile(const uint32_t *image) { return queries = reinterpret_cast<const float *>(image), split = true, *this; }
+    GemmArgs &screen_tile() { return screen = true, *this; }
+    GemmArgs &retry(const uint32_t *active) { return tile_active = active, *this; }
 };
 constexpr int kCountLine = 32;
 // Whether a MODE 2 launch of vg_search_flat's fused path runs the split tile: fp32 rows nominated by three bfloat16 products on the
@@ -109,6 +145,14 @@ static float screen_gemm_eps(bool dot, int dim)
     const float m = static_cast<float>(dim + 16) * 5.9604645e-8f;
     return dot ? 0.00390625f + 7.62939453125e-6f + 2.52f * m : 0.0078125f + 1.52587890625e-5f + 4.03f * m;
 }
+// The bfloat16 filter's (vg_index_enable_bf16_filter) share of a proof's margin, as a multiple of |q|^2 + max |x|^2: the
+// nomination GEMMs read bf16 copies of the rows and of the queries; what they nominate is re-scored exactly as before and the
+// proof widens its margin by the rounding the copies can introduce.  bfloat16 keeps 8 significant bits: rounding to nearest moves
+// an operand by at most 2^-8 of its magnitude, a product q_i*x_i by at most (2^-7 + 2^-16)|q_i x_i|, the dot product by
+// (2^-7 + 2^-16)|q||x| <= (2^-8 + 2^-17)(|q|^2 + |x|^2).  A Dot score is the dot product; an L2 score is
+// |x|^2 - 2 q.x (norms from the fp32 rows), TWICE that: (2^-7 + 2^-16)(|q|^2 + |x|^2).  (r02 used the Dot
+// bound for both — half of what L2 needs: ADVICE r02, tests/test_gpu_flat_bf16.py test_filter_worst_case_rounding.)
+float bf16_filter_eps(bool dot) { return (dot ? 0.00390625f : 0.0078125f) * 1.02f; }
 // Whether launch_gemm_t runs a kernel that honours GemmArgs::skip_stride for these arguments: the fp32 128 x 128 tiles (LDS-DMA and
 // register-staged), whose MODE 1 and MODE 2 are one body with one accumulation order.  Not the 32-row tiles (up to 96 queries), not
 // a bf16 kernel, not the split tile (`split`: gemm_runs_split's answer).  The ONE place that decides: the caller appends the sampled rows itself exactly where this is true (a row
@@ -124,111 +168,95 @@ __global__ void counts_narrow_kernel(const int *__restrict__ wide, int64_t nq, i
     if (q < nq) counts[q] = wide[q * kCountLine];
 }
 
-template <bool DOT, int MODE>
-static int32_t launch_gemm_t(bool dma, unsigned blocks, hipStream_t st, const GemmArgs &a, bool bf16)
+// a kernel that needs more dynamic LDS than the default 64 KiB: the attribute (on every call), the launch (none of an empty grid)
+template <class Kern, class... Args>
+static int32_t launch_lds(Kern kern, dim3 grid, dim3 threads, size_t lds, hipStream_t st, Args... args)
 {
+    VG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
+    if (grid.x != 0) VG_LAUNCH(kern, grid, threads, lds, st, args...);
+    return VG_OK;
+}
+// the 32-row tile of rb blocks of 32 query rows — fp32 rows: 1 .. 3, bf16 images: 1 .. 4 — as f(kernel, its LDS bytes)
+template <bool DOT, int M, bool BF16, class F>
+static int32_t with_g32_tile(int rb, F f)
+{
+    constexpr int kMost = BF16 ? 4 : 3;
+    if (rb <= 1) return f(flat_gemm_dma32_kernel<DOT, M, 1, BF16>, g32_lds_bytes<1>());
+    if (rb == 2) return f(flat_gemm_dma32_kernel<DOT, M, 2, BF16>, g32_lds_bytes<2>());
+    if (rb == 3) return f(flat_gemm_dma32_kernel<DOT, M, 3, BF16>, g32_lds_bytes<3>());
+    return f(flat_gemm_dma32_kernel<DOT, M, kMost, BF16>, g32_lds_bytes<kMost>());
+}
+
+template <bool DOT, int MODE>
+static int32_t launch_gemm_t(const GemmArgs &a)
+{
+    const NomCall &c = a.c;
+    const bool dma = c.ops.dma, bf16 = c.ops.bf16;
+    const hipStream_t st = c.st;
     const int skip = MODE == 2 ? a.skip_stride : 0;
-    VG_CHECK(skip == 0 || (skip > 1 && gemm_skips_sample(dma, a.nq, bf16, a.split)), VG_ERR_INVALID_ARG, "launch_gemm: skip_stride on a kernel without it");
+    VG_CHECK(skip == 0 || (skip > 1 && gemm_skips_sample(dma, c.cnt, bf16, a.split)), VG_ERR_INVALID_ARG, "launch_gemm: skip_stride on a kernel without it");
+    // the grid of the 128 x 128 tiles: whole groups of 8 row tiles per query tile (the XCD-aware order); a sample launches every
+    // tile_stride-th row tile, a launch with `skip` the tiles the sample left
+    const int64_t mt = (c.cnt + kGemmBM - 1) / kGemmBM, nt = (c.ops.n + kGemmBN - 1) / kGemmBN;
+    const int64_t tiles = skip ? nt - gemm_skip_sampled_tiles(nt, skip) : (nt + a.tile_stride - 1) / a.tile_stride;
+    const dim3 grid(static_cast<unsigned>(mt * ((tiles + 7) / 8) * 8)), threads(kGemmThreads);
     // the persistent 256 x 256 tile (bf16 images, or the split tile on the fp32 rows): one workgroup per CU, wide counters
     // (extra: the split tile's tile_active.  A retry's counters are flat_retry_prepare_kernel's to zero: those of the queries it
     // retries, the others keep what the screen counted)
     auto launch_big = [&](auto kern, size_t lds, auto... extra) -> int32_t {
-        VG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   static_cast<int>(lds)));
-        const int64_t mt = (a.nq + kBigBM - 1) / kBigBM, nt = (a.n + kBigBN - 1) / kBigBN;
-        const int64_t slots = mt * ((nt + 7) / 8) * 8, per_cu = std::max(a.cus / 8, 1) * 8;  // (one workgroup per CU: LDS)
-        if (a.counts_wide && !a.tile_active) VG_HIP(hipMemsetAsync(a.counts_wide, 0, sizeof(int) * static_cast<size_t>(a.nq) * kCountLine, st));
-        VG_LAUNCH(kern, dim3(static_cast<unsigned>(std::min(slots, per_cu))), dim3(kBigThreads), lds, st, a.queries, a.nq,
-                  a.base, a.n, a.dim, a.norms, a.thr, a.thr_stride, a.thr_off, a.counts_wide ? a.counts_wide : a.counts, a.cand, a.cap, a.mask,
-                  a.mask_stride, a.counts_wide ? kCountLine : 1, extra...);
+        const int64_t bmt = (c.cnt + kBigBM - 1) / kBigBM, bnt = (c.ops.n + kBigBN - 1) / kBigBN;
+        const int64_t slots = bmt * ((bnt + 7) / 8) * 8, per_cu = std::max(a.cus / 8, 1) * 8;  // (one workgroup per CU: LDS)
+        if (a.counts_wide && !a.tile_active) VG_HIP(hipMemsetAsync(a.counts_wide, 0, sizeof(int) * static_cast<size_t>(c.cnt) * kCountLine, st));
+        VG_TRY(launch_lds(kern, dim3(static_cast<unsigned>(std::min(slots, per_cu))), dim3(kBigThreads), lds, st, a.queries, c.cnt, c.ops.b, c.ops.n,
+                          c.ops.dim_words, c.ops.norms, a.thr, a.thr_stride, a.thr_off, a.counts_wide ? a.counts_wide : a.counts, a.cand, a.cap, c.mask,
+                          c.mask_stride, a.counts_wide ? kCountLine : 1, extra...));
         if (a.counts_wide)
-            VG_LAUNCH(counts_narrow_kernel, dim3(static_cast<unsigned>((a.nq + 255) / 256)), dim3(256), 0, st, a.counts_wide, a.nq, a.counts);
+            VG_LAUNCH(counts_narrow_kernel, dim3(static_cast<unsigned>((c.cnt + 255) / 256)), dim3(256), 0, st, a.counts_wide, c.cnt, a.counts);
         return VG_OK;
     };
+    // the 128 x 128 tiles (last: the row tiles a MODE 2 launch leaves out, 0 where the kernel has no such form) and the 32-row
+    // tiles (one workgroup per row tile — of the sample: per sampled one)
+    auto launch_tile = [&](auto kern, dim3 blocks, size_t lds, auto... last) -> int32_t {
+        return launch_lds(kern, blocks, threads, lds, st, a.queries, c.cnt, c.ops.b, c.ops.n, c.ops.dim_words, c.ops.norms, a.scores, a.tile_stride, a.out_cols, a.thr,
+                          a.thr_stride, a.thr_off, a.counts, a.cand, a.cap, c.mask, c.mask_stride, last...);
+    };
+    auto launch_128 = [&](auto kern, size_t lds, int last) { return launch_tile(kern, grid, lds, last); };
+    auto launch_g32 = [&](auto kern, size_t lds) { return launch_tile(kern, dim3(static_cast<unsigned>(tiles)), lds); };
+    constexpr int M = MODE == 0 ? 1 : MODE;
+    const int rb = static_cast<int>((c.cnt + kG32BM - 1) / kG32BM);
     if (MODE == 2 && a.split) {
-        VG_CHECK(!bf16 && gemm_runs_split(true, false, dma, a.nq, a.dim, a.cap, a.thr_stride), VG_ERR_INVALID_ARG, "launch_gemm: split tile on a call without it");
+        VG_CHECK(!bf16 && gemm_runs_split(true, false, dma, c.cnt, c.ops.dim_words, a.cap, a.thr_stride), VG_ERR_INVALID_ARG, "launch_gemm: split tile on a call without it");
         if (a.screen) return launch_big(flat_gemm_screen_big_kernel<DOT, 3>, big_lds_bytes<3>());
-        VG_CHECK(!a.tile_active || (a.nq <= 32 * kBigBM && a.counts_wide), VG_ERR_INVALID_ARG, "launch_gemm: tile_active is one word, with wide counters");
+        VG_CHECK(!a.tile_active || (c.cnt <= 32 * kBigBM && a.counts_wide), VG_ERR_INVALID_ARG, "launch_gemm: tile_active is one word, with wide counters");
         note_flat_split_launch();
         return launch_big(flat_gemm_split_big_kernel<DOT, 3>, big_lds_bytes<3>(), a.tile_active);
     }
-    if (skip) {  // the grid of the tiles that are left, in the same XCD-aware order
-        const int64_t mt = (a.nq + kGemmBM - 1) / kGemmBM, nt = (a.n + kGemmBN - 1) / kGemmBN;
-        const int64_t left = nt - gemm_skip_sampled_tiles(nt, skip);
-        if (left == 0) return VG_OK;
-        blocks = static_cast<unsigned>(mt * ((left + 7) / 8) * 8);
-    }
-    if (bf16) {  // rows of bfloat16 (a.dim = 4-byte words per row): the LDS-DMA tiles only
-        constexpr int M = MODE == 0 ? 1 : MODE;
+    if (skip && tiles == 0) return VG_OK;
+    if (bf16) {  // rows of bfloat16 (c.ops.dim_words = 4-byte words per row): the LDS-DMA tiles only
         // up to 128 queries: the tile of 1 .. 4 blocks of 32 query rows (HBM-bound at the bf16 rate: 65 .. 128 queries 0.44 .. 0.49 ms on
         // the 128 x 128 tile, 0.40 .. 0.45 on this one — tools/mid_batch_time.py)
-        if (a.nq <= 4 * kG32BM && !hook(kHookFlatNoSmallTile)) {
-            const bool one = a.nq <= kG32BM;
-            const int rb = static_cast<int>((a.nq + kG32BM - 1) / kG32BM);
-            auto kern = one ? flat_gemm_dma32_kernel<DOT, M, 1, true> : rb == 2 ? flat_gemm_dma32_kernel<DOT, M, 2, true> : rb == 3 ? flat_gemm_dma32_kernel<DOT, M, 3, true> : flat_gemm_dma32_kernel<DOT, M, 4, true>;
-            const size_t lds = one ? g32_lds_bytes<1>() : rb == 2 ? g32_lds_bytes<2>() : rb == 3 ? g32_lds_bytes<3>() : g32_lds_bytes<4>();
-            VG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       static_cast<int>(lds)));
-            const int64_t tiles = (a.n + kGemmBN - 1) / kGemmBN;
-            const int64_t grid = MODE == 1 ? (tiles + a.tile_stride - 1) / a.tile_stride : tiles;
-            VG_LAUNCH(kern, dim3(static_cast<unsigned>(grid)), dim3(kGemmThreads), lds, st, a.queries, a.nq, a.base,
-                      a.n, a.dim, a.norms, a.scores, a.tile_stride, a.out_cols, a.thr, a.thr_stride, a.thr_off, a.counts,
-                      a.cand, a.cap, a.mask, a.mask_stride);
-            return VG_OK;
-        }
+        if (c.cnt <= 4 * kG32BM && !hook(kHookFlatNoSmallTile)) return with_g32_tile<DOT, M, true>(rb, launch_g32);
         // more than one 128-query tile: the persistent 256 x 256 tile (32-bit candidate offsets: nq * cap < 2^31)
-        if (MODE == 2 && a.nq > kGemmBM && a.nq * static_cast<int64_t>(a.cap) < (int64_t(1) << 31) && a.thr_stride < 65536 &&
+        if (MODE == 2 && c.cnt > kGemmBM && c.cnt * static_cast<int64_t>(a.cap) < (int64_t(1) << 31) && a.thr_stride < 65536 &&
             !hook(kHookFlatNoBigTile)) {
             const bool two = hook(kHookFlatBigTile2);
             auto kern = two ? flat_gemm_bf16_big_kernel<DOT, 2> : hook(kHookFlatBigEarlyB) ? flat_gemm_bf16_big_kernel<DOT, 3, 512> : flat_gemm_bf16_big_kernel<DOT, 3>;
             return launch_big(kern, two ? big_lds_bytes<2>() : big_lds_bytes<3>());
         }
-        auto kern = flat_gemm_dma_kernel<DOT, M, 0, true>;
-        VG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   static_cast<int>(kDmaLdsBytes)));
-        VG_LAUNCH(kern, dim3(blocks), dim3(kGemmThreads), kDmaLdsBytes, st, a.queries, a.nq, a.base, a.n, a.dim,
-                  a.norms, a.scores, a.tile_stride, a.out_cols, a.thr, a.thr_stride, a.thr_off, a.counts, a.cand,
-                  a.cap, a.mask, a.mask_stride, 0);
-        return VG_OK;
+        return launch_128(flat_gemm_dma_kernel<DOT, M, 0, true>, kDmaLdsBytes, 0);
     }
     // (test hook kHookFlatNoSmallTile: always the 128-query tile)
     // 1 - 3 blocks of 32 queries: the HBM-bound shapes, and 65 .. 96 queries at three quarters of the 128-query tile's matrix work
     // (1.65 -> 1.28 ms per call at 1M x 768; 97 .. 128 queries: four blocks run as long as the 128 x 128 tile, which keeps them)
-    if (dma && MODE != 0 && a.nq <= 3 * kG32BM && !hook(kHookFlatNoSmallTile)) {
-        constexpr int M = MODE == 0 ? 1 : MODE;
-        const bool one = a.nq <= kG32BM;
-        const int rb = static_cast<int>((a.nq + kG32BM - 1) / kG32BM);
-        auto kern = one ? flat_gemm_dma32_kernel<DOT, M, 1> : rb == 2 ? flat_gemm_dma32_kernel<DOT, M, 2> : flat_gemm_dma32_kernel<DOT, M, 3>;
-        const size_t lds = one ? g32_lds_bytes<1>() : rb == 2 ? g32_lds_bytes<2>() : g32_lds_bytes<3>();
-        VG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   static_cast<int>(lds)));
-        const int64_t tiles = (a.n + kGemmBN - 1) / kGemmBN;
-        const int64_t grid = MODE == 1 ? (tiles + a.tile_stride - 1) / a.tile_stride : tiles;
-        VG_LAUNCH(kern, dim3(static_cast<unsigned>(grid)), dim3(kGemmThreads), lds, st, a.queries, a.nq, a.base,
-                  a.n, a.dim, a.norms, a.scores, a.tile_stride, a.out_cols, a.thr, a.thr_stride, a.thr_off, a.counts,
-                  a.cand, a.cap, a.mask, a.mask_stride);
-    } else if (dma) {
-        auto kern = flat_gemm_dma_kernel<DOT, MODE>;
-        VG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   static_cast<int>(kDmaLdsBytes)));
-        VG_LAUNCH(kern, dim3(blocks), dim3(kGemmThreads), kDmaLdsBytes, st, a.queries, a.nq, a.base, a.n, a.dim,
-                  a.norms, a.scores, a.tile_stride, a.out_cols, a.thr, a.thr_stride, a.thr_off, a.counts, a.cand,
-                  a.cap, a.mask, a.mask_stride, skip);
-    } else {
-        auto kern = flat_gemm_kernel<DOT, MODE>;
-        VG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   static_cast<int>(kGemmLdsBytes)));
-        VG_LAUNCH(kern, dim3(blocks), dim3(kGemmThreads), kGemmLdsBytes, st, a.queries, a.nq, a.base, a.n, a.dim,
-                  a.norms, a.scores, a.tile_stride, a.out_cols, a.thr, a.thr_stride, a.thr_off, a.counts, a.cand,
-                  a.cap, a.mask, a.mask_stride, skip);
-    }
-    return VG_OK;
+    if (dma && MODE != 0 && c.cnt <= 3 * kG32BM && !hook(kHookFlatNoSmallTile)) return with_g32_tile<DOT, M, false>(rb, launch_g32);
+    if (dma) return launch_128(flat_gemm_dma_kernel<DOT, MODE>, kDmaLdsBytes, skip);
+    return launch_128(flat_gemm_kernel<DOT, MODE>, kGemmLdsBytes, skip);
 }
 
 template <int MODE>
-static int32_t launch_gemm(bool dot, bool dma, unsigned blocks, hipStream_t st, const GemmArgs &a, bool bf16 = false)
+static int32_t launch_gemm(const GemmArgs &a)
 {
-    return dot ? launch_gemm_t<true, MODE>(dma, blocks, st, a, bf16) : launch_gemm_t<false, MODE>(dma, blocks, st, a, bf16);
+    return a.c.dot ? launch_gemm_t<true, MODE>(a) : launch_gemm_t<false, MODE>(a);
 }
 
 // fp32 -> bfloat16, round to nearest even (NaN stays NaN): rows of `dim` floats written as rows of `dim_pad` bfloat16, the tail
@@ -870,12 +898,367 @@ int32_t launch_page_patch(int64_t nq, int k, int off, int kk, bool descending, c
     return VG_OK;
 }
 
-}  // namespace vg
-
-VG_API int32_t vg_search_flat(vg_index *idx, const float *queries, int64_t nq, int32_t k, uint32_t *ids,
-                              float *scores, void *stream)
+// ---- the host side of a nomination: each step once --------------------------------------------------------------------------
+// The operands of a nomination on the fp32 rows (LDS-DMA, where the caller has it: rows of whole float4, 16-byte aligned)
+static GemmOperands fp32_operands(const vg_index *idx, const float *queries, bool dma = true)
 {
-    return vg::flat_search_masked(idx, queries, nq, k, nullptr, 0, ids, scores, stream);
+    return {queries, idx->d_vectors, idx->n, idx->dim, idx->d_norms, false, dma && idx->dim % 4 == 0 && aligned16(queries) && aligned16(idx->d_vectors)};
+}
+// The operands of a nomination on a bfloat16 image of the n rows (rows_bf16: dim_pad bfloat16 a row, `norms` its norms): the
+// queries rounded and padded alike into qbf — one launch — and the image.
+static int32_t gemm_operands(const float *queries, int64_t cnt, int dim, int64_t n, const float *norms, const uint16_t *rows_bf16, int dim_pad,
+                             uint16_t *qbf, hipStream_t st, GemmOperands *ops)
+{
+    VG_LAUNCH(f32_to_bf16_pad_kernel, dim3(static_cast<unsigned>((cnt * dim_pad + 255) / 256)), dim3(256), 0, st, queries, cnt, dim, dim_pad, qbf);
+    *ops = {reinterpret_cast<const float *>(qbf), reinterpret_cast<const float *>(rows_bf16), n, dim_pad / 2, norms, true, true};
+    return VG_OK;
+}
+// the columns of a row sample: every stride-th 128-row tile of n rows, whole tiles
+static int64_t sample_cols(int64_t n, int stride)
+{
+    const int64_t nt = (n + kGemmBN - 1) / kGemmBN;
+    return (nt + stride - 1) / stride * kGemmBN;
+}
+// the slices flat_select_kernel cuts a query's cols scores into: per_slice scores each, at most `most`
+static int select_slices(int64_t cols, int per_slice, int most)
+{
+    return static_cast<int>(std::min<int64_t>(most, std::max<int64_t>(1, cols / per_slice)));
+}
+constexpr int kFlatKc = 64;  // nominated candidates per query
+// Scratch of a nomination of cnt queries: the threshold step's (the sampled scores sc[cnt][cols], the select's lists, the merge's
+// row ids) and what it produces (nom: the thresholds, the counts, cap appended keys a query, the 64 picked).  What it was sized
+// with is what it is launched with.  A driver's scratch derives from it and carves itself where it is constructed, from `base` —
+// null: it only measures — and `bytes` is what it takes.
+struct NomScratch {
+    float *sc;
+    uint64_t *partial;
+    uint32_t *sid;
+    int64_t cols;
+    int slices;  // (slices_ = 0: the flat searches' rule)
+    ProbeNominated nom;
+    size_t bytes;
+    void carve(Carve &c, int64_t cnt, int64_t cols_, int sel_k, int cap, bool sampled = true, int slices_ = 0)
+    {
+        cols = cols_;
+        slices = slices_ ? slices_ : select_slices(cols, 4096, 64);
+        nom.sel_k = sel_k;
+        nom.cap = cap;
+        c.take(sc, sampled ? cnt * cols : 1);  // (not sampled: no launch reads it)
+        c.take(partial, cnt * slices * sel_k);
+        c.take(sid, cnt * sel_k);
+        c.take(nom.thr, cnt * sel_k);
+        c.take(nom.counts, cnt);
+        c.take(nom.cand, cnt * cap);
+        c.take(nom.cand_id, cnt * kFlatKc);
+        c.take(nom.cand_sc, cnt * kFlatKc);
+    }
+};
+static int32_t launch_flat_select(const NomScratch &s, int64_t cnt, int sel_k, hipStream_t st)
+{
+    VG_LAUNCH(flat_select_kernel, dim3(s.slices, static_cast<unsigned>(cnt)), dim3(kSelThreads), 0, st, s.sc, s.cols, s.slices, sel_k, s.partial);
+    return VG_OK;
+}
+// per query the sel_k best of its scores s.sc, ascending, into thr[cnt][sel_k] (ids: their columns)
+static int32_t select_thresholds(const NomScratch &s, int64_t cnt, int sel_k, uint32_t *ids, float *thr, hipStream_t st)
+{
+    VG_TRY(launch_flat_select(s, cnt, sel_k, st));
+    return launch_topk_merge(s.partial, cnt, s.slices, sel_k, false, ids, thr, st);
+}
+// (a) of a nomination: a query's thresholds are the sel_k best scores of a row sample (every stride-th row tile; rows its filter
+// rejects score +Inf), the last of them its append threshold; not `sampled` (few rows: the list holds them all): +Inf
+static int32_t sample_thresholds(const NomCall &c, const NomScratch &s, int stride, int sel_k, float *thr, bool sampled)
+{
+    if (!sampled) {
+        VG_LAUNCH(fill_f32_kernel, dim3(static_cast<unsigned>((c.cnt * sel_k + 255) / 256)), dim3(256), 0, c.st, thr, c.cnt * sel_k, INFINITY);
+        return VG_OK;
+    }
+    VG_TRY(launch_gemm<1>(GemmArgs::sample(c, s.sc, stride, s.cols)));
+    return select_thresholds(s, c.cnt, sel_k, s.sid, thr, c.st);
+}
+static int32_t launch_flat_pick(const ProbeNominated &nom, int64_t cnt, const int *only, hipStream_t st)
+{
+    VG_LAUNCH(flat_pick_kernel, dim3(static_cast<unsigned>(cnt)), dim3(256), 0, st, nom.cand, nom.counts, nom.cap, kFlatKc, nom.cand_id, nom.cand_sc, only);
+    return VG_OK;
+}
+// (d) of a nomination on the fp32 rows: the exact re-score and the proof, ids / scores [cnt][k] and fail[q] = 1 where the proof
+// does not hold.  k > 64: every appended row, sorted in LDS; k > kGemmMaxK: every appended row; otherwise the kFlatKc picked ones
+// (nom.thr null: the unfused variant's 64 best of the score matrix; only: see flat_verify_kernel).
+static int32_t launch_flat_verify(bool dot, int k, const vg_index *idx, const float *queries, int64_t cnt, const ProbeNominated &nom,
+                                  float eps_extra, uint32_t *ids, float *scores, int *fail, const int *only, hipStream_t st)
+{
+    return with_metric(dot, [&](auto dot_c) -> int32_t {
+        constexpr bool DOT = decltype(dot_c)::value;
+        const dim3 grid(static_cast<unsigned>(cnt)), threads(256);
+        if (nom.thr && k > 64)
+            VG_LAUNCH(flat_verify_sort_kernel<DOT>, grid, threads, sizeof(uint64_t) * static_cast<size_t>(nom.cap), st, idx->d_vectors, idx->dim, queries,
+                      idx->d_norm_max, nom.cand, nom.counts, nom.cap, k, ids, scores, fail, nom.thr, nom.sel_k, nom.sel_k - 1, eps_extra);
+        else if (nom.thr && k > kGemmMaxK)
+            VG_LAUNCH(flat_verify_all_kernel<DOT>, grid, threads, 0, st, idx->d_vectors, idx->dim, queries, idx->d_norm_max, nom.cand, nom.counts,
+                      nom.cap, k, ids, scores, fail, nom.thr, nom.sel_k, nom.sel_k - 1, eps_extra);
+        else
+            VG_LAUNCH(flat_verify_kernel<DOT>, grid, threads, 0, st, idx->d_vectors, idx->n, idx->dim, queries, idx->d_norm_max, nom.cand_id,
+                      nom.cand_sc, kFlatKc, k, ids, scores, fail, nom.thr, nom.sel_k, nom.sel_k - 1, nom.counts, nom.cap, eps_extra, only);
+        return VG_OK;
+    });
+}
+
+// ---- vg_search_flat -----------------------------------------------------------------------------------------------------------
+// One call, or one chunk of it (range): device pointers; mask: see flat_search_masked
+struct FlatCall {
+    vg_index *idx;
+    int k;
+    hipStream_t st;
+    bool dot;
+    const float *q;
+    int64_t nq;
+    const uint8_t *mask;
+    int64_t mask_stride;
+    uint32_t *oid;
+    float *osc;
+    int64_t n = idx->n;
+    int dim = idx->dim;
+    // queries q0 .. q0 + cnt - 1 with their filters and results: the offsets of a chunk, in one place
+    FlatCall range(int64_t q0, int64_t cnt) const
+    {
+        FlatCall r = *this;
+        r.q += q0 * dim, r.nq = cnt, r.oid += q0 * k, r.osc += q0 * k;
+        if (mask) r.mask += q0 * mask_stride;
+        return r;
+    }
+    // its nomination on the fp32 rows (test hook kHookFlatNoDma: force the register-staged GEMM)
+    NomCall nom() const { return {st, dot, fp32_operands(idx, q, !hook(kHookFlatNoDma)), nq, mask, mask_stride}; }
+};
+constexpr int kFlatCap = 4096;         // candidate keys per query (fused path, and the nomination on a quantizer's image)
+constexpr int kFlatSampleStride = 64;  // every 64th 128-row tile is sampled
+static int exact_slices(int64_t n) { return static_cast<int>(std::min<int64_t>(256, std::max<int64_t>(1, n / 64))); }
+// The sizes of the GEMM paths, fixed per call, and their scratch for qc queries, shared by the chunks
+struct FlatScratch : NomScratch {
+    bool fused;       // (test hook kHookFlatUnfused: materialise the score matrix)
+    bool use_sample;  // n <= cap: threshold +Inf, every row is appended
+    bool bf16;        // the bfloat16 filter (bf16_filter_eps)
+    bool may_split;   // a chunk above 128 queries may nominate on the split tile (gemm_runs_split, decided per chunk)
+    int ex_slices, pk;  // the exhaustive fall-back: slices of the rows, results per page
+    int64_t qc;       // queries per chunk
+    int *flags, *todo;  // the proofs' verdicts (flags[qc]: flat_todo_kernel's "every query" switch) and step 4's work list
+    uint64_t *fpartial, *min_keys;
+    uint32_t *fid;
+    float *fsc;
+    uint16_t *qbf;  // the chunk's queries in bfloat16, or as the split tile's hi | lo image
+    int *counts_wide;
+    uint32_t *tile_active;  // the retry's query tiles (flat_retry_prepare_kernel)
+    FlatScratch(const FlatCall &c, bool unfused, char *base) : fused(!unfused), use_sample(fused && c.n > kFlatCap)
+    {
+        // (any dim: the copies' rows are padded with zeros to whole K steps, vectors_bf16_dim)
+        bf16 = c.idx->d_vectors_bf16 != nullptr && fused && !hook(kHookFlatNoDma);
+        // thresholds kept per query: the sample_j-th best score of the row sample is the query's, ~64 * sample_j rows pass it
+        // (k > 64: ~3k of them); the unfused variant: the 64 nominated candidates
+        const int sel_k = !fused ? kFlatKc : c.k <= 64 ? 8 : std::min(64, std::max(8, (3 * c.k + 63) / 64));
+        ex_slices = exact_slices(c.n);
+        pk = std::min(c.k, 64);
+        // query chunk: whole 128-query tiles; unfused keeps the score matrix <= 2 GiB
+        qc = fused ? 4096 : (int64_t(2) << 30) / (c.n * 4);
+        if (qc > 4096) qc = 4096;
+        if (qc >= kGemmBM) qc = (qc / kGemmBM) * kGemmBM;
+        if (qc < 1) qc = 1;
+        if (qc > c.nq) qc = c.nq;
+        // without the filter, a chunk above 128 queries nominates on the split tile (gemm_runs_split, decided per chunk: the
+        // margin grows by split_gemm_eps, the chunk's queries are written as a hi | lo image, the appends count in wide counters)
+        may_split = gemm_runs_split(fused, bf16, true, qc, c.dim, kFlatCap, sel_k);
+        Carve cv{base};
+        // (unfused: nothing is appended, cap 0 — flat_verify_kernel reads no cap where it has no threshold)
+        carve(cv, qc, fused ? sample_cols(c.n, kFlatSampleStride) : c.n, sel_k, fused ? kFlatCap : 0, !fused || use_sample);
+        cv.take(flags, qc + 1);
+        cv.take(todo, qc + 1);
+        cv.take(fpartial, qc * ex_slices * pk);
+        cv.take(fid, qc * pk);
+        cv.take(fsc, qc * pk);
+        cv.take(min_keys, qc);
+        cv.take(qbf, bf16 ? qc * c.idx->vectors_bf16_dim : may_split ? 2 * qc * c.dim : 0);
+        cv.take(counts_wide, bf16 || may_split ? qc * kCountLine : 0);
+        cv.take(tile_active, may_split ? 1 : 0);
+        bytes = cv.off;
+    }
+};
+
+// small batch: HBM-bound exact scan, kScanQB queries per pass over the rows
+static int32_t flat_scan_small(const FlatCall &c)
+{
+    const int slices = static_cast<int>(std::min<int64_t>(4 * c.idx->ctx->compute_units, std::max<int64_t>(1, c.n / 64)));
+    ArenaCall ar(c.idx->ctx, c.st);
+    const int i_partial = ar.add(sizeof(uint64_t) * static_cast<size_t>(c.nq) * slices * c.k);
+    VG_TRY(ar.commit());
+    uint64_t *partial = ar.get<uint64_t>(i_partial);
+    const size_t lds = sizeof(float) * static_cast<size_t>(kScanQB) * c.dim + 4 * 64 * sizeof(uint64_t) + 64;
+    for (int64_t q0 = 0; q0 < c.nq; q0 += kScanQB) {
+        const int cnt = static_cast<int>(std::min<int64_t>(kScanQB, c.nq - q0));
+        ProfScope prof(c.idx->ctx, "flat_scan", c.st);
+        auto kern = c.dot ? flat_scan_mq_kernel<true> : flat_scan_mq_kernel<false>;
+        VG_LAUNCH(kern, dim3(slices), dim3(256), lds, c.st, c.idx->d_vectors, c.n, c.dim, c.q + q0 * c.dim, cnt, slices, c.k, partial + q0 * slices * c.k);
+    }
+    VG_TRY(launch_topk_merge(partial, c.nq, slices, c.k, c.dot, c.oid, c.osc, c.st));
+    return launch_flat_todo(nullptr, nullptr, static_cast<int>(c.nq), nullptr, c.idx->d_flat_stats, c.st);
+}
+
+// step 4: the exhaustive exact kernel for the chunk's queries of the work list, kk results each after floor_keys (null: the best)
+static int32_t launch_flat_exact(const FlatCall &c, const int *todo, int ex_slices, int kk, uint64_t *fpartial, const uint64_t *floor_keys)
+{
+    const unsigned slots = static_cast<unsigned>(std::min<int64_t>(c.nq, kExactSlots));
+    auto kern = c.dot ? flat_exact_kernel<true> : flat_exact_kernel<false>;
+    VG_LAUNCH(kern, dim3(ex_slices, slots), dim3(256), 0, c.st, c.idx->d_vectors, c.n, c.dim, c.q, todo, ex_slices, kk, fpartial, floor_keys, c.mask,
+              c.mask_stride);
+    return VG_OK;
+}
+// kGemmMaxK < k <= 64 of the unfused variant (64 nominated candidates cannot prove k near 64): the exhaustive exact kernel for
+// every query, one pass over the rows per query
+static int32_t flat_exact_every_query(const FlatCall &call)
+{
+    const int ex_slices = exact_slices(call.n);
+    const int64_t qc = std::min<int64_t>(call.nq, 4096);
+    ArenaCall ar(call.idx->ctx, call.st);
+    const int i_flags = ar.add(sizeof(int) * (static_cast<size_t>(qc) + 1));
+    const int i_todo = ar.add(sizeof(int) * (static_cast<size_t>(qc) + 1));
+    const int i_fpartial = ar.add(sizeof(uint64_t) * static_cast<size_t>(qc) * ex_slices * call.k);
+    VG_TRY(ar.commit());
+    int *flags = ar.get<int>(i_flags), *todo = ar.get<int>(i_todo);
+    uint64_t *fpartial = ar.get<uint64_t>(i_fpartial);
+    VG_HIP(hipMemsetAsync(flags, 0, sizeof(int) * static_cast<size_t>(qc), call.st));
+    VG_HIP(hipMemsetAsync(flags + qc, 1, sizeof(int), call.st));  // "every query" switch of flat_todo_kernel
+    for (int64_t q0 = 0; q0 < call.nq; q0 += qc) {
+        const FlatCall c = call.range(q0, std::min(qc, call.nq - q0));
+        VG_TRY(launch_flat_todo(flags, flags + qc, static_cast<int>(c.nq), todo, c.idx->d_flat_stats, c.st));
+        VG_TRY(launch_flat_exact(c, todo, ex_slices, c.k, fpartial, nullptr));
+        VG_TRY(launch_topk_merge(fpartial, c.nq, ex_slices, c.k, c.dot, c.oid, c.osc, c.st));
+    }
+    return VG_OK;
+}
+
+// The unfused variant (test hook) of a chunk: its whole score matrix, the 64 best per query, their re-score and proof
+static int32_t flat_unfused_chunk(const FlatCall &c, const FlatScratch &s)
+{
+    const NomCall nc = c.nom();
+    {
+        ProfScope prof(c.idx->ctx, "flat_gemm", c.st);
+        VG_TRY(launch_gemm<0>(GemmArgs::sample(nc, s.sc, 1, c.n)));
+    }
+    {
+        ProfScope prof(c.idx->ctx, "flat_select", c.st);
+        VG_TRY(launch_flat_select(s, c.nq, kFlatKc, c.st));
+    }
+    VG_TRY(launch_topk_merge(s.partial, c.nq, s.slices, kFlatKc, false, s.nom.cand_id, s.nom.cand_sc, c.st));
+    ProbeNominated nom = s.nom;
+    nom.thr = nullptr;  // nothing was appended: the proof argues from the 64th best score
+    return launch_flat_verify(c.dot, c.k, c.idx, c.q, c.nq, nom, 0.0f, c.oid, c.osc, s.flags, nullptr, c.st);
+}
+
+// The retry behind a screen.  A query whose proof held is finished; for the others (normally none) the split tile
+// runs on the 256-query tiles that hold one — launched ALWAYS, once per chunk: with no tile marked every workgroup
+// returns at once — then the pick and the proof again, for the flagged queries only and with the split tile's margin.
+// (test hook kHookFlatScreenFail: every screen proof counts as failed)
+static int32_t flat_screen_retry(const FlatCall &c, const NomCall &nc, const FlatScratch &s)
+{
+    const ProbeNominated &nom = s.nom;
+    VG_LAUNCH(flat_retry_prepare_kernel, dim3(1), dim3(kBigBM), 0, c.st, s.flags, hook(kHookFlatScreenFail), static_cast<int>(c.nq), nom.thr,
+              nom.sel_k, nom.sel_k - 1, nom.counts, s.counts_wide, s.tile_active, c.idx->d_flat_stats);
+    {
+        ProfScope prof(c.idx->ctx, "flat_retry", c.st);
+        VG_TRY(launch_gemm<2>(GemmArgs::append(nc, nom.thr, nom.sel_k, nom.counts, nom.cand, nom.cap)
+                                  .wide(s.counts_wide, c.idx->ctx->compute_units)
+                                  .split_tile(reinterpret_cast<const uint32_t *>(s.qbf))
+                                  .retry(s.tile_active)));
+    }
+    VG_TRY(launch_flat_pick(nom, c.nq, s.flags, c.st));
+    return launch_flat_verify(c.dot, c.k, c.idx, c.q, c.nq, nom, split_gemm_eps(c.dot, c.dim), c.oid, c.osc, s.flags, s.flags, c.st);
+}
+
+// The fused path of a chunk: thresholds from a row sample, the GEMM appending what falls below them, the re-score and the proof
+static int32_t flat_fused_chunk(const FlatCall &c, const FlatScratch &s)
+{
+    const vg_index *idx = c.idx;
+    const ProbeNominated &nom = s.nom;
+    NomCall nc = c.nom();
+    const bool split = gemm_runs_split(true, s.bf16, nc.ops.dma, c.nq, c.dim, nom.cap, nom.sel_k);
+    // ... behind a screen: the hi halves' product and the wide margin first, the split tile for the queries that leaves open
+    const bool screen = gemm_runs_screen(split, c.k);
+    const float eps_extra = screen ? screen_gemm_eps(c.dot, c.dim) : split ? split_gemm_eps(c.dot, c.dim) : s.bf16 ? bf16_filter_eps(c.dot) : 0.0f;
+    if (s.bf16) VG_TRY(gemm_operands(c.q, c.nq, c.dim, c.n, idx->d_norms, idx->d_vectors_bf16, idx->vectors_bf16_dim, s.qbf, c.st, &nc.ops));
+    // (a) threshold per query from a row sample
+    VG_TRY(sample_thresholds(nc, s, kFlatSampleStride, nom.sel_k, nom.thr, s.use_sample));
+    if (s.bf16 || split) VG_LAUNCH(flat_thr_cap_kernel, dim3(nc.ucnt()), dim3(64), 0, c.st, nom.thr, nom.sel_k, c.q, c.dim, idx->d_norm_max);
+    if (split)
+        VG_LAUNCH(flat_split_queries_kernel, dim3(static_cast<unsigned>((c.nq * (c.dim / 2) + 255) / 256)), dim3(256), 0, c.st, c.q, c.nq, c.dim,
+                  reinterpret_cast<uint32_t *>(s.qbf));
+    // (b) the GEMM, appending every element below its query's threshold.  The sampled tiles' scores are in `sc` already,
+    // bit for bit, where (a) ran the same tile: what passes there is appended from `sc` (which also sets the counters)
+    // and the GEMM leaves those tiles out — 63/64 of the elements (test hook kHookFlatRescoreSample: all of them again)
+    const bool once = s.use_sample && gemm_skips_sample(nc.ops.dma, c.nq, s.bf16, split);
+    if (!once) VG_HIP(hipMemsetAsync(nom.counts, 0, sizeof(int) * static_cast<size_t>(c.nq), c.st));
+    {
+        ProfScope prof(idx->ctx, "flat_gemm", c.st);
+        if (once)
+            VG_LAUNCH(flat_sample_append_kernel, dim3(nc.ucnt()), dim3(kSampleAppendThreads), 0, c.st, s.sc, s.cols, kFlatSampleStride, nom.thr,
+                      nom.sel_k, nom.sel_k - 1, nom.counts, nom.cand, nom.cap);
+        GemmArgs a = GemmArgs::append(nc, nom.thr, nom.sel_k, nom.counts, nom.cand, nom.cap);
+        a.wide(s.bf16 || split ? s.counts_wide : nullptr, idx->ctx->compute_units).skipping(once ? kFlatSampleStride : 0);
+        if (split) a.split_tile(reinterpret_cast<const uint32_t *>(s.qbf));
+        if (screen) a.screen_tile();
+        VG_TRY(launch_gemm<2>(a));
+    }
+    // (c) the kc best appended keys (k > kGemmMaxK: all of them go to the exact re-score), (d) the re-score and the proof
+    if (c.k <= kGemmMaxK) VG_TRY(launch_flat_pick(nom, c.nq, nullptr, c.st));
+    VG_TRY(launch_flat_verify(c.dot, c.k, idx, c.q, c.nq, nom, eps_extra, c.oid, c.osc, s.flags, nullptr, c.st));
+    return screen ? flat_screen_retry(c, nc, s) : VG_OK;
+}
+
+// test hook kHookFlatDebug: what the proofs and lists of the chunk at query q0 came to (waits for the stream)
+static void flat_debug_counts(const FlatCall &c, int64_t q0, const FlatScratch &s)
+{
+    std::vector<int> hf(c.nq), hc(c.nq);
+    (void)hipMemcpyAsync(hf.data(), s.flags, sizeof(int) * c.nq, hipMemcpyDeviceToHost, c.st);
+    (void)hipMemcpyAsync(hc.data(), s.nom.counts, sizeof(int) * c.nq, hipMemcpyDeviceToHost, c.st);
+    (void)hipStreamSynchronize(c.st);
+    int64_t nf = 0, csum = 0, cmax = 0;
+    for (int f : hf) nf += f != 0;
+    for (int n : hc) { csum += n; cmax = std::max<int64_t>(cmax, n); }
+    fprintf(stderr, "[vg_search_flat] chunk q0=%lld cnt=%lld: %lld queries failed the proof; "
+            "appended candidates avg %.1f max %lld\n", (long long)q0, (long long)c.nq, (long long)nf,
+            s.fused ? double(csum) / c.nq : 0.0, (long long)(s.fused ? cmax : 0));
+}
+
+// step 4 always launches, on the work list the proofs left behind (normally empty).  The exhaustive kernel keeps 64 keys per
+// wave: k > 64 comes in pages of 64, each page scanning for the keys after the previous page's last one
+static int32_t flat_fallback_pages(const FlatCall &c, const FlatScratch &s)
+{
+    const int *always = s.flags + s.qc;
+    const dim3 grid(static_cast<unsigned>(c.nq));
+    for (int off = 0; off < c.k; off += 64) {
+        const int kk = std::min(64, c.k - off);
+        VG_TRY(launch_flat_exact(c, s.todo, s.ex_slices, kk, s.fpartial, off ? s.min_keys : nullptr));
+        VG_TRY(launch_topk_merge(s.fpartial, c.nq, s.ex_slices, kk, c.dot, s.fid, s.fsc, c.st, s.flags, always));
+        if (c.k <= 64)
+            VG_LAUNCH(flat_patch_kernel, grid, dim3(64), 0, c.st, s.flags, always, c.k, s.fid, s.fsc, c.oid, c.osc);
+        else
+            VG_LAUNCH(flat_page_patch_kernel, grid, dim3(64), 0, c.st, s.flags, always, c.k, off, kk, c.dot, s.fid, s.fsc, c.oid, c.osc, s.min_keys);
+    }
+    return VG_OK;
+}
+
+// The GEMM paths: the batch in chunks of whole query tiles, each nominated and proved, its open queries scanned exhaustively
+static int32_t flat_gemm_search(const FlatCall &call, bool unfused)
+{
+    ArenaCall ar(call.idx->ctx, call.st);
+    const int i_all = ar.add(FlatScratch(call, unfused, nullptr).bytes);
+    VG_TRY(ar.commit());
+    const FlatScratch s(call, unfused, ar.get<char>(i_all));
+    int *always = s.flags + s.qc;  // test hook kHookFlatForceExact: run step 4 for every query
+    VG_HIP(hipMemsetAsync(always, hook(kHookFlatForceExact) ? 1 : 0, sizeof(int), call.st));
+    for (int64_t q0 = 0; q0 < call.nq; q0 += s.qc) {
+        const FlatCall c = call.range(q0, std::min(s.qc, call.nq - q0));
+        VG_TRY(s.fused ? flat_fused_chunk(c, s) : flat_unfused_chunk(c, s));
+        VG_TRY(launch_flat_todo(s.flags, always, static_cast<int>(c.nq), s.todo, c.idx->d_flat_stats, c.st));
+        if (hook(kHookFlatDebug)) flat_debug_counts(c, q0, s);
+        VG_TRY(flat_fallback_pages(c, s));
+    }
+    return VG_OK;
 }
 
 // vg_search_flat, and — with `mask` (a DEVICE pointer: bit i of byte i/8 of query q's mask at mask + q * mask_stride,
@@ -884,8 +1267,8 @@ VG_API int32_t vg_search_flat(vg_index *idx, const float *queries, int64_t nq, i
 // ("every wanted row not appended scores at or above the threshold"); the exhaustive fallback skips them too.
 // l2_scores: squared-L2 scores whatever the index's metric (vg_search_hnsw_brute on a Cosine index: hnsw's distance there is
 // 0.5 * squared L2, flat.Segment's is the dot product)
-int32_t vg::flat_search_masked(vg_index *idx, const float *queries, int64_t nq, int32_t k, const uint8_t *mask,
-                               int64_t mask_stride, uint32_t *ids, float *scores, void *stream, bool l2_scores, bool cand_replay)
+int32_t flat_search_masked(vg_index *idx, const float *queries, int64_t nq, int32_t k, const uint8_t *mask, int64_t mask_stride, uint32_t *ids,
+                           float *scores, void *stream, bool l2_scores, bool cand_replay)
 {
     VG_CHECK(idx, VG_ERR_INVALID_ARG, "vg_search_flat: NULL index");
     VG_CHECK(nq >= 0 && k >= 0, VG_ERR_INVALID_ARG, "vg_search_flat: negative nq or k");
@@ -893,303 +1276,41 @@ int32_t vg::flat_search_masked(vg_index *idx, const float *queries, int64_t nq, 
     VG_CHECK(idx->metric != VG_METRIC_HAMMING, VG_ERR_UNSUPPORTED, "unsupported metric for float32: Hamming");
     VG_CHECK(idx->n == 0 || idx->d_vectors, VG_ERR_NOT_READY, "vg_search_flat: index has no fp32 vectors");
     VG_CHECK(queries && ids && scores, VG_ERR_INVALID_ARG, "vg_search_flat: NULL buffer");
-    VG_CHECK(k <= vg::kFlatMaxK, VG_ERR_UNSUPPORTED, "vg_search_flat: k=%d exceeds %d", k, vg::kFlatMaxK);
-    const bool dot = idx->metric != VG_METRIC_L2 && !l2_scores;
-    const int64_t n = idx->n;
-    const int dim = idx->dim;
-    const int kc = 64;  // nominated candidates per query
+    VG_CHECK(k <= kFlatMaxK, VG_ERR_UNSUPPORTED, "vg_search_flat: k=%d exceeds %d", k, kFlatMaxK);
     // k beyond what 64 nominated candidates can prove: the fused GEMM path re-scores every appended row
     // (flat_verify_all_kernel); the unfused score-matrix variant (test hook) stops at 64
-    const bool unfused = vg::hook(vg::kHookFlatUnfused) && mask == nullptr;
-    const bool big_k_scan = k > vg::kGemmMaxK && unfused;  // unfused: 64 nominated candidates cannot prove k near 64
+    const bool unfused = hook(kHookFlatUnfused) && mask == nullptr;
     VG_CHECK(k <= 64 || !unfused, VG_ERR_UNSUPPORTED, "vg_search_flat: k=%d needs the fused GEMM path", k);
 
-    vg::SearchIO io;
-    VG_TRY(io.init(idx->ctx, stream, queries, static_cast<size_t>(nq) * dim, ids, scores, static_cast<size_t>(nq) * k));
-    const hipStream_t st = io.st;
-    const float *q = io.q.ptr;
-    uint32_t *oid = io.oid.ptr;
-    float *osc = io.osc.ptr;
-
-    if (n == 0) {
-        VG_TRY(vg::empty_results(nq, k, dot, oid, osc, st));
-    } else if (mask == nullptr && nq <= vg::kScanMaxBatch && k <= 64 && dim % 4 == 0 && dim <= 1024 && dim >= 64 && !vg::hook(vg::kHookFlatNoScan) &&
-               !vg::hook(vg::kHookFlatForceExact) && !unfused && (reinterpret_cast<uintptr_t>(idx->d_vectors) & 15) == 0) {
-        // small batch: HBM-bound exact scan, kScanQB queries per pass over the rows
-        const int slices = static_cast<int>(std::min<int64_t>(4 * idx->ctx->compute_units, std::max<int64_t>(1, n / 64)));
-        vg::ArenaCall ar(idx->ctx, st);
-        const int i_partial = ar.add(sizeof(uint64_t) * static_cast<size_t>(nq) * slices * k);
-        VG_TRY(ar.commit());
-        uint64_t *partial = ar.get<uint64_t>(i_partial);
-        const size_t lds = sizeof(float) * static_cast<size_t>(vg::kScanQB) * dim + 4 * 64 * sizeof(uint64_t) + 64;
-        for (int64_t q0 = 0; q0 < nq; q0 += vg::kScanQB) {
-            const int cnt = static_cast<int>(std::min<int64_t>(vg::kScanQB, nq - q0));
-            vg::ProfScope prof(idx->ctx, "flat_scan", st);
-            {
-                auto kern = dot ? vg::flat_scan_mq_kernel<true> : vg::flat_scan_mq_kernel<false>;
-                VG_LAUNCH(kern, dim3(slices), dim3(256), lds, st, idx->d_vectors, n, dim,
-                          q + q0 * dim, cnt, slices, k, partial + q0 * slices * k);
-            }
-        }
-        VG_TRY(vg::launch_topk_merge(partial, nq, slices, k, dot, oid, osc, st));
-        VG_LAUNCH(vg::flat_todo_kernel, dim3(1), dim3(256), 0, st, nullptr, nullptr, static_cast<int>(nq), nullptr,
-                  idx->d_flat_stats);
-    } else if (big_k_scan) {
-        // kGemmMaxK < k <= 64 on rows the register scan does not take (dim % 4, dim < 64 or > 1024): the
-        // exhaustive exact kernel for every query, one pass over the rows per query
-        const int ex_slices = static_cast<int>(std::min<int64_t>(256, std::max<int64_t>(1, n / 64)));
-        const int64_t qc = std::min<int64_t>(nq, 4096);
-        vg::ArenaCall ar(idx->ctx, st);
-        const int i_flags = ar.add(sizeof(int) * (static_cast<size_t>(qc) + 1));
-        const int i_todo = ar.add(sizeof(int) * (static_cast<size_t>(qc) + 1));
-        const int i_fpartial = ar.add(sizeof(uint64_t) * static_cast<size_t>(qc) * ex_slices * k);
-        VG_TRY(ar.commit());
-        int *flags = ar.get<int>(i_flags), *todo = ar.get<int>(i_todo);
-        uint64_t *fpartial = ar.get<uint64_t>(i_fpartial);
-        VG_HIP(hipMemsetAsync(flags, 0, sizeof(int) * static_cast<size_t>(qc), st));
-        VG_HIP(hipMemsetAsync(flags + qc, 1, sizeof(int), st));  // "every query" switch of flat_todo_kernel
-        for (int64_t q0 = 0; q0 < nq; q0 += qc) {
-            const int64_t cnt = std::min(qc, nq - q0);
-            VG_LAUNCH(vg::flat_todo_kernel, dim3(1), dim3(256), 0, st, flags, flags + qc, static_cast<int>(cnt), todo,
-                      idx->d_flat_stats);
-            const unsigned slots = static_cast<unsigned>(std::min<int64_t>(cnt, vg::kExactSlots));
-            {
-                auto kern = dot ? vg::flat_exact_kernel<true> : vg::flat_exact_kernel<false>;
-                VG_LAUNCH(kern, dim3(ex_slices, slots), dim3(256), 0, st, idx->d_vectors, n, dim,
-                          q + q0 * dim, todo, ex_slices, k, fpartial, nullptr, nullptr, 0);
-            }
-            VG_TRY(vg::launch_topk_merge(fpartial, cnt, ex_slices, k, dot, oid + q0 * k, osc + q0 * k, st));
-        }
-    } else {
-        const bool fused = !unfused;  // test hook: materialise the score matrix
-        const int cap = 4096;          // candidate keys per query (fused path)
-        // threshold = sample_j-th best score of the row sample: ~64 * sample_j rows pass it (k > 64: ~3k of them)
-        const int sample_j = k <= 64 ? 8 : std::min(64, std::max(8, (3 * k + 63) / 64));
-        const int sample_stride = 64;  // every 64th 128-row tile is sampled
-        const int64_t nt = (n + vg::kGemmBN - 1) / vg::kGemmBN;
-        const int64_t nst = (nt + sample_stride - 1) / sample_stride;  // sampled tiles
-        const int64_t ns = nst * vg::kGemmBN;                          // sampled columns
-        const bool use_sample = fused && n > cap;  // n <= cap: threshold +Inf, every row is appended
-
-        // query chunk: whole 128-query tiles; unfused keeps the score matrix <= 2 GiB
-        int64_t qc = fused ? 4096 : (int64_t(2) << 30) / (n * 4);
-        if (qc > 4096) qc = 4096;
-        if (qc >= vg::kGemmBM) qc = (qc / vg::kGemmBM) * vg::kGemmBM;
-        if (qc < 1) qc = 1;
-        if (qc > nq) qc = nq;
-        const int64_t sel_n = fused ? ns : n;
-        const int sel_slices = static_cast<int>(std::min<int64_t>(64, std::max<int64_t>(1, sel_n / 4096)));
-        const int sel_k = fused ? sample_j : kc;
-        const int ex_slices = static_cast<int>(std::min<int64_t>(256, std::max<int64_t>(1, n / 64)));
-
-        vg::ArenaCall ar(idx->ctx, st);
-        const int i_sc = ar.add(sizeof(float) * static_cast<size_t>(qc) * (fused ? (use_sample ? ns : 1) : n));
-        const int i_partial = ar.add(sizeof(uint64_t) * static_cast<size_t>(qc) * sel_slices * sel_k);
-        const int i_sid = ar.add(sizeof(uint32_t) * static_cast<size_t>(qc) * sel_k);
-        const int i_thr = ar.add(sizeof(float) * static_cast<size_t>(qc) * sel_k);
-        const int i_counts = ar.add(sizeof(int) * static_cast<size_t>(qc));
-        const int i_cand = ar.add(fused ? sizeof(uint64_t) * static_cast<size_t>(qc) * cap : 0);
-        const int i_cand_id = ar.add(sizeof(uint32_t) * static_cast<size_t>(qc) * kc);
-        const int i_cand_sc = ar.add(sizeof(float) * static_cast<size_t>(qc) * kc);
-        const int i_flags = ar.add(sizeof(int) * (static_cast<size_t>(qc) + 1));
-        const int i_todo = ar.add(sizeof(int) * (static_cast<size_t>(qc) + 1));
-        const int pk = std::min(k, 64);  // results per page of the exhaustive fallback
-        const int i_fpartial = ar.add(sizeof(uint64_t) * static_cast<size_t>(qc) * ex_slices * pk);
-        const int i_fid = ar.add(sizeof(uint32_t) * static_cast<size_t>(qc) * pk);
-        const int i_fsc = ar.add(sizeof(float) * static_cast<size_t>(qc) * pk);
-        const int i_minkeys = ar.add(sizeof(uint64_t) * static_cast<size_t>(qc));
-        // the bfloat16 filter (vg_index_enable_bf16_filter): the two nomination GEMMs read bf16 copies of the rows and
-        // of the queries; what they nominate is re-scored exactly as before and the proof widens its margin by the
-        // rounding the copies can introduce.  bfloat16 keeps 8 significant bits: rounding to nearest moves an operand
-        // by at most 2^-8 of its magnitude, a product q_i*x_i by at most (2^-7 + 2^-16)|q_i x_i|, the dot product by
-        // (2^-7 + 2^-16)|q||x| <= (2^-8 + 2^-17)(|q|^2 + |x|^2).  A Dot score is the dot product; an L2 score is
-        // |x|^2 - 2 q.x (norms from the fp32 rows), TWICE that: (2^-7 + 2^-16)(|q|^2 + |x|^2).  (r02 used the Dot
-        // bound for both — half of what L2 needs: ADVICE r02, tests/test_gpu_flat_bf16.py
-        // test_filter_worst_case_rounding.)  The verify kernels multiply eps_extra by |q|^2 + max|x|^2.
-        // (any dim: the copies' rows are padded with zeros to whole K steps, vectors_bf16_dim)
-        const bool bf16 = idx->d_vectors_bf16 != nullptr && fused && !vg::hook(vg::kHookFlatNoDma);
-        const int bdim = idx->vectors_bf16_dim;
-        const float bf16_eps = !bf16 ? 0.0f : (dot ? 0.00390625f : 0.0078125f) * 1.02f;
-        // without the filter, a chunk above 128 queries nominates on the split tile (gemm_runs_split, decided per chunk below: the
-        // margin grows by split_gemm_eps, the chunk's queries are written as a hi | lo image, the appends count in wide counters)
-        const bool may_split = vg::gemm_runs_split(fused, bf16, true, qc, dim, cap, sel_k);
-        const int i_qbf = ar.add(bf16 ? sizeof(uint16_t) * static_cast<size_t>(qc) * bdim : may_split ? sizeof(uint32_t) * static_cast<size_t>(qc) * dim : 0);
-        const int i_cwide = ar.add(bf16 || may_split ? sizeof(int) * static_cast<size_t>(qc) * vg::kCountLine : 0);
-        const int i_active = ar.add(may_split ? sizeof(uint32_t) : 0);  // the retry's query tiles (flat_retry_prepare_kernel)
-        VG_TRY(ar.commit());
-        uint16_t *qbf = ar.get<uint16_t>(i_qbf);
-        float *sc = ar.get<float>(i_sc), *thr = ar.get<float>(i_thr);
-        float *cand_sc = ar.get<float>(i_cand_sc), *fsc = ar.get<float>(i_fsc);
-        uint64_t *partial = ar.get<uint64_t>(i_partial), *fpartial = ar.get<uint64_t>(i_fpartial);
-        uint64_t *cand = ar.get<uint64_t>(i_cand);
-        uint64_t *min_keys = ar.get<uint64_t>(i_minkeys);
-        uint32_t *sid = ar.get<uint32_t>(i_sid), *cand_id = ar.get<uint32_t>(i_cand_id), *fid = ar.get<uint32_t>(i_fid);
-        int *counts = ar.get<int>(i_counts), *flags = ar.get<int>(i_flags), *todo = ar.get<int>(i_todo);
-        int *counts_wide = bf16 || may_split ? ar.get<int>(i_cwide) : nullptr;
-        uint32_t *tile_active = may_split ? ar.get<uint32_t>(i_active) : nullptr;
-
-        int *always = flags + qc;  // test hook kHookFlatForceExact: run step 4 for every query
-        VG_HIP(hipMemsetAsync(always, vg::hook(vg::kHookFlatForceExact) ? 1 : 0, sizeof(int), st));
-        for (int64_t q0 = 0; q0 < nq; q0 += qc) {
-            const int64_t cnt = std::min(qc, nq - q0);
-            const float *qp = q + q0 * dim;
-            const uint8_t *m0 = mask ? mask + q0 * mask_stride : nullptr;
-            const int64_t mt = (cnt + vg::kGemmBM - 1) / vg::kGemmBM;
-            const unsigned ucnt = static_cast<unsigned>(cnt);
-            // (test hook kHookFlatNoDma: force the register-staged GEMM)
-            const bool dma = dim % 4 == 0 && (reinterpret_cast<uintptr_t>(qp) & 15) == 0 &&
-                             (reinterpret_cast<uintptr_t>(idx->d_vectors) & 15) == 0 && !vg::hook(vg::kHookFlatNoDma);
-            const bool split = vg::gemm_runs_split(fused, bf16, dma, cnt, dim, cap, sel_k);
-            // ... behind a screen: the hi halves' product and the wide margin first, the split tile for the queries that leaves open
-            const bool screen = vg::gemm_runs_screen(split, k);
-            const float eps_extra = screen ? vg::screen_gemm_eps(dot, dim) : split ? vg::split_gemm_eps(dot, dim) : bf16_eps;
-            // operands of the nomination GEMMs
-            const float *ga = qp, *gb = idx->d_vectors;
-            int gdim = dim;
-            if (bf16) {
-                VG_LAUNCH(vg::f32_to_bf16_pad_kernel, dim3(static_cast<unsigned>((cnt * bdim + 255) / 256)), dim3(256), 0, st, qp,
-                          cnt, dim, bdim, qbf);
-                ga = reinterpret_cast<const float *>(qbf);
-                gb = reinterpret_cast<const float *>(idx->d_vectors_bf16);
-                gdim = bdim / 2;
-            }
-            if (fused) {
-                // (a) threshold per query from a row sample
-                if (use_sample) {
-                    VG_TRY(vg::launch_gemm<1>(dot, dma, static_cast<unsigned>(mt * ((nst + 7) / 8) * 8), st,
-                                              {ga, cnt, gb, n, gdim, idx->d_norms, sc, sample_stride, ns,
-                                               nullptr, 0, 0, nullptr, nullptr, 0, m0, mask_stride}, bf16));
-                    VG_LAUNCH(vg::flat_select_kernel, dim3(sel_slices, ucnt), dim3(vg::kSelThreads), 0, st, sc, ns,
-                              sel_slices, sel_k, partial);
-                    VG_TRY(vg::launch_topk_merge(partial, cnt, sel_slices, sel_k, false, sid, thr, st));
-                } else {
-                    VG_LAUNCH(vg::fill_f32_kernel, dim3(static_cast<unsigned>((cnt * sel_k + 255) / 256)), dim3(256),
-                              0, st, thr, cnt * sel_k, INFINITY);
-                }
-                if (bf16 || split) VG_LAUNCH(vg::flat_thr_cap_kernel, dim3(ucnt), dim3(64), 0, st, thr, sel_k, qp, dim, idx->d_norm_max);
-                if (split)
-                    VG_LAUNCH(vg::flat_split_queries_kernel, dim3(static_cast<unsigned>((cnt * (dim / 2) + 255) / 256)), dim3(256), 0, st, qp,
-                              cnt, dim, reinterpret_cast<uint32_t *>(qbf));
-                // (b) the GEMM, appending every element below its query's threshold.  The sampled tiles' scores are in `sc` already,
-                // bit for bit, where (a) ran the same tile: what passes there is appended from `sc` (which also sets the counters)
-                // and the GEMM leaves those tiles out — 63/64 of the elements (test hook kHookFlatRescoreSample: all of them again)
-                const bool once = use_sample && vg::gemm_skips_sample(dma, cnt, bf16, split);
-                if (!once) VG_HIP(hipMemsetAsync(counts, 0, sizeof(int) * static_cast<size_t>(cnt), st));
-                {
-                    vg::ProfScope prof(idx->ctx, "flat_gemm", st);
-                    if (once)
-                        VG_LAUNCH(vg::flat_sample_append_kernel, dim3(ucnt), dim3(vg::kSampleAppendThreads), 0, st, sc, ns, sample_stride,
-                                  thr, sel_k, sel_k - 1, counts, cand, cap);
-                    VG_TRY(vg::launch_gemm<2>(dot, dma, static_cast<unsigned>(mt * ((nt + 7) / 8) * 8), st,
-                                              {split ? reinterpret_cast<const float *>(qbf) : ga, cnt, gb, n, gdim, idx->d_norms, nullptr, 1, 0, thr,
-                                               sel_k, sel_k - 1, counts, cand, cap, m0, mask_stride, idx->ctx->compute_units,
-                                               bf16 || split ? counts_wide : nullptr, once ? sample_stride : 0, split, screen}, bf16));
-                }
-                // (c) the kc best appended keys (k > kGemmMaxK: all of them go to the exact re-score below)
-                if (k <= vg::kGemmMaxK)
-                    VG_LAUNCH(vg::flat_pick_kernel, dim3(ucnt), dim3(256), 0, st, cand, counts, cap, kc, cand_id, cand_sc, nullptr);
-            } else {
-                {
-                    vg::ProfScope prof(idx->ctx, "flat_gemm", st);
-                    VG_TRY(vg::launch_gemm<0>(dot, dma, static_cast<unsigned>(mt * ((nt + 7) / 8) * 8), st,
-                                              {qp, cnt, idx->d_vectors, n, dim, idx->d_norms, sc, 1, n, nullptr, 0, 0,
-                                               nullptr, nullptr, 0}));
-                }
-                {
-                    vg::ProfScope prof(idx->ctx, "flat_select", st);
-                    VG_LAUNCH(vg::flat_select_kernel, dim3(sel_slices, ucnt), dim3(vg::kSelThreads), 0, st, sc, n,
-                              sel_slices, kc, partial);
-                }
-                VG_TRY(vg::launch_topk_merge(partial, cnt, sel_slices, kc, false, cand_id, cand_sc, st));
-            }
-            const float *vthr = fused ? thr : nullptr;
-            if (fused && k > 64) {
-                const size_t sort_lds = sizeof(uint64_t) * static_cast<size_t>(cap);
-                auto vk = dot ? vg::flat_verify_sort_kernel<true> : vg::flat_verify_sort_kernel<false>;
-                VG_LAUNCH(vk, dim3(ucnt), dim3(256), sort_lds, st, idx->d_vectors, dim, qp, idx->d_norm_max, cand, counts, cap,
-                          k, oid + q0 * k, osc + q0 * k, flags, thr, sel_k, sel_k - 1, eps_extra);
-            } else if (fused && k > vg::kGemmMaxK) {
-                {
-                    auto kern = dot ? vg::flat_verify_all_kernel<true> : vg::flat_verify_all_kernel<false>;
-                    VG_LAUNCH(kern, dim3(ucnt), dim3(256), 0, st, idx->d_vectors, dim, qp,
-                              idx->d_norm_max, cand, counts, cap, k, oid + q0 * k, osc + q0 * k, flags, thr, sel_k,
-                              sel_k - 1, eps_extra);
-                }
-            } else {
-                auto kern = dot ? vg::flat_verify_kernel<true> : vg::flat_verify_kernel<false>;
-                VG_LAUNCH(kern, dim3(ucnt), dim3(256), 0, st, idx->d_vectors, n, dim, qp,
-                          idx->d_norm_max, cand_id, cand_sc, kc, k, oid + q0 * k, osc + q0 * k, flags, vthr,
-                          sel_k, sel_k - 1, counts, cap, eps_extra, nullptr);
-                // The retry behind a screen.  A query whose proof held is finished; for the others (normally none) the split tile
-                // runs on the 256-query tiles that hold one — launched ALWAYS, once per chunk: with no tile marked every workgroup
-                // returns at once — then the pick and the proof again, for the flagged queries only and with the split tile's margin.
-                // (test hook kHookFlatScreenFail: every screen proof counts as failed)
-                if (screen) {
-                    VG_LAUNCH(vg::flat_retry_prepare_kernel, dim3(1), dim3(vg::kBigBM), 0, st, flags, vg::hook(vg::kHookFlatScreenFail),
-                              static_cast<int>(cnt), thr, sel_k, sel_k - 1, counts, counts_wide, tile_active, idx->d_flat_stats);
-                    {
-                        vg::ProfScope prof(idx->ctx, "flat_retry", st);
-                        VG_TRY(vg::launch_gemm<2>(dot, dma, 0, st,
-                                                  {reinterpret_cast<const float *>(qbf), cnt, gb, n, gdim, idx->d_norms, nullptr, 1, 0, thr, sel_k,
-                                                   sel_k - 1, counts, cand, cap, m0, mask_stride, idx->ctx->compute_units, counts_wide, 0, true,
-                                                   false, tile_active}));
-                    }
-                    VG_LAUNCH(vg::flat_pick_kernel, dim3(ucnt), dim3(256), 0, st, cand, counts, cap, kc, cand_id, cand_sc, flags);
-                    VG_LAUNCH(kern, dim3(ucnt), dim3(256), 0, st, idx->d_vectors, n, dim, qp, idx->d_norm_max, cand_id, cand_sc, kc, k,
-                              oid + q0 * k, osc + q0 * k, flags, vthr, sel_k, sel_k - 1, counts, cap, vg::split_gemm_eps(dot, dim), flags);
-                }
-            }
-            // step 4 always launches, on the work list the proofs left behind (normally empty)
-            VG_LAUNCH(vg::flat_todo_kernel, dim3(1), dim3(256), 0, st, flags, always, static_cast<int>(cnt), todo,
-                      idx->d_flat_stats);
-            if (vg::hook(vg::kHookFlatDebug)) {
-                std::vector<int> hf(cnt), hc(cnt);
-                (void)hipMemcpyAsync(hf.data(), flags, sizeof(int) * cnt, hipMemcpyDeviceToHost, st);
-                (void)hipMemcpyAsync(hc.data(), counts, sizeof(int) * cnt, hipMemcpyDeviceToHost, st);
-                (void)hipStreamSynchronize(st);
-                int64_t nf = 0, csum = 0, cmax = 0;
-                for (int f : hf) nf += f != 0;
-                for (int c : hc) { csum += c; cmax = std::max<int64_t>(cmax, c); }
-                fprintf(stderr, "[vg_search_flat] chunk q0=%lld cnt=%lld: %lld queries failed the proof; "
-                        "appended candidates avg %.1f max %lld\n", (long long)q0, (long long)cnt, (long long)nf,
-                        fused ? double(csum) / cnt : 0.0, (long long)(fused ? cmax : 0));
-            }
-            // the exhaustive kernel keeps 64 keys per wave: k > 64 comes in pages of 64, each page scanning
-            // for the keys after the previous page's last one
-            const unsigned slots = static_cast<unsigned>(std::min<int64_t>(cnt, vg::kExactSlots));
-            for (int off = 0; off < k; off += 64) {
-                const int kk = std::min(64, k - off);
-                const uint64_t *floor_keys = off ? min_keys : nullptr;
-                {
-                    auto kern = dot ? vg::flat_exact_kernel<true> : vg::flat_exact_kernel<false>;
-                    VG_LAUNCH(kern, dim3(ex_slices, slots), dim3(256), 0, st, idx->d_vectors, n,
-                              dim, qp, todo, ex_slices, kk, fpartial, floor_keys, m0, mask_stride);
-                }
-                VG_TRY(vg::launch_topk_merge(fpartial, cnt, ex_slices, kk, dot, fid, fsc, st, flags, always));
-                if (k <= 64)
-                    VG_LAUNCH(vg::flat_patch_kernel, dim3(ucnt), dim3(64), 0, st, flags, always, k, fid, fsc,
-                              oid + q0 * k, osc + q0 * k);
-                else
-                    VG_LAUNCH(vg::flat_page_patch_kernel, dim3(ucnt), dim3(64), 0, st, flags, always, k, off, kk, dot, fid,
-                              fsc, oid + q0 * k, osc + q0 * k, min_keys);
-            }
-        }
-    }
+    SearchIO io;
+    VG_TRY(io.init(idx->ctx, stream, queries, static_cast<size_t>(nq) * idx->dim, ids, scores, static_cast<size_t>(nq) * k));
+    const bool dot = idx->metric != VG_METRIC_L2 && !l2_scores;
+    const FlatCall c{idx, k, io.st, dot, io.q.ptr, nq, mask, mask_stride, io.oid.ptr, io.osc.ptr};
+    const bool scan_small = mask == nullptr && nq <= kScanMaxBatch && k <= 64 && c.dim % 4 == 0 && c.dim <= 1024 && c.dim >= 64 &&
+                            !hook(kHookFlatNoScan) && !hook(kHookFlatForceExact) && !unfused && aligned16(idx->d_vectors);
+    if (c.n == 0)
+        VG_TRY(empty_results(nq, k, dot, c.oid, c.osc, c.st));
+    else if (scan_small)
+        VG_TRY(flat_scan_small(c));
+    else if (unfused && k > kGemmMaxK)
+        VG_TRY(flat_exact_every_query(c));
+    else
+        VG_TRY(flat_gemm_search(c, unfused));
     // queries whose scores may hold a NaN (a non-finite query value / row, an overflowing dot product): the reference's heap,
     // operation by operation (vg_cand_replay.hpp); every other query returns from this launch at once
-    if (n > 0 && cand_replay)
-        VG_TRY(vg::launch_cand_replay(vg::FlatF32Scorer{idx->d_vectors, idx->d_norm_max + 1, dim, dot, 0}, q, dim, n, nq, k, dot, mask, mask_stride,
-                                      oid, osc, st));
+    if (c.n > 0 && cand_replay)
+        VG_TRY(launch_cand_replay(FlatF32Scorer{idx->d_vectors, idx->d_norm_max + 1, c.dim, dot, 0}, c.q, c.dim, c.n, nq, k, dot, mask, mask_stride,
+                                  c.oid, c.osc, c.st));
     return io.finish();
 }
 
+// ---- the grouped nomination of the probed scans -------------------------------------------------------------------------------
 // The nomination + proof of vg_search_flat over MANY (queries, rows) problems in one set of launches: the partition-probed search
 // of k_probe.hip.  pair_queries: the (query, probe) pairs' query vectors bucketed by partition ([pairs, dim]); groups[g]: partition
 // g's pairs and rows; first_block_*: each group's first workgroup in the sample / main GEMM launch (device; the totals are not
 // known to the host: the grids are the host's upper bounds, surplus workgroups leave at once).  Per pair: ids / scores [pairs, k]
 // = its partition's k best rows by (score, row id) with exact scores, and fail[pair] = 1 where the proof does not hold (the caller
 // answers those queries with the exact probe kernels).  k <= kGemmMaxK; fp32 rows, dim % 4 == 0, 16-byte aligned.
-namespace vg {
 // thresholds kept per pair: the 8th best of the 1/8 row sample passes ~64 rows — enough for the 64-candidate re-score (k <= 48);
 // a larger k re-scores everything that passed and wants ~3k of them — ~5k under a bfloat16 nomination, whose proof needs the
 // threshold 2^-7 (|q|^2 + |x|^2) above the k-th score: at 3k, random-normal rows of dim 768 in partitions of 8192 failed the
@@ -1199,35 +1320,41 @@ int probe_gemm_sel_k(int k, bool bf16) { return k <= kGemmMaxK ? 8 : std::min(64
 // batch of 65535 pairs holds 1 GiB of them (4096, the flat search's, would be 2)
 constexpr int kProbeGemmCap = 2048;
 // (scratch: one piece of the caller's arena — the caller holds the arena for the call — carved here; the layout in one place)
-struct ProbeGemmLayout {
-    size_t sc, partial, sid, thr, counts, cand, cid, csc, qbf, total;
-    int sel_slices;
+struct ProbeGemmScratch : NomScratch {
+    uint16_t *qbf;  // bf16_dim > 0: the pairs' queries in bfloat16
+    ProbeGemmScratch(char *base, int64_t pairs, int64_t ns_max, int k, int bf16_dim)
+    {
+        Carve c{base};
+        carve(c, pairs, ns_max, probe_gemm_sel_k(k, bf16_dim > 0), kProbeGemmCap, true, select_slices(ns_max, 1024, 8));
+        c.take(qbf, pairs * bf16_dim);
+        bytes = c.off;
+    }
 };
-static ProbeGemmLayout probe_gemm_layout(int64_t pairs, int64_t ns_max, int k, int dim = 0 /* > 0: room for the pairs' queries in bfloat16 */)
+size_t flat_probe_gemm_scratch_bytes(int64_t pairs, int64_t ns_max, int k, int bf16_dim)
 {
-    constexpr int kc = 64, cap = kProbeGemmCap;
-    const int sel_k = probe_gemm_sel_k(k, dim > 0);
-    ProbeGemmLayout l;
-    l.sel_slices = static_cast<int>(std::min<int64_t>(8, std::max<int64_t>(1, ns_max / 1024)));
-    size_t at = 0;
-    auto piece = [&](size_t bytes) {
-        const size_t o = at;
-        at += (bytes + 255) & ~size_t(255);
-        return o;
-    };
-    l.sc = piece(sizeof(float) * static_cast<size_t>(pairs) * ns_max);
-    l.partial = piece(sizeof(uint64_t) * static_cast<size_t>(pairs) * l.sel_slices * sel_k);
-    l.sid = piece(sizeof(uint32_t) * static_cast<size_t>(pairs) * sel_k);
-    l.thr = piece(sizeof(float) * static_cast<size_t>(pairs) * sel_k);
-    l.counts = piece(sizeof(int) * static_cast<size_t>(pairs));
-    l.cand = piece(sizeof(uint64_t) * static_cast<size_t>(pairs) * cap);
-    l.cid = piece(sizeof(uint32_t) * static_cast<size_t>(pairs) * kc);
-    l.csc = piece(sizeof(float) * static_cast<size_t>(pairs) * kc);
-    l.qbf = piece(sizeof(uint16_t) * static_cast<size_t>(pairs) * dim);
-    l.total = at;
-    return l;
+    return ProbeGemmScratch(nullptr, pairs, ns_max, k, bf16_dim).bytes;
 }
-size_t flat_probe_gemm_scratch_bytes(int64_t pairs, int64_t ns_max, int k, int bf16_dim) { return probe_gemm_layout(pairs, ns_max, k, bf16_dim).total; }
+// One stage (MODE 1: sample, 2: append) over the groups: grid / first_block [MODE - 1] of the 128-query tiles (groups of more
+// than 64 pairs), [MODE + 1] of the 64-query tiles (flat_gemm_dma32_grouped_kernel<.., 2>: a group of at most 64 pairs is one
+// query tile, one workgroup per row tile, HBM-bound — a 128-query tile would spend the matrix cores on padding)
+template <int MODE>
+static int32_t launch_gemm_grouped(const GemmArgs &a, const GemmGroup *groups, int ngroups, const int64_t grid[4],
+                                   const int64_t *const first_block[4], const int64_t *mask_off)
+{
+    const NomCall &c = a.c;
+    return with_metric(c.dot, [&](auto dot_c) -> int32_t {
+        constexpr bool DOT = decltype(dot_c)::value;
+        const bool bf16 = c.ops.bf16;
+        auto launch = [&](auto kern, size_t lds, int at) -> int32_t {
+            return launch_lds(kern, dim3(static_cast<unsigned>(grid[at])), dim3(kGemmThreads), lds, c.st, groups, first_block[at], ngroups, a.queries,
+                              c.ops.b, c.ops.dim_words, c.ops.norms, a.scores, a.tile_stride, a.out_cols, a.thr, a.thr_stride, a.thr_off, a.counts, a.cand, a.cap,
+                              c.mask, mask_off);
+        };
+        VG_TRY(launch(bf16 ? flat_gemm_dma_grouped_kernel<DOT, MODE, true> : flat_gemm_dma_grouped_kernel<DOT, MODE>, kDmaLdsBytes, MODE - 1));
+        return launch(bf16 ? flat_gemm_dma32_grouped_kernel<DOT, MODE, kProbeRB, true> : flat_gemm_dma32_grouped_kernel<DOT, MODE, kProbeRB>,
+                      g32_lds_bytes<kProbeRB>(), MODE + 1);
+    });
+}
 
 int32_t flat_probe_gemm(vg_index *idx, const float *pair_queries, int64_t pairs, const GemmGroup *groups, const int64_t *const first_block[4],
                         int ngroups, const int64_t grid[4], int sample_stride, int64_t ns_max, int k, uint32_t *pair_ids,
@@ -1238,194 +1365,82 @@ int32_t flat_probe_gemm(vg_index *idx, const float *pair_queries, int64_t pairs,
     // img.rows != null: nominate on that bfloat16 row image (with its norms) instead of the fp32 rows, and leave the exact
     // re-score + proof to the caller: *nominated = where the per-pair thresholds / counts / 64 candidates are (the partition-probed
     // SQ8 scan, k_sq8_scan.hip)
-    // first_block / grid: [0] sample, [1] main launch of the 128-query tiles (groups of more than 64 pairs); [2], [3] the same of
-    // the 64-query tiles (flat_gemm_dma32_grouped_kernel<.., 2>: a group of at most 64 pairs is one query tile, one workgroup per
-    // row tile, HBM-bound — a 128-query tile would spend the matrix cores on padding)
-    const bool dot = idx->metric != VG_METRIC_L2;
-    const int dim = idx->dim;
     // (img.rows == idx->d_vectors_bf16: the fp32 rows' own bf16 filter, vg_index_enable_bf16_filter — the nomination runs on it,
     // the re-score and the proof below stay, the proof's margin widened as in vg_search_flat)
-    const bool bf16 = img.rows != nullptr;
-    const int kc = 64, cap = kProbeGemmCap, sel_k = probe_gemm_sel_k(k, bf16);
-    const bool own_filter = bf16 && img.rows == idx->d_vectors_bf16;
-    const float *const queries_f32 = pair_queries;
-    const int bdim = img.dim_pad;  // row length of the bfloat16 image
-    const ProbeGemmLayout l = probe_gemm_layout(pairs, ns_max, k, bdim);
-    const int sel_slices = l.sel_slices;
-    const float *grows = idx->d_vectors, *gnorms = idx->d_norms;
-    int gdim = idx->dim;
-    if (bf16) {
-        uint16_t *qbf = reinterpret_cast<uint16_t *>(scratch + l.qbf);
-        VG_LAUNCH(f32_to_bf16_pad_kernel, dim3(static_cast<unsigned>((pairs * bdim + 255) / 256)), dim3(256), 0, st, pair_queries,
-                  pairs, idx->dim, bdim, qbf);
-        pair_queries = reinterpret_cast<const float *>(qbf);
-        grows = reinterpret_cast<const float *>(img.rows);
-        gnorms = img.norms;
-        gdim = bdim / 2;
-    }
-    float *sc = reinterpret_cast<float *>(scratch + l.sc), *thr = reinterpret_cast<float *>(scratch + l.thr);
-    float *cand_sc = reinterpret_cast<float *>(scratch + l.csc);
-    uint64_t *partial = reinterpret_cast<uint64_t *>(scratch + l.partial), *cand = reinterpret_cast<uint64_t *>(scratch + l.cand);
-    uint32_t *sid = reinterpret_cast<uint32_t *>(scratch + l.sid), *cand_id = reinterpret_cast<uint32_t *>(scratch + l.cid);
-    int *counts = reinterpret_cast<int *>(scratch + l.counts);
-    const unsigned upairs = static_cast<unsigned>(pairs);
+    const bool dot = idx->metric != VG_METRIC_L2;
+    const bool bf16 = img.rows != nullptr, own_filter = bf16 && img.rows == idx->d_vectors_bf16;
+    const ProbeGemmScratch s(scratch, pairs, ns_max, k, img.dim_pad);
+    const ProbeNominated &nom = s.nom;
+    NomCall nc{st, dot, fp32_operands(idx, pair_queries), pairs, mask, 0};
+    if (bf16) VG_TRY(gemm_operands(pair_queries, pairs, idx->dim, idx->n, img.norms, img.rows, img.dim_pad, s.qbf, st, &nc.ops));
     // (a) a threshold per pair: the sel_k-th best score of every sample_stride-th row tile of its partition (columns no tile
     // writes — smaller partitions — hold +Inf)
-    VG_LAUNCH(fill_f32_kernel, dim3(static_cast<unsigned>((pairs * ns_max + 255) / 256)), dim3(256), 0, st, sc, pairs * ns_max, INFINITY);
-    {
-        auto kern = bf16 ? (dot ? flat_gemm_dma_grouped_kernel<true, 1, true> : flat_gemm_dma_grouped_kernel<false, 1, true>)
-                         : (dot ? flat_gemm_dma_grouped_kernel<true, 1> : flat_gemm_dma_grouped_kernel<false, 1>);
-        VG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   static_cast<int>(kDmaLdsBytes)));
-        if (grid[0])
-            VG_LAUNCH(kern, dim3(static_cast<unsigned>(grid[0])), dim3(kGemmThreads), kDmaLdsBytes, st, groups, first_block[0], ngroups,
-                      pair_queries, grows, gdim, gnorms, sc, sample_stride, ns_max, nullptr, 0, 0, nullptr, nullptr, 0, mask, mask_off);
-        auto kern32 = bf16 ? (dot ? flat_gemm_dma32_grouped_kernel<true, 1, kProbeRB, true> : flat_gemm_dma32_grouped_kernel<false, 1, kProbeRB, true>)
-                           : (dot ? flat_gemm_dma32_grouped_kernel<true, 1, kProbeRB> : flat_gemm_dma32_grouped_kernel<false, 1, kProbeRB>);
-        VG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern32), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   static_cast<int>(g32_lds_bytes<kProbeRB>())));
-        if (grid[2])
-            VG_LAUNCH(kern32, dim3(static_cast<unsigned>(grid[2])), dim3(kGemmThreads), g32_lds_bytes<kProbeRB>(), st, groups, first_block[2], ngroups,
-                      pair_queries, grows, gdim, gnorms, sc, sample_stride, ns_max, nullptr, 0, 0, nullptr, nullptr, 0, mask, mask_off);
-    }
-    VG_LAUNCH(flat_select_kernel, dim3(sel_slices, upairs), dim3(kSelThreads), 0, st, sc, ns_max, sel_slices, sel_k, partial);
-    VG_TRY(launch_topk_merge(partial, pairs, sel_slices, sel_k, false, sid, thr, st));
+    VG_LAUNCH(fill_f32_kernel, dim3(static_cast<unsigned>((pairs * ns_max + 255) / 256)), dim3(256), 0, st, s.sc, pairs * ns_max, INFINITY);
+    VG_TRY(launch_gemm_grouped<1>(GemmArgs::sample(nc, s.sc, sample_stride, ns_max), groups, ngroups, grid, first_block, mask_off));
+    VG_TRY(select_thresholds(s, pairs, nom.sel_k, s.sid, nom.thr, st));
     // (b) every element below its pair's threshold is appended to the pair's candidates
-    VG_HIP(hipMemsetAsync(counts, 0, sizeof(int) * static_cast<size_t>(pairs), st));
+    VG_HIP(hipMemsetAsync(nom.counts, 0, sizeof(int) * static_cast<size_t>(pairs), st));
     {
         ProfScope prof(idx->ctx, "flat_probe_gemm", st);
-        auto kern = bf16 ? (dot ? flat_gemm_dma_grouped_kernel<true, 2, true> : flat_gemm_dma_grouped_kernel<false, 2, true>)
-                         : (dot ? flat_gemm_dma_grouped_kernel<true, 2> : flat_gemm_dma_grouped_kernel<false, 2>);
-        VG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   static_cast<int>(kDmaLdsBytes)));
-        if (grid[1])
-            VG_LAUNCH(kern, dim3(static_cast<unsigned>(grid[1])), dim3(kGemmThreads), kDmaLdsBytes, st, groups, first_block[1], ngroups,
-                      pair_queries, grows, gdim, gnorms, nullptr, 1, 0, thr, sel_k, sel_k - 1, counts, cand, cap, mask, mask_off);
-        auto kern32 = bf16 ? (dot ? flat_gemm_dma32_grouped_kernel<true, 2, kProbeRB, true> : flat_gemm_dma32_grouped_kernel<false, 2, kProbeRB, true>)
-                           : (dot ? flat_gemm_dma32_grouped_kernel<true, 2, kProbeRB> : flat_gemm_dma32_grouped_kernel<false, 2, kProbeRB>);
-        VG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern32), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   static_cast<int>(g32_lds_bytes<kProbeRB>())));
-        if (grid[3])
-            VG_LAUNCH(kern32, dim3(static_cast<unsigned>(grid[3])), dim3(kGemmThreads), g32_lds_bytes<kProbeRB>(), st, groups, first_block[3], ngroups,
-                      pair_queries, grows, gdim, gnorms, nullptr, 1, 0, thr, sel_k, sel_k - 1, counts, cand, cap, mask, mask_off);
+        VG_TRY(launch_gemm_grouped<2>(GemmArgs::append(nc, nom.thr, nom.sel_k, nom.counts, nom.cand, nom.cap), groups, ngroups, grid, first_block,
+                                      mask_off));
     }
     // (c) the kc best of them, (d) re-scored exactly, the k best, and the proof against everything not nominated
     // (k > kGemmMaxK: every appended row is re-scored — flat_verify_all / _sort, as in vg_search_flat)
-    if (k <= kGemmMaxK) VG_LAUNCH(flat_pick_kernel, dim3(upairs), dim3(256), 0, st, cand, counts, cap, kc, cand_id, cand_sc, nullptr);
+    if (k <= kGemmMaxK) VG_TRY(launch_flat_pick(nom, pairs, nullptr, st));
     if (bf16 && !own_filter) {
-        nominated->thr = thr;
-        nominated->counts = counts;
-        nominated->cand_id = cand_id;
-        nominated->cand_sc = cand_sc;
-        nominated->cap = cap;
-        nominated->sel_k = sel_k;
-        nominated->cand = cand;
+        *nominated = nom;
         return VG_OK;
     }
-    const float eps_extra = own_filter ? (dot ? 0.00390625f : 0.0078125f) * 1.02f : 0.0f;
-    if (k > 64) {
-        auto vk = dot ? flat_verify_sort_kernel<true> : flat_verify_sort_kernel<false>;
-        VG_LAUNCH(vk, dim3(upairs), dim3(256), sizeof(uint64_t) * static_cast<size_t>(cap), st, idx->d_vectors, dim, queries_f32,
-                  idx->d_norm_max, cand, counts, cap, k, pair_ids, pair_scores, fail, thr, sel_k, sel_k - 1, eps_extra);
-    } else if (k > kGemmMaxK) {
-        auto vk = dot ? flat_verify_all_kernel<true> : flat_verify_all_kernel<false>;
-        VG_LAUNCH(vk, dim3(upairs), dim3(256), 0, st, idx->d_vectors, dim, queries_f32, idx->d_norm_max, cand, counts, cap, k, pair_ids,
-                  pair_scores, fail, thr, sel_k, sel_k - 1, eps_extra);
-    } else {
-        auto kern = dot ? flat_verify_kernel<true> : flat_verify_kernel<false>;
-        VG_LAUNCH(kern, dim3(upairs), dim3(256), 0, st, idx->d_vectors, idx->n, dim, queries_f32, idx->d_norm_max,
-                  cand_id, cand_sc, kc, k, pair_ids, pair_scores, fail, thr, sel_k, sel_k - 1, counts, cap, eps_extra, nullptr);
-    }
-    return VG_OK;
+    return launch_flat_verify(dot, k, idx, pair_queries, pairs, nom, own_filter ? bf16_filter_eps(dot) : 0.0f, pair_ids, pair_scores, fail, nullptr, st);
 }
-}  // namespace vg
 
+// ---- the nomination on a quantizer's bfloat16 image ---------------------------------------------------------------------------
 // The nomination stage of the fused flat search over ANY bfloat16 row image with its norms: thresholds from a row sample, the
 // bf16 MFMA GEMM appending what falls below them, the kc best per query — for a caller that re-scores and proves with its own
 // exact distance (nominated_pass, vg_nominate.hpp: rows = a quantizer's decoded rows rounded to bfloat16, norms = |x^|^2).
-// queries: cnt x dim fp32 (device), cnt <= 4096; img: n rows of img.dim_pad (dim rounded up to a multiple of 64, the tail zeros).  Outputs (device, caller's):
-// thr[cnt * sel_k] (the threshold is a query's last entry), counts[cnt], cand_id / cand_sc[cnt * 64] ascending (pick only).
-namespace vg {
-constexpr int kNomKc = 64, kNomCap = 4096, kNomStride = 64;
-struct NominateLayout {
-    size_t qbf, sc, partial, sid, cand, cwide, total;
-    int sel_slices;
-    int64_t ns;
-};
-static NominateLayout nominate_layout(int64_t cnt, int64_t n, int dim, int sel_k)
-{
-    NominateLayout l;
-    const int64_t nt = (n + kGemmBN - 1) / kGemmBN, nst = (nt + kNomStride - 1) / kNomStride;
-    l.ns = nst * kGemmBN;
-    l.sel_slices = static_cast<int>(std::min<int64_t>(64, std::max<int64_t>(1, l.ns / 4096)));
-    size_t at = 0;
-    auto piece = [&](size_t bytes) {
-        const size_t o = at;
-        at += (bytes + 255) & ~size_t(255);
-        return o;
-    };
-    l.qbf = piece(sizeof(uint16_t) * static_cast<size_t>(cnt) * dim);
-    l.sc = piece(sizeof(float) * static_cast<size_t>(cnt) * l.ns);
-    l.partial = piece(sizeof(uint64_t) * static_cast<size_t>(cnt) * l.sel_slices * sel_k);
-    l.sid = piece(sizeof(uint32_t) * static_cast<size_t>(cnt) * sel_k);
-    l.cand = piece(sizeof(uint64_t) * static_cast<size_t>(cnt) * kNomCap);
-    l.cwide = piece(sizeof(int) * static_cast<size_t>(cnt) * kCountLine);
-    l.total = at;
-    return l;
-}
-size_t flat_nominate_bf16_scratch(int64_t cnt, int64_t n, int dim_pad, int sel_k) { return nominate_layout(cnt, n, dim_pad, sel_k).total; }
-
-int32_t flat_nominate_bf16(vg_ctx *ctx, const NomImage &img, int64_t n, int dim, const float *queries, int64_t cnt, char *scratch,
-                           float *thr, int *counts, uint32_t *cand_id, float *cand_sc, hipStream_t st, bool dot, const uint8_t *mask,
-                           int64_t mask_stride, int sel_k, bool pick, const uint64_t **cand_keys, int *cap)
-{
-    // dot: scores are -q.x (the largest dot products first); mask: a row filter per query (mask + q * mask_stride) or for the
-    // batch (stride 0) — rejected rows are left out of the sample and of the candidates, as in flat_search_masked
-    // sel_k: thresholds kept per query (thr[cnt * sel_k], the last is the query's: ~64 * sel_k rows pass it); pick: the 64 best
-    // appended rows into cand_id / cand_sc; *cand_keys / *cap: every appended key, cap per query (in `scratch`)
-    // the queries are padded alike to the image's row length
-    const int dim_pad = img.dim_pad;
-    const float *norms = img.norms;
-    const NominateLayout l = nominate_layout(cnt, n, dim_pad, sel_k);
-    uint16_t *qbf = reinterpret_cast<uint16_t *>(scratch + l.qbf);
-    float *sc = reinterpret_cast<float *>(scratch + l.sc);
-    uint64_t *partial = reinterpret_cast<uint64_t *>(scratch + l.partial), *cand = reinterpret_cast<uint64_t *>(scratch + l.cand);
-    uint32_t *sid = reinterpret_cast<uint32_t *>(scratch + l.sid);
-    const int64_t mt = (cnt + kGemmBM - 1) / kGemmBM, nt = (n + kGemmBN - 1) / kGemmBN, nst = l.ns / kGemmBN;
-    VG_LAUNCH(f32_to_bf16_pad_kernel, dim3(static_cast<unsigned>((cnt * dim_pad + 255) / 256)), dim3(256), 0, st, queries, cnt, dim, dim_pad, qbf);
-    const float *ga = reinterpret_cast<const float *>(qbf), *gb = reinterpret_cast<const float *>(img.rows);
-    const int gdim = dim_pad / 2;
-    if (n > kNomCap) {
-        VG_TRY(launch_gemm<1>(dot, true, static_cast<unsigned>(mt * ((nst + 7) / 8) * 8), st,
-                              {ga, cnt, gb, n, gdim, norms, sc, kNomStride, l.ns, nullptr, 0, 0, nullptr, nullptr, 0, mask, mask_stride}, true));
-        VG_LAUNCH(flat_select_kernel, dim3(l.sel_slices, static_cast<unsigned>(cnt)), dim3(kSelThreads), 0, st, sc, l.ns, l.sel_slices,
-                  sel_k, partial);
-        VG_TRY(launch_topk_merge(partial, cnt, l.sel_slices, sel_k, false, sid, thr, st));
-    } else {
-        VG_LAUNCH(fill_f32_kernel, dim3(static_cast<unsigned>((cnt * sel_k + 255) / 256)), dim3(256), 0, st, thr, cnt * sel_k, INFINITY);
-    }
-    VG_LAUNCH(flat_thr_cap_kernel, dim3(static_cast<unsigned>(cnt)), dim3(64), 0, st, thr, sel_k, queries, dim, img.norm_max);
-    VG_HIP(hipMemsetAsync(counts, 0, sizeof(int) * static_cast<size_t>(cnt), st));
+// queries: cnt x idx->dim fp32 (device), cnt <= 4096; img: idx->n rows of img.dim_pad (dim rounded up to a multiple of 64, the tail
+// zeros).  dot: scores are -q.x (the largest dot products first); mask: a row filter per query (mask + q * mask_stride) or for the
+// batch (stride 0) — rejected rows are left out of the sample and of the candidates, as in flat_search_masked.
+// *nom (all of it in `scratch`): nominate_sel_k(k) thresholds per query (the last is the query's: ~64 * sel_k rows pass it), the
+// counts, every appended key, and — k <= kNomPickMaxK — the 64 best appended rows, ascending.
+struct NominateScratch : NomScratch {
+    uint16_t *qbf;  // the queries, padded like the image's rows
+    int *counts_wide;
+    NominateScratch(char *base, int64_t cnt, int64_t n, int dim_pad, int k)
     {
-        ProfScope prof(ctx, "sq8_nominate_gemm", st);
-        VG_TRY(launch_gemm<2>(dot, true, static_cast<unsigned>(mt * ((nt + 7) / 8) * 8), st,
-                              {ga, cnt, gb, n, gdim, norms, nullptr, 1, 0, thr, sel_k, sel_k - 1, counts, cand, kNomCap, mask, mask_stride,
-                               ctx->compute_units, reinterpret_cast<int *>(scratch + l.cwide)},
-                              true));
+        Carve c{base};
+        carve(c, cnt, sample_cols(n, kFlatSampleStride), nominate_sel_k(k), kFlatCap);
+        c.take(qbf, cnt * dim_pad);
+        c.take(counts_wide, cnt * kCountLine);
+        bytes = c.off;
     }
-    if (pick) VG_LAUNCH(flat_pick_kernel, dim3(static_cast<unsigned>(cnt)), dim3(256), 0, st, cand, counts, kNomCap, kNomKc, cand_id, cand_sc, nullptr);
-    *cand_keys = cand;
-    *cap = kNomCap;
-    return VG_OK;
-}
-}  // namespace vg
+};
+size_t flat_nominate_bf16_scratch(int64_t cnt, int64_t n, int dim_pad, int k) { return NominateScratch(nullptr, cnt, n, dim_pad, k).bytes; }
 
+int32_t flat_nominate_bf16(vg_index *idx, const NomImage &img, bool dot, const float *queries, int64_t cnt, const uint8_t *mask,
+                           int64_t mask_stride, int k, char *scratch, hipStream_t st, ProbeNominated *nom)
+{
+    const NominateScratch s(scratch, cnt, idx->n, img.dim_pad, k);
+    NomCall nc{st, dot, {}, cnt, mask, mask_stride};
+    VG_TRY(gemm_operands(queries, cnt, idx->dim, idx->n, img.norms, img.rows, img.dim_pad, s.qbf, st, &nc.ops));
+    *nom = s.nom;
+    VG_TRY(sample_thresholds(nc, s, kFlatSampleStride, nom->sel_k, nom->thr, idx->n > kFlatCap));
+    VG_LAUNCH(flat_thr_cap_kernel, dim3(nc.ucnt()), dim3(64), 0, st, nom->thr, nom->sel_k, queries, idx->dim, img.norm_max);
+    VG_HIP(hipMemsetAsync(nom->counts, 0, sizeof(int) * static_cast<size_t>(cnt), st));
+    {
+        ProfScope prof(idx->ctx, "sq8_nominate_gemm", st);
+        VG_TRY(launch_gemm<2>(GemmArgs::append(nc, nom->thr, nom->sel_k, nom->counts, nom->cand, nom->cap).wide(s.counts_wide, idx->ctx->compute_units)));
+    }
+    return k <= kNomPickMaxK ? launch_flat_pick(*nom, cnt, nullptr, st) : VG_OK;
+}
+
+// ---- the nomination of the threshold search -----------------------------------------------------------------------------------
 // The nomination of vg_search_flat_threshold (k_flat_threshold.hip) for batches: the caller's threshold folded into the fused GEMM.
 // Per query the append threshold (GEMM score form) is the user's — L2: t - |q|^2, Dot: -t — widened by the verify kernels' error
 // bound, or the sample threshold where that is lower; untight[q] = 1 where the user's stands (every row within it is appended
 // unless the list overflows), 0 where the sample tightened it, -1 where no bound holds (non-finite rows or query: the proof fails).
-// Outputs in the caller's buffers: gthr / qnorm / untight [cnt], counts [cnt], cand [cnt * cap] (GEMM keys).
-namespace vg {
+// Outputs (ThrNominated, in the scratch): gthr / qnorm / untight [cnt], counts [cnt], cand [cnt * cap] (GEMM keys).
 __global__ __launch_bounds__(64) void flat_thr_combine_kernel(const float *__restrict__ uthr, const float *__restrict__ sthr, int sel_k,
                                                               const float *__restrict__ queries, int dim, const float *__restrict__ norm_max,
                                                               float eps_extra, bool dot, float *__restrict__ gthr, float *__restrict__ qnorm,
@@ -1455,52 +1470,42 @@ __global__ __launch_bounds__(64) void flat_thr_combine_kernel(const float *__res
     gthr[q] = user ? ut : st;
     untight[q] = user ? 1 : 0;
 }
+// what the nomination keeps to itself: one piece of the caller's arena, for plan.qc queries
+struct ThrNomScratch : NomScratch {  // (nom.thr: the sample's thresholds)
+    ThrNominated out;
+    uint16_t *qbf;
+    int *counts_wide;
+    ThrNomScratch(char *base, const vg_index *idx, const ThrNomPlan &p, int64_t cnt)
+    {
+        Carve c{base};
+        carve(c, cnt, sample_cols(idx->n, p.sample_stride), p.sel_k, p.cap);
+        out.counts = nom.counts, out.cand = nom.cand;
+        c.take(out.gthr, cnt);
+        c.take(out.qnorm, cnt);
+        c.take(out.untight, cnt);
+        c.take(qbf, p.bf16 ? cnt * idx->vectors_bf16_dim : 0);
+        c.take(counts_wide, p.bf16 ? cnt * kCountLine : 0);
+        bytes = c.off;
+    }
+};
+size_t flat_thr_nominate_scratch(const vg_index *idx, const ThrNomPlan &p, int64_t qc) { return ThrNomScratch(nullptr, idx, p, qc).bytes; }
 
-int32_t flat_thr_nominate(vg_index *idx, hipStream_t st, const float *qp, const float *uthr, int64_t cnt, const uint8_t *m0,
-                          int64_t mask_stride, int cap, int sel_k, int sample_stride, bool bf16, float eps_extra, float *sc, uint64_t *partial,
-                          uint32_t *sid, float *sthr, uint16_t *qbf, int *counts_wide, float *gthr, float *qnorm, int *untight, int *counts,
-                          uint64_t *cand)
+int32_t flat_thr_nominate(vg_index *idx, const ThrNomPlan &p, const float *qp, const float *uthr, int64_t cnt, const uint8_t *m0,
+                          int64_t mask_stride, char *scratch, ThrNominated *nominated, hipStream_t st)
 {
+    const ThrNomScratch s(scratch, idx, p, cnt);
+    const ThrNominated &out = *nominated = s.out;
     const bool dot = idx->metric != VG_METRIC_L2;
-    const int64_t n = idx->n;
-    const int dim = idx->dim;
-    const int64_t mt = (cnt + kGemmBM - 1) / kGemmBM, nt = (n + kGemmBN - 1) / kGemmBN;
-    const int64_t nst = (nt + sample_stride - 1) / sample_stride, ns = nst * kGemmBN;
-    const int sel_slices = static_cast<int>(std::min<int64_t>(64, std::max<int64_t>(1, ns / 4096)));
-    const unsigned ucnt = static_cast<unsigned>(cnt);
-    const bool dma = dim % 4 == 0 && (reinterpret_cast<uintptr_t>(qp) & 15) == 0 && (reinterpret_cast<uintptr_t>(idx->d_vectors) & 15) == 0;
-    const float *ga = qp, *gb = idx->d_vectors;
-    int gdim = dim;
-    if (bf16) {
-        const int bdim = idx->vectors_bf16_dim;
-        VG_LAUNCH(f32_to_bf16_pad_kernel, dim3(static_cast<unsigned>((cnt * bdim + 255) / 256)), dim3(256), 0, st, qp, cnt, dim, bdim, qbf);
-        ga = reinterpret_cast<const float *>(qbf);
-        gb = reinterpret_cast<const float *>(idx->d_vectors_bf16);
-        gdim = bdim / 2;
-    }
-    const bool use_sample = n > cap;  // n <= cap: the list holds every row, the user's threshold stands
-    if (use_sample) {
-        VG_TRY(launch_gemm<1>(dot, dma || bf16, static_cast<unsigned>(mt * ((nst + 7) / 8) * 8), st,
-                              {ga, cnt, gb, n, gdim, idx->d_norms, sc, sample_stride, ns, nullptr, 0, 0, nullptr, nullptr, 0, m0, mask_stride}, bf16));
-        VG_LAUNCH(flat_select_kernel, dim3(sel_slices, ucnt), dim3(kSelThreads), 0, st, sc, ns, sel_slices, sel_k, partial);
-        VG_TRY(launch_topk_merge(partial, cnt, sel_slices, sel_k, false, sid, sthr, st));
-    }
-    VG_LAUNCH(flat_thr_combine_kernel, dim3(ucnt), dim3(64), 0, st, uthr, use_sample ? sthr : nullptr, sel_k, qp, dim, idx->d_norm_max,
-              eps_extra, dot, gthr, qnorm, untight);
-    VG_HIP(hipMemsetAsync(counts, 0, sizeof(int) * static_cast<size_t>(cnt), st));
+    NomCall nc{st, dot, fp32_operands(idx, qp), cnt, m0, mask_stride};
+    if (p.bf16) VG_TRY(gemm_operands(qp, cnt, idx->dim, idx->n, idx->d_norms, idx->d_vectors_bf16, idx->vectors_bf16_dim, s.qbf, st, &nc.ops));
+    const bool use_sample = idx->n > p.cap;  // n <= cap: the list holds every row, the user's threshold stands
+    if (use_sample) VG_TRY(sample_thresholds(nc, s, p.sample_stride, p.sel_k, s.nom.thr, true));
+    VG_LAUNCH(flat_thr_combine_kernel, dim3(nc.ucnt()), dim3(64), 0, st, uthr, use_sample ? s.nom.thr : nullptr, p.sel_k, qp, idx->dim, idx->d_norm_max,
+              p.eps_extra, dot, out.gthr, out.qnorm, out.untight);
+    VG_HIP(hipMemsetAsync(out.counts, 0, sizeof(int) * static_cast<size_t>(cnt), st));
     ProfScope prof(idx->ctx, "flat_thr_gemm", st);
-    VG_TRY(launch_gemm<2>(dot, dma || bf16, static_cast<unsigned>(mt * ((nt + 7) / 8) * 8), st,
-                          {ga, cnt, gb, n, gdim, idx->d_norms, nullptr, 1, 0, gthr, 1, 0, counts, cand, cap, m0, mask_stride,
-                           idx->ctx->compute_units, bf16 ? counts_wide : nullptr}, bf16));
-    return VG_OK;
+    return launch_gemm<2>(GemmArgs::append(nc, out.gthr, 1, out.counts, out.cand, p.cap).wide(p.bf16 ? s.counts_wide : nullptr, idx->ctx->compute_units));
 }
-
-int64_t flat_thr_sample_cols(int64_t n, int sample_stride)
-{
-    const int64_t nt = (n + kGemmBN - 1) / kGemmBN;
-    return (nt + sample_stride - 1) / sample_stride * kGemmBN;
-}
-static_assert(kCountLine == 32, "k_flat_threshold.hip sizes the counter lines as 32 ints");
 
 // the work list of the queries whose proof failed (todo[0] = how many, todo[1 ..] = which) and the statistics
 int32_t launch_flat_todo(const int *flags, const int *always, int cnt, int *todo, unsigned long long *stats, hipStream_t st)
@@ -1509,6 +1514,12 @@ int32_t launch_flat_todo(const int *flags, const int *always, int cnt, int *todo
     return VG_OK;
 }
 }  // namespace vg
+
+VG_API int32_t vg_search_flat(vg_index *idx, const float *queries, int64_t nq, int32_t k, uint32_t *ids,
+                              float *scores, void *stream)
+{
+    return vg::flat_search_masked(idx, queries, nq, k, nullptr, 0, ids, scores, stream);
+}
 
 namespace vg {
 int32_t append_bf16_rows(vg_index *idx, int64_t from, int64_t to, hipStream_t st)

@@ -233,8 +233,6 @@ __global__ void flat_thr_proof_kernel(int64_t cnt, const int *__restrict__ untig
     fail[q] = ok ? 0 : 1;
 }
 
-constexpr int kThrCountLine = 32;  // (kCountLine of k_flat.hip: the persistent bf16 tile's counter lines)
-
 __global__ void flat_thr_stats_kernel(unsigned long long *__restrict__ stats, long long searched, long long exact)
 {
     if (threadIdx.x == 0) {
@@ -274,8 +272,7 @@ VG_API int32_t vg_search_flat_threshold(vg_index *idx, const float *queries, int
     const bool force_exact = vg::hook(vg::kHookFlatForceExact);
     const bool nominate = n > 0 && !force_exact && (nq > vg::kThrQB || vg::hook(vg::kHookFlatNoScan));
     const bool bf16 = nominate && idx->d_vectors_bf16 != nullptr && !vg::hook(vg::kHookFlatNoDma);
-    // (the bfloat16 filter's share of the proof's margin: vg_search_flat's, k_flat.hip)
-    const float eps_extra = !bf16 ? 0.0f : (dot ? 0.00390625f : 0.0078125f) * 1.02f;
+    const float eps_extra = bf16 ? vg::bf16_filter_eps(dot) : 0.0f;
     // ~want rows pass the sample threshold: the sel_k-th best of every sample_stride-th 128-row tile passes ~sel_k * sample_stride
     // (the select kernels hold 64 keys: beyond 4096 rows the stride grows).  The bf16 proof's margin is ~2^-7 (|q|^2 + max|x|^2):
     // the sample threshold sits further from the max_results-th score.  The list holds 2x and more of what is expected to pass.
@@ -284,29 +281,18 @@ VG_API int32_t vg_search_flat_threshold(vg_index *idx, const float *queries, int
     const int sample_stride = static_cast<int>(std::max<int64_t>(64, (want + 63) / 64));
     int cap = 4096;  // appended rows per query
     while (cap < (bf16 ? 6 : 3) * max_results) cap <<= 1;
-    const int64_t ns = vg::flat_thr_sample_cols(n, sample_stride);
-    const int sel_slices = static_cast<int>(std::min<int64_t>(64, std::max<int64_t>(1, ns / 4096)));
     int64_t qc = std::min<int64_t>(4096, std::max<int64_t>(128, (int64_t(1) << 25) / cap));  // whole 128-query tiles, <= 2^25 keys
     qc = std::min<int64_t>(qc, nq);
     if (!nominate) qc = 0;
+    const vg::ThrNomPlan plan{cap, sel_k, sample_stride, bf16, eps_extra};
 
     vg::ArenaCall ar(idx->ctx, st);
     const int i_lists = ar.add(sizeof(uint64_t) * static_cast<size_t>(vg::kThrQB) * list_cap);
     const int i_cnt = ar.add(sizeof(int) * vg::kThrQB);
     const size_t uqc = static_cast<size_t>(qc);
-    const int i_sc = ar.add(sizeof(float) * uqc * ns);
-    const int i_partial = ar.add(sizeof(uint64_t) * uqc * sel_slices * sel_k);
-    const int i_sid = ar.add(sizeof(uint32_t) * uqc * sel_k);
-    const int i_sthr = ar.add(sizeof(float) * uqc * sel_k);
-    const int i_qbf = ar.add(bf16 ? sizeof(uint16_t) * uqc * idx->vectors_bf16_dim : 0);
-    const int i_cwide = ar.add(bf16 ? sizeof(int) * uqc * vg::kThrCountLine : 0);
-    const int i_gthr = ar.add(sizeof(float) * uqc);
-    const int i_qnorm = ar.add(sizeof(float) * uqc);
-    const int i_untight = ar.add(sizeof(int) * uqc);
-    const int i_gcounts = ar.add(sizeof(int) * uqc);
+    const int i_nom = ar.add(vg::flat_thr_nominate_scratch(idx, plan, qc));
     const int i_fail = ar.add(sizeof(int) * (uqc + 1));
     const int i_todo = ar.add(sizeof(int) * (uqc + 1));
-    const int i_cand = ar.add(sizeof(uint64_t) * uqc * cap);
     const int i_elist = ar.add(sizeof(uint64_t) * uqc * cap);
     const int i_ecount = ar.add(sizeof(int) * uqc);
     VG_TRY(ar.commit());
@@ -335,11 +321,8 @@ VG_API int32_t vg_search_flat_threshold(vg_index *idx, const float *queries, int
             VG_LAUNCH(vg::flat_thr_stats_kernel, dim3(1), dim3(64), 0, st, idx->d_flat_stats, static_cast<long long>(nq),
                       static_cast<long long>(force_exact ? nq : 0));
     } else {
-        float *sc = ar.get<float>(i_sc), *sthr = ar.get<float>(i_sthr), *gthr = ar.get<float>(i_gthr), *qnorm = ar.get<float>(i_qnorm);
-        uint64_t *partial = ar.get<uint64_t>(i_partial), *cand = ar.get<uint64_t>(i_cand), *elist = ar.get<uint64_t>(i_elist);
-        uint32_t *sid = ar.get<uint32_t>(i_sid);
-        uint16_t *qbf = ar.get<uint16_t>(i_qbf);
-        int *cwide = ar.get<int>(i_cwide), *untight = ar.get<int>(i_untight), *gcounts = ar.get<int>(i_gcounts);
+        uint64_t *elist = ar.get<uint64_t>(i_elist);
+        vg::ThrNominated nom;
         int *fail = ar.get<int>(i_fail), *todo = ar.get<int>(i_todo), *ecount = ar.get<int>(i_ecount);
         int *always = fail + qc;  // (flat_todo_kernel's "every query" switch: off)
         VG_HIP(hipMemsetAsync(always, 0, sizeof(int), st));
@@ -351,12 +334,11 @@ VG_API int32_t vg_search_flat_threshold(vg_index *idx, const float *queries, int
             float *os = io.osc.ptr + q0 * max_results;
             int32_t *oc = io.ocnt.ptr + q0;
             // (a) every row below the query's append threshold (the user's, widened, or the sample's) is appended
-            VG_TRY(vg::flat_thr_nominate(idx, st, qp, tp, c, m0, mask_stride, cap, sel_k, sample_stride, bf16, eps_extra, sc, partial, sid,
-                                         sthr, qbf, cwide, gthr, qnorm, untight, gcounts, cand));
+            VG_TRY(vg::flat_thr_nominate(idx, plan, qp, tp, c, m0, mask_stride, ar.get<char>(i_nom), &nom, st));
             // (b) re-scored exactly; the rows within the user's threshold form the query's list; (c) its best max_results
             {
                 vg::ProfScope prof(idx->ctx, "flat_thr_rescore", st);
-                VG_TRY(vg::launch_thr_rescore(dot, idx->d_vectors, dim, qp, tp, cand, gcounts, nullptr, c, cap, elist, ecount, st));
+                VG_TRY(vg::launch_thr_rescore(dot, idx->d_vectors, dim, qp, tp, nom.cand, nom.counts, nullptr, c, cap, elist, ecount, st));
             }
             {
                 vg::ProfScope prof(idx->ctx, "flat_thr_select", st);
@@ -365,7 +347,7 @@ VG_API int32_t vg_search_flat_threshold(vg_index *idx, const float *queries, int
             // (d) the proof; the queries it leaves go to the scan, kThrQB per pass over the rows
             VG_TRY(vg::with_metric(dot, [&](auto dot_c) -> int32_t {
                 VG_LAUNCH(vg::flat_thr_proof_kernel<decltype(dot_c)::value>, dim3(static_cast<unsigned>((c + 255) / 256)), dim3(256), 0, st, c,
-                          untight, gcounts, cap, gthr, qnorm, idx->d_norm_max, dim, eps_extra, max_results, oc, os, fail);
+                          nom.untight, nom.counts, cap, nom.gthr, nom.qnorm, idx->d_norm_max, dim, eps_extra, max_results, oc, os, fail);
                 return VG_OK;
             }));
             VG_TRY(vg::launch_flat_todo(fail, always, static_cast<int>(c), todo, idx->d_flat_stats, st));

@@ -455,7 +455,7 @@ struct ProbeNominated {
     float *cand_sc;
     int cap;               // appended keys kept per pair (counts above it: rows were dropped)
     int sel_k;
-    const uint64_t *cand;  // [pairs, cap]: every appended key (k > 48: all of them are re-scored)
+    uint64_t *cand;        // [pairs, cap]: every appended key (k > 48: all of them are re-scored)
 };
 constexpr int kProbeGemmMaxK = 160;  // deepest threshold: the 60th best of the 1/8 row sample, ~480 rows pass it
 // A bfloat16 row image the matrix-core nomination runs on (vg_nominate.hpp): a quantizer's DECODED rows rounded to bfloat16

@@ -24,10 +24,10 @@ inline int nominate_sel_k(int k) { return k <= kNomPickMaxK ? 8 : k <= 128 ? 16 
 
 struct GemmGroup;  // vg_flat_gemm.hpp
 // k_flat.hip
-size_t flat_nominate_bf16_scratch(int64_t cnt, int64_t n, int dim_pad, int sel_k);
-int32_t flat_nominate_bf16(vg_ctx *ctx, const NomImage &img, int64_t n, int dim, const float *queries, int64_t cnt, char *scratch,
-                           float *thr, int *counts, uint32_t *cand_id, float *cand_sc, hipStream_t st, bool dot, const uint8_t *mask,
-                           int64_t mask_stride, int sel_k, bool pick, const uint64_t **cand_keys, int *cap);
+// cnt queries' nomination for their k best on `img`, *nom and all it points to in `scratch` (flat_nominate_bf16_scratch bytes)
+size_t flat_nominate_bf16_scratch(int64_t cnt, int64_t n, int dim_pad, int k);
+int32_t flat_nominate_bf16(vg_index *idx, const NomImage &img, bool dot, const float *queries, int64_t cnt, const uint8_t *mask,
+                           int64_t mask_stride, int k, char *scratch, hipStream_t st, ProbeNominated *nom);
 size_t flat_probe_gemm_scratch_bytes(int64_t pairs, int64_t ns_max, int k, int bf16_dim);
 int32_t flat_probe_gemm(vg_index *idx, const float *pair_queries, int64_t pairs, const GemmGroup *groups, const int64_t *const first_block[4],
                         int ngroups, const int64_t grid[4], int sample_stride, int64_t ns_max, int k, uint32_t *pair_ids,
@@ -204,22 +204,14 @@ int32_t nominated_pass(vg_index *idx, const NomImage &img, bool dot, const float
     for (int64_t q0 = 0; q0 < nq; q0 += 4096) {
         const int64_t cnt = std::min<int64_t>(4096, nq - q0);
         ArenaCall ar(idx->ctx, st);
-        const int sel_k = nominate_sel_k(k);
-        const int i_scr = ar.add(flat_nominate_bf16_scratch(cnt, idx->n, img.dim_pad, sel_k));
-        const int i_thr = ar.add(sizeof(float) * static_cast<size_t>(cnt) * sel_k);
-        const int i_cnt = ar.add(sizeof(int) * static_cast<size_t>(cnt));
-        const int i_cid = ar.add(sizeof(uint32_t) * static_cast<size_t>(cnt) * 64);
-        const int i_csc = ar.add(sizeof(float) * static_cast<size_t>(cnt) * 64);
+        const int i_scr = ar.add(flat_nominate_bf16_scratch(cnt, idx->n, img.dim_pad, k));
         const int i_fail = ar.add(sizeof(int) * static_cast<size_t>(cnt));
         const int i_extra = ar.add(sizeof(float) * static_cast<size_t>(cnt) * extra_floats);
         VG_TRY(ar.commit());
-        float *thr = ar.get<float>(i_thr), *csc = ar.get<float>(i_csc);
-        int *counts = ar.get<int>(i_cnt), *fail = ar.get<int>(i_fail);
-        uint32_t *cid = ar.get<uint32_t>(i_cid);
+        int *fail = ar.get<int>(i_fail);
         const float *qq = q + q0 * idx->dim;
-        ProbeNominated nom{thr, counts, cid, csc, 0, sel_k, nullptr};
-        VG_TRY(flat_nominate_bf16(idx->ctx, img, idx->n, idx->dim, qq, cnt, ar.get<char>(i_scr), thr, counts, cid, csc, st, dot,
-                                  mask ? mask + q0 * mask_stride : nullptr, mask_stride, sel_k, k <= kNomPickMaxK, &nom.cand, &nom.cap));
+        ProbeNominated nom;
+        VG_TRY(flat_nominate_bf16(idx, img, dot, qq, cnt, mask ? mask + q0 * mask_stride : nullptr, mask_stride, k, ar.get<char>(i_scr), st, &nom));
         VG_TRY(verify(qq, cnt, nom, ar.get<float>(i_extra), oid + q0 * k, osc + q0 * k, fail));
         VG_TRY(failed_list(fail, cnt, q0, st, failed));
     }

@@ -52,12 +52,25 @@ int32_t launch_page_patch(int64_t nq, int k, int off, int kk, bool descending, c
 // cand_replay: the NaN replay of vg_cand_replay.hpp at the end (a caller that replays for itself passes false)
 int32_t flat_search_masked(vg_index *idx, const float *queries, int64_t nq, int32_t k, const uint8_t *mask, int64_t mask_stride,
                            uint32_t *ids, float *scores, void *stream, bool l2_scores = false, bool cand_replay = true);
-// the threshold search's nomination (k_flat_threshold.hip): sample columns, the GEMM passes, the proof's work list
-int64_t flat_thr_sample_cols(int64_t n, int sample_stride);
-int32_t flat_thr_nominate(vg_index *idx, hipStream_t st, const float *qp, const float *uthr, int64_t cnt, const uint8_t *m0,
-                          int64_t mask_stride, int cap, int sel_k, int sample_stride, bool bf16, float eps_extra, float *sc, uint64_t *partial,
-                          uint32_t *sid, float *sthr, uint16_t *qbf, int *counts_wide, float *gthr, float *qnorm, int *untight, int *counts,
-                          uint64_t *cand);
+// the bfloat16 filter's share of a proof's margin (a multiple of |q|^2 + max |x|^2)
+float bf16_filter_eps(bool dot);
+// The threshold search's nomination (k_flat_threshold.hip).  The plan: appended keys kept per query, thresholds kept per query,
+// every sample_stride-th row tile sampled, nomination on the bf16 filter's rows, the proof's extra margin.
+struct ThrNomPlan {
+    int cap, sel_k, sample_stride;
+    bool bf16;
+    float eps_extra;
+};
+// its outputs, in the scratch: [cnt] each, cand [cnt * cap] GEMM keys
+struct ThrNominated {
+    float *gthr, *qnorm;
+    int *untight, *counts;
+    uint64_t *cand;
+};
+// scratch: flat_thr_nominate_scratch bytes of the caller's arena, for chunks of up to qc queries
+size_t flat_thr_nominate_scratch(const vg_index *idx, const ThrNomPlan &plan, int64_t qc);
+int32_t flat_thr_nominate(vg_index *idx, const ThrNomPlan &plan, const float *qp, const float *uthr, int64_t cnt, const uint8_t *m0,
+                          int64_t mask_stride, char *scratch, ThrNominated *out, hipStream_t st);
 int32_t launch_flat_todo(const int *flags, const int *always, int cnt, int *todo, unsigned long long *stats, hipStream_t st);
 
 // ---- the threshold searches: k_flat_threshold.hip, k_probed_threshold.hip (and the large-k Vamana walk, k_graph.hip) ----
