@@ -552,6 +552,14 @@ func (r *Resident) FlatRetried() (int64, error) {
 	return int64(n), hipctx.Err(int32(st))
 }
 
+// FlatAppended: the candidates the fp32 flat search's nomination appended to its queries' lists since the rows were attached,
+// summed over the queries (thresholds set too high show as long lists here, too low as exhaustive queries in FlatStats).
+func (r *Resident) FlatAppended() (int64, error) {
+	var n C.int64_t
+	st := C.vg_index_flat_appended(r.h, &n, nil)
+	return int64(n), hipctx.Err(int32(st))
+}
+
 // SearchRaBitQ: exhaustive scan of the RaBitQ codes (rq.Distance per row).
 func (r *Resident) SearchRaBitQ(queries []float32, nq, k int) ([]uint32, []float32, error) {
 	ids, sc := r.out(nq, k)

@@ -105,7 +105,8 @@ extern "C" {
  *  threshold search over coded / partitioned flat segments: vg_search_flat_probed_threshold and
  *  vg_segment_search_threshold, found by symbol lookup.  Likewise the streaming Vamana index: vg_vamana_insert and
  *  vg_search_vamana_fresh, found by symbol lookup; and its delete path, vg_vamana_consolidate (with its caller-allocated
- *  vg_vamana_consolidate_stats), the same way.  Likewise vg_index_flat_retried, found by symbol lookup. */
+ *  vg_vamana_consolidate_stats), the same way.  Likewise vg_index_flat_retried and
+ *  vg_index_flat_appended, found by symbol lookup. */
 #define VG_ABI_MINOR 13
 #define VG_INVALID_ID 0xFFFFFFFFu
 #define VG_STREAM_LEGACY ((void *)1) /* == hipStreamLegacy */
@@ -709,6 +710,12 @@ int32_t vg_index_flat_stats(vg_index *idx, int64_t *queries, int64_t *exhaustive
  * not prove their answer and which the three-product pass nominated again.  A retried query is not an exhaustive one: it counts
  * in vg_index_flat_stats' second value only if its second proof fails too.  Synchronises the stream. */
 int32_t vg_index_flat_retried(vg_index *idx, int64_t *retried, void *stream);
+
+/* and one more: the sum over the queries of vg_search_flat's GEMM path since vg_index_set_vectors of the candidates the nomination
+ * appended to the query's list (a retried query: what its retry appended).  The thresholds come from a row sample; a wrong sample
+ * gives no wrong answer but a slow one — thresholds too low show in vg_index_flat_stats' second value, thresholds too high here.
+ * Found by symbol lookup, like vg_index_flat_retried.  Synchronises the stream. */
+int32_t vg_index_flat_appended(vg_index *idx, int64_t *appended, void *stream);
 
 /* exhaustive scan of the RaBitQ codes: RaBitQuantizer.Distance (rabitq.go:119-176) for every
  * row, best k by (Score, RowID).  The reference only scores RaBitQ codes node by node inside the

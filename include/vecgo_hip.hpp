@@ -648,6 +648,13 @@ public:
                                               r.ids.data(), r.scores.data(), r.counts.data(), nullptr));
         return r;
     }
+    // the candidates SearchFlat's nomination appended to its queries' lists since the rows were attached (vg_index_flat_appended)
+    int64_t FlatAppended()
+    {
+        int64_t n = 0;
+        check(vg_index_flat_appended(h_, &n, nullptr));
+        return n;
+    }
     // opt-in: nominate with a bfloat16 MFMA GEMM over a bf16 copy of the rows; results stay bit-identical (vecgo_hip.h)
     void EnableBF16Filter(bool on = true) { check(vg_index_enable_bf16_filter(h_, on ? 1 : 0, nullptr)); }
     // flat.Segment.Search PQ branch (flat/segment.go:476-483,678-689)

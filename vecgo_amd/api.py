@@ -1589,6 +1589,13 @@ class Index:
         check(self._lib.vg_index_flat_retried(self._h, C.byref(r), _stream_ptr(stream)))
         return r.value
 
+    def flat_appended(self, stream=None):
+        """vg_index_flat_appended: the candidates search_flat's nomination appended to its queries' lists since set_vectors, summed
+        over the queries of the GEMM path (long lists: thresholds too high; too low shows in flat_stats()[1])."""
+        r = C.c_int64(0)
+        check(self._lib.vg_index_flat_appended(self._h, C.byref(r), _stream_ptr(stream)))
+        return r.value
+
     def search_pq_adc(self, queries, k, out=None, stream=None):
         """flat.Segment.Search PQ branch (flat/segment.go:476-483,678-689,714-721)."""
         return self._search(self._lib.vg_search_pq_adc, queries, k, out=out, stream=stream)

@@ -206,12 +206,12 @@ VG_API int32_t vg_index_set_vectors(vg_index *idx, const float *base, void *stre
         VG_HIP(hipMalloc(reinterpret_cast<void **>(&idx->d_norms), static_cast<size_t>(idx->n) * sizeof(float)));
         VG_HIP(hipMalloc(reinterpret_cast<void **>(&idx->d_norm_max), 2 * sizeof(float)));  // [1]: max |x|, non-finite -> +Inf
         VG_HIP(hipMemsetAsync(idx->d_norm_max, 0, 2 * sizeof(float), st));
-        VG_HIP(hipMalloc(reinterpret_cast<void **>(&idx->d_flat_stats), 3 * sizeof(unsigned long long)));
+        VG_HIP(hipMalloc(reinterpret_cast<void **>(&idx->d_flat_stats), 4 * sizeof(unsigned long long)));
         VG_HIP(hipMemcpyAsync(idx->d_vectors, base, count * sizeof(float), hipMemcpyDefault, st));
         VG_LAUNCH(vg::row_norms_kernel, dim3(static_cast<unsigned>((idx->n + 3) / 4)), dim3(256),
                            0, st, idx->d_vectors, idx->n, idx->dim, idx->d_norms, reinterpret_cast<int *>(idx->d_norm_max + 1));
         VG_LAUNCH(vg::norm_max_kernel, dim3(1), dim3(1024), 0, st, idx->d_norms, idx->n, idx->d_norm_max);
-        VG_HIP(hipMemsetAsync(idx->d_flat_stats, 0, 3 * sizeof(unsigned long long), st));
+        VG_HIP(hipMemsetAsync(idx->d_flat_stats, 0, 4 * sizeof(unsigned long long), st));
         VG_HIP(hipStreamSynchronize(st));
         return VG_OK;
     }();

@@ -64,7 +64,8 @@ struct GemmArgs {
     // the sample itself (flat_sample_append_kernel).  Only where gemm_skips_sample() says so; 0: every tile.
     int skip_stride = 0;
     // MODE 2: the split tile (flat_gemm_split_big_kernel) — `queries` is flat_split_queries_kernel's image of the chunk, `base` the
-    // fp32 rows.  Set only where gemm_runs_split() says so (vg_search_flat's fused path).
+    // fp32 rows.  Set only where gemm_runs_split() says so (vg_search_flat's fused path).  MODE 1: the sample on the same tile
+    // (flat_gemm_sample_big_kernel), where sample_runs_big() says so.
     bool split = false;
     // with `split`: the screen (flat_gemm_screen_big_kernel), the product of the hi halves alone — where gemm_runs_screen() says so
     bool screen = false;
@@ -203,11 +204,14 @@ static int32_t launch_gemm_t(const GemmArgs &a)
     // the persistent 256 x 256 tile (bf16 images, or the split tile on the fp32 rows): one workgroup per CU, wide counters
     // (extra: the split tile's tile_active.  A retry's counters are flat_retry_prepare_kernel's to zero: those of the queries it
     // retries, the others keep what the screen counted)
-    auto launch_big = [&](auto kern, size_t lds, auto... extra) -> int32_t {
-        const int64_t bmt = (c.cnt + kBigBM - 1) / kBigBM, bnt = (c.ops.n + kBigBN - 1) / kBigBN;
+    auto big_grid = [&](int64_t bnt /* row tiles of 256 */) {
+        const int64_t bmt = (c.cnt + kBigBM - 1) / kBigBM;
         const int64_t slots = bmt * ((bnt + 7) / 8) * 8, per_cu = std::max(a.cus / 8, 1) * 8;  // (one workgroup per CU: LDS)
+        return dim3(static_cast<unsigned>(std::min(slots, per_cu)));
+    };
+    auto launch_big = [&](auto kern, size_t lds, auto... extra) -> int32_t {
         if (a.counts_wide && !a.tile_active) VG_HIP(hipMemsetAsync(a.counts_wide, 0, sizeof(int) * static_cast<size_t>(c.cnt) * kCountLine, st));
-        VG_TRY(launch_lds(kern, dim3(static_cast<unsigned>(std::min(slots, per_cu))), dim3(kBigThreads), lds, st, a.queries, c.cnt, c.ops.b, c.ops.n,
+        VG_TRY(launch_lds(kern, big_grid((c.ops.n + kBigBN - 1) / kBigBN), dim3(kBigThreads), lds, st, a.queries, c.cnt, c.ops.b, c.ops.n,
                           c.ops.dim_words, c.ops.norms, a.thr, a.thr_stride, a.thr_off, a.counts_wide ? a.counts_wide : a.counts, a.cand, a.cap, c.mask,
                           c.mask_stride, a.counts_wide ? kCountLine : 1, extra...));
         if (a.counts_wide)
@@ -224,6 +228,13 @@ static int32_t launch_gemm_t(const GemmArgs &a)
     auto launch_g32 = [&](auto kern, size_t lds) { return launch_tile(kern, dim3(static_cast<unsigned>(tiles)), lds); };
     constexpr int M = MODE == 0 ? 1 : MODE;
     const int rb = static_cast<int>((c.cnt + kG32BM - 1) / kG32BM);
+    if constexpr (MODE == 1) {
+        if (a.split) {  // the sample on the persistent tile: a row tile is a pair of sampled 128-row tiles
+            VG_CHECK(!bf16 && gemm_runs_split(true, false, dma, c.cnt, c.ops.dim_words, 0, 0), VG_ERR_INVALID_ARG, "launch_gemm: sample tile on a call without it");
+            return launch_lds(flat_gemm_sample_big_kernel<DOT, 3>, big_grid((tiles + 1) / 2), dim3(kBigThreads), big_lds_bytes<3>(), st, a.queries, c.cnt,
+                              c.ops.b, c.ops.n, c.ops.dim_words, c.ops.norms, a.scores, a.tile_stride, a.out_cols, c.mask, c.mask_stride);
+        }
+    }
     if (MODE == 2 && a.split) {
         VG_CHECK(!bf16 && gemm_runs_split(true, false, dma, c.cnt, c.ops.dim_words, a.cap, a.thr_stride), VG_ERR_INVALID_ARG, "launch_gemm: split tile on a call without it");
         if (a.screen) return launch_big(flat_gemm_screen_big_kernel<DOT, 3>, big_lds_bytes<3>());
@@ -295,12 +306,14 @@ __global__ void flat_split_queries_kernel(const float *__restrict__ src, int64_t
 
 // After the proofs: the work list of step 4 (todo[0] = how many queries need the exhaustive scan,
 // todo[1 + j] = the j-th of them, ascending) and the bookkeeping for vg_index_flat_stats
-// (stats[0] += queries of the chunk, stats[1] += those sent to the exhaustive kernel).
+// (stats[0] += queries of the chunk, stats[1] += those sent to the exhaustive kernel; counts, or null: stats[3] += the sum of
+// the chunk's candidate counts, what the fused path appended — vg_index_flat_appended).
 __global__ __launch_bounds__(256) void flat_todo_kernel(const int *__restrict__ flags, const int *__restrict__ always,
                                                         int cnt, int *__restrict__ todo,
-                                                        unsigned long long *__restrict__ stats)
+                                                        unsigned long long *__restrict__ stats, const int *__restrict__ counts)
 {
     __shared__ int part[256];
+    __shared__ unsigned long long appended[256];
     const int tid = threadIdx.x;
     const int per = (cnt + 255) / 256;
     const int lo = tid * per < cnt ? tid * per : cnt, hi = lo + per < cnt ? lo + per : cnt;
@@ -310,17 +323,25 @@ __global__ __launch_bounds__(256) void flat_todo_kernel(const int *__restrict__ 
     }
     const bool all = *always != 0;
     int mine = 0;
-    for (int i = lo; i < hi; i++) mine += (all || flags[i] != 0);
+    unsigned long long app = 0;
+    for (int i = lo; i < hi; i++) {
+        mine += (all || flags[i] != 0);
+        if (counts) app += static_cast<unsigned long long>(counts[i]);
+    }
     part[tid] = mine;
+    appended[tid] = app;
     __syncthreads();
     if (tid == 0) {
         int run = 0;
+        app = 0;
         for (int t = 0; t < 256; t++) {
             const int c = part[t];
             part[t] = run;
             run += c;
+            app += appended[t];
         }
         todo[0] = run;
+        if (counts) atomicAdd(&stats[3], app);
         atomicAdd(&stats[0], static_cast<unsigned long long>(cnt));
         atomicAdd(&stats[1], static_cast<unsigned long long>(run));
     }
@@ -807,6 +828,24 @@ static bool gemm_runs_screen(bool split, int k)
 {
     return split && !hook(kHookFlatNoScreen) && k <= (hook(kHookFlatScreenFail) ? kGemmMaxK : kScreenMaxK);
 }
+// Whether the threshold sample of a chunk (sample_thresholds) runs on the persistent tile too (flat_gemm_sample_big_kernel: the
+// screen's operands, one product q_hi.x_hi) instead of the fp32 128 x 128 tile: exactly where the chunk nominates on the split
+// tile (gemm_runs_split's answer, with or without the screen) and has a sample.  The ONE place that decides.  The sampled scores
+// need no error bound and no margin follows them (screen_gemm_eps, split_gemm_eps are untouched): they only CHOOSE a threshold.
+// Whatever it is, the nomination GEMM appends every row ITS score puts below it and the proofs argue from that threshold and that
+// GEMM's margin; on these paths gemm_skips_sample() is false, so no sampled score becomes an appended key.  A threshold a
+// little off costs time only: too low, a proof fails and the retry or the exhaustive kernel answers; too high, longer lists
+// (vg_index_flat_appended shows both).  Values bfloat16 cannot hold: a row with |x| >= 2^128 (1 - 2^-9), an Inf or a NaN makes
+// sample scores Inf or NaN (the fp32 sample: the same for Inf and NaN, finite or Inf for the first).  flat_select_kernel and
+// topk_merge_kernel order scores by make_key's bits, as they do today: a NaN with the sign bit sorts below -Inf, one without above
+// +Inf, so a NaN may become a threshold; flat_thr_cap_kernel replaces a NaN or an Inf by its bound, and where the bound itself is
+// not finite the tile's +-1e30 clamp stands in.  Such a row has |x|^2 = Inf or NaN: d_norm_max is not finite, no proof holds, and
+// the exhaustive kernel or the heap replay answers as before this kernel.
+// (test hook kHookFlatF32Sample: the fp32 128 x 128 sample as before)
+static bool sample_runs_big(bool split, bool use_sample)
+{
+    return split && use_sample && !hook(kHookFlatF32Sample);
+}
 constexpr int kScanMaxBatch = 4;  // ... and the batch size up to which the scan beats the 32-query GEMM tile
 template <bool DOT>
 __global__ __launch_bounds__(256) void flat_scan_mq_kernel(const float *__restrict__ base, int64_t n, int dim,
@@ -966,13 +1005,18 @@ static int32_t select_thresholds(const NomScratch &s, int64_t cnt, int sel_k, ui
 }
 // (a) of a nomination: a query's thresholds are the sel_k best scores of a row sample (every stride-th row tile; rows its filter
 // rejects score +Inf), the last of them its append threshold; not `sampled` (few rows: the list holds them all): +Inf
-static int32_t sample_thresholds(const NomCall &c, const NomScratch &s, int stride, int sel_k, float *thr, bool sampled)
+// (image: the sample on the persistent tile, from flat_split_queries_kernel's image of the queries, one workgroup on each of
+// the `cus` compute units — sample_runs_big)
+static int32_t sample_thresholds(const NomCall &c, const NomScratch &s, int stride, int sel_k, float *thr, bool sampled, const uint32_t *image = nullptr,
+                                 int cus = 0)
 {
     if (!sampled) {
         VG_LAUNCH(fill_f32_kernel, dim3(static_cast<unsigned>((c.cnt * sel_k + 255) / 256)), dim3(256), 0, c.st, thr, c.cnt * sel_k, INFINITY);
         return VG_OK;
     }
-    VG_TRY(launch_gemm<1>(GemmArgs::sample(c, s.sc, stride, s.cols)));
+    GemmArgs a = GemmArgs::sample(c, s.sc, stride, s.cols);
+    if (image) a.split_tile(image).wide(nullptr, cus);
+    VG_TRY(launch_gemm<1>(a));
     return select_thresholds(s, c.cnt, sel_k, s.sid, thr, c.st);
 }
 static int32_t launch_flat_pick(const ProbeNominated &nom, int64_t cnt, const int *only, hipStream_t st)
@@ -1181,12 +1225,15 @@ static int32_t flat_fused_chunk(const FlatCall &c, const FlatScratch &s)
     const bool screen = gemm_runs_screen(split, c.k);
     const float eps_extra = screen ? screen_gemm_eps(c.dot, c.dim) : split ? split_gemm_eps(c.dot, c.dim) : s.bf16 ? bf16_filter_eps(c.dot) : 0.0f;
     if (s.bf16) VG_TRY(gemm_operands(c.q, c.nq, c.dim, c.n, idx->d_norms, idx->d_vectors_bf16, idx->vectors_bf16_dim, s.qbf, c.st, &nc.ops));
-    // (a) threshold per query from a row sample
-    VG_TRY(sample_thresholds(nc, s, kFlatSampleStride, nom.sel_k, nom.thr, s.use_sample));
-    if (s.bf16 || split) VG_LAUNCH(flat_thr_cap_kernel, dim3(nc.ucnt()), dim3(64), 0, c.st, nom.thr, nom.sel_k, c.q, c.dim, idx->d_norm_max);
+    // (the split tile's image of the queries first: where sample_runs_big() says so, the sample reads it too)
+    const uint32_t *image = reinterpret_cast<const uint32_t *>(s.qbf);
     if (split)
         VG_LAUNCH(flat_split_queries_kernel, dim3(static_cast<unsigned>((c.nq * (c.dim / 2) + 255) / 256)), dim3(256), 0, c.st, c.q, c.nq, c.dim,
                   reinterpret_cast<uint32_t *>(s.qbf));
+    // (a) threshold per query from a row sample
+    VG_TRY(sample_thresholds(nc, s, kFlatSampleStride, nom.sel_k, nom.thr, s.use_sample, sample_runs_big(split, s.use_sample) ? image : nullptr,
+                             idx->ctx->compute_units));
+    if (s.bf16 || split) VG_LAUNCH(flat_thr_cap_kernel, dim3(nc.ucnt()), dim3(64), 0, c.st, nom.thr, nom.sel_k, c.q, c.dim, idx->d_norm_max);
     // (b) the GEMM, appending every element below its query's threshold.  The sampled tiles' scores are in `sc` already,
     // bit for bit, where (a) ran the same tile: what passes there is appended from `sc` (which also sets the counters)
     // and the GEMM leaves those tiles out — 63/64 of the elements (test hook kHookFlatRescoreSample: all of them again)
@@ -1254,7 +1301,7 @@ static int32_t flat_gemm_search(const FlatCall &call, bool unfused)
     for (int64_t q0 = 0; q0 < call.nq; q0 += s.qc) {
         const FlatCall c = call.range(q0, std::min(s.qc, call.nq - q0));
         VG_TRY(s.fused ? flat_fused_chunk(c, s) : flat_unfused_chunk(c, s));
-        VG_TRY(launch_flat_todo(s.flags, always, static_cast<int>(c.nq), s.todo, c.idx->d_flat_stats, c.st));
+        VG_TRY(launch_flat_todo(s.flags, always, static_cast<int>(c.nq), s.todo, c.idx->d_flat_stats, c.st, s.fused ? s.nom.counts : nullptr));
         if (hook(kHookFlatDebug)) flat_debug_counts(c, q0, s);
         VG_TRY(flat_fallback_pages(c, s));
     }
@@ -1508,9 +1555,10 @@ int32_t flat_thr_nominate(vg_index *idx, const ThrNomPlan &p, const float *qp, c
 }
 
 // the work list of the queries whose proof failed (todo[0] = how many, todo[1 ..] = which) and the statistics
-int32_t launch_flat_todo(const int *flags, const int *always, int cnt, int *todo, unsigned long long *stats, hipStream_t st)
+// (counts, or null: the chunk's candidate counts, for vg_index_flat_appended)
+int32_t launch_flat_todo(const int *flags, const int *always, int cnt, int *todo, unsigned long long *stats, hipStream_t st, const int *counts)
 {
-    VG_LAUNCH(flat_todo_kernel, dim3(1), dim3(256), 0, st, flags, always, cnt, todo, stats);
+    VG_LAUNCH(flat_todo_kernel, dim3(1), dim3(256), 0, st, flags, always, cnt, todo, stats, counts);
     return VG_OK;
 }
 }  // namespace vg
@@ -1532,6 +1580,19 @@ int32_t append_bf16_rows(vg_index *idx, int64_t from, int64_t to, hipStream_t st
     return VG_OK;
 }
 }  // namespace vg
+
+VG_API int32_t vg_index_flat_appended(vg_index *idx, int64_t *appended, void *stream)
+{
+    VG_CHECK(idx && appended, VG_ERR_INVALID_ARG, "vg_index_flat_appended: NULL index or pointer");
+    VG_CHECK(idx->d_flat_stats, VG_ERR_INVALID_ARG, "vg_index_flat_appended: no fp32 vectors attached");
+    VG_HIP(hipSetDevice(idx->ctx->device));
+    hipStream_t st = vg::pick_stream(idx->ctx, stream);
+    unsigned long long h = 0;
+    VG_HIP(hipMemcpyAsync(&h, idx->d_flat_stats + 3, sizeof h, hipMemcpyDeviceToHost, st));
+    VG_HIP(hipStreamSynchronize(st));
+    *appended = static_cast<int64_t>(h);
+    return VG_OK;
+}
 
 VG_API int32_t vg_index_enable_bf16_filter(vg_index *idx, int32_t on, void *stream)
 {

@@ -606,7 +606,8 @@ __global__ __launch_bounds__(kGemmThreads) void flat_gemm_dma_grouped_kernel(
 //    eight extra matrix instructions per tile on a 3-way bfloat16 split of t/2 against ones and of -|x|^2/2 — so that
 //    score < t  <=>  accumulator > 0, found with 8 v_max3 per 16 scores; only a (wave, 32 x 32 block) with a hit looks at its
 //    elements.  (fma + compare + branch per score cost 0.35 of 1.78 ms.)  The appended key's score is t - 2 acc (t - acc);
-//  * MODE 2 only (the append): the row sample of MODE 1 is 1/64 of the work and stays on the 128 x 128 tile.
+//  * MODE 2 (the append); the row sample of MODE 1, 1/64 of the work, has a score-writing form of the body for the fp32 rows
+//    (SAMPLE, below: it took 12 % of the screen's time on the 128 x 128 fp32 tile) and stays on the 128 x 128 tile elsewhere.
 // The scores differ from the 128-tile kernel's by roundings only (the accumulation starts from another value): they are a filter
 // whose error bound does not depend on the order (flat_verify_kernel's eps_extra).
 // WAR / RAW on the tiles as MI355X_MICROARCH.md prescribes for LDS-DMA: a wave waits for its own pieces (counted vmcnt), then the
@@ -664,20 +665,35 @@ __device__ __forceinline__ void split2_bf16(float a, float b, uint32_t &hi, uint
 // the others as it passes over the row-tile holes, and a workgroup that is left with no slot returns before it touches LDS
 // (vg_search_flat's retry of the queries whose screen proof failed).  One word: at most 32 query tiles (the launcher checks).
 enum { kBigImages = 0, kBigSplit = 1, kBigScreen = 2 };
-template <bool DOT, int NB, int PROBE, int OPS>
+// SAMPLE (flat_gemm_sample_big_kernel): the score-writing form, MODE 1 of the 128 x 128 tiles on this tile — the rows are every
+// tile_stride-th 128-row tile, written compactly into scores[q][out_cols] as the 128-row kernels write them, so a 256-row tile
+// is a PAIR of sampled 128-row tiles: sample tile ts takes rows [(2 ts) stride 128, + 128) through fill pieces 0-1 and rows
+// [(2 ts + 1) stride 128, + 128) through pieces 2-3, its output columns are ts * 256 ...  Only set_b / fill_b know of the two
+// halves; fills, swizzle, ring, K loop, waits and barrier are the append form's.  A half that does not exist (an odd number of
+// sampled tiles) re-reads the first half, rows past n their half's last row: such columns hold +Inf, none is written at or past
+// out_cols.  The accumulators start at zero and the epilogue writes what gemm_epilogue's MODE 1 writes, fma(-2, acc, |x|^2)
+// (Dot: -acc), +Inf for a row the query's filter rejects: no thresholds, no parked appends, no atomics.  A tile's stores are 128
+// per lane, for a fixed accumulator register the 32 lanes of a half-wave 32 consecutive columns of one query (128-byte runs).
+// They sit in front of the next tile's fills in the vector-memory queue (in-order retirement): a workgroup with a further tile
+// waits at the end of that tile's first K step for its 256 KiB to reach the L2 — at most the time the device takes to write one
+// sample (64 MB at 1024 queries x 1M rows: ~15 us) per 1024 queries, against the 128 x 128 fp32 sample's 237 us for the same.
+template <bool DOT, int NB, int PROBE, int OPS, bool SAMPLE = false>
 __device__ __forceinline__ void flat_gemm_big_body(
     const float *__restrict__ queries, int64_t nq, const float *__restrict__ base, int64_t n, int dim /* 4-byte words per row */,
     const float *__restrict__ norms, const float *__restrict__ thr, int thr_stride, int thr_off, int *__restrict__ counts,
     uint64_t *__restrict__ cand, int cap, const uint8_t *__restrict__ mask, int64_t mask_stride,
     int count_stride /* ints between two queries' counters: 32 = a 128-byte line each (see launch_gemm_t) */,
-    const uint32_t *__restrict__ tile_active = nullptr)
+    const uint32_t *__restrict__ tile_active = nullptr, float *__restrict__ scores = nullptr /* SAMPLE: [nq][out_cols] */,
+    int tile_stride = 1, int64_t out_cols = 0)
 {
     static_assert(NB == 2 || NB == 3, "two or three row-tile buffers");
     constexpr bool SPLIT = OPS != kBigImages;  // fp32 rows converted in registers (three products, or the screen's one)
     constexpr bool SCREEN = OPS == kBigScreen;
     extern __shared__ float gemm_lds[];
     const int mtiles = static_cast<int>((nq + kBigBM - 1) / kBigBM);
-    const int ntiles = static_cast<int>((n + kBigBN - 1) / kBigBN);
+    // (SAMPLE: the pairs of sampled 128-row tiles)
+    const int ntiles = SAMPLE ? static_cast<int>((((n + kGemmBN - 1) / kGemmBN + tile_stride - 1) / tile_stride + 1) / 2)
+                              : static_cast<int>((n + kBigBN - 1) / kBigBN);
     // Tile slots: slot bt = 8 jx + xcd holds (query tile tm = jx % mtiles, row tile tn = 8 (jx / mtiles) + xcd) — all query tiles
     // of a row tile on one XCD, back to back (see flat_gemm_kernel); the last 8 row tiles may have holes (tn >= ntiles).  A
     // workgroup's slots are blockIdx.x + i * gridDim.x (gridDim.x a multiple of 8: always the same XCD); a position keeps jx's
@@ -735,8 +751,8 @@ __device__ __forceinline__ void flat_gemm_big_body(
     // its rows past the end re-read the last one — their results are never appended) computes a per-piece offset.
     Pos a_pos = pos0, b_pos = pos0;
     int a_k = 0, b_k = 0, ia = 0, ib = 0;
-    const float *abase, *bbase;
-    int a_last, b_last;  // last row of the tile that exists (255 for a whole tile)
+    const float *abase, *bbase, *bbase1 = nullptr;  // (SAMPLE: the tile's halves)
+    int a_last, b_last, b_last1 = 0;  // last row of the tile that exists (255 for a whole tile; SAMPLE: of each half, 127)
     const uint32_t off0 = static_cast<uint32_t>((drow * dim + dgl * 4) * 4);
     auto set_a = [&](const Pos &ps) {
         const int64_t q0 = static_cast<int64_t>(tm_of(ps)) * kBigBM;
@@ -747,6 +763,14 @@ __device__ __forceinline__ void flat_gemm_big_body(
         const int64_t n0 = static_cast<int64_t>(tn_of(ps)) * kBigBN;
         bbase = base + n0 * dim;
         b_last = static_cast<int>(n - n0 < kBigBN ? n - n0 : kBigBN) - 1;
+    };
+    auto half_row0 = [&](const Pos &ps, int hf) { return (static_cast<int64_t>(tn_of(ps)) * 2 + hf) * tile_stride * kGemmBN; };
+    auto set_b_halves = [&](const Pos &ps) {
+        const int64_t r0 = half_row0(ps, 0), r1 = half_row0(ps, 1);  // (r0 < n: the tile exists)
+        bbase = base + r0 * dim;
+        b_last = static_cast<int>(n - r0 < kGemmBN ? n - r0 : kGemmBN) - 1;
+        bbase1 = r1 < n ? base + r1 * dim : bbase;
+        b_last1 = r1 < n ? static_cast<int>(n - r1 < kGemmBN ? n - r1 : kGemmBN) - 1 : b_last;
     };
     auto fill = [&](const float *src /* tile base + K step */, int last, int buf) {
         if (last == kBigBM - 1) {
@@ -760,6 +784,27 @@ __device__ __forceinline__ void flat_gemm_big_body(
             }
         }
     };
+    auto fill_b = [&](int k0, int buf) {
+        if constexpr (!SAMPLE) {
+            fill(bbase + k0, b_last, buf);
+        } else if (b_last == kGemmBN - 1 && b_last1 == kGemmBN - 1) {
+#pragma unroll
+            for (int p = 0; p < 4; p++) glds16((p < 2 ? bbase : bbase1) + k0 + static_cast<int64_t>(p & 1) * 64 * dim, off0, piece(buf, p));
+        } else {
+#pragma unroll
+            for (int p = 0; p < 4; p++) {
+                const int last = p < 2 ? b_last : b_last1;
+                const int row = (p & 1) * 64 + drow < last ? (p & 1) * 64 + drow : last;
+                glds16((p < 2 ? bbase : bbase1) + k0, static_cast<uint32_t>((row * dim + dgl * 4) * 4), piece(buf, p));
+            }
+        }
+    };
+    auto next_b = [&](const Pos &ps) {
+        if constexpr (SAMPLE)
+            set_b_halves(ps);
+        else
+            set_b(ps);
+    };
     auto stage_a = [&]() {
         fill(abase + a_k * kGemmBK, a_last, ia);
         ia ^= 1;
@@ -770,16 +815,16 @@ __device__ __forceinline__ void flat_gemm_big_body(
         }
     };
     auto stage_b = [&]() {
-        if (!(PROBE & 64)) fill(bbase + b_k * kGemmBK, b_last, 2 + ib);
+        if (!(PROBE & 64)) fill_b(b_k * kGemmBK, 2 + ib);
         ib = ib + 1 == NB ? 0 : ib + 1;
         if (++b_k == ksteps) {
             b_k = 0;
             step(b_pos);
-            if (b_pos.bt < total) set_b(b_pos);
+            if (b_pos.bt < total) next_b(b_pos);
         }
     };
     set_a(pos0);
-    set_b(pos0);
+    next_b(pos0);
 
     f32x16 acc[4][2];
     const int h = lane >> 5, f = (lane >> 1) & 7;
@@ -801,7 +846,13 @@ __device__ __forceinline__ void flat_gemm_big_body(
     // tile's loads are always followed by its tile_init: a load under a condition leaves the compiler with a "maybe pending"
     // register, and it drains the whole vector-memory queue, the fills in flight included, before the next tile overwrites it)
     float tq2[2], xq1;
+    float xn[2] = {0.0f, 0.0f};  // SAMPLE: |x|^2 of this lane's two columns of the tile being computed
     auto tile_loads = [&](const Pos &ps) {
+        if constexpr (SAMPLE) {  // the norm of column wc * 64 + lane, a row of half wc >> 1
+            const int64_t nn = half_row0(ps, wc >> 1) + (wc & 1) * 64 + lane;
+            xq1 = norms[nn < n ? nn : n - 1];
+            return;
+        }
         const int64_t q0 = static_cast<int64_t>(tm_of(ps)) * kBigBM, n0 = static_cast<int64_t>(tn_of(ps)) * kBigBN;
 #pragma unroll
         for (int i = 0; i < 2; i++) {
@@ -812,6 +863,15 @@ __device__ __forceinline__ void flat_gemm_big_body(
         xq1 = norms[nn < n ? nn : n - 1];
     };
     auto tile_init = [&]() {
+        if constexpr (SAMPLE) {  // (xn: pull_norms, in the prologue and in front of the previous tile's stores)
+#pragma unroll
+            for (int i = 0; i < 4; i++)
+#pragma unroll
+                for (int j = 0; j < 2; j++)
+#pragma unroll
+                    for (int r = 0; r < 16; r++) acc[i][j][r] = 0.0f;
+            return;
+        }
         const uint32_t one = 0x3F80u;  // bfloat16 1.0
         uint4 ta[4], xb[2];
         // (the tile being initialised: c_pos; queries past nq get -Inf = nothing passes, rows past n are never appended)
@@ -972,6 +1032,75 @@ __device__ __forceinline__ void flat_gemm_big_body(
         if (++tiles_done % kFlushEvery == 0) flush_parked();
     };
 
+    // SAMPLE: the finished tile's scores, in place of the appends (see the header).  xn is the tile's: tile_init replaces it next.
+    // The next tile's norms leave xq1 BEFORE the stores: behind them the compiler's wait for xq1 (a load older than the stores)
+    // would be a wait for half of the stores as well.
+    auto pull_norms = [&](float (&dst)[2]) {
+#pragma unroll
+        for (int j = 0; j < 2; j++) dst[j] = __shfl(xq1, j * 32 + (lane & 31));
+    };
+    auto tile_scores = [&](const Pos &ps) {
+        float xnext[2];
+        pull_norms(xnext);
+        __builtin_amdgcn_sched_barrier(0);
+        const int64_t q0 = static_cast<int64_t>(tm_of(ps)) * kBigBM;
+        int hv = 4 * h, lv = lane & 31;  // (kept out of the loop's invariants: see tile_append)
+        asm volatile("" : "+v"(hv), "+v"(lv));
+        // Registers 4 g .. 4 g + 3 of a block are four consecutive queries (8 g + 4 h ..) of one column: ONE offset walks the
+        // block's 16.  GUARDED: a tile that sticks out of the score matrix — queries past nq, or an absent second half's columns
+        // past out_cols — tests every store, a whole tile (wave-uniform) none.  MASKED: the filter bits of a group's four
+        // queries are loaded together and waited for once, group by group (left to the scheduler, the loads of all 128
+        // elements go out first and their addresses spill).  (hv opaque per block: the 64 lane masks of a lane's queries,
+        // computed once and kept in scalar registers for the second column, are 128 of them spilled.)
+        const int nq_in = static_cast<int>(nq - q0 < kBigBM ? nq - q0 : kBigBM);
+        float *const out = scores + q0 * out_cols + static_cast<int64_t>(tn_of(ps)) * kBigBN;  // (wave-uniform)
+        auto put = [&](auto guarded, auto masked) {
+            constexpr bool GUARDED = decltype(guarded)::value, MASKED = decltype(masked)::value;
+#pragma unroll
+            for (int j = 0; j < 2; j++) {
+                const int col = wc * 64 + j * 32 + lv;
+                const int64_t nn = half_row0(ps, wc >> 1) + (col & (kGemmBN - 1));
+                const bool col_ok = static_cast<int64_t>(tn_of(ps)) * kBigBN + col < out_cols, row_ok = nn < n;
+#pragma unroll
+                for (int i = 0; i < 4; i++) {
+                    asm volatile("" : "+v"(hv));
+                    int ql = wr * 128 + i * 32 + hv;
+                    int64_t off = ql * out_cols + col;
+#pragma unroll
+                    for (int g = 0; g < 4; g++) {
+                        bool keep[4];
+#pragma unroll
+                        for (int e = 0; e < 4; e++)
+                            keep[e] = row_ok && (!MASKED || ((!GUARDED || ql + e < nq_in) && mask_bit(mask + (q0 + ql + e) * mask_stride, nn)));
+#pragma unroll
+                        for (int e = 0; e < 4; e++) {
+                            const float sc = DOT ? -acc[i][j][4 * g + e] : __builtin_fmaf(-2.0f, acc[i][j][4 * g + e], xn[j]);
+                            if (!GUARDED || (ql + e < nq_in && col_ok)) out[off] = keep[e] ? sc : INFINITY;
+                            off += out_cols;
+                        }
+                        ql += 8;
+                        off += 4 * out_cols;
+                        asm volatile("" : "+v"(off));
+                        if (MASKED) __builtin_amdgcn_sched_barrier(0);
+                    }
+                }
+            }
+        };
+        const bool whole = nq_in == kBigBM && (static_cast<int64_t>(tn_of(ps)) + 1) * kBigBN <= out_cols;
+        if (mask == nullptr) {
+            if (whole)
+                put(std::false_type{}, std::false_type{});
+            else
+                put(std::true_type{}, std::false_type{});
+        } else {
+            if (whole)
+                put(std::false_type{}, std::true_type{});
+            else
+                put(std::true_type{}, std::true_type{});
+        }
+        xn[0] = xnext[0], xn[1] = xnext[1];
+    };
+
     // The four parts of a K step, part p multiplied from register set p & 1 while part p + 1 is read into the other.
     // bf16: part = operand group p (16 k); fa[set][block], fb[set][block] = the group's granules.
     // SPLIT: part = phase p of group p >> 1 (query blocks 2 (p & 1), + 1); fa[set][2 b + (0: hi, 1: lo)] = the phase's query
@@ -1066,6 +1195,7 @@ __device__ __forceinline__ void flat_gemm_big_body(
     stage_a();
     stage_b();
     if (NB == 3 && S > 1) stage_b();
+    if constexpr (SAMPLE) pull_norms(xn);
     tile_init();
     if (NB == 3 && S > 1)
         asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
@@ -1129,7 +1259,9 @@ __device__ __forceinline__ void flat_gemm_big_body(
         mfma_part(P3{});  // part 3 of step g, from registers
         __builtin_amdgcn_sched_barrier(0);
         if (last) {
-            if (!(PROBE & 1)) {
+            if constexpr (SAMPLE) {
+                tile_scores(c_pos);
+            } else if (!(PROBE & 1)) {
                 tile_append(c_pos);
             } else {  // stage probe: keep the accumulators alive without an epilogue
                 float sum = 0.0f;
@@ -1154,7 +1286,7 @@ __device__ __forceinline__ void flat_gemm_big_body(
             t++;
         }
     }
-    flush_parked();
+    if constexpr (!SAMPLE) flush_parked();
     if ((PROBE & 32768) && lane == 0) atomicAdd(&counts[nq * count_stride], flushes);  // (stage probe: how often a wave flushed, counts[nq])
 }
 
@@ -1187,6 +1319,17 @@ __global__ __launch_bounds__(kBigThreads) void flat_gemm_screen_big_kernel(
 {
     flat_gemm_big_body<DOT, NB, PROBE, kBigScreen>(queries, nq, base, n, dim, norms, thr, thr_stride, thr_off, counts, cand, cap, mask,
                                                    mask_stride, count_stride);
+}
+
+// the screen's operands and one product, the scores of every tile_stride-th 128-row tile written to scores[nq][out_cols]: the
+// row sample that sets the thresholds (SAMPLE in the body's header)
+template <bool DOT, int NB, int PROBE = 0>
+__global__ __launch_bounds__(kBigThreads) void flat_gemm_sample_big_kernel(
+    const float *__restrict__ queries, int64_t nq, const float *__restrict__ base, int64_t n, int dim, const float *__restrict__ norms,
+    float *__restrict__ scores, int tile_stride, int64_t out_cols, const uint8_t *__restrict__ mask, int64_t mask_stride)
+{
+    flat_gemm_big_body<DOT, NB, PROBE, kBigScreen, true>(queries, nq, base, n, dim, norms, nullptr, 0, 0, nullptr, nullptr, 0, mask, mask_stride, 1,
+                                                         nullptr, scores, tile_stride, out_cols);
 }
 
 // ---- 5..64 queries: the same pipeline with a 32 x 128 or 64 x 128 tile ------------------------------

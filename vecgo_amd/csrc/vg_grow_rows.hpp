@@ -35,8 +35,8 @@ static int32_t append_index_rows(vg_index *idx, const float *rows, int64_t count
         VG_HIP(hipMemsetAsync(idx->d_norm_max, 0, 2 * sizeof(float), st));
     }
     if (!idx->d_flat_stats) {
-        VG_HIP(hipMalloc(reinterpret_cast<void **>(&idx->d_flat_stats), 3 * sizeof(unsigned long long)));
-        VG_HIP(hipMemsetAsync(idx->d_flat_stats, 0, 3 * sizeof(unsigned long long), st));
+        VG_HIP(hipMalloc(reinterpret_cast<void **>(&idx->d_flat_stats), 4 * sizeof(unsigned long long)));
+        VG_HIP(hipMemsetAsync(idx->d_flat_stats, 0, 4 * sizeof(unsigned long long), st));
     }
     {
         int64_t cap = idx->rows_cap;

@@ -101,6 +101,7 @@ enum Hook {
     kHookFlatNoSplit,         // VG_FLAT_NO_SPLIT        vg_search_flat above 128 queries: the fp32 MFMA GEMM, not the split tile (three bf16 products)
     kHookFlatNoScreen,        // VG_FLAT_NO_SCREEN       vg_search_flat on the split tile: no one-product screen in front, the three-product pass for every tile
     kHookFlatScreenFail,      // VG_FLAT_SCREEN_FAIL     vg_search_flat behind a screen: every screen proof counts as failed, every query is retried on the split tile (and the screen runs up to k = 48, not 16)
+    kHookFlatF32Sample,       // VG_FLAT_F32_SAMPLE      vg_search_flat on the split tile: the threshold sample stays the fp32 128 x 128 tile's, not the persistent tile's one bf16 product
     kHookCount
 };
 bool hook(Hook h);
@@ -495,7 +496,7 @@ struct vg_index {
     float *d_norm_max = nullptr;  // [1] max ||x||^2: error bound of the GEMM-form scores
     uint16_t *d_vectors_bf16 = nullptr;  // optional bfloat16 copy of the rows: vg_index_enable_bf16_filter
     int32_t vectors_bf16_dim = 0;        // its row length: dim padded with zeros to whole 64-element K steps of the bf16 GEMM
-    unsigned long long *d_flat_stats = nullptr;  // [3] queries searched, queries sent to the exhaustive kernel, queries retried on the split tile behind a screen
+    unsigned long long *d_flat_stats = nullptr;  // [4] queries searched, queries sent to the exhaustive kernel, queries retried on the split tile behind a screen, candidates the fused path appended (vg_index_flat_appended)
     // RaBitQ: sign bits re-tiled [tile][group][lane][16 B] and the stored norms
     uint8_t *d_rq_tiles = nullptr;
     float *d_rq_norms = nullptr;

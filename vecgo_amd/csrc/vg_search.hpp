@@ -71,7 +71,8 @@ struct ThrNominated {
 size_t flat_thr_nominate_scratch(const vg_index *idx, const ThrNomPlan &plan, int64_t qc);
 int32_t flat_thr_nominate(vg_index *idx, const ThrNomPlan &plan, const float *qp, const float *uthr, int64_t cnt, const uint8_t *m0,
                           int64_t mask_stride, char *scratch, ThrNominated *out, hipStream_t st);
-int32_t launch_flat_todo(const int *flags, const int *always, int cnt, int *todo, unsigned long long *stats, hipStream_t st);
+int32_t launch_flat_todo(const int *flags, const int *always, int cnt, int *todo, unsigned long long *stats, hipStream_t st,
+                         const int *counts = nullptr);
 
 // ---- the threshold searches: k_flat_threshold.hip, k_probed_threshold.hip (and the large-k Vamana walk, k_graph.hip) ----
 constexpr int kThrMaxResults = 16384;  // the selection's LDS buffer (128 KiB of keys) and the replay's heap
