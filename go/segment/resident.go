@@ -13,6 +13,7 @@ package segment
 /*
 #cgo CFLAGS: -I${SRCDIR}/../../third_party/vecgo_hip/include
 #cgo LDFLAGS: -L${SRCDIR}/../../third_party/vecgo_hip -lvecgo_hip
+#include <stdlib.h>
 #include "vecgo_hip.h"
 */
 import "C"
@@ -395,6 +396,150 @@ func CRC32CDevice(devicePtr unsafe.Pointer, size int64) (uint32, error) {
 		return 0, err
 	}
 	return uint32(out), nil
+}
+
+// Moves is Engine.CompactWithContext's `moves` (engine/compaction.go:159-213) by row instead of by id: OldToNew over the
+// concatenated source rows (0xFFFFFFFF = deleted), NewSource / NewRow per row of the new segment.  The host keys its PK
+// index update with the ids it kept.
+type Moves struct {
+	OldToNew  []uint32
+	NewSource []int32
+	NewRow    []uint32
+}
+
+// Merge: the compaction's Iterate loop (engine/compaction.go:173-218; vg_index_merge) over resident segments: the rows of
+// sources[0], then sources[1], ... whose bit in deleted[s] is clear (bit i of byte i/8 = row i is deleted, the tombstone
+// snapshot as bytes; deleted nil or deleted[s] empty = nothing deleted there), as a new Resident with fp32 rows only.  The
+// memtable flush is the same call with one source and its HNSW tombstones.  Ids, metadata, payloads, minID / maxID and the
+// manifest commit stay with the caller.
+func Merge(sources []*Resident, deleted [][]byte) (*Resident, *Moves, error) {
+	p, err := hipctx.Ptr()
+	if err != nil {
+		return nil, nil, err
+	}
+	ctx := (*C.vg_ctx)(p)
+	if len(sources) == 0 {
+		return nil, nil, hipctx.Err(int32(C.VG_ERR_INVALID_ARG))
+	}
+	if deleted != nil && len(deleted) != len(sources) {
+		return nil, nil, fmt.Errorf("segment: Merge: %d bitmaps for %d sources", len(deleted), len(sources))
+	}
+	// the pointer arrays and the bitmaps travel in C memory: cgo passes no Go memory that holds Go pointers
+	slot := C.size_t(unsafe.Sizeof(uintptr(0)))
+	hs := (**C.vg_index)(C.calloc(C.size_t(len(sources)), slot))
+	ds := (**C.uint8_t)(C.calloc(C.size_t(len(sources)), slot))
+	defer C.free(unsafe.Pointer(hs))
+	defer C.free(unsafe.Pointer(ds))
+	hv, dv := unsafe.Slice(hs, len(sources)), unsafe.Slice(ds, len(sources))
+	total := 0
+	for s, src := range sources {
+		if src == nil {
+			return nil, nil, fmt.Errorf("segment: Merge: source %d is nil", s)
+		}
+		hv[s] = src.h
+		total += src.rows
+		if deleted == nil || len(deleted[s]) == 0 || src.rows == 0 {
+			continue
+		}
+		if len(deleted[s]) < (src.rows+7)/8 {
+			return nil, nil, fmt.Errorf("segment: Merge: deleted[%d] holds %d bytes, %d needed", s, len(deleted[s]), (src.rows+7)/8)
+		}
+		bits := C.CBytes(deleted[s])
+		defer C.free(bits)
+		dv[s] = (*C.uint8_t)(bits)
+	}
+	m := &Moves{OldToNew: make([]uint32, total), NewSource: make([]int32, total), NewRow: make([]uint32, total)}
+	var po, pr *C.uint32_t
+	var ps *C.int32_t
+	if total > 0 {
+		po, ps, pr = up(m.OldToNew), ip(m.NewSource), up(m.NewRow)
+	}
+	var out *C.vg_index
+	if err := hipctx.Err(int32(C.vg_index_merge(ctx, hs, ds, C.int32_t(len(sources)), &out, po, ps, pr, nil))); err != nil {
+		return nil, nil, err
+	}
+	live := 0
+	for _, v := range m.OldToNew {
+		if v != 0xFFFFFFFF {
+			live++
+		}
+	}
+	m.NewSource, m.NewRow = m.NewSource[:live], m.NewRow[:live]
+	return &Resident{ctx: ctx, h: out, rows: live, dim: sources[0].dim}, m, nil
+}
+
+// CompactOptions: what Engine.CompactWithContext takes from its configuration (engine/compaction.go:104-143): the
+// DiskANN threshold (0 = 10000), the flat writer's quantization (FlatQuant*, with SQ / PQ the quantizer handles FlatBuild
+// takes), the DiskANN writer's R / L / Alpha (R 0 = diskann.DefaultOptions: 64, 100, 1.2) and quantization (DiskANNQuant*, with
+// PQ / Int4 the handles DiskANNBuild takes).
+type CompactOptions struct {
+	DiskANNThreshold int
+	FlatQuant        int
+	DiskANNQuant     int
+	PQM              int
+	SQ, PQ, Int4     unsafe.Pointer
+	R, L             int
+	Alpha            float32
+	Seed             uint64
+}
+
+// CompactionPlan: the writer the engine chooses (engine/compaction.go:86-152) for totalRows source rows, deleted ones
+// included: DiskANN from the threshold up, else flat with max(1, totalRows/8192) partitions.
+func CompactionPlan(totalRows, diskANNThreshold int) (diskann bool, k int) {
+	if diskANNThreshold <= 0 {
+		diskANNThreshold = 10000
+	}
+	if totalRows >= diskANNThreshold {
+		return true, 0
+	}
+	if totalRows/8192 < 1 {
+		return false, 1
+	}
+	return false, totalRows / 8192
+}
+
+// Compact: Merge, then the writer CompactionPlan chooses, FlatBuild or DiskANNBuild, on the result.  What the builders do
+// with few rows passes through: FlatBuild leaves fewer live rows than k unpartitioned, DiskANNBuild refuses 0 rows ("no
+// vectors to write").  The Moves are the FINAL positions: Merge's composed with the builder's perm / invPerm.  (The
+// reference's flat NewRowID is the add order, right only for k = 1, compaction.go:205-206; these are the rows' true places.)
+func Compact(sources []*Resident, deleted [][]byte, o CompactOptions) (*Resident, *Moves, bool, error) {
+	total := 0
+	for s, src := range sources {
+		if src == nil {
+			return nil, nil, false, fmt.Errorf("segment: Compact: source %d is nil", s)
+		}
+		total += src.rows
+	}
+	diskann, k := CompactionPlan(total, o.DiskANNThreshold)
+	merged, m, err := Merge(sources, deleted)
+	if err != nil {
+		return nil, nil, false, err
+	}
+	var perm, inv []uint32
+	if diskann {
+		R, L, alpha := o.R, o.L, o.Alpha
+		if R == 0 {
+			R, L, alpha = 64, 100, 1.2
+		}
+		perm, inv, _, err = merged.DiskANNBuild(R, L, alpha, o.DiskANNQuant, o.PQM, o.Seed, o.PQ, o.Int4)
+	} else {
+		perm, inv, err = merged.FlatBuild(k, o.FlatQuant, o.PQM, o.Seed, o.SQ, o.PQ)
+	}
+	if err != nil {
+		merged.Close()
+		return nil, nil, false, err
+	}
+	f := &Moves{OldToNew: make([]uint32, len(m.OldToNew)), NewSource: make([]int32, len(perm)), NewRow: make([]uint32, len(perm))}
+	for i, v := range m.OldToNew {
+		f.OldToNew[i] = v
+		if v != 0xFFFFFFFF {
+			f.OldToNew[i] = inv[v]
+		}
+	}
+	for j, old := range perm {
+		f.NewSource[j], f.NewRow[j] = m.NewSource[old], m.NewRow[old]
+	}
+	return merged, f, diskann, nil
 }
 
 // VamanaGraph: (R, n*R neighbour ids with 0xFFFFFFFF = none, entry point) — what Writer.Flush writes.

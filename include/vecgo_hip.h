@@ -45,7 +45,7 @@
  *     needs a value the device computes: every *_train (the solves and convergence tests
  *     are the host's); the builders and maintenance calls (vg_hnsw_build / _insert /
  *     _compact, vg_vamana_build, vg_vamana_insert, vg_vamana_consolidate, vg_vamana_reorder_bfs, vg_flat_build, vg_diskann_build,
- *     vg_segment_*); vg_index_set_* and vg_index_enable_* (storage is replaced; the
+ *     vg_index_merge, vg_segment_*); vg_index_set_* and vg_index_enable_* (storage is replaced; the
  *     caller's buffer is free again at return); every getter; vg_search_hnsw_brute (reads
  *     its filter's population count and redo flags back); vg_search_sq8 and
  *     vg_search_pq_adc when the bfloat16 nomination takes the batch, and
@@ -106,7 +106,8 @@ extern "C" {
  *  vg_segment_search_threshold, found by symbol lookup.  Likewise the streaming Vamana index: vg_vamana_insert and
  *  vg_search_vamana_fresh, found by symbol lookup; and its delete path, vg_vamana_consolidate (with its caller-allocated
  *  vg_vamana_consolidate_stats), the same way.  Likewise vg_index_flat_retried and
- *  vg_index_flat_appended, found by symbol lookup. */
+ *  vg_index_flat_appended, found by symbol lookup.  Likewise the compaction's merge of resident indexes under tombstones,
+ *  vg_index_merge, found by symbol lookup. */
 #define VG_ABI_MINOR 13
 #define VG_INVALID_ID 0xFFFFFFFFu
 #define VG_STREAM_LEGACY ((void *)1) /* == hipStreamLegacy */
@@ -569,6 +570,44 @@ int32_t vg_vamana_reorder_bfs(vg_index *idx, uint32_t *perm, uint32_t *inv_perm,
  * vectorstore.ColumnarStore (internal/vectorstore/columnar.go:21-24) and of
  * flat.Segment.vectors (flat/segment.go:692).  Copied to HBM. */
 int32_t vg_index_set_vectors(vg_index *idx, const float *base, void *stream);
+/* Engine.CompactWithContext's Iterate loop (internal/engine/compaction.go:173-218; the memtable flush has the same shape with
+ * one source and its HNSW tombstones) over resident indexes: the sources are walked in order, each in row order
+ * (flat/segment.go:1028-1073), the rows whose bit is set in that source's tombstone bitmap are skipped (:179), the survivors
+ * are appended to one new index, and the maps say where every row went (the loop's `moves`, :159-213).  Nothing crosses
+ * PCIe but the bitmaps and the maps.  (Present when the symbol is: see VG_ABI_MINOR.)
+ *   Sources: sources[0 .. n_sources-1], on `ctx`, of one dim and metric, each with its fp32 rows (vg_index_set_vectors, or
+ *     an opened segment's).  Whatever else a source holds (codes, partitions, graphs, tombstones, nomination images) is
+ *     neither needed nor touched: sources are read-only.  The same index may be listed twice; its rows then appear twice.
+ *   deleted: NULL, or one pointer per source, any of them NULL: nothing is deleted there.  Otherwise vg_vamana_consolidate's
+ *     convention: bit i of byte i/8 = row i is deleted, ceil(n_s/8) bytes, host or device, any byte alignment; bits at or
+ *     above n_s are ignored.
+ *   *out: a new index on `ctx` with the sources' dim and metric, to be destroyed with vg_index_destroy.  Its rows are the
+ *     live rows of source 0 in ascending row order, then those of source 1, and so on, bit for bit; its norms are what
+ *     vg_index_set_vectors computes for those rows, bit for bit, and the largest norm and largest |x| are taken over the
+ *     merged rows (a deleted row may have held a source's maximum); capacities are exact and the flat search counters zero,
+ *     as after vg_index_set_vectors.  No codes, graph, partitions or bf16 image are carried over: the writer that follows
+ *     (vg_flat_build, vg_diskann_build) retrains and rebuilds, as the reference's does.
+ *   Maps, each NULL to skip, host or device: old_to_new[off_s + i] = the new row of source s row i, or VG_INVALID_ID if that
+ *     row is deleted, off_s = the row counts of the sources in front (sum of all n_s entries); new_source[j], new_row[j] =
+ *     where new row j came from (one entry per live row; a caller that has not counted them sizes both for the sum).
+ *   No live row: VG_OK, *out has 0 rows (as vg_index_create with n = 0), old_to_new is all VG_INVALID_ID.
+ *   Refusals, in this order, *out NULL and nothing written: NULL ctx, sources or out, n_sources < 1, a NULL source
+ *     VG_ERR_INVALID_ARG; a source on another context VG_ERR_INVALID_ARG; a source of another dim VG_ERR_DIM_MISMATCH; a
+ *     source of another metric VG_ERR_INVALID_ARG; metric Hamming VG_ERR_UNSUPPORTED; a source with rows but no fp32 rows
+ *     VG_ERR_NOT_READY; the sources' row counts (deleted rows included: the test comes before any allocation) summing to
+ *     0xFFFFFFFF or more VG_ERR_INVALID_ARG.  A failure after these (out of memory, a HIP error) returns its status with
+ *     *out NULL, nothing kept and the maps unspecified.
+ *   The result's row count is the number of old_to_new entries other than VG_INVALID_ID, or the sources' row counts less the
+ *     set bits below n_s of their bitmaps: there is no getter for an index's row count, so a caller that passes no
+ *     old_to_new counts its bitmaps.
+ *   Work: four kernel launches whatever the rows and however many sources.  Memory: the new rows (sources and result
+ *     coexist), plus scratch released before the call returns: two 4-byte words per live row (the (source, row) lists,
+ *     whether or not the caller asks for them), one per 2048 source rows, 48 bytes per source (the descriptors); and what
+ *     is staged for the host: 4 bytes per source row for an old_to_new in host memory (a device one is written where it
+ *     lies), n_s/8 bytes per bitmap in host memory (device ones are read where they lie).  Waits for `stream` (the row
+ *     count is read back). */
+int32_t vg_index_merge(vg_ctx *ctx, const vg_index *const *sources, const uint8_t *const *deleted, int32_t n_sources,
+                       vg_index **out, uint32_t *old_to_new, int32_t *new_source, uint32_t *new_row, void *stream);
 
 /* ---- L0 batch kernels: the dispatch seam (internal/simd/kernels.go:11-30) ------- */
 /* simd.SquaredL2Batch / simd.DotBatch (kernels.go:61-68 → batch_avx512.c:19-143):

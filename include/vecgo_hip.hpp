@@ -822,7 +822,93 @@ public:
     // Segment.Rerank (flat/segment.go:754-780) + top-k
     Result Rerank(const float *queries, int64_t nq, const uint32_t *cand, int nc, int k) { return run(nq, k, [&](Result &r) { return vg_rerank(h_, queries, nq, cand, nc, k, r.ids.data(), r.scores.data(), nullptr); }); }
 
+    int64_t Rows() const { return n_; }
+
+    // Where Engine.CompactWithContext's rows went (engine/compaction.go:159-213): oldToNew over the concatenated source rows
+    // (VG_INVALID_ID = deleted), newSource / newRow per row of the new segment
+    struct Moves {
+        std::vector<uint32_t> oldToNew;
+        std::vector<int32_t> newSource;
+        std::vector<uint32_t> newRow;
+    };
+    // The compaction's Iterate loop over resident segments (compaction.go:173-218; vg_index_merge): the rows of sources[0],
+    // then sources[1], ... whose bit in deleted[s] (bit i of byte i/8, host or device; a null entry or an empty vector = none
+    // deleted) is clear, as a new segment with fp32 rows only
+    static std::unique_ptr<Segment> Merge(std::shared_ptr<Context> ctx, const std::vector<const Segment *> &sources,
+                                          const std::vector<const uint8_t *> &deleted, Moves *moves = nullptr)
+    {
+        if (sources.empty() || (!deleted.empty() && deleted.size() != sources.size()))
+            throw std::invalid_argument("Segment::Merge: at least one source, and no bitmaps or one (may be null) per source");
+        std::vector<const vg_index *> hs;
+        int64_t total = 0;
+        for (const Segment *s : sources) {
+            if (!s) throw std::invalid_argument("Segment::Merge: null source");
+            hs.push_back(s->h_);
+            total += s->n_;
+        }
+        Moves m;
+        m.oldToNew.resize(static_cast<size_t>(total));
+        m.newSource.resize(static_cast<size_t>(total));
+        m.newRow.resize(static_cast<size_t>(total));
+        vg_index *out = nullptr;
+        check(vg_index_merge(ctx->handle(), hs.data(), deleted.empty() ? nullptr : deleted.data(), static_cast<int32_t>(hs.size()), &out,
+                             m.oldToNew.data(), m.newSource.data(), m.newRow.data(), nullptr));
+        int64_t live = 0;
+        for (uint32_t v : m.oldToNew) live += v != VG_INVALID_ID;
+        m.newSource.resize(static_cast<size_t>(live));
+        m.newRow.resize(static_cast<size_t>(live));
+        if (moves) *moves = std::move(m);
+        return std::unique_ptr<Segment>(new Segment(std::move(ctx), out, live, sources[0]->dim_));
+    }
+    // Engine.CompactWithContext's choice of writer (compaction.go:86-152) for totalRows source rows, deleted ones included:
+    // true = DiskANN (from diskannThreshold rows up, 0 = 10000), else flat with *k = max(1, totalRows / 8192) partitions
+    static bool CompactionPlan(int64_t totalRows, int64_t diskannThreshold, int *k)
+    {
+        if (totalRows >= (diskannThreshold > 0 ? diskannThreshold : 10000)) return true;
+        *k = totalRows / 8192 < 1 ? 1 : static_cast<int>(totalRows / 8192);
+        return false;
+    }
+    // Merge, then the writer CompactionPlan chooses: FlatBuild(k, flatQuantization, sq, pq) or DiskANNBuild(r, l, alpha,
+    // diskannQuantization, pq, iq).  *diskann says which; moves holds the FINAL positions, Merge's maps composed with the
+    // builder's perm / invPerm (the reference's flat NewRowID is right only for k = 1, compaction.go:205-206)
+    static std::unique_ptr<Segment> Compact(std::shared_ptr<Context> ctx, const std::vector<const Segment *> &sources,
+                                            const std::vector<const uint8_t *> &deleted, Moves *moves, bool *diskann,
+                                            int64_t diskannThreshold = 0, int flatQuantization = VG_QUANT_NONE,
+                                            std::shared_ptr<quantization::ScalarQuantizer> sq = nullptr,
+                                            std::shared_ptr<quantization::ProductQuantizer> pq = nullptr, int r = 64, int l = 100,
+                                            float alpha = 1.2f, int diskannQuantization = VG_QUANT_NONE,
+                                            std::shared_ptr<quantization::Int4Quantizer> iq = nullptr, uint64_t seed = 0, int pqM = 0)
+    {
+        int64_t total = 0;
+        for (const Segment *s : sources) {
+            if (!s) throw std::invalid_argument("Segment::Compact: null source");
+            total += s->n_;
+        }
+        int k = 0;
+        const bool ann = CompactionPlan(total, diskannThreshold, &k);
+        Moves m;
+        std::unique_ptr<Segment> merged = Merge(std::move(ctx), sources, deleted, &m);
+        std::vector<uint32_t> perm(static_cast<size_t>(merged->n_)), inv(static_cast<size_t>(merged->n_));
+        if (ann)
+            merged->DiskANNBuild(r, l, alpha, diskannQuantization, std::move(pq), std::move(iq), perm.data(), inv.data(), seed, pqM);
+        else
+            merged->FlatBuild(k, flatQuantization, std::move(sq), std::move(pq), perm.data(), inv.data(), seed, pqM);
+        Moves f;
+        f.oldToNew = m.oldToNew;
+        for (uint32_t &v : f.oldToNew)
+            if (v != VG_INVALID_ID) v = inv[v];
+        for (uint32_t p : perm) {
+            f.newSource.push_back(m.newSource[p]);
+            f.newRow.push_back(m.newRow[p]);
+        }
+        if (moves) *moves = std::move(f);
+        if (diskann) *diskann = ann;
+        return merged;
+    }
+
 private:
+    // a handle the library created (vg_index_merge)
+    Segment(std::shared_ptr<Context> ctx, vg_index *h, int64_t rows, int dim) : ctx_(std::move(ctx)), h_(h), n_(rows), dim_(dim) {}
     template <typename F>
     Result run(int64_t nq, int k, F f)
     {

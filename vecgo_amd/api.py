@@ -900,6 +900,15 @@ class Index:
         self._borrowed_handle = True
         return self
 
+    @classmethod
+    def _adopted(cls, ctx: Context, handle, n: int, dim: int, metric: int):
+        """An Index that owns a handle the library created (vg_index_merge): closed like one made by __init__."""
+        self = cls.__new__(cls)
+        self._lib, self.ctx, self._h = ctx._lib, ctx, handle
+        self.n, self.dim, self.metric = n, dim, Metric(metric)
+        self._keep = []
+        return self
+
     def close(self):
         if getattr(self, "_h", None):
             if not getattr(self, "_borrowed_handle", False):
@@ -1599,6 +1608,78 @@ class Index:
     def search_pq_adc(self, queries, k, out=None, stream=None):
         """flat.Segment.Search PQ branch (flat/segment.go:476-483,678-689,714-721)."""
         return self._search(self._lib.vg_search_pq_adc, queries, k, out=out, stream=stream)
+
+
+INVALID_ID = 0xFFFFFFFF   # VG_INVALID_ID
+
+
+def merge_indexes(ctx: Context, sources, deleted=None, stream=None):
+    """Engine.CompactWithContext's Iterate loop (engine/compaction.go:173-218) over resident indexes (vg_index_merge; the
+    rules are the header's): the live rows of sources[0], then of sources[1], ..., in row order, as a new Index.  deleted:
+    None, or one entry per source, each None / bool[n_s] / packed bits (numpy, or a torch uint8 tensor where it lies).
+    Returns (index, old_to_new, new_source, new_row): old_to_new is np.uint32 over the concatenated source rows (INVALID_ID =
+    deleted), new_source np.int32 and new_row np.uint32 have one entry per row of the new index."""
+    sources = list(sources)
+    if deleted is not None and len(deleted) != len(sources):
+        raise ValueError(f"merge_indexes: one deleted entry per source ({len(sources)}), got {len(deleted)}")
+    keep, ptrs = [], []
+    for s, src in enumerate(sources):
+        d = None if deleted is None else deleted[s]
+        if d is None or src.n == 0:
+            ptrs.append(None)
+            continue
+        m, pm, _ = src._packed_mask(d, 1, "merge_indexes")
+        keep.append(m)
+        ptrs.append(pm.value)
+    handles = (C.c_void_p * len(sources))(*[src._h.value for src in sources])
+    bitmaps = (C.c_void_p * len(sources))(*ptrs)
+    total = sum(src.n for src in sources)
+    old_to_new = np.empty(total, np.uint32)
+    new_source = np.empty(total, np.int32)
+    new_row = np.empty(total, np.uint32)
+    out = C.c_void_p()
+    check(ctx._lib.vg_index_merge(ctx._h, handles, None if deleted is None else bitmaps, C.c_int32(len(sources)), C.byref(out),
+                                  C.c_void_p(old_to_new.ctypes.data), C.c_void_p(new_source.ctypes.data),
+                                  C.c_void_p(new_row.ctypes.data), _stream_ptr(stream)))
+    live = int(np.count_nonzero(old_to_new != INVALID_ID))
+    merged = Index._adopted(ctx, out, live, sources[0].dim, int(sources[0].metric))
+    return merged, old_to_new, new_source[:live].copy(), new_row[:live].copy()
+
+
+def compaction_plan(total_rows: int, diskann_threshold: int = 0):
+    """The writer Engine.CompactWithContext chooses (engine/compaction.go:86-152) for `total_rows` source rows, deleted ones
+    included (it sums RowCount() before it looks at tombstones): ("diskann", 0) from diskann_threshold rows up (0 or less:
+    10000), else ("flat", k) with k = max(1, total_rows // 8192) partitions."""
+    threshold = diskann_threshold if diskann_threshold > 0 else 10000
+    if total_rows >= threshold:
+        return "diskann", 0
+    return "flat", max(1, total_rows // 8192)
+
+
+def compact(ctx: Context, sources, deleted=None, *, diskann_threshold=0, flat_quantizer=None, diskann=None, seed=0, stream=None):
+    """Engine.CompactWithContext on resident indexes: compaction_plan over the sources' row counts, merge_indexes, then the
+    chosen writer on the result — Index.flat_build(k, flat_quantizer, seed) or Index.diskann_build(seed=seed, **diskann)
+    (diskann: a dict of diskann_build's r / l / alpha / quantizer / pq_iters / max_batch / growth_div; unset ones take
+    diskann.DefaultOptions: 64 / 100 / 1.2 / no codes).  What the builders do with few rows passes through: flat_build leaves
+    fewer live rows than k unpartitioned, diskann_build refuses 0 rows ("no vectors to write").
+    Returns (index, kind, old_to_new, new_source, new_row) with the FINAL positions: merge_indexes' maps composed with the
+    builder's perm / inv_perm (the reference's flat NewRowID is right only for k = 1, compaction.go:205-206; these are the
+    rows' true places).  Ids, metadata and payloads are the caller's to move with new_source / new_row."""
+    sources = list(sources)
+    kind, k = compaction_plan(sum(src.n for src in sources), diskann_threshold)
+    merged, old_to_new, new_source, new_row = merge_indexes(ctx, sources, deleted, stream=stream)
+    try:
+        if kind == "flat":
+            perm, inv = merged.flat_build(k, quantizer=flat_quantizer, seed=seed, stream=stream)
+        else:
+            perm, inv, _ = merged.diskann_build(seed=seed, stream=stream, **(diskann or {}))
+    except Exception:
+        merged.close()
+        raise
+    live = old_to_new != INVALID_ID
+    final = old_to_new.copy()
+    final[live] = inv[old_to_new[live]]
+    return merged, kind, final, new_source[perm], new_row[perm]
 
 
 class SegmentInfo(C.Structure):

@@ -50,11 +50,17 @@ static unsigned rb_grid(int64_t total)
     return static_cast<unsigned>(std::max<int64_t>(1, std::min<int64_t>((total + 255) / 256, 8192)));
 }
 
+// the widest access that divides a row (rows start at a hipMalloc'd base: a word of that size is aligned in every row)
+static int64_t rb_word_bytes(int64_t row_bytes)
+{
+    return row_bytes % 16 == 0 ? 16 : row_bytes % 8 == 0 ? 8 : row_bytes % 4 == 0 ? 4 : row_bytes % 2 == 0 ? 2 : 1;
+}
+
 // array <- array gathered by perm, through scratch; row_bytes of any size, the widest access that divides it
 static int32_t rb_permute_rows(void *array, int64_t n, int64_t row_bytes, const uint32_t *perm, void *scratch, hipStream_t st)
 {
     if (!array || n == 0 || row_bytes == 0) return VG_OK;
-    const int64_t w = row_bytes % 16 == 0 ? 16 : row_bytes % 8 == 0 ? 8 : row_bytes % 4 == 0 ? 4 : row_bytes % 2 == 0 ? 2 : 1;
+    const int64_t w = rb_word_bytes(row_bytes);
     const int64_t words = row_bytes / w;
     const unsigned grid = rb_grid(n * words);
 #define VG_RB_GATHER(T) \
