@@ -65,9 +65,10 @@ struct GemmArgs {
     int skip_stride = 0;
     // MODE 2: the split tile (flat_gemm_split_big_kernel) — `queries` is flat_split_queries_kernel's image of the chunk, `base` the
     // fp32 rows.  Set only where gemm_runs_split() says so (vg_search_flat's fused path).  MODE 1: the sample on the same tile
-    // (flat_gemm_sample_big_kernel), where sample_runs_big() says so.
+    // (flat_gemm_sample_big_kernel), where sample_runs_big() says so — `queries` is that kernel's compact hi-only image.
     bool split = false;
-    // with `split`: the screen (flat_gemm_screen_big_kernel), the product of the hi halves alone — where gemm_runs_screen() says so
+    // with `split`: the screen (flat_gemm_screen_big_kernel), the product of the hi halves alone — where gemm_runs_screen() says so;
+    // `queries` is the compact hi-only image
     bool screen = false;
     // with `split`, not `screen`: the retry behind a screen.  Bit tm of the word = query tile tm holds a query to retry; the others
     // are not multiplied.  flat_retry_prepare_kernel has written it and zeroed the counters of the queries to retry.
@@ -91,7 +92,9 @@ struct GemmArgs {
     GemmArgs &wide(int *lines, int compute_units) { return counts_wide = lines, cus = compute_units, *this; }
     GemmArgs &skipping(int stride) { return skip_stride = stride, *this; }
     GemmArgs &split_tile(const uint32_t *image) { return queries = reinterpret_cast<const float *>(image), split = true, *this; }
-    GemmArgs &screen_tile() { return screen = true, *this; }
+    // (the screen and the sample read flat_split_queries_kernel's OTHER image, the compact hi-only one)
+    GemmArgs &sample_tile(const uint32_t *hi_image) { return split_tile(hi_image); }
+    GemmArgs &screen_tile(const uint32_t *hi_image) { return split_tile(hi_image), screen = true, *this; }
     GemmArgs &retry(const uint32_t *active) { return tile_active = active, *this; }
 };
 constexpr int kCountLine = 32;
@@ -231,13 +234,13 @@ static int32_t launch_gemm_t(const GemmArgs &a)
     if constexpr (MODE == 1) {
         if (a.split) {  // the sample on the persistent tile: a row tile is a pair of sampled 128-row tiles
             VG_CHECK(!bf16 && gemm_runs_split(true, false, dma, c.cnt, c.ops.dim_words, 0, 0), VG_ERR_INVALID_ARG, "launch_gemm: sample tile on a call without it");
-            return launch_lds(flat_gemm_sample_big_kernel<DOT, 3>, big_grid((tiles + 1) / 2), dim3(kBigThreads), big_lds_bytes<3>(), st, a.queries, c.cnt,
+            return launch_lds(flat_gemm_sample_big_kernel<DOT, 3>, big_grid((tiles + 1) / 2), dim3(kBigThreads), big_lds_bytes<3, true>(), st, a.queries, c.cnt,
                               c.ops.b, c.ops.n, c.ops.dim_words, c.ops.norms, a.scores, a.tile_stride, a.out_cols, c.mask, c.mask_stride);
         }
     }
     if (MODE == 2 && a.split) {
         VG_CHECK(!bf16 && gemm_runs_split(true, false, dma, c.cnt, c.ops.dim_words, a.cap, a.thr_stride), VG_ERR_INVALID_ARG, "launch_gemm: split tile on a call without it");
-        if (a.screen) return launch_big(flat_gemm_screen_big_kernel<DOT, 3>, big_lds_bytes<3>());
+        if (a.screen) return launch_big(flat_gemm_screen_big_kernel<DOT, 3>, big_lds_bytes<3, true>());
         VG_CHECK(!a.tile_active || (c.cnt <= 32 * kBigBM && a.counts_wide), VG_ERR_INVALID_ARG, "launch_gemm: tile_active is one word, with wide counters");
         note_flat_split_launch();
         return launch_big(flat_gemm_split_big_kernel<DOT, 3>, big_lds_bytes<3>(), a.tile_active);
@@ -290,18 +293,30 @@ __global__ void f32_to_bf16_pad_kernel(const float *__restrict__ src, int64_t ro
 // The queries of the split tile (flat_gemm_split_big_kernel) as an image of `dim` 4-byte words per row, like the fp32 row it is
 // made from: every 128-byte K step holds [hi of its 32 elements | lo of the same 32], so that both operands advance by the same
 // k per step.  One thread per pair of elements; dim % 32 == 0.
-__global__ void flat_split_queries_kernel(const float *__restrict__ src, int64_t rows, int dim, uint32_t *__restrict__ dst)
+// Beside it `hi_dst`, the compact image the screen and the sample on its tile read (flat_gemm_big_body, OPS = kBigScreen): the same
+// hi words and nothing else, blocked per (256-query tile, K step) in the tile's LDS order — block (tile, step) is 256 rows of
+// 16 words, slot (4 words) s of row R = granule s ^ ((R >> 2) & 3) of the step — so that a fill piece is one contiguous KiB.
+// It holds WHOLE tiles (flat_hi_image_rows): a row past `rows` is the last query's, which is what the tile's fills used to
+// re-read for it.  The grid covers the padded rows.
+static int64_t flat_hi_image_rows(int64_t rows) { return (rows + kBigBM - 1) / kBigBM * kBigBM; }
+__global__ void flat_split_queries_kernel(const float *__restrict__ src, int64_t rows, int dim, uint32_t *__restrict__ dst,
+                                          uint32_t *__restrict__ hi_dst)
 {
     const int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;  // pair index
     const int half = dim / 2;
-    if (i >= rows * half) return;
     const int64_t r = i / half;
+    if (r >= (rows + kBigBM - 1) / kBigBM * kBigBM) return;
+    const int64_t rs = r < rows ? r : rows - 1;
     const int p = static_cast<int>(i - r * half), s = p >> 4, w = p & 15;
-    const float2 v = *reinterpret_cast<const float2 *>(src + r * dim + 32 * s + 2 * w);
+    const float2 v = *reinterpret_cast<const float2 *>(src + rs * dim + 32 * s + 2 * w);
     uint32_t hi, lo;
     split2_bf16(v.x, v.y, hi, lo);
-    dst[r * dim + 32 * s + w] = hi;
-    dst[r * dim + 32 * s + 16 + w] = lo;
+    if (r < rows) {
+        dst[r * dim + 32 * s + w] = hi;
+        dst[r * dim + 32 * s + 16 + w] = lo;
+    }
+    const int R = static_cast<int>(r & (kBigBM - 1));
+    hi_dst[((r / kBigBM) * (dim / 32) + s) * (kBigBM * 16) + R * 16 + (((w >> 2) ^ ((R >> 2) & 3)) << 2) + (w & 3)] = hi;
 }
 
 // After the proofs: the work list of step 4 (todo[0] = how many queries need the exhaustive scan,
@@ -1005,7 +1020,7 @@ static int32_t select_thresholds(const NomScratch &s, int64_t cnt, int sel_k, ui
 }
 // (a) of a nomination: a query's thresholds are the sel_k best scores of a row sample (every stride-th row tile; rows its filter
 // rejects score +Inf), the last of them its append threshold; not `sampled` (few rows: the list holds them all): +Inf
-// (image: the sample on the persistent tile, from flat_split_queries_kernel's image of the queries, one workgroup on each of
+// (image: the sample on the persistent tile, from flat_split_queries_kernel's compact hi-only image of the queries, one workgroup on each of
 // the `cus` compute units — sample_runs_big)
 static int32_t sample_thresholds(const NomCall &c, const NomScratch &s, int stride, int sel_k, float *thr, bool sampled, const uint32_t *image = nullptr,
                                  int cus = 0)
@@ -1015,7 +1030,7 @@ static int32_t sample_thresholds(const NomCall &c, const NomScratch &s, int stri
         return VG_OK;
     }
     GemmArgs a = GemmArgs::sample(c, s.sc, stride, s.cols);
-    if (image) a.split_tile(image).wide(nullptr, cus);
+    if (image) a.sample_tile(image).wide(nullptr, cus);
     VG_TRY(launch_gemm<1>(a));
     return select_thresholds(s, c.cnt, sel_k, s.sid, thr, c.st);
 }
@@ -1088,6 +1103,7 @@ struct FlatScratch : NomScratch {
     uint32_t *fid;
     float *fsc;
     uint16_t *qbf;  // the chunk's queries in bfloat16, or as the split tile's hi | lo image
+    uint32_t *qhi;  // beside the hi | lo image: the compact hi-only one of the screen and the sample (whole 256-query tiles)
     int *counts_wide;
     uint32_t *tile_active;  // the retry's query tiles (flat_retry_prepare_kernel)
     FlatScratch(const FlatCall &c, bool unfused, char *base) : fused(!unfused), use_sample(fused && c.n > kFlatCap)
@@ -1118,6 +1134,7 @@ struct FlatScratch : NomScratch {
         cv.take(fsc, qc * pk);
         cv.take(min_keys, qc);
         cv.take(qbf, bf16 ? qc * c.idx->vectors_bf16_dim : may_split ? 2 * qc * c.dim : 0);
+        cv.take(qhi, may_split ? flat_hi_image_rows(qc) * (c.dim / 2) : 0);
         cv.take(counts_wide, bf16 || may_split ? qc * kCountLine : 0);
         cv.take(tile_active, may_split ? 1 : 0);
         bytes = cv.off;
@@ -1225,13 +1242,13 @@ static int32_t flat_fused_chunk(const FlatCall &c, const FlatScratch &s)
     const bool screen = gemm_runs_screen(split, c.k);
     const float eps_extra = screen ? screen_gemm_eps(c.dot, c.dim) : split ? split_gemm_eps(c.dot, c.dim) : s.bf16 ? bf16_filter_eps(c.dot) : 0.0f;
     if (s.bf16) VG_TRY(gemm_operands(c.q, c.nq, c.dim, c.n, idx->d_norms, idx->d_vectors_bf16, idx->vectors_bf16_dim, s.qbf, c.st, &nc.ops));
-    // (the split tile's image of the queries first: where sample_runs_big() says so, the sample reads it too)
-    const uint32_t *image = reinterpret_cast<const uint32_t *>(s.qbf);
+    // (the images of the queries first, one launch: hi | lo for the split tile — the nomination without a screen, the retry behind
+    // one — and the compact hi-only one for the screen and, where sample_runs_big() says so, the sample)
     if (split)
-        VG_LAUNCH(flat_split_queries_kernel, dim3(static_cast<unsigned>((c.nq * (c.dim / 2) + 255) / 256)), dim3(256), 0, c.st, c.q, c.nq, c.dim,
-                  reinterpret_cast<uint32_t *>(s.qbf));
+        VG_LAUNCH(flat_split_queries_kernel, dim3(static_cast<unsigned>((flat_hi_image_rows(c.nq) * (c.dim / 2) + 255) / 256)), dim3(256), 0, c.st, c.q,
+                  c.nq, c.dim, reinterpret_cast<uint32_t *>(s.qbf), s.qhi);
     // (a) threshold per query from a row sample
-    VG_TRY(sample_thresholds(nc, s, kFlatSampleStride, nom.sel_k, nom.thr, s.use_sample, sample_runs_big(split, s.use_sample) ? image : nullptr,
+    VG_TRY(sample_thresholds(nc, s, kFlatSampleStride, nom.sel_k, nom.thr, s.use_sample, sample_runs_big(split, s.use_sample) ? s.qhi : nullptr,
                              idx->ctx->compute_units));
     if (s.bf16 || split) VG_LAUNCH(flat_thr_cap_kernel, dim3(nc.ucnt()), dim3(64), 0, c.st, nom.thr, nom.sel_k, c.q, c.dim, idx->d_norm_max);
     // (b) the GEMM, appending every element below its query's threshold.  The sampled tiles' scores are in `sc` already,
@@ -1246,8 +1263,10 @@ static int32_t flat_fused_chunk(const FlatCall &c, const FlatScratch &s)
                       nom.sel_k, nom.sel_k - 1, nom.counts, nom.cand, nom.cap);
         GemmArgs a = GemmArgs::append(nc, nom.thr, nom.sel_k, nom.counts, nom.cand, nom.cap);
         a.wide(s.bf16 || split ? s.counts_wide : nullptr, idx->ctx->compute_units).skipping(once ? kFlatSampleStride : 0);
-        if (split) a.split_tile(reinterpret_cast<const uint32_t *>(s.qbf));
-        if (screen) a.screen_tile();
+        if (screen)
+            a.screen_tile(s.qhi);
+        else if (split)
+            a.split_tile(reinterpret_cast<const uint32_t *>(s.qbf));
         VG_TRY(launch_gemm<2>(a));
     }
     // (c) the kc best appended keys (k > kGemmMaxK: all of them go to the exact re-score), (d) the re-score and the proof

@@ -614,8 +614,10 @@ __global__ __launch_bounds__(kGemmThreads) void flat_gemm_dma_grouped_kernel(
 // barrier publishes them; a buffer is refilled only after a barrier that every wave passed with its reads retired (lgkmcnt(0)).
 constexpr int kBigBM = 256, kBigBN = 256, kBigThreads = 512;
 constexpr int kBigTile = kBigBM * kGemmBK;  // floats per operand tile (256 rows x 128 B = 32 KiB)
-template <int NB>
-constexpr size_t big_lds_bytes() { return (2 + NB) * kBigTile * sizeof(float); }
+constexpr int kBigHiTile = kBigBM * kGemmBK / 2;  // floats of a query tile of the compact hi-only image (256 queries x 64 B = 16 KiB)
+// two query tiles + NB row tiles.  HI (the screen and the sample on it): the query tiles are the compact image's, 2 x 16 + NB x 32 KiB
+template <int NB, bool HI = false>
+constexpr size_t big_lds_bytes() { return (2 * (HI ? kBigHiTile : kBigTile) + NB * kBigTile) * sizeof(float); }
 
 // x = p0 + p1 + p2 exactly (three bfloat16 = 24 significant bits; x finite), the three as the low halves of p0, p1, p2
 __device__ __forceinline__ void big_split3(float x, uint32_t &p0, uint32_t &p1, uint32_t &p2)
@@ -658,9 +660,17 @@ __device__ __forceinline__ void split2_bf16(float a, float b, uint32_t &hi, uint
 // (split2_bf16) in front of the group's first phase, between that phase's matrix instructions.  All four granule indices are
 // constant over the 16 lanes of a ds_read_b128 pass, so slot = granule ^ ((R >> 1) & 7) visits 16 different 16-byte bank groups
 // as in the bf16 tile: no bank conflicts.  The error of the three-product sum: see split_gemm_eps (k_flat.hip).
-// OPS = kBigScreen (flat_gemm_screen_big_kernel): the split tile's operands, fills and phases, but ONE product, q_hi.x_hi — a lane
-// converts its 8 floats of a group with the 4 v_cvt_pk_bf16_f32 of the split's hi half and reads only the hi granules of the query
-// image: 2 x 2 matrix instructions per phase.  Its error is the bfloat16 filter's: screen_gemm_eps (k_flat.hip).
+// OPS = kBigScreen (flat_gemm_screen_big_kernel): the split tile's row operand, row fills and phases, but ONE product, q_hi.x_hi —
+// a lane converts its 8 floats of a group with the 4 v_cvt_pk_bf16_f32 of the split's hi half: 2 x 2 matrix instructions per
+// phase.  Its error is the bfloat16 filter's: screen_gemm_eps (k_flat.hip).  It never reads a lo half, so `queries` is the COMPACT
+// image flat_split_queries_kernel writes beside the hi | lo one — the same hi values, nothing else: a query tile's K step is
+// 256 queries x 32 bfloat16 = 16 KiB, 64 B per query, filled by TWO pieces per wave (16 rows x 64 B each: lane l -> row l >> 2,
+// slot l & 3) where the hi | lo image takes four.  In memory the image is blocked per (query tile, K step) in LDS order, swizzle
+// included, and padded to whole tiles with copies of the last query: a piece is one contiguous KiB = 8 whole cache lines at a
+// wave-uniform address (64 B per query row-major would be 16 half lines per piece), and no fill knows of nq.  LDS: rows of 64 B,
+// four to a 256-byte bank window, slot s of row R holds granule s ^ ((R >> 2) & 3); lane (r, h) reads granule 2 j + h of group
+// j — constant over the 16 lanes of a ds_read_b128 pass, whose rows are every R & 3 four times with four different
+// (R >> 2) & 3: 16 different 16-byte bank groups.  2 x 16 + NB x 32 KiB of LDS (big_lds_bytes<NB, true>).
 // `tile_active` (or null: every tile): bit tm says whether query tile tm is multiplied at all — step() passes over the slots of
 // the others as it passes over the row-tile holes, and a workgroup that is left with no slot returns before it touches LDS
 // (vg_search_flat's retry of the queries whose screen proof failed).  One word: at most 32 query tiles (the launcher checks).
@@ -692,15 +702,15 @@ __device__ __forceinline__ void flat_gemm_big_body(
     extern __shared__ float gemm_lds[];
     const int mtiles = static_cast<int>((nq + kBigBM - 1) / kBigBM);
     // (SAMPLE: the pairs of sampled 128-row tiles)
-    const int ntiles = SAMPLE ? static_cast<int>((((n + kGemmBN - 1) / kGemmBN + tile_stride - 1) / tile_stride + 1) / 2)
-                              : static_cast<int>((n + kBigBN - 1) / kBigBN);
+    const int ntiles = __builtin_amdgcn_readfirstlane(SAMPLE ? static_cast<int>((((n + kGemmBN - 1) / kGemmBN + tile_stride - 1) / tile_stride + 1) / 2)
+                                                             : static_cast<int>((n + kBigBN - 1) / kBigBN));
     // Tile slots: slot bt = 8 jx + xcd holds (query tile tm = jx % mtiles, row tile tn = 8 (jx / mtiles) + xcd) — all query tiles
     // of a row tile on one XCD, back to back (see flat_gemm_kernel); the last 8 row tiles may have holes (tn >= ntiles).  A
     // workgroup's slots are blockIdx.x + i * gridDim.x (gridDim.x a multiple of 8: always the same XCD); a position keeps jx's
     // quotient and remainder by mtiles and steps them by the constants dq / dr — no division in the K-step loop (a 64-bit one is
     // ~120 scalar instructions, and the loop needed eight of them at every tile boundary, in front of the matrix instructions).
     const int total = mtiles * ((ntiles + 7) / 8) * 8, G = static_cast<int>(gridDim.x), xcd = static_cast<int>(blockIdx.x & 7);
-    const int dq = (G >> 3) / mtiles, dr = (G >> 3) % mtiles;
+    const int dq = __builtin_amdgcn_readfirstlane((G >> 3) / mtiles), dr = __builtin_amdgcn_readfirstlane((G >> 3) % mtiles);
     struct Pos {
         int bt, quo, rem;  // slot; (bt >> 3) / mtiles and % mtiles
     };
@@ -721,8 +731,10 @@ __device__ __forceinline__ void flat_gemm_big_body(
     };
     Pos pos0;
     pos0.bt = static_cast<int>(blockIdx.x);
-    pos0.quo = (pos0.bt >> 3) / mtiles;
-    pos0.rem = (pos0.bt >> 3) % mtiles;
+    // (the divisions run on the vector unit; said to be uniform here, the whole position state — and every fill address derived
+    // from it, a scalar operand of glds16 — stays in scalar registers, whatever the rest of the kernel makes the compiler prefer)
+    pos0.quo = __builtin_amdgcn_readfirstlane((pos0.bt >> 3) / mtiles);
+    pos0.rem = __builtin_amdgcn_readfirstlane((pos0.bt >> 3) % mtiles);
     if (pos0.bt < total && hole(pos0)) step(pos0);
     if (pos0.bt >= total) return;
     int my_tiles = 0;
@@ -740,10 +752,14 @@ __device__ __forceinline__ void flat_gemm_big_body(
     const int dgl = (lane & 7) ^ ((wave * 4 + (lane >> 4)) & 7);
     const uint32_t lds0 = static_cast<uint32_t>(reinterpret_cast<uintptr_t>(
         (__attribute__((address_space(3))) void *)gemm_lds));
-    // tile buffers: A0 A1 | B0 .. B(NB-1)
+    // tile buffers: A0 A1 | B0 .. B(NB-1), as float offsets.  SCREEN: the query tiles are the compact image's, 256 rows of 64 B
+    constexpr int kATile = SCREEN ? kBigHiTile : kBigTile, kARow = SCREEN ? kGemmBK / 2 : kGemmBK;
+    auto a_buf = [&](int i) { return i * kATile; };
+    auto b_buf = [&](int i) { return 2 * kATile + i * kBigTile; };
+    // this wave's 1 KiB of pass p of the tile at `buf`: 8 rows of 128 B (16 rows of 64 B)
     auto piece = [&](int buf, int p) {
         return static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(
-            static_cast<int>(lds0 + (buf * kBigTile + (p * 64 + wave * 8) * kGemmBK) * 4)));
+            static_cast<int>(lds0 + (buf + (p * 64 + wave * 8) * kGemmBK) * 4)));
     };
     // fetch cursors: the (tile, K step) the next query / row tile fill is for, its source and the buffer it goes to.  A piece's
     // source = a wave-uniform address (tile base + K step + the piece's first row: scalar arithmetic) + ONE per-lane offset
@@ -756,7 +772,9 @@ __device__ __forceinline__ void flat_gemm_big_body(
     const uint32_t off0 = static_cast<uint32_t>((drow * dim + dgl * 4) * 4);
     auto set_a = [&](const Pos &ps) {
         const int64_t q0 = static_cast<int64_t>(tm_of(ps)) * kBigBM;
-        abase = queries + q0 * dim;
+        // (SCREEN: the tile's ksteps blocks of the compact image — flat_split_queries_kernel, k_flat.hip — half the bytes of
+        // 256 rows of `dim` words.  The image holds whole tiles: its rows past nq ARE the last query, so its fill needs no a_last)
+        abase = queries + (SCREEN ? q0 * (dim / 2) : q0 * dim);
         a_last = static_cast<int>(nq - q0 < kBigBM ? nq - q0 : kBigBM) - 1;
     };
     auto set_b = [&](const Pos &ps) {
@@ -806,7 +824,17 @@ __device__ __forceinline__ void flat_gemm_big_body(
             set_b(ps);
     };
     auto stage_a = [&]() {
-        fill(abase + a_k * kGemmBK, a_last, ia);
+        if constexpr (SCREEN) {
+            // the compact image is blocked per (query tile, K step) in LDS order, swizzle included: a piece is one contiguous KiB
+            // (pass p = the block's half p, 8 KiB; thread t its 16 bytes at 16 t) — TWO pieces per wave and step
+            int t16 = tid;  // (opaque: hoisted out of the K-step loop, 16 t is one more register held through all of it)
+            asm volatile("" : "+v"(t16));
+            t16 *= 16;
+#pragma unroll
+            for (int p = 0; p < 2; p++) glds16(abase + a_k * kBigHiTile + p * 64 * kGemmBK, static_cast<uint32_t>(t16), piece(a_buf(ia), p));
+        } else {
+            fill(abase + a_k * kGemmBK, a_last, a_buf(ia));
+        }
         ia ^= 1;
         if (++a_k == ksteps) {
             a_k = 0;
@@ -815,7 +843,7 @@ __device__ __forceinline__ void flat_gemm_big_body(
         }
     };
     auto stage_b = [&]() {
-        if (!(PROBE & 64)) fill_b(b_k * kGemmBK, 2 + ib);
+        if (!(PROBE & 64)) fill_b(b_k * kGemmBK, b_buf(ib));
         ib = ib + 1 == NB ? 0 : ib + 1;
         if (++b_k == ksteps) {
             b_k = 0;
@@ -834,8 +862,12 @@ __device__ __forceinline__ void flat_gemm_big_body(
         // (SPLIT: 0, 1 = the query image's hi granule of group 0, 1; 2, 3 = the rows' first granule of group 0, 1)
         const int gran = !SPLIT ? 2 * j + h : j < 2 ? 2 * j + h : 4 * (j - 2) + 2 * h;
         lpart[j] = (lane & 31) * kGemmBK + (gran ^ f) * 4;
+        // SCREEN's query tile: rows of 64 B, four to a 256-byte bank window, slot s of row R holds granule s ^ ((R >> 2) & 3).  The
+        // 16 lanes of a ds_read_b128 pass ({0-3, 12-15, 20-27}, {4-11, 16-19, 28-31} and the same + 32: one granule each) are
+        // every R & 3 four times, with R >> 2 = {0, 3, 5, 6} or {1, 2, 4, 7} — all four values of (R >> 2) & 3: 16 bank groups.
+        if (SCREEN && j < 2) lpart[j] = (lane & 31) * kARow + (gran ^ ((lane >> 2) & 3)) * 4;
     }
-    const int a_wave = wr * 128 * kGemmBK, b_wave = wc * 64 * kGemmBK;  // wave-uniform
+    const int a_wave = wr * 128 * kARow, b_wave = wc * 64 * kGemmBK;  // wave-uniform
 
     // Per tile: lane l keeps the thresholds of the wave's query rows l and 64 + l and the norm of its row column l, loaded a
     // matrix group before the tile starts; tile_init hands every lane those of ITS rows (32 i + (l & 31)) and columns
@@ -1118,11 +1150,13 @@ __device__ __forceinline__ void flat_gemm_big_body(
             for (int i = 0; i < 2; i++) fb[set][i] = *reinterpret_cast<const float4 *>(pb + i * 32 * kGemmBK);
         } else {
             // (lo granule = hi granule + 4, the row's second granule = its first + 1: slots ^ 4 and ^ 1, floats ^ 16 and ^ 4)
-            const int oa = a_wave + lpart[p >> 1] + 2 * (p & 1) * 32 * kGemmBK;
+            // (SCREEN: the compact image has no lo granules; its rows are kARow floats)
+            // (its group 1 granule is group 0's + 2: slot ^ 2, floats ^ 8 — one register for both)
+            const int oa = a_wave + (SCREEN ? lpart[0] ^ (8 * (p >> 1)) : lpart[p >> 1]) + 2 * (p & 1) * 32 * kARow;
 #pragma unroll
             for (int b = 0; b < 2; b++) {
-                fa[set][2 * b] = *reinterpret_cast<const float4 *>(As + oa + b * 32 * kGemmBK);
-                if constexpr (!SCREEN) fa[set][2 * b + 1] = *reinterpret_cast<const float4 *>(As + ((oa + b * 32 * kGemmBK) ^ 16));
+                fa[set][2 * b] = *reinterpret_cast<const float4 *>(As + oa + b * 32 * kARow);
+                if constexpr (!SCREEN) fa[set][2 * b + 1] = *reinterpret_cast<const float4 *>(As + ((oa + b * 32 * kARow) ^ 16));
             }
             if constexpr ((p & 1) == 0) {
                 const int ob = b_wave + lpart[2 + (p >> 1)];
@@ -1205,7 +1239,7 @@ __device__ __forceinline__ void flat_gemm_big_body(
     asm volatile("" ::: "memory");
     int ra = 0, rb = 0;  // buffers the current step is read from
     __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): no scalar load pending at the loop's entry (see the wait inside it)
-    read_part(gemm_lds, gemm_lds + 2 * kBigTile, P0{});
+    read_part(gemm_lds + a_buf(0), gemm_lds + b_buf(0), P0{});
     // Step g: the four operand groups of the step's tiles, group j+1 read from LDS while group j is multiplied; the fills of the
     // NEXT step's tiles — query tile g+1, row tile g+NB-1, into the buffers the barrier at the end of step g-1 freed — go out
     // behind the first two groups' matrix instructions (an LDS-DMA piece costs the issuing wave ~60 cycles: eight of them right
@@ -1215,7 +1249,7 @@ __device__ __forceinline__ void flat_gemm_big_body(
     // of the last matrix group and waits lgkmcnt(0) there, i.e. for the reads just issued — the overlap the rotation exists for.
     int t = 0;  // the K step of the tile being computed (c_pos)
     for (int g = 0; g < S; g++) {
-        const float *As = gemm_lds + ra * kBigTile, *Bs = gemm_lds + (2 + rb) * kBigTile;
+        const float *As = gemm_lds + a_buf(ra), *Bs = gemm_lds + b_buf(rb);
         const bool last = t == ksteps - 1;
         Pos n_pos = c_pos;
         if (last) {
@@ -1247,6 +1281,8 @@ __device__ __forceinline__ void flat_gemm_big_body(
         // the compiler's own counter bookkeeping sees: after it, it knows that no LDS read — and no scalar load, which would force
         // every later LDS wait to lgkmcnt(0) — is pending.  The DMA wait stays asm (the compiler knows nothing of the fills):
         // step g+1's tiles = everything this wave has in flight but (NB = 3) the row tile g+2 issued after query tile g+1.
+        // vmcnt(4) is that row tile's FOUR pieces, whatever the query tile took in front of them (four pieces, the compact
+        // image's two): vector-memory operations retire in order, and a wave's pieces per step are queries first, rows last.
         __builtin_amdgcn_s_waitcnt(0xC07F);
         if (NB == 3 && g + 2 < S)
             asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
@@ -1254,7 +1290,7 @@ __device__ __forceinline__ void flat_gemm_big_body(
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         if (!(PROBE & 8)) __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
-        if (!(PROBE & 16)) read_part(gemm_lds + ra * kBigTile, gemm_lds + (2 + rb) * kBigTile, P0{});
+        if (!(PROBE & 16)) read_part(gemm_lds + a_buf(ra), gemm_lds + b_buf(rb), P0{});
         __builtin_amdgcn_sched_barrier(0);
         mfma_part(P3{});  // part 3 of step g, from registers
         __builtin_amdgcn_sched_barrier(0);
