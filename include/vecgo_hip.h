@@ -38,7 +38,7 @@
  *     (batches that keep the scan), vg_search_rabitq, vg_search_hnsw, vg_search_hnsw_pq,
  *     vg_search_hnsw_filtered, vg_search_hnsw_predicate, vg_search_vamana (k <= 512),
  *     vg_search_vamana_filtered, vg_search_vamana_threshold, vg_rerank,
- *     vg_score_candidates — with stats == NULL where there is one.  (The first call of
+ *     vg_score_candidates, vg_filter_evaluate, vg_mask_combine, vg_mask_popcount — with stats == NULL where there is one.  (The first call of
  *     an entry on a stream may allocate its scratch; tests/test_gpu_device_buffers.py
  *     asserts the list.)
  *     These WAIT for `stream` inside the call, device buffers or not, because the host
@@ -107,7 +107,9 @@ extern "C" {
  *  vg_search_vamana_fresh, found by symbol lookup; and its delete path, vg_vamana_consolidate (with its caller-allocated
  *  vg_vamana_consolidate_stats), the same way.  Likewise vg_index_flat_retried and
  *  vg_index_flat_appended, found by symbol lookup.  Likewise the compaction's merge of resident indexes under tombstones,
- *  vg_index_merge, found by symbol lookup. */
+ *  vg_index_merge, found by symbol lookup.  Likewise the metadata filters evaluated on the device: vg_columns_create /
+ *  _destroy / _set_f64 / _set_codes / _drop, vg_filter_evaluate (with its caller-allocated vg_filter_clause),
+ *  vg_mask_combine, vg_mask_popcount and vg_mask_alloc / _free, found by symbol lookup. */
 #define VG_ABI_MINOR 13
 #define VG_INVALID_ID 0xFFFFFFFFu
 #define VG_STREAM_LEGACY ((void *)1) /* == hipStreamLegacy */
@@ -608,6 +610,98 @@ int32_t vg_index_set_vectors(vg_index *idx, const float *base, void *stream);
  *     count is read back). */
 int32_t vg_index_merge(vg_ctx *ctx, const vg_index *const *sources, const uint8_t *const *deleted, int32_t n_sources,
                        vg_index **out, uint32_t *old_to_new, int32_t *new_source, uint32_t *new_row, void *stream);
+
+/* ---- Metadata filters on the device: resident columns -> row masks ------------------
+ * Every filtered search of this header takes its filter as one bit per row (mask / mask_stride).  These calls make those
+ * bits on the device from the segment's metadata columns, so a filtered batch needs only its predicates from the host: the
+ * counterpart of simd.FilterRangeF64 / FilterRangeF64Indices / CountRangeF64 / GatherU32 (internal/simd/kernels.go:126-170)
+ * and of AndWords / AndNotWords / OrWords / XorWords / PopcountWords (bitmap.go:26-55).  (Present when the symbols are:
+ * see VG_ABI_MINOR.)
+ *
+ * Semantics: the reference's.  A filter set is the AND of its filters (internal/metadata/unified.go:279-416,
+ *   metadata.FilterSet); an empty filter set matches every row (:280-282); a filter on a field the segment has no column
+ *   for matches nothing (numeric_index.go:1065-1068, unified.go:318-321).
+ *   Numeric fields (f64 columns; ops eq ne lt lte gt gte): a row matches iff it has a value for the field and
+ *   compareFloat64(value, op, filterVal) holds (numeric_index.go:1020-1037, the definition MatchRowID uses); int values
+ *   are stored as float64(I64) (:1072-1076).  Rows without the field never match, `ne` included (the reference's `ne`
+ *   starts from the rows that have the field, :1176-1182, :1211-1228).  The reference's range path with math.Nextafter
+ *   (:488-497) equals the strict compare for every non-NaN value.  For a stored NaN under `ne` the reference's own paths
+ *   disagree: the bitmap path and compareFloat64 keep the row, the sorted column scan drops it.  THIS LIBRARY FOLLOWS
+ *   compareFloat64 (a stated choice): the compares are IEEE compares, -0 equals +0, a NaN filter value matches nothing
+ *   except under `ne`, where it matches every present row, and a stored NaN matches only `ne`.
+ *   Categorical fields (code columns; ops eq and in): the reference keeps one bitmap per (key, value) (unified.go:316-348,
+ *   getBitmapLocked :1614); the device form is one uint32 dictionary code per row, VG_INVALID_ID = the row has no value;
+ *   the value -> code dictionary is the host's.  `eq` matches the rows whose code is the clause's, `in` the rows whose
+ *   code is in the clause's set (duplicates allowed); an empty set matches nothing (:327-330); a row without a value
+ *   matches nothing, also when the clause names VG_INVALID_ID itself.  Any other op on a code column, and `in` on an f64
+ *   column, is VG_ERR_UNSUPPORTED.
+ *   deleted: NULL, or one bitmap for the batch (bit i of byte i/8 = row i is deleted, ceil(rows/8) bytes, any byte
+ *   address): cleared from every query's mask in the same pass ("tombstones are the caller's: clear their bits").
+ *   Out of scope, the host's: `contains`, string ranges, array-valued fields, block statistics; a mask made on the host
+ *   joins a device one through vg_mask_combine.  Columns do not follow writes: the host uploads a column again.
+ *
+ * vg_columns: the resident columns of ONE segment of `rows` rows (rows < 2^31, else VG_ERR_UNSUPPORTED), fields 0..63 (the
+ *   caller's handle for a key).  vg_columns_set_f64: values[rows]; present: bit i of byte i/8 = row i has a value, NULL =
+ *   every row.  vg_columns_set_codes: codes[rows].  Both copy (host or device source), replace whatever the field held
+ *   (f64 or codes) and wait for `stream`, as vg_index_set_* do; vg_columns_drop leaves the field without a column (it then
+ *   matches nothing); create / set / drop / destroy are serialised by the caller against evaluations of the same columns.
+ *   Memory: 8 (f64) or 4 (codes) bytes per row, rows rounded up to VG_FILTER_TILE_ROWS, plus one presence bit per row.
+ *
+ * vg_filter_evaluate: query q's filter set = clauses[clause_off[q] .. clause_off[q+1]); clause_off has nq + 1 entries.
+ *   Bytes written: exactly ceil(rows/8) bytes per query at mask + q * mask_stride; mask_stride >= that many bytes
+ *   (mask_stride == 0 only for nq <= 1); bits at positions >= rows in the last byte are zero; the bytes between
+ *   ceil(rows/8) and mask_stride are left untouched.  counts[q] = the set bits of query q's mask (the selectivity
+ *   numerator of vg_search_hnsw_filtered and of the flat searches' callers); may be NULL.
+ *   Pointers: host or device, each on its own; mask may sit at any byte address with any stride — 8-byte word stores
+ *   where mask and mask_stride are 8-byte aligned, byte stores otherwise, the same bits.  With every buffer on the device
+ *   the call only enqueues on `stream`; a host buffer makes it wait.
+ *   Limits: at most 16 clauses per query, at most 4096 codes per `in` set: beyond them VG_ERR_UNSUPPORTED with the number
+ *   in the message.  VG_ERR_INVALID_ARG: a field outside 0..63, an unknown op, a non-monotone or negative clause_off, a set
+ *   range outside [0, n_sets), NULL cols / clause_off / mask, mask_stride below ceil(rows/8).  These are tested on the
+ *   arrays the host can read, before any work; clause arrays in DEVICE memory are the caller's to keep well formed (the
+ *   call does not read them back: a query then takes at most its first 16 clauses, and a clause with a field outside
+ *   0..63, an op its column does not have or a set range outside `sets` matches nothing).  A valid field with no column
+ *   set is no error: it matches nothing.  nq == 0: VG_OK.  rows == 0: VG_OK, no mask byte is written, counts are 0.
+ *   Work: one kernel launch; a workgroup owns VG_FILTER_TILE_ROWS rows, stages the column slices its queries name in LDS
+ *   once and loops over its queries ("Filter evaluation").
+ *
+ * vg_mask_combine: dst[q] = dst[q] OP src[q] over the ceil(rows/8) bytes of each of nq masks (VG_MASK_ANDNOT: dst & ~src,
+ *   simd/bitmap.go:26-48); src_stride 0 = one src for every query (a host-made mask, a tombstone bitmap); whole bytes:
+ *   the last byte's bits at or above `rows` are combined like the others.  nq <= 65535.  dst and src must not overlap.
+ * vg_mask_popcount: counts[q] = the set bits below `rows` of mask + q * mask_stride (bitmap.go:50-55); bits at or above
+ *   `rows` that the caller left set in the last byte are not counted.  Both take host or device pointers at any byte
+ *   address (8-byte words where everything is 8-byte aligned, bytes otherwise and at the tail) and only enqueue when
+ *   every buffer is on the device.
+ * vg_mask_alloc / vg_mask_free: `bytes` of zero-filled device memory for masks, for a host that has no HIP binding of its own
+ *   (the cgo shim): what vg_filter_evaluate fills and the filtered searches read.  bytes == 0 gives NULL; freeing NULL is
+ *   VG_OK; vg_mask_free waits for the device. */
+#define VG_FILTER_TILE_ROWS 4096 /* rows of one workgroup of vg_filter_evaluate: the tests' row seams */
+typedef struct vg_columns vg_columns;
+int32_t vg_columns_create(vg_ctx *ctx, int64_t rows, vg_columns **out);
+int32_t vg_columns_destroy(vg_columns *cols);
+int32_t vg_columns_set_f64(vg_columns *cols, int32_t field, const double *values, const uint8_t *present, void *stream);
+int32_t vg_columns_set_codes(vg_columns *cols, int32_t field, const uint32_t *codes, void *stream);
+int32_t vg_columns_drop(vg_columns *cols, int32_t field);
+
+enum { VG_FILTER_EQ = 0, VG_FILTER_NE, VG_FILTER_LT, VG_FILTER_LTE, VG_FILTER_GT, VG_FILTER_GTE, VG_FILTER_IN };
+typedef struct vg_filter_clause { /* 32 bytes, caller-allocated */
+    int32_t field, op;
+    double value;                 /* f64 columns */
+    uint32_t code;                /* code columns, VG_FILTER_EQ */
+    int32_t set_begin, set_count; /* code columns, VG_FILTER_IN: sets[set_begin .. set_begin + set_count) */
+    int32_t reserved;             /* 0 */
+} vg_filter_clause;
+int32_t vg_filter_evaluate(vg_columns *cols, const vg_filter_clause *clauses, const int32_t *clause_off, int64_t nq,
+                           const uint32_t *sets, int64_t n_sets, const uint8_t *deleted, uint8_t *mask, int64_t mask_stride,
+                           int64_t *counts, void *stream);
+
+enum { VG_MASK_AND = 0, VG_MASK_ANDNOT, VG_MASK_OR, VG_MASK_XOR };
+int32_t vg_mask_combine(vg_ctx *ctx, int32_t op, uint8_t *dst, int64_t dst_stride, const uint8_t *src, int64_t src_stride,
+                        int64_t nq, int64_t rows, void *stream);
+int32_t vg_mask_popcount(vg_ctx *ctx, const uint8_t *mask, int64_t mask_stride, int64_t nq, int64_t rows, int64_t *counts,
+                         void *stream);
+int32_t vg_mask_alloc(vg_ctx *ctx, int64_t bytes, uint8_t **out);
+int32_t vg_mask_free(vg_ctx *ctx, uint8_t *mask);
 
 /* ---- L0 batch kernels: the dispatch seam (internal/simd/kernels.go:11-30) ------- */
 /* simd.SquaredL2Batch / simd.DotBatch (kernels.go:61-68 → batch_avx512.c:19-143):

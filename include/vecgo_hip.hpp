@@ -927,4 +927,111 @@ private:
     int dim_;
 };
 
+// ---- metadata filters on the device -------------------------------------------------------------------------------------
+namespace metadata {
+
+// metadata.Operator as vg_filter_clause.op
+enum class Op : int32_t { Eq = VG_FILTER_EQ, Ne = VG_FILTER_NE, Lt = VG_FILTER_LT, Lte = VG_FILTER_LTE, Gt = VG_FILTER_GT, Gte = VG_FILTER_GTE, In = VG_FILTER_IN };
+enum class MaskOp : int32_t { And = VG_MASK_AND, AndNot = VG_MASK_ANDNOT, Or = VG_MASK_OR, Xor = VG_MASK_XOR };
+
+// One metadata.Filter against a resident column: `value` is read for a float64 column, `code` (Eq) and `codes` (In) for a
+// dictionary-coded one; VG_INVALID_ID is the code of a value the dictionary does not hold (no row matches it).
+struct Filter {
+    int32_t field = 0;
+    Op op = Op::Eq;
+    double value = 0.0;
+    uint32_t code = VG_INVALID_ID;
+    std::vector<uint32_t> codes;
+};
+using FilterSet = std::vector<Filter>;  // metadata.FilterSet: the AND of its filters; empty = every row
+
+// The resident metadata columns of one segment (vg_columns).  The value -> code dictionary, Set / Delete bookkeeping and
+// uploading a column again after writes stay the host's.
+class Columns {
+public:
+    Columns(std::shared_ptr<Context> ctx, int64_t rows) : ctx_(std::move(ctx)), rows_(rows) { check(vg_columns_create(ctx_->handle(), rows, &h_)); }
+    ~Columns() { vg_columns_destroy(h_); }
+    Columns(const Columns &) = delete;
+    Columns &operator=(const Columns &) = delete;
+    // values[rows]; present: bit i of byte i/8 = row i has a value, nullptr = every row (ints as float64(I64))
+    void SetFloat64(int32_t field, const double *values, const uint8_t *present = nullptr) { check(vg_columns_set_f64(h_, field, values, present, nullptr)); }
+    // codes[rows], VG_INVALID_ID = the row has no value
+    void SetCodes(int32_t field, const uint32_t *codes) { check(vg_columns_set_codes(h_, field, codes, nullptr)); }
+    void Drop(int32_t field) { check(vg_columns_drop(h_, field)); }
+    int64_t rows() const { return rows_; }
+    vg_columns *handle() const { return h_; }
+    const std::shared_ptr<Context> &context() const { return ctx_; }
+
+private:
+    std::shared_ptr<Context> ctx_;
+    vg_columns *h_ = nullptr;
+    int64_t rows_;
+};
+
+// The row masks of a query batch in device memory (vg_mask_alloc): data() / stride() go to the searches' mask /
+// mask_stride as they are; counts[q] = the rows query q's filter set matches.
+class DeviceMasks {
+public:
+    DeviceMasks(std::shared_ptr<Context> ctx, int64_t nq, int64_t rows) : ctx_(std::move(ctx)), nq_(nq), rows_(rows), stride_(((rows + 7) / 8 + 7) & ~int64_t(7))
+    {
+        check(vg_mask_alloc(ctx_->handle(), nq_ * stride_, &p_));
+        counts.assign(static_cast<size_t>(nq), 0);
+    }
+    ~DeviceMasks() { vg_mask_free(ctx_->handle(), p_); }
+    DeviceMasks(const DeviceMasks &) = delete;
+    DeviceMasks &operator=(const DeviceMasks &) = delete;
+    uint8_t *data() const { return p_; }
+    int64_t stride() const { return stride_; }
+    int64_t size() const { return nq_; }
+    // mask[q] = mask[q] op hostMask for every q: joins a mask made on the host (`contains`, string ranges)
+    void Combine(MaskOp op, const uint8_t *hostMask)
+    {
+        check(vg_mask_combine(ctx_->handle(), static_cast<int32_t>(op), p_, stride_, hostMask, 0, nq_, rows_, nullptr));
+    }
+    // counts the masks again (after Combine)
+    const std::vector<int64_t> &Popcount()
+    {
+        if (nq_ > 0) check(vg_mask_popcount(ctx_->handle(), p_, stride_, nq_, rows_, counts.data(), nullptr));
+        return counts;
+    }
+    std::vector<int64_t> counts;
+
+private:
+    std::shared_ptr<Context> ctx_;
+    uint8_t *p_ = nullptr;
+    int64_t nq_, rows_, stride_;
+};
+
+// UnifiedIndex.EvaluateFilter (internal/metadata/unified.go:279-416) for a batch (vg_filter_evaluate): one mask per filter
+// set, the deleted rows (bit i of byte i/8, nullptr = none) cleared from every one.  Only the predicates cross to the device.
+inline std::unique_ptr<DeviceMasks> EvaluateFilters(const Columns &cols, const std::vector<FilterSet> &sets, const uint8_t *deleted = nullptr)
+{
+    std::vector<vg_filter_clause> clauses;
+    std::vector<int32_t> off{0};
+    std::vector<uint32_t> codes;
+    for (const FilterSet &fs : sets) {
+        for (const Filter &f : fs) {
+            vg_filter_clause c{};
+            c.field = f.field;
+            c.op = static_cast<int32_t>(f.op);
+            c.value = f.value;
+            c.code = f.code;
+            if (f.op == Op::In) {
+                c.set_begin = static_cast<int32_t>(codes.size());
+                c.set_count = static_cast<int32_t>(f.codes.size());
+                codes.insert(codes.end(), f.codes.begin(), f.codes.end());
+            }
+            clauses.push_back(c);
+        }
+        off.push_back(static_cast<int32_t>(clauses.size()));
+    }
+    const int64_t nq = static_cast<int64_t>(sets.size());
+    auto masks = std::make_unique<DeviceMasks>(cols.context(), nq, cols.rows());
+    check(vg_filter_evaluate(cols.handle(), clauses.empty() ? nullptr : clauses.data(), off.data(), nq, codes.empty() ? nullptr : codes.data(),
+                             static_cast<int64_t>(codes.size()), deleted, masks->data(), masks->stride(), masks->counts.data(), nullptr));
+    return masks;
+}
+
+}  // namespace metadata
+
 }  // namespace vecgo

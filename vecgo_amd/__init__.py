@@ -7,8 +7,10 @@ interfaces (distance.Metric, quantization.ProductQuantizer, ...).
 from .api import (BinaryQuantizer, Comm, Context, Index, Int4Quantizer, Metric, OptimizedProductQuantizer, ProductQuantizer, RaBitQuantizer, ScalarQuantizer, Segment, VecgoHipError, crc32c, crc32c_device,  # noqa: F401
                   compact, compaction_plan, dot_batch, find_closest_centroids, hamming_batch, heap_replay, kmeans_assign, kmeans_train,
                   merge_indexes, merge_topk, merge_topk_packed, normalize_l2, pq_adc_lookup_batch, squared_l2_batch,
-                  squared_l2_bounded_batch)
+                  squared_l2_bounded_batch,
+                  Columns, FilterOp, MaskOp, FILTER_CLAUSE, FILTER_TILE_ROWS, evaluate_filters, mask_combine, mask_popcount, pack_filter_sets)
 
 __all__ = ["BinaryQuantizer", "Comm", "Context", "Index", "Int4Quantizer", "Metric", "OptimizedProductQuantizer", "ProductQuantizer", "RaBitQuantizer", "ScalarQuantizer", "Segment", "VecgoHipError", "crc32c", "crc32c_device",
            "compact", "compaction_plan", "dot_batch", "find_closest_centroids", "hamming_batch", "heap_replay", "kmeans_assign", "kmeans_train",
-           "merge_indexes", "merge_topk", "merge_topk_packed", "normalize_l2", "pq_adc_lookup_batch", "squared_l2_batch", "squared_l2_bounded_batch"]
+           "merge_indexes", "merge_topk", "merge_topk_packed", "normalize_l2", "pq_adc_lookup_batch", "squared_l2_batch", "squared_l2_bounded_batch",
+           "Columns", "FilterOp", "MaskOp", "FILTER_CLAUSE", "FILTER_TILE_ROWS", "evaluate_filters", "mask_combine", "mask_popcount", "pack_filter_sets"]

@@ -1774,3 +1774,204 @@ def crc32c_device(ctx: Context, data, stream=None) -> int:
     check(ctx._lib.vg_crc32c_device(ctx._h, C.c_void_p(data.data_ptr()), C.c_int64(data.numel() * data.element_size()), C.byref(out),
                                     _stream_ptr(stream)))
     return int(out.value)
+
+
+# ---- metadata filters on the device (vg_columns_*, vg_filter_evaluate, vg_mask_*) ------------------------------------------
+FILTER_TILE_ROWS = 4096   # VG_FILTER_TILE_ROWS: the rows one workgroup of vg_filter_evaluate owns (the tests' row seams)
+
+
+class FilterOp(enum.IntEnum):
+    """metadata.Operator as vg_filter_clause.op (VG_FILTER_*)."""
+    EQ = 0
+    NE = 1
+    LT = 2
+    LTE = 3
+    GT = 4
+    GTE = 5
+    IN = 6
+
+
+class MaskOp(enum.IntEnum):
+    """VG_MASK_*: simd.AndWords / AndNotWords / OrWords / XorWords (internal/simd/bitmap.go:26-48)."""
+    AND = 0
+    ANDNOT = 1
+    OR = 2
+    XOR = 3
+
+
+# vg_filter_clause: 32 bytes, `reserved` 0
+FILTER_CLAUSE = np.dtype({"names": ["field", "op", "value", "code", "set_begin", "set_count", "reserved"],
+                          "formats": [np.int32, np.int32, np.float64, np.uint32, np.int32, np.int32, np.int32],
+                          "offsets": [0, 4, 8, 16, 20, 24, 28], "itemsize": 32})
+
+
+def pack_filter_sets(filter_sets):
+    """[[(field, op, value-or-codes), ...] per query] -> (clauses: FILTER_CLAUSE[total], clause_off: int32[nq + 1],
+    sets: uint32[n_sets]) as vg_filter_evaluate reads them.  op: a FilterOp, its number or its name ("eq" ... "in").  An
+    `in` filter's third entry is its codes, appended to `sets`.  Any other filter's third entry goes into BOTH operand
+    fields, since which one is read depends on the column behind the field: `value` = float(v), and `code` = v where v is
+    an integer in uint32 range (INVALID_ID otherwise: no row holds it)."""
+    clauses, off, sets = [], [0], []
+    for fs in filter_sets:
+        for field, op, operand in fs:
+            op = FilterOp[op.upper()] if isinstance(op, str) else FilterOp(int(op))
+            rec = np.zeros((), FILTER_CLAUSE)
+            rec["field"], rec["op"] = int(field), int(op)
+            if op == FilterOp.IN:
+                codes = np.asarray(operand, np.uint32).reshape(-1)
+                rec["set_begin"], rec["set_count"] = len(sets), codes.size
+                rec["code"] = INVALID_ID
+                sets.extend(codes.tolist())
+            else:
+                rec["value"] = float(operand)
+                integral = isinstance(operand, (int, np.integer)) and not isinstance(operand, bool) and 0 <= int(operand) <= INVALID_ID
+                rec["code"] = int(operand) if integral else INVALID_ID
+            clauses.append(rec)
+        off.append(len(clauses))
+    packed = np.array(clauses, FILTER_CLAUSE) if clauses else np.zeros(0, FILTER_CLAUSE)
+    return packed, np.asarray(off, np.int32), np.asarray(sets, np.uint32)
+
+
+def _packed_bits(x, rows, what):
+    """bool[rows] / packed little-endian bits (numpy uint8, or a torch uint8 tensor where it lies) -> (keepalive, void*)"""
+    if x is None:
+        return None, None
+    if _is_torch(x):
+        if x.dtype != torch.uint8:
+            raise TypeError(f"{what}: a torch bitmap holds packed bits (uint8), got {x.dtype}")
+        m = x if x.is_contiguous() else x.contiguous()
+        if m.numel() < (rows + 7) // 8:
+            raise ValueError(f"{what}: a packed bitmap holds ceil(rows / 8) = {(rows + 7) // 8} bytes, got {m.numel()}")
+        return m, C.c_void_p(m.data_ptr())
+    m = np.asarray(x)
+    if m.dtype == np.bool_:
+        if m.size != rows:
+            raise ValueError(f"{what}: a bool bitmap has one entry per row ({rows}), got {m.size}")
+        m = np.packbits(m.reshape(-1), bitorder="little")
+    m = np.ascontiguousarray(m, np.uint8)
+    if m.size < (rows + 7) // 8:
+        raise ValueError(f"{what}: a packed bitmap holds ceil(rows / 8) = {(rows + 7) // 8} bytes, got {m.size}")
+    return m, C.c_void_p(m.ctypes.data)
+
+
+class Columns:
+    """The resident metadata columns of one segment (vg_columns): per field 0..63 one f64 per row with a presence bitmap
+    (numeric fields) or one uint32 dictionary code per row (categorical fields; INVALID_ID = no value)."""
+
+    def __init__(self, ctx: Context, rows: int):
+        self._lib = ctx._lib
+        self._ctx = ctx
+        h = C.c_void_p()
+        check(self._lib.vg_columns_create(ctx._h, C.c_int64(rows), C.byref(h)))
+        self._h = h
+        self.rows = rows
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.vg_columns_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_f64(self, field: int, values, present=None, stream=None):
+        """values: float64[rows] (numpy, or a torch float64 tensor where it lies); present: bool[rows] / packed bits, None =
+        every row has a value.  Replaces whatever the field held."""
+        if _is_torch(values):
+            if values.dtype != torch.float64 or values.numel() != self.rows:
+                raise TypeError(f"set_f64: a float64 tensor of {self.rows} values, got {values.dtype} x {values.numel()}")
+            v = values.contiguous()
+            pv = C.c_void_p(v.data_ptr())
+        else:
+            v = np.ascontiguousarray(values, np.float64)
+            if v.size != self.rows:
+                raise ValueError(f"set_f64: one value per row ({self.rows}), got {v.size}")
+            pv = C.c_void_p(v.ctypes.data)
+        p, pp = _packed_bits(present, self.rows, "set_f64 (present)")
+        check(self._lib.vg_columns_set_f64(self._h, C.c_int32(field), pv, pp, _stream_ptr(stream)))
+
+    def set_codes(self, field: int, codes, stream=None):
+        """codes: uint32[rows] (numpy, or a torch int32 tensor where it lies), INVALID_ID = the row has no value."""
+        c, pc = _ptr(codes, np.uint32)
+        n = c.numel() if _is_torch(c) else c.size
+        if n != self.rows:
+            raise ValueError(f"set_codes: one code per row ({self.rows}), got {n}")
+        check(self._lib.vg_columns_set_codes(self._h, C.c_int32(field), pc, _stream_ptr(stream)))
+
+    def drop(self, field: int):
+        check(self._lib.vg_columns_drop(self._h, C.c_int32(field)))
+
+
+def _mask_batch(x, rows, what, writable=False):
+    """a batch of packed masks where it lies: uint8 [nq, stride >= ceil(rows / 8)] or [ceil(rows / 8)] (one mask), numpy or
+    torch, rows contiguous -> (keepalive, void*, nq, stride in bytes; 0 for a single 1-D mask)"""
+    nbytes = (rows + 7) // 8
+    if _is_torch(x):
+        if x.dtype != torch.uint8 or x.ndim not in (1, 2) or (x.numel() and x.stride(-1) != 1):
+            raise TypeError(f"{what}: packed masks are uint8 [nq, bytes] with contiguous rows")
+        shape, stride, ptr = tuple(x.shape), (x.stride(0) if x.ndim == 2 else 0), x.data_ptr()
+    else:
+        if not isinstance(x, np.ndarray) or x.dtype != np.uint8 or x.ndim not in (1, 2) or (x.size and x.strides[-1] != 1):
+            raise TypeError(f"{what}: packed masks are uint8 [nq, bytes] with contiguous rows")
+        if writable and not x.flags.writeable:
+            raise ValueError(f"{what}: the array is read-only")
+        shape, stride, ptr = x.shape, (x.strides[0] if x.ndim == 2 else 0), x.ctypes.data
+    if shape[-1] < nbytes:
+        raise ValueError(f"{what}: a mask holds ceil(rows / 8) = {nbytes} bytes, got {shape[-1]}")
+    return x, C.c_void_p(ptr), (shape[0] if len(shape) == 2 else 1), stride
+
+
+def evaluate_filters(cols: Columns, filter_sets, deleted=None, out=None, counts=True, stream=None):
+    """UnifiedIndex.EvaluateFilter (internal/metadata/unified.go:279-416) for a batch on the device (vg_filter_evaluate; the
+    semantics are the header's).  filter_sets: one list of (field, op, value-or-codes) per query (pack_filter_sets); deleted:
+    None / bool[rows] / packed bits, cleared from every mask.  out: None = a new torch uint8 tensor [nq, stride] on the
+    context's device (stride = ceil(rows / 8) rounded up to 8 bytes; pass it with mask.stride(0) to the filtered searches, or
+    as it is to Index.search_*_filtered), or a torch tensor / numpy array [nq, stride] to fill where it lies.
+    Returns (masks, counts): counts int64[nq] on the masks' side (torch or numpy), None with counts=False."""
+    clauses, off, sets = pack_filter_sets(filter_sets)
+    nq = off.size - 1
+    nbytes = (cols.rows + 7) // 8
+    if out is None:
+        if torch is None:
+            raise RuntimeError("evaluate_filters: out=None makes a torch tensor; pass a numpy array without torch")
+        out = torch.zeros((nq, (nbytes + 7) // 8 * 8), dtype=torch.uint8, device=f"cuda:{cols._ctx.device}")
+    m, pm, mq, stride = _mask_batch(out, cols.rows, "evaluate_filters (out)", writable=True)
+    if mq != nq:
+        raise ValueError(f"evaluate_filters: one mask per query ({nq}), out has {mq}")
+    cnt = pc = None
+    if counts:
+        cnt = torch.zeros(nq, dtype=torch.int64, device=out.device) if _is_torch(out) else np.zeros(nq, np.int64)
+        pc = C.c_void_p(cnt.data_ptr() if _is_torch(cnt) else cnt.ctypes.data)
+    d, pd = _packed_bits(deleted, cols.rows, "evaluate_filters (deleted)")
+    check(cols._lib.vg_filter_evaluate(cols._h, C.c_void_p(clauses.ctypes.data) if clauses.size else None, C.c_void_p(off.ctypes.data),
+                                       C.c_int64(nq), C.c_void_p(sets.ctypes.data) if sets.size else None, C.c_int64(sets.size), pd, pm,
+                                       C.c_int64(stride), pc, _stream_ptr(stream)))
+    return out, cnt
+
+
+def mask_combine(ctx: Context, op, dst, src, rows: int, stream=None):
+    """dst[q] = dst[q] OP src[q] in place over packed masks (vg_mask_combine; simd/bitmap.go:26-48).  dst: uint8 [nq, stride]
+    or one 1-D mask; src: the same shape, or one 1-D mask for every query (a host-made mask, a tombstone bitmap).  numpy
+    or torch, each on its own."""
+    op = MaskOp[op.upper()] if isinstance(op, str) else MaskOp(int(op))
+    d, pd, nq, dstride = _mask_batch(dst, rows, "mask_combine (dst)", writable=True)
+    s, ps, sq, sstride = _mask_batch(src, rows, "mask_combine (src)")
+    if sq != nq and not (sq == 1 and sstride == 0):
+        raise ValueError(f"mask_combine: src holds {sq} masks, dst {nq}")
+    if nq > 1 and dstride == 0:
+        dstride = (rows + 7) // 8
+    check(ctx._lib.vg_mask_combine(ctx._h, C.c_int32(int(op)), pd, C.c_int64(dstride), ps, C.c_int64(sstride if sq == nq and nq > 1 else 0),
+                                   C.c_int64(nq), C.c_int64(rows), _stream_ptr(stream)))
+    return dst
+
+
+def mask_popcount(ctx: Context, mask, rows: int, stream=None):
+    """int64[nq]: the set bits below `rows` of each packed mask (vg_mask_popcount; simd/bitmap.go:50-55), on the masks' side."""
+    m, pm, nq, stride = _mask_batch(mask, rows, "mask_popcount")
+    cnt = torch.zeros(nq, dtype=torch.int64, device=mask.device) if _is_torch(mask) else np.zeros(nq, np.int64)
+    pc = C.c_void_p(cnt.data_ptr() if _is_torch(cnt) else cnt.ctypes.data)
+    check(ctx._lib.vg_mask_popcount(ctx._h, pm, C.c_int64(stride), C.c_int64(nq), C.c_int64(rows), pc, _stream_ptr(stream)))
+    return cnt
