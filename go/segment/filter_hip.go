@@ -226,3 +226,46 @@ func (r *Resident) EvaluateFilters(cols *Columns, sets [][]Filter, deleted []byt
 	}
 	return m, nil
 }
+
+// MaskRows: FilterResult.ToArrayInto for the batch (vg_mask_to_rows; engine/search.go:617-627): per query the ids of the
+// rows its mask keeps, ascending, at most outStride of them, the rest of its outStride slots NoCode (VG_INVALID_ID) — the
+// block feeds Rerank as it is.  The masks' Counts are refreshed: all set bits, also past outStride.
+func (m *DeviceMasks) MaskRows(outStride int) ([]uint32, error) {
+	if outStride < 0 {
+		return nil, fmt.Errorf("segment: MaskRows: outStride %d is negative", outStride)
+	}
+	rows := make([]uint32, m.NQ*outStride)
+	if m.p == nil || m.NQ == 0 {
+		return rows, nil
+	}
+	var rp *C.uint32_t
+	if len(rows) > 0 {
+		rp = up(rows)
+	}
+	err := hipctx.Err(int32(C.vg_mask_to_rows(m.ctx, m.p, C.int64_t(m.Stride), C.int64_t(m.NQ), C.int64_t(m.rows), rp, C.int64_t(outStride), lp(m.Counts), nil)))
+	return rows, err
+}
+
+// SearchPrefilter: the engine's bitmap strategy over this segment (vg_search_flat_prefilter; engine/search.go:602-736):
+// only the rows a query's mask keeps are fetched and scored (distance.SquaredL2 / Dot), the best k by (Score, RowID) kept.
+// The host picks it, as Engine.SearchIter does (selectivityCutoff / adaptiveThreshold, :572-586), from the masks' Counts.
+// mask / maskStride as SearchFiltered's (DeviceMasks.Bytes() and Stride, or host bytes; maskStride 0 = one mask for the
+// batch); IVF partitions are ignored.  k <= 16384.
+func (r *Resident) SearchPrefilter(queries []float32, nq, k int, mask []byte, maskStride int) ([]uint32, []float32, error) {
+	ids, sc := r.out(nq, k)
+	need := (r.rows + 7) / 8
+	if maskStride != 0 {
+		if maskStride < need {
+			return nil, nil, fmt.Errorf("SearchPrefilter: maskStride %d is shorter than a mask (%d bytes)", maskStride, need)
+		}
+		need += (nq - 1) * maskStride
+	}
+	if mask == nil || len(mask) < need {
+		return nil, nil, fmt.Errorf("SearchPrefilter: mask holds %d bytes, %d needed", len(mask), need)
+	}
+	if nq == 0 || k == 0 {
+		return ids, sc, nil
+	}
+	st := C.vg_search_flat_prefilter(r.h, fp(queries), C.int64_t(nq), C.int32_t(k), bp(mask), C.int64_t(maskStride), up(ids), fp(sc), nil)
+	return ids, sc, hipctx.Err(int32(st))
+}

@@ -38,7 +38,7 @@
  *     (batches that keep the scan), vg_search_rabitq, vg_search_hnsw, vg_search_hnsw_pq,
  *     vg_search_hnsw_filtered, vg_search_hnsw_predicate, vg_search_vamana (k <= 512),
  *     vg_search_vamana_filtered, vg_search_vamana_threshold, vg_rerank,
- *     vg_score_candidates, vg_filter_evaluate, vg_mask_combine, vg_mask_popcount — with stats == NULL where there is one.  (The first call of
+ *     vg_score_candidates, vg_filter_evaluate, vg_mask_combine, vg_mask_popcount, vg_mask_to_rows — with stats == NULL where there is one.  (The first call of
  *     an entry on a stream may allocate its scratch; tests/test_gpu_device_buffers.py
  *     asserts the list.)
  *     These WAIT for `stream` inside the call, device buffers or not, because the host
@@ -47,7 +47,8 @@
  *     _compact, vg_vamana_build, vg_vamana_insert, vg_vamana_consolidate, vg_vamana_reorder_bfs, vg_flat_build, vg_diskann_build,
  *     vg_index_merge, vg_segment_*); vg_index_set_* and vg_index_enable_* (storage is replaced; the
  *     caller's buffer is free again at return); every getter; vg_search_hnsw_brute (reads
- *     its filter's population count and redo flags back); vg_search_sq8 and
+ *     its filter's population count and redo flags back); vg_search_flat_prefilter (reads its
+ *     masks' population counts back to size its row lists); vg_search_sq8 and
  *     vg_search_pq_adc when the bfloat16 nomination takes the batch, and
  *     vg_search_flat_threshold when its nomination does (the proofs' flags are read
  *     back); any call that is handed a host buffer, a stats array on the host included.
@@ -109,7 +110,8 @@ extern "C" {
  *  vg_index_flat_appended, found by symbol lookup.  Likewise the compaction's merge of resident indexes under tombstones,
  *  vg_index_merge, found by symbol lookup.  Likewise the metadata filters evaluated on the device: vg_columns_create /
  *  _destroy / _set_f64 / _set_codes / _drop, vg_filter_evaluate (with its caller-allocated vg_filter_clause),
- *  vg_mask_combine, vg_mask_popcount and vg_mask_alloc / _free, found by symbol lookup. */
+ *  vg_mask_combine, vg_mask_popcount and vg_mask_alloc / _free, found by symbol lookup.  Likewise the pre-filter search
+ *  (the engine's bitmap strategy): vg_mask_to_rows and vg_search_flat_prefilter, found by symbol lookup. */
 #define VG_ABI_MINOR 13
 #define VG_INVALID_ID 0xFFFFFFFFu
 #define VG_STREAM_LEGACY ((void *)1) /* == hipStreamLegacy */
@@ -702,6 +704,47 @@ int32_t vg_mask_popcount(vg_ctx *ctx, const uint8_t *mask, int64_t mask_stride, 
                          void *stream);
 int32_t vg_mask_alloc(vg_ctx *ctx, int64_t bytes, uint8_t **out);
 int32_t vg_mask_free(vg_ctx *ctx, uint8_t *mask);
+
+/* ---- pre-filter search: score only the rows a filter keeps -------------------------------------
+ * The engine's bitmap strategy (internal/engine/search.go:500-737): when a query's filter keeps few rows, Engine.SearchIter
+ * does not scan.  It turns the filter result into row ids (ToArrayInto, :617-627), drops tombstones and sorts the ids
+ * (:633-678), fetches exactly those rows and scores them with distance.SquaredL2 / distance.Dot (:699-713), and keeps the best
+ * searchK in one CandidateHeap (:717-733).  The host chooses this path, as the engine does (selectivityCutoff /
+ * adaptiveThreshold, :572-586), from the counts vg_filter_evaluate gave it; no other search of this header routes here.
+ * (Present when the symbols are: see VG_ABI_MINOR.)
+ *
+ * vg_mask_to_rows: ToArrayInto for a batch of masks.  Per query q the ids of the set bits below `rows` of
+ *   mask + q * mask_stride, ascending, go to out_rows + q * out_stride: at most out_stride of them; the slots from the number
+ *   written up to out_stride are set to VG_INVALID_ID, so the block feeds vg_rerank / vg_score_candidates as it is.
+ *   counts[q] = ALL set bits below `rows`, also when that exceeds out_stride (the caller sees a truncation); may be NULL.
+ *   Bits at or above `rows` in the last byte are ignored, as vg_mask_popcount ignores them.  Masks: any byte address and any
+ *   stride >= ceil(rows/8) (mask_stride == 0 only for nq <= 1); host or device pointers, each on its own; with every buffer
+ *   on the device the call only enqueues.  nq == 0 or rows == 0: VG_OK (counts 0, every slot VG_INVALID_ID).  out_stride == 0
+ *   with counts set is a count only.  rows < 2^31.  Work: a workgroup compacts VG_MASK_ROWS_TILE_ROWS rows of one mask (tile
+ *   counts, a scan per mask, a scatter: row order is kept and a single mask still spreads over the chip).
+ *
+ * vg_search_flat_prefilter: search.go:602-736 over ONE resident segment.  Query q's candidates are the rows whose bit is set
+ *   in its mask (mask_stride == 0: one mask for the batch; tombstones are the caller's: it clears their bits); each is scored
+ *   from the fp32 rows with distance.SquaredL2 (L2) or distance.Dot (Dot, Cosine) in squaredL2Avx512 / dotProductAvx512 order;
+ *   ids/scores[nq*k] = the best k by (Score, RowID), best first, padded with VG_INVALID_ID and +Inf (L2) / -Inf (Dot, Cosine).
+ *   IVF partitions on the index are IGNORED — the strategy fetches rows by id and never probes: on an index with at most one
+ *   partition the result equals vg_search_flat_filtered(..., VG_SCAN_F32, ...) bit for bit, on a partitioned one that of the
+ *   same rows without partitions.  Codes, graphs and nomination images on the index are neither needed nor touched.
+ *   NaN scores: the CandidateHeap replayed with the engine's `Pop(); Push(c)` at capacity (search.go:725-733; see "NaN scores").
+ *   k <= 16384 (searchK = k * RefineFactor is the caller's).  The call WAITS for `stream` once: the masks' population counts
+ *   size the row lists.  Query chunks keep lists and keys inside the context's scratch cap.  A listed row costs one
+ *   16-lane exact product per query; the list of a query is cut into chunks of VG_PREFILTER_CHUNK_ROWS rows, one workgroup
+ *   each; with one mask for the batch a workgroup stages its listed rows in LDS and scores them against a group of queries.
+ *   Refused before any work: NULL index / buffers, negative nq or k, mask == NULL (a search without a filter is
+ *   vg_search_flat), mask_stride below ceil(rows/8) with nq > 1: VG_ERR_INVALID_ARG; Hamming: VG_ERR_UNSUPPORTED; rows but no
+ *   fp32 rows: VG_ERR_NOT_READY; k > 16384: VG_ERR_UNSUPPORTED with the number in the message.  nq == 0 or k == 0 writes
+ *   nothing; an index of 0 rows gives padding only. */
+#define VG_MASK_ROWS_TILE_ROWS 8192 /* rows of one workgroup of the compaction (vg_mask_to_rows): the tests' row seams */
+#define VG_PREFILTER_CHUNK_ROWS 256 /* listed rows of one workgroup of vg_search_flat_prefilter's score kernels */
+int32_t vg_mask_to_rows(vg_ctx *ctx, const uint8_t *mask, int64_t mask_stride, int64_t nq, int64_t rows, uint32_t *out_rows,
+                        int64_t out_stride, int64_t *counts, void *stream);
+int32_t vg_search_flat_prefilter(vg_index *idx, const float *queries, int64_t nq, int32_t k, const uint8_t *mask,
+                                 int64_t mask_stride, uint32_t *ids, float *scores, void *stream);
 
 /* ---- L0 batch kernels: the dispatch seam (internal/simd/kernels.go:11-30) ------- */
 /* simd.SquaredL2Batch / simd.DotBatch (kernels.go:61-68 → batch_avx512.c:19-143):
@@ -1377,7 +1420,9 @@ int32_t vg_comm_all_gather_topk(vg_comm *comm, const uint32_t *local_ids, const 
  * `score < bound` pre-tests do not reproduce while the bound is +Inf) is answered a second time by the reference's
  * heap replayed operation by operation with float comparisons, rows in the reference's order, and overwrites the first answer.
  * ids / scores then hold what the engine takes out of the heap — Pop() until empty (engine/search.go:859-862) — best first; a
- * NaN score's sign and payload are the instruction set's, not the algorithm's.  Rare by construction (such inputs are garbage)
+ * NaN score's sign and payload are the instruction set's, not the algorithm's.  (vg_search_flat_prefilter replays the engine's OWN loop,
+ * search.go:717-733: the same test, but `Pop(); Push(c)` at capacity where flat/segment.go:719 does ReplaceTop — with a NaN in the
+ * heap the two leave different layouts and, later, different answers.)  Rare by construction (such inputs are garbage)
  * and slow by design: one workgroup walks all rows per query — measured at 1M x 768 (tools/nan_replay_time.py): a call of 1024
  * queries takes 11.6 ms with none at risk, 90 ms with one, 101 ms with 64, 698 ms with all of them; an index holding a non-finite
  * row sends EVERY query there.  Every other query pays one extra kernel launch per call that returns at once (the probed searches: two —

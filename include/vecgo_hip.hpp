@@ -670,6 +670,9 @@ public:
     }
     // Segment.Search with a row filter (flat/segment.go:631-635): mask bit i of byte i/8 = filter.Matches(i)
     Result SearchFiltered(const float *queries, int64_t nq, int k, int nprobes, int scan, const uint8_t *mask, int64_t mask_stride) { return run(nq, k, [&](Result &r) { return vg_search_flat_filtered(h_, queries, nq, k, nprobes, scan, mask, mask_stride, r.ids.data(), r.scores.data(), nullptr); }); }
+    // the engine's bitmap strategy (engine/search.go:602-736): only the rows the mask keeps are fetched and scored; the host picks it
+    // for selective filters from the masks' counts; partitions are ignored; k <= 16384
+    Result SearchPrefilter(const float *queries, int64_t nq, int k, const uint8_t *mask, int64_t mask_stride) { return run(nq, k, [&](Result &r) { return vg_search_flat_prefilter(h_, queries, nq, k, mask, mask_stride, r.ids.data(), r.scores.data(), nullptr); }); }
     Result SearchProbed(const float *queries, int64_t nq, int k, int nprobes, int scan) { return run(nq, k, [&](Result &r) { return vg_search_flat_probed(h_, queries, nq, k, nprobes, scan, r.ids.data(), r.scores.data(), nullptr); }); }
     // hnsw.Insert over the segment's rows (hnsw.go:713-984, ids and levels of ApplyInsert); replaces the segment's graph
     void BuildHNSW(int m = 32, int efConstruction = 300, int maxBatch = 8192, int growthDiv = 32)
@@ -993,6 +996,14 @@ public:
     {
         if (nq_ > 0) check(vg_mask_popcount(ctx_->handle(), p_, stride_, nq_, rows_, counts.data(), nullptr));
         return counts;
+    }
+    // FilterResult.ToArrayInto for the batch (vg_mask_to_rows): [size() * outStride] row ids, ascending per query, at most
+    // outStride each, the rest VG_INVALID_ID; counts is refreshed (all set bits, also past outStride)
+    std::vector<uint32_t> Rows(int64_t outStride)
+    {
+        std::vector<uint32_t> rows(static_cast<size_t>(nq_ * outStride));
+        if (nq_ > 0) check(vg_mask_to_rows(ctx_->handle(), p_, stride_, nq_, rows_, rows.empty() ? nullptr : rows.data(), outStride, counts.data(), nullptr));
+        return rows;
     }
     std::vector<int64_t> counts;
 

@@ -967,6 +967,18 @@ class Index:
                             extra=(C.c_int32(nprobes), C.c_int32(scan), pm, C.c_int64(stride)),
                             out=out, stream=stream)
 
+    def search_flat_prefilter(self, queries, k, mask, out=None, stream=None):
+        """The engine's bitmap strategy over this segment (vg_search_flat_prefilter; engine/search.go:602-736): only the rows
+        whose mask bit is set are fetched and scored (distance.SquaredL2 / Dot from the fp32 rows), the best k by (score, row
+        id) are kept.  mask: as search_flat_filtered's (one for the batch or one per query; required).  IVF partitions are
+        ignored: on an unpartitioned index the answer equals search_flat_filtered(..., scan=SCAN_F32) bit for bit.  The
+        cost follows the rows the masks keep, so this is the call for selective filters (INTEGRATION.md has the crossover);
+        it waits for the stream once.  k <= 16384."""
+        if mask is None:
+            raise ValueError("search_flat_prefilter: a mask is required (a search without a filter is search_flat)")
+        m, pm, stride = self._packed_mask(mask, _rows(queries, self.dim), "search_flat_prefilter")
+        return self._search(self._lib.vg_search_flat_prefilter, queries, k, extra=(pm, C.c_int64(stride)), out=out, stream=stream)
+
     def enable_pq_nomination(self, on: bool = True, stream=None):
         """vg_index_enable_pq_nomination: batches of search_pq_adc (queries x rows >= 24M, k <= 256, K = 256) are nominated by a bfloat16
         MFMA GEMM over the decoded rows (+ n * dim * 2 bytes), re-scored from the codes against the query's distance table in
@@ -1778,6 +1790,8 @@ def crc32c_device(ctx: Context, data, stream=None) -> int:
 
 # ---- metadata filters on the device (vg_columns_*, vg_filter_evaluate, vg_mask_*) ------------------------------------------
 FILTER_TILE_ROWS = 4096   # VG_FILTER_TILE_ROWS: the rows one workgroup of vg_filter_evaluate owns (the tests' row seams)
+MASK_ROWS_TILE_ROWS = 8192    # VG_MASK_ROWS_TILE_ROWS: the rows one workgroup of mask_to_rows compacts (the tests' row seams)
+PREFILTER_CHUNK_ROWS = 256    # VG_PREFILTER_CHUNK_ROWS: the listed rows one workgroup of search_flat_prefilter scores
 
 
 class FilterOp(enum.IntEnum):
@@ -1975,3 +1989,36 @@ def mask_popcount(ctx: Context, mask, rows: int, stream=None):
     pc = C.c_void_p(cnt.data_ptr() if _is_torch(cnt) else cnt.ctypes.data)
     check(ctx._lib.vg_mask_popcount(ctx._h, pm, C.c_int64(stride), C.c_int64(nq), C.c_int64(rows), pc, _stream_ptr(stream)))
     return cnt
+
+
+def mask_to_rows(ctx: Context, mask, rows: int, out_stride=None, out=None, counts=True, stream=None):
+    """FilterResult.ToArrayInto for a batch of packed masks (vg_mask_to_rows; engine/search.go:617-627): per mask the ids of
+    its set bits below `rows`, ascending, at most out_stride of them, the rest of its out_stride slots INVALID_ID — the
+    block feeds Index.rerank / score_candidates as it is.  mask: uint8 [nq, stride] or one 1-D mask, numpy or torch, where it
+    lies.  out: None = a new uint32 array [nq, out_stride] on the masks' side (torch: int32), or one to fill.  out_stride
+    None = out's, or the largest count (which costs a count first); 0 = count only.  Returns (ids, counts): counts int64[nq] =
+    ALL set bits of each mask, also past out_stride; None with counts=False."""
+    m, pm, nq, stride = _mask_batch(mask, rows, "mask_to_rows")
+    on_torch = _is_torch(mask)
+    if out is not None:
+        if out.ndim != 2 or out.shape[0] != nq:
+            raise ValueError(f"mask_to_rows: out is [nq = {nq}, out_stride], got {tuple(out.shape)}")
+        if out_stride is None:
+            out_stride = out.shape[1]
+        elif out_stride != out.shape[1]:
+            raise ValueError(f"mask_to_rows: out has {out.shape[1]} slots per mask, out_stride is {out_stride}")
+    elif out_stride is None:
+        c = mask_popcount(ctx, mask, rows, stream=stream)
+        out_stride = int(c.max()) if nq else 0
+    cnt = pc = None
+    if counts:
+        cnt = torch.zeros(nq, dtype=torch.int64, device=mask.device) if on_torch else np.zeros(nq, np.int64)
+        pc = C.c_void_p(cnt.data_ptr() if on_torch else cnt.ctypes.data)
+    if out is None:
+        out = torch.empty((nq, out_stride), dtype=torch.int32, device=mask.device) if on_torch else np.empty((nq, out_stride), np.uint32)
+    o, po = _ptr(out, np.uint32, nq * out_stride)
+    if o is not out:
+        raise ValueError("mask_to_rows: out must be contiguous")
+    check(ctx._lib.vg_mask_to_rows(ctx._h, pm, C.c_int64(stride), C.c_int64(nq), C.c_int64(rows), po if nq * out_stride else None,
+                                   C.c_int64(out_stride), pc, _stream_ptr(stream)))
+    return out, cnt

@@ -115,6 +115,21 @@ struct CandHeapPolicy {
     __device__ static CItem pop(CItem *h, int &len, bool desc) { return cand_pop(h, len, desc); }
 };
 
+// the engine's bitmap strategy (engine/search.go:725-733; vg_search_flat_prefilter, k_prefilter.hip): the same test, but at
+// capacity `Heap.Pop(); Heap.Push(c)` — the last item sifts down from the root, then the candidate sifts up from the end.  With
+// totally ordered scores that keeps the same SET as ReplaceTop; with NaN scores in the heap the two leave different layouts,
+// and the layout decides what a NaN lets through afterwards.
+struct CandHeapPopPushPolicy {
+    __device__ static bool accepts(const CItem x, int len, int k, const CItem root, bool desc) { return len < k || cand_better(x, root, desc); }
+    __device__ static void offer(CItem *h, int &len, int k, const CItem x, bool desc)
+    {
+        if (len >= k) (void)cand_pop(h, len, desc);  // h.Pop()
+        cand_up(h, len, x, desc);                    // h.Push(cand)
+        len++;
+    }
+    __device__ static CItem pop(CItem *h, int &len, bool desc) { return cand_pop(h, len, desc); }
+};
+
 // 16 waves score a step's rows (a row's score is a chain load -> arithmetic -> next row per 16-lane group or lane: the walk's pace is
 // how many of those chains run side by side — 256 threads: 114 ms for one query over 1M x 768, 1024: 90; tools/nan_replay_time.py)
 constexpr int kReplayThreads = 1024;
