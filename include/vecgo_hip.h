@@ -38,7 +38,7 @@
  *     (batches that keep the scan), vg_search_rabitq, vg_search_hnsw, vg_search_hnsw_pq,
  *     vg_search_hnsw_filtered, vg_search_hnsw_predicate, vg_search_vamana (k <= 512),
  *     vg_search_vamana_filtered, vg_search_vamana_threshold, vg_rerank,
- *     vg_score_candidates, vg_filter_evaluate, vg_mask_combine, vg_mask_popcount, vg_mask_to_rows — with stats == NULL where there is one.  (The first call of
+ *     vg_score_candidates, vg_filter_evaluate, vg_mask_combine, vg_mask_popcount, vg_mask_to_rows, vg_rrf_fuse — with stats == NULL where there is one.  (The first call of
  *     an entry on a stream may allocate its scratch; tests/test_gpu_device_buffers.py
  *     asserts the list.)
  *     These WAIT for `stream` inside the call, device buffers or not, because the host
@@ -48,7 +48,9 @@
  *     vg_index_merge, vg_segment_*); vg_index_set_* and vg_index_enable_* (storage is replaced; the
  *     caller's buffer is free again at return); every getter; vg_search_hnsw_brute (reads
  *     its filter's population count and redo flags back); vg_search_flat_prefilter (reads its
- *     masks' population counts back to size its row lists); vg_search_sq8 and
+ *     masks' population counts back to size its row lists); vg_bm25_create (like vg_index_set_*) and
+ *     vg_bm25_search (query term arrays in device memory are read back: the terms' list lengths size the
+ *     key lists); vg_search_sq8 and
  *     vg_search_pq_adc when the bfloat16 nomination takes the batch, and
  *     vg_search_flat_threshold when its nomination does (the proofs' flags are read
  *     back); any call that is handed a host buffer, a stats array on the host included.
@@ -111,7 +113,9 @@ extern "C" {
  *  vg_index_merge, found by symbol lookup.  Likewise the metadata filters evaluated on the device: vg_columns_create /
  *  _destroy / _set_f64 / _set_codes / _drop, vg_filter_evaluate (with its caller-allocated vg_filter_clause),
  *  vg_mask_combine, vg_mask_popcount and vg_mask_alloc / _free, found by symbol lookup.  Likewise the pre-filter search
- *  (the engine's bitmap strategy): vg_mask_to_rows and vg_search_flat_prefilter, found by symbol lookup. */
+ *  (the engine's bitmap strategy): vg_mask_to_rows and vg_search_flat_prefilter, found by symbol lookup.  Likewise hybrid
+ *  search (the lexical leg and the fusion of Engine.HybridSearch): vg_bm25_create / _destroy / _stats / _search / _replayed and
+ *  vg_rrf_fuse, found by symbol lookup. */
 #define VG_ABI_MINOR 13
 #define VG_INVALID_ID 0xFFFFFFFFu
 #define VG_STREAM_LEGACY ((void *)1) /* == hipStreamLegacy */
@@ -745,6 +749,75 @@ int32_t vg_mask_to_rows(vg_ctx *ctx, const uint8_t *mask, int64_t mask_stride, i
                         int64_t out_stride, int64_t *counts, void *stream);
 int32_t vg_search_flat_prefilter(vg_index *idx, const float *queries, int64_t nq, int32_t k, const uint8_t *mask,
                                  int64_t mask_stride, uint32_t *ids, float *scores, void *stream);
+
+/* ---- hybrid search: a resident BM25 index and Reciprocal Rank Fusion ---------------------------------
+ * Engine.HybridSearch (internal/engine/engine.go:1538-1640) takes a vector top-max(2k, 50) and a BM25 top-max(2k, 50) from
+ * lexical/bm25 (MemoryIndex.Search, bm25.go:282-381) and fuses them by Reciprocal Rank Fusion (:1560-1602).  The host keeps
+ * what is text: the tokeniser, the string -> term id dictionary, math.Log (the idf) and the doc / row -> primary key maps; the
+ * device gets the inverted index as CSR postings and answers batches.  (Present when the symbols are: see VG_ABI_MINOR.)
+ *
+ * vg_bm25: the resident index.  Term t's posting list is post_doc / post_tf[term_off[t] .. term_off[t + 1]) (docID, count:
+ *   bm25.go:18-21); doc_len[d] = idx.docLengths[d] (0 for a deleted doc's slot); total_length = idx.totalLength and
+ *   doc_count = idx.docCount (passed on their own because deleted docs keep a slot); doc_to_id[d] = the id doc d is reported
+ *   and fused under (one resident segment: its row id), NULL = d itself.  vg_bm25_create copies (each array from host or
+ *   device memory) and waits once; like the metadata columns the index does not follow writes: the host uploads it again.
+ *   STATED DEVIATION: every posting list must be in STRICTLY ASCENDING doc order.  The reference's lists are in insertion
+ *   order, and after deleteLocked's swap-remove (bm25.go:252-254) and the reuse of freed doc ids (:191-195) they can be out of
+ *   order; its document-at-a-time walk then meets such a doc more than once and scores it in pieces — an artefact, not a
+ *   contract.  The host sorts the lists before the upload (the cgo shim does).  Arrays in HOST memory are checked: a list out
+ *   of order, or a doc id >= n_docs, is VG_ERR_INVALID_ARG naming the term.  Arrays in DEVICE memory are NOT validated (the
+ *   call does not read them back): they are the caller's to keep well formed; term_off is read back and checked either way.
+ *   Limits: n_docs < 2^31 and fewer than 2^63 postings (VG_ERR_UNSUPPORTED with the number), doc_count >= 1
+ *   (VG_ERR_INVALID_ARG with the number: the reference answers nothing for an empty index, bm25.go:286).
+ *   vg_bm25_stats: docs, terms, postings and the resident bytes (any pointer may be NULL).
+ *
+ * vg_bm25_search: query q's terms are q_terms[q_term_off[q] .. q_term_off[q + 1]) (term ids; an id >= n_terms is a term the
+ *   dictionary does not have: an empty list, which contributes nothing, bm25.go:302) with one idf per entry in q_idf.  THE IDF
+ *   COMES FROM THE CALLER: computeIDF (:383-387) is math.Log in float64, and Go's Log is not the device's; the host computes
+ *   math.Log(1 + (N - n + 0.5) / (n + 0.5)) and the device multiplies by exactly those doubles.  A term named twice is two
+ *   iterators and adds twice.  The answer is MemoryIndex.Search's, bit for bit: per doc, in float64 and nothing fused,
+ *   num = tf * (k1 + 1), denom = tf + k1 * (1 - b) + (k1 * b / avgDL) * docLen, score += idf * (num / denom), the constants
+ *   formed as bm25.go:314-317 forms them, the terms added IN THE QUERY'S TERM ORDER; a doc takes part when its float64 score
+ *   is > 0; the heap compares float32(score).  out_ids[nq * k] (through doc_to_id) and out_scores[nq * k] best first,
+ *   out_counts[q] = min(k, hits) (NULL: not wanted), the tail VG_INVALID_ID / -Inf.
+ *   Ties: candidateHeap (:394-441) is a binary min-heap that compares scores only, so among equal scores its layout decides
+ *   (k = 2 and scores 1, 1, 2 in doc order answer [C, B], not [C, A]).  The key selection answers a query exactly when its
+ *   best k scores are pairwise different and no further doc shares the k-th score; every other query is replayed through the
+ *   reference's push / up / down / pop over its docs in ascending order.  vg_bm25_replayed: the queries replayed since
+ *   vg_bm25_create (waits for `stream`), as vg_index_flat_retried counts the flat search's.
+ *   Work: a workgroup owns VG_BM25_TILE_DOCS docs of one query (their float64 sums in LDS) and walks each term's sub-range
+ *   of that tile in term order; the docs with a score become keys; the best k of each list are selected as the threshold
+ *   searches select theirs.  The lists are sized by the terms' list lengths: the query arrays are read on the host, so query
+ *   arrays in device memory make the call wait for `stream` once; query chunks keep the lists inside the context's scratch cap.
+ *   Pointers: host or device, each on its own, element-aligned.  Limits: k <= 16384 and at most 64 terms per query, beyond
+ *   them VG_ERR_UNSUPPORTED with the number in the message.  nq == 0 or k == 0 writes nothing; a query without terms and
+ *   k > hits are served.
+ *
+ * vg_rrf_fuse: engine.go:1560-1602 for a batch.  Query q's list A is a_ids[q * a_stride ..] of a_counts[q] entries (cut to
+ *   a_stride), list B likewise; a NULL ids or counts pointer, or a count of 0, is an empty list; VG_INVALID_ID entries are
+ *   skipped but keep their rank.  Rank r of list A SETS the id's score to 1.0f / float32(rrf_k + r + 1) — an id named twice
+ *   in A keeps its last rank, as the map assignment does; every rank of list B then ADDS the same term in float32, in
+ *   ascending rank.  out_ids / out_scores[nq * k]: the k best by score descending, the tail VG_INVALID_ID / -Inf;
+ *   out_counts[q] = min(k, distinct ids) (NULL: not wanted).  TIES ARE DEFINED AS ASCENDING ID.  The reference sorts the
+ *   entries of a Go map with an unstable sort, so its order inside equal scores — and which ids of a tied group it cuts at
+ *   k — is undefined; the result here is always one of the answers the reference can give.  The division is correctly rounded.
+ *   One workgroup per query sorts the two lists' (id, source, rank) keys in LDS, combines equal ids and sorts (score, id).
+ *   Limit: a_count + b_count <= 16384 per query (128 KiB of keys; HybridSearch up to k = 4096) and k <= 16384, beyond them
+ *   VG_ERR_UNSUPPORTED with the number; counts in device memory are not read back: their strides are taken as the counts.
+ *   With every buffer on the device the call only enqueues. */
+#define VG_BM25_TILE_DOCS 8192 /* docs of one workgroup of vg_bm25_search's score kernel: the tests' doc seams */
+typedef struct vg_bm25 vg_bm25;
+int32_t vg_bm25_create(vg_ctx *ctx, int64_t n_docs, int64_t n_terms, const int64_t *term_off, const uint32_t *post_doc,
+                       const uint32_t *post_tf, const uint32_t *doc_len, int64_t total_length, int64_t doc_count,
+                       const uint32_t *doc_to_id, vg_bm25 **out);
+int32_t vg_bm25_destroy(vg_bm25 *bm);
+int32_t vg_bm25_stats(vg_bm25 *bm, int64_t *docs, int64_t *terms, int64_t *postings, int64_t *bytes);
+int32_t vg_bm25_search(vg_bm25 *bm, const int32_t *q_term_off, const uint32_t *q_terms, const double *q_idf, int64_t nq, int32_t k,
+                       uint32_t *out_ids, float *out_scores, int32_t *out_counts, void *stream);
+int32_t vg_bm25_replayed(vg_bm25 *bm, int64_t *replayed, void *stream);
+int32_t vg_rrf_fuse(vg_ctx *ctx, int64_t nq, const uint32_t *a_ids, const int32_t *a_counts, int64_t a_stride, const uint32_t *b_ids,
+                    const int32_t *b_counts, int64_t b_stride, int32_t rrf_k, int32_t k, uint32_t *out_ids, float *out_scores,
+                    int32_t *out_counts, void *stream);
 
 /* ---- L0 batch kernels: the dispatch seam (internal/simd/kernels.go:11-30) ------- */
 /* simd.SquaredL2Batch / simd.DotBatch (kernels.go:61-68 → batch_avx512.c:19-143):

@@ -1045,4 +1045,78 @@ inline std::unique_ptr<DeviceMasks> EvaluateFilters(const Columns &cols, const s
 
 }  // namespace metadata
 
+// ---- hybrid search: the resident BM25 index and Reciprocal Rank Fusion ---------------------------------------------------
+namespace lexical {
+
+// What a batch of lexical or fused searches answers: [nq * k] ids / scores best first (VG_INVALID_ID / -Inf behind a short
+// list) and the hits per query.
+struct Hits {
+    std::vector<uint32_t> ids;
+    std::vector<float> scores;
+    std::vector<int32_t> counts;
+};
+
+// lexical/bm25.MemoryIndex resident on the device (vg_bm25): CSR postings in strictly ascending doc order (host arrays are
+// checked), doc lengths, idx.totalLength / idx.docCount and the doc -> id map (nullptr: the doc id itself).  The tokeniser, the
+// term dictionary and the idf stay the host's; the index does not follow writes: make a new one.
+class Bm25 {
+public:
+    Bm25(std::shared_ptr<Context> ctx, int64_t nDocs, const std::vector<int64_t> &termOff, const std::vector<uint32_t> &postDoc,
+         const std::vector<uint32_t> &postTf, const std::vector<uint32_t> &docLen, int64_t totalLength, int64_t docCount,
+         const uint32_t *docToId = nullptr)
+        : ctx_(std::move(ctx))
+    {
+        check(vg_bm25_create(ctx_->handle(), nDocs, static_cast<int64_t>(termOff.size()) - 1, termOff.data(), postDoc.data(), postTf.data(), docLen.data(),
+                             totalLength, docCount, docToId, &h_));
+    }
+    ~Bm25() { vg_bm25_destroy(h_); }
+    Bm25(const Bm25 &) = delete;
+    Bm25 &operator=(const Bm25 &) = delete;
+    // MemoryIndex.Search for a batch: query q's term ids termIds[termOff[q] .. termOff[q + 1]) with the caller's idf
+    // (math.Log(1 + (N - n + 0.5) / (n + 0.5))) per entry
+    Hits Search(const std::vector<int32_t> &termOff, const std::vector<uint32_t> &termIds, const std::vector<double> &idf, int k)
+    {
+        const int64_t nq = static_cast<int64_t>(termOff.size()) - 1;
+        Hits r;
+        r.ids.resize(static_cast<size_t>(nq) * k);
+        r.scores.resize(static_cast<size_t>(nq) * k);
+        r.counts.assign(static_cast<size_t>(nq), 0);
+        check(vg_bm25_search(h_, termOff.data(), termIds.data(), idf.data(), nq, k, r.ids.data(), r.scores.data(), r.counts.data(), nullptr));
+        return r;
+    }
+    // the queries whose tied scores went through the reference's heap on the device
+    int64_t Replayed()
+    {
+        int64_t n = 0;
+        check(vg_bm25_replayed(h_, &n, nullptr));
+        return n;
+    }
+    int64_t ResidentBytes()
+    {
+        int64_t bytes = 0;
+        check(vg_bm25_stats(h_, nullptr, nullptr, nullptr, &bytes));
+        return bytes;
+    }
+    vg_bm25 *handle() const { return h_; }
+
+private:
+    std::shared_ptr<Context> ctx_;
+    vg_bm25 *h_ = nullptr;
+};
+
+// The fusion of Engine.HybridSearch (engine.go:1560-1602) for a batch (vg_rrf_fuse): list A sets 1 / float32(rrfK + rank + 1)
+// per id, list B adds it; the best k by score, ties by ascending id.
+inline Hits FuseRRF(Context &ctx, int64_t nq, const uint32_t *aIds, const int32_t *aCounts, int64_t aStride, const uint32_t *bIds,
+                    const int32_t *bCounts, int64_t bStride, int rrfK, int k)
+{
+    Hits r;
+    r.ids.resize(static_cast<size_t>(nq) * k);
+    r.scores.resize(static_cast<size_t>(nq) * k);
+    r.counts.assign(static_cast<size_t>(nq), 0);
+    check(vg_rrf_fuse(ctx.handle(), nq, aIds, aCounts, aStride, bIds, bCounts, bStride, rrfK, k, r.ids.data(), r.scores.data(), r.counts.data(), nullptr));
+    return r;
+}
+
+}  // namespace lexical
+
 }  // namespace vecgo

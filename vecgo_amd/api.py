@@ -2022,3 +2022,166 @@ def mask_to_rows(ctx: Context, mask, rows: int, out_stride=None, out=None, count
     check(ctx._lib.vg_mask_to_rows(ctx._h, pm, C.c_int64(stride), C.c_int64(nq), C.c_int64(rows), po if nq * out_stride else None,
                                    C.c_int64(out_stride), pc, _stream_ptr(stream)))
     return out, cnt
+
+
+# ---- hybrid search: the resident BM25 index and Reciprocal Rank Fusion (vg_bm25_*, vg_rrf_fuse) ------------------------------
+BM25_TILE_DOCS = 8192   # VG_BM25_TILE_DOCS: the docs one workgroup of Bm25.search scores (the tests' doc seams)
+
+
+def _ptr_f64(x, count):
+    """(keepalive, void*) of float64 values: numpy, or a torch float64 tensor where it lies"""
+    if _is_torch(x):
+        if x.dtype != torch.float64:
+            raise TypeError(f"expected torch.float64, got {x.dtype}")
+        x = x if x.is_contiguous() else x.contiguous()
+        n, p = x.numel(), x.data_ptr()
+    else:
+        x = np.ascontiguousarray(x, np.float64)
+        n, p = x.size, x.ctypes.data
+    if n < count:
+        raise ValueError(f"buffer has {n} elements, need {count}")
+    return x, C.c_void_p(p)
+
+
+def _result_buffers(out, nq, k, like, device, counts=True):
+    """ids uint32 / scores float32 [nq, k] and counts int32 [nq] (numpy, or torch on `device` when `like` is a torch tensor)"""
+    if out is not None:
+        return out
+    if _is_torch(like):
+        dev = like.device if like.is_cuda else f"cuda:{device}"
+        return (torch.empty((nq, k), dtype=torch.int32, device=dev), torch.empty((nq, k), dtype=torch.float32, device=dev),
+                torch.zeros(nq, dtype=torch.int32, device=dev) if counts else None)
+    return np.empty((nq, k), np.uint32), np.empty((nq, k), np.float32), (np.zeros(nq, np.int32) if counts else None)
+
+
+class Bm25:
+    """A resident lexical/bm25 MemoryIndex (vg_bm25): CSR postings, doc lengths and the doc -> id map.  The tokeniser, the
+    string -> term id dictionary and the idf (math.Log) stay the host's; posting lists are in strictly ascending doc order
+    (host arrays are checked).  The index does not follow writes: build a new one."""
+
+    def __init__(self, ctx: Context, term_off, post_doc, post_tf, doc_len, total_length: int, doc_count: int, doc_to_id=None):
+        self._lib = ctx._lib
+        self._ctx = ctx
+        to, pto = _ptr(term_off, np.int64)
+        self.n_terms = (to.numel() if _is_torch(to) else to.size) - 1
+        dl, pdl = _ptr(doc_len, np.uint32)
+        self.n_docs = dl.numel() if _is_torch(dl) else dl.size
+        pd, ppd = _ptr(post_doc, np.uint32)
+        pt, ppt = _ptr(post_tf, np.uint32)
+        if (pd.numel() if _is_torch(pd) else pd.size) != (pt.numel() if _is_torch(pt) else pt.size):
+            raise ValueError("Bm25: post_doc and post_tf hold one entry per posting each")
+        di, pdi = _ptr(doc_to_id, np.uint32, self.n_docs) if doc_to_id is not None else (None, None)
+        if self.n_terms < 0:
+            raise ValueError("Bm25: term_off has n_terms + 1 entries")
+        h = C.c_void_p()
+        check(self._lib.vg_bm25_create(ctx._h, C.c_int64(self.n_docs), C.c_int64(self.n_terms), pto, ppd, ppt, pdl, C.c_int64(total_length),
+                                       C.c_int64(doc_count), pdi, C.byref(h)))
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.vg_bm25_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def stats(self):
+        """{docs, terms, postings, bytes} of the resident index (vg_bm25_stats)"""
+        v = [C.c_int64(0) for _ in range(4)]
+        check(self._lib.vg_bm25_stats(self._h, *[C.byref(x) for x in v]))
+        return dict(zip(("docs", "terms", "postings", "bytes"), (x.value for x in v)))
+
+    def replayed(self, stream=None) -> int:
+        """vg_bm25_replayed: the queries since the index was made whose ties sent them through the reference's heap"""
+        r = C.c_int64(0)
+        check(self._lib.vg_bm25_replayed(self._h, C.byref(r), _stream_ptr(stream)))
+        return r.value
+
+    def search(self, q_term_off, q_terms, q_idf, k: int, out=None, stream=None):
+        """MemoryIndex.Search for a batch (vg_bm25_search): query q's term ids q_terms[q_term_off[q] : q_term_off[q + 1]] with
+        one float64 idf each (the caller's math.Log).  Returns (ids uint32 [nq, k] through doc_to_id, scores float32 [nq, k]
+        best first, counts int32 [nq]); the tail is INVALID_ID / -inf.  numpy or torch, each on its own; out: the three
+        arrays to fill.  k <= 16384, at most 64 terms per query."""
+        qo, pqo = _ptr(q_term_off, np.int32)
+        nq = (qo.numel() if _is_torch(qo) else qo.size) - 1
+        if nq < 0:
+            raise ValueError("Bm25.search: q_term_off has nq + 1 entries")
+        qt, pqt = _ptr(q_terms, np.uint32)
+        nt = qt.numel() if _is_torch(qt) else qt.size
+        qi, pqi = _ptr_f64(q_idf, nt)
+        ids, scores, counts = _result_buffers(out, nq, k, qo, self._ctx.device)
+        i, pi = _ptr(ids, np.uint32, nq * k)
+        s, ps = _ptr(scores, np.float32, nq * k)
+        c, pc = _ptr(counts, np.int32, nq)
+        if i is not ids or s is not scores or c is not counts:
+            raise ValueError("Bm25.search: out must be contiguous arrays of uint32 / float32 / int32")
+        check(self._lib.vg_bm25_search(self._h, pqo, pqt if nt else None, pqi if nt else None, C.c_int64(nq), C.c_int32(k), pi, ps, pc,
+                                       _stream_ptr(stream)))
+        return ids, scores, counts
+
+
+def rrf_fuse(ctx: Context, a_ids, a_counts, b_ids, b_counts, k: int, rrf_k: int = 60, out=None, stream=None):
+    """The Reciprocal Rank Fusion of Engine.HybridSearch (vg_rrf_fuse; engine.go:1560-1602) for a batch: a_ids / b_ids uint32
+    [nq, stride] with a_counts / b_counts int32 [nq] entries each (None for a side: empty lists); rank r of A sets
+    1 / float32(rrf_k + r + 1), every rank of B adds it.  Returns (ids [nq, k], scores [nq, k] best first, ties by ascending
+    id, counts int32 [nq]).  At most 16384 entries per query in both lists together."""
+    def side(ids, counts, what):
+        if ids is None or counts is None:
+            return None, None, None, None, 0, None
+        if ids.ndim != 2:
+            raise ValueError(f"rrf_fuse: {what} ids are [nq, stride]")
+        i, pi = _ptr(ids, np.uint32)
+        c, pc = _ptr(counts, np.int32, ids.shape[0])
+        return i, pi, c, pc, int(ids.shape[1]), int(ids.shape[0])
+    a, pa, ca, pca, sa, na = side(a_ids, a_counts, "a")
+    b, pb, cb, pcb, sb, nb = side(b_ids, b_counts, "b")
+    if na is None and nb is None:
+        raise ValueError("rrf_fuse: both sides are None")
+    nq = na if na is not None else nb
+    if nb is not None and na is not None and na != nb:
+        raise ValueError(f"rrf_fuse: a holds {na} queries, b {nb}")
+    ids, scores, counts = _result_buffers(out, nq, k, a if a is not None else b, ctx.device)
+    i, pi = _ptr(ids, np.uint32, nq * k)
+    s, ps = _ptr(scores, np.float32, nq * k)
+    c, pc = _ptr(counts, np.int32, nq)
+    if i is not ids or s is not scores or c is not counts:
+        raise ValueError("rrf_fuse: out must be contiguous arrays of uint32 / float32 / int32")
+    check(ctx._lib.vg_rrf_fuse(ctx._h, C.c_int64(nq), pa, pca, C.c_int64(sa), pb, pcb, C.c_int64(sb), C.c_int32(rrf_k), C.c_int32(k), pi, ps, pc,
+                               _stream_ptr(stream)))
+    return ids, scores, counts
+
+
+def hybrid_search(index: Index, bm: Bm25, queries, q_term_off, q_terms, q_idf, k: int, rrf_k: int = 60, stream=None):
+    """Engine.HybridSearch for a batch over one resident segment (engine.go:1538-1602): the vector top-max(2k, 50) of
+    index.search_flat and the BM25 top-max(2k, 50) of bm.search, fused by rrf_fuse, all on one stream; the two legs' lists
+    never leave the device.  bm's doc_to_id maps docs to the index's row ids.  queries: float32 [nq, dim], numpy or torch.
+    Returns (ids, scores, counts) as torch tensors on the device."""
+    if torch is None:
+        raise RuntimeError("hybrid_search keeps its intermediate lists in torch device tensors")
+    dev = f"cuda:{index.ctx.device}"
+    vk = max(2 * k, 50)
+    nq = _rows(queries, index.dim)
+    q = queries if _is_torch(queries) and queries.is_cuda else torch.as_tensor(np.ascontiguousarray(queries, np.float32)).to(dev)
+    with torch.cuda.stream(stream) if isinstance(stream, torch.cuda.Stream) else _null_ctx():
+        v_ids = torch.empty((nq, vk), dtype=torch.int32, device=q.device)
+        v_sc = torch.empty((nq, vk), dtype=torch.float32, device=q.device)
+        index.search_flat(q, vk, out=(v_ids, v_sc), stream=stream)
+        v_cnt = torch.full((nq,), vk, dtype=torch.int32, device=q.device)   # (search_flat pads with INVALID_ID, which the fusion skips)
+        l_out = (torch.empty((nq, vk), dtype=torch.int32, device=q.device), torch.empty((nq, vk), dtype=torch.float32, device=q.device),
+                 torch.zeros(nq, dtype=torch.int32, device=q.device))
+        l_ids, _, l_cnt = bm.search(q_term_off, q_terms, q_idf, vk, out=l_out, stream=stream)
+        out = (torch.empty((nq, k), dtype=torch.int32, device=q.device), torch.empty((nq, k), dtype=torch.float32, device=q.device),
+               torch.zeros(nq, dtype=torch.int32, device=q.device))
+        return rrf_fuse(index.ctx, v_ids, v_cnt, l_ids, l_cnt, k, rrf_k=rrf_k, out=out, stream=stream)
+
+
+class _null_ctx:
+    def __enter__(self):
+        return None
+
+    def __exit__(self, *a):
+        return False

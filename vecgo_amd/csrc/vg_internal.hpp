@@ -103,6 +103,7 @@ enum Hook {
     kHookFlatScreenFail,      // VG_FLAT_SCREEN_FAIL     vg_search_flat behind a screen: every screen proof counts as failed, every query is retried on the split tile (and the screen runs up to k = 48, not 16)
     kHookFlatF32Sample,       // VG_FLAT_F32_SAMPLE      vg_search_flat on the split tile: the threshold sample stays the fp32 128 x 128 tile's, not the persistent tile's one bf16 product
     kHookPrefilterSmallScratch,  // VG_PREFILTER_SMALL_SCRATCH vg_search_flat_prefilter cuts its query chunks for 64 KiB of lists and keys, not the context's scratch cap: a test batch takes the several chunks a large one takes
+    kHookBm25SmallScratch,    // VG_BM25_SMALL_SCRATCH vg_bm25_search cuts its query chunks for 64 KiB of keys, not the context's scratch cap: a test batch takes the several chunks a large one takes
     kHookCount
 };
 bool hook(Hook h);
