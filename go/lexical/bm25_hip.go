@@ -3,9 +3,13 @@
 // A lexical.Index whose Search runs on the device: the resident BM25 index (vg_bm25) behind the interface of
 // lexical/bm25.MemoryIndex, and the Reciprocal Rank Fusion of Engine.HybridSearch (internal/engine/engine.go:1560-1602) for
 // a batch.  The seams are WithLexicalIndex (the engine takes any lexical.Index) and the fusion loop of HybridSearch.  What is
-// text stays here: the tokeniser, the term dictionary, math.Log for the idf and the doc -> primary key map.  The device
-// index does not follow writes: Add and Delete mark it dirty and the next Search uploads it again, its posting lists sorted
-// by doc (the library requires ascending lists; see vecgo_hip.h for why the reference's insertion order is not kept).
+// text stays here: the tokeniser, the term dictionary, math.Log for the idf and the doc -> primary key map.  Writes follow
+// the index onto the device: Add and Delete queue into a pending batch, and the next Search flushes it with ONE
+// vg_bm25_update (the first flush into a vg_bm25_create_empty index), which rewrites the resident image on the device;
+// nothing is sorted or uploaded again.  For that the dictionary is APPEND-ONLY: a term keeps its id for good, a term whose
+// list has emptied keeps an empty range on the device and is skipped in a query (the reference deletes the list,
+// bm25.go:259-261).  The document frequencies come from the host's own lists.  upload() — the whole image from host arrays,
+// lists sorted by doc, as vg_bm25_create wants them — remains as the recovery path after a failed update.
 package lexical
 
 /*
@@ -43,13 +47,15 @@ type HipIndex struct {
 	freeDocs   []uint32
 	docLengths []uint32
 	docTerms   [][]string
+	docTf      [][]uint32 // the counts of docTerms, entry for entry
 	inverted   map[string][]hipPosting
-	dict       map[string]uint32 // term -> id of the uploaded image
-	df         []int             // list length per term id of the uploaded image
+	dict       map[string]uint32 // term -> id: append-only, ids are never reassigned
+	resident   []bool            // per doc: does the device image hold a document in this slot?
+	touched    map[uint32]bool   // the pending batch: doc -> resident[doc] when the batch first touched it
 
 	totalLength int64
 	docCount    int
-	dirty       bool
+	dirty       bool // the device image cannot be trusted (a failed update): the next Search rebuilds it with upload()
 }
 
 var _ Index = (*HipIndex)(nil)
@@ -95,7 +101,8 @@ func NewHipIndex() (*HipIndex, error) {
 	if err != nil {
 		return nil, err
 	}
-	return &HipIndex{ctx: (*C.vg_ctx)(p), pkToDoc: map[model.ID]uint32{}, inverted: map[string][]hipPosting{}}, nil
+	return &HipIndex{ctx: (*C.vg_ctx)(p), pkToDoc: map[model.ID]uint32{}, inverted: map[string][]hipPosting{}, dict: map[string]uint32{},
+		touched: map[uint32]bool{}}, nil
 }
 
 // tokens: whitespace-separated, lower-cased; pure ASCII text splits at every byte up to ' ' and lowers A-Z only, other
@@ -144,7 +151,10 @@ func (x *HipIndex) Add(id model.ID, text string) error {
 		x.docToPK = append(x.docToPK, id)
 		x.docLengths = append(x.docLengths, 0)
 		x.docTerms = append(x.docTerms, nil)
+		x.docTf = append(x.docTf, nil)
+		x.resident = append(x.resident, false)
 	}
+	x.touch(doc)
 	x.pkToDoc[id] = doc
 	tf := map[string]uint32{}
 	length := 0
@@ -156,13 +166,25 @@ func (x *HipIndex) Add(id model.ID, text string) error {
 	x.totalLength += int64(length)
 	x.docCount++
 	terms := make([]string, 0, len(tf))
+	counts := make([]uint32, 0, len(tf))
 	for t, c := range tf {
 		terms = append(terms, t)
+		counts = append(counts, c)
 		x.inverted[t] = append(x.inverted[t], hipPosting{doc: doc, tf: c})
+		if _, ok := x.dict[t]; !ok {
+			x.dict[t] = uint32(len(x.dict))
+		}
 	}
 	x.docTerms[doc] = terms
-	x.dirty = true
+	x.docTf[doc] = counts
 	return nil
+}
+
+// touch notes that the pending batch changes doc, and whether the device image held a document there before it.
+func (x *HipIndex) touch(doc uint32) {
+	if _, ok := x.touched[doc]; !ok {
+		x.touched[doc] = x.resident[doc]
+	}
 }
 
 // Delete removes a document; its doc slot keeps length 0 and is reused by a later Add.
@@ -178,6 +200,7 @@ func (x *HipIndex) remove(id model.ID) {
 	if !ok {
 		return
 	}
+	x.touch(doc)
 	for _, t := range x.docTerms[doc] {
 		list := x.inverted[t]
 		for i := range list {
@@ -197,9 +220,9 @@ func (x *HipIndex) remove(id model.ID) {
 	x.docLengths[doc] = 0
 	x.docToPK[doc] = 0
 	x.docTerms[doc] = nil
+	x.docTf[doc] = nil
 	delete(x.pkToDoc, id)
 	x.freeDocs = append(x.freeDocs, doc)
-	x.dirty = true
 }
 
 func (x *HipIndex) drop() {
@@ -209,19 +232,58 @@ func (x *HipIndex) drop() {
 	}
 }
 
-// upload replaces the device image: CSR postings with every list sorted by doc.
+// flush applies the pending batch with one vg_bm25_update: the docs the device holds and the batch touched are deleted,
+// the touched docs that hold a document now are added (a doc in both lists is a replace).  Term ids are the dictionary's.
+func (x *HipIndex) flush() error {
+	if x.h == nil {
+		if st := C.vg_bm25_create_empty(x.ctx, C.int32_t(0), &x.h); st != C.VG_OK {
+			return hipctx.Err(int32(st))
+		}
+	}
+	var del, docs, lens, terms, tfs []uint32
+	off := make([]int64, 1, len(x.touched)+1)
+	for doc, had := range x.touched {
+		if had {
+			del = append(del, doc)
+		}
+		if x.docTerms[doc] == nil {
+			continue
+		}
+		docs = append(docs, doc)
+		lens = append(lens, x.docLengths[doc])
+		for i, t := range x.docTerms[doc] {
+			terms = append(terms, x.dict[t])
+			tfs = append(tfs, x.docTf[doc][i])
+		}
+		off = append(off, int64(len(terms)))
+	}
+	st := C.vg_bm25_update(x.h, u32p(del), C.int64_t(len(del)), u32p(docs), u32p(lens), nil, C.int64_t(len(docs)), i64p(off), u32p(terms), u32p(tfs),
+		C.int64_t(len(x.docLengths)), C.int64_t(len(x.dict)), C.int64_t(x.totalLength), C.int64_t(x.docCount), nil)
+	if st != C.VG_OK {
+		x.dirty = true // the image is as it was before the call, the batch is not in it: rebuild
+		return hipctx.Err(int32(st))
+	}
+	for _, doc := range del {
+		x.resident[doc] = false
+	}
+	for _, doc := range docs {
+		x.resident[doc] = true
+	}
+	x.touched = map[uint32]bool{}
+	return nil
+}
+
+// upload replaces the device image from the host's lists (the recovery path after a failed update): CSR postings under the
+// dictionary's ids — a term without a list is an empty range — with every list sorted by doc.
 func (x *HipIndex) upload() error {
 	x.drop()
-	names := make([]string, 0, len(x.inverted))
-	for t := range x.inverted {
-		names = append(names, t)
+	names := make([]string, len(x.dict))
+	for t, id := range x.dict {
+		names[id] = t
 	}
-	sort.Strings(names)
-	x.dict = make(map[string]uint32, len(names))
-	x.df = make([]int, len(names))
 	off := make([]int64, 1, len(names)+1)
 	var docs, tfs []uint32
-	for i, t := range names {
+	for _, t := range names {
 		list := append([]hipPosting(nil), x.inverted[t]...)
 		sort.Slice(list, func(a, b int) bool { return list[a].doc < list[b].doc })
 		for _, p := range list {
@@ -229,20 +291,23 @@ func (x *HipIndex) upload() error {
 			tfs = append(tfs, p.tf)
 		}
 		off = append(off, int64(len(docs)))
-		x.dict[t] = uint32(i)
-		x.df[i] = len(list)
 	}
 	st := C.vg_bm25_create(x.ctx, C.int64_t(len(x.docLengths)), C.int64_t(len(names)), i64p(off), u32p(docs), u32p(tfs), u32p(x.docLengths),
 		C.int64_t(x.totalLength), C.int64_t(x.docCount), nil, &x.h)
 	if st != C.VG_OK {
 		return hipctx.Err(int32(st))
 	}
+	for doc := range x.resident {
+		x.resident[doc] = x.docTerms[doc] != nil
+	}
+	x.touched = map[uint32]bool{}
 	x.dirty = false
 	return nil
 }
 
-// queryArrays: the term ids of the texts' tokens that have a posting list, with the reference's idf
-// (math.Log(1 + (N - n + 0.5) / (n + 0.5))) per entry.
+// queryArrays: the term ids of the texts' tokens that have a posting list — a term whose list has emptied is skipped, as the
+// reference has deleted it — with the reference's idf (math.Log(1 + (N - n + 0.5) / (n + 0.5))) per entry, n from the
+// host's own list.
 func (x *HipIndex) queryArrays(texts []string) ([]int32, []uint32, []float64) {
 	off := make([]int32, 1, len(texts)+1)
 	var terms []uint32
@@ -250,12 +315,12 @@ func (x *HipIndex) queryArrays(texts []string) ([]int32, []uint32, []float64) {
 	n := float64(x.docCount)
 	for _, text := range texts {
 		for _, t := range tokens(text) {
-			id, ok := x.dict[t]
-			if !ok {
+			list := x.inverted[t]
+			if len(list) == 0 {
 				continue
 			}
-			df := float64(x.df[id])
-			terms = append(terms, id)
+			df := float64(len(list))
+			terms = append(terms, x.dict[t])
 			idf = append(idf, math.Log(1+(n-df+0.5)/(df+0.5)))
 		}
 		off = append(off, int32(len(terms)))
@@ -283,8 +348,12 @@ func (x *HipIndex) searchLocked(texts []string, k int) ([]uint32, []float32, []i
 		}
 		return ids, scores, counts, nil
 	}
-	if x.dirty || x.h == nil {
+	if x.dirty {
 		if err := x.upload(); err != nil {
+			return nil, nil, nil, err
+		}
+	} else if x.h == nil || len(x.touched) > 0 {
+		if err := x.flush(); err != nil {
 			return nil, nil, nil, err
 		}
 	}
@@ -317,7 +386,7 @@ func (x *HipIndex) Search(ctx context.Context, text string, k int) ([]model.Cand
 	return out, nil
 }
 
-// Replayed: the queries since the last upload whose tied scores went through the reference's heap on the device.
+// Replayed: the queries since the index was made (updates keep the count) whose tied scores went through the reference's heap on the device.
 func (x *HipIndex) Replayed() (int64, error) {
 	x.mu.Lock()
 	defer x.mu.Unlock()
@@ -331,7 +400,7 @@ func (x *HipIndex) Replayed() (int64, error) {
 	return int64(n), nil
 }
 
-// ResidentBytes: what the uploaded image holds on the device.
+// ResidentBytes: what the index holds on the device, the spare image of the updates included.
 func (x *HipIndex) ResidentBytes() (int64, error) {
 	x.mu.Lock()
 	defer x.mu.Unlock()
@@ -343,6 +412,34 @@ func (x *HipIndex) ResidentBytes() (int64, error) {
 		return 0, hipctx.Err(int32(st))
 	}
 	return int64(bytes), nil
+}
+
+// Export copies the resident image out (what persists an index the host never assembled): the term offsets, the postings
+// and the doc lengths, under the dictionary's term ids.  Pending writes are flushed first.
+func (x *HipIndex) Export() ([]int64, []uint32, []uint32, []uint32, error) {
+	x.mu.Lock()
+	defer x.mu.Unlock()
+	if x.dirty {
+		if err := x.upload(); err != nil {
+			return nil, nil, nil, nil, err
+		}
+	} else if x.h == nil || len(x.touched) > 0 {
+		if err := x.flush(); err != nil {
+			return nil, nil, nil, nil, err
+		}
+	}
+	var nDocs, nTerms, nPost, bytes C.int64_t
+	if st := C.vg_bm25_stats(x.h, &nDocs, &nTerms, &nPost, &bytes); st != C.VG_OK {
+		return nil, nil, nil, nil, hipctx.Err(int32(st))
+	}
+	off := make([]int64, int(nTerms)+1)
+	docs := make([]uint32, int(nPost))
+	tfs := make([]uint32, int(nPost))
+	lens := make([]uint32, int(nDocs))
+	if st := C.vg_bm25_export(x.h, i64p(off), u32p(docs), u32p(tfs), u32p(lens), nil, nil); st != C.VG_OK {
+		return nil, nil, nil, nil, hipctx.Err(int32(st))
+	}
+	return off, docs, tfs, lens, nil
 }
 
 // Close implements Index.

@@ -50,7 +50,7 @@
  *     its filter's population count and redo flags back); vg_search_flat_prefilter (reads its
  *     masks' population counts back to size its row lists); vg_bm25_create (like vg_index_set_*) and
  *     vg_bm25_search (query term arrays in device memory are read back: the terms' list lengths size the
- *     key lists); vg_search_sq8 and
+ *     key lists); vg_bm25_update (reads its error flag and the new offsets back) and vg_bm25_export to host memory; vg_search_sq8 and
  *     vg_search_pq_adc when the bfloat16 nomination takes the batch, and
  *     vg_search_flat_threshold when its nomination does (the proofs' flags are read
  *     back); any call that is handed a host buffer, a stats array on the host included.
@@ -115,7 +115,8 @@ extern "C" {
  *  vg_mask_combine, vg_mask_popcount and vg_mask_alloc / _free, found by symbol lookup.  Likewise the pre-filter search
  *  (the engine's bitmap strategy): vg_mask_to_rows and vg_search_flat_prefilter, found by symbol lookup.  Likewise hybrid
  *  search (the lexical leg and the fusion of Engine.HybridSearch): vg_bm25_create / _destroy / _stats / _search / _replayed and
- *  vg_rrf_fuse, found by symbol lookup. */
+ *  vg_rrf_fuse, found by symbol lookup.  Likewise the writes to a resident BM25 index: vg_bm25_create_empty, vg_bm25_update
+ *  and vg_bm25_export, found by symbol lookup. */
 #define VG_ABI_MINOR 13
 #define VG_INVALID_ID 0xFFFFFFFFu
 #define VG_STREAM_LEGACY ((void *)1) /* == hipStreamLegacy */
@@ -760,7 +761,7 @@ int32_t vg_search_flat_prefilter(vg_index *idx, const float *queries, int64_t nq
  *   bm25.go:18-21); doc_len[d] = idx.docLengths[d] (0 for a deleted doc's slot); total_length = idx.totalLength and
  *   doc_count = idx.docCount (passed on their own because deleted docs keep a slot); doc_to_id[d] = the id doc d is reported
  *   and fused under (one resident segment: its row id), NULL = d itself.  vg_bm25_create copies (each array from host or
- *   device memory) and waits once; like the metadata columns the index does not follow writes: the host uploads it again.
+ *   device memory) and waits once; writes reach the index through vg_bm25_update (below), not through another upload.
  *   STATED DEVIATION: every posting list must be in STRICTLY ASCENDING doc order.  The reference's lists are in insertion
  *   order, and after deleteLocked's swap-remove (bm25.go:252-254) and the reuse of freed doc ids (:191-195) they can be out of
  *   order; its document-at-a-time walk then meets such a doc more than once and scores it in pieces — an artefact, not a
@@ -815,6 +816,58 @@ int32_t vg_bm25_stats(vg_bm25 *bm, int64_t *docs, int64_t *terms, int64_t *posti
 int32_t vg_bm25_search(vg_bm25 *bm, const int32_t *q_term_off, const uint32_t *q_terms, const double *q_idf, int64_t nq, int32_t k,
                        uint32_t *out_ids, float *out_scores, int32_t *out_counts, void *stream);
 int32_t vg_bm25_replayed(vg_bm25 *bm, int64_t *replayed, void *stream);
+/* Writes to the resident index, without a rebuild.  (Present when the symbols are: see VG_ABI_MINOR.)
+ *
+ * vg_bm25_update: one call is a batch of MemoryIndex.deleteLocked (bm25.go:238-278) followed by a batch of Add (:180-229),
+ *   applied to the CSR image where it lies: the host no longer sorts and uploads the whole index after a write.
+ *   Deletes: every posting of a doc in del_docs[n_del] leaves its list, doc_len[d] becomes 0 and doc_to_id[d] 0 (:268-269); a
+ *   doc named twice, or one without postings, is fine.  Adds: added doc i is add_docs[i], of length add_len[i], reported under
+ *   add_ids[i], with the postings (add_terms[p], add_tf[p]) for p in add_off[i] .. add_off[i + 1] — the document-major form
+ *   in which a host's tf map arrives (:205-228); add_docs in any order; a doc in both lists is a replace (deletes apply
+ *   first).  The host allocates doc ids: the free list of :191-195 stays with it, as the dictionary does.
+ *   Afterwards the index is bit for bit the one vg_bm25_create would hold for the updated index, with STABLE TERM IDS: term
+ *   t's list is its old list without the deleted docs together with its added postings, strictly ascending by doc; a list
+ *   that empties stays as an empty range (the reference deletes it, :259-261: the host skips a term whose df is 0); the ids
+ *   from the old n_terms up to n_terms_new are new terms, unused ones empty ranges.  n_docs grows to n_docs_new, slots
+ *   without a document have length 0 (and id 0); neither size may shrink (VG_ERR_INVALID_ARG with the number).
+ *   total_length and doc_count come from the caller as in vg_bm25_create and the three constants are formed as there;
+ *   doc_count == 0 afterwards is allowed (the index then answers nothing).  vg_bm25_replayed keeps counting across updates.
+ *   doc_to_id: an index made with the array (or vg_bm25_create_empty(.., 1, ..)) requires add_ids; an identity index refuses
+ *   a non-NULL add_ids (VG_ERR_INVALID_ARG).
+ *   FAILURE IS ATOMIC: the next image is built beside the current one; an error flag is read back together with the new
+ *   offsets (whose host copy vg_bm25_search sizes its key lists from), and that readback is the call's one wait for `stream`
+ *   — besides add_off in device memory, which is read back first (it sizes the call, as term_off does in vg_bm25_create), and
+ *   an array that has to grow.  After a failed call the index is exactly as it was.
+ *   Checks: arrays in HOST memory are validated before anything is enqueued — a doc >= n_docs_new, a deleted doc >= the old
+ *   n_docs, a term >= n_terms_new, a doc named twice in add_docs, a term named twice inside one doc, a decreasing add_off:
+ *   VG_ERR_INVALID_ARG naming the doc or the term.  Arrays in DEVICE memory are not validated, the rule vg_bm25_create
+ *   states (ids out of range are caught on the device all the same: VG_ERR_INVALID_ARG, nothing is written out of range).  One
+ *   check is made on the device for either kind: an added doc that still has a surviving posting in a list it is added to
+ *   (an add into a live slot) is VG_ERR_INVALID_ARG naming the doc.
+ *   Limits (VG_ERR_UNSUPPORTED with the number): n_docs_new < 2^31, term ids are uint32, fewer than 2^31 added postings per
+ *   call.  n_del == 0, n_add == 0 or both are served.  More than 2^32 postings are NOT TESTED: posting offsets are int64
+ *   throughout by construction, a test of that size does not run in seconds.
+ *   Memory: the postings and the offsets ping-pong between two buffers with capacity (the second appears at the first
+ *   update; a buffer too small for old + added postings is replaced by one of max(need, 1.5 x the larger of the two));
+ *   doc_len / doc_to_id grow by the same rule and are written only after the error check has passed.  vg_bm25_stats reports
+ *   the bytes actually held: 8 per offset slot and 8 per posting slot of BOTH images, 4 (8 with doc_to_id) per doc slot.
+ *   A search on ANOTHER stream that overlaps an update is the caller's to order: it may read buffers the update rewrites.
+ *   Work: one streaming pass over the old postings marks them live or deleted and ranks them (VG_BM25_UPDATE_CHUNK postings
+ *   per workgroup), the added postings are radix-sorted by (term, doc), a scan over n_terms_new gives the new offsets, and a
+ *   second streaming pass writes every posting to its final position: HBM bytes, proportional to the index, not a host sort
+ *   plus a PCIe upload of it.
+ * vg_bm25_create_empty: an index with no docs, no terms and doc_count 0 (vg_bm25_create keeps refusing one); with_doc_to_id
+ *   != 0: it reports through a doc_to_id array that the updates' add_ids fill.  vg_bm25_search on an index whose doc_count is
+ *   0 writes the empty answer (VG_INVALID_ID / -Inf, counts 0), as bm25.go:286 answers nothing.
+ * vg_bm25_export: the image copied out, each array to host or device memory, any pointer NULL = not wanted; sizes from
+ *   vg_bm25_stats (term_off: terms + 1).  What a host needs to persist an index it never built. */
+#define VG_BM25_UPDATE_CHUNK 2048 /* postings one workgroup of the update's passes owns: the tests' posting seams */
+int32_t vg_bm25_create_empty(vg_ctx *ctx, int32_t with_doc_to_id, vg_bm25 **out);
+int32_t vg_bm25_update(vg_bm25 *bm, const uint32_t *del_docs, int64_t n_del, const uint32_t *add_docs, const uint32_t *add_len,
+                       const uint32_t *add_ids, int64_t n_add, const int64_t *add_off, const uint32_t *add_terms, const uint32_t *add_tf,
+                       int64_t n_docs_new, int64_t n_terms_new, int64_t total_length, int64_t doc_count, void *stream);
+int32_t vg_bm25_export(vg_bm25 *bm, int64_t *term_off, uint32_t *post_doc, uint32_t *post_tf, uint32_t *doc_len, uint32_t *doc_to_id,
+                       void *stream);
 int32_t vg_rrf_fuse(vg_ctx *ctx, int64_t nq, const uint32_t *a_ids, const int32_t *a_counts, int64_t a_stride, const uint32_t *b_ids,
                     const int32_t *b_counts, int64_t b_stride, int32_t rrf_k, int32_t k, uint32_t *out_ids, float *out_scores,
                     int32_t *out_counts, void *stream);

@@ -1058,7 +1058,8 @@ struct Hits {
 
 // lexical/bm25.MemoryIndex resident on the device (vg_bm25): CSR postings in strictly ascending doc order (host arrays are
 // checked), doc lengths, idx.totalLength / idx.docCount and the doc -> id map (nullptr: the doc id itself).  The tokeniser, the
-// term dictionary and the idf stay the host's; the index does not follow writes: make a new one.
+// term dictionary and the idf stay the host's; writes reach the index through Update (vg_bm25_update), which rewrites the image
+// on the device: term ids are stable, a failed call leaves the index as it was.
 class Bm25 {
 public:
     Bm25(std::shared_ptr<Context> ctx, int64_t nDocs, const std::vector<int64_t> &termOff, const std::vector<uint32_t> &postDoc,
@@ -1070,6 +1071,44 @@ public:
                              totalLength, docCount, docToId, &h_));
     }
     ~Bm25() { vg_bm25_destroy(h_); }
+    // an index without docs or terms that Update fills (vg_bm25_create_empty); withDocToId: results go through the ids Update is given
+    static std::unique_ptr<Bm25> Empty(std::shared_ptr<Context> ctx, bool withDocToId = false)
+    {
+        std::unique_ptr<Bm25> b(new Bm25());
+        b->ctx_ = std::move(ctx);
+        check(vg_bm25_create_empty(b->ctx_->handle(), withDocToId ? 1 : 0, &b->h_));
+        return b;
+    }
+    // a batch of MemoryIndex.Delete followed by a batch of Add (vg_bm25_update): the docs delDocs go, then added doc i = addDocs[i] of
+    // length addLen[i] arrives with the postings (addTerms[p], addTf[p]), p in addOff[i] .. addOff[i + 1]; addIds: the ids the docs
+    // are reported under (an index with a doc -> id map), empty otherwise.  nDocs / nTerms: the sizes afterwards (never smaller).
+    void Update(const std::vector<uint32_t> &delDocs, const std::vector<uint32_t> &addDocs, const std::vector<uint32_t> &addLen,
+                const std::vector<uint32_t> &addIds, const std::vector<int64_t> &addOff, const std::vector<uint32_t> &addTerms,
+                const std::vector<uint32_t> &addTf, int64_t nDocs, int64_t nTerms, int64_t totalLength, int64_t docCount)
+    {
+        check(vg_bm25_update(h_, delDocs.data(), static_cast<int64_t>(delDocs.size()), addDocs.data(), addLen.data(),
+                             addIds.empty() ? nullptr : addIds.data(), static_cast<int64_t>(addDocs.size()), addOff.data(), addTerms.data(),
+                             addTf.data(), nDocs, nTerms, totalLength, docCount, nullptr));
+    }
+    // the resident image copied out (vg_bm25_export): what persists an index the host never built
+    struct Image {
+        std::vector<int64_t> termOff;
+        std::vector<uint32_t> postDoc, postTf, docLen, docToId;
+    };
+    Image Export(bool withDocToId)
+    {
+        int64_t docs = 0, terms = 0, postings = 0;
+        check(vg_bm25_stats(h_, &docs, &terms, &postings, nullptr));
+        Image im;
+        im.termOff.resize(static_cast<size_t>(terms) + 1);
+        im.postDoc.resize(static_cast<size_t>(postings));
+        im.postTf.resize(static_cast<size_t>(postings));
+        im.docLen.resize(static_cast<size_t>(docs));
+        if (withDocToId) im.docToId.resize(static_cast<size_t>(docs));
+        check(vg_bm25_export(h_, im.termOff.data(), im.postDoc.data(), im.postTf.data(), im.docLen.data(), withDocToId ? im.docToId.data() : nullptr,
+                             nullptr));
+        return im;
+    }
     Bm25(const Bm25 &) = delete;
     Bm25 &operator=(const Bm25 &) = delete;
     // MemoryIndex.Search for a batch: query q's term ids termIds[termOff[q] .. termOff[q + 1]) with the caller's idf
@@ -1100,6 +1139,7 @@ public:
     vg_bm25 *handle() const { return h_; }
 
 private:
+    Bm25() = default;
     std::shared_ptr<Context> ctx_;
     vg_bm25 *h_ = nullptr;
 };

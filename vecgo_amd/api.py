@@ -2026,6 +2026,7 @@ def mask_to_rows(ctx: Context, mask, rows: int, out_stride=None, out=None, count
 
 # ---- hybrid search: the resident BM25 index and Reciprocal Rank Fusion (vg_bm25_*, vg_rrf_fuse) ------------------------------
 BM25_TILE_DOCS = 8192   # VG_BM25_TILE_DOCS: the docs one workgroup of Bm25.search scores (the tests' doc seams)
+BM25_UPDATE_CHUNK = 2048   # VG_BM25_UPDATE_CHUNK: the postings one workgroup of Bm25.update's passes owns (the tests' posting seams)
 
 
 def _ptr_f64(x, count):
@@ -2057,7 +2058,8 @@ def _result_buffers(out, nq, k, like, device, counts=True):
 class Bm25:
     """A resident lexical/bm25 MemoryIndex (vg_bm25): CSR postings, doc lengths and the doc -> id map.  The tokeniser, the
     string -> term id dictionary and the idf (math.Log) stay the host's; posting lists are in strictly ascending doc order
-    (host arrays are checked).  The index does not follow writes: build a new one."""
+    (host arrays are checked).  Writes reach it through update(), which rewrites the image on the device; empty() makes
+    an index that only updates fill, export() copies the image out."""
 
     def __init__(self, ctx: Context, term_off, post_doc, post_tf, doc_len, total_length: int, doc_count: int, doc_to_id=None):
         self._lib = ctx._lib
@@ -2077,6 +2079,60 @@ class Bm25:
         check(self._lib.vg_bm25_create(ctx._h, C.c_int64(self.n_docs), C.c_int64(self.n_terms), pto, ppd, ppt, pdl, C.c_int64(total_length),
                                        C.c_int64(doc_count), pdi, C.byref(h)))
         self._h = h
+        self.mapped = doc_to_id is not None
+
+    @classmethod
+    def empty(cls, ctx: Context, with_doc_to_id: bool = False):
+        """vg_bm25_create_empty: an index without docs or terms that update() fills; it answers nothing until then.
+        with_doc_to_id: results are reported through the ids update() is given."""
+        self = cls.__new__(cls)
+        self._lib, self._ctx, self.n_terms, self.n_docs, self.mapped = ctx._lib, ctx, 0, 0, bool(with_doc_to_id)
+        h = C.c_void_p()
+        check(self._lib.vg_bm25_create_empty(ctx._h, C.c_int32(1 if with_doc_to_id else 0), C.byref(h)))
+        self._h = h
+        return self
+
+    def update(self, del_docs, add_docs, add_len, add_off, add_terms, add_tf, n_docs: int, n_terms: int, total_length: int, doc_count: int,
+               add_ids=None, stream=None):
+        """vg_bm25_update: delete the docs del_docs, then add the docs add_docs (lengths add_len, reported under add_ids on an
+        index with a doc_to_id map), doc i's postings being (add_terms[p], add_tf[p]) for p in add_off[i] : add_off[i + 1]
+        (int64, one entry more than add_docs).  n_docs / n_terms: the index's sizes afterwards (they never shrink; term ids
+        are stable, new terms are the ids behind the old ones); total_length / doc_count as in the constructor.  numpy or
+        torch arrays, each on its own; None or an empty array for a side that is not wanted.  A failed call (VecgoHipError)
+        leaves the index as it was."""
+        def side(x, dtype):
+            if x is None:
+                return None, None, 0
+            a, p = _ptr(x, dtype)
+            n = a.numel() if _is_torch(a) else a.size
+            return a, (p if n else None), n
+        dd, pdd, n_del = side(del_docs, np.uint32)
+        ad, pad, n_add = side(add_docs, np.uint32)
+        al, pal, n_len = side(add_len, np.uint32)
+        ai, pai, n_ids = side(add_ids, np.uint32)
+        ao, pao, n_off = side(add_off, np.int64)
+        at, pat, n_at = side(add_terms, np.uint32)
+        af, paf, n_af = side(add_tf, np.uint32)
+        if n_len != n_add or (n_add and n_off != n_add + 1) or n_at != n_af or (add_ids is not None and n_add and n_ids != n_add):
+            raise ValueError("Bm25.update: add_len (and add_ids) hold one entry per added doc, add_off one more, add_terms and add_tf one per posting")
+        if add_ids is not None and n_add == 0:
+            pai = None
+        check(self._lib.vg_bm25_update(self._h, pdd, C.c_int64(n_del), pad, pal, pai if add_ids is not None else None, C.c_int64(n_add),
+                                       pao if n_add else None, pat, paf, C.c_int64(n_docs), C.c_int64(n_terms), C.c_int64(total_length),
+                                       C.c_int64(doc_count), _stream_ptr(stream)))
+        self.n_docs, self.n_terms = n_docs, n_terms
+
+    def export(self, stream=None):
+        """vg_bm25_export: the resident image as numpy arrays (term_off int64, post_doc, post_tf, doc_len, doc_to_id or None)"""
+        st = self.stats()
+        term_off = np.empty(st["terms"] + 1, np.int64)
+        post_doc, post_tf = np.empty(st["postings"], np.uint32), np.empty(st["postings"], np.uint32)
+        doc_len = np.empty(st["docs"], np.uint32)
+        doc_to_id = np.empty(st["docs"], np.uint32) if self.mapped else None
+        check(self._lib.vg_bm25_export(self._h, C.c_void_p(term_off.ctypes.data), C.c_void_p(post_doc.ctypes.data), C.c_void_p(post_tf.ctypes.data),
+                                       C.c_void_p(doc_len.ctypes.data), C.c_void_p(doc_to_id.ctypes.data) if self.mapped else None,
+                                       _stream_ptr(stream)))
+        return term_off, post_doc, post_tf, doc_len, doc_to_id
 
     def close(self):
         if getattr(self, "_h", None):

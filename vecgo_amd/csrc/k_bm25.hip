@@ -20,22 +20,10 @@
 #include <algorithm>
 #include <vector>
 
+#include "vg_bm25.hpp"
 #include "vg_device.hpp"
 #include "vg_internal.hpp"
 #include "vg_search.hpp"
-
-struct vg_bm25 {
-    vg_ctx *ctx = nullptr;
-    int64_t n_docs = 0, n_terms = 0, n_post = 0;
-    int64_t *d_term_off = nullptr;   // n_terms + 1
-    uint32_t *d_post_doc = nullptr;  // n_post, ascending inside a term's list
-    uint32_t *d_post_tf = nullptr;   // n_post
-    uint32_t *d_doc_len = nullptr;   // n_docs
-    uint32_t *d_doc_to_id = nullptr; // n_docs, or null: identity
-    unsigned long long *d_replayed = nullptr;  // [1] queries the heap replay answered
-    std::vector<int64_t> h_term_off;           // the offsets on the host: the lists' lengths bound a query's hits
-    double k1_plus_1 = 0, k1_1b = 0, k1_b_avgdl = 0;  // bm25.go:314-317
-};
 
 namespace vg {
 namespace {
@@ -381,17 +369,16 @@ __global__ __launch_bounds__(kRrfThreads) void rrf_fuse_kernel(const uint32_t *_
     if (tid == 0 && out_counts) out_counts[q] = kept;
 }
 
-// `count` elements of a caller's array on the host: where they lie, or copied back on the stream (which is then waited for)
-template <typename T>
-int32_t host_view(const T *p, size_t count, hipStream_t st, std::vector<T> &store, const T *&out)
+// the answer of an index without docs (bm25.go:286): nothing, for every query
+__global__ __launch_bounds__(256) void bm25_empty_answer_kernel(uint32_t *__restrict__ ids, float *__restrict__ scores, int32_t *__restrict__ counts,
+                                                                int64_t nq, int k)
 {
-    out = p;
-    if (count == 0 || !is_device_ptr(p)) return VG_OK;
-    store.resize(count);
-    VG_HIP(hipMemcpyAsync(store.data(), p, count * sizeof(T), hipMemcpyDeviceToHost, st));
-    VG_HIP(hipStreamSynchronize(st));
-    out = store.data();
-    return VG_OK;
+    const int64_t total = nq * k;
+    for (int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < total; i += static_cast<int64_t>(gridDim.x) * blockDim.x) {
+        ids[i] = VG_INVALID_ID;
+        scores[i] = -INFINITY;
+        if (counts && i < nq) counts[i] = 0;
+    }
 }
 
 template <typename T>
@@ -409,6 +396,15 @@ struct QueryChunk {
 }  // namespace
 }  // namespace vg
 
+void vg::bm25_set_constants(vg_bm25 *bm, int64_t total_length, int64_t doc_count)
+{
+    const double avg_dl = static_cast<double>(total_length) / static_cast<double>(doc_count);  // bm25.go:314-317; k1 = 1.2, b = 0.75
+    bm->k1_plus_1 = 2.2;  // the reference's constants are exact constant expressions rounded ONCE: k1 + 1, k1 * (1 - b), k1 * b
+    bm->k1_1b = 0.3;
+    bm->k1_b_avgdl = 0.9 / avg_dl;
+    bm->doc_count = doc_count;
+}
+
 VG_API int32_t vg_bm25_destroy(vg_bm25 *bm)
 {
     if (!bm) return VG_OK;
@@ -419,6 +415,9 @@ VG_API int32_t vg_bm25_destroy(vg_bm25 *bm)
     vg::drop_device(&bm->d_post_tf);
     vg::drop_device(&bm->d_doc_len);
     vg::drop_device(&bm->d_doc_to_id);
+    vg::drop_device(&bm->d_alt_off);
+    vg::drop_device(&bm->d_alt_doc);
+    vg::drop_device(&bm->d_alt_tf);
     vg::drop_device(&bm->d_replayed);
     delete bm;
     return VG_OK;
@@ -472,10 +471,8 @@ VG_API int32_t vg_bm25_create(vg_ctx *ctx, int64_t n_docs, int64_t n_terms, cons
     bm->n_docs = n_docs;
     bm->n_terms = n_terms;
     bm->n_post = n_post;
-    const double avg_dl = static_cast<double>(total_length) / static_cast<double>(doc_count);  // bm25.go:314-317; k1 = 1.2, b = 0.75
-    bm->k1_plus_1 = 2.2;  // the reference's constants are exact constant expressions rounded ONCE: k1 + 1, k1 * (1 - b), k1 * b
-    bm->k1_1b = 0.3;
-    bm->k1_b_avgdl = 0.9 / avg_dl;
+    bm->mapped = doc_to_id != nullptr;
+    vg::bm25_set_constants(bm, total_length, doc_count);
     int32_t s = vg::upload(&bm->d_term_off, h_off.data(), h_off.size(), st);
     if (s == VG_OK) s = vg::upload(&bm->d_post_doc, post_doc, static_cast<size_t>(n_post), st);
     if (s == VG_OK) s = vg::upload(&bm->d_post_tf, post_tf, static_cast<size_t>(n_post), st);
@@ -502,8 +499,12 @@ VG_API int32_t vg_bm25_stats(vg_bm25 *bm, int64_t *docs, int64_t *terms, int64_t
     if (docs) *docs = bm->n_docs;
     if (terms) *terms = bm->n_terms;
     if (postings) *postings = bm->n_post;
-    if (bytes)
-        *bytes = (bm->n_terms + 1) * 8 + bm->n_post * 8 + bm->n_docs * 4 + (bm->d_doc_to_id ? bm->n_docs * 4 : 0);
+    if (bytes) {  // what is held: an array vg_bm25_update has grown counts with its room, and so does the second image
+        const int64_t off = std::max(bm->off_cap, bm->n_terms + 1) + (bm->d_alt_off ? bm->alt_off_cap : 0);
+        const int64_t post = std::max(bm->post_cap, bm->n_post) + (bm->d_alt_doc ? bm->alt_post_cap : 0);
+        const int64_t docs = std::max(bm->docs_cap, bm->n_docs);
+        *bytes = off * 8 + post * 8 + docs * 4 + (bm->d_doc_to_id ? docs * 4 : 0);
+    }
     return VG_OK;
 }
 
@@ -573,6 +574,16 @@ VG_API int32_t vg_bm25_search(vg_bm25 *bm, const int32_t *q_term_off, const uint
         VG_TRY(own_cnt.init(static_cast<size_t>(nq), st));
     }
     int32_t *cnt_out = out_counts ? ocnt.ptr : own_cnt.ptr;
+    if (bm->doc_count == 0) {  // bm25.go:286: an index without docs (vg_bm25_create_empty, or updated down to none) answers nothing
+        const int64_t total = nq * k;
+        VG_LAUNCH(vg::bm25_empty_answer_kernel, dim3(static_cast<unsigned>(std::min<int64_t>((total + 255) / 256, 1024))), dim3(256), 0, st, oid.ptr,
+                  osc.ptr, cnt_out, nq, k);
+        VG_TRY(oid.finish());
+        VG_TRY(osc.finish());
+        if (out_counts) VG_TRY(ocnt.finish());
+        if (d_off.owned || d_terms.owned || d_idf.owned) VG_HIP(hipStreamSynchronize(st));
+        return VG_OK;
+    }
 
     // query chunks whose key lists (8 bytes per query and slot of the chunk's longest list) stay inside the context's scratch cap
     const int64_t cap_bytes = vg::hook(vg::kHookBm25SmallScratch) ? 65536 : vg::scratch_cap(ctx);  // (the hook: several chunks for a test batch)

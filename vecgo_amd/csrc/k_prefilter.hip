@@ -27,13 +27,14 @@
 #include "vg_device.hpp"
 #include "vg_exact.hpp"
 #include "vg_internal.hpp"
+#include "vg_scan.hpp"
 #include "vg_search.hpp"
 
 namespace vg {
 namespace {
 
 constexpr int kCompactTile = VG_MASK_ROWS_TILE_ROWS;  // rows of one workgroup of the compaction: a 32-bit mask word per thread
-constexpr int kCompactThreads = 256;
+constexpr int kCompactThreads = kScanThreads;  // (block_scan and prefix_kernel, vg_scan.hpp)
 static_assert(kCompactTile == kCompactThreads * 32, "a thread keeps one 32-bit word of the tile");
 constexpr int kScoreChunk = VG_PREFILTER_CHUNK_ROWS;  // listed rows of one workgroup of the score kernels
 constexpr int kScoreThreads = 256;
@@ -57,28 +58,6 @@ __device__ __forceinline__ uint32_t mask_word32(const uint8_t *__restrict__ m, i
     return w;
 }
 
-// the workgroup's inclusive prefix of x at this thread and the workgroup's total (all threads call; wsum: one slot per wave)
-__device__ __forceinline__ long long block_scan(long long x, long long *wsum, long long &total)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    long long inc = x;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const long long y = __shfl_up(inc, off);
-        if (lane >= off) inc += y;
-    }
-    __syncthreads();  // the previous use of wsum has been read
-    if (lane == 63) wsum[wave] = inc;
-    __syncthreads();
-    long long before = 0;
-    total = 0;
-    for (int w = 0; w < kCompactThreads / 64; w++) {
-        if (w < wave) before += wsum[w];
-        total += wsum[w];
-    }
-    return before + inc;
-}
-
 // (1) tile_cnt[list * tiles + tile] <- the set bits of the tile; one workgroup per (list, tile)
 __global__ __launch_bounds__(kCompactThreads) void mask_tile_count_kernel(const uint8_t *__restrict__ mask, int64_t mask_stride, int64_t rows,
                                                                           int64_t tiles, int words, uint32_t *__restrict__ tile_cnt)
@@ -93,26 +72,7 @@ __global__ __launch_bounds__(kCompactThreads) void mask_tile_count_kernel(const 
     if (threadIdx.x == 0) tile_cnt[blockIdx.x] = static_cast<uint32_t>(wsum[0] + wsum[1] + wsum[2] + wsum[3]);
 }
 
-// (2) segment blockIdx.x of v (n values each) <- its exclusive prefix sums, in place; the segment's total to tot64 / tot32
-template <typename T>
-__global__ __launch_bounds__(kCompactThreads) void prefix_kernel(T *__restrict__ v, int64_t n, int64_t *__restrict__ tot64, int *__restrict__ tot32)
-{
-    __shared__ long long wsum[kCompactThreads / 64];
-    T *p = v + static_cast<int64_t>(blockIdx.x) * n;
-    long long carry = 0;
-    for (int64_t i0 = 0; i0 < n; i0 += kCompactThreads) {
-        const int64_t i = i0 + threadIdx.x;
-        const long long x = i < n ? static_cast<long long>(p[i]) : 0;
-        long long total;
-        const long long inc = block_scan(x, wsum, total);
-        if (i < n) p[i] = static_cast<T>(carry + inc - x);
-        carry += total;
-    }
-    if (threadIdx.x == 0) {
-        if (tot64) tot64[blockIdx.x] = carry;
-        if (tot32) tot32[blockIdx.x] = static_cast<int>(carry);
-    }
-}
+// (2) one workgroup per mask turns its tile counts into offsets and the mask's total: prefix_kernel (vg_scan.hpp)
 
 // (3) the tile's ids, ascending, behind its offset.  List l goes to out + l * out_stride, at most out_stride ids of it
 // (list_off null), or — the search's CSR block — to out + list_off[l] - list_off[0], whole.
