@@ -689,6 +689,25 @@ func (r *Resident) EnablePQNomination(on bool) error {
 	return hipctx.Err(int32(C.vg_index_enable_pq_nomination(r.h, v, nil)))
 }
 
+// EnablePQNominationFromCodes: the same nomination without the decoded-row image — the GEMM's row tiles are gathered from the
+// decoded codebook by the codes (8 dimensions per sub-quantizer; batches above 128 queries).  Resident: 4 bytes a row and the
+// codebook.  The two modes are exclusive; results unchanged.
+func (r *Resident) EnablePQNominationFromCodes(on bool) error {
+	v := C.int32_t(0)
+	if on {
+		v = 1
+	}
+	return hipctx.Err(int32(C.vg_index_enable_pq_nomination_from_codes(r.h, v, nil)))
+}
+
+// PQNominationInfo: mode 0 (off), 1 (the decoded-row image) or 2 (from the codes), and the device bytes the mode keeps resident.
+func (r *Resident) PQNominationInfo() (mode int, heldBytes int64, err error) {
+	var m C.int32_t
+	var b C.int64_t
+	st := C.vg_index_pq_nomination_info(r.h, &m, &b)
+	return int(m), int64(b), hipctx.Err(int32(st))
+}
+
 // FlatRetried: how many queries of the fp32 flat search, since the rows were attached, the one-product bfloat16 screen left
 // open and the three-product pass nominated again (a host whose neighbours lie closer than ~2^-7 relative sees it grow).
 func (r *Resident) FlatRetried() (int64, error) {

@@ -116,7 +116,8 @@ extern "C" {
  *  (the engine's bitmap strategy): vg_mask_to_rows and vg_search_flat_prefilter, found by symbol lookup.  Likewise hybrid
  *  search (the lexical leg and the fusion of Engine.HybridSearch): vg_bm25_create / _destroy / _stats / _search / _replayed and
  *  vg_rrf_fuse, found by symbol lookup.  Likewise the writes to a resident BM25 index: vg_bm25_create_empty, vg_bm25_update
- *  and vg_bm25_export, found by symbol lookup. */
+ *  and vg_bm25_export, found by symbol lookup.  Likewise the PQ batch nomination from the codes:
+ *  vg_index_enable_pq_nomination_from_codes and vg_index_pq_nomination_info, found by symbol lookup. */
 #define VG_ABI_MINOR 13
 #define VG_INVALID_ID 0xFFFFFFFFu
 #define VG_STREAM_LEGACY ((void *)1) /* == hipStreamLegacy */
@@ -1579,6 +1580,23 @@ int32_t vg_search_pq_adc(vg_index *idx, const float *queries, int64_t nq, int32_
  * proves no other row can enter the k best; a query whose proof fails is scanned as before.  Smaller batches and the
  * filtered / probed searches keep the table scan.  Dropped by vg_index_set_pq_codes.  (VG_ABI_MINOR 10.) */
 int32_t vg_index_enable_pq_nomination(vg_index *idx, int32_t on, void *stream);
+/* The same nomination WITHOUT the image of the decoded rows, for the index sizes PQ exists for.  With 8 dimensions per
+ * sub-quantizer a 16-byte granule of a decoded bfloat16 row is exactly one centroid, so the nomination GEMM fills its row tiles
+ * from a bfloat16 copy of the decoded codebook ((dim padded to 64) / 8 * 4 KiB: 393 KB at m = 96, resident in the L2) by the row's
+ * code bytes; the operands are bit for bit the image's, and so are the re-score, the proof and the results.  Resident: that
+ * codebook, the rows' norms (4 bytes a row) and their largest — at most rows * (4 + dim_pad / 32) + (dim_pad / 8 + 1) * 4096 + 4096
+ * bytes, 0.05x the codes at m = 96 where the image is 16x; the threshold sample's row tiles (rows / 64) are decoded into the call's
+ * scratch.  Refusals as vg_index_enable_pq_nomination's, in its order (NULL index, no PQ codes, untrained, numCentroids != 256),
+ * then sub-vectors of other than 8 dimensions: VG_ERR_UNSUPPORTED.  Any m (granules from m on read zeros).  The two modes
+ * are exclusive: enabling one frees the other's state; on == 0 frees this one's; vg_index_set_pq_codes drops it.  Batches it takes:
+ * unfiltered, ascending, k <= 256, rows > k, 16-byte aligned device queries, MORE THAN 128 queries, and queries x rows at or above
+ * its own crossover against the scan (README, Limits); every other batch keeps the table scan, with the same results.  Found by
+ * symbol lookup. */
+int32_t vg_index_enable_pq_nomination_from_codes(vg_index *idx, int32_t on, void *stream);
+/* Which PQ nomination an index holds and what it costs: *mode = 0 (off), 1 (the image: vg_index_enable_pq_nomination) or 2 (from
+ * the codes); *held_bytes = the device memory the mode keeps resident (mode 1: the image, the norms and norm_max).  Either
+ * pointer may be NULL.  Found by symbol lookup. */
+int32_t vg_index_pq_nomination_info(const vg_index *idx, int32_t *mode, int64_t *held_bytes);
 
 #ifdef __cplusplus
 }

@@ -661,6 +661,20 @@ public:
     Result SearchPQ(const float *queries, int64_t nq, int k) { return run(nq, k, [&](Result &r) { return vg_search_pq_adc(h_, queries, nq, k, r.ids.data(), r.scores.data(), nullptr); }); }
     // opt-in: batches of SearchPQ nominated by a bfloat16 MFMA GEMM over the decoded rows, re-scored from the codes; results unchanged
     void EnablePQNomination(bool on = true) { check(vg_index_enable_pq_nomination(h_, on ? 1 : 0, nullptr)); }
+    // the same without the image of the decoded rows: the GEMM's row tiles gathered from the decoded codebook by the codes
+    // (8 dimensions per sub-quantizer, batches above 128 queries); the two modes are exclusive
+    void EnablePQNominationFromCodes(bool on = true) { check(vg_index_enable_pq_nomination_from_codes(h_, on ? 1 : 0, nullptr)); }
+    // mode: 0 off, 1 the image, 2 from the codes; held_bytes: the device memory the mode keeps resident
+    struct PQNomination {
+        int32_t mode;
+        int64_t held_bytes;
+    };
+    PQNomination PQNominationInfo() const
+    {
+        PQNomination r{0, 0};
+        check(vg_index_pq_nomination_info(h_, &r.mode, &r.held_bytes));
+        return r;
+    }
     Result SearchRaBitQ(const float *queries, int64_t nq, int k) { return run(nq, k, [&](Result &r) { return vg_search_rabitq(h_, queries, nq, k, r.ids.data(), r.scores.data(), nullptr); }); }
     // IVF partitions (flat/segment.go:187-207) and the probed scan of flat.Segment.Search (:727-749):
     // scan = VG_SCAN_F32 / VG_SCAN_PQ / VG_SCAN_SQ8, nprobes <= 0 means 1 as in the reference

@@ -985,6 +985,20 @@ class Index:
         the reference's order and proven: ids and scores stay bit-identical."""
         check(self._lib.vg_index_enable_pq_nomination(self._h, C.c_int32(1 if on else 0), _stream_ptr(stream)))
 
+    def enable_pq_nomination_from_codes(self, on: bool = True, stream=None):
+        """vg_index_enable_pq_nomination_from_codes: the same nomination without the image of the decoded rows — the GEMM's row tiles
+        are gathered from a bfloat16 copy of the decoded codebook by the rows' codes (8 dimensions per sub-quantizer, K = 256;
+        batches above 128 queries, from queries x rows >= 13M).  Resident: 4 bytes a row and the codebook.  Exclusive with enable_pq_nomination; ids and
+        scores stay bit-identical."""
+        check(self._lib.vg_index_enable_pq_nomination_from_codes(self._h, C.c_int32(1 if on else 0), _stream_ptr(stream)))
+
+    def pq_nomination_info(self):
+        """vg_index_pq_nomination_info: (mode, held_bytes) — mode 0 off, 1 the decoded-row image, 2 from the codes; held_bytes the
+        device memory the mode keeps resident."""
+        mode, held = C.c_int32(0), C.c_int64(0)
+        check(self._lib.vg_index_pq_nomination_info(self._h, C.byref(mode), C.byref(held)))
+        return mode.value, held.value
+
     def enable_sq8_nomination(self, on: bool = True, stream=None):
         """vg_index_enable_sq8_nomination: batches of search_sq8 (L2 or Dot, 5 queries up, k <= 256, any dim) are nominated by a
         bfloat16 MFMA GEMM over the dequantised rows (+ n * dim * 2 bytes), re-scored exactly from the codes and proven: ids and

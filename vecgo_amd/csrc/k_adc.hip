@@ -1057,6 +1057,7 @@ VG_API int32_t vg_index_set_pq_codes(vg_index *idx, vg_pq *pq, const uint8_t *co
         idx->d_pq_tiles = nullptr;
     }
     VG_TRY(vg::nom_free(idx->pq_nom, st));  // the old codes' nomination image (vg_index_enable_pq_nomination again after new codes)
+    VG_TRY(vg::nom_free(idx->pq_cnom, st));  // ... and their norms (vg_index_enable_pq_nomination_from_codes)
     idx->pq = pq;
     idx->pq_groups = (pq->m + 15) / 16;
     idx->n_tiles = (idx->n + 63) / 64;
@@ -1097,15 +1098,17 @@ constexpr int64_t kPqNomMinPairs = 24000000;
 // one wave per row: lane l decodes sub-quantizers l, l + 64, ... — v = float32(int8) * scale ; v = v + offset, the two rounded
 // operations of the reference's dequantisation (pq.go:204-214) — rounds to bfloat16 (nearest even), writes the image row
 // (dim_pad elements, zeros from dim on) and the row's norm
-__global__ __launch_bounds__(256) void pq_decode_bf16_kernel(const uint8_t *__restrict__ codes, int64_t n, int m, int k, int sd,
-                                                             const int8_t *__restrict__ codebooks, const float *__restrict__ scales,
-                                                             const float *__restrict__ offsets, uint16_t *__restrict__ out, int dim_pad,
-                                                             float *__restrict__ norms, int *__restrict__ norm_max_bits)
+// (ROWS false: the norms alone — pq_norms_kernel, the nomination from the codes: the same operations in the same order)
+template <bool ROWS>
+__device__ __forceinline__ void pq_decode_row(const uint8_t *__restrict__ codes, int64_t n, int m, int k, int sd,
+                                              const int8_t *__restrict__ codebooks, const float *__restrict__ scales,
+                                              const float *__restrict__ offsets, uint16_t *__restrict__ out, int dim_pad,
+                                              float *__restrict__ norms, int *__restrict__ norm_max_bits)
 {
     const int lane = threadIdx.x & 63;
     const int64_t row = static_cast<int64_t>(blockIdx.x) * 4 + (threadIdx.x >> 6);
     if (row >= n) return;  // (whole waves)
-    uint16_t *dst = out + row * dim_pad;
+    uint16_t *dst = ROWS ? out + row * dim_pad : nullptr;
     float nrm = 0.0f;
     for (int j = lane; j < m; j += 64) {
         const int c = codes[row * m + j];
@@ -1116,10 +1119,11 @@ __global__ __launch_bounds__(256) void pq_decode_bf16_kernel(const uint8_t *__re
             v = v + of;
             nrm = __builtin_fmaf(v, v, nrm);
             const uint32_t b = __float_as_uint(v);
-            dst[j * sd + d] = static_cast<uint16_t>((b + 0x7FFFu + ((b >> 16) & 1u)) >> 16);
+            if constexpr (ROWS) dst[j * sd + d] = static_cast<uint16_t>((b + 0x7FFFu + ((b >> 16) & 1u)) >> 16);
         }
     }
-    for (int j = m * sd + lane; j < dim_pad; j += 64) dst[j] = 0;
+    if constexpr (ROWS)
+        for (int j = m * sd + lane; j < dim_pad; j += 64) dst[j] = 0;
     for (int off = 32; off > 0; off >>= 1) nrm += __shfl_xor(nrm, off);
     if (lane == 0) {
         norms[row] = nrm;
@@ -1127,6 +1131,42 @@ __global__ __launch_bounds__(256) void pq_decode_bf16_kernel(const uint8_t *__re
         const int nb = __float_as_int(nrm == nrm ? nrm : INFINITY);  // non-negative floats order like their bits
         if (nb > *reinterpret_cast<volatile int *>(norm_max_bits)) atomicMax(norm_max_bits, nb);  // (a wave per row: only where it raises the value)
     }
+}
+__global__ __launch_bounds__(256) void pq_decode_bf16_kernel(const uint8_t *__restrict__ codes, int64_t n, int m, int k, int sd,
+                                                             const int8_t *__restrict__ codebooks, const float *__restrict__ scales,
+                                                             const float *__restrict__ offsets, uint16_t *__restrict__ out, int dim_pad,
+                                                             float *__restrict__ norms, int *__restrict__ norm_max_bits)
+{
+    pq_decode_row<true>(codes, n, m, k, sd, codebooks, scales, offsets, out, dim_pad, norms, norm_max_bits);
+}
+__global__ __launch_bounds__(256) void pq_norms_kernel(const uint8_t *__restrict__ codes, int64_t n, int m, int k, int sd,
+                                                       const int8_t *__restrict__ codebooks, const float *__restrict__ scales,
+                                                       const float *__restrict__ offsets, float *__restrict__ norms, int *__restrict__ norm_max_bits)
+{
+    pq_decode_row<false>(codes, n, m, k, sd, codebooks, scales, offsets, nullptr, 0, norms, norm_max_bits);
+}
+// The decoded codebook of the nomination from the codes (PqCodesNom::cb16; K = 256, sub-dimension 8): thread per entry (j, c) of
+// `blocks` sub-quantizers, its 8 values decoded and rounded as pq_decode_row rounds them — 16 bytes, what the image of the decoded
+// rows holds at granule j of every row with code c there; the blocks from m on are zeros, the image's padding
+__global__ void pq_codebook_bf16_kernel(const int8_t *__restrict__ codebooks, const float *__restrict__ scales, const float *__restrict__ offsets,
+                                        int m, int blocks, uint4 *__restrict__ cb16)
+{
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= blocks * 256) return;
+    const int j = t >> 8;
+    uint32_t w[4] = {0u, 0u, 0u, 0u};
+    if (j < m) {
+        const int8_t *cb = codebooks + static_cast<int64_t>(t) * 8;
+        const float sc = scales[j], of = offsets[j];
+#pragma unroll
+        for (int d = 0; d < 8; d++) {
+            float v = static_cast<float>(cb[d]) * sc;
+            v = v + of;
+            const uint32_t b = __float_as_uint(v);
+            w[d >> 1] |= ((b + 0x7FFFu + ((b >> 16) & 1u)) >> 16) << (16 * (d & 1));
+        }
+    }
+    cb16[t] = make_uint4(w[0], w[1], w[2], w[3]);
 }
 
 // pqAdcLookupAvx512 (internal/simd/src/floats_avx512.c:135-167) of one row's code against a query's table in the reference's
@@ -1176,6 +1216,16 @@ static bool pq_nomination_applies(const vg_index *idx, const float *d_queries, i
     return idx->pq_nom.rows && !mask && !desc && (nq * idx->n >= kPqNomMinPairs || hook(kHookPqNomAlways)) && k <= kNomMaxK && idx->n > k && idx->pq->k == 256 &&
            aligned16(d_queries);
 }
+// The same for the nomination from the codes (vg_index_enable_pq_nomination_from_codes): more than 128 queries — the persistent
+// tile's batches; the gathered fill has no 128-row form — and its own crossover against the scan (tools/pq_nominate_codes_time.py,
+// ms scanned / from the codes, k = 10 and k = 100): 129 queries x 100k rows 0.31 / 0.24 and 0.53 / 0.32, x 300k 0.71 / 0.31, x 1M
+// 2.0 / 0.56; 1024 x 1M 12.5 / 1.68, 1024 x 10M 118 / 14.8 — it won at every batch measured, the smallest 12.9M pairs.
+constexpr int64_t kPqCodesNomMinPairs = 13000000;
+static bool pq_codes_nomination_applies(const vg_index *idx, const float *d_queries, int64_t nq, int k, const uint8_t *mask, bool desc)
+{
+    return idx->pq_cnom.cb16 && !mask && !desc && nq > 128 && (nq * idx->n >= kPqCodesNomMinPairs || hook(kHookPqNomAlways)) && k <= kNomMaxK &&
+           idx->n > k && idx->pq->k == 256 && aligned16(d_queries);
+}
 }  // namespace vg
 
 VG_API int32_t vg_index_enable_pq_nomination(vg_index *idx, int32_t on, void *stream)
@@ -1189,10 +1239,65 @@ VG_API int32_t vg_index_enable_pq_nomination(vg_index *idx, int32_t on, void *st
     const vg_pq *pq = idx->pq;
     VG_CHECK(pq->trained, VG_ERR_NOT_TRAINED, "ProductQuantizer not trained");
     VG_CHECK(pq->k == 256, VG_ERR_UNSUPPORTED, "vg_index_enable_pq_nomination: needs numCentroids == 256 (got %d), as the table scan does", pq->k);
+    VG_TRY(vg::nom_free(idx->pq_cnom, st));  // (the two modes are exclusive)
     return vg::nom_build(idx->pq_nom, idx->n, idx->dim, st, [&](const vg::NomImage &b, int *norm_max_bits) {
         hipLaunchKernelGGL(vg::pq_decode_bf16_kernel, dim3(static_cast<unsigned>((idx->n + 3) / 4)), dim3(256), 0, st, idx->d_pq_rows, idx->n,
                            pq->m, pq->k, pq->subdim, pq->d_codebooks, pq->d_scales, pq->d_offsets, b.rows, b.dim_pad, b.norms, norm_max_bits);
     });
+}
+
+VG_API int32_t vg_index_enable_pq_nomination_from_codes(vg_index *idx, int32_t on, void *stream)
+{
+    VG_CHECK(idx, VG_ERR_INVALID_ARG, "vg_index_enable_pq_nomination_from_codes: NULL index");
+    VG_HIP(hipSetDevice(idx->ctx->device));
+    hipStream_t st = vg::pick_stream(idx->ctx, stream);
+    VG_TRY(vg::nom_free(idx->pq_cnom, st));
+    if (!on) return VG_OK;
+    VG_CHECK(idx->pq && idx->d_pq_rows, VG_ERR_NOT_READY, "vg_index_enable_pq_nomination_from_codes: index has no PQ codes");
+    const vg_pq *pq = idx->pq;
+    VG_CHECK(pq->trained, VG_ERR_NOT_TRAINED, "ProductQuantizer not trained");
+    VG_CHECK(pq->k == 256, VG_ERR_UNSUPPORTED, "vg_index_enable_pq_nomination_from_codes: needs numCentroids == 256 (got %d), as the table scan does",
+             pq->k);
+    VG_CHECK(pq->subdim == 8, VG_ERR_UNSUPPORTED,
+             "vg_index_enable_pq_nomination_from_codes: needs sub-vectors of 8 dimensions (got %d): a 16-byte granule of a row is one centroid",
+             pq->subdim);
+    VG_TRY(vg::nom_free(idx->pq_nom, st));  // (the two modes are exclusive)
+    // built aside and published together, as nom_build publishes an image
+    vg::PqCodesNom b;
+    b.dim_pad = (idx->dim + 63) & ~63;
+    const int blocks = b.dim_pad / 8;
+    hipError_t e = hipMalloc(reinterpret_cast<void **>(&b.cb16), static_cast<size_t>(blocks) * 256 * 16);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&b.norms), static_cast<size_t>(idx->n) * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&b.norm_max), sizeof(float));
+    if (e == hipSuccess) e = hipMemsetAsync(b.norm_max, 0, sizeof(float), st);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(vg::pq_codebook_bf16_kernel, dim3(static_cast<unsigned>(blocks)), dim3(256), 0, st, pq->d_codebooks, pq->d_scales,
+                           pq->d_offsets, pq->m, blocks, reinterpret_cast<uint4 *>(b.cb16));
+        hipLaunchKernelGGL(vg::pq_norms_kernel, dim3(static_cast<unsigned>((idx->n + 3) / 4)), dim3(256), 0, st, idx->d_pq_rows, idx->n, pq->m, pq->k,
+                           pq->subdim, pq->d_codebooks, pq->d_scales, pq->d_offsets, b.norms, reinterpret_cast<int *>(b.norm_max));
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) {
+        (void)hipFree(b.cb16);
+        (void)hipFree(b.norms);
+        (void)hipFree(b.norm_max);
+        VG_HIP(e);
+    }
+    idx->pq_cnom = b;
+    return VG_OK;
+}
+
+VG_API int32_t vg_index_pq_nomination_info(const vg_index *idx, int32_t *mode, int64_t *held_bytes)
+{
+    VG_CHECK(idx, VG_ERR_INVALID_ARG, "vg_index_pq_nomination_info: NULL index");
+    const int32_t md = idx->pq_nom.rows ? 1 : idx->pq_cnom.cb16 ? 2 : 0;
+    if (mode) *mode = md;
+    if (held_bytes)
+        *held_bytes = md == 1   ? idx->n * (static_cast<int64_t>(idx->pq_nom.dim_pad) * 2 + 4) + 4  // the image, the norms, norm_max
+                      : md == 2 ? idx->pq_cnom.held_bytes(idx->n)
+                                : 0;
+    return VG_OK;
 }
 
 VG_API int32_t vg_search_pq_adc(vg_index *idx, const float *queries, int64_t nq, int32_t k,
@@ -1319,17 +1424,27 @@ static int32_t pq_adc_search_impl(vg_index *idx, const float *queries, int64_t n
 
     if (idx->n == 0) {
         VG_TRY(vg::empty_results(nq, k, false, oid, osc, st));
-    } else if (allow_nomination && vg::pq_nomination_applies(idx, q, nq, k, mask, desc)) {
+    } else if (allow_nomination && (vg::pq_nomination_applies(idx, q, nq, k, mask, desc) || vg::pq_codes_nomination_applies(idx, q, nq, k, mask, desc))) {
+        const bool from_codes = !idx->pq_nom.rows;  // (the modes are exclusive)
+        const float *const norm_max = from_codes ? idx->pq_cnom.norm_max : idx->pq_nom.norm_max;
         std::vector<int> failed;
         // per pass: the queries' tables (BuildDistanceTable, the reference's layout), then the table sums of the nominees
         auto verify = [&](const float *qq, int64_t cnt, const vg::ProbeNominated &nom, float *tables, uint32_t *pid, float *psc,
                           int *fail) -> int32_t {
             VG_TRY(vg::launch_pq_build_table(pq, qq, cnt, tables, false, st));
             return vg::launch_nominated_verify<false>(vg::PqTableRow{idx->d_pq_rows, tables, pq->m, pq->subdim, idx->dim}, qq,
-                                                      idx->pq_nom.norm_max, cnt, nom, k, pid, psc, fail, st);
+                                                      norm_max, cnt, nom, k, pid, psc, fail, st);
         };
-        VG_TRY(vg::nominated_pass(idx, idx->pq_nom, false, q, nq, k, nullptr, 0, static_cast<size_t>(pq->m) * 256, oid, osc,
-                                  st, failed, verify));
+        if (from_codes)  // the GEMM's operands are the image's, bit for bit: the same margin (pq_nominate_eps) holds
+            VG_TRY(vg::nominated_pass_by(
+                idx, [&](int64_t cnt) { return vg::flat_nominate_pq_codes_scratch(cnt, idx->n, idx->pq_cnom.dim_pad, k); },
+                [&](const float *qq, int64_t, int64_t cnt, char *scratch, vg::ProbeNominated *nom) {
+                    return vg::flat_nominate_pq_codes(idx, idx->pq_cnom, qq, cnt, k, scratch, st, nom);
+                },
+                q, nq, k, static_cast<size_t>(pq->m) * 256, oid, osc, st, failed, verify));
+        else
+            VG_TRY(vg::nominated_pass(idx, idx->pq_nom, false, q, nq, k, nullptr, 0, static_cast<size_t>(pq->m) * 256, oid, osc,
+                                      st, failed, verify));
         // the table scan for the queries whose proof failed (ties at the k-th score, thresholds too tight)
         VG_TRY(vg::rescan_failed(failed, q, idx->dim, k, nullptr, 0, 0, oid, osc, st,
                                  [&](const float *fq, int64_t nf, const uint8_t *, int64_t, uint32_t *fid, float *fsc) {

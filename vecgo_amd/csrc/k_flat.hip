@@ -73,6 +73,10 @@ struct GemmArgs {
     // with `split`, not `screen`: the retry behind a screen.  Bit tm of the word = query tile tm holds a query to retry; the others
     // are not multiplied.  flat_retry_prepare_kernel has written it and zeroed the counters of the queries to retry.
     const uint32_t *tile_active = nullptr;
+    // MODE 2: the code-gathered tile (flat_gemm_codes_big_kernel) — c.ops.b is the decoded PQ codebook (PqCodesNom::cb16), `codes` the
+    // n rows' code bytes, code_m a row
+    const uint8_t *codes = nullptr;
+    int code_m = 0;
 
     explicit GemmArgs(const NomCall &call) : c(call), queries(call.ops.a) {}
     // MODE 0 / 1: the scores of every stride-th row tile into sc[cnt][cols] (stride 1: the whole score matrix)
@@ -96,6 +100,7 @@ struct GemmArgs {
     GemmArgs &sample_tile(const uint32_t *hi_image) { return split_tile(hi_image); }
     GemmArgs &screen_tile(const uint32_t *hi_image) { return split_tile(hi_image), screen = true, *this; }
     GemmArgs &retry(const uint32_t *active) { return tile_active = active, *this; }
+    GemmArgs &from_codes(const uint8_t *rows, int m) { return codes = rows, code_m = m, *this; }
 };
 constexpr int kCountLine = 32;
 // Whether a MODE 2 launch of vg_search_flat's fused path runs the split tile: fp32 rows nominated by three bfloat16 products on the
@@ -244,6 +249,14 @@ static int32_t launch_gemm_t(const GemmArgs &a)
         VG_CHECK(!a.tile_active || (c.cnt <= 32 * kBigBM && a.counts_wide), VG_ERR_INVALID_ARG, "launch_gemm: tile_active is one word, with wide counters");
         note_flat_split_launch();
         return launch_big(flat_gemm_split_big_kernel<DOT, 3>, big_lds_bytes<3>(), a.tile_active);
+    }
+    if (MODE == 2 && a.codes) {  // (any number of queries: there is no row image another tile could read)
+        if constexpr (MODE == 2 && !DOT) {
+            VG_CHECK(bf16 && c.cnt * static_cast<int64_t>(a.cap) < (int64_t(1) << 31) && a.thr_stride < 65536 && c.ops.dim_words % kGemmBK == 0,
+                     VG_ERR_INVALID_ARG, "launch_gemm: the code-gathered tile on a call without it");
+            return launch_big(flat_gemm_codes_big_kernel<false, 3>, big_lds_bytes<3>(), a.codes, a.code_m);
+        }
+        VG_CHECK(false, VG_ERR_INVALID_ARG, "launch_gemm: the code-gathered tile is L2's append");
     }
     if (skip && tiles == 0) return VG_OK;
     if (bf16) {  // rows of bfloat16 (c.ops.dim_words = 4-byte words per row): the LDS-DMA tiles only
@@ -1497,6 +1510,76 @@ int32_t flat_nominate_bf16(vg_index *idx, const NomImage &img, bool dot, const f
     {
         ProfScope prof(idx->ctx, "sq8_nominate_gemm", st);
         VG_TRY(launch_gemm<2>(GemmArgs::append(nc, nom->thr, nom->sel_k, nom->counts, nom->cand, nom->cap).wide(s.counts_wide, idx->ctx->compute_units)));
+    }
+    return k <= kNomPickMaxK ? launch_flat_pick(*nom, cnt, nullptr, st) : VG_OK;
+}
+
+// ---- the PQ nomination from the codes -----------------------------------------------------------------------------------------
+// flat_nominate_bf16 without the image of the decoded rows (vg_index_enable_pq_nomination_from_codes, k_adc.hip): the append GEMM
+// gathers its row tiles from the decoded codebook by the codes (flat_gemm_codes_big_kernel); the threshold sample needs decoded rows
+// for every 64th 128-row tile only — those are decoded into the CALL's scratch (rows / 64 of the image: 1.6 % of it), their norms
+// gathered beside them, and the sample kernels run over that compact image with tile stride 1: the same kernels on the same
+// operands as the image's sample, so the same thresholds.
+// thread per (compact row, granule): compact row c = sampled tile c / 128, its row c % 128
+__global__ void pq_sample_rows_kernel(const uint8_t *__restrict__ codes, int64_t n, int m, const uint4 *__restrict__ cb16, int granules,
+                                      const float *__restrict__ norms, int64_t rows_c, int stride, uint4 *__restrict__ out,
+                                      float *__restrict__ norms_c)
+{
+    const int64_t t = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+    const int64_t c = t / granules;
+    const int j = static_cast<int>(t - c * granules);
+    if (c >= rows_c) return;
+    const int64_t row = (c / kGemmBN) * stride * kGemmBN + (c % kGemmBN);  // (< n: rows_c counts the sampled rows that exist)
+    const int code = j < m ? codes[row * m + j] : 0;
+    out[c * granules + j] = cb16[static_cast<int64_t>(j) * 256 + code];
+    if (j == 0) norms_c[c] = norms[row];
+}
+// the rows of every stride-th 128-row tile of n rows that exist (only the last tile of all can be short)
+static int64_t sample_rows(int64_t n, int stride)
+{
+    const int64_t nt = (n + kGemmBN - 1) / kGemmBN, nts = (nt + stride - 1) / stride;
+    const int64_t last0 = (nts - 1) * stride * kGemmBN;
+    return (nts - 1) * kGemmBN + std::min<int64_t>(kGemmBN, n - last0);
+}
+struct PqCodesScratch : NominateScratch {
+    uint16_t *srows;  // the sampled tiles' decoded rows, dim_pad each
+    float *snorms;
+    PqCodesScratch(char *base, int64_t cnt, int64_t n, int dim_pad, int k) : NominateScratch(base, cnt, n, dim_pad, k)
+    {
+        Carve c{base, bytes};
+        const int64_t rows_c = n > kFlatCap ? sample_rows(n, kFlatSampleStride) : 0;
+        c.take(srows, rows_c * dim_pad);
+        c.take(snorms, rows_c);
+        bytes = c.off;
+    }
+};
+size_t flat_nominate_pq_codes_scratch(int64_t cnt, int64_t n, int dim_pad, int k) { return PqCodesScratch(nullptr, cnt, n, dim_pad, k).bytes; }
+
+int32_t flat_nominate_pq_codes(vg_index *idx, const PqCodesNom &cn, const float *queries, int64_t cnt, int k, char *scratch, hipStream_t st,
+                               ProbeNominated *nom)
+{
+    const PqCodesScratch s(scratch, cnt, idx->n, cn.dim_pad, k);
+    const int m = idx->pq->m, granules = cn.dim_pad / 8;
+    NomCall nc{st, false, {}, cnt, nullptr, 0};
+    // (the GEMM's "rows" are the codebook; n, the row length and the norms are the decoded rows')
+    VG_TRY(gemm_operands(queries, cnt, idx->dim, idx->n, cn.norms, cn.cb16, cn.dim_pad, s.qbf, st, &nc.ops));
+    *nom = s.nom;
+    const bool sampled = idx->n > kFlatCap;
+    NomCall sc = nc;
+    if (sampled) {
+        const int64_t rows_c = sample_rows(idx->n, kFlatSampleStride);
+        VG_LAUNCH(pq_sample_rows_kernel, dim3(static_cast<unsigned>((rows_c * granules + 255) / 256)), dim3(256), 0, st, idx->d_pq_rows, idx->n, m,
+                  reinterpret_cast<const uint4 *>(cn.cb16), granules, cn.norms, rows_c, kFlatSampleStride, reinterpret_cast<uint4 *>(s.srows), s.snorms);
+        sc.ops.b = reinterpret_cast<const float *>(s.srows), sc.ops.n = rows_c, sc.ops.norms = s.snorms;
+    }
+    VG_TRY(sample_thresholds(sc, s, 1, nom->sel_k, nom->thr, sampled));
+    VG_LAUNCH(flat_thr_cap_kernel, dim3(nc.ucnt()), dim3(64), 0, st, nom->thr, nom->sel_k, queries, idx->dim, cn.norm_max);
+    VG_HIP(hipMemsetAsync(nom->counts, 0, sizeof(int) * static_cast<size_t>(cnt), st));
+    {
+        ProfScope prof(idx->ctx, "pq_codes_gemm", st);
+        VG_TRY(launch_gemm<2>(GemmArgs::append(nc, nom->thr, nom->sel_k, nom->counts, nom->cand, nom->cap)
+                                  .wide(s.counts_wide, idx->ctx->compute_units)
+                                  .from_codes(idx->d_pq_rows, m)));
     }
     return k <= kNomPickMaxK ? launch_flat_pick(*nom, cnt, nullptr, st) : VG_OK;
 }

@@ -674,7 +674,16 @@ __device__ __forceinline__ void split2_bf16(float a, float b, uint32_t &hi, uint
 // `tile_active` (or null: every tile): bit tm says whether query tile tm is multiplied at all — step() passes over the slots of
 // the others as it passes over the row-tile holes, and a workgroup that is left with no slot returns before it touches LDS
 // (vg_search_flat's retry of the queries whose screen proof failed).  One word: at most 32 query tiles (the launcher checks).
-enum { kBigImages = 0, kBigSplit = 1, kBigScreen = 2 };
+// OPS = kBigCodes (flat_gemm_codes_big_kernel): the bf16 tile of kBigImages with NO row image.  The rows are PQ codes of
+// sub-dimension 8, so granule j of a decoded bfloat16 row is entry code[row][j] of sub-quantizer j's decoded codebook: `base` is that
+// codebook, [dim / 4][256] entries of 16 bytes (sub-quantizers from code_m on: all zeros — the image's padding), `codes` the
+// row-major code bytes (code_m per row, any alignment).  Only the row tile's fill differs: the lane that reads granule g of row r
+// at K step s from the image reads entry (8 s + g, codes[r][8 s + g]) instead — the tile in LDS is bit for bit the image's, so
+// swizzle, ring, MFMA loop, sign test, appends and the proof's margin (pq_nominate_eps) are kBigImages'.  A lane's four code bytes
+// of a step (one per piece) are loaded one row-tile step AHEAD of the fill that uses them, in front of the previous fill's pieces
+// in the vector-memory queue: the fill waits for them by count (its own four pieces and the query tile's four are younger), not
+// for the tile in flight.  Rows past the end of the matrix re-read the last row's codes, as the image's fill re-reads the last row.
+enum { kBigImages = 0, kBigSplit = 1, kBigScreen = 2, kBigCodes = 3 };
 // SAMPLE (flat_gemm_sample_big_kernel): the score-writing form, MODE 1 of the 128 x 128 tiles on this tile — the rows are every
 // tile_stride-th 128-row tile, written compactly into scores[q][out_cols] as the 128-row kernels write them, so a 256-row tile
 // is a PAIR of sampled 128-row tiles: sample tile ts takes rows [(2 ts) stride 128, + 128) through fill pieces 0-1 and rows
@@ -694,11 +703,13 @@ __device__ __forceinline__ void flat_gemm_big_body(
     uint64_t *__restrict__ cand, int cap, const uint8_t *__restrict__ mask, int64_t mask_stride,
     int count_stride /* ints between two queries' counters: 32 = a 128-byte line each (see launch_gemm_t) */,
     const uint32_t *__restrict__ tile_active = nullptr, float *__restrict__ scores = nullptr /* SAMPLE: [nq][out_cols] */,
-    int tile_stride = 1, int64_t out_cols = 0)
+    int tile_stride = 1, int64_t out_cols = 0, const uint8_t *__restrict__ codes = nullptr /* kBigCodes: [n][code_m] */, int code_m = 0)
 {
     static_assert(NB == 2 || NB == 3, "two or three row-tile buffers");
-    constexpr bool SPLIT = OPS != kBigImages;  // fp32 rows converted in registers (three products, or the screen's one)
+    constexpr bool SPLIT = OPS == kBigSplit || OPS == kBigScreen;  // fp32 rows converted in registers (three products, or the screen's one)
     constexpr bool SCREEN = OPS == kBigScreen;
+    constexpr bool CODES = OPS == kBigCodes;
+    static_assert(!CODES || (NB == 3 && !SAMPLE && PROBE == 0), "the code-gathered tile: three row buffers, the append form");
     extern __shared__ float gemm_lds[];
     const int mtiles = static_cast<int>((nq + kBigBM - 1) / kBigBM);
     // (SAMPLE: the pairs of sampled 128-row tiles)
@@ -777,9 +788,13 @@ __device__ __forceinline__ void flat_gemm_big_body(
         abase = queries + (SCREEN ? q0 * (dim / 2) : q0 * dim);
         a_last = static_cast<int>(nq - q0 < kBigBM ? nq - q0 : kBigBM) - 1;
     };
+    const uint8_t *kbase = nullptr;  // kBigCodes: the codes of the cursor's tile (wave-uniform)
     auto set_b = [&](const Pos &ps) {
         const int64_t n0 = static_cast<int64_t>(tn_of(ps)) * kBigBN;
-        bbase = base + n0 * dim;
+        if constexpr (CODES)
+            kbase = codes + n0 * code_m;
+        else
+            bbase = base + n0 * dim;
         b_last = static_cast<int>(n - n0 < kBigBN ? n - n0 : kBigBN) - 1;
     };
     auto half_row0 = [&](const Pos &ps, int hf) { return (static_cast<int64_t>(tn_of(ps)) * 2 + hf) * tile_stride * kGemmBN; };
@@ -842,7 +857,57 @@ __device__ __forceinline__ void flat_gemm_big_body(
             if (a_pos.bt < total) set_a(a_pos);
         }
     };
+    // kBigCodes.  The cursor (b_pos, b_k, kbase, b_last) is the step whose codes are loaded NEXT, one step ahead of the fills; cc =
+    // the codes of the step to fill next, K step f_k of its tile.  The loads are asm like the fills (the compiler's counter
+    // bookkeeping knows neither); cc is read first by the statement that waits for it.
+    uint32_t cc[4] = {0u, 0u, 0u, 0u};
+    int f_k = 0;
+    auto load_codes = [&]() {
+        const int j = b_k * 8 + dgl;
+        const int jj = j < code_m ? j : 0;  // (a granule past the sub-quantizers: any byte of the row — its block of `base` is zeros)
+        f_k = b_k;
+#pragma unroll
+        for (int p = 0; p < 4; p++) {
+            const int row = p * 64 + drow < b_last ? p * 64 + drow : b_last;
+            const uint32_t voff = static_cast<uint32_t>(row * code_m + jj);
+            asm volatile("global_load_ubyte %0, %1, %2" : "=v"(cc[p]) : "v"(voff), "s"(kbase) : "memory");
+        }
+        if (++b_k == ksteps) {
+            b_k = 0;
+            if (b_pos.bt < total) {
+                step(b_pos);
+                if (b_pos.bt < total) set_b(b_pos);  // (past the stream's end: the last tile's codes once more, never multiplied)
+            }
+        }
+    };
+    // W: vector-memory operations younger than cc's loads that may still be in flight (0: the prologue waits for everything)
+    auto stage_codes = [&](auto W) {
+        const uint32_t jo = static_cast<uint32_t>(f_k * 8 + dgl) << 12;  // entry (j, 0): 256 entries of 16 bytes per sub-quantizer
+        // (the wait and the FIRST reads of cc in one statement: handed cc as an in-out operand of a bare wait, the compiler copies
+        // the four registers in front of it — before the bytes have arrived)
+        uint32_t off[4];
+#define VG_CODES_OFFSETS(cnt)                                                                                                         \
+    asm volatile("s_waitcnt vmcnt(" #cnt ")\n\tv_lshl_add_u32 %0, %4, 4, %8\n\tv_lshl_add_u32 %1, %5, 4, %8\n\tv_lshl_add_u32 %2, %6, 4, %8\n\t" \
+                 "v_lshl_add_u32 %3, %7, 4, %8"                                                                                      \
+                 : "=&v"(off[0]), "=&v"(off[1]), "=&v"(off[2]), "=&v"(off[3])                                                        \
+                 : "v"(cc[0]), "v"(cc[1]), "v"(cc[2]), "v"(cc[3]), "v"(jo)                                                           \
+                 : "memory")
+        if constexpr (decltype(W)::value == 8)
+            VG_CODES_OFFSETS(8);
+        else
+            VG_CODES_OFFSETS(0);
+#undef VG_CODES_OFFSETS
+        load_codes();
+#pragma unroll
+        for (int p = 0; p < 4; p++) glds16(base, off[p], piece(b_buf(ib), p));
+        ib = ib + 1 == NB ? 0 : ib + 1;
+    };
     auto stage_b = [&]() {
+        if constexpr (CODES) {
+            // in the K loop: behind the codes' loads went the previous fill's four pieces and this step's query tile's four
+            stage_codes(std::integral_constant<int, 8>{});
+            return;
+        }
         if (!(PROBE & 64)) fill_b(b_k * kGemmBK, b_buf(ib));
         ib = ib + 1 == NB ? 0 : ib + 1;
         if (++b_k == ksteps) {
@@ -1225,13 +1290,21 @@ __device__ __forceinline__ void flat_gemm_big_body(
 
     // prologue: the first step's tiles (NB = 3: and the second step's row tile) in flight, the first tile's starting values
     // computed under them, then published
+    if constexpr (CODES) load_codes();  // (of the first step)
     tile_loads(pos0);
     stage_a();
-    stage_b();
-    if (NB == 3 && S > 1) stage_b();
+    if constexpr (CODES) {
+        stage_codes(std::integral_constant<int, 0>{});
+        if (S > 1) stage_codes(std::integral_constant<int, 0>{});
+    } else {
+        stage_b();
+        if (NB == 3 && S > 1) stage_b();
+    }
     if constexpr (SAMPLE) pull_norms(xn);
     tile_init();
-    if (NB == 3 && S > 1)
+    if (CODES && S > 1)
+        asm volatile("s_waitcnt vmcnt(8)" ::: "memory");  // (the second step's four pieces and the third's four code bytes)
+    else if (NB == 3 && S > 1)
         asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
     else
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1284,7 +1357,9 @@ __device__ __forceinline__ void flat_gemm_big_body(
         // vmcnt(4) is that row tile's FOUR pieces, whatever the query tile took in front of them (four pieces, the compact
         // image's two): vector-memory operations retire in order, and a wave's pieces per step are queries first, rows last.
         __builtin_amdgcn_s_waitcnt(0xC07F);
-        if (NB == 3 && g + 2 < S)
+        if (CODES && g + 2 < S)  // (kBigCodes: behind query tile g+1 went the code bytes of row tile g+3 and row tile g+2's four pieces)
+            asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+        else if (NB == 3 && g + 2 < S)
             asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
         else
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1345,6 +1420,17 @@ __global__ __launch_bounds__(kBigThreads) void flat_gemm_split_big_kernel(
 {
     flat_gemm_big_body<DOT, NB, PROBE, kBigSplit>(queries, nq, base, n, dim, norms, thr, thr_stride, thr_off, counts, cand, cap, mask,
                                                   mask_stride, count_stride, tile_active);
+}
+// bf16 queries against rows gathered from a decoded PQ codebook by their codes (kBigCodes): `base` = the codebook, dim = words per
+// padded row; the operands are bit for bit flat_gemm_bf16_big_kernel's over the image of the decoded rows
+template <bool DOT, int NB>
+__global__ __launch_bounds__(kBigThreads) void flat_gemm_codes_big_kernel(
+    const float *__restrict__ queries, int64_t nq, const float *__restrict__ base, int64_t n, int dim, const float *__restrict__ norms,
+    const float *__restrict__ thr, int thr_stride, int thr_off, int *__restrict__ counts, uint64_t *__restrict__ cand, int cap,
+    const uint8_t *__restrict__ mask, int64_t mask_stride, int count_stride, const uint8_t *__restrict__ codes, int code_m)
+{
+    flat_gemm_big_body<DOT, NB, 0, kBigCodes>(queries, nq, base, n, dim, norms, thr, thr_stride, thr_off, counts, cand, cap, mask, mask_stride,
+                                              count_stride, nullptr, nullptr, 1, 0, codes, code_m);
 }
 // the same operands, the product of the hi halves alone (the screen in front of the split tile)
 template <bool DOT, int NB, int PROBE = 0>

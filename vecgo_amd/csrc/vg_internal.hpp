@@ -480,6 +480,26 @@ inline int32_t nom_free(NomImage &img, hipStream_t st)
     img = NomImage{};
     return VG_OK;
 }
+// The PQ nomination FROM THE CODES (vg_index_enable_pq_nomination_from_codes, k_adc.hip; all null when off): no decoded-row image —
+// the nomination GEMM's row tile is gathered from a bfloat16 copy of the decoded codebook, granule by granule (sub-dimension 8: a
+// 16-byte granule of a decoded row IS one centroid).  Resident: that codebook, the rows' norms and their largest.
+struct PqCodesNom {
+    uint16_t *cb16 = nullptr;   // [dim_pad / 8][256][8] bfloat16: entry (j, c) = centroid c of sub-quantizer j decoded and rounded; j >= m: zeros
+    int32_t dim_pad = 0;        // dim padded to whole 64-element K steps, as NomImage's
+    float *norms = nullptr;     // n: |x^|^2, as NomImage's
+    float *norm_max = nullptr;  // [1]
+    int64_t held_bytes(int64_t n) const { return cb16 ? static_cast<int64_t>(dim_pad / 8) * 256 * 16 + n * 4 + 4 : 0; }
+};
+inline int32_t nom_free(PqCodesNom &cn, hipStream_t st)
+{
+    if (!cn.cb16) return VG_OK;
+    VG_HIP(hipStreamSynchronize(st));
+    VG_HIP(hipFree(cn.cb16));
+    VG_HIP(hipFree(cn.norms));
+    VG_HIP(hipFree(cn.norm_max));
+    cn = PqCodesNom{};
+    return VG_OK;
+}
 }  // namespace vg
 
 struct vg_index {
@@ -526,6 +546,7 @@ struct vg_index {
     // PQ codes in the reference's row-major layout (random access by node id in graph search)
     uint8_t *d_pq_rows = nullptr;
     vg::NomImage pq_nom;               // vg_index_enable_pq_nomination: the DECODED rows (pq.go:185-229)
+    vg::PqCodesNom pq_cnom;            // vg_index_enable_pq_nomination_from_codes: the decoded CODEBOOK and the rows' norms
     uint8_t *d_rq_rows = nullptr;
     // SQ8 codes, re-tiled like the PQ codes: [tile][group of 16 dims][lane][16 B]; see k_sq8_scan.hip
     vg_sq8 *sq = nullptr;
@@ -556,6 +577,7 @@ inline const char *held_segment_state(const vg_index *idx)
            : idx->d_vamana                       ? "a Vamana graph"
            : idx->sq_nom.rows                    ? "an SQ8 nomination image"
            : idx->pq_nom.rows                    ? "a PQ nomination image"
+           : idx->pq_cnom.cb16                   ? "a PQ nomination from the codes"
                                                  : nullptr;
 }
 // The same for the streaming Vamana insert (vg_vamana_insert): what its new rows would lack, or null
@@ -570,6 +592,7 @@ inline const char *held_fresh_state(const vg_index *idx)
            : idx->d_hnsw_tomb                    ? "HNSW tombstones"
            : idx->sq_nom.rows                    ? "an SQ8 nomination image"
            : idx->pq_nom.rows                    ? "a PQ nomination image"
+           : idx->pq_cnom.cb16                   ? "a PQ nomination from the codes"
                                                  : nullptr;
 }
 }  // namespace vg

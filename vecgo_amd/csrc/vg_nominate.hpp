@@ -28,6 +28,10 @@ struct GemmGroup;  // vg_flat_gemm.hpp
 size_t flat_nominate_bf16_scratch(int64_t cnt, int64_t n, int dim_pad, int k);
 int32_t flat_nominate_bf16(vg_index *idx, const NomImage &img, bool dot, const float *queries, int64_t cnt, const uint8_t *mask,
                            int64_t mask_stride, int k, char *scratch, hipStream_t st, ProbeNominated *nom);
+// the same for the PQ nomination from the codes (PqCodesNom, vg_internal.hpp): L2, unfiltered
+size_t flat_nominate_pq_codes_scratch(int64_t cnt, int64_t n, int dim_pad, int k);
+int32_t flat_nominate_pq_codes(vg_index *idx, const PqCodesNom &cn, const float *queries, int64_t cnt, int k, char *scratch, hipStream_t st,
+                               ProbeNominated *nom);
 size_t flat_probe_gemm_scratch_bytes(int64_t pairs, int64_t ns_max, int k, int bf16_dim);
 int32_t flat_probe_gemm(vg_index *idx, const float *pair_queries, int64_t pairs, const GemmGroup *groups, const int64_t *const first_block[4],
                         int ngroups, const int64_t grid[4], int sample_stride, int64_t ns_max, int k, uint32_t *pair_ids,
@@ -196,26 +200,39 @@ inline int32_t failed_list(const int *d_fail, int64_t cnt, int64_t base, hipStre
 // query / for the batch, or null): writes every query's k results and lists the queries whose proof failed — the caller searches
 // those again (rescan_failed).  4096 queries a pass.  verify(queries, cnt, nom, extra, ids, scores, fail) re-scores and proves a
 // pass's nominations; extra: extra_floats per query of the pass's scratch (the PQ distance tables).
-template <class Verify>
-int32_t nominated_pass(vg_index *idx, const NomImage &img, bool dot, const float *q, int64_t nq, int k, const uint8_t *mask,
-                       int64_t mask_stride, size_t extra_floats, uint32_t *oid, float *osc, hipStream_t st, std::vector<int> &failed,
-                       Verify verify)
+// nominate(queries, q0, cnt, scratch, &nom): a pass's nomination in scratch_bytes(cnt) of scratch.
+template <class ScratchBytes, class Nominate, class Verify>
+int32_t nominated_pass_by(vg_index *idx, ScratchBytes scratch_bytes, Nominate nominate, const float *q, int64_t nq, int k, size_t extra_floats,
+                          uint32_t *oid, float *osc, hipStream_t st, std::vector<int> &failed, Verify verify)
 {
     for (int64_t q0 = 0; q0 < nq; q0 += 4096) {
         const int64_t cnt = std::min<int64_t>(4096, nq - q0);
         ArenaCall ar(idx->ctx, st);
-        const int i_scr = ar.add(flat_nominate_bf16_scratch(cnt, idx->n, img.dim_pad, k));
+        const int i_scr = ar.add(scratch_bytes(cnt));
         const int i_fail = ar.add(sizeof(int) * static_cast<size_t>(cnt));
         const int i_extra = ar.add(sizeof(float) * static_cast<size_t>(cnt) * extra_floats);
         VG_TRY(ar.commit());
         int *fail = ar.get<int>(i_fail);
         const float *qq = q + q0 * idx->dim;
         ProbeNominated nom;
-        VG_TRY(flat_nominate_bf16(idx, img, dot, qq, cnt, mask ? mask + q0 * mask_stride : nullptr, mask_stride, k, ar.get<char>(i_scr), st, &nom));
+        VG_TRY(nominate(qq, q0, cnt, ar.get<char>(i_scr), &nom));
         VG_TRY(verify(qq, cnt, nom, ar.get<float>(i_extra), oid + q0 * k, osc + q0 * k, fail));
         VG_TRY(failed_list(fail, cnt, q0, st, failed));
     }
     return VG_OK;
+}
+// on a bfloat16 image of the decoded rows
+template <class Verify>
+int32_t nominated_pass(vg_index *idx, const NomImage &img, bool dot, const float *q, int64_t nq, int k, const uint8_t *mask,
+                       int64_t mask_stride, size_t extra_floats, uint32_t *oid, float *osc, hipStream_t st, std::vector<int> &failed,
+                       Verify verify)
+{
+    return nominated_pass_by(
+        idx, [&](int64_t cnt) { return flat_nominate_bf16_scratch(cnt, idx->n, img.dim_pad, k); },
+        [&](const float *qq, int64_t q0, int64_t cnt, char *scratch, ProbeNominated *nom) {
+            return flat_nominate_bf16(idx, img, dot, qq, cnt, mask ? mask + q0 * mask_stride : nullptr, mask_stride, k, scratch, st, nom);
+        },
+        q, nq, k, extra_floats, oid, osc, st, failed, verify);
 }
 
 // The failed queries of a batch searched again: their queries (and, with a filter per query, their filters of mask_bytes) gathered,
