@@ -1,5 +1,5 @@
 """Chosen inputs for the fan-in merge (vg_merge_topk / _packed, vg_comm_all_gather_topk -> pack_keys_kernel, topk_merge_kernel,
-merge_nan_replay_kernel in vecgo_amd/csrc/k_adc.hip), the reference they are compared with, and a model of which of the
+merge_nan_replay_kernel in vecgo_amd/csrc/k_topk_merge.hip), the reference they are compared with, and a model of which of the
 kernel's selection paths an input reaches.  Plain numpy; the reference is the oracle's CandidateHeap on the CPU.
 
 Builders return (ids[lists, nq, k] uint32, scores[lists, nq, k] float32, id_offsets[lists] uint32).  Every list is best first,
@@ -49,7 +49,7 @@ def merge_path(ids, scores, k, descending, id_offsets=None) -> MergePath:
 
     This is a MODEL OF THE CODE UNDER TEST, not a reference: it restates the kernel's own two bounds and its survivor count so
     that a test case can assert that it reaches the path it was written for.  It says nothing about what the merge should
-    return (that is reference_merge below).  It mirrors vecgo_amd/csrc/k_adc.hip, topk_merge_kernel:
+    return (that is reference_merge below).  It mirrors vecgo_amd/csrc/k_topk_merge.hip, topk_merge_kernel:
       - first bound, the smallest k-th key of any list:            the loop `for (int l = tid; l < lists; ...) src[l * k + (k - 1)]`
       - second bound, the k-th smallest list head, computed only if `lists >= k && lists <= kMergeBuf && k >= 1`, over the
         heads padded to a power of two, and applied only if it is a real key (`hk != kKeyMax`)

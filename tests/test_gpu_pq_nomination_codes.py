@@ -237,6 +237,38 @@ def test_memory_and_lifetime(vg, ctx, nominate_always):
     assert i4.pq_nomination_info() == (0, 0)
 
 
+def test_each_entry_point_switches_its_own_mode(vg, ctx, nominate_always):
+    """enable_X(False) drops mode X alone; a refused enable_X(True) leaves a different active mode as it was"""
+    rng = np.random.default_rng(78)
+    n, dim, m, nq, k = 9000, 128, 16, 160, 10
+    opq = _random_pq(rng, dim, m)
+    codes = _clustered_codes(rng, n, m)
+    pq, idx = _mk(vg, ctx, opq, codes, n)
+    q = _queries(rng, _decoded(opq, codes), nq)
+    plain = idx.search_pq_adc(q, k)
+    idx.enable_pq_nomination_from_codes(True)
+    idx.enable_pq_nomination(False)                           # not its mode: mode 2 stays, and still takes the batch
+    assert idx.pq_nomination_info()[0] == 2
+    got, launches = _launches(ctx, lambda: idx.search_pq_adc(q, k))
+    assert launches >= 1 and _same(plain, got)
+    idx.enable_pq_nomination(True)
+    held = idx.pq_nomination_info()
+    assert held == (1, n * (dim * 2 + 4) + 4)                 # the image (dim_pad = dim here), the norms, norm_max
+    idx.enable_pq_nomination_from_codes(False)                # not its mode: mode 1 stays
+    assert idx.pq_nomination_info() == held
+    assert _same(plain, idx.search_pq_adc(q, k))
+    # sub-vectors of 4 dimensions: the image is on, from the codes is refused and the image stays
+    o4 = _random_pq(rng, 64, 16)
+    p4, i4 = _mk(vg, ctx, o4, rng.integers(0, 256, (100, 16)).astype(np.uint8), 100)
+    i4.enable_pq_nomination(True)
+    held = i4.pq_nomination_info()
+    assert held == (1, 100 * (64 * 2 + 4) + 4)
+    with pytest.raises(vg.VecgoHipError) as e:
+        i4.enable_pq_nomination_from_codes(True)
+    assert e.value.status == -5
+    assert i4.pq_nomination_info() == held
+
+
 def test_reorder_moves_the_norms_with_the_codes(vg, ctx, nominate_always):
     """vg_vamana_reorder_bfs on an index with the mode on (as the image's case in tests/test_gpu_vamana_reorder.py): afterwards the
     nominated batch equals the table scan over the permuted codes and a fresh index of them"""

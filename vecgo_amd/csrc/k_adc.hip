@@ -25,6 +25,9 @@
 // Per-row arithmetic = pqAdcLookupAvx512 (internal/simd/src/floats_avx512.c:135-167):
 // 16 lane accumulators acc[l] += table[(16g+l)*256 + code[16g+l]] for g ascending, the
 // _mm512_reduce_add_ps tree, then the m%16 tail added sequentially.  fp32 adds only.
+//
+// (The fan-in merge of the scan's partial lists: k_topk_merge.hip.  The opt-in batch nomination the driver tries first:
+// k_pq_nominate.hip.)
 #include <algorithm>
 
 #include "vg_adc_row.hpp"
@@ -55,7 +58,6 @@ constexpr int kAdcWaves = VG_ADC_WAVES;       // 512 threads, one workgroup per 
 constexpr int kAdcThreads = kAdcWaves * kWave;
 constexpr int kAdcSyncEvery = 2;              // iterations between candidate-buffer checks
 constexpr int kAdcBuf = 4096;                 // candidate keys in LDS (32 KiB)
-constexpr int kAdcMaxK = 1024;
 
 __global__ void pq_retile_kernel(const uint8_t *__restrict__ codes, int64_t n, int m, int groups,
                                  int64_t n_tiles, uint4 *__restrict__ tiles)
@@ -421,119 +423,6 @@ __global__ __launch_bounds__(kAdcThreads) void pq_adc_scan_kernel(
 // 10M rows — 7.0 k vs 8.2 k queries/s.  The one-query scan is bound by the HBM stream, not by LDS (r02 stage probes,
 // DESIGN.md section 4), so there was nothing for it to win there either.  Dropped in r03.)
 
-// One workgroup per query: merges `lists` ascending key lists of length k (kKeyMax padded)
-// into the k best keys, best first, and decodes them to (id, score).
-// Pruning: the k-th key of any single list bounds the global k-th key from above, and so does
-// the k-th smallest list head; only keys <= T = min of the two bounds can make the result.
-constexpr int kMergeThreads = 256;
-constexpr int kMergeBuf = 4096;
-__global__ __launch_bounds__(kMergeThreads) void topk_merge_kernel(
-    const uint64_t *__restrict__ partial, int lists, int k, bool descending,
-    uint32_t *__restrict__ ids, float *__restrict__ scores, const int *__restrict__ only_if,
-    const int *__restrict__ always)
-{
-    __shared__ uint64_t buf[kMergeBuf];
-    __shared__ unsigned long long tmin;
-    __shared__ int cnt;
-    const int q = blockIdx.x;
-    if (only_if && !only_if[q] && !(always && always[0])) return;  // query not selected
-    const int tid = threadIdx.x;
-    const uint64_t *src = partial + static_cast<int64_t>(q) * lists * k;
-    const int64_t total = static_cast<int64_t>(lists) * k;
-    uint32_t *oid = ids + static_cast<int64_t>(q) * k;
-    float *osc = scores + static_cast<int64_t>(q) * k;
-    if (tid == 0) {
-        tmin = kKeyMax;
-        cnt = 0;
-    }
-    __syncthreads();
-    uint64_t t = kKeyMax;
-    for (int l = tid; l < lists; l += kMergeThreads) {
-        uint64_t v = src[static_cast<int64_t>(l) * k + (k - 1)];
-        t = v < t ? v : t;
-    }
-    if (t != kKeyMax) atomicMin(&tmin, static_cast<unsigned long long>(t));
-    // Second bound: the heads of k different lists are k different keys, so the k-th smallest HEAD
-    // is >= the global k-th key too.  With many short lists it is far tighter than the first
-    // (1024 lists of 10: ~2.5 survivors per list under T1, ~1.5k in total under the head bound).
-    if (lists >= k && lists <= kMergeBuf && k >= 1) {
-        int n2 = 1;
-        while (n2 < lists) n2 <<= 1;
-        for (int l = tid; l < n2; l += kMergeThreads) buf[l] = l < lists ? src[static_cast<int64_t>(l) * k] : kKeyMax;
-        __syncthreads();
-        bitonic_sort_lds(buf, n2, tid, kMergeThreads);
-        const uint64_t hk = buf[k - 1];
-        __syncthreads();  // everyone has read buf[k-1] before the buffer is reused below
-        if (tid == 0 && hk != kKeyMax) atomicMin(&tmin, static_cast<unsigned long long>(hk));
-    }
-    __syncthreads();
-    const uint64_t T = tmin;
-    // lists are ascending: walk each from its head while keys stay <= T (usually 0-2 steps)
-    for (int l = tid; l < lists; l += kMergeThreads) {
-        const uint64_t *lp = src + static_cast<int64_t>(l) * k;
-        for (int i = 0; i < k; i++) {
-            const uint64_t key = lp[i];
-            if (key == kKeyMax || key > T) break;
-            int pos = atomicAdd(&cnt, 1);
-            if (pos < kMergeBuf) buf[pos] = key;
-        }
-    }
-    __syncthreads();
-    const int c = cnt;
-    int have;
-    if (c <= 1024) {
-        // brute-force rank among the survivors; a candidate listed twice (the same score and global id in two lists) is two
-        // equal keys: the buffer position breaks the tie, so they take consecutive ranks, as the sort below places them
-        for (int i = tid; i < c; i += kMergeThreads) {
-            const uint64_t e = buf[i];
-            int rank = 0;
-            for (int j = 0; j < c; j++) {
-                const uint64_t o = buf[j];
-                rank += (o < e || (o == e && j < i)) ? 1 : 0;
-            }
-            if (rank < k) {
-                oid[rank] = key_row(e);
-                osc[rank] = key_score(e, descending);
-            }
-        }
-        have = c < k ? c : k;
-    } else {
-        // many survivors (heavy ties / adversarial order): chunked sort of everything
-        int kept = 0;
-        int64_t pos = 0;
-        __syncthreads();
-        do {
-            int room = kMergeBuf - kept;
-            int take = static_cast<int>((total - pos) < room ? (total - pos) : room);
-            for (int i = tid; i < take; i += kMergeThreads) buf[kept + i] = src[pos + i];
-            for (int i = kept + take + tid; i < kMergeBuf; i += kMergeThreads) buf[i] = kKeyMax;
-            __syncthreads();
-            bitonic_sort_lds(buf, kMergeBuf, tid, kMergeThreads);
-            pos += take;
-            kept = k;  // k <= kAdcMaxK < kMergeBuf; slots past the real keys hold kKeyMax
-        } while (pos < total);
-        have = 0;
-        for (int i = tid; i < k; i += kMergeThreads) {
-            const uint64_t e = buf[i];
-            if (e != kKeyMax) {
-                oid[i] = key_row(e);
-                osc[i] = key_score(e, descending);
-            }
-        }
-        // count real keys among the first k (uniform across threads)
-        int lo = 0, hi = k;
-        while (lo < hi) {
-            int mid = (lo + hi) >> 1;
-            if (buf[mid] != kKeyMax) lo = mid + 1; else hi = mid;
-        }
-        have = lo;
-    }
-    for (int i = have + tid; i < k; i += kMergeThreads) {
-        oid[i] = VG_INVALID_ID;
-        osc[i] = descending ? -INFINITY : INFINITY;
-    }
-}
-
 // k > 64: per query, the k best keys of the union of `lists` per-wave lists (64 keys each,
 // ascending, kKeyMax padded) and a proof that nothing better was dropped: a wave only ever
 // discards keys above its own 64th key, so the result is exact iff the k-th selected key is not
@@ -641,14 +530,6 @@ __global__ void patch_results_kernel(const int *__restrict__ flags, int k, const
     }
 }
 
-int32_t launch_topk_merge(const uint64_t *partial, int64_t nq, int lists, int k, bool descending,
-                          uint32_t *ids, float *scores, hipStream_t st, const int *only_if, const int *always)
-{
-    if (nq == 0 || k == 0) return VG_OK;
-    VG_LAUNCH(topk_merge_kernel, dim3(static_cast<unsigned>(nq)), dim3(kMergeThreads), 0,
-                       st, partial, lists, k, descending, ids, scores, only_if, always);
-    return VG_OK;
-}
 
 // ---- partition-probed ADC scan (flat/segment.go:727-744 over the :678-689 branch) -----------------
 // One workgroup per (query, share of its probe list): the query's table is staged once, then the
@@ -888,161 +769,6 @@ static int32_t launch_scan_wide(const vg_index *idx, const float *tables, int64_
 
 }  // namespace vg
 
-namespace vg {
-// (id, score) lists [lists][nq][k] -> keys [nq][lists][k] (ascending per list is preserved)
-// list_stride: elements between the starts of two lists in ids[] / scores[] (nq*k when the lists are dense;
-// 2*nq*k for the all-gathered [list][ids | score bits][nq][k] image of vg_comm.hip)
-__global__ void pack_keys_kernel(const uint32_t *__restrict__ ids, const float *__restrict__ scores,
-                                 int lists, int64_t nq, int k, int64_t list_stride, bool descending,
-                                 const uint32_t *__restrict__ offsets, uint64_t *__restrict__ keys)
-{
-    const int64_t gid = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-    const int64_t total = static_cast<int64_t>(lists) * nq * k;
-    if (gid >= total) return;
-    const int i = static_cast<int>(gid % k);
-    const int64_t q = (gid / k) % nq;
-    const int l = static_cast<int>(gid / (static_cast<int64_t>(k) * nq));
-    const int64_t src = l * list_stride + q * k + i;
-    const uint32_t id = ids[src];
-    uint64_t key = kKeyMax;
-    if (id != VG_INVALID_ID) key = make_key(scores[src], id + (offsets ? offsets[l] : 0u), descending);
-    keys[(q * lists + l) * k + i] = key;
-}
-}  // namespace vg
-
-namespace vg {
-// The engine's fan-in when a list holds a NaN score (include/vecgo_hip.h "NaN scores"): engine/search.go:904-908 pushes every
-// segment's candidates — in the order they were popped from the segment's heap, worst first, i.e. each list here from its last
-// valid entry to its first — into ONE CandidateHeap with TryPushBounded(k), then pops it (:915-918).  The key merge above is that
-// outcome while no score is a NaN; a query with one is replayed here by one wave and overwrites the key merge's answer.  Ids are
-// the offset (global) ones: offsets ascend with the segment, so (SegmentID, RowID) orders like the global id.
-__global__ __launch_bounds__(64) void merge_nan_replay_kernel(const uint32_t *__restrict__ ids_in, const float *__restrict__ scores_in, int lists,
-                                                              int64_t nq, int k, int64_t list_stride, bool desc,
-                                                              const uint32_t *__restrict__ offsets, uint32_t *__restrict__ ids,
-                                                              float *__restrict__ scores)
-{
-    extern __shared__ uint64_t merge_lds[];
-    CItem *heap = reinterpret_cast<CItem *>(merge_lds);
-    const int64_t q = blockIdx.x;
-    const int lane = threadIdx.x;
-    // a NaN, or a -0.0 score: InternalCandidateBetter compares floats, for which -0.0 == +0.0 (the lower global id wins),
-    // while the key orders -0.0 strictly first; the replay below compares floats.  (The library's own searches emit one sign of
-    // zero per metric; a caller's lists may hold both.)
-    bool nan = false;
-    for (int t = lane; t < lists * k; t += 64) {
-        const int64_t src = static_cast<int64_t>(t / k) * list_stride + q * k + t % k;
-        if (ids_in[src] != VG_INVALID_ID) {
-            const float v = scores_in[src];
-            nan = nan || v != v || __float_as_uint(v) == 0x80000000u;
-        }
-    }
-    if (!__any(nan)) return;
-    int len = 0;
-    for (int l = 0; l < lists; l++) {
-        const int64_t base = static_cast<int64_t>(l) * list_stride + q * k;
-        int cnt = 0;  // valid entries are a prefix of the list
-        for (int i0 = 0; i0 < k; i0 += 64) {
-            const bool valid = i0 + lane < k && ids_in[base + i0 + lane] != VG_INVALID_ID;
-            cnt += __popcll(__ballot(valid));
-        }
-        const uint32_t off = offsets ? offsets[l] : 0u;
-        for (int i = cnt - 1; i >= 0; i--) {
-            const CItem x{scores_in[base + i], ids_in[base + i] + off};
-            if (len < k) {
-                cand_up(heap, len, x, desc);
-                len++;
-            } else if (cand_better(x, cand_load(heap, 0), desc)) {
-                cand_down(heap, 0, len, x, desc);
-            }
-        }
-    }
-    const int nres = len;
-    for (int i = nres - 1; i >= 0; i--) {
-        const CItem it = cand_pop(heap, len, desc);
-        if (lane == 0) {
-            ids[q * k + i] = it.row;
-            scores[q * k + i] = it.score;
-        }
-    }
-    for (int i = nres + lane; i < k; i += 64) {
-        ids[q * k + i] = VG_INVALID_ID;
-        scores[q * k + i] = desc ? -INFINITY : INFINITY;
-    }
-}
-}  // namespace vg
-
-static int32_t merge_topk_impl(vg_ctx *ctx, const uint32_t *ids_in, const float *scores_in, int64_t list_stride,
-                               int32_t lists, int64_t nq, int32_t k, int32_t metric, const uint32_t *id_offsets,
-                               uint32_t *ids, float *scores, void *stream);
-
-VG_API int32_t vg_merge_topk(vg_ctx *ctx, const uint32_t *ids_in, const float *scores_in, int32_t lists,
-                             int64_t nq, int32_t k, int32_t metric, const uint32_t *id_offsets,
-                             uint32_t *ids, float *scores, void *stream)
-{
-    return merge_topk_impl(ctx, ids_in, scores_in, nq * k, lists, nq, k, metric, id_offsets, ids, scores, stream);
-}
-
-VG_API int32_t vg_merge_topk_packed(vg_ctx *ctx, const uint32_t *packed, int32_t lists, int64_t nq, int32_t k,
-                                    int32_t metric, const uint32_t *id_offsets, uint32_t *ids, float *scores,
-                                    void *stream)
-{
-    VG_CHECK(lists == 0 || nq == 0 || k == 0 || (packed && vg::is_device_ptr(packed)), VG_ERR_INVALID_ARG,
-             "vg_merge_topk_packed: packed must be device memory");
-    return merge_topk_impl(ctx, packed, reinterpret_cast<const float *>(packed) + nq * k, 2 * nq * k, lists, nq, k,
-                           metric, id_offsets, ids, scores, stream);
-}
-
-static int32_t merge_topk_impl(vg_ctx *ctx, const uint32_t *ids_in, const float *scores_in, int64_t list_stride,
-                               int32_t lists, int64_t nq, int32_t k, int32_t metric, const uint32_t *id_offsets,
-                               uint32_t *ids, float *scores, void *stream)
-{
-    VG_CHECK(ctx, VG_ERR_INVALID_ARG, "vg_merge_topk: ctx is NULL");
-    VG_CHECK(lists >= 0 && nq >= 0 && k >= 0, VG_ERR_INVALID_ARG, "vg_merge_topk: negative count");
-    if (nq == 0 || k == 0) return VG_OK;
-    VG_CHECK(ids && scores, VG_ERR_INVALID_ARG, "vg_merge_topk: NULL output");
-    VG_CHECK(lists == 0 || (ids_in && scores_in), VG_ERR_INVALID_ARG, "vg_merge_topk: NULL input");
-    VG_CHECK(k <= vg::kAdcMaxK, VG_ERR_UNSUPPORTED, "vg_merge_topk: k=%d exceeds %d", k, vg::kAdcMaxK);
-    VG_CHECK(metric >= VG_METRIC_L2 && metric <= VG_METRIC_DOT, VG_ERR_UNSUPPORTED,
-             "vg_merge_topk: unsupported metric %d", metric);
-    VG_HIP(hipSetDevice(ctx->device));
-    hipStream_t st = vg::pick_stream(ctx, stream);
-    const bool desc = metric != VG_METRIC_L2;
-    const size_t total = static_cast<size_t>(lists) * nq * k;
-    const bool dense = list_stride == nq * k;  // the packed image is device memory already (checked by the caller)
-    vg::DevIn<uint32_t> i_in, offs;
-    vg::DevIn<float> s_in;
-    vg::DevOut<uint32_t> oid;
-    vg::DevOut<float> osc;
-    if (dense) {
-        VG_TRY(i_in.init(ids_in, total, st));
-        VG_TRY(s_in.init(scores_in, total, st));
-    } else {
-        i_in.ptr = ids_in;
-        s_in.ptr = scores_in;
-    }
-    VG_TRY(offs.init(id_offsets, id_offsets ? static_cast<size_t>(lists) : 0, st));
-    VG_TRY(oid.init(ids, static_cast<size_t>(nq) * k, st));
-    VG_TRY(osc.init(scores, static_cast<size_t>(nq) * k, st));
-    const int nl = lists > 0 ? lists : 1;
-    vg::ArenaCall ar(ctx, st);
-    const int i_keys = ar.add(sizeof(uint64_t) * static_cast<size_t>(nl) * nq * k);
-    VG_TRY(ar.commit());
-    uint64_t *keys = ar.get<uint64_t>(i_keys);
-    if (lists == 0) {
-        VG_HIP(hipMemsetAsync(keys, 0xFF, static_cast<size_t>(nq) * k * 8, st));
-    } else {
-        VG_LAUNCH(vg::pack_keys_kernel, dim3(static_cast<unsigned>((total + 255) / 256)), dim3(256),
-                           0, st, i_in.ptr, s_in.ptr, lists, nq, k, list_stride, desc, offs.ptr, keys);
-    }
-    VG_TRY(vg::launch_topk_merge(keys, nq, nl, k, desc, oid.ptr, osc.ptr, st));
-    if (lists > 0 && !vg::hook(vg::kHookNoCandReplay))  // queries with a NaN or a -0.0 score in a list: the engine's heap, operation by operation
-        VG_LAUNCH(vg::merge_nan_replay_kernel, dim3(static_cast<unsigned>(nq)), dim3(64), sizeof(uint64_t) * (static_cast<size_t>(k) + 4), st,
-                  i_in.ptr, s_in.ptr, lists, nq, k, list_stride, desc, offs.ptr, oid.ptr, osc.ptr);
-    VG_TRY(oid.finish());
-    VG_TRY(osc.finish());
-    return VG_OK;
-}
-
 VG_API int32_t vg_index_set_pq_codes(vg_index *idx, vg_pq *pq, const uint8_t *codes, void *stream)
 {
     VG_CHECK(idx && pq, VG_ERR_INVALID_ARG, "vg_index_set_pq_codes: NULL handle");
@@ -1056,8 +782,7 @@ VG_API int32_t vg_index_set_pq_codes(vg_index *idx, vg_pq *pq, const uint8_t *co
         VG_HIP(hipFree(idx->d_pq_tiles));
         idx->d_pq_tiles = nullptr;
     }
-    VG_TRY(vg::nom_free(idx->pq_nom, st));  // the old codes' nomination image (vg_index_enable_pq_nomination again after new codes)
-    VG_TRY(vg::nom_free(idx->pq_cnom, st));  // ... and their norms (vg_index_enable_pq_nomination_from_codes)
+    VG_TRY(vg::nom_free(idx->pq_nom, st));  // the old codes' nomination (vg_index_enable_pq_nomination / _from_codes again after new codes)
     idx->pq = pq;
     idx->pq_groups = (pq->m + 15) / 16;
     idx->n_tiles = (idx->n + 63) / 64;
@@ -1078,225 +803,6 @@ VG_API int32_t vg_index_set_pq_codes(vg_index *idx, vg_pq *pq, const uint8_t *co
                        dim3(256), 0, st, in.ptr, idx->n, pq->m, idx->pq_groups, idx->n_tiles,
                        reinterpret_cast<uint4 *>(idx->d_pq_tiles));
     VG_HIP(hipStreamSynchronize(st));
-    return VG_OK;
-}
-
-// ---- batched search through a bfloat16 nomination (vg_index_enable_pq_nomination) ----------------------------------------------
-// One table scan per query runs at the LDS gather rate: 12.5 ms for 1024 queries x 1M x m = 96.  A row's table sum IS a squared
-// distance — sum_j |q_j - C_j[code_j]|^2 = |q - x^|^2 for the DECODED row x^ (pq.go:185-229; the table entries are computed from
-// the same fp32 centroid values, pq.go:468-491) — so with the opt-in image (x^ rounded to bfloat16, 2 bytes per dimension) the batch
-// runs the shared nomination (vg_nominate.hpp), re-scores with the reference's own arithmetic — BuildDistanceTable +
-// pqAdcLookupAvx512 on the CODES (PqTableRow) — and proves the result (bfloat16 rounding of both operands, fp32 accumulation on
-// both sides).  A query whose proof fails is scanned as before.
-namespace vg {
-// the batches the nomination takes: 1M x 768, m = 96, k = 10: 16 queries 0.24 ms scanned / 0.39 nominated, 32: 0.46 / 0.41, 64: 0.86 /
-// 0.43, 1024: 12.4 / 1.7 (tools/pq_nominate_time.py) — the scan costs ~12 us per query and 1M rows, the nomination ~0.4 ms up to
-// 128 queries; 100k rows: 128 queries 0.27 / 0.31, 256: 0.50 / 0.28 — from 24M (query, row) pairs up.  Test hook VG_PQ_NOM_ALWAYS:
-// every batch.
-constexpr int64_t kPqNomMinPairs = 24000000;
-
-// one wave per row: lane l decodes sub-quantizers l, l + 64, ... — v = float32(int8) * scale ; v = v + offset, the two rounded
-// operations of the reference's dequantisation (pq.go:204-214) — rounds to bfloat16 (nearest even), writes the image row
-// (dim_pad elements, zeros from dim on) and the row's norm
-// (ROWS false: the norms alone — pq_norms_kernel, the nomination from the codes: the same operations in the same order)
-template <bool ROWS>
-__device__ __forceinline__ void pq_decode_row(const uint8_t *__restrict__ codes, int64_t n, int m, int k, int sd,
-                                              const int8_t *__restrict__ codebooks, const float *__restrict__ scales,
-                                              const float *__restrict__ offsets, uint16_t *__restrict__ out, int dim_pad,
-                                              float *__restrict__ norms, int *__restrict__ norm_max_bits)
-{
-    const int lane = threadIdx.x & 63;
-    const int64_t row = static_cast<int64_t>(blockIdx.x) * 4 + (threadIdx.x >> 6);
-    if (row >= n) return;  // (whole waves)
-    uint16_t *dst = ROWS ? out + row * dim_pad : nullptr;
-    float nrm = 0.0f;
-    for (int j = lane; j < m; j += 64) {
-        const int c = codes[row * m + j];
-        const int8_t *cb = codebooks + (static_cast<int64_t>(j) * k + c) * sd;
-        const float sc = scales[j], of = offsets[j];
-        for (int d = 0; d < sd; d++) {
-            float v = static_cast<float>(cb[d]) * sc;
-            v = v + of;
-            nrm = __builtin_fmaf(v, v, nrm);
-            const uint32_t b = __float_as_uint(v);
-            if constexpr (ROWS) dst[j * sd + d] = static_cast<uint16_t>((b + 0x7FFFu + ((b >> 16) & 1u)) >> 16);
-        }
-    }
-    if constexpr (ROWS)
-        for (int j = m * sd + lane; j < dim_pad; j += 64) dst[j] = 0;
-    for (int off = 32; off > 0; off >>= 1) nrm += __shfl_xor(nrm, off);
-    if (lane == 0) {
-        norms[row] = nrm;
-        // a NaN norm (a NaN scale / offset) must reach norm_max: NaN -> +Inf, the proof's comparisons then fail and the scan answers
-        const int nb = __float_as_int(nrm == nrm ? nrm : INFINITY);  // non-negative floats order like their bits
-        if (nb > *reinterpret_cast<volatile int *>(norm_max_bits)) atomicMax(norm_max_bits, nb);  // (a wave per row: only where it raises the value)
-    }
-}
-__global__ __launch_bounds__(256) void pq_decode_bf16_kernel(const uint8_t *__restrict__ codes, int64_t n, int m, int k, int sd,
-                                                             const int8_t *__restrict__ codebooks, const float *__restrict__ scales,
-                                                             const float *__restrict__ offsets, uint16_t *__restrict__ out, int dim_pad,
-                                                             float *__restrict__ norms, int *__restrict__ norm_max_bits)
-{
-    pq_decode_row<true>(codes, n, m, k, sd, codebooks, scales, offsets, out, dim_pad, norms, norm_max_bits);
-}
-__global__ __launch_bounds__(256) void pq_norms_kernel(const uint8_t *__restrict__ codes, int64_t n, int m, int k, int sd,
-                                                       const int8_t *__restrict__ codebooks, const float *__restrict__ scales,
-                                                       const float *__restrict__ offsets, float *__restrict__ norms, int *__restrict__ norm_max_bits)
-{
-    pq_decode_row<false>(codes, n, m, k, sd, codebooks, scales, offsets, nullptr, 0, norms, norm_max_bits);
-}
-// The decoded codebook of the nomination from the codes (PqCodesNom::cb16; K = 256, sub-dimension 8): thread per entry (j, c) of
-// `blocks` sub-quantizers, its 8 values decoded and rounded as pq_decode_row rounds them — 16 bytes, what the image of the decoded
-// rows holds at granule j of every row with code c there; the blocks from m on are zeros, the image's padding
-__global__ void pq_codebook_bf16_kernel(const int8_t *__restrict__ codebooks, const float *__restrict__ scales, const float *__restrict__ offsets,
-                                        int m, int blocks, uint4 *__restrict__ cb16)
-{
-    const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= blocks * 256) return;
-    const int j = t >> 8;
-    uint32_t w[4] = {0u, 0u, 0u, 0u};
-    if (j < m) {
-        const int8_t *cb = codebooks + static_cast<int64_t>(t) * 8;
-        const float sc = scales[j], of = offsets[j];
-#pragma unroll
-        for (int d = 0; d < 8; d++) {
-            float v = static_cast<float>(cb[d]) * sc;
-            v = v + of;
-            const uint32_t b = __float_as_uint(v);
-            w[d >> 1] |= ((b + 0x7FFFu + ((b >> 16) & 1u)) >> 16) << (16 * (d & 1));
-        }
-    }
-    cb16[t] = make_uint4(w[0], w[1], w[2], w[3]);
-}
-
-// pqAdcLookupAvx512 (internal/simd/src/floats_avx512.c:135-167) of one row's code against a query's table in the reference's
-// own layout (m rows of 256): 16 lane sums over the full groups, the _mm512_reduce_add_ps tree, the tail added in order — what
-// pq_adc_scan_kernel computes from its LDS image
-__device__ __forceinline__ float pq_adc_row_score(const float *__restrict__ lut, const uint8_t *__restrict__ code, int m)
-{
-    float s[16];
-#pragma unroll
-    for (int l = 0; l < 16; l++) s[l] = 0.0f;
-    int i = 0;
-    for (; i + 16 <= m; i += 16) {
-        float t[16];
-#pragma unroll
-        for (int l = 0; l < 16; l++) t[l] = lut[(i + l) * 256 + code[i + l]];
-#pragma unroll
-        for (int l = 0; l < 16; l++) s[l] = s[l] + t[l];
-    }
-    float total = reduce16_regs(s);
-    for (; i < m; i++) total = total + lut[i * 256 + code[i]];
-    return total;
-}
-
-// the proof's margin: |s~ + |q|^2 - table sum| for any row.  bfloat16 rounding of q and x^: (2^-7 + 2^-16)(|q|^2 + |x^|^2); the GEMM's
-// fp32 accumulation and the norm's: 2 dim u of the same; the table's entries ((sd + 2) u each, relative) and their 16-lane sum
-// ((m / 16 + 4 + 15) u): 2 (m + sd + 6) u of the same (|q - x^|^2 <= 2 (|q|^2 + |x^|^2)).
-__device__ __forceinline__ float pq_nominate_eps(int dim, int m, int sd, float qn, float norm_max)
-{
-    return ((4.0f * static_cast<float>(dim) + 2.0f * static_cast<float>(m + sd + 6)) * 5.9604645e-8f + 0.0078125f * 1.02f) * (qn + norm_max) + 1e-30f;
-}
-
-// the verify pair's Row (vg_nominate.hpp): the table sum of a nominated row from the codes against query q's table
-struct PqTableRow {
-    const uint8_t *codes;  // n * m, row-major
-    const float *tables;   // per query: m rows of 256
-    int m, sd, dim;        // dim = m * sd
-    __device__ float score(int64_t q, const float *, uint32_t id) const
-    {
-        return pq_adc_row_score(tables + q * m * 256, codes + static_cast<int64_t>(id) * m, m);
-    }
-    __device__ float eps(float qn, float norm_max) const { return pq_nominate_eps(dim, m, sd, qn, norm_max); }
-};
-
-// whether a batch takes the nomination (device queries; ascending table sums over the whole segment, no row filter)
-static bool pq_nomination_applies(const vg_index *idx, const float *d_queries, int64_t nq, int k, const uint8_t *mask, bool desc)
-{
-    return idx->pq_nom.rows && !mask && !desc && (nq * idx->n >= kPqNomMinPairs || hook(kHookPqNomAlways)) && k <= kNomMaxK && idx->n > k && idx->pq->k == 256 &&
-           aligned16(d_queries);
-}
-// The same for the nomination from the codes (vg_index_enable_pq_nomination_from_codes): more than 128 queries — the persistent
-// tile's batches; the gathered fill has no 128-row form — and its own crossover against the scan (tools/pq_nominate_codes_time.py,
-// ms scanned / from the codes, k = 10 and k = 100): 129 queries x 100k rows 0.31 / 0.24 and 0.53 / 0.32, x 300k 0.71 / 0.31, x 1M
-// 2.0 / 0.56; 1024 x 1M 12.5 / 1.68, 1024 x 10M 118 / 14.8 — it won at every batch measured, the smallest 12.9M pairs.
-constexpr int64_t kPqCodesNomMinPairs = 13000000;
-static bool pq_codes_nomination_applies(const vg_index *idx, const float *d_queries, int64_t nq, int k, const uint8_t *mask, bool desc)
-{
-    return idx->pq_cnom.cb16 && !mask && !desc && nq > 128 && (nq * idx->n >= kPqCodesNomMinPairs || hook(kHookPqNomAlways)) && k <= kNomMaxK &&
-           idx->n > k && idx->pq->k == 256 && aligned16(d_queries);
-}
-}  // namespace vg
-
-VG_API int32_t vg_index_enable_pq_nomination(vg_index *idx, int32_t on, void *stream)
-{
-    VG_CHECK(idx, VG_ERR_INVALID_ARG, "vg_index_enable_pq_nomination: NULL index");
-    VG_HIP(hipSetDevice(idx->ctx->device));
-    hipStream_t st = vg::pick_stream(idx->ctx, stream);
-    VG_TRY(vg::nom_free(idx->pq_nom, st));
-    if (!on) return VG_OK;
-    VG_CHECK(idx->pq && idx->d_pq_rows, VG_ERR_NOT_READY, "vg_index_enable_pq_nomination: index has no PQ codes");
-    const vg_pq *pq = idx->pq;
-    VG_CHECK(pq->trained, VG_ERR_NOT_TRAINED, "ProductQuantizer not trained");
-    VG_CHECK(pq->k == 256, VG_ERR_UNSUPPORTED, "vg_index_enable_pq_nomination: needs numCentroids == 256 (got %d), as the table scan does", pq->k);
-    VG_TRY(vg::nom_free(idx->pq_cnom, st));  // (the two modes are exclusive)
-    return vg::nom_build(idx->pq_nom, idx->n, idx->dim, st, [&](const vg::NomImage &b, int *norm_max_bits) {
-        hipLaunchKernelGGL(vg::pq_decode_bf16_kernel, dim3(static_cast<unsigned>((idx->n + 3) / 4)), dim3(256), 0, st, idx->d_pq_rows, idx->n,
-                           pq->m, pq->k, pq->subdim, pq->d_codebooks, pq->d_scales, pq->d_offsets, b.rows, b.dim_pad, b.norms, norm_max_bits);
-    });
-}
-
-VG_API int32_t vg_index_enable_pq_nomination_from_codes(vg_index *idx, int32_t on, void *stream)
-{
-    VG_CHECK(idx, VG_ERR_INVALID_ARG, "vg_index_enable_pq_nomination_from_codes: NULL index");
-    VG_HIP(hipSetDevice(idx->ctx->device));
-    hipStream_t st = vg::pick_stream(idx->ctx, stream);
-    VG_TRY(vg::nom_free(idx->pq_cnom, st));
-    if (!on) return VG_OK;
-    VG_CHECK(idx->pq && idx->d_pq_rows, VG_ERR_NOT_READY, "vg_index_enable_pq_nomination_from_codes: index has no PQ codes");
-    const vg_pq *pq = idx->pq;
-    VG_CHECK(pq->trained, VG_ERR_NOT_TRAINED, "ProductQuantizer not trained");
-    VG_CHECK(pq->k == 256, VG_ERR_UNSUPPORTED, "vg_index_enable_pq_nomination_from_codes: needs numCentroids == 256 (got %d), as the table scan does",
-             pq->k);
-    VG_CHECK(pq->subdim == 8, VG_ERR_UNSUPPORTED,
-             "vg_index_enable_pq_nomination_from_codes: needs sub-vectors of 8 dimensions (got %d): a 16-byte granule of a row is one centroid",
-             pq->subdim);
-    VG_TRY(vg::nom_free(idx->pq_nom, st));  // (the two modes are exclusive)
-    // built aside and published together, as nom_build publishes an image
-    vg::PqCodesNom b;
-    b.dim_pad = (idx->dim + 63) & ~63;
-    const int blocks = b.dim_pad / 8;
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(&b.cb16), static_cast<size_t>(blocks) * 256 * 16);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&b.norms), static_cast<size_t>(idx->n) * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&b.norm_max), sizeof(float));
-    if (e == hipSuccess) e = hipMemsetAsync(b.norm_max, 0, sizeof(float), st);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(vg::pq_codebook_bf16_kernel, dim3(static_cast<unsigned>(blocks)), dim3(256), 0, st, pq->d_codebooks, pq->d_scales,
-                           pq->d_offsets, pq->m, blocks, reinterpret_cast<uint4 *>(b.cb16));
-        hipLaunchKernelGGL(vg::pq_norms_kernel, dim3(static_cast<unsigned>((idx->n + 3) / 4)), dim3(256), 0, st, idx->d_pq_rows, idx->n, pq->m, pq->k,
-                           pq->subdim, pq->d_codebooks, pq->d_scales, pq->d_offsets, b.norms, reinterpret_cast<int *>(b.norm_max));
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) {
-        (void)hipFree(b.cb16);
-        (void)hipFree(b.norms);
-        (void)hipFree(b.norm_max);
-        VG_HIP(e);
-    }
-    idx->pq_cnom = b;
-    return VG_OK;
-}
-
-VG_API int32_t vg_index_pq_nomination_info(const vg_index *idx, int32_t *mode, int64_t *held_bytes)
-{
-    VG_CHECK(idx, VG_ERR_INVALID_ARG, "vg_index_pq_nomination_info: NULL index");
-    const int32_t md = idx->pq_nom.rows ? 1 : idx->pq_cnom.cb16 ? 2 : 0;
-    if (mode) *mode = md;
-    if (held_bytes)
-        *held_bytes = md == 1   ? idx->n * (static_cast<int64_t>(idx->pq_nom.dim_pad) * 2 + 4) + 4  // the image, the norms, norm_max
-                      : md == 2 ? idx->pq_cnom.held_bytes(idx->n)
-                                : 0;
     return VG_OK;
 }
 
@@ -1424,27 +930,9 @@ static int32_t pq_adc_search_impl(vg_index *idx, const float *queries, int64_t n
 
     if (idx->n == 0) {
         VG_TRY(vg::empty_results(nq, k, false, oid, osc, st));
-    } else if (allow_nomination && (vg::pq_nomination_applies(idx, q, nq, k, mask, desc) || vg::pq_codes_nomination_applies(idx, q, nq, k, mask, desc))) {
-        const bool from_codes = !idx->pq_nom.rows;  // (the modes are exclusive)
-        const float *const norm_max = from_codes ? idx->pq_cnom.norm_max : idx->pq_nom.norm_max;
+    } else if (allow_nomination && vg::pq_nomination_applies(idx, q, nq, k, mask, desc)) {
         std::vector<int> failed;
-        // per pass: the queries' tables (BuildDistanceTable, the reference's layout), then the table sums of the nominees
-        auto verify = [&](const float *qq, int64_t cnt, const vg::ProbeNominated &nom, float *tables, uint32_t *pid, float *psc,
-                          int *fail) -> int32_t {
-            VG_TRY(vg::launch_pq_build_table(pq, qq, cnt, tables, false, st));
-            return vg::launch_nominated_verify<false>(vg::PqTableRow{idx->d_pq_rows, tables, pq->m, pq->subdim, idx->dim}, qq,
-                                                      norm_max, cnt, nom, k, pid, psc, fail, st);
-        };
-        if (from_codes)  // the GEMM's operands are the image's, bit for bit: the same margin (pq_nominate_eps) holds
-            VG_TRY(vg::nominated_pass_by(
-                idx, [&](int64_t cnt) { return vg::flat_nominate_pq_codes_scratch(cnt, idx->n, idx->pq_cnom.dim_pad, k); },
-                [&](const float *qq, int64_t, int64_t cnt, char *scratch, vg::ProbeNominated *nom) {
-                    return vg::flat_nominate_pq_codes(idx, idx->pq_cnom, qq, cnt, k, scratch, st, nom);
-                },
-                q, nq, k, static_cast<size_t>(pq->m) * 256, oid, osc, st, failed, verify));
-        else
-            VG_TRY(vg::nominated_pass(idx, idx->pq_nom, false, q, nq, k, nullptr, 0, static_cast<size_t>(pq->m) * 256, oid, osc,
-                                      st, failed, verify));
+        VG_TRY(vg::pq_nominated_pass(idx, q, nq, k, oid, osc, st, failed));
         // the table scan for the queries whose proof failed (ties at the k-th score, thresholds too tight)
         VG_TRY(vg::rescan_failed(failed, q, idx->dim, k, nullptr, 0, 0, oid, osc, st,
                                  [&](const float *fq, int64_t nf, const uint8_t *, int64_t, uint32_t *fid, float *fsc) {

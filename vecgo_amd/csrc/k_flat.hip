@@ -73,7 +73,7 @@ struct GemmArgs {
     // with `split`, not `screen`: the retry behind a screen.  Bit tm of the word = query tile tm holds a query to retry; the others
     // are not multiplied.  flat_retry_prepare_kernel has written it and zeroed the counters of the queries to retry.
     const uint32_t *tile_active = nullptr;
-    // MODE 2: the code-gathered tile (flat_gemm_codes_big_kernel) — c.ops.b is the decoded PQ codebook (PqCodesNom::cb16), `codes` the
+    // MODE 2: the code-gathered tile (flat_gemm_codes_big_kernel) — c.ops.b is the decoded PQ codebook (NomImage::rows of a from_codes state), `codes` the
     // n rows' code bytes, code_m a row
     const uint8_t *codes = nullptr;
     int code_m = 0;
@@ -1483,43 +1483,11 @@ int32_t flat_probe_gemm(vg_index *idx, const float *pair_queries, int64_t pairs,
 // batch (stride 0) — rejected rows are left out of the sample and of the candidates, as in flat_search_masked.
 // *nom (all of it in `scratch`): nominate_sel_k(k) thresholds per query (the last is the query's: ~64 * sel_k rows pass it), the
 // counts, every appended key, and — k <= kNomPickMaxK — the 64 best appended rows, ascending.
-struct NominateScratch : NomScratch {
-    uint16_t *qbf;  // the queries, padded like the image's rows
-    int *counts_wide;
-    NominateScratch(char *base, int64_t cnt, int64_t n, int dim_pad, int k)
-    {
-        Carve c{base};
-        carve(c, cnt, sample_cols(n, kFlatSampleStride), nominate_sel_k(k), kFlatCap);
-        c.take(qbf, cnt * dim_pad);
-        c.take(counts_wide, cnt * kCountLine);
-        bytes = c.off;
-    }
-};
-size_t flat_nominate_bf16_scratch(int64_t cnt, int64_t n, int dim_pad, int k) { return NominateScratch(nullptr, cnt, n, dim_pad, k).bytes; }
-
-int32_t flat_nominate_bf16(vg_index *idx, const NomImage &img, bool dot, const float *queries, int64_t cnt, const uint8_t *mask,
-                           int64_t mask_stride, int k, char *scratch, hipStream_t st, ProbeNominated *nom)
-{
-    const NominateScratch s(scratch, cnt, idx->n, img.dim_pad, k);
-    NomCall nc{st, dot, {}, cnt, mask, mask_stride};
-    VG_TRY(gemm_operands(queries, cnt, idx->dim, idx->n, img.norms, img.rows, img.dim_pad, s.qbf, st, &nc.ops));
-    *nom = s.nom;
-    VG_TRY(sample_thresholds(nc, s, kFlatSampleStride, nom->sel_k, nom->thr, idx->n > kFlatCap));
-    VG_LAUNCH(flat_thr_cap_kernel, dim3(nc.ucnt()), dim3(64), 0, st, nom->thr, nom->sel_k, queries, idx->dim, img.norm_max);
-    VG_HIP(hipMemsetAsync(nom->counts, 0, sizeof(int) * static_cast<size_t>(cnt), st));
-    {
-        ProfScope prof(idx->ctx, "sq8_nominate_gemm", st);
-        VG_TRY(launch_gemm<2>(GemmArgs::append(nc, nom->thr, nom->sel_k, nom->counts, nom->cand, nom->cap).wide(s.counts_wide, idx->ctx->compute_units)));
-    }
-    return k <= kNomPickMaxK ? launch_flat_pick(*nom, cnt, nullptr, st) : VG_OK;
-}
-
-// ---- the PQ nomination from the codes -----------------------------------------------------------------------------------------
-// flat_nominate_bf16 without the image of the decoded rows (vg_index_enable_pq_nomination_from_codes, k_adc.hip): the append GEMM
-// gathers its row tiles from the decoded codebook by the codes (flat_gemm_codes_big_kernel); the threshold sample needs decoded rows
-// for every 64th 128-row tile only — those are decoded into the CALL's scratch (rows / 64 of the image: 1.6 % of it), their norms
-// gathered beside them, and the sample kernels run over that compact image with tile stride 1: the same kernels on the same
-// operands as the image's sample, so the same thresholds.
+// The PQ nomination from the codes (img.from_codes: vg_index_enable_pq_nomination_from_codes, k_pq_nominate.hip; L2, unfiltered) has no
+// image of the decoded rows: the append GEMM gathers its row tiles from the decoded codebook by the codes
+// (flat_gemm_codes_big_kernel); the threshold sample needs decoded rows for every 64th 128-row tile only — those are decoded into
+// the CALL's scratch (rows / 64 of the image: 1.6 % of it), their norms gathered beside them, and the sample kernels run over that
+// compact image with tile stride 1: the same kernels on the same operands as the image's sample, so the same thresholds.
 // thread per (compact row, granule): compact row c = sampled tile c / 128, its row c % 128
 __global__ void pq_sample_rows_kernel(const uint8_t *__restrict__ codes, int64_t n, int m, const uint4 *__restrict__ cb16, int granules,
                                       const float *__restrict__ norms, int64_t rows_c, int stride, uint4 *__restrict__ out,
@@ -1541,45 +1509,50 @@ static int64_t sample_rows(int64_t n, int stride)
     const int64_t last0 = (nts - 1) * stride * kGemmBN;
     return (nts - 1) * kGemmBN + std::min<int64_t>(kGemmBN, n - last0);
 }
-struct PqCodesScratch : NominateScratch {
-    uint16_t *srows;  // the sampled tiles' decoded rows, dim_pad each
-    float *snorms;
-    PqCodesScratch(char *base, int64_t cnt, int64_t n, int dim_pad, int k) : NominateScratch(base, cnt, n, dim_pad, k)
+struct NominateScratch : NomScratch {
+    uint16_t *qbf;  // the queries, padded like the image's rows
+    int *counts_wide;
+    int64_t rows_c;   // from the codes: the sampled tiles' rows (0: an image, or too few rows for a sample) ...
+    uint16_t *srows;  // ... decoded, dim_pad each ...
+    float *snorms;    // ... and their norms
+    NominateScratch(char *base, int64_t cnt, int64_t n, const NomImage &img, int k)
     {
-        Carve c{base, bytes};
-        const int64_t rows_c = n > kFlatCap ? sample_rows(n, kFlatSampleStride) : 0;
-        c.take(srows, rows_c * dim_pad);
+        Carve c{base};
+        carve(c, cnt, sample_cols(n, kFlatSampleStride), nominate_sel_k(k), kFlatCap);
+        c.take(qbf, cnt * img.dim_pad);
+        c.take(counts_wide, cnt * kCountLine);
+        rows_c = img.from_codes && n > kFlatCap ? sample_rows(n, kFlatSampleStride) : 0;
+        c.take(srows, rows_c * img.dim_pad);
         c.take(snorms, rows_c);
         bytes = c.off;
     }
 };
-size_t flat_nominate_pq_codes_scratch(int64_t cnt, int64_t n, int dim_pad, int k) { return PqCodesScratch(nullptr, cnt, n, dim_pad, k).bytes; }
+size_t flat_nominate_bf16_scratch(int64_t cnt, int64_t n, const NomImage &img, int k) { return NominateScratch(nullptr, cnt, n, img, k).bytes; }
 
-int32_t flat_nominate_pq_codes(vg_index *idx, const PqCodesNom &cn, const float *queries, int64_t cnt, int k, char *scratch, hipStream_t st,
-                               ProbeNominated *nom)
+int32_t flat_nominate_bf16(vg_index *idx, const NomImage &img, bool dot, const float *queries, int64_t cnt, const uint8_t *mask,
+                           int64_t mask_stride, int k, char *scratch, hipStream_t st, ProbeNominated *nom)
 {
-    const PqCodesScratch s(scratch, cnt, idx->n, cn.dim_pad, k);
-    const int m = idx->pq->m, granules = cn.dim_pad / 8;
-    NomCall nc{st, false, {}, cnt, nullptr, 0};
-    // (the GEMM's "rows" are the codebook; n, the row length and the norms are the decoded rows')
-    VG_TRY(gemm_operands(queries, cnt, idx->dim, idx->n, cn.norms, cn.cb16, cn.dim_pad, s.qbf, st, &nc.ops));
+    const NominateScratch s(scratch, cnt, idx->n, img, k);
+    NomCall nc{st, dot, {}, cnt, mask, mask_stride};
+    // (from the codes the GEMM's "rows" are the codebook; n, the row length and the norms are the decoded rows')
+    VG_TRY(gemm_operands(queries, cnt, idx->dim, idx->n, img.norms, img.rows, img.dim_pad, s.qbf, st, &nc.ops));
     *nom = s.nom;
-    const bool sampled = idx->n > kFlatCap;
-    NomCall sc = nc;
-    if (sampled) {
-        const int64_t rows_c = sample_rows(idx->n, kFlatSampleStride);
-        VG_LAUNCH(pq_sample_rows_kernel, dim3(static_cast<unsigned>((rows_c * granules + 255) / 256)), dim3(256), 0, st, idx->d_pq_rows, idx->n, m,
-                  reinterpret_cast<const uint4 *>(cn.cb16), granules, cn.norms, rows_c, kFlatSampleStride, reinterpret_cast<uint4 *>(s.srows), s.snorms);
-        sc.ops.b = reinterpret_cast<const float *>(s.srows), sc.ops.n = rows_c, sc.ops.norms = s.snorms;
+    NomCall sc = nc;  // the sample's operands: the image's, or the sampled tiles decoded here
+    if (s.rows_c) {
+        const int granules = img.dim_pad / 8;
+        VG_LAUNCH(pq_sample_rows_kernel, dim3(static_cast<unsigned>((s.rows_c * granules + 255) / 256)), dim3(256), 0, st, idx->d_pq_rows, idx->n,
+                  idx->pq->m, reinterpret_cast<const uint4 *>(img.rows), granules, img.norms, s.rows_c, kFlatSampleStride,
+                  reinterpret_cast<uint4 *>(s.srows), s.snorms);
+        sc.ops.b = reinterpret_cast<const float *>(s.srows), sc.ops.n = s.rows_c, sc.ops.norms = s.snorms;
     }
-    VG_TRY(sample_thresholds(sc, s, 1, nom->sel_k, nom->thr, sampled));
-    VG_LAUNCH(flat_thr_cap_kernel, dim3(nc.ucnt()), dim3(64), 0, st, nom->thr, nom->sel_k, queries, idx->dim, cn.norm_max);
+    VG_TRY(sample_thresholds(sc, s, s.rows_c ? 1 : kFlatSampleStride, nom->sel_k, nom->thr, idx->n > kFlatCap));
+    VG_LAUNCH(flat_thr_cap_kernel, dim3(nc.ucnt()), dim3(64), 0, st, nom->thr, nom->sel_k, queries, idx->dim, img.norm_max);
     VG_HIP(hipMemsetAsync(nom->counts, 0, sizeof(int) * static_cast<size_t>(cnt), st));
     {
-        ProfScope prof(idx->ctx, "pq_codes_gemm", st);
-        VG_TRY(launch_gemm<2>(GemmArgs::append(nc, nom->thr, nom->sel_k, nom->counts, nom->cand, nom->cap)
-                                  .wide(s.counts_wide, idx->ctx->compute_units)
-                                  .from_codes(idx->d_pq_rows, m)));
+        ProfScope prof(idx->ctx, img.from_codes ? "pq_codes_gemm" : "sq8_nominate_gemm", st);
+        GemmArgs a = GemmArgs::append(nc, nom->thr, nom->sel_k, nom->counts, nom->cand, nom->cap).wide(s.counts_wide, idx->ctx->compute_units);
+        if (img.from_codes) a.from_codes(idx->d_pq_rows, idx->pq->m);
+        VG_TRY(launch_gemm<2>(a));
     }
     return k <= kNomPickMaxK ? launch_flat_pick(*nom, cnt, nullptr, st) : VG_OK;
 }

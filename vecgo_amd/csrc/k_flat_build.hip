@@ -411,7 +411,7 @@ VG_API int32_t vg_flat_build(vg_index *idx, int32_t num_partitions, int32_t quan
     VG_CHECK(!idx->d_pq_tiles && !idx->d_pq_rows && !idx->d_sq_tiles && !idx->d_rq_rows && !idx->d_rq_tiles && !idx->d_int4_rows,
              VG_ERR_UNSUPPORTED, "vg_flat_build: the index holds codes already: the writer quantizes the reordered rows itself");
     VG_CHECK(!idx->d_centroids && idx->num_partitions == 0, VG_ERR_UNSUPPORTED, "vg_flat_build: the index is partitioned already");
-    VG_CHECK(!idx->pq_nom.rows && !idx->pq_cnom.cb16 && !idx->sq_nom.rows, VG_ERR_UNSUPPORTED, "vg_flat_build: the index holds a nomination image");
+    VG_CHECK(!idx->pq_nom.rows && !idx->sq_nom.rows, VG_ERR_UNSUPPORTED, "vg_flat_build: the index holds a nomination image");
     VG_CHECK(quantization == VG_QUANT_NONE || quantization == VG_QUANT_SQ8 || quantization == VG_QUANT_PQ, VG_ERR_INVALID_ARG,
              "vg_flat_build: quantization %d is none of VG_QUANT_NONE / _SQ8 / _PQ (format.go:22-26)", quantization);
     VG_CHECK(kmeans_iters >= 0 && pq_iters >= 0 && pq_m >= 0, VG_ERR_INVALID_ARG, "vg_flat_build: negative iteration count or pq_m");

@@ -546,7 +546,7 @@ VG_API int32_t vg_index_enable_sq8_nomination(vg_index *idx, int32_t on, void *s
     VG_TRY(vg::nom_free(idx->sq_nom, st));
     if (!on) return VG_OK;
     VG_CHECK(idx->sq && idx->d_sq_tiles, VG_ERR_NOT_READY, "vg_index_enable_sq8_nomination: index has no SQ8 codes");
-    return vg::nom_build(idx->sq_nom, idx->n, idx->dim, st, [&](const vg::NomImage &b, int *norm_max_bits) {
+    return vg::nom_build(idx->sq_nom, idx->n, idx->dim, vg::NomImage::body_bytes(idx->n, vg::nom_dim_pad(idx->dim), false), false, st, [&](const vg::NomImage &b, int *norm_max_bits) {
         hipLaunchKernelGGL(vg::sq8_dequant_bf16_kernel, dim3(static_cast<unsigned>(idx->n_tiles)), dim3(64), 0, st,
                            reinterpret_cast<const uint4 *>(idx->d_sq_tiles), idx->n, idx->dim, idx->sq_groups, idx->sq->d_mins, idx->sq->d_inv,
                            b.rows, b.dim_pad, b.norms, norm_max_bits);

@@ -334,8 +334,7 @@ VG_API int32_t vg_vamana_reorder_bfs(vg_index *idx, uint32_t *perm, uint32_t *in
     need(idx->d_vectors, n * idx->dim * 4);
     need(idx->d_vectors_bf16, n * bf16_bytes);
     need(idx->d_pq_rows, n * pq_m);
-    need(idx->pq_nom.rows, n * idx->pq_nom.dim_pad * 2);
-    need(idx->pq_cnom.norms, n * 4);
+    need(idx->pq_nom.row_image(), n * idx->pq_nom.dim_pad * 2);
     need(idx->d_rq_rows, n * (rq_nb + 4));
     need(idx->d_sq_tiles, idx->n_tiles * idx->sq_groups * 64 * 16);
     need(idx->sq_nom.rows, n * idx->sq_nom.dim_pad * 2);
@@ -403,9 +402,9 @@ VG_API int32_t vg_vamana_reorder_bfs(vg_index *idx, uint32_t *perm, uint32_t *in
             if (idx->d_pq_tiles)
                 VG_TRY(vg::launch_pq_retile(idx->d_pq_rows, n, idx->pq->m, idx->pq_groups, (n + 63) / 64, idx->d_pq_tiles, st));
         }
-        VG_TRY(vg::rb_permute_rows(idx->pq_nom.rows, n, static_cast<int64_t>(idx->pq_nom.dim_pad) * 2, p, scratch, st));
+        // (from the codes: no row image; its sample tiles are decoded per call)
+        VG_TRY(vg::rb_permute_rows(idx->pq_nom.row_image(), n, static_cast<int64_t>(idx->pq_nom.dim_pad) * 2, p, scratch, st));
         VG_TRY(vg::rb_permute_rows(idx->pq_nom.norms, n, 4, p, scratch, st));
-        VG_TRY(vg::rb_permute_rows(idx->pq_cnom.norms, n, 4, p, scratch, st));  // (from the codes: no row image; its sample tiles are decoded per call)
         // RaBitQ: rows, then tiles and norms[0, n) rebuilt from them (norms[n], the largest |norm|, does not move)
         if (idx->d_rq_rows) {
             VG_TRY(vg::rb_permute_rows(idx->d_rq_rows, n, rq_nb + 4, p, scratch, st));

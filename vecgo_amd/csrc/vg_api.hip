@@ -308,7 +308,6 @@ VG_API int32_t vg_index_destroy(vg_index *idx)
     if (idx->d_sq_tiles) (void)hipFree(idx->d_sq_tiles);
     (void)vg::nom_free(idx->sq_nom, idx->ctx->stream);
     (void)vg::nom_free(idx->pq_nom, idx->ctx->stream);
-    (void)vg::nom_free(idx->pq_cnom, idx->ctx->stream);
     if (idx->d_int4_rows) (void)hipFree(idx->d_int4_rows);
     if (idx->d_centroids) (void)hipFree(idx->d_centroids);
     if (idx->d_part_off) (void)hipFree(idx->d_part_off);

@@ -463,11 +463,21 @@ struct ProbeNominated {
 constexpr int kProbeGemmMaxK = 160;  // deepest threshold: the 60th best of the 1/8 row sample, ~480 rows pass it
 // A bfloat16 row image the matrix-core nomination runs on (vg_nominate.hpp): a quantizer's DECODED rows rounded to bfloat16
 // (vg_index_enable_sq8_nomination, vg_index_enable_pq_nomination; all null when off), or a view of the fp32 rows' bf16 filter.
+// The PQ nomination FROM THE CODES (vg_index_enable_pq_nomination_from_codes, k_pq_nominate.hip) keeps no decoded-row image: the
+// nomination GEMM's row tile is gathered from a bfloat16 copy of the decoded codebook, granule by granule (sub-dimension 8: a
+// 16-byte granule of a decoded row IS one centroid).  Its state is the same object with that codebook in the rows' place
+// (from_codes), so an index holds one PQ nomination or the other, never both.
 struct NomImage {
-    uint16_t *rows = nullptr;  // n * dim_pad
+    uint16_t *rows = nullptr;  // n * dim_pad; from_codes: [dim_pad / 8][256][8], entry (j, c) = centroid c of sub-quantizer j decoded and rounded; j >= m: zeros
     int32_t dim_pad = 0;       // the row length: dim padded with zeros to whole 64-element K steps of the bf16 GEMM
     float *norms = nullptr;    // n: |x^|^2 (fp32 of the unrounded values)
     float *norm_max = nullptr; // [1]: the largest of them
+    bool from_codes = false;   // `rows` is the decoded codebook, not the decoded rows
+    // what vg_index_pq_nomination_info reports: 0 off, 1 the image of the decoded rows, 2 from the codes
+    int mode() const { return !rows ? 0 : from_codes ? 2 : 1; }
+    uint16_t *row_image() const { return from_codes ? nullptr : rows; }  // the decoded rows, where the mode keeps them
+    static int64_t body_bytes(int64_t n, int dim_pad, bool from_codes) { return (from_codes ? int64_t(dim_pad / 8) * 256 * 8 : n * dim_pad) * 2; }
+    int64_t held_bytes(int64_t n) const { return rows ? body_bytes(n, dim_pad, from_codes) + n * 4 + 4 : 0; }  // the body, the norms, norm_max
 };
 // Frees an image (after the stream's work that may read it) and leaves it empty.
 inline int32_t nom_free(NomImage &img, hipStream_t st)
@@ -478,26 +488,6 @@ inline int32_t nom_free(NomImage &img, hipStream_t st)
     VG_HIP(hipFree(img.norms));
     VG_HIP(hipFree(img.norm_max));
     img = NomImage{};
-    return VG_OK;
-}
-// The PQ nomination FROM THE CODES (vg_index_enable_pq_nomination_from_codes, k_adc.hip; all null when off): no decoded-row image —
-// the nomination GEMM's row tile is gathered from a bfloat16 copy of the decoded codebook, granule by granule (sub-dimension 8: a
-// 16-byte granule of a decoded row IS one centroid).  Resident: that codebook, the rows' norms and their largest.
-struct PqCodesNom {
-    uint16_t *cb16 = nullptr;   // [dim_pad / 8][256][8] bfloat16: entry (j, c) = centroid c of sub-quantizer j decoded and rounded; j >= m: zeros
-    int32_t dim_pad = 0;        // dim padded to whole 64-element K steps, as NomImage's
-    float *norms = nullptr;     // n: |x^|^2, as NomImage's
-    float *norm_max = nullptr;  // [1]
-    int64_t held_bytes(int64_t n) const { return cb16 ? static_cast<int64_t>(dim_pad / 8) * 256 * 16 + n * 4 + 4 : 0; }
-};
-inline int32_t nom_free(PqCodesNom &cn, hipStream_t st)
-{
-    if (!cn.cb16) return VG_OK;
-    VG_HIP(hipStreamSynchronize(st));
-    VG_HIP(hipFree(cn.cb16));
-    VG_HIP(hipFree(cn.norms));
-    VG_HIP(hipFree(cn.norm_max));
-    cn = PqCodesNom{};
     return VG_OK;
 }
 }  // namespace vg
@@ -545,8 +535,7 @@ struct vg_index {
     uint32_t vamana_entry = 0;
     // PQ codes in the reference's row-major layout (random access by node id in graph search)
     uint8_t *d_pq_rows = nullptr;
-    vg::NomImage pq_nom;               // vg_index_enable_pq_nomination: the DECODED rows (pq.go:185-229)
-    vg::PqCodesNom pq_cnom;            // vg_index_enable_pq_nomination_from_codes: the decoded CODEBOOK and the rows' norms
+    vg::NomImage pq_nom;               // vg_index_enable_pq_nomination: the DECODED rows (pq.go:185-229); _from_codes: the decoded CODEBOOK
     uint8_t *d_rq_rows = nullptr;
     // SQ8 codes, re-tiled like the PQ codes: [tile][group of 16 dims][lane][16 B]; see k_sq8_scan.hip
     vg_sq8 *sq = nullptr;
@@ -567,6 +556,8 @@ struct vg_index {
 namespace vg {
 // What a segment's index holds besides fp32 rows and an HNSW graph, or null: rows appended or lists rewritten by a
 // memtable's entry point (vg_hnsw_insert, vg_hnsw_compact) would leave it behind
+// (a PQ nomination, pq_nom, has no arm: it exists only beside d_pq_rows — both enable functions want the codes, and
+// vg_index_set_pq_codes frees it before it replaces them — so "PQ codes" answers for it)
 inline const char *held_segment_state(const vg_index *idx)
 {
     return (idx->d_pq_tiles || idx->d_pq_rows)   ? "PQ codes"
@@ -576,8 +567,6 @@ inline const char *held_segment_state(const vg_index *idx)
            : idx->d_centroids                    ? "IVF partitions"
            : idx->d_vamana                       ? "a Vamana graph"
            : idx->sq_nom.rows                    ? "an SQ8 nomination image"
-           : idx->pq_nom.rows                    ? "a PQ nomination image"
-           : idx->pq_cnom.cb16                   ? "a PQ nomination from the codes"
                                                  : nullptr;
 }
 // The same for the streaming Vamana insert (vg_vamana_insert): what its new rows would lack, or null
@@ -591,8 +580,6 @@ inline const char *held_fresh_state(const vg_index *idx)
            : idx->d_hnsw_l0                      ? "an HNSW graph"
            : idx->d_hnsw_tomb                    ? "HNSW tombstones"
            : idx->sq_nom.rows                    ? "an SQ8 nomination image"
-           : idx->pq_nom.rows                    ? "a PQ nomination image"
-           : idx->pq_cnom.cb16                   ? "a PQ nomination from the codes"
                                                  : nullptr;
 }
 }  // namespace vg

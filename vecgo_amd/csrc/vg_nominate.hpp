@@ -1,5 +1,5 @@
 // vg_nominate.hpp — the batched search through a bfloat16 nomination image, shared by the quantizers that have one
-// (vg_index_enable_sq8_nomination, k_sq8_scan.hip; vg_index_enable_pq_nomination, k_adc.hip).
+// (vg_index_enable_sq8_nomination, k_sq8_scan.hip; vg_index_enable_pq_nomination and _from_codes, k_pq_nominate.hip).
 // The image holds a quantizer's DECODED rows x^ rounded to bfloat16 with their norms (NomImage, vg_internal.hpp); the fused flat
 // search's nomination runs on it (k_flat.hip flat_nominate_bf16: threshold from a row sample, bf16 MFMA GEMM, the 64 best per
 // query), the verify kernels below re-score the nominees with the reference's own arithmetic on the CODES (the quantizer's Row)
@@ -25,13 +25,10 @@ inline int nominate_sel_k(int k) { return k <= kNomPickMaxK ? 8 : k <= 128 ? 16 
 struct GemmGroup;  // vg_flat_gemm.hpp
 // k_flat.hip
 // cnt queries' nomination for their k best on `img`, *nom and all it points to in `scratch` (flat_nominate_bf16_scratch bytes)
-size_t flat_nominate_bf16_scratch(int64_t cnt, int64_t n, int dim_pad, int k);
+// (img.from_codes, the PQ nomination from the codes: L2, unfiltered)
+size_t flat_nominate_bf16_scratch(int64_t cnt, int64_t n, const NomImage &img, int k);
 int32_t flat_nominate_bf16(vg_index *idx, const NomImage &img, bool dot, const float *queries, int64_t cnt, const uint8_t *mask,
                            int64_t mask_stride, int k, char *scratch, hipStream_t st, ProbeNominated *nom);
-// the same for the PQ nomination from the codes (PqCodesNom, vg_internal.hpp): L2, unfiltered
-size_t flat_nominate_pq_codes_scratch(int64_t cnt, int64_t n, int dim_pad, int k);
-int32_t flat_nominate_pq_codes(vg_index *idx, const PqCodesNom &cn, const float *queries, int64_t cnt, int k, char *scratch, hipStream_t st,
-                               ProbeNominated *nom);
 size_t flat_probe_gemm_scratch_bytes(int64_t pairs, int64_t ns_max, int k, int bf16_dim);
 int32_t flat_probe_gemm(vg_index *idx, const float *pair_queries, int64_t pairs, const GemmGroup *groups, const int64_t *const first_block[4],
                         int ngroups, const int64_t grid[4], int sample_stride, int64_t ns_max, int k, uint32_t *pair_ids,
@@ -43,17 +40,23 @@ int32_t launch_sq8_verify(vg_index *idx, const float *queries, int64_t nq, const
 bool sq8_nomination_applies(const vg_index *idx, const float *d_queries, int64_t nq, int k);
 int32_t sq8_nominated_pass(vg_index *idx, const float *q, int64_t nq, int k, const uint8_t *mask, int64_t mask_stride, uint32_t *oid,
                            float *osc, hipStream_t st, std::vector<int> &failed);
+// k_pq_nominate.hip (ascending table sums over the whole segment: mask null, desc false, or the batch does not apply)
+bool pq_nomination_applies(const vg_index *idx, const float *d_queries, int64_t nq, int k, const uint8_t *mask, bool desc);
+int32_t pq_nominated_pass(vg_index *idx, const float *q, int64_t nq, int k, uint32_t *oid, float *osc, hipStream_t st, std::vector<int> &failed);
 
-// Builds an image of n rows of dim elements into `img` (empty): launch(const NomImage &, int *norm_max_bits) launches the
-// quantizer's build kernel, which writes the rows (the tail from dim on zeros), their norms and atomicMax-es their largest into
-// norm_max (zeroed here).  The three arrays are published together, after the image is built: a failure half way leaves the index
+// Builds the nomination state of n rows of dim elements into `img` (empty): its body of body_bytes (NomImage::body_bytes — the
+// decoded rows, or from_codes the decoded codebook), the norms and norm_max.  launch(const NomImage &, int *norm_max_bits) launches
+// the quantizer's build kernels, which write the body (a row's tail from dim on zeros), the rows' norms and atomicMax their largest
+// into norm_max (zeroed here).  The arrays are published together, after all of it is built: a failure half way leaves the index
 // as it was (the batch searches test `rows` alone — ADVICE r05: a failed second allocation left it set next to null norms).
+inline int nom_dim_pad(int dim) { return (dim + 63) & ~63; }  // whole K steps of the bf16 GEMM; the padding is zeros
 template <class Launch>
-int32_t nom_build(NomImage &img, int64_t n, int dim, hipStream_t st, Launch launch)
+int32_t nom_build(NomImage &img, int64_t n, int dim, int64_t body_bytes, bool from_codes, hipStream_t st, Launch launch)
 {
     NomImage b;
-    b.dim_pad = (dim + 63) & ~63;  // whole K steps of the bf16 GEMM; the padding is zeros
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(&b.rows), static_cast<size_t>(n) * b.dim_pad * sizeof(uint16_t));
+    b.dim_pad = nom_dim_pad(dim);
+    b.from_codes = from_codes;
+    hipError_t e = hipMalloc(reinterpret_cast<void **>(&b.rows), static_cast<size_t>(body_bytes));
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&b.norms), static_cast<size_t>(n) * sizeof(float));
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&b.norm_max), sizeof(float));
     if (e == hipSuccess) e = hipMemsetAsync(b.norm_max, 0, sizeof(float), st);
@@ -200,39 +203,26 @@ inline int32_t failed_list(const int *d_fail, int64_t cnt, int64_t base, hipStre
 // query / for the batch, or null): writes every query's k results and lists the queries whose proof failed — the caller searches
 // those again (rescan_failed).  4096 queries a pass.  verify(queries, cnt, nom, extra, ids, scores, fail) re-scores and proves a
 // pass's nominations; extra: extra_floats per query of the pass's scratch (the PQ distance tables).
-// nominate(queries, q0, cnt, scratch, &nom): a pass's nomination in scratch_bytes(cnt) of scratch.
-template <class ScratchBytes, class Nominate, class Verify>
-int32_t nominated_pass_by(vg_index *idx, ScratchBytes scratch_bytes, Nominate nominate, const float *q, int64_t nq, int k, size_t extra_floats,
-                          uint32_t *oid, float *osc, hipStream_t st, std::vector<int> &failed, Verify verify)
+template <class Verify>
+int32_t nominated_pass(vg_index *idx, const NomImage &img, bool dot, const float *q, int64_t nq, int k, const uint8_t *mask,
+                       int64_t mask_stride, size_t extra_floats, uint32_t *oid, float *osc, hipStream_t st, std::vector<int> &failed,
+                       Verify verify)
 {
     for (int64_t q0 = 0; q0 < nq; q0 += 4096) {
         const int64_t cnt = std::min<int64_t>(4096, nq - q0);
         ArenaCall ar(idx->ctx, st);
-        const int i_scr = ar.add(scratch_bytes(cnt));
+        const int i_scr = ar.add(flat_nominate_bf16_scratch(cnt, idx->n, img, k));
         const int i_fail = ar.add(sizeof(int) * static_cast<size_t>(cnt));
         const int i_extra = ar.add(sizeof(float) * static_cast<size_t>(cnt) * extra_floats);
         VG_TRY(ar.commit());
         int *fail = ar.get<int>(i_fail);
         const float *qq = q + q0 * idx->dim;
         ProbeNominated nom;
-        VG_TRY(nominate(qq, q0, cnt, ar.get<char>(i_scr), &nom));
+        VG_TRY(flat_nominate_bf16(idx, img, dot, qq, cnt, mask ? mask + q0 * mask_stride : nullptr, mask_stride, k, ar.get<char>(i_scr), st, &nom));
         VG_TRY(verify(qq, cnt, nom, ar.get<float>(i_extra), oid + q0 * k, osc + q0 * k, fail));
         VG_TRY(failed_list(fail, cnt, q0, st, failed));
     }
     return VG_OK;
-}
-// on a bfloat16 image of the decoded rows
-template <class Verify>
-int32_t nominated_pass(vg_index *idx, const NomImage &img, bool dot, const float *q, int64_t nq, int k, const uint8_t *mask,
-                       int64_t mask_stride, size_t extra_floats, uint32_t *oid, float *osc, hipStream_t st, std::vector<int> &failed,
-                       Verify verify)
-{
-    return nominated_pass_by(
-        idx, [&](int64_t cnt) { return flat_nominate_bf16_scratch(cnt, idx->n, img.dim_pad, k); },
-        [&](const float *qq, int64_t q0, int64_t cnt, char *scratch, ProbeNominated *nom) {
-            return flat_nominate_bf16(idx, img, dot, qq, cnt, mask ? mask + q0 * mask_stride : nullptr, mask_stride, k, scratch, st, nom);
-        },
-        q, nq, k, extra_floats, oid, osc, st, failed, verify);
 }
 
 // The failed queries of a batch searched again: their queries (and, with a filter per query, their filters of mask_bytes) gathered,

@@ -14,11 +14,18 @@
 
 namespace vg {
 
-// ---- k_adc.hip ------------------------------------------------------------------------------------
+// ---- k_topk_merge.hip -----------------------------------------------------------------------------
+// the merge kernels' workgroup and LDS key buffer (topk_merge_kernel; topk_select_verify_kernel, k_adc.hip), and the largest k they
+// take: vg_search_pq_adc's and vg_merge_topk's limit
+constexpr int kMergeThreads = 256;
+constexpr int kMergeBuf = 4096;
+constexpr int kAdcMaxK = 1024;
 // per query the k best of `lists` k-lists of keys -> ids / scores; only_if[q] == 0 leaves query q alone unless always[0] != 0
 int32_t launch_topk_merge(const uint64_t *partial, int64_t nq, int lists, int k, bool descending,
                           uint32_t *ids, float *scores, hipStream_t st, const int *only_if = nullptr,
                           const int *always = nullptr);
+
+// ---- k_adc.hip ------------------------------------------------------------------------------------
 // row-major PQ codes -> the scan's tiles (vg_vamana_reorder_bfs rebuilds them from its permuted codes)
 int32_t launch_pq_retile(const uint8_t *codes, int64_t n, int m, int groups, int64_t n_tiles, uint8_t *tiles, hipStream_t st);
 // the probed partitions' rows by table lookups, `split` k-lists per query
