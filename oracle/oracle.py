@@ -161,6 +161,23 @@ _sig("vgo_hnsw_build", C.c_int32, _f32p, C.c_int64, C.c_int32, C.c_int32, C.c_in
      C.c_int32, _u32p, _u32p, _u32p, _u32p, _i32p)
 
 
+class HnswBuildLog(C.Structure):
+    _fields_ = [("events", C.c_void_p), ("cap_events", C.c_int64), ("n_events", C.c_int64),
+                ("own", _i32p), ("cap_own", C.c_int64), ("n_own", C.c_int64)]
+
+
+_sig("vgo_hnsw_build_logged", C.c_int32, _f32p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+     C.c_int32, _u32p, _u32p, _u32p, _u32p, _i32p, C.POINTER(HnswBuildLog))
+
+LINK_ALREADY, LINK_APPENDED, LINK_PRUNED = 0, 1, 2
+LINK_TIE_ANY, LINK_TIE_MEMBERS, LINK_FARTHER, LINK_UNCHANGED, LINK_TIE_LAST, LINK_TIE_NEW, LINK_ROW_CHOSEN = 1, 2, 4, 8, 16, 32, 64
+# vgo_hnsw_link_event, one per addConnection call in application order
+LINK_EVENT = np.dtype([("batch", np.int32), ("level", np.int32), ("node", np.uint32), ("new_node", np.uint32),
+                       ("pos", np.int32), ("deg", np.int32), ("outcome", np.int32), ("flags", np.int32)])
+# one per (new node, level): what the insert search returned and how many of them the row kept
+OWN_ROW = np.dtype([("node", np.int32), ("level", np.int32), ("candidates", np.int32), ("kept", np.int32)])
+
+
 def _f(a):
     a = np.ascontiguousarray(a, dtype=np.float32)
     return a, a.ctypes.data_as(_f32p)
@@ -614,9 +631,11 @@ def hnsw_layout(n, m):
     return levels, rows[:top].copy(), top
 
 
-def hnsw_build(base, dim, m=32, ef=300, metric=METRIC_L2, max_batch=1, growth_div=32):
+def hnsw_build(base, dim, m=32, ef=300, metric=METRIC_L2, max_batch=1, growth_div=32, events=False):
     """hnsw insert loop (hnsw.go:713-984) over rows 0..n-1; returns (l0[n,2m], upper, entry_point) with
-    upper = [(slot[n], adj[rows, m]) per level 1..top] — the layout HnswIndex / the C-ABI take."""
+    upper = [(slot[n], adj[rows, m]) per level 1..top] — the layout HnswIndex / the C-ABI take.  events: returns
+    (l0, upper, entry_point, links, own) with links a LINK_EVENT array (one entry per addConnection call, in application
+    order) and own an OWN_ROW array (one per new node and level)."""
     b, pb = _f(base)
     n = b.size // dim
     _, rows, top = hnsw_layout(n, m)
@@ -625,14 +644,25 @@ def hnsw_build(base, dim, m=32, ef=300, metric=METRIC_L2, max_batch=1, growth_di
     adj = np.empty((max(int(rows.sum()), 1), m), np.uint32)
     entry = C.c_uint32(0)
     mx = C.c_int32(0)
-    r = lib.vgo_hnsw_build(pb, n, dim, metric, m, ef, max_batch, growth_div, l0.ctypes.data_as(_u32p),
-                           slots.ctypes.data_as(_u32p), adj.ctypes.data_as(_u32p), C.byref(entry), C.byref(mx))
+    graph_args = (pb, n, dim, metric, m, ef, max_batch, growth_div, l0.ctypes.data_as(_u32p),
+                  slots.ctypes.data_as(_u32p), adj.ctypes.data_as(_u32p), C.byref(entry), C.byref(mx))
+    if events:
+        pairs = n + int(rows.sum())
+        links = np.zeros(2 * m * n + m * int(rows.sum()), LINK_EVENT)  # every own row is at most full
+        own = np.zeros(pairs, OWN_ROW)
+        log = HnswBuildLog(links.ctypes.data, links.size, 0, own.ctypes.data_as(_i32p), own.size, 0)
+        r = lib.vgo_hnsw_build_logged(*graph_args, C.byref(log))
+        assert log.n_events <= links.size and log.n_own <= own.size
+    else:
+        r = lib.vgo_hnsw_build(*graph_args)
     if r != 0:
         raise ValueError("vgo_hnsw_build: bad arguments")
     upper, off = [], 0
     for l in range(top):
         upper.append((slots[l].copy(), adj[off:off + int(rows[l])].copy()))
         off += int(rows[l])
+    if events:
+        return l0, upper, int(entry.value), links[:log.n_events].copy(), own[:log.n_own].copy()
     return l0, upper, int(entry.value)
 
 

@@ -256,6 +256,36 @@ int32_t vgo_hnsw_build(const float *base, int64_t n, int32_t dim, int32_t metric
                        int32_t max_batch, int32_t growth_div, uint32_t *l0, uint32_t *slots, uint32_t *adj,
                        uint32_t *entry_point, int32_t *max_level);
 
+/* What the build's back links did (tests/hnsw_build_seams.py): one vgo_hnsw_link_event per addConnection call, in
+ * application order.  pos = the record's place in its target row's chain within the batch (0-based; records reach a
+ * row in ascending id of the new node).  Equality of cached distances is float ==, what the heap's comparisons see. */
+enum { VGO_LINK_ALREADY = 0, VGO_LINK_APPENDED = 1, VGO_LINK_PRUNED = 2 };
+enum {
+    VGO_LINK_TIE_ANY = 1,       /* pruned: two of the deg + 1 cached distances are equal */
+    VGO_LINK_TIE_MEMBERS = 2,   /* pruned: two members' cached distances are equal */
+    VGO_LINK_FARTHER = 4,       /* pruned: the newcomer is strictly farther than every member */
+    VGO_LINK_UNCHANGED = 8,     /* pruned: the row came out with the same ids in the same slots */
+    VGO_LINK_TIE_LAST = 16,     /* pruned: the newcomer's distance equals the last slot's */
+    VGO_LINK_TIE_NEW = 32,      /* pruned: the newcomer's distance equals some member's */
+    VGO_LINK_ROW_CHOSEN = 64    /* pruned: applyHeuristic chose every member of the row the last time it was
+                                   selected (nothing filled up, nothing appended since): ascending distances */
+};
+typedef struct {
+    int32_t batch, level;
+    uint32_t node, new_node; /* the target row's node; the node being linked back */
+    int32_t pos, deg, outcome, flags;
+} vgo_hnsw_link_event;
+typedef struct {
+    vgo_hnsw_link_event *events; /* cap_events entries */
+    int64_t cap_events, n_events; /* n_events counts every call, stored or not */
+    int32_t *own;                /* cap_own x 4: node, level, candidates the insert search returned, members kept */
+    int64_t cap_own, n_own;
+} vgo_hnsw_build_log;
+/* vgo_hnsw_build with the log filled (log may be NULL): the same graph */
+int32_t vgo_hnsw_build_logged(const float *base, int64_t n, int32_t dim, int32_t metric, int32_t m, int32_t ef,
+                              int32_t max_batch, int32_t growth_div, uint32_t *l0, uint32_t *slots, uint32_t *adj,
+                              uint32_t *entry_point, int32_t *max_level, vgo_hnsw_build_log *log);
+
 int32_t vgo_hnsw_search_ws(const vgo_hnsw_graph *g, const float *query, int32_t k, int32_t ef,
                            uint32_t *ids, float *scores, vgo_search_stats *stats, uint32_t *visited_ws,
                            uint32_t epoch);

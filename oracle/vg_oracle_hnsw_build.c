@@ -72,6 +72,9 @@ typedef struct {
     int32_t *adj_cnt;
     int64_t level_off[64];
     int32_t top;
+    uint32_t *before; /* log only: a row's ids before a prune (m0) */
+    uint8_t *chosen;  /* log only, per row (layer 0 by node, then the upper rows): the row is full and applyHeuristic
+                         chose every member the last time it was selected; nothing was appended since */
 } builder;
 
 static void row_of(builder *b, uint32_t node, int level, uint32_t **ids, float **d, int32_t **cnt, int *deg)
@@ -90,6 +93,11 @@ static void row_of(builder *b, uint32_t node, int level, uint32_t **ids, float *
     *deg = b->m;
 }
 
+static int64_t row_index(const builder *b, uint32_t node, int level)
+{
+    return level == 0 ? (int64_t)node : b->n + b->level_off[level - 1] + b->slots[(int64_t)(level - 1) * b->n + node];
+}
+
 /* h.distanceFunc (newDistanceFunc hnsw.go:2218-2238) */
 static float pair_dist(const builder *b, uint32_t x, uint32_t y)
 {
@@ -100,10 +108,12 @@ static float pair_dist(const builder *b, uint32_t x, uint32_t y)
 }
 
 /* selectNeighbors hnsw.go:986-1024 (Heuristic = true, the default); consumes the max-heap `q`.
- * out: best-first items, returns their number (<= m). */
-static int select_neighbors(const builder *b, vgo_prioq *q, int m, vgo_pq_item *out, vgo_pq_item *temp)
+ * out: best-first items, returns their number (<= m).  *nchosen: how many of them applyHeuristic chose (the rest
+ * were filled up; 0 on the simple path). */
+static int select_neighbors(const builder *b, vgo_prioq *q, int m, vgo_pq_item *out, vgo_pq_item *temp, int *nchosen)
 {
     vgo_pq_item it;
+    *nchosen = 0;
     if (q->len <= m) { /* selectNeighborsSimple :993-1009 */
         int n = 0;
         while (q->len > 0) {
@@ -140,6 +150,7 @@ static int select_neighbors(const builder *b, vgo_prioq *q, int m, vgo_pq_item *
         }
         if (good) out[sel++] = temp[i];
     }
+    *nchosen = sel;
     for (int i = 0; i < nt && sel < m; i++) { /* fillUpNeighbors :1087-1106 */
         int found = 0;
         for (int s = 0; s < sel; s++)
@@ -152,37 +163,65 @@ static int select_neighbors(const builder *b, vgo_prioq *q, int m, vgo_pq_item *
     return sel;
 }
 
-/* addConnection hnsw.go:455-499 (+ Simple :501-518, Prune :520-555) */
-static void add_connection(builder *b, vgo_prioq *q, vgo_pq_item *out, vgo_pq_item *temp, uint32_t source,
-                           uint32_t target, int level, float dist)
+/* addConnection hnsw.go:455-499 (+ Simple :501-518, Prune :520-555); returns VGO_LINK_*, *flags for a prune */
+static int add_connection(builder *b, vgo_prioq *q, vgo_pq_item *out, vgo_pq_item *temp, uint32_t source,
+                          uint32_t target, int level, float dist, int *flags)
 {
     uint32_t *ids;
     float *d;
     int32_t *cnt;
     int deg;
     row_of(b, source, level, &ids, &d, &cnt, &deg);
+    if (flags) *flags = 0;
     for (int i = 0; i < *cnt; i++)
-        if (ids[i] == target) return;
+        if (ids[i] == target) return VGO_LINK_ALREADY;
+    uint8_t *chosen = flags ? b->chosen + row_index(b, source, level) : NULL;
     if (*cnt < deg) {
         ids[*cnt] = target;
         d[*cnt] = dist;
         (*cnt)++;
-        return;
+        if (chosen) *chosen = 0;
+        return VGO_LINK_APPENDED;
+    }
+    if (flags) { /* the log's view of the row before the prune */
+        int farther = 1;
+        if (*chosen) *flags |= VGO_LINK_ROW_CHOSEN;
+        for (int i = 0; i < *cnt; i++) {
+            if (!(dist > d[i])) farther = 0;
+            if (dist == d[i]) *flags |= VGO_LINK_TIE_ANY | VGO_LINK_TIE_NEW;
+            for (int j = 0; j < i; j++)
+                if (d[i] == d[j]) *flags |= VGO_LINK_TIE_ANY | VGO_LINK_TIE_MEMBERS;
+        }
+        if (farther) *flags |= VGO_LINK_FARTHER;
+        if (dist == d[*cnt - 1]) *flags |= VGO_LINK_TIE_LAST;
+        memcpy(b->before, ids, sizeof(uint32_t) * (size_t)deg);
     }
     q->len = 0;
     for (int i = 0; i < *cnt; i++) vgo_prioq_push(q, (vgo_pq_item){ids[i], d[i]});
     vgo_prioq_push(q, (vgo_pq_item){target, dist});
-    int k = select_neighbors(b, q, deg, out, temp);
+    int nchosen;
+    int k = select_neighbors(b, q, deg, out, temp, &nchosen);
     for (int i = 0; i < deg; i++) {
         ids[i] = i < k ? out[i].node : INVALID;
         d[i] = i < k ? out[i].dist : 0.0f;
     }
     *cnt = k;
+    if (chosen) *chosen = nchosen == deg;
+    if (flags && memcmp(b->before, ids, sizeof(uint32_t) * (size_t)deg) == 0) *flags |= VGO_LINK_UNCHANGED;
+    return VGO_LINK_PRUNED;
 }
 
 int32_t vgo_hnsw_build(const float *base, int64_t n, int32_t dim, int32_t metric, int32_t m, int32_t ef,
                        int32_t max_batch, int32_t growth_div, uint32_t *l0, uint32_t *slots, uint32_t *adj,
                        uint32_t *entry_point, int32_t *max_level)
+{
+    return vgo_hnsw_build_logged(base, n, dim, metric, m, ef, max_batch, growth_div, l0, slots, adj, entry_point,
+                                 max_level, NULL);
+}
+
+int32_t vgo_hnsw_build_logged(const float *base, int64_t n, int32_t dim, int32_t metric, int32_t m, int32_t ef,
+                              int32_t max_batch, int32_t growth_div, uint32_t *l0, uint32_t *slots, uint32_t *adj,
+                              uint32_t *entry_point, int32_t *max_level, vgo_hnsw_build_log *log)
 {
     if (n <= 0 || dim <= 0 || m < 2 || ef < 1 || max_batch < 1 || growth_div < 1) return -1;
     builder b;
@@ -208,6 +247,12 @@ int32_t vgo_hnsw_build(const float *base, int64_t n, int32_t dim, int32_t metric
     b.l0_cnt = (int32_t *)calloc((size_t)n, sizeof(int32_t));
     b.adj_d = (float *)calloc((size_t)(rows > 0 ? rows : 1) * m, sizeof(float));
     b.adj_cnt = (int32_t *)calloc((size_t)(rows > 0 ? rows : 1), sizeof(int32_t));
+    /* log: a chain counter per row (layer 0 by node, upper rows after them), zeroed at every batch */
+    int32_t *chain = log ? (int32_t *)malloc(sizeof(int32_t) * (size_t)(n + rows)) : NULL;
+    b.before = log ? (uint32_t *)malloc(sizeof(uint32_t) * (size_t)b.m0) : NULL;
+    b.chosen = log ? (uint8_t *)calloc((size_t)(n + rows), 1) : NULL;
+    int32_t batch_no = 0;
+    if (log) log->n_events = log->n_own = 0;
     for (int64_t i = 0; i < n * b.m0; i++) l0[i] = INVALID;
     for (int64_t i = 0; i < rows * m; i++) adj[i] = INVALID;
     for (int l = 0; l < b.top; l++) { /* slot = rank of the node among the nodes of that level, id order */
@@ -284,7 +329,20 @@ int32_t vgo_hnsw_build(const float *base, int64_t n, int32_t dim, int32_t metric
                 cur = best.node;
                 cur_d = best.dist;
                 const int maxc = level == 0 ? b.m0 : m;
-                int k = select_neighbors(&b, &res, maxc, out, temp);
+                const int ncand = res.len;
+                int nchosen;
+                int k = select_neighbors(&b, &res, maxc, out, temp, &nchosen);
+                if (log) {
+                    b.chosen[row_index(&b, (uint32_t)t, level)] = nchosen == maxc;
+                    if (log->n_own < log->cap_own) {
+                        int32_t *w = log->own + 4 * log->n_own;
+                        w[0] = (int32_t)t;
+                        w[1] = level;
+                        w[2] = ncand;
+                        w[3] = k;
+                    }
+                    log->n_own++;
+                }
                 uint32_t *ids;
                 float *dd;
                 int32_t *cnt;
@@ -298,6 +356,7 @@ int32_t vgo_hnsw_build(const float *base, int64_t n, int32_t dim, int32_t metric
             }
         }
         /* the batch's back links, id order (insertNode :975-979) */
+        if (log) memset(chain, 0, sizeof(int32_t) * (size_t)(n + rows));
         for (int64_t t = done; t < done + bsz; t++) {
             const int32_t lt = levels[t];
             for (int level = lt < cur_top ? lt : cur_top; level >= 0; level--) {
@@ -306,7 +365,26 @@ int32_t vgo_hnsw_build(const float *base, int64_t n, int32_t dim, int32_t metric
                 int32_t *cnt;
                 int deg;
                 row_of(&b, (uint32_t)t, level, &ids, &dd, &cnt, &deg);
-                for (int i = 0; i < *cnt; i++) add_connection(&b, &pq, out, temp, ids[i], (uint32_t)t, level, dd[i]);
+                for (int i = 0; i < *cnt; i++) {
+                    int flags = 0;
+                    const int what = add_connection(&b, &pq, out, temp, ids[i], (uint32_t)t, level, dd[i],
+                                                    log ? &flags : NULL);
+                    if (!log) continue;
+                    const int64_t r = row_index(&b, ids[i], level);
+                    if (log->n_events < log->cap_events) {
+                        vgo_hnsw_link_event *e = log->events + log->n_events;
+                        e->batch = batch_no;
+                        e->level = level;
+                        e->node = ids[i];
+                        e->new_node = (uint32_t)t;
+                        e->pos = chain[r];
+                        e->deg = level == 0 ? b.m0 : m;
+                        e->outcome = what;
+                        e->flags = flags;
+                    }
+                    chain[r]++;
+                    log->n_events++;
+                }
             }
         }
         for (int64_t t = done; t < done + bsz; t++) /* updateEntryPoint :885-900 */
@@ -315,6 +393,7 @@ int32_t vgo_hnsw_build(const float *base, int64_t n, int32_t dim, int32_t metric
                 entry = (uint32_t)t;
             }
         done += bsz;
+        batch_no++;
     }
     *entry_point = entry;
     *max_level = cur_top;
@@ -328,6 +407,9 @@ int32_t vgo_hnsw_build(const float *base, int64_t n, int32_t dim, int32_t metric
     free(b.l0_cnt);
     free(b.adj_d);
     free(b.adj_cnt);
+    free(chain);
+    free(b.before);
+    free(b.chosen);
     free(levels);
     return 0;
 }

@@ -341,6 +341,7 @@ __global__ __launch_bounds__(kSelThreads) void build_select_kernel(BuildGraph g,
 // ---- 3. back links ---------------------------------------------------------------------------------
 struct LinkTotals {  // over the whole build (VG_BUILD_DEBUG prints them)
     unsigned long long records, skipped, appended, pruned, good_rows_seen, longest_chain;
+    unsigned long long skipped_stable;  // of `skipped`: on a row with tied members, by `stable`
     // rows with >= 1000 records in a batch (hubs), 100 MHz ticks: where one workgroup's time goes
     unsigned long long hub_rows, hub_records, hub_applied, hub_sort, hub_scan, hub_gather, hub_replay, hub_total, hub_ties, max_wg;
 };
@@ -435,7 +436,7 @@ __global__ __launch_bounds__(kLinkThreads) void build_link_kernel(BuildGraph g, 
     uint64_t bits = 0;
     bool good = false, ties = false;
     bool stable = false;  // a good row WITH ties that a far record was seen to leave exactly as it is (see below)
-    unsigned int n_skip = 0, n_app = 0, n_prune = 0, n_tie = 0;
+    unsigned int n_skip = 0, n_skip_stable = 0, n_app = 0, n_prune = 0, n_tie = 0;
     auto row_has_ties = [&]() {
         const float nxt = __shfl_down(dist, 1);
         return __ballot(lane + 1 < cnt && dist == nxt) != 0;
@@ -487,6 +488,7 @@ __global__ __launch_bounds__(kLinkThreads) void build_link_kernel(BuildGraph g, 
                 const int rest = nadd - chunk * 64 < 64 ? nadd - chunk * 64 : 64;  // records in this chunk
                 const int f = work ? __builtin_ctzll(work) : rest;                  // lane of the first of them
                 n_skip += static_cast<unsigned int>(f - (a & 63));
+                if (ties && stable) n_skip_stable += static_cast<unsigned int>(f - (a & 63));
                 a = chunk * 64 + f;
                 if (f == rest) continue;  // the chunk is done: next chunk (or the end)
                 t = __shfl(ct, f);
@@ -681,6 +683,7 @@ __global__ __launch_bounds__(kLinkThreads) void build_link_kernel(BuildGraph g, 
             if (totals) {
                 atomicAdd(&totals->records, static_cast<unsigned long long>(nadd));
                 atomicAdd(&totals->skipped, static_cast<unsigned long long>(n_skip));
+                atomicAdd(&totals->skipped_stable, static_cast<unsigned long long>(n_skip_stable));
                 atomicAdd(&totals->appended, static_cast<unsigned long long>(n_app));
                 atomicAdd(&totals->pruned, static_cast<unsigned long long>(n_prune));
                 atomicAdd(&totals->good_rows_seen, static_cast<unsigned long long>(g.good[srow] ? 1 : 0));
@@ -1017,9 +1020,11 @@ static int32_t run_batches(vg_ctx *ctx, hipStream_t st, const BuildGraph &g, con
     if (r.totals) {
         LinkTotals t{};
         VG_HIP(hipMemcpy(&t, r.totals, sizeof(t), hipMemcpyDeviceToHost));
-        fprintf(stderr, "%s: back links %llu = %llu skipped (farther than a fully chosen row's last member) + %llu appended + "
+        fprintf(stderr, "%s: back links %llu = %llu skipped (farther than a fully chosen row's last member; %llu of them on a "
+                        "settled row with tied members) + %llu appended + "
                         "%llu pruned; target-row visits that found the row fully chosen %llu; longest per-row chain in one batch %llu\n",
-                fn, t.records, t.skipped, t.appended, t.pruned, t.good_rows_seen, std::max(dbg.max_chain, t.longest_chain));
+                fn, t.records, t.skipped, t.skipped_stable, t.appended, t.pruned, t.good_rows_seen,
+                std::max(dbg.max_chain, t.longest_chain));
         fprintf(stderr, "%s: rows with >= 1000 back links in a batch: %llu visits, %llu records of which %llu applied; per visit "
                         "%.1f us in all = sort %.1f + scan %.1f + gather %.1f + replay %.1f (us); heap replays (ties) %llu\n", fn,
                 t.hub_rows, t.hub_records, t.hub_applied,
