@@ -679,6 +679,26 @@ func (r *Resident) EnableSQ8Nomination(on bool) error {
 	return hipctx.Err(int32(C.vg_index_enable_sq8_nomination(r.h, v, nil)))
 }
 
+// EnableSQ8NominationFromCodes: the same nomination without the dequantised-row image — the queries are scaled by the inverse
+// scales and the GEMM's row tiles converted from the code tiles (whole-segment, unfiltered batches above 128 queries).  Resident:
+// 4 bytes a row and 4 a dimension.  The two modes are exclusive; results unchanged.
+func (r *Resident) EnableSQ8NominationFromCodes(on bool) error {
+	v := C.int32_t(0)
+	if on {
+		v = 1
+	}
+	return hipctx.Err(int32(C.vg_index_enable_sq8_nomination_from_codes(r.h, v, nil)))
+}
+
+// SQ8NominationInfo: mode 0 (off), 1 (the dequantised-row image) or 2 (from the codes), the device bytes the mode keeps resident,
+// and the queries whose proof failed and the scan answered since the mode was enabled.
+func (r *Resident) SQ8NominationInfo() (mode int, heldBytes, rescanned int64, err error) {
+	var m C.int32_t
+	var b, n C.int64_t
+	st := C.vg_index_sq8_nomination_info(r.h, &m, &b, &n)
+	return int(m), int64(b), int64(n), hipctx.Err(int32(st))
+}
+
 // EnablePQNomination: batches of SearchPQ (queries x rows >= 24M, k <= 256) are nominated by a bfloat16 MFMA GEMM over the decoded
 // rows (+ rows*dim*2 bytes of device memory) and re-scored from the codes against the query's distance table; results unchanged.
 func (r *Resident) EnablePQNomination(on bool) error {

@@ -117,7 +117,8 @@ extern "C" {
  *  search (the lexical leg and the fusion of Engine.HybridSearch): vg_bm25_create / _destroy / _stats / _search / _replayed and
  *  vg_rrf_fuse, found by symbol lookup.  Likewise the writes to a resident BM25 index: vg_bm25_create_empty, vg_bm25_update
  *  and vg_bm25_export, found by symbol lookup.  Likewise the PQ batch nomination from the codes:
- *  vg_index_enable_pq_nomination_from_codes and vg_index_pq_nomination_info, found by symbol lookup. */
+ *  vg_index_enable_pq_nomination_from_codes and vg_index_pq_nomination_info, found by symbol lookup.  Likewise the SQ8 batch
+ *  nomination from the codes: vg_index_enable_sq8_nomination_from_codes and vg_index_sq8_nomination_info, found by symbol lookup. */
 #define VG_ABI_MINOR 13
 #define VG_INVALID_ID 0xFFFFFFFFu
 #define VG_STREAM_LEGACY ((void *)1) /* == hipStreamLegacy */
@@ -1597,6 +1598,23 @@ int32_t vg_index_enable_pq_nomination_from_codes(vg_index *idx, int32_t on, void
  * the codes); *held_bytes = the device memory the mode keeps resident (mode 1: the image, the norms and norm_max).  Either
  * pointer may be NULL.  Found by symbol lookup. */
 int32_t vg_index_pq_nomination_info(const vg_index *idx, int32_t *mode, int64_t *held_bytes);
+/* vg_index_enable_sq8_nomination WITHOUT the image of the dequantised rows.  A code is an integer, and bfloat16 holds c - 128
+ * exactly: the nomination GEMM multiplies the queries scaled by the inverse scales, bf16(q_d * inv_d) — the only rounded operand —
+ * by the centred codes, which its row tiles convert from the index's own code tiles; its scores differ from the image mode's by the
+ * per-query constant 2 q.mid (Dot: q.mid), mid_d = min_d + 128 inv_d, which the proof takes back.  Re-score (sq.L2Distance /
+ * sq.DotProduct on the codes), proof and results are the image mode's and the scan's, bit for bit.  Resident: the rows' norms
+ * (4 bytes a row), mid (4 bytes a padded dimension) and two floats — rows * 4 + dim_pad * 4 + 8 bytes, where the image is rows *
+ * dim_pad * 2; the threshold sample's row tiles (rows / 64) are converted into the call's scratch.  Refusals as
+ * vg_index_enable_sq8_nomination's (NULL index, no SQ8 codes).  The two modes are exclusive: enabling one frees the other's
+ * state; on == 0 frees this one's and leaves the other; vg_index_set_sq8_codes drops either.  Batches it takes: whole-segment
+ * vg_search_sq8, L2 or Dot, unfiltered, MORE THAN 128 queries, k <= 256, rows > k, 16-byte aligned device queries, and queries x
+ * rows at or above its crossover against the scan (README, Limits); filtered batches, probed partitions and smaller batches keep
+ * the scan, with the same results.  Found by symbol lookup. */
+int32_t vg_index_enable_sq8_nomination_from_codes(vg_index *idx, int32_t on, void *stream);
+/* Which SQ8 nomination an index holds and what it does: *mode = 0 (off), 1 (the image: vg_index_enable_sq8_nomination) or 2 (from
+ * the codes); *held_bytes = the device memory the mode keeps resident; *rescanned = the queries, since the mode was enabled, whose
+ * proof failed and which the scan answered (0 when off).  Any pointer may be NULL.  Found by symbol lookup. */
+int32_t vg_index_sq8_nomination_info(const vg_index *idx, int32_t *mode, int64_t *held_bytes, int64_t *rescanned);
 
 #ifdef __cplusplus
 }

@@ -675,6 +675,21 @@ public:
         check(vg_index_pq_nomination_info(h_, &r.mode, &r.held_bytes));
         return r;
     }
+    // the SQ8 batch nomination without the image of the dequantised rows: the GEMM's row tiles converted from the code tiles
+    // (batches above 128 queries, unfiltered, the whole segment); exclusive with EnableSQ8Nomination; results unchanged
+    void EnableSQ8NominationFromCodes(bool on = true) { check(vg_index_enable_sq8_nomination_from_codes(h_, on ? 1 : 0, nullptr)); }
+    // mode: 0 off, 1 the image, 2 from the codes; held_bytes: the device memory the mode keeps resident; rescanned: queries whose
+    // proof failed and the scan answered, since the mode was enabled
+    struct SQ8Nomination {
+        int32_t mode;
+        int64_t held_bytes, rescanned;
+    };
+    SQ8Nomination SQ8NominationInfo() const
+    {
+        SQ8Nomination r{0, 0, 0};
+        check(vg_index_sq8_nomination_info(h_, &r.mode, &r.held_bytes, &r.rescanned));
+        return r;
+    }
     Result SearchRaBitQ(const float *queries, int64_t nq, int k) { return run(nq, k, [&](Result &r) { return vg_search_rabitq(h_, queries, nq, k, r.ids.data(), r.scores.data(), nullptr); }); }
     // IVF partitions (flat/segment.go:187-207) and the probed scan of flat.Segment.Search (:727-749):
     // scan = VG_SCAN_F32 / VG_SCAN_PQ / VG_SCAN_SQ8, nprobes <= 0 means 1 as in the reference

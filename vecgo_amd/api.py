@@ -1005,6 +1005,20 @@ class Index:
         scores stay bit-identical."""
         check(self._lib.vg_index_enable_sq8_nomination(self._h, C.c_int32(1 if on else 0), _stream_ptr(stream)))
 
+    def enable_sq8_nomination_from_codes(self, on: bool = True, stream=None):
+        """vg_index_enable_sq8_nomination_from_codes: the same nomination without the image of the dequantised rows — the queries are
+        scaled by the inverse scales and the GEMM's row tiles converted from the code tiles, bf16(code - 128), exact (whole-segment,
+        unfiltered batches above 128 queries, from queries x rows >= 12M).  Resident: 4 bytes a row and 4 a dimension.  Exclusive
+        with enable_sq8_nomination; ids and scores stay bit-identical."""
+        check(self._lib.vg_index_enable_sq8_nomination_from_codes(self._h, C.c_int32(1 if on else 0), _stream_ptr(stream)))
+
+    def sq8_nomination_info(self):
+        """vg_index_sq8_nomination_info: (mode, held_bytes, rescanned) — mode 0 off, 1 the dequantised-row image, 2 from the codes;
+        held_bytes the device memory the mode keeps resident; rescanned the queries whose proof failed since it was enabled."""
+        mode, held, rescanned = C.c_int32(0), C.c_int64(0), C.c_int64(0)
+        check(self._lib.vg_index_sq8_nomination_info(self._h, C.byref(mode), C.byref(held), C.byref(rescanned)))
+        return mode.value, held.value, rescanned.value
+
     def search_sq8(self, queries, k, out=None, stream=None):
         """flat.Segment.Search SQ8 branch (flat/segment.go:517-604)."""
         return self._search(self._lib.vg_search_sq8, queries, k, out=out, stream=stream)

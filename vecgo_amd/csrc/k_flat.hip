@@ -77,6 +77,9 @@ struct GemmArgs {
     // n rows' code bytes, code_m a row
     const uint8_t *codes = nullptr;
     int code_m = 0;
+    // with `codes`: the SQ8 code tile (flat_gemm_sq8_big_kernel) — `codes` is the index's SQ8 code tiles, code_m their groups of 16
+    // dimensions; c.ops.b is not read
+    bool sq8 = false;
 
     explicit GemmArgs(const NomCall &call) : c(call), queries(call.ops.a) {}
     // MODE 0 / 1: the scores of every stride-th row tile into sc[cnt][cols] (stride 1: the whole score matrix)
@@ -101,6 +104,7 @@ struct GemmArgs {
     GemmArgs &screen_tile(const uint32_t *hi_image) { return split_tile(hi_image), screen = true, *this; }
     GemmArgs &retry(const uint32_t *active) { return tile_active = active, *this; }
     GemmArgs &from_codes(const uint8_t *rows, int m) { return codes = rows, code_m = m, *this; }
+    GemmArgs &from_sq8_codes(const uint8_t *tiles, int groups) { return codes = tiles, code_m = groups, sq8 = true, *this; }
 };
 constexpr int kCountLine = 32;
 // Whether a MODE 2 launch of vg_search_flat's fused path runs the split tile: fp32 rows nominated by three bfloat16 products on the
@@ -250,6 +254,14 @@ static int32_t launch_gemm_t(const GemmArgs &a)
         note_flat_split_launch();
         return launch_big(flat_gemm_split_big_kernel<DOT, 3>, big_lds_bytes<3>(), a.tile_active);
     }
+    if (MODE == 2 && a.codes && a.sq8) {  // (likewise; L2 and Dot)
+        if constexpr (MODE == 2) {
+            VG_CHECK(bf16 && c.cnt * static_cast<int64_t>(a.cap) < (int64_t(1) << 31) && a.thr_stride < 65536 && c.ops.dim_words % kGemmBK == 0 &&
+                         a.code_m > 0 && c.ops.n > 0,
+                     VG_ERR_INVALID_ARG, "launch_gemm: the SQ8 code tile on a call without it");
+            return launch_big(flat_gemm_sq8_big_kernel<DOT, 3>, big_lds_bytes<3>(), a.codes, a.code_m);
+        }
+    }
     if (MODE == 2 && a.codes) {  // (any number of queries: there is no row image another tile could read)
         if constexpr (MODE == 2 && !DOT) {
             VG_CHECK(bf16 && c.cnt * static_cast<int64_t>(a.cap) < (int64_t(1) << 31) && a.thr_stride < 65536 && c.ops.dim_words % kGemmBK == 0,
@@ -288,19 +300,28 @@ static int32_t launch_gemm(const GemmArgs &a)
 
 // fp32 -> bfloat16, round to nearest even (NaN stays NaN): rows of `dim` floats written as rows of `dim_pad` bfloat16, the tail
 // zeros (operands of the bf16 GEMM are padded to whole K steps)
+__device__ __forceinline__ uint16_t bf16_rne_bits(uint32_t u)
+{
+    if ((u & 0x7F800000u) == 0x7F800000u && (u & 0x007FFFFFu) != 0) return static_cast<uint16_t>((u >> 16) | 0x0040u);
+    return static_cast<uint16_t>((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
+}
 __global__ void f32_to_bf16_pad_kernel(const float *__restrict__ src, int64_t rows, int dim, int dim_pad, uint16_t *__restrict__ dst)
 {
     const int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
     if (i >= rows * dim_pad) return;
     const int64_t r = i / dim_pad;
     const int j = static_cast<int>(i - r * dim_pad);
-    const uint32_t u = j < dim ? __float_as_uint(src[r * dim + j]) : 0u;
-    uint16_t v;
-    if ((u & 0x7F800000u) == 0x7F800000u && (u & 0x007FFFFFu) != 0)
-        v = static_cast<uint16_t>((u >> 16) | 0x0040u);
-    else
-        v = static_cast<uint16_t>((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
-    dst[i] = v;
+    dst[i] = bf16_rne_bits(j < dim ? __float_as_uint(src[r * dim + j]) : 0u);
+}
+// the same of src[r][j] * scale[j] — one fp32 rounding, then the bfloat16 one: the queries of the SQ8 nomination from the codes
+__global__ void f32_scaled_to_bf16_pad_kernel(const float *__restrict__ src, const float *__restrict__ scale, int64_t rows, int dim, int dim_pad,
+                                              uint16_t *__restrict__ dst)
+{
+    const int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (i >= rows * dim_pad) return;
+    const int64_t r = i / dim_pad;
+    const int j = static_cast<int>(i - r * dim_pad);
+    dst[i] = bf16_rne_bits(j < dim ? __float_as_uint(src[r * dim + j] * scale[j]) : 0u);
 }
 
 // The queries of the split tile (flat_gemm_split_big_kernel) as an image of `dim` 4-byte words per row, like the fp32 row it is
@@ -973,10 +994,15 @@ static GemmOperands fp32_operands(const vg_index *idx, const float *queries, boo
 }
 // The operands of a nomination on a bfloat16 image of the n rows (rows_bf16: dim_pad bfloat16 a row, `norms` its norms): the
 // queries rounded and padded alike into qbf — one launch — and the image.
+// (scale, or null: the queries multiplied by it element by element first — f32_scaled_to_bf16_pad_kernel)
 static int32_t gemm_operands(const float *queries, int64_t cnt, int dim, int64_t n, const float *norms, const uint16_t *rows_bf16, int dim_pad,
-                             uint16_t *qbf, hipStream_t st, GemmOperands *ops)
+                             uint16_t *qbf, hipStream_t st, GemmOperands *ops, const float *scale = nullptr)
 {
-    VG_LAUNCH(f32_to_bf16_pad_kernel, dim3(static_cast<unsigned>((cnt * dim_pad + 255) / 256)), dim3(256), 0, st, queries, cnt, dim, dim_pad, qbf);
+    const dim3 grid(static_cast<unsigned>((cnt * dim_pad + 255) / 256));
+    if (scale)
+        VG_LAUNCH(f32_scaled_to_bf16_pad_kernel, grid, dim3(256), 0, st, queries, scale, cnt, dim, dim_pad, qbf);
+    else
+        VG_LAUNCH(f32_to_bf16_pad_kernel, grid, dim3(256), 0, st, queries, cnt, dim, dim_pad, qbf);
     *ops = {reinterpret_cast<const float *>(qbf), reinterpret_cast<const float *>(rows_bf16), n, dim_pad / 2, norms, true, true};
     return VG_OK;
 }
@@ -1502,6 +1528,33 @@ __global__ void pq_sample_rows_kernel(const uint8_t *__restrict__ codes, int64_t
     out[c * granules + j] = cb16[static_cast<int64_t>(j) * 256 + code];
     if (j == 0) norms_c[c] = norms[row];
 }
+// The SQ8 nomination from the codes (img.scale: vg_index_enable_sq8_nomination_from_codes, k_sq8_scan.hip; L2 and Dot, unfiltered)
+// likewise: the queries' image is bf16(q_d inv_d), the append GEMM converts its row tiles from the code tiles
+// (flat_gemm_sq8_big_kernel), and the sampled tiles are converted here the same way — bf16(code - 128), exact — so that sample and
+// append score in one space, s' = |x^|^2 - 2 (q o inv).(c - 128) (Dot: -(q o inv).(c - 128)), and the thresholds need no shift.
+// thread per (compact row, 16-dimension group of dim_pad / 16); groups from `groups` on are zeros
+__global__ void sq8_sample_rows_kernel(const uint4 *__restrict__ tiles, int groups, int groups_pad, const float *__restrict__ norms, int64_t rows_c,
+                                       int stride, uint4 *__restrict__ out, float *__restrict__ norms_c)
+{
+    const int64_t t = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+    const int64_t c = t / groups_pad;
+    const int g = static_cast<int>(t - c * groups_pad);
+    if (c >= rows_c) return;
+    const int64_t row = (c / kGemmBN) * stride * kGemmBN + (c % kGemmBN);  // (< n: rows_c counts the sampled rows that exist)
+    uint32_t w[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
+    if (g < groups) {
+        const uint4 code = tiles[((row >> 6) * groups + g) * 64 + (row & 63)];
+        const uint32_t cw[4] = {code.x, code.y, code.z, code.w};
+#pragma unroll
+        for (int e = 0; e < 16; e++) {
+            const float v = static_cast<float>(static_cast<int>((cw[e >> 2] >> (8 * (e & 3))) & 0xFFu) - 128);  // (exact in bfloat16)
+            w[e >> 1] |= (__float_as_uint(v) >> 16) << (16 * (e & 1));
+        }
+    }
+    out[(c * groups_pad + g) * 2] = make_uint4(w[0], w[1], w[2], w[3]);
+    out[(c * groups_pad + g) * 2 + 1] = make_uint4(w[4], w[5], w[6], w[7]);
+    if (g == 0) norms_c[c] = norms[row];
+}
 // the rows of every stride-th 128-row tile of n rows that exist (only the last tile of all can be short)
 static int64_t sample_rows(int64_t n, int stride)
 {
@@ -1535,10 +1588,16 @@ int32_t flat_nominate_bf16(vg_index *idx, const NomImage &img, bool dot, const f
     const NominateScratch s(scratch, cnt, idx->n, img, k);
     NomCall nc{st, dot, {}, cnt, mask, mask_stride};
     // (from the codes the GEMM's "rows" are the codebook; n, the row length and the norms are the decoded rows')
-    VG_TRY(gemm_operands(queries, cnt, idx->dim, idx->n, img.norms, img.rows, img.dim_pad, s.qbf, st, &nc.ops));
+    VG_TRY(gemm_operands(queries, cnt, idx->dim, idx->n, img.norms, img.rows, img.dim_pad, s.qbf, st, &nc.ops, img.scale));
     *nom = s.nom;
     NomCall sc = nc;  // the sample's operands: the image's, or the sampled tiles decoded here
-    if (s.rows_c) {
+    if (s.rows_c && img.scale) {
+        const int groups_pad = img.dim_pad / 16;
+        VG_LAUNCH(sq8_sample_rows_kernel, dim3(static_cast<unsigned>((s.rows_c * groups_pad + 255) / 256)), dim3(256), 0, st,
+                  reinterpret_cast<const uint4 *>(idx->d_sq_tiles), idx->sq_groups, groups_pad, img.norms, s.rows_c, kFlatSampleStride,
+                  reinterpret_cast<uint4 *>(s.srows), s.snorms);
+        sc.ops.b = reinterpret_cast<const float *>(s.srows), sc.ops.n = s.rows_c, sc.ops.norms = s.snorms;
+    } else if (s.rows_c) {
         const int granules = img.dim_pad / 8;
         VG_LAUNCH(pq_sample_rows_kernel, dim3(static_cast<unsigned>((s.rows_c * granules + 255) / 256)), dim3(256), 0, st, idx->d_pq_rows, idx->n,
                   idx->pq->m, reinterpret_cast<const uint4 *>(img.rows), granules, img.norms, s.rows_c, kFlatSampleStride,
@@ -1549,9 +1608,12 @@ int32_t flat_nominate_bf16(vg_index *idx, const NomImage &img, bool dot, const f
     VG_LAUNCH(flat_thr_cap_kernel, dim3(nc.ucnt()), dim3(64), 0, st, nom->thr, nom->sel_k, queries, idx->dim, img.norm_max);
     VG_HIP(hipMemsetAsync(nom->counts, 0, sizeof(int) * static_cast<size_t>(cnt), st));
     {
-        ProfScope prof(idx->ctx, img.from_codes ? "pq_codes_gemm" : "sq8_nominate_gemm", st);
+        ProfScope prof(idx->ctx, img.scale ? "sq8_codes_gemm" : img.from_codes ? "pq_codes_gemm" : "sq8_nominate_gemm", st);
         GemmArgs a = GemmArgs::append(nc, nom->thr, nom->sel_k, nom->counts, nom->cand, nom->cap).wide(s.counts_wide, idx->ctx->compute_units);
-        if (img.from_codes) a.from_codes(idx->d_pq_rows, idx->pq->m);
+        if (img.scale)
+            a.from_sq8_codes(idx->d_sq_tiles, idx->sq_groups);
+        else if (img.from_codes)
+            a.from_codes(idx->d_pq_rows, idx->pq->m);
         VG_TRY(launch_gemm<2>(a));
     }
     return k <= kNomPickMaxK ? launch_flat_pick(*nom, cnt, nullptr, st) : VG_OK;

@@ -132,6 +132,7 @@ struct PqTableRow {
         return pq_adc_row_score(tables + q * m * 256, codes + static_cast<int64_t>(id) * m, m);
     }
     __device__ float eps(float qn, float norm_max) const { return pq_nominate_eps(dim, m, sd, qn, norm_max); }
+    static constexpr bool kShifted = false;  // (the GEMM multiplies the decoded rows themselves)
 };
 
 // The nomination from the codes (vg_index_enable_pq_nomination_from_codes) takes more than 128 queries — the persistent

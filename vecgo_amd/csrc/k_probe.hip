@@ -690,7 +690,7 @@ static int32_t probed_whole_shortcut(const ProbedCall &c, bool *done)
     if (c.scan == VG_SCAN_F32 && c.nq >= 8) return vg::flat_search_masked(idx, c.q, c.nq, c.k, c.mk, c.mask_stride, c.oid, c.osc, c.st);
     // A filtered SQ8 batch over the whole segment with vg_index_enable_sq8_nomination: the bf16 nomination with the filter in its
     // epilogue, the exact re-score from the codes, the proof (k_sq8_scan.hip); queries whose proof fails take the probe kernels
-    if (c.scan == VG_SCAN_SQ8 && c.allow_nomination && vg::sq8_nomination_applies(idx, c.q, c.nq, c.k)) {
+    if (c.scan == VG_SCAN_SQ8 && c.allow_nomination && vg::sq8_nomination_applies(idx, c.q, c.nq, c.k, c.mk)) {
         std::vector<int> failed;
         VG_TRY(vg::sq8_nominated_pass(idx, c.q, c.nq, c.k, c.mk, c.mask_stride, c.oid, c.osc, c.st, failed));
         return c.rescan(failed);
@@ -734,7 +734,7 @@ struct ProbedGemmPath {
         f32 = c.scan == VG_SCAN_F32 && gemm_shape && (reinterpret_cast<uintptr_t>(idx->d_vectors) & 15) == 0;
         // SQ8 with vg_index_enable_sq8_nomination: the same grouped nomination on the bfloat16 image of the dequantised rows, the
         // pairs' 64 candidates re-scored from the codes and proven by the verify pair (launch_sq8_verify, k_sq8_scan.hip)
-        sq8 = c.scan == VG_SCAN_SQ8 && gemm_shape && c.allow_nomination && idx->sq_nom.rows != nullptr;
+        sq8 = c.scan == VG_SCAN_SQ8 && gemm_shape && c.allow_nomination && idx->sq_nom.row_image() != nullptr;
         const bool gemm = applies();
         if (gemm) {  // launch bounds from the partition sizes: one query tile per partition + the batch's further tiles on the largest
             int64_t sum_s = 0, sum_m = 0, max_s = 0, max_m = 0, max_nst = 0, max_nt = 0;

@@ -456,6 +456,105 @@ struct Sq8Row {
     {
         return (4.0f * (static_cast<float>(dim) * 5.9604645e-8f) + (DOT ? 0.00390625f : 0.0078125f) * 1.02f) * (qn + norm_max) + 1e-30f;
     }
+    static constexpr bool kShifted = false;  // (the GEMM multiplies the dequantised rows themselves)
+};
+
+// ---- the same from the codes (vg_index_enable_sq8_nomination_from_codes): no image of the dequantised rows -----------------------
+// The reference decodes x^_d = float32(c_d) inv_d + min_d (quantizer.go:241-247).  With c'_d = c_d - 128, an integer in -128 .. 127
+// that bfloat16 holds exactly, y = c' o inv and mid_d = min_d + 128 inv_d:  q.x^ = (q o inv).c' + q.mid.  The GEMM multiplies the
+// query image bf16(q_d inv_d) — the ONLY rounded operand — by the exact c', converted from the code tiles inside the tile's fill
+// (flat_gemm_sq8_big_kernel) and, for the sampled tiles, in the call's scratch (sq8_sample_rows_kernel, k_flat.hip): both score
+//     s' = |x^|^2 - 2 (q o inv).c'   (Dot: -(q o inv).c'),
+// the image mode's space moved by the per-query constant 2 q.mid (Dot: q.mid), which the verify pair takes back (Sq8CodesRow::shift).
+// The codes are CENTRED because the query rounding is relative to |q| |c o inv|: uncentred that is |q| |x^ - min|, on normal rows
+// about 5 sigma per dimension where |x^ - mid| is about one.
+// The state (NomImage, from_codes with `scale`): rows = mid as dim_pad floats (zeros from dim on) and, behind them, one float
+// H2 = sum_d (|min_d| + 255 |inv_d|)^2 (Dot's margin); norms = |x^|^2 exactly as the image mode computes them; norm_max =
+// max over the rows of max(|x^|^2, |y|^2), so that 2.002 (|q|^2 + norm_max) still lies above every |s'| (flat_thr_cap_kernel:
+// |s'| <= |x^|^2 + 2.01 |q||y|) and B = |q|^2 + norm_max scales every term below.  NaN -> +Inf as in the image mode.
+__global__ void sq8_mid_kernel(const float *__restrict__ mins, const float *__restrict__ inv, int dim, int dim_pad, float *__restrict__ mid)
+{
+    float h2 = 0.0f;  // one workgroup of 64 lanes
+    for (int j = threadIdx.x; j < dim_pad; j += 64) {
+        mid[j] = j < dim ? __builtin_fmaf(128.0f, inv[j], mins[j]) : 0.0f;
+        if (j < dim) {
+            const float h = fabsf(mins[j]) + 255.0f * fabsf(inv[j]);
+            h2 = __builtin_fmaf(h, h, h2);
+        }
+    }
+    for (int off = 32; off > 0; off >>= 1) h2 += __shfl_xor(h2, off);
+    if (threadIdx.x == 0) mid[dim_pad] = h2;
+}
+// one lane per row of a 64-row tile, as sq8_dequant_bf16_kernel without the image: the same |x^|^2, and |y|^2 beside it for norm_max
+__global__ __launch_bounds__(64) void sq8_codes_norms_kernel(const uint4 *__restrict__ tiles, int64_t n, int dim, int groups,
+                                                             const float *__restrict__ mins, const float *__restrict__ inv,
+                                                             float *__restrict__ norms, int *__restrict__ norm_max_bits)
+{
+    const int64_t tile = blockIdx.x;
+    const int lane = threadIdx.x;
+    const int64_t row = tile * 64 + lane;
+    float nrm = 0.0f, cn = 0.0f;
+    if (row < n) {
+        for (int g = 0; g < groups; g++) {
+            const uint4 c = tiles[(tile * groups + g) * 64 + lane];
+            const uint32_t w[4] = {c.x, c.y, c.z, c.w};
+#pragma unroll
+            for (int t = 0; t < 16; t++) {
+                const int j = g * 16 + t;
+                if (j < dim) {
+                    const uint32_t code = (w[t >> 2] >> (8 * (t & 3))) & 0xFFu;
+                    const float x = __builtin_fmaf(static_cast<float>(code), inv[j], mins[j]);
+                    const float y = static_cast<float>(static_cast<int>(code) - 128) * inv[j];
+                    nrm = __builtin_fmaf(x, x, nrm);
+                    cn = __builtin_fmaf(y, y, cn);
+                }
+            }
+        }
+        norms[row] = nrm;
+    }
+    float mx = 0.0f;
+    if (row < n) mx = nrm == nrm && cn == cn ? fmaxf(nrm, cn) : INFINITY;
+    for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off));
+    if (lane == 0) atomicMax(norm_max_bits, __float_as_int(mx));  // non-negative floats order like their bits
+}
+
+// the verify pair's Row from the codes: Sq8Row's exact score (the re-score is the same), the score space's constant and its margin
+template <bool DOT>
+struct Sq8CodesRow : Sq8Row<DOT> {
+    const float *mid;  // dim_pad floats, then H2
+    int dim_pad;
+    static constexpr bool kShifted = true;
+    __device__ float shift(const float *qv, int lane) const  // the lane's share of q.mid
+    {
+        float c = 0.0f;
+        for (int j = lane; j < this->dim; j += 64) c = __builtin_fmaf(qv[j], mid[j], c);
+        return c;
+    }
+    // |s' + |q|^2 - 2 q.mid - L2Distance| (Dot: |s' - q.mid - (-DotProduct)|) for any row, in units of B = |q|^2 + norm_max, u = 2^-24:
+    //  query rounding   the image is q_d inv_d (1 + d)(1 + b), |d| <= u (the fp32 product), |b| <= 2^-8 (bfloat16, nearest even); the
+    //                   products with c' are exact in fp32: |sum - q.y| <= (2^-8 + 2 u) |q||y| <= (2^-9 + u) B; L2 scores twice that
+    //  GEMM sum         the tile starts at s (|s| <= 1.501 B for L2, 2.002 B for Dot, by flat_thr_cap_kernel), adds dim products
+    //                   (S = sum |products| <= 0.51 B) and the key's fma: screen_gemm_eps's term (k_flat.hip), 4.03 (dim + 16) u
+    //                   for L2, 2.52 (dim + 16) u for Dot
+    //  norms, x^        L2: the stored |x^|^2 is a sum of dim fmas, dim u B; x^ itself is one fma off c inv + min, u |q||x^| twice: u B
+    //  mid, q.mid       mid is one fma (u |mid_d|), the wave's sum dim / 64 fmas and 6 additions: (dim / 64 + 8) u |q||mid|, and
+    //                   |mid| <= |x^| + |y| <= 2 sqrt(norm_max), |q||mid| <= B; L2 takes it twice: (dim / 32 + 16) u
+    //  the comparison   tau + |q|^2 - 2 q.mid - eps (Dot: -tau + q.mid + eps): three (two) roundings of at most 5 B (3 B), and
+    //                   |q|^2 as the kernel sums it, (dim / 64 + 7) u: 16 u + (dim / 64 + 7) u  (Dot: 8 u)
+    //  the reference    L2: q - x^ rounded (2 u), 16 lane sums of dim / 16 fmas, the reduction tree and the tail (21): (dim / 16 + 23) u
+    //                   |q - x^|^2 <= (dim / 8 + 46) u B.  Dot: a running sum of dim rounded products, (dim + 2) u |q||x^| <=
+    //                   (dim / 2 + 1) u B — and its decode rounds c inv BEFORE it adds min: u (|min_d| + 255 |inv_d|) per element, which
+    //                   no row's norm bounds (every code of a dimension may be 128): u |q| sqrt(H2) <= u (|q|^2 + H2) / 2
+    //  L2:  2^-8 + 2 u + (4.03 (dim + 16) + dim + 1 + dim / 32 + 16 + 16 + dim / 64 + 7 + dim / 8 + 46) u  <=  2^-8 1.001 + (6 dim + 160) u
+    //  Dot: 2^-9 + u + (2.52 (dim + 16) + dim / 64 + 8 + 8 + dim / 2 + 1) u  <=  2^-9 1.001 + (3.5 dim + 64) u,  + u (|q|^2 + H2)
+    // At dim 768: 4.19e-3 B for L2, beside the image mode's 8.15e-3 (two rounded operands).  Denormal products the matrix unit may
+    // flush: below 1e-35 dim, inside the absolute term.  tests/test_sq8_nomination_codes_bound_cpu.py models the sums.
+    __device__ float eps(float qn, float norm_max) const
+    {
+        const float d = static_cast<float>(this->dim), u = 5.9604645e-8f;
+        if (DOT) return (0.001953125f * 1.001f + (3.5f * d + 64.0f) * u) * (qn + norm_max) + u * (qn + mid[dim_pad]) + 1e-30f;
+        return (0.00390625f * 1.001f + (6.0f * d + 160.0f) * u) * (qn + norm_max) + 1e-30f;
+    }
 };
 
 // the verify pair over nq query rows whose nomination (thresholds, count, candidates each) the batch search or another file
@@ -470,19 +569,37 @@ int32_t launch_sq8_verify(vg_index *idx, const float *queries, int64_t nq, const
     return launch_nominated_verify<false>(Sq8Row<false>{tiles, idx->sq_groups, idx->dim, idx->sq->d_mins, idx->sq->d_inv}, queries,
                                           idx->sq_nom.norm_max, nq, nom, k, ids, scores, fail, st);
 }
-// whether a batch takes the nomination (vg_index_enable_sq8_nomination; device queries)
-bool sq8_nomination_applies(const vg_index *idx, const float *d_queries, int64_t nq, int k)
+// The nomination from the codes takes more than 128 queries — the persistent tile's batches; the register-staged fill has no
+// 128-row form — over the whole segment, unfiltered, from kSq8NomCodesMinPairs (query, row) pairs up (tools/sq8_nominate_codes_time.py;
+// test hook VG_SQ8_NOM_CODES_ALWAYS: any number of pairs).
+constexpr int64_t kSq8NomCodesMinPairs = 12000000;
+// whether a batch takes the nomination (vg_index_enable_sq8_nomination, _from_codes; device queries; mask: the batch's row filter, or null)
+bool sq8_nomination_applies(const vg_index *idx, const float *d_queries, int64_t nq, int k, const uint8_t *mask)
 {
-    return idx->sq_nom.rows && nq >= VG_SQ8_NOM_MIN_Q && k <= kNomMaxK && idx->n > k && aligned16(d_queries);
+    const int mode = idx->sq_nom.mode();
+    if (mode == 2 && (mask || nq <= 128 || (nq * idx->n < kSq8NomCodesMinPairs && !hook(kHookSq8NomCodesAlways)))) return false;
+    return mode && nq >= VG_SQ8_NOM_MIN_Q && k <= kNomMaxK && idx->n > k && aligned16(d_queries);
 }
 // nominated_pass with the SQ8 re-score (mask: a device row filter per query / for the batch, or null)
 int32_t sq8_nominated_pass(vg_index *idx, const float *q, int64_t nq, int k, const uint8_t *mask, int64_t mask_stride, uint32_t *oid,
                            float *osc, hipStream_t st, std::vector<int> &failed)
 {
-    return nominated_pass(idx, idx->sq_nom, idx->metric != VG_METRIC_L2, q, nq, k, mask, mask_stride, 0, oid, osc, st, failed,
-                          [&](const float *qq, int64_t cnt, const ProbeNominated &nom, float *, uint32_t *ids, float *scores, int *fail) {
-                              return launch_sq8_verify(idx, qq, cnt, nom, k, ids, scores, fail, st);
-                          });
+    const bool dot = idx->metric != VG_METRIC_L2, codes = idx->sq_nom.mode() == 2;
+    const size_t before = failed.size();
+    VG_TRY(nominated_pass(idx, idx->sq_nom, dot, q, nq, k, mask, mask_stride, 0, oid, osc, st, failed,
+                          [&](const float *qq, int64_t cnt, const ProbeNominated &nom, float *, uint32_t *ids, float *scores, int *fail) -> int32_t {
+                              if (!codes) return launch_sq8_verify(idx, qq, cnt, nom, k, ids, scores, fail, st);
+                              const NomImage &img = idx->sq_nom;
+                              const uint4 *tiles = reinterpret_cast<const uint4 *>(idx->d_sq_tiles);
+                              const float *mid = reinterpret_cast<const float *>(img.rows);
+                              if (dot)
+                                  return launch_nominated_verify<true>(Sq8CodesRow<true>{{tiles, idx->sq_groups, idx->dim, idx->sq->d_mins, idx->sq->d_inv}, mid, img.dim_pad},
+                                                                       qq, img.norm_max, cnt, nom, k, ids, scores, fail, st);
+                              return launch_nominated_verify<false>(Sq8CodesRow<false>{{tiles, idx->sq_groups, idx->dim, idx->sq->d_mins, idx->sq->d_inv}, mid, img.dim_pad},
+                                                                    qq, img.norm_max, cnt, nom, k, ids, scores, fail, st);
+                          }));
+    idx->sq_nom_rescanned += static_cast<int64_t>(failed.size() - before);  // (vg_index_sq8_nomination_info)
+    return VG_OK;
 }
 
 // vg_cand_replay.hpp's scorer for the SQ8 scan: sq.L2Distance / sq.DotProduct of a row's code (flat/segment.go:517-604, :659-667),
@@ -538,19 +655,54 @@ int32_t sq8_nan_replay(vg_index *idx, const float *d_queries, int64_t nq, int k,
 
 }  // namespace vg
 
-VG_API int32_t vg_index_enable_sq8_nomination(vg_index *idx, int32_t on, void *stream)
+// vg_index_enable_sq8_nomination (mode 1) and vg_index_enable_sq8_nomination_from_codes (mode 2); fn: the entry point's name.
+// As for PQ (k_pq_nominate.hip): turning a mode off, or on again, drops that mode only; turning it on drops the other one too, but
+// only once nothing can refuse.
+static int32_t sq8_nomination_enable(vg_index *idx, int mode, int32_t on, void *stream, const char *fn)
 {
-    VG_CHECK(idx, VG_ERR_INVALID_ARG, "vg_index_enable_sq8_nomination: NULL index");
+    VG_CHECK(idx, VG_ERR_INVALID_ARG, "%s: NULL index", fn);
     VG_HIP(hipSetDevice(idx->ctx->device));
     hipStream_t st = vg::pick_stream(idx->ctx, stream);
-    VG_TRY(vg::nom_free(idx->sq_nom, st));
+    if (idx->sq_nom.mode() == mode) VG_TRY(vg::nom_free(idx->sq_nom, st));
     if (!on) return VG_OK;
-    VG_CHECK(idx->sq && idx->d_sq_tiles, VG_ERR_NOT_READY, "vg_index_enable_sq8_nomination: index has no SQ8 codes");
-    return vg::nom_build(idx->sq_nom, idx->n, idx->dim, vg::NomImage::body_bytes(idx->n, vg::nom_dim_pad(idx->dim), false), false, st, [&](const vg::NomImage &b, int *norm_max_bits) {
-        hipLaunchKernelGGL(vg::sq8_dequant_bf16_kernel, dim3(static_cast<unsigned>(idx->n_tiles)), dim3(64), 0, st,
-                           reinterpret_cast<const uint4 *>(idx->d_sq_tiles), idx->n, idx->dim, idx->sq_groups, idx->sq->d_mins, idx->sq->d_inv,
-                           b.rows, b.dim_pad, b.norms, norm_max_bits);
-    });
+    VG_CHECK(idx->sq && idx->d_sq_tiles, VG_ERR_NOT_READY, "%s: index has no SQ8 codes", fn);
+    VG_TRY(vg::nom_free(idx->sq_nom, st));
+    idx->sq_nom_rescanned = 0;
+    const uint4 *tiles = reinterpret_cast<const uint4 *>(idx->d_sq_tiles);
+    const dim3 grid(static_cast<unsigned>(idx->n_tiles));
+    const int dim_pad = vg::nom_dim_pad(idx->dim);
+    if (mode == 1)
+        return vg::nom_build(idx->sq_nom, idx->n, idx->dim, vg::NomImage::body_bytes(idx->n, dim_pad, false), false, st, [&](const vg::NomImage &b, int *norm_max_bits) {
+            hipLaunchKernelGGL(vg::sq8_dequant_bf16_kernel, grid, dim3(64), 0, st, tiles, idx->n, idx->dim, idx->sq_groups, idx->sq->d_mins, idx->sq->d_inv,
+                               b.rows, b.dim_pad, b.norms, norm_max_bits);
+        });
+    // from the codes: mid and H2 in the rows' place (4 dim_pad + 4 bytes), the norms, norm_max
+    VG_TRY(vg::nom_build(idx->sq_nom, idx->n, idx->dim, static_cast<int64_t>(dim_pad + 1) * 4, true, st, [&](const vg::NomImage &b, int *norm_max_bits) {
+        hipLaunchKernelGGL(vg::sq8_mid_kernel, dim3(1), dim3(64), 0, st, idx->sq->d_mins, idx->sq->d_inv, idx->dim, b.dim_pad, reinterpret_cast<float *>(b.rows));
+        hipLaunchKernelGGL(vg::sq8_codes_norms_kernel, grid, dim3(64), 0, st, tiles, idx->n, idx->dim, idx->sq_groups, idx->sq->d_mins, idx->sq->d_inv, b.norms,
+                           norm_max_bits);
+    }));
+    idx->sq_nom.scale = idx->sq->d_inv;  // (the quantizer's: it outlives its codes on the index, vg_index_set_sq8_codes)
+    return VG_OK;
+}
+
+VG_API int32_t vg_index_enable_sq8_nomination(vg_index *idx, int32_t on, void *stream)
+{
+    return sq8_nomination_enable(idx, 1, on, stream, "vg_index_enable_sq8_nomination");
+}
+
+VG_API int32_t vg_index_enable_sq8_nomination_from_codes(vg_index *idx, int32_t on, void *stream)
+{
+    return sq8_nomination_enable(idx, 2, on, stream, "vg_index_enable_sq8_nomination_from_codes");
+}
+
+VG_API int32_t vg_index_sq8_nomination_info(const vg_index *idx, int32_t *mode, int64_t *held_bytes, int64_t *rescanned)
+{
+    VG_CHECK(idx, VG_ERR_INVALID_ARG, "vg_index_sq8_nomination_info: NULL index");
+    if (mode) *mode = idx->sq_nom.mode();
+    if (held_bytes) *held_bytes = idx->sq_nom.held_bytes(idx->n);
+    if (rescanned) *rescanned = idx->sq_nom.mode() ? idx->sq_nom_rescanned : 0;
+    return VG_OK;
 }
 
 VG_API int32_t vg_index_set_sq8_codes(vg_index *idx, vg_sq8 *sq, const uint8_t *codes, void *stream)
@@ -566,7 +718,7 @@ VG_API int32_t vg_index_set_sq8_codes(vg_index *idx, vg_sq8 *sq, const uint8_t *
         VG_HIP(hipFree(idx->d_sq_tiles));
         idx->d_sq_tiles = nullptr;
     }
-    VG_TRY(vg::nom_free(idx->sq_nom, st));  // the old codes' nomination image (vg_index_enable_sq8_nomination again after new codes)
+    VG_TRY(vg::nom_free(idx->sq_nom, st));  // the old codes' nomination (vg_index_enable_sq8_nomination / _from_codes again after new codes)
     idx->sq = sq;
     idx->sq_groups = (idx->dim + 15) / 16;
     idx->n_tiles = (idx->n + 63) / 64;
@@ -600,7 +752,7 @@ static int32_t sq8_search_impl(vg_index *idx, const float *queries, int64_t nq, 
     float *osc = io.osc.ptr;
     if (idx->n == 0) {
         VG_TRY(vg::empty_results(nq, k, false, oid, osc, st));
-    } else if (allow_nomination && vg::sq8_nomination_applies(idx, q, nq, k)) {
+    } else if (allow_nomination && vg::sq8_nomination_applies(idx, q, nq, k, nullptr)) {
         std::vector<int> failed;
         VG_TRY(vg::sq8_nominated_pass(idx, q, nq, k, nullptr, 0, oid, osc, st, failed));
         // the scan kernels for the queries whose proof failed (ties at the k-th score, thresholds too tight)

@@ -337,7 +337,7 @@ VG_API int32_t vg_vamana_reorder_bfs(vg_index *idx, uint32_t *perm, uint32_t *in
     need(idx->pq_nom.row_image(), n * idx->pq_nom.dim_pad * 2);
     need(idx->d_rq_rows, n * (rq_nb + 4));
     need(idx->d_sq_tiles, idx->n_tiles * idx->sq_groups * 64 * 16);
-    need(idx->sq_nom.rows, n * idx->sq_nom.dim_pad * 2);
+    need(idx->sq_nom.row_image(), n * idx->sq_nom.dim_pad * 2);
     need(idx->d_int4_rows, n * int4_row);
 
     // BFS state: order (perm), inv (inv_perm), the large levels' keys, masks and counts, and the scratch
@@ -420,7 +420,8 @@ VG_API int32_t vg_vamana_reorder_bfs(vg_index *idx, uint32_t *perm, uint32_t *in
             VG_HIP(hipMemcpyAsync(idx->d_sq_tiles, scratch, static_cast<size_t>(tiles * idx->sq_groups * 64 * 16), hipMemcpyDeviceToDevice,
                                   st));
         }
-        VG_TRY(vg::rb_permute_rows(idx->sq_nom.rows, n, static_cast<int64_t>(idx->sq_nom.dim_pad) * 2, p, scratch, st));
+        // (from the codes: no row image, the norms alone move with the codes)
+        VG_TRY(vg::rb_permute_rows(idx->sq_nom.row_image(), n, static_cast<int64_t>(idx->sq_nom.dim_pad) * 2, p, scratch, st));
         VG_TRY(vg::rb_permute_rows(idx->sq_nom.norms, n, 4, p, scratch, st));
         // INT4 rows
         VG_TRY(vg::rb_permute_rows(idx->d_int4_rows, n, int4_row, p, scratch, st));

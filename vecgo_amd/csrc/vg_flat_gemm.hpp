@@ -683,7 +683,25 @@ __device__ __forceinline__ void split2_bf16(float a, float b, uint32_t &hi, uint
 // of a step (one per piece) are loaded one row-tile step AHEAD of the fill that uses them, in front of the previous fill's pieces
 // in the vector-memory queue: the fill waits for them by count (its own four pieces and the query tile's four are younger), not
 // for the tile in flight.  Rows past the end of the matrix re-read the last row's codes, as the image's fill re-reads the last row.
-enum { kBigImages = 0, kBigSplit = 1, kBigScreen = 2, kBigCodes = 3 };
+// OPS = kBigSq8 (flat_gemm_sq8_big_kernel): the bf16 tile of kBigImages over SQ8 codes, with no row image either.  The row operand is
+// bf16(code - 128), an integer bfloat16 holds exactly; `codes` is the index's code tiles, [64-row tile][16-dimension group][row] of
+// 16 bytes, code_m the groups of a row tile.  There is no table to gather from, so the fill goes through registers: a K step of a
+// 256-row tile is 4 (64-row tiles) x 4 (groups) x 64 granules of 16 codes = 2048 halves of 8 codes, four per lane.  Piece j of
+// wave w is group 4 s + j of rows 32 w .. 32 w + 31 — lane l: row 32 w + (l & 31), the granule's half l >> 5 (8 bytes: the two
+// half-waves of a load read the two halves of the same 32 consecutive granules, 512 contiguous bytes) — loaded one row-tile step
+// AHEAD of its fill, as kBigCodes loads its code bytes.  When the step is staged the lane turns each half into 8 bfloat16 (codes ^
+// 0x80 are the centred values as signed bytes; int -> float -> v_cvt_pk_bf16_f32, all exact) and writes them with ds_write_b128
+// where the image's fill would have put granule 2 j + (l >> 5) of that row: slot = granule ^ ((row >> 1) & 7).  The 32 lanes of a
+// half-wave write one granule index of 32 consecutive rows, 128 B apart: for 16 consecutive rows (and for the 16 lanes of a
+// ds_read_b128 pass, {0-3, 12-15, 20-27}, ...) (row >> 1) & 7 takes each value twice, once per row parity — 16 different 16-byte
+// bank groups of the 256-byte bank row, no conflict.  Groups from code_m on are written as zeros (their loads re-read the last
+// group), 64-row tiles past the last one re-read the last one (rows past n: never appended).
+// Publish: a fill by registers is an LDS write.  The wait in front of the barrier that ends a step is lgkmcnt(0) for every form of
+// the body — it retires these writes too — and the tile is first read two steps later.  The counted vmcnt waits: a wave's
+// vector-memory operations of a step are the query tile's four pieces, then this fill's four loads (of the step after next), so
+// the step's end waits vmcnt(4) — the queries have landed, the loads may fly — and the fill waits vmcnt(4) for its own loads of the
+// step before, behind which went only this step's four query pieces.
+enum { kBigImages = 0, kBigSplit = 1, kBigScreen = 2, kBigCodes = 3, kBigSq8 = 4 };
 // SAMPLE (flat_gemm_sample_big_kernel): the score-writing form, MODE 1 of the 128 x 128 tiles on this tile — the rows are every
 // tile_stride-th 128-row tile, written compactly into scores[q][out_cols] as the 128-row kernels write them, so a 256-row tile
 // is a PAIR of sampled 128-row tiles: sample tile ts takes rows [(2 ts) stride 128, + 128) through fill pieces 0-1 and rows
@@ -710,6 +728,8 @@ __device__ __forceinline__ void flat_gemm_big_body(
     constexpr bool SCREEN = OPS == kBigScreen;
     constexpr bool CODES = OPS == kBigCodes;
     static_assert(!CODES || (NB == 3 && !SAMPLE && PROBE == 0), "the code-gathered tile: three row buffers, the append form");
+    constexpr bool SQ8 = OPS == kBigSq8;
+    static_assert(!SQ8 || (NB == 3 && !SAMPLE && PROBE == 0), "the SQ8 code tile: three row buffers, the append form");
     extern __shared__ float gemm_lds[];
     const int mtiles = static_cast<int>((nq + kBigBM - 1) / kBigBM);
     // (SAMPLE: the pairs of sampled 128-row tiles)
@@ -791,7 +811,11 @@ __device__ __forceinline__ void flat_gemm_big_body(
     const uint8_t *kbase = nullptr;  // kBigCodes: the codes of the cursor's tile (wave-uniform)
     auto set_b = [&](const Pos &ps) {
         const int64_t n0 = static_cast<int64_t>(tn_of(ps)) * kBigBN;
-        if constexpr (CODES)
+        if constexpr (SQ8) {
+            // this wave's 64-row code tile of the row tile (rows 32 w ..: tile w >> 1), the last one that exists at most
+            const int64_t t64 = static_cast<int64_t>(tn_of(ps)) * 4 + (wave >> 1), t_last = (n + 63) / 64 - 1;
+            kbase = codes + (t64 < t_last ? t64 : t_last) * code_m * 1024;
+        } else if constexpr (CODES)
             kbase = codes + n0 * code_m;
         else
             bbase = base + n0 * dim;
@@ -902,7 +926,62 @@ __device__ __forceinline__ void flat_gemm_big_body(
         for (int p = 0; p < 4; p++) glds16(base, off[p], piece(b_buf(ib), p));
         ib = ib + 1 == NB ? 0 : ib + 1;
     };
+    // kBigSq8.  The cursor and f_k as for kBigCodes; sq[j] = the lane's 8 codes of piece j of the step to fill next.
+    unsigned long long sq[4] = {0ull, 0ull, 0ull, 0ull};
+    const uint32_t sq_lane = static_cast<uint32_t>((((wave & 1) * 32 + (lane & 31)) * 16) + 8 * (lane >> 5));  // bytes into a (tile, group)
+    const int sq_dst = (wave * 32 + (lane & 31)) * kGemmBK, sq_f = (lane >> 1) & 7;  // floats: the lane's row of the tile; its swizzle
+    auto load_sq8 = [&]() {
+        f_k = b_k;
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const int gq = b_k * 4 + j;
+            const uint32_t voff = static_cast<uint32_t>((gq < code_m ? gq : code_m - 1) * 1024) + sq_lane;
+            asm volatile("global_load_dwordx2 %0, %1, %2" : "=v"(sq[j]) : "v"(voff), "s"(kbase) : "memory");
+        }
+        if (++b_k == ksteps) {
+            b_k = 0;
+            if (b_pos.bt < total) {
+                step(b_pos);
+                if (b_pos.bt < total) set_b(b_pos);  // (past the stream's end: the last tile's codes once more, never multiplied)
+            }
+        }
+    };
+    // W: vector-memory operations younger than sq's loads that may still be in flight (0: the prologue waits for everything)
+    auto stage_sq8 = [&](auto W) {
+        // (the wait and the FIRST reads of sq in one statement, as stage_codes has them)
+        unsigned long long v[4];
+#define VG_SQ8_TAKE(cnt)                                                                                                            \
+    asm volatile("s_waitcnt vmcnt(" #cnt ")\n\tv_lshlrev_b64 %0, 0, %4\n\tv_lshlrev_b64 %1, 0, %5\n\tv_lshlrev_b64 %2, 0, %6\n\t"      \
+                 "v_lshlrev_b64 %3, 0, %7"                                                                                          \
+                 : "=&v"(v[0]), "=&v"(v[1]), "=&v"(v[2]), "=&v"(v[3])                                                              \
+                 : "v"(sq[0]), "v"(sq[1]), "v"(sq[2]), "v"(sq[3])                                                                  \
+                 : "memory")
+        if constexpr (decltype(W)::value == 4)
+            VG_SQ8_TAKE(4);
+        else
+            VG_SQ8_TAKE(0);
+#undef VG_SQ8_TAKE
+        const int g0 = f_k * 4;  // the step's first group
+        load_sq8();
+        float *const dst = gemm_lds + b_buf(ib) + sq_dst;
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const uint32_t lo = static_cast<uint32_t>(v[j]) ^ 0x80808080u, hi = static_cast<uint32_t>(v[j] >> 32) ^ 0x80808080u;
+            auto pair = [](uint32_t w, int at) {  // bytes at, at + 1 of w as signed values -> two bfloat16
+                const float a = static_cast<float>(static_cast<int8_t>(w >> (8 * at))), b = static_cast<float>(static_cast<int8_t>(w >> (8 * at + 8)));
+                return __builtin_bit_cast(uint32_t, __builtin_convertvector(vg_f32x2{a, b}, vg_bf16x2));
+            };
+            uint4 o = make_uint4(pair(lo, 0), pair(lo, 2), pair(hi, 0), pair(hi, 2));
+            if (g0 + j >= code_m) o = make_uint4(0u, 0u, 0u, 0u);  // (wave-uniform: a group past the row's dimensions)
+            *reinterpret_cast<uint4 *>(dst + ((2 * j + (lane >> 5)) ^ sq_f) * 4) = o;
+        }
+        ib = ib + 1 == NB ? 0 : ib + 1;
+    };
     auto stage_b = [&]() {
+        if constexpr (SQ8) {
+            stage_sq8(std::integral_constant<int, 4>{});
+            return;
+        }
         if constexpr (CODES) {
             // in the K loop: behind the codes' loads went the previous fill's four pieces and this step's query tile's four
             stage_codes(std::integral_constant<int, 8>{});
@@ -1291,9 +1370,13 @@ __device__ __forceinline__ void flat_gemm_big_body(
     // prologue: the first step's tiles (NB = 3: and the second step's row tile) in flight, the first tile's starting values
     // computed under them, then published
     if constexpr (CODES) load_codes();  // (of the first step)
+    if constexpr (SQ8) load_sq8();
     tile_loads(pos0);
     stage_a();
-    if constexpr (CODES) {
+    if constexpr (SQ8) {
+        stage_sq8(std::integral_constant<int, 0>{});
+        if (S > 1) stage_sq8(std::integral_constant<int, 0>{});
+    } else if constexpr (CODES) {
         stage_codes(std::integral_constant<int, 0>{});
         if (S > 1) stage_codes(std::integral_constant<int, 0>{});
     } else {
@@ -1308,6 +1391,7 @@ __device__ __forceinline__ void flat_gemm_big_body(
         asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
     else
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if constexpr (SQ8) __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): the first tiles' LDS writes (behind them: the third step's four loads)
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
     int ra = 0, rb = 0;  // buffers the current step is read from
@@ -1431,6 +1515,17 @@ __global__ __launch_bounds__(kBigThreads) void flat_gemm_codes_big_kernel(
 {
     flat_gemm_big_body<DOT, NB, 0, kBigCodes>(queries, nq, base, n, dim, norms, thr, thr_stride, thr_off, counts, cand, cap, mask, mask_stride,
                                               count_stride, nullptr, nullptr, 1, 0, codes, code_m);
+}
+// bf16 queries (scaled by the quantizer's inverse scales) against SQ8 code tiles centred and converted in registers (kBigSq8):
+// `base` is not read, dim = words per padded row, `tiles` the index's code tiles of `groups` 16-dimension groups
+template <bool DOT, int NB>
+__global__ __launch_bounds__(kBigThreads) void flat_gemm_sq8_big_kernel(
+    const float *__restrict__ queries, int64_t nq, const float *__restrict__ base, int64_t n, int dim, const float *__restrict__ norms,
+    const float *__restrict__ thr, int thr_stride, int thr_off, int *__restrict__ counts, uint64_t *__restrict__ cand, int cap,
+    const uint8_t *__restrict__ mask, int64_t mask_stride, int count_stride, const uint8_t *__restrict__ tiles, int groups)
+{
+    flat_gemm_big_body<DOT, NB, 0, kBigSq8>(queries, nq, base, n, dim, norms, thr, thr_stride, thr_off, counts, cand, cap, mask, mask_stride,
+                                            count_stride, nullptr, nullptr, 1, 0, tiles, groups);
 }
 // the same operands, the product of the hi halves alone (the screen in front of the split tile)
 template <bool DOT, int NB, int PROBE = 0>

@@ -92,6 +92,7 @@ enum Hook {
     kHookFlatBigTile2,        // VG_FLAT_BIG_TILE_2      bf16 256 x 256 tile with two row-tile buffers (128 KiB) instead of three
     kHookFlatBigEarlyB,       // VG_FLAT_BIG_EARLY_B     bf16 256 x 256 tile: row-tile fills behind the first matrix group of a step
     kHookPqNomAlways,         // VG_PQ_NOM_ALWAYS        vg_index_enable_pq_nomination: batches of any size take the nomination
+    kHookSq8NomCodesAlways,   // VG_SQ8_NOM_CODES_ALWAYS vg_index_enable_sq8_nomination_from_codes: no crossover of (query, row) pairs
     kHookKmNoRanges,          // VG_KM_NO_RANGES         k-means: the listed points' exact pass in one walk over the centroids (no ranges)
     kHookNoCandReplay,        // VG_NO_CAND_REPLAY       no heap replay for queries whose scores may hold a NaN (vg_cand_replay.hpp): what the fast paths alone answer
     kHookVamanaSmallScratch,  // VG_VAMANA_SMALL_SCRATCH a small batch takes several launches: vg_search_vamana with k > 512 gets 64 MiB of per-launch scratch, the Vamana builders' visited bitmaps (VamanaBatch, vg_vamana_common.hpp) 64 KiB
@@ -473,11 +474,16 @@ struct NomImage {
     float *norms = nullptr;    // n: |x^|^2 (fp32 of the unrounded values)
     float *norm_max = nullptr; // [1]: the largest of them
     bool from_codes = false;   // `rows` is the decoded codebook, not the decoded rows
+    // The SQ8 nomination from the codes (vg_index_enable_sq8_nomination_from_codes, k_sq8_scan.hip): from_codes with `scale` set.
+    // `rows` holds dim_pad floats, mid_d = min_d + 128 inv_d (zeros from dim on) — the offset of its score space; the GEMM's row
+    // tile is converted from the code tiles, bf16(code - 128), and the queries are multiplied by `scale` before they are rounded.
+    const float *scale = nullptr;  // the quantizer's inverse scales (borrowed), or null
+    int64_t body = 0;              // bytes of `rows`
     // what vg_index_pq_nomination_info reports: 0 off, 1 the image of the decoded rows, 2 from the codes
     int mode() const { return !rows ? 0 : from_codes ? 2 : 1; }
     uint16_t *row_image() const { return from_codes ? nullptr : rows; }  // the decoded rows, where the mode keeps them
     static int64_t body_bytes(int64_t n, int dim_pad, bool from_codes) { return (from_codes ? int64_t(dim_pad / 8) * 256 * 8 : n * dim_pad) * 2; }
-    int64_t held_bytes(int64_t n) const { return rows ? body_bytes(n, dim_pad, from_codes) + n * 4 + 4 : 0; }  // the body, the norms, norm_max
+    int64_t held_bytes(int64_t n) const { return rows ? body + n * 4 + 4 : 0; }  // the body, the norms, norm_max
 };
 // Frees an image (after the stream's work that may read it) and leaves it empty.
 inline int32_t nom_free(NomImage &img, hipStream_t st)
@@ -539,7 +545,8 @@ struct vg_index {
     uint8_t *d_rq_rows = nullptr;
     // SQ8 codes, re-tiled like the PQ codes: [tile][group of 16 dims][lane][16 B]; see k_sq8_scan.hip
     vg_sq8 *sq = nullptr;
-    vg::NomImage sq_nom;               // vg_index_enable_sq8_nomination: the dequantised codes
+    vg::NomImage sq_nom;               // vg_index_enable_sq8_nomination: the dequantised codes; _from_codes: the score space's offset
+    int64_t sq_nom_rescanned = 0;      // queries whose proof failed and the scan answered, since sq_nom was enabled
     uint8_t *d_sq_tiles = nullptr;
     int32_t sq_groups = 0;  // ceil(dim/16)
     // INT4 codes of a DiskANN segment, row-major n * ceil(dim/2), and the quantizer's lookup table

@@ -1,10 +1,11 @@
 // vg_nominate.hpp — the batched search through a bfloat16 nomination image, shared by the quantizers that have one
-// (vg_index_enable_sq8_nomination, k_sq8_scan.hip; vg_index_enable_pq_nomination and _from_codes, k_pq_nominate.hip).
+// (vg_index_enable_sq8_nomination and _from_codes, k_sq8_scan.hip; vg_index_enable_pq_nomination and _from_codes, k_pq_nominate.hip).
 // The image holds a quantizer's DECODED rows x^ rounded to bfloat16 with their norms (NomImage, vg_internal.hpp); the fused flat
 // search's nomination runs on it (k_flat.hip flat_nominate_bf16: threshold from a row sample, bf16 MFMA GEMM, the 64 best per
 // query), the verify kernels below re-score the nominees with the reference's own arithmetic on the CODES (the quantizer's Row)
 // and prove that no row outside them can enter the k best: outside rows have GEMM score >= tau, and
-// |GEMM score + |q|^2 - exact score| <= Row::eps.  A query whose proof fails is searched again by the caller's exact path.
+// |GEMM score + |q|^2 - offset - exact score| <= Row::eps, offset = the Row's per-query constant between the GEMM's score space and
+// the exact one (zero for an image of the decoded rows).  A query whose proof fails is searched again by the caller's exact path.
 #pragma once
 
 #include <algorithm>
@@ -25,7 +26,7 @@ inline int nominate_sel_k(int k) { return k <= kNomPickMaxK ? 8 : k <= 128 ? 16 
 struct GemmGroup;  // vg_flat_gemm.hpp
 // k_flat.hip
 // cnt queries' nomination for their k best on `img`, *nom and all it points to in `scratch` (flat_nominate_bf16_scratch bytes)
-// (img.from_codes, the PQ nomination from the codes: L2, unfiltered)
+// (img.from_codes, a nomination from the codes: unfiltered; PQ: L2; SQ8, img.scale: L2 and Dot, more than 128 queries)
 size_t flat_nominate_bf16_scratch(int64_t cnt, int64_t n, const NomImage &img, int k);
 int32_t flat_nominate_bf16(vg_index *idx, const NomImage &img, bool dot, const float *queries, int64_t cnt, const uint8_t *mask,
                            int64_t mask_stride, int k, char *scratch, hipStream_t st, ProbeNominated *nom);
@@ -37,7 +38,7 @@ int32_t flat_probe_gemm(vg_index *idx, const float *pair_queries, int64_t pairs,
 // k_sq8_scan.hip
 int32_t launch_sq8_verify(vg_index *idx, const float *queries, int64_t nq, const ProbeNominated &nom, int k, uint32_t *ids, float *scores,
                           int *fail, hipStream_t st);
-bool sq8_nomination_applies(const vg_index *idx, const float *d_queries, int64_t nq, int k);
+bool sq8_nomination_applies(const vg_index *idx, const float *d_queries, int64_t nq, int k, const uint8_t *mask);
 int32_t sq8_nominated_pass(vg_index *idx, const float *q, int64_t nq, int k, const uint8_t *mask, int64_t mask_stride, uint32_t *oid,
                            float *osc, hipStream_t st, std::vector<int> &failed);
 // k_pq_nominate.hip (ascending table sums over the whole segment: mask null, desc false, or the batch does not apply)
@@ -56,6 +57,7 @@ int32_t nom_build(NomImage &img, int64_t n, int dim, int64_t body_bytes, bool fr
     NomImage b;
     b.dim_pad = nom_dim_pad(dim);
     b.from_codes = from_codes;
+    b.body = body_bytes;
     hipError_t e = hipMalloc(reinterpret_cast<void **>(&b.rows), static_cast<size_t>(body_bytes));
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&b.norms), static_cast<size_t>(n) * sizeof(float));
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&b.norm_max), sizeof(float));
@@ -76,8 +78,35 @@ int32_t nom_build(NomImage &img, int64_t n, int dim, int64_t body_bytes, bool fr
 }
 
 // per query: the exact score of its 64 nominated rows (Row::score), the k best by (score, row id), and the proof.
-// Row: dim (the queries' row length), score(q, qv, id) — row id's exact score for query q (qv: its values) — and
-// eps(qn, norm_max) — |s~ + |q|^2 - exact score| for any row, the margin of the proof.
+// Row: dim (the queries' row length), score(q, qv, id) — row id's exact score for query q (qv: its values) —,
+// eps(qn, norm_max) — |s~ + |q|^2 - offset - exact score| for any row, the margin of the proof — and kShifted: whether the GEMM's
+// score space has a per-query constant c, L2 exact ~ s~ + |q|^2 - 2 c, Dot (the scores are -q.x) exact ~ s~ - c; then shift(qv,
+// lane) is the lane's share of c, summed over the wave.  The images of the decoded rows have none (their kernels are what they
+// were); the SQ8 nomination from the codes multiplies centred codes and has c = q.mid (Sq8CodesRow, k_sq8_scan.hip).  A NaN c
+// fails the proof.
+// the Row's score-space constant (see nominated_verify_kernel): its lanes' shares summed over the wave; Row::kShifted false: none
+template <class Row>
+__device__ __forceinline__ float wave_shift(const Row &row, const float *qv, int lane)
+{
+    if constexpr (Row::kShifted) {
+        float c = row.shift(qv, lane);
+        for (int off = 32; off > 0; off >>= 1) c += __shfl_xor(c, off);
+        return c;
+    } else {
+        return 0.0f;
+    }
+}
+// what the k-th exact score is compared with: tau in the exact score's space
+template <class Row, bool DOT>
+__device__ __forceinline__ float shifted_tau(float tau, float qn, float shift)
+{
+    const float t = DOT ? -tau : tau + qn;
+    if constexpr (Row::kShifted)
+        return DOT ? t + shift : t - 2.0f * shift;
+    else
+        return t;
+}
+
 template <class Row, bool DOT>
 __global__ __launch_bounds__(64) void nominated_verify_kernel(Row row, const float *__restrict__ queries, const float *__restrict__ norm_max,
                                                               const uint32_t *__restrict__ cand_ids, const float *__restrict__ cand_scores, int k,
@@ -99,10 +128,11 @@ __global__ __launch_bounds__(64) void nominated_verify_kernel(Row row, const flo
     float qn = 0.0f;
     for (int j = lane; j < dim; j += 64) qn = __builtin_fmaf(qv[j], qv[j], qn);
     for (int off = 32; off > 0; off >>= 1) qn += __shfl_xor(qn, off);
+    const float shift = wave_shift(row, qv, lane);
     const uint64_t kth = readlane_u64(tk.list, k - 1);
     const float tq = thr[q * thr_stride + (thr_stride - 1)];
     const int cnt = counts[q];
-    bool ok = cnt <= cap;  // overflow: rows below the threshold were dropped
+    bool ok = cnt <= cap && shift == shift;  // overflow: rows below the threshold were dropped
     const float tau = cnt > kc ? fminf(tq, cand_scores[q * kc + (kc - 1)]) : tq;
     const bool have_all = tq == INFINITY && cnt <= kc;
     if (ok && !have_all && tau != INFINITY) {
@@ -110,9 +140,9 @@ __global__ __launch_bounds__(64) void nominated_verify_kernel(Row row, const flo
         if (kth == kKeyMax)
             ok = false;
         else if (DOT)
-            ok = key_score(kth, true) > (-tau) + eps;  // outside rows: -q.x >= tau
+            ok = key_score(kth, true) > shifted_tau<Row, true>(tau, qn, shift) + eps;  // outside rows: -q.x >= tau
         else
-            ok = key_score(kth, false) < (tau + qn) - eps;
+            ok = key_score(kth, false) < shifted_tau<Row, false>(tau, qn, shift) - eps;
     }
     if (lane < k) {
         const uint64_t e = tk.list;
@@ -156,17 +186,18 @@ __global__ __launch_bounds__(256) void nominated_verify_sort_kernel(Row row, con
     float qn = 0.0f;
     for (int j = lane; j < dim; j += 64) qn = __builtin_fmaf(qv[j], qv[j], qn);
     for (int off = 32; off > 0; off >>= 1) qn += __shfl_xor(qn, off);
+    const float shift = wave_shift(row, qv, lane);
     const uint64_t kth = k - 1 < n2 ? sortbuf[k - 1] : kKeyMax;
     const float tau = thr[q * thr_stride + (thr_stride - 1)];
-    bool ok = total <= cap;
+    bool ok = total <= cap && shift == shift;
     if (ok && tau != INFINITY) {  // (tau == +Inf: no threshold was set, every accepted row was appended)
         const float eps = row.eps(qn, norm_max[0]);
         if (kth == kKeyMax)
             ok = false;
         else if (DOT)
-            ok = key_score(kth, true) > (-tau) + eps;
+            ok = key_score(kth, true) > shifted_tau<Row, true>(tau, qn, shift) + eps;
         else
-            ok = key_score(kth, false) < (tau + qn) - eps;
+            ok = key_score(kth, false) < shifted_tau<Row, false>(tau, qn, shift) - eps;
     }
     if (lane == 0) fail[q] = ok ? 0 : 1;
 }
