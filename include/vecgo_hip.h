@@ -118,7 +118,8 @@ extern "C" {
  *  vg_rrf_fuse, found by symbol lookup.  Likewise the writes to a resident BM25 index: vg_bm25_create_empty, vg_bm25_update
  *  and vg_bm25_export, found by symbol lookup.  Likewise the PQ batch nomination from the codes:
  *  vg_index_enable_pq_nomination_from_codes and vg_index_pq_nomination_info, found by symbol lookup.  Likewise the SQ8 batch
- *  nomination from the codes: vg_index_enable_sq8_nomination_from_codes and vg_index_sq8_nomination_info, found by symbol lookup. */
+ *  nomination from the codes: vg_index_enable_sq8_nomination_from_codes and vg_index_sq8_nomination_info, found by symbol lookup.  Likewise the test
+ *  entry point vg_int4_scan_plan, found by symbol lookup. */
 #define VG_ABI_MINOR 13
 #define VG_INVALID_ID 0xFFFFFFFFu
 #define VG_STREAM_LEGACY ((void *)1) /* == hipStreamLegacy */
@@ -1089,6 +1090,12 @@ int32_t vg_int4_decode(vg_int4 *iq, const uint8_t *codes, int64_t n, float *out,
  * int4L2DistancePrecomputedAvx512 order (:127-189) for each of the n codes.  out[n]. */
 int32_t vg_int4_l2_distance_batch(vg_int4 *iq, const float *query, const uint8_t *codes, int64_t n,
                                   int32_t precomputed, float *out, void *stream);
+/* Test entry point, read-only: what vg_int4_l2_distance_batch would launch for n > 0 rows whose codes are (1) or are not (0)
+ * 16-byte aligned, on this context's device and under the test hook VG_INT4_SMALL_GRID as it stands.  Nothing runs.
+ * plan[4] = {kernel, waves per workgroup, workgroups, dynamic LDS bytes}; kernel 0: the table scan (dim % 256 == 0, dim <= 1024),
+ * 1: the pair-table scan over rows of whole 128-byte pieces, 2: the pair-table scan with a shorter last piece, 3: a lane per
+ * row (dim % 64 != 0 or unaligned codes).  Both summation orders take the same plan.  Found by symbol lookup (see VG_ABI_MINOR). */
+int32_t vg_int4_scan_plan(vg_int4 *iq, int64_t n, int32_t codes_aligned16, int64_t *plan);
 /* INT4 codes of a DiskANN segment (diskann/segment.go:378-416), n * ceil(dim/2) bytes; scored by
  * vg_search_vamana kind 3.  The quantizer must outlive the index. */
 int32_t vg_index_set_int4_codes(vg_index *idx, vg_int4 *iq, const uint8_t *codes, void *stream);

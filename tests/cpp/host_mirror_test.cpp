@@ -13,6 +13,7 @@
 #include <random>
 
 #include "../../vecgo_amd/csrc/vg_build_plan.hpp"
+#include "../../vecgo_amd/csrc/vg_int4_plan.hpp"
 #include "../../vecgo_amd/csrc/vg_scan_slices.hpp"
 #include "../../vecgo_amd/csrc/vg_walk_chunk.hpp"
 #include "vecgo_hip.hpp"
@@ -87,6 +88,78 @@ static_assert(9376 >= 8 * vg::scan_slices(1, 9376, 256, 4) && 4688 < 8 * vg::sca
               "600 001 rows reach the SQ8 8-wave workgroup (trips 2 / 1), 300 001 do not");
 static_assert(vg::scan_slices(65, 313, 256, 4) == 16, "20 000 rows, 1030 RaBitQ queries in blocks of 16");
 static_assert(vg::scan_slices(150, 313, 256, 4) == 8, "20 000 rows, 600 SQ8 queries in groups of 4");
+
+// the kernel and launch shape of a one-query INT4 distance scan (vg_int4_plan.hpp): arguments (dim, codes 16-byte aligned, rows,
+// CUs, test hook VG_INT4_SMALL_GRID) -> kernel, waves per workgroup, workgroups, dynamic LDS bytes.  tests/test_scan_shapes_cpu.py
+// pins tests/scan_shapes.py to the same lines.  These are the launches vg_int4_l2_distance_batch made before the rule moved
+// into the header: dim % 256 == 0 up to 1024 the table scan on min(ceil(tiles / waves), CUs) workgroups, other dim % 64 == 0
+// the pair-table scan on ceil(tiles / 4), everything else a lane per row in workgroups of 256.
+constexpr bool i4_is(vg::Int4ScanPlan p, int32_t kernel, int32_t waves, int64_t blocks, int64_t lds)
+{
+    return p.kernel == kernel && p.waves == waves && p.blocks == blocks && p.lds == lds;
+}
+#define I4_PLAN(DIM, ALIGNED, N, CUS, HOOK, KERNEL, WAVES, BLOCKS, LDS) \
+    static_assert(i4_is(vg::int4_scan_plan(DIM, ALIGNED, N, CUS, HOOK), vg::KERNEL, WAVES, BLOCKS, LDS), #DIM " " #ALIGNED " " #N " " #CUS " " #HOOK)
+// a tail piece of 32, 64, 96 bytes alone and behind whole pieces; unaligned codes: a lane per row whatever the dimension
+I4_PLAN(64, true, 1000000, 256, false, kI4PairTail, 4, 3907, 0);
+I4_PLAN(64, false, 1000000, 256, false, kI4Row, 4, 3907, 0);
+I4_PLAN(128, true, 1000000, 256, false, kI4PairTail, 4, 3907, 0);
+I4_PLAN(128, false, 1000000, 256, false, kI4Row, 4, 3907, 0);
+I4_PLAN(192, true, 1000000, 256, false, kI4PairTail, 4, 3907, 0);
+I4_PLAN(192, false, 1000000, 256, false, kI4Row, 4, 3907, 0);
+I4_PLAN(320, true, 1000000, 256, false, kI4PairTail, 4, 3907, 0);
+I4_PLAN(320, false, 1000000, 256, false, kI4Row, 4, 3907, 0);
+I4_PLAN(1088, true, 1000000, 256, false, kI4PairTail, 4, 3907, 0);
+I4_PLAN(1088, false, 1000000, 256, false, kI4Row, 4, 3907, 0);
+// whole 128-byte pieces above the table scan's 1024 dimensions
+I4_PLAN(1280, true, 1000000, 256, false, kI4Pair128, 4, 3907, 0);
+I4_PLAN(1280, false, 1000000, 256, false, kI4Row, 4, 3907, 0);
+I4_PLAN(1536, true, 1000000, 256, false, kI4Pair128, 4, 3907, 0);
+I4_PLAN(1536, false, 1000000, 256, false, kI4Row, 4, 3907, 0);
+I4_PLAN(3072, true, 1000000, 256, false, kI4Pair128, 4, 3907, 0);
+I4_PLAN(3072, false, 1000000, 256, false, kI4Row, 4, 3907, 0);
+I4_PLAN(1536, true, 5, 256, true, kI4Pair128, 4, 1, 0);        // (the hook touches the table scan alone)
+I4_PLAN(1536, true, 833, 256, false, kI4Pair128, 4, 4, 0);
+// dim % 64 != 0
+I4_PLAN(2056, true, 1000000, 256, false, kI4Row, 4, 3907, 0);
+I4_PLAN(2056, false, 1000000, 256, false, kI4Row, 4, 3907, 0);
+I4_PLAN(2056, true, 130, 256, true, kI4Row, 4, 1, 0);
+I4_PLAN(95, true, 130, 256, false, kI4Row, 4, 1, 0);
+// the table scan: 12 waves beside the table, 10 at dim 1024; workgroups capped by the CUs, by the hook at 2, and never
+// more than the tiles ask for (3000 rows: 47 tiles; 65 rows: 2)
+I4_PLAN(256, true, 1000000, 256, false, kI4Tab, 12, 256, 126976);
+I4_PLAN(256, false, 1000000, 256, false, kI4Row, 4, 3907, 0);
+I4_PLAN(768, true, 1000000, 256, false, kI4Tab, 12, 256, 159744);
+I4_PLAN(768, false, 1000000, 256, false, kI4Row, 4, 3907, 0);
+I4_PLAN(1024, true, 1000000, 256, false, kI4Tab, 10, 256, 157696);
+I4_PLAN(1024, false, 1000000, 256, false, kI4Row, 4, 3907, 0);
+I4_PLAN(256, true, 1000000, 304, false, kI4Tab, 12, 304, 126976);
+I4_PLAN(256, true, 1000000, 256, true, kI4Tab, 12, 2, 126976);
+I4_PLAN(256, true, 3000, 256, false, kI4Tab, 12, 4, 126976);
+I4_PLAN(256, true, 3000, 256, true, kI4Tab, 12, 2, 126976);
+I4_PLAN(256, true, 65, 256, true, kI4Tab, 12, 1, 126976);
+I4_PLAN(256, true, 1, 0, false, kI4Tab, 12, 1, 126976);
+I4_PLAN(512, true, 1000000, 304, false, kI4Tab, 12, 304, 143360);
+I4_PLAN(512, true, 1000000, 256, true, kI4Tab, 12, 2, 143360);
+I4_PLAN(512, true, 3000, 256, false, kI4Tab, 12, 4, 143360);
+I4_PLAN(512, true, 3000, 256, true, kI4Tab, 12, 2, 143360);
+I4_PLAN(512, true, 65, 256, true, kI4Tab, 12, 1, 143360);
+I4_PLAN(512, true, 1, 0, false, kI4Tab, 12, 1, 143360);
+I4_PLAN(768, true, 1000000, 304, false, kI4Tab, 12, 304, 159744);
+I4_PLAN(768, true, 1000000, 256, true, kI4Tab, 12, 2, 159744);
+I4_PLAN(768, true, 3000, 256, false, kI4Tab, 12, 4, 159744);
+I4_PLAN(768, true, 3000, 256, true, kI4Tab, 12, 2, 159744);
+I4_PLAN(768, true, 65, 256, true, kI4Tab, 12, 1, 159744);
+I4_PLAN(768, true, 1, 0, false, kI4Tab, 12, 1, 159744);
+I4_PLAN(1024, true, 1000000, 304, false, kI4Tab, 10, 304, 157696);
+I4_PLAN(1024, true, 1000000, 256, true, kI4Tab, 10, 2, 157696);
+I4_PLAN(1024, true, 3000, 256, false, kI4Tab, 10, 5, 157696);
+I4_PLAN(1024, true, 3000, 256, true, kI4Tab, 10, 2, 157696);
+I4_PLAN(1024, true, 65, 256, true, kI4Tab, 10, 1, 157696);
+I4_PLAN(1024, true, 1, 0, false, kI4Tab, 10, 1, 157696);
+#undef I4_PLAN
+static_assert(vg::int4_whole_pieces(640) && vg::int4_whole_pieces(1536) && !vg::int4_whole_pieces(544) && !vg::int4_whole_pieces(64),
+              "the body of int4_scan_kernel: row bytes a multiple of 128");
 
 // The (node, level) pairs and the batches of a plan, restated: pair_base is contiguous, every node's pairs are levels
 // 0..min(level, top when its batch began) in order, every batch starts from the entry point and top level that

@@ -5,6 +5,9 @@ can size itself to reach a given trip count and say which kernel it reached.  No
   tile_of       the one-query deal of sq8_scan_kernel, rabitq_scan_kernel and pq_adc_scan_kernel<.., ONCE = true>:
                 trip i of workgroup s, wave w scores tile (i * slices + s) * waves + w
   sq8_wide      vg_search_sq8: one query over at least 8 tiles per slice runs the 8-wave workgroup
+  int4_plan     vecgo_amd/csrc/vg_int4_plan.hpp (pinned the same way): the kernel and launch shape of a one-query INT4 distance scan
+  int4_trips    the tiles a persistent wave of int4_scan_tab_kernel walks: wave w of workgroup b takes tiles b * waves + w,
+                + blocks * waves, ...
 """
 
 SQ8_WAVES, SQ8_WIDE_WAVES, RABITQ_WAVES, ADC_WAVES = 4, 8, 4, 8
@@ -30,6 +33,26 @@ def trips(tiles, slices, waves):
     j, j + step, j + 2 step, ... below `tiles`"""
     step = slices * waves
     return (tiles + step - 1) // step, tiles // step
+
+
+INT4_PAIR_WAVES, INT4_TAB_WAVES, INT4_TAB_STRIDE, INT4_TAB_MAX_DIM, INT4_TAB_LDS, INT4_SMALL_GRID = 4, 12, 144, 1024, 160 * 1024, 2
+
+
+def int4_plan(dim, codes_aligned16, n, cus, small_grid=False):
+    """(kernel, waves, blocks, dynamic LDS bytes) of vg::int4_scan_plan; kernel is "tab", "pair128", "pair_tail" or "row" """
+    tiles = n_tiles(n)
+    if dim % 64 or not codes_aligned16:
+        return "row", 4, (n + 255) // 256, 0
+    if dim % 256 == 0 and dim <= INT4_TAB_MAX_DIM:
+        waves = min(INT4_TAB_WAVES, (INT4_TAB_LDS - dim * 64) // (64 * INT4_TAB_STRIDE))
+        cap = INT4_SMALL_GRID if small_grid else max(cus, 1)
+        return "tab", waves, min((tiles + waves - 1) // waves, cap), dim * 64 + waves * 64 * INT4_TAB_STRIDE
+    return ("pair128" if (dim // 2) % 128 == 0 else "pair_tail"), INT4_PAIR_WAVES, (tiles + INT4_PAIR_WAVES - 1) // INT4_PAIR_WAVES, 0
+
+
+def int4_trips(n, blocks, waves):
+    """(largest, smallest) number of tiles a wave of the table scan walks (0: the wave returns after the barrier)"""
+    return trips(n_tiles(n), blocks, waves)
 
 
 def slices_for(n, cus, wg_per_cu, tile_group=1, units=1):

@@ -79,6 +79,15 @@ def test_int4_scan_persistent_waves_many_tiles(vg, ctx, n, dim):
     mn = (rng.standard_normal(dim) * 0.5).astype(np.float32); df = (rng.random(dim) * 3 + 0.1).astype(np.float32)
     iq = vg.Int4Quantizer(ctx, dim); iq.set_params(mn, df)
     ref = o.Int4Quantizer(dim); ref.set_params(mn, df)
+    # the walk this test is about, from the plan and the device's CUs (tests/test_gpu_int4_scans.py walks 3 and 4 tiles on any device)
+    from tests import scan_shapes as sh
+    cus = ctx.device_info()["compute_units"]
+    plan = iq.scan_plan(n)
+    assert (plan["kernel"], plan["waves"], plan["blocks"], plan["lds"]) == sh.int4_plan(dim, True, n, cus) and plan["kernel"] == "tab"
+    busiest = sh.int4_trips(n, plan["blocks"], plan["waves"])[0]
+    if busiest < 2:
+        pytest.skip(f"{cus} CUs x {plan['waves']} waves hold all {sh.n_tiles(n)} tiles of {n} rows: no wave walks a second tile")
+    assert busiest == -(-sh.n_tiles(n) // (min(cus, -(-sh.n_tiles(n) // plan["waves"])) * plan["waves"])) and (cus != 256 or busiest in (2, 3))
     codes = rng.integers(0, 256, (n, dim // 2), dtype=np.uint8)
     q = (rng.standard_normal(dim) * 2).astype(np.float32)
     assert np.array_equal(bits(iq.l2_distance_batch(q, codes)), bits(ref.l2_distance_batch(q, codes)))

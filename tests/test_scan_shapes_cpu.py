@@ -1,5 +1,5 @@
 """tests/scan_shapes.py against the cases tests/cpp/host_mirror_test.cpp static_asserts for vg::scan_slices (the header and its
-Python restatement must not drift apart), and the dealt mapping on cases small enough to count by hand."""
+Python restatement must not drift apart), the same for vg::int4_scan_plan, and the dealt mapping on cases small enough to count by hand."""
 import pytest
 
 from tests import scan_shapes as sh
@@ -61,6 +61,69 @@ def test_rows_for_on_256_cus(want, wg_per_cu, waves, tile_group, n, tiles, slice
     assert n % 64 not in (0, 63)
     if wg_per_cu == 4:                         # the SQ8 / RaBitQ slices: 600 001 rows reach SQ8's 8-wave workgroup
         assert sh.sq8_wide(1, tiles, slices) == (n == 600_001)
+
+
+# (dim, codes 16-byte aligned, rows, CUs, VG_INT4_SMALL_GRID) -> (kernel, waves, workgroups, dynamic LDS bytes): the same lines as
+# the I4_PLAN static_asserts of host_mirror_test.cpp for vg::int4_scan_plan
+M = 1_000_000
+INT4_PLAN_CASES = [
+    ((64, True, M, 256, False), ("pair_tail", 4, 3907, 0)), ((64, False, M, 256, False), ("row", 4, 3907, 0)),
+    ((128, True, M, 256, False), ("pair_tail", 4, 3907, 0)), ((128, False, M, 256, False), ("row", 4, 3907, 0)),
+    ((192, True, M, 256, False), ("pair_tail", 4, 3907, 0)), ((192, False, M, 256, False), ("row", 4, 3907, 0)),
+    ((320, True, M, 256, False), ("pair_tail", 4, 3907, 0)), ((320, False, M, 256, False), ("row", 4, 3907, 0)),
+    ((1088, True, M, 256, False), ("pair_tail", 4, 3907, 0)), ((1088, False, M, 256, False), ("row", 4, 3907, 0)),
+    ((1280, True, M, 256, False), ("pair128", 4, 3907, 0)), ((1280, False, M, 256, False), ("row", 4, 3907, 0)),
+    ((1536, True, M, 256, False), ("pair128", 4, 3907, 0)), ((1536, False, M, 256, False), ("row", 4, 3907, 0)),
+    ((3072, True, M, 256, False), ("pair128", 4, 3907, 0)), ((3072, False, M, 256, False), ("row", 4, 3907, 0)),
+    ((1536, True, 5, 256, True), ("pair128", 4, 1, 0)), ((1536, True, 833, 256, False), ("pair128", 4, 4, 0)),
+    ((2056, True, M, 256, False), ("row", 4, 3907, 0)), ((2056, False, M, 256, False), ("row", 4, 3907, 0)),
+    ((2056, True, 130, 256, True), ("row", 4, 1, 0)), ((95, True, 130, 256, False), ("row", 4, 1, 0)),
+    ((256, True, M, 256, False), ("tab", 12, 256, 126976)), ((256, False, M, 256, False), ("row", 4, 3907, 0)),
+    ((768, True, M, 256, False), ("tab", 12, 256, 159744)), ((768, False, M, 256, False), ("row", 4, 3907, 0)),
+    ((1024, True, M, 256, False), ("tab", 10, 256, 157696)), ((1024, False, M, 256, False), ("row", 4, 3907, 0)),
+] + [case for dim, waves, lds, few in ((256, 12, 126976, 4), (512, 12, 143360, 4), (768, 12, 159744, 4), (1024, 10, 157696, 5)) for case in (
+    ((dim, True, M, 304, False), ("tab", waves, 304, lds)),
+    ((dim, True, M, 256, True), ("tab", waves, 2, lds)),
+    ((dim, True, 3000, 256, False), ("tab", waves, few, lds)),
+    ((dim, True, 3000, 256, True), ("tab", waves, 2, lds)),
+    ((dim, True, 65, 256, True), ("tab", waves, 1, lds)),
+    ((dim, True, 1, 0, False), ("tab", waves, 1, lds)))]
+
+
+@pytest.mark.parametrize("args,plan", INT4_PLAN_CASES)
+def test_int4_plan_matches_the_header(args, plan):
+    assert sh.int4_plan(*args) == plan
+
+
+def test_int4_plan_cases_are_the_static_asserts():
+    """every I4_PLAN line of host_mirror_test.cpp is a case above and the other way round: neither list can grow alone"""
+    import pathlib
+    import re
+    src = (pathlib.Path(__file__).resolve().parent / "cpp" / "host_mirror_test.cpp").read_text()
+    names = {"kI4Tab": "tab", "kI4Pair128": "pair128", "kI4PairTail": "pair_tail", "kI4Row": "row"}
+    lines = re.findall(r"^I4_PLAN\((\d+), (true|false), (\d+), (\d+), (true|false), (\w+), (\d+), (\d+), (\d+)\);", src, flags=re.M)
+    asserted = {((int(d), a == "true", int(n), int(c), h == "true"), (names[k], int(w), int(b), int(l))) for d, a, n, c, h, k, w, b, l in lines}
+    assert asserted == set(INT4_PLAN_CASES) and len(lines) == len(INT4_PLAN_CASES)
+
+
+def test_int4_scan_plan_is_exported_and_bound():
+    import ctypes as C
+
+    import vecgo_amd
+    from vecgo_amd import _lib
+    lib = _lib.load()
+    assert "vg_int4_scan_plan" in _lib.declared_symbols() and hasattr(lib, "vg_int4_scan_plan")
+    assert lib.vg_int4_scan_plan(None, C.c_int64(1), 1, None) == -1           # a NULL quantizer is a status, not a crash
+    assert callable(vecgo_amd.Int4Quantizer.scan_plan) and vecgo_amd.Int4Quantizer.SCAN_KERNELS == ("tab", "pair128", "pair_tail", "row")
+    assert lib.vg_debug_set_hook(b"VG_INT4_SMALL_GRID", 0) == 0               # the hook's name is known
+
+
+def test_int4_trips_by_hand():
+    # 2 workgroups of 12 waves: 24 persistent waves, wave j walks tiles j, j + 24, ...
+    assert sh.int4_trips(64 * 24, 2, 12) == (1, 1) and sh.int4_trips(64 * 24 + 1, 2, 12) == (2, 1)
+    assert sh.int4_trips(64 * 72, 2, 12) == (3, 3) and sh.int4_trips(4700, 2, 12) == (4, 3) and sh.int4_trips(3900, 2, 10) == (4, 3)
+    assert sh.int4_trips(5 * 64, 1, 12) == (1, 0)                           # idle waves
+    assert sh.tile_of(3, 1, 11, 2, 12) == 95                                # trip 3 of the last wave: tile 3 * 24 + 12 + 11
 
 
 @pytest.mark.parametrize("cus", [8, 64, 120, 228, 256, 304])

@@ -723,6 +723,15 @@ class Int4Quantizer:
         """L2Distance (int4.go:133-147) of one query against each of n codes."""
         return self._dist(query, codes, 1, out, stream)
 
+    SCAN_KERNELS = ("tab", "pair128", "pair_tail", "row")   # Int4ScanKernel, csrc/vg_int4_plan.hpp
+
+    def scan_plan(self, n: int, codes_aligned16: bool = True) -> dict:
+        """What l2_distance / l2_distance_batch would launch over n rows (vg_int4_scan_plan; nothing runs): the kernel's name,
+        waves per workgroup, workgroups and dynamic LDS bytes."""
+        plan = (C.c_int64 * 4)()
+        check(self._lib.vg_int4_scan_plan(self._h, C.c_int64(n), C.c_int32(1 if codes_aligned16 else 0), plan))
+        return {"kernel": self.SCAN_KERNELS[plan[0]], "waves": int(plan[1]), "blocks": int(plan[2]), "lds": int(plan[3])}
+
 
 def hamming_batch(ctx: Context, a, codes, out=None, stream=None):
     """simd.Hamming (kernels.go:71) of one byte string against n contiguous ones."""

@@ -4,6 +4,7 @@
 #include <type_traits>
 
 #include "vg_device.hpp"
+#include "vg_int4_plan.hpp"
 #include "vg_internal.hpp"
 #include "vg_search.hpp"
 
@@ -203,8 +204,6 @@ __global__ __launch_bounds__(256) void int4_l2_precomputed_kernel(const float *_
 // one packed-fp32 instruction on the pair with scalar-loaded diff / min / query: 2 - 2.5 vector instructions per
 // dimension.  Accumulators and their order are the kernels' above: PRE — both 16-element halves of a 32-block into
 // sum[]; batch order — sub-blocks 0, 1 of a 64-block into s1, 2, 3 into s2, s1 += s2 at the end.
-constexpr int kI4Waves = 4;
-constexpr int kI4Stride = 144;  // LDS bytes per staged row piece (128 + 16)
 template <bool PRE>
 __global__ __launch_bounds__(kI4Waves * 64) void int4_scan_kernel(const float *__restrict__ query,
                                                                   const uint8_t *__restrict__ codes, int64_t n, int dim,
@@ -261,7 +260,7 @@ __global__ __launch_bounds__(kI4Waves * 64) void int4_scan_kernel(const float *_
     };
     // rows past n re-read row n - 1 (their result is not stored); loads are unguarded (a guarded load makes hipcc
     // wait for the previous one at the join)
-    if ((row_bytes & 127) == 0) {
+    if (int4_whole_pieces(row_bytes)) {
         // whole 128-byte pieces: 8 lanes per row, the next piece's lines in flight while this one is scored
         const int r = lane >> 3, part = lane & 7;
         const uint8_t *src[8];
@@ -377,9 +376,6 @@ __device__ __forceinline__ void i4_issue_word(I4Vals8 &x, uint32_t w, uint32_t b
 #define VG_I4_T(var)
 #define VG_I4_TACC(acc, a, b)
 #endif
-constexpr int kI4TabWaves = 12;
-constexpr int kI4TabStride = 144;
-constexpr int kI4TabMaxDim = 1024;
 
 // the 16 code bytes of a 32-element block, read from the wave's staging buffer under the same in-order accounting as
 // the lookups ("memory": the staging writes before it stay before it, the next piece's writes stay after the last one)
@@ -742,32 +738,38 @@ VG_API int32_t vg_int4_l2_distance_batch(vg_int4 *iq, const float *query, const 
     VG_TRY(q.init(query, static_cast<size_t>(iq->dim), st));
     VG_TRY(c.init(codes, static_cast<size_t>(n * cs), st, vg::kAnyAlign));
     VG_TRY(o.init(out, static_cast<size_t>(n), st));
-    const bool scan = iq->dim % 64 == 0 && vg::aligned16(c.ptr);
-    const unsigned scan_blocks = static_cast<unsigned>(((n + 63) / 64 + vg::kI4Waves - 1) / vg::kI4Waves);
+    // the kernel and its launch shape: vg_int4_plan.hpp (the rule exists there alone; vg_int4_scan_plan shows it to a test)
+    const vg::Int4ScanPlan plan = vg::int4_scan_plan(iq->dim, vg::aligned16(c.ptr), n, iq->ctx->compute_units, vg::hook(vg::kHookInt4SmallGrid));
+    const dim3 grid(static_cast<unsigned>(plan.blocks)), block(plan.waves * 64);
     vg::ProfScope prof(iq->ctx, "int4_scan", st);
-    if (scan && iq->dim % 256 == 0 && iq->dim <= vg::kI4TabMaxDim) {
-        const int waves = static_cast<int>(std::min<int64_t>(vg::kI4TabWaves, (160 * 1024 - static_cast<int64_t>(iq->dim) * 64) / (64 * vg::kI4TabStride)));
-        const size_t lds = static_cast<size_t>(iq->dim) * 64 + static_cast<size_t>(waves) * 64 * vg::kI4TabStride;
-        const int64_t tiles = (n + 63) / 64;
-        const unsigned blocks = static_cast<unsigned>(std::min<int64_t>((tiles + waves - 1) / waves, std::max(iq->ctx->compute_units, 1)));
+    if (plan.kernel == vg::kI4Tab) {
         auto kern = precomputed ? vg::int4_scan_tab_kernel<true> : vg::int4_scan_tab_kernel<false>;
         VG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   static_cast<int>(lds)));
-        VG_LAUNCH(kern, dim3(blocks), dim3(waves * 64), lds, st, q.ptr, c.ptr, n, iq->dim, iq->d_min, iq->d_diff,
-                  o.ptr);
-    } else if (scan && precomputed)
-        VG_LAUNCH(vg::int4_scan_kernel<true>, dim3(scan_blocks), dim3(vg::kI4Waves * 64), 0, st, q.ptr, c.ptr, n, iq->dim,
-                  iq->d_min, iq->d_diff, o.ptr);
-    else if (scan)
-        VG_LAUNCH(vg::int4_scan_kernel<false>, dim3(scan_blocks), dim3(vg::kI4Waves * 64), 0, st, q.ptr, c.ptr, n, iq->dim,
-                  iq->d_min, iq->d_diff, o.ptr);
+                                   static_cast<int>(plan.lds)));
+        VG_LAUNCH(kern, grid, block, static_cast<size_t>(plan.lds), st, q.ptr, c.ptr, n, iq->dim, iq->d_min, iq->d_diff, o.ptr);
+    } else if (plan.kernel != vg::kI4Row && precomputed)
+        VG_LAUNCH(vg::int4_scan_kernel<true>, grid, block, 0, st, q.ptr, c.ptr, n, iq->dim, iq->d_min, iq->d_diff, o.ptr);
+    else if (plan.kernel != vg::kI4Row)
+        VG_LAUNCH(vg::int4_scan_kernel<false>, grid, block, 0, st, q.ptr, c.ptr, n, iq->dim, iq->d_min, iq->d_diff, o.ptr);
     else if (precomputed)
-        VG_LAUNCH(vg::int4_l2_precomputed_kernel, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, st, q.ptr,
-                  c.ptr, n, iq->dim, iq->d_table, o.ptr);
+        VG_LAUNCH(vg::int4_l2_precomputed_kernel, grid, block, 0, st, q.ptr, c.ptr, n, iq->dim, iq->d_table, o.ptr);
     else
-        VG_LAUNCH(vg::int4_l2_batch_kernel, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, st, q.ptr, c.ptr,
-                  n, iq->dim, iq->d_min, iq->d_diff, o.ptr);
+        VG_LAUNCH(vg::int4_l2_batch_kernel, grid, block, 0, st, q.ptr, c.ptr, n, iq->dim, iq->d_min, iq->d_diff, o.ptr);
     VG_TRY(o.finish());
+    return VG_OK;
+}
+
+// what vg_int4_l2_distance_batch would launch for n rows (read-only, nothing runs): plan[4] = {kernel (0 tab, 1 pair128,
+// 2 pair_tail, 3 row: Int4ScanKernel), waves per workgroup, workgroups, dynamic LDS bytes}
+VG_API int32_t vg_int4_scan_plan(vg_int4 *iq, int64_t n, int32_t codes_aligned16, int64_t *plan)
+{
+    VG_CHECK(iq && plan, VG_ERR_INVALID_ARG, "vg_int4_scan_plan: NULL quantizer or plan");
+    VG_CHECK(n > 0, VG_ERR_INVALID_ARG, "vg_int4_scan_plan: n must be positive");
+    const vg::Int4ScanPlan p = vg::int4_scan_plan(iq->dim, codes_aligned16 != 0, n, iq->ctx->compute_units, vg::hook(vg::kHookInt4SmallGrid));
+    plan[0] = p.kernel;
+    plan[1] = p.waves;
+    plan[2] = p.blocks;
+    plan[3] = p.lds;
     return VG_OK;
 }
 

@@ -328,7 +328,8 @@ static const char *const kHookNames[kHookCount] = {"VG_FLAT_NO_SMALL_TILE", "VG_
                                                    "VG_FLAT_BIG_TILE_2", "VG_FLAT_BIG_EARLY_B", "VG_PQ_NOM_ALWAYS", "VG_SQ8_NOM_CODES_ALWAYS", "VG_KM_NO_RANGES", "VG_NO_CAND_REPLAY",
                                                    "VG_VAMANA_SMALL_SCRATCH", "VG_FLAT_RESCORE_SAMPLE", "VG_PTHR_FORCE_HIST",
                                                    "VG_WALK_SMALL_SCRATCH", "VG_FLAT_NO_SPLIT", "VG_FLAT_NO_SCREEN", "VG_FLAT_SCREEN_FAIL",
-                                                   "VG_FLAT_F32_SAMPLE", "VG_PREFILTER_SMALL_SCRATCH", "VG_BM25_SMALL_SCRATCH"};
+                                                   "VG_FLAT_F32_SAMPLE", "VG_PREFILTER_SMALL_SCRATCH", "VG_BM25_SMALL_SCRATCH",
+                                                   "VG_INT4_SMALL_GRID"};
 static void hooks_from_env()
 {
     for (int h = 0; h < kHookCount; h++) {
