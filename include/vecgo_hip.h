@@ -1130,7 +1130,9 @@ enum { VG_SCAN_F32 = 0, VG_SCAN_PQ = 1, VG_SCAN_SQ8 = 2 };
  * only, one top-k by (score, row id).  With at most one partition it is vg_search_flat /
  * vg_search_pq_adc / vg_search_sq8.  k <= 512 (pages of 64 results), nprobes <= 64.  Equal centroid distances: the
  * reference's selection loop (kmeans.go:255-269, taken for nprobes <= partitions / 4 && nprobes < 16) is replayed, so the
- * probed partitions are the reference's also among duplicated centroids; its full sort leaves ties unpinned (by id here). */
+ * probed partitions are the reference's also among duplicated centroids; its full sort leaves ties unpinned (by id here).
+ * VG_SCAN_PQ takes any m: a table beyond one LDS image (m >= 144, e.g. dim 1536 at the writer's dim / 8 = 192) is walked in
+ * 96 KiB chunks, same limits, same ids and score bits.  (An unpartitioned index is vg_search_pq_adc, whose k <= 64 for m > 96.) */
 int32_t vg_search_flat_probed(vg_index *idx, const float *queries, int64_t nq, int32_t k, int32_t nprobes,
                               int32_t scan, uint32_t *ids, float *scores, void *stream);
 /* flat.Segment.Search with `filter segment.Filter` set (flat/segment.go:447): a row whose filter.Matches(rowID) is false
@@ -1139,7 +1141,8 @@ int32_t vg_search_flat_probed(vg_index *idx, const float *queries, int64_t nq, i
  * one partition.  mask: bit i of byte i/8 set = filter.Matches(i) (tombstones are the caller's: clear their bits); query q
  * reads mask + q * mask_stride (0 = one mask for the batch, else >= ceil(rows/8)); NULL = vg_search_flat_probed.  Block
  * skipping by field statistics (MatchesBlock, :614-628) only ever skips rows no filter bit is set for.  k <= 512,
- * nprobes <= 64.  (VG_ABI_MINOR 4.) */
+ * nprobes <= 64; VG_SCAN_PQ with any m, partitioned or not (a table beyond one LDS image is walked in chunks; a 64-row tile
+ * the filter leaves nothing of is not read).  (VG_ABI_MINOR 4.) */
 int32_t vg_search_flat_filtered(vg_index *idx, const float *queries, int64_t nq, int32_t k, int32_t nprobes,
                                 int32_t scan, const uint8_t *mask, int64_t mask_stride, uint32_t *ids, float *scores,
                                 void *stream);
@@ -1172,8 +1175,9 @@ int32_t vg_search_flat_filtered(vg_index *idx, const float *queries, int64_t nq,
  * NaN EXACT scores inside step 2's heap are dropped by the filter and the rest are ordered by key.
  * Refusals, each decided before any work: max_results > 16384 VG_ERR_UNSUPPORTED (the number in the message); Hamming
  * VG_ERR_UNSUPPORTED; nprobes > 64 VG_ERR_UNSUPPORTED; a scan kind the index has no data for, or rerank != 0 without fp32
- * rows, VG_ERR_NOT_READY; a PQ of other than 256 centroids VG_ERR_UNSUPPORTED, as vg_search_flat_probed(VG_SCAN_PQ); a PQ
- * table that does not fit one LDS image (m > 96) VG_ERR_UNSUPPORTED.  (Present when the symbol is: see VG_ABI_MINOR.) */
+ * rows, VG_ERR_NOT_READY; a PQ of other than 256 centroids VG_ERR_UNSUPPORTED, as vg_search_flat_probed(VG_SCAN_PQ).  A PQ
+ * table that does not fit one LDS image (m > 96) is served: its scan walks the table in 96 KiB chunks for 32 tiles of rows at a
+ * time, the same scores, lists and passes.  (Present when the symbol is: see VG_ABI_MINOR.) */
 int32_t vg_search_flat_probed_threshold(vg_index *idx, const float *queries, int64_t nq, const float *thresholds,
                                         int32_t max_results, int32_t nprobes, int32_t scan /* VG_SCAN_* */, int32_t rerank,
                                         const uint8_t *mask, int64_t mask_stride,
@@ -1228,7 +1232,9 @@ int32_t vg_segment_open_flat(vg_ctx *ctx, const void *image, int64_t size, int32
  * follows the segment (SQ8 codes: L2Distance / DotProduct by metric; PQ: table lookups, L2 segments
  * only — see vg_segment.hip; else fp32 rows) and, when the segment has more than one IVF partition,
  * only the nprobes closest partitions are scanned (:727-744; nprobes <= 0 means 1).  k <= 512 and
- * nprobes <= 64 on the partitioned path.
+ * nprobes <= 64 on the partitioned path.  A PQ segment of any m is searched, filtered and threshold-searched
+ * (vg_segment_search_filtered, vg_segment_search_threshold); only the unpartitioned, unfiltered search of a
+ * table beyond one LDS image (m > 96) keeps vg_search_pq_adc's k <= 64.
  * On a DiskANN segment: diskann.Segment.Search (diskann/segment.go:487-706) = vg_search_vamana with
  * the distFn of the segment's quantization (RaBitQ, else PQ, else INT4, else fp32); nprobes is unused,
  * like the search-list size the reference computes and never reads. */

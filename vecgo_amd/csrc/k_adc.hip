@@ -31,6 +31,7 @@
 #include <algorithm>
 
 #include "vg_adc_row.hpp"
+#include "vg_adc_wide.hpp"
 #include "vg_device.hpp"
 #include "vg_internal.hpp"
 #include "vg_cand_replay.hpp"
@@ -588,13 +589,21 @@ __global__ __launch_bounds__(kAdcThreads) void pq_adc_probe_kernel(
                              partial + (q * split + y) * k);
 }
 
+static int32_t launch_probe_scan_adc_wide(const vg_index *idx, const float *tables, const uint32_t *probes, const uint32_t *part_off,
+                                          int64_t nq, int np, int split, int k, uint64_t *partial, const uint64_t *min_keys, bool desc,
+                                          const uint8_t *mask, int64_t mask_stride, hipStream_t st);
+
 int32_t launch_probe_scan_adc(const vg_index *idx, const float *tables, const uint32_t *probes, const uint32_t *part_off,
                               int64_t nq, int np, int split, int k, uint64_t *partial, const uint64_t *min_keys, bool desc,
                               const uint8_t *mask, int64_t mask_stride, hipStream_t st)
 {
     const vg_pq *pq = idx->pq;
-    // a table that fits LDS next to the scan kernel's buffers, k <= 64: the pipelined scan kernel over the probed ranges
     const size_t scan_lds = static_cast<size_t>(lut_image_words(pq->m)) * sizeof(float) + kAdcBuf * sizeof(uint64_t) + sizeof(AdcShared);
+    const size_t lds = static_cast<size_t>(lut_image_words(pq->m)) * sizeof(float) + kAdcWaves * 64 * sizeof(uint64_t) + 64;
+    // a table neither kernel below holds in LDS (m >= 144): walked in chunks (test hook kHookAdcWideAlways: whatever m is)
+    if (lds > 160 * 1024 || hook(kHookAdcWideAlways))
+        return launch_probe_scan_adc_wide(idx, tables, probes, part_off, nq, np, split, k, partial, min_keys, desc, mask, mask_stride, st);
+    // a table that fits LDS next to the scan kernel's buffers, k <= 64: the pipelined scan kernel over the probed ranges
     if (k <= 64 && scan_lds <= 160 * 1024 && !hook(kHookProbeNoGroup)) {
         auto pick = [&](auto masked_tag) {
             constexpr bool M = decltype(masked_tag)::value;
@@ -615,7 +624,6 @@ int32_t launch_probe_scan_adc(const vg_index *idx, const float *tables, const ui
         }
         return VG_OK;
     }
-    const size_t lds = static_cast<size_t>(lut_image_words(pq->m)) * sizeof(float) + kAdcWaves * 64 * sizeof(uint64_t) + 64;
     VG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(pq_adc_probe_kernel),
                                hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
     for (int64_t q0 = 0; q0 < nq; q0 += 65535) {
@@ -661,88 +669,38 @@ static int32_t launch_scan(const vg_index *idx, const float *tables, int64_t nq,
 }
 
 // ---------------------------------------------------------------------------------------------
-// m above what one LDS image holds (fp32 table of m KiB: m > 96 with the top-k buffers; d = 1536 at 8 dims per
-// sub-quantizer is m = 192).  The table is walked in CHUNKS of up to 6 full groups (96 KiB): a workgroup takes a
-// batch of kWideTiles tiles per wave, keeps their 16 slot accumulators in registers, and for each chunk stages
-// that chunk's table rows into LDS and adds the chunk's groups for every tile of the batch.  Every row still
-// adds its groups in ascending order into the same 16 accumulators, so the sum is pqAdcLookupAvx512's.  The
-// table is re-staged once per batch (m KiB from L2 against kAdcWaves * kWideTiles * 64 * m bytes of codes: a
-// quarter of the code traffic at 4 tiles per wave).  k <= 64.
+// m above what one LDS image holds (m > 96 with the top-k buffers): the table walked in 96 KiB chunks for a batch of kWideTiles
+// tiles per wave — adc_wide_walk, vg_adc_wide.hpp.  k <= 64 per launch.
 // ---------------------------------------------------------------------------------------------
-constexpr int kWideTiles = 4;
-constexpr int kWideChunkGroups = 6;
-constexpr int kWideChunkWords = (kWideChunkGroups / 2) * 8192;
+constexpr size_t kWideLdsBytes = kWideLdsWords * sizeof(float) + kAdcWaves * 64 * sizeof(uint64_t) + 64;  // the walker's, then wg_rank_merge's
 
+// the unfiltered whole segment: workgroup (query q, slice s) as in pq_adc_scan_kernel
 __global__ __launch_bounds__(kAdcThreads) void pq_adc_scan_wide_kernel(
     const uint4 *__restrict__ tiles, int64_t n_rows, int64_t n_tiles, int m, int groups,
     const float *__restrict__ tables, int slices, int nq, int k, uint64_t *__restrict__ partial)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    float *lut = reinterpret_cast<float *>(smem);                  // one chunk: [pair][c][32]
-    float *lut_tail = lut + kWideChunkWords;                       // m % 16 natural rows [j][c]
-    uint64_t *buf = reinterpret_cast<uint64_t *>(lut_tail + 15 * 256);
+    float *lut = reinterpret_cast<float *>(smem);
+    uint64_t *buf = reinterpret_cast<uint64_t *>(lut + kWideLdsWords);
     const int b = blockIdx.x;
     const int xcd = b & 7, o = b >> 3;
     const int q = o % nq;
     const int s = (o / nq) * 8 + xcd;
     const int64_t t0 = n_tiles * s / slices, t1 = n_tiles * (s + 1) / slices;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, rot = lane & 15;
-    const int gfull = m >> 4, tail = m & 15;
-    const int nchunks = gfull ? (gfull + kWideChunkGroups - 1) / kWideChunkGroups : 1;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const float *image = tables + static_cast<int64_t>(q) * lut_image_words(m);
-    const int tail_word = ((gfull + 1) >> 1) * 8192;
     WaveTopK wtk;
     wtk.init(k);
     for (int64_t b0 = t0; b0 < t1; b0 += static_cast<int64_t>(kAdcWaves) * kWideTiles) {
-        float acc[kWideTiles][16];
+        bool want[kWideTiles];
+        float total[kWideTiles];
 #pragma unroll
-        for (int tb = 0; tb < kWideTiles; tb++)
-#pragma unroll
-            for (int l = 0; l < 16; l++) acc[tb][l] = 0.0f;
-        for (int c = 0; c < nchunks; c++) {
-            const int g0 = c * kWideChunkGroups;
-            const int gc = gfull - g0 < kWideChunkGroups ? gfull - g0 : kWideChunkGroups;
-            __syncthreads();  // the previous chunk's lookups are done
-            {
-                const int words = ((gc + 1) >> 1) * 8192;
-                const float4 *src = reinterpret_cast<const float4 *>(image + (g0 >> 1) * 8192);
-                float4 *dst = reinterpret_cast<float4 *>(lut);
-                for (int i = tid; i < words / 4; i += kAdcThreads) dst[i] = src[i];
-                if (c == nchunks - 1 && tail) {
-                    const float4 *ts = reinterpret_cast<const float4 *>(image + tail_word);
-                    float4 *td = reinterpret_cast<float4 *>(lut_tail);
-                    for (int i = tid; i < tail * 64; i += kAdcThreads) td[i] = ts[i];
-                }
-            }
-            __syncthreads();
-#pragma unroll
-            for (int tb = 0; tb < kWideTiles; tb++) {
-                const int64_t tile = b0 + static_cast<int64_t>(tb) * kAdcWaves + wave;
-                if (tile < t1) {
-                    const uint4 *tp = tiles + (tile * groups) * 64 + lane;
-                    for (int g = 0; g < gc; g++) {
-                        const uint4 cw = tp[(g0 + g) * 64];
-#pragma unroll
-                        for (int sl = 0; sl < 16; sl++)
-                            acc[tb][sl] = acc[tb][sl] + lut[((g >> 1) * 256 + code_byte(cw, sl)) * 32 + (g & 1) * 16 + ((sl + rot) & 15)];
-                    }
-                }
-            }
-        }
+        for (int tb = 0; tb < kWideTiles; tb++) want[tb] = b0 + static_cast<int64_t>(tb) * kAdcWaves + wave < t1;
+        adc_wide_walk<kAdcWaves>(tiles, groups, m, image, lut, b0, want, tid, total);
 #pragma unroll
         for (int tb = 0; tb < kWideTiles; tb++) {
-            const int64_t tile = b0 + static_cast<int64_t>(tb) * kAdcWaves + wave;
-            uint64_t key = kKeyMax;
-            if (tile < t1) {
-                float total = reduce16_regs(acc[tb]);
-                if (tail) {
-                    const uint4 cw = tiles[(tile * groups + gfull) * 64 + lane];
-                    for (int l = 0; l < tail; l++) total = total + lut_tail[l * 256 + code_byte(cw, l)];
-                }
-                const int64_t row = tile * 64 + lane;
-                if (row < n_rows) key = make_key(total, static_cast<uint32_t>(row), false);
-            }
-            wtk.offer(key, lane);
+            const int64_t row = (b0 + static_cast<int64_t>(tb) * kAdcWaves + wave) * 64 + lane;
+            wtk.offer(want[tb] && row < n_rows ? make_key(total[tb], static_cast<uint32_t>(row), false) : kKeyMax, lane);
         }
     }
     __syncthreads();
@@ -750,10 +708,59 @@ __global__ __launch_bounds__(kAdcThreads) void pq_adc_scan_wide_kernel(
     wg_rank_merge<kAdcWaves>(wtk, buf, reinterpret_cast<int *>(buf + kAdcWaves * 64), wave, lane, tid, k, out);
 }
 
+// pq_adc_probe_kernel over such a table (same arguments, same grid): the tiles covering each probed range in batches, a tile
+// outside the range or that the filter leaves no row of not wanted
+__global__ __launch_bounds__(kAdcThreads) void pq_adc_probe_wide_kernel(
+    const uint4 *__restrict__ tiles, int64_t n_rows, int m, int groups, const float *__restrict__ tables,
+    const uint32_t *__restrict__ probes, const uint32_t *__restrict__ part_off, int np, int split, int k,
+    uint64_t *__restrict__ partial, const uint64_t *__restrict__ min_keys, bool desc, const uint8_t *__restrict__ mask,
+    int64_t mask_stride)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    float *lut = reinterpret_cast<float *>(smem);
+    uint64_t *buf = reinterpret_cast<uint64_t *>(lut + kWideLdsWords);
+    const int y = blockIdx.x;
+    const int64_t q = blockIdx.y;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const float *image = tables + q * lut_image_words(m);
+    const uint8_t *mq = mask ? mask + q * mask_stride : nullptr;  // filter.Matches (segment.go:631-635)
+    const uint64_t floor_key = min_keys ? min_keys[q] : 0;       // paged results (k > 64)
+    WaveTopK wtk;
+    wtk.init(k);
+    for (int j = y; j < np; j += split) {
+        const uint32_t p = probes[q * np + j];
+        const int64_t R0 = part_off[p], R1 = part_off[p + 1];
+        const int64_t tt0 = R0 >> 6, tt1 = (R1 + 63) >> 6;
+        for (int64_t b0 = tt0; b0 < tt1; b0 += static_cast<int64_t>(kAdcWaves) * kWideTiles) {
+            bool want[kWideTiles], live[kWideTiles];
+            float total[kWideTiles];
+#pragma unroll
+            for (int tb = 0; tb < kWideTiles; tb++) {
+                const int64_t tile = b0 + static_cast<int64_t>(tb) * kAdcWaves + wave;
+                const int64_t row = tile * 64 + lane;
+                live[tb] = tile < tt1 && row >= R0 && row < R1 && row < n_rows && mask_bit(mq, row);
+                want[tb] = __any(live[tb]) != 0;
+            }
+            adc_wide_walk<kAdcWaves>(tiles, groups, m, image, lut, b0, want, tid, total);
+#pragma unroll
+            for (int tb = 0; tb < kWideTiles; tb++) {
+                if (!want[tb]) continue;
+                const int64_t row = (b0 + static_cast<int64_t>(tb) * kAdcWaves + wave) * 64 + lane;
+                uint64_t key = live[tb] ? make_key(total[tb], static_cast<uint32_t>(row), desc) : kKeyMax;
+                if (min_keys && key <= floor_key) key = kKeyMax;
+                wtk.offer(key, lane);
+            }
+        }
+    }
+    __syncthreads();
+    wg_rank_merge<kAdcWaves>(wtk, buf, reinterpret_cast<int *>(buf + kAdcWaves * 64), wave, lane, tid, k,
+                             partial + (q * split + y) * k);
+}
+
 static int32_t launch_scan_wide(const vg_index *idx, const float *tables, int64_t nq, int k, int slices,
                                 uint64_t *partial, hipStream_t st)
 {
-    const size_t lds = (kWideChunkWords + 15 * 256) * sizeof(float) + kAdcWaves * 64 * sizeof(uint64_t) + 64;
+    const size_t lds = kWideLdsBytes;
     VG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(pq_adc_scan_wide_kernel),
                                hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
     const int64_t max_q = (1ll << 30) / slices;
@@ -763,6 +770,24 @@ static int32_t launch_scan_wide(const vg_index *idx, const float *tables, int64_
         VG_LAUNCH(pq_adc_scan_wide_kernel, dim3(static_cast<unsigned>(cnt * slices)), dim3(kAdcThreads), lds, st,
                   reinterpret_cast<const uint4 *>(idx->d_pq_tiles), idx->n, idx->n_tiles, idx->pq->m, idx->pq_groups,
                   tables + q0 * lut_image_words(idx->pq->m), slices, static_cast<int>(cnt), k, partial + q0 * slices * k);
+    }
+    return VG_OK;
+}
+
+static int32_t launch_probe_scan_adc_wide(const vg_index *idx, const float *tables, const uint32_t *probes, const uint32_t *part_off,
+                                          int64_t nq, int np, int split, int k, uint64_t *partial, const uint64_t *min_keys, bool desc,
+                                          const uint8_t *mask, int64_t mask_stride, hipStream_t st)
+{
+    const vg_pq *pq = idx->pq;
+    VG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(pq_adc_probe_wide_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                               static_cast<int>(kWideLdsBytes)));
+    for (int64_t q0 = 0; q0 < nq; q0 += 65535) {
+        const int64_t cnt = nq - q0 < 65535 ? nq - q0 : 65535;
+        ProfScope prof(idx->ctx, "pq_adc_probe", st);
+        VG_LAUNCH(pq_adc_probe_wide_kernel, dim3(static_cast<unsigned>(split), static_cast<unsigned>(cnt)), dim3(kAdcThreads),
+                  kWideLdsBytes, st, reinterpret_cast<const uint4 *>(idx->d_pq_tiles), idx->n, pq->m, idx->pq_groups,
+                  tables + q0 * lut_image_words(pq->m), probes + q0 * np, part_off, np, split, k, partial + q0 * split * k,
+                  min_keys ? min_keys + q0 : nullptr, desc, mask ? mask + q0 * mask_stride : nullptr, mask_stride);
     }
     return VG_OK;
 }

@@ -696,8 +696,9 @@ static int32_t probed_whole_shortcut(const ProbedCall &c, bool *done)
         return c.rescan(failed);
     }
     // A filtered PQ scan of the whole segment, k <= 64 and a table that fits LDS: the pipelined scan of vg_search_pq_adc with
-    // the filter where keys are made (the probe kernel is the plain loop, twice its time)
-    if (c.scan == VG_SCAN_PQ && c.k <= 64 && idx->pq->m <= 96)
+    // the filter where keys are made (the probe kernel is the plain loop, twice its time; a wider table, and test hook
+    // kHookAdcWideAlways: the chunked probe kernel over the 64 pieces below)
+    if (c.scan == VG_SCAN_PQ && c.k <= 64 && idx->pq->m <= 96 && !vg::hook(vg::kHookAdcWideAlways))
         return vg::pq_adc_search_masked(idx, c.q, c.nq, c.k, c.mk, c.mask_stride, c.dot, c.oid, c.osc, c.st);
     *done = false;
     return VG_OK;

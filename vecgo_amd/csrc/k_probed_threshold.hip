@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "vg_adc_row.hpp"
+#include "vg_adc_wide.hpp"
 #include "vg_cand_replay.hpp"
 #include "vg_device.hpp"
 #include "vg_exact.hpp"
@@ -29,7 +30,7 @@
 namespace vg {
 
 constexpr int kPthrBins = 65536;        // the top 16 bits of a key
-constexpr size_t kPthrLutMax = 96 * 1024;  // a PQ table image the scan holds in LDS (m <= 96 at 256 centroids)
+constexpr size_t kPthrLutMax = 96 * 1024;  // a PQ table image the scan holds in LDS (m <= 96 at 256 centroids); beyond: pthr_scan_wide_kernel
 enum PthrMode { kPthrThr = 0, kPthrHist = 1, kPthrBin = 2 };
 
 // the query of slot s of a launch (qmap null: s)
@@ -318,12 +319,108 @@ static int32_t launch_pthr(const S &sc, int mode, size_t lds, const PthrArgs &a,
     return go(pthr_scan_kernel<S, kPthrThr, QB>);
 }
 
+// ---- the scan over a PQ table beyond one LDS image (m > 96) -----------------------------------------------------------------
+// pthr_scan_kernel<PthrPq, MODE, 1>'s sibling: same grid, ranges, slices, mask, slot map and consumers, but the scores of a batch
+// of kWideTiles tiles per wave come out of one walk over the table's chunks (adc_wide_walk, vg_adc_wide.hpp) — pthr_scan_kernel
+// scores a row step at a time against a whole image, so this is a kernel of its own, not a scorer.  tables: per slot.
+// LDS: the walker's chunk and tail rows (111 KiB), kPthrHist: then the histogram slots (8 KiB).  One workgroup per CU, 8 waves.
+constexpr int kPthrWideWaves = 8;
+template <int MODE>
+__global__ __launch_bounds__(kPthrWideWaves * 64) void pthr_scan_wide_kernel(
+    const uint4 *__restrict__ tiles, const float *__restrict__ tables, int m, int groups, bool desc, const int *__restrict__ qmap, int64_t n,
+    const uint32_t *__restrict__ probes, const uint32_t *__restrict__ part_off, int np, int sub_n, const float *__restrict__ thr,
+    const uint32_t *__restrict__ cut, const uint8_t *__restrict__ mask, int64_t mask_stride, int64_t list_cap, uint64_t *__restrict__ lists,
+    int *__restrict__ counts, unsigned *__restrict__ hist)
+{
+    extern __shared__ __attribute__((aligned(16))) float pthr_lds[];
+    constexpr int kThreads = kPthrWideWaves * 64;
+    const int s = blockIdx.x, j = blockIdx.y;
+    const int64_t slot = blockIdx.z;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    int64_t R0, R1;
+    if (probes) {
+        const uint32_t p = probes[slot * np + j];
+        R0 = part_off[p];
+        R1 = part_off[p + 1];
+    } else {
+        R0 = n * j / np;
+        R1 = n * (j + 1) / np;
+    }
+    if (R1 <= R0) return;  // (the whole workgroup)
+    const int64_t qq = pthr_query(qmap, slot);
+    const float tq = MODE == kPthrThr ? thr[qq] : 0.0f;
+    const uint32_t cq = MODE == kPthrBin ? cut[slot] : 0u;
+    const uint8_t *mq = mask ? mask + qq * mask_stride : nullptr;
+    const float *image = tables + slot * lut_image_words(m);
+    uint32_t *htags = reinterpret_cast<uint32_t *>(pthr_lds + kWideLdsWords);
+    unsigned *hslots = htags + kPthrSlots;
+    if (MODE == kPthrHist) {
+        for (int t = tid; t < kPthrSlots; t += kThreads) {
+            htags[t] = kPthrNoBin;
+            hslots[t] = 0u;
+        }
+        __syncthreads();
+    }
+    const int64_t u0 = R0 >> 6, u1 = (R1 + 63) >> 6;
+    const int64_t t0 = u0 + (u1 - u0) * s / sub_n, t1 = u0 + (u1 - u0) * (s + 1) / sub_n;
+    for (int64_t b0 = t0; b0 < t1; b0 += static_cast<int64_t>(kPthrWideWaves) * kWideTiles) {
+        bool want[kWideTiles], live[kWideTiles];
+        float total[kWideTiles];
+#pragma unroll
+        for (int tb = 0; tb < kWideTiles; tb++) {
+            const int64_t tile = b0 + static_cast<int64_t>(tb) * kPthrWideWaves + wave;
+            const int64_t row = tile * 64 + lane;
+            live[tb] = tile < t1 && row >= R0 && row < R1 && mask_bit(mq, row);  // (filter.Matches)
+            want[tb] = __any(live[tb]) != 0;  // a tile the range or the filter leaves nothing of: its rows are not read
+        }
+        adc_wide_walk<kPthrWideWaves>(tiles, groups, m, image, pthr_lds, b0, want, tid, total);
+#pragma unroll
+        for (int tb = 0; tb < kWideTiles; tb++) {
+            if (!want[tb]) continue;
+            const int64_t row = (b0 + static_cast<int64_t>(tb) * kPthrWideWaves + wave) * 64 + lane;
+            const float v = total[tb];
+            const uint64_t key = make_key(v, static_cast<uint32_t>(row), desc);
+            const uint32_t bin = static_cast<uint32_t>(key >> 48);
+            if (MODE == kPthrHist) {
+                wave_hist(live[tb], bin, htags, hslots, hist + slot * kPthrBins, lane);
+            } else {
+                const bool pass = live[tb] && (MODE == kPthrBin ? bin <= cq : (desc ? v >= tq : v <= tq));
+                wave_append(pass, key, counts + slot, lists + slot * list_cap, lane);
+            }
+        }
+    }
+    if (MODE == kPthrHist) {
+        __syncthreads();
+        for (int t = tid; t < kPthrSlots; t += kThreads)
+            if (hslots[t] != 0u) atomicAdd(&hist[slot * kPthrBins + htags[t]], hslots[t]);
+    }
+}
+
+static int32_t launch_pthr_wide(const vg_index *idx, const float *tables, bool desc, int mode, const PthrArgs &a, hipStream_t st)
+{
+    const dim3 grid(static_cast<unsigned>(a.sub), static_cast<unsigned>(a.np), static_cast<unsigned>(a.nq));
+    const size_t bytes = sizeof(float) * kWideLdsWords + (mode == kPthrHist ? sizeof(uint32_t) * 2 * kPthrSlots : 0);
+    auto go = [&](auto kern) -> int32_t {
+        VG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(bytes)));
+        VG_LAUNCH(kern, grid, dim3(kPthrWideWaves * 64), bytes, st, reinterpret_cast<const uint4 *>(idx->d_pq_tiles), tables, idx->pq->m,
+                  idx->pq_groups, desc, a.qmap, a.n, a.probes, a.part_off, a.np, a.sub, a.thr, a.cut, a.mask, a.mask_stride, a.list_cap, a.lists,
+                  a.counts, a.hist);
+        return VG_OK;
+    };
+    if (mode == kPthrHist) return go(pthr_scan_wide_kernel<kPthrHist>);
+    if (mode == kPthrBin) return go(pthr_scan_wide_kernel<kPthrBin>);
+    return go(pthr_scan_wide_kernel<kPthrThr>);
+}
+
 // the scorer of the call: scan kind, metric, the fp32 register form; qb: kThrQB (the whole segment, fp32 / SQ8) or 1
 static int32_t pthr_pass(const vg_index *idx, int32_t scan, int qb, const float *tables, int mode, const PthrArgs &a, hipStream_t st)
 {
     VG_CHECK(!(a.qmap && a.probes), VG_ERR_INVALID_ARG, "pthr_pass: a slot map over probed partitions");
     const bool dot = idx->metric != VG_METRIC_L2;
     if (scan == VG_SCAN_PQ) {
+        // a table beyond one LDS image: the chunked sibling (test hook kHookAdcWideAlways: whatever m is)
+        if (sizeof(float) * static_cast<size_t>(lut_image_words(idx->pq->m)) > kPthrLutMax || hook(kHookAdcWideAlways))
+            return launch_pthr_wide(idx, tables, dot, mode, a, st);
         const PthrPq sc{reinterpret_cast<const uint4 *>(idx->d_pq_tiles), tables, idx->pq->m, idx->pq_groups, dot};
         return launch_pthr<PthrPq, 1>(sc, mode, sizeof(float) * static_cast<size_t>(lut_image_words(idx->pq->m)), a, st);
     }
@@ -384,8 +481,6 @@ VG_API int32_t vg_search_flat_probed_threshold(vg_index *idx, const float *queri
     } else if (scan == VG_SCAN_PQ) {
         VG_CHECK(idx->pq && (n == 0 || idx->d_pq_tiles), VG_ERR_NOT_READY, "%s: index has no PQ codes", fn);
         VG_CHECK(idx->pq->k == 256, VG_ERR_UNSUPPORTED, "%s: LUT scan needs numCentroids == 256 (got %d)", fn, idx->pq->k);
-        VG_CHECK(sizeof(float) * static_cast<size_t>(vg::lut_image_words(idx->pq->m)) <= vg::kPthrLutMax, VG_ERR_UNSUPPORTED,
-                 "%s: m=%d lookup table does not fit one LDS image (m <= 96)", fn, idx->pq->m);
     } else {
         VG_CHECK(idx->sq && (n == 0 || idx->d_sq_tiles), VG_ERR_NOT_READY, "%s: index has no SQ8 codes", fn);
     }
