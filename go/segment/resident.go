@@ -699,6 +699,26 @@ func (r *Resident) SQ8NominationInfo() (mode int, heldBytes, rescanned int64, er
 	return int(m), int64(b), int64(n), hipctx.Err(int32(st))
 }
 
+// EnableRaBitQNomination: batches of SearchRaBitQ above 128 queries (k <= 256, queries x rows >= 12M) are nominated by an int8 MFMA
+// GEMM over the sign bits (exact Hamming distances), listed behind a conservative screen, re-scored with popcount and the
+// reference's formula and proven; nothing resident; results unchanged.  An index holding a negative stored norm keeps the scan.
+func (r *Resident) EnableRaBitQNomination(on bool) error {
+	v := C.int32_t(0)
+	if on {
+		v = 1
+	}
+	return hipctx.Err(int32(C.vg_index_enable_rabitq_nomination(r.h, v, nil)))
+}
+
+// RaBitQNominationInfo: whether the mode is on, the device bytes it keeps resident (0), the queries whose list was incomplete and
+// the scan answered since the mode was enabled, and the VG_RABITQ_NOM_CHECK hook's count of disagreeing Hamming distances.
+func (r *Resident) RaBitQNominationInfo() (on bool, heldBytes, rescanned, mismatched int64, err error) {
+	var m C.int32_t
+	var b, n, x C.int64_t
+	st := C.vg_index_rabitq_nomination_info(r.h, &m, &b, &n, &x)
+	return m != 0, int64(b), int64(n), int64(x), hipctx.Err(int32(st))
+}
+
 // EnablePQNomination: batches of SearchPQ (queries x rows >= 24M, k <= 256) are nominated by a bfloat16 MFMA GEMM over the decoded
 // rows (+ rows*dim*2 bytes of device memory) and re-scored from the codes against the query's distance table; results unchanged.
 func (r *Resident) EnablePQNomination(on bool) error {

@@ -119,7 +119,8 @@ extern "C" {
  *  and vg_bm25_export, found by symbol lookup.  Likewise the PQ batch nomination from the codes:
  *  vg_index_enable_pq_nomination_from_codes and vg_index_pq_nomination_info, found by symbol lookup.  Likewise the SQ8 batch
  *  nomination from the codes: vg_index_enable_sq8_nomination_from_codes and vg_index_sq8_nomination_info, found by symbol lookup.  Likewise the test
- *  entry point vg_int4_scan_plan, found by symbol lookup. */
+ *  entry point vg_int4_scan_plan, found by symbol lookup.  Likewise the RaBitQ batch nomination on the int8 matrix cores:
+ *  vg_index_enable_rabitq_nomination and vg_index_rabitq_nomination_info, found by symbol lookup. */
 #define VG_ABI_MINOR 13
 #define VG_INVALID_ID 0xFFFFFFFFu
 #define VG_STREAM_LEGACY ((void *)1) /* == hipStreamLegacy */
@@ -1628,6 +1629,27 @@ int32_t vg_index_enable_sq8_nomination_from_codes(vg_index *idx, int32_t on, voi
  * the codes); *held_bytes = the device memory the mode keeps resident; *rescanned = the queries, since the mode was enabled, whose
  * proof failed and which the scan answered (0 when off).  Any pointer may be NULL.  Found by symbol lookup. */
 int32_t vg_index_sq8_nomination_info(const vg_index *idx, int32_t *mode, int64_t *held_bytes, int64_t *rescanned);
+/* vg_search_rabitq batches through an int8 matrix-core nomination.  A Hamming distance is a dot product of +-1 vectors: the GEMM
+ * multiplies the queries' and rows' sign bits, expanded to int8 in registers from the index's own code tiles, and accumulates in
+ * int32 — the Hamming distance of every (query, row) pair comes out EXACT, no rounded operand and no margin.  Its epilogue lists
+ * (row, h) for the pairs whose exact score may be at or below the query's threshold (the sel-th best score of every 64th 64-row
+ * tile): a conservative screen — every pair whose rq.Distance, in the reference's operation order, is <= the threshold passes —
+ * that replaces the formula's division by a product with RN(1 / dim) moved one ulp towards zero (below 1 / dim, so the product
+ * rounds to no more than the quotient).  The listed rows are re-scored with popcount and the reference's formula, the k best taken by (score, row id), and a
+ * query is proved when its list (4096 keys) did not overflow and holds k rows at or below the threshold; the others go through the
+ * scan.  Results are the scan's, bit for bit; the NaN replay stays the last step.  Resident: nothing beyond the code tiles and
+ * norms (held_bytes 0).  The screen's inequality needs stored norms that are not negative (Encode's never are): enabling looks at
+ * them once, and an index that holds a NEGATIVE stored norm keeps the scan for every batch.  Refusals: NULL index
+ * VG_ERR_INVALID_ARG; no RaBitQ codes VG_ERR_NOT_READY.  on == 0 turns the mode off; vg_index_set_rabitq_codes drops it; enabling
+ * again zeroes the counters; vg_vamana_reorder_bfs leaves it correct (nothing of it is per row).  Batches it takes: MORE THAN 128
+ * queries, k <= 256, rows > k, any dim the index accepts, and queries x rows at or above its crossover against the scan (README,
+ * Limits); every other batch runs the scan as before.  Found by symbol lookup. */
+int32_t vg_index_enable_rabitq_nomination(vg_index *idx, int32_t on, void *stream);
+/* *on = whether the mode is enabled; *held_bytes = the device memory it keeps resident (0); *rescanned = the queries, since the mode
+ * was enabled, whose list was incomplete and which the scan answered; *mismatched = under the test hook VG_RABITQ_NOM_CHECK, the
+ * listed keys whose Hamming distance from the GEMM was not the popcount's (0 unless the kernel is wrong).  Zeros when off.  Any
+ * pointer may be NULL.  Found by symbol lookup. */
+int32_t vg_index_rabitq_nomination_info(const vg_index *idx, int32_t *on, int64_t *held_bytes, int64_t *rescanned, int64_t *mismatched);
 
 #ifdef __cplusplus
 }

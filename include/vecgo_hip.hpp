@@ -690,6 +690,21 @@ public:
         check(vg_index_sq8_nomination_info(h_, &r.mode, &r.held_bytes, &r.rescanned));
         return r;
     }
+    // SearchRaBitQ batches above 128 queries through an int8 matrix-core nomination over the sign bits (exact Hamming distances, a
+    // conservative screen, exact re-score and proof; nothing resident); other batches keep the scan; results unchanged
+    void EnableRaBitQNomination(bool on = true) { check(vg_index_enable_rabitq_nomination(h_, on ? 1 : 0, nullptr)); }
+    // on: whether the mode is enabled; held_bytes: the device memory it keeps resident (0); rescanned: queries whose list was
+    // incomplete and the scan answered, since the mode was enabled; mismatched: the VG_RABITQ_NOM_CHECK hook's count
+    struct RaBitQNomination {
+        int32_t on;
+        int64_t held_bytes, rescanned, mismatched;
+    };
+    RaBitQNomination RaBitQNominationInfo() const
+    {
+        RaBitQNomination r{0, 0, 0, 0};
+        check(vg_index_rabitq_nomination_info(h_, &r.on, &r.held_bytes, &r.rescanned, &r.mismatched));
+        return r;
+    }
     Result SearchRaBitQ(const float *queries, int64_t nq, int k) { return run(nq, k, [&](Result &r) { return vg_search_rabitq(h_, queries, nq, k, r.ids.data(), r.scores.data(), nullptr); }); }
     // IVF partitions (flat/segment.go:187-207) and the probed scan of flat.Segment.Search (:727-749):
     // scan = VG_SCAN_F32 / VG_SCAN_PQ / VG_SCAN_SQ8, nprobes <= 0 means 1 as in the reference

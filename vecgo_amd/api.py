@@ -1028,6 +1028,21 @@ class Index:
         check(self._lib.vg_index_sq8_nomination_info(self._h, C.byref(mode), C.byref(held), C.byref(rescanned)))
         return mode.value, held.value, rescanned.value
 
+    def enable_rabitq_nomination(self, on: bool = True, stream=None):
+        """vg_index_enable_rabitq_nomination: batches of search_rabitq above 128 queries (k <= 256, queries x rows >= 12M) are nominated by
+        an int8 MFMA GEMM over the sign bits — the Hamming distances come out exact —, listed behind a conservative screen, re-scored
+        with popcount and the reference's formula and proven; the others keep the scan.  Nothing resident; ids and scores stay
+        bit-identical.  An index that holds a negative stored norm keeps the scan."""
+        check(self._lib.vg_index_enable_rabitq_nomination(self._h, C.c_int32(1 if on else 0), _stream_ptr(stream)))
+
+    def rabitq_nomination_info(self):
+        """vg_index_rabitq_nomination_info: (on, held_bytes, rescanned, mismatched) — held_bytes the device memory the mode keeps
+        resident (0); rescanned the queries whose list was incomplete and the scan answered since it was enabled; mismatched, under
+        the test hook VG_RABITQ_NOM_CHECK, the listed keys whose Hamming distance was not the popcount's."""
+        on, held, rescanned, mismatched = C.c_int32(0), C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        check(self._lib.vg_index_rabitq_nomination_info(self._h, C.byref(on), C.byref(held), C.byref(rescanned), C.byref(mismatched)))
+        return on.value, held.value, rescanned.value, mismatched.value
+
     def search_sq8(self, queries, k, out=None, stream=None):
         """flat.Segment.Search SQ8 branch (flat/segment.go:517-604)."""
         return self._search(self._lib.vg_search_sq8, queries, k, out=out, stream=stream)

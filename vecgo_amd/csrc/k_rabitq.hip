@@ -4,13 +4,13 @@
 #include "vg_device.hpp"
 #include "vg_exact.hpp"
 #include "vg_internal.hpp"
+#include "vg_nominate.hpp"
+#include "vg_rabitq.hpp"
 #include "vg_cand_replay.hpp"
 #include "vg_scan_slices.hpp"
 #include "vg_search.hpp"
 
 namespace vg {
-
-__host__ __device__ inline int rq_words(int dim) { return (dim + 63) / 64; }
 
 // Encode (rabitq.go:51-78): 16 lanes per vector.  Norm: dotProductAvx512 order, float64 sqrt.
 // Bits: lane L of the group owns elements 4L..4L+3 of each 64-element word = one nibble.
@@ -45,41 +45,6 @@ __global__ __launch_bounds__(256) void rabitq_encode_kernel(const float *__restr
         out[nw * 8 + 2] = (nb >> 16) & 0xFF;
         out[nw * 8 + 3] = (nb >> 24) & 0xFF;
     }
-}
-
-__device__ inline float rq_formula(float qn, float yn, float dimf, float hamming)
-{
-    // rabitq.go:170-175, fp32, left to right, no fusion
-    const float t1 = qn - yn;
-    const float t1sq = t1 * t1;
-    float t2 = 4.0f * qn;
-    t2 = t2 * yn;
-    t2 = t2 / dimf;
-    t2 = t2 * hamming;
-    return t1sq + t2;
-}
-
-// popcount(a ^ c) over nbytes bytes: dwords, 8 loads in flight at a time, when both are 4-byte aligned
-__device__ __forceinline__ int hamming_bytes(const uint8_t *__restrict__ a, const uint8_t *__restrict__ c, int64_t nbytes)
-{
-    int h = 0;
-    int64_t b = 0;
-    if (((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(c)) & 3) == 0) {
-        const uint32_t *aw = reinterpret_cast<const uint32_t *>(a), *cw = reinterpret_cast<const uint32_t *>(c);
-        const int64_t nw = nbytes >> 2;
-        int64_t w = 0;
-        for (; w + 8 <= nw; w += 8) {
-            uint32_t x[8];
-#pragma unroll
-            for (int u = 0; u < 8; u++) x[u] = cw[w + u];
-#pragma unroll
-            for (int u = 0; u < 8; u++) h += __popc(x[u] ^ aw[w + u]);
-        }
-        for (; w < nw; w++) h += __popc(cw[w] ^ aw[w]);
-        b = nw << 2;
-    }
-    for (; b < nbytes; b++) h += __popc(static_cast<unsigned>(a[b] ^ c[b]));
-    return h;
 }
 
 // Distance of one query code (bits + norm, as produced by Encode) against n reference-layout
@@ -269,7 +234,9 @@ __global__ __launch_bounds__(kRqThreads) void rabitq_scan_kernel(
 // in its L2.
 constexpr int kRqMq = 16;      // queries per workgroup pass
 constexpr int kRqMqTiles = 2;  // 64-row tiles per trip
-template <int G>               // 16-byte groups per row, compile-time (6 at dim 768); 0 = runtime `groups`
+// STRIDE: the launch walks every STRIDE-th tile — logical tile t of its n_tiles is tile t * STRIDE of the array (the nomination's
+// threshold sample, launch_rabitq_sample); 1, the scan, is the kernel as it was.
+template <int G, int STRIDE = 1>  // G: 16-byte groups per row, compile-time (6 at dim 768); 0 = runtime `groups`
 __global__ __launch_bounds__(kRqThreads) void rabitq_scan_mq_kernel(
     const uint4 *__restrict__ tiles, const float *__restrict__ norms, int64_t n_rows, int64_t n_tiles,
     int groups_rt, int dim, const uint8_t *__restrict__ qcodes /* nq * (nb+4) */, int nb, int slices, int nq,
@@ -322,7 +289,7 @@ __global__ __launch_bounds__(kRqThreads) void rabitq_scan_mq_kernel(
         bool live[kRqMqTiles];
 #pragma unroll
         for (int t = 0; t < kRqMqTiles; t++) {
-            const int64_t tt = tile + t < t1 ? tile + t : tile;  // a trip's second tile may lie past the slice
+            const int64_t tt = (tile + t < t1 ? tile + t : tile) * STRIDE;  // a trip's second tile may lie past the slice
             const int64_t row = tt * 64 + lane;
             live[t] = tile + t < t1 && row < n_rows;
             if (G) {
@@ -351,7 +318,7 @@ __global__ __launch_bounds__(kRqThreads) void rabitq_scan_mq_kernel(
                         const uint4 qq = qbits[qi * groups + g];
 #pragma unroll
                         for (int t = 0; t < kRqMqTiles; t++) {
-                            const int64_t tt = tile + t < t1 ? tile + t : tile;
+                            const int64_t tt = (tile + t < t1 ? tile + t : tile) * STRIDE;
                             const uint4 cc = tiles[(tt * groups + g) * 64 + lane];
                             h[t] += __popc(cc.x ^ qq.x) + __popc(cc.y ^ qq.y) + __popc(cc.z ^ qq.z) + __popc(cc.w ^ qq.w);
                         }
@@ -362,7 +329,7 @@ __global__ __launch_bounds__(kRqThreads) void rabitq_scan_mq_kernel(
                 for (int t = 0; t < kRqMqTiles; t++) {
                     const float d = rq_formula(qn, y[t], dimf, static_cast<float>(h[t]));
                     if (__ballot(live[t] && d <= tau_d[qi])) {
-                        const int64_t row = (tile + t) * 64 + lane;
+                        const int64_t row = (tile + t) * STRIDE * 64 + lane;
                         uint64_t key = live[t] ? make_key(d, static_cast<uint32_t>(row), false) : kKeyMax;
                         if (paged && key <= min_keys[q0 + qi]) key = kKeyMax;
                         tk[qi].offer(key, lane);
@@ -509,6 +476,7 @@ VG_API int32_t vg_index_set_rabitq_codes(vg_index *idx, const uint8_t *codes, vo
     VG_CHECK(idx->dim <= 8192, VG_ERR_UNSUPPORTED, "vg_index_set_rabitq_codes: dim %d > 8192", idx->dim);
     VG_HIP(hipSetDevice(idx->ctx->device));
     hipStream_t st = vg::pick_stream(idx->ctx, stream);
+    VG_TRY(vg::rabitq_nomination_drop(idx));  // vg_index_enable_rabitq_nomination again after new codes
     if (idx->d_rq_tiles) {
         VG_HIP(hipStreamSynchronize(st));
         VG_HIP(hipFree(idx->d_rq_tiles));
@@ -542,6 +510,71 @@ VG_API int32_t vg_index_set_rabitq_codes(vg_index *idx, const uint8_t *codes, vo
     return VG_OK;
 }
 
+namespace vg {
+
+static size_t rabitq_mq_lds(const vg_index *idx)
+{
+    return static_cast<size_t>(kRqMq) * idx->rq_groups * 16 + kRqWaves * 64 * sizeof(uint64_t) + kRqWaves * sizeof(int) + kRqMq * sizeof(float);
+}
+
+int32_t rabitq_scan_batch(vg_index *idx, const float *q, int64_t nq, int k, uint8_t *qcodes, uint32_t *oid, float *osc, hipStream_t st)
+{
+    const int nb = rq_words(idx->dim) * 8;
+    // two or more queries: blocks of kRqMq queries share every code load (rabitq_scan_mq_kernel)
+    const bool mq = nq >= 2;
+    const int64_t units = mq ? (nq + kRqMq - 1) / kRqMq : nq;  // workgroups per slice
+    const int slices = scan_slices(units, idx->n_tiles, idx->ctx->compute_units, 4);  // ~4 workgroups of 256 threads per CU (swept 2..8: 3-4 best)
+    const size_t mq_lds = rabitq_mq_lds(idx);
+    ArenaCall ar(idx->ctx, st);
+    PagedTopK pages;  // a wave keeps 64 keys: k > 64 comes in pages of 64, one scan per page
+    pages.add(ar, nq, k, slices);
+    VG_TRY(ar.commit());
+    VG_LAUNCH(rabitq_encode_kernel, dim3(static_cast<unsigned>((nq + 15) / 16)), dim3(256), 0, st, q, nq, idx->dim, qcodes);
+    const int64_t max_q = (1ll << 30) / slices;
+    return pages.run(ar, slices, false, oid, osc, st, [&](int kk, uint64_t *partial, const uint64_t *floor) -> int32_t {
+        for (int64_t q0 = 0; mq && q0 < nq; q0 += max_q * kRqMq) {  // whole query blocks per launch
+            const int64_t cnt = std::min<int64_t>(nq - q0, max_q * kRqMq);
+            const int64_t ng = (cnt + kRqMq - 1) / kRqMq;
+            auto kern = idx->rq_groups == 6 ? rabitq_scan_mq_kernel<6> : rabitq_scan_mq_kernel<0>;
+            ProfScope prof(idx->ctx, "rabitq_scan_mq", st);
+            VG_LAUNCH(kern, dim3(static_cast<unsigned>(ng * slices)), dim3(kRqThreads), mq_lds, st,
+                      reinterpret_cast<const uint4 *>(idx->d_rq_tiles), idx->d_rq_norms, idx->n, idx->n_tiles, idx->rq_groups, idx->dim,
+                      qcodes + q0 * (nb + 4), nb, slices, static_cast<int>(cnt), kk, partial + q0 * slices * kk, floor ? floor + q0 : nullptr);
+        }
+        for (int64_t q0 = 0; !mq && q0 < nq; q0 += max_q) {
+            const int64_t cnt = nq - q0 < max_q ? nq - q0 : max_q;
+            ProfScope prof(idx->ctx, "rabitq_scan", st);
+            VG_LAUNCH(rabitq_scan_kernel, dim3(static_cast<unsigned>(cnt * slices)), dim3(kRqThreads), 0, st,
+                      reinterpret_cast<const uint4 *>(idx->d_rq_tiles), idx->d_rq_norms, idx->n, idx->n_tiles, idx->rq_groups, idx->dim,
+                      qcodes + q0 * (nb + 4), nb, slices, static_cast<int>(cnt), kk, partial + q0 * slices * kk, floor ? floor + q0 : nullptr);
+        }
+        return VG_OK;
+    });
+}
+
+// the sampled tiles: 0, 64, 128, ... of the index's n_tiles
+static int64_t rabitq_sample_tiles(const vg_index *idx) { return (idx->n_tiles + 63) / 64; }
+int rabitq_sample_slices(const vg_index *idx, int64_t cnt)
+{
+    return scan_slices((cnt + kRqMq - 1) / kRqMq, rabitq_sample_tiles(idx), idx->ctx->compute_units, 4);
+}
+int32_t launch_rabitq_sample(const vg_index *idx, const uint8_t *qcodes, int64_t cnt, int sel_k, int slices, uint64_t *partial, uint32_t *ids,
+                             float *thr, hipStream_t st)
+{
+    const int nb = rq_words(idx->dim) * 8;
+    const int64_t ng = (cnt + kRqMq - 1) / kRqMq;
+    auto kern = idx->rq_groups == 6 ? rabitq_scan_mq_kernel<6, 64> : rabitq_scan_mq_kernel<0, 64>;
+    {
+        ProfScope prof(idx->ctx, "rabitq_nom_sample", st);
+        VG_LAUNCH(kern, dim3(static_cast<unsigned>(ng * slices)), dim3(kRqThreads), rabitq_mq_lds(idx), st,
+                  reinterpret_cast<const uint4 *>(idx->d_rq_tiles), idx->d_rq_norms, idx->n, rabitq_sample_tiles(idx), idx->rq_groups, idx->dim, qcodes,
+                  nb, slices, static_cast<int>(cnt), sel_k, partial, static_cast<const uint64_t *>(nullptr));
+    }
+    return launch_topk_merge(partial, cnt, slices, sel_k, false, ids, thr, st);
+}
+
+}  // namespace vg
+
 VG_API int32_t vg_search_rabitq(vg_index *idx, const float *queries, int64_t nq, int32_t k, uint32_t *ids,
                                 float *scores, void *stream)
 {
@@ -559,43 +592,24 @@ VG_API int32_t vg_search_rabitq(vg_index *idx, const float *queries, int64_t nq,
         VG_TRY(vg::empty_results(nq, k, false, io.oid.ptr, io.osc.ptr, st));
     } else {
         const int nb = vg::rq_words(idx->dim) * 8;
-        // two or more queries: blocks of kRqMq queries share every code load (rabitq_scan_mq_kernel)
-        const bool mq = nq >= 2;
-        const int64_t units = mq ? (nq + vg::kRqMq - 1) / vg::kRqMq : nq;  // workgroups per slice
-        const int slices = vg::scan_slices(units, idx->n_tiles, idx->ctx->compute_units, 4);  // ~4 workgroups of 256 threads per CU (swept 2..8: 3-4 best)
-        const size_t mq_lds = static_cast<size_t>(vg::kRqMq) * idx->rq_groups * 16 + vg::kRqWaves * 64 * sizeof(uint64_t) +
-                              vg::kRqWaves * sizeof(int) + vg::kRqMq * sizeof(float);
-        vg::ArenaCall ar(idx->ctx, st);
-        const int i_qcodes = ar.add(static_cast<size_t>(nq) * (nb + 4));
-        vg::PagedTopK pages;  // a wave keeps 64 keys: k > 64 comes in pages of 64, one scan per page
-        pages.add(ar, nq, k, slices);
-        VG_TRY(ar.commit());
-        uint8_t *qcodes = ar.get<uint8_t>(i_qcodes);
-        VG_LAUNCH(vg::rabitq_encode_kernel, dim3(static_cast<unsigned>((nq + 15) / 16)), dim3(256), 0, st,
-                           q, nq, idx->dim, qcodes);
-        const int64_t max_q = (1ll << 30) / slices;
-        VG_TRY(pages.run(ar, slices, false, io.oid.ptr, io.osc.ptr, st, [&](int kk, uint64_t *partial, const uint64_t *floor) -> int32_t {
-            for (int64_t q0 = 0; mq && q0 < nq; q0 += max_q * vg::kRqMq) {  // whole query blocks per launch
-                const int64_t cnt = std::min<int64_t>(nq - q0, max_q * vg::kRqMq);
-                const int64_t ng = (cnt + vg::kRqMq - 1) / vg::kRqMq;
-                auto kern = idx->rq_groups == 6 ? vg::rabitq_scan_mq_kernel<6> : vg::rabitq_scan_mq_kernel<0>;
-                vg::ProfScope prof(idx->ctx, "rabitq_scan_mq", st);
-                VG_LAUNCH(kern, dim3(static_cast<unsigned>(ng * slices)), dim3(vg::kRqThreads), mq_lds, st,
-                          reinterpret_cast<const uint4 *>(idx->d_rq_tiles), idx->d_rq_norms, idx->n, idx->n_tiles,
-                          idx->rq_groups, idx->dim, qcodes + q0 * (nb + 4), nb, slices, static_cast<int>(cnt), kk,
-                          partial + q0 * slices * kk, floor ? floor + q0 : nullptr);
-            }
-            for (int64_t q0 = 0; !mq && q0 < nq; q0 += max_q) {
-                const int64_t cnt = nq - q0 < max_q ? nq - q0 : max_q;
-                vg::ProfScope prof(idx->ctx, "rabitq_scan", st);
-                VG_LAUNCH(vg::rabitq_scan_kernel, dim3(static_cast<unsigned>(cnt * slices)),
-                                   dim3(vg::kRqThreads), 0, st, reinterpret_cast<const uint4 *>(idx->d_rq_tiles),
-                                   idx->d_rq_norms, idx->n, idx->n_tiles, idx->rq_groups, idx->dim,
-                                   qcodes + q0 * (nb + 4), nb, slices, static_cast<int>(cnt), kk,
-                                   partial + q0 * slices * kk, floor ? floor + q0 : nullptr);
-            }
-            return VG_OK;
-        }));
+        vg::DevTmp<uint8_t> qc;  // the queries' codes: the scan's and the nomination's operand, and the replay's
+        VG_TRY(qc.init(static_cast<size_t>(nq) * (nb + 4), st));
+        uint8_t *qcodes = qc.ptr;
+        if (vg::rabitq_nomination_applies(idx, nq, k)) {
+            // vg_index_enable_rabitq_nomination: the int8 matrix-core nomination, the exact re-score and the proof (k_rabitq_nominate.hip);
+            // the queries whose proof failed go through the scan
+            VG_LAUNCH(vg::rabitq_encode_kernel, dim3(static_cast<unsigned>((nq + 15) / 16)), dim3(256), 0, st, q, nq, idx->dim, qcodes);
+            std::vector<int> failed;
+            VG_TRY(vg::rabitq_nominated_pass(idx, qcodes, nq, k, io.oid.ptr, io.osc.ptr, st, failed));
+            VG_TRY(vg::rescan_failed(failed, q, idx->dim, k, nullptr, 0, 0, io.oid.ptr, io.osc.ptr, st,
+                                     [&](const float *fq, int64_t nf, const uint8_t *, int64_t, uint32_t *fid, float *fsc) -> int32_t {
+                                         vg::DevTmp<uint8_t> fc;
+                                         VG_TRY(fc.init(static_cast<size_t>(nf) * (nb + 4), st));
+                                         return vg::rabitq_scan_batch(idx, fq, nf, k, fc.ptr, fid, fsc, st);
+                                     }));
+        } else {
+            VG_TRY(vg::rabitq_scan_batch(idx, q, nq, k, qcodes, io.oid.ptr, io.osc.ptr, st));
+        }
         // queries whose distances may hold a NaN: the reference's heap, operation by operation (vg_cand_replay.hpp)
         VG_TRY(vg::launch_cand_replay(vg::RabitqScorer{idx->d_rq_rows, qcodes, idx->d_rq_norms + idx->n, idx->dim, nb}, q, idx->dim, idx->n, nq, k,
                                       false, nullptr, 0, io.oid.ptr, io.osc.ptr, st));

@@ -107,6 +107,8 @@ enum Hook {
     kHookBm25SmallScratch,    // VG_BM25_SMALL_SCRATCH vg_bm25_search cuts its query chunks for 64 KiB of keys, not the context's scratch cap: a test batch takes the several chunks a large one takes
     kHookInt4SmallGrid,       // VG_INT4_SMALL_GRID    vg_int4_l2_distance_batch launches int4_scan_tab_kernel on at most 2 workgroups (vg_int4_plan.hpp), the same kernel, waves and LDS: a few thousand rows give every wave the several tiles it walks over millions
     kHookAdcWideAlways,       // VG_ADC_WIDE_ALWAYS    every PQ probed, filtered or threshold scan walks its table in chunks (adc_wide_walk, vg_adc_wide.hpp) whatever m is: the chunk seams at a few rows, wide against narrow results on one index
+    kHookRabitqNomAlways,     // VG_RABITQ_NOM_ALWAYS  vg_index_enable_rabitq_nomination: no crossover of (query, row) pairs
+    kHookRabitqNomCheck,      // VG_RABITQ_NOM_CHECK   vg_index_enable_rabitq_nomination: the verify compares every listed key's Hamming distance (the GEMM's) with its own popcount and counts the disagreements (vg_index_rabitq_nomination_info's `mismatched`)
     kHookCount
 };
 bool hook(Hook h);
@@ -521,6 +523,11 @@ struct vg_index {
     uint8_t *d_rq_tiles = nullptr;
     float *d_rq_norms = nullptr;
     int32_t rq_groups = 0;  // ceil(((dim+63)/64*8) / 16)
+    // vg_index_enable_rabitq_nomination (k_rabitq_nominate.hip): nothing resident — the mode's GEMM reads the tiles and norms above
+    bool rq_nom_on = false;
+    bool rq_nom_negative = false;    // a stored norm is negative: the screen's inequality does not hold, every batch keeps the scan
+    int64_t rq_nom_rescanned = 0;    // queries whose proof failed and the scan answered, since the mode was enabled
+    int64_t rq_nom_mismatched = 0;   // VG_RABITQ_NOM_CHECK: listed keys whose Hamming distance was not the popcount's
     // HNSW adjacency
     uint32_t *d_hnsw_l0 = nullptr;     // n*m0
     float *d_hnsw_l0_dist = nullptr;   // n*m0 cached edge distances (Neighbor.Dist) for the predicate-aware walk, or null
