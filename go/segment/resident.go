@@ -771,6 +771,29 @@ func (r *Resident) SearchRaBitQ(queries []float32, nq, k int) ([]uint32, []float
 	return ids, sc, hipctx.Err(int32(st))
 }
 
+// SearchInt4: exhaustive scan of the INT4 codes of a DiskANN segment (iq.L2Distance per row, the walk's own score), the k best by
+// (Score, RowID), scores ascending under every metric; k <= 512.  mask nil: every row takes part; else bit i of byte i/8 =
+// filter.Matches(i), len(mask) == ceil(rows/8) for one mask (maskStride 0) or (nq-1)*maskStride + ceil(rows/8) for one per query.
+func (r *Resident) SearchInt4(queries []float32, nq, k int, mask []byte, maskStride int) ([]uint32, []float32, error) {
+	ids, sc := r.out(nq, k)
+	var pm *C.uint8_t
+	if mask != nil {
+		need := (r.rows + 7) / 8
+		if maskStride != 0 {
+			if maskStride < need {
+				return nil, nil, fmt.Errorf("SearchInt4: maskStride %d is shorter than a mask (%d bytes)", maskStride, need)
+			}
+			need += (nq - 1) * maskStride
+		}
+		if len(mask) < need || len(mask) == 0 {
+			return nil, nil, fmt.Errorf("SearchInt4: mask holds %d bytes, %d needed", len(mask), need)
+		}
+		pm = bp(mask)
+	}
+	st := C.vg_search_int4(r.h, fp(queries), C.int64_t(nq), C.int32_t(k), pm, C.int64_t(maskStride), up(ids), fp(sc), nil)
+	return ids, sc, hipctx.Err(int32(st))
+}
+
 // SearchProbed: a partitioned flat segment, only the nprobes closest partitions (flat/segment.go:727-749).
 func (r *Resident) SearchProbed(queries []float32, nq, k, nprobes int, scan int32) ([]uint32, []float32, error) {
 	ids, sc := r.out(nq, k)

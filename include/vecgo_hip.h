@@ -120,7 +120,8 @@ extern "C" {
  *  vg_index_enable_pq_nomination_from_codes and vg_index_pq_nomination_info, found by symbol lookup.  Likewise the SQ8 batch
  *  nomination from the codes: vg_index_enable_sq8_nomination_from_codes and vg_index_sq8_nomination_info, found by symbol lookup.  Likewise the test
  *  entry point vg_int4_scan_plan, found by symbol lookup.  Likewise the RaBitQ batch nomination on the int8 matrix cores:
- *  vg_index_enable_rabitq_nomination and vg_index_rabitq_nomination_info, found by symbol lookup. */
+ *  vg_index_enable_rabitq_nomination and vg_index_rabitq_nomination_info, found by symbol lookup.  Likewise the exhaustive
+ *  search over an index's INT4 codes, vg_search_int4, found by symbol lookup. */
 #define VG_ABI_MINOR 13
 #define VG_INVALID_ID 0xFFFFFFFFu
 #define VG_STREAM_LEGACY ((void *)1) /* == hipStreamLegacy */
@@ -1100,6 +1101,27 @@ int32_t vg_int4_scan_plan(vg_int4 *iq, int64_t n, int32_t codes_aligned16, int64
 /* INT4 codes of a DiskANN segment (diskann/segment.go:378-416), n * ceil(dim/2) bytes; scored by
  * vg_search_vamana kind 3.  The quantizer must outlive the index. */
 int32_t vg_index_set_int4_codes(vg_index *idx, vg_int4 *iq, const uint8_t *codes, void *stream);
+/* Exhaustive scan of the INT4 codes: Int4Quantizer.L2Distance (int4.go:136-147, int4L2DistancePrecomputedAvx512 order,
+ * int4_avx512.c:127-189) for every row that takes part — the bits vg_int4_l2_distance_batch(precomputed = 1) writes for the row and
+ * vg_search_vamana kind 3 reports for it.  The reference only scores INT4 codes node by node inside the Vamana search
+ * (diskann/segment.go:558-565); the scan is the candidate stage of a rerank pipeline, the answer to a selective filter and the
+ * walk's ground truth.  Scores ascend whatever the index's metric (the DiskANN scorer is this L2-type distance under every
+ * metric, see vg_search_vamana_threshold).  ids / scores[nq * k]: the k best rows by (Score, RowID), best first; unused slots
+ * VG_INVALID_ID / +Inf.  Pointers host or device, at any alignment.
+ *   mask: the vg_search_vamana_filtered convention — bit i of byte i/8 set: row i takes part; query q reads mask + q * mask_stride,
+ *   mask_stride 0: one mask for the batch, NULL: every row.  A 64-row tile none of whose rows a batch mask keeps is not read.
+ *   k <= 512 (pages of 64 results, one scan per page).  Queries whose scores may hold a NaN are answered as
+ *   flat.Segment.Search's heap loop answers them (flat/segment.go:714-721; "NaN scores" below).
+ *   One query: the streaming scans of vg_int4_l2_distance_batch with the selection fused in (dim % 64 == 0; other dims a lane
+ *   per row).  Batches of 5 queries or more: a workgroup carries 8 queries over every decoded row (dim % 32 == 0, dim <= 4096;
+ *   other dims the lane-per-row kernel once per query — the same results, slower).  Nothing new is resident: the kernels read
+ *   the index's own codes; per call the partial lists and the page state.
+ *   Refusals, in this order, nothing written: NULL index VG_ERR_INVALID_ARG; negative nq or k VG_ERR_INVALID_ARG; nq == 0 or
+ *   k == 0 VG_OK; rows but no INT4 codes VG_ERR_NOT_READY; NULL queries / ids / scores VG_ERR_INVALID_ARG; k > 512
+ *   VG_ERR_UNSUPPORTED; mask_stride nonzero, nq > 1 and mask_stride < ceil(rows / 8) VG_ERR_INVALID_ARG.  An index without rows
+ *   answers padding.  Found by symbol lookup (see VG_ABI_MINOR). */
+int32_t vg_search_int4(vg_index *idx, const float *queries, int64_t nq, int32_t k, const uint8_t *mask, int64_t mask_stride,
+                       uint32_t *ids, float *scores, void *stream);
 
 /* ---- graph construction: neighbour selection ---------------------- */
 /* Vamana robustPrune (diskann/writer.go:571-625) for n_nodes nodes at once.  cands[n_nodes*nc]

@@ -706,6 +706,9 @@ public:
         return r;
     }
     Result SearchRaBitQ(const float *queries, int64_t nq, int k) { return run(nq, k, [&](Result &r) { return vg_search_rabitq(h_, queries, nq, k, r.ids.data(), r.scores.data(), nullptr); }); }
+    // exhaustive scan of the INT4 codes (Int4Quantizer.L2Distance per row, the DiskANN walk's own score; ascending under every
+    // metric; k <= 512); mask: bit i of byte i/8 = the row takes part, one per query mask_stride apart or (0) one for the batch
+    Result SearchInt4(const float *queries, int64_t nq, int k, const uint8_t *mask = nullptr, int64_t mask_stride = 0) { return run(nq, k, [&](Result &r) { return vg_search_int4(h_, queries, nq, k, mask, mask_stride, r.ids.data(), r.scores.data(), nullptr); }); }
     // IVF partitions (flat/segment.go:187-207) and the probed scan of flat.Segment.Search (:727-749):
     // scan = VG_SCAN_F32 / VG_SCAN_PQ / VG_SCAN_SQ8, nprobes <= 0 means 1 as in the reference
     void SetPartitions(const float *centroids, const uint32_t *part_offsets, int num_partitions)

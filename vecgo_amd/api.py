@@ -945,6 +945,14 @@ class Index:
         self._keep.append(iq)
         check(self._lib.vg_index_set_int4_codes(self._h, iq._h, pc, _stream_ptr(stream)))
 
+    def search_int4(self, queries, k, mask=None, out=None, stream=None):
+        """Exhaustive scan of the INT4 codes (vg_search_int4): Int4Quantizer.L2Distance (int4.go:136-147) per row — the bits
+        l2_distance gives the row and search_vamana(kind=3) reports for it —, the k best by (Score, RowID), scores ascending
+        whatever the metric.  mask: as search_flat_filtered's (bool[n] / packed bits for the batch, bool[nq, n] / packed
+        [nq, stride >= ceil(n/8)] for one filter per query; None = every row).  k <= 512."""
+        m, pm, stride = (None, None, 0) if mask is None else self._packed_mask(mask, _rows(queries, self.dim), "search_int4")
+        return self._search(self._lib.vg_search_int4, queries, k, extra=(pm, C.c_int64(stride)), out=out, stream=stream)
+
     def set_partitions(self, centroids, part_offsets, stream=None):
         """IVF partitions of a flat segment (flat/segment.go:187-207): centroids [P, dim] fp32 and the
         first row of every partition [P + 1] uint32; None / empty removes them."""

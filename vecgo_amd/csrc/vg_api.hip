@@ -329,7 +329,7 @@ static const char *const kHookNames[kHookCount] = {"VG_FLAT_NO_SMALL_TILE", "VG_
                                                    "VG_VAMANA_SMALL_SCRATCH", "VG_FLAT_RESCORE_SAMPLE", "VG_PTHR_FORCE_HIST",
                                                    "VG_WALK_SMALL_SCRATCH", "VG_FLAT_NO_SPLIT", "VG_FLAT_NO_SCREEN", "VG_FLAT_SCREEN_FAIL",
                                                    "VG_FLAT_F32_SAMPLE", "VG_PREFILTER_SMALL_SCRATCH", "VG_BM25_SMALL_SCRATCH",
-                                                   "VG_INT4_SMALL_GRID", "VG_ADC_WIDE_ALWAYS", "VG_RABITQ_NOM_ALWAYS", "VG_RABITQ_NOM_CHECK"};
+                                                   "VG_INT4_SMALL_GRID", "VG_INT4_SEARCH_SMALL_GRID", "VG_ADC_WIDE_ALWAYS", "VG_RABITQ_NOM_ALWAYS", "VG_RABITQ_NOM_CHECK"};
 static void hooks_from_env()
 {
     for (int h = 0; h < kHookCount; h++) {

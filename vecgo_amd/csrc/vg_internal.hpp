@@ -106,6 +106,7 @@ enum Hook {
     kHookPrefilterSmallScratch,  // VG_PREFILTER_SMALL_SCRATCH vg_search_flat_prefilter cuts its query chunks for 64 KiB of lists and keys, not the context's scratch cap: a test batch takes the several chunks a large one takes
     kHookBm25SmallScratch,    // VG_BM25_SMALL_SCRATCH vg_bm25_search cuts its query chunks for 64 KiB of keys, not the context's scratch cap: a test batch takes the several chunks a large one takes
     kHookInt4SmallGrid,       // VG_INT4_SMALL_GRID    vg_int4_l2_distance_batch launches int4_scan_tab_kernel on at most 2 workgroups (vg_int4_plan.hpp), the same kernel, waves and LDS: a few thousand rows give every wave the several tiles it walks over millions
+    kHookInt4SearchSmallGrid, // VG_INT4_SEARCH_SMALL_GRID vg_search_int4 launches at most 2 workgroups / 2 slices (the table form through vg_int4_plan.hpp's cap): a few thousand rows give every wave several trips and the merge several lists
     kHookAdcWideAlways,       // VG_ADC_WIDE_ALWAYS    every PQ probed, filtered or threshold scan walks its table in chunks (adc_wide_walk, vg_adc_wide.hpp) whatever m is: the chunk seams at a few rows, wide against narrow results on one index
     kHookRabitqNomAlways,     // VG_RABITQ_NOM_ALWAYS  vg_index_enable_rabitq_nomination: no crossover of (query, row) pairs
     kHookRabitqNomCheck,      // VG_RABITQ_NOM_CHECK   vg_index_enable_rabitq_nomination: the verify compares every listed key's Hamming distance (the GEMM's) with its own popcount and counts the disagreements (vg_index_rabitq_nomination_info's `mismatched`)
