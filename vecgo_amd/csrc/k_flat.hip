@@ -1439,9 +1439,10 @@ size_t flat_probe_gemm_scratch_bytes(int64_t pairs, int64_t ns_max, int k, int b
 {
     return ProbeGemmScratch(nullptr, pairs, ns_max, k, bf16_dim).bytes;
 }
-// One stage (MODE 1: sample, 2: append) over the groups: grid / first_block [MODE - 1] of the 128-query tiles (groups of more
-// than 64 pairs), [MODE + 1] of the 64-query tiles (flat_gemm_dma32_grouped_kernel<.., 2>: a group of at most 64 pairs is one
-// query tile, one workgroup per row tile, HBM-bound — a 128-query tile would spend the matrix cores on padding)
+// One stage (MODE 1: sample, 2: append) over the groups: grid / first_block [MODE - 1] of the 128 x 128 tiles (groups of more
+// than kProbeSmallMax = 512 pairs, k_probe.hip), [MODE + 1] of the small tiles (flat_gemm_dma32_grouped_kernel<.., kProbeRB>: a
+// group of at most 512 pairs in query tiles of kProbeRB * 32 = 128, one workgroup per query tile and row tile, which runs only the
+// blocks of 32 query rows that hold a query — a 128 x 128 tile would spend the matrix cores on padding)
 template <int MODE>
 static int32_t launch_gemm_grouped(const GemmArgs &a, const GemmGroup *groups, int ngroups, const int64_t grid[4],
                                    const int64_t *const first_block[4], const int64_t *mask_off)

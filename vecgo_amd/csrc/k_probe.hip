@@ -409,19 +409,20 @@ __global__ __launch_bounds__(256) void probe_bucket_count_kernel(const uint32_t 
     if (i < pairs) atomicAdd(&counts[probes[i]], 1u);
 }
 
-constexpr int64_t kProbeSmallMax = 512;  // pairs per partition up to which the 64-query tiles take the group
+constexpr int64_t kProbeSmallMax = 512;  // pairs per partition up to which the small (kProbeRB * 32 = 128-query) tiles take the group
 // one workgroup: the groups (pairs and rows of each partition) and each group's first workgroup in the two GEMM launches
 __global__ __launch_bounds__(1024) void probe_bucket_scan_kernel(const uint32_t *__restrict__ counts, const uint32_t *__restrict__ part_off,
                                                                  int parts, uint32_t *__restrict__ cursor, GemmGroup *__restrict__ groups,
                                                                  int64_t *__restrict__ fb_sample, int64_t *__restrict__ fb_main,
                                                                  int64_t *__restrict__ fb_sample_small, int64_t *__restrict__ fb_main_small)
 {
-    // A group of up to kProbeSmallMax pairs takes 64-query tiles (flat_gemm_dma32_grouped_kernel<.., 2>: one workgroup per query tile
-    // and row tile), a larger one the 128-query tiles; each group has workgroups in one of the two launches.  A full 64-query tile
-    // costs half a 128-query one (6.2 against 16.6 us per 8192-row partition: the small tile is balanced between the matrix unit
-    // and the rows' bytes) and a group's last tile is half empty on average whatever its size — 1024 queries x 8 probes over 122
-    // partitions are groups of 67 +- 8 pairs: r05 sent those of more than 64 pairs (three in five) to one half-empty 128-query
-    // tile each.
+    // A group of up to kProbeSmallMax = 512 pairs takes the small tiles (flat_gemm_dma32_grouped_kernel<.., kProbeRB>: kProbeRB = 4
+    // blocks of 32 query rows, one workgroup per query tile and row tile, which spends the matrix unit only on the blocks of 32 that
+    // hold a query), a group of 513 pairs or more the 128 x 128 tiles (flat_gemm_dma_grouped_kernel, whose row tiles per query tile
+    // are rounded up to a multiple of 8); each group has workgroups in one of the two launches, each launch its own prefix sums
+    // (fb_sample / fb_main, fb_sample_small / fb_main_small).  A group's last tile is half empty on average whatever its size —
+    // 1024 queries x 8 probes over 122 partitions are groups of 67 +- 8 pairs: on the small tile such a group pays for 3 blocks
+    // of 32, on the 128 x 128 tile for a whole one.
     __shared__ int64_t seg_c[1024], seg_s[1024], seg_m[1024], seg_ss[1024], seg_sm[1024];
     const int tid = threadIdx.x;
     const int per = (parts + 1023) / 1024;
@@ -713,7 +714,7 @@ static int32_t probed_whole_shortcut(const ProbedCall &c, bool *done)
 // plan() decides whether the path applies and adds its arena pieces; run() after the arena's commit().
 struct ProbedGemmPath {
     bool f32 = false, sq8 = false;
-    int64_t grids[4] = {0, 0, 0, 0}, ns_max = 0;  // sample / main of the 128-query tiles, sample / main of the 64-query tiles
+    int64_t grids[4] = {0, 0, 0, 0}, ns_max = 0;  // sample / main of the 128 x 128 tiles, sample / main of the small (kProbeRB * 32-query) tiles
     vg::NomImage gimg;  // the image the nomination runs on: none (the fp32 rows), the SQ8 image, or a view of the fp32 rows' bf16 filter
     int i_bcnt = 0, i_bcur = 0, i_bgrp = 0, i_fbs = 0, i_fbm = 0, i_fbss = 0, i_fbsm = 0, i_bpair = 0, i_pairq = 0, i_pids = 0, i_pscore = 0,
         i_pfail = 0, i_qfail = 0, i_moff = 0, i_gscr = 0;
@@ -755,7 +756,7 @@ struct ProbedGemmPath {
             }
             grids[0] = sum_s + (pairs / vg::kGemmBM) * max_s;
             grids[1] = sum_m + (pairs / vg::kGemmBM) * max_m;
-            grids[2] += (pairs / (vg::kProbeRB * vg::kG32BM)) * max_nst;  // (64-query tiles: a partition's first + the batch's further ones on the largest)
+            grids[2] += (pairs / (vg::kProbeRB * vg::kG32BM)) * max_nst;  // (small tiles: a partition's first + the batch's further ones on the largest)
             grids[3] += (pairs / (vg::kProbeRB * vg::kG32BM)) * max_nt;
         }
         const size_t gw = gemm ? static_cast<size_t>(parts) + 1 : 0;
