@@ -719,6 +719,26 @@ func (r *Resident) RaBitQNominationInfo() (on bool, heldBytes, rescanned, mismat
 	return m != 0, int64(b), int64(n), int64(x), hipctx.Err(int32(st))
 }
 
+// EnableInt4Nomination: unfiltered batches of SearchInt4 above 128 queries (k <= 256, dim % 32 == 0, queries x rows above the
+// measured crossover) are nominated by a bfloat16 MFMA GEMM whose row tiles are converted from the nibble codes, re-scored with
+// Int4Quantizer.L2Distance and proven.  Resident: 4 bytes a row and 8 a dimension; results unchanged.
+func (r *Resident) EnableInt4Nomination(on bool) error {
+	v := C.int32_t(0)
+	if on {
+		v = 1
+	}
+	return hipctx.Err(int32(C.vg_index_enable_int4_nomination(r.h, v, nil)))
+}
+
+// Int4NominationInfo: mode 1 while the nomination is enabled, the device bytes it keeps resident, and the queries whose proof
+// failed and the scan answered since the mode was enabled.
+func (r *Resident) Int4NominationInfo() (mode int, heldBytes, rescanned int64, err error) {
+	var m C.int32_t
+	var b, n C.int64_t
+	st := C.vg_index_int4_nomination_info(r.h, &m, &b, &n)
+	return int(m), int64(b), int64(n), hipctx.Err(int32(st))
+}
+
 // EnablePQNomination: batches of SearchPQ (queries x rows >= 24M, k <= 256) are nominated by a bfloat16 MFMA GEMM over the decoded
 // rows (+ rows*dim*2 bytes of device memory) and re-scored from the codes against the query's distance table; results unchanged.
 func (r *Resident) EnablePQNomination(on bool) error {

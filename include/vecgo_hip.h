@@ -121,7 +121,8 @@ extern "C" {
  *  nomination from the codes: vg_index_enable_sq8_nomination_from_codes and vg_index_sq8_nomination_info, found by symbol lookup.  Likewise the test
  *  entry point vg_int4_scan_plan, found by symbol lookup.  Likewise the RaBitQ batch nomination on the int8 matrix cores:
  *  vg_index_enable_rabitq_nomination and vg_index_rabitq_nomination_info, found by symbol lookup.  Likewise the exhaustive
- *  search over an index's INT4 codes, vg_search_int4, found by symbol lookup. */
+ *  search over an index's INT4 codes, vg_search_int4, found by symbol lookup.  Likewise its batch nomination on the matrix cores:
+ *  vg_index_enable_int4_nomination and vg_index_int4_nomination_info, found by symbol lookup. */
 #define VG_ABI_MINOR 13
 #define VG_INVALID_ID 0xFFFFFFFFu
 #define VG_STREAM_LEGACY ((void *)1) /* == hipStreamLegacy */
@@ -1672,6 +1673,24 @@ int32_t vg_index_enable_rabitq_nomination(vg_index *idx, int32_t on, void *strea
  * listed keys whose Hamming distance from the GEMM was not the popcount's (0 unless the kernel is wrong).  Zeros when off.  Any
  * pointer may be NULL.  Found by symbol lookup. */
 int32_t vg_index_rabitq_nomination_info(const vg_index *idx, int32_t *on, int64_t *held_bytes, int64_t *rescanned, int64_t *mismatched);
+/* vg_search_int4 batches through a bfloat16 matrix-core nomination from the nibble codes.  A nibble is an integer, and bfloat16 holds
+ * c - 8 exactly: the nomination GEMM multiplies the queries scaled by diff / 15, bf16(q_d * diff_d / 15) — the only rounded operand —
+ * by the centred nibbles, which its row tiles convert from the index's own row-major codes (nothing is re-tiled or copied); its
+ * scores differ from the exact ones by |q|^2 and the per-query constant 2 q.mid, mid_d = min_d + 8 diff_d / 15, which the proof
+ * takes back.  The nominated rows are re-scored with Int4Quantizer.L2Distance, the k best taken by (score, row id), and a query
+ * whose proof fails goes through the scan: ids and score bits are vg_search_int4's without the mode, the NaN replay stays the
+ * last step.  Resident: the rows' norms (4 bytes a row), mid and the scale (8 bytes a padded dimension) and two floats — rows * 4 +
+ * dim_pad * 8 + 8 bytes; the threshold sample's row tiles (rows / 64) are converted into the call's scratch.  A non-finite min or
+ * diff leaves no proof standing: every query of a batch the mode takes is rescanned.  Refusals: NULL index VG_ERR_INVALID_ARG; no
+ * INT4 codes VG_ERR_NOT_READY.  on == 0 turns the mode off; enabling again rebuilds the state and zeroes the counter;
+ * vg_index_set_int4_codes (vg_diskann_build's included) drops it; vg_vamana_reorder_bfs moves the norms with the codes.  Batches it
+ * takes: unfiltered (mask NULL), MORE THAN 128 queries, k <= 256, rows > k, dim % 32 == 0, 16-byte aligned device queries, and
+ * queries x rows at or above its crossover against the scan (README, Limits); every other batch runs the scan as before.  Found by
+ * symbol lookup. */
+int32_t vg_index_enable_int4_nomination(vg_index *idx, int32_t on, void *stream);
+/* *mode = 1 while the mode is enabled, else 0; *held_bytes = the device memory it keeps resident; *rescanned = the queries, since the
+ * mode was enabled, whose proof failed and which the scan answered (0 when off).  Any pointer may be NULL.  Found by symbol lookup. */
+int32_t vg_index_int4_nomination_info(const vg_index *idx, int32_t *mode, int64_t *held_bytes, int64_t *rescanned);
 
 #ifdef __cplusplus
 }

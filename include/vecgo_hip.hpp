@@ -709,6 +709,22 @@ public:
     // exhaustive scan of the INT4 codes (Int4Quantizer.L2Distance per row, the DiskANN walk's own score; ascending under every
     // metric; k <= 512); mask: bit i of byte i/8 = the row takes part, one per query mask_stride apart or (0) one for the batch
     Result SearchInt4(const float *queries, int64_t nq, int k, const uint8_t *mask = nullptr, int64_t mask_stride = 0) { return run(nq, k, [&](Result &r) { return vg_search_int4(h_, queries, nq, k, mask, mask_stride, r.ids.data(), r.scores.data(), nullptr); }); }
+    // SearchInt4 batches above 128 queries (unfiltered, k <= 256, dim % 32 == 0) through a bfloat16 matrix-core nomination whose row
+    // tiles are converted from the nibble codes (exact re-score and proof; 4 bytes a row resident); other batches keep the scan;
+    // results unchanged
+    void EnableInt4Nomination(bool on = true) { check(vg_index_enable_int4_nomination(h_, on ? 1 : 0, nullptr)); }
+    // mode: 1 while enabled; held_bytes: the device memory the mode keeps resident; rescanned: queries whose proof failed and the
+    // scan answered, since the mode was enabled
+    struct Int4Nomination {
+        int32_t mode;
+        int64_t held_bytes, rescanned;
+    };
+    Int4Nomination Int4NominationInfo() const
+    {
+        Int4Nomination r{0, 0, 0};
+        check(vg_index_int4_nomination_info(h_, &r.mode, &r.held_bytes, &r.rescanned));
+        return r;
+    }
     // IVF partitions (flat/segment.go:187-207) and the probed scan of flat.Segment.Search (:727-749):
     // scan = VG_SCAN_F32 / VG_SCAN_PQ / VG_SCAN_SQ8, nprobes <= 0 means 1 as in the reference
     void SetPartitions(const float *centroids, const uint32_t *part_offsets, int num_partitions)

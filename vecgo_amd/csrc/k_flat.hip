@@ -80,6 +80,9 @@ struct GemmArgs {
     // with `codes`: the SQ8 code tile (flat_gemm_sq8_big_kernel) — `codes` is the index's SQ8 code tiles, code_m their groups of 16
     // dimensions; c.ops.b is not read
     bool sq8 = false;
+    // with `codes`: the INT4 code tile (flat_gemm_int4_big_kernel) — `codes` is the index's row-major INT4 rows, code_m the bytes of a
+    // row; c.ops.b is not read
+    bool int4 = false;
 
     explicit GemmArgs(const NomCall &call) : c(call), queries(call.ops.a) {}
     // MODE 0 / 1: the scores of every stride-th row tile into sc[cnt][cols] (stride 1: the whole score matrix)
@@ -105,6 +108,7 @@ struct GemmArgs {
     GemmArgs &retry(const uint32_t *active) { return tile_active = active, *this; }
     GemmArgs &from_codes(const uint8_t *rows, int m) { return codes = rows, code_m = m, *this; }
     GemmArgs &from_sq8_codes(const uint8_t *tiles, int groups) { return codes = tiles, code_m = groups, sq8 = true, *this; }
+    GemmArgs &from_int4_codes(const uint8_t *rows, int row_bytes) { return codes = rows, code_m = row_bytes, int4 = true, *this; }
 };
 constexpr int kCountLine = 32;
 // Whether a MODE 2 launch of vg_search_flat's fused path runs the split tile: fp32 rows nominated by three bfloat16 products on the
@@ -261,6 +265,15 @@ static int32_t launch_gemm_t(const GemmArgs &a)
                      VG_ERR_INVALID_ARG, "launch_gemm: the SQ8 code tile on a call without it");
             return launch_big(flat_gemm_sq8_big_kernel<DOT, 3>, big_lds_bytes<3>(), a.codes, a.code_m);
         }
+    }
+    if (MODE == 2 && a.codes && a.int4) {  // (likewise; L2.  Rows of whole 16-byte halves, padded to the K steps that cover them: what the fill's bounds rest on)
+        if constexpr (MODE == 2 && !DOT) {
+            VG_CHECK(bf16 && c.cnt * static_cast<int64_t>(a.cap) < (int64_t(1) << 31) && a.thr_stride < 65536 && a.code_m > 0 && a.code_m % 16 == 0 &&
+                         c.ops.dim_words == (2 * a.code_m + 63) / 64 * kGemmBK && c.ops.n > 0,
+                     VG_ERR_INVALID_ARG, "launch_gemm: the INT4 code tile on a call without it");
+            return launch_big(flat_gemm_int4_big_kernel<3>, big_lds_bytes<3>(), a.codes, a.code_m);
+        }
+        VG_CHECK(false, VG_ERR_INVALID_ARG, "launch_gemm: the INT4 code tile is L2's append");
     }
     if (MODE == 2 && a.codes) {  // (any number of queries: there is no row image another tile could read)
         if constexpr (MODE == 2 && !DOT) {
@@ -1556,6 +1569,25 @@ __global__ void sq8_sample_rows_kernel(const uint4 *__restrict__ tiles, int grou
     out[(c * groups_pad + g) * 2 + 1] = make_uint4(w[4], w[5], w[6], w[7]);
     if (g == 0) norms_c[c] = norms[row];
 }
+// The INT4 nomination (img.int4: vg_index_enable_int4_nomination, k_int4_nominate.hip; L2, unfiltered) likewise: the queries' image is
+// bf16(q_d diff_d / 15), the append GEMM converts its row tiles from the row-major nibble codes (flat_gemm_int4_big_kernel), and the
+// sampled tiles are converted here with the same function — bf16(c - 8), exact — so that sample and append score in one space.
+// thread per (compact row, 32-dimension block of dim_pad / 32): 16 code bytes -> four granules; blocks past the row are zeros
+__global__ void int4_sample_rows_kernel(const uint8_t *__restrict__ codes, int row_bytes, int blocks_pad, const float *__restrict__ norms,
+                                        int64_t rows_c, int stride, uint4 *__restrict__ out, float *__restrict__ norms_c)
+{
+    const int64_t t = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+    const int64_t c = t / blocks_pad;
+    const int b = static_cast<int>(t - c * blocks_pad);
+    if (c >= rows_c) return;
+    const int64_t row = (c / kGemmBN) * stride * kGemmBN + (c % kGemmBN);  // (< n: rows_c counts the sampled rows that exist)
+    const bool in = b * 16 < row_bytes;  // (row_bytes % 16 == 0: a block lies inside the row or past it as a whole)
+    const uint4 code = in ? *reinterpret_cast<const uint4 *>(codes + row * row_bytes + b * 16) : make_uint4(0u, 0u, 0u, 0u);
+    const uint32_t w[4] = {code.x, code.y, code.z, code.w};
+#pragma unroll
+    for (int k = 0; k < 4; k++) out[(c * blocks_pad + b) * 4 + k] = in ? int4_word_bf16(w[k] ^ 0x88888888u) : make_uint4(0u, 0u, 0u, 0u);
+    if (b == 0) norms_c[c] = norms[row];
+}
 // the rows of every stride-th 128-row tile of n rows that exist (only the last tile of all can be short)
 static int64_t sample_rows(int64_t n, int stride)
 {
@@ -1592,7 +1624,12 @@ int32_t flat_nominate_bf16(vg_index *idx, const NomImage &img, bool dot, const f
     VG_TRY(gemm_operands(queries, cnt, idx->dim, idx->n, img.norms, img.rows, img.dim_pad, s.qbf, st, &nc.ops, img.scale));
     *nom = s.nom;
     NomCall sc = nc;  // the sample's operands: the image's, or the sampled tiles decoded here
-    if (s.rows_c && img.scale) {
+    if (s.rows_c && img.int4) {
+        const int blocks_pad = img.dim_pad / 32;
+        VG_LAUNCH(int4_sample_rows_kernel, dim3(static_cast<unsigned>((s.rows_c * blocks_pad + 255) / 256)), dim3(256), 0, st, idx->d_int4_rows,
+                  idx->dim / 2, blocks_pad, img.norms, s.rows_c, kFlatSampleStride, reinterpret_cast<uint4 *>(s.srows), s.snorms);
+        sc.ops.b = reinterpret_cast<const float *>(s.srows), sc.ops.n = s.rows_c, sc.ops.norms = s.snorms;
+    } else if (s.rows_c && img.scale) {
         const int groups_pad = img.dim_pad / 16;
         VG_LAUNCH(sq8_sample_rows_kernel, dim3(static_cast<unsigned>((s.rows_c * groups_pad + 255) / 256)), dim3(256), 0, st,
                   reinterpret_cast<const uint4 *>(idx->d_sq_tiles), idx->sq_groups, groups_pad, img.norms, s.rows_c, kFlatSampleStride,
@@ -1609,9 +1646,11 @@ int32_t flat_nominate_bf16(vg_index *idx, const NomImage &img, bool dot, const f
     VG_LAUNCH(flat_thr_cap_kernel, dim3(nc.ucnt()), dim3(64), 0, st, nom->thr, nom->sel_k, queries, idx->dim, img.norm_max);
     VG_HIP(hipMemsetAsync(nom->counts, 0, sizeof(int) * static_cast<size_t>(cnt), st));
     {
-        ProfScope prof(idx->ctx, img.scale ? "sq8_codes_gemm" : img.from_codes ? "pq_codes_gemm" : "sq8_nominate_gemm", st);
+        ProfScope prof(idx->ctx, img.int4 ? "int4_codes_gemm" : img.scale ? "sq8_codes_gemm" : img.from_codes ? "pq_codes_gemm" : "sq8_nominate_gemm", st);
         GemmArgs a = GemmArgs::append(nc, nom->thr, nom->sel_k, nom->counts, nom->cand, nom->cap).wide(s.counts_wide, idx->ctx->compute_units);
-        if (img.scale)
+        if (img.int4)
+            a.from_int4_codes(idx->d_int4_rows, idx->dim / 2);
+        else if (img.scale)
             a.from_sq8_codes(idx->d_sq_tiles, idx->sq_groups);
         else if (img.from_codes)
             a.from_codes(idx->d_pq_rows, idx->pq->m);

@@ -440,6 +440,7 @@ VG_API int32_t vg_index_set_int4_codes(vg_index *idx, vg_int4 *iq, const uint8_t
         VG_HIP(hipFree(idx->d_int4_rows));
         idx->d_int4_rows = nullptr;
     }
+    VG_TRY(vg::nom_free(idx->i4_nom, st));  // the old codes' nomination (vg_index_enable_int4_nomination again after new codes)
     idx->int4_table = iq->d_table;
     idx->int4_min = iq->d_min;
     idx->int4_diff = iq->d_diff;

@@ -1,0 +1,190 @@
+// k_int4_nominate.hip — the INT4 batch search through a bfloat16 nomination (vg_index_enable_int4_nomination) for gfx950: the
+// kernels that build the nomination's state from the nibble codes, the verify pair's Row, which batches take it, and the pass the
+// search driver (vg_search_int4, k_int4_search.hip) runs for them.
+#include "vg_device.hpp"
+#include "vg_internal.hpp"
+#include "vg_nominate.hpp"
+#include "vg_search.hpp"
+
+// The multi-query scan (int4_search_mq_kernel) decodes every code once per 8 queries and is bound by the vector ALU: 55.3 ms per
+// 1024 queries x 1M x 768.  The reference decodes x^_d = fl(fl(fl(c_d / 15) diff_d) + min_d) (int4_table_kernel, k_int4.hip; int4.go:
+// 152-163).  With c'_d = c_d - 8, an integer in -8 .. 7 that bfloat16 holds exactly, the scale s_d = fl(diff_d / 15), y = c' o s and
+// mid_d = fl(min_d + 8 s_d):  q.x^ ~ (q o s).c' + q.mid.  The GEMM multiplies the query image bf16(fl(q_d s_d)) — the ONLY rounded
+// operand — by the exact c', converted from the row-major codes inside the tile's fill (flat_gemm_int4_big_kernel, vg_flat_gemm.hpp)
+// and, for the sampled tiles, in the call's scratch (int4_sample_rows_kernel, k_flat.hip): both score
+//     s' = |x^|^2 - 2 (q o s).c',
+// the exact L2 score's space moved by |q|^2 and by the per-query constant 2 q.mid, which the verify pair takes back (Int4Row::shift).
+// vg_search_int4 scores L2 under every metric: there is no Dot form.  (Why c - 8 and not 2 c - 15: vg_flat_gemm.hpp, kBigInt4.)
+// The state (NomImage, from_codes with `int4`): rows = mid as dim_pad floats, the scale as dim_pad floats (zeros from dim on, both),
+// then one float H2 = sum_d (|min_d| + |diff_d|)^2 (the margin's decode term); norms = |x^|^2 summed from the decoded values;
+// norm_max = max over the rows of max(|x^|^2, |y|^2), so that 2.002 (|q|^2 + norm_max) lies above every |s'| (flat_thr_cap_kernel)
+// and B = |q|^2 + norm_max scales the margin.  NaN -> +Inf: a non-finite min or diff makes every proof fail and the scan answers.
+// Held: 4 n + 8 dim_pad + 8 bytes — nothing in rows x dim.
+namespace vg {
+// From how many (query, row) pairs a batch takes the nomination.  Measured (MI355X, tools/int4_nominate_time.py, dim 768, ms per
+// call, scan / nominated, both in one run on one index): k = 10 — 129 queries x 100k rows 1.251 / 0.238, 1024 x 100k 5.760 / 0.471,
+// 1024 x 1M 55.607 / 1.802, 1024 x 10M 552.0 / 14.99; k = 100 — 1024 x 1M 112.57 / 2.387.  The nomination won at every shape: the
+// constant is the smallest measured product, 129 x 100k, and nothing below it was measured.  Test hook VG_INT4_NOM_ALWAYS: any.
+constexpr int64_t kInt4NomMinPairs = 12900000;
+
+// one workgroup of 64 lanes: mid, the scale and H2
+__global__ void int4_mid_kernel(const float *__restrict__ mins, const float *__restrict__ diff, int dim, int dim_pad, float *__restrict__ mid)
+{
+    float h2 = 0.0f;
+    for (int j = threadIdx.x; j < dim_pad; j += 64) {
+        const float s = j < dim ? diff[j] / 15.0f : 0.0f;
+        mid[dim_pad + j] = s;
+        mid[j] = j < dim ? __builtin_fmaf(8.0f, s, mins[j]) : 0.0f;  // (8 s is exact: one rounding)
+        if (j < dim) {
+            const float h = fabsf(mins[j]) + fabsf(diff[j]);
+            h2 = __builtin_fmaf(h, h, h2);
+        }
+    }
+    for (int off = 32; off > 0; off >>= 1) h2 += __shfl_xor(h2, off);
+    if (threadIdx.x == 0) mid[2 * dim_pad] = h2;
+}
+// 16 lanes per row (a wave: four rows; lane t of a row takes bytes t, t + 16, ... — any dim, any alignment): |x^|^2 from the
+// reference's three rounded operations, |y|^2 beside it for norm_max.  (The sums' order is this kernel's own: they feed the GEMM's
+// starting value and the margin, which counts dim roundings for them.)
+__global__ __launch_bounds__(256) void int4_codes_norms_kernel(const uint8_t *__restrict__ codes, int64_t n, int dim, const float *__restrict__ mins,
+                                                               const float *__restrict__ diff, float *__restrict__ norms,
+                                                               int *__restrict__ norm_max_bits)
+{
+    const int64_t row = (static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x) >> 4;
+    const int t = threadIdx.x & 15, row_bytes = (dim + 1) / 2;
+    float nrm = 0.0f, cn = 0.0f;
+    if (row < n) {
+        const uint8_t *cp = codes + row * row_bytes;
+        for (int b = t; b < row_bytes; b += 16) {
+            const uint32_t byte = cp[b];
+#pragma unroll
+            for (int e = 0; e < 2; e++) {
+                const int j = 2 * b + e;
+                if (j < dim) {
+                    const uint32_t c = e ? byte & 15u : byte >> 4;
+                    const float a = static_cast<float>(c) / 15.0f;
+                    const float p = a * diff[j];
+                    const float x = p + mins[j];
+                    const float y = static_cast<float>(static_cast<int>(c) - 8) * (diff[j] / 15.0f);
+                    nrm = __builtin_fmaf(x, x, nrm);
+                    cn = __builtin_fmaf(y, y, cn);
+                }
+            }
+        }
+    }
+    for (int off = 8; off > 0; off >>= 1) {
+        nrm += __shfl_xor(nrm, off);
+        cn += __shfl_xor(cn, off);
+    }
+    if (row < n && t == 0) norms[row] = nrm;
+    // NaN -> +Inf, as the SQ8 state's kernels have it (sq8_dequant_bf16_kernel, k_sq8_scan.hip)
+    float mx = 0.0f;
+    if (row < n) mx = nrm == nrm && cn == cn ? fmaxf(nrm, cn) : INFINITY;
+    for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off));
+    if ((threadIdx.x & 63) == 0) atomicMax(norm_max_bits, __float_as_int(mx));  // non-negative floats order like their bits
+}
+
+// the verify pair's Row (vg_nominate.hpp): Int4Quantizer.L2Distance of a nominated row with the bits the scan writes
+// (int4_l2_precomputed on the quantizer's table: vg_device.hpp), the score space's constant and its margin
+struct Int4Row {
+    const uint8_t *rows;  // n * dim / 2
+    const float *table;
+    int dim;
+    const float *mid;  // dim_pad floats, the scale's dim_pad, then H2
+    int dim_pad;
+    static constexpr bool kShifted = true;
+    __device__ float score(int64_t, const float *qv, uint32_t id) const
+    {
+        return int4_l2_precomputed(qv, rows + static_cast<int64_t>(id) * (dim >> 1), dim, table);
+    }
+    __device__ float shift(const float *qv, int lane) const  // the lane's share of q.mid
+    {
+        float c = 0.0f;
+        for (int j = lane; j < dim; j += 64) c = __builtin_fmaf(qv[j], mid[j], c);
+        return c;
+    }
+    // |s' + |q|^2 - 2 q.mid - L2Distance| for any row, u = 2^-24, B = |q|^2 + norm_max, H2 as above.  Sq8CodesRow::eps's terms
+    // (k_sq8_scan.hip) with the INT4 decode in the place of SQ8's single fma:
+    //  query rounding   the image is q_d s_d (1 + d)(1 + b), |d| <= u (the fp32 product), |b| <= 2^-8 (bfloat16, nearest even); the
+    //                   products with c' are exact in fp32: |sum - q.y| <= (2^-8 + 2 u) |q||y| <= (2^-9 + u) B, the score twice that.
+    //                   (|y|^2 <= norm_max up to the (dim + 1) u of its own sum: inside the leading term's 1.001)
+    //  GEMM sum         the tile starts at (t - |x^|^2) / 2 (at most 1.501 B, by flat_thr_cap_kernel), adds dim products (S = sum
+    //                   |products| <= 0.51 B) and the key's fma: screen_gemm_eps's term (k_flat.hip), 4.03 (dim + 16) u
+    //  norms            the stored |x^|^2 is a sum of dim fmas in int4_codes_norms_kernel's order: dim u B
+    //  the decode       x^_d = (c/15 (1 + a) diff_d (1 + b) + min_d)(1 + e) with |a|, |b|, |e| <= u — the rounding of c / 15, of its
+    //                   product with diff, of the sum: two more than SQ8's fma — and y_d + mid_d = c diff_d/15 (1 + g) + min_d +
+    //                   m mid_d with |g| <= u (the rounding of diff / 15 in the scale; 8 s is exact) and |m| <= u (mid's one fma):
+    //                   |x^_d - y_d - mid_d| <= u (3 |c diff_d / 15| + |x^_d| + |mid_d|) + O(u^2).  No row's norm bounds these: min
+    //                   and c diff / 15 may cancel in every row.  Each of the three is at most h_d = |min_d| + |diff_d| (1 + 3 u):
+    //                   |q.x^ - q.(y + mid)| <= 5 u |q| sqrt(H2) <= 2.5 u (|q|^2 + H2), the score twice that; taken as 6 u for the
+    //                   second-order terms
+    //  q.mid            the wave's sum: dim / 64 fmas and 6 additions, (dim / 64 + 8) u |q||mid|, and |mid| <= |x^| + |y| + the
+    //                   decode term <= 2 sqrt(norm_max) (1 + O(u)), |q||mid| <= B; taken twice: (dim / 32 + 16) u
+    //  the comparison   tau + |q|^2 - 2 q.mid - eps: three roundings of at most 5 B, and |q|^2 as the kernel sums it,
+    //                   (dim / 64 + 7) u: 16 u + (dim / 64 + 7) u
+    //  the reference    int4L2DistancePrecomputedAvx512's order: q_d - x^_d rounded (2 u on its square), sixteen lane sums of dim / 16
+    //                   fmas each (a 32-block feeds its two halves into the same sixteen, in order), the four-level tree over them
+    //                   and the tail: (dim / 16 + 23) u |q - x^|^2 <= (dim / 8 + 46) u B
+    //  2^-8 + 2 u + (4.03 (dim + 16) + dim + dim / 32 + 16 + 16 + dim / 64 + 7 + dim / 8 + 46) u  <=  2^-8 1.001 + (6 dim + 160) u,
+    //  + 6 u (|q|^2 + H2).  At dim 768: 4.19e-3 B.  Denormal products the matrix unit may flush: below 1e-35 dim, inside the absolute
+    // term.  tests/test_int4_nomination_bound_cpu.py models the sums.
+    __device__ float eps(float qn, float norm_max) const
+    {
+        const float d = static_cast<float>(dim), u = 5.9604645e-8f;
+        return (0.00390625f * 1.001f + (6.0f * d + 160.0f) * u) * (qn + norm_max) + 6.0f * u * (qn + mid[2 * dim_pad]) + 1e-30f;
+    }
+};
+
+// The nomination takes more than 128 queries — the persistent tile's batches; the register-staged fill has no 128-row form — over
+// the whole segment, unfiltered, rows of whole 16-byte halves of a K step (dim % 32 == 0), from kInt4NomMinPairs pairs up.
+// (device queries; mask: the batch's row filter, or null)
+bool int4_nomination_applies(const vg_index *idx, const float *d_queries, int64_t nq, int k, const uint8_t *mask)
+{
+    if (!idx->i4_nom.rows || mask || nq <= 128 || idx->dim % 32 != 0) return false;
+    if (nq * idx->n < kInt4NomMinPairs && !hook(kHookInt4NomAlways)) return false;
+    return k <= kNomMaxK && idx->n > k && aligned16(d_queries);
+}
+// nominated_pass with the INT4 re-score
+int32_t int4_nominated_pass(vg_index *idx, const float *q, int64_t nq, int k, uint32_t *oid, float *osc, hipStream_t st, std::vector<int> &failed)
+{
+    const NomImage &img = idx->i4_nom;
+    const size_t before = failed.size();
+    const Int4Row row{idx->d_int4_rows, idx->int4_table, idx->dim, reinterpret_cast<const float *>(img.rows), img.dim_pad};
+    VG_TRY(nominated_pass(idx, img, false, q, nq, k, nullptr, 0, 0, oid, osc, st, failed,
+                          [&](const float *qq, int64_t cnt, const ProbeNominated &nom, float *, uint32_t *ids, float *scores, int *fail) -> int32_t {
+                              return launch_nominated_verify<false>(row, qq, img.norm_max, cnt, nom, k, ids, scores, fail, st);
+                          }));
+    idx->i4_nom_rescanned += static_cast<int64_t>(failed.size() - before);  // (vg_index_int4_nomination_info)
+    return VG_OK;
+}
+}  // namespace vg
+
+VG_API int32_t vg_index_enable_int4_nomination(vg_index *idx, int32_t on, void *stream)
+{
+    VG_CHECK(idx, VG_ERR_INVALID_ARG, "vg_index_enable_int4_nomination: NULL index");
+    VG_HIP(hipSetDevice(idx->ctx->device));
+    hipStream_t st = vg::pick_stream(idx->ctx, stream);
+    VG_TRY(vg::nom_free(idx->i4_nom, st));
+    if (!on) return VG_OK;
+    VG_CHECK(idx->d_int4_rows && idx->int4_min && idx->int4_diff, VG_ERR_NOT_READY, "vg_index_enable_int4_nomination: index has no INT4 codes");
+    idx->i4_nom_rescanned = 0;
+    const int dim_pad = vg::nom_dim_pad(idx->dim);
+    // mid, the scale and H2 in the rows' place (8 dim_pad + 4 bytes), the norms, norm_max
+    VG_TRY(vg::nom_build(idx->i4_nom, idx->n, idx->dim, static_cast<int64_t>(2 * dim_pad + 1) * 4, true, st, [&](const vg::NomImage &b, int *norm_max_bits) {
+        hipLaunchKernelGGL(vg::int4_mid_kernel, dim3(1), dim3(64), 0, st, idx->int4_min, idx->int4_diff, idx->dim, b.dim_pad, reinterpret_cast<float *>(b.rows));
+        hipLaunchKernelGGL(vg::int4_codes_norms_kernel, dim3(static_cast<unsigned>((idx->n + 15) / 16)), dim3(256), 0, st, idx->d_int4_rows, idx->n, idx->dim,
+                           idx->int4_min, idx->int4_diff, b.norms, norm_max_bits);
+    }));
+    idx->i4_nom.int4 = true;
+    idx->i4_nom.scale = reinterpret_cast<const float *>(idx->i4_nom.rows) + dim_pad;
+    return VG_OK;
+}
+
+VG_API int32_t vg_index_int4_nomination_info(const vg_index *idx, int32_t *mode, int64_t *held_bytes, int64_t *rescanned)
+{
+    VG_CHECK(idx, VG_ERR_INVALID_ARG, "vg_index_int4_nomination_info: NULL index");
+    if (mode) *mode = idx->i4_nom.rows ? 1 : 0;
+    if (held_bytes) *held_bytes = idx->i4_nom.held_bytes(idx->n);
+    if (rescanned) *rescanned = idx->i4_nom.rows ? idx->i4_nom_rescanned : 0;
+    return VG_OK;
+}

@@ -11,6 +11,7 @@
 #include "vg_int4_plan.hpp"
 #include "vg_int4_scan.hpp"
 #include "vg_internal.hpp"
+#include "vg_nominate.hpp"
 #include "vg_scan_slices.hpp"
 #include "vg_search.hpp"
 
@@ -423,7 +424,18 @@ VG_API int32_t vg_search_int4(vg_index *idx, const float *queries, int64_t nq, i
         VG_TRY(vg::empty_results(nq, k, false, io.oid.ptr, io.osc.ptr, st));
     } else {
         const int64_t stride = nq > 1 ? mask_stride : 0;
-        VG_TRY(vg::int4_scan_batch(idx, io.q.ptr, nq, k, io.mk.ptr, stride, io.oid.ptr, io.osc.ptr, st));
+        if (vg::int4_nomination_applies(idx, io.q.ptr, nq, k, io.mk.ptr)) {
+            // vg_index_enable_int4_nomination (k_int4_nominate.hip): the matrix-core nomination, the exact re-score and the proof; the
+            // scan for the queries whose proof failed (ties at the k-th score, thresholds too tight)
+            std::vector<int> failed;
+            VG_TRY(vg::int4_nominated_pass(idx, io.q.ptr, nq, k, io.oid.ptr, io.osc.ptr, st, failed));
+            VG_TRY(vg::rescan_failed(failed, io.q.ptr, idx->dim, k, nullptr, 0, 0, io.oid.ptr, io.osc.ptr, st,
+                                     [&](const float *fq, int64_t nf, const uint8_t *, int64_t, uint32_t *fid, float *fsc) {
+                                         return vg::int4_scan_batch(idx, fq, nf, k, nullptr, 0, fid, fsc, st);
+                                     }));
+        } else {
+            VG_TRY(vg::int4_scan_batch(idx, io.q.ptr, nq, k, io.mk.ptr, stride, io.oid.ptr, io.osc.ptr, st));
+        }
         // queries whose distances may hold a NaN: the reference's heap, operation by operation (vg_cand_replay.hpp)
         VG_TRY(vg::launch_cand_replay(vg::Int4Scorer{idx->d_int4_rows, idx->int4_table, idx->int4_min, idx->int4_diff, idx->dim}, io.q.ptr,
                                       idx->dim, idx->n, nq, k, false, io.mk.ptr, stride, io.oid.ptr, io.osc.ptr, st));

@@ -339,6 +339,7 @@ VG_API int32_t vg_vamana_reorder_bfs(vg_index *idx, uint32_t *perm, uint32_t *in
     need(idx->d_sq_tiles, idx->n_tiles * idx->sq_groups * 64 * 16);
     need(idx->sq_nom.row_image(), n * idx->sq_nom.dim_pad * 2);
     need(idx->d_int4_rows, n * int4_row);
+    need(idx->i4_nom.norms, n * 4);
 
     // BFS state: order (perm), inv (inv_perm), the large levels' keys, masks and counts, and the scratch
     vg::DevTmp<uint32_t> order, inv, counts;
@@ -423,8 +424,9 @@ VG_API int32_t vg_vamana_reorder_bfs(vg_index *idx, uint32_t *perm, uint32_t *in
         // (from the codes: no row image, the norms alone move with the codes)
         VG_TRY(vg::rb_permute_rows(idx->sq_nom.row_image(), n, static_cast<int64_t>(idx->sq_nom.dim_pad) * 2, p, scratch, st));
         VG_TRY(vg::rb_permute_rows(idx->sq_nom.norms, n, 4, p, scratch, st));
-        // INT4 rows
+        // INT4 rows, and the norms of their nomination (nothing else of it follows the rows)
         VG_TRY(vg::rb_permute_rows(idx->d_int4_rows, n, int4_row, p, scratch, st));
+        VG_TRY(vg::rb_permute_rows(idx->i4_nom.norms, n, 4, p, scratch, st));
     }
     if (perm) VG_HIP(hipMemcpyAsync(perm, order.ptr, static_cast<size_t>(n) * 4, hipMemcpyDefault, st));
     if (inv_perm) VG_HIP(hipMemcpyAsync(inv_perm, inv.ptr, static_cast<size_t>(n) * 4, hipMemcpyDefault, st));

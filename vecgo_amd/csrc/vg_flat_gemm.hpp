@@ -701,7 +701,41 @@ __device__ __forceinline__ void split2_bf16(float a, float b, uint32_t &hi, uint
 // vector-memory operations of a step are the query tile's four pieces, then this fill's four loads (of the step after next), so
 // the step's end waits vmcnt(4) — the queries have landed, the loads may fly — and the fill waits vmcnt(4) for its own loads of the
 // step before, behind which went only this step's four query pieces.
-enum { kBigImages = 0, kBigSplit = 1, kBigScreen = 2, kBigCodes = 3, kBigSq8 = 4 };
+// OPS = kBigInt4 (flat_gemm_int4_big_kernel): the bf16 tile of kBigImages over INT4 codes, no row image and no re-tiled copy.  The row
+// operand is bf16(c - 8), c the nibble — an integer in -8 .. 7 — and `codes` is the index's own row-major rows: code_m = dim / 2
+// bytes a row (dim % 32 == 0: every row and every half of a K step is 16-byte aligned), dimension 2 b in the HIGH nibble of byte b.
+// (c - 8, scale diff / 15, and not the symmetric 2 c - 15 with diff / 30: both are exact in bfloat16, but c - 8 is the nibble with
+// its top bit flipped read as a signed 4-bit field — one v_xor_b32 per 8 nibbles and one v_bfe_i32 each — where 2 c - 15 takes a
+// shift-and-add more per nibble in a fill that is all vector ALU; the half-step by which c - 8 is off centre moves |y| by
+// diff / 30 a dimension, nothing beside the query's 2^-8.)  A K step of a 256-row tile is 256 x 32 bytes, ONE 16-byte load per
+// lane: lane l of wave w reads row 32 w + (l >> 1), half l & 1, at row * code_m + 32 s + 16 (l & 1) — two neighbouring lanes read 32
+// contiguous bytes — one row-tile step AHEAD of its fill, as kBigSq8 loads its code bytes.  When the step is staged the lane turns its
+// four words into four granules (word k = bytes 4 k .. 4 k + 3 = dimensions 8 k .. 8 k + 7 of the half: int -> float ->
+// v_cvt_pk_bf16_f32, all exact) and writes them with four ds_write_b128 where the image's fill would have put granules 4 (l & 1) + k
+// of that row: slot = granule ^ ((row >> 1) & 7).  (The other conversion, a 256-entry LDS table from a code byte to its bf16 pair, was
+// not built: the tile's five buffers are the CU's whole 160 KiB, and 16 more LDS reads per lane and step go through the port the
+// operand reads already fill.)  Bank groups: the 16 lanes of a write pass are 8 consecutive rows R (from a multiple of 8) x 2 halves,
+// for a fixed k.  A row is 128 B, so its 16-byte bank group is 8 (R & 1) + slot; over the 8 rows (R >> 1) & 7 takes four consecutive
+// values f (each with both parities), k ^ f four different low bit pairs, and the two halves differ in bit 2 of the granule: 8
+// different slots per parity, 16 different bank groups, no conflict.  The ds_read_b128 side is kBigImages': the tile in LDS is bit
+// for bit the image's.  Seams: dim % 64 == 32 — the last K step's second half lies past the row: its lanes re-read the first half
+// (the bytes behind the row are the next row's, or past the allocation) and write zeros; rows past n re-read the last row (never
+// appended).  The counted waits: a wave's vector-memory operations of a step are the query tile's four pieces, then this fill's ONE
+// load (of the step after next), so the step's end waits vmcnt(1) — the queries have landed, the load may fly — and the fill waits
+// vmcnt(4) for its own load of the step before, behind which went only this step's four query pieces.  (More operations behind the
+// load — a finished tile's appends — only make the same count wait for more: retirement is in order.)
+enum { kBigImages = 0, kBigSplit = 1, kBigScreen = 2, kBigCodes = 3, kBigSq8 = 4, kBigInt4 = 5 };
+// a word of INT4 codes with every nibble's top bit flipped (x = bytes ^ 0x88888888) as its granule of 8 bfloat16: nibble - 8, the
+// high nibble of a byte first
+typedef uint32_t vg_u32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ uint4 int4_word_bf16(uint32_t x)
+{
+    auto pair = [x](int at) {  // byte at / 8: its high, then its low nibble, as signed 4-bit fields
+        const float a = static_cast<float>(static_cast<int>(x << (24 - at)) >> 28), b = static_cast<float>(static_cast<int>(x << (28 - at)) >> 28);
+        return __builtin_bit_cast(uint32_t, __builtin_convertvector(vg_f32x2{a, b}, vg_bf16x2));
+    };
+    return make_uint4(pair(0), pair(8), pair(16), pair(24));
+}
 // SAMPLE (flat_gemm_sample_big_kernel): the score-writing form, MODE 1 of the 128 x 128 tiles on this tile — the rows are every
 // tile_stride-th 128-row tile, written compactly into scores[q][out_cols] as the 128-row kernels write them, so a 256-row tile
 // is a PAIR of sampled 128-row tiles: sample tile ts takes rows [(2 ts) stride 128, + 128) through fill pieces 0-1 and rows
@@ -730,6 +764,8 @@ __device__ __forceinline__ void flat_gemm_big_body(
     static_assert(!CODES || (NB == 3 && !SAMPLE && PROBE == 0), "the code-gathered tile: three row buffers, the append form");
     constexpr bool SQ8 = OPS == kBigSq8;
     static_assert(!SQ8 || (NB == 3 && !SAMPLE && PROBE == 0), "the SQ8 code tile: three row buffers, the append form");
+    constexpr bool INT4 = OPS == kBigInt4;
+    static_assert(!INT4 || (NB == 3 && !SAMPLE && PROBE == 0 && !DOT), "the INT4 code tile: three row buffers, the append form, L2");
     extern __shared__ float gemm_lds[];
     const int mtiles = static_cast<int>((nq + kBigBM - 1) / kBigBM);
     // (SAMPLE: the pairs of sampled 128-row tiles)
@@ -815,7 +851,7 @@ __device__ __forceinline__ void flat_gemm_big_body(
             // this wave's 64-row code tile of the row tile (rows 32 w ..: tile w >> 1), the last one that exists at most
             const int64_t t64 = static_cast<int64_t>(tn_of(ps)) * 4 + (wave >> 1), t_last = (n + 63) / 64 - 1;
             kbase = codes + (t64 < t_last ? t64 : t_last) * code_m * 1024;
-        } else if constexpr (CODES)
+        } else if constexpr (CODES || INT4)  // (INT4: code_m = the bytes of a row)
             kbase = codes + n0 * code_m;
         else
             bbase = base + n0 * dim;
@@ -977,7 +1013,55 @@ __device__ __forceinline__ void flat_gemm_big_body(
         }
         ib = ib + 1 == NB ? 0 : ib + 1;
     };
+    // kBigInt4.  The cursor and f_k as for kBigCodes; i4 = the lane's 16 code bytes of the step to fill next, i4_past whether they
+    // are the half past the row's end (then: the first half again, written as zeros).
+    vg_u32x4 i4 = {0u, 0u, 0u, 0u};
+    bool i4_past = false;
+    const int i4_row = wave * 32 + (lane >> 1), i4_half = lane & 1;
+    auto load_int4 = [&]() {
+        f_k = b_k;
+        const int at = b_k * 32 + i4_half * 16;  // the half's first byte of the row
+        i4_past = at >= code_m;
+        const uint32_t voff = static_cast<uint32_t>((i4_row < b_last ? i4_row : b_last) * code_m + (i4_past ? at - 16 : at));
+        asm volatile("global_load_dwordx4 %0, %1, %2" : "=v"(i4) : "v"(voff), "s"(kbase) : "memory");
+        if (++b_k == ksteps) {
+            b_k = 0;
+            if (b_pos.bt < total) {
+                step(b_pos);
+                if (b_pos.bt < total) set_b(b_pos);  // (past the stream's end: the last tile's codes once more, never multiplied)
+            }
+        }
+    };
+    // W: vector-memory operations younger than i4's load that may still be in flight (0: the prologue waits for everything)
+    auto stage_int4 = [&](auto W) {
+        // (the wait and the FIRST reads of i4 in one statement, as stage_codes has them; the reads flip every nibble's top bit)
+        uint32_t x[4];
+#define VG_INT4_TAKE(cnt)                                                                                                        \
+    asm volatile("s_waitcnt vmcnt(" #cnt ")\n\tv_xor_b32 %0, %8, %4\n\tv_xor_b32 %1, %8, %5\n\tv_xor_b32 %2, %8, %6\n\tv_xor_b32 %3, %8, %7" \
+                 : "=&v"(x[0]), "=&v"(x[1]), "=&v"(x[2]), "=&v"(x[3])                                                           \
+                 : "v"(i4.x), "v"(i4.y), "v"(i4.z), "v"(i4.w), "s"(0x88888888u)                                                 \
+                 : "memory")
+        if constexpr (decltype(W)::value == 4)
+            VG_INT4_TAKE(4);
+        else
+            VG_INT4_TAKE(0);
+#undef VG_INT4_TAKE
+        const bool past = i4_past;
+        load_int4();
+        float *const dst = gemm_lds + b_buf(ib) + i4_row * kGemmBK;
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            uint4 o = int4_word_bf16(x[k]);
+            if (past) o = make_uint4(0u, 0u, 0u, 0u);
+            *reinterpret_cast<uint4 *>(dst + ((4 * i4_half + k) ^ ((i4_row >> 1) & 7)) * 4) = o;
+        }
+        ib = ib + 1 == NB ? 0 : ib + 1;
+    };
     auto stage_b = [&]() {
+        if constexpr (INT4) {
+            stage_int4(std::integral_constant<int, 4>{});
+            return;
+        }
         if constexpr (SQ8) {
             stage_sq8(std::integral_constant<int, 4>{});
             return;
@@ -1371,9 +1455,13 @@ __device__ __forceinline__ void flat_gemm_big_body(
     // computed under them, then published
     if constexpr (CODES) load_codes();  // (of the first step)
     if constexpr (SQ8) load_sq8();
+    if constexpr (INT4) load_int4();
     tile_loads(pos0);
     stage_a();
-    if constexpr (SQ8) {
+    if constexpr (INT4) {
+        stage_int4(std::integral_constant<int, 0>{});
+        if (S > 1) stage_int4(std::integral_constant<int, 0>{});
+    } else if constexpr (SQ8) {
         stage_sq8(std::integral_constant<int, 0>{});
         if (S > 1) stage_sq8(std::integral_constant<int, 0>{});
     } else if constexpr (CODES) {
@@ -1387,11 +1475,13 @@ __device__ __forceinline__ void flat_gemm_big_body(
     tile_init();
     if (CODES && S > 1)
         asm volatile("s_waitcnt vmcnt(8)" ::: "memory");  // (the second step's four pieces and the third's four code bytes)
+    else if (INT4 && S > 1)
+        asm volatile("s_waitcnt vmcnt(1)" ::: "memory");  // (the third step's one code load)
     else if (NB == 3 && S > 1)
         asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
     else
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if constexpr (SQ8) __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): the first tiles' LDS writes (behind them: the third step's four loads)
+    if constexpr (SQ8 || INT4) __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): the first tiles' LDS writes (behind them: the third step's four loads)
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
     int ra = 0, rb = 0;  // buffers the current step is read from
@@ -1443,6 +1533,8 @@ __device__ __forceinline__ void flat_gemm_big_body(
         __builtin_amdgcn_s_waitcnt(0xC07F);
         if (CODES && g + 2 < S)  // (kBigCodes: behind query tile g+1 went the code bytes of row tile g+3 and row tile g+2's four pieces)
             asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+        else if (INT4 && g + 2 < S)  // (kBigInt4: behind query tile g+1 went the ONE code load of row tile g+3)
+            asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
         else if (NB == 3 && g + 2 < S)
             asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
         else
@@ -1526,6 +1618,17 @@ __global__ __launch_bounds__(kBigThreads) void flat_gemm_sq8_big_kernel(
 {
     flat_gemm_big_body<DOT, NB, 0, kBigSq8>(queries, nq, base, n, dim, norms, thr, thr_stride, thr_off, counts, cand, cap, mask, mask_stride,
                                             count_stride, nullptr, nullptr, 1, 0, tiles, groups);
+}
+// bf16 queries (scaled by diff / 15) against the index's row-major INT4 codes, centred and converted in registers (kBigInt4):
+// `base` is not read, dim = words per padded row, `codes` the n rows of row_bytes = (the rows' dimensions) / 2 bytes; L2
+template <int NB>
+__global__ __launch_bounds__(kBigThreads) void flat_gemm_int4_big_kernel(
+    const float *__restrict__ queries, int64_t nq, const float *__restrict__ base, int64_t n, int dim, const float *__restrict__ norms,
+    const float *__restrict__ thr, int thr_stride, int thr_off, int *__restrict__ counts, uint64_t *__restrict__ cand, int cap,
+    const uint8_t *__restrict__ mask, int64_t mask_stride, int count_stride, const uint8_t *__restrict__ codes, int row_bytes)
+{
+    flat_gemm_big_body<false, NB, 0, kBigInt4>(queries, nq, base, n, dim, norms, thr, thr_stride, thr_off, counts, cand, cap, mask, mask_stride,
+                                               count_stride, nullptr, nullptr, 1, 0, codes, row_bytes);
 }
 // the same operands, the product of the hi halves alone (the screen in front of the split tile)
 template <bool DOT, int NB, int PROBE = 0>

@@ -109,6 +109,7 @@ enum Hook {
     kHookInt4SearchSmallGrid, // VG_INT4_SEARCH_SMALL_GRID vg_search_int4 launches at most 2 workgroups / 2 slices (the table form through vg_int4_plan.hpp's cap): a few thousand rows give every wave several trips and the merge several lists
     kHookAdcWideAlways,       // VG_ADC_WIDE_ALWAYS    every PQ probed, filtered or threshold scan walks its table in chunks (adc_wide_walk, vg_adc_wide.hpp) whatever m is: the chunk seams at a few rows, wide against narrow results on one index
     kHookRabitqNomAlways,     // VG_RABITQ_NOM_ALWAYS  vg_index_enable_rabitq_nomination: no crossover of (query, row) pairs
+    kHookInt4NomAlways,       // VG_INT4_NOM_ALWAYS    vg_index_enable_int4_nomination: no crossover of (query, row) pairs
     kHookRabitqNomCheck,      // VG_RABITQ_NOM_CHECK   vg_index_enable_rabitq_nomination: the verify compares every listed key's Hamming distance (the GEMM's) with its own popcount and counts the disagreements (vg_index_rabitq_nomination_info's `mismatched`)
     kHookCount
 };
@@ -483,6 +484,10 @@ struct NomImage {
     // `rows` holds dim_pad floats, mid_d = min_d + 128 inv_d (zeros from dim on) — the offset of its score space; the GEMM's row
     // tile is converted from the code tiles, bf16(code - 128), and the queries are multiplied by `scale` before they are rounded.
     const float *scale = nullptr;  // the quantizer's inverse scales (borrowed), or null
+    // The INT4 nomination (vg_index_enable_int4_nomination, k_int4_nominate.hip): from_codes with `int4` set.  `rows` holds mid_d =
+    // min_d + 8 scale_d as dim_pad floats, the scale diff_d / 15 as dim_pad floats behind them (`scale` points there; both zeros from
+    // dim on) and one float H2 (Int4Row::eps); the GEMM's row tile is converted from the index's row-major nibble codes, bf16(c - 8).
+    bool int4 = false;
     int64_t body = 0;              // bytes of `rows`
     // what vg_index_pq_nomination_info reports: 0 off, 1 the image of the decoded rows, 2 from the codes
     int mode() const { return !rows ? 0 : from_codes ? 2 : 1; }
@@ -561,6 +566,8 @@ struct vg_index {
     int32_t sq_groups = 0;  // ceil(dim/16)
     // INT4 codes of a DiskANN segment, row-major n * ceil(dim/2), and the quantizer's lookup table
     uint8_t *d_int4_rows = nullptr;
+    vg::NomImage i4_nom;               // vg_index_enable_int4_nomination: the score space's offset and scale, the rows' norms
+    int64_t i4_nom_rescanned = 0;      // queries whose proof failed and the scan answered, since i4_nom was enabled
     const float *int4_table = nullptr;  // borrowed from the vg_int4
     const float *int4_min = nullptr, *int4_diff = nullptr;  // (same)
     // IVF partitions of a flat segment: centroids [P*dim], first row of every partition [P+1]

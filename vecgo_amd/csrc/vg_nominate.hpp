@@ -26,7 +26,8 @@ inline int nominate_sel_k(int k) { return k <= kNomPickMaxK ? 8 : k <= 128 ? 16 
 struct GemmGroup;  // vg_flat_gemm.hpp
 // k_flat.hip
 // cnt queries' nomination for their k best on `img`, *nom and all it points to in `scratch` (flat_nominate_bf16_scratch bytes)
-// (img.from_codes, a nomination from the codes: unfiltered; PQ: L2; SQ8, img.scale: L2 and Dot, more than 128 queries)
+// (img.from_codes, a nomination from the codes: unfiltered; PQ: L2; SQ8, img.scale: L2 and Dot, more than 128 queries; INT4,
+// img.int4: L2, more than 128 queries, dim % 32 == 0)
 size_t flat_nominate_bf16_scratch(int64_t cnt, int64_t n, const NomImage &img, int k);
 int32_t flat_nominate_bf16(vg_index *idx, const NomImage &img, bool dot, const float *queries, int64_t cnt, const uint8_t *mask,
                            int64_t mask_stride, int k, char *scratch, hipStream_t st, ProbeNominated *nom);
@@ -44,6 +45,9 @@ int32_t sq8_nominated_pass(vg_index *idx, const float *q, int64_t nq, int k, con
 // k_pq_nominate.hip (ascending table sums over the whole segment: mask null, desc false, or the batch does not apply)
 bool pq_nomination_applies(const vg_index *idx, const float *d_queries, int64_t nq, int k, const uint8_t *mask, bool desc);
 int32_t pq_nominated_pass(vg_index *idx, const float *q, int64_t nq, int k, uint32_t *oid, float *osc, hipStream_t st, std::vector<int> &failed);
+// k_int4_nominate.hip (L2 over the whole segment: mask null, or the batch does not apply)
+bool int4_nomination_applies(const vg_index *idx, const float *d_queries, int64_t nq, int k, const uint8_t *mask);
+int32_t int4_nominated_pass(vg_index *idx, const float *q, int64_t nq, int k, uint32_t *oid, float *osc, hipStream_t st, std::vector<int> &failed);
 
 // Builds the nomination state of n rows of dim elements into `img` (empty): its body of body_bytes (NomImage::body_bytes — the
 // decoded rows, or from_codes the decoded codebook), the norms and norm_max.  launch(const NomImage &, int *norm_max_bits) launches
