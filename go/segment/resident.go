@@ -730,7 +730,14 @@ func (r *Resident) EnableInt4Nomination(on bool) error {
 	return hipctx.Err(int32(C.vg_index_enable_int4_nomination(r.h, v, nil)))
 }
 
-// Int4NominationInfo: mode 1 while the nomination is enabled, the device bytes it keeps resident, and the queries whose proof
+// EnableInt4NominationSmallBatches: EnableInt4Nomination(true), and unfiltered batches of 5 .. 128 queries take the nomination too
+// (mode 2; dim <= 2496, from their own crossover up), on a GEMM of one query tile that reads the codes straight into the matrix
+// instruction's registers.  Nothing more is resident.  Filtered batches, fewer than 5 queries, dim % 32 != 0 and k > 256 keep the scan.
+func (r *Resident) EnableInt4NominationSmallBatches() error {
+	return hipctx.Err(int32(C.vg_index_enable_int4_nomination(r.h, C.int32_t(2), nil)))
+}
+
+// Int4NominationInfo: mode 1 while the nomination is enabled (2: with small batches), the device bytes it keeps resident, and the queries whose proof
 // failed and the scan answered since the mode was enabled.
 func (r *Resident) Int4NominationInfo() (mode int, heldBytes, rescanned int64, err error) {
 	var m C.int32_t

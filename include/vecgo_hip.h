@@ -1685,10 +1685,14 @@ int32_t vg_index_rabitq_nomination_info(const vg_index *idx, int32_t *on, int64_
  * INT4 codes VG_ERR_NOT_READY.  on == 0 turns the mode off; enabling again rebuilds the state and zeroes the counter;
  * vg_index_set_int4_codes (vg_diskann_build's included) drops it; vg_vamana_reorder_bfs moves the norms with the codes.  Batches it
  * takes: unfiltered (mask NULL), MORE THAN 128 queries, k <= 256, rows > k, dim % 32 == 0, 16-byte aligned device queries, and
- * queries x rows at or above its crossover against the scan (README, Limits); every other batch runs the scan as before.  Found by
- * symbol lookup. */
+ * queries x rows at or above its crossover against the scan (README, Limits); every other batch runs the scan as before.
+ * on == 2 (any other non-zero value is 1): the same, and unfiltered batches of 5 .. 128 queries take the nomination too, under
+ * the same conditions and dim <= 2496, from their own crossover up — on a GEMM of one query tile whose waves read the codes from
+ * global memory straight into the matrix instruction's registers, the queries' image resident in LDS (97 .. 128 queries from
+ * dim 608 on run as two launches of two 32-query blocks).  Nothing more is resident.  Still the scan's: filtered batches, fewer
+ * than 5 queries, dim % 32 != 0, k > 256.  Found by symbol lookup. */
 int32_t vg_index_enable_int4_nomination(vg_index *idx, int32_t on, void *stream);
-/* *mode = 1 while the mode is enabled, else 0; *held_bytes = the device memory it keeps resident; *rescanned = the queries, since the
+/* *mode = 1 while the mode is enabled, 2 when it was enabled with on == 2, else 0; *held_bytes = the device memory it keeps resident; *rescanned = the queries, since the
  * mode was enabled, whose proof failed and which the scan answered (0 when off).  Any pointer may be NULL.  Found by symbol lookup. */
 int32_t vg_index_int4_nomination_info(const vg_index *idx, int32_t *mode, int64_t *held_bytes, int64_t *rescanned);
 

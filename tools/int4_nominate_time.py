@@ -3,8 +3,10 @@
 min and max: the run's spread), the GEMM's share from the profile scope, what the mode keeps resident, the queries the scan had to
 answer again, and equality of the results.  Last, the SQ8 nomination from the codes at 1024 x 1M, k = 10, for the comparison the
 two tiles invite (the same tile, half the fill bytes).
-    python tools/int4_nominate_time.py [max_rows]
-Segments of 100k and 1M rows, and of 10M with max_rows >= 10000000 (the rows are encoded a million at a time)."""
+    python tools/int4_nominate_time.py [max_rows] [small]
+Segments of 100k and 1M rows, and of 10M with max_rows >= 10000000 (the rows are encoded a million at a time).
+small: the batches of 8 .. 128 queries that the mode takes when enabled with small_batches (flat_gemm_int4_small_kernel) instead —
+windows of ~300 ms, the GEMM's share from its own profile scope, no SQ8 comparison: where kInt4NomSmallMinPairs comes from."""
 import statistics
 import sys
 from pathlib import Path
@@ -13,6 +15,8 @@ import torch
 import vecgo_amd as vg, bench
 ctx = vg.Context(0); dev = torch.device("cuda", 0)
 max_rows = int(sys.argv[1]) if len(sys.argv) > 1 else 1_000_000
+SMALL = "small" in sys.argv[2:]
+WINDOW_MS = 300 if SMALL else 20
 q = bench.gen_queries(2, dev)[0]
 st = torch.cuda.current_stream()
 iq = vg.Int4Quantizer(ctx, 768)
@@ -23,7 +27,7 @@ for lo in range(0, codes.shape[0], 1_000_000):
 from tests import hooks
 hooks.set_hook("VG_INT4_NOM_ALWAYS", 1)                  # every batch above 128 queries takes the mode: where the crossover is
 hooks.set_hook("VG_SQ8_NOM_CODES_ALWAYS", 1)
-SCOPE = "int4_codes_gemm"
+SCOPE = "int4_codes_gemm_small" if SMALL else "int4_codes_gemm"
 
 
 def window(search, qs, k, reps):
@@ -44,8 +48,8 @@ def shape(idx, n, nq, k, windows=5):
     ms, res = {0: [], 1: []}, {}
     for w in range(windows + 1):                         # the legs alternate; the first round warms up
         for md in (0, 1):
-            idx.enable_int4_nomination(bool(md))
-            reps = max(1, int(20 / (55e-9 * nq * n * (1 if md == 0 else 0.05) + 0.2)))   # ~20 ms a window, at least one call
+            idx.enable_int4_nomination(bool(md), small_batches=SMALL)
+            reps = max(1, int(WINDOW_MS / (55e-9 * nq * n * (1 if md == 0 else 0.05) + 0.2)))   # ~WINDOW_MS a window, at least one call
             t, res[md] = window(idx.search_int4, qs, k, reps)
             if w:
                 ms[md].append(t)
@@ -54,7 +58,7 @@ def shape(idx, n, nq, k, windows=5):
     idx.search_int4(qs, k, stream=st); torch.cuda.synchronize()
     l, gms = ctx.profile_read(SCOPE); ctx.profile_enable(False)
     rescanned = idx.int4_nomination_info()[2]            # (of the calls since the mode was last enabled; the queries of one call fail alike)
-    calls = max(1, int(20 / (55e-9 * nq * n * 0.05 + 0.2))) + 2
+    calls = max(1, int(WINDOW_MS / (55e-9 * nq * n * 0.05 + 0.2))) + 2
     line = f"{n:8d} rows  k {k:3d}  {nq:5d} queries:"
     for md, name in ((0, "scan"), (1, "nominated")):
         line += f"  {name} {statistics.median(ms[md]):8.3f} ms [{min(ms[md]):.3f} .. {max(ms[md]):.3f}]"
@@ -64,6 +68,8 @@ def shape(idx, n, nq, k, windows=5):
 
 
 PLAN = [(100_000, [(129, 10), (1024, 10)]), (1_000_000, [(1024, 10), (1024, 100)]), (10_000_000, [(1024, 10)])]
+if SMALL:
+    PLAN = [(n, [(nq, 10) for nq in (8, 32, 64, 96, 128)] + ([(128, 100)] if n == 1_000_000 else [])) for n in (100_000, 1_000_000, 10_000_000)]
 int4_ms = None
 for n, shapes in PLAN:
     if n > codes.shape[0]:
@@ -77,6 +83,8 @@ for n, shapes in PLAN:
             int4_ms = t
     idx.close()
 del codes
+if SMALL:
+    sys.exit(0)
 rows = bench.gen_rows(0, 1_000_000, dev)
 sq = vg.ScalarQuantizer(ctx, 768)
 sq.train(rows[:65536])

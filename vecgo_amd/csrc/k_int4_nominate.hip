@@ -26,6 +26,14 @@ namespace vg {
 // 1024 x 1M 55.607 / 1.802, 1024 x 10M 552.0 / 14.99; k = 100 — 1024 x 1M 112.57 / 2.387.  The nomination won at every shape: the
 // constant is the smallest measured product, 129 x 100k, and nothing below it was measured.  Test hook VG_INT4_NOM_ALWAYS: any.
 constexpr int64_t kInt4NomMinPairs = 12900000;
+// The same for batches of 5 .. 128 queries under on = 2 (flat_gemm_int4_small_kernel).  Measured (MI355X, tools/int4_nominate_time.py
+// [max_rows] small, dim 768, k = 10, ms per call, scan / nominated, alternating windows of ~300 ms in one run on one index; the windows
+// of a leg lay within 1 % of each other, 3 % at one shape): 100k rows — 8 queries 0.198 / 0.173, 32 0.383 / 0.175, 64 0.592 / 0.200,
+// 96 0.995 / 0.218, 128 0.956 / 0.254; 1M — 8 0.662 / 0.269, 32 2.010 / 0.279, 64 3.720 / 0.363, 96 7.344 / 0.414, 128 7.143 / 0.565
+// (k = 100: 15.29 / 0.762); 10M — 8 4.788 / 1.199, 32 17.63 / 1.266, 64 34.84 / 1.921, 96 70.23 / 2.318, 128 69.21 / 3.558.  The
+// nomination won at every shape, by 14 % at the smallest: the constant is the smallest measured product, 8 x 100k, and nothing below
+// it was measured.  Test hook VG_INT4_NOM_ALWAYS: any.
+constexpr int64_t kInt4NomSmallMinPairs = 800000;
 
 // one workgroup of 64 lanes: mid, the scale and H2
 __global__ void int4_mid_kernel(const float *__restrict__ mins, const float *__restrict__ diff, int dim, int dim_pad, float *__restrict__ mid)
@@ -137,11 +145,19 @@ struct Int4Row {
 
 // The nomination takes more than 128 queries — the persistent tile's batches; the register-staged fill has no 128-row form — over
 // the whole segment, unfiltered, rows of whole 16-byte halves of a K step (dim % 32 == 0), from kInt4NomMinPairs pairs up.
+// Enabled with on = 2 (NomImage::int4_small) it also takes 5 .. 128 queries, on the tile of one query tile
+// (flat_gemm_int4_small_kernel, vg_int4_small_gemm.hpp) from kInt4NomSmallMinPairs pairs up, where a block of 32 queries' image of
+// a row fits that tile's LDS (int4_small_tile_fits: dim <= 2496).
 // (device queries; mask: the batch's row filter, or null)
 bool int4_nomination_applies(const vg_index *idx, const float *d_queries, int64_t nq, int k, const uint8_t *mask)
 {
-    if (!idx->i4_nom.rows || mask || nq <= 128 || idx->dim % 32 != 0) return false;
-    if (nq * idx->n < kInt4NomMinPairs && !hook(kHookInt4NomAlways)) return false;
+    if (!idx->i4_nom.rows || mask || idx->dim % 32 != 0) return false;
+    if (nq <= 128) {
+        if (!idx->i4_nom.int4_small || nq < 5 || !int4_small_tile_fits(idx->dim)) return false;
+        if (nq * idx->n < kInt4NomSmallMinPairs && !hook(kHookInt4NomAlways)) return false;
+    } else if (nq * idx->n < kInt4NomMinPairs && !hook(kHookInt4NomAlways)) {
+        return false;
+    }
     return k <= kNomMaxK && idx->n > k && aligned16(d_queries);
 }
 // nominated_pass with the INT4 re-score
@@ -176,6 +192,7 @@ VG_API int32_t vg_index_enable_int4_nomination(vg_index *idx, int32_t on, void *
                            idx->int4_min, idx->int4_diff, b.norms, norm_max_bits);
     }));
     idx->i4_nom.int4 = true;
+    idx->i4_nom.int4_small = on == 2;
     idx->i4_nom.scale = reinterpret_cast<const float *>(idx->i4_nom.rows) + dim_pad;
     return VG_OK;
 }
@@ -183,7 +200,7 @@ VG_API int32_t vg_index_enable_int4_nomination(vg_index *idx, int32_t on, void *
 VG_API int32_t vg_index_int4_nomination_info(const vg_index *idx, int32_t *mode, int64_t *held_bytes, int64_t *rescanned)
 {
     VG_CHECK(idx, VG_ERR_INVALID_ARG, "vg_index_int4_nomination_info: NULL index");
-    if (mode) *mode = idx->i4_nom.rows ? 1 : 0;
+    if (mode) *mode = !idx->i4_nom.rows ? 0 : idx->i4_nom.int4_small ? 2 : 1;
     if (held_bytes) *held_bytes = idx->i4_nom.held_bytes(idx->n);
     if (rescanned) *rescanned = idx->i4_nom.rows ? idx->i4_nom_rescanned : 0;
     return VG_OK;

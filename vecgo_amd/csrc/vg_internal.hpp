@@ -488,7 +488,8 @@ struct NomImage {
     // min_d + 8 scale_d as dim_pad floats, the scale diff_d / 15 as dim_pad floats behind them (`scale` points there; both zeros from
     // dim on) and one float H2 (Int4Row::eps); the GEMM's row tile is converted from the index's row-major nibble codes, bf16(c - 8).
     bool int4 = false;
-    int64_t body = 0;              // bytes of `rows`
+    bool int4_small = false;       // with `int4`: enabled with on = 2 — batches of 5 .. 128 queries take the nomination too
+    int64_t body = 0;             // bytes of `rows`
     // what vg_index_pq_nomination_info reports: 0 off, 1 the image of the decoded rows, 2 from the codes
     int mode() const { return !rows ? 0 : from_codes ? 2 : 1; }
     uint16_t *row_image() const { return from_codes ? nullptr : rows; }  // the decoded rows, where the mode keeps them

@@ -48,6 +48,12 @@ int32_t pq_nominated_pass(vg_index *idx, const float *q, int64_t nq, int k, uint
 // k_int4_nominate.hip (L2 over the whole segment: mask null, or the batch does not apply)
 bool int4_nomination_applies(const vg_index *idx, const float *d_queries, int64_t nq, int k, const uint8_t *mask);
 int32_t int4_nominated_pass(vg_index *idx, const float *q, int64_t nq, int k, uint32_t *oid, float *osc, hipStream_t st, std::vector<int> &failed);
+// k_int4_small.hip: the INT4 append GEMM of one query tile (cnt <= 128; flat_gemm_int4_small_kernel) — whether a row of dim
+// dimensions fits its LDS at all, and the launch (qimg: cnt x dim_pad bfloat16; counts[q * count_stride]; cus: compute units)
+bool int4_small_tile_fits(int dim);
+int32_t launch_int4_small_gemm(const uint16_t *qimg, int64_t cnt, int dim_pad, const uint8_t *codes, int64_t n, int row_bytes, const float *norms,
+                               const float *thr, int thr_stride, int thr_off, int *counts, int count_stride, uint64_t *cand, int cap, int cus,
+                               hipStream_t st);
 
 // Builds the nomination state of n rows of dim elements into `img` (empty): its body of body_bytes (NomImage::body_bytes — the
 // decoded rows, or from_codes the decoded codebook), the norms and norm_max.  launch(const NomImage &, int *norm_max_bits) launches
