@@ -690,7 +690,15 @@ func (r *Resident) EnableSQ8NominationFromCodes(on bool) error {
 	return hipctx.Err(int32(C.vg_index_enable_sq8_nomination_from_codes(r.h, v, nil)))
 }
 
-// SQ8NominationInfo: mode 0 (off), 1 (the dequantised-row image) or 2 (from the codes), the device bytes the mode keeps resident,
+// EnableSQ8NominationFromCodesSmallBatches: EnableSQ8NominationFromCodes(true), and unfiltered whole-segment batches of 5 .. 128
+// queries take the nomination too (mode 3; dim <= 2528, from their own crossover up), on a GEMM of one query tile that reads the
+// code tiles straight into the matrix instruction's registers.  Nothing more is resident.  Filtered batches, probed partitions and
+// fewer than 5 queries keep the scan.
+func (r *Resident) EnableSQ8NominationFromCodesSmallBatches() error {
+	return hipctx.Err(int32(C.vg_index_enable_sq8_nomination_from_codes(r.h, C.int32_t(2), nil)))
+}
+
+// SQ8NominationInfo: mode 0 (off), 1 (the dequantised-row image), 2 (from the codes) or 3 (from the codes, small batches too), the device bytes the mode keeps resident,
 // and the queries whose proof failed and the scan answered since the mode was enabled.
 func (r *Resident) SQ8NominationInfo() (mode int, heldBytes, rescanned int64, err error) {
 	var m C.int32_t

@@ -1646,10 +1646,15 @@ int32_t vg_index_pq_nomination_info(const vg_index *idx, int32_t *mode, int64_t 
  * state; on == 0 frees this one's and leaves the other; vg_index_set_sq8_codes drops either.  Batches it takes: whole-segment
  * vg_search_sq8, L2 or Dot, unfiltered, MORE THAN 128 queries, k <= 256, rows > k, 16-byte aligned device queries, and queries x
  * rows at or above its crossover against the scan (README, Limits); filtered batches, probed partitions and smaller batches keep
- * the scan, with the same results.  Found by symbol lookup. */
+ * the scan, with the same results.
+ * on == 2 (any other non-zero value is 1): the same, and unfiltered whole-segment batches of 5 .. 128 queries take the nomination
+ * too, under the same conditions and dim <= 2528, from their own crossover up — on a GEMM of one query tile whose waves read the
+ * code tiles from global memory straight into the matrix instruction's registers, the queries' image resident in LDS (97 .. 128
+ * queries from dim 609 on run as two launches of two 32-query blocks).  Nothing more is resident; vg_index_sq8_nomination_info
+ * reports mode 3.  Still the scan's: filtered batches, probed partitions, fewer than 5 queries, k > 256.  Found by symbol lookup. */
 int32_t vg_index_enable_sq8_nomination_from_codes(vg_index *idx, int32_t on, void *stream);
-/* Which SQ8 nomination an index holds and what it does: *mode = 0 (off), 1 (the image: vg_index_enable_sq8_nomination) or 2 (from
- * the codes); *held_bytes = the device memory the mode keeps resident; *rescanned = the queries, since the mode was enabled, whose
+/* Which SQ8 nomination an index holds and what it does: *mode = 0 (off), 1 (the image: vg_index_enable_sq8_nomination), 2 (from
+ * the codes) or 3 (from the codes, enabled with on == 2); *held_bytes = the device memory the mode keeps resident; *rescanned = the queries, since the mode was enabled, whose
  * proof failed and which the scan answered (0 when off).  Any pointer may be NULL.  Found by symbol lookup. */
 int32_t vg_index_sq8_nomination_info(const vg_index *idx, int32_t *mode, int64_t *held_bytes, int64_t *rescanned);
 /* vg_search_rabitq batches through an int8 matrix-core nomination.  A Hamming distance is a dot product of +-1 vectors: the GEMM

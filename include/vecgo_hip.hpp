@@ -678,7 +678,9 @@ public:
     // the SQ8 batch nomination without the image of the dequantised rows: the GEMM's row tiles converted from the code tiles
     // (batches above 128 queries, unfiltered, the whole segment); exclusive with EnableSQ8Nomination; results unchanged
     void EnableSQ8NominationFromCodes(bool on = true) { check(vg_index_enable_sq8_nomination_from_codes(h_, on ? 1 : 0, nullptr)); }
-    // mode: 0 off, 1 the image, 2 from the codes; held_bytes: the device memory the mode keeps resident; rescanned: queries whose
+    // the same, and unfiltered whole-segment batches of 5 .. 128 queries (dim <= 2528) take the nomination too (mode 3)
+    void EnableSQ8NominationFromCodesSmallBatches() { check(vg_index_enable_sq8_nomination_from_codes(h_, 2, nullptr)); }
+    // mode: 0 off, 1 the image, 2 from the codes, 3 from the codes with small batches; held_bytes: the device memory the mode keeps resident; rescanned: queries whose
     // proof failed and the scan answered, since the mode was enabled
     struct SQ8Nomination {
         int32_t mode;

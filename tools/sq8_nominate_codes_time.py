@@ -2,8 +2,11 @@
 (vg_index_enable_sq8_nomination, mode 1) and the nomination from the codes (vg_index_enable_sq8_nomination_from_codes, mode 2) —
 ms per call (the median of several timed windows, with their min and max: the run's spread), the GEMM's share from the profile
 scopes, what each mode keeps resident, the queries the scan had to answer again, and equality of the results.
-    python tools/sq8_nominate_codes_time.py [max_rows]
-Segments of 100k, 300k and 1M rows, and of 4M with max_rows >= 4000000; the legs of a shape alternate inside one run."""
+    python tools/sq8_nominate_codes_time.py [max_rows] [small]
+Segments of 100k, 300k and 1M rows, and of 4M with max_rows >= 4000000; the legs of a shape alternate inside one run.
+small: the batches of 8 .. 128 queries that mode 2 takes when enabled with small_batches (info mode 3, flat_gemm_sq8_small_kernel)
+instead — segments of 100k, 1M and (max_rows >= 10000000) 10M rows, windows of ~300 ms, the scan against mode 3 and the image mode:
+where kSq8NomCodesSmallMinPairs comes from."""
 import statistics
 import sys
 from pathlib import Path
@@ -12,16 +15,18 @@ import torch
 import vecgo_amd as vg, bench
 ctx = vg.Context(0); dev = torch.device("cuda", 0)
 max_rows = int(sys.argv[1]) if len(sys.argv) > 1 else 1_000_000
+SMALL = "small" in sys.argv[2:]
+WINDOW_MS = 300 if SMALL else 20
 rows = bench.gen_rows(0, max(max_rows, 1_000_000), dev)
 q = bench.gen_queries(2, dev)[0]
 st = torch.cuda.current_stream()
 sq = vg.ScalarQuantizer(ctx, 768)
 sq.train(rows[:65536])
-codes = sq.encode(rows)
+codes = torch.cat([sq.encode(rows[lo:lo + 1_000_000]) for lo in range(0, rows.shape[0], 1_000_000)])   # (a million at a time)
 del rows
 from tests import hooks
 hooks.set_hook("VG_SQ8_NOM_CODES_ALWAYS", 1)           # every batch above 128 queries takes mode 2: where the crossover is
-SCOPES = {1: "sq8_nominate_gemm", 2: "sq8_codes_gemm"}
+SCOPES = {1: "sq8_nominate_gemm", 2: "sq8_codes_gemm_small" if SMALL else "sq8_codes_gemm"}
 NAMES = {0: "scan", 1: "image", 2: "from codes"}
 
 
@@ -38,7 +43,7 @@ def switch(idx, md):
     idx.enable_sq8_nomination(False)
     idx.enable_sq8_nomination_from_codes(False)
     if md:
-        (idx.enable_sq8_nomination if md == 1 else idx.enable_sq8_nomination_from_codes)(True)
+        idx.enable_sq8_nomination(True) if md == 1 else idx.enable_sq8_nomination_from_codes(True, small_batches=SMALL)
 
 
 def same(a, b):
@@ -51,7 +56,7 @@ def shape(idx, n, nq, k, legs, windows=5):
     for w in range(windows + 1):                        # the legs alternate; the first round warms up
         for md in legs:
             switch(idx, md)
-            reps = max(1, int(20 / (45e-9 * nq * n * (1 if md == 0 else 0.05) + 0.2)))   # ~20 ms a window, at least one call
+            reps = max(1, int(WINDOW_MS / (45e-9 * nq * n * (1 if md == 0 else 0.05) + 0.2)))   # ~WINDOW_MS a window, at least one call
             t, r = window(idx, qs, k, reps)
             if w:
                 ms[md].append(t)
@@ -82,6 +87,8 @@ PLAN = [(100_000, [(129, 10), (257, 10), (1024, 10)]),
         (300_000, [(129, 10), (257, 10)]),
         (1_000_000, [(129, 10), (257, 10), (1024, 10), (1024, 100)]),
         (4_000_000, [(1024, 10)])]
+if SMALL:
+    PLAN = [(n, [(nq, 10) for nq in (8, 32, 64, 96, 128)] + ([(128, 100)] if n == 1_000_000 else [])) for n in (100_000, 1_000_000, 10_000_000)]
 for n, shapes in PLAN:
     if n > codes.shape[0]:
         continue

@@ -263,6 +263,16 @@ static int32_t launch_gemm_t(const GemmArgs &a)
             VG_CHECK(bf16 && c.cnt * static_cast<int64_t>(a.cap) < (int64_t(1) << 31) && a.thr_stride < 65536 && c.ops.dim_words % kGemmBK == 0 &&
                          a.code_m > 0 && c.ops.n > 0,
                      VG_ERR_INVALID_ARG, "launch_gemm: the SQ8 code tile on a call without it");
+            // one query tile: code tiles from global memory into the matrix unit's registers (k_sq8_small.hip; rows too long for its LDS: the big tile)
+            if (c.cnt <= kGemmBM && sq8_small_tile_fits(16 * a.code_m)) {
+                if (a.counts_wide) VG_HIP(hipMemsetAsync(a.counts_wide, 0, sizeof(int) * static_cast<size_t>(c.cnt) * kCountLine, st));
+                VG_TRY(launch_sq8_small_gemm<DOT>(reinterpret_cast<const uint16_t *>(a.queries), c.cnt, 2 * c.ops.dim_words, a.codes, c.ops.n, a.code_m,
+                                                  c.ops.norms, a.thr, a.thr_stride, a.thr_off, a.counts_wide ? a.counts_wide : a.counts,
+                                                  a.counts_wide ? kCountLine : 1, a.cand, a.cap, a.cus, st));
+                if (a.counts_wide)
+                    VG_LAUNCH(counts_narrow_kernel, dim3(static_cast<unsigned>((c.cnt + 255) / 256)), dim3(256), 0, st, a.counts_wide, c.cnt, a.counts);
+                return VG_OK;
+            }
             return launch_big(flat_gemm_sq8_big_kernel<DOT, 3>, big_lds_bytes<3>(), a.codes, a.code_m);
         }
     }
@@ -1657,7 +1667,8 @@ int32_t flat_nominate_bf16(vg_index *idx, const NomImage &img, bool dot, const f
     VG_HIP(hipMemsetAsync(nom->counts, 0, sizeof(int) * static_cast<size_t>(cnt), st));
     {
         const bool i4_small = img.int4 && cnt <= kGemmBM && int4_small_tile_fits(idx->dim);  // (launch_gemm's choice: the small INT4 tile)
-        ProfScope prof(idx->ctx, i4_small ? "int4_codes_gemm_small" : img.int4 ? "int4_codes_gemm" : img.scale ? "sq8_codes_gemm" : img.from_codes ? "pq_codes_gemm" : "sq8_nominate_gemm", st);
+        const bool s8_small = !img.int4 && img.scale && cnt <= kGemmBM && sq8_small_tile_fits(idx->dim);  // (likewise: the small SQ8 tile)
+        ProfScope prof(idx->ctx, i4_small ? "int4_codes_gemm_small" : img.int4 ? "int4_codes_gemm" : s8_small ? "sq8_codes_gemm_small" : img.scale ? "sq8_codes_gemm" : img.from_codes ? "pq_codes_gemm" : "sq8_nominate_gemm", st);
         GemmArgs a = GemmArgs::append(nc, nom->thr, nom->sel_k, nom->counts, nom->cand, nom->cap).wide(s.counts_wide, idx->ctx->compute_units);
         if (img.int4)
             a.from_int4_codes(idx->d_int4_rows, idx->dim / 2);

@@ -569,15 +569,39 @@ int32_t launch_sq8_verify(vg_index *idx, const float *queries, int64_t nq, const
     return launch_nominated_verify<false>(Sq8Row<false>{tiles, idx->sq_groups, idx->dim, idx->sq->d_mins, idx->sq->d_inv}, queries,
                                           idx->sq_nom.norm_max, nq, nom, k, ids, scores, fail, st);
 }
-// The nomination from the codes takes more than 128 queries — the persistent tile's batches; the register-staged fill has no
-// 128-row form — over the whole segment, unfiltered, from kSq8NomCodesMinPairs (query, row) pairs up (tools/sq8_nominate_codes_time.py;
+// The nomination from the codes takes more than 128 queries on the persistent tile — its register-staged fill has no 128-row
+// form; fewer run the tile below when it is enabled — over the whole segment, unfiltered, from kSq8NomCodesMinPairs (query, row) pairs up (tools/sq8_nominate_codes_time.py;
 // test hook VG_SQ8_NOM_CODES_ALWAYS: any number of pairs).
 constexpr int64_t kSq8NomCodesMinPairs = 12000000;
+// The same for batches of 5 .. 128 queries when the mode was enabled with on = 2 (NomImage::sq8_small; reported as mode 3): the tile
+// of one query tile (flat_gemm_sq8_small_kernel, vg_sq8_small_gemm.hpp), where a block of 32 queries' image of a row fits that
+// tile's LDS (sq8_small_tile_fits: dim <= 2528), from kSq8NomCodesSmallMinPairs pairs up.
+// Measured (MI355X, tools/sq8_nominate_codes_time.py 10000000 small, dim 768, k = 10, ms per call, scan / mode 3 / image mode,
+// alternating windows of ~300 ms in one run on one index, the median of 5; the windows of a leg lay within 1 % of each other, 4 %
+// at one shape; no query was rescanned, bits equal; profiles/sq8_nominate_codes_time_small.txt):
+//   100k rows —   8 queries 0.125 / 0.173 / 0.197,  32: 0.271 / 0.184 / 0.290,  64: 0.399 / 0.197 / 0.352,  96: 0.573 / 0.224 / 0.345,
+//                128: 0.685 / 0.257 / 0.382
+//   1M rows   —   8: 0.504 / 0.329 / 0.383,  32: 1.590 / 0.335 / 0.396,  64: 3.156 / 0.360 / 0.417,  96: 5.268 / 0.418 / 0.464,
+//                128: 6.453 / 0.559 / 0.496  (k = 100: 13.63 / 0.807 / 0.771)
+//   10M rows  —   8: 4.516 / 1.627 / 2.445,  32: 16.45 / 1.689 / 2.530,  64: 31.55 / 1.891 / 2.592,  96: 49.72 / 2.321 / 3.083,
+//                128: 61.41 / 3.583 / 3.349
+// The GEMM's own time (its profile scope): 100k — 0.037, 0.041, 0.055, 0.071, 0.101 ms; 1M — 0.167, 0.168, 0.195, 0.246, 0.384
+// (k = 100: 0.420); 10M — 1.381, 1.416, 1.536, 1.922, 3.196: 5.6 TB/s of code bytes at 8 x 10M, and 128 queries two passes.
+// The nomination LOST at 8 x 100k (0.8M pairs, 0.72x) and won at every other shape by far more than the spread: the constant is
+// the smallest product measured at which it won, 32 x 100k; nothing between 0.8M and 3.2M pairs was measured.  Against the image
+// mode it is 0.56x .. 0.90x of the time up to 96 queries and 1.05x .. 1.13x at 128 (two launches).  Test hook
+// VG_SQ8_NOM_CODES_ALWAYS: any.
+constexpr int64_t kSq8NomCodesSmallMinPairs = 3200000;
 // whether a batch takes the nomination (vg_index_enable_sq8_nomination, _from_codes; device queries; mask: the batch's row filter, or null)
 bool sq8_nomination_applies(const vg_index *idx, const float *d_queries, int64_t nq, int k, const uint8_t *mask)
 {
     const int mode = idx->sq_nom.mode();
-    if (mode == 2 && (mask || nq <= 128 || (nq * idx->n < kSq8NomCodesMinPairs && !hook(kHookSq8NomCodesAlways)))) return false;
+    if (mode == 2 && nq <= 128) {
+        if (mask || !idx->sq_nom.sq8_small || !sq8_small_tile_fits(idx->dim)) return false;
+        if (nq * idx->n < kSq8NomCodesSmallMinPairs && !hook(kHookSq8NomCodesAlways)) return false;
+    } else if (mode == 2 && (mask || (nq * idx->n < kSq8NomCodesMinPairs && !hook(kHookSq8NomCodesAlways)))) {
+        return false;
+    }
     return mode && nq >= VG_SQ8_NOM_MIN_Q && k <= kNomMaxK && idx->n > k && aligned16(d_queries);
 }
 // nominated_pass with the SQ8 re-score (mask: a device row filter per query / for the batch, or null)
@@ -683,6 +707,7 @@ static int32_t sq8_nomination_enable(vg_index *idx, int mode, int32_t on, void *
                            norm_max_bits);
     }));
     idx->sq_nom.scale = idx->sq->d_inv;  // (the quantizer's: it outlives its codes on the index, vg_index_set_sq8_codes)
+    idx->sq_nom.sq8_small = on == 2;
     return VG_OK;
 }
 
@@ -699,7 +724,7 @@ VG_API int32_t vg_index_enable_sq8_nomination_from_codes(vg_index *idx, int32_t 
 VG_API int32_t vg_index_sq8_nomination_info(const vg_index *idx, int32_t *mode, int64_t *held_bytes, int64_t *rescanned)
 {
     VG_CHECK(idx, VG_ERR_INVALID_ARG, "vg_index_sq8_nomination_info: NULL index");
-    if (mode) *mode = idx->sq_nom.mode();
+    if (mode) *mode = idx->sq_nom.sq8_small ? 3 : idx->sq_nom.mode();  // (3: from the codes, small batches too)
     if (held_bytes) *held_bytes = idx->sq_nom.held_bytes(idx->n);
     if (rescanned) *rescanned = idx->sq_nom.mode() ? idx->sq_nom_rescanned : 0;
     return VG_OK;

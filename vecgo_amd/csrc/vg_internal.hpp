@@ -489,6 +489,7 @@ struct NomImage {
     // dim on) and one float H2 (Int4Row::eps); the GEMM's row tile is converted from the index's row-major nibble codes, bf16(c - 8).
     bool int4 = false;
     bool int4_small = false;       // with `int4`: enabled with on = 2 — batches of 5 .. 128 queries take the nomination too
+    bool sq8_small = false;        // with `scale` (SQ8 from the codes): enabled with on = 2 — batches of 5 .. 128 queries take the nomination too
     int64_t body = 0;             // bytes of `rows`
     // what vg_index_pq_nomination_info reports: 0 off, 1 the image of the decoded rows, 2 from the codes
     int mode() const { return !rows ? 0 : from_codes ? 2 : 1; }

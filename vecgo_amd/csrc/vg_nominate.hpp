@@ -54,6 +54,14 @@ bool int4_small_tile_fits(int dim);
 int32_t launch_int4_small_gemm(const uint16_t *qimg, int64_t cnt, int dim_pad, const uint8_t *codes, int64_t n, int row_bytes, const float *norms,
                                const float *thr, int thr_stride, int thr_off, int *counts, int count_stride, uint64_t *cand, int cap, int cus,
                                hipStream_t st);
+// k_sq8_small.hip: the SQ8 append GEMM of one query tile over the code tiles (cnt <= 128; flat_gemm_sq8_small_kernel) — whether a
+// row of dim dimensions fits its LDS at all (dim <= 2528), and the launch (qimg: cnt x dim_pad bfloat16; tiles: the index's code
+// tiles of `groups` groups; counts[q * count_stride]; cus: compute units)
+bool sq8_small_tile_fits(int dim);
+template <bool DOT>
+int32_t launch_sq8_small_gemm(const uint16_t *qimg, int64_t cnt, int dim_pad, const uint8_t *tiles, int64_t n, int groups, const float *norms,
+                              const float *thr, int thr_stride, int thr_off, int *counts, int count_stride, uint64_t *cand, int cap, int cus,
+                              hipStream_t st);
 
 // Builds the nomination state of n rows of dim elements into `img` (empty): its body of body_bytes (NomImage::body_bytes — the
 // decoded rows, or from_codes the decoded codebook), the norms and norm_max.  launch(const NomImage &, int *norm_max_bits) launches
