@@ -775,7 +775,15 @@ func (r *Resident) EnablePQNominationFromCodes(on bool) error {
 	return hipctx.Err(int32(C.vg_index_enable_pq_nomination_from_codes(r.h, v, nil)))
 }
 
-// PQNominationInfo: mode 0 (off), 1 (the decoded-row image) or 2 (from the codes), and the device bytes the mode keeps resident.
+// EnablePQNominationFromCodesSmallBatches: EnablePQNominationFromCodes(true), and unfiltered batches of 32 .. 128 queries take the
+// nomination too (mode 3; m <= 318, from 32M (query, row) pairs up), on a GEMM of one query tile whose lanes gather their codebook
+// entries by the code bytes straight into the matrix instruction's registers.  Nothing more is resident.  Filtered batches and
+// fewer than 32 queries keep the scan.
+func (r *Resident) EnablePQNominationFromCodesSmallBatches() error {
+	return hipctx.Err(int32(C.vg_index_enable_pq_nomination_from_codes(r.h, C.int32_t(2), nil)))
+}
+
+// PQNominationInfo: mode 0 (off), 1 (the decoded-row image), 2 (from the codes) or 3 (from the codes, small batches too), and the device bytes the mode keeps resident.
 func (r *Resident) PQNominationInfo() (mode int, heldBytes int64, err error) {
 	var m C.int32_t
 	var b C.int64_t

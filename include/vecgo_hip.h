@@ -1628,11 +1628,17 @@ int32_t vg_index_enable_pq_nomination(vg_index *idx, int32_t on, void *stream);
  * then sub-vectors of other than 8 dimensions: VG_ERR_UNSUPPORTED.  Any m (granules from m on read zeros).  The two modes
  * are exclusive: enabling one frees the other's state; on == 0 frees this one's; vg_index_set_pq_codes drops it.  Batches it takes:
  * unfiltered, ascending, k <= 256, rows > k, 16-byte aligned device queries, MORE THAN 128 queries, and queries x rows at or above
- * its own crossover against the scan (README, Limits); every other batch keeps the table scan, with the same results.  Found by
- * symbol lookup. */
+ * its own crossover against the scan (README, Limits); every other batch keeps the table scan, with the same results.
+ * on == 2 (any other non-zero value is 1): the same, and unfiltered ascending batches of 32 .. 128 queries with queries x rows >= 32M
+ * take the nomination too, under the same conditions and m <= 318 (dim 2544).  (The tile serves 5 .. 128 queries; 8 queries lost to
+ * the scan at every size measured and 9 .. 31 were never measured, so 5 .. 31 keep the scan: README, Limits.)  It runs
+ * on a GEMM of one query tile whose lanes gather their codebook entry by their row's code byte from global memory
+ * straight into the matrix instruction's register, the queries' image resident in LDS (97 .. 128 queries from m = 79 on run as two
+ * launches of two 32-query blocks).  Nothing more is resident; vg_index_pq_nomination_info reports mode 3.  Still the scan's:
+ * filtered batches, fewer than 32 queries, k > 256, m > 318.  Found by symbol lookup. */
 int32_t vg_index_enable_pq_nomination_from_codes(vg_index *idx, int32_t on, void *stream);
-/* Which PQ nomination an index holds and what it costs: *mode = 0 (off), 1 (the image: vg_index_enable_pq_nomination) or 2 (from
- * the codes); *held_bytes = the device memory the mode keeps resident (mode 1: the image, the norms and norm_max).  Either
+/* Which PQ nomination an index holds and what it costs: *mode = 0 (off), 1 (the image: vg_index_enable_pq_nomination), 2 (from
+ * the codes) or 3 (from the codes, enabled with on == 2); *held_bytes = the device memory the mode keeps resident (mode 1: the image, the norms and norm_max).  Either
  * pointer may be NULL.  Found by symbol lookup. */
 int32_t vg_index_pq_nomination_info(const vg_index *idx, int32_t *mode, int64_t *held_bytes);
 /* vg_index_enable_sq8_nomination WITHOUT the image of the dequantised rows.  A code is an integer, and bfloat16 holds c - 128

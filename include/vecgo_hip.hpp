@@ -664,7 +664,9 @@ public:
     // the same without the image of the decoded rows: the GEMM's row tiles gathered from the decoded codebook by the codes
     // (8 dimensions per sub-quantizer, batches above 128 queries); the two modes are exclusive
     void EnablePQNominationFromCodes(bool on = true) { check(vg_index_enable_pq_nomination_from_codes(h_, on ? 1 : 0, nullptr)); }
-    // mode: 0 off, 1 the image, 2 from the codes; held_bytes: the device memory the mode keeps resident
+    // the same, and unfiltered batches of 32 .. 128 queries from 32M (query, row) pairs (m <= 318) take the nomination too (mode 3)
+    void EnablePQNominationFromCodesSmallBatches() { check(vg_index_enable_pq_nomination_from_codes(h_, 2, nullptr)); }
+    // mode: 0 off, 1 the image, 2 from the codes, 3 from the codes with small batches; held_bytes: the device memory the mode keeps resident
     struct PQNomination {
         int32_t mode;
         int64_t held_bytes;

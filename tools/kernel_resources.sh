@@ -13,6 +13,7 @@ for f in *.hip; do
     extra=""
     [ "$f" = "k_pq_train.hip" ] && extra="-mllvm -amdgpu-mfma-vgpr-form"
     { [ "$f" = "k_int4_small.hip" ] || [ "$f" = "k_sq8_small.hip" ]; } && extra="-Xclang -target-feature -Xclang -packed-fp32-ops"   # (the Makefile's flags for that unit)
+    [ "$f" = "k_pq_small.hip" ] && extra="-Xclang -target-feature -Xclang -packed-fp32-ops -mllvm -amdgpu-mfma-vgpr-form"
     /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -fvisibility=hidden \
         -I../../include $extra -c "$f" -o "$tmp/$f.o" -Rpass-analysis=kernel-resource-usage 2>&1 |
         grep -E "Function Name|VGPRs:|AGPRs:|Occupancy|VGPRs Spill|LDS Size" |

@@ -1,8 +1,13 @@
 """vg_search_pq_adc, nq queries x rows x 768 (m = 96, K = 256): the table scan, the nomination on the image of the decoded rows
 (vg_index_enable_pq_nomination, mode 1) and the nomination from the codes (vg_index_enable_pq_nomination_from_codes, mode 2) —
 ms per call, the GEMM's share from the profile scopes, what each mode keeps resident, and equality of the results.
-    python tools/pq_nominate_codes_time.py [rows]
-Above 2M rows: one pass, 1024 queries, k = 10, the scan against mode 2 (the image would be 16x the codes)."""
+    python tools/pq_nominate_codes_time.py [rows] [small]
+Above 2M rows: one pass, 1024 queries, k = 10, the scan against mode 2 (the image would be 16x the codes).
+small: the batches of 8 .. 128 queries that mode 2 takes when enabled with small_batches (info mode 3, flat_gemm_pq_small_kernel)
+instead — segments of 100k, 1M and (rows >= 10000000) 10M rows, k = 10 (128 x 1M: k = 100 too), the scan against mode 3 and the
+image mode, the three legs alternating on one index in windows of ~300 ms, every shape warmed, the median of 5 windows with their
+min and max: where kPqNomCodesSmallMinPairs comes from."""
+import statistics
 import sys
 from pathlib import Path
 sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
@@ -10,13 +15,14 @@ import torch
 import vecgo_amd as vg, bench
 ctx = vg.Context(0); dev = torch.device("cuda", 0)
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 1_000_000
-big = n > 2_000_000
+SMALL = "small" in sys.argv[2:]
+big = n > 2_000_000 and not SMALL
 rows = bench.gen_rows(0, n, dev)
 q = bench.gen_queries(2, dev)[0]
 st = torch.cuda.current_stream()
 pq = vg.ProductQuantizer(ctx, 768, 96, 256)
 pq.train(rows[:65536], iters=5)
-codes = pq.encode(rows)
+codes = torch.cat([pq.encode(rows[lo:lo + 1_000_000]) for lo in range(0, n, 1_000_000)]) if SMALL else pq.encode(rows)   # (small: a million at a time)
 del rows
 from tests import hooks
 hooks.set_hook("VG_PQ_NOM_ALWAYS", 1)                  # every batch above 128 queries takes the nomination: where the crossover is
@@ -57,6 +63,54 @@ def same(a, b):
     return bool(torch.equal(a[0], b[0]) and torch.equal(a[1].view(torch.int32), b[1].view(torch.int32)))
 
 
+def small_shape(ix, rows_n, nq, k, windows=5):
+    """one line: the median / min / max ms per call of each leg, the GEMM's own ms per call, equality with the scan"""
+    qs = q[:nq].contiguous()
+    legs = {0: "scan", 3: "mode 3", 1: "image"}
+    scope = {3: "pq_codes_gemm_small", 1: "sq8_nominate_gemm"}
+
+    def switch(md):
+        ix.enable_pq_nomination(False)
+        ix.enable_pq_nomination_from_codes(False)
+        if md:
+            ix.enable_pq_nomination(True) if md == 1 else ix.enable_pq_nomination_from_codes(True, small_batches=True)
+
+    ms, res, gemm = {md: [] for md in legs}, {}, {}
+    for w in range(windows + 1):                        # the legs alternate; the first round warms up
+        for md in legs:
+            switch(md)
+            est = 0.012 * nq * rows_n / 1e6 + 0.1 if md == 0 else 0.3 + 0.3 * rows_n / 1e6   # ms a call, roughly
+            reps = max(3, int(300 / est))                  # ~300 ms a window
+            r = ix.search_pq_adc(qs, k, stream=st)
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(st)
+            for _ in range(reps): r = ix.search_pq_adc(qs, k, stream=st)
+            e1.record(st); torch.cuda.synchronize()
+            if w:
+                ms[md].append(e0.elapsed_time(e1) / reps)
+            res[md] = r
+            if md and w == windows:                     # the GEMM's own time: ten calls under the profile's events
+                ctx.profile_read(scope[md]); ctx.profile_enable(True)
+                for _ in range(10): ix.search_pq_adc(qs, k, stream=st)
+                torch.cuda.synchronize()
+                gemm[md] = ctx.profile_read(scope[md])[1] / 10; ctx.profile_enable(False)
+    txt = "  ".join(f"{legs[md]} {statistics.median(ms[md]):8.3f} [{min(ms[md]):.3f} {max(ms[md]):.3f}]" for md in legs)
+    print(f"{rows_n:9d} rows k {k:3d} {nq:4d} queries: {txt}  GEMM mode 3 {gemm[3]:6.3f} image {gemm[1]:6.3f} ms/call  "
+          f"scan / mode 3 {statistics.median(ms[0]) / statistics.median(ms[3]):5.2f}  bits equal: {same(res[0], res[3])} {same(res[0], res[1])}", flush=True)
+
+
+if SMALL:
+    del idx
+    for rows_n in (100_000, 1_000_000, 10_000_000):
+        if rows_n > n:
+            continue
+        ix = vg.Index(ctx, rows_n, 768)
+        ix.set_pq_codes(pq, codes[:rows_n].contiguous())
+        for nq, k in [(nq, 10) for nq in (8, 32, 64, 96, 128)] + ([(128, 100)] if rows_n == 1_000_000 else []):
+            small_shape(ix, rows_n, nq, k)
+        del ix
+    sys.exit(0)
 print(f"{n} rows x 768, m 96: codes {code_bytes / 1e6:.1f} MB", flush=True)
 for k in ((10,) if big else (10, 100)):
     for nq in ((1024,) if big else (129, 256, 512, 1024)):

@@ -299,6 +299,17 @@ static int32_t launch_gemm_t(const GemmArgs &a)
         if constexpr (MODE == 2 && !DOT) {
             VG_CHECK(bf16 && c.cnt * static_cast<int64_t>(a.cap) < (int64_t(1) << 31) && a.thr_stride < 65536 && c.ops.dim_words % kGemmBK == 0,
                      VG_ERR_INVALID_ARG, "launch_gemm: the code-gathered tile on a call without it");
+            // one query tile: codebook entries gathered by the codes into the matrix unit's registers (k_pq_small.hip; rows too long for its LDS,
+            // or fewer than 16 code bytes in all: the big tile)
+            if (c.cnt <= kGemmBM && pq_small_tile_takes(a.code_m, c.ops.n)) {
+                if (a.counts_wide) VG_HIP(hipMemsetAsync(a.counts_wide, 0, sizeof(int) * static_cast<size_t>(c.cnt) * kCountLine, st));
+                VG_TRY(launch_pq_small_gemm(reinterpret_cast<const uint16_t *>(a.queries), c.cnt, 2 * c.ops.dim_words, a.codes, c.ops.n, a.code_m,
+                                            reinterpret_cast<const uint4 *>(c.ops.b), c.ops.norms, a.thr, a.thr_stride, a.thr_off,
+                                            a.counts_wide ? a.counts_wide : a.counts, a.counts_wide ? kCountLine : 1, a.cand, a.cap, a.cus, st));
+                if (a.counts_wide)
+                    VG_LAUNCH(counts_narrow_kernel, dim3(static_cast<unsigned>((c.cnt + 255) / 256)), dim3(256), 0, st, a.counts_wide, c.cnt, a.counts);
+                return VG_OK;
+            }
             return launch_big(flat_gemm_codes_big_kernel<false, 3>, big_lds_bytes<3>(), a.codes, a.code_m);
         }
         VG_CHECK(false, VG_ERR_INVALID_ARG, "launch_gemm: the code-gathered tile is L2's append");
@@ -1668,7 +1679,9 @@ int32_t flat_nominate_bf16(vg_index *idx, const NomImage &img, bool dot, const f
     {
         const bool i4_small = img.int4 && cnt <= kGemmBM && int4_small_tile_fits(idx->dim);  // (launch_gemm's choice: the small INT4 tile)
         const bool s8_small = !img.int4 && img.scale && cnt <= kGemmBM && sq8_small_tile_fits(idx->dim);  // (likewise: the small SQ8 tile)
-        ProfScope prof(idx->ctx, i4_small ? "int4_codes_gemm_small" : img.int4 ? "int4_codes_gemm" : s8_small ? "sq8_codes_gemm_small" : img.scale ? "sq8_codes_gemm" : img.from_codes ? "pq_codes_gemm" : "sq8_nominate_gemm", st);
+        const bool pq_small = !img.int4 && !img.scale && img.from_codes && cnt <= kGemmBM &&
+                              pq_small_tile_takes(idx->pq->m, idx->n);  // (likewise: the small PQ tile)
+        ProfScope prof(idx->ctx, i4_small ? "int4_codes_gemm_small" : img.int4 ? "int4_codes_gemm" : s8_small ? "sq8_codes_gemm_small" : img.scale ? "sq8_codes_gemm" : pq_small ? "pq_codes_gemm_small" : img.from_codes ? "pq_codes_gemm" : "sq8_nominate_gemm", st);
         GemmArgs a = GemmArgs::append(nc, nom->thr, nom->sel_k, nom->counts, nom->cand, nom->cap).wide(s.counts_wide, idx->ctx->compute_units);
         if (img.int4)
             a.from_int4_codes(idx->d_int4_rows, idx->dim / 2);

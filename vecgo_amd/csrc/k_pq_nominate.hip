@@ -135,19 +135,65 @@ struct PqTableRow {
     static constexpr bool kShifted = false;  // (the GEMM multiplies the decoded rows themselves)
 };
 
-// The nomination from the codes (vg_index_enable_pq_nomination_from_codes) takes more than 128 queries — the persistent
-// tile's batches; the gathered fill has no 128-row form — and has its own crossover against the scan (tools/pq_nominate_codes_time.py,
+// The nomination from the codes (vg_index_enable_pq_nomination_from_codes) takes more than 128 queries on the persistent tile —
+// its gathered fill has no 128-row form; fewer run the tile below when it is enabled — and has its own crossover against the scan (tools/pq_nominate_codes_time.py,
 // ms scanned / from the codes, k = 10 and k = 100): 129 queries x 100k rows 0.31 / 0.24 and 0.53 / 0.32, x 300k 0.71 / 0.31, x 1M
 // 2.0 / 0.56; 1024 x 1M 12.5 / 1.68, 1024 x 10M 118 / 14.8 — it won at every batch measured, the smallest 12.9M pairs.
 constexpr int64_t kPqNomCodesMinPairs = 13000000;
+// The same for batches of 5 .. 128 queries when the mode was enabled with on = 2 (NomImage::pq_small; reported as mode 3): the tile
+// of one query tile (flat_gemm_pq_small_kernel, vg_pq_small_gemm.hpp), where a block of 32 queries' image of a row fits that
+// tile's LDS (pq_small_tile_fits: m <= 318) and the codes are at least the 16 bytes of one load, from kPqNomCodesSmallMinPairs
+// pairs up.
+// Measured (MI355X, tools/pq_nominate_codes_time.py 10000000 small, dim 768, m = 96, k = 10, ms per call, scan / mode 3 / image
+// mode, alternating windows of ~300 ms in one run on one index per segment size, every shape warmed, the median of 5; the windows
+// of a leg lay within 1 % of each other, 9 % at 128 x 100k; bits equal at every shape; profiles/pq_nominate_codes_time_small.txt):
+//   100k rows —   8 queries 0.040 / 0.168 / 0.208,  32: 0.077 / 0.175 / 0.277,  64: 0.134 / 0.195 / 0.346,  96: 0.189 / 0.212 / 0.338,
+//                128: 0.245 / 0.244 / 0.383
+//   1M rows   —   8: 0.128 / 0.340 / 0.386,  32: 0.417 / 0.347 / 0.411,  64: 0.811 / 0.363 / 0.442,  96: 1.206 / 0.387 / 0.474,
+//                128: 1.601 / 0.558 / 0.509  (k = 100: 1.858 / 0.646 / 0.626)
+//   10M rows  —   8: 0.970 / 2.026 / 2.445,  32: 3.734 / 2.072 / 2.552,  64: 7.418 / 2.110 / 2.594,  96: 11.12 / 2.203 / 3.099,
+//                128: 14.82 / 4.009 / 3.391
+// The GEMM's own time (its profile scope): 100k — 0.032, 0.037, 0.050, 0.062, 0.092 ms; 1M — 0.184, 0.189, 0.200, 0.220, 0.388
+// (k = 100: 0.413); 10M — 1.730, 1.757, 1.763, 1.807, 3.571: one pass costs the same from 8 to 96 queries, 128 queries are two
+// passes (two launches of two blocks).  What bounds a pass is NOT established.  It is not HBM (96 MB of code bytes a pass over 1M
+// rows: 0.012 ms at 8 TB/s; 0.55 TB/s reached) and not the matrix unit (49 GFLOP at one block: 0.02 ms).  A pass gathers 1.5 GB of
+// codebook entries through the vector caches: 8.3 TB/s at 1M rows, 8.7 TB/s at 10M — over 256 CUs at 2.4 GHz that is 13.5 .. 14.2 B
+// a clock and CU, 21 .. 22 % of the 64 B a clock a CU's vector cache nominally delivers (39 TB/s over the chip; the nominal figure
+// was not measured here).  At a fifth of that rate the gather's throughput is not shown to be the limit: with 18 loads in flight a
+// wave and 2 .. 3 waves a SIMD the pass may as well be bound by the gathers' latency or by occupancy; no counter run separated
+// them.  The rest of a call (0.16 ms: the sample, the pick, the tables and the verify) is not this kernel's.  From the ISA
+// (re-read after the change below): the K loop's waits are all counted, vmcnt(17) and vmcnt(16) before a step's two matrix
+// instructions — the 16 gathers and the code load issued behind the slot — and the ring's registers are reused in place (no copy
+// at a chunk's end, unlike both siblings); a gather is three vector instructions (shift, and-or, shift), not two.  The epilogue's
+// first wait is vmcnt(19), for the tile's two norms, loaded ahead of the tile's first chunk: the next position's 16 gathers and 2
+// code loads stay in flight under it (the chunk loop is a do-while: with a path around it the compiler had put vmcnt(1) there,
+// a drain at every tile's end).  What still drains the ring: an APPEND — the returning atomic is waited for with vmcnt(0), in the
+// branch only a lane with a row below its threshold takes — and the first steps of a tile wait two loads deeper than the ring
+// asks, the norms' loads lying between two chunks' gathers.  Gathers run a chunk of 128 dimensions ahead and the codes two.  The
+// timings above were taken before that change of the tile's end.  A second run after it (the same file, run 2) gave every mode-3
+// figure within 3 % of the table, 96 x 10M 2.321 ms (5 % above): the change bought nothing measurable, the crossover is the same.
+// The nomination LOST to the scan at every 100k-row shape (0.24x .. 0.89x, a tie at 128 x 100k) and at 8 queries at every size
+// (0.38x at 1M, 0.48x at 10M: a pass over the codes costs the same for 8 queries as for 96, the scan 12 us a query and 1M rows).
+// It won from 32 queries x 1M rows up: 1.20x, 64: 2.23x, 96: 3.12x, 128: 2.87x; 10M rows: 1.80x, 3.52x, 5.05x, 3.70x — by far more
+// than the spread.  Because 8 x 10M (80M pairs) lost where 32 x 1M (32M pairs) won, a product alone does not separate them: the
+// batch size 8 stays on the scan as a whole (kPqNomCodesSmallMinQueries: 32, the smallest batch measured that won; nothing between
+// 8 and 32 queries was measured) and the constant is the smallest product measured at which the nomination won, 32 x 1M; nothing
+// between 12.8M and 32M pairs was measured.  Against the image mode it is 0.71x .. 0.85x of the time up to 96 queries and 1.10x ..
+// 1.18x at 128 (two passes), holding 4 bytes a row where the image holds 16x the codes.  Test hook VG_PQ_NOM_ALWAYS: any batch of
+// 5 queries up.
+constexpr int kPqNomCodesSmallMinQueries = 32;
+constexpr int64_t kPqNomCodesSmallMinPairs = 32000000;
 
 // whether a batch takes the nomination (device queries; ascending table sums over the whole segment, no row filter)
 bool pq_nomination_applies(const vg_index *idx, const float *d_queries, int64_t nq, int k, const uint8_t *mask, bool desc)
 {
     const int mode = idx->pq_nom.mode();
-    const int64_t min_pairs = mode == 2 ? kPqNomCodesMinPairs : kPqNomMinPairs;
-    return mode && !mask && !desc && (mode == 1 || nq > 128) && (nq * idx->n >= min_pairs || hook(kHookPqNomAlways)) && k <= kNomMaxK &&
-           idx->n > k && idx->pq->k == 256 && aligned16(d_queries);
+    const bool small = mode == 2 && nq <= 128;  // the small tile's batches, where it was enabled and takes the rows
+    if (small && (!idx->pq_nom.pq_small || nq < 5 || !pq_small_tile_takes(idx->pq->m, idx->n))) return false;
+    if (small && nq < kPqNomCodesSmallMinQueries && !hook(kHookPqNomAlways)) return false;
+    const int64_t min_pairs = small ? kPqNomCodesSmallMinPairs : mode == 2 ? kPqNomCodesMinPairs : kPqNomMinPairs;
+    return mode && !mask && !desc && (nq * idx->n >= min_pairs || hook(kHookPqNomAlways)) && k <= kNomMaxK && idx->n > k && idx->pq->k == 256 &&
+           aligned16(d_queries);
 }
 
 // nominated_pass with the PQ re-score.  (From the codes the GEMM's operands are the image's, bit for bit: the same margin,
@@ -165,7 +211,7 @@ int32_t pq_nominated_pass(vg_index *idx, const float *q, int64_t nq, int k, uint
 }
 }  // namespace vg
 
-// vg_index_enable_pq_nomination (mode 1) and vg_index_enable_pq_nomination_from_codes (mode 2); fn: the entry point's name.
+// vg_index_enable_pq_nomination (mode 1) and vg_index_enable_pq_nomination_from_codes (mode 2; on == 2: small batches too); fn: the entry point's name.
 // Turning a mode off, or on again, drops that mode only; turning it on drops the other one too, but only once nothing can refuse.
 static int32_t pq_nomination_enable(vg_index *idx, int mode, int32_t on, void *stream, const char *fn)
 {
@@ -183,7 +229,7 @@ static int32_t pq_nomination_enable(vg_index *idx, int mode, int32_t on, void *s
              "%s: needs sub-vectors of 8 dimensions (got %d): a 16-byte granule of a row is one centroid", fn, pq->subdim);
     VG_TRY(vg::nom_free(idx->pq_nom, st));
     const int dim_pad = vg::nom_dim_pad(idx->dim), blocks = dim_pad / 8;
-    return vg::nom_build(idx->pq_nom, idx->n, idx->dim, vg::NomImage::body_bytes(idx->n, dim_pad, from_codes), from_codes, st,
+    VG_TRY(vg::nom_build(idx->pq_nom, idx->n, idx->dim, vg::NomImage::body_bytes(idx->n, dim_pad, from_codes), from_codes, st,
                          [&](const vg::NomImage &b, int *norm_max_bits) {
                              const dim3 rows_grid(static_cast<unsigned>((idx->n + 3) / 4));
                              if (!from_codes) {
@@ -195,7 +241,9 @@ static int32_t pq_nomination_enable(vg_index *idx, int mode, int32_t on, void *s
                                                 pq->d_scales, pq->d_offsets, pq->m, blocks, reinterpret_cast<uint4 *>(b.rows));
                              hipLaunchKernelGGL(vg::pq_norms_kernel, rows_grid, dim3(256), 0, st, idx->d_pq_rows, idx->n, pq->m, pq->k, pq->subdim,
                                                 pq->d_codebooks, pq->d_scales, pq->d_offsets, b.norms, norm_max_bits);
-                         });
+                         }));
+    idx->pq_nom.pq_small = from_codes && on == 2;  // (any other non-zero value is 1)
+    return VG_OK;
 }
 
 VG_API int32_t vg_index_enable_pq_nomination(vg_index *idx, int32_t on, void *stream)
@@ -211,7 +259,7 @@ VG_API int32_t vg_index_enable_pq_nomination_from_codes(vg_index *idx, int32_t o
 VG_API int32_t vg_index_pq_nomination_info(const vg_index *idx, int32_t *mode, int64_t *held_bytes)
 {
     VG_CHECK(idx, VG_ERR_INVALID_ARG, "vg_index_pq_nomination_info: NULL index");
-    if (mode) *mode = idx->pq_nom.mode();
+    if (mode) *mode = idx->pq_nom.pq_small ? 3 : idx->pq_nom.mode();  // (3: from the codes, small batches too)
     if (held_bytes) *held_bytes = idx->pq_nom.held_bytes(idx->n);
     return VG_OK;
 }

@@ -1,0 +1,61 @@
+// k_pq_small.hip — the launcher of the PQ nomination's small-batch append GEMM (flat_gemm_pq_small_kernel,
+// vg_pq_small_gemm.hpp) for gfx950: which 32-query blocks share a launch, its LDS and its persistent grid.  Called by launch_gemm
+// (k_flat.hip) for an append over PQ codes with at most 128 queries.
+#include <algorithm>
+
+#include "vg_internal.hpp"
+#include "vg_nominate.hpp"
+#include "vg_pq_small_gemm.hpp"
+
+namespace vg {
+// Whether one block of 32 queries' image of a row of m sub-quantizers fits in LDS: the small tile's only limit on m (m <= 318)
+bool pq_small_tile_fits(int m) { return m > 0 && pq_small_lds_bytes(1, m) <= kPqsLdsMax; }
+// ... and the codes of n rows hold the 16 bytes of one of its code loads: what the launch, the profile scope and the batches' test ask
+bool pq_small_tile_takes(int m, int64_t n) { return pq_small_tile_fits(m) && n * m >= 16; }
+
+template <int RB>
+static int32_t launch_rb(size_t lds, int cus, int64_t ntiles, hipStream_t st, const uint16_t *q, int nq, int dim_pad, const uint8_t *codes, int64_t n,
+                         int m, const uint4 *cb16, const float *norms, const float *thr, int thr_stride, int thr_off, int *counts, int count_stride,
+                         uint64_t *cand, int cap)
+{
+    auto kern = flat_gemm_pq_small_kernel<RB>;
+    VG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
+    // persistent: as many workgroups as the device holds at once (LDS and registers decide how many a CU takes), a tile each at most
+    int per_cu = 1;
+    VG_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, kPqsThreads, lds));
+    const int64_t grid = std::min<int64_t>(ntiles, static_cast<int64_t>(std::max(cus, 1)) * std::max(per_cu, 1));
+    VG_LAUNCH(kern, dim3(static_cast<unsigned>(grid)), dim3(kPqsThreads), lds, st, q, nq, dim_pad, codes, n, m, cb16, norms, thr, thr_stride, thr_off,
+              counts, count_stride, cand, cap);
+    return VG_OK;
+}
+
+// cnt <= 128 queries (qimg: cnt x dim_pad bfloat16) against n > 0 rows of m code bytes (n m >= 16) and the decoded codebook cb16 of
+// dim_pad / 8 slices.  The image of the blocks of a launch is resident in LDS: where all of the batch's blocks do not fit, the
+// batch runs as the fewest launches of equally many blocks that do (a pass over the codes each) — decided here, once, from the shapes.
+int32_t launch_pq_small_gemm(const uint16_t *qimg, int64_t cnt, int dim_pad, const uint8_t *codes, int64_t n, int m, const uint4 *cb16,
+                             const float *norms, const float *thr, int thr_stride, int thr_off, int *counts, int count_stride, uint64_t *cand, int cap,
+                             int cus, hipStream_t st)
+{
+    VG_CHECK(cnt > 0 && cnt <= 128 && n > 0 && pq_small_tile_takes(m, n) && dim_pad >= 16 * pq_small_steps(m) && dim_pad % 8 == 0 && aligned16(qimg, cb16),
+             VG_ERR_INVALID_ARG, "launch_pq_small_gemm: a call the small PQ tile does not take");
+    const int rb = static_cast<int>((cnt + 31) / 32);
+    int launches = 1;
+    while (pq_small_lds_bytes((rb + launches - 1) / launches, m) > kPqsLdsMax) launches++;
+    const int per = (rb + launches - 1) / launches;  // blocks a launch
+    const int64_t ntiles = (n + kPqsBN - 1) / kPqsBN;
+    for (int64_t q0 = 0; q0 < cnt; q0 += per * 32) {
+        const int qc = static_cast<int>(std::min<int64_t>(per * 32, cnt - q0)), b = (qc + 31) / 32;
+        const size_t lds = pq_small_lds_bytes(b, m);
+        auto go = [&](auto kern_rb) {
+            return launch_rb<decltype(kern_rb)::value>(lds, cus, ntiles, st, qimg + q0 * dim_pad, qc, dim_pad, codes, n, m, cb16, norms,
+                                                       thr + q0 * thr_stride, thr_stride, thr_off, counts + q0 * count_stride, count_stride,
+                                                       cand + q0 * cap, cap);
+        };
+        VG_TRY(b == 1   ? go(std::integral_constant<int, 1>{})
+               : b == 2 ? go(std::integral_constant<int, 2>{})
+               : b == 3 ? go(std::integral_constant<int, 3>{})
+                        : go(std::integral_constant<int, 4>{}));
+    }
+    return VG_OK;
+}
+}  // namespace vg

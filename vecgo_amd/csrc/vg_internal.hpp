@@ -490,8 +490,9 @@ struct NomImage {
     bool int4 = false;
     bool int4_small = false;       // with `int4`: enabled with on = 2 — batches of 5 .. 128 queries take the nomination too
     bool sq8_small = false;        // with `scale` (SQ8 from the codes): enabled with on = 2 — batches of 5 .. 128 queries take the nomination too
+    bool pq_small = false;         // PQ from the codes (from_codes, neither of the above): enabled with on = 2 — likewise
     int64_t body = 0;             // bytes of `rows`
-    // what vg_index_pq_nomination_info reports: 0 off, 1 the image of the decoded rows, 2 from the codes
+    // 0 off, 1 the image of the decoded rows, 2 from the codes (vg_index_pq_nomination_info reports 3 for 2 with pq_small)
     int mode() const { return !rows ? 0 : from_codes ? 2 : 1; }
     uint16_t *row_image() const { return from_codes ? nullptr : rows; }  // the decoded rows, where the mode keeps them
     static int64_t body_bytes(int64_t n, int dim_pad, bool from_codes) { return (from_codes ? int64_t(dim_pad / 8) * 256 * 8 : n * dim_pad) * 2; }

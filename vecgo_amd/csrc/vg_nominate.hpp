@@ -62,6 +62,14 @@ template <bool DOT>
 int32_t launch_sq8_small_gemm(const uint16_t *qimg, int64_t cnt, int dim_pad, const uint8_t *tiles, int64_t n, int groups, const float *norms,
                               const float *thr, int thr_stride, int thr_off, int *counts, int count_stride, uint64_t *cand, int cap, int cus,
                               hipStream_t st);
+// k_pq_small.hip: the PQ append GEMM of one query tile gathered from the decoded codebook by the codes (cnt <= 128;
+// flat_gemm_pq_small_kernel) — whether a row of m sub-quantizers fits its LDS at all (m <= 318), and the launch (qimg: cnt x dim_pad
+// bfloat16; codes: n rows of m bytes, n m >= 16; cb16: NomImage::rows of a from_codes state; counts[q * count_stride]; cus: compute units)
+bool pq_small_tile_fits(int m);
+bool pq_small_tile_takes(int m, int64_t n);  // fits, and n m >= 16: the one test of whether a batch of at most 128 queries runs the tile
+int32_t launch_pq_small_gemm(const uint16_t *qimg, int64_t cnt, int dim_pad, const uint8_t *codes, int64_t n, int m, const uint4 *cb16,
+                             const float *norms, const float *thr, int thr_stride, int thr_off, int *counts, int count_stride, uint64_t *cand, int cap,
+                             int cus, hipStream_t st);
 
 // Builds the nomination state of n rows of dim elements into `img` (empty): its body of body_bytes (NomImage::body_bytes — the
 // decoded rows, or from_codes the decoded codebook), the norms and norm_max.  launch(const NomImage &, int *norm_max_bits) launches
