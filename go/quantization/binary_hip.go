@@ -143,6 +143,44 @@ func (bq *HIPBinaryQuantizer) ComputeHammingDistanceBatch(query []float32, codes
 	return hipctx.Err(int32(st))
 }
 
+// AttachCodes hands n codes of words() uint64 each to a resident index (segment.Resident.Handle()): held once on the
+// device, scanned by SearchCodes.  codes nil drops them.
+func (bq *HIPBinaryQuantizer) AttachCodes(index unsafe.Pointer, codes []uint64) error {
+	var pc *C.uint8_t
+	if len(codes) > 0 {
+		pc = (*C.uint8_t)(unsafe.Pointer(&codes[0]))
+	}
+	return hipctx.Err(int32(C.vg_index_set_binary_codes((*C.vg_index)(index), C.float(bq.threshold), pc, nil)))
+}
+
+// SearchCodes: the k nearest codes of each of nq row-major float queries by (Hamming distance, row id); scores are the
+// distances as float32, unused slots 0xFFFFFFFF / +Inf.  mask: bit i of byte i/8 = row i takes part, maskStride bytes apart
+// per query or 0 for one mask, nil for every row.
+func (bq *HIPBinaryQuantizer) SearchCodes(index unsafe.Pointer, queries []float32, nq, k int, mask []byte, maskStride int) ([]uint32, []float32, error) {
+	if len(queries) != nq*bq.dimension {
+		return nil, nil, hipctx.ErrDimensionMismatch
+	}
+	ids, scores := make([]uint32, nq*k), make([]float32, nq*k)
+	if nq == 0 || k == 0 {
+		return ids, scores, nil
+	}
+	var pm *C.uint8_t
+	if len(mask) > 0 {
+		pm = u8(mask)
+	}
+	st := C.vg_search_binary((*C.vg_index)(index), f32(queries), C.int64_t(nq), C.int32_t(k), pm, C.int64_t(maskStride),
+		(*C.uint32_t)(unsafe.Pointer(&ids[0])), f32(scores), nil)
+	return ids, scores, hipctx.Err(int32(st))
+}
+
+// CodesInfo: the device bytes an index's binary codes hold, the queries a matrix-core path answered and those of them the
+// scan answered after all.
+func (bq *HIPBinaryQuantizer) CodesInfo(index unsafe.Pointer) (codeBytes, nominated, rescanned int64, err error) {
+	var b, n, r C.int64_t
+	st := C.vg_index_binary_info((*C.vg_index)(index), &b, &n, &r)
+	return int64(b), int64(n), int64(r), hipctx.Err(int32(st))
+}
+
 func (bq *HIPBinaryQuantizer) BytesPerDimension() int { return 0 }                         // binary.go:194-196
 func (bq *HIPBinaryQuantizer) BytesTotal() int        { return (bq.dimension + 7) / 8 }    // binary.go:199-201
 func (bq *HIPBinaryQuantizer) WordBytes() int         { return int(C.vg_binary_code_bytes(C.int32_t(bq.dimension))) }

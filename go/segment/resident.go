@@ -137,6 +137,10 @@ func (r *Resident) UploadInt4Codes(iq unsafe.Pointer, codes []byte) error {
 	return hipctx.Err(int32(C.vg_index_set_int4_codes(r.h, (*C.vg_int4)(iq), bp(codes), nil)))
 }
 
+// Handle: the index behind the segment, for the bindings that live with their quantizer (HIPBinaryQuantizer.AttachCodes /
+// SearchCodes / CodesInfo).
+func (r *Resident) Handle() unsafe.Pointer { return unsafe.Pointer(r.h) }
+
 // UploadRaBitQCodes: n*BytesTotal() code bytes (diskann/segment.go:1393-1408).
 func (r *Resident) UploadRaBitQCodes(codes []byte) error {
 	return hipctx.Err(int32(C.vg_index_set_rabitq_codes(r.h, bp(codes), nil)))

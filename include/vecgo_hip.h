@@ -122,7 +122,9 @@ extern "C" {
  *  entry point vg_int4_scan_plan, found by symbol lookup.  Likewise the RaBitQ batch nomination on the int8 matrix cores:
  *  vg_index_enable_rabitq_nomination and vg_index_rabitq_nomination_info, found by symbol lookup.  Likewise the exhaustive
  *  search over an index's INT4 codes, vg_search_int4, found by symbol lookup.  Likewise its batch nomination on the matrix cores:
- *  vg_index_enable_int4_nomination and vg_index_int4_nomination_info, found by symbol lookup. */
+ *  vg_index_enable_int4_nomination and vg_index_int4_nomination_info, found by symbol lookup.  Likewise the exhaustive Hamming
+ *  search over an index's binary codes: vg_index_set_binary_codes, vg_search_binary and vg_index_binary_info, found by symbol
+ *  lookup. */
 #define VG_ABI_MINOR 13
 #define VG_INVALID_ID 0xFFFFFFFFu
 #define VG_STREAM_LEGACY ((void *)1) /* == hipStreamLegacy */
@@ -1123,6 +1125,39 @@ int32_t vg_index_set_int4_codes(vg_index *idx, vg_int4 *iq, const uint8_t *codes
  *   answers padding.  Found by symbol lookup (see VG_ABI_MINOR). */
 int32_t vg_search_int4(vg_index *idx, const float *queries, int64_t nq, int32_t k, const uint8_t *mask, int64_t mask_stride,
                        uint32_t *ids, float *scores, void *stream);
+
+/* ---- exhaustive Hamming search over BinaryQuantizer codes (internal/quantization/binary.go) ----
+ * vg_index_set_binary_codes: n codes of vg_binary_code_bytes(dim) bytes each, row-major, host or device at any alignment —
+ * exactly what vg_binary_encode writes (Encode / EncodeUint64Into, binary.go:86-154; the bits past dim are zero).  `threshold`
+ * is kept for encoding the queries.  A second call replaces the codes, codes NULL drops them.  Resident: the codes once, row-major,
+ * padded with zero rows to whole 64-row tiles; no second copy in another layout.  An index that holds binary codes is a segment's:
+ * vg_hnsw_insert, vg_hnsw_compact, vg_vamana_insert, vg_vamana_reorder_bfs, vg_flat_build and vg_diskann_build refuse it
+ * (VG_ERR_UNSUPPORTED, "binary codes" in the message) until the codes are dropped; vg_index_merge carries no codes over.
+ * Status: NULL index VG_ERR_INVALID_ARG.
+ * vg_search_binary: queries are float32 rows, encoded on the device by Encode's rule (v[i] >= threshold) as ComputeHammingDistance
+ * does (binary.go:158-171); scores[q * k + i] = float(popcount(code_q xor code_row)) (HammingDistance, :221-239), exact, so the
+ * lists feed vg_merge_topk, the sharded fan-in and vg_rerank unchanged.  ids: the k best rows by (Hamming distance, row id)
+ * ascending, under every index metric; unused slots VG_INVALID_ID / +Inf.  mask / mask_stride: vg_search_int4's convention (one
+ * mask for the batch — a 64-row tile none of whose rows it keeps is not read —, one per query, or NULL).  k <= 512 (pages of 64
+ * results, one scan per page); dim <= 196608.  One kernel serves every batch: a workgroup carries 16 queries (4 up to 4 queries,
+ * 1 for one) over its slice of the rows, each 64-row tile read once per block with 16-byte loads (dim > 1024 with an odd number
+ * of 64-bit words: 8-byte loads, slower).  Per call: the queries' codes, the partial lists and the page state.
+ *   Refusals, in this order, nothing written: NULL index VG_ERR_INVALID_ARG; negative nq or k VG_ERR_INVALID_ARG; nq == 0 or
+ *   k == 0 VG_OK; rows but no binary codes VG_ERR_NOT_READY; NULL queries / ids / scores VG_ERR_INVALID_ARG; k > 512
+ *   VG_ERR_UNSUPPORTED; mask_stride nonzero, nq > 1 and mask_stride < ceil(rows / 8) VG_ERR_INVALID_ARG.  An index without rows
+ *   answers padding.
+ *   Unfiltered batches of more than 128 queries (code bytes <= 1024, k <= 256, rows > k, queries x rows >= 102.4M, or 12.9M when k > 64) go through the
+ *   int8 matrix cores: a threshold from every 64th row tile, a 256 x 256 tile GEMM fed from the same row-major codes whose
+ *   epilogue lists the rows at or below the threshold, a select kernel with the proof (the list did not overflow and holds k keys);
+ *   a query whose proof fails — rows tied at the threshold can outnumber the list — is answered by the scan.  Nothing is resident
+ *   for it and no result changes.
+ * vg_index_binary_info: *code_bytes the device bytes the codes hold (0: none); *nominated / *rescanned the queries the matrix-core
+ * path answered, and those of them the scan had to answer after all, since the codes were set.  Any of the three may be NULL.
+ * All three found by symbol lookup (see VG_ABI_MINOR). */
+int32_t vg_index_set_binary_codes(vg_index *idx, float threshold, const uint8_t *codes, void *stream);
+int32_t vg_search_binary(vg_index *idx, const float *queries, int64_t nq, int32_t k, const uint8_t *mask, int64_t mask_stride,
+                         uint32_t *ids, float *scores, void *stream);
+int32_t vg_index_binary_info(const vg_index *idx, int64_t *code_bytes, int64_t *nominated, int64_t *rescanned);
 
 /* ---- graph construction: neighbour selection ---------------------- */
 /* Vamana robustPrune (diskann/writer.go:571-625) for n_nodes nodes at once.  cands[n_nodes*nc]

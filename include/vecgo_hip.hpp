@@ -729,6 +729,21 @@ public:
         check(vg_index_int4_nomination_info(h_, &r.mode, &r.held_bytes, &r.rescanned));
         return r;
     }
+    // BinaryQuantizer codes of the rows (what vg_binary_encode writes), the threshold the queries are encoded with; nullptr drops them
+    void SetBinaryCodes(float threshold, const uint8_t *codes) { check(vg_index_set_binary_codes(h_, threshold, codes, nullptr)); }
+    // exhaustive Hamming scan of the binary codes: scores float(popcount(code_q xor code_row)), the k best by (distance, row id)
+    // under every metric; k <= 512; mask as SearchInt4's
+    Result SearchBinary(const float *queries, int64_t nq, int k, const uint8_t *mask = nullptr, int64_t mask_stride = 0) { return run(nq, k, [&](Result &r) { return vg_search_binary(h_, queries, nq, k, mask, mask_stride, r.ids.data(), r.scores.data(), nullptr); }); }
+    // code_bytes: the device memory the codes hold; nominated / rescanned: queries a matrix-core path answered and gave back (0: none)
+    struct BinaryCodes {
+        int64_t code_bytes, nominated, rescanned;
+    };
+    BinaryCodes BinaryInfo() const
+    {
+        BinaryCodes r{0, 0, 0};
+        check(vg_index_binary_info(h_, &r.code_bytes, &r.nominated, &r.rescanned));
+        return r;
+    }
     // IVF partitions (flat/segment.go:187-207) and the probed scan of flat.Segment.Search (:727-749):
     // scan = VG_SCAN_F32 / VG_SCAN_PQ / VG_SCAN_SQ8, nprobes <= 0 means 1 as in the reference
     void SetPartitions(const float *centroids, const uint32_t *part_offsets, int num_partitions)

@@ -953,6 +953,29 @@ class Index:
         m, pm, stride = (None, None, 0) if mask is None else self._packed_mask(mask, _rows(queries, self.dim), "search_int4")
         return self._search(self._lib.vg_search_int4, queries, k, extra=(pm, C.c_int64(stride)), out=out, stream=stream)
 
+    def set_binary_codes(self, bq: "BinaryQuantizer", codes, stream=None):
+        """vg_index_set_binary_codes: [n, words * 8] uint8 as bq.encode writes them (numpy or torch, host or device), held once,
+        row-major; bq.threshold encodes the queries of search_binary.  codes None drops them."""
+        if codes is None:
+            check(self._lib.vg_index_set_binary_codes(self._h, C.c_float(0.0), None, _stream_ptr(stream)))
+            return
+        c, pc = _ptr(codes, np.uint8, self.n * bq.words * 8)
+        check(self._lib.vg_index_set_binary_codes(self._h, C.c_float(float(bq.threshold)), pc, _stream_ptr(stream)))
+
+    def search_binary(self, queries, k, mask=None, out=None, stream=None):
+        """Exhaustive Hamming scan of the binary codes (vg_search_binary): the float32 queries are encoded by the quantizer's rule
+        and scored as ComputeHammingDistance scores them (binary.go:158-171); scores are float(popcount(xor)), the k best by
+        (distance, row id) whatever the metric.  mask: as search_int4's.  k <= 512."""
+        m, pm, stride = (None, None, 0) if mask is None else self._packed_mask(mask, _rows(queries, self.dim), "search_binary")
+        return self._search(self._lib.vg_search_binary, queries, k, extra=(pm, C.c_int64(stride)), out=out, stream=stream)
+
+    def binary_info(self):
+        """vg_index_binary_info: (code_bytes, nominated, rescanned) — the device bytes the codes hold; the queries a matrix-core path
+        answered and those of them the scan answered after all (both 0: every query is the scan's)."""
+        held, nominated, rescanned = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        check(self._lib.vg_index_binary_info(self._h, C.byref(held), C.byref(nominated), C.byref(rescanned)))
+        return held.value, nominated.value, rescanned.value
+
     def set_partitions(self, centroids, part_offsets, stream=None):
         """IVF partitions of a flat segment (flat/segment.go:187-207): centroids [P, dim] fp32 and the
         first row of every partition [P + 1] uint32; None / empty removes them."""

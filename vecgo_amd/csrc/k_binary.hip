@@ -16,6 +16,7 @@
 #include "vg_device.hpp"
 #include "vg_exact.hpp"
 #include "vg_internal.hpp"
+#include "vg_search.hpp"
 
 namespace vg {
 
@@ -115,6 +116,13 @@ __global__ __launch_bounds__(256) void normalize_l2_kernel(float *__restrict__ v
     if (L == 0 && ok) ok[row] = 1;
 }
 
+int32_t launch_binary_encode(const float *d_vectors, int64_t n, int dim, float threshold, uint8_t *d_codes, hipStream_t st)
+{
+    VG_LAUNCH(binary_encode_kernel, dim3(static_cast<unsigned>((n + 15) / 16)), dim3(256), 0, st, d_vectors, n, dim,
+              static_cast<const float *>(nullptr), threshold, d_codes);
+    return VG_OK;
+}
+
 }  // namespace vg
 
 VG_API int64_t vg_binary_code_bytes(int32_t dim) { return static_cast<int64_t>((dim + 63) / 64) * 8; }
@@ -156,8 +164,7 @@ VG_API int32_t vg_binary_encode(vg_ctx *ctx, int32_t dim, float threshold, const
     vg::DevOut<uint8_t> c;
     VG_TRY(v.init(vectors, static_cast<size_t>(n) * dim, st));
     VG_TRY(c.init(codes, static_cast<size_t>(n) * vg_binary_code_bytes(dim), st));
-    VG_LAUNCH(vg::binary_encode_kernel, dim3(static_cast<unsigned>((n + 15) / 16)), dim3(256), 0, st, v.ptr, n, dim,
-              static_cast<const float *>(nullptr), threshold, c.ptr);
+    VG_TRY(vg::launch_binary_encode(v.ptr, n, dim, threshold, c.ptr, st));
     VG_TRY(c.finish());
     return VG_OK;
 }

@@ -315,6 +315,7 @@ VG_API int32_t vg_vamana_reorder_bfs(vg_index *idx, uint32_t *perm, uint32_t *in
              "vg_vamana_reorder_bfs: the index holds %s, state of a memtable or flat segment that the DiskANN writer never has",
              idx->d_hnsw_l0 ? "an HNSW graph" : idx->d_hnsw_tomb ? "HNSW tombstones" : idx->d_hnsw_l0_dist ? "HNSW edge distances"
                                                                                              : "IVF partitions");
+    VG_CHECK(!idx->d_bin_rows, VG_ERR_UNSUPPORTED, "vg_vamana_reorder_bfs: the index holds binary codes, which the permutation would leave behind");
     const int64_t n = idx->n;
     if (n == 0) return VG_OK;
     VG_HIP(hipSetDevice(idx->ctx->device));

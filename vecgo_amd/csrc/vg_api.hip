@@ -310,6 +310,7 @@ VG_API int32_t vg_index_destroy(vg_index *idx)
     (void)vg::nom_free(idx->pq_nom, idx->ctx->stream);
     (void)vg::nom_free(idx->i4_nom, idx->ctx->stream);
     if (idx->d_int4_rows) (void)hipFree(idx->d_int4_rows);
+    if (idx->d_bin_rows) (void)hipFree(idx->d_bin_rows);
     if (idx->d_centroids) (void)hipFree(idx->d_centroids);
     if (idx->d_part_off) (void)hipFree(idx->d_part_off);
     delete idx;
@@ -330,7 +331,8 @@ static const char *const kHookNames[kHookCount] = {"VG_FLAT_NO_SMALL_TILE", "VG_
                                                    "VG_VAMANA_SMALL_SCRATCH", "VG_FLAT_RESCORE_SAMPLE", "VG_PTHR_FORCE_HIST",
                                                    "VG_WALK_SMALL_SCRATCH", "VG_FLAT_NO_SPLIT", "VG_FLAT_NO_SCREEN", "VG_FLAT_SCREEN_FAIL",
                                                    "VG_FLAT_F32_SAMPLE", "VG_PREFILTER_SMALL_SCRATCH", "VG_BM25_SMALL_SCRATCH",
-                                                   "VG_INT4_SMALL_GRID", "VG_INT4_SEARCH_SMALL_GRID", "VG_ADC_WIDE_ALWAYS", "VG_RABITQ_NOM_ALWAYS", "VG_INT4_NOM_ALWAYS", "VG_RABITQ_NOM_CHECK"};
+                                                   "VG_INT4_SMALL_GRID", "VG_INT4_SEARCH_SMALL_GRID", "VG_ADC_WIDE_ALWAYS", "VG_RABITQ_NOM_ALWAYS", "VG_INT4_NOM_ALWAYS", "VG_RABITQ_NOM_CHECK",
+                                                   "VG_BINARY_SMALL_GRID", "VG_BINARY_NOM_ALWAYS", "VG_BINARY_NO_NOM"};
 static void hooks_from_env()
 {
     for (int h = 0; h < kHookCount; h++) {

@@ -111,6 +111,9 @@ enum Hook {
     kHookRabitqNomAlways,     // VG_RABITQ_NOM_ALWAYS  vg_index_enable_rabitq_nomination: no crossover of (query, row) pairs
     kHookInt4NomAlways,       // VG_INT4_NOM_ALWAYS    vg_index_enable_int4_nomination: no crossover of (query, row) pairs
     kHookRabitqNomCheck,      // VG_RABITQ_NOM_CHECK   vg_index_enable_rabitq_nomination: the verify compares every listed key's Hamming distance (the GEMM's) with its own popcount and counts the disagreements (vg_index_rabitq_nomination_info's `mismatched`)
+    kHookBinarySmallGrid,     // VG_BINARY_SMALL_GRID  vg_search_binary launches at most 2 workgroups / 2 slices: a few thousand rows give every wave several trips and the merge several lists
+    kHookBinaryNomAlways,     // VG_BINARY_NOM_ALWAYS  vg_search_binary's matrix-core path: no crossover of (query, row) pairs
+    kHookBinaryNoNom,         // VG_BINARY_NO_NOM      vg_search_binary: the scan only
     kHookCount
 };
 bool hook(Hook h);
@@ -573,6 +576,12 @@ struct vg_index {
     int64_t i4_nom_rescanned = 0;      // queries whose proof failed and the scan answered, since i4_nom was enabled
     const float *int4_table = nullptr;  // borrowed from the vg_int4
     const float *int4_min = nullptr, *int4_diff = nullptr;  // (same)
+    // BinaryQuantizer codes (vg_index_set_binary_codes, k_binary_search.hip): row-major n * ceil(dim/64) * 8 bytes, padded with
+    // zero rows to whole 64-row tiles; the threshold the queries are encoded with
+    uint8_t *d_bin_rows = nullptr;
+    int64_t bin_bytes = 0;  // the bytes d_bin_rows holds
+    int64_t bin_nominated = 0, bin_rescanned = 0;  // queries the matrix-core path answered / of those, the scan after all, since the codes were set
+    float bin_threshold = 0.0f;
     // IVF partitions of a flat segment: centroids [P*dim], first row of every partition [P+1]
     float *d_centroids = nullptr;
     uint32_t *d_part_off = nullptr;
@@ -591,6 +600,7 @@ inline const char *held_segment_state(const vg_index *idx)
            : idx->d_sq_tiles                     ? "SQ8 codes"
            : idx->d_int4_rows                    ? "INT4 codes"
            : (idx->d_rq_tiles || idx->d_rq_rows) ? "RaBitQ codes"
+           : idx->d_bin_rows                     ? "binary codes"
            : idx->d_centroids                    ? "IVF partitions"
            : idx->d_vamana                       ? "a Vamana graph"
            : idx->sq_nom.rows                    ? "an SQ8 nomination image"
@@ -603,6 +613,7 @@ inline const char *held_fresh_state(const vg_index *idx)
            : idx->d_sq_tiles                     ? "SQ8 codes"
            : idx->d_int4_rows                    ? "INT4 codes"
            : (idx->d_rq_tiles || idx->d_rq_rows) ? "RaBitQ codes"
+           : idx->d_bin_rows                     ? "binary codes"
            : idx->d_centroids                    ? "IVF partitions"
            : idx->d_hnsw_l0                      ? "an HNSW graph"
            : idx->d_hnsw_tomb                    ? "HNSW tombstones"

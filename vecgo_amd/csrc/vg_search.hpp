@@ -8,6 +8,7 @@
 
 #include <algorithm>
 #include <type_traits>
+#include <vector>
 
 #include "vg_internal.hpp"
 #include "vg_walk_chunk.hpp"
@@ -141,6 +142,23 @@ int32_t sq8_nan_replay(vg_index *idx, const float *d_queries, int64_t nq, int k,
 // ---- k_vamana_build.hip ---------------------------------------------------------------------------
 // vg_vamana_build's defaults (r, l, alpha of 0) and every refusal it makes before it allocates, with its status and message
 int32_t vamana_build_check(const vg_index *idx, int32_t &r, int32_t &l, float &alpha, int32_t max_batch, int32_t growth_div);
+
+// ---- k_binary.hip ---------------------------------------------------------------------------------
+// BinaryQuantizer.Encode of n rows (device buffers): bit i = v[i] >= threshold, ceil(dim / 64) * 8 bytes a row
+int32_t launch_binary_encode(const float *d_vectors, int64_t n, int dim, float threshold, uint8_t *d_codes, hipStream_t st);
+
+// ---- k_binary_search.hip, k_binary_nominate.hip ----------------------------------------------------
+// vg_search_binary's scan of nq device queries (encode, scan, pages, merge): ids / scores [nq * k]
+int32_t binary_scan_batch(vg_index *idx, const float *q, int64_t nq, int k, const uint8_t *mask, int64_t mask_stride, uint32_t *oid,
+                          float *osc, hipStream_t st);
+// the matrix path's threshold sample: every 64th tile scored by the scan kernel, the sel_k best ids / scores per query
+int binary_sample_slices(const vg_index *idx, int64_t cnt);
+int32_t launch_binary_sample(const vg_index *idx, const uint64_t *qcodes, int64_t cnt, int sel_k, int slices, uint64_t *partial, uint32_t *ids,
+                             float *thr, hipStream_t st);
+// whether a batch takes the matrix path; the path: every query's k results, `failed` the queries whose proof failed
+bool binary_nomination_applies(const vg_index *idx, int64_t nq, int k, const uint8_t *mask);
+int32_t binary_nominated_pass(vg_index *idx, const float *q, int64_t nq, int k, uint32_t *oid, float *osc, hipStream_t st,
+                              std::vector<int> &failed);
 
 // ---- k_rabitq.hip ---------------------------------------------------------------------------------
 // sign bits + norm of each vector (RaBitQ Encode)
