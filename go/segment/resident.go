@@ -749,7 +749,18 @@ func (r *Resident) EnableInt4NominationSmallBatches() error {
 	return hipctx.Err(int32(C.vg_index_enable_int4_nomination(r.h, C.int32_t(2), nil)))
 }
 
-// Int4NominationInfo: mode 1 while the nomination is enabled (2: with small batches), the device bytes it keeps resident, and the queries whose proof
+// EnableInt4NominationFiltered: the nomination with batches under a row filter (one per query, or one for the batch) taken too —
+// mode 5, or 6 with smallBatches (on | 4) — within what the mode allows and from the filtered crossovers up; a selective batch
+// filter lets the one-query-tile GEMM skip the 64-row tiles it empties.  Nothing more is resident; results unchanged.
+func (r *Resident) EnableInt4NominationFiltered(smallBatches bool) error {
+	v := C.int32_t(5)
+	if smallBatches {
+		v = 6
+	}
+	return hipctx.Err(int32(C.vg_index_enable_int4_nomination(r.h, v, nil)))
+}
+
+// Int4NominationInfo: mode 1 while the nomination is enabled (2: with small batches; 5, 6: with filtered batches), the device bytes it keeps resident, and the queries whose proof
 // failed and the scan answered since the mode was enabled.
 func (r *Resident) Int4NominationInfo() (mode int, heldBytes, rescanned int64, err error) {
 	var m C.int32_t

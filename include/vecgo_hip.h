@@ -1736,9 +1736,17 @@ int32_t vg_index_rabitq_nomination_info(const vg_index *idx, int32_t *on, int64_
  * the same conditions and dim <= 2496, from their own crossover up — on a GEMM of one query tile whose waves read the codes from
  * global memory straight into the matrix instruction's registers, the queries' image resident in LDS (97 .. 128 queries from
  * dim 608 on run as two launches of two 32-query blocks).  Nothing more is resident.  Still the scan's: filtered batches, fewer
- * than 5 queries, dim % 32 != 0, k > 256.  Found by symbol lookup. */
+ * than 5 queries, dim % 32 != 0, k > 256.
+ * `on` is read as bits: on & 3 is the mode above (1 or 2), on & 4 adds FILTERED batches — on == 5 and on == 6: a batch under a row
+ * filter, one per query or one for the batch (mask_stride 0), takes the nomination too, within what on & 3 allows, under the same
+ * conditions, from the filtered crossovers up (README, Limits).  The threshold sample reads the filter's bits of the sampled rows, the
+ * GEMMs append kept rows only (the one-query-tile GEMM skips every 64-row tile that a batch filter empties).  A filter that leaves
+ * the sample too few rows for a threshold gets every kept row listed: that complete list is accepted as it is up to 64 rows at
+ * k <= 48 and up to 4096 rows at k > 48, a longer one at k <= 48 is proven against its 64th best score, and one that overflows
+ * 4096 is rescanned under the query's own filter and counted, and a filter that keeps fewer than k rows yields the scan's padded answer.  Nothing more is
+ * resident.  on == 4 (a flag without a mode) and on > 6: VG_ERR_INVALID_ARG, the state as it was.  Found by symbol lookup. */
 int32_t vg_index_enable_int4_nomination(vg_index *idx, int32_t on, void *stream);
-/* *mode = 1 while the mode is enabled, 2 when it was enabled with on == 2, else 0; *held_bytes = the device memory it keeps resident; *rescanned = the queries, since the
+/* *mode = 1 while the mode is enabled, 2 when it was enabled with on == 2, 5 or 6 with on == 5 or 6, else 0; *held_bytes = the device memory it keeps resident; *rescanned = the queries, since the
  * mode was enabled, whose proof failed and which the scan answered (0 when off).  Any pointer may be NULL.  Found by symbol lookup. */
 int32_t vg_index_int4_nomination_info(const vg_index *idx, int32_t *mode, int64_t *held_bytes, int64_t *rescanned);
 

@@ -715,9 +715,10 @@ public:
     Result SearchInt4(const float *queries, int64_t nq, int k, const uint8_t *mask = nullptr, int64_t mask_stride = 0) { return run(nq, k, [&](Result &r) { return vg_search_int4(h_, queries, nq, k, mask, mask_stride, r.ids.data(), r.scores.data(), nullptr); }); }
     // SearchInt4 batches above 128 queries (unfiltered, k <= 256, dim % 32 == 0) through a bfloat16 matrix-core nomination whose row
     // tiles are converted from the nibble codes (exact re-score and proof; 4 bytes a row resident); other batches keep the scan;
-    // results unchanged.  small_batches (mode 2): unfiltered batches of 5 .. 128 queries (dim <= 2496) take it too
-    void EnableInt4Nomination(bool on = true, bool small_batches = false) { check(vg_index_enable_int4_nomination(h_, on ? (small_batches ? 2 : 1) : 0, nullptr)); }
-    // mode: 1 while enabled, 2 with small_batches; held_bytes: the device memory the mode keeps resident; rescanned: queries whose proof failed and the
+    // results unchanged.  small_batches (mode 2): unfiltered batches of 5 .. 128 queries (dim <= 2496) take it too; filtered (on | 4,
+    // modes 5 and 6): batches under a row filter, per query or for the batch, take it too within what the mode allows
+    void EnableInt4Nomination(bool on = true, bool small_batches = false, bool filtered = false) { check(vg_index_enable_int4_nomination(h_, on ? ((small_batches ? 2 : 1) | (filtered ? 4 : 0)) : 0, nullptr)); }
+    // mode: 1 while enabled, 2 with small_batches, 5 / 6 with filtered; held_bytes: the device memory the mode keeps resident; rescanned: queries whose proof failed and the
     // scan answered, since the mode was enabled
     struct Int4Nomination {
         int32_t mode;

@@ -1080,17 +1080,20 @@ class Index:
         check(self._lib.vg_index_rabitq_nomination_info(self._h, C.byref(on), C.byref(held), C.byref(rescanned), C.byref(mismatched)))
         return on.value, held.value, rescanned.value, mismatched.value
 
-    def enable_int4_nomination(self, on: bool = True, small_batches: bool = False, stream=None):
+    def enable_int4_nomination(self, on: bool = True, small_batches: bool = False, filtered: bool = False, stream=None):
         """vg_index_enable_int4_nomination: unfiltered batches of search_int4 above 128 queries (k <= 256, dim % 32 == 0, queries x rows
         above the measured crossover) are nominated by a bfloat16 MFMA GEMM whose row tiles are converted from the nibble codes,
         bf16(c - 8), exact, against the queries scaled by diff / 15; re-scored with Int4Quantizer.L2Distance and proven; the others
         keep the scan.  small_batches (mode 2): unfiltered batches of 5 .. 128 queries take it too (dim <= 2496), on a tile that reads
-        the codes straight into the matrix unit's registers.  Resident: 4 bytes a row and 8 a dimension.  ids and scores stay
+        the codes straight into the matrix unit's registers.  filtered (on | 4: modes 5 and 6): batches under a row filter — one
+        per query or one for the batch — take it too, within what the mode allows and from the filtered crossovers up; a batch filter
+        lets the small tile skip the 64-row tiles it empties.  Resident: 4 bytes a row and 8 a dimension.  ids and scores stay
         bit-identical."""
-        check(self._lib.vg_index_enable_int4_nomination(self._h, C.c_int32((2 if small_batches else 1) if on else 0), _stream_ptr(stream)))
+        mode = ((2 if small_batches else 1) | (4 if filtered else 0)) if on else 0
+        check(self._lib.vg_index_enable_int4_nomination(self._h, C.c_int32(mode), _stream_ptr(stream)))
 
     def int4_nomination_info(self):
-        """vg_index_int4_nomination_info: (mode, held_bytes, rescanned) — mode 1 while enabled, 2 with small_batches; held_bytes the device memory the mode
+        """vg_index_int4_nomination_info: (mode, held_bytes, rescanned) — mode 1 while enabled, 2 with small_batches, 5 / 6 with filtered; held_bytes the device memory the mode
         keeps resident; rescanned the queries whose proof failed and the scan answered since it was enabled."""
         mode, held, rescanned = C.c_int32(0), C.c_int64(0), C.c_int64(0)
         check(self._lib.vg_index_int4_nomination_info(self._h, C.byref(mode), C.byref(held), C.byref(rescanned)))

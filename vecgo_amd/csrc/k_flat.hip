@@ -286,7 +286,7 @@ static int32_t launch_gemm_t(const GemmArgs &a)
                 if (a.counts_wide) VG_HIP(hipMemsetAsync(a.counts_wide, 0, sizeof(int) * static_cast<size_t>(c.cnt) * kCountLine, st));
                 VG_TRY(launch_int4_small_gemm(reinterpret_cast<const uint16_t *>(a.queries), c.cnt, 2 * c.ops.dim_words, a.codes, c.ops.n, a.code_m,
                                               c.ops.norms, a.thr, a.thr_stride, a.thr_off, a.counts_wide ? a.counts_wide : a.counts,
-                                              a.counts_wide ? kCountLine : 1, a.cand, a.cap, a.cus, st));
+                                              a.counts_wide ? kCountLine : 1, a.cand, a.cap, a.cus, st, c.mask, c.mask_stride));
                 if (a.counts_wide)
                     VG_LAUNCH(counts_narrow_kernel, dim3(static_cast<unsigned>((c.cnt + 255) / 256)), dim3(256), 0, st, a.counts_wide, c.cnt, a.counts);
                 return VG_OK;
@@ -586,20 +586,39 @@ __global__ void fill_f32_kernel(float *p, int64_t n, float v)
 // starts its accumulators at (t - |x|^2) / 2 and reads a row's score back as t - 2 acc: with t = 1e30 standing in for +Inf the dot
 // product is absorbed, every appended score comes back as ~0, and the 64 "best" of them were an arbitrary 64 (r06: Dot segments of
 // up to 4096 rows, batches above 128 queries, answered wrongly — tests/test_gpu_nonfinite.py found it).  One wave per query.
+__device__ __forceinline__ float thr_cap_bound(const float *__restrict__ queries, int64_t q, int dim, const float *__restrict__ norm_max, int lane)
+{
+    float qn = 0.0f;
+    for (int j = lane; j < dim; j += 64) qn = __builtin_fmaf(queries[q * dim + j], queries[q * dim + j], qn);
+    for (int off = 32; off > 0; off >>= 1) qn += __shfl_xor(qn, off);
+    return 2.002f * (qn + norm_max[0]);
+}
 __global__ __launch_bounds__(64) void flat_thr_cap_kernel(float *__restrict__ thr, int sel_k, const float *__restrict__ queries, int dim,
                                                           const float *__restrict__ norm_max)
 {
     const int64_t q = blockIdx.x;
     const int lane = threadIdx.x;
-    float qn = 0.0f;
-    for (int j = lane; j < dim; j += 64) qn = __builtin_fmaf(queries[q * dim + j], queries[q * dim + j], qn);
-    for (int off = 32; off > 0; off >>= 1) qn += __shfl_xor(qn, off);
-    const float bound = 2.002f * (qn + norm_max[0]);
+    const float bound = thr_cap_bound(queries, q, dim, norm_max, lane);
     if (!(bound < 1e30f)) return;  // not finite: the tile's own clamp stands in, and every proof fails on its (infinite) margin
     for (int i = lane; i < sel_k; i += 64) {
         const float t = thr[q * sel_k + i];
         if (!(t < bound)) thr[q * sel_k + i] = bound;  // (NaN too)
     }
+}
+// The same cap for the GEMM ALONE: the query's append threshold thr[q][sel_k - 1], capped, into gemm_thr[q]; thr itself stays as
+// the sample left it.  In place, the cap hides "no threshold" from the verify pair (vg_nominate.hpp): a query whose filter leaves the
+// sample fewer than sel_k rows has every kept row appended — a COMPLETE list, which the pair accepts as it is (tq == +Inf) — but
+// after the cap it looked like a threshold to prove against, and a list of fewer than k rows, or one whose k-th score lies within
+// the margin of the (huge) bound, failed the proof and went to the scan: every query of a selective filter.  The filtered INT4
+// nomination (flat_nominate_bf16 with a mask) takes this one; unfiltered calls take the kernel above, as they did.
+__global__ __launch_bounds__(64) void flat_thr_cap_gemm_kernel(const float *__restrict__ thr, int sel_k, const float *__restrict__ queries, int dim,
+                                                               const float *__restrict__ norm_max, float *__restrict__ gemm_thr)
+{
+    const int64_t q = blockIdx.x;
+    const int lane = threadIdx.x;
+    const float bound = thr_cap_bound(queries, q, dim, norm_max, lane);
+    const float t = thr[q * sel_k + sel_k - 1];
+    if (lane == 0) gemm_thr[q] = bound < 1e30f && !(t < bound) ? bound : t;  // (a bound that is not finite: t as it is, see above)
 }
 
 // ---- 2. per-query streaming select of the kc smallest scores -------------------------------
@@ -1600,7 +1619,7 @@ __global__ void sq8_sample_rows_kernel(const uint4 *__restrict__ tiles, int grou
     out[(c * groups_pad + g) * 2 + 1] = make_uint4(w[4], w[5], w[6], w[7]);
     if (g == 0) norms_c[c] = norms[row];
 }
-// The INT4 nomination (img.int4: vg_index_enable_int4_nomination, k_int4_nominate.hip; L2, unfiltered) likewise: the queries' image is
+// The INT4 nomination (img.int4: vg_index_enable_int4_nomination, k_int4_nominate.hip; L2; filtered too: sample_mask_gather_kernel) likewise: the queries' image is
 // bf16(q_d diff_d / 15), the append GEMM converts its row tiles from the row-major nibble codes (flat_gemm_int4_big_kernel), and the
 // sampled tiles are converted here with the same function — bf16(c - 8), exact — so that sample and append score in one space.
 // thread per (compact row, 32-dimension block of dim_pad / 32): 16 code bytes -> four granules; blocks past the row are zeros
@@ -1619,6 +1638,19 @@ __global__ void int4_sample_rows_kernel(const uint8_t *__restrict__ codes, int r
     for (int k = 0; k < 4; k++) out[(c * blocks_pad + b) * 4 + k] = in ? int4_word_bf16(w[k] ^ 0x88888888u) : make_uint4(0u, 0u, 0u, 0u);
     if (b == 0) norms_c[c] = norms[row];
 }
+// A row filter over the compact rows of a from-codes sample: the sample kernels index a filter by THEIR row number, and compact row
+// c is row (c / 128) stride 128 + c % 128 (the kernels above).  Eight compact rows from a multiple of 8 are eight consecutive rows
+// from a multiple of 8, so a compact filter's byte b is the filter's byte (b / 16) stride 16 + b % 16: a byte gather, of any of the
+// three from-codes modes' sample.  thread per (filter, byte): `masks` filters at mask_stride bytes in, cbytes = (rows_c + 7) / 8 out
+// (the last byte's bits past rows_c are the source's — the kernels test the row number first).
+__global__ void sample_mask_gather_kernel(const uint8_t *__restrict__ mask, int64_t mask_stride, int64_t masks, int64_t cbytes, int stride,
+                                          uint8_t *__restrict__ out)
+{
+    const int64_t t = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (t >= masks * cbytes) return;
+    const int64_t m = t / cbytes, b = t - m * cbytes;
+    out[t] = mask[m * mask_stride + (b / (kGemmBN / 8)) * stride * (kGemmBN / 8) + b % (kGemmBN / 8)];
+}
 // the rows of every stride-th 128-row tile of n rows that exist (only the last tile of all can be short)
 static int64_t sample_rows(int64_t n, int stride)
 {
@@ -1632,7 +1664,12 @@ struct NominateScratch : NomScratch {
     int64_t rows_c;   // from the codes: the sampled tiles' rows (0: an image, or too few rows for a sample) ...
     uint16_t *srows;  // ... decoded, dim_pad each ...
     float *snorms;    // ... and their norms
-    NominateScratch(char *base, int64_t cnt, int64_t n, const NomImage &img, int k)
+    // `masks` row filters (0 none, 1 the batch's, cnt one per query) on the INT4 nomination: the filters over the compact rows
+    // (sample_mask_gather_kernel; cbytes each, 0 without a sample) and the GEMM's own capped thresholds (flat_thr_cap_gemm_kernel)
+    uint8_t *cmask;
+    int64_t cbytes;
+    float *gthr;
+    NominateScratch(char *base, int64_t cnt, int64_t n, const NomImage &img, int k, int64_t masks)
     {
         Carve c{base};
         carve(c, cnt, sample_cols(n, kFlatSampleStride), nominate_sel_k(k), kFlatCap);
@@ -1641,15 +1678,25 @@ struct NominateScratch : NomScratch {
         rows_c = img.from_codes && n > kFlatCap ? sample_rows(n, kFlatSampleStride) : 0;
         c.take(srows, rows_c * img.dim_pad);
         c.take(snorms, rows_c);
+        // (Carve::take hands out a pointer for a count of zero too: what another call has not got is null)
+        cbytes = masks && img.int4 ? (rows_c + 7) / 8 : 0;
+        cmask = nullptr, gthr = nullptr;
+        if (cbytes) c.take(cmask, masks * cbytes);
+        if (masks && img.int4) c.take(gthr, cnt);
         bytes = c.off;
     }
 };
-size_t flat_nominate_bf16_scratch(int64_t cnt, int64_t n, const NomImage &img, int k) { return NominateScratch(nullptr, cnt, n, img, k).bytes; }
+size_t flat_nominate_bf16_scratch(int64_t cnt, int64_t n, const NomImage &img, int k, int64_t masks)
+{
+    return NominateScratch(nullptr, cnt, n, img, k, masks).bytes;
+}
 
 int32_t flat_nominate_bf16(vg_index *idx, const NomImage &img, bool dot, const float *queries, int64_t cnt, const uint8_t *mask,
                            int64_t mask_stride, int k, char *scratch, hipStream_t st, ProbeNominated *nom)
 {
-    const NominateScratch s(scratch, cnt, idx->n, img, k);
+    const int64_t masks = !mask ? 0 : mask_stride ? cnt : 1;
+    const NominateScratch s(scratch, cnt, idx->n, img, k, masks);
+    VG_CHECK(!mask || !img.from_codes || img.int4, VG_ERR_INVALID_ARG, "flat_nominate_bf16: a filter on a from-codes mode without one");
     NomCall nc{st, dot, {}, cnt, mask, mask_stride};
     // (from the codes the GEMM's "rows" are the codebook; n, the row length and the norms are the decoded rows')
     VG_TRY(gemm_operands(queries, cnt, idx->dim, idx->n, img.norms, img.rows, img.dim_pad, s.qbf, st, &nc.ops, img.scale));
@@ -1660,6 +1707,11 @@ int32_t flat_nominate_bf16(vg_index *idx, const NomImage &img, bool dot, const f
         VG_LAUNCH(int4_sample_rows_kernel, dim3(static_cast<unsigned>((s.rows_c * blocks_pad + 255) / 256)), dim3(256), 0, st, idx->d_int4_rows,
                   idx->dim / 2, blocks_pad, img.norms, s.rows_c, kFlatSampleStride, reinterpret_cast<uint4 *>(s.srows), s.snorms);
         sc.ops.b = reinterpret_cast<const float *>(s.srows), sc.ops.n = s.rows_c, sc.ops.norms = s.snorms;
+        if (mask) {  // the sample sees compact rows: so must its filter (the append below sees real rows and keeps the caller's)
+            VG_LAUNCH(sample_mask_gather_kernel, dim3(static_cast<unsigned>((masks * s.cbytes + 255) / 256)), dim3(256), 0, st, mask, mask_stride, masks,
+                      s.cbytes, kFlatSampleStride, s.cmask);
+            sc.mask = s.cmask, sc.mask_stride = mask_stride ? s.cbytes : 0;
+        }
     } else if (s.rows_c && img.scale) {
         const int groups_pad = img.dim_pad / 16;
         VG_LAUNCH(sq8_sample_rows_kernel, dim3(static_cast<unsigned>((s.rows_c * groups_pad + 255) / 256)), dim3(256), 0, st,
@@ -1674,7 +1726,10 @@ int32_t flat_nominate_bf16(vg_index *idx, const NomImage &img, bool dot, const f
         sc.ops.b = reinterpret_cast<const float *>(s.srows), sc.ops.n = s.rows_c, sc.ops.norms = s.snorms;
     }
     VG_TRY(sample_thresholds(sc, s, s.rows_c ? 1 : kFlatSampleStride, nom->sel_k, nom->thr, idx->n > kFlatCap));
-    VG_LAUNCH(flat_thr_cap_kernel, dim3(nc.ucnt()), dim3(64), 0, st, nom->thr, nom->sel_k, queries, idx->dim, img.norm_max);
+    if (s.gthr)  // (the filtered INT4 nomination: nom->thr keeps its +Inf for the verify pair)
+        VG_LAUNCH(flat_thr_cap_gemm_kernel, dim3(nc.ucnt()), dim3(64), 0, st, nom->thr, nom->sel_k, queries, idx->dim, img.norm_max, s.gthr);
+    else
+        VG_LAUNCH(flat_thr_cap_kernel, dim3(nc.ucnt()), dim3(64), 0, st, nom->thr, nom->sel_k, queries, idx->dim, img.norm_max);
     VG_HIP(hipMemsetAsync(nom->counts, 0, sizeof(int) * static_cast<size_t>(cnt), st));
     {
         const bool i4_small = img.int4 && cnt <= kGemmBM && int4_small_tile_fits(idx->dim);  // (launch_gemm's choice: the small INT4 tile)
@@ -1683,6 +1738,7 @@ int32_t flat_nominate_bf16(vg_index *idx, const NomImage &img, bool dot, const f
                               pq_small_tile_takes(idx->pq->m, idx->n);  // (likewise: the small PQ tile)
         ProfScope prof(idx->ctx, i4_small ? "int4_codes_gemm_small" : img.int4 ? "int4_codes_gemm" : s8_small ? "sq8_codes_gemm_small" : img.scale ? "sq8_codes_gemm" : pq_small ? "pq_codes_gemm_small" : img.from_codes ? "pq_codes_gemm" : "sq8_nominate_gemm", st);
         GemmArgs a = GemmArgs::append(nc, nom->thr, nom->sel_k, nom->counts, nom->cand, nom->cap).wide(s.counts_wide, idx->ctx->compute_units);
+        if (s.gthr) a.thr = s.gthr, a.thr_stride = 1, a.thr_off = 0;
         if (img.int4)
             a.from_int4_codes(idx->d_int4_rows, idx->dim / 2);
         else if (img.scale)

@@ -34,6 +34,19 @@ constexpr int64_t kInt4NomMinPairs = 12900000;
 // nomination won at every shape, by 14 % at the smallest: the constant is the smallest measured product, 8 x 100k, and nothing below
 // it was measured.  Test hook VG_INT4_NOM_ALWAYS: any.
 constexpr int64_t kInt4NomSmallMinPairs = 800000;
+// The same for FILTERED batches (on & 4): a filter makes the scan cheaper (a selective one by the tiles it drops), the nomination
+// hardly, so these stand apart from the two above.  Measured (MI355X, tools/int4_nominate_time.py 1000000 filtered, dim 768, k = 10,
+// ms per call, filtered scan / filtered nomination, alternating windows of ~100 ms in one run on one index, the windows of a leg
+// within 1 % of each other; profiles/int4_nominate_time_filtered.txt), a batch filter keeping 100 % / 10 % / 1 % of the rows, then one
+// per query keeping 10 %.  Above 128 queries: 129 x 100k, 10 %: 1.141 / 0.314; 1024 x 1M: 55.31 / 1.687, 55.18 / 2.076, 28.35 / 3.054,
+// 56.03 / 2.547 (k = 100, 10 %: 111.5 / 2.921).  The nomination won everywhere: the smallest measured product, 129 x 100k.
+// 5 .. 128 queries, 100k rows: 8 queries 0.198 / 0.179, 0.163 / 0.176, 0.140 / 0.173, 0.161 / 0.178 — the scan wins under every
+// selective filter —; 32: 0.383 / 0.182, 0.306 / 0.182, 0.256 / 0.183, 0.304 / 0.190; 128: 0.954 / 0.269, 0.874 / 0.288, 0.597 / 0.308,
+// 0.883 / 0.327.  1M rows: 8: 0.662 / 0.283, 0.584 / 0.280, 0.495 / 0.256, 0.587 / 0.287; 32: 2.022 / 0.290, 1.942 / 0.288, 1.357 / 0.264,
+// 1.965 / 0.306; 128: 7.164 / 0.578, 7.090 / 0.583, 4.040 / 0.513, 7.199 / 0.794.  From 32 x 100k up the nomination won under every
+// filter kind: that product is the constant, and 8 x 100k keeps the scan.  No query was rescanned in any line.
+constexpr int64_t kInt4NomMaskedMinPairs = 12900000;
+constexpr int64_t kInt4NomMaskedSmallMinPairs = 3200000;
 
 // one workgroup of 64 lanes: mid, the scale and H2
 __global__ void int4_mid_kernel(const float *__restrict__ mins, const float *__restrict__ diff, int dim, int dim_pad, float *__restrict__ mid)
@@ -136,6 +149,8 @@ struct Int4Row {
     //  2^-8 + 2 u + (4.03 (dim + 16) + dim + dim / 32 + 16 + 16 + dim / 64 + 7 + dim / 8 + 46) u  <=  2^-8 1.001 + (6 dim + 160) u,
     //  + 6 u (|q|^2 + H2).  At dim 768: 4.19e-3 B.  Denormal products the matrix unit may flush: below 1e-35 dim, inside the absolute
     // term.  tests/test_int4_nomination_bound_cpu.py models the sums.
+    // A row filter (on & 4) changes none of it: the bound is per (query, row), and a filter only takes rows away — from the list
+    // and from the rows outside it alike — so the same margin separates the kept rows' k-th score from the kept rows outside.
     __device__ float eps(float qn, float norm_max) const
     {
         const float d = static_cast<float>(dim), u = 5.9604645e-8f;
@@ -147,26 +162,28 @@ struct Int4Row {
 // the whole segment, unfiltered, rows of whole 16-byte halves of a K step (dim % 32 == 0), from kInt4NomMinPairs pairs up.
 // Enabled with on = 2 (NomImage::int4_small) it also takes 5 .. 128 queries, on the tile of one query tile
 // (flat_gemm_int4_small_kernel, vg_int4_small_gemm.hpp) from kInt4NomSmallMinPairs pairs up, where a block of 32 queries' image of
-// a row fits that tile's LDS (int4_small_tile_fits: dim <= 2496).
-// (device queries; mask: the batch's row filter, or null)
+// a row fits that tile's LDS (int4_small_tile_fits: dim <= 2496).  Enabled with on & 4 (NomImage::int4_masked) a batch under a row
+// filter — one per query, or one for the batch — takes it too, within what on & 3 allows and from the filtered constants up.
+// (device queries; mask: the batch's row filter, per query or one for all, or null)
 bool int4_nomination_applies(const vg_index *idx, const float *d_queries, int64_t nq, int k, const uint8_t *mask)
 {
-    if (!idx->i4_nom.rows || mask || idx->dim % 32 != 0) return false;
+    if (!idx->i4_nom.rows || (mask && !idx->i4_nom.int4_masked) || idx->dim % 32 != 0) return false;
     if (nq <= 128) {
         if (!idx->i4_nom.int4_small || nq < 5 || !int4_small_tile_fits(idx->dim)) return false;
-        if (nq * idx->n < kInt4NomSmallMinPairs && !hook(kHookInt4NomAlways)) return false;
-    } else if (nq * idx->n < kInt4NomMinPairs && !hook(kHookInt4NomAlways)) {
+        if (nq * idx->n < (mask ? kInt4NomMaskedSmallMinPairs : kInt4NomSmallMinPairs) && !hook(kHookInt4NomAlways)) return false;
+    } else if (nq * idx->n < (mask ? kInt4NomMaskedMinPairs : kInt4NomMinPairs) && !hook(kHookInt4NomAlways)) {
         return false;
     }
     return k <= kNomMaxK && idx->n > k && aligned16(d_queries);
 }
 // nominated_pass with the INT4 re-score
-int32_t int4_nominated_pass(vg_index *idx, const float *q, int64_t nq, int k, uint32_t *oid, float *osc, hipStream_t st, std::vector<int> &failed)
+int32_t int4_nominated_pass(vg_index *idx, const float *q, int64_t nq, int k, const uint8_t *mask, int64_t mask_stride, uint32_t *oid, float *osc,
+                            hipStream_t st, std::vector<int> &failed)
 {
     const NomImage &img = idx->i4_nom;
     const size_t before = failed.size();
     const Int4Row row{idx->d_int4_rows, idx->int4_table, idx->dim, reinterpret_cast<const float *>(img.rows), img.dim_pad};
-    VG_TRY(nominated_pass(idx, img, false, q, nq, k, nullptr, 0, 0, oid, osc, st, failed,
+    VG_TRY(nominated_pass(idx, img, false, q, nq, k, mask, mask_stride, 0, oid, osc, st, failed,
                           [&](const float *qq, int64_t cnt, const ProbeNominated &nom, float *, uint32_t *ids, float *scores, int *fail) -> int32_t {
                               return launch_nominated_verify<false>(row, qq, img.norm_max, cnt, nom, k, ids, scores, fail, st);
                           }));
@@ -178,6 +195,8 @@ int32_t int4_nominated_pass(vg_index *idx, const float *q, int64_t nq, int k, ui
 VG_API int32_t vg_index_enable_int4_nomination(vg_index *idx, int32_t on, void *stream)
 {
     VG_CHECK(idx, VG_ERR_INVALID_ARG, "vg_index_enable_int4_nomination: NULL index");
+    // on & 3: the mode (1, or 2 with the small batches); on & 4: filtered batches too — of a mode, so 4 alone is none
+    VG_CHECK(on != 4 && on <= 6, VG_ERR_INVALID_ARG, "vg_index_enable_int4_nomination: on=%d is a flag without a mode, or above 6", on);
     VG_HIP(hipSetDevice(idx->ctx->device));
     hipStream_t st = vg::pick_stream(idx->ctx, stream);
     VG_TRY(vg::nom_free(idx->i4_nom, st));
@@ -192,7 +211,8 @@ VG_API int32_t vg_index_enable_int4_nomination(vg_index *idx, int32_t on, void *
                            idx->int4_min, idx->int4_diff, b.norms, norm_max_bits);
     }));
     idx->i4_nom.int4 = true;
-    idx->i4_nom.int4_small = on == 2;
+    idx->i4_nom.int4_small = on > 0 && (on & 3) == 2;
+    idx->i4_nom.int4_masked = on > 0 && (on & 4) != 0;
     idx->i4_nom.scale = reinterpret_cast<const float *>(idx->i4_nom.rows) + dim_pad;
     return VG_OK;
 }
@@ -200,7 +220,7 @@ VG_API int32_t vg_index_enable_int4_nomination(vg_index *idx, int32_t on, void *
 VG_API int32_t vg_index_int4_nomination_info(const vg_index *idx, int32_t *mode, int64_t *held_bytes, int64_t *rescanned)
 {
     VG_CHECK(idx, VG_ERR_INVALID_ARG, "vg_index_int4_nomination_info: NULL index");
-    if (mode) *mode = !idx->i4_nom.rows ? 0 : idx->i4_nom.int4_small ? 2 : 1;
+    if (mode) *mode = !idx->i4_nom.rows ? 0 : (idx->i4_nom.int4_small ? 2 : 1) | (idx->i4_nom.int4_masked ? 4 : 0);
     if (held_bytes) *held_bytes = idx->i4_nom.held_bytes(idx->n);
     if (rescanned) *rescanned = idx->i4_nom.rows ? idx->i4_nom_rescanned : 0;
     return VG_OK;

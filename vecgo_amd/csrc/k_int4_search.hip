@@ -426,12 +426,13 @@ VG_API int32_t vg_search_int4(vg_index *idx, const float *queries, int64_t nq, i
         const int64_t stride = nq > 1 ? mask_stride : 0;
         if (vg::int4_nomination_applies(idx, io.q.ptr, nq, k, io.mk.ptr)) {
             // vg_index_enable_int4_nomination (k_int4_nominate.hip): the matrix-core nomination, the exact re-score and the proof; the
-            // scan for the queries whose proof failed (ties at the k-th score, thresholds too tight)
+            // scan for the queries whose proof failed (ties at the k-th score, thresholds too tight, lists that overflowed) — under
+            // the batch's filter, or each under its own
             std::vector<int> failed;
-            VG_TRY(vg::int4_nominated_pass(idx, io.q.ptr, nq, k, io.oid.ptr, io.osc.ptr, st, failed));
-            VG_TRY(vg::rescan_failed(failed, io.q.ptr, idx->dim, k, nullptr, 0, 0, io.oid.ptr, io.osc.ptr, st,
-                                     [&](const float *fq, int64_t nf, const uint8_t *, int64_t, uint32_t *fid, float *fsc) {
-                                         return vg::int4_scan_batch(idx, fq, nf, k, nullptr, 0, fid, fsc, st);
+            VG_TRY(vg::int4_nominated_pass(idx, io.q.ptr, nq, k, io.mk.ptr, stride, io.oid.ptr, io.osc.ptr, st, failed));
+            VG_TRY(vg::rescan_failed(failed, io.q.ptr, idx->dim, k, io.mk.ptr, stride, (idx->n + 7) / 8, io.oid.ptr, io.osc.ptr, st,
+                                     [&](const float *fq, int64_t nf, const uint8_t *fm, int64_t fstride, uint32_t *fid, float *fsc) {
+                                         return vg::int4_scan_batch(idx, fq, nf, k, fm, fstride, fid, fsc, st);
                                      }));
         } else {
             VG_TRY(vg::int4_scan_batch(idx, io.q.ptr, nq, k, io.mk.ptr, stride, io.oid.ptr, io.osc.ptr, st));

@@ -11,28 +11,30 @@ namespace vg {
 // Whether one block of 32 queries' image of a dim-dimensional row fits in LDS: the small tile's only limit on dim (dim <= 2496)
 bool int4_small_tile_fits(int dim) { return dim > 0 && dim % 32 == 0 && int4_small_lds_bytes(1, dim / 2) <= kI4sLdsMax; }
 
-template <int RB>
+// (MASKED, BATCH: a row filter per query / one for the batch — the kernel's variants of their own)
+template <int RB, bool MASKED, bool BATCH>
 static int32_t launch_rb(dim3 threads, size_t lds, int cus, int64_t ntiles, hipStream_t st, const uint16_t *q, int nq, int dim_pad, const uint8_t *codes,
                          int64_t n, int row_bytes, const float *norms, const float *thr, int thr_stride, int thr_off, int *counts, int count_stride,
-                         uint64_t *cand, int cap)
+                         uint64_t *cand, int cap, const uint8_t *mask, int64_t mask_stride)
 {
-    auto kern = flat_gemm_int4_small_kernel<RB>;
+    auto kern = flat_gemm_int4_small_kernel<RB, MASKED, BATCH>;
     VG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
     // persistent: as many workgroups as the device holds at once (LDS and registers decide how many a CU takes), a tile each at most
     int per_cu = 1;
     VG_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, kI4sThreads, lds));
     const int64_t grid = std::min<int64_t>(ntiles, static_cast<int64_t>(std::max(cus, 1)) * std::max(per_cu, 1));
     VG_LAUNCH(kern, dim3(static_cast<unsigned>(grid)), threads, lds, st, q, nq, dim_pad, codes, n, row_bytes, norms, thr, thr_stride, thr_off, counts,
-              count_stride, cand, cap);
+              count_stride, cand, cap, mask, mask_stride);
     return VG_OK;
 }
 
 // cnt <= 128 queries (qimg: cnt x dim_pad bfloat16) against n > 0 rows of row_bytes code bytes.  The image of the blocks of a launch
 // is resident in LDS: where all of the batch's blocks do not fit, the batch runs as the fewest launches of equally many blocks
-// that do (a pass over the codes each) — decided here, once, from the shapes.
+// that do (a pass over the codes each) — decided here, once, from the shapes.  mask: a device row filter per query (at mask_stride
+// bytes; a launch of the split gets its own queries') or for the batch (mask_stride 0), or null.
 int32_t launch_int4_small_gemm(const uint16_t *qimg, int64_t cnt, int dim_pad, const uint8_t *codes, int64_t n, int row_bytes, const float *norms,
                                const float *thr, int thr_stride, int thr_off, int *counts, int count_stride, uint64_t *cand, int cap, int cus,
-                               hipStream_t st)
+                               hipStream_t st, const uint8_t *mask, int64_t mask_stride)
 {
     VG_CHECK(cnt > 0 && cnt <= 128 && n > 0 && row_bytes > 0 && row_bytes % 16 == 0 && dim_pad >= 2 * row_bytes && aligned16(qimg, codes) &&
                  int4_small_tile_fits(2 * row_bytes),
@@ -46,9 +48,14 @@ int32_t launch_int4_small_gemm(const uint16_t *qimg, int64_t cnt, int dim_pad, c
         const int qc = static_cast<int>(std::min<int64_t>(per * 32, cnt - q0)), b = (qc + 31) / 32;
         const size_t lds = int4_small_lds_bytes(b, row_bytes);
         auto go = [&](auto kern_rb) {
-            return launch_rb<decltype(kern_rb)::value>(dim3(kI4sThreads), lds, cus, ntiles, st, qimg + q0 * dim_pad, qc, dim_pad, codes, n, row_bytes, norms,
-                                                       thr + q0 * thr_stride, thr_stride, thr_off, counts + q0 * count_stride, count_stride,
-                                                       cand + q0 * cap, cap);
+            constexpr int RB = decltype(kern_rb)::value;
+            auto with = [&](auto masked, auto batch) {
+                return launch_rb<RB, decltype(masked)::value, decltype(batch)::value>(
+                    dim3(kI4sThreads), lds, cus, ntiles, st, qimg + q0 * dim_pad, qc, dim_pad, codes, n, row_bytes, norms, thr + q0 * thr_stride, thr_stride,
+                    thr_off, counts + q0 * count_stride, count_stride, cand + q0 * cap, cap, mask ? mask + q0 * mask_stride : nullptr, mask_stride);
+            };
+            if (!mask) return with(std::false_type{}, std::false_type{});
+            return mask_stride == 0 ? with(std::true_type{}, std::true_type{}) : with(std::true_type{}, std::false_type{});
         };
         VG_TRY(b == 1   ? go(std::integral_constant<int, 1>{})
                : b == 2 ? go(std::integral_constant<int, 2>{})

@@ -38,6 +38,19 @@
 //    (in LDS; -Inf for the padded queries of the last block: they never append), a returning atomic on the query's counter
 //    parked until the tile's end, the key make_key(score, row) — the form Int4Row's verify pair reads.  Rows past n re-read the
 //    last row and are never listed.
+//  * row filters (vg_index_enable_int4_nomination's on & 4) are variants of their own, MASKED and BATCH template parameters: the
+//    unfiltered instantiations are the code they were.
+//    BATCH — one filter for all queries: a wave's 64 rows are 8 bytes of it.  A tile whose 8 bytes are zero is SKIPPED by its
+//    wave: no code load, no matrix instruction, no epilogue (at 1 % kept rows about half of the 64-row tiles).  The wave has to
+//    know the next tile it will compute while the current one's last superstep runs — that is when the next loads go out — so
+//    the filter is read ahead, in WINDOWS of 8 of the wave's tiles: one vector load, lane l takes byte l & 7 of the wave's rows in
+//    tile (8 w + (l >> 3)) of the workgroup's sequence, a ballot of "byte != 0" is the window's live tiles.  The window after the
+//    current one is already in flight (issued when the current one was entered, a tile or more before its first use), so the
+//    row loads never wait for a filter byte.  The epilogue's bit of row (j, r) comes out of the window's registers with one lane
+//    shuffle per row block, at the tile's start, and stands beside `row < n`.  The waves of a workgroup skip independently: after
+//    the image's barrier there is none.
+//    Per-query filters — no skip, and the K loop is untouched: the lane reads its query's bit only for a score that has passed
+//    the threshold (a few rows in a thousand).  A launch of a host-side split gets the filter of ITS first query.
 // The error bound (Int4Row::eps, k_int4_nominate.hip, "GEMM sum"): that term allows a start at (t - |x^|^2) / 2 (at most 1.501 B),
 // dim products (S = sum |products| <= 0.51 B) and the key's fma, (dim + 16) roundings of at most u (|s| + S) each whatever their
 // order, the score twice that: 4.03 (dim + 16) u B.  This tile starts at ZERO: its dim roundings are of partial sums of at most S
@@ -49,6 +62,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <type_traits>
 
 #include "vg_device.hpp"
 #include "vg_flat_gemm.hpp"
@@ -65,15 +79,62 @@ __host__ __device__ constexpr size_t int4_small_lds_bytes(int rb, int row_bytes)
     return static_cast<size_t>(int4_small_slots(row_bytes)) * 8 * 16 * (rb * 32) + sizeof(float) * (rb * 32);
 }
 
+// The batch filter read ahead by one wave of flat_gemm_int4_small_kernel<RB, true, true> (see the header): the wave's tiles by
+// ordinal i (tile first + i G, i < mine), the filter's bytes of 8 of them a window.  Only that variant has one; the others hold
+// an I4sNoFilter.
+struct I4sNoFilter {};
+struct I4sFilterWindows {
+    const uint8_t *mask;
+    int64_t mask_bytes;
+    int first, G, wave, lane, mine;
+    uint32_t win, win_next;  // this lane's byte of window win_at, and of the one behind it
+    uint64_t win_live;       // bit l: lane l's byte of `win` is not zero
+    int win_at;
+    __device__ __forceinline__ uint32_t load_window(int w) const
+    {
+        const int64_t tt = static_cast<int64_t>(first) + static_cast<int64_t>(8 * w + (lane >> 3)) * G;
+        const int64_t at = tt * (kI4sBN / 8) + wave * 8 + (lane & 7);    // (a tile past the last one: past the filter's end as well)
+        const uint32_t b = mask[at < mask_bytes ? at : mask_bytes - 1];  // (unconditional, like the row loads)
+        return at < mask_bytes ? b : 0u;
+    }
+    // the first ordinal >= i (in window win_at or behind it) whose tile keeps a row; `mine`: none
+    __device__ __forceinline__ int next_live(int i)
+    {
+        for (;;) {
+            if (i >= mine) return mine;
+            if ((i >> 3) != win_at) {  // (always the next window: ordinals only grow)
+                win = win_next;
+                win_at = i >> 3;
+                win_next = load_window(win_at + 1);
+                win_live = __ballot(win != 0u);
+            }
+            const uint64_t m = win_live & (~uint64_t(0) << (8 * (i & 7)));
+            if (m != 0) return win_at * 8 + (__builtin_ctzll(m) >> 3);
+            i = (win_at + 1) * 8;
+        }
+    }
+    // windows 0 and 1 loaded; the wave's first live ordinal
+    __device__ __forceinline__ int init(const uint8_t *mask_, int64_t n, int ntiles, int G_, int wave_, int lane_)
+    {
+        mask = mask_, mask_bytes = (n + 7) >> 3, first = static_cast<int>(blockIdx.x), G = G_, wave = wave_, lane = lane_;
+        mine = (ntiles - first + G - 1) / G;
+        win = load_window(0), win_next = load_window(1), win_live = __ballot(win != 0u), win_at = 0;
+        return next_live(0);
+    }
+};
+
 // queries: nq x dim_pad bfloat16 (gemm_operands' image, the tail from dim on zeros), nq <= 32 RB; codes: n rows of row_bytes =
-// dim / 2 (dim % 32 == 0), 16-byte aligned; counts: counts[q * count_stride]; cand: cap keys a query
-template <int RB>
+// dim / 2 (dim % 32 == 0), 16-byte aligned; counts: counts[q * count_stride]; cand: cap keys a query; MASKED: mask, a bit per row,
+// (n + 7) / 8 bytes at any alignment — BATCH: one for all queries, otherwise query q's at mask + q * mask_stride
+template <int RB, bool MASKED = false, bool BATCH = false>
 __global__ __launch_bounds__(kI4sThreads) void flat_gemm_int4_small_kernel(
     const uint16_t *__restrict__ queries, int nq, int dim_pad, const uint8_t *__restrict__ codes, int64_t n, int row_bytes,
     const float *__restrict__ norms, const float *__restrict__ thr, int thr_stride, int thr_off, int *__restrict__ counts, int count_stride,
-    uint64_t *__restrict__ cand, int cap)
+    uint64_t *__restrict__ cand, int cap, const uint8_t *__restrict__ mask, int64_t mask_stride)
 {
     static_assert(RB >= 1 && RB <= 4, "one to four blocks of 32 queries");
+    static_assert(MASKED || !BATCH, "a batch filter is a filter");
+    constexpr bool SKIP = MASKED && BATCH;
     constexpr int QB = RB * 32;
     extern __shared__ float gemm_lds[];
     const int ntiles = static_cast<int>((n + kI4sBN - 1) / kI4sBN), G = static_cast<int>(gridDim.x);
@@ -115,10 +176,29 @@ __global__ __launch_bounds__(kI4sThreads) void flat_gemm_int4_small_kernel(
     };
     auto word = [](const uint4 &v, int m) { return m == 0 ? v.x : m == 1 ? v.y : m == 2 ? v.z : v.w; };
 
+    // SKIP: the wave's tiles by ordinal i (tile blockIdx.x + i G) and the filter's windows over them; otherwise an empty struct
+    std::conditional_t<SKIP, I4sFilterWindows, I4sNoFilter> fw;
+    int ord = 0;
+    if constexpr (SKIP) {
+        ord = fw.init(mask, n, ntiles, G, wave, lane);
+        if (ord >= fw.mine) return;  // (the wave alone: there is no barrier behind the image's)
+    }
+
     f32x16 acc[RB][2];
     uint4 cur[2][4], nxt[2][4];
-    load_step(static_cast<int>(blockIdx.x), 0, cur);
-    for (int t = static_cast<int>(blockIdx.x); t < ntiles; t += G) {
+    int t = static_cast<int>(blockIdx.x) + ord * G;
+    load_step(t, 0, cur);
+    while (t < ntiles) {
+        // the tile this wave computes next (ntiles or more: none).  SKIP: this tile's filter bits leave the window first — lane
+        // (r, h)'s rows 32 j + r are bit r & 7 of the byte that lane 8 (ord & 7) + 4 j + (r >> 3) holds
+        int t_next = t + G;
+        bool kept[2] = {true, true};
+        if constexpr (SKIP) {
+#pragma unroll
+            for (int j = 0; j < 2; j++) kept[j] = (__shfl(fw.win, 8 * (ord & 7) + 4 * j + (r >> 3)) >> (r & 7)) & 1u;
+            ord = fw.next_live(ord + 1);
+            t_next = static_cast<int>(blockIdx.x) + ord * G;  // (ord <= mine: at most ntiles - 1 + G)
+        }
         const int64_t n0 = static_cast<int64_t>(t) * kI4sBN + wave * 64;
         float xn[2];
 #pragma unroll
@@ -136,7 +216,7 @@ __global__ __launch_bounds__(kI4sThreads) void flat_gemm_int4_small_kernel(
             // the next superstep's loads — of the next tile behind the last one; past the stream's end: the last tile's first again,
             // never multiplied (unconditional: a load under a condition makes the compiler drain the queue)
             const bool last = S + 1 == nsuper;
-            const int tn = last ? (t + G < ntiles ? t + G : ntiles - 1) : t;
+            const int tn = last ? (t_next < ntiles ? t_next : ntiles - 1) : t;
             load_step(tn, last ? 0 : S + 1, nxt);
             const int a = S < full ? 4 : a_last, lim = S < full ? 8 : rest;
 #pragma unroll
@@ -185,7 +265,7 @@ __global__ __launch_bounds__(kI4sThreads) void flat_gemm_int4_small_kernel(
 #pragma unroll
         for (int j = 0; j < 2; j++) {
             const int64_t nn = n0 + j * 32 + r;
-            const bool row_ok = nn < n;
+            const bool row_ok = nn < n && kept[j];
 #pragma unroll
             for (int b = 0; b < RB; b++) {
                 // a block's 16 scores and compares with no branch between them; only a block in which something passed looks again
@@ -208,6 +288,8 @@ __global__ __launch_bounds__(kI4sThreads) void flat_gemm_int4_small_kernel(
                         const int q = b * 32 + (e & 3) + 8 * (e >> 2) + hv;
                         asm volatile("" : "+v"(sc[e]));  // (compared again here: 16 lane masks kept per block spill the scalar registers)
                         if (!(sc[e] < tq[e]) || q >= nq) continue;
+                        if constexpr (MASKED && !BATCH)  // (only now: for the few scores that passed)
+                            if (!mask_bit(mask + static_cast<int64_t>(q) * mask_stride, nn)) continue;
                         if (parked) store_parked();
                         park_pos = atomicAdd(&counts[static_cast<int64_t>(q) * count_stride], 1);
                         park_q = q;
@@ -218,6 +300,7 @@ __global__ __launch_bounds__(kI4sThreads) void flat_gemm_int4_small_kernel(
             }
         }
         if (parked) store_parked();
+        t = t_next;
     }
 }
 

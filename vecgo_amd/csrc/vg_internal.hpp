@@ -491,7 +491,8 @@ struct NomImage {
     // min_d + 8 scale_d as dim_pad floats, the scale diff_d / 15 as dim_pad floats behind them (`scale` points there; both zeros from
     // dim on) and one float H2 (Int4Row::eps); the GEMM's row tile is converted from the index's row-major nibble codes, bf16(c - 8).
     bool int4 = false;
-    bool int4_small = false;       // with `int4`: enabled with on = 2 — batches of 5 .. 128 queries take the nomination too
+    bool int4_small = false;       // with `int4`: enabled with on & 3 == 2 — batches of 5 .. 128 queries take the nomination too
+    bool int4_masked = false;      // with `int4`: enabled with on & 4 — batches under a row filter take it too
     bool sq8_small = false;        // with `scale` (SQ8 from the codes): enabled with on = 2 — batches of 5 .. 128 queries take the nomination too
     bool pq_small = false;         // PQ from the codes (from_codes, neither of the above): enabled with on = 2 — likewise
     int64_t body = 0;             // bytes of `rows`

@@ -26,9 +26,9 @@ inline int nominate_sel_k(int k) { return k <= kNomPickMaxK ? 8 : k <= 128 ? 16 
 struct GemmGroup;  // vg_flat_gemm.hpp
 // k_flat.hip
 // cnt queries' nomination for their k best on `img`, *nom and all it points to in `scratch` (flat_nominate_bf16_scratch bytes)
-// (img.from_codes, a nomination from the codes: unfiltered; PQ: L2; SQ8, img.scale: L2 and Dot, more than 128 queries; INT4,
-// img.int4: L2, more than 128 queries, dim % 32 == 0)
-size_t flat_nominate_bf16_scratch(int64_t cnt, int64_t n, const NomImage &img, int k);
+// (img.from_codes, a nomination from the codes: PQ: L2, unfiltered; SQ8, img.scale: L2 and Dot, unfiltered; INT4, img.int4: L2,
+// dim % 32 == 0, with a filter too: `masks` of them — 0 none, 1 one for the batch, cnt one per query — size the scratch)
+size_t flat_nominate_bf16_scratch(int64_t cnt, int64_t n, const NomImage &img, int k, int64_t masks = 0);
 int32_t flat_nominate_bf16(vg_index *idx, const NomImage &img, bool dot, const float *queries, int64_t cnt, const uint8_t *mask,
                            int64_t mask_stride, int k, char *scratch, hipStream_t st, ProbeNominated *nom);
 size_t flat_probe_gemm_scratch_bytes(int64_t pairs, int64_t ns_max, int k, int bf16_dim);
@@ -45,15 +45,18 @@ int32_t sq8_nominated_pass(vg_index *idx, const float *q, int64_t nq, int k, con
 // k_pq_nominate.hip (ascending table sums over the whole segment: mask null, desc false, or the batch does not apply)
 bool pq_nomination_applies(const vg_index *idx, const float *d_queries, int64_t nq, int k, const uint8_t *mask, bool desc);
 int32_t pq_nominated_pass(vg_index *idx, const float *q, int64_t nq, int k, uint32_t *oid, float *osc, hipStream_t st, std::vector<int> &failed);
-// k_int4_nominate.hip (L2 over the whole segment: mask null, or the batch does not apply)
+// k_int4_nominate.hip (L2 over the whole segment; mask: the batch's device row filter — per query at mask_stride, one for all at
+// stride 0 — or null; a filtered batch applies only where the mode was enabled with on & 4)
 bool int4_nomination_applies(const vg_index *idx, const float *d_queries, int64_t nq, int k, const uint8_t *mask);
-int32_t int4_nominated_pass(vg_index *idx, const float *q, int64_t nq, int k, uint32_t *oid, float *osc, hipStream_t st, std::vector<int> &failed);
+int32_t int4_nominated_pass(vg_index *idx, const float *q, int64_t nq, int k, const uint8_t *mask, int64_t mask_stride, uint32_t *oid, float *osc,
+                            hipStream_t st, std::vector<int> &failed);
 // k_int4_small.hip: the INT4 append GEMM of one query tile (cnt <= 128; flat_gemm_int4_small_kernel) — whether a row of dim
-// dimensions fits its LDS at all, and the launch (qimg: cnt x dim_pad bfloat16; counts[q * count_stride]; cus: compute units)
+// dimensions fits its LDS at all, and the launch (qimg: cnt x dim_pad bfloat16; counts[q * count_stride]; cus: compute units;
+// mask: a device row filter per query / for the batch (mask_stride 0), or null)
 bool int4_small_tile_fits(int dim);
 int32_t launch_int4_small_gemm(const uint16_t *qimg, int64_t cnt, int dim_pad, const uint8_t *codes, int64_t n, int row_bytes, const float *norms,
                                const float *thr, int thr_stride, int thr_off, int *counts, int count_stride, uint64_t *cand, int cap, int cus,
-                               hipStream_t st);
+                               hipStream_t st, const uint8_t *mask = nullptr, int64_t mask_stride = 0);
 // k_sq8_small.hip: the SQ8 append GEMM of one query tile over the code tiles (cnt <= 128; flat_gemm_sq8_small_kernel) — whether a
 // row of dim dimensions fits its LDS at all (dim <= 2528), and the launch (qimg: cnt x dim_pad bfloat16; tiles: the index's code
 // tiles of `groups` groups; counts[q * count_stride]; cus: compute units)
@@ -268,7 +271,7 @@ int32_t nominated_pass(vg_index *idx, const NomImage &img, bool dot, const float
     for (int64_t q0 = 0; q0 < nq; q0 += 4096) {
         const int64_t cnt = std::min<int64_t>(4096, nq - q0);
         ArenaCall ar(idx->ctx, st);
-        const int i_scr = ar.add(flat_nominate_bf16_scratch(cnt, idx->n, img, k));
+        const int i_scr = ar.add(flat_nominate_bf16_scratch(cnt, idx->n, img, k, !mask ? 0 : mask_stride ? cnt : 1));
         const int i_fail = ar.add(sizeof(int) * static_cast<size_t>(cnt));
         const int i_extra = ar.add(sizeof(float) * static_cast<size_t>(cnt) * extra_floats);
         VG_TRY(ar.commit());
