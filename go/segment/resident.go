@@ -798,7 +798,18 @@ func (r *Resident) EnablePQNominationFromCodesSmallBatches() error {
 	return hipctx.Err(int32(C.vg_index_enable_pq_nomination_from_codes(r.h, C.int32_t(2), nil)))
 }
 
-// PQNominationInfo: mode 0 (off), 1 (the decoded-row image), 2 (from the codes) or 3 (from the codes, small batches too), and the device bytes the mode keeps resident.
+// EnablePQNominationFromCodesFiltered: the nomination from the codes with batches under a row filter (one per query, or one for the
+// batch) taken too — mode 6, or 7 with smallBatches (on | 4) — within what the mode allows and from the filtered crossovers up; a
+// batch filter lets a wave of the one-query-tile GEMM skip the 64-row slices it empties.  Nothing more is resident; results unchanged.
+func (r *Resident) EnablePQNominationFromCodesFiltered(smallBatches bool) error {
+	v := C.int32_t(5)
+	if smallBatches {
+		v = 6
+	}
+	return hipctx.Err(int32(C.vg_index_enable_pq_nomination_from_codes(r.h, v, nil)))
+}
+
+// PQNominationInfo: mode 0 (off), 1 (the decoded-row image), 2 (from the codes), 3 (from the codes, small batches too) or 6 / 7 (those two with filtered batches), and the device bytes the mode keeps resident.
 func (r *Resident) PQNominationInfo() (mode int, heldBytes int64, err error) {
 	var m C.int32_t
 	var b C.int64_t

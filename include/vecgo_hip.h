@@ -1670,10 +1670,21 @@ int32_t vg_index_enable_pq_nomination(vg_index *idx, int32_t on, void *stream);
  * on a GEMM of one query tile whose lanes gather their codebook entry by their row's code byte from global memory
  * straight into the matrix instruction's register, the queries' image resident in LDS (97 .. 128 queries from m = 79 on run as two
  * launches of two 32-query blocks).  Nothing more is resident; vg_index_pq_nomination_info reports mode 3.  Still the scan's:
- * filtered batches, fewer than 32 queries, k > 256, m > 318.  Found by symbol lookup. */
+ * fewer than 32 queries, k > 256, m > 318.
+ * `on` is read as bits: on & 3 is the mode above (1 or 2; 3 and a negative value read as 1), on & 4 adds FILTERED batches — on == 5
+ * and on == 6: a vg_search_flat_filtered / vg_segment_search batch with VG_SCAN_PQ over the whole segment, under one row filter per
+ * query or one for the batch (mask_stride 0), takes the nomination too, within what on & 3 allows and under the same conditions:
+ * above 128 queries from queries x rows >= 129M, 32 .. 128 queries (on == 6) from >= 32M (README, Limits).  The threshold sample reads
+ * the filter's bits of the sampled rows, the GEMMs append kept rows only; under a batch filter a wave of the one-query-tile GEMM walks
+ * only the 64-row slices of its tiles that keep a row.  A filter that leaves the sample too few rows for a threshold gets every kept
+ * row listed: that complete list is accepted as it is up to 64 rows at k <= 48 and up to 4096 rows at k > 48; a query whose proof
+ * fails is searched again without the nomination under its own filter; a filter that keeps fewer than k rows yields the scan's padded
+ * answer.  Nothing more is resident; the info call reports 6 and 7 (2 and 3, + 4).  on == 4 (a flag without a mode) and on > 6:
+ * VG_ERR_INVALID_ARG, the state as it was.  Filtered batches under vg_index_enable_pq_nomination (the image), probed partitions,
+ * descending (Dot) scores, the threshold searches and fewer than 32 queries keep the scan.  Found by symbol lookup. */
 int32_t vg_index_enable_pq_nomination_from_codes(vg_index *idx, int32_t on, void *stream);
 /* Which PQ nomination an index holds and what it costs: *mode = 0 (off), 1 (the image: vg_index_enable_pq_nomination), 2 (from
- * the codes) or 3 (from the codes, enabled with on == 2); *held_bytes = the device memory the mode keeps resident (mode 1: the image, the norms and norm_max).  Either
+ * the codes), 3 (from the codes, enabled with on == 2), or 6 / 7 (those two enabled with on & 4: filtered batches too); *held_bytes = the device memory the mode keeps resident (mode 1: the image, the norms and norm_max).  Either
  * pointer may be NULL.  Found by symbol lookup. */
 int32_t vg_index_pq_nomination_info(const vg_index *idx, int32_t *mode, int64_t *held_bytes);
 /* vg_index_enable_sq8_nomination WITHOUT the image of the dequantised rows.  A code is an integer, and bfloat16 holds c - 128

@@ -666,7 +666,10 @@ public:
     void EnablePQNominationFromCodes(bool on = true) { check(vg_index_enable_pq_nomination_from_codes(h_, on ? 1 : 0, nullptr)); }
     // the same, and unfiltered batches of 32 .. 128 queries from 32M (query, row) pairs (m <= 318) take the nomination too (mode 3)
     void EnablePQNominationFromCodesSmallBatches() { check(vg_index_enable_pq_nomination_from_codes(h_, 2, nullptr)); }
-    // mode: 0 off, 1 the image, 2 from the codes, 3 from the codes with small batches; held_bytes: the device memory the mode keeps resident
+    // the same with filtered batches (on | 4, modes 6 and 7): SearchFiltered batches with VG_SCAN_PQ over the whole segment, one filter
+    // per query or one for the batch, take the nomination too — above 128 queries, and with small_batches 32 .. 128
+    void EnablePQNominationFromCodesFiltered(bool small_batches = false) { check(vg_index_enable_pq_nomination_from_codes(h_, small_batches ? 6 : 5, nullptr)); }
+    // mode: 0 off, 1 the image, 2 from the codes, 3 from the codes with small batches, 6 / 7 those with filtered batches; held_bytes: the device memory the mode keeps resident
     struct PQNomination {
         int32_t mode;
         int64_t held_bytes;

@@ -1025,19 +1025,22 @@ class Index:
         the reference's order and proven: ids and scores stay bit-identical."""
         check(self._lib.vg_index_enable_pq_nomination(self._h, C.c_int32(1 if on else 0), _stream_ptr(stream)))
 
-    def enable_pq_nomination_from_codes(self, on: bool = True, small_batches: bool = False, stream=None):
+    def enable_pq_nomination_from_codes(self, on: bool = True, small_batches: bool = False, filtered: bool = False, stream=None):
         """vg_index_enable_pq_nomination_from_codes: the same nomination without the image of the decoded rows — the GEMM's row tiles
         are gathered from a bfloat16 copy of the decoded codebook by the rows' codes (8 dimensions per sub-quantizer, K = 256;
         batches above 128 queries, from queries x rows >= 13M).  small_batches (on = 2, reported as mode 3): unfiltered batches of
         32 .. 128 queries with queries x rows >= 32M take it too (m <= 318; the tile serves 5 .. 128, but 8 queries lost to the scan
         and 9 .. 31 were never measured), on a tile whose lanes gather the codebook entries straight into the matrix unit's
-        registers.  Resident: 4 bytes a row and the codebook.  Exclusive with enable_pq_nomination; ids and scores stay
-        bit-identical."""
-        check(self._lib.vg_index_enable_pq_nomination_from_codes(self._h, C.c_int32((2 if small_batches else 1) if on else 0), _stream_ptr(stream)))
+        registers.  filtered (on | 4: modes 6 and 7): search_flat_filtered batches with scan = PQ over the whole segment — one
+        filter per query or one for the batch — take it too, within what the mode allows and from the filtered crossovers up; a
+        batch filter lets a wave of the small tile skip the 64-row slices it empties.  Resident: 4 bytes a row and the codebook.
+        Exclusive with enable_pq_nomination; ids and scores stay bit-identical."""
+        mode = ((2 if small_batches else 1) | (4 if filtered else 0)) if on else 0
+        check(self._lib.vg_index_enable_pq_nomination_from_codes(self._h, C.c_int32(mode), _stream_ptr(stream)))
 
     def pq_nomination_info(self):
         """vg_index_pq_nomination_info: (mode, held_bytes) — mode 0 off, 1 the decoded-row image, 2 from the codes, 3 from the codes
-        with small batches; held_bytes the device memory the mode keeps resident."""
+        with small batches, 6 / 7 those two with filtered batches; held_bytes the device memory the mode keeps resident."""
         mode, held = C.c_int32(0), C.c_int64(0)
         check(self._lib.vg_index_pq_nomination_info(self._h, C.byref(mode), C.byref(held)))
         return mode.value, held.value

@@ -955,9 +955,9 @@ static int32_t pq_adc_search_impl(vg_index *idx, const float *queries, int64_t n
 
     if (idx->n == 0) {
         VG_TRY(vg::empty_results(nq, k, false, oid, osc, st));
-    } else if (allow_nomination && vg::pq_nomination_applies(idx, q, nq, k, mask, desc)) {
+    } else if (allow_nomination && !mask && vg::pq_nomination_applies(idx, q, nq, k, nullptr, desc)) {  // (a filtered batch: probed_whole_shortcut, k_probe.hip)
         std::vector<int> failed;
-        VG_TRY(vg::pq_nominated_pass(idx, q, nq, k, oid, osc, st, failed));
+        VG_TRY(vg::pq_nominated_pass(idx, q, nq, k, nullptr, 0, oid, osc, st, failed));
         // the table scan for the queries whose proof failed (ties at the k-th score, thresholds too tight)
         VG_TRY(vg::rescan_failed(failed, q, idx->dim, k, nullptr, 0, 0, oid, osc, st,
                                  [&](const float *fq, int64_t nf, const uint8_t *, int64_t, uint32_t *fid, float *fsc) {

@@ -305,7 +305,8 @@ static int32_t launch_gemm_t(const GemmArgs &a)
                 if (a.counts_wide) VG_HIP(hipMemsetAsync(a.counts_wide, 0, sizeof(int) * static_cast<size_t>(c.cnt) * kCountLine, st));
                 VG_TRY(launch_pq_small_gemm(reinterpret_cast<const uint16_t *>(a.queries), c.cnt, 2 * c.ops.dim_words, a.codes, c.ops.n, a.code_m,
                                             reinterpret_cast<const uint4 *>(c.ops.b), c.ops.norms, a.thr, a.thr_stride, a.thr_off,
-                                            a.counts_wide ? a.counts_wide : a.counts, a.counts_wide ? kCountLine : 1, a.cand, a.cap, a.cus, st));
+                                            a.counts_wide ? a.counts_wide : a.counts, a.counts_wide ? kCountLine : 1, a.cand, a.cap, a.cus, st, c.mask,
+                                            c.mask_stride));
                 if (a.counts_wide)
                     VG_LAUNCH(counts_narrow_kernel, dim3(static_cast<unsigned>((c.cnt + 255) / 256)), dim3(256), 0, st, a.counts_wide, c.cnt, a.counts);
                 return VG_OK;
@@ -610,7 +611,7 @@ __global__ __launch_bounds__(64) void flat_thr_cap_kernel(float *__restrict__ th
 // sample fewer than sel_k rows has every kept row appended — a COMPLETE list, which the pair accepts as it is (tq == +Inf) — but
 // after the cap it looked like a threshold to prove against, and a list of fewer than k rows, or one whose k-th score lies within
 // the margin of the (huge) bound, failed the proof and went to the scan: every query of a selective filter.  The filtered INT4
-// nomination (flat_nominate_bf16 with a mask) takes this one; unfiltered calls take the kernel above, as they did.
+// and PQ nominations from the codes (flat_nominate_bf16 with a mask) take this one; every other call takes the kernel above, as it did.
 __global__ __launch_bounds__(64) void flat_thr_cap_gemm_kernel(const float *__restrict__ thr, int sel_k, const float *__restrict__ queries, int dim,
                                                                const float *__restrict__ norm_max, float *__restrict__ gemm_thr)
 {
@@ -1664,8 +1665,9 @@ struct NominateScratch : NomScratch {
     int64_t rows_c;   // from the codes: the sampled tiles' rows (0: an image, or too few rows for a sample) ...
     uint16_t *srows;  // ... decoded, dim_pad each ...
     float *snorms;    // ... and their norms
-    // `masks` row filters (0 none, 1 the batch's, cnt one per query) on the INT4 nomination: the filters over the compact rows
-    // (sample_mask_gather_kernel; cbytes each, 0 without a sample) and the GEMM's own capped thresholds (flat_thr_cap_gemm_kernel)
+    // `masks` row filters (0 none, 1 the batch's, cnt one per query) on a from-codes nomination that takes them (INT4, PQ:
+    // NomImage::codes_take_filters): the filters over the compact rows (sample_mask_gather_kernel; cbytes each, 0 without a sample)
+    // and the GEMM's own capped thresholds (flat_thr_cap_gemm_kernel)
     uint8_t *cmask;
     int64_t cbytes;
     float *gthr;
@@ -1679,10 +1681,11 @@ struct NominateScratch : NomScratch {
         c.take(srows, rows_c * img.dim_pad);
         c.take(snorms, rows_c);
         // (Carve::take hands out a pointer for a count of zero too: what another call has not got is null)
-        cbytes = masks && img.int4 ? (rows_c + 7) / 8 : 0;
+        const bool filtered = masks && img.codes_take_filters();
+        cbytes = filtered ? (rows_c + 7) / 8 : 0;
         cmask = nullptr, gthr = nullptr;
         if (cbytes) c.take(cmask, masks * cbytes);
-        if (masks && img.int4) c.take(gthr, cnt);
+        if (filtered) c.take(gthr, cnt);
         bytes = c.off;
     }
 };
@@ -1696,22 +1699,25 @@ int32_t flat_nominate_bf16(vg_index *idx, const NomImage &img, bool dot, const f
 {
     const int64_t masks = !mask ? 0 : mask_stride ? cnt : 1;
     const NominateScratch s(scratch, cnt, idx->n, img, k, masks);
-    VG_CHECK(!mask || !img.from_codes || img.int4, VG_ERR_INVALID_ARG, "flat_nominate_bf16: a filter on a from-codes mode without one");
+    VG_CHECK(!mask || !img.from_codes || img.codes_take_filters(), VG_ERR_INVALID_ARG, "flat_nominate_bf16: a filter on a from-codes mode without one");
     NomCall nc{st, dot, {}, cnt, mask, mask_stride};
     // (from the codes the GEMM's "rows" are the codebook; n, the row length and the norms are the decoded rows')
     VG_TRY(gemm_operands(queries, cnt, idx->dim, idx->n, img.norms, img.rows, img.dim_pad, s.qbf, st, &nc.ops, img.scale));
     *nom = s.nom;
     NomCall sc = nc;  // the sample's operands: the image's, or the sampled tiles decoded here
+    // a from-codes sample sees compact rows: so must its filter (the append below sees real rows and keeps the caller's)
+    auto sample_filter = [&]() -> int32_t {
+        VG_LAUNCH(sample_mask_gather_kernel, dim3(static_cast<unsigned>((masks * s.cbytes + 255) / 256)), dim3(256), 0, st, mask, mask_stride, masks,
+                  s.cbytes, kFlatSampleStride, s.cmask);
+        sc.mask = s.cmask, sc.mask_stride = mask_stride ? s.cbytes : 0;
+        return VG_OK;
+    };
     if (s.rows_c && img.int4) {
         const int blocks_pad = img.dim_pad / 32;
         VG_LAUNCH(int4_sample_rows_kernel, dim3(static_cast<unsigned>((s.rows_c * blocks_pad + 255) / 256)), dim3(256), 0, st, idx->d_int4_rows,
                   idx->dim / 2, blocks_pad, img.norms, s.rows_c, kFlatSampleStride, reinterpret_cast<uint4 *>(s.srows), s.snorms);
         sc.ops.b = reinterpret_cast<const float *>(s.srows), sc.ops.n = s.rows_c, sc.ops.norms = s.snorms;
-        if (mask) {  // the sample sees compact rows: so must its filter (the append below sees real rows and keeps the caller's)
-            VG_LAUNCH(sample_mask_gather_kernel, dim3(static_cast<unsigned>((masks * s.cbytes + 255) / 256)), dim3(256), 0, st, mask, mask_stride, masks,
-                      s.cbytes, kFlatSampleStride, s.cmask);
-            sc.mask = s.cmask, sc.mask_stride = mask_stride ? s.cbytes : 0;
-        }
+        if (mask) VG_TRY(sample_filter());
     } else if (s.rows_c && img.scale) {
         const int groups_pad = img.dim_pad / 16;
         VG_LAUNCH(sq8_sample_rows_kernel, dim3(static_cast<unsigned>((s.rows_c * groups_pad + 255) / 256)), dim3(256), 0, st,
@@ -1724,9 +1730,10 @@ int32_t flat_nominate_bf16(vg_index *idx, const NomImage &img, bool dot, const f
                   idx->pq->m, reinterpret_cast<const uint4 *>(img.rows), granules, img.norms, s.rows_c, kFlatSampleStride,
                   reinterpret_cast<uint4 *>(s.srows), s.snorms);
         sc.ops.b = reinterpret_cast<const float *>(s.srows), sc.ops.n = s.rows_c, sc.ops.norms = s.snorms;
+        if (mask) VG_TRY(sample_filter());
     }
     VG_TRY(sample_thresholds(sc, s, s.rows_c ? 1 : kFlatSampleStride, nom->sel_k, nom->thr, idx->n > kFlatCap));
-    if (s.gthr)  // (the filtered INT4 nomination: nom->thr keeps its +Inf for the verify pair)
+    if (s.gthr)  // (a filtered nomination from INT4 or PQ codes: nom->thr keeps its +Inf for the verify pair)
         VG_LAUNCH(flat_thr_cap_gemm_kernel, dim3(nc.ucnt()), dim3(64), 0, st, nom->thr, nom->sel_k, queries, idx->dim, img.norm_max, s.gthr);
     else
         VG_LAUNCH(flat_thr_cap_kernel, dim3(nc.ucnt()), dim3(64), 0, st, nom->thr, nom->sel_k, queries, idx->dim, img.norm_max);

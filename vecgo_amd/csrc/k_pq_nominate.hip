@@ -184,25 +184,59 @@ constexpr int64_t kPqNomCodesMinPairs = 13000000;
 constexpr int kPqNomCodesSmallMinQueries = 32;
 constexpr int64_t kPqNomCodesSmallMinPairs = 32000000;
 
-// whether a batch takes the nomination (device queries; ascending table sums over the whole segment, no row filter)
+// The same for FILTERED batches from the codes (on & 4, NomImage::pq_masked): above 128 queries the big tile with the filter in its
+// epilogue, 5 .. 128 queries the small tile's MASKED variants (on & 3 == 2).  A filter makes the scan a little cheaper and the
+// nomination mostly dearer, so these stand apart from the constants above.
+// Measured (MI355X, tools/pq_nominate_codes_time.py 1000000 filtered, dim 768, m = 96, k = 10, ms per call, filtered scan / filtered
+// nomination, alternating windows of ~100 ms in one run on one index, the windows of a leg within 1 % of each other (4 % at 32 x
+// 100k); profiles/pq_nominate_codes_time_filtered.txt), a batch filter keeping 100 % / 10 % / 1 % of the rows, then one per query
+// keeping 10 %; bits equal and no query rescanned in any line.
+// Above 128 queries (the big tile): 129 x 100k, 10 %: 0.282 / 0.304 — LOST, it keeps the scan; 129 x 1M, 10 % and 1 %: 2.087 / 0.644,
+// 1.979 / 0.815; 256 x 1M, 1 %: 3.173 / 0.860; 1024 x 1M: 13.49 / 1.868, 13.46 / 2.244, 12.61 / 2.756, 15.88 / 2.682 (k = 100, 10 %:
+// 27.07 / 2.755).  The scan gets 7 % faster at 1 % kept, the big tile 48 % slower (its GEMM 1.575 -> 2.444 ms: thresholds from a
+// hundredth of the sample pass more rows, and every pass reads a filter bit), as for INT4.  The constant is the smallest measured
+// product that won, 129 x 1M; nothing between 12.9M and 129M pairs was measured.
+// 5 .. 128 queries (the small tile), 100k rows: 32 queries 0.084 / 0.179, 0.078 / 0.184, 0.073 / 0.181, 0.079 / 0.188; 128: 0.264 /
+// 0.261, 0.241 / 0.274, 0.223 / 0.303, 0.244 / 0.323 — lost everywhere but for a tie under the keep-all filter: 100k rows keep the
+// scan.  1M rows: 8 queries 0.141 / 0.348, 0.136 / 0.341, 0.126 / 0.271, 0.140 / 0.347 — lost 0.40x .. 0.46x, so the floor of 32
+// queries stays for filtered batches; 32: 0.472 / 0.356, 0.472 / 0.350, 0.420 / 0.281, 0.511 / 0.360; 128: 1.723 / 0.565, 1.703 /
+// 0.565, 1.604 / 0.464, 1.943 / 0.732 — won 1.33x .. 3.46x.  The constant is the smallest measured product that won, 32 x 1M, with
+// nothing between 12.8M and 32M pairs measured: as unfiltered.
+// What the slice skip buys (the GEMM's scope, 1M rows, 100 % / 10 % / 1 % kept): 32 queries 0.191 / 0.190 / 0.127 ms, 8 queries
+// 0.183 / 0.182 / 0.118, 128 queries (two launches) 0.385 / 0.389 / 0.292: at 1 % kept 53 % of the 64-row slices are empty and a
+// pass costs 34 % less (its gathers are the pass's cost, see above); at 10 % one slice in 850 is empty and nothing changes.  One
+// filter per query has no skip and reads a bit for every score under its threshold: 0.197 at 32 queries, 0.542 at 128.  Over 100k
+// rows (391 tiles for 512 workgroups and more: a workgroup has one tile, a skipped slice shortens nothing) the 1 % filter makes the
+// pass dearer, 0.095 -> 0.141 ms at 128 queries, by the appends its looser thresholds let through.
+constexpr int64_t kPqNomCodesMaskedMinPairs = 129000000;
+constexpr int kPqNomCodesMaskedSmallMinQueries = 32;
+constexpr int64_t kPqNomCodesMaskedSmallMinPairs = 32000000;
+
+// whether a batch takes the nomination (device queries; ascending table sums over the whole segment; mask: the batch's row filter,
+// per query or one for all, or null — a filtered batch only from the codes, where the mode was enabled with on & 4)
 bool pq_nomination_applies(const vg_index *idx, const float *d_queries, int64_t nq, int k, const uint8_t *mask, bool desc)
 {
     const int mode = idx->pq_nom.mode();
+    if (mask && !(mode == 2 && idx->pq_nom.pq_masked)) return false;
     const bool small = mode == 2 && nq <= 128;  // the small tile's batches, where it was enabled and takes the rows
     if (small && (!idx->pq_nom.pq_small || nq < 5 || !pq_small_tile_takes(idx->pq->m, idx->n))) return false;
-    if (small && nq < kPqNomCodesSmallMinQueries && !hook(kHookPqNomAlways)) return false;
-    const int64_t min_pairs = small ? kPqNomCodesSmallMinPairs : mode == 2 ? kPqNomCodesMinPairs : kPqNomMinPairs;
-    return mode && !mask && !desc && (nq * idx->n >= min_pairs || hook(kHookPqNomAlways)) && k <= kNomMaxK && idx->n > k && idx->pq->k == 256 &&
+    if (small && nq < (mask ? kPqNomCodesMaskedSmallMinQueries : kPqNomCodesSmallMinQueries) && !hook(kHookPqNomAlways)) return false;
+    const int64_t min_pairs = small       ? (mask ? kPqNomCodesMaskedSmallMinPairs : kPqNomCodesSmallMinPairs)
+                              : mode == 2 ? (mask ? kPqNomCodesMaskedMinPairs : kPqNomCodesMinPairs)
+                                          : kPqNomMinPairs;
+    return mode && !desc && (nq * idx->n >= min_pairs || hook(kHookPqNomAlways)) && k <= kNomMaxK && idx->n > k && idx->pq->k == 256 &&
            aligned16(d_queries);
 }
 
 // nominated_pass with the PQ re-score.  (From the codes the GEMM's operands are the image's, bit for bit: the same margin,
-// pq_nominate_eps, holds.)
-int32_t pq_nominated_pass(vg_index *idx, const float *q, int64_t nq, int k, uint32_t *oid, float *osc, hipStream_t st, std::vector<int> &failed)
+// pq_nominate_eps, holds.  A row filter changes none of it: the bound is per (query, row), and a filter only takes rows away, from
+// the list and from the rows outside it alike.)
+int32_t pq_nominated_pass(vg_index *idx, const float *q, int64_t nq, int k, const uint8_t *mask, int64_t mask_stride, uint32_t *oid, float *osc,
+                          hipStream_t st, std::vector<int> &failed)
 {
     const vg_pq *pq = idx->pq;
     // per pass: the queries' tables (BuildDistanceTable, the reference's layout), then the table sums of the nominees
-    return nominated_pass(idx, idx->pq_nom, false, q, nq, k, nullptr, 0, static_cast<size_t>(pq->m) * 256, oid, osc, st, failed,
+    return nominated_pass(idx, idx->pq_nom, false, q, nq, k, mask, mask_stride, static_cast<size_t>(pq->m) * 256, oid, osc, st, failed,
                           [&](const float *qq, int64_t cnt, const ProbeNominated &nom, float *tables, uint32_t *pid, float *psc, int *fail) -> int32_t {
                               VG_TRY(launch_pq_build_table(pq, qq, cnt, tables, false, st));
                               return launch_nominated_verify<false>(PqTableRow{idx->d_pq_rows, tables, pq->m, pq->subdim, idx->dim}, qq,
@@ -211,11 +245,13 @@ int32_t pq_nominated_pass(vg_index *idx, const float *q, int64_t nq, int k, uint
 }
 }  // namespace vg
 
-// vg_index_enable_pq_nomination (mode 1) and vg_index_enable_pq_nomination_from_codes (mode 2; on == 2: small batches too); fn: the entry point's name.
+// vg_index_enable_pq_nomination (mode 1) and vg_index_enable_pq_nomination_from_codes (mode 2; `on` as bits: on & 3 == 2: small batches too,
+// on & 4: filtered batches too — of a mode, so 4 alone is none); fn: the entry point's name.
 // Turning a mode off, or on again, drops that mode only; turning it on drops the other one too, but only once nothing can refuse.
 static int32_t pq_nomination_enable(vg_index *idx, int mode, int32_t on, void *stream, const char *fn)
 {
     VG_CHECK(idx, VG_ERR_INVALID_ARG, "%s: NULL index", fn);
+    VG_CHECK(mode != 2 || (on != 4 && on <= 6), VG_ERR_INVALID_ARG, "%s: on=%d is a flag without a mode, or above 6", fn, on);
     VG_HIP(hipSetDevice(idx->ctx->device));
     hipStream_t st = vg::pick_stream(idx->ctx, stream);
     if (idx->pq_nom.mode() == mode) VG_TRY(vg::nom_free(idx->pq_nom, st));
@@ -242,7 +278,8 @@ static int32_t pq_nomination_enable(vg_index *idx, int mode, int32_t on, void *s
                              hipLaunchKernelGGL(vg::pq_norms_kernel, rows_grid, dim3(256), 0, st, idx->d_pq_rows, idx->n, pq->m, pq->k, pq->subdim,
                                                 pq->d_codebooks, pq->d_scales, pq->d_offsets, b.norms, norm_max_bits);
                          }));
-    idx->pq_nom.pq_small = from_codes && on == 2;  // (any other non-zero value is 1)
+    idx->pq_nom.pq_small = from_codes && on > 0 && (on & 3) == 2;  // (1, 3 and a negative value are 1)
+    idx->pq_nom.pq_masked = from_codes && on > 0 && (on & 4) != 0;
     return VG_OK;
 }
 
@@ -259,7 +296,8 @@ VG_API int32_t vg_index_enable_pq_nomination_from_codes(vg_index *idx, int32_t o
 VG_API int32_t vg_index_pq_nomination_info(const vg_index *idx, int32_t *mode, int64_t *held_bytes)
 {
     VG_CHECK(idx, VG_ERR_INVALID_ARG, "vg_index_pq_nomination_info: NULL index");
-    if (mode) *mode = idx->pq_nom.pq_small ? 3 : idx->pq_nom.mode();  // (3: from the codes, small batches too)
+    // (3: from the codes, small batches too; 6 and 7: 2 and 3 with filtered batches)
+    if (mode) *mode = (idx->pq_nom.pq_small ? 3 : idx->pq_nom.mode()) | (idx->pq_nom.pq_masked ? 4 : 0);
     if (held_bytes) *held_bytes = idx->pq_nom.held_bytes(idx->n);
     return VG_OK;
 }

@@ -13,28 +13,35 @@ bool pq_small_tile_fits(int m) { return m > 0 && pq_small_lds_bytes(1, m) <= kPq
 // ... and the codes of n rows hold the 16 bytes of one of its code loads: what the launch, the profile scope and the batches' test ask
 bool pq_small_tile_takes(int m, int64_t n) { return pq_small_tile_fits(m) && n * m >= 16; }
 
-template <int RB>
+constexpr int kPqsSmallGrid = 2;  // workgroups under the test hook VG_PQ_SMALL_GRID
+
+// (MASKED, BATCH: a row filter per query / one for the batch — the kernel's variants of their own)
+template <int RB, bool MASKED, bool BATCH>
 static int32_t launch_rb(size_t lds, int cus, int64_t ntiles, hipStream_t st, const uint16_t *q, int nq, int dim_pad, const uint8_t *codes, int64_t n,
                          int m, const uint4 *cb16, const float *norms, const float *thr, int thr_stride, int thr_off, int *counts, int count_stride,
-                         uint64_t *cand, int cap)
+                         uint64_t *cand, int cap, const uint8_t *mask, int64_t mask_stride)
 {
-    auto kern = flat_gemm_pq_small_kernel<RB>;
+    auto kern = flat_gemm_pq_small_kernel<RB, MASKED, BATCH>;
     VG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
     // persistent: as many workgroups as the device holds at once (LDS and registers decide how many a CU takes), a tile each at most
     int per_cu = 1;
     VG_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, kPqsThreads, lds));
-    const int64_t grid = std::min<int64_t>(ntiles, static_cast<int64_t>(std::max(cus, 1)) * std::max(per_cu, 1));
+    int64_t grid = std::min<int64_t>(ntiles, static_cast<int64_t>(std::max(cus, 1)) * std::max(per_cu, 1));
+    if (hook(kHookPqSmallGrid)) grid = std::min<int64_t>(grid, kPqsSmallGrid);
     VG_LAUNCH(kern, dim3(static_cast<unsigned>(grid)), dim3(kPqsThreads), lds, st, q, nq, dim_pad, codes, n, m, cb16, norms, thr, thr_stride, thr_off,
-              counts, count_stride, cand, cap);
+              counts, count_stride, cand, cap, mask, mask_stride);
     return VG_OK;
 }
 
 // cnt <= 128 queries (qimg: cnt x dim_pad bfloat16) against n > 0 rows of m code bytes (n m >= 16) and the decoded codebook cb16 of
 // dim_pad / 8 slices.  The image of the blocks of a launch is resident in LDS: where all of the batch's blocks do not fit, the
 // batch runs as the fewest launches of equally many blocks that do (a pass over the codes each) — decided here, once, from the shapes.
+// mask: a device row filter per query (at mask_stride bytes; a launch of the split gets its own queries') or for the batch
+// (mask_stride 0: the variant that skips the 64-row slices the filter empties, where the filter has the 8 bytes of one — n >= 64 —
+// else the per-query variant at stride 0), or null.
 int32_t launch_pq_small_gemm(const uint16_t *qimg, int64_t cnt, int dim_pad, const uint8_t *codes, int64_t n, int m, const uint4 *cb16,
                              const float *norms, const float *thr, int thr_stride, int thr_off, int *counts, int count_stride, uint64_t *cand, int cap,
-                             int cus, hipStream_t st)
+                             int cus, hipStream_t st, const uint8_t *mask, int64_t mask_stride)
 {
     VG_CHECK(cnt > 0 && cnt <= 128 && n > 0 && pq_small_tile_takes(m, n) && dim_pad >= 16 * pq_small_steps(m) && dim_pad % 8 == 0 && aligned16(qimg, cb16),
              VG_ERR_INVALID_ARG, "launch_pq_small_gemm: a call the small PQ tile does not take");
@@ -43,13 +50,19 @@ int32_t launch_pq_small_gemm(const uint16_t *qimg, int64_t cnt, int dim_pad, con
     while (pq_small_lds_bytes((rb + launches - 1) / launches, m) > kPqsLdsMax) launches++;
     const int per = (rb + launches - 1) / launches;  // blocks a launch
     const int64_t ntiles = (n + kPqsBN - 1) / kPqsBN;
+    const bool skip = mask && mask_stride == 0 && n >= 64;
     for (int64_t q0 = 0; q0 < cnt; q0 += per * 32) {
         const int qc = static_cast<int>(std::min<int64_t>(per * 32, cnt - q0)), b = (qc + 31) / 32;
         const size_t lds = pq_small_lds_bytes(b, m);
         auto go = [&](auto kern_rb) {
-            return launch_rb<decltype(kern_rb)::value>(lds, cus, ntiles, st, qimg + q0 * dim_pad, qc, dim_pad, codes, n, m, cb16, norms,
-                                                       thr + q0 * thr_stride, thr_stride, thr_off, counts + q0 * count_stride, count_stride,
-                                                       cand + q0 * cap, cap);
+            constexpr int RB = decltype(kern_rb)::value;
+            auto with = [&](auto masked, auto batch) {
+                return launch_rb<RB, decltype(masked)::value, decltype(batch)::value>(
+                    lds, cus, ntiles, st, qimg + q0 * dim_pad, qc, dim_pad, codes, n, m, cb16, norms, thr + q0 * thr_stride, thr_stride, thr_off,
+                    counts + q0 * count_stride, count_stride, cand + q0 * cap, cap, mask ? mask + q0 * mask_stride : nullptr, mask_stride);
+            };
+            if (!mask) return with(std::false_type{}, std::false_type{});
+            return skip ? with(std::true_type{}, std::true_type{}) : with(std::true_type{}, std::false_type{});
         };
         VG_TRY(b == 1   ? go(std::integral_constant<int, 1>{})
                : b == 2 ? go(std::integral_constant<int, 2>{})

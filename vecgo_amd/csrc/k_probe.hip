@@ -696,6 +696,14 @@ static int32_t probed_whole_shortcut(const ProbedCall &c, bool *done)
         VG_TRY(vg::sq8_nominated_pass(idx, c.q, c.nq, c.k, c.mk, c.mask_stride, c.oid, c.osc, c.st, failed));
         return c.rescan(failed);
     }
+    // A filtered PQ batch over the whole segment with vg_index_enable_pq_nomination_from_codes' on & 4: the nomination from the codes
+    // with the filter in the GEMMs (the big tile's masked epilogue; the small tile's masked variants, k_pq_small.hip), the table sums
+    // of the nominees, the proof (k_pq_nominate.hip); queries whose proof fails take the scan below, or the probe kernels
+    if (c.scan == VG_SCAN_PQ && c.allow_nomination && vg::pq_nomination_applies(idx, c.q, c.nq, c.k, c.mk, c.dot)) {
+        std::vector<int> failed;
+        VG_TRY(vg::pq_nominated_pass(idx, c.q, c.nq, c.k, c.mk, c.mask_stride, c.oid, c.osc, c.st, failed));
+        return c.rescan(failed);
+    }
     // A filtered PQ scan of the whole segment, k <= 64 and a table that fits LDS: the pipelined scan of vg_search_pq_adc with
     // the filter where keys are made (the probe kernel is the plain loop, twice its time; a wider table, and test hook
     // kHookAdcWideAlways: the chunked probe kernel over the 64 pieces below)

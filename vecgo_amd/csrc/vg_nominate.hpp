@@ -26,8 +26,9 @@ inline int nominate_sel_k(int k) { return k <= kNomPickMaxK ? 8 : k <= 128 ? 16 
 struct GemmGroup;  // vg_flat_gemm.hpp
 // k_flat.hip
 // cnt queries' nomination for their k best on `img`, *nom and all it points to in `scratch` (flat_nominate_bf16_scratch bytes)
-// (img.from_codes, a nomination from the codes: PQ: L2, unfiltered; SQ8, img.scale: L2 and Dot, unfiltered; INT4, img.int4: L2,
-// dim % 32 == 0, with a filter too: `masks` of them — 0 none, 1 one for the batch, cnt one per query — size the scratch)
+// (img.from_codes, a nomination from the codes: SQ8, img.scale: L2 and Dot, unfiltered; PQ: L2; INT4, img.int4: L2, dim % 32 == 0;
+// these two with a filter too (NomImage::codes_take_filters): `masks` of them — 0 none, 1 one for the batch, cnt one per query —
+// size the scratch)
 size_t flat_nominate_bf16_scratch(int64_t cnt, int64_t n, const NomImage &img, int k, int64_t masks = 0);
 int32_t flat_nominate_bf16(vg_index *idx, const NomImage &img, bool dot, const float *queries, int64_t cnt, const uint8_t *mask,
                            int64_t mask_stride, int k, char *scratch, hipStream_t st, ProbeNominated *nom);
@@ -42,9 +43,12 @@ int32_t launch_sq8_verify(vg_index *idx, const float *queries, int64_t nq, const
 bool sq8_nomination_applies(const vg_index *idx, const float *d_queries, int64_t nq, int k, const uint8_t *mask);
 int32_t sq8_nominated_pass(vg_index *idx, const float *q, int64_t nq, int k, const uint8_t *mask, int64_t mask_stride, uint32_t *oid,
                            float *osc, hipStream_t st, std::vector<int> &failed);
-// k_pq_nominate.hip (ascending table sums over the whole segment: mask null, desc false, or the batch does not apply)
+// k_pq_nominate.hip (ascending table sums over the whole segment: desc false, or the batch does not apply; mask: the batch's device
+// row filter — per query at mask_stride, one for all at stride 0 — or null; a filtered batch applies only from the codes and where
+// that mode was enabled with on & 4)
 bool pq_nomination_applies(const vg_index *idx, const float *d_queries, int64_t nq, int k, const uint8_t *mask, bool desc);
-int32_t pq_nominated_pass(vg_index *idx, const float *q, int64_t nq, int k, uint32_t *oid, float *osc, hipStream_t st, std::vector<int> &failed);
+int32_t pq_nominated_pass(vg_index *idx, const float *q, int64_t nq, int k, const uint8_t *mask, int64_t mask_stride, uint32_t *oid, float *osc,
+                          hipStream_t st, std::vector<int> &failed);
 // k_int4_nominate.hip (L2 over the whole segment; mask: the batch's device row filter — per query at mask_stride, one for all at
 // stride 0 — or null; a filtered batch applies only where the mode was enabled with on & 4)
 bool int4_nomination_applies(const vg_index *idx, const float *d_queries, int64_t nq, int k, const uint8_t *mask);
@@ -67,12 +71,13 @@ int32_t launch_sq8_small_gemm(const uint16_t *qimg, int64_t cnt, int dim_pad, co
                               hipStream_t st);
 // k_pq_small.hip: the PQ append GEMM of one query tile gathered from the decoded codebook by the codes (cnt <= 128;
 // flat_gemm_pq_small_kernel) — whether a row of m sub-quantizers fits its LDS at all (m <= 318), and the launch (qimg: cnt x dim_pad
-// bfloat16; codes: n rows of m bytes, n m >= 16; cb16: NomImage::rows of a from_codes state; counts[q * count_stride]; cus: compute units)
+// bfloat16; codes: n rows of m bytes, n m >= 16; cb16: NomImage::rows of a from_codes state; counts[q * count_stride]; cus: compute units;
+// mask: a device row filter per query / for the batch (mask_stride 0), or null)
 bool pq_small_tile_fits(int m);
 bool pq_small_tile_takes(int m, int64_t n);  // fits, and n m >= 16: the one test of whether a batch of at most 128 queries runs the tile
 int32_t launch_pq_small_gemm(const uint16_t *qimg, int64_t cnt, int dim_pad, const uint8_t *codes, int64_t n, int m, const uint4 *cb16,
                              const float *norms, const float *thr, int thr_stride, int thr_off, int *counts, int count_stride, uint64_t *cand, int cap,
-                             int cus, hipStream_t st);
+                             int cus, hipStream_t st, const uint8_t *mask = nullptr, int64_t mask_stride = 0);
 
 // Builds the nomination state of n rows of dim elements into `img` (empty): its body of body_bytes (NomImage::body_bytes — the
 // decoded rows, or from_codes the decoded codebook), the norms and norm_max.  launch(const NomImage &, int *norm_max_bits) launches

@@ -3,7 +3,7 @@
 //     s = |x^|^2 - 2 q.x^,   q and the decoded row x^ both rounded to bfloat16 — the operands the image mode and the big
 // code-gathered tile multiply, bit for bit: the row operand is an entry of the decoded codebook (NomImage::rows of a from_codes
 // state, [dim_pad / 8][256] entries of 16 bytes, pq_codebook_bf16_kernel), the query operand gemm_operands' image.
-// Kept in a header so that tools/ubench can time the same code; launched by k_pq_small.hip.  L2, unfiltered, MODE 2 (append).
+// Kept in a header so that tools/ubench can time the same code; launched by k_pq_small.hip.  L2, MODE 2 (append); row filters: the last point below.
 //
 // The counterpart of vg_int4_small_gemm.hpp and vg_sq8_small_gemm.hpp — a single query tile, so a row is consumed by exactly one
 // wave, LDS holding the queries' image alone — with one difference that shapes it: there is nothing to convert.  With 8 dimensions
@@ -70,6 +70,36 @@
 //  * the epilogue is gemm_epilogue's append (vg_flat_gemm.hpp) as in both siblings: score = fma(-2, acc, |x^|^2), compared with
 //    the query's threshold (in LDS; -Inf for the padded queries of the last block: they never append), a returning atomic on the
 //    query's counter parked until the tile's end, the key make_key(score, row).
+//  * row filters (vg_index_enable_pq_nomination_from_codes' on & 4) are variants of their own, MASKED and BATCH template parameters:
+//    the unfiltered instantiations are the code they were (the same instructions but for one kernel-argument offset, the same
+//    registers: diffed against the ISA of the kernel without the parameters).
+//    Per-query filters (MASKED, not BATCH) — the K loop is untouched: a lane reads its query's bit only for a score that has passed
+//    the threshold, inside the branch that drains for the append's atomic anyway.  A launch of a host-side split gets the filter
+//    of ITS first query.
+//    BATCH — one filter for all queries.  A wave's 64 rows of a tile are 8 bytes of it; a slice whose 8 bytes are zero is never
+//    WALKED: no code load, no gather, no matrix instruction, no epilogue — and the gathers are what a pass costs.  After the image's
+//    barrier the four waves of a workgroup have nothing in common (no barrier, no LDS write), so each wave walks its OWN stream of
+//    (tile, chunk) positions over the tiles whose slice keeps a row; a wave without one leaves behind that barrier.  advance()
+//    runs two chunks ahead of the matrix instructions and must know the next such tile without waiting for a load, so the filter
+//    is held as a wave-uniform BITMAP of a WINDOW of the wave's tiles (PqsFilterWindows): one vector load, lane l the 8 bytes of
+//    the wave's slice in tile (64 w + l) of the workgroup's sequence (at any alignment; a slice that sticks out of the filter —
+//    the last tile's — reads the filter's last 8 bytes and shifts; the launch takes this variant from n = 64 up), a ballot of
+//    "not zero", and s_ff1_i32_b64 from the current position steps to the next tile: scalar work between two chunks.
+//    The window is 64 tiles, a lane each — one load instruction whatever the length, so the longest one a ballot holds: with
+//    G workgroups it covers 64 G tiles, which is every tile a wave ever has up to 12.6M rows at 768 workgroups: ONE filter load a wave
+//    and kernel, in the prologue.  Where a wave has more, the next window is loaded WHEN THE CURRENT ONE IS SPENT and waited for
+//    there, a drain of the ring once in 64 of the wave's tiles (384 chunks at m = 96, walked or not).  Loading it a window ahead,
+//    as flat_gemm_int4_small_kernel does with its windows of 8, was built first and read in the ISA: the load sits in the rare
+//    branch of advance(), the compiler lands it in a temporary and copies it to the window's register behind the branch's merge,
+//    with s_waitcnt vmcnt(0) in front of the copy — on EVERY way through the merge, i.e. a drain at every tile's end, what the
+//    do-while above exists to avoid.  As built: the ways through advance() that stay inside a window have no vector-memory
+//    operation and no wait; the K loop's waits are vmcnt(17) / vmcnt(16) as unfiltered; vmcnt(0) stands behind the window's load
+//    alone (and at the appends).  Past its end the stream repeats the first chunk of the tile it is on — the last one it walked,
+//    in range — never a skipped slot.  A walked slice's rows still test their own bit: the two filter bytes with a lane's rows'
+//    bits are loaded beside the tile's norms (the epilogue's first wait is vmcnt(19) as before: both are older than everything
+//    in flight) and stand beside `row < n`; bits at or past n can make the last slice walked, never a row appended.
+//    Registers (profiles/kernel_resources.txt): 150 / 192 / 226 / 256 VGPRs BATCH, 150 / 192 / 224 / 256 per query, no AGPRs, no
+//    scratch, the unfiltered occupancy.  Measured: the comment above kPqNomCodesMaskedMinPairs (k_pq_nominate.hip).
 // The error bound (pq_nominate_eps, k_pq_nominate.hip).  The operands are the image's bit for bit, so the bfloat16 term
 // (2^-7 + 2^-16)(|q|^2 + |x^|^2) is the image mode's; what differs is the sum's order and start.  The formula allows 4 dim u
 // (|q|^2 + |x^|^2), u = 2^-24, for "the GEMM's fp32 accumulation and the norm's".  This tile starts at ZERO and adds dim products
@@ -92,6 +122,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <type_traits>
 
 #include "vg_device.hpp"
 #include "vg_flat_gemm.hpp"
@@ -119,16 +150,83 @@ __device__ __forceinline__ uint4 pq_small_shr_bytes(uint4 v, uint32_t s)
     return make_uint4(a0, a1, a2, a3);
 }
 
+// The batch filter as one wave of flat_gemm_pq_small_kernel<RB, true, true> reads it (see the header): the wave's tiles by ordinal
+// i (tile first + i G, i < mine), the wave's 8 filter bytes of 64 of them a window, one tile a lane, kept as a wave-uniform bitmap
+// of the slices that keep a row.  Only that variant has one; the others hold a PqsNoFilter.
+constexpr int kPqsWindow = 64;
+struct PqsNoFilter {};
+struct PqsFilterWindows {
+    const uint8_t *mask;
+    int64_t mask_bytes;  // (n + 7) / 8 >= 8: the launch's condition for this variant
+    int first, G, wave, lane, mine;
+    uint64_t live;  // bit l: ordinal kPqsWindow win_at + l keeps a row (wave-uniform; clear from `mine` on)
+    int win_at;
+    // lane l: where the 8 filter bytes of this wave's rows in the tile of ordinal kPqsWindow w + l start
+    __device__ __forceinline__ int64_t slice_at(int w) const
+    {
+        return (first + (static_cast<int64_t>(kPqsWindow) * w + lane) * G) * (kPqsBN / 8) + wave * 8;
+    }
+    // ... the load of them: unconditional, 8 bytes at any alignment, and never outside the filter — a slice that ends past it (the
+    // last tile's, or an ordinal that is no tile) reads the filter's last 8 bytes
+    __device__ __forceinline__ uint64_t load_window(int w) const
+    {
+        const int64_t at = slice_at(w), last = mask_bytes - 8;
+        uint64_t v;
+        __builtin_memcpy(&v, mask + (at > last ? last : at), 8);
+        return v;
+    }
+    // ... and the slice's 64 bits from what was loaded: shifted down where the address was clamped, zeros coming in; zeros for an
+    // ordinal from `mine` on
+    __device__ __forceinline__ uint64_t window_bits(int w, uint64_t v) const
+    {
+        const int64_t at = slice_at(w), last = mask_bytes - 8, over = at > last ? at - last : 0;
+        v = over >= 8 ? 0 : v >> (8 * over);
+        return static_cast<int64_t>(kPqsWindow) * w + lane < mine ? v : 0;
+    }
+    // the next window becomes the current one: loaded and waited for here, the one place where the stream drains for the filter
+    __device__ __forceinline__ void enter()
+    {
+        win_at++;
+        live = __ballot(window_bits(win_at, load_window(win_at)) != 0);
+    }
+    // the first ordinal >= i (in window win_at or behind it; i <= the window's end + 1) whose slice keeps a row; `mine`: none
+    __device__ __forceinline__ int next_live(int i)
+    {
+        if (i >= mine) return mine;
+        if (i / kPqsWindow == win_at) {
+            const uint64_t m = live & (~uint64_t(0) << (i % kPqsWindow));
+            if (m != 0) return win_at * kPqsWindow + __builtin_ctzll(m);
+        }
+        do {  // the windows behind it, until one keeps a row
+            if ((win_at + 1) * kPqsWindow >= mine) return mine;
+            enter();
+        } while (live == 0);
+        return win_at * kPqsWindow + __builtin_ctzll(live);
+    }
+    // window 0 loaded; the wave's first live ordinal
+    __device__ __forceinline__ int init(const uint8_t *mask_, int64_t n, int ntiles, int G_, int wave_, int lane_)
+    {
+        mask = mask_, mask_bytes = (n + 7) >> 3, first = static_cast<int>(blockIdx.x), G = G_, wave = wave_, lane = lane_;
+        mine = (ntiles - first + G - 1) / G;
+        win_at = -1;
+        enter();
+        return next_live(0);
+    }
+};
+
 // queries: nq x dim_pad bfloat16 (gemm_operands' image, the tail from dim on zeros), nq <= 32 RB, dim_pad >= 16 steps; codes: n rows
 // of m bytes, n m >= 16; cb16: the decoded codebook, at least 2 steps slices of 256 entries; counts: counts[q * count_stride];
-// cand: cap keys a query
-template <int RB>
+// cand: cap keys a query; MASKED: mask, a bit per row, (n + 7) / 8 bytes at any alignment — BATCH: one for all queries (n >= 64: 8
+// bytes of it exist), otherwise query q's at mask + q * mask_stride (a stride of 0: one for all, without the skip)
+template <int RB, bool MASKED = false, bool BATCH = false>
 __global__ __launch_bounds__(kPqsThreads) void flat_gemm_pq_small_kernel(
     const uint16_t *__restrict__ queries, int nq, int dim_pad, const uint8_t *__restrict__ codes, int64_t n, int m,
     const uint4 *__restrict__ cb16, const float *__restrict__ norms, const float *__restrict__ thr, int thr_stride, int thr_off,
-    int *__restrict__ counts, int count_stride, uint64_t *__restrict__ cand, int cap)
+    int *__restrict__ counts, int count_stride, uint64_t *__restrict__ cand, int cap, const uint8_t *__restrict__ mask, int64_t mask_stride)
 {
     static_assert(RB >= 1 && RB <= 4, "one to four blocks of 32 queries");
+    static_assert(MASKED || !BATCH, "a batch filter is a filter");
+    constexpr bool SKIP = MASKED && BATCH;
     constexpr int QB = RB * 32, D = kPqsDepth;
     extern __shared__ float gemm_lds[];
     const int ntiles = static_cast<int>((n + kPqsBN - 1) / kPqsBN), G = static_cast<int>(gridDim.x);
@@ -186,13 +284,27 @@ __global__ __launch_bounds__(kPqsThreads) void flat_gemm_pq_small_kernel(
             dst[j] = slice[ent_h + code];
         }
     };
+    // SKIP: the wave's tiles by ordinal (tile blockIdx.x + ordinal G) and the filter's windows over them; otherwise an empty struct.
+    // ord1: the ordinal of the tile the stream is on — fw.mine: the stream has ended
+    std::conditional_t<SKIP, PqsFilterWindows, PqsNoFilter> fw;
+    int ord1 = 0;
+    if constexpr (SKIP) {
+        ord1 = fw.init(mask, n, ntiles, G, wave, lane);
+        if (ord1 >= fw.mine) return;  // (the wave alone: there is no barrier behind the image's)
+    }
     // the stream's next position behind (t, c): the next chunk, the next tile's first, past the end the last tile's first again
+    // (SKIP: the wave's next tile whose slice keeps a row; past the end the tile it is on — a walked one, in range — again)
     auto advance = [&](int &t, int &c) {
         if (c + 1 < nchunks) {
             c++;
         } else {
             c = 0;
-            t = t + G < ntiles ? t + G : ntiles - 1;
+            if constexpr (SKIP) {
+                ord1 = fw.next_live(ord1 + 1);
+                if (ord1 < fw.mine) t = static_cast<int>(blockIdx.x) + ord1 * G;
+            } else {
+                t = t + G < ntiles ? t + G : ntiles - 1;
+            }
         }
     };
 
@@ -200,7 +312,9 @@ __global__ __launch_bounds__(kPqsThreads) void flat_gemm_pq_small_kernel(
     uint4 ring[D][2], cur[2], nxt[2];
     // the stream's start: the codes of position 0 and its gathers, the codes of position 1
     int t1 = static_cast<int>(blockIdx.x), c1 = 0;  // the position whose gathers are issued next
+    if constexpr (SKIP) t1 += ord1 * G;
     const int c0 = c1;
+    int t = t1, ord = ord1;  // the tile that is computed, SKIP: and its ordinal
     load_codes(t1, c1, nxt);
     take_codes(t1, c1, nxt, cur);
     advance(t1, c1);
@@ -212,7 +326,13 @@ __global__ __launch_bounds__(kPqsThreads) void flat_gemm_pq_small_kernel(
         gather(c0, p, cur, ring[p]);
         __builtin_amdgcn_sched_barrier(0);  // (in the ring's order: the K loop waits for its slots by count)
     }
-    for (int t = static_cast<int>(blockIdx.x); t < ntiles; t += G) {
+    auto more = [&]() {
+        if constexpr (SKIP)
+            return ord < fw.mine;
+        else
+            return t < ntiles;
+    };
+    while (more()) {
         const int64_t n0 = static_cast<int64_t>(t) * kPqsBN + wave * 64;
         // the tile's norms: two loads ahead of the tile's first chunk (its first steps wait two loads deeper than the ring asks), and
         // older than everything in flight when the epilogue reads them
@@ -222,6 +342,16 @@ __global__ __launch_bounds__(kPqsThreads) void flat_gemm_pq_small_kernel(
             const int64_t nn = n0 + j * 32 + r;
             xn[j] = norms[nn < n ? nn : n - 1];
         }
+        // SKIP: the filter's bytes with the rows' bits, beside the norms and as old as they are when the epilogue reads them
+        uint32_t fbyte[2] = {0xFFu, 0xFFu};
+        if constexpr (SKIP) {
+#pragma unroll
+            for (int j = 0; j < 2; j++) {
+                const int64_t nn = n0 + j * 32 + r;
+                fbyte[j] = mask[(nn < n ? nn : n - 1) >> 3];
+            }
+        }
+        int t_next = t + G, ord_next = 0;  // SKIP: the position behind the tile's last chunk
 #pragma unroll
         for (int b = 0; b < RB; b++)
 #pragma unroll
@@ -233,6 +363,7 @@ __global__ __launch_bounds__(kPqsThreads) void flat_gemm_pq_small_kernel(
             // (t1, c1) is the position behind (t, c): its codes have been in flight for a chunk; the position behind it is loaded now
             take_codes(t1, c1, nxt, cur);
             const int cg = c1;
+            if constexpr (SKIP) t_next = t1, ord_next = ord1;
             advance(t1, c1);
             __builtin_amdgcn_sched_barrier(0);
             load_codes(t1, c1, nxt);
@@ -272,7 +403,7 @@ __global__ __launch_bounds__(kPqsThreads) void flat_gemm_pq_small_kernel(
 #pragma unroll
         for (int j = 0; j < 2; j++) {
             const int64_t nn = n0 + j * 32 + r;
-            const bool row_ok = nn < n;
+            const bool row_ok = nn < n && (!SKIP || ((fbyte[j] >> (nn & 7)) & 1u));
 #pragma unroll
             for (int b = 0; b < RB; b++) {
                 // a block's 16 scores and compares with no branch between them; only a block in which something passed looks again
@@ -295,6 +426,8 @@ __global__ __launch_bounds__(kPqsThreads) void flat_gemm_pq_small_kernel(
                         const int q = b * 32 + (e & 3) + 8 * (e >> 2) + hv;
                         asm volatile("" : "+v"(sc[e]));  // (compared again here: 16 lane masks kept per block spill the scalar registers)
                         if (!(sc[e] < tq[e]) || q >= nq) continue;
+                        if constexpr (MASKED && !BATCH)  // (only now: for the few scores that passed)
+                            if (!mask_bit(mask + static_cast<int64_t>(q) * mask_stride, nn)) continue;
                         if (parked) store_parked();
                         park_pos = atomicAdd(&counts[static_cast<int64_t>(q) * count_stride], 1);
                         park_q = q;
@@ -305,6 +438,7 @@ __global__ __launch_bounds__(kPqsThreads) void flat_gemm_pq_small_kernel(
             }
         }
         if (parked) store_parked();
+        t = t_next, ord = ord_next;
     }
 }
 
