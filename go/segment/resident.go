@@ -702,6 +702,18 @@ func (r *Resident) EnableSQ8NominationFromCodesSmallBatches() error {
 	return hipctx.Err(int32(C.vg_index_enable_sq8_nomination_from_codes(r.h, C.int32_t(2), nil)))
 }
 
+// EnableSQ8NominationFromCodesFiltered: the nomination from the codes with whole-segment batches under a row filter (one per query,
+// or one for the batch; L2 and Dot) taken too — mode 6, or 7 with smallBatches (on | 4) — within what the mode allows and from the
+// filtered crossovers up; a batch filter lets a wave of the one-query-tile GEMM skip the 64-row code tiles it empties.  Nothing more
+// is resident; results unchanged.
+func (r *Resident) EnableSQ8NominationFromCodesFiltered(smallBatches bool) error {
+	v := C.int32_t(5)
+	if smallBatches {
+		v = 6
+	}
+	return hipctx.Err(int32(C.vg_index_enable_sq8_nomination_from_codes(r.h, v, nil)))
+}
+
 // SQ8NominationInfo: mode 0 (off), 1 (the dequantised-row image), 2 (from the codes) or 3 (from the codes, small batches too), the device bytes the mode keeps resident,
 // and the queries whose proof failed and the scan answered since the mode was enabled.
 func (r *Resident) SQ8NominationInfo() (mode int, heldBytes, rescanned int64, err error) {

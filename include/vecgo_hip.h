@@ -1699,14 +1699,21 @@ int32_t vg_index_pq_nomination_info(const vg_index *idx, int32_t *mode, int64_t 
  * vg_search_sq8, L2 or Dot, unfiltered, MORE THAN 128 queries, k <= 256, rows > k, 16-byte aligned device queries, and queries x
  * rows at or above its crossover against the scan (README, Limits); filtered batches, probed partitions and smaller batches keep
  * the scan, with the same results.
- * on == 2 (any other non-zero value is 1): the same, and unfiltered whole-segment batches of 5 .. 128 queries take the nomination
- * too, under the same conditions and dim <= 2528, from their own crossover up — on a GEMM of one query tile whose waves read the
- * code tiles from global memory straight into the matrix instruction's registers, the queries' image resident in LDS (97 .. 128
- * queries from dim 609 on run as two launches of two 32-query blocks).  Nothing more is resident; vg_index_sq8_nomination_info
- * reports mode 3.  Still the scan's: filtered batches, probed partitions, fewer than 5 queries, k > 256.  Found by symbol lookup. */
+ * `on` is read as bits.  on & 3 == 2 (1, 3 and a negative value are 1): the same, and unfiltered whole-segment batches of 5 .. 128
+ * queries take the nomination too, under the same conditions and dim <= 2528, from their own crossover up — on a GEMM of one query
+ * tile whose waves read the code tiles from global memory straight into the matrix instruction's registers, the queries' image
+ * resident in LDS (97 .. 128 queries from dim 609 on run as two launches of two 32-query blocks).  Nothing more is resident;
+ * vg_index_sq8_nomination_info reports mode 3.
+ * on & 4 (on == 5 or 6; reported as mode 6 or 7): whole-segment batches under a row filter — vg_search_flat_filtered and
+ * vg_segment_search with VG_SCAN_SQ8, one filter per query or one for the batch, L2 or Dot — take the nomination too, within what
+ * on & 3 allows and from the filtered crossovers up (README, Limits): above 128 queries the filter bit is read where a row would be
+ * appended; up to 128 a batch filter lets a wave skip every 64-row code tile it empties — those bytes are never loaded — and one
+ * filter per query is read behind the threshold.  A query whose proof fails is searched again under its own filter.  Without the
+ * flag (on == 1, 2) a filtered batch keeps the scan as before.  on == 4 (a flag without a mode) and on > 6 are VG_ERR_INVALID_ARG,
+ * the state as it was.  Still the scan's: probed partitions, fewer than 5 queries, k > 256.  Found by symbol lookup. */
 int32_t vg_index_enable_sq8_nomination_from_codes(vg_index *idx, int32_t on, void *stream);
 /* Which SQ8 nomination an index holds and what it does: *mode = 0 (off), 1 (the image: vg_index_enable_sq8_nomination), 2 (from
- * the codes) or 3 (from the codes, enabled with on == 2); *held_bytes = the device memory the mode keeps resident; *rescanned = the queries, since the mode was enabled, whose
+ * the codes), 3 (from the codes, enabled with on == 2) or 6 / 7 (those two enabled with on & 4: filtered batches too); *held_bytes = the device memory the mode keeps resident; *rescanned = the queries, since the mode was enabled, whose
  * proof failed and which the scan answered (0 when off).  Any pointer may be NULL.  Found by symbol lookup. */
 int32_t vg_index_sq8_nomination_info(const vg_index *idx, int32_t *mode, int64_t *held_bytes, int64_t *rescanned);
 /* vg_search_rabitq batches through an int8 matrix-core nomination.  A Hamming distance is a dot product of +-1 vectors: the GEMM

@@ -685,7 +685,10 @@ public:
     void EnableSQ8NominationFromCodes(bool on = true) { check(vg_index_enable_sq8_nomination_from_codes(h_, on ? 1 : 0, nullptr)); }
     // the same, and unfiltered whole-segment batches of 5 .. 128 queries (dim <= 2528) take the nomination too (mode 3)
     void EnableSQ8NominationFromCodesSmallBatches() { check(vg_index_enable_sq8_nomination_from_codes(h_, 2, nullptr)); }
-    // mode: 0 off, 1 the image, 2 from the codes, 3 from the codes with small batches; held_bytes: the device memory the mode keeps resident; rescanned: queries whose
+    // the same with filtered batches (on | 4, modes 6 and 7): SearchFiltered batches with VG_SCAN_SQ8 over the whole segment, one filter
+    // per query or one for the batch, L2 and Dot, take the nomination too — above 128 queries, and with small_batches 5 .. 128
+    void EnableSQ8NominationFromCodesFiltered(bool small_batches = false) { check(vg_index_enable_sq8_nomination_from_codes(h_, small_batches ? 6 : 5, nullptr)); }
+    // mode: 0 off, 1 the image, 2 from the codes, 3 from the codes with small batches, 6 / 7 those with filtered batches; held_bytes: the device memory the mode keeps resident; rescanned: queries whose
     // proof failed and the scan answered, since the mode was enabled
     struct SQ8Nomination {
         int32_t mode;

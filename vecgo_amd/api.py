@@ -1051,18 +1051,21 @@ class Index:
         scores stay bit-identical."""
         check(self._lib.vg_index_enable_sq8_nomination(self._h, C.c_int32(1 if on else 0), _stream_ptr(stream)))
 
-    def enable_sq8_nomination_from_codes(self, on: bool = True, small_batches: bool = False, stream=None):
+    def enable_sq8_nomination_from_codes(self, on: bool = True, small_batches: bool = False, filtered: bool = False, stream=None):
         """vg_index_enable_sq8_nomination_from_codes: the same nomination without the image of the dequantised rows — the queries are
         scaled by the inverse scales and the GEMM's row tiles converted from the code tiles, bf16(code - 128), exact (whole-segment,
         unfiltered batches above 128 queries, from queries x rows >= 12M).  small_batches (on = 2, reported as mode 3): unfiltered
         batches of 5 .. 128 queries take it too (dim <= 2528), on a tile that reads the code tiles straight into the matrix unit's
-        registers.  Resident: 4 bytes a row and 4 a dimension.  Exclusive with enable_sq8_nomination; ids and scores stay
-        bit-identical."""
-        check(self._lib.vg_index_enable_sq8_nomination_from_codes(self._h, C.c_int32((2 if small_batches else 1) if on else 0), _stream_ptr(stream)))
+        registers.  filtered (on | 4: modes 6 and 7): search_flat_filtered batches with scan = SQ8 over the whole segment, L2 or
+        Dot — one filter per query or one for the batch — take it too, within what the mode allows and from the filtered
+        crossovers up; a batch filter lets a wave of the small tile skip the 64-row code tiles it empties.  Resident: 4 bytes a row
+        and 4 a dimension.  Exclusive with enable_sq8_nomination; ids and scores stay bit-identical."""
+        mode = ((2 if small_batches else 1) | (4 if filtered else 0)) if on else 0
+        check(self._lib.vg_index_enable_sq8_nomination_from_codes(self._h, C.c_int32(mode), _stream_ptr(stream)))
 
     def sq8_nomination_info(self):
         """vg_index_sq8_nomination_info: (mode, held_bytes, rescanned) — mode 0 off, 1 the dequantised-row image, 2 from the codes, 3 from
-        the codes with small batches;
+        the codes with small batches, 6 / 7 those two with filtered batches;
         held_bytes the device memory the mode keeps resident; rescanned the queries whose proof failed since it was enabled."""
         mode, held, rescanned = C.c_int32(0), C.c_int64(0), C.c_int64(0)
         check(self._lib.vg_index_sq8_nomination_info(self._h, C.byref(mode), C.byref(held), C.byref(rescanned)))

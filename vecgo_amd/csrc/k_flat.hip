@@ -268,7 +268,7 @@ static int32_t launch_gemm_t(const GemmArgs &a)
                 if (a.counts_wide) VG_HIP(hipMemsetAsync(a.counts_wide, 0, sizeof(int) * static_cast<size_t>(c.cnt) * kCountLine, st));
                 VG_TRY(launch_sq8_small_gemm<DOT>(reinterpret_cast<const uint16_t *>(a.queries), c.cnt, 2 * c.ops.dim_words, a.codes, c.ops.n, a.code_m,
                                                   c.ops.norms, a.thr, a.thr_stride, a.thr_off, a.counts_wide ? a.counts_wide : a.counts,
-                                                  a.counts_wide ? kCountLine : 1, a.cand, a.cap, a.cus, st));
+                                                  a.counts_wide ? kCountLine : 1, a.cand, a.cap, a.cus, st, c.mask, c.mask_stride));
                 if (a.counts_wide)
                     VG_LAUNCH(counts_narrow_kernel, dim3(static_cast<unsigned>((c.cnt + 255) / 256)), dim3(256), 0, st, a.counts_wide, c.cnt, a.counts);
                 return VG_OK;
@@ -610,8 +610,11 @@ __global__ __launch_bounds__(64) void flat_thr_cap_kernel(float *__restrict__ th
 // the sample left it.  In place, the cap hides "no threshold" from the verify pair (vg_nominate.hpp): a query whose filter leaves the
 // sample fewer than sel_k rows has every kept row appended — a COMPLETE list, which the pair accepts as it is (tq == +Inf) — but
 // after the cap it looked like a threshold to prove against, and a list of fewer than k rows, or one whose k-th score lies within
-// the margin of the (huge) bound, failed the proof and went to the scan: every query of a selective filter.  The filtered INT4
-// and PQ nominations from the codes (flat_nominate_bf16 with a mask) take this one; every other call takes the kernel above, as it did.
+// the margin of the (huge) bound, failed the proof and went to the scan: every query of a selective filter.  The filtered
+// nominations from the codes (INT4, SQ8, PQ: flat_nominate_bf16 with a mask) take this one; every other call takes the kernel above,
+// as it did.  Nothing here or in the pair's complete-list path depends on the metric: the bound lies above every row's |score| for
+// L2 and Dot alike (Dot scores are -q.x, ascending as L2's), and "no threshold" is +Inf for both — SQ8 from the codes is the one
+// mode that brings Dot here.
 __global__ __launch_bounds__(64) void flat_thr_cap_gemm_kernel(const float *__restrict__ thr, int sel_k, const float *__restrict__ queries, int dim,
                                                                const float *__restrict__ norm_max, float *__restrict__ gemm_thr)
 {
@@ -1593,7 +1596,7 @@ __global__ void pq_sample_rows_kernel(const uint8_t *__restrict__ codes, int64_t
     out[c * granules + j] = cb16[static_cast<int64_t>(j) * 256 + code];
     if (j == 0) norms_c[c] = norms[row];
 }
-// The SQ8 nomination from the codes (img.scale: vg_index_enable_sq8_nomination_from_codes, k_sq8_scan.hip; L2 and Dot, unfiltered)
+// The SQ8 nomination from the codes (img.scale: vg_index_enable_sq8_nomination_from_codes, k_sq8_scan.hip; L2 and Dot; filtered too: sample_mask_gather_kernel)
 // likewise: the queries' image is bf16(q_d inv_d), the append GEMM converts its row tiles from the code tiles
 // (flat_gemm_sq8_big_kernel), and the sampled tiles are converted here the same way — bf16(code - 128), exact — so that sample and
 // append score in one space, s' = |x^|^2 - 2 (q o inv).(c - 128) (Dot: -(q o inv).(c - 128)), and the thresholds need no shift.
@@ -1665,9 +1668,9 @@ struct NominateScratch : NomScratch {
     int64_t rows_c;   // from the codes: the sampled tiles' rows (0: an image, or too few rows for a sample) ...
     uint16_t *srows;  // ... decoded, dim_pad each ...
     float *snorms;    // ... and their norms
-    // `masks` row filters (0 none, 1 the batch's, cnt one per query) on a from-codes nomination that takes them (INT4, PQ:
-    // NomImage::codes_take_filters): the filters over the compact rows (sample_mask_gather_kernel; cbytes each, 0 without a sample)
-    // and the GEMM's own capped thresholds (flat_thr_cap_gemm_kernel)
+    // `masks` row filters (0 none, 1 the batch's, cnt one per query) on a nomination from the codes (INT4, SQ8, PQ): the filters
+    // over the compact rows (sample_mask_gather_kernel; cbytes each, 0 without a sample) and the GEMM's own capped thresholds
+    // (flat_thr_cap_gemm_kernel)
     uint8_t *cmask;
     int64_t cbytes;
     float *gthr;
@@ -1681,7 +1684,7 @@ struct NominateScratch : NomScratch {
         c.take(srows, rows_c * img.dim_pad);
         c.take(snorms, rows_c);
         // (Carve::take hands out a pointer for a count of zero too: what another call has not got is null)
-        const bool filtered = masks && img.codes_take_filters();
+        const bool filtered = masks && img.from_codes;
         cbytes = filtered ? (rows_c + 7) / 8 : 0;
         cmask = nullptr, gthr = nullptr;
         if (cbytes) c.take(cmask, masks * cbytes);
@@ -1699,7 +1702,6 @@ int32_t flat_nominate_bf16(vg_index *idx, const NomImage &img, bool dot, const f
 {
     const int64_t masks = !mask ? 0 : mask_stride ? cnt : 1;
     const NominateScratch s(scratch, cnt, idx->n, img, k, masks);
-    VG_CHECK(!mask || !img.from_codes || img.codes_take_filters(), VG_ERR_INVALID_ARG, "flat_nominate_bf16: a filter on a from-codes mode without one");
     NomCall nc{st, dot, {}, cnt, mask, mask_stride};
     // (from the codes the GEMM's "rows" are the codebook; n, the row length and the norms are the decoded rows')
     VG_TRY(gemm_operands(queries, cnt, idx->dim, idx->n, img.norms, img.rows, img.dim_pad, s.qbf, st, &nc.ops, img.scale));
@@ -1724,6 +1726,7 @@ int32_t flat_nominate_bf16(vg_index *idx, const NomImage &img, bool dot, const f
                   reinterpret_cast<const uint4 *>(idx->d_sq_tiles), idx->sq_groups, groups_pad, img.norms, s.rows_c, kFlatSampleStride,
                   reinterpret_cast<uint4 *>(s.srows), s.snorms);
         sc.ops.b = reinterpret_cast<const float *>(s.srows), sc.ops.n = s.rows_c, sc.ops.norms = s.snorms;
+        if (mask) VG_TRY(sample_filter());
     } else if (s.rows_c) {
         const int granules = img.dim_pad / 8;
         VG_LAUNCH(pq_sample_rows_kernel, dim3(static_cast<unsigned>((s.rows_c * granules + 255) / 256)), dim3(256), 0, st, idx->d_pq_rows, idx->n,
@@ -1733,7 +1736,7 @@ int32_t flat_nominate_bf16(vg_index *idx, const NomImage &img, bool dot, const f
         if (mask) VG_TRY(sample_filter());
     }
     VG_TRY(sample_thresholds(sc, s, s.rows_c ? 1 : kFlatSampleStride, nom->sel_k, nom->thr, idx->n > kFlatCap));
-    if (s.gthr)  // (a filtered nomination from INT4 or PQ codes: nom->thr keeps its +Inf for the verify pair)
+    if (s.gthr)  // (a filtered nomination from the codes: nom->thr keeps its +Inf for the verify pair — L2 and Dot alike, see the kernel)
         VG_LAUNCH(flat_thr_cap_gemm_kernel, dim3(nc.ucnt()), dim3(64), 0, st, nom->thr, nom->sel_k, queries, idx->dim, img.norm_max, s.gthr);
     else
         VG_LAUNCH(flat_thr_cap_kernel, dim3(nc.ucnt()), dim3(64), 0, st, nom->thr, nom->sel_k, queries, idx->dim, img.norm_max);

@@ -592,15 +592,46 @@ constexpr int64_t kSq8NomCodesMinPairs = 12000000;
 // mode it is 0.56x .. 0.90x of the time up to 96 queries and 1.05x .. 1.13x at 128 (two launches).  Test hook
 // VG_SQ8_NOM_CODES_ALWAYS: any.
 constexpr int64_t kSq8NomCodesSmallMinPairs = 3200000;
-// whether a batch takes the nomination (vg_index_enable_sq8_nomination, _from_codes; device queries; mask: the batch's row filter, or null)
+// The same for FILTERED batches from the codes (on & 4, NomImage::sq8_masked; a filter per query or one for the batch): above 128
+// queries the big tile with the filter in its epilogue, 5 .. 128 queries the small tile's MASKED variants (on & 3 == 2).  A filter
+// makes the scan cheaper and the nomination mostly dearer, so these stand apart from the constants above.
+// Measured (MI355X, tools/sq8_nominate_codes_time.py 1000000 filtered, dim 768, k = 10, L2, ms per call, filtered scan / filtered
+// nomination, alternating windows of ~200 ms in one run on one index, the median of 5, the windows of a leg within 1 % of each other
+// (3 % at 129 x 100k, 1 %); profiles/sq8_nominate_codes_time_filtered.txt), a batch filter keeping 100 % / 10 % / 1 % of the rows, then
+// one per query keeping 10 %; bits equal and no query rescanned in any line.
+// Above 128 queries (the big tile): 129 x 100k: 1.089 / 0.277, 0.979 / 0.326, 0.699 / 0.353, 0.982 / 0.301; 1024 x 100k: 5.694 /
+// 0.527, 5.459 / 0.686, 3.353 / 0.759, 5.453 / 0.666; 129 x 1M: 9.068 / 0.571, 9.012 / 0.678, 4.629 / 0.860, 8.987 / 0.767; 1024 x
+// 1M: 50.89 / 1.764, 50.18 / 2.127, 26.20 / 2.923, 50.37 / 2.614 (k = 100, 10 %: 104.1 / 3.504; Dot, 10 % and per query: 108.9 /
+// 2.055, 109.1 / 2.524).  Won everywhere, 1.98x at the least (129 x 100k, 1 %).  The scan gets up to 49 % faster at 1 % kept, the
+// big tile up to 75 % slower (its GEMM at 1024 x 1M 1.501 -> 1.833 -> 2.631 ms: thresholds from a hundredth of the sample pass more
+// rows, and every pass reads a filter bit), as for INT4 and PQ.  The constant is the smallest measured product, 129 x 100k; nothing
+// between 12M and 12.9M pairs was measured.
+// 5 .. 128 queries (the small tile), 100k rows: 8 queries 0.268 / 0.186, 0.200 / 0.182, 0.170 / 0.179, 0.191 / 0.177 — LOST at 1 %
+// kept (0.95x) and within 10 % elsewhere: 0.8M pairs keep the scan; 32: 0.394 / 0.191, 0.320 / 0.190, 0.273 / 0.190, 0.315 / 0.197;
+// 128: 1.055 / 0.270, 0.948 / 0.283, 0.688 / 0.296, 0.944 / 0.325 — won 1.44x .. 3.91x.  1M rows: 8: 0.746 / 0.340, 0.674 / 0.339,
+// 0.539 / 0.272, 0.669 / 0.337; 32: 1.934 / 0.345, 1.860 / 0.346, 1.213 / 0.279, 1.857 / 0.350 (Dot, 10 % and per query: 4.138 /
+// 0.348, 4.156 / 0.359); 128: 7.019 / 0.565, 6.946 / 0.579, 3.887 / 0.502, 6.975 / 0.794 — won 1.98x .. 12.4x.  The constant is the
+// smallest measured product that won under every filter, 32 x 100k, with nothing between 0.8M and 3.2M pairs measured: as unfiltered.
+// What the skip of emptied code tiles buys (the GEMM's scope, 1M rows, 100 % / 10 % / 1 % kept): 8 queries 0.178 / 0.176 / 0.112 ms,
+// 32 queries 0.180 / 0.183 / 0.115, 128 queries (two launches) 0.380 / 0.391 / 0.317: at 1 % kept 53 % of the 64-row code tiles are
+// empty and a one-launch pass costs 36 % less — the tile is HBM-bound and those bytes are not read; at 10 % one tile in 850 is empty
+// and nothing changes.  One filter per query has no skip and reads a bit for every score under its threshold: 0.182 at 32 queries,
+// 0.600 at 128.  Over 100k rows (391 row tiles for 256 or 512 workgroups: a workgroup has one tile or two, a skipped code tile shortens next to nothing)
+// the 1 % filter makes the pass dearer at 128 queries, 0.105 -> 0.134 ms, by the appends its looser thresholds let through.
+constexpr int64_t kSq8NomCodesMaskedMinPairs = 12900000;
+constexpr int64_t kSq8NomCodesMaskedSmallMinPairs = 3200000;
+// whether a batch takes the nomination (vg_index_enable_sq8_nomination, _from_codes; device queries; mask: the batch's row filter, per
+// query or one for all, or null — from the codes a filtered batch only where the mode was enabled with on & 4)
 bool sq8_nomination_applies(const vg_index *idx, const float *d_queries, int64_t nq, int k, const uint8_t *mask)
 {
     const int mode = idx->sq_nom.mode();
-    if (mode == 2 && nq <= 128) {
-        if (mask || !idx->sq_nom.sq8_small || !sq8_small_tile_fits(idx->dim)) return false;
-        if (nq * idx->n < kSq8NomCodesSmallMinPairs && !hook(kHookSq8NomCodesAlways)) return false;
-    } else if (mode == 2 && (mask || (nq * idx->n < kSq8NomCodesMinPairs && !hook(kHookSq8NomCodesAlways)))) {
-        return false;
+    if (mode == 2) {
+        if (mask && !idx->sq_nom.sq8_masked) return false;
+        const bool small = nq <= 128;  // the small tile's batches, where it was enabled and takes the rows
+        if (small && (!idx->sq_nom.sq8_small || !sq8_small_tile_fits(idx->dim))) return false;
+        const int64_t min_pairs = small ? (mask ? kSq8NomCodesMaskedSmallMinPairs : kSq8NomCodesSmallMinPairs)
+                                        : (mask ? kSq8NomCodesMaskedMinPairs : kSq8NomCodesMinPairs);
+        if (nq * idx->n < min_pairs && !hook(kHookSq8NomCodesAlways)) return false;
     }
     return mode && nq >= VG_SQ8_NOM_MIN_Q && k <= kNomMaxK && idx->n > k && aligned16(d_queries);
 }
@@ -680,11 +711,13 @@ int32_t sq8_nan_replay(vg_index *idx, const float *d_queries, int64_t nq, int k,
 }  // namespace vg
 
 // vg_index_enable_sq8_nomination (mode 1) and vg_index_enable_sq8_nomination_from_codes (mode 2); fn: the entry point's name.
-// As for PQ (k_pq_nominate.hip): turning a mode off, or on again, drops that mode only; turning it on drops the other one too, but
-// only once nothing can refuse.
+// Mode 2 reads `on` as bits, as for PQ (k_pq_nominate.hip): on & 3 == 2: small batches too, on & 4: filtered batches too — of a mode,
+// so 4 alone is none.  Turning a mode off, or on again, drops that mode only; turning it on drops the other one too, but only once
+// nothing can refuse.
 static int32_t sq8_nomination_enable(vg_index *idx, int mode, int32_t on, void *stream, const char *fn)
 {
     VG_CHECK(idx, VG_ERR_INVALID_ARG, "%s: NULL index", fn);
+    VG_CHECK(mode != 2 || (on != 4 && on <= 6), VG_ERR_INVALID_ARG, "%s: on=%d is a flag without a mode, or above 6", fn, on);
     VG_HIP(hipSetDevice(idx->ctx->device));
     hipStream_t st = vg::pick_stream(idx->ctx, stream);
     if (idx->sq_nom.mode() == mode) VG_TRY(vg::nom_free(idx->sq_nom, st));
@@ -707,7 +740,8 @@ static int32_t sq8_nomination_enable(vg_index *idx, int mode, int32_t on, void *
                            norm_max_bits);
     }));
     idx->sq_nom.scale = idx->sq->d_inv;  // (the quantizer's: it outlives its codes on the index, vg_index_set_sq8_codes)
-    idx->sq_nom.sq8_small = on == 2;
+    idx->sq_nom.sq8_small = on > 0 && (on & 3) == 2;  // (1, 3 and a negative value are 1)
+    idx->sq_nom.sq8_masked = on > 0 && (on & 4) != 0;
     return VG_OK;
 }
 
@@ -724,7 +758,8 @@ VG_API int32_t vg_index_enable_sq8_nomination_from_codes(vg_index *idx, int32_t 
 VG_API int32_t vg_index_sq8_nomination_info(const vg_index *idx, int32_t *mode, int64_t *held_bytes, int64_t *rescanned)
 {
     VG_CHECK(idx, VG_ERR_INVALID_ARG, "vg_index_sq8_nomination_info: NULL index");
-    if (mode) *mode = idx->sq_nom.sq8_small ? 3 : idx->sq_nom.mode();  // (3: from the codes, small batches too)
+    // (3: from the codes, small batches too; 6 and 7: 2 and 3 with filtered batches)
+    if (mode) *mode = (idx->sq_nom.sq8_small ? 3 : idx->sq_nom.mode()) | (idx->sq_nom.sq8_masked ? 4 : 0);
     if (held_bytes) *held_bytes = idx->sq_nom.held_bytes(idx->n);
     if (rescanned) *rescanned = idx->sq_nom.mode() ? idx->sq_nom_rescanned : 0;
     return VG_OK;

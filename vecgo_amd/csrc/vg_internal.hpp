@@ -115,6 +115,7 @@ enum Hook {
     kHookBinaryNomAlways,     // VG_BINARY_NOM_ALWAYS  vg_search_binary's matrix-core path: no crossover of (query, row) pairs
     kHookBinaryNoNom,         // VG_BINARY_NO_NOM      vg_search_binary: the scan only
     kHookPqSmallGrid,         // VG_PQ_SMALL_GRID      flat_gemm_pq_small_kernel (k_pq_small.hip) launches at most 2 workgroups: a few hundred thousand rows give every wave the hundreds of tiles, and the several filter windows, it walks over hundreds of millions
+    kHookSq8SmallGrid,        // VG_SQ8_SMALL_GRID     flat_gemm_sq8_small_kernel (k_sq8_small.hip) launches at most 2 workgroups: a few hundred thousand rows give every wave the hundreds of tiles, and the several filter windows, it walks over hundreds of millions
     kHookCount
 };
 bool hook(Hook h);
@@ -494,14 +495,13 @@ struct NomImage {
     bool int4 = false;
     bool int4_small = false;       // with `int4`: enabled with on & 3 == 2 — batches of 5 .. 128 queries take the nomination too
     bool int4_masked = false;      // with `int4`: enabled with on & 4 — batches under a row filter take it too
-    bool sq8_small = false;        // with `scale` (SQ8 from the codes): enabled with on = 2 — batches of 5 .. 128 queries take the nomination too
+    bool sq8_small = false;        // with `scale` (SQ8 from the codes): enabled with on & 3 == 2 — batches of 5 .. 128 queries take the nomination too
+    bool sq8_masked = false;       // with `scale`: enabled with on & 4 — batches under a row filter take it too
     bool pq_small = false;         // PQ from the codes (from_codes, neither of the above): enabled with on & 3 == 2 — likewise
     bool pq_masked = false;        // PQ from the codes: enabled with on & 4 — batches under a row filter take it too
     int64_t body = 0;             // bytes of `rows`
     // 0 off, 1 the image of the decoded rows, 2 from the codes (vg_index_pq_nomination_info reports 3 for 2 with pq_small, + 4 with pq_masked)
     int mode() const { return !rows ? 0 : from_codes ? 2 : 1; }
-    // a from-codes state whose nomination takes row filters (flat_nominate_bf16): the INT4 one and PQ's; SQ8's has no masked small tile
-    bool codes_take_filters() const { return from_codes && (int4 || !scale); }
     uint16_t *row_image() const { return from_codes ? nullptr : rows; }  // the decoded rows, where the mode keeps them
     static int64_t body_bytes(int64_t n, int dim_pad, bool from_codes) { return (from_codes ? int64_t(dim_pad / 8) * 256 * 8 : n * dim_pad) * 2; }
     int64_t held_bytes(int64_t n) const { return rows ? body + n * 4 + 4 : 0; }  // the body, the norms, norm_max

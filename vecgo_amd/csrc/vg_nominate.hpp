@@ -26,9 +26,8 @@ inline int nominate_sel_k(int k) { return k <= kNomPickMaxK ? 8 : k <= 128 ? 16 
 struct GemmGroup;  // vg_flat_gemm.hpp
 // k_flat.hip
 // cnt queries' nomination for their k best on `img`, *nom and all it points to in `scratch` (flat_nominate_bf16_scratch bytes)
-// (img.from_codes, a nomination from the codes: SQ8, img.scale: L2 and Dot, unfiltered; PQ: L2; INT4, img.int4: L2, dim % 32 == 0;
-// these two with a filter too (NomImage::codes_take_filters): `masks` of them — 0 none, 1 one for the batch, cnt one per query —
-// size the scratch)
+// (img.from_codes, a nomination from the codes: SQ8, img.scale: L2 and Dot; PQ: L2; INT4, img.int4: L2, dim % 32 == 0; all three
+// with a filter too: `masks` of them — 0 none, 1 one for the batch, cnt one per query — size the scratch)
 size_t flat_nominate_bf16_scratch(int64_t cnt, int64_t n, const NomImage &img, int k, int64_t masks = 0);
 int32_t flat_nominate_bf16(vg_index *idx, const NomImage &img, bool dot, const float *queries, int64_t cnt, const uint8_t *mask,
                            int64_t mask_stride, int k, char *scratch, hipStream_t st, ProbeNominated *nom);
@@ -63,12 +62,13 @@ int32_t launch_int4_small_gemm(const uint16_t *qimg, int64_t cnt, int dim_pad, c
                                hipStream_t st, const uint8_t *mask = nullptr, int64_t mask_stride = 0);
 // k_sq8_small.hip: the SQ8 append GEMM of one query tile over the code tiles (cnt <= 128; flat_gemm_sq8_small_kernel) — whether a
 // row of dim dimensions fits its LDS at all (dim <= 2528), and the launch (qimg: cnt x dim_pad bfloat16; tiles: the index's code
-// tiles of `groups` groups; counts[q * count_stride]; cus: compute units)
+// tiles of `groups` groups; counts[q * count_stride]; cus: compute units; mask: a device row filter per query / for the batch
+// (mask_stride 0), or null)
 bool sq8_small_tile_fits(int dim);
 template <bool DOT>
 int32_t launch_sq8_small_gemm(const uint16_t *qimg, int64_t cnt, int dim_pad, const uint8_t *tiles, int64_t n, int groups, const float *norms,
                               const float *thr, int thr_stride, int thr_off, int *counts, int count_stride, uint64_t *cand, int cap, int cus,
-                              hipStream_t st);
+                              hipStream_t st, const uint8_t *mask = nullptr, int64_t mask_stride = 0);
 // k_pq_small.hip: the PQ append GEMM of one query tile gathered from the decoded codebook by the codes (cnt <= 128;
 // flat_gemm_pq_small_kernel) — whether a row of m sub-quantizers fits its LDS at all (m <= 318), and the launch (qimg: cnt x dim_pad
 // bfloat16; codes: n rows of m bytes, n m >= 16; cb16: NomImage::rows of a from_codes state; counts[q * count_stride]; cus: compute units;

@@ -81,7 +81,7 @@
 //    barrier the four waves of a workgroup have nothing in common (no barrier, no LDS write), so each wave walks its OWN stream of
 //    (tile, chunk) positions over the tiles whose slice keeps a row; a wave without one leaves behind that barrier.  advance()
 //    runs two chunks ahead of the matrix instructions and must know the next such tile without waiting for a load, so the filter
-//    is held as a wave-uniform BITMAP of a WINDOW of the wave's tiles (PqsFilterWindows): one vector load, lane l the 8 bytes of
+//    is held as a wave-uniform BITMAP of a WINDOW of the wave's tiles (SliceFilterWindows, vg_slice_windows.hpp): one vector load, lane l the 8 bytes of
 //    the wave's slice in tile (64 w + l) of the workgroup's sequence (at any alignment; a slice that sticks out of the filter —
 //    the last tile's — reads the filter's last 8 bytes and shifts; the launch takes this variant from n = 64 up), a ballot of
 //    "not zero", and s_ff1_i32_b64 from the current position steps to the next tile: scalar work between two chunks.
@@ -126,6 +126,7 @@
 
 #include "vg_device.hpp"
 #include "vg_flat_gemm.hpp"
+#include "vg_slice_windows.hpp"
 
 namespace vg {
 
@@ -150,69 +151,7 @@ __device__ __forceinline__ uint4 pq_small_shr_bytes(uint4 v, uint32_t s)
     return make_uint4(a0, a1, a2, a3);
 }
 
-// The batch filter as one wave of flat_gemm_pq_small_kernel<RB, true, true> reads it (see the header): the wave's tiles by ordinal
-// i (tile first + i G, i < mine), the wave's 8 filter bytes of 64 of them a window, one tile a lane, kept as a wave-uniform bitmap
-// of the slices that keep a row.  Only that variant has one; the others hold a PqsNoFilter.
-constexpr int kPqsWindow = 64;
-struct PqsNoFilter {};
-struct PqsFilterWindows {
-    const uint8_t *mask;
-    int64_t mask_bytes;  // (n + 7) / 8 >= 8: the launch's condition for this variant
-    int first, G, wave, lane, mine;
-    uint64_t live;  // bit l: ordinal kPqsWindow win_at + l keeps a row (wave-uniform; clear from `mine` on)
-    int win_at;
-    // lane l: where the 8 filter bytes of this wave's rows in the tile of ordinal kPqsWindow w + l start
-    __device__ __forceinline__ int64_t slice_at(int w) const
-    {
-        return (first + (static_cast<int64_t>(kPqsWindow) * w + lane) * G) * (kPqsBN / 8) + wave * 8;
-    }
-    // ... the load of them: unconditional, 8 bytes at any alignment, and never outside the filter — a slice that ends past it (the
-    // last tile's, or an ordinal that is no tile) reads the filter's last 8 bytes
-    __device__ __forceinline__ uint64_t load_window(int w) const
-    {
-        const int64_t at = slice_at(w), last = mask_bytes - 8;
-        uint64_t v;
-        __builtin_memcpy(&v, mask + (at > last ? last : at), 8);
-        return v;
-    }
-    // ... and the slice's 64 bits from what was loaded: shifted down where the address was clamped, zeros coming in; zeros for an
-    // ordinal from `mine` on
-    __device__ __forceinline__ uint64_t window_bits(int w, uint64_t v) const
-    {
-        const int64_t at = slice_at(w), last = mask_bytes - 8, over = at > last ? at - last : 0;
-        v = over >= 8 ? 0 : v >> (8 * over);
-        return static_cast<int64_t>(kPqsWindow) * w + lane < mine ? v : 0;
-    }
-    // the next window becomes the current one: loaded and waited for here, the one place where the stream drains for the filter
-    __device__ __forceinline__ void enter()
-    {
-        win_at++;
-        live = __ballot(window_bits(win_at, load_window(win_at)) != 0);
-    }
-    // the first ordinal >= i (in window win_at or behind it; i <= the window's end + 1) whose slice keeps a row; `mine`: none
-    __device__ __forceinline__ int next_live(int i)
-    {
-        if (i >= mine) return mine;
-        if (i / kPqsWindow == win_at) {
-            const uint64_t m = live & (~uint64_t(0) << (i % kPqsWindow));
-            if (m != 0) return win_at * kPqsWindow + __builtin_ctzll(m);
-        }
-        do {  // the windows behind it, until one keeps a row
-            if ((win_at + 1) * kPqsWindow >= mine) return mine;
-            enter();
-        } while (live == 0);
-        return win_at * kPqsWindow + __builtin_ctzll(live);
-    }
-    // window 0 loaded; the wave's first live ordinal
-    __device__ __forceinline__ int init(const uint8_t *mask_, int64_t n, int ntiles, int G_, int wave_, int lane_)
-    {
-        mask = mask_, mask_bytes = (n + 7) >> 3, first = static_cast<int>(blockIdx.x), G = G_, wave = wave_, lane = lane_;
-        mine = (ntiles - first + G - 1) / G;
-        win_at = -1;
-        enter();
-        return next_live(0);
-    }
-};
+static_assert(kPqsBN == kSliceBN, "the filter windows' row tile is this tile's");
 
 // queries: nq x dim_pad bfloat16 (gemm_operands' image, the tail from dim on zeros), nq <= 32 RB, dim_pad >= 16 steps; codes: n rows
 // of m bytes, n m >= 16; cb16: the decoded codebook, at least 2 steps slices of 256 entries; counts: counts[q * count_stride];
@@ -286,7 +225,7 @@ __global__ __launch_bounds__(kPqsThreads) void flat_gemm_pq_small_kernel(
     };
     // SKIP: the wave's tiles by ordinal (tile blockIdx.x + ordinal G) and the filter's windows over them; otherwise an empty struct.
     // ord1: the ordinal of the tile the stream is on — fw.mine: the stream has ended
-    std::conditional_t<SKIP, PqsFilterWindows, PqsNoFilter> fw;
+    std::conditional_t<SKIP, SliceFilterWindows, SliceNoFilter> fw;
     int ord1 = 0;
     if constexpr (SKIP) {
         ord1 = fw.init(mask, n, ntiles, G, wave, lane);

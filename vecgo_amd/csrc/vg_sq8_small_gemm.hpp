@@ -2,7 +2,7 @@
 // (flat_gemm_sq8_small_kernel): bf16 queries (scaled by the quantizer's inverse scales) against the index's SQ8 code TILES, scoring
 // in flat_gemm_sq8_big_kernel's space,
 //     s' = |x^|^2 - 2 (q o inv).c'   (Dot: -(q o inv).c'),   c' = code - 128 exact in bfloat16, the image of q o inv the only rounded operand.
-// Kept in a header so that tools/ubench can time the same code; launched by k_sq8_small.hip.
+// Kept in a header so that tools/ubench can time the same code; launched by k_sq8_small.hip.  Row filters: the last point below.
 //
 // The counterpart of vg_int4_small_gemm.hpp — a single query tile, so a row is consumed by exactly one wave and goes from global
 // memory straight into the registers that feed v_mfma_f32_32x32x16_bf16, LDS holding the queries' image alone — but not a copy: the
@@ -51,6 +51,32 @@
 //  * the epilogue is gemm_epilogue's append (vg_flat_gemm.hpp) as in the INT4 small tile: score = fma(-2, acc, |x^|^2) (Dot: -acc),
 //    compared with the query's threshold (in LDS; -Inf for the padded queries of the last block: they never append), a returning
 //    atomic on the query's counter parked until the tile's end, the key make_key(score, row) — the form Sq8CodesRow's verify pair reads.
+//  * row filters (vg_index_enable_sq8_nomination_from_codes' on & 4) are variants of their own, MASKED and BATCH template parameters:
+//    the unfiltered instantiations keep their vector instructions, waits and registers (diffed against the ISA of the kernel
+//    without the parameters: one s_add_i32 at the tile loop's end became an s_mov_b32 and the scalar registers are numbered
+//    differently; VGPRs, AGPRs and occupancy as they were, profiles/kernel_resources.txt).
+//    Per-query filters (MASKED, not BATCH) — the K loop is untouched (vmcnt(18) / (19) as unfiltered): a lane reads its query's bit
+//    only for a score that has passed the threshold, inside the branch that drains for the append's atomic anyway.  A launch of a
+//    host-side split gets the filter of ITS first query.
+//    BATCH — one filter for all queries.  A wave's 64 rows of a row tile are exactly one code tile, groups x 1024 contiguous
+//    bytes, and 8 bytes of the filter; a code tile whose 8 bytes are zero is never loaded, converted or multiplied — HBM bytes
+//    not read, on the one small tile that is HBM-bound.  After the image's barrier the four waves of a workgroup have nothing in
+//    common, so each wave walks its OWN stream of live code tiles (SliceFilterWindows, vg_slice_windows.hpp: a wave-uniform
+//    bitmap of a window of 64 of the wave's tiles, one 8-byte load a lane at any alignment; a slice that sticks out of the
+//    filter — the last row tile's — reads the filter's last 8 bytes and shifts, never past (n + 7) / 8; the launch takes this
+//    variant from n = 64 up); a wave without one leaves behind that barrier.  The ring keeps flying across skipped tiles: the
+//    last chunk's slots load the first chunk of the next LIVE tile, unconditionally as before, and that tile is found at the
+//    tile's START, ahead of its chunks — scalar work (s_ff1 on the bitmap) while the window lasts.  The next window is loaded
+//    when the current one is spent and waited for there (why not a window ahead: the note in vg_pq_small_gemm.hpp), a drain once
+//    in 64 of the wave's tiles that lies between two tiles, where the chunk's-end copy has drained the ring anyway.  Read from
+//    the ISA: the window's load and its vmcnt(0) stand in blocks ahead of the K loop only; the K loop's waits are vmcnt(20) per
+//    step (Dot: 18) — the 16 pieces, the tile's two norms and the two filter bytes with a lane's rows' bits, loaded beside the
+//    norms — and vmcnt(21) (19) between steps, i.e. the unfiltered waits two loads deeper; vmcnt(0) at a chunk's end and at the
+//    appends as unfiltered.  Past its end the stream repeats the first chunk of the tile it is on — a walked one, in range.  A
+//    walked tile's rows still test their own bit beside `row < n`; bits at or past n can make the last tile walked, never a row
+//    appended.  Registers (profiles/kernel_resources.txt): at most 6 VGPRs above the unfiltered ones, no scratch; the Dot variants of
+//    two query blocks take 194 / 196 VGPRs beside 64 AGPRs and lose the second workgroup a CU that 192 allowed.
+//    Measured: the comment above kSq8NomCodesMaskedMinPairs (k_sq8_scan.hip).
 // The error bound (Sq8CodesRow::eps, k_sq8_scan.hip, "GEMM sum"): that term allows a start at s (|s| <= 1.501 B for L2, 2.002 B for
 // Dot), dim products (S = sum |products| <= 0.51 B) and the key's fma, (dim + 16) roundings of at most u (|s| + S) each whatever
 // their order: 4.03 (dim + 16) u B for L2 (the score is twice the sum), 2.52 (dim + 16) u B for Dot.  This tile starts at ZERO: its
@@ -73,13 +99,16 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <type_traits>
 
 #include "vg_device.hpp"
 #include "vg_flat_gemm.hpp"
+#include "vg_slice_windows.hpp"
 
 namespace vg {
 
 constexpr int kS8sThreads = 256, kS8sBN = 256, kS8sDepth = 8;
+static_assert(kS8sBN == kSliceBN, "the filter windows' row tile is this tile's");
 constexpr size_t kS8sLdsMax = 160 * 1024;  // a CU's LDS (gfx950)
 // the 32-dimension steps of a row of `groups` 16-dimension groups
 __host__ __device__ constexpr int sq8_small_steps(int groups) { return (groups + 1) >> 1; }
@@ -101,14 +130,17 @@ __device__ __forceinline__ uint4 sq8_half_bf16(uint32_t lo, uint32_t hi)
 
 // queries: nq x dim_pad bfloat16 (gemm_operands' image scaled by the inverse scales, the tail from dim on zeros), nq <= 32 RB,
 // dim_pad >= 32 steps; tiles: the index's code tiles, n_tiles = ceil(n / 64) of `groups` groups; counts: counts[q * count_stride];
-// cand: cap keys a query
-template <bool DOT, int RB>
+// cand: cap keys a query; MASKED: mask, a bit per row, (n + 7) / 8 bytes at any alignment — BATCH: one for all queries (n >= 64: 8
+// bytes of it exist), otherwise query q's at mask + q * mask_stride (a stride of 0: one for all, without the skip)
+template <bool DOT, int RB, bool MASKED = false, bool BATCH = false>
 __global__ __launch_bounds__(kS8sThreads) void flat_gemm_sq8_small_kernel(
     const uint16_t *__restrict__ queries, int nq, int dim_pad, const uint8_t *__restrict__ tiles, int64_t n, int groups,
     const float *__restrict__ norms, const float *__restrict__ thr, int thr_stride, int thr_off, int *__restrict__ counts, int count_stride,
-    uint64_t *__restrict__ cand, int cap)
+    uint64_t *__restrict__ cand, int cap, const uint8_t *__restrict__ mask, int64_t mask_stride)
 {
     static_assert(RB >= 1 && RB <= 4, "one to four blocks of 32 queries");
+    static_assert(MASKED || !BATCH, "a batch filter is a filter");
+    constexpr bool SKIP = MASKED && BATCH;
     constexpr int QB = RB * 32, D = kS8sDepth;
     extern __shared__ float gemm_lds[];
     const int ntiles = static_cast<int>((n + kS8sBN - 1) / kS8sBN), G = static_cast<int>(gridDim.x);
@@ -144,21 +176,54 @@ __global__ __launch_bounds__(kS8sThreads) void flat_gemm_sq8_small_kernel(
         for (int j = 0; j < 2; j++) dst[j] = *reinterpret_cast<const uint4 *>(p + off + j * 512);
     };
 
+    // SKIP: the wave's tiles by ordinal (tile blockIdx.x + ordinal G) and the filter's windows over them; otherwise an empty struct.
+    // ord: the ordinal of the tile that is computed — fw.mine: the wave's stream has ended
+    std::conditional_t<SKIP, SliceFilterWindows, SliceNoFilter> fw;
+    int ord = 0, t = static_cast<int>(blockIdx.x);
+    if constexpr (SKIP) {
+        ord = fw.init(mask, n, ntiles, G, wave, lane);
+        if (ord >= fw.mine) return;  // (the wave alone: there is no barrier behind the image's)
+        t += ord * G;
+    }
+
     f32x16 acc[RB][2];
     uint4 ring[D][2];
 #pragma unroll
     for (int p = 0; p < D; p++) {
-        load_step(static_cast<int>(blockIdx.x), p, ring[p]);
+        load_step(t, p, ring[p]);
         __builtin_amdgcn_sched_barrier(0);  // (in the ring's order: the K loop waits for its slots by count)
     }
-    for (int t = static_cast<int>(blockIdx.x); t < ntiles; t += G) {
+    auto more = [&]() {
+        if constexpr (SKIP)
+            return ord < fw.mine;
+        else
+            return t < ntiles;
+    };
+    while (more()) {
         const int64_t n0 = static_cast<int64_t>(t) * kS8sBN + wave * 64;
+        // SKIP: the wave's next tile whose slice keeps a row, found BEFORE the tile's chunks (scalar work inside a window; the one
+        // load and wait of a window's end lie here, ahead of the K loop) — the tile whose first chunk the last chunk's slots load.
+        // Past the stream's end: this tile — a walked one, in range — again.
+        int ord_next = 0, t_next = t + G;
+        if constexpr (SKIP) {
+            ord_next = fw.next_live(ord + 1);
+            t_next = ord_next < fw.mine ? static_cast<int>(blockIdx.x) + ord_next * G : t;
+        }
         float xn[2] = {0.0f, 0.0f};
         if (!DOT) {
 #pragma unroll
             for (int j = 0; j < 2; j++) {
                 const int64_t nn = n0 + j * 32 + r;
                 xn[j] = norms[nn < n ? nn : n - 1];
+            }
+        }
+        // SKIP: the filter's bytes with the rows' bits, beside the norms and as old as they are when the epilogue reads them
+        uint32_t fbyte[2] = {0xFFu, 0xFFu};
+        if constexpr (SKIP) {
+#pragma unroll
+            for (int j = 0; j < 2; j++) {
+                const int64_t nn = n0 + j * 32 + r;
+                fbyte[j] = mask[(nn < n ? nn : n - 1) >> 3];
             }
         }
 #pragma unroll
@@ -171,7 +236,7 @@ __global__ __launch_bounds__(kS8sThreads) void flat_gemm_sq8_small_kernel(
             // the chunk whose loads take the slots this one frees — of the next tile behind the last one; past the stream's end: the
             // last tile's first again, never multiplied
             const bool last = c + 1 == nchunks;
-            const int tn = last ? (t + G < ntiles ? t + G : ntiles - 1) : t, cn = last ? 0 : c + 1;
+            const int tn = !last ? t : SKIP ? t_next : (t + G < ntiles ? t + G : ntiles - 1), cn = last ? 0 : c + 1;
 #pragma unroll
             for (int p = 0; p < D; p++) {
                 const int i = c * D + p;
@@ -224,7 +289,7 @@ __global__ __launch_bounds__(kS8sThreads) void flat_gemm_sq8_small_kernel(
 #pragma unroll
         for (int j = 0; j < 2; j++) {
             const int64_t nn = n0 + j * 32 + r;
-            const bool row_ok = nn < n;
+            const bool row_ok = nn < n && (!SKIP || ((fbyte[j] >> (nn & 7)) & 1u));
 #pragma unroll
             for (int b = 0; b < RB; b++) {
                 // a block's 16 scores and compares with no branch between them; only a block in which something passed looks again
@@ -247,6 +312,8 @@ __global__ __launch_bounds__(kS8sThreads) void flat_gemm_sq8_small_kernel(
                         const int q = b * 32 + (e & 3) + 8 * (e >> 2) + hv;
                         asm volatile("" : "+v"(sc[e]));  // (compared again here: 16 lane masks kept per block spill the scalar registers)
                         if (!(sc[e] < tq[e]) || q >= nq) continue;
+                        if constexpr (MASKED && !BATCH)  // (only now: for the few scores that passed)
+                            if (!mask_bit(mask + static_cast<int64_t>(q) * mask_stride, nn)) continue;
                         if (parked) store_parked();
                         park_pos = atomicAdd(&counts[static_cast<int64_t>(q) * count_stride], 1);
                         park_q = q;
@@ -257,6 +324,7 @@ __global__ __launch_bounds__(kS8sThreads) void flat_gemm_sq8_small_kernel(
             }
         }
         if (parked) store_parked();
+        t = t_next, ord = ord_next;
     }
 }
 
